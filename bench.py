@@ -5,16 +5,20 @@ A "step" is one pass of the whole hot path over one batch of synthetic 30 s clip
 resident in HBM: log-mel front-end -> encoder -> greedy decode (4 SOT steps + up to 444 tokens; with
 synthetic weights eot practically never wins, so every clip runs the full 448-step context) -> ids.
 
-    python bench.py                      # N=1: BASELINE configs[1] (Whisper-small, batch 1) as the headline value,
-                                         #      plus a "batch64" object = configs[2] timed in the same run (and "batch256": the same at 256 clips)
+    python bench.py                      # N=1: BASELINE configs[1] (Whisper-small, batch 1) as the headline value, nothing else
+    python bench.py --full               # the same headline, plus every other leg: rooflines, host PCM, forced lengths, demo.wav,
+                                         #      "batch64" = configs[2] timed in the same run (and "batch256": the same at 256 clips),
+                                         #      batch2..8, realistic lengths, turbo fp16, config0, the CPU baseline
     python bench.py --batch 64           # configs[2] as the headline value
     python bench.py --gpus 8             # configs[4]: spawns 8 ranks (one per GPU, RCCL), 64 clips per GPU
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8     # the same, launched by the driver
+    python bench.py --dump-outputs DIR   # also writes the ids of the last timed step to DIR/ids.npy (+ DIR/ids_len.npy)
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts `python -m torch.distributed.run` as a CHILD
 process before anything in this process has touched a GPU, relays its single JSON line and exits with its code.
 
-Prints ONE JSON line (rank 0). `roofline` is for the dominant kernel of the timed region, `cpu_baseline` is the CPU
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times `--steps` steps and prints the line; everything
+else is behind `--full`. There `roofline` is for the dominant kernel of the timed region, `cpu_baseline` is the CPU
 oracle ("port") timed on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
 """
 import argparse
@@ -47,6 +51,12 @@ def parse_args(argv=None):
     ap.add_argument("--max-new", type=int, default=0, help="0 = until eot or context (444 ids)")
     ap.add_argument("--dtype", default="", choices=["", "bf16", "fp16"],
                     help="16-bit storage / MFMA operand type; default: bf16, fp16 for --model turbo (BASELINE configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines, the other BASELINE configs, realistic lengths, the CPU baseline and, at "
+                         "N > 1, the single-GPU point (the --no-* options below leave legs of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (token ids, all clips, float64, padded with -1) to DIR/ids.npy "
+                         "and the row lengths to DIR/ids_len.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-batch64", action="store_true", help="N=1, batch 1 only: skip the batch-64 leg")
     ap.add_argument("--no-batch256", action="store_true", help="N=1, batch 1 only: skip the batch-256 leg (not a BASELINE config: what one GPU's HBM allows)")
@@ -55,8 +65,8 @@ def parse_args(argv=None):
                     help="N=1, batch 1 only: skip the realistic-length legs (batch64_len100: 64 clips with budgets of 60-150 ids; stream64: 384 clips through 64 refilled slots)")
     ap.add_argument("--no-config0", action="store_true", help="N=1, batch 1 only: skip the tiny / demo.wav CPU-vs-GPU leg (configs[0])")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed region and its roofline: no host-PCM / forced-length / demo.wav / batch-64 / turbo / "
-                         "config0 / CPU legs (profiling runs: every launch in the trace belongs to the headline workload)")
+                    help="only the timed region, even with --full: no roofline / host-PCM / forced-length / demo.wav / batch-64 / "
+                         "turbo / config0 / CPU legs (profiling runs: every launch in the trace belongs to the headline workload)")
     ap.add_argument("--model-dir", default=os.environ.get("AXW_BENCH_MODEL_DIR", "/tmp/axw_bench_models"))
     return ap.parse_args(argv)
 
@@ -617,6 +627,7 @@ def run_rank(args) -> int:
 
         dt, ids = timed_steps(one_step, args.steps, args.warmup, sync, barrier)
         stage, dec_steps, n_tok = {}, 0, float(np.mean([len(r) for r in ids]))
+        last_rows = ids
     else:
         import whisper_axera_amd as wa
 
@@ -655,6 +666,10 @@ def run_rank(args) -> int:
             rc = 3
         n_tok = float(np.mean([len(r) for r in ids]))
         dec_steps = stage["steps"] / args.steps
+        last_rows = gathered["ids"] if use_dist else ids
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_rows)
 
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
@@ -680,7 +695,7 @@ def run_rank(args) -> int:
         """N > 1: the same per-GPU workload on ONE GPU in the same run — rank 0 alone times a few more steps (no collective
         inside) while the other ranks wait at the second barrier — the reference point of the weak-scaling ratio
         value / (N * this): N=1 runs of this script default to batch 1, so the ratio of two driver lines says nothing."""
-        if not (use_dist and world > 1):
+        if not (use_dist and world > 1) or args.no_extras:
             return
         barrier()
         if rank == 0:
@@ -811,7 +826,7 @@ def run_rank(args) -> int:
         if rank == 0 and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, dims, mdir, clips[0], ids[0], dec_steps, dtype)
 
-    if rank == 0 and not rehearsal:
+    if rank == 0 and not rehearsal and not args.no_extras:
         out["config"]["other_configs"] = other_configs_summary(out)
 
     if use_dist:
@@ -826,8 +841,27 @@ def run_rank(args) -> int:
     return rc
 
 
+def dump_outputs(out_dir, rows):
+    """What the timed path returned in its last step: the greedy ids of every clip (all ranks' rows at N > 1, in global
+    order) as float64 [clips, longest row] padded with -1 (every token id is exact), and the row lengths as float64 [clips]."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = max((len(r) for r in rows), default=0)
+    ids = np.full((len(rows), n), -1.0, dtype=np.float64)
+    for i, r in enumerate(rows):
+        ids[i, : len(r)] = r
+    np.save(os.path.join(out_dir, "ids.npy"), ids)
+    np.save(os.path.join(out_dir, "ids_len.npy"), np.array([len(r) for r in rows], dtype=np.float64))
+
+
 def main():
     args = parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        return 2
+    if not args.full:
+        args.no_extras = True  # a plain run: set-up, warm-up, the timed steps, the outputs, the line
     if args.no_extras:
         args.no_batch64 = args.no_batch256 = args.no_turbo = args.no_config0 = args.no_cpu_baseline = args.no_realistic = True
     if args.gpus < 1:

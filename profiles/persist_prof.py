@@ -1,7 +1,7 @@
 """Summarise AX_WHISPER_PERSIST_PROF output: per-phase time of the persistent batch-1 decode launch.
 
-    AX_WHISPER_PERSIST_PROF=gpurun_out/pp.txt python bench.py --steps 1 --warmup 0 --no-cpu-baseline
-    python profiles/persist_prof.py gpurun_out/pp.txt
+    AX_WHISPER_PERSIST_PROF=/tmp/pp.txt python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+    python profiles/persist_prof.py /tmp/pp.txt
 """
 import sys
 

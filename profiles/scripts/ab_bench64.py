@@ -4,7 +4,7 @@ import subprocess
 import sys
 
 n = sys.argv[1] if len(sys.argv) > 1 else "64"
-out = subprocess.run([sys.executable, "bench.py", "--batch", n, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-batch64"] + sys.argv[2:],
+out = subprocess.run([sys.executable, "bench.py", "--batch", n, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-batch64"] + sys.argv[2:],
                      capture_output=True, text=True).stdout.strip().splitlines()[-1]
 j = json.loads(out)
 r = j["roofline"]

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 cp profiles/r03_pmc_traffic.json $OUT/pmc_before.json 2>/dev/null
 if [ "$1" != "b64" ]; then
 # the driver's line: configs[1] as value + batch64 (configs[2]) + turbo_fp16_b16 (configs[3]) + config0 + cpu_baseline
-python bench.py > $OUT/bench_b1.json 2> $OUT/bench_b1.err || exit 1
+python bench.py --full > $OUT/bench_b1.json 2> $OUT/bench_b1.err || exit 1
 # kernel stats of the headline workload ONLY (--no-extras: every decode_persistent_kernel launch in the trace is one
 # 448-step clip of the timed workload, so AverageNs IS the launch the roofline is quoted on)
 cd /tmp
@@ -34,9 +34,9 @@ python3 profiles/pmc_summarize.py $OUT/pmc small_b64 r03_pmc_traffic.json > $OUT
 find $OUT/stats_b64 -name "*kernel_stats.csv" -exec cp {} $OUT/b64_kernel_stats.csv \;
 find $OUT/stats_b64_1br -name "*kernel_stats.csv" -exec cp {} $OUT/b64_1branch_kernel_stats.csv \;
 rm -rf $OUT/pmc $OUT/stats_b64 $OUT/stats_b64_1br
-AX_WHISPER_DECODE_BRANCHES=1 python bench.py --batch 64 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_b64_1branch.json 2> $OUT/bench_b64_1br.err || exit 1
-python bench.py --batch 64 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_b64.json 2> $OUT/bench_b64.err || exit 1
-python bench.py --model turbo --batch 16 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b16.json 2> $OUT/bench_turbo_b16.err || exit 1
-python bench.py --model turbo --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b1.json 2> $OUT/bench_turbo_b1.err || exit 1
+AX_WHISPER_DECODE_BRANCHES=1 python bench.py --full --batch 64 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_b64_1branch.json 2> $OUT/bench_b64_1br.err || exit 1
+python bench.py --full --batch 64 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_b64.json 2> $OUT/bench_b64.err || exit 1
+python bench.py --full --model turbo --batch 16 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b16.json 2> $OUT/bench_turbo_b16.err || exit 1
+python bench.py --full --model turbo --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b1.json 2> $OUT/bench_turbo_b1.err || exit 1
 cp profiles/r03_pmc_traffic.json $OUT/r03_pmc_traffic_b64.json
 ls -la $OUT

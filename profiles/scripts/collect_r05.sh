@@ -23,7 +23,7 @@ stats() {  # stats <name> <env assignments or ''> <bench args...>
 }
 case "$1" in
 b1)
-  python bench.py > $OUT/bench_b1.json 2> $OUT/bench_b1.err || exit 1
+  python bench.py --full > $OUT/bench_b1.json 2> $OUT/bench_b1.err || exit 1
   stats b1 "AXW_NOP=1" --steps 4 --warmup 2 --no-extras || exit 1
   pmc small_b1 1 || exit 1
   # in-kernel timeline of the persistent launch (per-phase sums + the absolute timeline of one mid-utterance layer)
@@ -54,15 +54,15 @@ b64)
   # the attention launches on one time axis, two branches in flight (production) and one branch
   AX_WHISPER_ATTN_STAMP=$OUT/stamps_b64.csv python profiles/scripts/attn_stamp.py 64 small > $OUT/attn_stamps_b64.txt 2> $OUT/attn_stamps_b64.err || exit 1
   AX_WHISPER_DECODE_BRANCHES=1 AX_WHISPER_ATTN_STAMP=$OUT/stamps_b64_1br.csv python profiles/scripts/attn_stamp.py 64 small > $OUT/attn_stamps_b64_1branch.txt 2> $OUT/attn_stamps_b64_1br.err || exit 1
-  python bench.py --batch 64 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_b64.json 2> $OUT/bench_b64.err || exit 1
+  python bench.py --full --batch 64 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_b64.json 2> $OUT/bench_b64.err || exit 1
   ;;
 extra)
   pmc turbo_b16 16 turbo fp16 || exit 1
   pmc small_b256 256 small || exit 1
   AX_WHISPER_ATTN_STAMP=$OUT/stamps_b256.csv python profiles/scripts/attn_stamp.py 256 small > $OUT/attn_stamps_b256.txt 2> $OUT/attn_stamps_b256.err || exit 1
   AX_WHISPER_ATTN_STAMP=$OUT/stamps_turbo16.csv python profiles/scripts/attn_stamp.py 16 turbo fp16 > $OUT/attn_stamps_turbo_b16.txt 2> $OUT/attn_stamps_turbo16.err || exit 1
-  python bench.py --model turbo --batch 16 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b16.json 2> $OUT/bench_turbo_b16.err || exit 1
-  python bench.py --model turbo --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b1.json 2> $OUT/bench_turbo_b1.err || exit 1
+  python bench.py --full --model turbo --batch 16 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b16.json 2> $OUT/bench_turbo_b16.err || exit 1
+  python bench.py --full --model turbo --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_turbo_fp16_b1.json 2> $OUT/bench_turbo_b1.err || exit 1
   ;;
 *) echo "usage: collect_r05.sh b1|b2|b3|b64|extra"; exit 2;;
 esac

@@ -71,7 +71,7 @@ def test_bench_gpus_8_rehearsal_is_configs4():
     """BASELINE configs[4] — 8 ranks x 64 clips = 512 — as far as it can be run without eight GPUs: the rank spawn, the
     default of 64 clips per GPU, the gather of all 512 id rows, the single-GPU reference leg behind the barrier and the ONE
     JSON line (gloo, stand-in engine)."""
-    rc, lines, err = _run_bench(["--gpus", "8", "--steps", "2", "--warmup", "1"], {"OMP_NUM_THREADS": "1"})
+    rc, lines, err = _run_bench(["--gpus", "8", "--steps", "2", "--warmup", "1", "--full"], {"OMP_NUM_THREADS": "1"})
     assert rc == 0, err
     assert len(lines) == 1
     j = lines[0]
@@ -92,3 +92,33 @@ def test_bench_exits_nonzero_when_a_rank_dies_mid_step():
     assert rc != 0 and not lines, (rc, lines)
     assert "injected failure" in err
     assert time.time() - t0 < 200
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """Without --full a run times its steps and prints the line: no single-GPU point, no other configs."""
+    rc, lines, err = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2"], {})
+    assert rc == 0, err
+    assert len(lines) == 1
+    j = lines[0]
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert "single_gpu_same_batch" not in j and "other_configs" not in j["config"]
+
+
+def test_bench_dump_outputs_are_the_gathered_ids(tmp_path):
+    """--dump-outputs DIR: the last timed step's ids of every clip (both ranks' rows) as float64, padded with -1, and
+    the same arrays from a second run with the same arguments."""
+    import numpy as np
+
+    got = []
+    for run in ("a", "b"):
+        rc, lines, err = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "0", "--batch", "3",
+                                     "--dump-outputs", str(tmp_path / run)], {})
+        assert rc == 0, err
+        assert len(lines) == 1
+        ids, n = np.load(tmp_path / run / "ids.npy"), np.load(tmp_path / run / "ids_len.npy")
+        assert ids.dtype == np.float64 and n.dtype == np.float64
+        assert ids.shape == (6, int(n.max())) and n.shape == (6,)
+        for row, k in zip(ids, n.astype(int)):
+            assert (row[:k] >= 0).all() and (row[k:] == -1).all()
+        got.append((ids, n))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
