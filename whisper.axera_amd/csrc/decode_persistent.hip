@@ -110,123 +110,25 @@ size_t qfold_floats(int d_model, int n_layer) { return (size_t)n_layer * (size_t
 // QF: the query fold above (d_model <= 768: the fp32 rows of M cost 2 * CD more registers per lane)
 template <int LD, int CD, int LF, int CF, bool PROF, bool QF>
 __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) {
-  constexpr int D = 8 * LD * CD, F = 8 * LF * CF, H = D / 64;
-  static_assert(F == 4 * D, "mlp width");
-  // a poller lane owns PAIRS of adjacent vector elements: pair tid + j*PL (j < GPD) = elements 2*pair, 2*pair + 1
-  constexpr int GPD = (D / 2 + PL - 1) / PL, GD = 2 * GPD, NPART = H * kCrossSplit * kPS;
-  constexpr int NPP = NPART / 2, NPP1 = (NPP + 1) / 2, GP1 = (NPP1 + PL - 1) / PL, GP2 = (NPP - NPP1 + CT - 1) / CT;  // partial-record pairs, split between the roles
-  static_assert(NPART % 2 == 0 && kPS % 2 == 0 && kRec % 2 == 0 && D % 2 == 0, "pair polls need even layouts");
-  constexpr int NU = kCrossSplit * H;  // cross-attention units per layer
-  // granule buffers (u64 units)
-  constexpr int O_QKV = 0, O_ATT = 3 * D, O_Y1 = 4 * D, O_CQ = 5 * D, O_PART = 6 * D, O_Y2 = 10 * D, O_HID = 11 * D, O_Y3 = 15 * D,
-                O_AMAX = 16 * D, O_STAT = 16 * D + 512;  // statistics of producer p: granules O_STAT + 16 p, + 1: a line of its own (packed, 8
-                                                        // producers' partial-line stores per line: units gather 0.4 us later, 108.7 -> 111.1 ms)
+  AXW_PERSIST_SHAPES
   constexpr int XG = D, X0R = 2 * D, A0S = 3 * D;  // QF: act[XG..) = g_cross . x0, act[X0R..) = x0 (written with the QKV LayerNorm, read by
                                                   // the row producers), act[A0S + slot] = A0 of the slot's row (free until the partial records)
-  static_assert(NPART <= 3 * D + D / 8 && NU * kRec <= 4 * D, "partial buffer");
-  static_assert(kCrossSplit * NCW == 24, "cross-attention key blocks");
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  h16* sK = reinterpret_cast<h16*>(smem);                  // [8 blk][8][64 keys][8]  (blocked, lane = key)
-  h16* sV = sK + NCW * 4096;                                // cross tiles: [512 keys][64]; self-attention cache: per block [8 (key/8)][64 dims][8 keys]
-  float* act = reinterpret_cast<float*>(smem + kKvBytes);    // [F + D/8] input vector of the current rows phase
-  float* wpart = act + F + D / 8;                            // [NCW][kPS] per-wave attention partials
-  float* red = wpart + NCW * kPS;                            // [2*NPW] LayerNorm partial sums, [2*NPW] = the stage's mean (QF: the statistics' shift)
-  unsigned* qs = reinterpret_cast<unsigned*>(red + 2 * NPW + 4);  // [64] query of the attention phase as packed h16 pairs: [32] hi, [32] lo
-  float* am_v = reinterpret_cast<float*>(qs) + 64;           // [16] argmax scratch
-  int* am_i = reinterpret_cast<int*>(am_v + 16);             // [16]
-  int* ctl = am_i + 16;                                      // [16]: 0 give-up flag, 1 argmax of the step
-  float* pk = reinterpret_cast<float*>(ctl + 16);            // [64] this workgroup's rows of the phase, assembled for the one-instruction publish
-  float* pscr = pk + 64;                                     // [NCW][64] probability transpose scratch
-  long long* prof_acc = reinterpret_cast<long long*>(pscr + NCW * 64);  // [64] per-phase time sums + one layer's absolute timeline (profiling runs only)
-
-  // tid is re-derived behind an opaque asm at the top of every layer: without it the compiler hoists every
-  // per-thread address of every phase out of the step loop and keeps >100 registers of loop invariants alive
-  int tid = threadIdx.x;
-  const bool poller = tid < PL;  // wave-uniform
-  const int P = gridDim.x, wg = blockIdx.x;
-  const int L = p.n_layer;
-  u64* const G = p.gran;
+  AXW_PERSIST_LDS(4)  // red[2*NPW]: the stage's mean (QF: the statistics' shift), red[2*NPW + 1]: the shift the sums are relative to
+  AXW_PERSIST_IDS
   const __amdgpu_buffer_rsrc_t GR = __builtin_amdgcn_make_buffer_rsrc((void*)p.gran, 0, p.gran_bytes, 0x27000);
-
-  // self-attention ownership: unit (l, h) -> workgroup P-1-(l*H+h). The other NS workgroups take the cross-attention
-  // units: unit u of layer l -> workgroup (l*NU + u) % NS.
-  const int sa_unit = P - 1 - wg;
-  const int sa_layer = sa_unit < L * H ? sa_unit / H : -1, sa_head = sa_unit % H;
-  const int NS = P - L * H;
-  // producers of the d-row phases (one pass of CT/LD resp. CT/LF rows each, workgroups 0..): only they consume the
-  // attention outputs / cross-attention partials / mlp hidden vector; every other workgroup skips those three phases
-  // altogether (no polls, no barriers): a hand-off is the faster the fewer workgroups poll it (-5 % decode time)
-  constexpr int NP_D = (D + CT / LD - 1) / (CT / LD), NP_F2 = (D + CT / LF - 1) / (CT / LF);
-  const int rwg = (wg - NS + P) % P;  // row roles by a rotated workgroup index: rwg 0 = the first self-attention owner
-  const bool in_o = rwg < NP_D, in_f2 = rwg < NP_F2;
-
-  if (p.fault && wg == 0) return;  // test hook: a workgroup that never publishes; everybody else must give up and drain
-  for (int i = tid; i < kKvBytes / 16; i += PT) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};  // masked keys must be finite
-  if (tid < 16) ctl[tid] = 0;
-  if (PROF && tid < 64) prof_acc[tid] = 0;
-  __syncthreads();
-
-  long long t_last = PROF ? wall_clock64() : 0;
-  // pollers stamp slots 0..15 (thread 0), compute waves 16..31 (thread PL)
+  AXW_PERSIST_ROLES
+  AXW_PERSIST_INIT
 #define AXW_TL(IDX) \
   if (PROF && tl_on && (tid == 0 || tid == PL)) prof_acc[32 + (IDX)] = wall_clock64();
-#define AXW_STAMP(IDX) \
-  if (PROF && (tid == 0 || tid == PL)) { const long long t_now = wall_clock64(); prof_acc[IDX] += t_now - t_last; t_last = t_now; }
-  // first barrier of a phase: everybody learns whether a poller gave up
-#define AXW_BARRIER_CHECK(CODE)                                                                                          \
-  {                                                                                                                      \
-    wg_barrier();                                                                                                        \
-    if (ctl[0]) {                                                                                                        \
-      if (tid == 0) __hip_atomic_store((gu32*)p.err, (unsigned)(CODE) | 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
-      return;                                                                                                            \
-    }                                                                                                                    \
-  }
-
-  // Launch parameters that are read once per STEP or less (token feedback, teacher forcing, dumps, results) are not
-  // kept in scalar registers for the whole launch: they are re-read from the kernel-argument segment at their use,
-  // through a pointer the compiler cannot see through (so it can neither hoist the loads out of the step loop nor
-  // keep their results live). The d_model-768 instantiation was spilling 185 scalar registers into vector lanes.
-  const __attribute__((address_space(4))) PersistParams* kargs =
-      (const __attribute__((address_space(4))) PersistParams*)__builtin_amdgcn_kernarg_segment_ptr();
-#define AXW_COLD(FIELD) ([&] { auto* kp_ = kargs; asm volatile("" : "+s"(kp_)); return kp_->FIELD; }())
   int tok = AXW_COLD(sot)[0];
   int n_out = 0, n_done = 0, steps_run = 0;
-
-  // Cross-attention unit of this workgroup in the t-th layer of the LAUNCH (t = step * L + l), or -1. The units of
-  // consecutive layers take consecutive ranges of NU workgroups modulo NS, counted over the whole launch and not per
-  // step: 2 * NU <= NS then keeps the two units of any workgroup at least two layers apart across the step boundary
-  // as well. (Counted per step, the last layer's range wrapped onto the first layer's of the next step whenever
-  // L * NU > NS — large-v3-turbo: 4 x 60 units on 176 workgroups — and a workgroup staged the next step's K tiles over
-  // the ones its last-layer unit had not used yet: logits off by 4e-2 at every step of that model.)
-  auto ca_unit_of = [&](int t) -> int {
-    if (wg >= NS) return -1;
-    int r = (wg - (int)(((long)t * NU) % NS)) % NS;
-    if (r < 0) r += NS;
-    return r < NU ? r : -1;
-  };
 
   if (poller) {
     // ======================================================================================= pollers
     float x[GD];        // residual stream, element tid + k*PL
     float lg[GD], lb[GD];
-    float g2[GD];       // QF, row producers: the cross-attention LayerNorm's gain of the NEXT layer to run (A0 = W_cq (g . x0)),
-                        // requested a stage ahead like lg / lb: a polling wave must have no load in flight
     float shift = 0.f;  // LayerNorm variance shift (previous mean): sums stay small without a second pass
-    auto el = [&](int k) { return 2 * (tid + (k >> 1) * PL) + (k & 1); };  // vector element of register slot k
-    auto g2_prefetch = [&](int layer) {
-#pragma unroll
-      for (int k = 0; k < GD; ++k) { const int i = el(k); g2[k] = (QF && in_o && i < D) ? p.fl[(long)layer * DecArena::f_stride(D) + DecArena::F_CROSS_LN_W * D + i] : 0.f; }
-    };
-    g2_prefetch(0);
-    auto ln_prefetch = [&](const float* g, const float* be) {
-#pragma unroll
-      for (int k = 0; k < GD; ++k) {
-        const int i = el(k);
-        lg[k] = i < D ? g[i] : 0.f;
-        lb[k] = i < D ? be[i] : 0.f;
-      }
-    };
+    AXW_POLLER_PREFETCH
     // the pairs of a d-wide vector that starts at granule `base`
 #define AXW_PAIRS_D(BASE) [&](int j) { const int pr = tid + j * PL; return 2 * pr < D ? (BASE) + 2 * pr : -1; }
 
@@ -288,12 +190,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
   }
 
     for (int step = 0; step < p.total_steps; ++step) {
-      // x = token_embedding[tok] + positional_embedding[step]   (export_onnx.py:334-336)
-#pragma unroll
-      for (int k = 0; k < GD; ++k) {
-        const int i = el(k);
-        x[k] = i < D ? (float)AXW_COLD(tok_emb)[(long)tok * D + i] + AXW_COLD(pos)[(long)step * D + i] : 0.f;
-      }
+      AXW_EMBED(x, tok)
       ln_prefetch(p.fl + DecArena::F_ATTN_LN_W * D, p.fl + DecArena::F_ATTN_LN_B * D);
 
       for (int l = 0; l < L; ++l) {
@@ -370,7 +267,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           AXW_TL(4)
         }
         // ---- cross-attention unit: collect the head's query
-        const int cu = ca_unit_of(step * L + l);
+        const int cu = ca_unit_of(step * L + l, NU, wg, NS);
         if (cu >= 0) {
           const int ca_head = cu / kCrossSplit;
           if constexpr (QF) {
@@ -559,7 +456,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     };
     qkv_prefetch(0);
     {  // the first layer's cross-attention unit has no previous layer to hide behind
-      const int cu0 = ca_unit_of(0);
+      const int cu0 = ca_unit_of(0, NU, wg, NS);
       if (cu0 >= 0) {
         const int lane = ctid & 63, cw = __builtin_amdgcn_readfirstlane(ctid >> 6);
         const long off = (long)(cu0 / kCrossSplit) * 24 * 4096 + (long)((cu0 % kCrossSplit) * NCW + cw) * 4096;
@@ -583,12 +480,12 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         const float *b_qkv = FL + DecArena::F_B_QKV * D, *b_o = FL + DecArena::F_B_O * D, *b_cq = FL + DecArena::F_B_CQ * D,
                     *b_co = FL + DecArena::F_B_CO * D, *b_fc1 = FL + DecArena::F_B_FC1 * D, *b_fc2 = FL + DecArena::F_B_FC2 * D;
         const unsigned tag = (unsigned)(step * L + l + 1);
-        const int cu = ca_unit_of(step * L + l);
+        const int cu = ca_unit_of(step * L + l, NU, wg, NS);
         // Cross K/V tiles are constant during the utterance: the unit this workgroup runs in the NEXT layer is staged
         // into LDS now (LDS-DMA, 16 x 1 KiB per wave), a few instructions after each publish of this layer, so that no
         // publish waits behind a burst of DMA requests. Units of one workgroup are at least two layers apart (ca_unit_of).
         const int ln = l + 1 < L ? l + 1 : 0;
-        const int cun = ca_unit_of(step * L + l + 1);
+        const int cun = ca_unit_of(step * L + l + 1, NU, wg, NS);
         auto kv_piece = [&](int i0, int i1) {
           if (cun < 0) return;
           const int kb = (cun % kCrossSplit) * NCW + cw;  // 64-key block of this wave (24 blocks = t_pad 1536)
@@ -893,23 +790,16 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     }
   }
 
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): no LDS-DMA may still be in flight when the workgroup's LDS is released
-  if (PROF) {
-    __syncthreads();
-    if (tid < 64) AXW_COLD(prof)[(long)wg * 64 + tid] = prof_acc[tid];
-  }
+  AXW_PERSIST_DRAIN
   if (wg == 0 && tid == 0) {
     AXW_COLD(n_out)[0] = n_out;
     AXW_COLD(state)->step = steps_run;
     AXW_COLD(state)->n_done = n_done;
   }
-#undef AXW_COLD
-#undef AXW_BARRIER_CHECK
-#undef AXW_STAMP
 #undef AXW_TL
 }
 
-// ---------------------------------------------------------------------------------------- host side
+// ---------------------------------------------------------------------------------------- host side (both launches)
 int decode_persistent_grid(int d_model, int n_cu) {
   int g = n_cu < d_model ? n_cu : d_model;  // every workgroup owns at least one row of the narrowest layer
   return g < 256 ? g : 256;                 // the argmax merge reads 2 granules per workgroup with 512 poller lanes
@@ -919,46 +809,39 @@ bool decode_persistent_supported(int d_model, int n_head, int n_layer, int n_cu)
   const int P = decode_persistent_grid(d_model, n_cu);
   // one (layer, head) self-attention cache per workgroup; the rest take the 3 * n_head cross-attention units of a layer
   if (P - n_layer * n_head < 2 * kCrossSplit * n_head) return false;  // and units of one workgroup >= 2 layers apart
-  switch (d_model) { case 128: case 256: case 384: case 512: case 768: case 1280: return true; default: return false; }
+  return persist_dispatch(d_model, [](auto) { return hipSuccess; }) == hipSuccess;
+}
+int decode_persistent_max_clips(int d_model, int n_head, int n_layer, int grid) {
+  // every linear layer must be ONE pass of rows per workgroup (a second pass overwrites the rows the next clip still
+  // needs): true up to d_model 768, not for 1280 (mlp.0: 20 rows per workgroup in passes of 16)
+  if (d_model > 768) return 1;
+  int nc = 1;
+  // every workgroup that owns no self-attention head takes at most ONE cross-attention unit (a clip's head and key range) per
+  // layer, and the later clips' vectors must fit what the K/V region leaves of the CU's 160 KB of LDS
+  while (nc < 3 && grid - n_layer * n_head >= (nc + 1) * kCrossSplit * n_head && persist_lds_bytes(d_model, nc + 1) <= 160 * 1024) ++nc;
+  return nc;
 }
 // 16 d-wide buffers, the argmax pairs at 16 d (up to 512 granules), the fold's statistics at 16 d + 512 (one 16-granule line
 // per row producer, at most d / 16 of them), the error word last
-size_t decode_persistent_gran_bytes(int d_model, int grid) { return ((size_t)16 * d_model + 512 + (size_t)d_model + 64 + 0 * (size_t)grid) * 8; }
-
-static size_t persist_lds_bytes(int d) {
-  return (size_t)kKvBytes + ((size_t)4 * d + d / 8 + NCW * kPS + 2 * NPW + 4 + 64 + 16 + 16 + 16 + 64 + NCW * 64) * 4 + 64 * 8 + 64;
-}
-
-template <int LD, int CD, int LF, int CF, bool PROF, bool QF>
-static hipError_t launch_one_prof(const PersistParams& p, int grid, hipStream_t s) {
-  const size_t lds = persist_lds_bytes(8 * LD * CD);
-  auto kfn = decode_persistent_kernel<LD, CD, LF, CF, PROF, QF>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(PT), lds, s, p);
-  return hipGetLastError();
-}
+size_t decode_persistent_gran_bytes(int d_model, int /*grid*/) { return ((size_t)16 * d_model + 512 + (size_t)d_model + 64) * 8; }
 
 // the profiling stamps are a separate instantiation: the production kernel carries none of their code
 template <int LD, int CD, int LF, int CF>
 static hipError_t launch_one(const PersistParams& p, int grid, hipStream_t s) {
-  if constexpr (8 * LD * CD <= 768) {  // the query fold, when the engine built its arena (p.qf)
-    if (p.qf) return p.prof ? launch_one_prof<LD, CD, LF, CF, true, true>(p, grid, s) : launch_one_prof<LD, CD, LF, CF, false, true>(p, grid, s);
+  constexpr int D = 8 * LD * CD;
+  if constexpr (D <= 768) {  // the query fold, when the engine built its arena (p.qf)
+    if (p.qf)
+      return launch_persistent(p.prof ? decode_persistent_kernel<LD, CD, LF, CF, true, true> : decode_persistent_kernel<LD, CD, LF, CF, false, true>, D, 1, p, grid, s);
   }
-  return p.prof ? launch_one_prof<LD, CD, LF, CF, true, false>(p, grid, s) : launch_one_prof<LD, CD, LF, CF, false, false>(p, grid, s);
+  return launch_persistent(p.prof ? decode_persistent_kernel<LD, CD, LF, CF, true, false> : decode_persistent_kernel<LD, CD, LF, CF, false, false>, D, 1, p, grid, s);
 }
 
 hipError_t launch_decode_persistent(const PersistParams& p, int d_model, int grid, hipStream_t s) {
   if (p.n_clip >= 2) return launch_decode_persistent2(p, d_model, grid, s);  // two or three clips: decode_persistent2.hip
-  switch (d_model) {
-    case 128: return launch_one<16, 1, 32, 2>(p, grid, s);
-    case 256: return launch_one<32, 1, 64, 2>(p, grid, s);
-    case 384: return launch_one<16, 3, 64, 3>(p, grid, s);
-    case 512: return launch_one<32, 2, 64, 4>(p, grid, s);
-    case 768: return launch_one<32, 3, 64, 6>(p, grid, s);
-    case 1280: return launch_one<32, 5, 64, 10>(p, grid, s);
-    default: return hipErrorInvalidValue;
-  }
+  return persist_dispatch(d_model, [&](auto sh) {
+    using S = decltype(sh);
+    return launch_one<S::LD, S::CD, S::LF, S::CF>(p, grid, s);
+  });
 }
 
 }  // inline namespace AXW_NS

@@ -1,4 +1,4 @@
-// decode_persistent2.hip — the greedy decode loops of TWO clips as a single persistent launch (gfx950).
+// decode_persistent2.hip — the greedy decode loops of two or three clips as a single persistent launch (gfx950).
 //
 // The one-clip launch (decode_persistent.hip) spends two thirds of a decoder layer waiting for hand-offs: eight dependent
 // all-to-all exchanges of 1.1-1.7 us each against ~9 us of arithmetic (profiles/r04_persist_phases_summary.txt). Here every
@@ -11,8 +11,10 @@
 // global memory (PersistParams::self_k1 / self_v1, the per-owner layouts of the LDS cache, read past L1) and its cross K/V
 // are read from their slot; the d-wide input vector, the query and the argmax scratch exist once per clip (3.4 KB), the two
 // wide LDS vectors (mlp hidden, cross-attention partial records) are shared and handed over with one more barrier.
-// The kernel body is the one-clip kernel's, phase by phase, with a clip loop around every phase (NC = 2); it is a separate
-// translation unit so that the one-clip kernel — the headline path — keeps its register allocation to the instruction.
+// The phases are the one-clip kernel's, with a clip loop around every phase (NC = 2, 3); the prologue (shapes, granule
+// offsets, LDS carve-up, roles, fault hook, kernel-argument access) and the host side are shared with it through
+// decode_persistent_common.hpp. It is a separate translation unit so that the one-clip kernel — the headline path — keeps its
+// register allocation to the instruction.
 #include "decode_persistent_common.hpp"
 
 namespace axw {
@@ -33,35 +35,15 @@ inline namespace AXW_NS {
 template <int LD, int CD, int LF, int CF, bool PROF, int NC, bool QF>
 __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) {
   static_assert(NC == 2 || NC == 3, "two or three clips per launch");
-  constexpr int D = 8 * LD * CD, F = 8 * LF * CF, H = D / 64;
-  static_assert(F == 4 * D, "mlp width");
-  // a poller lane owns PAIRS of adjacent vector elements: pair tid + j*PL (j < GPD) = elements 2*pair, 2*pair + 1
-  constexpr int GPD = (D / 2 + PL - 1) / PL, GD = 2 * GPD, NPART = H * kCrossSplit * kPS;
-  constexpr int NPP = NPART / 2, NPP1 = (NPP + 1) / 2, GP1 = (NPP1 + PL - 1) / PL, GP2 = (NPP - NPP1 + CT - 1) / CT;  // partial-record pairs, split between the roles
-  static_assert(NPART % 2 == 0 && kPS % 2 == 0 && kRec % 2 == 0 && D % 2 == 0, "pair polls need even layouts");
-  constexpr int NU = kCrossSplit * H;  // cross-attention units per layer and clip
-  constexpr int NUC = NC * NU;         // ... per layer: unit r = clip r / NU, (head, key range) r % NU
-  // granule buffers (u64 units)
-  constexpr int O_QKV = 0, O_ATT = 3 * D, O_Y1 = 4 * D, O_CQ = 5 * D, O_PART = 6 * D, O_Y2 = 10 * D, O_HID = 11 * D, O_Y3 = 15 * D,
-                O_AMAX = 16 * D, O_STAT = 16 * D + 512;  // (QF) statistics of row producer p: granules O_STAT + 16 p, + 1
-  static_assert(NPART <= 3 * D + D / 8 && NU * kRec <= 4 * D, "partial buffer");
-  static_assert(kCrossSplit * NCW == 24, "cross-attention key blocks");
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  h16* sK = reinterpret_cast<h16*>(smem);                  // [8 blk][8][64 keys][8]  (blocked, lane = key)
-  h16* sV = sK + NCW * 4096;                                // cross tiles: [512 keys][64]; self-attention cache: per block [8 (key/8)][64 dims][8 keys]
-  float* act = reinterpret_cast<float*>(smem + kKvBytes);    // [F + D/8] input vector of the current rows phase
-  float* wpart = act + F + D / 8;                            // [NCW][kPS] per-wave attention partials
-  float* red = wpart + NCW * kPS;                            // [2*NPW] LayerNorm partial sums
-  unsigned* qs = reinterpret_cast<unsigned*>(red + 2 * NPW);  // [64] query of the attention phase as packed h16 pairs: [32] hi, [32] lo
-  float* am_v = reinterpret_cast<float*>(qs) + 64;           // [16] argmax scratch
-  int* am_i = reinterpret_cast<int*>(am_v + 16);             // [16]
-  int* ctl = am_i + 16;                                      // [16]: 0 give-up flag, 1 argmax of the step
-  float* pk = reinterpret_cast<float*>(ctl + 16);            // [64] this workgroup's rows of the phase, assembled for the one-instruction publish
-  float* pscr = pk + 64;                                     // [NCW][64] probability transpose scratch
-  long long* prof_acc = reinterpret_cast<long long*>(pscr + NCW * 64);  // [64] per-phase time sums + one layer's absolute timeline (profiling runs only)
+  AXW_PERSIST_SHAPES
+  // Cross-attention units per layer (ca_unit_of): unit r = clip r / NU, (head, key range) r % NU, each ONE clip's — a
+  // workgroup's 128 KB of tiles are one clip's, as in the one-clip launch, and NC times as many workgroups are busy per layer.
+  // NUC <= NS only guarantees one unit per workgroup and layer, so a workgroup may own units in CONSECUTIVE layers: the tiles of
+  // the next unit are requested only after this layer's attention block is through (kv_piece below).
+  constexpr int NUC = NC * NU;
+  AXW_PERSIST_LDS(0)
   // every clip after the first: its own d-wide input vector [D], attention query [64], argmax scratch [32] and the self-attention
-  // k, v rows of its CURRENT step [64 words = 128 h16] (persist2_lds_bytes)
+  // k, v rows of its CURRENT step [64 words = 128 h16] (persist_lds_bytes)
   constexpr int XW = D + 64 + 32 + 64;
   float* const xbase = reinterpret_cast<float*>(prof_acc + 64);
   float* actc[NC];
@@ -86,88 +68,19 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
   auto x0s = [&](int c) { return qfs + c * 68 + 32; };
   auto shs = [&](int c) { return qfs + c * 68 + 64; };
 
-  // tid is re-derived behind an opaque asm at the top of every layer: without it the compiler hoists every
-  // per-thread address of every phase out of the step loop and keeps >100 registers of loop invariants alive
-  int tid = threadIdx.x;
-  const bool poller = tid < PL;  // wave-uniform
-  const int P = gridDim.x, wg = blockIdx.x;
-  const int L = p.n_layer;
-  u64* const G = p.gran;
+  AXW_PERSIST_IDS
   const __amdgpu_buffer_rsrc_t GR = __builtin_amdgcn_make_buffer_rsrc((void*)p.gran, 0, (NC - 1) * (int)(p.gran_clip_u64 * 8) + p.gran_bytes, 0x27000);
   const int gco = (int)p.gran_clip_u64;  // granule index of clip c's area: c * gco
 
-  // self-attention ownership: unit (l, h) -> workgroup P-1-(l*H+h). The other NS workgroups take the cross-attention
-  // units: unit u of layer l -> workgroup (l*NU + u) % NS.
-  const int sa_unit = P - 1 - wg;
-  const int sa_layer = sa_unit < L * H ? sa_unit / H : -1, sa_head = sa_unit % H;
-  const int NS = P - L * H;
-  // producers of the d-row phases (one pass of CT/LD resp. CT/LF rows each, workgroups 0..): only they consume the
-  // attention outputs / cross-attention partials / mlp hidden vector; every other workgroup skips those three phases
-  // altogether (no polls, no barriers): a hand-off is the faster the fewer workgroups poll it (-5 % decode time)
-  constexpr int NP_D = (D + CT / LD - 1) / (CT / LD), NP_F2 = (D + CT / LF - 1) / (CT / LF);
-  // Row roles go by a ROTATED workgroup index (rwg 0 = the first self-attention owner): the d-wide layers' producers are then
-  // workgroups that own a head (busy with attention in one layer of twelve), not the ones that run a cross-attention unit in
-  // most layers — with two clips interleaved, a producer that is also a unit holder puts one clip's rows behind the other
-  // clip's attention block.
-  const int rwg = (wg - NS + P) % P;
-  const bool in_o = rwg < NP_D, in_f2 = rwg < NP_F2;
-  // (Measured and switched off: a head's owner that produces no QKV rows running clip 0's self-attention block BEFORE clip 1's
-  //  QKV LayerNorm — its query is on its way already — 134.0 -> 143.8 ms per pair: the owners' later phases slip behind.)
-  constexpr bool sa_first = false;
-
-  if (p.fault && wg == 0) return;  // test hook: a workgroup that never publishes; everybody else must give up and drain
-  for (int i = tid; i < kKvBytes / 16; i += PT) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};  // masked keys must be finite
-  if (tid < 16) ctl[tid] = 0;
-  if (PROF && tid < 64) prof_acc[tid] = 0;
-  __syncthreads();
-
-  long long t_last = PROF ? wall_clock64() : 0;
-  // pollers stamp slots 0..15 (thread 0), compute waves 16..31 (thread PL)
+  AXW_PERSIST_ROLES
+  AXW_PERSIST_INIT
 #define AXW_TL(IDX) \
   if (PROF && tl_on && (tid == 0 || tid == PL) && (p.prof_clip || prof_acc[32 + (IDX)] == 0)) prof_acc[32 + (IDX)] = wall_clock64();
-#define AXW_STAMP(IDX) \
-  if (PROF && (tid == 0 || tid == PL)) { const long long t_now = wall_clock64(); prof_acc[IDX] += t_now - t_last; t_last = t_now; }
-  // first barrier of a phase: everybody learns whether a poller gave up
-#define AXW_BARRIER_CHECK(CODE)                                                                                          \
-  {                                                                                                                      \
-    wg_barrier();                                                                                                        \
-    if (ctl[0]) {                                                                                                        \
-      if (tid == 0) __hip_atomic_store((gu32*)p.err, (unsigned)(CODE) | 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
-      return;                                                                                                            \
-    }                                                                                                                    \
-  }
-
-  // Launch parameters that are read once per STEP or less (token feedback, teacher forcing, dumps, results) are not
-  // kept in scalar registers for the whole launch: they are re-read from the kernel-argument segment at their use,
-  // through a pointer the compiler cannot see through (so it can neither hoist the loads out of the step loop nor
-  // keep their results live). The d_model-768 instantiation was spilling 185 scalar registers into vector lanes.
-  const __attribute__((address_space(4))) PersistParams* kargs =
-      (const __attribute__((address_space(4))) PersistParams*)__builtin_amdgcn_kernarg_segment_ptr();
-#define AXW_COLD(FIELD) ([&] { auto* kp_ = kargs; asm volatile("" : "+s"(kp_)); return kp_->FIELD; }())
   int tok[NC], n_out[NC];
   bool fin[NC];  // this clip has emitted eot / spent its budget: it rides along (its results are ignored) until the other one has, too
 #pragma unroll
   for (int c = 0; c < NC; ++c) { tok[c] = AXW_COLD(sot)[0]; n_out[c] = 0; fin[c] = false; }
   int n_done = 0, steps_run = 0;
-
-  // Cross-attention unit of this workgroup in the t-th layer of the LAUNCH (t = step * L + l), or -1. The units of
-  // consecutive layers take consecutive ranges of NU workgroups modulo NS, counted over the whole launch and not per
-  // step: 2 * NU <= NS then keeps the two units of any workgroup at least two layers apart across the step boundary
-  // as well. (Counted per step, the last layer's range wrapped onto the first layer's of the next step whenever
-  // L * NU > NS — large-v3-turbo: 4 x 60 units on 176 workgroups — and a workgroup staged the next step's K tiles over
-  // the ones its last-layer unit had not used yet: logits off by 4e-2 at every step of that model.)
-  // Two clips: NC * NU units per layer, each ONE clip's (head, key range) — a workgroup's 128 KB of tiles are one clip's, as
-  // in the one-clip launch, and twice as many workgroups are busy per layer. NC * NU <= NS only guarantees one unit per
-  // workgroup and layer, so a workgroup may own units in CONSECUTIVE layers: the tiles of the next unit are requested
-  // only after this layer's attention block is through (kv_piece below).
-  auto ca_unit_of = [&](int t) -> int {
-    if (wg >= NS) return -1;
-    int r = (wg - (int)(((long)t * NUC) % NS)) % NS;
-    if (r < 0) r += NS;
-    return r < NUC ? r : -1;
-  };
-
-  // per-clip argmax scratch (clip 1's sits behind its query)
 
   if (poller) {
     // ======================================================================================= pollers
@@ -176,22 +89,8 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     float shift[NC];    // LayerNorm variance shift (previous mean): sums stay small without a second pass
 #pragma unroll
     for (int c = 0; c < NC; ++c) shift[c] = 0.f;
-    auto el = [&](int k) { return 2 * (tid + (k >> 1) * PL) + (k & 1); };  // vector element of register slot k
-    float g2[GD];       // QF, row producers: the cross-attention LayerNorm's gain of the next layer to run (requested a stage ahead)
-    auto g2_prefetch = [&](int layer) {
-#pragma unroll
-      for (int k = 0; k < GD; ++k) { const int i = el(k); g2[k] = (QF && in_o && i < D) ? p.fl[(long)layer * DecArena::f_stride(D) + DecArena::F_CROSS_LN_W * D + i] : 0.f; }
-    };
-    g2_prefetch(0);
+    AXW_POLLER_PREFETCH
     const int row0 = rwg * (CT / LD);  // QF: first row of this producer's slice of the d-wide layers
-    auto ln_prefetch = [&](const float* g, const float* be) {
-#pragma unroll
-      for (int k = 0; k < GD; ++k) {
-        const int i = el(k);
-        lg[k] = i < D ? g[i] : 0.f;
-        lb[k] = i < D ? be[i] : 0.f;
-      }
-    };
     // the pairs of a d-wide vector of clip C that starts at granule `base` of its area
 #define AXW_PAIRS_D(BASE, C) [&](int j) { const int pr = tid + j * PL; return 2 * pr < D ? (C) * gco + (BASE) + 2 * pr : -1; }
 
@@ -230,14 +129,8 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
   }
 
     for (int step = 0; step < p.total_steps; ++step) {
-      // x = token_embedding[tok] + positional_embedding[step]   (export_onnx.py:334-336)
 #pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int k = 0; k < GD; ++k) {
-          const int i = el(k);
-          x[c][k] = i < D ? (float)AXW_COLD(tok_emb)[(long)tok[c] * D + i] + AXW_COLD(pos)[(long)step * D + i] : 0.f;
-        }
+      for (int c = 0; c < NC; ++c) AXW_EMBED(x[c], tok[c])
       ln_prefetch(p.fl + DecArena::F_ATTN_LN_W * D, p.fl + DecArena::F_ATTN_LN_B * D);
 
       for (int l = 0; l < L; ++l) {
@@ -253,27 +146,6 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           q[tid] = hi;
           q[32 + tid] = lo;
         };
-        // self-attention owner, clip 0: collect q, k, v of the head; append k, v to the LDS cache; its blocks are the compute waves'
-#define AXW_SA0_POLL                                                                                                   \
-  {                                                                                                                    \
-    unsigned v[2];                                                                                                     \
-    const bool fail = gather2<1>(GR, tag, v, p.err, ctl, qkv_pair(0));                                                 \
-    if (tid < 32) stage_q(v, qs);                                                                                      \
-    else if (tid < 96) {                                                                                               \
-      _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                                  \
-        const int dd = 2 * (tid & 31) + e;                                                                             \
-        const float val = __uint_as_float(v[e]);                                                                       \
-        if (tid < 64) /* K row `step`, blocked [blk][d/8][key%64][8] */                                                \
-          sK[(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)val;                            \
-        else          /* V row `step`, TRANSPOSED per block: [blk][key%64 / 8][dim][8 keys] */                         \
-          sV[(step >> 6) * 4096 + ((step >> 3) & 7) * 512 + dd * 8 + (step & 7)] = (h16)val;                           \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if (fail) ctl[0] = 1;                                                                                              \
-    AXW_STAMP(2)                                                                                                       \
-    AXW_BARRIER_CHECK(0x200 + l)                                                                                       \
-    AXW_STAMP(3)                                                                                                       \
-  }
         // ---- QKV
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -285,13 +157,33 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           AXW_LN_STAGE_X(y, l > 0, fail, 0x100 + l, c, in_o)
           AXW_STAMP(1)
           AXW_TL(1)
-          if (c == 0 && l == sa_layer && sa_first) AXW_SA0_POLL
         }
         if constexpr (QF) ln_prefetch(FL + DecArena::F_MLP_LN_W * D, FL + DecArena::F_MLP_LN_B * D);
         else ln_prefetch(FL + DecArena::F_CROSS_LN_W * D, FL + DecArena::F_CROSS_LN_B * D);
         // ---- self-attention owner (clip 0: LDS cache, clip 1: global memory)
+        // (Measured and switched off: a head's owner that produces no QKV rows running clip 0's self-attention block BEFORE clip 1's
+        //  QKV LayerNorm — its query is on its way already — 134.0 -> 143.8 ms per pair: the owners' later phases slip behind.)
         if (l == sa_layer) {
-          if (!sa_first) AXW_SA0_POLL
+          {  // clip 0: collect q, k, v of the head; append k, v to the LDS cache; its blocks are the compute waves'
+            unsigned v[2];
+            const bool fail = gather2<1>(GR, tag, v, p.err, ctl, qkv_pair(0));
+            if (tid < 32) stage_q(v, qs);
+            else if (tid < 96) {
+#pragma unroll
+              for (int e = 0; e < 2; ++e) {
+                const int dd = 2 * (tid & 31) + e;
+                const float val = __uint_as_float(v[e]);
+                if (tid < 64)  // K row `step`, blocked [blk][d/8][key%64][8]
+                  sK[(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)val;
+                else           // V row `step`, TRANSPOSED per block: [blk][key%64 / 8][dim][8 keys]
+                  sV[(step >> 6) * 4096 + ((step >> 3) & 7) * 512 + dd * 8 + (step & 7)] = (h16)val;
+              }
+            }
+            if (fail) ctl[0] = 1;
+            AXW_STAMP(2)
+            AXW_BARRIER_CHECK(0x200 + l)
+            AXW_STAMP(3)
+          }
 #pragma unroll
           for (int c = 1; c < NC; ++c) {
             // The later clips' caches live in global memory (there is one LDS region, and it is clip 0's). Their blocks are run by the POLLER
@@ -379,7 +271,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
             AXW_BARRIER_CHECK(0x300 + l)
           }
         }
-        const int cu = ca_unit_of(step * L + l);
+        const int cu = ca_unit_of(step * L + l, NUC, wg, NS);
         if constexpr (QF) {
           // ---- cross-attention unit: T of the head + the producers' statistics of ITS clip -> the head's query (decode_persistent.hip)
           if (cu >= 0) {
@@ -545,31 +437,24 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         best[c] = best_idx;
       }
       wg_barrier();  // B5: am_v/am_i are free again
-      const int gi = step - 3;
-      if (NC == 1 && AXW_COLD(forced)) {
-        if (wg == 0 && tid == 0 && AXW_COLD(argmax_dump) && gi <= AXW_COLD(n_forced)) AXW_COLD(argmax_dump)[gi] = best[0];
-        if (gi < AXW_COLD(n_forced)) tok[0] = AXW_COLD(forced)[gi];
-      } else {
-        // Whisper.cpp:219-222 per clip: eot, the context's end or the clip's budget ends ITS loop; with two clips the one
-        // that is through rides along (same feed, results ignored) until the other is, too
-        bool all_fin = true;
+      // Whisper.cpp:219-222 per clip: eot, the context's end or the clip's budget ends ITS loop; the clip that is through rides
+      // along (same feed, results ignored) until the others are, too
+      bool all_fin = true;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const int mn = c == 0 ? AXW_COLD(max_new) : (c == 1 ? AXW_COLD(max_new1) : AXW_COLD(max_new2));
-          if (!fin[c] && (best[c] == AXW_COLD(eot) || step + 1 >= AXW_COLD(n_ctx) || n_out[c] >= mn)) fin[c] = true;
-          if (!fin[c]) {
-            if (wg == 0 && tid == 0) (c == 0 ? AXW_COLD(out_ids) : AXW_COLD(out_ids1) + (long)(c - 1) * AXW_COLD(n_ctx))[n_out[c]] = best[c];
-            ++n_out[c];
-            tok[c] = best[c];
-          }
-          all_fin &= fin[c];
+      for (int c = 0; c < NC; ++c) {
+        const int mn = c == 0 ? AXW_COLD(max_new) : (c == 1 ? AXW_COLD(max_new1) : AXW_COLD(max_new2));
+        if (!fin[c] && (best[c] == AXW_COLD(eot) || step + 1 >= AXW_COLD(n_ctx) || n_out[c] >= mn)) fin[c] = true;
+        if (!fin[c]) {
+          if (wg == 0 && tid == 0) (c == 0 ? AXW_COLD(out_ids) : AXW_COLD(out_ids1) + (long)(c - 1) * AXW_COLD(n_ctx))[n_out[c]] = best[c];
+          ++n_out[c];
+          tok[c] = best[c];
         }
-        if (all_fin) { n_done = NC; break; }
+        all_fin &= fin[c];
       }
+      if (all_fin) { n_done = NC; break; }
     }
 #undef AXW_LN_STAGE
 #undef AXW_LN_STAGE_X
-#undef AXW_SA0_POLL
 #undef AXW_PAIRS_D
   } else {
     // ======================================================================================= compute waves
@@ -589,11 +474,6 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     // the busiest: their mlp.0 rows could only be requested after their cross-attention-output publish, ~2 us before
     // use, and arrived late — every consumer of the hidden vector waited for them: 1.2 us of skew per layer).
     const int pk_f = (NP_D + NP_F <= P && NP_Q <= P && NP_D + NP_F + NP_Q >= P) ? NP_D : ((NP_F <= P && NP_Q <= P && NP_F + NP_Q >= P) ? 0 : -1);
-    const bool is_fc1 = pk_f < 0 || (rwg >= pk_f && rwg < pk_f + NP_F);
-    // its mlp.2 rows can be requested a phase earlier (no mlp.0 rows in the way); not for wide models: 10 chunks per lane
-    // held across the mlp.0 phase do not fit the register budget (the d=1280 instantiation went to scratch)
-    constexpr bool kEarlyFc2 = NC == 1 && CF <= 6;
-    const bool early_fc2 = kEarlyFc2 && in_f2 && !is_fc1;
     const int pk_d = 0;  // d rows in passes of CT/LD (or CT/LF) rows: never more producers than workgroups (P <= d)
     // two register sets for the d-wide layers are enough: a phase computes from one while the next phase's rows land
     // in the other (qkv A, o B, cq A, co B, mlp.0 A, [mlp.2 F], next qkv / vocabulary A)
@@ -601,7 +481,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     RowSet<LF, CF> rs_fc2;
     ra.prefetch(p.wl, p.fl + DecArena::F_B_QKV * D, D, 3 * D, rwg, P, ctid, pk_qkv);
     {  // the first layer's cross-attention unit has no previous layer to hide behind
-      const int cu0 = ca_unit_of(0);
+      const int cu0 = ca_unit_of(0, NUC, wg, NS);
       if (cu0 >= 0) {  // its K tiles; the V tiles are layer 0's own pieces
         const int lane = ctid & 63, cw = __builtin_amdgcn_readfirstlane(ctid >> 6);
         const int u0 = cu0 % NU;
@@ -624,14 +504,14 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         const float *b_qkv = FL + DecArena::F_B_QKV * D, *b_o = FL + DecArena::F_B_O * D, *b_cq = FL + DecArena::F_B_CQ * D,
                     *b_co = FL + DecArena::F_B_CO * D, *b_fc1 = FL + DecArena::F_B_FC1 * D, *b_fc2 = FL + DecArena::F_B_FC2 * D;
         const unsigned tag = (unsigned)(step * L + l + 1);
-        const int cu = ca_unit_of(step * L + l);
+        const int cu = ca_unit_of(step * L + l, NUC, wg, NS);
         // Cross K/V tiles are constant during the utterance: they are staged into LDS ahead of their use (LDS-DMA, 16 x 1 KiB
         // per wave), a few instructions after each publish, so that no publish waits behind a burst of DMA requests. A
         // workgroup may own units in consecutive layers (ca_unit_of), so the region is free only once THIS layer's block is
         // through: the K tiles (pieces 0-7) of the next layer's unit go out behind the publishes that follow the block, its
         // V tiles (8-15) behind the next layer's publishes that precede it.
         const int ln = l + 1 < L ? l + 1 : 0;
-        const int cun = ca_unit_of(step * L + l + 1);
+        const int cun = ca_unit_of(step * L + l + 1, NUC, wg, NS);
         auto kv_piece = [&](int i0, int i1) {
           const int un = i0 < 8 ? cun : cu, lay = i0 < 8 ? ln : l;  // (a call never straddles piece 8)
           if (un < 0) return;
@@ -644,26 +524,6 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)dst, 16, 0, kKvAux);
           }
         };
-        // self-attention of one head over keys 0..step (export_onnx.py:103-147: the -60000 mask + the separate current-token
-        // column of the reference equal causal attention), clip 0: the LDS cache. No second workgroup barrier: the compute wave
-        // that arrives last merges the block partials and publishes.
-#define AXW_SA0_COMP                                                                                                   \
-  {                                                                                                                    \
-    AXW_BARRIER_CHECK(0x200 + l)                                                                                       \
-    const int nblk = (step >> 6) + 1;                                                                                  \
-    if (cw < nblk) attn_block<true>(sK + cw * 4096, sV + cw * 4096, qs, cw * 64 + lane <= step, pscr + cw * 64, wpart + cw * kPS, lane); \
-    __builtin_amdgcn_wave_barrier();                                                                                   \
-    int old = 0;                                                                                                       \
-    if (lane == 0) old = __hip_atomic_fetch_add(ctl + 3, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);           \
-    old = __builtin_amdgcn_readfirstlane(old);                                                                         \
-    if ((old + 1) % NCW == 0) {                                                                                        \
-      float m, lt, ov;                                                                                                 \
-      merge_partials(wpart, nblk, lane, &m, &lt, &ov);                                                                 \
-      gput(G + O_ATT + sa_head * 64 + lane, tag, ov / lt);                                                             \
-    }                                                                                                                  \
-    AXW_STAMP(18)                                                                                                      \
-    AXW_TL(11)                                                                                                         \
-  }
         // ---- QKV rows (export_onnx.py:245-247)
         float res[2];
 #pragma unroll
@@ -680,7 +540,6 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           }
           AXW_STAMP(17)
           AXW_TL(10)
-          if (c == 0 && l == sa_layer && sa_first) AXW_SA0_COMP
         }
         // QF, row producers: A0 = W_cq (g . x0) of this slot's row for EVERY clip (g . x0 has been in LDS since the clip's QKV stage);
         // the rows of W_cq take the set the QKV rows leave. In the layer whose head this workgroup owns, behind clip 0's blocks.
@@ -702,7 +561,24 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         }
         // ---- self-attention (clip 1's blocks are the poller waves' — see there: only the hand-over of its query is shared)
         if (l == sa_layer) {
-          if (!sa_first) AXW_SA0_COMP
+          {  // self-attention of one head over keys 0..step (export_onnx.py:103-147: the -60000 mask + the separate current-token
+             // column of the reference equal causal attention), clip 0: the LDS cache. No second workgroup barrier: the compute
+             // wave that arrives last merges the block partials and publishes.
+            AXW_BARRIER_CHECK(0x200 + l)
+            const int nblk = (step >> 6) + 1;
+            if (cw < nblk) attn_block<true>(sK + cw * 4096, sV + cw * 4096, qs, cw * 64 + lane <= step, pscr + cw * 64, wpart + cw * kPS, lane);
+            __builtin_amdgcn_wave_barrier();
+            int old = 0;
+            if (lane == 0) old = __hip_atomic_fetch_add(ctl + 3, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+            old = __builtin_amdgcn_readfirstlane(old);
+            if ((old + 1) % NCW == 0) {
+              float m, lt, ov;
+              merge_partials(wpart, nblk, lane, &m, &lt, &ov);
+              gput(G + O_ATT + sa_head * 64 + lane, tag, ov / lt);
+            }
+            AXW_STAMP(18)
+            AXW_TL(11)
+          }
           a0_rows();
 #pragma unroll
           for (int c = 1; c < NC; ++c) AXW_BARRIER_CHECK(0x200 + l)
@@ -807,9 +683,6 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           }
         }
         ra.prefetch(w_fc1, b_fc1, D, F, rwg, P, ctid, pk_f);
-        if constexpr (kEarlyFc2) {
-          if (early_fc2) rs_fc2.prefetch(w_fc2, b_fc2, F, D, rwg, P, ctid, pk_d);
-        }
         kv_piece(0, 3);
         AXW_STAMP(25)
         AXW_TL(15)
@@ -825,7 +698,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           if (c == 0) kv_piece(3, 5);
           // (behind the LAST clip's publish: next to the mlp.0 rows, which the second clip still needs, the 6 chunks per lane of
           //  the mlp.2 rows do not fit the register budget — as loads followed by vmcnt(0) + a scratch store they cost 2 us per layer)
-          if (c == NC - 1 && !early_fc2) rs_fc2.prefetch(w_fc2, b_fc2, F, D, rwg, P, ctid, pk_d);
+          if (c == NC - 1) rs_fc2.prefetch(w_fc2, b_fc2, F, D, rwg, P, ctid, pk_d);
           AXW_STAMP(27)
           AXW_TL(16)
         }
@@ -895,6 +768,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         int bi[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) { bv[c] = -INFINITY; bi[c] = 0x7fffffff; }
+        // (a dead dump, kept: deleting it moves the register allocation of the d_model 128 and 256 two-clip kernels)
         float* dump = (NC == 1 && AXW_COLD(logits_dump)) ? AXW_COLD(logits_dump) + (long)(step - 3) * N : nullptr;
         const int r0 = ra.r0, r1 = ra.r1;
         auto consume = [&](const u32x4 (&wr)[CD], int row) {
@@ -973,28 +847,19 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         best[c] = best_idx;
       }
       wg_barrier();  // B5
-      const int gi = step - 3;
-      if (NC == 1 && AXW_COLD(forced)) {
-        if (gi < AXW_COLD(n_forced)) tok[0] = AXW_COLD(forced)[gi];
-      } else {
-        bool all_fin = true;
+      bool all_fin = true;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const int mn = c == 0 ? AXW_COLD(max_new) : (c == 1 ? AXW_COLD(max_new1) : AXW_COLD(max_new2));
-          if (!fin[c] && (best[c] == AXW_COLD(eot) || step + 1 >= AXW_COLD(n_ctx) || n_out[c] >= mn)) fin[c] = true;
-          if (!fin[c]) { ++n_out[c]; tok[c] = best[c]; }
-          all_fin &= fin[c];
-        }
-        if (all_fin) { n_done = NC; break; }
+      for (int c = 0; c < NC; ++c) {
+        const int mn = c == 0 ? AXW_COLD(max_new) : (c == 1 ? AXW_COLD(max_new1) : AXW_COLD(max_new2));
+        if (!fin[c] && (best[c] == AXW_COLD(eot) || step + 1 >= AXW_COLD(n_ctx) || n_out[c] >= mn)) fin[c] = true;
+        if (!fin[c]) { ++n_out[c]; tok[c] = best[c]; }
+        all_fin &= fin[c];
       }
+      if (all_fin) { n_done = NC; break; }
     }
   }
 
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): no LDS-DMA may still be in flight when the workgroup's LDS is released
-  if (PROF) {
-    __syncthreads();
-    if (tid < 64) AXW_COLD(prof)[(long)wg * 64 + tid] = prof_acc[tid];
-  }
+  AXW_PERSIST_DRAIN
   if (wg == 0 && tid == 0) {
     AXW_COLD(n_out)[0] = n_out[0];
 #pragma unroll
@@ -1002,47 +867,15 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     AXW_COLD(state)->step = steps_run;
     AXW_COLD(state)->n_done = n_done;
   }
-#undef AXW_SA0_COMP
-#undef AXW_COLD
-#undef AXW_BARRIER_CHECK
-#undef AXW_STAMP
 #undef AXW_TL
 }
 
 // ---------------------------------------------------------------------------------------- host side
-static size_t persist2_lds_bytes(int d, int nc) {
-  // the one-clip launch's LDS + per later clip its d-wide input vector, query (64 words), argmax scratch (32) and the
-  // self-attention k, v rows of its current step (64) + the poller waves' attention scratch
-  return (size_t)kKvBytes + ((size_t)4 * d + d / 8 + NCW * kPS + 2 * NPW + 64 + 16 + 16 + 16 + 64 + NCW * 64) * 4 + 64 * 8 + 64 +
-         ((size_t)(nc - 1) * (d + 64 + 32 + 64) + NPW * kPS + NPW * 64 + (size_t)nc * 68) * 4;  // (+ the query fold's 68 words per clip)
-}
-int decode_persistent_max_clips(int d_model, int n_head, int n_layer, int grid) {
-  // every linear layer must be ONE pass of rows per workgroup (a second pass overwrites the rows the next clip still
-  // needs): true up to d_model 768, not for 1280 (mlp.0: 20 rows per workgroup in passes of 16)
-  switch (d_model) { case 128: case 256: case 384: case 512: case 768: break; default: return 1; }
-  int nc = 1;
-  // every workgroup that owns no self-attention head takes at most ONE cross-attention unit (a clip's head and key range) per
-  // layer, and the later clips' vectors must fit what the K/V region leaves of the CU's 160 KB of LDS
-  while (nc < 3 && grid - n_layer * n_head >= (nc + 1) * kCrossSplit * n_head && persist2_lds_bytes(d_model, nc + 1) <= 160 * 1024) ++nc;
-  return nc;
-}
-
-template <int LD, int CD, int LF, int CF, int NC, bool PROF, bool QF>
-static hipError_t launch_multi_q(const PersistParams& p, int grid, hipStream_t s) {
-  const size_t lds = persist2_lds_bytes(8 * LD * CD, NC);
-  auto kfn = decode_persistent_kernel<LD, CD, LF, CF, PROF, NC, QF>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(PT), lds, s, p);
-  return hipGetLastError();
-}
+// (grid, supported shapes, clip count and granule area: decode_persistent.hip)
 template <int LD, int CD, int LF, int CF, int NC, bool PROF = false>
 static hipError_t launch_multi(const PersistParams& p, int grid, hipStream_t s) {  // the query fold where the engine built its arena
-  return p.qf ? launch_multi_q<LD, CD, LF, CF, NC, PROF, true>(p, grid, s) : launch_multi_q<LD, CD, LF, CF, NC, PROF, false>(p, grid, s);
-}
-template <int LD, int CD, int LF, int CF>
-static hipError_t launch_nc(const PersistParams& p, int grid, hipStream_t s) {
-  return p.n_clip == 2 ? launch_multi<LD, CD, LF, CF, 2>(p, grid, s) : launch_multi<LD, CD, LF, CF, 3>(p, grid, s);
+  return launch_persistent(p.qf ? decode_persistent_kernel<LD, CD, LF, CF, PROF, NC, true> : decode_persistent_kernel<LD, CD, LF, CF, PROF, NC, false>,
+                           8 * LD * CD, NC, p, grid, s);
 }
 
 hipError_t launch_decode_persistent2(const PersistParams& p, int d_model, int grid, hipStream_t s) {
@@ -1053,14 +886,11 @@ hipError_t launch_decode_persistent2(const PersistParams& p, int d_model, int gr
     if (d_model != 768) return hipErrorInvalidValue;
     return p.n_clip == 2 ? launch_multi<32, 3, 64, 6, 2, true>(p, grid, s) : launch_multi<32, 3, 64, 6, 3, true>(p, grid, s);
   }
-  switch (d_model) {
-    case 128: return launch_nc<16, 1, 32, 2>(p, grid, s);
-    case 256: return launch_nc<32, 1, 64, 2>(p, grid, s);
-    case 384: return launch_nc<16, 3, 64, 3>(p, grid, s);
-    case 512: return launch_nc<32, 2, 64, 4>(p, grid, s);
-    case 768: return launch_nc<32, 3, 64, 6>(p, grid, s);
-    default: return hipErrorInvalidValue;
-  }
+  return persist_dispatch(d_model, [&](auto sh) {
+    using S = decltype(sh);
+    if constexpr (S::D > 768) return hipErrorInvalidValue;  // one pass of rows per workgroup and layer (decode_persistent_max_clips)
+    else return p.n_clip == 2 ? launch_multi<S::LD, S::CD, S::LF, S::CF, 2>(p, grid, s) : launch_multi<S::LD, S::CD, S::LF, S::CF, 3>(p, grid, s);
+  });
 }
 
 }  // inline namespace AXW_NS

@@ -1,6 +1,7 @@
-// decode_persistent_common.hpp — device helpers shared by the persistent decode launches (decode_persistent.hip: one clip
-// per launch; decode_persistent2.hip: two clips per launch): lane-group reductions, {tag, value} granules and their polls,
-// weight-row sets with the one-instruction publish, the 64-key attention block, the partial merge.
+// decode_persistent_common.hpp — what the persistent decode launches share (decode_persistent.hip: one clip per launch;
+// decode_persistent2.hip: two or three clips per launch): lane-group reductions, {tag, value} granules and their polls,
+// weight-row sets with the one-instruction publish, the 64-key attention block, the partial merge, the kernels' common
+// prologue, and the host side's LDS size, shape table and launch.
 #pragma once
 #include "common.hpp"
 
@@ -602,6 +603,190 @@ __device__ __forceinline__ void qfold_publish(int lane, const float* pk, const f
     if (on) gput(Gc + o_y1 + r0 + lane, tag, pk[lane]);
   }
 }
+
+// ---------------------------------------------------------------------------------------- kernel prologue (both launches)
+// Macros, not functions: they name the kernel's own values (template arguments, tid, ctl, p, ...), and a helper that took
+// them as arguments was measured to move the register allocation of the production kernels.
+// The shapes: a poller lane owns PAIRS of adjacent vector elements: pair tid + j*PL (j < GPD) = elements 2*pair, 2*pair + 1;
+// the cross-attention partial records travel as pairs, split between the roles (NPP1 by the pollers, the rest by the compute
+// waves); NU cross-attention units per layer and clip. Granule buffers of a clip in u64 units: the statistics of row producer
+// p (query fold) at O_STAT + 16 p, + 1 — a line of its own (packed, 8 producers' partial-line stores per line: units gather
+// 0.4 us later, 108.7 -> 111.1 ms).
+#define AXW_PERSIST_SHAPES                                                                                                   \
+  constexpr int D = 8 * LD * CD, F = 8 * LF * CF, H = D / 64;                                                                \
+  static_assert(F == 4 * D, "mlp width");                                                                                    \
+  constexpr int GPD = (D / 2 + PL - 1) / PL, GD = 2 * GPD, NPART = H * kCrossSplit * kPS;                                    \
+  constexpr int NPP = NPART / 2, NPP1 = (NPP + 1) / 2, GP1 = (NPP1 + PL - 1) / PL, GP2 = (NPP - NPP1 + CT - 1) / CT;         \
+  static_assert(NPART % 2 == 0 && kPS % 2 == 0 && kRec % 2 == 0 && D % 2 == 0, "pair polls need even layouts");             \
+  constexpr int NU = kCrossSplit * H;                                                                                        \
+  constexpr int O_QKV = 0, O_ATT = 3 * D, O_Y1 = 4 * D, O_CQ = 5 * D, O_PART = 6 * D, O_Y2 = 10 * D, O_HID = 11 * D,          \
+                O_Y3 = 15 * D, O_AMAX = 16 * D, O_STAT = 16 * D + 512;                                                       \
+  static_assert(NPART <= 3 * D + D / 8 && NU * kRec <= 4 * D, "partial buffer");                                             \
+  static_assert(kCrossSplit * NCW == 24, "cross-attention key blocks");
+
+// The LDS both kernels carve the same way (persist_lds_bytes); QS_GAP: words between the LayerNorm sums and the query.
+//   sK [8 blk][8][64 keys][8] (blocked, lane = key); sV: cross tiles [512 keys][64], self-attention cache per block
+//   [8 (key/8)][64 dims][8 keys]; act [F + D/8]: input vector of the current rows phase; wpart [NCW][kPS]: per-wave attention
+//   partials; red [2*NPW]: LayerNorm partial sums; qs [64]: query of the attention phase as packed h16 pairs ([32] hi, [32] lo);
+//   am_v, am_i [16]: argmax scratch; ctl [16]: 0 give-up flag, 1 argmax of the step, 2.. LDS arrival counters; pk [64]: this
+//   workgroup's rows of the phase, assembled for the one-instruction publish; pscr [NCW][64]: probability transpose scratch;
+//   prof_acc [64]: per-phase time sums + one layer's absolute timeline (profiling runs only)
+#define AXW_PERSIST_LDS(QS_GAP)                                                                                              \
+  extern __shared__ __attribute__((aligned(16))) char smem[];                                                                \
+  h16* sK = reinterpret_cast<h16*>(smem);                                                                                    \
+  h16* sV = sK + NCW * 4096;                                                                                                 \
+  float* act = reinterpret_cast<float*>(smem + kKvBytes);                                                                    \
+  float* wpart = act + F + D / 8;                                                                                            \
+  float* red = wpart + NCW * kPS;                                                                                            \
+  unsigned* qs = reinterpret_cast<unsigned*>(red + 2 * NPW + QS_GAP);                                                        \
+  float* am_v = reinterpret_cast<float*>(qs) + 64;                                                                           \
+  int* am_i = reinterpret_cast<int*>(am_v + 16);                                                                             \
+  int* ctl = am_i + 16;                                                                                                      \
+  float* pk = reinterpret_cast<float*>(ctl + 16);                                                                            \
+  float* pscr = pk + 64;                                                                                                     \
+  long long* prof_acc = reinterpret_cast<long long*>(pscr + NCW * 64);
+
+// tid is re-derived behind an opaque asm at the top of every layer: without it the compiler hoists every per-thread address
+// of every phase out of the step loop and keeps >100 registers of loop invariants alive
+#define AXW_PERSIST_IDS                                                                                                      \
+  int tid = threadIdx.x;                                                                                                     \
+  const bool poller = tid < PL; /* wave-uniform */                                                                           \
+  const int P = gridDim.x, wg = blockIdx.x;                                                                                  \
+  const int L = p.n_layer;                                                                                                   \
+  u64* const G = p.gran;
+
+// Self-attention ownership: unit (l, h) -> workgroup P-1-(l*H+h); the other NS workgroups take the cross-attention units
+// (ca_unit_of). Producers of the d-row phases (one pass of CT/LD resp. CT/LF rows each): only they consume the attention
+// outputs / cross-attention partials / mlp hidden vector; every other workgroup skips those three phases altogether (no polls,
+// no barriers): a hand-off is the faster the fewer workgroups poll it (-5 % decode time). Row roles go by a ROTATED workgroup
+// index (rwg 0 = the first self-attention owner): the d-wide layers' producers are then workgroups that own a head (busy with
+// attention in one layer of twelve), not the ones that run a cross-attention unit in most layers — with several clips
+// interleaved, a producer that is also a unit holder puts one clip's rows behind the other clip's attention block.
+#define AXW_PERSIST_ROLES                                                                                                    \
+  const int sa_unit = P - 1 - wg;                                                                                            \
+  const int sa_layer = sa_unit < L * H ? sa_unit / H : -1, sa_head = sa_unit % H;                                            \
+  const int NS = P - L * H;                                                                                                  \
+  constexpr int NP_D = (D + CT / LD - 1) / (CT / LD), NP_F2 = (D + CT / LF - 1) / (CT / LF);                                 \
+  const int rwg = (wg - NS + P) % P;                                                                                         \
+  const bool in_o = rwg < NP_D, in_f2 = rwg < NP_F2;
+
+// The fault hook (AX_WHISPER_PERSIST_FAULT: a workgroup that never publishes; everybody else must give up and drain), the
+// zeroed K/V region (masked keys must be finite), the control words and the profile sums. Then kargs: launch parameters that
+// are read once per STEP or less (token feedback, teacher forcing, dumps, results) are not kept in scalar registers for the
+// whole launch; AXW_COLD re-reads them from the kernel-argument segment at their use, through a pointer the compiler cannot see
+// through (so it can neither hoist the loads out of the step loop nor keep their results live). The d_model-768 instantiation
+// was spilling 185 scalar registers into vector lanes.
+#define AXW_PERSIST_INIT                                                                                                     \
+  if (p.fault && wg == 0) return;                                                                                            \
+  for (int i = tid; i < kKvBytes / 16; i += PT) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};                   \
+  if (tid < 16) ctl[tid] = 0;                                                                                                \
+  if (PROF && tid < 64) prof_acc[tid] = 0;                                                                                   \
+  __syncthreads();                                                                                                           \
+  long long t_last = PROF ? wall_clock64() : 0;                                                                              \
+  const __attribute__((address_space(4))) PersistParams* kargs =                                                             \
+      (const __attribute__((address_space(4))) PersistParams*)__builtin_amdgcn_kernarg_segment_ptr();
+#define AXW_COLD(FIELD) ([&] { auto* kp_ = kargs; asm volatile("" : "+s"(kp_)); return kp_->FIELD; }())
+
+// profile stamps: pollers stamp slots 0..15 (thread 0), compute waves 16..31 (thread PL)
+#define AXW_STAMP(IDX) \
+  if (PROF && (tid == 0 || tid == PL)) { const long long t_now = wall_clock64(); prof_acc[IDX] += t_now - t_last; t_last = t_now; }
+// first barrier of a phase: everybody learns whether a poller gave up
+#define AXW_BARRIER_CHECK(CODE)                                                                                          \
+  {                                                                                                                      \
+    wg_barrier();                                                                                                        \
+    if (ctl[0]) {                                                                                                        \
+      if (tid == 0) __hip_atomic_store((gu32*)p.err, (unsigned)(CODE) | 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+      return;                                                                                                            \
+    }                                                                                                                    \
+  }
+
+// The pollers' per-register-slot helpers: el(k) = vector element of register slot k; g2_prefetch (QF, row producers): the
+// cross-attention LayerNorm's gain of the NEXT layer to run (A0 = W_cq (g . x0)), requested a stage ahead like lg / lb by
+// ln_prefetch — a polling wave must have no load in flight.
+#define AXW_POLLER_PREFETCH                                                                                                  \
+  auto el = [&](int k) { return 2 * (tid + (k >> 1) * PL) + (k & 1); };                                                     \
+  float g2[GD];                                                                                                              \
+  auto g2_prefetch = [&](int layer) {                                                                                        \
+    _Pragma("unroll") for (int k = 0; k < GD; ++k) {                                                                         \
+      const int i = el(k);                                                                                                   \
+      g2[k] = (QF && in_o && i < D) ? p.fl[(long)layer * DecArena::f_stride(D) + DecArena::F_CROSS_LN_W * D + i] : 0.f;      \
+    }                                                                                                                        \
+  };                                                                                                                         \
+  g2_prefetch(0);                                                                                                            \
+  auto ln_prefetch = [&](const float* g, const float* be) {                                                                  \
+    _Pragma("unroll") for (int k = 0; k < GD; ++k) {                                                                         \
+      const int i = el(k);                                                                                                   \
+      lg[k] = i < D ? g[i] : 0.f;                                                                                            \
+      lb[k] = i < D ? be[i] : 0.f;                                                                                           \
+    }                                                                                                                        \
+  };
+// a clip's residual stream at the start of a step: x = token_embedding[TOK] + positional_embedding[step] (export_onnx.py:334-336)
+#define AXW_EMBED(X, TOK)                                                                                                    \
+  _Pragma("unroll") for (int k = 0; k < GD; ++k) {                                                                           \
+    const int i = el(k);                                                                                                     \
+    X[k] = i < D ? (float)AXW_COLD(tok_emb)[(long)(TOK) * D + i] + AXW_COLD(pos)[(long)step * D + i] : 0.f;                 \
+  }
+// the end of a launch: no LDS-DMA may still be in flight when the workgroup's LDS is released (vmcnt(0)); the profile sums out
+#define AXW_PERSIST_DRAIN                                                                                                    \
+  __builtin_amdgcn_s_waitcnt(0x0F70);                                                                                        \
+  if (PROF) {                                                                                                                \
+    __syncthreads();                                                                                                         \
+    if (tid < 64) AXW_COLD(prof)[(long)wg * 64 + tid] = prof_acc[tid];                                                       \
+  }
+
+// Cross-attention unit of workgroup wg in the t-th layer of the LAUNCH (t = step * L + l), or -1; nu units per layer, ns
+// workgroups without a self-attention head. The units of consecutive layers take consecutive ranges of nu workgroups modulo
+// ns, counted over the whole launch and not per step: 2 * nu <= ns then keeps the two units of any workgroup at least two
+// layers apart across the step boundary as well. (Counted per step, the last layer's range wrapped onto the first layer's of
+// the next step whenever L * nu > ns — large-v3-turbo: 4 x 60 units on 176 workgroups — and a workgroup staged the next
+// step's K tiles over the ones its last-layer unit had not used yet: logits off by 4e-2 at every step of that model.)
+__device__ __forceinline__ int ca_unit_of(int t, int nu, int wg, int ns) {
+  if (wg >= ns) return -1;
+  int r = (wg - (int)(((long)t * nu) % ns)) % ns;
+  if (r < 0) r += ns;
+  return r < nu ? r : -1;
+}
+
+// ---------------------------------------------------------------------------------------- host side
+// LDS bytes of a launch with nc clips: the K/V region and the carve-up of both kernels (act [F + D/8], wpart, red, qs, am_v,
+// am_i, ctl, pk, pscr, prof_acc), then per layout: one clip keeps 4 words behind the LayerNorm sums (the stage's mean and
+// shift); several clips keep, per clip after the first, its d-wide input vector, query (64 words), argmax scratch (32) and the
+// self-attention k, v rows of its current step (64), then the poller waves' attention scratch and the query fold's 68 words
+// per clip
+inline size_t persist_lds_bytes(int d, int nc) {
+  const size_t common = (size_t)kKvBytes + ((size_t)4 * d + d / 8 + NCW * kPS + 2 * NPW + 64 + 16 + 16 + 16 + 64 + NCW * 64) * 4 + 64 * 8 + 64;
+  if (nc == 1) return common + 4 * 4;
+  return common + ((size_t)(nc - 1) * (d + 64 + 32 + 64) + NPW * kPS + NPW * 64 + (size_t)nc * 68) * 4;
+}
+
+// The supported shapes: d_model = 8*LD*CD (rows with K = d: LD lanes x CD 16-byte chunks), 4*d_model = 8*LF*CF.
+// fn(PersistShape<...>{}) for d_model, hipErrorInvalidValue for any other width.
+template <int LD_, int CD_, int LF_, int CF_>
+struct PersistShape { static constexpr int LD = LD_, CD = CD_, LF = LF_, CF = CF_, D = 8 * LD_ * CD_; };
+template <typename Fn>
+hipError_t persist_dispatch(int d_model, Fn&& fn) {
+  switch (d_model) {
+    case 128: return fn(PersistShape<16, 1, 32, 2>{});
+    case 256: return fn(PersistShape<32, 1, 64, 2>{});
+    case 384: return fn(PersistShape<16, 3, 64, 3>{});
+    case 512: return fn(PersistShape<32, 2, 64, 4>{});
+    case 768: return fn(PersistShape<32, 3, 64, 6>{});
+    case 1280: return fn(PersistShape<32, 5, 64, 10>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// one persistent kernel instantiation on `grid` workgroups with the LDS of nc clips
+inline hipError_t launch_persistent(void (*kfn)(PersistParams), int d, int nc, const PersistParams& p, int grid, hipStream_t s) {
+  const size_t lds = persist_lds_bytes(d, nc);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(PT), lds, s, p);
+  return hipGetLastError();
+}
+
+// two or three clips per launch (decode_persistent2.hip); launch_decode_persistent hands n_clip >= 2 on
+hipError_t launch_decode_persistent2(const PersistParams& p, int d_model, int grid, hipStream_t s);
 
 }  // inline namespace AXW_NS
 }  // namespace axw
