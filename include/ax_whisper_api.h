@@ -172,12 +172,34 @@ AX_WHISPER_API int AX_WHISPER_StreamStep(AX_WHISPER_HANDLE handle, int n_steps, 
 AX_WHISPER_API int AX_WHISPER_StreamCollect(AX_WHISPER_HANDLE handle, int slot, int32_t* ids, int* n_ids);
 AX_WHISPER_API int AX_WHISPER_StreamClose(AX_WHISPER_HANDLE handle);
 
+/* ---- segment timestamps (DESIGN.md "Segment timestamps")
+ * Timestamp mode feeds [sot, <language>, transcribe] (no <|notimestamps|>) and applies Whisper's timestamp rules on the GPU at
+ * every sampled step; ids then hold timestamp tokens: id timestamp_begin + k means k * 0.02 s, timestamp_begin =
+ * AX_WHISPER_GetConfigInt(h, "timestamp_begin"). Needs n_vocab - timestamp_begin == 1501 (else -1, AX_WHISPER_LastError). */
+/** RunPCMBatchTokens in timestamp mode; max_new_clip: optional [batch] per-clip budgets (<= 0: none), may be NULL. Sharded
+ *  over the handle's devices. ids: host [batch][n_text_ctx]. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampTokens(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                         int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids);
+/** DecodeForced in timestamp mode over the slots EncodeMel filled: logits (may be NULL) = the raw logits before the rules,
+ *  [batch][n_forced+1][n_vocab]; chosen = the id the rules pick at each step, [batch][n_forced+1]. */
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestamps(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
+                                                     float* logits, int32_t* chosen);
+/** The rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] with n_hist[b] sampled ids of clip b
+ *  (prefix excluded) -> chosen [batch]. */
+AX_WHISPER_API int AX_WHISPER_ApplyTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                                  int batch, int32_t* chosen);
+/** Host only (no handle, no GPU): one clip's ids (eot excluded) -> at most n_max segments [start[k], end[k]] in seconds, text ids
+ *  ids[tok_begin[k] .. tok_end[k]) (Transcript of that range is the segment's text); *n_seg = segments written.
+ *  clip_seconds = min(num_samples / 16000, 30). n_max = n / 2 + 1 always suffices. */
+AX_WHISPER_API int AX_WHISPER_SplitSegments(const int32_t* ids, int n, int timestamp_begin, int eot, float clip_seconds, int n_max,
+                                            float* start, float* end, int* tok_begin, int* tok_end, int* n_seg);
+
 /** Stage timings of the last Run* / DecodeGreedy* call, ms (hipEvent): [0] front-end, [1] encoder,
  *  [2] decode loop, [3] whole call (wall), [4] decode steps executed. */
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
 /** Time `iters` launches of one named piece on the handle's stream with hipEvents; returns
  *  total ms in *ms_total. what: "decode_step" (one captured step graph at decode offset
- *  `arg`), "encoder", "frontend", or a kernel name listed in DESIGN.md. */
+ *  `arg`), "decode_step_ts" (the same step in timestamp mode), "encoder", "frontend", or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);
 

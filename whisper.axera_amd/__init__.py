@@ -64,6 +64,10 @@ SYMBOLS = {
     "AX_WHISPER_StreamClose": (C.c_int, [C.c_void_p]),
     "AX_WHISPER_GetTimings": (C.c_int, [C.c_void_p, fp]),
     "AX_WHISPER_Bench": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, fp]),
+    "AX_WHISPER_RunPCMBatchTimestampTokens": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]),
+    "AX_WHISPER_DecodeForcedTimestamps": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, fp, ip]),
+    "AX_WHISPER_ApplyTimestampRules": (C.c_int, [C.c_void_p, fp, ip, C.POINTER(C.c_int), C.c_int, ip]),
+    "AX_WHISPER_SplitSegments": (C.c_int, [ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 
@@ -125,6 +129,22 @@ def detokenize_with_table(tokens_path: str, ids) -> bytes:
     return b
 
 
+def split_segments(ids, timestamp_begin: int, eot: int, clip_seconds: float):
+    """One clip's timestamp-mode ids (eot excluded) -> [(start_s, end_s, tok_begin, tok_end)] (AX_WHISPER_SplitSegments, host
+    only): ids[tok_begin:tok_end] are the segment's text ids."""
+    L = load_library()
+    a = np.ascontiguousarray(ids, dtype=np.int32)
+    n_max = len(a) // 2 + 1
+    st, en = np.zeros(n_max, dtype=np.float32), np.zeros(n_max, dtype=np.float32)
+    tb, te = np.zeros(n_max, dtype=np.int32), np.zeros(n_max, dtype=np.int32)
+    n = C.c_int()
+    pi = C.POINTER(C.c_int)
+    if L.AX_WHISPER_SplitSegments(a.ctypes.data_as(ip), len(a), int(timestamp_begin), int(eot), float(clip_seconds), n_max,
+                                  st.ctypes.data_as(fp), en.ctypes.data_as(fp), tb.ctypes.data_as(pi), te.ctypes.data_as(pi), C.byref(n)) != 0:
+        raise RuntimeError("AX_WHISPER_SplitSegments failed")
+    return [(float(st[k]), float(en[k]), int(tb[k]), int(te[k])) for k in range(n.value)]
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -149,6 +169,7 @@ class Whisper:
         self.n_mels, self.n_vocab, self.n_text_ctx = g("n_mels"), g("n_vocab"), g("n_text_ctx")
         self.n_text_layer, self.n_text_state, self.eot = g("n_text_layer"), g("n_text_state"), g("eot")
         self.sot_seq = [g(f"sot_seq{i}") for i in range(4)]
+        self.timestamp_begin = g("timestamp_begin")
         self.n_devices = self.L.AX_WHISPER_GetDeviceCount(self.h)
 
     def close(self):
@@ -196,6 +217,56 @@ class Whisper:
 
     def run_tokens(self, pcm, max_new: int = 0):
         return self.run_tokens_batch([pcm], max_new)[0]
+
+    # ---- segment timestamps (timestamp mode: prefix [sot, lang, transcribe], Whisper's timestamp rules on the GPU)
+    def run_timestamp_tokens_batch(self, clips, max_new: int = 0, max_new_clip=None):
+        """ids per clip, timestamp tokens included (AX_WHISPER_RunPCMBatchTimestampTokens)."""
+        clips = [_f32(c) for c in clips]
+        B = len(clips)
+        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
+        lens = (C.c_int * B)(*[len(c) for c in clips])
+        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        n = (C.c_int * B)()
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampTokens(self.h, ptrs, lens, B, max_new, mc, ids.ctypes.data_as(ip), n),
+                    "RunPCMBatchTimestampTokens")
+        return [ids[b, : n[b]].tolist() for b in range(B)]
+
+    def segments(self, ids, num_samples: int):
+        """[(start_s, end_s, text)] of one clip's timestamp-mode ids."""
+        clip_s = min(num_samples / 16000.0, 30.0)
+        return [(s, e, self.transcript(ids[tb:te])) for s, e, tb, te in split_segments(ids, self.timestamp_begin, self.eot, clip_s)]
+
+    def run_timestamps(self, audio, max_new: int = 0):
+        """PCM (16 kHz mono f32) -> [(start_s, end_s, text)], one entry per segment."""
+        a = _f32(audio)
+        return self.segments(self.run_timestamp_tokens_batch([a], max_new)[0], len(a))
+
+    def decode_forced_timestamps(self, batch: int, forced, want_logits: bool = True):
+        """Teacher-forced timestamp-mode decode of the EncodeMel slots -> (raw logits [batch][n+1][n_vocab] or None,
+        chosen [batch][n+1]: the ids the rules pick at each step)."""
+        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
+        n = f.shape[1]
+        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
+        ch = np.empty((batch, n + 1), dtype=np.int32)
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestamps(self.h, batch, f.ctypes.data_as(ip), n,
+                                                             logits.ctypes.data_as(fp) if want_logits else None, ch.ctypes.data_as(ip)),
+                    "DecodeForcedTimestamps")
+        return logits, ch
+
+    def apply_timestamp_rules(self, logits, histories):
+        """The rules kernel alone: logits [batch][n_vocab], one id history per clip -> chosen id per clip."""
+        lg = _f32(logits).reshape(-1, self.n_vocab)
+        B = lg.shape[0]
+        hist = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        nh = (C.c_int * B)()
+        for b, h in enumerate(histories):
+            hist[b, : len(h)] = h
+            nh[b] = len(h)
+        out = np.zeros(B, dtype=np.int32)
+        self._check(self.L.AX_WHISPER_ApplyTimestampRules(self.h, lg.ctypes.data_as(fp), hist.ctypes.data_as(ip), nh, B,
+                                                           out.ctypes.data_as(ip)), "ApplyTimestampRules")
+        return out.tolist()
 
     def run_batch(self, clips):
         clips = [_f32(c) for c in clips]

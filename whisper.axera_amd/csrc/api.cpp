@@ -242,6 +242,14 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTokens(AX_WHISPER_HANDLE handle, const 
   });
 }
 
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampTokens(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                         int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
+  if (!handle || !pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    g.run_tokens_mode(Engine::kDecodeTimestamps, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids);
+  });
+}
+
 AX_WHISPER_API int AX_WHISPER_RunDeviceBatchTokens(AX_WHISPER_HANDLE handle, const float* d_pcm, int stride,
                                                    const int* num_samples, int batch, int max_new, int32_t* ids, int* n_ids) {
   if (!handle || !d_pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
@@ -412,6 +420,60 @@ AX_WHISPER_API int AX_WHISPER_DecodeForced(AX_WHISPER_HANDLE handle, int batch, 
                                            float* logits, int32_t* argmax_ids) {
   if (!handle || (n_forced > 0 && !forced)) return -1;
   return guarded(handle, [&](Engine& e) { e.decode_forced(batch, forced, n_forced, logits, argmax_ids); });
+}
+
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestamps(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
+                                                     float* logits, int32_t* chosen) {
+  if (!handle || (n_forced > 0 && !forced)) return -1;
+  return guarded(handle, [&](Engine& e) { e.decode_forced_mode(Engine::kDecodeTimestamps, batch, forced, n_forced, logits, chosen); });
+}
+
+AX_WHISPER_API int AX_WHISPER_ApplyTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                                  int batch, int32_t* chosen) {
+  if (!handle || !logits || !hist || !n_hist || !chosen || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.apply_timestamp_rules(logits, hist, n_hist, batch, chosen); });
+}
+
+// Host only: one clip's ids (eot excluded) -> segments (DESIGN.md "Segment timestamps": openai-whisper's single-window split,
+// plus the tail rule). Any ids are accepted; the result never exceeds n_max entries.
+AX_WHISPER_API int AX_WHISPER_SplitSegments(const int32_t* ids, int n, int timestamp_begin, int eot, float clip_seconds, int n_max,
+                                            float* start, float* end, int* tok_begin, int* tok_end, int* n_seg) {
+  if ((n > 0 && !ids) || n < 0 || !n_seg || n_max < 0 || (n_max > 0 && (!start || !end || !tok_begin || !tok_end))) return -1;
+  *n_seg = 0;
+  const int T = timestamp_begin;
+  auto ts = [&](int i) { return ids[i] >= T; };
+  auto time = [&](int i) { return (float)(ids[i] - T) * 0.02f; };
+  int count = 0;
+  // [lo, hi): a segment's slice; its text ids are the ids < eot
+  auto emit = [&](int lo, int hi, float t0, float t1) {
+    int tb = -1, te = -1;
+    for (int i = lo; i < hi; ++i)
+      if (ids[i] < eot) { if (tb < 0) tb = i; te = i + 1; }
+    if (tb < 0 || count >= n_max) return;  // no text: dropped
+    start[count] = t0; end[count] = t1; tok_begin[count] = tb; tok_end[count] = te;
+    ++count;
+  };
+  std::vector<int> bounds;
+  for (int i = 1; i < n; ++i)
+    if (ts(i - 1) && ts(i)) bounds.push_back(i);
+  if (!bounds.empty()) {
+    if (n >= 2 && ts(n - 1) && !ts(n - 2)) bounds.push_back(n);
+    int prev = 0;
+    float prev_end = 0.f;
+    for (int b : bounds) {
+      prev_end = time(b - 1);
+      emit(prev, b, time(prev), prev_end);
+      prev = b;
+    }
+    if (prev < n) emit(prev, n, ts(prev) ? time(prev) : prev_end, clip_seconds);  // the tail: one window keeps it
+  } else {
+    int last = -1;
+    for (int i = 0; i < n; ++i)
+      if (ts(i)) last = i;
+    emit(0, n, 0.f, (last >= 0 && ids[last] != T) ? time(last) : clip_seconds);
+  }
+  *n_seg = count;
+  return 0;
 }
 
 AX_WHISPER_API int AX_WHISPER_DecodeGreedy(AX_WHISPER_HANDLE handle, int batch, int max_new, int32_t* ids, int* n_ids) {

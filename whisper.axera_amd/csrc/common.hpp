@@ -405,8 +405,23 @@ struct AdvanceParams {
   const int* forced; int n_forced;   // teacher forcing (device [B][n_forced]) or nullptr
   int* argmax_dump;           // optional [B][n_forced+1]
   const h16* tok_emb; const float* pos; float* x; int d_model;  // fused embedding of the next step
+  int n_prefix;               // prefix tokens fed before the first sampled step (sot[0 .. n_prefix)); 0 means 4
 };
 void launch_advance(const AdvanceParams& p, hipStream_t s);
+
+// ---- timestamp rules (decode_timestamps.hip): one argmax partial per clip that samples at this step, chosen under
+// Whisper's timestamp rules from the clip's dumped logits row and its history
+struct TsRulesParams {
+  const float* logits; long stride;  // fp32 rows [batch][stride], stride a multiple of 4
+  int batch, n_vocab, eot, ts_begin;  // ts_begin = no_timestamps + 1: id of 0.00 s
+  const int* off;                    // device [batch] or nullptr (every clip samples); clips with off < n_prefix - 1 are skipped
+  int n_prefix;
+  const int* done;                   // device [batch] or nullptr: finished clips are skipped
+  const int* out_ids; const int* n_out; int n_ctx;   // greedy history: [batch][n_ctx] ids, [batch] counts
+  const int* forced; int n_forced;   // teacher-forced history [batch][n_forced] (n = off - n_prefix + 1), or nullptr
+  float* amax_val; int* amax_idx; int amax_stride;   // out: partial 0 of clip b at b * amax_stride
+};
+void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s);
 
 // ---- persistent decode (decode_persistent.hip, decode_persistent2.hip): the whole greedy loop of one to three clips in ONE launch
 typedef unsigned long long u64;

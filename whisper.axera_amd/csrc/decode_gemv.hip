@@ -486,7 +486,7 @@ void launch_gemv(const GemvParams& p, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------- advance
-// Whisper.cpp:207-222: steps 0..2 feed the next SOT token and drop the logits; from step 3 on the
+// Whisper.cpp:207-222: steps 0..n_prefix-2 feed the next SOT token and drop the logits; from step n_prefix-1 (3) on the
 // argmax is either the stop condition (eot / context full) or the next recorded + fed token.
 // One wave per clip merges the per-workgroup argmax partials (first max wins); 16 clips per workgroup. Every clip
 // advances its OWN offset (the reference decodes one utterance at a time and stops it at its own eot,
@@ -510,6 +510,7 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
   }
   if (b >= p.batch) return;
   const int s = p.off[b];  // this clip's offset: the position that was fed in this step
+  const int n_pre = p.n_prefix > 0 ? p.n_prefix : 4;  // [sot, lang, transcribe, notimestamps] unless timestamps are decoded
   constexpr int MAXJ = 8;  // d_model <= 2048: lane l owns elements 4l + 256j
   const int d = p.d_model;
   // x of every slot is re-seeded every step, finished slots included (their rows of the linear layers keep running and
@@ -528,7 +529,7 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
   bool advance = !done_b;  // a finished (or idle) slot keeps its offset: its cache row and position stay in bounds for good
   if (done_b) {
     // nothing: the slot waits for Engine::stream_admit or the end of the batch
-  } else if (s < 3) {
+  } else if (s < n_pre - 1) {
     tok = p.sot[s + 1];
     if (lane == 0) p.tok[b] = tok;
   } else {
@@ -546,7 +547,7 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
     // no logit compared greater than -inf (all NaN / -inf: non-finite audio): std::max_element returns index 0
     // (Whisper.cpp:42-45); never let the "no candidate" index reach the embedding lookup below
     if ((unsigned)idx >= (unsigned)p.n_vocab) idx = 0;
-    const int gi = s - 3;
+    const int gi = s - (n_pre - 1);
     if (p.forced) {
       if (gi < p.n_forced) tok = p.forced[(long)b * p.n_forced + gi];
     } else {

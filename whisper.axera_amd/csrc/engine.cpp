@@ -248,6 +248,7 @@ void Engine::load_config(const std::string& dir, const std::string& type, const 
   sot_seq_[2] = cfg_.transcribe;
   sot_seq_[3] = cfg_.no_timestamps;
   for (int i = 0; i < 4; ++i) cfg_.ints["sot_seq" + std::to_string(i)] = sot_seq_[i];
+  cfg_.ints["timestamp_begin"] = cfg_.no_timestamps + 1;  // id of the 0.00 s timestamp (timestamp mode)
 }
 
 // Slaney mel filterbank, arithmetic as librosa.h:102-144 (fp32), stored transposed [201][n_mels].
@@ -524,6 +525,7 @@ void Engine::free_slot_buffers() {
   graphs_.clear();
   for (void* p : slot_allocs_) (void)hipFree(p);
   slot_allocs_.clear();
+  d_ts_logits_ = nullptr;  // (one of slot_allocs_)
   if (h_pcm_) { (void)hipHostFree(h_pcm_); h_pcm_ = nullptr; }
   cap_ = 0;
 }
@@ -799,8 +801,15 @@ void Engine::run_encoder(int batch, const int* d_slot_map) {
 // ------------------------------------------------------------------------------ public entry points
 void Engine::run_tokens(const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
                         int32_t* ids, int* n_ids, const int* max_new_clip) {
+  run_tokens_mode(kDecodePlain, pcm, d_pcm, d_stride, n_samples, batch, max_new, ids, n_ids, max_new_clip);
+}
+
+void Engine::run_tokens_mode(int mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
+                             int max_new, int32_t* ids, int* n_ids, const int* max_new_clip) {
   if (batch < 1) throw std::runtime_error("batch must be >= 1");
   require_no_stream("run_tokens");
+  if (mode == kDecodeTimestamps) require_timestamp_vocab();
+  TsModeScope ts(ts_mode_, mode == kDecodeTimestamps ? 1 : 0);
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   ensure_capacity(batch);
@@ -904,11 +913,20 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
 }
 
 void Engine::decode_forced(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) {
+  decode_forced_mode(kDecodePlain, batch, forced, n_forced, logits, argmax_ids);
+}
+
+void Engine::decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) {
   require_no_stream("decode_forced");
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_forced: batch exceeds the encoded slots");
-  if (n_forced < 0 || n_forced + 4 > cfg_.n_text_ctx) throw std::runtime_error("decode_forced: n_forced out of range");
+  const bool tsm = mode == kDecodeTimestamps;
+  const int n_prefix = tsm ? 3 : 4;
+  if (n_forced < 0 || n_forced + n_prefix > cfg_.n_text_ctx) throw std::runtime_error("decode_forced: n_forced out of range");
+  if (tsm) require_timestamp_vocab();
+  TsModeScope ts(ts_mode_, tsm ? 1 : 0);
+  if (tsm) ensure_ts_logits();
   hipStream_t s = stream();
   const int nv = cfg_.n_vocab, rows = n_forced + 1;
   // device scratch of this call, freed on every path out (a HIP_CHECK below may throw)
@@ -924,16 +942,19 @@ void Engine::decode_forced(int batch, const int32_t* forced, int n_forced, float
   float* d_logits = (float*)b_logits.p;
   if (n_forced) HIP_CHECK(hipMemcpy(d_forced, forced, (size_t)batch * n_forced * 4, hipMemcpyHostToDevice));
   bool done = false;
-  if (batch == 1 && persistent_usable()) {
+  if (batch == 1 && !tsm && persistent_usable()) {
     if (run_persistent(cfg_.n_text_ctx, d_forced, n_forced, d_logits, d_arg) >= 0) { done = true; persistent_succeeded(); }
     else persistent_gave_up();
   }
   if (!done) reset_decode_state(batch);
   if (!done) ensure_branch_streams(batch);
-  for (int st = 0; !done && st < 4 + n_forced; ++st) {
-    const int gi = st - 3;
+  for (int st = 0; !done && st < n_prefix + n_forced; ++st) {
+    const int gi = st - (n_prefix - 1);
     float* lrow = (d_logits && gi >= 0) ? d_logits + (size_t)gi * nv : nullptr;
     enqueue_decode_step(batch, cfg_.n_text_ctx, d_forced, n_forced, lrow, (long)rows * nv, d_arg);
+    // timestamp mode: the step dumped its rows into d_ts_logits_ (16-byte row stride) for the rules kernel
+    if (tsm && lrow) HIP_CHECK(hipMemcpy2DAsync(lrow, (size_t)rows * nv * 4, d_ts_logits_, (size_t)ts_stride_ * 4, (size_t)nv * 4, batch,
+                                                hipMemcpyDeviceToDevice, s));
   }
   HIP_CHECK(hipStreamSynchronize(s));
   if (logits) HIP_CHECK(hipMemcpy(logits, d_logits, (size_t)batch * rows * nv * 4, hipMemcpyDeviceToHost));
@@ -941,7 +962,13 @@ void Engine::decode_forced(int batch, const int32_t* forced, int n_forced, float
 }
 
 void Engine::decode_greedy(int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
+  decode_greedy_mode(kDecodePlain, batch, max_new, max_new_clip, ids, n_ids);
+}
+
+void Engine::decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
   require_no_stream("decode_greedy");
+  if (mode == kDecodeTimestamps) require_timestamp_vocab();
+  TsModeScope ts(ts_mode_, mode == kDecodeTimestamps ? 1 : 0);
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_greedy: batch exceeds the encoded slots");
   hipStream_t s = stream();
@@ -954,6 +981,42 @@ void Engine::decode_greedy(int batch, int max_new, const int* max_new_clip, int3
   (void)hipEventElapsedTime(&timings[2], ev_[2], ev_[3]);
   timings[3] = timings[2];
   timings[4] = (float)steps;
+}
+
+// The rules kernel alone, on host rows and histories (tests; callers with logits of their own)
+void Engine::apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) {
+  require_no_stream("apply_timestamp_rules");
+  require_timestamp_vocab();
+  if (batch < 1 || !logits || !hist || !n_hist || !chosen) throw std::runtime_error("apply_timestamp_rules: bad arguments");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  hipStream_t s = stream();
+  const int nv = cfg_.n_vocab, Tc = cfg_.n_text_ctx;
+  const long stride = ((long)nv + 3) / 4 * 4;
+  for (int b = 0; b < batch; ++b)
+    if (n_hist[b] < 0 || n_hist[b] > Tc) throw std::runtime_error("apply_timestamp_rules: n_hist out of range");
+  struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+  } b_log, b_hist, b_n, b_val, b_idx;
+  HIP_CHECK(hipMalloc(&b_log.p, (size_t)batch * stride * 4));
+  HIP_CHECK(hipMalloc(&b_hist.p, (size_t)batch * Tc * 4));
+  HIP_CHECK(hipMalloc(&b_n.p, (size_t)batch * 4));
+  HIP_CHECK(hipMalloc(&b_val.p, (size_t)batch * 4));
+  HIP_CHECK(hipMalloc(&b_idx.p, (size_t)batch * 4));
+  HIP_CHECK(hipMemcpy2DAsync(b_log.p, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_hist.p, hist, (size_t)batch * Tc * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_n.p, n_hist, (size_t)batch * 4, hipMemcpyHostToDevice, s));
+  TsRulesParams r{};
+  r.logits = (const float*)b_log.p; r.stride = stride; r.batch = batch;
+  r.n_vocab = nv; r.eot = cfg_.eot; r.ts_begin = cfg_.no_timestamps + 1;
+  r.off = nullptr; r.n_prefix = 3; r.done = nullptr;
+  r.out_ids = (const int*)b_hist.p; r.n_out = (const int*)b_n.p; r.n_ctx = Tc;
+  r.amax_val = (float*)b_val.p; r.amax_idx = (int*)b_idx.p; r.amax_stride = 1;
+  launch_timestamp_rules(r, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(chosen, b_idx.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
 }
 
 }  // inline namespace AXW_NS

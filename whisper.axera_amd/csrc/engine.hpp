@@ -42,6 +42,11 @@ class Engine final : public IEngine {
   int stream_step(int n_steps, int* finished_slots) override;
   void stream_collect(int slot, int32_t* ids, int* n_ids) override;
   void stream_close() override;
+  void run_tokens_mode(int mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
+                       int32_t* ids, int* n_ids, const int* max_new_clip) override;
+  void decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) override;
+  void decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
+  void apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) override;
   int scan_stored16(int batch, int n_max, char (*names)[32], long long* nonfinite, float* maxabs) override;
   float bench(const std::string& what, int batch, int arg, int iters) override;
   void set_stream(void* s) override { user_stream_ = static_cast<hipStream_t>(s); }
@@ -79,6 +84,19 @@ class Engine final : public IEngine {
   int decode_branches(int batch) const;
   void ensure_branch_streams(int batch);
   hipGraphExec_t step_graph(int batch, int max_new);
+  long graph_key(int batch, int max_new) const { return ((((long)batch * 1024 + max_new) * 32 + step_mask_) << 1) | ts_mode_; }
+  // timestamp mode (DecodeMode): set for the duration of one *_mode call; the step sequences read it
+  int ts_mode_ = 0;
+  struct TsModeScope {
+    int& m;
+    TsModeScope(int& mm, int v) : m(mm) { m = v; }
+    ~TsModeScope() { m = 0; }
+  };
+  void require_timestamp_vocab() const;
+  void ensure_ts_logits();  // d_ts_logits_ [cap][ts_stride_], allocated on first use under device_capture_mutex
+  void enqueue_timestamp_rules(int batch, const int* d_forced, int n_forced, hipStream_t s);
+  float* d_ts_logits_ = nullptr;
+  long ts_stride_ = 0;
   void recover_streams();
   int greedy_loop(int batch, int max_new, const int* max_new_clip = nullptr);
   // batch 1: the whole loop as one persistent launch (decode_persistent.hip); returns steps run, -1 if it gave up

@@ -106,13 +106,17 @@ void Engine::enqueue_decode_step(int batch, int max_new, const int* d_forced, in
   p.W = tok_emb_; p.bias = nullptr; p.N = cfg_.n_vocab; p.K = d;
   p.prologue = PRO_LAYERNORM; p.in = d_xdec_; p.ln_w = dec_ln_w_; p.ln_b = dec_ln_b_;
   p.epilogue = GEPI_LOGITS; p.state = d_state_; p.off = d_off_; p.amax_val = d_amax_val_; p.amax_idx = d_amax_idx_; p.amax_stride = n_amax_part_;
-  p.skip_before_step = 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
+  // timestamp mode: the launch also runs at the step that fed `transcribe` and dumps every row for the rules kernel
+  if (ts_mode_) { d_logits = d_ts_logits_; logits_stride = ts_stride_; }
+  p.skip_before_step = ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
   gemv(p, [&](GemvParams& q, int b0) {
     q.in += (long)b0 * d; q.amax_val += (long)b0 * n_amax_part_; q.amax_idx += (long)b0 * n_amax_part_; q.off += b0;
     if (q.logits_dump) q.logits_dump += (long)b0 * logits_stride;
   });
+  if (ts_mode_ && (step_mask_ & 4)) enqueue_timestamp_rules(batch, d_forced, n_forced, s);
   AdvanceParams a{};
-  a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = gemv_grid(p); a.amax_stride = n_amax_part_;
+  a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = ts_mode_ ? 1 : gemv_grid(p); a.amax_stride = n_amax_part_;
+  a.n_prefix = ts_mode_ ? 3 : 0;
   a.state = d_state_; a.off = d_off_; a.tok = d_tok_; a.done = d_done_; a.n_out = d_nout_; a.out_ids = d_out_ids_; a.batch = batch;
   a.n_ctx = Tc; a.eot = cfg_.eot; a.max_new = max_new; a.n_vocab = cfg_.n_vocab; a.max_new_clip = d_max_new_clip_; a.sot = d_sot_;
   a.forced = d_forced; a.n_forced = n_forced; a.argmax_dump = d_argmax;
@@ -407,13 +411,16 @@ void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_fo
   const int vocab_rt = decode_logits_resident_ok(d, batch) ? 0 : logits_rt();
   p.rt = vocab_rt;
   p.amax_val = d_amax_val_; p.amax_idx = d_amax_idx_; p.amax_stride = n_amax_part_;
-  p.skip_before_step = 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
+  if (ts_mode_) { d_logits = d_ts_logits_; logits_stride = ts_stride_; }  // (as in enqueue_decode_step)
+  p.skip_before_step = ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
   gemm(p, [&](DecGemmParams& q, int b0) {
     q.amax_val += (long)b0 * n_amax_part_; q.amax_idx += (long)b0 * n_amax_part_;
     if (q.logits_dump) q.logits_dump += (long)b0 * logits_stride;
   });
+  if (ts_mode_ && (step_mask_ & 4)) enqueue_timestamp_rules(batch, d_forced, n_forced, s);
   AdvanceParams a{};
-  a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = decode_gemm_grid(cfg_.n_vocab, vocab_rt); a.amax_stride = n_amax_part_;
+  a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = ts_mode_ ? 1 : decode_gemm_grid(cfg_.n_vocab, vocab_rt); a.amax_stride = n_amax_part_;
+  a.n_prefix = ts_mode_ ? 3 : 0;
   a.state = d_state_; a.off = d_off_; a.tok = d_tok_; a.done = d_done_; a.n_out = d_nout_; a.out_ids = d_out_ids_; a.batch = batch;
   a.n_ctx = Tc; a.eot = cfg_.eot; a.max_new = max_new; a.n_vocab = cfg_.n_vocab; a.max_new_clip = d_max_new_clip_; a.sot = d_sot_;
   a.forced = d_forced; a.n_forced = n_forced; a.argmax_dump = d_argmax;
@@ -473,7 +480,7 @@ void Engine::ensure_branch_streams(int batch) {
 }
 
 hipGraphExec_t Engine::step_graph(int batch, int max_new) {
-  const long key = ((long)batch * 1024 + max_new) * 32 + step_mask_;
+  const long key = graph_key(batch, max_new);  // plain and timestamp-mode steps are different graphs
   auto it = graphs_.find(key);
   if (it != graphs_.end()) return it->second;
   hipStream_t s = stream();
@@ -481,6 +488,7 @@ hipGraphExec_t Engine::step_graph(int batch, int max_new) {
   // nobody on this device allocates, copies synchronously or captures while this capture is open (iengine.hpp)
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   ensure_branch_streams(batch);  // before the capture opens
+  if (ts_mode_) ensure_ts_logits();
   HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   hipError_t cap_err = hipSuccess;
   try {
@@ -537,13 +545,15 @@ hipGraphExec_t Engine::step_graph(int batch, int max_new) {
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.
 int Engine::greedy_loop(int batch, int max_new, const int* max_new_clip) {
   const int Tc = cfg_.n_text_ctx;
-  if (max_new <= 0 || max_new > Tc - 4) max_new = Tc - 4;
+  const int n_prefix = ts_mode_ ? 3 : 4;  // timestamp mode: no <|notimestamps|>, one more id fits the context
+  if (max_new <= 0 || max_new > Tc - n_prefix) max_new = Tc - n_prefix;
   // One clip: the persistent launch. Two or three clips: ONE multi-clip persistent launch, phase by phase (one clip's rows are
   // computed while the others' hand-offs are in flight; decode_persistent2.hip) — Whisper-small, 444 ids per clip: 134 ms per
   // pair against 2 x 116 ms for one launch per clip (shapes without a multi-clip launch, AX_WHISPER_PERSIST2=0) and 316 ms through
   // the launch-per-phase path. Each clip stops at its own eot / budget.
   // (asked ONCE per request: persistent_usable() counts a back-off down)
-  const bool usable = batch <= std::max(2, persist_max_clips_) && persistent_usable();
+  // (timestamp mode: the launch-per-phase step only — the persistent launches carry no timestamp rules)
+  const bool usable = !ts_mode_ && batch <= std::max(2, persist_max_clips_) && persistent_usable();
   if (usable && batch >= 2 && batch <= persist_max_clips_) {
     int mn[3] = {max_new, -1, -1};
     for (int b = 0; b < batch; ++b) mn[b] = (max_new_clip && max_new_clip[b] > 0) ? std::min(max_new, max_new_clip[b]) : max_new;
@@ -658,6 +668,34 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
     return -1;
   }
   return h_poll_[9];
+}
+
+// ------------------------------------------------------------------------------ timestamp mode
+void Engine::require_timestamp_vocab() const {
+  const int T = cfg_.no_timestamps + 1;
+  if (cfg_.n_vocab - T != 1501 || T <= cfg_.eot)
+    throw std::runtime_error("timestamp mode needs 1501 timestamp ids after <|notimestamps|> (n_vocab " + std::to_string(cfg_.n_vocab) +
+                             ", no_timestamps " + std::to_string(cfg_.no_timestamps) + ")");
+}
+
+void Engine::ensure_ts_logits() {
+  if (d_ts_logits_) return;
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  ts_stride_ = ((long)cfg_.n_vocab + 3) / 4 * 4;  // 16-byte rows for the rules kernel's loads
+  d_ts_logits_ = (float*)dalloc((size_t)cap_ * ts_stride_ * 4, true);
+  slot_allocs_.push_back(d_ts_logits_);  // freed (and re-made at the new capacity) with the other slot buffers
+}
+
+// Between the logits launch and advance_kernel: one argmax partial per sampling clip, chosen under the timestamp rules
+void Engine::enqueue_timestamp_rules(int batch, const int* d_forced, int n_forced, hipStream_t s) {
+  TsRulesParams r{};
+  r.logits = d_ts_logits_; r.stride = ts_stride_; r.batch = batch;
+  r.n_vocab = cfg_.n_vocab; r.eot = cfg_.eot; r.ts_begin = cfg_.no_timestamps + 1;
+  r.off = d_off_; r.n_prefix = 3; r.done = d_forced ? nullptr : d_done_;
+  r.out_ids = d_out_ids_; r.n_out = d_nout_; r.n_ctx = cfg_.n_text_ctx;
+  r.forced = d_forced; r.n_forced = n_forced;
+  r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
+  launch_timestamp_rules(r, s);
 }
 
 void Engine::fetch_ids(int batch, int32_t* ids, int* n_ids) {

@@ -314,10 +314,13 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   HIP_CHECK(hipEventCreate(&a));
   HIP_CHECK(hipEventCreate(&b));
   float ms = 0.f;
-  if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn") {
-    // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches
-    step_mask_ = what == "decode_step" ? 15 : (what == "decode_gemv" ? 1 : 2);
+  if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn" || what == "decode_step_ts") {
+    // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;
+    // decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel)
+    step_mask_ = (what == "decode_step" || what == "decode_step_ts") ? 15 : (what == "decode_gemv" ? 1 : 2);
     struct Restore { int& m; ~Restore() { m = 15; } } restore{step_mask_};
+    if (what == "decode_step_ts") require_timestamp_vocab();
+    TsModeScope ts(ts_mode_, what == "decode_step_ts" ? 1 : 0);
     const int Tc = cfg_.n_text_ctx;
     reset_decode_state(batch);
     hipGraphExec_t g = step_graph(batch, Tc - 4);
@@ -351,7 +354,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
     struct Restore { int& m; ~Restore() { m = 15; } } restore{step_mask_};
     const int Tc = cfg_.n_text_ctx;
     reset_decode_state(batch);
-    const long key = ((long)batch * 1024 + (Tc - 4)) * 32 + step_mask_;
+    const long key = graph_key(batch, Tc - 4);
     auto old = graphs_.find(key);
     if (old != graphs_.end()) { (void)hipGraphExecDestroy(old->second); graphs_.erase(old); }
     stamp_meta_.clear();

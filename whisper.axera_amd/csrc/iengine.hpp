@@ -48,6 +48,17 @@ class IEngine {
   // every 16-bit tensor the engine STORES between kernels (encoder activations of `batch` clips, cross / self K/V caches, the
   // decoder's activation pairs): non-finite count and max |x| per buffer; returns the number of buffers reported (<= n_max)
   virtual int scan_stored16(int batch, int n_max, char (*names)[32], long long* nonfinite, float* maxabs) = 0;
+  // decode modes of the *_mode variants: kDecodePlain = the calls above (prefix [sot, lang, transcribe, notimestamps]),
+  // kDecodeTimestamps = prefix [sot, lang, transcribe] and Whisper's timestamp rules at every sampled step (DESIGN.md
+  // "Segment timestamps"); ids then include timestamp tokens
+  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1 };
+  virtual void run_tokens_mode(int mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
+                               int max_new, int32_t* ids, int* n_ids, const int* max_new_clip) = 0;
+  // timestamp mode: logits are the raw logits (before the rules), argmax_ids the ids the rules choose
+  virtual void decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) = 0;
+  virtual void decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
+  // the rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] (n_hist[b] ids each) -> chosen [batch]
+  virtual void apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) = 0;
   virtual float bench(const std::string& what, int batch, int arg, int iters) = 0;
   virtual void set_stream(void* hip_stream) = 0;
   virtual const ModelConfig& config() const = 0;

@@ -91,6 +91,20 @@ class DeviceGroup {
     });
   }
 
+  // The same sharding for E::run_tokens_mode (a decode mode, optional per-clip budgets max_new_clip [batch]).
+  void run_tokens_mode(int mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int n_ctx,
+                       int32_t* ids, int* n_ids) {
+    if (batch < 1) throw std::runtime_error("batch must be >= 1");
+    const int G = size(), world = G < batch ? G : batch;
+    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
+    run_sharded(batch, world, [&](int w, int lo, int hi) {
+      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
+      std::lock_guard<std::mutex> lock(e.mutex());
+      e.run_tokens_mode(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, ids + (size_t)lo * n_ctx, n_ids + lo,
+                        max_new_clip ? max_new_clip + lo : nullptr);
+    });
+  }
+
  private:
   std::vector<std::unique_ptr<E>> engines_;
   std::atomic<unsigned> next_{0};

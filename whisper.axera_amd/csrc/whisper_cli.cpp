@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "ax_whisper_api.h"
 
@@ -21,6 +22,7 @@ static void usage(const char* prog) {
           "  -t, --model_type    tiny, base, small, turbo, large (string [=turbo])\n"
           "  -p, --model_path    model path which contains tiny/ base/ small/ turbo/ (string [=../models-mi355x])\n"
           "      --language      en, zh (string [=zh])\n"
+          "      --timestamps    after Result:, one line per segment: [mm:ss.mmm --> mm:ss.mmm] text\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -71,8 +73,45 @@ static bool wav_frames(const char* path, long* frames) {
   }
 }
 
+static std::string mmss(float t) {
+  const long ms = (long)(t * 1000.f + 0.5f);
+  char b[32];
+  snprintf(b, sizeof b, "%02ld:%02ld.%03ld", ms / 60000, (ms / 1000) % 60, ms % 1000);
+  return b;
+}
+
+// --timestamps: the clip decoded again in timestamp mode, split into segments (AX_WHISPER_SplitSegments), one line each
+static int print_segments(AX_WHISPER_HANDLE h, const char* wav) {
+  float* pcm = nullptr;
+  int n = 0;
+  if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
+  const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx");
+  std::vector<int32_t> ids(n_ctx > 0 ? n_ctx : 448);
+  int n_ids = 0;
+  const float* clips[1] = {pcm};
+  const int rc = AX_WHISPER_RunPCMBatchTimestampTokens(h, clips, &n, 1, 0, nullptr, ids.data(), &n_ids);
+  free(pcm);
+  if (rc != 0) return -1;
+  const float clip_s = n / 16000.f < 30.f ? n / 16000.f : 30.f;
+  const int n_max = n_ids / 2 + 1;
+  std::vector<float> st(n_max), en(n_max);
+  std::vector<int> tb(n_max), te(n_max);
+  int n_seg = 0;
+  if (AX_WHISPER_SplitSegments(ids.data(), n_ids, AX_WHISPER_GetConfigInt(h, "timestamp_begin"), AX_WHISPER_GetConfigInt(h, "eot"), clip_s,
+                               n_max, st.data(), en.data(), tb.data(), te.data(), &n_seg) != 0)
+    return -1;
+  for (int k = 0; k < n_seg; ++k) {
+    char* text = nullptr;
+    if (AX_WHISPER_Transcript(h, ids.data() + tb[k], te[k] - tb[k], &text) != 0) return -1;
+    printf("[%s --> %s] %s\n", mmss(st[k]).c_str(), mmss(en[k]).c_str(), text ? text : "");
+    free(text);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
+  bool timestamps = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -89,6 +128,7 @@ int main(int argc, char** argv) {
         val("language", nullptr, language))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
+    if (a == "--timestamps") { timestamps = true; continue; }
     fprintf(stderr, "undefined option: %s\n", a.c_str());
     usage(argv[0]);
     return 1;
@@ -119,7 +159,14 @@ int main(int argc, char** argv) {
   }
   t1 = std::chrono::steady_clock::now();
   printf("Result: %s\n", result);
-  printf("RTF: %.4f\n", std::chrono::duration<double>(t1 - t0).count() / duration);
+  const double rtf = std::chrono::duration<double>(t1 - t0).count() / duration;  // of AX_WHISPER_RunFile alone
+  if (timestamps && print_segments(handle, wav.c_str()) != 0) {
+    printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
+    free(result);
+    AX_WHISPER_Uninit(handle);
+    return -1;
+  }
+  printf("RTF: %.4f\n", rtf);
   free(result);
   AX_WHISPER_Uninit(handle);
   return 0;
