@@ -194,12 +194,44 @@ AX_WHISPER_API int AX_WHISPER_ApplyTimestampRules(AX_WHISPER_HANDLE handle, cons
 AX_WHISPER_API int AX_WHISPER_SplitSegments(const int32_t* ids, int n, int timestamp_begin, int eot, float clip_seconds, int n_max,
                                             float* start, float* end, int* tok_begin, int* tok_end, int* n_seg);
 
+/* ---- long-form: audio longer than 30 s (DESIGN.md "Long-form")
+ * The file's log-mel is computed once over the whole file (reflect pad at the file's two ends, one maximum over all of its
+ * frames) and kept in HBM; the window at `seek` (frames of 10 ms) is frames [seek, seek + 3000) of it, zero past the file's last
+ * frame. The loop: while seek < num_samples / 160, decode the window in timestamp mode (every window starts fresh: no
+ * conditioning on earlier text), cut it with the window rule, seek += advance. One pass decodes the current window of every
+ * unfinished file side by side, in slots 0..A-1; more files than the handle's slots (max_batch of Init) wait for a place.
+ * AX_WHISPER_FEATURE_MODE=openai has no long-form meaning: these calls refuse it. The PCM and log-mel stores of a call are
+ * capped at AX_WHISPER_LONG_MAX_BYTES (default 4 GiB); a call beyond it returns -1 (AX_WHISPER_LastError). */
+/** Host only (no handle, no GPU): the window rule. One window's ids (eot excluded), window_frames = min(3000, num_samples / 160 -
+ *  seek) -> at most n_max segments (start / end in seconds relative to the window, text ids ids[tok_begin[k] .. tok_end[k]) as in
+ *  SplitSegments) and *advance, the frames the next window starts later (1 .. window_frames). Consecutive timestamp pairs close
+ *  segments; ids after the last pair belong to no segment (the next window decodes that audio again); an advance <= 0 (a pair
+ *  closing at 0.00 s) becomes window_frames. n_max = n / 2 + 1 always suffices. */
+AX_WHISPER_API int AX_WHISPER_SplitWindow(const int32_t* ids, int n, int timestamp_begin, int eot, int window_frames, int n_max,
+                                          float* start, float* end, int* tok_begin, int* tok_end, int* n_seg, int* advance);
+/** Stage level: whole-file front-end + window kernel for one file. mel_out: host [n_mels*3000] f32; seek 0 is bit-equal to
+ *  AX_WHISPER_ComputeMel of the same input. */
+AX_WHISPER_API int AX_WHISPER_ComputeMelWindow(AX_WHISPER_HANDLE handle, const float* pcm, int num_samples, int seek, float* mel_out);
+/** The loop over n_files files; returns the raw log of every decoded window. Window k: win_info[k*7 .. k*7+6] = file index, seek,
+ *  window_frames, advance, n_ids, pass, encoder slot; ids[k*n_text_ctx ..] = its n_ids ids (all of them, also those after the last
+ *  boundary). max_new: per-window id budget (<= 0: until eot or the context end). max_passes (<= 0: none) stops after that many
+ *  passes: the call returns 0 with the windows decoded so far, and slot s still holds the cross K/V of the last pass's window
+ *  in slot s (AX_WHISPER_GetCrossKV). win_cap: windows the two arrays can take; too small -> -1 with the needed count in the
+ *  error text and nothing written. With several devices the files are split in contiguous blocks, one per engine: the log holds
+ *  the first engine's windows first, pass and slot are the engine's own. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                int max_new, int max_passes, int win_cap, int* win_info, int32_t* ids, int* n_windows);
+/** Text of a whole file: the transcripts of the loop's segments, concatenated (zh post-pass as in Transcript). *result malloc'd. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLong(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, char** result);
+AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result);
+
 /** Stage timings of the last Run* / DecodeGreedy* call, ms (hipEvent): [0] front-end, [1] encoder,
  *  [2] decode loop, [3] whole call (wall), [4] decode steps executed. */
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
 /** Time `iters` launches of one named piece on the handle's stream with hipEvents; returns
  *  total ms in *ms_total. what: "decode_step" (one captured step graph at decode offset
- *  `arg`), "decode_step_ts" (the same step in timestamp mode), "encoder", "frontend", or a kernel name listed in DESIGN.md. */
+ *  `arg`), "decode_step_ts" (the same step in timestamp mode), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
+ *  files of `arg` seconds + one window kernel), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);
 

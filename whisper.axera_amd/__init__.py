@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import time
 import subprocess
 
@@ -68,6 +69,11 @@ SYMBOLS = {
     "AX_WHISPER_DecodeForcedTimestamps": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, fp, ip]),
     "AX_WHISPER_ApplyTimestampRules": (C.c_int, [C.c_void_p, fp, ip, C.POINTER(C.c_int), C.c_int, ip]),
     "AX_WHISPER_SplitSegments": (C.c_int, [ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_SplitWindow": (C.c_int, [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_ComputeMelWindow": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_int, fp]),
+    "AX_WHISPER_RunPCMLongWindows": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLong": (C.c_int, [C.c_void_p, fp, C.c_int, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunFileLong": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
 }
 
 
@@ -143,6 +149,23 @@ def split_segments(ids, timestamp_begin: int, eot: int, clip_seconds: float):
                                   st.ctypes.data_as(fp), en.ctypes.data_as(fp), tb.ctypes.data_as(pi), te.ctypes.data_as(pi), C.byref(n)) != 0:
         raise RuntimeError("AX_WHISPER_SplitSegments failed")
     return [(float(st[k]), float(en[k]), int(tb[k]), int(te[k])) for k in range(n.value)]
+
+
+def split_window(ids, timestamp_begin: int, eot: int, window_frames: int):
+    """The long-form window rule (AX_WHISPER_SplitWindow, host only): one window's ids (eot excluded) ->
+    ([(start_s, end_s, tok_begin, tok_end)] relative to the window, advance in frames of 10 ms)."""
+    L = load_library()
+    a = np.ascontiguousarray(ids, dtype=np.int32)
+    n_max = len(a) // 2 + 1
+    st, en = np.zeros(n_max, dtype=np.float32), np.zeros(n_max, dtype=np.float32)
+    tb, te = np.zeros(n_max, dtype=np.int32), np.zeros(n_max, dtype=np.int32)
+    n, adv = C.c_int(), C.c_int()
+    pi = C.POINTER(C.c_int)
+    if L.AX_WHISPER_SplitWindow(a.ctypes.data_as(ip), len(a), int(timestamp_begin), int(eot), int(window_frames), n_max,
+                                st.ctypes.data_as(fp), en.ctypes.data_as(fp), tb.ctypes.data_as(pi), te.ctypes.data_as(pi),
+                                C.byref(n), C.byref(adv)) != 0:
+        raise RuntimeError("AX_WHISPER_SplitWindow failed")
+    return [(float(st[k]), float(en[k]), int(tb[k]), int(te[k])) for k in range(n.value)], adv.value
 
 
 def _f32(a):
@@ -241,6 +264,62 @@ class Whisper:
         """PCM (16 kHz mono f32) -> [(start_s, end_s, text)], one entry per segment."""
         a = _f32(audio)
         return self.segments(self.run_timestamp_tokens_batch([a], max_new)[0], len(a))
+
+    # ---- long-form: audio longer than 30 s, seek over 30 s windows on the segment timestamps
+    def compute_mel_window(self, pcm, seek: int) -> np.ndarray:
+        """Whole-file front-end + window kernel: the [n_mels][3000] window at `seek` (frames of 10 ms) of one file."""
+        a = _f32(pcm)
+        out = np.empty((self.n_mels, 3000), dtype=np.float32)
+        self._check(self.L.AX_WHISPER_ComputeMelWindow(self.h, a.ctypes.data_as(fp), len(a), int(seek), out.ctypes.data_as(fp)), "ComputeMelWindow")
+        return out
+
+    def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0):
+        """The seek loop over `files` (PCM arrays), one window of every unfinished file per pass. Per file, the list of its
+        decoded windows (seek, window_frames, advance, ids, pass, slot) in order. max_new: id budget per window;
+        max_passes > 0 stops after that many passes (the slots then hold the last pass's cross K/V)."""
+        files = [_f32(f) for f in files]
+        n = len(files)
+        ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
+        lens = (C.c_int * n)(*[len(f) for f in files])
+        # room for every window advancing fully, twice over; a call that decodes more says how many, and is repeated
+        cap = sum(len(f) // 160 // 3000 + 2 for f in files) * 2
+        while True:
+            info = np.zeros((cap, 7), dtype=np.int32)
+            ids = np.zeros((cap, self.n_text_ctx), dtype=np.int32)
+            nw = C.c_int()
+            rc = self.L.AX_WHISPER_RunPCMLongWindows(self.h, ptrs, lens, n, int(max_new), int(max_passes), cap,
+                                                     info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip), C.byref(nw))
+            if rc != 0:
+                msg = (self.L.AX_WHISPER_LastError(self.h) or b"").decode()
+                need = re.search(r"(\d+) windows were decoded, win_cap is", msg)
+                if need:
+                    cap = int(need.group(1))
+                    continue
+                raise RuntimeError("RunPCMLongWindows failed: " + msg)
+            break
+        out = [[] for _ in range(n)]
+        for k in range(nw.value):
+            f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
+            out[f].append((seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot))
+        return out
+
+    def run_long(self, audio, max_new: int = 0):
+        """PCM (16 kHz mono f32) of any length -> [(start_s, end_s, text)] with absolute times, one entry per segment."""
+        out = []
+        for seek, wf, _adv, ids, _p, _s in self.run_long_windows([audio], max_new)[0]:
+            for s, e, tb, te in split_window(ids, self.timestamp_begin, self.eot, wf)[0]:
+                out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te])))
+        return out
+
+    def run_long_text(self, audio) -> str:
+        """PCM or a wav path of any length -> the whole text (AX_WHISPER_RunPCMLong / RunFileLong)."""
+        out = C.c_void_p()
+        if isinstance(audio, (str, os.PathLike)):
+            self._check(self.L.AX_WHISPER_RunFileLong(self.h, os.fspath(audio).encode(), C.byref(out)), "RunFileLong")
+        else:
+            a = _f32(audio)
+            self._check(self.L.AX_WHISPER_RunPCMLong(self.h, a.ctypes.data_as(fp), len(a), C.byref(out)), "RunPCMLong")
+        return self._take(out.value)
 
     def decode_forced_timestamps(self, batch: int, forced, want_logits: bool = True):
         """Teacher-forced timestamp-mode decode of the EncodeMel slots -> (raw logits [batch][n+1][n_vocab] or None,

@@ -10,6 +10,7 @@
 // the reference's t2s.json + .ocd2 dictionaries are found; AX_WHISPER_Detokenize returns the raw bytes.
 #include "../../include/ax_whisper_api.h"
 
+#include <algorithm>
 #include <climits>
 #include <cstdlib>
 #include <cstring>
@@ -214,23 +215,29 @@ AX_WHISPER_API int AX_WHISPER_RunPCM(AX_WHISPER_HANDLE handle, float* pcm_data, 
   return AX_WHISPER_RunPCMBatch(handle, &pcm_data, &num_samples, 1, result);
 }
 
-AX_WHISPER_API int AX_WHISPER_RunFile(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
+// the file decode of RunFile / RunFileLong: false (and the handle's error text set) when the file cannot be used
+static bool load_wav_for_run(AX_WHISPER_HANDLE handle, const char* wav_file, axw::WavData& wav) {
   std::string err;
   if (!axw::load_audio_file(wav_file, wav, err)) {
     H(handle)->set_error("load wav failed: " + err);
     fprintf(stderr, "[ax_whisper] load wav failed: %s\n", err.c_str());
-    return -1;
+    return false;
   }
   if (wav.mono.empty()) {
     H(handle)->set_error("wav file holds no samples");
-    return -1;
+    return false;
   }
   if (wav.sample_rate != 16000)  // the reference silently mis-transcribes (no resampler anywhere in its C++)
     fprintf(stderr, "[ax_whisper] warning: %s is %d Hz, expected 16000 Hz (see cpp/resample_wav.sh of the reference)\n",
             wav_file, wav.sample_rate);
+  return true;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFile(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
   return AX_WHISPER_RunPCM(handle, wav.mono.data(), (int)wav.mono.size(), result);
 }
 
@@ -474,6 +481,82 @@ AX_WHISPER_API int AX_WHISPER_SplitSegments(const int32_t* ids, int n, int times
   }
   *n_seg = count;
   return 0;
+}
+
+// ---- long-form (DESIGN.md "Long-form")
+// Host only: the window rule of the seek loop (longform.hpp). Any ids are accepted; at most n_max segments are written.
+AX_WHISPER_API int AX_WHISPER_SplitWindow(const int32_t* ids, int n, int timestamp_begin, int eot, int window_frames, int n_max,
+                                          float* start, float* end, int* tok_begin, int* tok_end, int* n_seg, int* advance) {
+  if ((n > 0 && !ids) || n < 0 || !n_seg || !advance || n_max < 0 || (n_max > 0 && (!start || !end || !tok_begin || !tok_end))) return -1;
+  *n_seg = 0;
+  *advance = 0;
+  try {
+    std::vector<axw::WindowSegment> segs;
+    *advance = axw::split_window(ids, n, timestamp_begin, eot, window_frames, segs);
+    const int count = (int)std::min<size_t>(segs.size(), (size_t)n_max);
+    for (int k = 0; k < count; ++k) {
+      start[k] = segs[k].start; end[k] = segs[k].end; tok_begin[k] = segs[k].tok_begin; tok_end[k] = segs[k].tok_end;
+    }
+    *n_seg = count;
+    return 0;
+  } catch (...) {
+    return -1;
+  }
+}
+
+AX_WHISPER_API int AX_WHISPER_ComputeMelWindow(AX_WHISPER_HANDLE handle, const float* pcm, int num_samples, int seek, float* mel_out) {
+  if (!handle || !pcm || !mel_out || num_samples < 1 || seek < 0) return -1;
+  return guarded(handle, [&](Engine& e) { e.compute_mel_window(pcm, num_samples, seek, mel_out); });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                int max_new, int max_passes, int win_cap, int* win_info, int32_t* ids, int* n_windows) {
+  if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids))) return -1;
+  for (int b = 0; b < n_files; ++b)
+    if (!pcm[b] || num_samples[b] < 1) return -1;
+  *n_windows = 0;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    std::vector<axw::LongWindow> log;
+    g.run_long_windows(pcm, num_samples, n_files, max_new, max_passes, log);
+    // nothing is written unless everything fits
+    if ((long)log.size() > win_cap)
+      throw std::runtime_error("RunPCMLongWindows: " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
+    const int Tc = g.primary().config().n_text_ctx;
+    for (size_t k = 0; k < log.size(); ++k) {
+      const axw::LongWindow& w = log[k];
+      const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
+      memcpy(win_info + k * 7, row, sizeof row);
+      memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
+    }
+    *n_windows = (int)log.size();
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLong(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, char** result) {
+  if (!handle || !pcm_data || !result || num_samples < 1) return -1;
+  *result = nullptr;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    Engine& e = g.primary();
+    std::vector<axw::LongWindow> log;
+    const float* files[1] = {pcm_data};
+    g.run_long_windows(files, &num_samples, 1, 0, 0, log);
+    const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
+    std::string text;
+    std::vector<axw::WindowSegment> segs;
+    for (const axw::LongWindow& w : log) {
+      axw::split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
+      for (const axw::WindowSegment& sg : segs) text += e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);  // host only
+    }
+    *result = strdup(text.c_str());
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return AX_WHISPER_RunPCMLong(handle, wav.mono.data(), (int)wav.mono.size(), result);
 }
 
 AX_WHISPER_API int AX_WHISPER_DecodeGreedy(AX_WHISPER_HANDLE handle, int batch, int max_new, int32_t* ids, int* n_ids) {

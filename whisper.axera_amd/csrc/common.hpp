@@ -248,6 +248,29 @@ struct FrontendParams {
 void launch_frontend(const FrontendParams& p, hipStream_t s);
 void launch_mel_to_tm(const float* mel_ref, h16* mel_tm, int batch, int n_mels, int mel_rows, hipStream_t s);
 
+// long-form (DESIGN "Long-form"): the front-end over whole files. FrontendParams carries pcm (the base the offsets below count
+// from), n_samples / gmax [n_files], batch = n_files, max_frames = frames of the longest file, the constants; stride, logmel,
+// mel_*, overflow and openai are not read.
+struct LongStoreParams {
+  const long long* pcm_off;    // device [n_files]: file b's samples are pcm[pcm_off[b] ...]
+  const long long* frame_off;  // device [n_files]: file b's rows are store[frame_off[b] ...]
+  float* store;                // device [sum of 1 + n_samples / 160][n_mels] fp32 log-mel, before clamp and scale
+};
+void launch_frontend_long(const FrontendParams& p, const LongStoreParams& ls, hipStream_t s);
+// window a of a pass = rows [win_seek[a], win_seek[a] + 3000) of file win_file[a] -> encoder slot a
+struct MelWindowParams {
+  const float* store;
+  const long long* frame_off;  // device [n_files]
+  const int* n_frames;         // device [n_files]: rows the file has in the store
+  const unsigned* gmax;        // device [n_files] (ordered-int encoded, as FrontendParams::gmax)
+  const int* win_file;         // device [n_windows]
+  const int* win_seek;         // device [n_windows], 0 <= seek
+  h16* mel_tm;                 // device [n_windows][mel_rows][n_mels] or nullptr
+  float* mel_ref;              // device [n_windows][n_mels][3000] or nullptr
+  int mel_rows, n_mels, n_windows;
+};
+void launch_mel_window(const MelWindowParams& p, hipStream_t s);
+
 // ------------------------------------------------------------------ decoder
 struct DecState {          // device-resident loop state, one per engine
   int step;                // decoder steps run since the last reset (bookkeeping; no kernel derives a position from it)

@@ -164,6 +164,7 @@ void Engine::destroy() {
   allocs_.clear();
   if (load_stage_) { (void)hipFree(load_stage_); load_stage_ = nullptr; }
   if (d_over_) { (void)hipFree(d_over_); d_over_ = nullptr; over_cap_ = 0; }
+  free_long_arena();
   if (h_poll_) { (void)hipHostFree(h_poll_); h_poll_ = nullptr; }
   for (auto& e : ev_) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   for (auto& e : ev_join_) if (e) { (void)hipEventDestroy(e); e = nullptr; }

@@ -47,6 +47,9 @@ class Engine final : public IEngine {
   void decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) override;
   void decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
   void apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) override;
+  void compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) override;
+  void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                        std::vector<LongWindow>& log) override;
   int scan_stored16(int batch, int n_max, char (*names)[32], long long* nonfinite, float* maxabs) override;
   float bench(const std::string& what, int batch, int arg, int iters) override;
   void set_stream(void* s) override { user_stream_ = static_cast<hipStream_t>(s); }
@@ -98,6 +101,21 @@ class Engine final : public IEngine {
   float* d_ts_logits_ = nullptr;
   long ts_stride_ = 0;
   void recover_streams();
+  // long-form (engine_long.cpp): the PCM and the log-mel rows of every file of one call in one arena, kept for the next call
+  // when small (allocated and freed under device_capture_mutex)
+  struct LongArena {
+    char* base = nullptr; size_t bytes = 0;
+    float *pcm = nullptr, *store = nullptr;
+    long long *pcm_off = nullptr, *frame_off = nullptr;
+    int *n_samples = nullptr, *n_frames = nullptr, *win_file = nullptr, *win_seek = nullptr;
+    unsigned* gmax = nullptr;
+    int n_files = 0, n_windows = 0;
+  } long_;
+  int* h_long_win_ = nullptr; int h_long_win_cap_ = 0;  // pinned [2][windows per pass]: file and seek of every slot
+  void long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows);  // upload + whole-file front-end
+  void long_windows_to_slots(const int* files, const int* seeks, int count, bool want_ref_layout);
+  void long_release();
+  void free_long_arena();
   int greedy_loop(int batch, int max_new, const int* max_new_clip = nullptr);
   // batch 1: the whole loop as one persistent launch (decode_persistent.hip); returns steps run, -1 if it gave up
   int run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot = 0, int max_new1 = -1, int max_new2 = -1);

@@ -1,0 +1,200 @@
+// engine_long.cpp — long-form transcription (DESIGN.md "Long-form"): the log-mel of whole files kept in HBM, and the seek loop
+// that decodes one 30 s window of every unfinished file per pass through the batched encoder and the timestamp-mode step graph.
+#include "engine_impl.hpp"
+
+namespace axw {
+inline namespace AXW_NS {
+
+// bytes the PCM and the log-mel rows of one call may take (AX_WHISPER_LONG_MAX_BYTES; default 4 GiB = about 9 hours of audio
+// at 80 mels): a call beyond it is refused with this text instead of failing somewhere in hipMalloc
+static size_t long_max_bytes() {
+  const char* e = getenv("AX_WHISPER_LONG_MAX_BYTES");
+  const long long v = e ? atoll(e) : 0;
+  return v > 0 ? (size_t)v : (size_t)4 << 30;
+}
+static constexpr size_t kLongKeepBytes = (size_t)256 << 20;  // an arena up to this size stays allocated for the next call
+
+void Engine::free_long_arena() {
+  if (long_.base) (void)hipFree(long_.base);
+  long_ = LongArena{};
+  if (h_long_win_) { (void)hipHostFree(h_long_win_); h_long_win_ = nullptr; h_long_win_cap_ = 0; }
+}
+
+void Engine::long_release() {
+  if (long_.bytes <= kLongKeepBytes) return;
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  free_long_arena();
+}
+
+// pcm == nullptr: n_files files of silence (bench)
+void Engine::long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows) {
+  if (feature_openai_)
+    throw std::runtime_error("long-form needs the default front-end: AX_WHISPER_FEATURE_MODE=openai trims the input to 30 s before the STFT");
+  if (cfg_.n_mels % 8 != 0) throw std::runtime_error("long-form needs n_mels to be a multiple of 8");
+  const int nm = cfg_.n_mels;
+  std::vector<long long> pcm_off(n_files), frame_off(n_files);
+  std::vector<int> nf(n_files);
+  size_t samples = 0, frames = 0;
+  int max_frames = 1;
+  for (int b = 0; b < n_files; ++b) {
+    if (n_samples[b] < 1) throw std::runtime_error("file " + std::to_string(b) + ": empty audio");
+    if (n_samples[b] > (1 << 29)) throw std::runtime_error("file " + std::to_string(b) + ": more than 2^29 samples");
+    if (pcm) {
+      unsigned bad = 0;
+      for (int i = 0; i < n_samples[b]; ++i) bad |= !std::isfinite(pcm[b][i]);
+      if (bad) throw std::runtime_error("file " + std::to_string(b) + ": non-finite PCM sample (NaN or Inf)");
+    }
+    pcm_off[b] = (long long)samples;
+    frame_off[b] = (long long)frames;
+    nf[b] = 1 + n_samples[b] / kHop;
+    samples += ((size_t)n_samples[b] + 3) & ~(size_t)3;  // every file starts on a 16-byte boundary
+    frames += (size_t)nf[b];
+    max_frames = std::max(max_frames, nf[b]);
+  }
+  // arena: [pcm | store | pcm_off | frame_off | n_samples | n_frames | gmax | win_file | win_seek], pieces 256-byte aligned
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t o = 0;
+  const size_t o_pcm = o; o += up(samples * 4);
+  const size_t o_store = o; o += up(frames * nm * 4);
+  const size_t o_poff = o; o += up((size_t)n_files * 8);
+  const size_t o_foff = o; o += up((size_t)n_files * 8);
+  const size_t o_ns = o; o += up((size_t)n_files * 4);
+  const size_t o_nf = o; o += up((size_t)n_files * 4);
+  const size_t o_gmax = o; o += up((size_t)n_files * 4);
+  const size_t o_wf = o; o += up((size_t)n_windows * 4);
+  const size_t o_ws = o; o += up((size_t)n_windows * 4);
+  if (o > long_max_bytes())
+    throw std::runtime_error("long-form: the PCM and log-mel stores of this call need " + std::to_string(o) + " bytes, the cap is " +
+                             std::to_string(long_max_bytes()) + " (AX_WHISPER_LONG_MAX_BYTES)");
+  // allocation and synchronous copies: not beside another handle's stream capture (iengine.hpp)
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipStreamSynchronize(stream()));  // an earlier call on this stream may still read the arena
+  if (o > long_.bytes) {
+    free_long_arena();
+    HIP_CHECK(hipMalloc((void**)&long_.base, o));
+    long_.bytes = o;
+  }
+  if (n_windows > h_long_win_cap_) {
+    if (h_long_win_) { (void)hipHostFree(h_long_win_); h_long_win_ = nullptr; h_long_win_cap_ = 0; }
+    HIP_CHECK(hipHostMalloc((void**)&h_long_win_, (size_t)2 * n_windows * 4, hipHostMallocDefault));
+    h_long_win_cap_ = n_windows;
+  }
+  char* a = long_.base;
+  long_.pcm = (float*)(a + o_pcm); long_.store = (float*)(a + o_store);
+  long_.pcm_off = (long long*)(a + o_poff); long_.frame_off = (long long*)(a + o_foff);
+  long_.n_samples = (int*)(a + o_ns); long_.n_frames = (int*)(a + o_nf); long_.gmax = (unsigned*)(a + o_gmax);
+  long_.win_file = (int*)(a + o_wf); long_.win_seek = (int*)(a + o_ws);
+  long_.n_files = n_files; long_.n_windows = n_windows;
+  for (int b = 0; b < n_files; ++b) {
+    if (pcm) HIP_CHECK(hipMemcpy(long_.pcm + pcm_off[b], pcm[b], (size_t)n_samples[b] * 4, hipMemcpyHostToDevice));
+    else HIP_CHECK(hipMemset(long_.pcm + pcm_off[b], 0, (size_t)n_samples[b] * 4));
+  }
+  HIP_CHECK(hipMemcpy(long_.pcm_off, pcm_off.data(), (size_t)n_files * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(long_.frame_off, frame_off.data(), (size_t)n_files * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(long_.n_samples, n_samples, (size_t)n_files * 4, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(long_.n_frames, nf.data(), (size_t)n_files * 4, hipMemcpyHostToDevice));
+  HIP_CHECK(hipDeviceSynchronize());  // (the engine's streams are not ordered against the null stream)
+  FrontendParams p{};
+  p.pcm = long_.pcm; p.n_samples = long_.n_samples; p.batch = n_files; p.n_mels = nm;
+  p.twiddle = twiddle_; p.window = window_; p.mel_basis = mel_basis_t_;
+  p.gmax = long_.gmax; p.max_frames = max_frames;
+  LongStoreParams ls{long_.pcm_off, long_.frame_off, long_.store};
+  launch_frontend_long(p, ls, stream());
+}
+
+// window i of this pass = file files[i] at seeks[i] -> encoder slot i. The caller waits for the stream before the next pass
+// (fetch_ids), so one pinned staging buffer serves every pass.
+void Engine::long_windows_to_slots(const int* files, const int* seeks, int count, bool want_ref_layout) {
+  if (count < 1 || count > long_.n_windows || count > cap_) throw std::runtime_error("long-form: bad window count");
+  for (int i = 0; i < count; ++i)
+    if (files[i] < 0 || files[i] >= long_.n_files || seeks[i] < 0) throw std::runtime_error("long-form: bad window");
+  memcpy(h_long_win_, files, (size_t)count * 4);
+  memcpy(h_long_win_ + count, seeks, (size_t)count * 4);
+  hipStream_t s = stream();
+  HIP_CHECK(hipMemcpyAsync(long_.win_file, h_long_win_, (size_t)count * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(long_.win_seek, h_long_win_ + count, (size_t)count * 4, hipMemcpyHostToDevice, s));
+  MelWindowParams w{};
+  w.store = long_.store; w.frame_off = long_.frame_off; w.n_frames = long_.n_frames; w.gmax = long_.gmax;
+  w.win_file = long_.win_file; w.win_seek = long_.win_seek;
+  w.mel_tm = d_mel_tm_; w.mel_ref = want_ref_layout ? d_mel_ref_ : nullptr;
+  w.mel_rows = mel_rows_; w.n_mels = cfg_.n_mels; w.n_windows = count;
+  launch_mel_window(w, s);
+}
+
+void Engine::compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) {
+  require_no_stream("compute_mel_window");
+  if (seek < 0) throw std::runtime_error("compute_mel_window: negative seek");
+  HIP_CHECK(hipSetDevice(device_));
+  ensure_capacity(1);
+  const float* arr[1] = {pcm};
+  long_prepare(arr, &n_samples, 1, 1);
+  const int file = 0;
+  long_windows_to_slots(&file, &seek, 1, true);
+  HIP_CHECK(hipMemcpyAsync(mel_out, d_mel_ref_, (size_t)cfg_.n_mels * kFramesOut * 4, hipMemcpyDeviceToHost, stream()));
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  long_release();
+}
+
+void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                              std::vector<LongWindow>& log) {
+  if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
+  require_no_stream("run_long_windows");
+  require_timestamp_vocab();
+  TsModeScope ts(ts_mode_, 1);
+  HIP_CHECK(hipSetDevice(device_));
+  auto t0 = std::chrono::steady_clock::now();
+  // windows per pass: the engine's capacity (AX_WHISPER_MAX_BATCH / max_batch of Init, or what earlier calls grew it to);
+  // more files than that wait for a place
+  const int S = std::min(n_files, std::max(cap_, 1));
+  ensure_capacity(S);
+  hipStream_t s = stream();
+  HIP_CHECK(hipEventRecord(ev_[0], s));
+  long_prepare(pcm, n_samples, n_files, S);
+  HIP_CHECK(hipEventRecord(ev_[1], s));
+  const int T = cfg_.no_timestamps + 1, E = cfg_.eot, Tc = cfg_.n_text_ctx;
+  std::vector<int> seek(n_files, 0), active, files(S), seeks(S), n_ids(S);
+  std::vector<int32_t> ids((size_t)S * Tc);
+  std::vector<WindowSegment> segs;
+  int next_file = 0, steps = 0;
+  for (int pass = 0; max_passes <= 0 || pass < max_passes; ++pass) {
+    // finished files leave, the others move up, waiting files take the free places
+    int k = 0;
+    for (int f : active)
+      if (seek[f] < n_samples[f] / kHop) active[k++] = f;
+    active.resize(k);
+    while ((int)active.size() < S && next_file < n_files) {
+      if (n_samples[next_file] / kHop > 0) active.push_back(next_file);  // (a file below one frame has no window)
+      ++next_file;
+    }
+    const int A = (int)active.size();
+    if (A == 0) break;
+    for (int i = 0; i < A; ++i) { files[i] = active[i]; seeks[i] = seek[active[i]]; }
+    long_windows_to_slots(files.data(), seeks.data(), A, false);
+    run_encoder(A);
+    steps += greedy_loop(A, max_new, nullptr);
+    fetch_ids(A, ids.data(), n_ids.data());
+    for (int i = 0; i < A; ++i) {
+      const int f = files[i];
+      LongWindow w;
+      w.file = f; w.seek = seeks[i]; w.pass = pass; w.slot = i;
+      w.window_frames = std::min(kFramesOut, n_samples[f] / kHop - seeks[i]);
+      const int n = std::max(0, std::min(n_ids[i], Tc));
+      w.ids.assign(ids.begin() + (size_t)i * Tc, ids.begin() + (size_t)i * Tc + n);
+      w.advance = split_window(w.ids.data(), n, T, E, w.window_frames, segs);
+      seek[f] += w.advance;
+      log.push_back(std::move(w));
+    }
+  }
+  HIP_CHECK(hipEventRecord(ev_[3], s));
+  HIP_CHECK(hipEventSynchronize(ev_[3]));
+  (void)hipEventElapsedTime(&timings[0], ev_[0], ev_[1]);  // upload + whole-file front-end
+  timings[1] = 0.f;                                        // (encoder and decode loop alternate: both are in [2])
+  (void)hipEventElapsedTime(&timings[2], ev_[1], ev_[3]);
+  timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  timings[4] = (float)steps;
+  long_release();
+}
+
+}  // inline namespace AXW_NS
+}  // namespace axw

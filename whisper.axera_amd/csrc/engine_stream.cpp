@@ -440,6 +440,30 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
     HIP_CHECK(hipEventRecord(a, s));
     for (int i = 0; i < iters; ++i) run_frontend(d_pcm_, (int)pcm_stride_, ns.data(), batch, false);
     HIP_CHECK(hipEventRecord(b, s));
+  } else if (what == "frontend_long") {
+    // whole-file front-end of `batch` files of `arg` seconds (silence) + one window kernel over all of them
+    if (arg < 1 || arg > 33554) throw std::runtime_error("bench frontend_long: arg = seconds of audio per file, 1 .. 33554");
+    std::vector<int> ns(batch, arg * 16000), files(batch), seeks(batch, 0);
+    for (int i = 0; i < batch; ++i) files[i] = i;
+    long_prepare(nullptr, ns.data(), batch, batch);  // allocates, fills, and runs the front-end once (warm)
+    long_windows_to_slots(files.data(), seeks.data(), batch, false);
+    FrontendParams p{};
+    p.pcm = long_.pcm; p.n_samples = long_.n_samples; p.batch = batch; p.n_mels = cfg_.n_mels;
+    p.twiddle = twiddle_; p.window = window_; p.mel_basis = mel_basis_t_;
+    p.gmax = long_.gmax; p.max_frames = 1 + ns[0] / kHop;
+    const LongStoreParams ls{long_.pcm_off, long_.frame_off, long_.store};
+    HIP_CHECK(hipEventRecord(a, s));
+    for (int i = 0; i < iters; ++i) {
+      launch_frontend_long(p, ls, s);
+      long_windows_to_slots(files.data(), seeks.data(), batch, false);
+    }
+    HIP_CHECK(hipEventRecord(b, s));
+    HIP_CHECK(hipEventSynchronize(b));
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    long_release();
+    return ms;
   } else {
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);

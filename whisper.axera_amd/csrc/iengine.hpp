@@ -11,6 +11,8 @@
 #include <string>
 #include <vector>
 
+#include "longform.hpp"
+
 namespace axw {
 
 struct ModelConfig {
@@ -59,6 +61,13 @@ class IEngine {
   virtual void decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
   // the rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] (n_hist[b] ids each) -> chosen [batch]
   virtual void apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) = 0;
+  // long-form (DESIGN.md "Long-form"): the whole-file front-end + the window kernel for one file -> the window at `seek`
+  // (frames) in the reference layout, host [n_mels * 3000]
+  virtual void compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) = 0;
+  // the seek loop over n_files files, one window of every unfinished file per pass; log: every decoded window in execution
+  // order (file counts from 0 within this call). max_new: per-window id budget (<= 0: none), max_passes <= 0: until every file ends
+  virtual void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                                std::vector<LongWindow>& log) = 0;
   virtual float bench(const std::string& what, int batch, int arg, int iters) = 0;
   virtual void set_stream(void* hip_stream) = 0;
   virtual const ModelConfig& config() const = 0;

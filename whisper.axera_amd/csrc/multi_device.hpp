@@ -105,6 +105,25 @@ class DeviceGroup {
     });
   }
 
+  // Long-form (E::run_long_windows): the FILES are split into contiguous blocks, one per engine; every engine runs its own seek
+  // loop. The log holds worker 0's windows first, then worker 1's, ...; file indices count over the whole call, pass and slot
+  // are the engine's own. W needs an int member `file`.
+  template <typename W>
+  void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, std::vector<W>& log) {
+    if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
+    const int G = size(), world = G < n_files ? G : n_files;
+    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
+    std::vector<std::vector<W>> logs(world);
+    run_sharded(n_files, world, [&](int w, int lo, int hi) {
+      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
+      std::lock_guard<std::mutex> lock(e.mutex());
+      e.run_long_windows(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, logs[w]);
+      for (W& x : logs[w]) x.file += lo;
+    });
+    for (auto& l : logs)
+      for (W& x : l) log.push_back(std::move(x));
+  }
+
  private:
   std::vector<std::unique_ptr<E>> engines_;
   std::atomic<unsigned> next_{0};

@@ -23,6 +23,10 @@ static void usage(const char* prog) {
           "  -p, --model_path    model path which contains tiny/ base/ small/ turbo/ (string [=../models-mi355x])\n"
           "      --language      en, zh (string [=zh])\n"
           "      --timestamps    after Result:, one line per segment: [mm:ss.mmm --> mm:ss.mmm] text\n"
+          "      --long          transcribe the whole file, not only its first 30 s: Result: is the whole text, followed by\n"
+          "                      one [mm:ss.mmm --> mm:ss.mmm] line per segment with times from the file's start (hours\n"
+          "                      roll into the minutes: 75:03.120). RTF: is wall time over the file's duration; without\n"
+          "                      --long it divides by the whole duration although at most 30 s are decoded\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -73,12 +77,12 @@ static bool wav_frames(const char* path, long* frames) {
   }
 }
 
-static std::string mmss(float t) {
-  const long ms = (long)(t * 1000.f + 0.5f);
+static std::string mmss_ms(long ms) {
   char b[32];
   snprintf(b, sizeof b, "%02ld:%02ld.%03ld", ms / 60000, (ms / 1000) % 60, ms % 1000);
   return b;
 }
+static std::string mmss(float t) { return mmss_ms((long)(t * 1000.f + 0.5f)); }
 
 // --timestamps: the clip decoded again in timestamp mode, split into segments (AX_WHISPER_SplitSegments), one line each
 static int print_segments(AX_WHISPER_HANDLE h, const char* wav) {
@@ -109,9 +113,44 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav) {
   return 0;
 }
 
+// --long: the seek loop over the whole file (AX_WHISPER_RunPCMLongWindows), its text, then one line per segment
+static int run_long(AX_WHISPER_HANDLE h, const char* wav, std::string& text, std::string& lines) {
+  float* pcm = nullptr;
+  int n = 0;
+  if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
+  const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
+  const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
+  int cap = n / 160 + 1;  // every window advances by at least one frame
+  std::vector<int> info((size_t)cap * 7);
+  std::vector<int32_t> ids((size_t)cap * n_ctx);
+  int n_win = 0;
+  const float* files[1] = {pcm};
+  const int rc = AX_WHISPER_RunPCMLongWindows(h, files, &n, 1, 0, 0, cap, info.data(), ids.data(), &n_win);
+  free(pcm);
+  if (rc != 0) return -1;
+  for (int k = 0; k < n_win; ++k) {
+    const int* w = &info[(size_t)k * 7];
+    const int32_t* wi = &ids[(size_t)k * n_ctx];
+    const int n_max = w[4] / 2 + 1;
+    std::vector<float> st(n_max), en(n_max);
+    std::vector<int> tb(n_max), te(n_max);
+    int n_seg = 0, adv = 0;
+    if (AX_WHISPER_SplitWindow(wi, w[4], T, E, w[2], n_max, st.data(), en.data(), tb.data(), te.data(), &n_seg, &adv) != 0) return -1;
+    for (int s = 0; s < n_seg; ++s) {
+      char* t = nullptr;
+      if (AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t) != 0) return -1;
+      text += t ? t : "";
+      // (absolute times in integer milliseconds: a float second loses the millisecond after a few hours)
+      lines += "[" + mmss_ms(w[1] * 10L + (long)(st[s] * 1000.f + 0.5f)) + " --> " + mmss_ms(w[1] * 10L + (long)(en[s] * 1000.f + 0.5f)) + "] " + (t ? t : "") + "\n";
+      free(t);
+    }
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
-  bool timestamps = false;
+  bool timestamps = false, longform = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -129,6 +168,7 @@ int main(int argc, char** argv) {
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
+    if (a == "--long") { longform = true; continue; }
     fprintf(stderr, "undefined option: %s\n", a.c_str());
     usage(argv[0]);
     return 1;
@@ -149,6 +189,21 @@ int main(int argc, char** argv) {
   auto t1 = std::chrono::steady_clock::now();
   if (!handle) { printf("AX_WHISPER_Init failed!\n"); return -1; }
   printf("Init whisper success, take %.4fseconds\n", std::chrono::duration<double>(t1 - t0).count());
+
+  if (longform) {
+    t0 = std::chrono::steady_clock::now();
+    std::string text, lines;
+    if (run_long(handle, wav.c_str(), text, lines) != 0) {
+      printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
+      AX_WHISPER_Uninit(handle);
+      return -1;
+    }
+    t1 = std::chrono::steady_clock::now();
+    printf("Result: %s\n%s", text.c_str(), lines.c_str());
+    printf("RTF: %.4f\n", std::chrono::duration<double>(t1 - t0).count() / duration);
+    AX_WHISPER_Uninit(handle);
+    return 0;
+  }
 
   t0 = std::chrono::steady_clock::now();
   char* result = nullptr;
