@@ -475,6 +475,9 @@ struct PersistParams {
   int* out_ids1; int* n_out1; int max_new1;
   // three clips (n_clip == 3): clip 2's ids at out_ids1 + n_ctx, its count at n_out1 + 1, its self cache self_clip_stride elements on
   int max_new2; long self_clip_stride;
+  // One-clip launch: the poller waves keep the tail of their workgroup's vocabulary rows in registers for the whole launch
+  // (decode_persistent.hip "resident vocabulary rows"); 0 (AX_WHISPER_VOCAB_RESIDENT=0): every row is streamed every step
+  int vocab_resident;
 };
 bool decode_persistent_supported(int d_model, int n_head, int n_layer, int n_cu);
 int decode_persistent_grid(int d_model, int n_cu);
@@ -483,6 +486,7 @@ size_t qfold_floats(int d_model, int n_layer);                // floats of the q
 void launch_qfold_build(const h16* wl, const float* fl, float* qf, int d_model, int n_layer, hipStream_t s);
 hipError_t launch_decode_persistent(const PersistParams& p, int d_model, int grid, hipStream_t s);  // n_clip 1, 2 or 3
 int decode_persistent_max_clips(int d_model, int n_head, int n_layer, int grid);  // clips per persistent launch: 1, 2 or 3
+int decode_persistent_vocab_resident_rows(int d_model, int n_vocab, int grid);    // vocabulary rows a workgroup of the one-clip launch keeps on-chip
 
 // weight preparation (device): raw file dtype -> h16 / fp32, with the layout changes the kernels want
 void launch_convert_to_h16(const void* src, int src_dtype /*0 f32,1 bf16,2 f16*/, h16* dst, long n, hipStream_t s);

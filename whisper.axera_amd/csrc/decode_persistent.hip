@@ -108,9 +108,23 @@ size_t qfold_floats(int d_model, int n_layer) { return (size_t)n_layer * (size_t
 // ---------------------------------------------------------------------------------------- the kernel
 // d_model = 8*LD*CD (rows with K = d: LD lanes x CD 16-byte chunks), 4*d_model = 8*LF*CF.
 // QF: the query fold above (d_model <= 768: the fp32 rows of M cost 2 * CD more registers per lane)
+//
+// Resident vocabulary rows (round 7). The vocabulary projection is the one phase of a step that is bound by bytes: every
+// workgroup streams the same ~N / P rows of the tied embedding from HBM at every step, while its poller waves hold two floats
+// of residual stream per lane and spin. So the pollers load the TAIL of the workgroup's range once per launch — kVocabRes<>
+// passes of PL / LD rows in the lane layout of rows_load<LD, CD> — and compute those logits from their registers behind the
+// final LayerNorm, with the same rows_dot<LD, CD> (same element order, same group_sum: every logit keeps its bits); the compute
+// waves stream only the head of the range and compute wave 0 folds the pollers' eight candidates into the workgroup's pair
+// (first max wins by index, so who computed a row cannot change the token). PersistParams::vocab_resident == 0: none.
+// Passes per instantiation: what the pollers' registers hold without a spill. At d_model 768 a pass is 12 registers per lane and
+// the poller loop itself needs ~50 of the 128: six passes (96 of a workgroup's ~203 rows); the seventh spills 8 registers, and
+// the timeline build, which has a few registers less to give, keeps five. Rows wider than 3 chunks keep none.
+template <int CD, bool PROF>
+constexpr int kVocabRes = CD > 3 ? 0 : PROF ? 5 : 6;
 template <int LD, int CD, int LF, int CF, bool PROF, bool QF>
 __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) {
   AXW_PERSIST_SHAPES
+  constexpr int NRES = kVocabRes<CD, PROF>, VCAP = NRES * (PL / LD);  // resident passes, rows
   constexpr int XG = D, X0R = 2 * D, A0S = 3 * D;  // QF: act[XG..) = g_cross . x0, act[X0R..) = x0 (written with the QKV LayerNorm, read by
                                                   // the row producers), act[A0S + slot] = A0 of the slot's row (free until the partial records)
   AXW_PERSIST_LDS(4)  // red[2*NPW]: the stage's mean (QF: the statistics' shift), red[2*NPW + 1]: the shift the sums are relative to
@@ -129,6 +143,32 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     float lg[GD], lb[GD];
     float shift = 0.f;  // LayerNorm variance shift (previous mean): sums stay small without a second pass
     AXW_POLLER_PREFETCH
+    // resident vocabulary rows: slot tid / LD keeps rows vb + slot (+ k * PL / LD) of [vb, v1) = the last min(VCAP, rows) of the
+    // workgroup's range (RowSet::prefetch's even deal). Nothing of it is in flight when the first poll is issued.
+    // Kept as single registers behind an opaque asm, not as the loads' 4-register tuples: tuples that live across the whole step
+    // loop fragment the register file (spills from the 4th pass on), and rows the compiler can see through are unpacked to fp32
+    // ONCE in front of the loop and kept that way — twice the registers.
+    unsigned vres[NRES > 0 ? NRES : 1][4 * CD];
+    auto vocab_tail = [&](int& v0, int& vb, int& v1) {
+      const unsigned N = (unsigned)AXW_COLD(n_vocab);
+      v0 = (int)((unsigned)rwg * N / (unsigned)P);
+      v1 = (int)((unsigned)(rwg + 1) * N / (unsigned)P);
+      vb = AXW_COLD(vocab_resident) ? (v1 - v0 > VCAP ? v1 - VCAP : v0) : v1;
+    };
+    if constexpr (NRES > 0) {  // (loaded with the switch off as well: a few rows once per launch, and no second code path)
+      int v0, vb, v1;
+      vocab_tail(v0, vb, v1);
+      if (vb == v1) vb = v0;
+#pragma unroll
+      for (int k = 0; k < NRES; ++k) {
+        const int row = vb + k * (PL / LD) + tid / LD;
+        u32x4 w[CD];
+        rows_load<LD, CD>(w, AXW_COLD(tok_emb), D, row < v1 ? row : v0, tid);
+#pragma unroll
+        for (int i = 0; i < 4 * CD; ++i) { vres[k][i] = w[i / 4][i % 4]; asm volatile("" : "+v"(vres[k][i])); }
+      }
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    }
     // the pairs of a d-wide vector that starts at granule `base`
 #define AXW_PAIRS_D(BASE) [&](int j) { const int pr = tid + j * PL; return 2 * pr < D ? (BASE) + 2 * pr : -1; }
 
@@ -371,6 +411,37 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         unsigned y[GD];
         const bool fail = gather2<GPD>(GR, (unsigned)(step * L + L), y, p.err, ctl, AXW_PAIRS_D(O_Y3));
         AXW_LN_STAGE(y, true, fail, 0x900)
+        if constexpr (NRES > 0) {  // the resident rows' logits: act is the normalised vector until the next step's first stage
+          int v0, vb, v1;
+          vocab_tail(v0, vb, v1);
+          if (vb < v1) {
+            float* dump = AXW_COLD(logits_dump) ? AXW_COLD(logits_dump) + (long)(step - 3) * AXW_COLD(n_vocab) : nullptr;
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+#pragma unroll
+            for (int k = 0; k < NRES; ++k) {
+              u32x4 w[CD];
+#pragma unroll
+              for (int i = 0; i < 4 * CD; ++i) {  // a COPY behind the asm: a resident register that the loop redefined would travel as a phi
+                unsigned t;
+                asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(vres[k][i]));
+                w[i / 4][i % 4] = t;
+              }
+              int tid2 = tid;
+              asm volatile("" : "+v"(tid2));  // the activations are re-read from LDS in every pass, not held (24 registers) across the passes
+              const float acc = rows_dot<LD, CD>(w, act, tid2);
+              const int row = vb + k * (PL / LD) + tid / LD;
+              if (tid % LD == 0 && row < v1) {
+                if (dump) dump[row] = acc;
+                if (acc > bv) { bv = acc; bi = row; }
+              }
+            }
+            wave_argmax(bv, bi);
+            // one candidate per poller wave in pscr (free between the attention phases); am_v[0..8) is not: the pollers write
+            // the grid's merge there behind B3, while compute wave 0 may still be folding
+            if ((tid & 63) == 0) { pscr[tid >> 6] = bv; reinterpret_cast<int*>(pscr)[NPW + (tid >> 6)] = bi; }
+          }
+        }
         AXW_STAMP(14)
         wg_barrier();  // B3: the compute waves have their workgroup argmax
         unsigned v[2];  // {value, row index} of workgroup tid: one pair
@@ -720,7 +791,9 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         float bv = -INFINITY;
         int bi = 0x7fffffff;
         float* dump = AXW_COLD(logits_dump) ? AXW_COLD(logits_dump) + (long)(step - 3) * N : nullptr;
-        const int r0 = ra.r0, r1 = ra.r1;
+        // the pollers hold the last `nres` rows of the range (vocab_tail): stream the rest
+        const int nres = NRES > 0 && AXW_COLD(vocab_resident) ? (ra.r1 - ra.r0 > VCAP ? VCAP : ra.r1 - ra.r0) : 0;
+        const int r0 = ra.r0, r1 = ra.r1 - nres;
         auto consume = [&](const u32x4 (&wr)[CD], int row) {
           float acc;
           if constexpr (kActInRegs) acc = rows_dot_reg<LD, CD>(wr, a);
@@ -765,6 +838,13 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         if (ctid == 0) {
           for (int w2 = 1; w2 < NCW; ++w2)
             if (am_v[8 + w2] > bv || (am_v[8 + w2] == bv && am_i[8 + w2] < bi)) { bv = am_v[8 + w2]; bi = am_i[8 + w2]; }
+          if (nres > 0) {  // the poller waves' candidates over the resident rows
+            for (int w2 = 0; w2 < NPW; ++w2) {
+              const float pv = pscr[w2];
+              const int pi = reinterpret_cast<const int*>(pscr)[NPW + w2];
+              if (pv > bv || (pv == bv && pi < bi)) { bv = pv; bi = pi; }
+            }
+          }
           am_v[8] = bv; am_i[8] = bi;
         }
         __builtin_amdgcn_wave_barrier();
@@ -820,6 +900,18 @@ int decode_persistent_max_clips(int d_model, int n_head, int n_layer, int grid) 
   // layer, and the later clips' vectors must fit what the K/V region leaves of the CU's 160 KB of LDS
   while (nc < 3 && grid - n_layer * n_head >= (nc + 1) * kCrossSplit * n_head && persist_lds_bytes(d_model, nc + 1) <= 160 * 1024) ++nc;
   return nc;
+}
+// rows per workgroup that the one-clip launch keeps in its poller waves (the production instantiation; a workgroup whose range
+// is shorter keeps all of it: the smallest range of the even deal has n_vocab / grid rows)
+int decode_persistent_vocab_resident_rows(int d_model, int n_vocab, int grid) {
+  int cap = 0;
+  (void)persist_dispatch(d_model, [&](auto sh) {
+    using S = decltype(sh);
+    cap = kVocabRes<S::CD, false> * (PL / S::LD);
+    return hipSuccess;
+  });
+  const int rows = grid > 0 ? n_vocab / grid : 0;
+  return cap < rows ? cap : rows;
 }
 // 16 d-wide buffers, the argmax pairs at 16 d (up to 512 granules), the fold's statistics at 16 d + 512 (one 16-granule line
 // per row producer, at most d / 16 of them), the error word last

@@ -115,6 +115,12 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
           HIP_CHECK(hipStreamSynchronize(own_stream_));
         }
       }
+      // the one-clip launch keeps the tail of every workgroup's vocabulary rows in its poller waves' registers for the whole
+      // utterance (decode_persistent.hip, round 7); AX_WHISPER_VOCAB_RESIDENT=0: every row is streamed at every step (A/B, tests)
+      {
+        const char* ev = getenv("AX_WHISPER_VOCAB_RESIDENT");
+        if (!(ev && ev[0] == '0')) vocab_resident_rows_ = decode_persistent_vocab_resident_rows(cfg_.n_text_state, cfg_.n_vocab, persist_grid_);
+      }
       if (persist_max_clips_ >= 2) {
         self1_bytes_ = (size_t)cfg_.n_text_layer * cfg_.n_text_head * 8 * 4096 * 2;  // one later clip's cache (K; V alike)
         d_self_k1_ = (h16*)dalloc((persist_max_clips_ - 1) * self1_bytes_, true);
@@ -128,6 +134,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
   cfg_.ints["persistent_max_clips"] = persist_max_clips_;
   cfg_.ints["persistent_decode"] = persistent_ok_ ? 1 : 0;  // visible through AX_WHISPER_GetConfigInt
   cfg_.ints["persistent_qfold"] = d_qfold_ ? 1 : 0;
+  cfg_.ints["vocab_resident_rows"] = vocab_resident_rows_;
   cfg_.ints["persistent_giveups"] = 0;
   {  // batched decode as clip-block GEMMs with LayerNorm prologue / residual epilogue (enqueue_decode_step_batched)
     const char* e = getenv("AX_WHISPER_BATCHED_LN");

@@ -233,6 +233,7 @@ class Engine final : public IEngine {
   void persistent_gave_up();
   void persistent_succeeded();
   int persist_grid_ = 0;
+  int vocab_resident_rows_ = 0;        // one-clip launch: vocabulary rows per workgroup held in the poller waves (0: AX_WHISPER_VOCAB_RESIDENT=0 or unsupported width)
   u64* d_gran_ = nullptr; size_t gran_bytes_ = 0;
   float* d_qfold_ = nullptr;  // query-fold arena of the one-clip launch (d_model <= 768), nullptr = unfolded
   std::map<long, hipGraphExec_t> graphs_;  // key: batch * 1024 + max_new

@@ -639,6 +639,7 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
   p.prof = d_prof;
   { const char* pc = getenv("AX_WHISPER_PERSIST_PROF_CLIP"); p.prof_clip = pc && pc[0] == '1'; }
   p.fault = getenv("AX_WHISPER_PERSIST_FAULT") ? 1 : 0;
+  p.vocab_resident = vocab_resident_rows_ > 0 ? 1 : 0;
   HIP_CHECK(hipMemsetAsync(d_gran_, 0, p.n_clip * gran_bytes_, s));
   HIP_CHECK(hipMemsetAsync(d_state_, 0, sizeof(DecState), s));
   HIP_CHECK(hipMemsetAsync(d_nout_ + slot, 0, 4 * p.n_clip, s));
