@@ -225,12 +225,53 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const 
 AX_WHISPER_API int AX_WHISPER_RunPCMLong(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, char** result);
 AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result);
 
+/* ---- confidence: token log-probabilities, no-speech, silent-window skipping (DESIGN.md "Confidence")
+ * All in timestamp mode, natural logarithms, float32. At a sampled step the rules leave a final allowed set A (rules 1-5); the chosen
+ * id c is the one timestamp mode picks, and its log-probability is x[c] - logsumexp(x[A]) (nothing finite left: -inf; x[c] = +inf: 0).
+ * A clip that kept n ids has n + 1 decisions: one per id, plus the one that ended it (eot, or the id dropped at the budget / the
+ * context end; ended_eot says which). avg_logprob = (sum of the n kept ids' values + the last one if it was eot) / (n + 1).
+ * no_speech_logprob = x[no_speech] - logsumexp of the WHOLE row (NaN entries left out) at the step that fed sot;
+ * no_speech = AX_WHISPER_GetConfigInt(h, "no_speech") (the config file's key, default no_timestamps - 1). The device value is the
+ * LOG; the probability the thresholds compare is exp() of it, taken on the host. */
+/** RunPCMBatchTimestampTokens (the same ids) + token_logprob [batch][n_text_ctx] (entries 0 .. n_ids[b], the rest 0), avg_logprob,
+ *  no_speech_logprob, ended_eot [batch]. Sharded over the handle's devices. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampScores(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                         int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids,
+                                                         float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
+/** DecodeForcedTimestamps + logprob [batch][n_forced+1] of each step's chosen id, no_speech_logprob [batch] and (may be NULL)
+ *  logits0 [batch][n_vocab]: the raw row of decode offset 0, which the no-speech value was taken from (`logits` starts at offset 2). */
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampScores(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
+                                                          float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob,
+                                                          float* logits0);
+/** ApplyTimestampRules + logprob [batch]: the scored rules kernel alone on host data. */
+AX_WHISPER_API int AX_WHISPER_ScoreTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                                  int batch, int32_t* chosen, float* logprob);
+/** The no-speech kernel alone on host data: logits [batch][n_vocab] -> out [batch]. */
+AX_WHISPER_API int AX_WHISPER_NoSpeechLogProb(AX_WHISPER_HANDLE handle, const float* logits, int batch, float* out);
+/** Host only (no handle, no GPU): the silent-window rule. 1 iff exp(no_speech_logprob) > no_speech_threshold and NOT
+ *  (avg_logprob > logprob_threshold), else 0. logprob_threshold = +inf: no-speech alone decides; a NaN no_speech_threshold: never.
+ *  openai-whisper's values are 0.6 and -1.0. */
+AX_WHISPER_API int AX_WHISPER_LongWindowIsSilent(float no_speech_logprob, float avg_logprob, float no_speech_threshold,
+                                                 float logprob_threshold);
+/** RunPCMLongWindows under the silent-window rule: a window the rule calls silent emits no segment and advances by its
+ *  window_frames. win_score[k*3 .. k*3+2] = no_speech_logprob, avg_logprob, skipped (0 / 1) of window k. A NaN
+ *  no_speech_threshold switches the rule off: the windows are RunPCMLongWindows' own, with their scores. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsScored(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                      int n_files, int max_new, int max_passes, float no_speech_threshold,
+                                                      float logprob_threshold, int win_cap, int* win_info, int32_t* ids, float* win_score,
+                                                      int* n_windows);
+/** RunPCMLong / RunFileLong under the silent-window rule (skipped windows add no text). */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongOpts(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                             float logprob_threshold, char** result);
+AX_WHISPER_API int AX_WHISPER_RunFileLongOpts(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
+                                              float logprob_threshold, char** result);
+
 /** Stage timings of the last Run* / DecodeGreedy* call, ms (hipEvent): [0] front-end, [1] encoder,
  *  [2] decode loop, [3] whole call (wall), [4] decode steps executed. */
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
 /** Time `iters` launches of one named piece on the handle's stream with hipEvents; returns
  *  total ms in *ms_total. what: "decode_step" (one captured step graph at decode offset
- *  `arg`), "decode_step_ts" (the same step in timestamp mode), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
+ *  `arg`), "decode_step_ts" (the same step in timestamp mode), "decode_step_ts_scored" (in scored mode), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
  *  files of `arg` seconds + one window kernel), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);

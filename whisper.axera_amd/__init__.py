@@ -74,6 +74,14 @@ SYMBOLS = {
     "AX_WHISPER_RunPCMLongWindows": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]),
     "AX_WHISPER_RunPCMLong": (C.c_int, [C.c_void_p, fp, C.c_int, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_RunFileLong": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunPCMBatchTimestampScores": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_DecodeForcedTimestampScores": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, fp, ip, fp, fp, fp]),
+    "AX_WHISPER_ScoreTimestampRules": (C.c_int, [C.c_void_p, fp, ip, C.POINTER(C.c_int), C.c_int, ip, fp]),
+    "AX_WHISPER_NoSpeechLogProb": (C.c_int, [C.c_void_p, fp, C.c_int, fp]),
+    "AX_WHISPER_LongWindowIsSilent": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float]),
+    "AX_WHISPER_RunPCMLongWindowsScored": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongOpts": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunFileLongOpts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
 }
 
 
@@ -168,6 +176,19 @@ def split_window(ids, timestamp_begin: int, eot: int, window_frames: int):
     return [(float(st[k]), float(en[k]), int(tb[k]), int(te[k])) for k in range(n.value)], adv.value
 
 
+def long_window_is_silent(no_speech_logprob: float, avg_logprob: float, no_speech_threshold: float, logprob_threshold: float) -> bool:
+    """The silent-window rule of the long-form loop (AX_WHISPER_LongWindowIsSilent, host only): exp(no_speech_logprob) >
+    no_speech_threshold and not avg_logprob > logprob_threshold, in float32."""
+    L = load_library()
+    return bool(L.AX_WHISPER_LongWindowIsSilent(float(no_speech_logprob), float(avg_logprob), float(no_speech_threshold), float(logprob_threshold)))
+
+
+def _thresholds(no_speech_threshold, logprob_threshold):
+    """None -> the values that switch a comparison off: NaN (never silent) / +inf (no-speech alone decides)."""
+    return (float("nan") if no_speech_threshold is None else float(no_speech_threshold),
+            float("inf") if logprob_threshold is None else float(logprob_threshold))
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -193,6 +214,7 @@ class Whisper:
         self.n_text_layer, self.n_text_state, self.eot = g("n_text_layer"), g("n_text_state"), g("eot")
         self.sot_seq = [g(f"sot_seq{i}") for i in range(4)]
         self.timestamp_begin = g("timestamp_begin")
+        self.no_speech = g("no_speech")
         self.n_devices = self.L.AX_WHISPER_GetDeviceCount(self.h)
 
     def close(self):
@@ -255,6 +277,62 @@ class Whisper:
                     "RunPCMBatchTimestampTokens")
         return [ids[b, : n[b]].tolist() for b in range(B)]
 
+    # ---- confidence: timestamp mode + the log-probability of every decision and of <|nospeech|> (DESIGN.md "Confidence")
+    def run_timestamp_scores_batch(self, clips, max_new: int = 0, max_new_clip=None):
+        """Per clip a dict: ids (those of run_timestamp_tokens_batch), token_logprob (len(ids) + 1 values: one per id, then the
+        decision that ended the clip), avg_logprob, no_speech_logprob, ended_eot (AX_WHISPER_RunPCMBatchTimestampScores)."""
+        clips = [_f32(c) for c in clips]
+        B = len(clips)
+        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
+        lens = (C.c_int * B)(*[len(c) for c in clips])
+        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        n = (C.c_int * B)()
+        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
+        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+        eot = (C.c_int * B)()
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampScores(self.h, ptrs, lens, B, max_new, mc, ids.ctypes.data_as(ip), n, lp.ctypes.data_as(fp),
+                                                                 avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), eot), "RunPCMBatchTimestampScores")
+        return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
+                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+
+    def decode_forced_timestamp_scores(self, batch: int, forced, want_logits: bool = True, want_logits0: bool = True):
+        """decode_forced_timestamps + (logprob [batch][n+1] of each step's chosen id, no_speech_logprob [batch], logits0
+        [batch][n_vocab] or None: the raw row of decode offset 0). Returns (logits, chosen, logprob, no_speech_logprob, logits0)."""
+        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
+        n = f.shape[1]
+        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
+        l0 = np.empty((batch, self.n_vocab), dtype=np.float32) if want_logits0 else None
+        ch = np.empty((batch, n + 1), dtype=np.int32)
+        lp = np.empty((batch, n + 1), dtype=np.float32)
+        nsp = np.empty(batch, dtype=np.float32)
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampScores(self.h, batch, f.ctypes.data_as(ip), n, logits.ctypes.data_as(fp) if want_logits else None,
+                                                                  ch.ctypes.data_as(ip), lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
+                                                                  l0.ctypes.data_as(fp) if want_logits0 else None), "DecodeForcedTimestampScores")
+        return logits, ch, lp, nsp, l0
+
+    def score_timestamp_rules(self, logits, histories):
+        """The scored rules kernel alone: logits [batch][n_vocab], one id history per clip -> (chosen ids, their log-probabilities)."""
+        lg = _f32(logits).reshape(-1, self.n_vocab)
+        B = lg.shape[0]
+        hist = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        nh = (C.c_int * B)()
+        for b, h in enumerate(histories):
+            hist[b, : len(h)] = h
+            nh[b] = len(h)
+        out = np.zeros(B, dtype=np.int32)
+        lp = np.zeros(B, dtype=np.float32)
+        self._check(self.L.AX_WHISPER_ScoreTimestampRules(self.h, lg.ctypes.data_as(fp), hist.ctypes.data_as(ip), nh, B, out.ctypes.data_as(ip),
+                                                           lp.ctypes.data_as(fp)), "ScoreTimestampRules")
+        return out.tolist(), lp
+
+    def no_speech_logprob(self, logits) -> np.ndarray:
+        """The no-speech kernel alone: logits [batch][n_vocab] -> log p(<|nospeech|>) over each whole row."""
+        lg = _f32(logits).reshape(-1, self.n_vocab)
+        out = np.zeros(lg.shape[0], dtype=np.float32)
+        self._check(self.L.AX_WHISPER_NoSpeechLogProb(self.h, lg.ctypes.data_as(fp), lg.shape[0], out.ctypes.data_as(fp)), "NoSpeechLogProb")
+        return out
+
     def segments(self, ids, num_samples: int):
         """[(start_s, end_s, text)] of one clip's timestamp-mode ids."""
         clip_s = min(num_samples / 16000.0, 30.0)
@@ -273,10 +351,14 @@ class Whisper:
         self._check(self.L.AX_WHISPER_ComputeMelWindow(self.h, a.ctypes.data_as(fp), len(a), int(seek), out.ctypes.data_as(fp)), "ComputeMelWindow")
         return out
 
-    def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0):
+    def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0, no_speech_threshold=None, logprob_threshold=None, scores: bool = False):
         """The seek loop over `files` (PCM arrays), one window of every unfinished file per pass. Per file, the list of its
         decoded windows (seek, window_frames, advance, ids, pass, slot) in order. max_new: id budget per window;
-        max_passes > 0 stops after that many passes (the slots then hold the last pass's cross K/V)."""
+        max_passes > 0 stops after that many passes (the slots then hold the last pass's cross K/V).
+        With a threshold (the silent-window rule: a skipped window advances by its window_frames) or scores=True the call is the
+        scored one and every tuple gains (no_speech_logprob, avg_logprob, skipped)."""
+        scored = scores or no_speech_threshold is not None or logprob_threshold is not None
+        nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
         files = [_f32(f) for f in files]
         n = len(files)
         ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
@@ -286,9 +368,15 @@ class Whisper:
         while True:
             info = np.zeros((cap, 7), dtype=np.int32)
             ids = np.zeros((cap, self.n_text_ctx), dtype=np.int32)
+            sc = np.zeros((cap, 3), dtype=np.float32)
             nw = C.c_int()
-            rc = self.L.AX_WHISPER_RunPCMLongWindows(self.h, ptrs, lens, n, int(max_new), int(max_passes), cap,
-                                                     info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip), C.byref(nw))
+            if scored:
+                rc = self.L.AX_WHISPER_RunPCMLongWindowsScored(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, cap,
+                                                               info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
+                                                               sc.ctypes.data_as(fp), C.byref(nw))
+            else:
+                rc = self.L.AX_WHISPER_RunPCMLongWindows(self.h, ptrs, lens, n, int(max_new), int(max_passes), cap,
+                                                         info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip), C.byref(nw))
             if rc != 0:
                 msg = (self.L.AX_WHISPER_LastError(self.h) or b"").decode()
                 need = re.search(r"(\d+) windows were decoded, win_cap is", msg)
@@ -300,7 +388,20 @@ class Whisper:
         out = [[] for _ in range(n)]
         for k in range(nw.value):
             f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
-            out[f].append((seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot))
+            w = (seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot)
+            out[f].append(w + (float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2])) if scored else w)
+        return out
+
+    def run_long_scored(self, audio, max_new: int = 0, no_speech_threshold=None, logprob_threshold=None):
+        """run_long with confidence -> [(start_s, end_s, text, avg_logprob, no_speech_prob)]: every segment carries its window's two
+        numbers (as openai-whisper reports them); windows the silent-window rule skips yield nothing."""
+        out = []
+        for seek, wf, _adv, ids, _p, _s, nsp, avg, skipped in self.run_long_windows([audio], max_new, no_speech_threshold=no_speech_threshold,
+                                                                                     logprob_threshold=logprob_threshold, scores=True)[0]:
+            if skipped:
+                continue
+            for s, e, tb, te in split_window(ids, self.timestamp_begin, self.eot, wf)[0]:
+                out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te]), avg, float(np.exp(np.float32(nsp)))))
         return out
 
     def run_long(self, audio, max_new: int = 0):
@@ -311,9 +412,18 @@ class Whisper:
                 out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te])))
         return out
 
-    def run_long_text(self, audio) -> str:
-        """PCM or a wav path of any length -> the whole text (AX_WHISPER_RunPCMLong / RunFileLong)."""
+    def run_long_text(self, audio, no_speech_threshold=None, logprob_threshold=None) -> str:
+        """PCM or a wav path of any length -> the whole text (AX_WHISPER_RunPCMLong / RunFileLong; with a threshold: the *Opts
+        forms, the text without the windows the silent-window rule skips)."""
         out = C.c_void_p()
+        if no_speech_threshold is not None or logprob_threshold is not None:
+            nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
+            if isinstance(audio, (str, os.PathLike)):
+                self._check(self.L.AX_WHISPER_RunFileLongOpts(self.h, os.fspath(audio).encode(), nst, lpt, C.byref(out)), "RunFileLongOpts")
+            else:
+                a = _f32(audio)
+                self._check(self.L.AX_WHISPER_RunPCMLongOpts(self.h, a.ctypes.data_as(fp), len(a), nst, lpt, C.byref(out)), "RunPCMLongOpts")
+            return self._take(out.value)
         if isinstance(audio, (str, os.PathLike)):
             self._check(self.L.AX_WHISPER_RunFileLong(self.h, os.fspath(audio).encode(), C.byref(out)), "RunFileLong")
         else:

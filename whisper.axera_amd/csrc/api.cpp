@@ -441,6 +441,35 @@ AX_WHISPER_API int AX_WHISPER_ApplyTimestampRules(AX_WHISPER_HANDLE handle, cons
   return guarded(handle, [&](Engine& e) { e.apply_timestamp_rules(logits, hist, n_hist, batch, chosen); });
 }
 
+// ---- confidence (DESIGN.md "Confidence")
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampScores(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                         int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids,
+                                                         float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
+  if (!handle || !pcm || !num_samples || !ids || !n_ids || !token_logprob || !avg_logprob || !no_speech_logprob || !ended_eot || batch < 1) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    g.run_tokens_scores(pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids, token_logprob,
+                        avg_logprob, no_speech_logprob, ended_eot);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampScores(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
+                                                          float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob,
+                                                          float* logits0) {
+  if (!handle || (n_forced > 0 && !forced)) return -1;
+  return guarded(handle, [&](Engine& e) { e.decode_forced_scores(batch, forced, n_forced, logits, chosen, logprob, no_speech_logprob, logits0); });
+}
+
+AX_WHISPER_API int AX_WHISPER_ScoreTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                                  int batch, int32_t* chosen, float* logprob) {
+  if (!handle || !logits || !hist || !n_hist || !chosen || !logprob || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.score_timestamp_rules(logits, hist, n_hist, batch, chosen, logprob); });
+}
+
+AX_WHISPER_API int AX_WHISPER_NoSpeechLogProb(AX_WHISPER_HANDLE handle, const float* logits, int batch, float* out) {
+  if (!handle || !logits || !out || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.no_speech_logprob(logits, batch, out); });
+}
+
 // Host only: one clip's ids (eot excluded) -> segments (DESIGN.md "Segment timestamps": openai-whisper's single-window split,
 // plus the tail rule). Any ids are accepted; the result never exceeds n_max entries.
 AX_WHISPER_API int AX_WHISPER_SplitSegments(const int32_t* ids, int n, int timestamp_begin, int eot, float clip_seconds, int n_max,
@@ -532,22 +561,75 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const 
   });
 }
 
-AX_WHISPER_API int AX_WHISPER_RunPCMLong(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, char** result) {
+// text of one file's windows; opts: the silent-window rule's thresholds, or nullptr (the unscored loop)
+static int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const axw::LongScoreOptions* opts, char** result) {
   if (!handle || !pcm_data || !result || num_samples < 1) return -1;
   *result = nullptr;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     Engine& e = g.primary();
     std::vector<axw::LongWindow> log;
     const float* files[1] = {pcm_data};
-    g.run_long_windows(files, &num_samples, 1, 0, 0, log);
+    if (opts) g.run_long_windows_scored(files, &num_samples, 1, 0, 0, *opts, log);
+    else g.run_long_windows(files, &num_samples, 1, 0, 0, log);
     const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
     std::string text;
     std::vector<axw::WindowSegment> segs;
     for (const axw::LongWindow& w : log) {
+      if (w.skipped) continue;
       axw::split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
       for (const axw::WindowSegment& sg : segs) text += e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);  // host only
     }
     *result = strdup(text.c_str());
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLong(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, char** result) {
+  return long_text(handle, pcm_data, num_samples, nullptr, result);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongOpts(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                             float logprob_threshold, char** result) {
+  const axw::LongScoreOptions opts{no_speech_threshold, logprob_threshold};
+  return long_text(handle, pcm_data, num_samples, &opts, result);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileLongOpts(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
+                                              float logprob_threshold, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return AX_WHISPER_RunPCMLongOpts(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold, result);
+}
+
+AX_WHISPER_API int AX_WHISPER_LongWindowIsSilent(float no_speech_logprob, float avg_logprob, float no_speech_threshold,
+                                                 float logprob_threshold) {
+  return axw::long_window_is_silent(no_speech_logprob, avg_logprob, no_speech_threshold, logprob_threshold) ? 1 : 0;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsScored(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                      int n_files, int max_new, int max_passes, float no_speech_threshold,
+                                                      float logprob_threshold, int win_cap, int* win_info, int32_t* ids, float* win_score,
+                                                      int* n_windows) {
+  if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids || !win_score))) return -1;
+  for (int b = 0; b < n_files; ++b)
+    if (!pcm[b] || num_samples[b] < 1) return -1;
+  *n_windows = 0;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    std::vector<axw::LongWindow> log;
+    g.run_long_windows_scored(pcm, num_samples, n_files, max_new, max_passes, axw::LongScoreOptions{no_speech_threshold, logprob_threshold}, log);
+    // nothing is written unless everything fits
+    if ((long)log.size() > win_cap)
+      throw std::runtime_error("RunPCMLongWindowsScored: " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
+    const int Tc = g.primary().config().n_text_ctx;
+    for (size_t k = 0; k < log.size(); ++k) {
+      const axw::LongWindow& w = log[k];
+      const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
+      memcpy(win_info + k * 7, row, sizeof row);
+      memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
+      win_score[k * 3] = w.no_speech_logprob; win_score[k * 3 + 1] = w.avg_logprob; win_score[k * 3 + 2] = w.skipped ? 1.f : 0.f;
+    }
+    *n_windows = (int)log.size();
   });
 }
 

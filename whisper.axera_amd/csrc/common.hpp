@@ -445,6 +445,16 @@ struct TsRulesParams {
   float* amax_val; int* amax_idx; int amax_stride;   // out: partial 0 of clip b at b * amax_stride
 };
 void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s);
+// Scored form (DESIGN.md "Confidence"): the rules kernel that also writes, for every clip that samples at this step, the
+// log-probability of the chosen id under the final allowed set and the decision id, both at index n = the clip's history length.
+// With `off` and `no_speech` set, clips at decode offset 0 get log p(no_speech_id) over their whole row instead.
+struct TsScoreParams {
+  float* logprob; int* decision; long stride;   // out: [batch][stride], entry n of clip b (n < stride)
+  float* no_speech; int no_speech_id;           // out: [batch], or nullptr
+};
+void launch_timestamp_rules_scored(const TsRulesParams& p, const TsScoreParams& q, hipStream_t s);
+// out[b] = logits[b][id] - logsumexp(logits[b][0 .. n_vocab)), NaN entries left out; rows [batch][stride], stride a multiple of 4
+void launch_row_logprob(const float* logits, long stride, int n_vocab, int id, int batch, float* out, hipStream_t s);
 
 // ---- persistent decode (decode_persistent.hip, decode_persistent2.hip): the whole greedy loop of one to three clips in ONE launch
 typedef unsigned long long u64;

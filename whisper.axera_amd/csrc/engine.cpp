@@ -257,6 +257,7 @@ void Engine::load_config(const std::string& dir, const std::string& type, const 
   sot_seq_[3] = cfg_.no_timestamps;
   for (int i = 0; i < 4; ++i) cfg_.ints["sot_seq" + std::to_string(i)] = sot_seq_[i];
   cfg_.ints["timestamp_begin"] = cfg_.no_timestamps + 1;  // id of the 0.00 s timestamp (timestamp mode)
+  if (!cfg_.ints.count("no_speech")) cfg_.ints["no_speech"] = cfg_.no_timestamps - 1;  // <|nospeech|> (scored mode), where the file omits it
 }
 
 // Slaney mel filterbank, arithmetic as librosa.h:102-144 (fp32), stored transposed [201][n_mels].
@@ -534,6 +535,8 @@ void Engine::free_slot_buffers() {
   for (void* p : slot_allocs_) (void)hipFree(p);
   slot_allocs_.clear();
   d_ts_logits_ = nullptr;  // (one of slot_allocs_)
+  d_tok_lp_ = nullptr; d_dec_id_ = nullptr; d_nospeech_ = nullptr;  // (likewise)
+  score_out_ = TsScoreParams{};
   if (h_pcm_) { (void)hipHostFree(h_pcm_); h_pcm_ = nullptr; }
   cap_ = 0;
 }
@@ -816,8 +819,10 @@ void Engine::run_tokens_mode(int mode, const float* const* pcm, const float* d_p
                              int max_new, int32_t* ids, int* n_ids, const int* max_new_clip) {
   if (batch < 1) throw std::runtime_error("batch must be >= 1");
   require_no_stream("run_tokens");
+  if (mode < kDecodePlain || mode > kDecodeScored) throw std::runtime_error("run_tokens: unknown decode mode");
   if (mode == kDecodeTimestamps) require_timestamp_vocab();
-  TsModeScope ts(ts_mode_, mode == kDecodeTimestamps ? 1 : 0);
+  if (mode == kDecodeScored) require_scored_vocab();
+  TsModeScope ts(ts_mode_, mode);
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   ensure_capacity(batch);
@@ -842,6 +847,12 @@ void Engine::run_tokens_mode(int mode, const float* const* pcm, const float* d_p
   (void)hipEventElapsedTime(&timings[2], ev_[2], ev_[3]);
   timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   timings[4] = (float)steps;
+}
+
+void Engine::run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int32_t* ids,
+                               int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
+  run_tokens_mode(kDecodeScored, pcm, nullptr, 0, n_samples, batch, max_new, ids, n_ids, max_new_clip);
+  fetch_scores(batch, n_ids, token_logprob, avg_logprob, no_speech_logprob, ended_eot);
 }
 
 // Whisper.cpp:231-236: zh transcripts pass through OpenCC's t2s.json. The reference resolves "t2s.json" (and the two
@@ -925,26 +936,51 @@ void Engine::decode_forced(int batch, const int32_t* forced, int n_forced, float
 }
 
 void Engine::decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) {
+  if (mode != kDecodePlain && mode != kDecodeTimestamps) throw std::runtime_error("decode_forced: unknown decode mode");
+  decode_forced_impl(mode, batch, forced, n_forced, logits, argmax_ids, nullptr, nullptr, nullptr);
+}
+
+void Engine::decode_forced_scores(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen, float* logprob,
+                                  float* no_speech_logprob, float* logits0) {
+  decode_forced_impl(kDecodeScored, batch, forced, n_forced, logits, chosen, logprob, no_speech_logprob, logits0);
+}
+
+void Engine::decode_forced_impl(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids, float* logprob,
+                                float* no_speech_logprob, float* logits0) {
   require_no_stream("decode_forced");
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_forced: batch exceeds the encoded slots");
-  const bool tsm = mode == kDecodeTimestamps;
+  const bool tsm = mode != kDecodePlain, scored = mode == kDecodeScored;
   const int n_prefix = tsm ? 3 : 4;
   if (n_forced < 0 || n_forced + n_prefix > cfg_.n_text_ctx) throw std::runtime_error("decode_forced: n_forced out of range");
   if (tsm) require_timestamp_vocab();
-  TsModeScope ts(ts_mode_, tsm ? 1 : 0);
+  if (scored) require_scored_vocab();
+  TsModeScope ts(ts_mode_, mode);
   if (tsm) ensure_ts_logits();
+  if (scored) ensure_ts_scores();
   hipStream_t s = stream();
   const int nv = cfg_.n_vocab, rows = n_forced + 1;
   // device scratch of this call, freed on every path out (a HIP_CHECK below may throw)
   struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
-  } b_forced, b_arg, b_logits;
+  } b_forced, b_arg, b_logits, b_lp, b_dec, b_nsp, b_l0;
   HIP_CHECK(hipMalloc(&b_forced.p, std::max<size_t>((size_t)batch * n_forced * 4, 256)));
   HIP_CHECK(hipMalloc(&b_arg.p, (size_t)batch * rows * 4));
   if (logits) HIP_CHECK(hipMalloc(&b_logits.p, (size_t)batch * rows * nv * 4));
+  // scored: this call's own score arrays ([batch][rows]: the rules kernel's index is the history length) for its duration
+  struct ScoreOutScope {
+    TsScoreParams& out; TsScoreParams saved;
+    ~ScoreOutScope() { out = saved; }
+  } score_scope{score_out_, score_out_};
+  if (scored) {
+    HIP_CHECK(hipMalloc(&b_lp.p, (size_t)batch * rows * 4));
+    HIP_CHECK(hipMalloc(&b_dec.p, (size_t)batch * rows * 4));
+    HIP_CHECK(hipMalloc(&b_nsp.p, (size_t)batch * 4));
+    if (logits0) HIP_CHECK(hipMalloc(&b_l0.p, (size_t)batch * nv * 4));
+    score_out_.logprob = (float*)b_lp.p; score_out_.decision = (int*)b_dec.p; score_out_.stride = rows; score_out_.no_speech = (float*)b_nsp.p;
+  }
   int* d_forced = (int*)b_forced.p;
   int* d_arg = (int*)b_arg.p;
   float* d_logits = (float*)b_logits.p;
@@ -963,8 +999,14 @@ void Engine::decode_forced_mode(int mode, int batch, const int32_t* forced, int 
     // timestamp mode: the step dumped its rows into d_ts_logits_ (16-byte row stride) for the rules kernel
     if (tsm && lrow) HIP_CHECK(hipMemcpy2DAsync(lrow, (size_t)rows * nv * 4, d_ts_logits_, (size_t)ts_stride_ * 4, (size_t)nv * 4, batch,
                                                 hipMemcpyDeviceToDevice, s));
+    // scored: the row of decode offset 0, which the no-speech value was taken from
+    if (st == 0 && b_l0.p) HIP_CHECK(hipMemcpy2DAsync(b_l0.p, (size_t)nv * 4, d_ts_logits_, (size_t)ts_stride_ * 4, (size_t)nv * 4, batch,
+                                                      hipMemcpyDeviceToDevice, s));
   }
   HIP_CHECK(hipStreamSynchronize(s));
+  if (logprob) HIP_CHECK(hipMemcpy(logprob, b_lp.p, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
+  if (no_speech_logprob) HIP_CHECK(hipMemcpy(no_speech_logprob, b_nsp.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  if (logits0 && b_l0.p) HIP_CHECK(hipMemcpy(logits0, b_l0.p, (size_t)batch * nv * 4, hipMemcpyDeviceToHost));
   if (logits) HIP_CHECK(hipMemcpy(logits, d_logits, (size_t)batch * rows * nv * 4, hipMemcpyDeviceToHost));
   if (argmax_ids) HIP_CHECK(hipMemcpy(argmax_ids, d_arg, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
 }
@@ -975,8 +1017,9 @@ void Engine::decode_greedy(int batch, int max_new, const int* max_new_clip, int3
 
 void Engine::decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
   require_no_stream("decode_greedy");
+  if (mode != kDecodePlain && mode != kDecodeTimestamps) throw std::runtime_error("decode_greedy: unknown decode mode");
   if (mode == kDecodeTimestamps) require_timestamp_vocab();
-  TsModeScope ts(ts_mode_, mode == kDecodeTimestamps ? 1 : 0);
+  TsModeScope ts(ts_mode_, mode);
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_greedy: batch exceeds the encoded slots");
   hipStream_t s = stream();
@@ -993,6 +1036,16 @@ void Engine::decode_greedy_mode(int mode, int batch, int max_new, const int* max
 
 // The rules kernel alone, on host rows and histories (tests; callers with logits of their own)
 void Engine::apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) {
+  rules_on_host_rows(logits, hist, n_hist, batch, chosen, nullptr);
+}
+
+void Engine::score_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) {
+  if (!logprob) throw std::runtime_error("score_timestamp_rules: bad arguments");
+  rules_on_host_rows(logits, hist, n_hist, batch, chosen, logprob);
+}
+
+// logprob != nullptr: the scored kernel (each clip's entry at index 0 of a one-entry score row)
+void Engine::rules_on_host_rows(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) {
   require_no_stream("apply_timestamp_rules");
   require_timestamp_vocab();
   if (batch < 1 || !logits || !hist || !n_hist || !chosen) throw std::runtime_error("apply_timestamp_rules: bad arguments");
@@ -1006,7 +1059,11 @@ void Engine::apply_timestamp_rules(const float* logits, const int32_t* hist, con
   struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
-  } b_log, b_hist, b_n, b_val, b_idx;
+  } b_log, b_hist, b_n, b_val, b_idx, b_lp, b_dec;
+  if (logprob) {  // [batch][n_text_ctx + 1]: the kernel's index is the history length
+    HIP_CHECK(hipMalloc(&b_lp.p, (size_t)batch * (Tc + 1) * 4));
+    HIP_CHECK(hipMalloc(&b_dec.p, (size_t)batch * (Tc + 1) * 4));
+  }
   HIP_CHECK(hipMalloc(&b_log.p, (size_t)batch * stride * 4));
   HIP_CHECK(hipMalloc(&b_hist.p, (size_t)batch * Tc * 4));
   HIP_CHECK(hipMalloc(&b_n.p, (size_t)batch * 4));
@@ -1021,9 +1078,35 @@ void Engine::apply_timestamp_rules(const float* logits, const int32_t* hist, con
   r.off = nullptr; r.n_prefix = 3; r.done = nullptr;
   r.out_ids = (const int*)b_hist.p; r.n_out = (const int*)b_n.p; r.n_ctx = Tc;
   r.amax_val = (float*)b_val.p; r.amax_idx = (int*)b_idx.p; r.amax_stride = 1;
-  launch_timestamp_rules(r, s);
+  if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{(float*)b_lp.p, (int*)b_dec.p, (long)Tc + 1, nullptr, 0}, s);
+  else launch_timestamp_rules(r, s);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(chosen, b_idx.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+  for (int b = 0; logprob && b < batch; ++b)
+    HIP_CHECK(hipMemcpyAsync(logprob + b, (const float*)b_lp.p + (size_t)b * (Tc + 1) + n_hist[b], 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// The no-speech kernel alone, on host rows
+void Engine::no_speech_logprob(const float* logits, int batch, float* out) {
+  require_no_stream("no_speech_logprob");
+  require_scored_vocab();
+  if (batch < 1 || !logits || !out) throw std::runtime_error("no_speech_logprob: bad arguments");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  hipStream_t s = stream();
+  const int nv = cfg_.n_vocab;
+  const long stride = ((long)nv + 3) / 4 * 4;
+  struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+  } b_log, b_out;
+  HIP_CHECK(hipMalloc(&b_log.p, (size_t)batch * stride * 4));
+  HIP_CHECK(hipMalloc(&b_out.p, (size_t)batch * 4));
+  HIP_CHECK(hipMemcpy2DAsync(b_log.p, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
+  launch_row_logprob((const float*)b_log.p, stride, nv, (int)cfg_.ints.at("no_speech"), batch, (float*)b_out.p, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(out, b_out.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
 }
 

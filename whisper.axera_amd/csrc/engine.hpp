@@ -51,6 +51,14 @@ class Engine final : public IEngine {
   void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                         std::vector<LongWindow>& log) override;
   int scan_stored16(int batch, int n_max, char (*names)[32], long long* nonfinite, float* maxabs) override;
+  void run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int32_t* ids,
+                         int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) override;
+  void decode_forced_scores(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen, float* logprob,
+                            float* no_speech_logprob, float* logits0) override;
+  void score_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) override;
+  void no_speech_logprob(const float* logits, int batch, float* out) override;
+  void run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                               const LongScoreOptions& opts, std::vector<LongWindow>& log) override;
   float bench(const std::string& what, int batch, int arg, int iters) override;
   void set_stream(void* s) override { user_stream_ = static_cast<hipStream_t>(s); }
   const ModelConfig& config() const override { return cfg_; }
@@ -87,8 +95,9 @@ class Engine final : public IEngine {
   int decode_branches(int batch) const;
   void ensure_branch_streams(int batch);
   hipGraphExec_t step_graph(int batch, int max_new);
-  long graph_key(int batch, int max_new) const { return ((((long)batch * 1024 + max_new) * 32 + step_mask_) << 1) | ts_mode_; }
-  // timestamp mode (DecodeMode): set for the duration of one *_mode call; the step sequences read it
+  // (two bits for the mode: plain, timestamp and scored steps are three different graphs)
+  long graph_key(int batch, int max_new) const { return ((((long)batch * 1024 + max_new) * 32 + step_mask_) << 2) | ts_mode_; }
+  // decode mode (DecodeMode: 0 plain, 1 timestamps, 2 timestamps + scores): set for the duration of one *_mode call; the step sequences read it
   int ts_mode_ = 0;
   struct TsModeScope {
     int& m;
@@ -100,6 +109,20 @@ class Engine final : public IEngine {
   void enqueue_timestamp_rules(int batch, const int* d_forced, int n_forced, hipStream_t s);
   float* d_ts_logits_ = nullptr;
   long ts_stride_ = 0;
+  // scored mode (DESIGN.md "Confidence"): per-clip log-probability and id of every decision [cap][n_text_ctx], log p(<|nospeech|>)
+  // [cap]; allocated like d_ts_logits_. score_out_ is where the scored rules kernel writes: these arrays, except inside
+  // decode_forced_scores (its own [batch][n_forced + 1] buffers)
+  float* d_tok_lp_ = nullptr; int* d_dec_id_ = nullptr; float* d_nospeech_ = nullptr;
+  TsScoreParams score_out_{};
+  void require_scored_vocab() const;  // require_timestamp_vocab + a usable no_speech id
+  void ensure_ts_scores();
+  // scores of the last scored greedy loop over `batch` slots (n_ids: what fetch_ids returned)
+  void fetch_scores(int batch, const int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
+  void decode_forced_impl(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids, float* logprob,
+                          float* no_speech_logprob, float* logits0);
+  void rules_on_host_rows(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob);
+  void long_windows_impl(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                         const LongScoreOptions* opts, std::vector<LongWindow>& log);
   void recover_streams();
   // long-form (engine_long.cpp): the PCM and the log-mel rows of every file of one call in one arena, kept for the next call
   // when small (allocated and freed under device_capture_mutex)

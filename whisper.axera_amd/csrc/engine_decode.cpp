@@ -108,7 +108,8 @@ void Engine::enqueue_decode_step(int batch, int max_new, const int* d_forced, in
   p.epilogue = GEPI_LOGITS; p.state = d_state_; p.off = d_off_; p.amax_val = d_amax_val_; p.amax_idx = d_amax_idx_; p.amax_stride = n_amax_part_;
   // timestamp mode: the launch also runs at the step that fed `transcribe` and dumps every row for the rules kernel
   if (ts_mode_) { d_logits = d_ts_logits_; logits_stride = ts_stride_; }
-  p.skip_before_step = ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
+  // (scored mode: from offset 0 on — the row of the step that fed sot is the no-speech row; the row of offset 1 is computed and ignored)
+  p.skip_before_step = ts_mode_ == 2 ? 0 : ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
   gemv(p, [&](GemvParams& q, int b0) {
     q.in += (long)b0 * d; q.amax_val += (long)b0 * n_amax_part_; q.amax_idx += (long)b0 * n_amax_part_; q.off += b0;
     if (q.logits_dump) q.logits_dump += (long)b0 * logits_stride;
@@ -412,7 +413,7 @@ void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_fo
   p.rt = vocab_rt;
   p.amax_val = d_amax_val_; p.amax_idx = d_amax_idx_; p.amax_stride = n_amax_part_;
   if (ts_mode_) { d_logits = d_ts_logits_; logits_stride = ts_stride_; }  // (as in enqueue_decode_step)
-  p.skip_before_step = ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
+  p.skip_before_step = ts_mode_ == 2 ? 0 : ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
   gemm(p, [&](DecGemmParams& q, int b0) {
     q.amax_val += (long)b0 * n_amax_part_; q.amax_idx += (long)b0 * n_amax_part_;
     if (q.logits_dump) q.logits_dump += (long)b0 * logits_stride;
@@ -489,6 +490,7 @@ hipGraphExec_t Engine::step_graph(int batch, int max_new) {
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   ensure_branch_streams(batch);  // before the capture opens
   if (ts_mode_) ensure_ts_logits();
+  if (ts_mode_ == 2) ensure_ts_scores();
   HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   hipError_t cap_err = hipSuccess;
   try {
@@ -696,7 +698,51 @@ void Engine::enqueue_timestamp_rules(int batch, const int* d_forced, int n_force
   r.out_ids = d_out_ids_; r.n_out = d_nout_; r.n_ctx = cfg_.n_text_ctx;
   r.forced = d_forced; r.n_forced = n_forced;
   r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
-  launch_timestamp_rules(r, s);
+  if (ts_mode_ == 2) launch_timestamp_rules_scored(r, score_out_, s);  // + the decision's log-probability, the no-speech value at offset 0
+  else launch_timestamp_rules(r, s);
+}
+
+void Engine::require_scored_vocab() const {
+  require_timestamp_vocab();
+  const auto it = cfg_.ints.find("no_speech");
+  if (it == cfg_.ints.end() || it->second < 0 || it->second >= cfg_.n_vocab)
+    throw std::runtime_error("scored decode needs a no_speech id inside the vocabulary");
+}
+
+void Engine::ensure_ts_scores() {
+  if (d_tok_lp_) return;
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  const size_t n = (size_t)cap_ * cfg_.n_text_ctx;
+  d_tok_lp_ = (float*)dalloc(n * 4, true);
+  d_dec_id_ = (int*)dalloc(n * 4, true);
+  d_nospeech_ = (float*)dalloc((size_t)cap_ * 4, true);
+  for (void* p : {(void*)d_tok_lp_, (void*)d_dec_id_, (void*)d_nospeech_}) slot_allocs_.push_back(p);  // freed (and re-made) with the slot buffers
+  score_out_ = TsScoreParams{d_tok_lp_, d_dec_id_, (long)cfg_.n_text_ctx, d_nospeech_, (int)cfg_.ints.at("no_speech")};
+}
+
+// After fetch_ids of a scored greedy loop. Decision i of clip b sits at index i: i < n_ids are the kept ids, i == n_ids the decision
+// that ended the clip (eot, or the id dropped at the budget / context end).
+void Engine::fetch_scores(int batch, const int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
+  hipStream_t s = stream();
+  const int Tc = cfg_.n_text_ctx;
+  std::vector<float> lp((size_t)batch * Tc), nsp(batch);
+  std::vector<int> dec((size_t)batch * Tc);
+  HIP_CHECK(hipMemcpyAsync(lp.data(), d_tok_lp_, lp.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(dec.data(), d_dec_id_, dec.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(nsp.data(), d_nospeech_, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  for (int b = 0; b < batch; ++b) {
+    const int n = std::max(0, std::min(n_ids[b], Tc - 1));
+    const bool eot = dec[(size_t)b * Tc + n] == cfg_.eot;
+    double sum = eot ? (double)lp[(size_t)b * Tc + n] : 0.0;
+    for (int i = 0; i < n; ++i) sum += (double)lp[(size_t)b * Tc + i];
+    if (token_logprob) {
+      for (int i = 0; i < Tc; ++i) token_logprob[(size_t)b * Tc + i] = i <= n ? lp[(size_t)b * Tc + i] : 0.f;
+    }
+    if (avg_logprob) avg_logprob[b] = (float)(sum / (double)(n + 1));  // openai-whisper: sum_logprobs / (len(tokens) + 1)
+    if (no_speech_logprob) no_speech_logprob[b] = nsp[b];
+    if (ended_eot) ended_eot[b] = eot ? 1 : 0;
+  }
 }
 
 void Engine::fetch_ids(int batch, int32_t* ids, int* n_ids) {

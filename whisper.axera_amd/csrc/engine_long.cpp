@@ -138,10 +138,23 @@ void Engine::compute_mel_window(const float* pcm, int n_samples, int seek, float
 
 void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                               std::vector<LongWindow>& log) {
+  long_windows_impl(pcm, n_samples, n_files, max_new, max_passes, nullptr, log);
+}
+
+void Engine::run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                                     const LongScoreOptions& opts, std::vector<LongWindow>& log) {
+  long_windows_impl(pcm, n_samples, n_files, max_new, max_passes, &opts, log);
+}
+
+// opts != nullptr: the windows are decoded in scored mode, every log entry carries its two numbers, and a window the silent-window
+// rule drops emits nothing and advances by its whole length (DESIGN.md "Confidence")
+void Engine::long_windows_impl(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                               const LongScoreOptions* opts, std::vector<LongWindow>& log) {
   if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
   require_no_stream("run_long_windows");
   require_timestamp_vocab();
-  TsModeScope ts(ts_mode_, 1);
+  if (opts) require_scored_vocab();
+  TsModeScope ts(ts_mode_, opts ? kDecodeScored : kDecodeTimestamps);
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   // windows per pass: the engine's capacity (AX_WHISPER_MAX_BATCH / max_batch of Init, or what earlier calls grew it to);
@@ -155,6 +168,7 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   const int T = cfg_.no_timestamps + 1, E = cfg_.eot, Tc = cfg_.n_text_ctx;
   std::vector<int> seek(n_files, 0), active, files(S), seeks(S), n_ids(S);
   std::vector<int32_t> ids((size_t)S * Tc);
+  std::vector<float> avg(S), nsp(S);
   std::vector<WindowSegment> segs;
   int next_file = 0, steps = 0;
   for (int pass = 0; max_passes <= 0 || pass < max_passes; ++pass) {
@@ -174,6 +188,7 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
     run_encoder(A);
     steps += greedy_loop(A, max_new, nullptr);
     fetch_ids(A, ids.data(), n_ids.data());
+    if (opts) fetch_scores(A, n_ids.data(), nullptr, avg.data(), nsp.data(), nullptr);
     for (int i = 0; i < A; ++i) {
       const int f = files[i];
       LongWindow w;
@@ -181,7 +196,14 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
       w.window_frames = std::min(kFramesOut, n_samples[f] / kHop - seeks[i]);
       const int n = std::max(0, std::min(n_ids[i], Tc));
       w.ids.assign(ids.begin() + (size_t)i * Tc, ids.begin() + (size_t)i * Tc + n);
-      w.advance = split_window(w.ids.data(), n, T, E, w.window_frames, segs);
+      if (opts) {
+        w.no_speech_logprob = nsp[i]; w.avg_logprob = avg[i];
+        w.skipped = long_window_is_silent(nsp[i], avg[i], opts->no_speech_threshold, opts->logprob_threshold);
+        if (getenv("AX_WHISPER_LONG_LOG"))
+          fprintf(stderr, "[ax_whisper] long: file %d seek %d: no_speech_logprob %.4f avg_logprob %.4f%s\n", f, seeks[i], nsp[i], avg[i],
+                  w.skipped ? " (skipped)" : "");
+      }
+      w.advance = w.skipped ? w.window_frames : split_window(w.ids.data(), n, T, E, w.window_frames, segs);
       seek[f] += w.advance;
       log.push_back(std::move(w));
     }

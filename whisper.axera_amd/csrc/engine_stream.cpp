@@ -314,13 +314,15 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   HIP_CHECK(hipEventCreate(&a));
   HIP_CHECK(hipEventCreate(&b));
   float ms = 0.f;
-  if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn" || what == "decode_step_ts") {
+  if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn" || what == "decode_step_ts" || what == "decode_step_ts_scored") {
     // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;
-    // decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel)
-    step_mask_ = (what == "decode_step" || what == "decode_step_ts") ? 15 : (what == "decode_gemv" ? 1 : 2);
+    // decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel); decode_step_ts_scored: with the scored rules kernel
+    const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored";
+    step_mask_ = whole ? 15 : (what == "decode_gemv" ? 1 : 2);
     struct Restore { int& m; ~Restore() { m = 15; } } restore{step_mask_};
     if (what == "decode_step_ts") require_timestamp_vocab();
-    TsModeScope ts(ts_mode_, what == "decode_step_ts" ? 1 : 0);
+    if (what == "decode_step_ts_scored") require_scored_vocab();
+    TsModeScope ts(ts_mode_, what == "decode_step_ts" ? kDecodeTimestamps : what == "decode_step_ts_scored" ? kDecodeScored : kDecodePlain);
     const int Tc = cfg_.n_text_ctx;
     reset_decode_state(batch);
     hipGraphExec_t g = step_graph(batch, Tc - 4);

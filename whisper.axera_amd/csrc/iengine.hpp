@@ -53,7 +53,9 @@ class IEngine {
   // decode modes of the *_mode variants: kDecodePlain = the calls above (prefix [sot, lang, transcribe, notimestamps]),
   // kDecodeTimestamps = prefix [sot, lang, transcribe] and Whisper's timestamp rules at every sampled step (DESIGN.md
   // "Segment timestamps"); ids then include timestamp tokens
-  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1 };
+  // kDecodeScored = kDecodeTimestamps that also keeps, per clip, the log-probability of every decision and log p(<|nospeech|>) at
+  // the step that fed sot (DESIGN.md "Confidence"); the ids are those of kDecodeTimestamps
+  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1, kDecodeScored = 2 };
   virtual void run_tokens_mode(int mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
                                int max_new, int32_t* ids, int* n_ids, const int* max_new_clip) = 0;
   // timestamp mode: logits are the raw logits (before the rules), argmax_ids the ids the rules choose
@@ -61,6 +63,23 @@ class IEngine {
   virtual void decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
   // the rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] (n_hist[b] ids each) -> chosen [batch]
   virtual void apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) = 0;
+  // ---- confidence (DESIGN.md "Confidence"). token_logprob [batch][n_text_ctx]: entries 0 .. n_ids[b] (one per kept id + the
+  // decision that ended the clip), the rest 0; avg_logprob, no_speech_logprob, ended_eot [batch]
+  virtual void run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
+                                 int32_t* ids, int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob,
+                                 int* ended_eot) = 0;
+  // decode_forced_mode(kDecodeTimestamps) + logprob [batch][n_forced+1] of each step's chosen id, no_speech_logprob [batch] and
+  // (optional) logits0 [batch][n_vocab], the raw row of decode offset 0
+  virtual void decode_forced_scores(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen, float* logprob,
+                                    float* no_speech_logprob, float* logits0) = 0;
+  // apply_timestamp_rules + logprob [batch]: the scored kernel alone on host rows
+  virtual void score_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen,
+                                     float* logprob) = 0;
+  // the no-speech kernel alone: logits [batch][n_vocab] -> out [batch] = log p(<|nospeech|>) over the whole row
+  virtual void no_speech_logprob(const float* logits, int batch, float* out) = 0;
+  // run_long_windows with the scores of every window in the log; the silent-window rule under opts' thresholds
+  virtual void run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                                       const LongScoreOptions& opts, std::vector<LongWindow>& log) = 0;
   // long-form (DESIGN.md "Long-form"): the whole-file front-end + the window kernel for one file -> the window at `seek`
   // (frames) in the reference layout, host [n_mels * 3000]
   virtual void compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) = 0;

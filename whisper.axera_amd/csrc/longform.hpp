@@ -6,6 +6,7 @@
 // "Long-form"). The single-clip split (AX_WHISPER_SplitSegments) keeps a trailing piece and is a different contract.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -56,10 +57,26 @@ inline int split_window(const int32_t* ids, int n, int T, int E, int window_fram
   return (int)advance;
 }
 
+// The silent-window rule of the seek loop (DESIGN.md "Confidence"; openai-whisper transcribe(): should_skip). no_speech_logprob:
+// log p(<|nospeech|>) at the step that fed sot; avg_logprob: the window's average token log-probability. A window is skipped iff
+// the no-speech PROBABILITY exceeds its threshold and the average log-probability does not exceed its own: logprob_threshold
+// = +inf skips on no-speech alone, a NaN no_speech_threshold never skips. All in float32, both comparisons strict.
+inline bool long_window_is_silent(float no_speech_logprob, float avg_logprob, float no_speech_threshold, float logprob_threshold) {
+  return std::exp(no_speech_logprob) > no_speech_threshold && !(avg_logprob > logprob_threshold);
+}
+
+// scored long-form: thresholds of the silent-window rule (NaN no_speech_threshold: the rule is off, scores are still fetched)
+struct LongScoreOptions {
+  float no_speech_threshold, logprob_threshold;
+};
+
 // one decoded window of AX_WHISPER_RunPCMLongWindows, in execution order
 struct LongWindow {
   int file, seek, window_frames, advance, pass, slot;
   std::vector<int32_t> ids;  // all of them, also those after the last boundary
+  // scored calls only: the window's two numbers and whether the silent-window rule dropped it (then advance == window_frames)
+  float no_speech_logprob = 0.f, avg_logprob = 0.f;
+  bool skipped = false;
 };
 
 }  // namespace axw

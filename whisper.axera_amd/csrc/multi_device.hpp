@@ -105,6 +105,20 @@ class DeviceGroup {
     });
   }
 
+  // The same sharding for E::run_tokens_scores (timestamp mode + per-clip scores; token_logprob [batch][n_ctx])
+  void run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int n_ctx,
+                         int32_t* ids, int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
+    if (batch < 1) throw std::runtime_error("batch must be >= 1");
+    const int G = size(), world = G < batch ? G : batch;
+    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
+    run_sharded(batch, world, [&](int w, int lo, int hi) {
+      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
+      std::lock_guard<std::mutex> lock(e.mutex());
+      e.run_tokens_scores(pcm + lo, n_samples + lo, hi - lo, max_new, max_new_clip ? max_new_clip + lo : nullptr, ids + (size_t)lo * n_ctx,
+                          n_ids + lo, token_logprob + (size_t)lo * n_ctx, avg_logprob + lo, no_speech_logprob + lo, ended_eot + lo);
+    });
+  }
+
   // Long-form (E::run_long_windows): the FILES are split into contiguous blocks, one per engine; every engine runs its own seek
   // loop. The log holds worker 0's windows first, then worker 1's, ...; file indices count over the whole call, pass and slot
   // are the engine's own. W needs an int member `file`.
@@ -118,6 +132,24 @@ class DeviceGroup {
       E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
       std::lock_guard<std::mutex> lock(e.mutex());
       e.run_long_windows(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, logs[w]);
+      for (W& x : logs[w]) x.file += lo;
+    });
+    for (auto& l : logs)
+      for (W& x : l) log.push_back(std::move(x));
+  }
+
+  // E::run_long_windows_scored, sharded the same way (O: the thresholds of the silent-window rule)
+  template <typename W, typename O>
+  void run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const O& opts,
+                               std::vector<W>& log) {
+    if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
+    const int G = size(), world = G < n_files ? G : n_files;
+    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
+    std::vector<std::vector<W>> logs(world);
+    run_sharded(n_files, world, [&](int w, int lo, int hi) {
+      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
+      std::lock_guard<std::mutex> lock(e.mutex());
+      e.run_long_windows_scored(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, opts, logs[w]);
       for (W& x : logs[w]) x.file += lo;
     });
     for (auto& l : logs)

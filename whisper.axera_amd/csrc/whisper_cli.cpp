@@ -7,6 +7,7 @@
 // duration (:76,93-103). The AX_SYS_Init / AX_ENGINE_Init block (:37-61) is gone: the library
 // initialises the GPU itself. Only the C ABI is used.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +28,10 @@ static void usage(const char* prog) {
           "                      one [mm:ss.mmm --> mm:ss.mmm] line per segment with times from the file's start (hours\n"
           "                      roll into the minutes: 75:03.120). RTF: is wall time over the file's duration; without\n"
           "                      --long it divides by the whole duration although at most 30 s are decoded\n"
+          "      --no_speech_threshold X, --logprob_threshold Y   (with --long) skip a window whose no-speech probability is above X\n"
+          "                      unless its average token log-probability is above Y (without X nothing is skipped, without Y the\n"
+          "                      no-speech probability alone decides; openai-whisper uses 0.6 and -1.0). Each segment line then ends\n"
+          "                      in (avg_logprob ..., no_speech ...)\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -113,8 +118,11 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav) {
   return 0;
 }
 
-// --long: the seek loop over the whole file (AX_WHISPER_RunPCMLongWindows), its text, then one line per segment
-static int run_long(AX_WHISPER_HANDLE h, const char* wav, std::string& text, std::string& lines) {
+// --long: the seek loop over the whole file (AX_WHISPER_RunPCMLongWindows), its text, then one line per segment.
+// scored: under the silent-window rule (AX_WHISPER_RunPCMLongWindowsScored); skipped windows print nothing, the other lines end
+// in their window's two numbers
+static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_speech_threshold, float logprob_threshold, std::string& text,
+                    std::string& lines) {
   float* pcm = nullptr;
   int n = 0;
   if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
@@ -123,12 +131,18 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, std::string& text, std
   int cap = n / 160 + 1;  // every window advances by at least one frame
   std::vector<int> info((size_t)cap * 7);
   std::vector<int32_t> ids((size_t)cap * n_ctx);
+  std::vector<float> score(scored ? (size_t)cap * 3 : 0);
   int n_win = 0;
   const float* files[1] = {pcm};
-  const int rc = AX_WHISPER_RunPCMLongWindows(h, files, &n, 1, 0, 0, cap, info.data(), ids.data(), &n_win);
+  const int rc = scored ? AX_WHISPER_RunPCMLongWindowsScored(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold, cap, info.data(),
+                                                             ids.data(), score.data(), &n_win)
+                        : AX_WHISPER_RunPCMLongWindows(h, files, &n, 1, 0, 0, cap, info.data(), ids.data(), &n_win);
   free(pcm);
   if (rc != 0) return -1;
   for (int k = 0; k < n_win; ++k) {
+    if (scored && score[(size_t)k * 3 + 2] != 0.f) continue;  // a silent window
+    char tail[96] = "";
+    if (scored) snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g)", score[(size_t)k * 3 + 1], std::exp(score[(size_t)k * 3]));
     const int* w = &info[(size_t)k * 7];
     const int32_t* wi = &ids[(size_t)k * n_ctx];
     const int n_max = w[4] / 2 + 1;
@@ -141,7 +155,7 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, std::string& text, std
       if (AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t) != 0) return -1;
       text += t ? t : "";
       // (absolute times in integer milliseconds: a float second loses the millisecond after a few hours)
-      lines += "[" + mmss_ms(w[1] * 10L + (long)(st[s] * 1000.f + 0.5f)) + " --> " + mmss_ms(w[1] * 10L + (long)(en[s] * 1000.f + 0.5f)) + "] " + (t ? t : "") + "\n";
+      lines += "[" + mmss_ms(w[1] * 10L + (long)(st[s] * 1000.f + 0.5f)) + " --> " + mmss_ms(w[1] * 10L + (long)(en[s] * 1000.f + 0.5f)) + "] " + (t ? t : "") + tail + "\n";
       free(t);
     }
   }
@@ -151,6 +165,7 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, std::string& text, std
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
   bool timestamps = false, longform = false;
+  std::string nst_arg, lpt_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -164,7 +179,7 @@ int main(int argc, char** argv) {
       return false;
     };
     if (val("wav", "-w", wav) || val("model_type", "-t", model_type) || val("model_path", "-p", model_path) ||
-        val("language", nullptr, language))
+        val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -174,6 +189,16 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (wav.empty()) { fprintf(stderr, "need option: --wav\n"); usage(argv[0]); return 1; }
+  const bool scored = !nst_arg.empty() || !lpt_arg.empty();
+  if (scored && !longform) { fprintf(stderr, "--no_speech_threshold / --logprob_threshold need --long\n"); usage(argv[0]); return 1; }
+  // one flag alone: no threshold on the average = no-speech alone decides (+inf); no threshold on no-speech = nothing is skipped
+  // (NaN; as in openai-whisper, where the average only ever overrides a no-speech verdict) and the lines just carry their numbers
+  float no_speech_threshold = NAN, logprob_threshold = INFINITY;
+  {
+    char* end = nullptr;
+    if (!nst_arg.empty()) { no_speech_threshold = strtof(nst_arg.c_str(), &end); if (*end) { fprintf(stderr, "bad value: --no_speech_threshold %s\n", nst_arg.c_str()); return 1; } }
+    if (!lpt_arg.empty()) { logprob_threshold = strtof(lpt_arg.c_str(), &end); if (*end) { fprintf(stderr, "bad value: --logprob_threshold %s\n", lpt_arg.c_str()); return 1; } }
+  }
 
   printf("wav_file: %s\n", wav.c_str());
   printf("model_path: %s\n", model_path.c_str());
@@ -193,7 +218,7 @@ int main(int argc, char** argv) {
   if (longform) {
     t0 = std::chrono::steady_clock::now();
     std::string text, lines;
-    if (run_long(handle, wav.c_str(), text, lines) != 0) {
+    if (run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, text, lines) != 0) {
       printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
       AX_WHISPER_Uninit(handle);
       return -1;
