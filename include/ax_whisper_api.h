@@ -266,6 +266,16 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongOpts(AX_WHISPER_HANDLE handle, float* pc
 AX_WHISPER_API int AX_WHISPER_RunFileLongOpts(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
                                               float logprob_threshold, char** result);
 
+/** Host only (no handle, no GPU): the decode path Init picks for a decoder shape on a device with n_cu compute units, and the
+ *  persistent launch's cross-attention role assignment, from the engine's own functions. plan4[0] = workgroups of the
+ *  persistent launch, [1] = 1 iff the shape gets it (GetConfigInt "persistent_decode"), [2] = clips per launch
+ *  ("persistent_max_clips"; 0 when [1] is 0), [3] = workgroups that own no self-attention head. units (may be NULL):
+ *  [n_slots][plan4[0]], the cross-attention unit (clip * 3 * n_head + head * 3 + key range, or -1) of every workgroup in layer
+ *  slots t0 .. t0 + n_slots - 1 (slot = step * n_layer + layer) of a launch with n_clips clips. -1 on bad arguments, or when
+ *  units are asked for a launch the shape does not get. */
+AX_WHISPER_API int AX_WHISPER_PersistentDecodePlan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots,
+                                                   int* plan4, int* units);
+
 /** Stage timings of the last Run* / DecodeGreedy* call, ms (hipEvent): [0] front-end, [1] encoder,
  *  [2] decode loop, [3] whole call (wall), [4] decode steps executed. */
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);

@@ -82,6 +82,7 @@ SYMBOLS = {
     "AX_WHISPER_RunPCMLongWindowsScored": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_RunPCMLongOpts": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_RunFileLongOpts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_PersistentDecodePlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 
@@ -181,6 +182,26 @@ def long_window_is_silent(no_speech_logprob: float, avg_logprob: float, no_speec
     no_speech_threshold and not avg_logprob > logprob_threshold, in float32."""
     L = load_library()
     return bool(L.AX_WHISPER_LongWindowIsSilent(float(no_speech_logprob), float(avg_logprob), float(no_speech_threshold), float(logprob_threshold)))
+
+
+def persistent_decode_plan(d_model: int, n_head: int, n_layer: int, n_cu: int, n_clips: int = 0, t0: int = 0, n_slots: int = 0):
+    """The decode path Init picks for a decoder shape on n_cu compute units (AX_WHISPER_PersistentDecodePlan, host only) ->
+    dict(grid, supported, max_clips, free_workgroups); with n_clips > 0 also units: int32 [n_slots][grid], the cross-attention
+    unit (or -1) of every workgroup in layer slots t0 .. t0 + n_slots - 1 of an n_clips launch."""
+    L = load_library()
+    plan = (C.c_int * 4)()
+    units = None
+    if n_clips > 0:
+        if L.AX_WHISPER_PersistentDecodePlan(d_model, n_head, n_layer, n_cu, 0, 0, 0, plan, None) != 0:
+            raise RuntimeError("AX_WHISPER_PersistentDecodePlan failed")
+        units = np.empty((n_slots, plan[0]), dtype=np.int32)
+    if L.AX_WHISPER_PersistentDecodePlan(d_model, n_head, n_layer, n_cu, n_clips, t0, n_slots, plan,
+                                         units.ctypes.data_as(C.POINTER(C.c_int)) if units is not None else None) != 0:
+        raise RuntimeError("AX_WHISPER_PersistentDecodePlan failed")
+    out = dict(grid=plan[0], supported=bool(plan[1]), max_clips=plan[2], free_workgroups=plan[3])
+    if units is not None:
+        out["units"] = units
+    return out
 
 
 def _thresholds(no_speech_threshold, logprob_threshold):

@@ -382,6 +382,11 @@ AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char*
   return it == m.end() ? INT_MIN : (int)it->second;
 }
 
+AX_WHISPER_API int AX_WHISPER_PersistentDecodePlan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots,
+                                                   int* plan4, int* units) {
+  return axw::persistent_decode_plan(d_model, n_head, n_layer, n_cu, n_clips, t0, n_slots, plan4, units);
+}
+
 AX_WHISPER_API const char* AX_WHISPER_LastError(AX_WHISPER_HANDLE handle) {
   Handle* h = H(handle);
   if (!h) return g_init_error.c_str();

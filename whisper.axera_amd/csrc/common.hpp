@@ -497,6 +497,8 @@ void launch_qfold_build(const h16* wl, const float* fl, float* qf, int d_model, 
 hipError_t launch_decode_persistent(const PersistParams& p, int d_model, int grid, hipStream_t s);  // n_clip 1, 2 or 3
 int decode_persistent_max_clips(int d_model, int n_head, int n_layer, int grid);  // clips per persistent launch: 1, 2 or 3
 int decode_persistent_vocab_resident_rows(int d_model, int n_vocab, int grid);    // vocabulary rows a workgroup of the one-clip launch keeps on-chip
+// host only: the decisions above for a shape + the cross-attention role assignment of a launch (AX_WHISPER_PersistentDecodePlan)
+int decode_persistent_plan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots, int* plan4, int* units);
 
 // weight preparation (device): raw file dtype -> h16 / fp32, with the layout changes the kernels want
 void launch_convert_to_h16(const void* src, int src_dtype /*0 f32,1 bf16,2 f16*/, h16* dst, long n, hipStream_t s);

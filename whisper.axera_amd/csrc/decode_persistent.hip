@@ -936,5 +936,26 @@ hipError_t launch_decode_persistent(const PersistParams& p, int d_model, int gri
   });
 }
 
+// What Init decides for a decoder shape on n_cu compute units, and who runs which cross-attention unit: the three functions
+// above and the kernels' own ca_unit_of, on the host (AX_WHISPER_PersistentDecodePlan; no device is touched).
+// plan4: grid, supported (0 / 1), clips per launch (0 when unsupported), workgroups without a self-attention head.
+// units (optional) [n_slots][grid]: the unit of every workgroup in layer slots t0 .. t0 + n_slots - 1 of an n_clips launch.
+int decode_persistent_plan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots, int* plan4, int* units) {
+  if (d_model < 1 || n_head < 1 || n_layer < 1 || n_cu < 1 || !plan4) return -1;
+  const int grid = decode_persistent_grid(d_model, n_cu);
+  const bool ok = decode_persistent_supported(d_model, n_head, n_layer, n_cu);
+  const int ns = grid - n_layer * n_head;
+  plan4[0] = grid;
+  plan4[1] = ok ? 1 : 0;
+  plan4[2] = ok ? decode_persistent_max_clips(d_model, n_head, n_layer, grid) : 0;
+  plan4[3] = ns;
+  if (!units) return 0;
+  if (!ok || n_clips < 1 || n_clips > plan4[2] || t0 < 0 || n_slots < 0) return -1;
+  const int nu = n_clips * kCrossSplit * n_head;  // NU (one clip) / NUC (decode_persistent2.hip)
+  for (int t = 0; t < n_slots; ++t)
+    for (int wg = 0; wg < grid; ++wg) units[(long)t * grid + wg] = ca_unit_of(t0 + t, nu, wg, ns);
+  return 0;
+}
+
 }  // inline namespace AXW_NS
 }  // namespace axw

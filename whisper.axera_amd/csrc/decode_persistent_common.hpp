@@ -740,7 +740,8 @@ __device__ __forceinline__ void qfold_publish(int lane, const float* pk, const f
 // layers apart across the step boundary as well. (Counted per step, the last layer's range wrapped onto the first layer's of
 // the next step whenever L * nu > ns — large-v3-turbo: 4 x 60 units on 176 workgroups — and a workgroup staged the next
 // step's K tiles over the ones its last-layer unit had not used yet: logits off by 4e-2 at every step of that model.)
-__device__ __forceinline__ int ca_unit_of(int t, int nu, int wg, int ns) {
+// (__host__ as well: persistent_decode_plan hands this very function to the host-side check of the assignment.)
+__host__ __device__ __forceinline__ int ca_unit_of(int t, int nu, int wg, int ns) {
   if (wg >= ns) return -1;
   int r = (wg - (int)(((long)t * nu) % ns)) % ns;
   if (r < 0) r += ns;

@@ -132,6 +132,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
   }
   cfg_.ints["persistent_two_clips"] = persist_max_clips_ >= 2 ? 1 : 0;
   cfg_.ints["persistent_max_clips"] = persist_max_clips_;
+  cfg_.ints["persistent_grid"] = persistent_ok_ ? persist_grid_ : 0;  // workgroups of the persistent launch (0: none)
   cfg_.ints["persistent_decode"] = persistent_ok_ ? 1 : 0;  // visible through AX_WHISPER_GetConfigInt
   cfg_.ints["persistent_qfold"] = d_qfold_ ? 1 : 0;
   cfg_.ints["vocab_resident_rows"] = vocab_resident_rows_;
@@ -1119,6 +1120,10 @@ IEngine* make_engine_f16(const std::string& model_type, const std::string& model
 #else
 IEngine* make_engine_bf16(const std::string& model_type, const std::string& model_path, const std::string& language, int device, int max_batch) {
   return new bf::Engine(model_type, model_path, language, device, max_batch);
+}
+// the dispatch rules do not depend on the storage type: one definition, from the bfloat16 build
+int persistent_decode_plan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots, int* plan4, int* units) {
+  return bf::decode_persistent_plan(d_model, n_head, n_layer, n_cu, n_clips, t0, n_slots, plan4, units);
 }
 #endif
 }  // namespace axw

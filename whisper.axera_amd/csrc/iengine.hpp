@@ -115,5 +115,8 @@ std::recursive_mutex& device_capture_mutex(int device);
 
 IEngine* make_engine_bf16(const std::string& model_type, const std::string& model_path, const std::string& language, int device, int max_batch);
 IEngine* make_engine_f16(const std::string& model_type, const std::string& model_path, const std::string& language, int device, int max_batch);
+// Host only: which persistent launch a decoder shape gets on n_cu compute units and its cross-attention role assignment
+// (decode_persistent.hip: decode_persistent_plan; include/ax_whisper_api.h: AX_WHISPER_PersistentDecodePlan).
+int persistent_decode_plan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots, int* plan4, int* units);
 
 }  // namespace axw

@@ -26,6 +26,7 @@ DIMS = {
     "base":   dict(n_mels=80,  d=512,  heads=8,  enc_layers=6,  dec_layers=6,  n_vocab=51865, n_langs=99),
     "small":  dict(n_mels=80,  d=768,  heads=12, enc_layers=12, dec_layers=12, n_vocab=51865, n_langs=99),
     "turbo":  dict(n_mels=128, d=1280, heads=20, enc_layers=32, dec_layers=4,  n_vocab=51866, n_langs=100),
+    "large":  dict(n_mels=128, d=1280, heads=20, enc_layers=32, dec_layers=32, n_vocab=51866, n_langs=100),  # large-v3
     # reduced dims for fast parity tests (same graph, head_dim 64)
     "micro":  dict(n_mels=80,  d=128,  heads=2,  enc_layers=2,  dec_layers=2,  n_vocab=51865, n_langs=99),
     "mini":   dict(n_mels=80,  d=256,  heads=4,  enc_layers=2,  dec_layers=3,  n_vocab=51865, n_langs=99),
@@ -39,6 +40,17 @@ DIMS = {
 
 N_AUDIO_CTX = 1500
 N_TEXT_CTX = 448
+
+
+def depth_dims(d: int, dec_layers: int, enc_layers: int = 1) -> dict:
+    """Dims of a synthetic model of width d (head_dim 64) with any decoder depth: which decode path a model gets depends
+    on its width and decoder depth alone (DESIGN.md "Which decode path a model shape gets"), so the tests of the depth edges
+    register such entries in DIMS. The 1280-wide ones take large-v3's front half (128 mels, 100 languages), as w1280 does."""
+    if d % 64:
+        raise ValueError("d must be a multiple of the head width 64")
+    wide = d >= 1280
+    return dict(n_mels=128 if wide else 80, d=d, heads=d // 64, enc_layers=enc_layers, dec_layers=dec_layers,
+                n_vocab=51866 if wide else 51865, n_langs=100 if wide else 99)
 
 LANGUAGE_CODES = (
     "en,zh,de,es,ru,ko,fr,ja,pt,tr,pl,ca,nl,ar,sv,it,id,hi,fi,vi,he,uk,el,ms,cs,ro,da,hu,ta,no,"
