@@ -63,7 +63,9 @@ int main(int argc, char** argv) {
       p.t_pad = t_pad;
     }
     hipStream_t s; CK(hipStreamCreate(&s));
+    gemm_last_kernel = gemm_prev_kernel = 0;
     launch_gemm(p, s);  // first launch: checked below (resid: C was 0)
+    const int ran_prev = gemm_prev_kernel, ran_last = gemm_last_kernel;  // what the selection really launched (Q,K / V^T: two launches)
     CK(hipStreamSynchronize(s));
     std::vector<unsigned char> hC(cbytes);
     CK(hipMemcpy(hC.data(), dC, cbytes, hipMemcpyDeviceToHost));
@@ -122,7 +124,8 @@ int main(int argc, char** argv) {
     CK(hipStreamSynchronize(s));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double tf = 2.0 * rows * sh.N * sh.K / (ms / iters * 1e-3) / 1e12;
-    printf("%-46s %8.3f ms  %7.1f TFLOP/s  (%.3f of 2500)   spot err %.2e %s\n", sh.name, ms / iters, tf, tf / 2500, max_err,
+    printf("%-46s tile selection %d -> kernel %d%s  %8.3f ms  %7.1f TFLOP/s  (%.3f of 2500)   spot err %.2e %s\n", sh.name, gemm_force_tile,
+           ran_last, ran_prev ? (ran_prev == 1 ? " (and 1)" : ran_prev == 2 ? " (and 2)" : " (and 5)") : "", ms / iters, tf, tf / 2500, max_err,
            max_err < (f32out ? 2e-3 : 4e-3) ? "ok" : "MISMATCH");
     fflush(stdout);
     (void)hipFree(dA); (void)hipFree(dW); (void)hipFree(db); (void)hipFree(dC); (void)hipStreamDestroy(s);

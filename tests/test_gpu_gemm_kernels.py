@@ -1,10 +1,13 @@
 """GPU: the encoder GEMM kernels one by one against an fp64 host reference (profiles/microbench/gemm_shapes.cpp compiles
-csrc/gemm.hip unchanged and spot-checks 4000 random outputs per shape: bias, GELU, in-place residual and Q / K / V^T
-epilogues at the encoder's own shapes at 64 clips, 4096^3, and a one-clip launch).
+csrc/gemm.hip unchanged and spot-checks 4000 random outputs per shape: bias, GELU, residual and Q / K / V^T epilogues at the
+encoder's own shapes at 64 clips, 4096^3, and a one-clip launch). A spot check: the residual epilogue is checked onto zeros
+here (C == 0, so storing instead of adding would pass); the in-place add onto a non-zero C, the other three epilogues, whole
+outputs and everything outside them are covered by tests/test_gpu_encoder_kernels.py.
 
 launch_gemm picks a kernel by tile count, so the end-to-end parity tests only ever run the choices it makes for Whisper's
 dimensions (128x128 at one clip, the 256x128 ring at a few clips, the one-stream-per-CU 256x256 kernel at batch); here
-every kernel is forced on every shape."""
+every kernel is forced on every shape (each line prints the kernel that really ran: forcing 5 falls back where the stream
+kernel's rule excludes a launch)."""
 import os
 import subprocess
 

@@ -151,8 +151,9 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     // A/B and test switches of the batched decode sequence (read per engine)
     if (const char* t = getenv("AX_WHISPER_GEMV_MAX")) gemv_max_ = std::max(1, std::min(4, atoi(t)));
     if (const char* t = getenv("AX_WHISPER_CROSS_SPLIT")) cross_split_env_ = atoi(t);
-    // encoder attention: rescale threshold of the running softmax maximum (tests run 0 = rescale on every increase)
-    if (const char* t = getenv("AX_WHISPER_ENC_RESCALE_THR")) enc_rescale_thr_ = std::max(0.f, std::min(16.f, (float)atof(t)));
+    // encoder attention: rescale threshold of the running softmax maximum (tests run 0 = rescale on every increase).
+    // A probability may reach 2^thr before it is narrowed to h16: IEEE half ends at 65504 < 2^16, so its build stops at 15.
+    if (const char* t = getenv("AX_WHISPER_ENC_RESCALE_THR")) enc_rescale_thr_ = std::max(0.f, std::min(AXW_F16 ? 15.f : 16.f, (float)atof(t)));
   }
   cfg_.ints["t2s"] = t2s_ ? 1 : 0;
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half

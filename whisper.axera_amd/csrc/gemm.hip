@@ -805,6 +805,10 @@ __global__ __launch_bounds__(512) void gemm256ps_bf16_kernel(GemmParams p) {
 }
 
 int gemm_force_tile = 0;  // 0: by tile count; 1: 128x128, 2: 256x128, 5: 256x256 stream per CU (tests and microbenchmarks)
+// What really ran (host side only; tests and microbenchmarks): the kernel of the last launch, same numbering, and of the one
+// before it (EPI_QKV and EPI_CROSS_KV are two launches) — forcing 5 falls back where the stream kernel's rule excludes it.
+int gemm_last_kernel = 0, gemm_prev_kernel = 0;
+static void note_kernel(int k) { gemm_prev_kernel = gemm_last_kernel; gemm_last_kernel = k; }
 
 template <int EPI, bool SW>
 static void launch_one(GemmParams p, int n_begin, int n_end, hipStream_t s) {
@@ -834,6 +838,7 @@ static void launch_one(GemmParams p, int n_begin, int n_end, hipStream_t s) {
       }
       const int cus = n_cus.load(std::memory_order_relaxed);
       p.n_tiles = (n_end - n_begin) / BN3;
+      note_kernel(5);
       hipLaunchKernelGGL((gemm256ps_bf16_kernel<EPI, SW>), dim3(tiles_sq < cus ? tiles_sq : cus), dim3(512), lds, s, p);
       return;
     }
@@ -841,10 +846,12 @@ static void launch_one(GemmParams p, int n_begin, int n_end, hipStream_t s) {
   p.n_tiles = (n_end - n_begin) / BN;
   const int tiles256 = p.n_tiles * mt256 * p.batch;
   if (gemm_force_tile == 2 || (gemm_force_tile == 0 && tiles256 >= 256 && p.K >= 2 * BK)) {  // enough 256-row tiles for every CU: deep-ring kernel
+    note_kernel(2);
     hipLaunchKernelGGL((gemm256_bf16_kernel<EPI, SW>), dim3(tiles256), dim3(512), 3 * STAGE2_BYTES, s, p);
     return;
   }
   dim3 grid(p.n_tiles * ((p.M + BM - 1) / BM) * p.batch);
+  note_kernel(1);
   hipLaunchKernelGGL((gemm_bf16_kernel<EPI, SW>), grid, dim3(256), 4 * TILE_BYTES, s, p);
 }
 
@@ -860,6 +867,7 @@ void launch_gemm(const GemmParams& p, hipStream_t s) {
       q.n_begin = 0;
       q.n_tiles = p.N / BN;
       dim3 grid(q.n_tiles * ((p.M + BM - 1) / BM) * p.batch, p.ksplit);
+      note_kernel(1);
       hipLaunchKernelGGL((gemm_bf16_kernel<EPI_PARTIAL_F32, false>), grid, dim3(256), 4 * TILE_BYTES, s, q);
       break;
     }
