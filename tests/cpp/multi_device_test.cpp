@@ -18,8 +18,21 @@ struct FakeEngine {
   static std::atomic<int> concurrent, max_concurrent, wait_ms;
   explicit FakeEngine(int d) : device(d) {}
   std::mutex& mutex() { return mu; }
-  void run_tokens(const float* const* pcm, const float* d_pcm, int, const int* n_samples, int batch, int max_new, int32_t* ids, int* n_ids) {
+  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1, kDecodeScored = 2 };
+  struct ClipScores { float *token_logprob, *avg_logprob, *no_speech_logprob; int* ended_eot; };
+  struct Window { int file, seek; };
+  struct Options { float threshold; };
+  // what the last call was handed (check_offsets)
+  DecodeMode seen_mode = kDecodePlain;
+  const int* seen_max_new_clip = nullptr;
+  ClipScores seen_scores{};
+  const Options* seen_opts = nullptr;
+  void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int, const int* n_samples, int batch, int max_new,
+                  const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores) {
     assert(d_pcm == nullptr);
+    seen_mode = mode;
+    seen_max_new_clip = max_new_clip;
+    seen_scores = scores ? *scores : ClipScores{};
     const int c = ++concurrent;
     int m = max_concurrent.load();
     while (c > m && !max_concurrent.compare_exchange_weak(m, c)) {}
@@ -36,6 +49,13 @@ struct FakeEngine {
       for (int i = 0; i < n; ++i) ids[(size_t)b * 448 + i] = (int32_t)pcm[b][0] + i;
     }
     --concurrent;
+  }
+  // two windows per file, file counted from 0 within this call
+  void run_long_windows(const float* const* pcm, const int*, int n_files, int, int, const Options* opts, std::vector<Window>& log) {
+    seen_opts = opts;
+    calls.push_back({n_files, pcm[0]});
+    for (int f = 0; f < n_files; ++f)
+      for (int k = 0; k < 2; ++k) log.push_back({f, 1000 * device + k});
   }
 };
 std::atomic<int> FakeEngine::concurrent{0}, FakeEngine::max_concurrent{0}, FakeEngine::wait_ms{0};
@@ -69,10 +89,10 @@ static void run_case(int G, int B, int max_new) {
   std::vector<int> n(B, -1), wn(B, -1);
   FakeEngine::max_concurrent = 0;
   FakeEngine::wait_ms = (G < B ? G : B) > 1 ? 2000 : 0;
-  g.run_tokens(ptrs.data(), lens.data(), B, max_new, 448, ids.data(), n.data());
+  g.run_tokens(FakeEngine::kDecodePlain, ptrs.data(), lens.data(), B, max_new, nullptr, 448, ids.data(), n.data());
   FakeEngine::wait_ms = 0;
   FakeEngine single(99);
-  single.run_tokens(ptrs.data(), nullptr, 0, lens.data(), B, max_new, want.data(), wn.data());
+  single.run_tokens(FakeEngine::kDecodePlain, ptrs.data(), nullptr, 0, lens.data(), B, max_new, nullptr, want.data(), wn.data(), nullptr);
   assert(n == wn && ids == want);  // joined result == one engine over the whole batch, in order
   const int world = G < B ? G : B, per = (B + world - 1) / world;
   int covered = 0;
@@ -104,7 +124,7 @@ static void check_errors() {
   std::vector<int> n(B);
   bool threw = false;
   try {
-    g.run_tokens(ptrs.data(), lens.data(), B, 0, 448, ids.data(), n.data());
+    g.run_tokens(FakeEngine::kDecodePlain, ptrs.data(), lens.data(), B, 0, nullptr, 448, ids.data(), n.data());
   } catch (const std::exception& e) {
     threw = true;
     assert(strstr(e.what(), "device worker 2") && strstr(e.what(), "poisoned"));
@@ -112,7 +132,7 @@ static void check_errors() {
   assert(threw);
   for (int d = 0; d < 4; ++d) assert(g.at(d).calls.size() == 1);  // every worker was joined (none left running)
   bool t2 = false;
-  try { g.run_tokens(ptrs.data(), lens.data(), 0, 0, 448, ids.data(), n.data()); } catch (const std::exception&) { t2 = true; }
+  try { g.run_tokens(FakeEngine::kDecodePlain, ptrs.data(), lens.data(), 0, 0, nullptr, 448, ids.data(), n.data()); } catch (const std::exception&) { t2 = true; }
   assert(t2);
 }
 
@@ -124,20 +144,64 @@ static void check_rotation() {
   const float* ptr = clip.data();
   int len = 4, n = 0;
   std::vector<int32_t> ids(448);
-  for (int call = 0; call < 7; ++call) g.run_tokens(&ptr, &len, 1, 0, 448, ids.data(), &n);
+  for (int call = 0; call < 7; ++call) g.run_tokens(FakeEngine::kDecodePlain, &ptr, &len, 1, 0, nullptr, 448, ids.data(), &n);
   assert(g.at(0).calls.size() == 3 && g.at(1).calls.size() == 2 && g.at(2).calls.size() == 2);
   // two clips on three devices: devices (1, 2) after seven 1-clip calls, then (0, 1)
   const float* two[2] = {ptr, ptr};
   int lens[2] = {4, 4}, ns[2];
   std::vector<int32_t> ids2(2 * 448);
-  g.run_tokens(two, lens, 2, 0, 448, ids2.data(), ns);
+  g.run_tokens(FakeEngine::kDecodePlain, two, lens, 2, 0, nullptr, 448, ids2.data(), ns);
   assert(g.at(1).calls.size() == 3 && g.at(2).calls.size() == 3 && g.at(0).calls.size() == 3);
   // a full batch always uses every device, block w on device w
   const float* six[6] = {ptr, ptr, ptr, ptr, ptr, ptr};
   int lens6[6] = {4, 4, 4, 4, 4, 4}, ns6[6];
   std::vector<int32_t> ids6(6 * 448);
-  g.run_tokens(six, lens6, 6, 0, 448, ids6.data(), ns6);
+  g.run_tokens(FakeEngine::kDecodePlain, six, lens6, 6, 0, nullptr, 448, ids6.data(), ns6);
   for (int d = 0; d < 3; ++d) assert(g.at(d).calls.size() == 4 && g.at(d).calls.back().first == 2);
+}
+
+static void check_offsets() {
+  // every per-clip array of a call reaches worker w offset by its block's first clip (token_logprob: by whole rows); a long-form
+  // log comes back worker by worker with the files renumbered over the whole call
+  const int G = 3, B = 7, n_ctx = 448, per = 3;  // blocks [0, 3), [3, 6), [6, 7)
+  axw::DeviceGroup<FakeEngine> g;
+  for (int d = 0; d < G; ++d) g.add(std::unique_ptr<FakeEngine>(new FakeEngine(d)));
+  std::vector<std::vector<float>> clips(B);
+  std::vector<const float*> ptrs(B);
+  std::vector<int> lens(B, 4), budgets(B, 2), n(B), eot(B);
+  for (int b = 0; b < B; ++b) { clips[b].assign(4, (float)(1000 + 10 * b)); ptrs[b] = clips[b].data(); }
+  std::vector<int32_t> ids((size_t)B * n_ctx);
+  std::vector<float> tok((size_t)B * n_ctx), avg(B), nsp(B);
+  const FakeEngine::ClipScores scores{tok.data(), avg.data(), nsp.data(), eot.data()};
+  g.run_tokens(FakeEngine::kDecodeScored, ptrs.data(), lens.data(), B, 0, budgets.data(), n_ctx, ids.data(), n.data(), &scores);
+  for (int w = 0; w < G; ++w) {
+    const FakeEngine& e = g.at(w);
+    const int lo = w * per;
+    assert(e.calls.size() == 1 && e.calls[0].second == ptrs[lo]);
+    assert(e.seen_mode == FakeEngine::kDecodeScored);
+    assert(e.seen_max_new_clip == budgets.data() + lo);
+    assert(e.seen_scores.token_logprob == tok.data() + (size_t)lo * n_ctx);
+    assert(e.seen_scores.avg_logprob == avg.data() + lo && e.seen_scores.no_speech_logprob == nsp.data() + lo);
+    assert(e.seen_scores.ended_eot == eot.data() + lo);
+  }
+  // absent arrays stay absent
+  const FakeEngine::ClipScores only_avg{nullptr, avg.data(), nullptr, nullptr};
+  g.run_tokens(FakeEngine::kDecodeScored, ptrs.data(), lens.data(), B, 0, nullptr, n_ctx, ids.data(), n.data(), &only_avg);
+  for (int w = 0; w < G; ++w) {
+    const FakeEngine& e = g.at(w);
+    assert(e.seen_max_new_clip == nullptr && e.seen_scores.token_logprob == nullptr && e.seen_scores.ended_eot == nullptr);
+    assert(e.seen_scores.avg_logprob == avg.data() + w * per && e.seen_scores.no_speech_logprob == nullptr);
+  }
+  const FakeEngine::Options opts{0.5f};
+  std::vector<FakeEngine::Window> log;
+  g.run_long_windows(ptrs.data(), lens.data(), B, 0, 0, &opts, log);
+  assert(log.size() == (size_t)2 * B);
+  for (int f = 0; f < B; ++f)
+    for (int k = 0; k < 2; ++k) {
+      const FakeEngine::Window& x = log[(size_t)2 * f + k];
+      assert(x.file == f && x.seek == 1000 * (f / per) + k);  // worker 0's windows first, files counted over the whole call
+    }
+  for (int w = 0; w < G; ++w) assert(g.at(w).seen_opts == &opts && g.at(w).calls.back().second == ptrs[w * per]);
 }
 
 static void check_device_lists() {
@@ -158,6 +222,7 @@ int main() {
     for (int B : {1, 2, 5, 8, 64, 65}) run_case(G, B, B % 2 ? 0 : 3);
   check_errors();
   check_rotation();
+  check_offsets();
   check_device_lists();
   printf("multi_device ok\n");
   return 0;

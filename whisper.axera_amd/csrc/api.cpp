@@ -97,6 +97,20 @@ int guarded_group(AX_WHISPER_HANDLE handle, F&& f) {
   }
 }
 
+// f(): the host-only entry points (no handle); exceptions become -1 + the thread's init error text
+template <typename F>
+int guarded_host(F&& f) {
+  try {
+    return f();
+  } catch (const std::exception& e) {
+    g_init_error = e.what();
+    return -1;
+  } catch (...) {
+    g_init_error = "unknown error";
+    return -1;
+  }
+}
+
 int visible_devices() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
@@ -245,7 +259,7 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTokens(AX_WHISPER_HANDLE handle, const 
                                                 int batch, int max_new, int32_t* ids, int* n_ids) {
   if (!handle || !pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    g.run_tokens(pcm, num_samples, batch, max_new, g.primary().config().n_text_ctx, ids, n_ids);
+    g.run_tokens(Engine::kDecodePlain, pcm, num_samples, batch, max_new, nullptr, g.primary().config().n_text_ctx, ids, n_ids);
   });
 }
 
@@ -253,21 +267,23 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampTokens(AX_WHISPER_HANDLE handl
                                                          int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
   if (!handle || !pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    g.run_tokens_mode(Engine::kDecodeTimestamps, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids);
+    g.run_tokens(Engine::kDecodeTimestamps, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids);
   });
 }
 
 AX_WHISPER_API int AX_WHISPER_RunDeviceBatchTokens(AX_WHISPER_HANDLE handle, const float* d_pcm, int stride,
                                                    const int* num_samples, int batch, int max_new, int32_t* ids, int* n_ids) {
   if (!handle || !d_pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
-  return guarded(handle, [&](Engine& e) { e.run_tokens(nullptr, d_pcm, stride, num_samples, batch, max_new, ids, n_ids); });
+  return AX_WHISPER_RunDeviceBatchTokensRagged(handle, d_pcm, stride, num_samples, batch, max_new, nullptr, ids, n_ids);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunDeviceBatchTokensRagged(AX_WHISPER_HANDLE handle, const float* d_pcm, int stride,
                                                          const int* num_samples, int batch, int max_new,
                                                          const int* max_new_clip, int32_t* ids, int* n_ids) {
   if (!handle || !d_pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
-  return guarded(handle, [&](Engine& e) { e.run_tokens(nullptr, d_pcm, stride, num_samples, batch, max_new, ids, n_ids, max_new_clip); });
+  return guarded(handle, [&](Engine& e) {
+    e.run_tokens(Engine::kDecodePlain, nullptr, d_pcm, stride, num_samples, batch, max_new, max_new_clip, ids, n_ids, nullptr);
+  });
 }
 
 AX_WHISPER_API int AX_WHISPER_RunPCMBatch(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
@@ -279,7 +295,7 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatch(AX_WHISPER_HANDLE handle, const float*
     const int Tc = e.config().n_text_ctx;
     std::vector<int32_t> ids((size_t)batch * Tc);
     std::vector<int> n(batch);
-    g.run_tokens(pcm, num_samples, batch, 0, Tc, ids.data(), n.data());
+    g.run_tokens(Engine::kDecodePlain, pcm, num_samples, batch, 0, nullptr, Tc, ids.data(), n.data());
     for (int b = 0; b < batch; ++b) results[b] = strdup(e.transcript(ids.data() + (size_t)b * Tc, n[b]).c_str());  // host only
   });
 }
@@ -299,17 +315,11 @@ AX_WHISPER_API int AX_WHISPER_Transcript(AX_WHISPER_HANDLE handle, const int32_t
 AX_WHISPER_API int AX_WHISPER_ConvertT2S(const char* config_path, const char* text, char** result) {
   if (!config_path || !text || !result) return -1;
   *result = nullptr;
-  try {
+  return guarded_host([&] {
     axw::T2SConverter conv(config_path);
     *result = strdup(conv.convert(text).c_str());
     return *result ? 0 : -1;
-  } catch (const std::exception& e) {
-    g_init_error = e.what();
-    return -1;
-  } catch (...) {
-    g_init_error = "unknown error";
-    return -1;
-  }
+  });
 }
 
 // the two byte paths of the drop-in boundary on their own, host only (no handle, no GPU): parity tests hold them bit-equal to
@@ -318,7 +328,7 @@ AX_WHISPER_API int AX_WHISPER_LoadAudioFile(const char* path, float** samples, i
   if (!path || !samples || !n_samples) return -1;
   *samples = nullptr;
   *n_samples = 0;
-  try {
+  return guarded_host([&] {
     axw::WavData wav;
     std::string err;
     if (!axw::load_audio_file(path, wav, err)) { g_init_error = "load wav failed: " + err; return -1; }
@@ -328,20 +338,14 @@ AX_WHISPER_API int AX_WHISPER_LoadAudioFile(const char* path, float** samples, i
     *n_samples = (int)wav.mono.size();
     if (info) { info[0] = wav.sample_rate; info[1] = wav.channels; }
     return 0;
-  } catch (const std::exception& e) {
-    g_init_error = e.what();
-    return -1;
-  } catch (...) {
-    g_init_error = "unknown error";
-    return -1;
-  }
+  });
 }
 
 AX_WHISPER_API int AX_WHISPER_DetokenizeWithTable(const char* tokens_path, const int32_t* ids, int n, char** result, int* n_bytes) {
   if (!tokens_path || (n > 0 && !ids) || !result || !n_bytes) return -1;
   *result = nullptr;
   *n_bytes = 0;
-  try {
+  return guarded_host([&] {
     const std::vector<std::string> table = axw::load_token_table(tokens_path);
     std::string s;
     for (int i = 0; i < n; ++i)
@@ -352,13 +356,7 @@ AX_WHISPER_API int AX_WHISPER_DetokenizeWithTable(const char* tokens_path, const
     (*result)[s.size()] = 0;
     *n_bytes = (int)s.size();
     return 0;
-  } catch (const std::exception& e) {
-    g_init_error = e.what();
-    return -1;
-  } catch (...) {
-    g_init_error = "unknown error";
-    return -1;
-  }
+  });
 }
 
 AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char* key) {
@@ -431,19 +429,19 @@ AX_WHISPER_API int AX_WHISPER_ScanStored16(AX_WHISPER_HANDLE handle, int batch, 
 AX_WHISPER_API int AX_WHISPER_DecodeForced(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
                                            float* logits, int32_t* argmax_ids) {
   if (!handle || (n_forced > 0 && !forced)) return -1;
-  return guarded(handle, [&](Engine& e) { e.decode_forced(batch, forced, n_forced, logits, argmax_ids); });
+  return guarded(handle, [&](Engine& e) { e.decode_forced(Engine::kDecodePlain, batch, forced, n_forced, logits, argmax_ids, nullptr); });
 }
 
 AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestamps(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
                                                      float* logits, int32_t* chosen) {
   if (!handle || (n_forced > 0 && !forced)) return -1;
-  return guarded(handle, [&](Engine& e) { e.decode_forced_mode(Engine::kDecodeTimestamps, batch, forced, n_forced, logits, chosen); });
+  return guarded(handle, [&](Engine& e) { e.decode_forced(Engine::kDecodeTimestamps, batch, forced, n_forced, logits, chosen, nullptr); });
 }
 
 AX_WHISPER_API int AX_WHISPER_ApplyTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
                                                   int batch, int32_t* chosen) {
   if (!handle || !logits || !hist || !n_hist || !chosen || batch < 1) return -1;
-  return guarded(handle, [&](Engine& e) { e.apply_timestamp_rules(logits, hist, n_hist, batch, chosen); });
+  return guarded(handle, [&](Engine& e) { e.timestamp_rules(logits, hist, n_hist, batch, chosen, nullptr); });
 }
 
 // ---- confidence (DESIGN.md "Confidence")
@@ -452,8 +450,8 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampScores(AX_WHISPER_HANDLE handl
                                                          float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
   if (!handle || !pcm || !num_samples || !ids || !n_ids || !token_logprob || !avg_logprob || !no_speech_logprob || !ended_eot || batch < 1) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    g.run_tokens_scores(pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids, token_logprob,
-                        avg_logprob, no_speech_logprob, ended_eot);
+    const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
+    g.run_tokens(Engine::kDecodeScored, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids, &scores);
   });
 }
 
@@ -461,13 +459,16 @@ AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampScores(AX_WHISPER_HANDLE hand
                                                           float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob,
                                                           float* logits0) {
   if (!handle || (n_forced > 0 && !forced)) return -1;
-  return guarded(handle, [&](Engine& e) { e.decode_forced_scores(batch, forced, n_forced, logits, chosen, logprob, no_speech_logprob, logits0); });
+  return guarded(handle, [&](Engine& e) {
+    const Engine::ForcedScores scores{logprob, no_speech_logprob, logits0};
+    e.decode_forced(Engine::kDecodeScored, batch, forced, n_forced, logits, chosen, &scores);
+  });
 }
 
 AX_WHISPER_API int AX_WHISPER_ScoreTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
                                                   int batch, int32_t* chosen, float* logprob) {
   if (!handle || !logits || !hist || !n_hist || !chosen || !logprob || batch < 1) return -1;
-  return guarded(handle, [&](Engine& e) { e.score_timestamp_rules(logits, hist, n_hist, batch, chosen, logprob); });
+  return guarded(handle, [&](Engine& e) { e.timestamp_rules(logits, hist, n_hist, batch, chosen, logprob); });
 }
 
 AX_WHISPER_API int AX_WHISPER_NoSpeechLogProb(AX_WHISPER_HANDLE handle, const float* logits, int batch, float* out) {
@@ -543,27 +544,37 @@ AX_WHISPER_API int AX_WHISPER_ComputeMelWindow(AX_WHISPER_HANDLE handle, const f
   return guarded(handle, [&](Engine& e) { e.compute_mel_window(pcm, num_samples, seek, mel_out); });
 }
 
-AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
-                                                int max_new, int max_passes, int win_cap, int* win_info, int32_t* ids, int* n_windows) {
-  if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids))) return -1;
+// the seek loop of RunPCMLongWindows[Scored] (`who`) and its log written out; opts / win_score: the scored call's, or nullptr
+static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* const* pcm, const int* num_samples, int n_files, int max_new,
+                        int max_passes, const axw::LongScoreOptions* opts, int win_cap, int* win_info, int32_t* ids, float* win_score,
+                        int* n_windows) {
+  if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids || (opts && !win_score))))
+    return -1;
   for (int b = 0; b < n_files; ++b)
     if (!pcm[b] || num_samples[b] < 1) return -1;
   *n_windows = 0;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     std::vector<axw::LongWindow> log;
-    g.run_long_windows(pcm, num_samples, n_files, max_new, max_passes, log);
+    g.run_long_windows(pcm, num_samples, n_files, max_new, max_passes, opts, log);
     // nothing is written unless everything fits
     if ((long)log.size() > win_cap)
-      throw std::runtime_error("RunPCMLongWindows: " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
+      throw std::runtime_error(std::string(who) + ": " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
     const int Tc = g.primary().config().n_text_ctx;
     for (size_t k = 0; k < log.size(); ++k) {
       const axw::LongWindow& w = log[k];
       const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
       memcpy(win_info + k * 7, row, sizeof row);
       memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
+      if (opts) { win_score[k * 3] = w.no_speech_logprob; win_score[k * 3 + 1] = w.avg_logprob; win_score[k * 3 + 2] = w.skipped ? 1.f : 0.f; }
     }
     *n_windows = (int)log.size();
   });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                int max_new, int max_passes, int win_cap, int* win_info, int32_t* ids, int* n_windows) {
+  return long_windows(handle, "RunPCMLongWindows", pcm, num_samples, n_files, max_new, max_passes, nullptr, win_cap, win_info, ids, nullptr,
+                      n_windows);
 }
 
 // text of one file's windows; opts: the silent-window rule's thresholds, or nullptr (the unscored loop)
@@ -574,8 +585,7 @@ static int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples,
     Engine& e = g.primary();
     std::vector<axw::LongWindow> log;
     const float* files[1] = {pcm_data};
-    if (opts) g.run_long_windows_scored(files, &num_samples, 1, 0, 0, *opts, log);
-    else g.run_long_windows(files, &num_samples, 1, 0, 0, log);
+    g.run_long_windows(files, &num_samples, 1, 0, 0, opts, log);
     const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
     std::string text;
     std::vector<axw::WindowSegment> segs;
@@ -616,26 +626,9 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsScored(AX_WHISPER_HANDLE handle, 
                                                       int n_files, int max_new, int max_passes, float no_speech_threshold,
                                                       float logprob_threshold, int win_cap, int* win_info, int32_t* ids, float* win_score,
                                                       int* n_windows) {
-  if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids || !win_score))) return -1;
-  for (int b = 0; b < n_files; ++b)
-    if (!pcm[b] || num_samples[b] < 1) return -1;
-  *n_windows = 0;
-  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    std::vector<axw::LongWindow> log;
-    g.run_long_windows_scored(pcm, num_samples, n_files, max_new, max_passes, axw::LongScoreOptions{no_speech_threshold, logprob_threshold}, log);
-    // nothing is written unless everything fits
-    if ((long)log.size() > win_cap)
-      throw std::runtime_error("RunPCMLongWindowsScored: " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
-    const int Tc = g.primary().config().n_text_ctx;
-    for (size_t k = 0; k < log.size(); ++k) {
-      const axw::LongWindow& w = log[k];
-      const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
-      memcpy(win_info + k * 7, row, sizeof row);
-      memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
-      win_score[k * 3] = w.no_speech_logprob; win_score[k * 3 + 1] = w.avg_logprob; win_score[k * 3 + 2] = w.skipped ? 1.f : 0.f;
-    }
-    *n_windows = (int)log.size();
-  });
+  const axw::LongScoreOptions opts{no_speech_threshold, logprob_threshold};
+  return long_windows(handle, "RunPCMLongWindowsScored", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids, win_score,
+                      n_windows);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {
@@ -653,7 +646,7 @@ AX_WHISPER_API int AX_WHISPER_DecodeGreedy(AX_WHISPER_HANDLE handle, int batch, 
 AX_WHISPER_API int AX_WHISPER_DecodeGreedyRagged(AX_WHISPER_HANDLE handle, int batch, int max_new, const int* max_new_clip,
                                                  int32_t* ids, int* n_ids) {
   if (!handle || !ids || !n_ids) return -1;
-  return guarded(handle, [&](Engine& e) { e.decode_greedy(batch, max_new, max_new_clip, ids, n_ids); });
+  return guarded(handle, [&](Engine& e) { e.decode_greedy(Engine::kDecodePlain, batch, max_new, max_new_clip, ids, n_ids); });
 }
 
 AX_WHISPER_API int AX_WHISPER_StreamOpen(AX_WHISPER_HANDLE handle, int n_slots) {

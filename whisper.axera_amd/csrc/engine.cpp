@@ -538,7 +538,7 @@ void Engine::free_slot_buffers() {
   slot_allocs_.clear();
   d_ts_logits_ = nullptr;  // (one of slot_allocs_)
   d_tok_lp_ = nullptr; d_dec_id_ = nullptr; d_nospeech_ = nullptr;  // (likewise)
-  score_out_ = TsScoreParams{};
+  own_scores_ = TsScoreParams{};
   if (h_pcm_) { (void)hipHostFree(h_pcm_); h_pcm_ = nullptr; }
   cap_ = 0;
 }
@@ -812,19 +812,14 @@ void Engine::run_encoder(int batch, const int* d_slot_map) {
 }
 
 // ------------------------------------------------------------------------------ public entry points
-void Engine::run_tokens(const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
-                        int32_t* ids, int* n_ids, const int* max_new_clip) {
-  run_tokens_mode(kDecodePlain, pcm, d_pcm, d_stride, n_samples, batch, max_new, ids, n_ids, max_new_clip);
-}
-
-void Engine::run_tokens_mode(int mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
-                             int max_new, int32_t* ids, int* n_ids, const int* max_new_clip) {
+void Engine::run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
+                        int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores) {
   if (batch < 1) throw std::runtime_error("batch must be >= 1");
   require_no_stream("run_tokens");
   if (mode < kDecodePlain || mode > kDecodeScored) throw std::runtime_error("run_tokens: unknown decode mode");
+  if (scores && mode != kDecodeScored) throw std::runtime_error("run_tokens: scores need the scored decode mode");
   if (mode == kDecodeTimestamps) require_timestamp_vocab();
   if (mode == kDecodeScored) require_scored_vocab();
-  TsModeScope ts(ts_mode_, mode);
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   ensure_capacity(batch);
@@ -839,7 +834,7 @@ void Engine::run_tokens_mode(int mode, const float* const* pcm, const float* d_p
   HIP_CHECK(hipEventRecord(ev_[1], s));
   run_encoder(batch);
   HIP_CHECK(hipEventRecord(ev_[2], s));
-  const int steps = greedy_loop(batch, max_new, max_new_clip);
+  const int steps = greedy_loop(StepSpec{mode}, batch, max_new, max_new_clip);
   fetch_ids(batch, ids, n_ids);
   // stage timings (events 3/4 are reused by the poll; bracket decode with a fresh record)
   HIP_CHECK(hipEventRecord(ev_[3], s));
@@ -849,12 +844,7 @@ void Engine::run_tokens_mode(int mode, const float* const* pcm, const float* d_p
   (void)hipEventElapsedTime(&timings[2], ev_[2], ev_[3]);
   timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   timings[4] = (float)steps;
-}
-
-void Engine::run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int32_t* ids,
-                               int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
-  run_tokens_mode(kDecodeScored, pcm, nullptr, 0, n_samples, batch, max_new, ids, n_ids, max_new_clip);
-  fetch_scores(batch, n_ids, token_logprob, avg_logprob, no_speech_logprob, ended_eot);
+  if (scores) fetch_scores(batch, n_ids, scores->token_logprob, scores->avg_logprob, scores->no_speech_logprob, scores->ended_eot);
 }
 
 // Whisper.cpp:231-236: zh transcripts pass through OpenCC's t2s.json. The reference resolves "t2s.json" (and the two
@@ -933,22 +923,11 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
   }
 }
 
-void Engine::decode_forced(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) {
-  decode_forced_mode(kDecodePlain, batch, forced, n_forced, logits, argmax_ids);
-}
-
-void Engine::decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) {
-  if (mode != kDecodePlain && mode != kDecodeTimestamps) throw std::runtime_error("decode_forced: unknown decode mode");
-  decode_forced_impl(mode, batch, forced, n_forced, logits, argmax_ids, nullptr, nullptr, nullptr);
-}
-
-void Engine::decode_forced_scores(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen, float* logprob,
-                                  float* no_speech_logprob, float* logits0) {
-  decode_forced_impl(kDecodeScored, batch, forced, n_forced, logits, chosen, logprob, no_speech_logprob, logits0);
-}
-
-void Engine::decode_forced_impl(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids, float* logprob,
-                                float* no_speech_logprob, float* logits0) {
+void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids,
+                           const ForcedScores* scores) {
+  if (mode < kDecodePlain || mode > kDecodeScored) throw std::runtime_error("decode_forced: unknown decode mode");
+  if (scores && mode != kDecodeScored) throw std::runtime_error("decode_forced: scores need the scored decode mode");
+  const ForcedScores out = scores ? *scores : ForcedScores{};
   require_no_stream("decode_forced");
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
@@ -958,30 +937,21 @@ void Engine::decode_forced_impl(int mode, int batch, const int32_t* forced, int 
   if (n_forced < 0 || n_forced + n_prefix > cfg_.n_text_ctx) throw std::runtime_error("decode_forced: n_forced out of range");
   if (tsm) require_timestamp_vocab();
   if (scored) require_scored_vocab();
-  TsModeScope ts(ts_mode_, mode);
   if (tsm) ensure_ts_logits();
   if (scored) ensure_ts_scores();
   hipStream_t s = stream();
   const int nv = cfg_.n_vocab, rows = n_forced + 1;
-  // device scratch of this call, freed on every path out (a HIP_CHECK below may throw)
-  struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-  } b_forced, b_arg, b_logits, b_lp, b_dec, b_nsp, b_l0;
+  DevBuf b_forced, b_arg, b_logits, b_lp, b_dec, b_nsp, b_l0;  // scratch of this call
   HIP_CHECK(hipMalloc(&b_forced.p, std::max<size_t>((size_t)batch * n_forced * 4, 256)));
   HIP_CHECK(hipMalloc(&b_arg.p, (size_t)batch * rows * 4));
   if (logits) HIP_CHECK(hipMalloc(&b_logits.p, (size_t)batch * rows * nv * 4));
-  // scored: this call's own score arrays ([batch][rows]: the rules kernel's index is the history length) for its duration
-  struct ScoreOutScope {
-    TsScoreParams& out; TsScoreParams saved;
-    ~ScoreOutScope() { out = saved; }
-  } score_scope{score_out_, score_out_};
-  if (scored) {
+  StepSpec spec{mode};
+  if (scored) {  // this call's own score arrays ([batch][rows]: the rules kernel's index is the history length)
     HIP_CHECK(hipMalloc(&b_lp.p, (size_t)batch * rows * 4));
     HIP_CHECK(hipMalloc(&b_dec.p, (size_t)batch * rows * 4));
     HIP_CHECK(hipMalloc(&b_nsp.p, (size_t)batch * 4));
-    if (logits0) HIP_CHECK(hipMalloc(&b_l0.p, (size_t)batch * nv * 4));
-    score_out_.logprob = (float*)b_lp.p; score_out_.decision = (int*)b_dec.p; score_out_.stride = rows; score_out_.no_speech = (float*)b_nsp.p;
+    if (out.logits0) HIP_CHECK(hipMalloc(&b_l0.p, (size_t)batch * nv * 4));
+    spec.score_out = TsScoreParams{(float*)b_lp.p, (int*)b_dec.p, (long)rows, (float*)b_nsp.p, own_scores_.no_speech_id};
   }
   int* d_forced = (int*)b_forced.p;
   int* d_arg = (int*)b_arg.p;
@@ -997,7 +967,7 @@ void Engine::decode_forced_impl(int mode, int batch, const int32_t* forced, int 
   for (int st = 0; !done && st < n_prefix + n_forced; ++st) {
     const int gi = st - (n_prefix - 1);
     float* lrow = (d_logits && gi >= 0) ? d_logits + (size_t)gi * nv : nullptr;
-    enqueue_decode_step(batch, cfg_.n_text_ctx, d_forced, n_forced, lrow, (long)rows * nv, d_arg);
+    enqueue_decode_step(spec, batch, cfg_.n_text_ctx, d_forced, n_forced, lrow, (long)rows * nv, d_arg);
     // timestamp mode: the step dumped its rows into d_ts_logits_ (16-byte row stride) for the rules kernel
     if (tsm && lrow) HIP_CHECK(hipMemcpy2DAsync(lrow, (size_t)rows * nv * 4, d_ts_logits_, (size_t)ts_stride_ * 4, (size_t)nv * 4, batch,
                                                 hipMemcpyDeviceToDevice, s));
@@ -1006,27 +976,22 @@ void Engine::decode_forced_impl(int mode, int batch, const int32_t* forced, int 
                                                       hipMemcpyDeviceToDevice, s));
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  if (logprob) HIP_CHECK(hipMemcpy(logprob, b_lp.p, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
-  if (no_speech_logprob) HIP_CHECK(hipMemcpy(no_speech_logprob, b_nsp.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
-  if (logits0 && b_l0.p) HIP_CHECK(hipMemcpy(logits0, b_l0.p, (size_t)batch * nv * 4, hipMemcpyDeviceToHost));
+  if (out.logprob) HIP_CHECK(hipMemcpy(out.logprob, b_lp.p, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
+  if (out.no_speech_logprob) HIP_CHECK(hipMemcpy(out.no_speech_logprob, b_nsp.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  if (out.logits0) HIP_CHECK(hipMemcpy(out.logits0, b_l0.p, (size_t)batch * nv * 4, hipMemcpyDeviceToHost));
   if (logits) HIP_CHECK(hipMemcpy(logits, d_logits, (size_t)batch * rows * nv * 4, hipMemcpyDeviceToHost));
   if (argmax_ids) HIP_CHECK(hipMemcpy(argmax_ids, d_arg, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
 }
 
-void Engine::decode_greedy(int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
-  decode_greedy_mode(kDecodePlain, batch, max_new, max_new_clip, ids, n_ids);
-}
-
-void Engine::decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
+void Engine::decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
   require_no_stream("decode_greedy");
   if (mode != kDecodePlain && mode != kDecodeTimestamps) throw std::runtime_error("decode_greedy: unknown decode mode");
   if (mode == kDecodeTimestamps) require_timestamp_vocab();
-  TsModeScope ts(ts_mode_, mode);
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_greedy: batch exceeds the encoded slots");
   hipStream_t s = stream();
   HIP_CHECK(hipEventRecord(ev_[2], s));
-  const int steps = greedy_loop(batch, max_new, max_new_clip);
+  const int steps = greedy_loop(StepSpec{mode}, batch, max_new, max_new_clip);
   fetch_ids(batch, ids, n_ids);
   HIP_CHECK(hipEventRecord(ev_[3], s));
   HIP_CHECK(hipEventSynchronize(ev_[3]));
@@ -1037,17 +1002,8 @@ void Engine::decode_greedy_mode(int mode, int batch, int max_new, const int* max
 }
 
 // The rules kernel alone, on host rows and histories (tests; callers with logits of their own)
-void Engine::apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) {
-  rules_on_host_rows(logits, hist, n_hist, batch, chosen, nullptr);
-}
-
-void Engine::score_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) {
-  if (!logprob) throw std::runtime_error("score_timestamp_rules: bad arguments");
-  rules_on_host_rows(logits, hist, n_hist, batch, chosen, logprob);
-}
-
 // logprob != nullptr: the scored kernel (each clip's entry at index 0 of a one-entry score row)
-void Engine::rules_on_host_rows(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) {
+void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) {
   require_no_stream("apply_timestamp_rules");
   require_timestamp_vocab();
   if (batch < 1 || !logits || !hist || !n_hist || !chosen) throw std::runtime_error("apply_timestamp_rules: bad arguments");
@@ -1058,10 +1014,7 @@ void Engine::rules_on_host_rows(const float* logits, const int32_t* hist, const 
   const long stride = ((long)nv + 3) / 4 * 4;
   for (int b = 0; b < batch; ++b)
     if (n_hist[b] < 0 || n_hist[b] > Tc) throw std::runtime_error("apply_timestamp_rules: n_hist out of range");
-  struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-  } b_log, b_hist, b_n, b_val, b_idx, b_lp, b_dec;
+  DevBuf b_log, b_hist, b_n, b_val, b_idx, b_lp, b_dec;
   if (logprob) {  // [batch][n_text_ctx + 1]: the kernel's index is the history length
     HIP_CHECK(hipMalloc(&b_lp.p, (size_t)batch * (Tc + 1) * 4));
     HIP_CHECK(hipMalloc(&b_dec.p, (size_t)batch * (Tc + 1) * 4));
@@ -1099,10 +1052,7 @@ void Engine::no_speech_logprob(const float* logits, int batch, float* out) {
   hipStream_t s = stream();
   const int nv = cfg_.n_vocab;
   const long stride = ((long)nv + 3) / 4 * 4;
-  struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-  } b_log, b_out;
+  DevBuf b_log, b_out;
   HIP_CHECK(hipMalloc(&b_log.p, (size_t)batch * stride * 4));
   HIP_CHECK(hipMalloc(&b_out.p, (size_t)batch * 4));
   HIP_CHECK(hipMemcpy2DAsync(b_log.p, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));

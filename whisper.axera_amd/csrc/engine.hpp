@@ -27,38 +27,28 @@ class Engine final : public IEngine {
   ~Engine() override;
   Engine(const Engine&) = delete;
 
-  void run_tokens(const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
-                  int32_t* ids, int* n_ids, const int* max_new_clip = nullptr) override;
+  void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
+                  const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores) override;
   std::string detokenize(const int32_t* ids, int n) const override;
   std::string transcript(const int32_t* ids, int n) const override;
   bool has_t2s() const { return (bool)t2s_; }
   void compute_mel(const float* pcm, int n_samples, float* mel_out) override;
   void encode_mel(const float* mel, int batch) override;
   void get_cross_kv(int slot, float* k_out, float* v_out) override;
-  void decode_forced(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) override;
-  void decode_greedy(int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
+  void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
+                     const ForcedScores* scores) override;
+  void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
+  void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) override;
+  void no_speech_logprob(const float* logits, int batch, float* out) override;
   void stream_open(int n_slots) override;
   void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) override;
   int stream_step(int n_steps, int* finished_slots) override;
   void stream_collect(int slot, int32_t* ids, int* n_ids) override;
   void stream_close() override;
-  void run_tokens_mode(int mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
-                       int32_t* ids, int* n_ids, const int* max_new_clip) override;
-  void decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) override;
-  void decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
-  void apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) override;
   void compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) override;
   void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                        std::vector<LongWindow>& log) override;
+                        const LongScoreOptions* opts, std::vector<LongWindow>& log) override;
   int scan_stored16(int batch, int n_max, char (*names)[32], long long* nonfinite, float* maxabs) override;
-  void run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int32_t* ids,
-                         int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) override;
-  void decode_forced_scores(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen, float* logprob,
-                            float* no_speech_logprob, float* logits0) override;
-  void score_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) override;
-  void no_speech_logprob(const float* logits, int batch, float* out) override;
-  void run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                               const LongScoreOptions& opts, std::vector<LongWindow>& log) override;
   float bench(const std::string& what, int batch, int arg, int iters) override;
   void set_stream(void* s) override { user_stream_ = static_cast<hipStream_t>(s); }
   const ModelConfig& config() const override { return cfg_; }
@@ -87,42 +77,47 @@ class Engine final : public IEngine {
                     int* pinned_ns = nullptr);
   void run_encoder(int batch, const int* d_slot_map = nullptr);  // cross K/V of clip b goes to slot d_slot_map[b] (device), else b
   void reset_decode_state(int batch, const int* max_new_clip = nullptr);
-  void enqueue_decode_step(int batch, int max_new, const int* d_forced, int n_forced, float* d_logits, long logits_stride,
-                           int* d_argmax);
-  void enqueue_decode_step_batched(int batch, int max_new, const int* d_forced, int n_forced, float* d_logits,
+  // What one decoder step is built as: every step sequence, the graph it is captured into and the key that graph is cached
+  // under are made from ONE of these, handed down as an argument.
+  struct StepSpec {
+    DecodeMode mode = kDecodePlain;
+    // launches of the step (all: 15): 1 GEMV/GEMM launches, 2 attention launches, 4 advance, 8 act_prep, 16 attention launches stamp
+    // themselves (bench only)
+    int mask = 15;
+    TsScoreParams score_out{};  // kDecodeScored: where the scored rules kernel writes
+  };
+  // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
+  // the rules kernel; first_step: the first decode step whose row is computed
+  struct LogitsDump { float* rows; long stride; int first_step; };
+  LogitsDump logits_dump(const StepSpec& spec, float* d_logits, long logits_stride) const;
+  void enqueue_decode_step(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, float* d_logits,
+                           long logits_stride, int* d_argmax);
+  void enqueue_decode_step_batched(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, float* d_logits,
                                    long logits_stride, int* d_argmax);
-  void enqueue_layers_cblock(int b0, int nb, hipStream_t s, bool forced, bool one_branch);
+  // what both end in: the rules kernel (timestamp and scored mode) and advance_kernel; n_part: argmax partials of the logits launch
+  void enqueue_step_tail(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, int* d_argmax, int n_part,
+                         hipStream_t s);
+  void enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStream_t s, bool forced, bool one_branch);
   int decode_branches(int batch) const;
   void ensure_branch_streams(int batch);
-  hipGraphExec_t step_graph(int batch, int max_new);
+  // the captured step of spec.mode / spec.mask; a scored graph writes the engine's own score arrays (spec.score_out is not read)
+  hipGraphExec_t step_graph(StepSpec spec, int batch, int max_new);
   // (two bits for the mode: plain, timestamp and scored steps are three different graphs)
-  long graph_key(int batch, int max_new) const { return ((((long)batch * 1024 + max_new) * 32 + step_mask_) << 2) | ts_mode_; }
-  // decode mode (DecodeMode: 0 plain, 1 timestamps, 2 timestamps + scores): set for the duration of one *_mode call; the step sequences read it
-  int ts_mode_ = 0;
-  struct TsModeScope {
-    int& m;
-    TsModeScope(int& mm, int v) : m(mm) { m = v; }
-    ~TsModeScope() { m = 0; }
-  };
+  static long graph_key(const StepSpec& spec, int batch, int max_new) { return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 2) | spec.mode; }
   void require_timestamp_vocab() const;
   void ensure_ts_logits();  // d_ts_logits_ [cap][ts_stride_], allocated on first use under device_capture_mutex
-  void enqueue_timestamp_rules(int batch, const int* d_forced, int n_forced, hipStream_t s);
+  void enqueue_timestamp_rules(const StepSpec& spec, int batch, const int* d_forced, int n_forced, hipStream_t s);
   float* d_ts_logits_ = nullptr;
   long ts_stride_ = 0;
   // scored mode (DESIGN.md "Confidence"): per-clip log-probability and id of every decision [cap][n_text_ctx], log p(<|nospeech|>)
-  // [cap]; allocated like d_ts_logits_. score_out_ is where the scored rules kernel writes: these arrays, except inside
-  // decode_forced_scores (its own [batch][n_forced + 1] buffers)
+  // [cap]; allocated like d_ts_logits_. own_scores_: these arrays as the scored rules kernel takes them (decode_forced hands it
+  // its own [batch][n_forced + 1] buffers instead)
   float* d_tok_lp_ = nullptr; int* d_dec_id_ = nullptr; float* d_nospeech_ = nullptr;
-  TsScoreParams score_out_{};
+  TsScoreParams own_scores_{};
   void require_scored_vocab() const;  // require_timestamp_vocab + a usable no_speech id
   void ensure_ts_scores();
   // scores of the last scored greedy loop over `batch` slots (n_ids: what fetch_ids returned)
   void fetch_scores(int batch, const int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
-  void decode_forced_impl(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids, float* logprob,
-                          float* no_speech_logprob, float* logits0);
-  void rules_on_host_rows(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob);
-  void long_windows_impl(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                         const LongScoreOptions* opts, std::vector<LongWindow>& log);
   void recover_streams();
   // long-form (engine_long.cpp): the PCM and the log-mel rows of every file of one call in one arena, kept for the next call
   // when small (allocated and freed under device_capture_mutex)
@@ -139,7 +134,7 @@ class Engine final : public IEngine {
   void long_windows_to_slots(const int* files, const int* seeks, int count, bool want_ref_layout);
   void long_release();
   void free_long_arena();
-  int greedy_loop(int batch, int max_new, const int* max_new_clip = nullptr);
+  int greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip = nullptr);
   // batch 1: the whole loop as one persistent launch (decode_persistent.hip); returns steps run, -1 if it gave up
   int run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot = 0, int max_new1 = -1, int max_new2 = -1);
   void fetch_ids(int batch, int32_t* ids, int* n_ids);
@@ -239,13 +234,12 @@ class Engine final : public IEngine {
   DecState* d_state_ = nullptr;
   int* h_poll_ = nullptr;  // pinned
   int split_self_ = 2, split_cross_ = 6;
-  int step_mask_ = 15;  // bench only: 1 GEMV/GEMM launches, 2 attention launches, 4 advance, 8 act_prep, 16 attention launches stamp themselves
   // bench "attn_stamp": every decode_attention launch of a captured step gets a {min begin, max end} slot (DecAttnParams::stamp)
   struct StampMeta { int layer, cross, b0, nb; };
   static constexpr size_t kStampWgs = 4096, kStampLaunches = 256;
   unsigned long long* d_stamp_ = nullptr;
   std::vector<StampMeta> stamp_meta_;
-  unsigned long long* next_stamp(int layer, int cross, int b0, int nb);
+  unsigned long long* next_stamp(const StepSpec& spec, int layer, int cross, int b0, int nb);
   // persistent batch-1 decode
   bool batched_ln_ = false;         // batched decode: clip-block GEMM sequence (AX_WHISPER_BATCHED_LN=0 disables)
   bool persistent_ok_ = false;      // model shape supported and not disabled (AX_WHISPER_DECODE=graph)
@@ -259,7 +253,7 @@ class Engine final : public IEngine {
   int vocab_resident_rows_ = 0;        // one-clip launch: vocabulary rows per workgroup held in the poller waves (0: AX_WHISPER_VOCAB_RESIDENT=0 or unsupported width)
   u64* d_gran_ = nullptr; size_t gran_bytes_ = 0;
   float* d_qfold_ = nullptr;  // query-fold arena of the one-clip launch (d_model <= 768), nullptr = unfolded
-  std::map<long, hipGraphExec_t> graphs_;  // key: batch * 1024 + max_new
+  std::map<long, hipGraphExec_t> graphs_;  // key: graph_key
   hipEvent_t ev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 

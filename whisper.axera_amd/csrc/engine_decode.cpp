@@ -27,14 +27,14 @@ void Engine::reset_decode_state(int batch, const int* max_new_clip) {
 }
 
 // One decoder step for `batch` slots: the launch sequence that is captured into the step graph.
-void Engine::enqueue_decode_step(int batch, int max_new, const int* d_forced, int n_forced, float* d_logits,
+void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, float* d_logits,
                                  long logits_stride, int* d_argmax) {
   const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, Tc = cfg_.n_text_ctx;
   hipStream_t s = stream();
   // 3+ clips: the clip-block sequence (a 4-clip step: 0.78 ms through the GEMV family, 0.59 through clip-block GEMMs);
   // one clip that cannot use the persistent launch and two clips that cannot either stay on the GEMV family
   if (batch > gemv_max_) {
-    enqueue_decode_step_batched(batch, max_new, d_forced, n_forced, d_logits, logits_stride, d_argmax);
+    enqueue_decode_step_batched(spec, batch, max_new, d_forced, n_forced, d_logits, logits_stride, d_argmax);
     return;
   }
 
@@ -44,7 +44,7 @@ void Engine::enqueue_decode_step(int batch, int max_new, const int* d_forced, in
       GemvParams q = p;
       q.batch = std::min(4, batch - b0);
       offset(q, b0);
-      if (step_mask_ & 1) launch_gemv(q, s);
+      if (spec.mask & 1) launch_gemv(q, s);
     }
   };
   auto attn = [&](const h16* kc, const h16* vc, long stride, int n_keys, int cap_blocks, float* part, int n_split) {
@@ -53,7 +53,7 @@ void Engine::enqueue_decode_step(int batch, int max_new, const int* d_forced, in
     a.batch = batch; a.n_head = H; a.d_model = d; a.n_keys = n_keys; a.cap_blocks = cap_blocks; a.state = d_state_;
     a.off = d_off_;
     a.done = d_forced ? d_done_none_ : d_done_;
-    if (step_mask_ & 2) launch_decode_attention(a, s);
+    if (spec.mask & 2) launch_decode_attention(a, s);
   };
 
   const long self_stride = (long)H * Tc * 64, cross_stride = (long)H * t_pad_ * 64;
@@ -106,29 +106,40 @@ void Engine::enqueue_decode_step(int batch, int max_new, const int* d_forced, in
   p.W = tok_emb_; p.bias = nullptr; p.N = cfg_.n_vocab; p.K = d;
   p.prologue = PRO_LAYERNORM; p.in = d_xdec_; p.ln_w = dec_ln_w_; p.ln_b = dec_ln_b_;
   p.epilogue = GEPI_LOGITS; p.state = d_state_; p.off = d_off_; p.amax_val = d_amax_val_; p.amax_idx = d_amax_idx_; p.amax_stride = n_amax_part_;
-  // timestamp mode: the launch also runs at the step that fed `transcribe` and dumps every row for the rules kernel
-  if (ts_mode_) { d_logits = d_ts_logits_; logits_stride = ts_stride_; }
-  // (scored mode: from offset 0 on — the row of the step that fed sot is the no-speech row; the row of offset 1 is computed and ignored)
-  p.skip_before_step = ts_mode_ == 2 ? 0 : ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
+  const LogitsDump dump = logits_dump(spec, d_logits, logits_stride);
+  p.skip_before_step = dump.first_step; p.logits_dump = dump.rows; p.logits_dump_stride = dump.stride;
   gemv(p, [&](GemvParams& q, int b0) {
     q.in += (long)b0 * d; q.amax_val += (long)b0 * n_amax_part_; q.amax_idx += (long)b0 * n_amax_part_; q.off += b0;
-    if (q.logits_dump) q.logits_dump += (long)b0 * logits_stride;
+    if (q.logits_dump) q.logits_dump += (long)b0 * dump.stride;
   });
-  if (ts_mode_ && (step_mask_ & 4)) enqueue_timestamp_rules(batch, d_forced, n_forced, s);
-  AdvanceParams a{};
-  a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = ts_mode_ ? 1 : gemv_grid(p); a.amax_stride = n_amax_part_;
-  a.n_prefix = ts_mode_ ? 3 : 0;
-  a.state = d_state_; a.off = d_off_; a.tok = d_tok_; a.done = d_done_; a.n_out = d_nout_; a.out_ids = d_out_ids_; a.batch = batch;
-  a.n_ctx = Tc; a.eot = cfg_.eot; a.max_new = max_new; a.n_vocab = cfg_.n_vocab; a.max_new_clip = d_max_new_clip_; a.sot = d_sot_;
-  a.forced = d_forced; a.n_forced = n_forced; a.argmax_dump = d_argmax;
-  a.tok_emb = tok_emb_; a.pos = dec_pos_; a.x = d_xdec_; a.d_model = d;
-  a.done_host = d_forced ? nullptr : d_done_live_;
-  if (step_mask_ & 4) launch_advance(a, s);
+  enqueue_step_tail(spec, batch, max_new, d_forced, n_forced, d_argmax, gemv_grid(p), s);
 }
 
-// bench "attn_stamp" (step_mask_ bit 16): the next {min begin, max end} slot, with what the launch is
-unsigned long long* Engine::next_stamp(int layer, int cross, int b0, int nb) {
-  if (!(step_mask_ & 16) || !d_stamp_) return nullptr;
+// timestamp mode: the logits launch also runs at the step that fed `transcribe` and dumps every row for the rules kernel
+// (scored mode: from offset 0 on — the row of the step that fed sot is the no-speech row; the row of offset 1 is computed and ignored)
+Engine::LogitsDump Engine::logits_dump(const StepSpec& spec, float* d_logits, long logits_stride) const {
+  if (spec.mode == kDecodePlain) return {d_logits, logits_stride, 3};
+  return {d_ts_logits_, ts_stride_, spec.mode == kDecodeScored ? 0 : 2};
+}
+
+void Engine::enqueue_step_tail(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, int* d_argmax, int n_part,
+                               hipStream_t s) {
+  const bool rules = spec.mode != kDecodePlain;  // the rules kernel leaves one argmax partial per clip
+  if (rules && (spec.mask & 4)) enqueue_timestamp_rules(spec, batch, d_forced, n_forced, s);
+  AdvanceParams a{};
+  a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = rules ? 1 : n_part; a.amax_stride = n_amax_part_;
+  a.n_prefix = rules ? 3 : 0;
+  a.state = d_state_; a.off = d_off_; a.tok = d_tok_; a.done = d_done_; a.n_out = d_nout_; a.out_ids = d_out_ids_; a.batch = batch;
+  a.n_ctx = cfg_.n_text_ctx; a.eot = cfg_.eot; a.max_new = max_new; a.n_vocab = cfg_.n_vocab; a.max_new_clip = d_max_new_clip_; a.sot = d_sot_;
+  a.forced = d_forced; a.n_forced = n_forced; a.argmax_dump = d_argmax;
+  a.tok_emb = tok_emb_; a.pos = dec_pos_; a.x = d_xdec_; a.d_model = cfg_.n_text_state;
+  a.done_host = d_forced ? nullptr : d_done_live_;
+  if (spec.mask & 4) launch_advance(a, s);
+}
+
+// bench "attn_stamp" (StepSpec::mask bit 16): the next {min begin, max end} slot, with what the launch is
+unsigned long long* Engine::next_stamp(const StepSpec& spec, int layer, int cross, int b0, int nb) {
+  if (!(spec.mask & 16) || !d_stamp_) return nullptr;
   if (stamp_meta_.size() >= kStampLaunches) return nullptr;
   stamp_meta_.push_back({layer, cross, b0, nb});
   return d_stamp_ + 2 * kStampWgs * (stamp_meta_.size() - 1);  // room for kStampWgs workgroups per launch
@@ -138,7 +149,7 @@ unsigned long long* Engine::next_stamp(int layer, int cross, int b0, int nb) {
 // consumer and the residual add the epilogue of its producer, so a layer is 7 launches instead of 11
 // (AX_WHISPER_BATCHED_LN=0: the older sequence with a separate LayerNorm/h16-pair preparation launch and split-K
 // partials). b0 is a multiple of 16: every per-clip buffer of the range starts at a whole clip block.
-void Engine::enqueue_layers_cblock(int b0, int nb, hipStream_t s, bool forced, bool one_branch) {
+void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStream_t s, bool forced, bool one_branch) {
   const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, Tc = cfg_.n_text_ctx;
   const long self_stride = (long)H * Tc * 64, cross_stride = (long)H * t_pad_ * 64;
   const long frag0 = (long)(b0 / 16) * 512;  // fragment-major pair layouts: clip blocks are 512 elements apart within a k-step
@@ -180,8 +191,8 @@ void Engine::enqueue_layers_cblock(int b0, int nb, hipStream_t s, bool forced, b
   int cur_layer = 0;
   // kind: 2 qkv, 3 o, 4 co, 5 fc1, 6 fc2 (0 / 1 are the attention launches) — bench "attn_stamp" puts every launch of the step on one axis
   auto cgo = [&](DecCGemmParams c, int kind) {
-    if (step_mask_ & 16) { c.stamp = next_stamp(cur_layer, kind, b0, nb); c.stamp_point = gemm_stamp_point; }
-    if (step_mask_ & 1) launch_decode_cgemm(c, s);
+    if (spec.mask & 16) { c.stamp = next_stamp(spec, cur_layer, kind, b0, nb); c.stamp_point = gemm_stamp_point; }
+    if (spec.mask & 1) launch_decode_cgemm(c, s);
   };
   auto attn = [&](const h16* kc, const h16* vc, long stride, int n_keys, int cap_blocks) {
     DecAttnParams a{};
@@ -220,7 +231,7 @@ void Engine::enqueue_layers_cblock(int b0, int nb, hipStream_t s, bool forced, b
     c.out = qd; c.k_cache = sk; c.v_cache = sv; c.kv_batch_stride = self_stride;
     if (qfold) { c.fold_row0 = 3 * d; c.ln_w2 = w.cross_ln_w; c.out2 = a0; }
     cgo(c, 2);
-    if (step_mask_ & 2) { DecAttnParams a = attn(sk, sv, self_stride, -1, Tc / 64); a.stamp = next_stamp(l, 0, b0, nb); launch_decode_attention(a, s); }
+    if (spec.mask & 2) { DecAttnParams a = attn(sk, sv, self_stride, -1, Tc / 64); a.stamp = next_stamp(spec, l, 0, b0, nb); launch_decode_attention(a, s); }
     c = qfold ? cgemm(wq.w_o, cfold_[l].b_o2, 2 * d, d, GEPI_RESID, 1) : cgemm(wq.w_o, w.b_o, d, d, GEPI_RESID, 1);
     c.a_hi = att_hi; c.a_lo = att_lo; c.out = x;
     if (qfold) { c.fold_row0 = d; c.W_lo = wq.m_lo; c.out2 = a0; c.stat_part = statp; }
@@ -232,8 +243,8 @@ void Engine::enqueue_layers_cblock(int b0, int nb, hipStream_t s, bool forced, b
       a.mpart = d_attn_mpart_ + (long)b0 * H * kCrossSplitMax * 66;
       a.mcnt = d_attn_mcnt_ + (long)b0 * H;
       a.tq = a0; a.stat_part = statp; a.fold_s = cfold_[l].s; a.fold_c = cfold_[l].c;
-      a.stamp = next_stamp(l, 1, b0, nb);
-      if (step_mask_ & 2) launch_decode_attention(a, s);
+      a.stamp = next_stamp(spec, l, 1, b0, nb);
+      if (spec.mask & 2) launch_decode_attention(a, s);
     } else if (fuse_cq && d <= 1024) {  // the cross-attention workgroups project their own queries (decode_attention_kernel<1>)
       DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64);
       a.q = nullptr;
@@ -241,13 +252,13 @@ void Engine::enqueue_layers_cblock(int b0, int nb, hipStream_t s, bool forced, b
       a.mpart = d_attn_mpart_ + (long)b0 * H * kCrossSplitMax * 66;
       a.mcnt = d_attn_mcnt_ + (long)b0 * H;
       a.x = x; a.ln_w = w.cross_ln_w; a.ln_b = w.cross_ln_b; a.wq = w.w_cq; a.bq = w.b_cq;
-      a.stamp = next_stamp(l, 1, b0, nb);
-      if (step_mask_ & 2) launch_decode_attention(a, s);
+      a.stamp = next_stamp(spec, l, 1, b0, nb);
+      if (spec.mask & 2) launch_decode_attention(a, s);
     } else {
       c = cgemm(wq.w_cq, w.b_cq, d, d, GEPI_STORE, 1);
       c.x = x; c.ln_w = w.cross_ln_w; c.ln_b = w.cross_ln_b; c.out = qd;
       cgo(c, 7);
-      if (step_mask_ & 2) { DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64); a.stamp = next_stamp(l, 1, b0, nb); launch_decode_attention(a, s); }
+      if (spec.mask & 2) { DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64); a.stamp = next_stamp(spec, l, 1, b0, nb); launch_decode_attention(a, s); }
     }
     c = cgemm(wq.w_co, w.b_co, d, d, GEPI_RESID, 1);
     c.a_hi = att_hi; c.a_lo = att_lo; c.out = x;
@@ -290,7 +301,7 @@ int Engine::decode_branches(int batch) const {
 
 // Batched variant (3+ clips): LayerNorm -> h16 pairs (act_prep), MFMA GEMMs that read the weights once for the
 // whole batch, one attention workgroup per (clip, head) writing its output directly (no split partials).
-void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_forced, int n_forced, float* d_logits,
+void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, float* d_logits,
                                          long logits_stride, int* d_argmax) {
   const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, Tc = cfg_.n_text_ctx;
   hipStream_t s = stream();
@@ -305,14 +316,14 @@ void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_fo
       q.nbs = nbs_;
       q.off = d_off_ + b0;
       offset(q, b0);
-      if (step_mask_ & 1) launch_decode_gemm(q, s);
+      if (spec.mask & 1) launch_decode_gemm(q, s);
     }
   };
   // residual GEMMs write split-K partial sums; the next LayerNorm prep folds them (+ bias) into x, in fixed order
   int pend_n = 0;
   const float* pend_bias = nullptr;
   auto ln = [&](const float* g, const float* be) {
-    if (step_mask_ & 8)
+    if (spec.mask & 8)
       launch_act_prep(d_xdec_, g, be, d_act_[0], d_act_[1], batch, d, true, nbs_, d_part_, pend_n, cap_, pend_bias, s);
     pend_n = 0;
   };
@@ -347,8 +358,8 @@ void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_fo
       a.mpart = d_attn_mpart_;
       a.mcnt = d_attn_mcnt_;
     }
-    a.stamp = next_stamp(stamp_layer, n_keys >= 0 ? 1 : 0, 0, batch);
-    if (step_mask_ & 2) launch_decode_attention(a, s);
+    a.stamp = next_stamp(spec, stamp_layer, n_keys >= 0 ? 1 : 0, 0, batch);
+    if (spec.mask & 2) launch_decode_attention(a, s);
   };
   auto base = [&](const h16* W, const float* bias, int N, int K, const h16* ahi, const h16* alo, int epi) {
     DecGemmParams p{};
@@ -364,7 +375,7 @@ void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_fo
     // attention launches (a single chain leaves the chip idle between its ~85 dependent launches).
     const int nbr = decode_branches(batch);
     if (nbr == 1) {
-      enqueue_layers_cblock(0, batch, s, d_forced != nullptr, true);
+      enqueue_layers_cblock(spec, 0, batch, s, d_forced != nullptr, true);
     } else {
       const int per = ((batch + nbr - 1) / nbr + 15) / 16 * 16;
       HIP_CHECK(hipEventRecord(ev_fork_, s));
@@ -373,7 +384,7 @@ void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_fo
         if (nb <= 0) break;
         hipStream_t bs = i == 0 ? s : branch_stream_[i - 1];
         if (i > 0) HIP_CHECK(hipStreamWaitEvent(bs, ev_fork_, 0));
-        enqueue_layers_cblock(b0, nb, bs, d_forced != nullptr, false);
+        enqueue_layers_cblock(spec, b0, nb, bs, d_forced != nullptr, false);
         if (i > 0) {
           HIP_CHECK(hipEventRecord(ev_join_[i - 1], bs));
           HIP_CHECK(hipStreamWaitEvent(s, ev_join_[i - 1], 0));
@@ -412,22 +423,13 @@ void Engine::enqueue_decode_step_batched(int batch, int max_new, const int* d_fo
   const int vocab_rt = decode_logits_resident_ok(d, batch) ? 0 : logits_rt();
   p.rt = vocab_rt;
   p.amax_val = d_amax_val_; p.amax_idx = d_amax_idx_; p.amax_stride = n_amax_part_;
-  if (ts_mode_) { d_logits = d_ts_logits_; logits_stride = ts_stride_; }  // (as in enqueue_decode_step)
-  p.skip_before_step = ts_mode_ == 2 ? 0 : ts_mode_ ? 2 : 3; p.logits_dump = d_logits; p.logits_dump_stride = logits_stride;
+  const LogitsDump dump = logits_dump(spec, d_logits, logits_stride);
+  p.skip_before_step = dump.first_step; p.logits_dump = dump.rows; p.logits_dump_stride = dump.stride;
   gemm(p, [&](DecGemmParams& q, int b0) {
     q.amax_val += (long)b0 * n_amax_part_; q.amax_idx += (long)b0 * n_amax_part_;
-    if (q.logits_dump) q.logits_dump += (long)b0 * logits_stride;
+    if (q.logits_dump) q.logits_dump += (long)b0 * dump.stride;
   });
-  if (ts_mode_ && (step_mask_ & 4)) enqueue_timestamp_rules(batch, d_forced, n_forced, s);
-  AdvanceParams a{};
-  a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = ts_mode_ ? 1 : decode_gemm_grid(cfg_.n_vocab, vocab_rt); a.amax_stride = n_amax_part_;
-  a.n_prefix = ts_mode_ ? 3 : 0;
-  a.state = d_state_; a.off = d_off_; a.tok = d_tok_; a.done = d_done_; a.n_out = d_nout_; a.out_ids = d_out_ids_; a.batch = batch;
-  a.n_ctx = Tc; a.eot = cfg_.eot; a.max_new = max_new; a.n_vocab = cfg_.n_vocab; a.max_new_clip = d_max_new_clip_; a.sot = d_sot_;
-  a.forced = d_forced; a.n_forced = n_forced; a.argmax_dump = d_argmax;
-  a.tok_emb = tok_emb_; a.pos = dec_pos_; a.x = d_xdec_; a.d_model = d;
-  a.done_host = d_forced ? nullptr : d_done_live_;
-  if (step_mask_ & 4) launch_advance(a, s);
+  enqueue_step_tail(spec, batch, max_new, d_forced, n_forced, d_argmax, decode_gemm_grid(cfg_.n_vocab, vocab_rt), s);
 }
 
 // The persistent launch needs every workgroup resident at once; when it gives up (CUs taken by somebody else) the
@@ -480,8 +482,8 @@ void Engine::ensure_branch_streams(int batch) {
     if (!branch_stream_[i]) HIP_CHECK(hipStreamCreateWithFlags(&branch_stream_[i], hipStreamNonBlocking));
 }
 
-hipGraphExec_t Engine::step_graph(int batch, int max_new) {
-  const long key = graph_key(batch, max_new);  // plain and timestamp-mode steps are different graphs
+hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
+  const long key = graph_key(spec, batch, max_new);  // plain and timestamp-mode steps are different graphs
   auto it = graphs_.find(key);
   if (it != graphs_.end()) return it->second;
   hipStream_t s = stream();
@@ -489,12 +491,12 @@ hipGraphExec_t Engine::step_graph(int batch, int max_new) {
   // nobody on this device allocates, copies synchronously or captures while this capture is open (iengine.hpp)
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   ensure_branch_streams(batch);  // before the capture opens
-  if (ts_mode_) ensure_ts_logits();
-  if (ts_mode_ == 2) ensure_ts_scores();
+  if (spec.mode != kDecodePlain) ensure_ts_logits();
+  if (spec.mode == kDecodeScored) { ensure_ts_scores(); spec.score_out = own_scores_; }
   HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   hipError_t cap_err = hipSuccess;
   try {
-    enqueue_decode_step(batch, max_new, nullptr, 0, nullptr, 0, nullptr);
+    enqueue_decode_step(spec, batch, max_new, nullptr, 0, nullptr, 0, nullptr);
     cap_err = hipStreamEndCapture(s, &graph);
   } catch (...) {
     (void)hipStreamEndCapture(s, &graph);
@@ -520,7 +522,7 @@ hipGraphExec_t Engine::step_graph(int batch, int max_new) {
      // ORDER: the probe REPLAYS the step, i.e. runs real decoder steps on whatever state the buffers hold. Every caller
      // therefore asks for its graph BEFORE it sets up the decode state of a request (greedy_loop, stream_begin, bench).
     static const bool align = [] { const char* e = getenv("AX_WHISPER_ALIGN_QUEUES"); return !(e && e[0] == '0'); }();
-    if (align && !user_stream_ && batch > gemv_max_ && batched_ln_ && decode_branches(batch) >= 2 && step_mask_ == 15) {
+    if (align && !user_stream_ && batch > gemv_max_ && batched_ln_ && decode_branches(batch) >= 2 && spec.mask == 15) {
       constexpr size_t kMaxPadStreams = 8;  // per engine, whatever the number of distinct (batch, max_new) graphs a server sees
       int tries = 0;
       bool aligned = graph_branch_shares_queue(hold.e, branch_stream_[0]);
@@ -545,9 +547,9 @@ hipGraphExec_t Engine::step_graph(int batch, int max_new) {
 }
 
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.
-int Engine::greedy_loop(int batch, int max_new, const int* max_new_clip) {
+int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip) {
   const int Tc = cfg_.n_text_ctx;
-  const int n_prefix = ts_mode_ ? 3 : 4;  // timestamp mode: no <|notimestamps|>, one more id fits the context
+  const int n_prefix = spec.mode != kDecodePlain ? 3 : 4;  // timestamp mode: no <|notimestamps|>, one more id fits the context
   if (max_new <= 0 || max_new > Tc - n_prefix) max_new = Tc - n_prefix;
   // One clip: the persistent launch. Two or three clips: ONE multi-clip persistent launch, phase by phase (one clip's rows are
   // computed while the others' hand-offs are in flight; decode_persistent2.hip) — Whisper-small, 444 ids per clip: 134 ms per
@@ -555,7 +557,7 @@ int Engine::greedy_loop(int batch, int max_new, const int* max_new_clip) {
   // the launch-per-phase path. Each clip stops at its own eot / budget.
   // (asked ONCE per request: persistent_usable() counts a back-off down)
   // (timestamp mode: the launch-per-phase step only — the persistent launches carry no timestamp rules)
-  const bool usable = !ts_mode_ && batch <= std::max(2, persist_max_clips_) && persistent_usable();
+  const bool usable = spec.mode == kDecodePlain && batch <= std::max(2, persist_max_clips_) && persistent_usable();
   if (usable && batch >= 2 && batch <= persist_max_clips_) {
     int mn[3] = {max_new, -1, -1};
     for (int b = 0; b < batch; ++b) mn[b] = (max_new_clip && max_new_clip[b] > 0) ? std::min(max_new, max_new_clip[b]) : max_new;
@@ -574,7 +576,7 @@ int Engine::greedy_loop(int batch, int max_new, const int* max_new_clip) {
     if (b == batch) { persistent_succeeded(); return steps; }
     persistent_gave_up();  // these utterances (and the next few) take the launch-per-phase path
   }
-  hipGraphExec_t g = step_graph(batch, max_new);  // (a fresh multi-branch graph is probed with replays: before the state is set)
+  hipGraphExec_t g = step_graph(spec, batch, max_new);  // (a fresh multi-branch graph is probed with replays: before the state is set)
   reset_decode_state(batch, max_new_clip);
   hipStream_t s = stream();
   const int total = std::min(Tc, 4 + max_new);
@@ -690,7 +692,7 @@ void Engine::ensure_ts_logits() {
 }
 
 // Between the logits launch and advance_kernel: one argmax partial per sampling clip, chosen under the timestamp rules
-void Engine::enqueue_timestamp_rules(int batch, const int* d_forced, int n_forced, hipStream_t s) {
+void Engine::enqueue_timestamp_rules(const StepSpec& spec, int batch, const int* d_forced, int n_forced, hipStream_t s) {
   TsRulesParams r{};
   r.logits = d_ts_logits_; r.stride = ts_stride_; r.batch = batch;
   r.n_vocab = cfg_.n_vocab; r.eot = cfg_.eot; r.ts_begin = cfg_.no_timestamps + 1;
@@ -698,7 +700,7 @@ void Engine::enqueue_timestamp_rules(int batch, const int* d_forced, int n_force
   r.out_ids = d_out_ids_; r.n_out = d_nout_; r.n_ctx = cfg_.n_text_ctx;
   r.forced = d_forced; r.n_forced = n_forced;
   r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
-  if (ts_mode_ == 2) launch_timestamp_rules_scored(r, score_out_, s);  // + the decision's log-probability, the no-speech value at offset 0
+  if (spec.mode == kDecodeScored) launch_timestamp_rules_scored(r, spec.score_out, s);  // + the decision's log-probability, the no-speech value at offset 0
   else launch_timestamp_rules(r, s);
 }
 
@@ -717,7 +719,7 @@ void Engine::ensure_ts_scores() {
   d_dec_id_ = (int*)dalloc(n * 4, true);
   d_nospeech_ = (float*)dalloc((size_t)cap_ * 4, true);
   for (void* p : {(void*)d_tok_lp_, (void*)d_dec_id_, (void*)d_nospeech_}) slot_allocs_.push_back(p);  // freed (and re-made) with the slot buffers
-  score_out_ = TsScoreParams{d_tok_lp_, d_dec_id_, (long)cfg_.n_text_ctx, d_nospeech_, (int)cfg_.ints.at("no_speech")};
+  own_scores_ = TsScoreParams{d_tok_lp_, d_dec_id_, (long)cfg_.n_text_ctx, d_nospeech_, (int)cfg_.ints.at("no_speech")};
 }
 
 // After fetch_ids of a scored greedy loop. Decision i of clip b sits at index i: i < n_ids are the kept ids, i == n_ids the decision

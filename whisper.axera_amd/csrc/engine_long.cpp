@@ -136,25 +136,15 @@ void Engine::compute_mel_window(const float* pcm, int n_samples, int seek, float
   long_release();
 }
 
-void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                              std::vector<LongWindow>& log) {
-  long_windows_impl(pcm, n_samples, n_files, max_new, max_passes, nullptr, log);
-}
-
-void Engine::run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                                     const LongScoreOptions& opts, std::vector<LongWindow>& log) {
-  long_windows_impl(pcm, n_samples, n_files, max_new, max_passes, &opts, log);
-}
-
 // opts != nullptr: the windows are decoded in scored mode, every log entry carries its two numbers, and a window the silent-window
 // rule drops emits nothing and advances by its whole length (DESIGN.md "Confidence")
-void Engine::long_windows_impl(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                               const LongScoreOptions* opts, std::vector<LongWindow>& log) {
+void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
+                              const LongScoreOptions* opts, std::vector<LongWindow>& log) {
   if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
   require_no_stream("run_long_windows");
   require_timestamp_vocab();
   if (opts) require_scored_vocab();
-  TsModeScope ts(ts_mode_, opts ? kDecodeScored : kDecodeTimestamps);
+  const StepSpec spec{opts ? kDecodeScored : kDecodeTimestamps};
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   // windows per pass: the engine's capacity (AX_WHISPER_MAX_BATCH / max_batch of Init, or what earlier calls grew it to);
@@ -186,7 +176,7 @@ void Engine::long_windows_impl(const float* const* pcm, const int* n_samples, in
     for (int i = 0; i < A; ++i) { files[i] = active[i]; seeks[i] = seek[active[i]]; }
     long_windows_to_slots(files.data(), seeks.data(), A, false);
     run_encoder(A);
-    steps += greedy_loop(A, max_new, nullptr);
+    steps += greedy_loop(spec, A, max_new, nullptr);
     fetch_ids(A, ids.data(), n_ids.data());
     if (opts) fetch_scores(A, n_ids.data(), nullptr, avg.data(), nsp.data(), nullptr);
     for (int i = 0; i < A; ++i) {

@@ -28,7 +28,8 @@ void Engine::stream_open(int n_slots) {
   ensure_capacity(std::max(n_slots, 3));
   const int n = std::max(n_slots, 3);  // the step sequence of 3+ slots handles any mix of idle and active slots
   hipStream_t s = stream();
-  (void)step_graph(n, cfg_.n_text_ctx - 4);  // captured here, outside the serving loop (and probed with replays: before the state is set)
+  // plain mode, every launch. Captured here, outside the serving loop (and probed with replays: before the state is set)
+  (void)step_graph(StepSpec{}, n, cfg_.n_text_ctx - 4);
   reset_decode_state(n);
   std::vector<int> ones(n, 1);         // every slot idle: its attention launches return at once
   HIP_CHECK(hipMemcpy(d_done_, ones.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -134,7 +135,7 @@ int Engine::stream_step(int n_steps, int* finished_slots) {
       ++active;
     }
   };
-  hipGraphExec_t g = step_graph(n, cfg_.n_text_ctx - 4);
+  hipGraphExec_t g = step_graph(StepSpec{}, n, cfg_.n_text_ctx - 4);  // the graph stream_open captured
   // The host runs two steps ahead of the device (it waits for step k-2 before it enqueues step k): the queue never runs dry,
   // and what the host sees in the flags is at most two steps old, so a waiting clip takes a freed slot within two steps.
   for (int st = 0; st < std::max(1, n_steps); ++st) {
@@ -318,14 +319,13 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
     // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;
     // decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel); decode_step_ts_scored: with the scored rules kernel
     const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored";
-    step_mask_ = whole ? 15 : (what == "decode_gemv" ? 1 : 2);
-    struct Restore { int& m; ~Restore() { m = 15; } } restore{step_mask_};
     if (what == "decode_step_ts") require_timestamp_vocab();
     if (what == "decode_step_ts_scored") require_scored_vocab();
-    TsModeScope ts(ts_mode_, what == "decode_step_ts" ? kDecodeTimestamps : what == "decode_step_ts_scored" ? kDecodeScored : kDecodePlain);
+    StepSpec spec{what == "decode_step_ts" ? kDecodeTimestamps : what == "decode_step_ts_scored" ? kDecodeScored : kDecodePlain};
+    spec.mask = whole ? 15 : (what == "decode_gemv" ? 1 : 2);
     const int Tc = cfg_.n_text_ctx;
     reset_decode_state(batch);
-    hipGraphExec_t g = step_graph(batch, Tc - 4);
+    hipGraphExec_t g = step_graph(spec, batch, Tc - 4);
     arg = std::max(0, std::min(arg, Tc - 1 - iters));
     DecState st{arg, 0, 0, 0};
     std::vector<int> offs(batch, arg);  // every slot at position `arg`
@@ -352,15 +352,15 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
       d_stamp_ = (unsigned long long*)dalloc((size_t)2 * kStampWgs * kStampLaunches * 8, true);
       allocs_.push_back(d_stamp_);
     }
-    step_mask_ = 15 | 16;
-    struct Restore { int& m; ~Restore() { m = 15; } } restore{step_mask_};
+    StepSpec spec{};
+    spec.mask = 15 | 16;
     const int Tc = cfg_.n_text_ctx;
     reset_decode_state(batch);
-    const long key = graph_key(batch, Tc - 4);
+    const long key = graph_key(spec, batch, Tc - 4);
     auto old = graphs_.find(key);
     if (old != graphs_.end()) { (void)hipGraphExecDestroy(old->second); graphs_.erase(old); }
     stamp_meta_.clear();
-    hipGraphExec_t g = step_graph(batch, Tc - 4);
+    hipGraphExec_t g = step_graph(spec, batch, Tc - 4);
     const int warm_replays = iters >= 100 ? iters - 100 : 0;
     arg = std::max(0, std::min(arg, Tc - 4 - warm_replays));  // every replay advances the clips by one position
     DecState st{arg, 0, 0, 0};

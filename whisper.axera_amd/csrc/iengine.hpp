@@ -27,10 +27,23 @@ struct ModelConfig {
 class IEngine {
  public:
   virtual ~IEngine() {}
+  // decode modes: kDecodePlain = prefix [sot, lang, transcribe, notimestamps];
+  // kDecodeTimestamps = prefix [sot, lang, transcribe] and Whisper's timestamp rules at every sampled step (DESIGN.md
+  // "Segment timestamps"); ids then include timestamp tokens
+  // kDecodeScored = kDecodeTimestamps that also keeps, per clip, the log-probability of every decision and log p(<|nospeech|>) at
+  // the step that fed sot (DESIGN.md "Confidence"); the ids are those of kDecodeTimestamps
+  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1, kDecodeScored = 2 };
+  // what kDecodeScored keeps (DESIGN.md "Confidence"); every array may be null.
+  // greedy: token_logprob [batch][n_text_ctx]: entries 0 .. n_ids[b] (one per kept id + the decision that ended the clip), the
+  // rest 0; avg_logprob, no_speech_logprob, ended_eot [batch]
+  struct ClipScores { float *token_logprob, *avg_logprob, *no_speech_logprob; int* ended_eot; };
+  // forced: logprob [batch][n_forced+1] of each step's chosen id, no_speech_logprob [batch], logits0 [batch][n_vocab]: the raw row
+  // of decode offset 0
+  struct ForcedScores { float *logprob, *no_speech_logprob, *logits0; };
   // full path, host PCM or device PCM; ids [batch][n_text_ctx], n_ids [batch]
-  // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new
-  virtual void run_tokens(const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
-                          int32_t* ids, int* n_ids, const int* max_new_clip = nullptr) = 0;
+  // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new; scores: kDecodeScored only
+  virtual void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
+                          int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores) = 0;
   virtual std::string detokenize(const int32_t* ids, int n) const = 0;
   // detokenize + the reference's zh post-pass (Traditional -> Simplified, Whisper.cpp:231-236) when its OpenCC data files were found
   virtual std::string transcript(const int32_t* ids, int n) const = 0;
@@ -38,9 +51,16 @@ class IEngine {
   virtual void compute_mel(const float* pcm, int n_samples, float* mel_out) = 0;
   virtual void encode_mel(const float* mel, int batch) = 0;
   virtual void get_cross_kv(int slot, float* k_out, float* v_out) = 0;
-  virtual void decode_forced(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) = 0;
-  // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new
-  virtual void decode_greedy(int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
+  // timestamp and scored mode: logits are the raw logits (before the rules), chosen the ids the rules choose; scores: kDecodeScored only
+  virtual void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
+                             const ForcedScores* scores) = 0;
+  // plain or timestamp mode; max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new
+  virtual void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
+  // the rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] (n_hist[b] ids each) -> chosen [batch];
+  // logprob [batch] (null: the unscored kernel): the scored kernel, + the log-probability of every chosen id
+  virtual void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) = 0;
+  // the no-speech kernel alone: logits [batch][n_vocab] -> out [batch] = log p(<|nospeech|>) over the whole row
+  virtual void no_speech_logprob(const float* logits, int batch, float* out) = 0;
   // utterance slots refilled while the others decode (include/ax_whisper_api.h: AX_WHISPER_Stream*)
   virtual void stream_open(int n_slots) = 0;
   virtual void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) = 0;
@@ -50,43 +70,14 @@ class IEngine {
   // every 16-bit tensor the engine STORES between kernels (encoder activations of `batch` clips, cross / self K/V caches, the
   // decoder's activation pairs): non-finite count and max |x| per buffer; returns the number of buffers reported (<= n_max)
   virtual int scan_stored16(int batch, int n_max, char (*names)[32], long long* nonfinite, float* maxabs) = 0;
-  // decode modes of the *_mode variants: kDecodePlain = the calls above (prefix [sot, lang, transcribe, notimestamps]),
-  // kDecodeTimestamps = prefix [sot, lang, transcribe] and Whisper's timestamp rules at every sampled step (DESIGN.md
-  // "Segment timestamps"); ids then include timestamp tokens
-  // kDecodeScored = kDecodeTimestamps that also keeps, per clip, the log-probability of every decision and log p(<|nospeech|>) at
-  // the step that fed sot (DESIGN.md "Confidence"); the ids are those of kDecodeTimestamps
-  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1, kDecodeScored = 2 };
-  virtual void run_tokens_mode(int mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
-                               int max_new, int32_t* ids, int* n_ids, const int* max_new_clip) = 0;
-  // timestamp mode: logits are the raw logits (before the rules), argmax_ids the ids the rules choose
-  virtual void decode_forced_mode(int mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids) = 0;
-  virtual void decode_greedy_mode(int mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
-  // the rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] (n_hist[b] ids each) -> chosen [batch]
-  virtual void apply_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen) = 0;
-  // ---- confidence (DESIGN.md "Confidence"). token_logprob [batch][n_text_ctx]: entries 0 .. n_ids[b] (one per kept id + the
-  // decision that ended the clip), the rest 0; avg_logprob, no_speech_logprob, ended_eot [batch]
-  virtual void run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                                 int32_t* ids, int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob,
-                                 int* ended_eot) = 0;
-  // decode_forced_mode(kDecodeTimestamps) + logprob [batch][n_forced+1] of each step's chosen id, no_speech_logprob [batch] and
-  // (optional) logits0 [batch][n_vocab], the raw row of decode offset 0
-  virtual void decode_forced_scores(int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen, float* logprob,
-                                    float* no_speech_logprob, float* logits0) = 0;
-  // apply_timestamp_rules + logprob [batch]: the scored kernel alone on host rows
-  virtual void score_timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen,
-                                     float* logprob) = 0;
-  // the no-speech kernel alone: logits [batch][n_vocab] -> out [batch] = log p(<|nospeech|>) over the whole row
-  virtual void no_speech_logprob(const float* logits, int batch, float* out) = 0;
-  // run_long_windows with the scores of every window in the log; the silent-window rule under opts' thresholds
-  virtual void run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                                       const LongScoreOptions& opts, std::vector<LongWindow>& log) = 0;
   // long-form (DESIGN.md "Long-form"): the whole-file front-end + the window kernel for one file -> the window at `seek`
   // (frames) in the reference layout, host [n_mels * 3000]
   virtual void compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) = 0;
   // the seek loop over n_files files, one window of every unfinished file per pass; log: every decoded window in execution
   // order (file counts from 0 within this call). max_new: per-window id budget (<= 0: none), max_passes <= 0: until every file ends
+  // opts (null: the unscored loop): the scores of every window in the log; the silent-window rule under opts' thresholds
   virtual void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
-                                std::vector<LongWindow>& log) = 0;
+                                const LongScoreOptions* opts, std::vector<LongWindow>& log) = 0;
   virtual float bench(const std::string& what, int batch, int arg, int iters) = 0;
   virtual void set_stream(void* hip_stream) = 0;
   virtual const ModelConfig& config() const = 0;

@@ -64,8 +64,8 @@ void run_sharded(int n, int world, Fn&& fn) {
     if (failed[w]) throw std::runtime_error("device worker " + std::to_string(w) + ": " + errors[w]);
 }
 
-// G engines, one per device. E needs: std::mutex& mutex(); void run_tokens(const float* const* pcm, const float* d_pcm,
-// int d_stride, const int* n_samples, int batch, int max_new, int32_t* ids, int* n_ids).
+// G engines, one per device. E needs: std::mutex& mutex(); an enum DecodeMode; a struct ClipScores {float *token_logprob,
+// *avg_logprob, *no_speech_logprob; int* ended_eot;}; run_tokens and run_long_windows as they are called below.
 template <typename E>
 class DeviceGroup {
  public:
@@ -75,81 +75,33 @@ class DeviceGroup {
   E& at(int i) { return *engines_.at(i); }
   E& primary() { return *engines_.at(0); }
 
-  // Host PCM of `batch` clips -> ids [batch][n_ctx], n_ids [batch]. With one engine (or one clip) this is the
-  // engine's own call; otherwise workers = min(G, batch) engines each take one contiguous block. An engine is
-  // serialised by its own mutex (a handle may be shared between threads), engines of different devices run concurrently.
-  void run_tokens(const float* const* pcm, const int* n_samples, int batch, int max_new, int n_ctx, int32_t* ids, int* n_ids) {
+  // Host PCM of `batch` clips -> ids [batch][n_ctx], n_ids [batch] (E::run_tokens: a decode mode, optional per-clip budgets
+  // max_new_clip [batch], optional per-clip scores, token_logprob [batch][n_ctx]). With one engine (or one clip) this is the
+  // engine's own call; otherwise workers = min(G, batch) engines each take one contiguous block of every per-clip array.
+  void run_tokens(typename E::DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
+                  int n_ctx, int32_t* ids, int* n_ids, const typename E::ClipScores* scores = nullptr) {
     if (batch < 1) throw std::runtime_error("batch must be >= 1");
-    const int G = size(), world = G < batch ? G : batch;
-    // calls with fewer clips than devices start at a rotating device, so that concurrent small requests on one handle
-    // (a server thread pool calling AX_WHISPER_RunPCM) spread over the GPUs instead of queueing on the first engine
-    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
-    run_sharded(batch, world, [&](int w, int lo, int hi) {
-      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
-      std::lock_guard<std::mutex> lock(e.mutex());
-      e.run_tokens(pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, ids + (size_t)lo * n_ctx, n_ids + lo);
+    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
+    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
+      typename E::ClipScores sc{};
+      if (scores)
+        sc = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
+              from(scores->ended_eot, lo)};
+      e.run_tokens(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), ids + (size_t)lo * n_ctx, n_ids + lo,
+                   scores ? &sc : nullptr);
     });
   }
 
-  // The same sharding for E::run_tokens_mode (a decode mode, optional per-clip budgets max_new_clip [batch]).
-  void run_tokens_mode(int mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int n_ctx,
-                       int32_t* ids, int* n_ids) {
-    if (batch < 1) throw std::runtime_error("batch must be >= 1");
-    const int G = size(), world = G < batch ? G : batch;
-    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
-    run_sharded(batch, world, [&](int w, int lo, int hi) {
-      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
-      std::lock_guard<std::mutex> lock(e.mutex());
-      e.run_tokens_mode(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, ids + (size_t)lo * n_ctx, n_ids + lo,
-                        max_new_clip ? max_new_clip + lo : nullptr);
-    });
-  }
-
-  // The same sharding for E::run_tokens_scores (timestamp mode + per-clip scores; token_logprob [batch][n_ctx])
-  void run_tokens_scores(const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip, int n_ctx,
-                         int32_t* ids, int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
-    if (batch < 1) throw std::runtime_error("batch must be >= 1");
-    const int G = size(), world = G < batch ? G : batch;
-    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
-    run_sharded(batch, world, [&](int w, int lo, int hi) {
-      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
-      std::lock_guard<std::mutex> lock(e.mutex());
-      e.run_tokens_scores(pcm + lo, n_samples + lo, hi - lo, max_new, max_new_clip ? max_new_clip + lo : nullptr, ids + (size_t)lo * n_ctx,
-                          n_ids + lo, token_logprob + (size_t)lo * n_ctx, avg_logprob + lo, no_speech_logprob + lo, ended_eot + lo);
-    });
-  }
-
-  // Long-form (E::run_long_windows): the FILES are split into contiguous blocks, one per engine; every engine runs its own seek
-  // loop. The log holds worker 0's windows first, then worker 1's, ...; file indices count over the whole call, pass and slot
-  // are the engine's own. W needs an int member `file`.
-  template <typename W>
-  void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, std::vector<W>& log) {
-    if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
-    const int G = size(), world = G < n_files ? G : n_files;
-    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
-    std::vector<std::vector<W>> logs(world);
-    run_sharded(n_files, world, [&](int w, int lo, int hi) {
-      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
-      std::lock_guard<std::mutex> lock(e.mutex());
-      e.run_long_windows(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, logs[w]);
-      for (W& x : logs[w]) x.file += lo;
-    });
-    for (auto& l : logs)
-      for (W& x : l) log.push_back(std::move(x));
-  }
-
-  // E::run_long_windows_scored, sharded the same way (O: the thresholds of the silent-window rule)
+  // Long-form (E::run_long_windows; opts: the thresholds of the silent-window rule, or null): the FILES are split into contiguous
+  // blocks, one per engine; every engine runs its own seek loop. The log holds worker 0's windows first, then worker 1's, ...; file
+  // indices count over the whole call, pass and slot are the engine's own. W needs an int member `file`.
   template <typename W, typename O>
-  void run_long_windows_scored(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const O& opts,
-                               std::vector<W>& log) {
+  void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const O* opts,
+                        std::vector<W>& log) {
     if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
-    const int G = size(), world = G < n_files ? G : n_files;
-    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
-    std::vector<std::vector<W>> logs(world);
-    run_sharded(n_files, world, [&](int w, int lo, int hi) {
-      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
-      std::lock_guard<std::mutex> lock(e.mutex());
-      e.run_long_windows_scored(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, opts, logs[w]);
+    std::vector<std::vector<W>> logs(size());
+    for_each_shard(n_files, [&](E& e, int w, int lo, int hi) {
+      e.run_long_windows(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, opts, logs[w]);
       for (W& x : logs[w]) x.file += lo;
     });
     for (auto& l : logs)
@@ -157,6 +109,21 @@ class DeviceGroup {
   }
 
  private:
+  // fn(engine, worker, lo, hi) for every non-empty block of n items (run_sharded over min(G, n) workers). An engine is serialised
+  // by its own mutex (a handle may be shared between threads), engines of different devices run concurrently.
+  template <typename Fn>
+  void for_each_shard(int n, Fn&& fn) {
+    const int G = size(), world = G < n ? G : n;
+    // calls with fewer items than devices start at a rotating device, so that concurrent small requests on one handle
+    // (a server thread pool calling AX_WHISPER_RunPCM) spread over the GPUs instead of queueing on the first engine
+    const unsigned first = world < G ? next_.fetch_add((unsigned)world) % (unsigned)G : 0u;
+    run_sharded(n, world, [&](int w, int lo, int hi) {
+      E& e = *engines_[(first + (unsigned)w) % (unsigned)G];
+      std::lock_guard<std::mutex> lock(e.mutex());
+      fn(e, w, lo, hi);
+    });
+  }
+
   std::vector<std::unique_ptr<E>> engines_;
   std::atomic<unsigned> next_{0};
 };
