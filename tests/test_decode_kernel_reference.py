@@ -1,0 +1,434 @@
+"""No GPU: the bounds of tests/decode_kernel_reference.py hold for a faithful float32 emulation of every batched decode-step
+kernel, and do not hold for sixteen seeded defects — at the shapes tests/test_gpu_decode_kernels.py runs, through the very check
+(`verify`) it applies to the GPU's dumps.
+
+The emulations follow the kernels' arithmetic in numpy float32: the one-pass LayerNorm statistics in the lanes' and waves' order,
+the pair split, k-steps dealt round-robin over eight waves with hi and lo accumulated one after the other and the waves added in
+order behind the bias, erf GELU, 16-bit stores; the two-pass statistics of act_prep behind its fixed-order partial fold; the
+online softmax per wave over every fourth 64-key block, the waves' merge, the splits' fold in split order, exp in float32.
+
+Defect 9 (softmax scale 0.125 + 2^-10, 0.8 % of every score) is visible in BOTH builds: the attention output leaves as an (hi, lo)
+pair or as fp32 partials, never as one 16-bit value, so 16 (bfloat16) or 22 (half) bits of it are checked. Defect 11 is modelled
+as an empty split recording (m, l) = (0, 1) — one phantom key of weight 1 — because a record of (-inf, 0, 0) adds nothing whatever
+weight the fold gives it. Defects 1 and 2 drop terms of relative size u16 with random signs, sqrt(K) u16 |w||a| in all, against an
+any-order accumulation bound of 2 K u K |w||a| (4 K u on the fold rows): their ratio is 2^15 / K^1.5 in bfloat16 and 2^11 / K^1.5 in
+half. So defect 1 is visible in bfloat16 at every K here and in half at K = 128 only (1.4; 0.1 at K = 768), and defect 2 (K = 384,
+768) in bfloat16 only — in half M_hi alone carries 11 bits and what M_lo adds lies below what any fp32 summation order may lose.
+Defect 4 (tanh GELU, up to 5e-4 from erf) needs the pair input at K = 128 for the same reason. Defect 1 is asserted on stored-pair inputs; behind the LayerNorm prologue the any-order bound of the
+statistics (K u on the mean, (3 K + 4) kappa u on the variance) is as large as the lo half in bfloat16 at these K."""
+import numpy as np
+import pytest
+import torch
+
+import decode_kernel_reference as R
+from encoder_kernel_reference import GUARD, from_bits, round16, sentinel, to_bits
+
+F = np.float32
+DTYPES = ("bf16", "f16")
+
+
+def guarded(a):
+    g = sentinel(GUARD // 2, 2)
+    return np.concatenate([g, np.ascontiguousarray(a).ravel().view(np.uint16), g])
+
+
+def exp32(x):
+    with np.errstate(under="ignore", over="ignore"):
+        return np.exp(x.astype(F) if isinstance(x, np.ndarray) else F(x)).astype(F)
+
+
+# ------------------------------------------------------------------------------------------ emulations
+def emu_ln_onepass(x, g, b, eps=True):
+    """decode_cgemm_kernel's prologue: x fp32 [B][K]; lane (r, q) of wave w sums its 8 values of the k-steps w, w + 8, ...; the four
+    q lanes pair up as (0 + 1) + (2 + 3); the eight waves are added in order."""
+    B, K = x.shape
+    KS = K // 32
+    v = x.reshape(B, KS, 4, 2, 4)
+    s1w, s2w = np.zeros((8, B, 4), F), np.zeros((8, B, 4), F)
+    for ks in range(KS):
+        for u in range(2):
+            t = v[:, ks, :, u]
+            s1w[ks % 8] += (t[..., 0] + t[..., 1]) + (t[..., 2] + t[..., 3])
+            s2w[ks % 8] += (t[..., 0] * t[..., 0] + t[..., 1] * t[..., 1]) + (t[..., 2] * t[..., 2] + t[..., 3] * t[..., 3])
+    lanes = lambda s: (s[..., 0] + s[..., 1]) + (s[..., 2] + s[..., 3])
+    s1, s2 = np.zeros(B, F), np.zeros(B, F)
+    for w in range(8):
+        s1 += lanes(s1w[w]); s2 += lanes(s2w[w])
+    mean = (s1 / F(K))[:, None]
+    var = np.maximum(s2[:, None] / F(K) - mean * mean, F(0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rstd = (F(1) / np.sqrt(var + (F(1e-5) if eps else F(0)))).astype(F)
+        return ((x - mean) * rstd * g + b).astype(F)
+
+
+def emu_mma(W, hi, lo, bias, Wl=None, drop_lo=False, drop_wl=False):
+    """y[b][n]: eight waves take the k-steps round-robin, hi then lo per k-step (fp32), then bias + the waves in order."""
+    K = W.shape[1]
+    acc = np.zeros((8, hi.shape[0], W.shape[0]), F)
+    for ks in range(K // 32):
+        sl = slice(ks * 32, ks * 32 + 32)
+        a = acc[ks % 8]
+        a += hi[:, sl] @ W[:, sl].T
+        if not drop_lo:
+            a += lo[:, sl] @ W[:, sl].T
+        if Wl is not None and not drop_wl:
+            a += hi[:, sl] @ Wl[:, sl].T
+            a += lo[:, sl] @ Wl[:, sl].T
+    y = np.broadcast_to(bias.astype(F), acc[0].shape).copy()
+    for w in range(8):
+        y += acc[w]
+    return y
+
+
+def gelu32(y, tanh=False):
+    t = torch.from_numpy(y)
+    if tanh:
+        return (0.5 * t * (1 + torch.tanh(0.7978845608028654 * (t + 0.044715 * t ** 3)))).numpy()
+    return (F(0.5) * y * (F(1) + torch.erf(t * F(0.70710678118654752440)).numpy())).astype(F)
+
+
+def put_pair(state, hn, ln_, idx, y, dt):
+    hb, lb = R.pair_bits(y, dt)
+    h, l = state[hn].copy(), state[ln_].copy()
+    h[idx], l[idx] = hb, lb
+    return {hn: guarded(h), ln_: guarded(l)}
+
+
+def emu_gemm(p, state, dt, defect=None):
+    st = R.typed(p, state)
+    N, K, B, nbs, epi = p["N"], p["K"], p["batch"], p["nbs"], p["epilogue"]
+    fr0 = p.get("fold_row0", 0)
+    W = from_bits(R.unpack_weight(st[p["W"]], N, K), dt).astype(F)
+    bias = st[p["bias"]].astype(F) if p.get("bias") else np.zeros(N, F)
+    drop_lo = defect == "drop_lo"
+    hi2 = lo2 = None
+    if p.get("ln_w"):
+        x = st[p["x"]][:B * K].reshape(B, K)
+        hi, lo = R.pair_split(emu_ln_onepass(x, st[p["ln_w"]], st[p["ln_b"]], eps=defect != "no_eps"), dt)
+        if p.get("ln_w2"):
+            hi2, lo2 = R.pair_split(x * st[p["ln_w2"]], dt)
+    else:
+        idx = R.frag_index(np.arange(B)[:, None], np.arange(K)[None, :], nbs)
+        hi, lo = from_bits(st[p["a_hi"]][idx], dt).astype(F), from_bits(st[p["a_lo"]][idx], dt).astype(F)
+    bi, ni = np.arange(B)[:, None], np.arange(N)[None, :]
+    got = {}
+    if epi == R.GEPI_PARTIAL:
+        ks, pb = p["ksplit"], p["part_batch"]
+        out = st[p["out"]].copy()
+        for s in range(ks):
+            sl = slice(s * K // ks, (s + 1) * K // ks)
+            out[((s * pb + bi) * N + ni).ravel()] = emu_mma(W[:, sl], hi[:, sl], lo[:, sl], np.zeros(N, F), drop_lo=drop_lo).ravel()
+        return {p["out"]: guarded(out)}
+    nx = fr0 if fr0 else N
+    y = emu_mma(W[:nx], hi, lo, bias[:nx], drop_lo=drop_lo)
+    y2 = None
+    if fr0 and hi2 is not None:
+        y2 = emu_mma(W[fr0:], hi2, lo2, bias[fr0:], drop_lo=drop_lo)
+    elif fr0:
+        Wl = from_bits(R.unpack_weight(st[p["W_lo"]], N - fr0, K), dt).astype(F)
+        y2 = emu_mma(W[fr0:], hi, lo, bias[fr0:], Wl=Wl, drop_lo=drop_lo, drop_wl=defect == "drop_mlo")
+    if epi == R.GEPI_STORE:
+        out = st[p["out"]].copy()
+        out[:B * N] = y.ravel()
+        got[p["out"]] = guarded(out)
+    elif epi == R.GEPI_RESID:
+        out = st[p["out"]].copy()
+        xn = y if defect == "resid_store" else out[:B * nx].reshape(B, nx) + y
+        out[:B * nx] = xn.ravel()
+        got[p["out"]] = guarded(out)
+        if fr0:
+            o2 = st[p["out2"]].copy()
+            o2[:B * (N - fr0)] = (o2[:B * (N - fr0)].reshape(B, -1) + y2).ravel()
+            got[p["out2"]] = guarded(o2)
+        if p.get("stat_part"):
+            xb = xn.reshape(B, nx // 16, 16)
+            s1 = xb.sum(2, dtype=F)
+            dm = xb - (s1 * F(1 / 16))[..., None]
+            sp = st[p["stat_part"]].copy()
+            sp[:B * (nx // 16) * 2] = np.stack([s1, (dm * dm).sum(2, dtype=F)], 2).ravel()
+            got[p["stat_part"]] = guarded(sp)
+    elif epi == R.GEPI_GELU:
+        got.update(put_pair(st, p["out_hi"], p["out_lo"], R.frag_index(bi, ni, nbs), gelu32(y, tanh=defect == "gelu_tanh"), dt))
+    elif epi == R.GEPI_QKV_CACHE:
+        d, bs, Tc = p["d_model"], p["kv_batch_stride"], p["n_ctx_pad"]
+        out = st[p["out"]].copy()
+        out[:B * d] = y[:, :d].ravel()
+        got[p["out"]] = guarded(out)
+        off = st[p["off"]][:B].astype(np.int64)[:, None]
+        if defect == "cache_clip0":
+            off = np.full_like(off, off[0, 0])
+        if defect == "cache_plus1":
+            off = off + 1
+        c = np.arange(d)[None, :]
+        base = bi * bs + (c >> 6) * Tc * 64
+        kc, vc = st[p["k_cache"]].copy(), st[p["v_cache"]].copy()
+        kc[(base + R.kcache_index(off, c & 63, "swap" if defect == "cache_swap" else None)) % kc.size] = to_bits(y[:, d:2 * d], dt)  # (a kernel would leave the buffer)
+        vc[base + R.vcache_index(off, c & 63)] = to_bits(y[:, 2 * d:3 * d], dt)
+        got.update({p["k_cache"]: guarded(kc), p["v_cache"]: guarded(vc)})
+        if fr0:
+            o2 = st[p["out2"]].copy()
+            o2[:B * d] = y2.ravel()
+            got[p["out2"]] = guarded(o2)
+    elif epi == R.GEPI_LOGITS:
+        grid, stv = R.dgemm_grid(N, p["rt"]), p["amax_stride"]
+        av, ai = st[p["amax_val"]].copy(), st[p["amax_idx"]].copy()
+        dump = st[p["logits_dump"]].copy() if p.get("logits_dump") else None
+        if (st[p["off"]][:B] >= p["skip_before_step"]).any():
+            seen = np.ones(N, dtype=bool)
+            if defect == "skip_block" and p["rt"] == 0:  # the third body of the last trip of the 3 G loop is left out
+                n_rb = (N + 15) // 16
+                for w in range(grid):
+                    mine = np.arange(w, n_rb, grid)
+                    if mine.size % 3 == 0:
+                        seen[mine[-1] * 16:mine[-1] * 16 + 16] = False
+            ym = np.where(seen[None, :], y, -np.inf).astype(F)
+            v, i = R.argmax_expect(ym, N, p["rt"], grid, last=defect == "argmax_last")
+            for c in range(B):
+                av[c * stv:c * stv + grid], ai[c * stv:c * stv + grid] = v[c], i[c]
+                if dump is not None:
+                    row = dump[c * p["logits_dump_stride"]:c * p["logits_dump_stride"] + N]
+                    row[seen] = y[c, seen]
+        got.update({p["amax_val"]: guarded(av), p["amax_idx"]: guarded(ai)})
+        if dump is not None:
+            got[p["logits_dump"]] = guarded(dump)
+    return got
+
+
+def emu_actprep(p, state, dt, defect=None):
+    st = R.typed(p, state)
+    B, K, nbs, n_part, pb = p["batch"], p["K"], p["nbs"], p["n_part"], p.get("part_batch", 0)
+    x = st[p["x"]].copy()
+    v = x[:B * K].reshape(B, K).copy()
+    if n_part:
+        v += st[p["part_bias"]]
+        for s in range(n_part - (1 if defect == "slice_left_out" else 0)):
+            v += st[p["part"]][s * pb * K:(s * pb + B) * K].reshape(B, K)
+        x[:B * K] = v.ravel()
+    if p["do_ln"]:
+        mean = (v.sum(1, dtype=F) / F(K))[:, None]
+        t = v - mean
+        rstd = F(1) / np.sqrt((t * t).sum(1, dtype=F)[:, None] / F(K) + F(1e-5))
+        v = (t * rstd * st[p["g"]] + st[p["be"]]).astype(F)
+    got = put_pair(st, p["hi"], p["lo"], R.frag_index(np.arange(B)[:, None], np.arange(K)[None, :], nbs), v, dt)
+    got[p["x"]] = guarded(x)
+    return got
+
+
+def emu_query(p, st, dt, defect):
+    B, d = p["batch"], p["d_model"]
+    if p.get("tq"):
+        tq = st[p["tq"]][:B * d].reshape(B, d)
+        sp = st[p["stat_part"]][:B * (d // 16) * 2].reshape(B, d // 16, 2)
+        mean = (sp[..., 0].sum(1, dtype=F) / F(d))[:, None]
+        dm = sp[..., 0] * F(1 / 16) - mean
+        t = sp[..., 1] + (F(0) if defect == "fold_no_between" else F(16) * dm * dm)
+        rstd = F(1) / np.sqrt(t.sum(1, dtype=F)[:, None] / F(d) + F(1e-5))
+        return (rstd * (tq - mean * st[p["fold_s"]]) + st[p["fold_c"]]).astype(F)
+    if p.get("wq"):
+        x = st[p["x"]][:B * d].reshape(B, d)
+        s1, s2 = x.sum(1, dtype=F), (x * x).sum(1, dtype=F)  # one pass, as the kernel (its order: 256 threads x 4, then the waves)
+        mean = (s1 / F(d))[:, None]
+        var = np.maximum(s2[:, None] / F(d) - mean * mean, F(0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            y = ((x - mean) * (F(1) / np.sqrt(var + (F(1e-5) if defect != "no_eps" else F(0)))) * st[p["ln_w"]] + st[p["ln_b"]]).astype(F)
+        return (y @ from_bits(st[p["wq"]], dt).astype(F).reshape(d, d).T + st[p["bq"]]).astype(F)
+    return st[p["q"]][:B * d].reshape(B, d)
+
+
+def emu_split(q, k, v, n_keys, blk0, blk1, defect):
+    """One workgroup: blocks [blk0, blk1) dealt over four waves; returns (m, l, o[64]) of the split."""
+    scale = F(0.125) + (F(2.0 ** -10) if defect == "scale" else F(0))
+    recs = []
+    for w in range(4):
+        m_w, l, o = F(-np.inf), np.zeros(64, F), np.zeros(64, F)
+        for blk in range(blk0 + w, min(blk1, (n_keys + 63) // 64), 4):
+            kk, vv = k[blk * 64:blk * 64 + 64], v[blk * 64:blk * 64 + 64]
+            sc = (kk @ q).astype(F) * scale
+            key = blk * 64 + np.arange(64)
+            sc[(key > n_keys) if defect == "mask_gt" else (key >= n_keys)] = -np.inf
+            m_new = max(m_w, sc.max())
+            alpha, pk = exp32(m_w - m_new), exp32(sc - m_new)
+            l = l * alpha + pk
+            o = o * alpha + (pk @ vv).astype(F)
+            m_w = m_new
+        recs.append((m_w, l.sum(dtype=F), o))
+    m = max(r[0] for r in recs)
+    L, O = F(0), np.zeros(64, F)
+    if m > -np.inf:
+        for mw, lw, ow in recs:
+            f = exp32(mw - m)
+            L, O = L + f * lw, O + f * ow
+    elif defect == "empty_weight1":
+        m, L = F(0), F(1)
+    return m, L, O
+
+
+def emu_attn(p, state, dt, defect=None):
+    st = R.typed(p, state)
+    B, H, d, cap, ns = p["batch"], p["n_head"], p["d_model"], p["cap_blocks"], p.get("n_split", 1)
+    q = emu_query(p, st, dt, defect)
+    k = R.kv_natural(st[p["k"]], B, H, cap, p["kv_batch_stride"], dt, True).astype(F)
+    v = R.kv_natural(st[p["v"]], B, H, cap, p["kv_batch_stride"], dt, False).astype(F)
+    bps = (cap + ns - 1) // ns
+    pair = bool(p.get("out_hi"))
+    vals = np.zeros((B, d), F)
+    part = None if pair else st[p["part"]].copy()
+    for b in range(B):
+        if st[p["done"]][b]:
+            continue
+        nk = p["n_keys"] if p["n_keys"] >= 0 else int(st[p["off"]][b]) + 1
+        for h in range(H):
+            recs = [emu_split(q[b, h * 64:h * 64 + 64], k[b, h], v[b, h], nk, s * bps, min(cap, (s + 1) * bps), defect) for s in range(ns)]
+            if not pair:
+                for s, (m, l, o) in enumerate(recs):
+                    at = ((b * H + h) * ns + s) * R.PART
+                    part[at], part[at + 1], part[at + 2:at + R.PART] = m, l, o
+                continue
+            M, Ls, O = F(-np.inf), F(0), np.zeros(64, F)
+            for m2, l2, o2 in recs:
+                mn = max(M, m2)
+                if defect == "no_rescale":
+                    f1, f2 = F(M > -np.inf), F(m2 > -np.inf)
+                else:
+                    f1, f2 = (exp32(M - mn) if M > -np.inf else F(0)), (exp32(m2 - mn) if m2 > -np.inf else F(0))
+                Ls, O, M = f1 * Ls + f2 * l2, f1 * O + f2 * o2, mn
+            vals[b, h * 64:h * 64 + 64] = O / Ls
+    if not pair:
+        return {p["part"]: guarded(part)}
+    act = np.nonzero(st[p["done"]][:B] == 0)[0]
+    got = put_pair(st, p["out_hi"], p["out_lo"], R.frag_index(act[:, None], np.arange(d)[None, :], p["nbs"]), vals[act], dt)
+    if p.get("mcnt"):
+        got[p["mpart"]], got[p["mcnt"]] = guarded(st[p["mpart"]]), guarded(st[p["mcnt"]])
+    return got
+
+
+def emu_pack(cmd, p, state, dt):
+    st = R.typed(p, state, cmd)
+    w = st[p["w"]].reshape(p["N"], p["K"])
+    if cmd == "packw":
+        return {p["wp"]: guarded(R.pack_weight(w))}
+    hi, lo = R.pair_bits(w, dt)
+    return {p["hi"]: guarded(R.pack_weight(hi)), p["lo"]: guarded(R.pack_weight(lo))}
+
+
+def run_emulated(dt, group, defect=None):
+    bufs, launches = group
+    state, prev, notes = dict(bufs), None, {}
+    for cmd, ident, p, outs in launches:
+        got = (emu_gemm if cmd in ("cgemm", "dgemm") else emu_actprep if cmd == "actprep" else emu_attn if cmd == "attn" else
+               (lambda p_, s_, d_, x_: emu_pack(cmd, p_, s_, d_)))(p, state, dt, defect)
+        assert set(got) == set(outs), (ident, sorted(got), outs)
+        for k_, v_ in R.verify(cmd, ident, p, state, got, dt, prev).items():
+            notes[k_] = max(notes.get(k_, 0.0), v_)
+        prev = got
+        for name in outs:
+            state[name] = R.strip(ident, got[name])
+    return notes
+
+
+# ------------------------------------------------------------------------------------------ the groups (shapes of the GPU test)
+OFFS8 = (0, 7, 63, 64, 65, 127, 128, 447)
+GROUPS = {
+    "cgemm_ln_store": lambda dt: R.linear_group(dt, 1, "cgemm", K=384, N=40, batch=17, nbs=3, epi=R.GEPI_STORE, ln=True),
+    "cgemm_ln_store_1280": lambda dt: R.linear_group(dt, 2, "cgemm", K=1280, N=72, batch=15, nbs=2, epi=R.GEPI_STORE, rt=2, ln=True),
+    "cgemm_pair_resid_128": lambda dt: R.linear_group(dt, 3, "cgemm", K=128, N=48, batch=16, nbs=2, epi=R.GEPI_RESID),
+    "cgemm_pair_resid_768": lambda dt: R.linear_group(dt, 4, "cgemm", K=768, N=40, batch=17, nbs=3, epi=R.GEPI_RESID),
+    "cgemm_pair_resid_3072": lambda dt: R.linear_group(dt, 5, "cgemm", K=3072, N=24, batch=4, nbs=1, epi=R.GEPI_RESID, family="realistic"),
+    "cgemm_ln_gelu": lambda dt: R.linear_group(dt, 6, "cgemm", K=384, N=100, batch=40, nbs=4, epi=R.GEPI_GELU, rt=2, ln=True),
+    "cgemm_qkv": lambda dt: R.linear_group(dt, 7, "cgemm", K=384, N=1152, batch=8, nbs=1, epi=R.GEPI_QKV_CACHE, ln=True, d_model=384, offs=OFFS8),
+    "dgemm_gelu": lambda dt: R.linear_group(dt, 8, "dgemm", K=1280, N=100, batch=17, nbs=3, epi=R.GEPI_GELU, rt=4),
+    "dgemm_qkv": lambda dt: R.linear_group(dt, 9, "dgemm", K=1280, N=1152, batch=8, nbs=2, epi=R.GEPI_QKV_CACHE, d_model=384, offs=OFFS8[::-1]),
+    "partial_768": lambda dt: R.partial_group(dt, 10, K=768, d=384, batch=17, nbs=2),
+    "partial_1280": lambda dt: R.partial_group(dt, 11, K=1280, d=384, batch=3, nbs=1),
+    "logits_rt4": lambda dt: R.logits_group(dt, 12, K=1280, N=300, batch=17, nbs=2, rt=4),
+    "logits_rt0_769": lambda dt: R.logits_group(dt, 13, K=128, N=769 * 16 - 5, batch=16, nbs=1, rt=0),
+    "logits_rt0_768": lambda dt: R.logits_group(dt, 14, K=128, N=768 * 16 - 5, batch=17, nbs=2, rt=0),
+    "logits_skip": lambda dt: R.logits_group(dt, 15, K=128, N=83, batch=16, nbs=1, rt=0, offs=np.arange(16) % 3, skip=3),
+    "actprep": lambda dt: (lambda b: (b, [R.actprep_launch(np.random.default_rng(16), b, K=1280, batch=17, nbs=3, n_part=3, do_ln=True, part_batch=20)]))({}),
+    "actprep_plain": lambda dt: (lambda b: (b, [R.actprep_launch(np.random.default_rng(17), b, K=384, batch=1, nbs=1, n_part=0, do_ln=False, part_batch=0)]))({}),
+    "fold_384": lambda dt: R.fold_group(dt, 18, d=384, batch=4, nbs=1, n_split=6, n_keys=200),
+    "fold_384_benign": lambda dt: R.fold_group(dt, 19, d=384, batch=4, nbs=1, n_split=1, n_keys=65, family="benign"),
+    "attn_self_pair": lambda dt: R.attn_group(dt, 20, cap=7, offs=(0, 62, 63, 64, 127, 128, 255, 256, 447), batch=9),
+    "attn_self_part2": lambda dt: R.attn_group(dt, 21, cap=7, offs=(0, 63, 64, 255), batch=4, n_split=2, out="part"),
+    "attn_cross_65_s3": lambda dt: R.attn_group(dt, 22, cap=24, n_keys=65, n_split=3, relaunch=True),
+    "attn_cross_1500_s6": lambda dt: R.attn_group(dt, 23, cap=24, n_keys=1500, n_split=6, relaunch=True),
+    "attn_fused_384": lambda dt: R.attn_group(dt, 24, H=6, batch=5, cap=24, n_keys=64, mode="fused"),
+    "attn_cross_1476_s4": lambda dt: R.attn_group(dt, 29, cap=24, n_keys=1476, n_split=4),
+    "cgemm_pair_gelu_128": lambda dt: R.linear_group(dt, 30, "cgemm", K=128, N=100, batch=17, nbs=2, epi=R.GEPI_GELU),
+    "attn_fused_640": lambda dt: R.attn_group(dt, 26, H=10, cap=24, n_keys=65, mode="fused", n_split=2),
+    "attn_done": lambda dt: R.attn_group(dt, 27, cap=24, n_keys=65, n_split=2, done=(0, 1, 0), done_late=1),
+    "pack": lambda dt: (lambda gs: (dict(gs[0][0], **{"w2": gs[1][0]["w"], "hi": gs[1][0]["hi"], "lo": gs[1][0]["lo"]}),
+                                    [gs[0][1][0], R.launch("packw_split", "packw_split", N=37, K=96, w="w2", hi="hi", lo="lo")]))(R.pack_groups(dt, 28, 37, 96)),
+}
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("name", sorted(GROUPS))
+def test_float32_emulation_stays_within_the_bounds(name, dt):
+    notes = run_emulated(dt, GROUPS[name](dt))
+    for what, w in sorted(notes.items()):
+        print(f"{dt} {name} {what}: emulation error / bound {w:.3f}")
+        assert w <= 1.0
+
+
+# defect -> the groups it must fail on (each at a shape of the GPU test)
+DEFECTS = {
+    "drop_lo": {"bf16": ("cgemm_pair_resid_128", "cgemm_pair_resid_768", "dgemm_gelu", "partial_768", "logits_rt4"),  # 1
+                "f16": ("cgemm_pair_resid_128", "cgemm_pair_gelu_128")},
+    "drop_mlo": {"bf16": ("fold_384", "fold_384_benign"), "f16": ()},                                             # 2 (half: see above)
+    "resid_store": ("cgemm_pair_resid_128", "cgemm_pair_resid_3072"),                                            # 3
+    "gelu_tanh": ("cgemm_pair_gelu_128",),                                                                # 4
+    "cache_clip0": ("cgemm_qkv", "dgemm_qkv"),                                                                   # 5
+    "cache_plus1": ("cgemm_qkv", "dgemm_qkv"),                                                                   # 6
+    "cache_swap": ("cgemm_qkv", "dgemm_qkv"),                                                                    # 7
+    "mask_gt": ("attn_self_pair", "attn_cross_65_s3", "attn_self_part2"),                                        # 8
+    "scale": ("attn_self_pair", "attn_cross_1500_s6"),                                                           # 9
+    "no_rescale": ("attn_cross_1500_s6", "attn_cross_1476_s4"),                                                    # 10
+    "empty_weight1": ("attn_self_part2", "attn_cross_65_s3"),                                                    # 11
+    "fold_no_between": ("fold_384", "fold_384_benign"),                                                          # 12
+    "no_eps": ("cgemm_ln_store", "attn_fused_384"),                                                              # 13
+    "argmax_last": ("logits_rt4", "logits_rt0_769"),                                                             # 14
+    "skip_block": ("logits_rt0_768",),                                                                           # 15
+    "slice_left_out": ("actprep", "partial_768"),                                                                # 16
+}
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("defect", sorted(DEFECTS))
+def test_seeded_defect_fails(defect, dt):
+    names = DEFECTS[defect]
+    for name in names[dt] if isinstance(names, dict) else names:
+        try:
+            run_emulated(dt, GROUPS[name](dt), defect)
+        except AssertionError as e:
+            print(f"{dt} {defect}: caught at {name}: {str(e)[:150]}")
+            continue
+        pytest.fail(f"{dt}: defect {defect} passes at {name}")
+
+
+def test_index_maps():
+    """frag_index / wfrag_index are bijections onto whole tiles; the K cache map covers a head's blocks exactly once."""
+    i = R.frag_index(np.arange(40)[:, None], np.arange(96)[None, :], 3)
+    assert np.unique(i).size == i.size and i.max() < 3 * 3 * 512
+    j = R.wfrag_index(np.arange(48)[:, None], np.arange(96)[None, :], 3)
+    assert sorted(j.ravel()) == list(range(48 * 96))
+    k = R.kcache_index(np.arange(448)[:, None], np.arange(64)[None, :])
+    assert sorted(k.ravel()) == list(range(448 * 64))
+    assert R.kcache_index(65, 9) == 4096 + 512 + 8 + 1 and R.frag_index(17, 41, 3) == ((1 * 3 + 1) * 64 + 1 * 16 + 1) * 8 + 1
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_pair_split_carries_16_or_22_bits(dt):
+    rng = np.random.default_rng(0)
+    x = (rng.standard_normal(200000) * np.exp(rng.uniform(-9, 9, 200000))).astype(F)
+    hi, lo = R.pair_split(x, dt)
+    err = np.abs(x.astype(np.float64) - (hi.astype(np.float64) + lo))
+    assert (err <= R.pair_err(x.astype(np.float64), dt)).all()
+    bits = 16 if dt == "bf16" else 22
+    assert (err[np.abs(x) > 2.0 ** -2] <= 2.0 ** -bits * np.abs(x[np.abs(x) > 2.0 ** -2])).all()
+    assert (err / np.abs(x)).max() > 2.0 ** -(bits + 3)  # and not many more: the bound is the format's
+
+
+def test_ksplit_rule_and_resident_shapes():
+    assert [R.ksplit_for(k) for k in (384, 512, 768, 1280, 5120)] == [1, 2, 3, 4, 4]
+    assert R.logits_resident_ok(1280, 48) and not R.logits_resident_ok(1280, 64) and R.logits_resident_ok(768, 64) and not R.logits_resident_ok(1536, 16)
