@@ -143,7 +143,7 @@ int main(int argc, char** argv) {
         const long N = p.N, K = p.K, B = p.batch, KS = K / 32, n_rb = (N + 15) / 16, nbs = p.nbs, fr0 = p.fold_row0, d = p.d_model;
         if (N < 1 || K < 128 || K % 128 || B < 1 || nbs < (B + 15) / 16 || (p.rt != 1 && p.rt != 2) || fr0 < 0 || fr0 >= N) die("bad cgemm shape");
         const bool ln = has(kv, "ln_w");
-        p.W = (const h16*)need(kv, "W", 2, n_rb * KS * 512);
+        p.W = (const h16*)need(kv, "W", 2, layout::wfrag_tile_offset(n_rb, 0, KS));
         p.bias = (const float*)ptr(kv, "bias", 4, N);
         if (ln) {
           if (K > 1280) die("LayerNorm prologue: K > 1280");
@@ -151,8 +151,8 @@ int main(int argc, char** argv) {
           p.ln_w = (const float*)need(kv, "ln_w", 4, K);
           p.ln_b = (const float*)need(kv, "ln_b", 4, K);
         } else {
-          p.a_hi = (const h16*)need(kv, "a_hi", 2, KS * nbs * 512);
-          p.a_lo = (const h16*)need(kv, "a_lo", 2, KS * nbs * 512);
+          p.a_hi = (const h16*)need(kv, "a_hi", 2, layout::pair_elems(KS, nbs));
+          p.a_lo = (const h16*)need(kv, "a_lo", 2, layout::pair_elems(KS, nbs));
         }
         if (fr0 > 0) {  // what launch_decode_cgemm aborts on, and the row blocks W_lo is indexed with
           if (fr0 % (16 * p.rt) || (N - fr0) % (16 * p.rt)) die("query fold: fold_row0 and the fold rows are whole row tiles");
@@ -160,7 +160,7 @@ int main(int argc, char** argv) {
           if (ln) p.ln_w2 = (const float*)need(kv, "ln_w2", 4, K);
           else {
             if (K > 1024) die("query fold: pair input with K > 1024");
-            p.W_lo = (const h16*)need(kv, "W_lo", 2, (N - fr0) / 16 * KS * 512);
+            p.W_lo = (const h16*)need(kv, "W_lo", 2, layout::wfrag_tile_offset((N - fr0) / 16, 0, KS));
           }
         }
         const long nx = fr0 > 0 ? fr0 : N;
@@ -179,8 +179,8 @@ int main(int argc, char** argv) {
             break;
           case GEPI_GELU:
             if (fr0) die("GELU has no fold rows");
-            p.out_hi = (h16*)need(kv, "out_hi", 2, (N + 31) / 32 * nbs * 512);
-            p.out_lo = (h16*)need(kv, "out_lo", 2, (N + 31) / 32 * nbs * 512);
+            p.out_hi = (h16*)need(kv, "out_hi", 2, layout::pair_elems((N + 31) / 32, nbs));
+            p.out_lo = (h16*)need(kv, "out_lo", 2, layout::pair_elems((N + 31) / 32, nbs));
             break;
           case GEPI_QKV_CACHE:
             if (!(N == 3 * d && fr0 == 0) && !(N == 4 * d && fr0 == 3 * d && ln)) die("QKV_CACHE: N is 3 d_model, or 4 d_model with fold rows");
@@ -201,16 +201,16 @@ int main(int argc, char** argv) {
         const long N = p.N, K = p.K, B = p.batch, KS = K / 32, n_rb = (N + 15) / 16, nbs = p.nbs, d = p.d_model;
         if (N < 1 || K < 128 || K % 128 || B < 1 || B > 64 || nbs < (B + 15) / 16 || (p.rt != 0 && p.rt != 1 && p.rt != 2 && p.rt != 4)) die("bad dgemm shape");
         if (p.rt == 0 && (p.epilogue != GEPI_LOGITS || !decode_logits_resident_ok(p.K, p.batch))) die("rt 0: the resident vocabulary projection does not take this launch");
-        p.W = (const h16*)need(kv, "W", 2, n_rb * KS * 512);
+        p.W = (const h16*)need(kv, "W", 2, layout::wfrag_tile_offset(n_rb, 0, KS));
         p.bias = (const float*)ptr(kv, "bias", 4, N);
-        p.a_hi = (const h16*)need(kv, "a_hi", 2, KS * nbs * 512);
-        p.a_lo = (const h16*)need(kv, "a_lo", 2, KS * nbs * 512);
+        p.a_hi = (const h16*)need(kv, "a_hi", 2, layout::pair_elems(KS, nbs));
+        p.a_lo = (const h16*)need(kv, "a_lo", 2, layout::pair_elems(KS, nbs));
         gx = decode_gemm_grid(p.N, p.rt);
         switch (p.epilogue) {
           case GEPI_STORE: case GEPI_RESID: p.out = (float*)need(kv, "out", 4, B * N); break;
           case GEPI_GELU:
-            p.out_hi = (h16*)need(kv, "out_hi", 2, (N + 31) / 32 * nbs * 512);
-            p.out_lo = (h16*)need(kv, "out_lo", 2, (N + 31) / 32 * nbs * 512);
+            p.out_hi = (h16*)need(kv, "out_hi", 2, layout::pair_elems((N + 31) / 32, nbs));
+            p.out_lo = (h16*)need(kv, "out_lo", 2, layout::pair_elems((N + 31) / 32, nbs));
             break;
           case GEPI_QKV_CACHE:
             if (N != 3 * d) die("QKV_CACHE: N is 3 d_model");
@@ -242,8 +242,8 @@ int main(int argc, char** argv) {
         float* x = (float*)need(kv, "x", 4, B * K);
         const float* g = do_ln ? (const float*)need(kv, "g", 4, K) : nullptr;
         const float* be = do_ln ? (const float*)need(kv, "be", 4, K) : nullptr;
-        h16* hi = (h16*)need(kv, "hi", 2, K / 32 * nbs * 512);
-        h16* lo = (h16*)need(kv, "lo", 2, K / 32 * nbs * 512);
+        h16* hi = (h16*)need(kv, "hi", 2, layout::pair_elems(K / 32, nbs));
+        h16* lo = (h16*)need(kv, "lo", 2, layout::pair_elems(K / 32, nbs));
         const float* part = n_part ? (const float*)need(kv, "part", 4, ((n_part - 1) * pb + B) * K) : nullptr;
         const float* pbias = n_part ? (const float*)need(kv, "part_bias", 4, K) : nullptr;
         gx = B;
@@ -254,10 +254,10 @@ int main(int argc, char** argv) {
         p.cap_blocks = (int)num(kv, "cap_blocks"); p.n_split = (int)num(kv, "n_split", 1); p.kv_batch_stride = num(kv, "kv_batch_stride");
         p.nbs = (int)num(kv, "nbs"); p.done_late = (int)num(kv, "done_late");
         const long B = p.batch, H = p.n_head, d = p.d_model, cap = p.cap_blocks, ns = p.n_split;
-        if (B < 1 || H < 1 || d != H * 64 || cap < 1 || ns < 1 || ns > cap || p.kv_batch_stride < H * cap * 4096 ||
+        if (B < 1 || H < 1 || d != H * 64 || cap < 1 || ns < 1 || ns > cap || p.kv_batch_stride < H * layout::kv_head_elems(cap * layout::kKvBlockKeys) ||
             !(p.n_keys == -1 || (p.n_keys >= 1 && p.n_keys <= cap * 64))) die("bad attention shape");
-        p.k = (const h16*)need(kv, "k", 2, (B - 1) * p.kv_batch_stride + H * cap * 4096);
-        p.v = (const h16*)need(kv, "v", 2, (B - 1) * p.kv_batch_stride + H * cap * 4096);
+        p.k = (const h16*)need(kv, "k", 2, (B - 1) * p.kv_batch_stride + H * layout::kv_head_elems(cap * layout::kKvBlockKeys));
+        p.v = (const h16*)need(kv, "v", 2, (B - 1) * p.kv_batch_stride + H * layout::kv_head_elems(cap * layout::kKvBlockKeys));
         p.done = (const int*)need(kv, "done", 4, B);
         if (p.n_keys < 0) {
           p.off = (const int*)need(kv, "off", 4, B);
@@ -268,15 +268,15 @@ int main(int argc, char** argv) {
         if (pair == has(kv, "part")) die("attention writes the pair or the partials");
         if (pair) {
           if (p.nbs < (B + 15) / 16) die("nbs below the clip blocks");
-          p.out_hi = (h16*)need(kv, "out_hi", 2, d / 32 * p.nbs * 512);
-          p.out_lo = (h16*)need(kv, "out_lo", 2, d / 32 * p.nbs * 512);
+          p.out_hi = (h16*)need(kv, "out_hi", 2, layout::pair_elems(d / 32, p.nbs));
+          p.out_lo = (h16*)need(kv, "out_lo", 2, layout::pair_elems(d / 32, p.nbs));
           if (ns > 1) {
             if (ns > 6) die("the fold of a launch takes at most 6 splits");
-            p.mpart = (float*)need(kv, "mpart", 4, B * H * ns * 66);
+            p.mpart = (float*)need(kv, "mpart", 4, layout::part_elems(B, H, ns));
             p.mcnt = (unsigned*)need(kv, "mcnt", 4, B * H);
           }
         } else {
-          p.part = (float*)need(kv, "part", 4, B * H * ns * 66);
+          p.part = (float*)need(kv, "part", 4, layout::part_elems(B, H, ns));
         }
         if (has(kv, "tq")) {  // folded query: what launch_decode_attention aborts on
           if (d > 1024 || (ns != 1 && !pair)) die("folded query: unsupported launch");
@@ -299,7 +299,7 @@ int main(int argc, char** argv) {
       } else {
         const long N = num(kv, "N"), K = num(kv, "K");
         if (N < 1 || K < 32 || K % 32) die("bad pack shape");
-        const long packed = (N + 15) / 16 * (K / 32) * 512;
+        const long packed = layout::wfrag_elems(N, K);
         if (cmd == "packw") {
           launch_pack_weight_frag((const h16*)need(kv, "w", 2, N * K), (h16*)need(kv, "wp", 2, packed), (int)N, (int)K, nullptr);
         } else {

@@ -16,11 +16,15 @@ half. So defect 1 is visible in bfloat16 at every K here and in half at K = 128 
 768) in bfloat16 only — in half M_hi alone carries 11 bits and what M_lo adds lies below what any fp32 summation order may lose.
 Defect 4 (tanh GELU, up to 5e-4 from erf) needs the pair input at K = 128 for the same reason. Defect 1 is asserted on stored-pair inputs; behind the LayerNorm prologue the any-order bound of the
 statistics (K u on the mean, (3 K + 4) kappa u on the variance) is as large as the lo half in bfloat16 at these K."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 import torch
 
 import decode_kernel_reference as R
+import encoder_kernel_reference as E
 from encoder_kernel_reference import GUARD, from_bits, round16, sentinel, to_bits
 
 F = np.float32
@@ -406,8 +410,19 @@ def test_seeded_defect_fails(defect, dt):
         pytest.fail(f"{dt}: defect {defect} passes at {name}")
 
 
-def test_index_maps():
-    """frag_index / wfrag_index are bijections onto whole tiles; the K cache map covers a head's blocks exactly once."""
+def layout_tables(tmp_path):
+    """The engine's own index functions (csrc/decode_layout.hpp), printed by tests/cpp/decode_layout_tables.cpp built with g++."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "decode_layout_tables"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(root, "whisper.axera_amd", "csrc"), "-o", str(exe),
+                    os.path.join(root, "tests", "cpp", "decode_layout_tables.cpp")], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    return {ln.split()[0]: np.array(ln.split()[1:], dtype=np.int64) for ln in out.splitlines()}
+
+
+def test_index_maps(tmp_path):
+    """frag_index / wfrag_index are bijections onto whole tiles; the K cache map covers a head's blocks exactly once; and the ONE
+    definition the kernels and the engine index through (csrc/decode_layout.hpp) equals these maps element for element."""
     i = R.frag_index(np.arange(40)[:, None], np.arange(96)[None, :], 3)
     assert np.unique(i).size == i.size and i.max() < 3 * 3 * 512
     j = R.wfrag_index(np.arange(48)[:, None], np.arange(96)[None, :], 3)
@@ -415,6 +430,41 @@ def test_index_maps():
     k = R.kcache_index(np.arange(448)[:, None], np.arange(64)[None, :])
     assert sorted(k.ravel()) == list(range(448 * 64))
     assert R.kcache_index(65, 9) == 4096 + 512 + 8 + 1 and R.frag_index(17, 41, 3) == ((1 * 3 + 1) * 64 + 1 * 16 + 1) * 8 + 1
+
+    T = layout_tables(tmp_path)
+    keys, dims = np.arange(448)[:, None], np.arange(64)[None, :]
+    assert np.array_equal(T["frag"].reshape(40, 96), i)
+    assert np.array_equal(T["wfrag"].reshape(40, 96), j[:40])
+    assert np.array_equal(T["k"].reshape(448, 64), k)
+    assert np.array_equal(T["v"].reshape(448, 64), R.vcache_index(keys, dims))
+    # the packing kernels' direction is the inverse of wfrag_index; rows 40..47 are the padding of the last row block
+    src = T["wfrag_source"].reshape(48 * 96, 2)
+    assert np.array_equal(R.wfrag_index(src[:, 0], src[:, 1], 3), np.arange(48 * 96))
+    # the readers' pieces: (block, 8-dim chunk, key) of K is where kcache_index puts dimension 8 * chunk of key 64 * block + key
+    blk, ch, row = np.arange(7)[:, None, None], np.arange(8)[None, :, None], np.arange(64)[None, None, :]
+    assert np.array_equal(T["kv_chunk"].reshape(7, 8, 64), R.kcache_index(blk * 64 + row, ch * 8))
+    assert np.array_equal(T["v_row"], R.vcache_index(np.arange(448), 0))
+    # the persistent launches' LDS V, [key / 64][(key % 64) / 8][dim][8 keys], stated here: a bijection per block whose 16-byte
+    # pieces the same (block, chunk, row) walk reads with chunk = 8-key group, row = dim
+    vt = T["vt"].reshape(448, 64)
+    assert np.array_equal(vt, (keys >> 6) * 4096 + ((keys >> 3) & 7) * 512 + dims * 8 + (keys & 7))
+    assert sorted(vt.ravel()) == list(range(448 * 64))
+    assert np.array_equal(T["sizes"], [3 * 3 * 512, 48 * 96, 3 * 512, 2 * 512, 512, 448 * 64, (2 * 3 + 1) * 512])
+    assert np.array_equal(T["part"], [66, 0, 1, 2, 6, ((3 * 12 + 5) * 6 + 2) * 66, 4 * 12 * 6 * 66])
+
+    # the encoder reference's cross-K / cross-V formulas (EPI_CROSS_KV of gemm_expect): a launch whose value at (key t, column n) is
+    # 128 t + n exactly, two heads, so the position of every value in the expected buffers IS the reference's map
+    d, tp = 128, 448
+    a = np.stack([np.arange(tp), np.ones(tp)], axis=1)
+    w = np.stack([np.full(2 * d, d), np.arange(2 * d) % d], axis=1)
+    bufs = dict(A=to_bits(a, "f16"), W=to_bits(w, "f16"), C=np.zeros(2 * tp * 64, np.uint16), C2=np.zeros(2 * tp * 64, np.uint16))
+    exp = E.gemm_expect(dict(epi=E.EPI_CROSS_KV, M=tp, N=2 * d, K=2, batch=1, d=d, A="A", W="W", a_bs=0, lda=2, n_layer=1, t_pad=tp,
+                             nbt=1, C="C", C2="C2"), bufs, "f16")
+    want = (128 * keys + dims).astype(np.float64)
+    for head in range(2):
+        assert np.array_equal(exp["C"].ref[head * T["sizes"][5] + T["k"].reshape(448, 64)], want + 64 * head)
+        assert np.array_equal(exp["C2"].ref[head * T["sizes"][5] + T["v"].reshape(448, 64)], want + 64 * head)
+    assert exp["C"].written.all() and exp["C2"].written.all()
 
 
 @pytest.mark.parametrize("dt", DTYPES)

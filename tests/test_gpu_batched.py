@@ -155,22 +155,33 @@ def test_model_widths_batched_and_single_vs_oracle(built_lib, oracle_mod, tmp_pa
         e.close()
 
 
-@pytest.mark.parametrize("B", [3, 4])
-def test_cross_attention_splits_and_decode_families_agree(built_lib, micro_case, monkeypatch, B):
+@pytest.mark.parametrize("B,n_forced", [(3, 8), (4, 8), (4, 70)], ids=["3", "4", "4-past-key-block-64"])
+def test_cross_attention_splits_and_decode_families_agree(built_lib, micro_case, monkeypatch, B, n_forced):
     """At few clips the key blocks of a (clip, head) are divided among several workgroups that meet through a ticket
     (decoder.hip); the result must not depend on the split count (fold in split order), and the GEMV family (still the
-    path of one and two clips without the persistent launch) must agree with the clip-block GEMMs on the same clips."""
+    path of one and two clips without the persistent launch) must agree with the clip-block GEMMs on the same clips.
+
+    70 forced ids (decode offsets 0..72): every family appends K / V rows on both sides of the self cache's first 64-key block
+    boundary — the four-clip GEMV kernel, the clip-block GEMM and, in that case only, the split-K sequence
+    (AX_WHISPER_BATCHED_LN=0: decode_gemm_kernel + act_prep) — and attends over two blocks. The bounds are those of the 8-id cases:
+    the families differ in fp32 summation order and in which side of a rounding boundary a cached 16-bit K / V value falls, per row;
+    neither grows with the number of cached rows (softmax weights sum to 1), while a row appended at a wrong index is an error of
+    the size of the logits themselves."""
     mels = np.stack(_mels(B))
-    forced = np.tile(np.array([[50258 + (i * 7) % 100 for i in range(8)]], dtype=np.int32), (B, 1))
+    forced = np.tile(np.array([[50258 + (i * 7) % 100 for i in range(n_forced)]], dtype=np.int32), (B, 1))
     out = {}
-    for name, env in (("default", {}), ("one workgroup", {"AX_WHISPER_CROSS_SPLIT": "1"}), ("three", {"AX_WHISPER_CROSS_SPLIT": "3"}),
-                      ("gemv family", {"AX_WHISPER_GEMV_MAX": "4"})):
-        for k in ("AX_WHISPER_CROSS_SPLIT", "AX_WHISPER_GEMV_MAX"):
+    cases = [("default", {}), ("one workgroup", {"AX_WHISPER_CROSS_SPLIT": "1"}), ("three", {"AX_WHISPER_CROSS_SPLIT": "3"}),
+             ("gemv family", {"AX_WHISPER_GEMV_MAX": "4"})]
+    if n_forced > 64:
+        cases.append(("split-K sequence", {"AX_WHISPER_BATCHED_LN": "0"}))
+    for name, env in cases:
+        for k in ("AX_WHISPER_CROSS_SPLIT", "AX_WHISPER_GEMV_MAX", "AX_WHISPER_BATCHED_LN"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         e = built_lib.Whisper("micro", micro_case.root, "zh", device=0, max_batch=B)
         try:
+            assert e.L.AX_WHISPER_GetConfigInt(e.h, b"batched_ln") == (0 if name == "split-K sequence" else 1)
             e.encode_mel(mels)
             out[name] = e.decode_forced(B, forced)[0]
         finally:
@@ -182,6 +193,10 @@ def test_cross_attention_splits_and_decode_families_agree(built_lib, micro_case,
     d = float(np.abs(out["gemv family"] - out["default"]).max())
     print(f"B={B} GEMV family vs clip-block GEMMs: {d:.3e}")
     assert d < 5e-3
+    if "split-K sequence" in out:
+        d = float(np.abs(out["split-K sequence"] - out["default"]).max())
+        print(f"B={B} split-K sequence vs clip-block GEMMs: {d:.3e}")
+        assert d < 2e-3  # the bound of test_gpu_fullsize.test_small_batched_decode_sequences_agree (both sides carry (hi, lo) pairs)
 
 
 @pytest.mark.parametrize("B", [3, 6])

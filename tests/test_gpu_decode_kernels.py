@@ -47,7 +47,7 @@ def _driver_exe(dt):
     exe = os.path.join(BUILD, "decode_kernels_driver." + dt)
     src = os.path.join(ROOT, "tests", "cpp", "decode_kernels_driver.cpp")
     objs = [os.path.join(BUILD, f"{k}.{dt}.o") for k in ("decode_gemm", "decoder")]
-    srcs = [src] + [os.path.join(PKG, "csrc", f) for f in ("decode_gemm.hip", "decoder.hip", "common.hpp")]
+    srcs = [src] + [os.path.join(PKG, "csrc", f) for f in ("decode_gemm.hip", "decoder.hip", "common.hpp", "decode_layout.hpp")]
     newest = max(os.path.getmtime(f) for f in srcs + [o for o in objs if os.path.exists(o)])
     if os.path.exists(exe) and os.path.getmtime(exe) >= newest:
         return exe

@@ -58,7 +58,7 @@ def _driver_exe(dt):
     exe = os.path.join(BUILD, "encoder_kernels_driver." + dt)
     src = os.path.join(ROOT, "tests", "cpp", "encoder_kernels_driver.cpp")
     objs = [os.path.join(BUILD, f"{k}.{dt}.o") for k in ("gemm", "encoder_attn")]
-    srcs = [src] + [os.path.join(PKG, "csrc", f) for f in ("gemm.hip", "encoder_attn.hip", "common.hpp")]
+    srcs = [src] + [os.path.join(PKG, "csrc", f) for f in ("gemm.hip", "encoder_attn.hip", "common.hpp", "decode_layout.hpp")]
     newest = max(os.path.getmtime(f) for f in srcs + [o for o in objs if os.path.exists(o)])
     if os.path.exists(exe) and os.path.getmtime(exe) >= newest:
         return exe

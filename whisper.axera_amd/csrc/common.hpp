@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "decode_layout.hpp"
+
 // ------------------------------------------------------------------ the 16-bit storage / MFMA operand type
 // Every kernel file and the engine are compiled TWICE (Makefile): -DAXW_F16=0 -> bfloat16 (the default; what
 // BASELINE configs[1], [2], [4] name), -DAXW_F16=1 -> IEEE half (configs[3]: "Whisper-turbo fp16"; also the dtype
@@ -41,8 +43,6 @@ constexpr int kNFFT = 400;
 constexpr int kHop = 160;
 constexpr int kBins = 201;
 constexpr int kFramesOut = 3000;   // Whisper.cpp:172 resize(3000)
-constexpr int kHeadDim = 64;       // all Whisper sizes
-constexpr int kKeyBlk = 64;        // keys per block of the decode K layout
 
 // ------------------------------------------------------------------ device helpers
 #ifdef __HIPCC__
@@ -82,11 +82,16 @@ __device__ __forceinline__ void h16split2(float x0, float x1, unsigned& hi, unsi
 // v_permlane{16,32}_swap across rows — ~8 short vector instructions; the __shfl_xor form compiles to six dependent
 // ds_bpermute round trips (~700 cycles of latency per call, which bounded the K/V block loop of decode_attention_kernel)
 #define AXW_DPP_F(CTRL, X) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(X), CTRL, 0xf, 0xf, true))
-__device__ __forceinline__ float wave_sum(float v) {
+// sum over the 16 lanes of a DPP row (equal lane >> 4), in every lane of the row: the four butterfly steps
+__device__ __forceinline__ float row16_sum(float v) {
   v += AXW_DPP_F(0xB1, v);   // quad_perm [1,0,3,2]
   v += AXW_DPP_F(0x4E, v);   // quad_perm [2,3,0,1]
   v += AXW_DPP_F(0x141, v);  // row_half_mirror
   v += AXW_DPP_F(0x140, v);  // row_mirror
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+  v = row16_sum(v);
   {
     auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
@@ -113,29 +118,53 @@ __device__ __forceinline__ float wave_max(float v) {
   }
   return v;
 }
-// (value, index) maximum over the wave in every lane, lower index on equal values; DPP butterflies inside a 16-lane row,
-// v_permlane{16,32}_swap across rows (the __shfl_xor form: twelve dependent ds_bpermute round trips)
-__device__ __forceinline__ void wave_argmax(float& v, int& idx) {
-  auto take = [&](float ov, int oi) { if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; } };
+// THE argmax tie rule, "first maximum wins" (std::max_element, Whisper.cpp:42-45): candidate (ov, oi) replaces (v, i) when it is
+// greater, or equal with the lower index. A NaN candidate never wins. Every merge of argmax candidates goes through here.
+__device__ __forceinline__ void argmax_take(float& v, int& i, float ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+// (value, index) maximum over the 16 lanes of a DPP row in every lane of the row: the four butterfly steps
+__device__ __forceinline__ void row16_argmax(float& v, int& idx) {
 #define AXW_DPP_I(CTRL, X) __builtin_amdgcn_update_dpp(0, X, CTRL, 0xf, 0xf, true)
-#define AXW_ARGMAX_STEP(CTRL) { const float ov = __int_as_float(AXW_DPP_I(CTRL, __float_as_int(v))); const int oi = AXW_DPP_I(CTRL, idx); take(ov, oi); }
+#define AXW_ARGMAX_STEP(CTRL) { const float ov = __int_as_float(AXW_DPP_I(CTRL, __float_as_int(v))); const int oi = AXW_DPP_I(CTRL, idx); argmax_take(v, idx, ov, oi); }
   AXW_ARGMAX_STEP(0xB1)   // quad_perm [1,0,3,2]
   AXW_ARGMAX_STEP(0x4E)   // quad_perm [2,3,0,1]
   AXW_ARGMAX_STEP(0x141)  // row_half_mirror
   AXW_ARGMAX_STEP(0x140)  // row_mirror
 #undef AXW_ARGMAX_STEP
 #undef AXW_DPP_I
+}
+// (value, index) maximum over the wave in every lane, lower index on equal values; DPP butterflies inside a 16-lane row,
+// v_permlane{16,32}_swap across rows (the __shfl_xor form: twelve dependent ds_bpermute round trips)
+__device__ __forceinline__ void wave_argmax(float& v, int& idx) {
+  row16_argmax(v, idx);
   {
     auto rv = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     auto ri = __builtin_amdgcn_permlane16_swap((unsigned)idx, (unsigned)idx, false, false);
     v = __uint_as_float(rv[0]); idx = (int)ri[0];
-    take(__uint_as_float(rv[1]), (int)ri[1]);
+    argmax_take(v, idx, __uint_as_float(rv[1]), (int)ri[1]);
   }
   {
     auto rv = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     auto ri = __builtin_amdgcn_permlane32_swap((unsigned)idx, (unsigned)idx, false, false);
     v = __uint_as_float(rv[0]); idx = (int)ri[0];
-    take(__uint_as_float(rv[1]), (int)ri[1]);
+    argmax_take(v, idx, __uint_as_float(rv[1]), (int)ri[1]);
+  }
+}
+// GEPI_QKV_CACHE, one output y of row n for the clip with index b among the launch's per-clip pointers: the q row, or the
+// self-attention K (blocked) / V (row-major) cache append at row `key` = the clip's own offset (export_onnx.py:245-247,
+// Whisper.cpp:328-342). P: GemvParams, DecGemmParams or DecCGemmParams (rows n < 3 d_model; `key` is not used for n < d_model).
+template <class P>
+__device__ __forceinline__ void store_qkv_cache(const P& p, int b, int n, float y, int key) {
+  const int d = p.d_model;
+  if (n < d) {
+    p.out[(long)b * d + n] = y;
+  } else {
+    const int c = (n < 2 * d) ? n - d : n - 2 * d;
+    const int head = c >> 6, dd = c & 63;
+    const long base = (long)b * p.kv_batch_stride + head * layout::kv_head_elems(p.n_ctx_pad);
+    if (n < 2 * d) p.k_cache[base + layout::k_index(key, dd)] = (h16)y;
+    else p.v_cache[base + layout::v_index(key, dd)] = (h16)y;
   }
 }
 
@@ -315,7 +344,7 @@ struct GemvParams {
   int prologue;
   const float* in;            // PRO_PLAIN: [B][K]; PRO_LAYERNORM: x [B][K]
   const float* ln_w; const float* ln_b;
-  const float* part; int n_split; int n_head;   // PRO_ATTN_COMBINE: partials [B][H][n_split][66]
+  const float* part; int n_split; int n_head;   // PRO_ATTN_COMBINE: partials [B][H][n_split] of layout::kPartStride floats
   // epilogue
   int epilogue;
   float* out;                 // [B][N]

@@ -29,19 +29,12 @@ __device__ __forceinline__ void split_bf16(float x, h16& hi, h16& lo) {
   lo = (h16)(x - (float)hi);
 }
 
-// Fragment-major layouts: both MFMA operands are stored in the order the 16x16x32 instruction consumes them, so
-// every operand load of a wave is ONE contiguous 1 KiB access (lane*16 bytes):
-//   activations  ap[((ks * nbs + c) * 64 + lane) * 8 + j] = a[clip = c*16 + (lane&15)][k = ks*32 + (lane>>4)*8 + j]
-//   weights      wp[((nb * KS + ks) * 64 + lane) * 8 + j] = W[row = nb*16 + (lane&15)][k = ks*32 + (lane>>4)*8 + j]
-__device__ __forceinline__ long frag_index(int row, int k, int row_blocks_stride /* nbs or unused */, int ks_count, bool weight) {
-  const int ks = k >> 5, q = (k >> 3) & 3, j = k & 7, blk = row >> 4, r = row & 15;
-  const long tile = weight ? ((long)blk * ks_count + ks) : ((long)ks * row_blocks_stride + blk);
-  return (tile * 64 + q * 16 + r) * 8 + j;
-}
+// Fragment-major layouts (decode_layout.hpp): both MFMA operands are stored in the order the 16x16x32 instruction consumes
+// them, so every operand load of a wave is ONE contiguous 1 KiB access (lane*16 bytes).
 __device__ __forceinline__ void store_pair_frag(float x, h16* hi, h16* lo, int clip, int k, int nbs) {
   h16 h, l;
   split_bf16(x, h, l);
-  const long i = frag_index(clip, k, nbs, 0, false);
+  const long i = layout::frag_index(clip, k, nbs);
   hi[i] = h; lo[i] = l;
 }
 
@@ -111,14 +104,10 @@ void launch_act_prep(float* x, const float* g, const float* be, h16* hi, h16* lo
 
 // row-major h16 [N][K] -> fragment-major (rows padded to a multiple of 16 with zeros)
 __global__ void pack_weight_frag_kernel(const h16* __restrict__ w, h16* __restrict__ wp, int N, int K) {
-  const int KS = K / 32;
-  const long total = (long)((N + 15) / 16) * KS * 512;
+  const long total = layout::wfrag_elems(N, K);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
-    const long tile = i >> 9;
-    const int ks = (int)(tile % KS), nb = (int)(tile / KS);
-    const int row = nb * 16 + (lane & 15), k = ks * 32 + (lane >> 4) * 8 + j;
-    wp[i] = row < N ? w[(long)row * K + k] : (h16)0.f;
+    const layout::RowK src = layout::wfrag_source(i, K / 32);
+    wp[i] = src.row < N ? w[(long)src.row * K + src.k] : (h16)0.f;
   }
 }
 void launch_pack_weight_frag(const h16* w, h16* wp, int N, int K, hipStream_t s) {
@@ -127,15 +116,11 @@ void launch_pack_weight_frag(const h16* w, h16* wp, int N, int K, hipStream_t s)
 
 // row-major fp32 [N][K] -> TWO fragment-major h16 arrays, hi = h16(m) and lo = h16(m - hi) (the query fold's product matrix M)
 __global__ void pack_weight_frag_split_kernel(const float* __restrict__ w, h16* __restrict__ hi, h16* __restrict__ lo, int N, int K) {
-  const int KS = K / 32;
-  const long total = (long)((N + 15) / 16) * KS * 512;
+  const long total = layout::wfrag_elems(N, K);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
-    const long tile = i >> 9;
-    const int ks = (int)(tile % KS), nb = (int)(tile / KS);
-    const int row = nb * 16 + (lane & 15), k = ks * 32 + (lane >> 4) * 8 + j;
+    const layout::RowK src = layout::wfrag_source(i, K / 32);
     h16 h = (h16)0.f, l = (h16)0.f;
-    if (row < N) split_bf16(w[(long)row * K + k], h, l);
+    if (src.row < N) split_bf16(w[(long)src.row * K + src.k], h, l);
     hi[i] = h;
     lo[i] = l;
   }
@@ -160,10 +145,10 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecGemmParams p) {
 
   const h16* wrow[RT];
 #pragma unroll
-  for (int t = 0; t < RT; ++t) wrow[t] = p.W + ((long)min(nb0 + t, n_rb - 1) * KS_all + ks_base) * 512 + lane * 8;
-  const h16* ahi = p.a_hi + ks_base * ((long)p.nbs * 512) + lane * 8;
-  const h16* alo = p.a_lo + ks_base * ((long)p.nbs * 512) + lane * 8;
-  const long a_step = (long)p.nbs * 512;  // elements between consecutive k-steps of the activations
+  for (int t = 0; t < RT; ++t) wrow[t] = p.W + layout::wfrag_tile_offset(min(nb0 + t, n_rb - 1), ks_base, KS_all) + layout::frag_lane_offset(lane);
+  const long a_step = layout::frag_kstep_stride(p.nbs);  // elements between consecutive k-steps of the activations
+  const h16* ahi = p.a_hi + ks_base * a_step + layout::frag_lane_offset(lane);
+  const h16* alo = p.a_lo + ks_base * a_step + layout::frag_lane_offset(lane);
 
   // The bias of this thread's outputs is requested first: every output of a thread has the same weight row
   // (512 % (16 * RT) == 0), and a load issued in the epilogue, behind the reduction barrier, would add one more
@@ -186,11 +171,11 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecGemmParams p) {
   struct Frag { h16x8 w[RT], h[NB], l[NB]; };
   auto load = [&](Frag& f, int ks) {
 #pragma unroll
-    for (int t = 0; t < RT; ++t) f.w[t] = *reinterpret_cast<const h16x8*>(wrow[t] + (long)ks * 512);
+    for (int t = 0; t < RT; ++t) f.w[t] = *reinterpret_cast<const h16x8*>(wrow[t] + (long)ks * layout::kFragTileElems);
 #pragma unroll
     for (int c = 0; c < NB; ++c) {
-      f.h[c] = *reinterpret_cast<const h16x8*>(ahi + ks * a_step + c * 512);
-      f.l[c] = *reinterpret_cast<const h16x8*>(alo + ks * a_step + c * 512);
+      f.h[c] = *reinterpret_cast<const h16x8*>(ahi + ks * a_step + c * layout::kClipBlockStride);
+      f.l[c] = *reinterpret_cast<const h16x8*>(alo + ks * a_step + c * layout::kClipBlockStride);
     }
   };
   auto mma = [&](const Frag& f) {
@@ -256,20 +241,7 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecGemmParams p) {
       case GEPI_STORE: p.out[(long)b * p.N + n] = y; break;
       case GEPI_GELU: store_pair_frag(gelu_erf(y), p.out_hi, p.out_lo, b, n, p.nbs); break;
       case GEPI_RESID: p.out[(long)b * p.N + n] += y; break;
-      case GEPI_QKV_CACHE: {
-        const int d = p.d_model;
-        if (n < d) {
-          p.out[(long)b * d + n] = y;
-        } else {
-          const int step = p.off[b];  // this clip's cache row
-          const int cc = (n < 2 * d) ? n - d : n - 2 * d;
-          const int head = cc >> 6, dd = cc & 63;
-          const long base = (long)b * p.kv_batch_stride + (long)head * p.n_ctx_pad * 64;
-          if (n < 2 * d) p.k_cache[base + (long)(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)y;
-          else p.v_cache[base + (long)step * 64 + dd] = (h16)y;
-        }
-        break;
-      }
+      case GEPI_QKV_CACHE: store_qkv_cache(p, b, n, y, n < p.d_model ? 0 : p.off[b]); break;  // K / V rows: this clip's cache row
       case GEPI_LOGITS:
         if (p.logits_dump) p.logits_dump[(long)b * p.logits_dump_stride + n] = y;
         red[8 * RT * NB * 256 + nl * (NB * 16) + b] = y;  // [16*RT rows][NB*16 clips] for the argmax below
@@ -285,7 +257,7 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecGemmParams p) {
         const int n = n0 + i;
         if (n >= p.N) break;
         const float y = red[8 * RT * NB * 256 + i * (NB * 16) + tid];
-        if (y > best_v) { best_v = y; best_i = n; }
+        argmax_take(best_v, best_i, y, n);
       }
       p.amax_val[(long)tid * p.amax_stride + blockIdx.x] = best_v;
       p.amax_idx[(long)tid * p.amax_stride + blockIdx.x] = best_i;
@@ -300,17 +272,6 @@ __device__ __forceinline__ float sum_lanes_16_32(float v) {
   v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
   auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// sum over the 16 lanes of a DPP row (equal lane >> 4), in every lane of the row
-__device__ __forceinline__ float row16_sum_f(float v) {
-#define AXW_DPP_ROW(CTRL, X) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(X), CTRL, 0xf, 0xf, true))
-  v += AXW_DPP_ROW(0xB1, v);   // quad_perm [1,0,3,2]
-  v += AXW_DPP_ROW(0x4E, v);   // quad_perm [2,3,0,1]
-  v += AXW_DPP_ROW(0x141, v);  // row_half_mirror
-  v += AXW_DPP_ROW(0x140, v);  // row_mirror
-#undef AXW_DPP_ROW
-  return v;
 }
 
 // ---------------------------------------------------------------------------- clip-block GEMM (DecCGemmParams)
@@ -358,7 +319,7 @@ __global__ __launch_bounds__(512) void decode_cgemm_kernel(DecCGemmParams p) {
 
   const h16* wrow[RT];
 #pragma unroll
-  for (int t = 0; t < RT; ++t) wrow[t] = p.W + (long)min(nb0 + t, n_rb - 1) * KS * 512 + lane * 8;
+  for (int t = 0; t < RT; ++t) wrow[t] = p.W + layout::wfrag_tile_offset(min(nb0 + t, n_rb - 1), 0, KS) + layout::frag_lane_offset(lane);
 
   f32x4 acc[RT];
 #pragma unroll
@@ -373,7 +334,7 @@ __global__ __launch_bounds__(512) void decode_cgemm_kernel(DecCGemmParams p) {
     for (int c = 0; c < CH; ++c) {
       const int ks = min(wave + 8 * c, KS - 1);
 #pragma unroll
-      for (int t = 0; t < RT; ++t) w[c][t] = *reinterpret_cast<const h16x8*>(wrow[t] + (long)ks * 512);
+      for (int t = 0; t < RT; ++t) w[c][t] = *reinterpret_cast<const h16x8*>(wrow[t] + (long)ks * layout::kFragTileElems);
     }
     // lane (r, q) holds x[clip r][k = ks*32 + 8q .. +8] of every k-step of this wave: exactly its MFMA B fragment
     const float* xr = p.x + (long)min(cb * 16 + r, p.batch - 1) * p.K;
@@ -454,22 +415,23 @@ __global__ __launch_bounds__(512) void decode_cgemm_kernel(DecCGemmParams p) {
     // an out-of-range offset — their loads return zeros and move NO bytes. A clip block is 2 x 1 KB per k-step whatever it
     // holds: at 4 clips mlp.2 (K = 3072) pulled 196 KB of activations per workgroup through its CU for 49 KB of content, and
     // was the slowest GEMM launch of the few-clip step (6.0 us; profiles/r05_step_timeline_b4.txt).
-    const long a_step = (long)p.nbs * 512;
-    const unsigned a_bytes = (unsigned)((long)KS * a_step * 2 - (long)cb * 1024);
-    const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc((void*)(p.a_hi + (long)cb * 512), 0, (int)a_bytes, 0x27000);
-    const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(p.a_lo + (long)cb * 512), 0, (int)a_bytes, 0x27000);
-    const int a_off = cb * 16 + r < p.batch ? lane * 16 : 0x7ffffff0;
+    const long a_step = layout::frag_kstep_stride(p.nbs);
+    const long a_cb = layout::frag_tile_offset(0, cb, p.nbs);  // this clip block inside k-step 0
+    const unsigned a_bytes = (unsigned)((layout::pair_elems(KS, p.nbs) - a_cb) * 2);
+    const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc((void*)(p.a_hi + a_cb), 0, (int)a_bytes, 0x27000);
+    const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(p.a_lo + a_cb), 0, (int)a_bytes, 0x27000);
+    const int a_off = cb * 16 + r < p.batch ? layout::frag_lane_offset(lane) * 2 : 0x7ffffff0;
     struct Frag { h16x8 w[RT], wl[FOLD ? RT : 1], h, l; };
     const h16* wlrow[RT];  // FOLD: the lo halves of the fold rows' weights (their own array, row block 0 = row fold_row0)
 #pragma unroll
-    for (int t = 0; t < RT; ++t) wlrow[t] = (FOLD && fw) ? p.W_lo + (long)(nb0 + t - fr0 / 16) * KS * 512 + lane * 8 : nullptr;
+    for (int t = 0; t < RT; ++t) wlrow[t] = (FOLD && fw) ? p.W_lo + layout::wfrag_tile_offset(nb0 + t - fr0 / 16, 0, KS) + layout::frag_lane_offset(lane) : nullptr;
     auto load = [&](Frag& f, int ks) {
 #pragma unroll
-      for (int t = 0; t < RT; ++t) f.w[t] = *reinterpret_cast<const h16x8*>(wrow[t] + (long)ks * 512);
+      for (int t = 0; t < RT; ++t) f.w[t] = *reinterpret_cast<const h16x8*>(wrow[t] + (long)ks * layout::kFragTileElems);
       if constexpr (FOLD) {
         if (fw) {
 #pragma unroll
-          for (int t = 0; t < RT; ++t) f.wl[t] = *reinterpret_cast<const h16x8*>(wlrow[t] + (long)ks * 512);
+          for (int t = 0; t < RT; ++t) f.wl[t] = *reinterpret_cast<const h16x8*>(wlrow[t] + (long)ks * layout::kFragTileElems);
         }
       }
       const int so = (int)(ks * a_step * 2);  // wave-uniform: the scalar offset of the k-step
@@ -530,9 +492,9 @@ __global__ __launch_bounds__(512) void decode_cgemm_kernel(DecCGemmParams p) {
       if (fw) { p.out2[(long)b * (p.N - fr0) + (n - fr0)] = xn; break; }
       p.out[(long)b * nx + n] = xn;
       if (p.stat_part) {  // the 16 rows of this block for one clip sit in one DPP row (RT == 1: launch_decode_cgemm checks)
-        const float s1 = row16_sum_f(xn);
+        const float s1 = row16_sum(xn);
         const float dm = xn - s1 * (1.f / 16.f);
-        const float q2 = row16_sum_f(dm * dm);
+        const float q2 = row16_sum(dm * dm);
         if (nn == 0) *reinterpret_cast<f32x2_t*>(p.stat_part + ((long)b * (nx >> 4) + blockIdx.x) * 2) = f32x2_t{s1, q2};
       }
       break;
@@ -540,17 +502,8 @@ __global__ __launch_bounds__(512) void decode_cgemm_kernel(DecCGemmParams p) {
     case GEPI_GELU: store_pair_frag(gelu_erf(y), p.out_hi, p.out_lo, b, n, p.nbs); break;
     case GEPI_QKV_CACHE: {
       const int d = p.d_model;
-      if (n < d) {
-        p.out[(long)b * d + n] = y;
-      } else if (n >= 3 * d) {  // query-fold rows: A0
-        p.out2[(long)b * d + (n - 3 * d)] = y;
-      } else {
-        const int cc = (n < 2 * d) ? n - d : n - 2 * d;
-        const int head = cc >> 6, dd = cc & 63;
-        const long base = (long)b * p.kv_batch_stride + (long)head * p.n_ctx_pad * 64;
-        if (n < 2 * d) p.k_cache[base + (long)(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)y;
-        else p.v_cache[base + (long)step * 64 + dd] = (h16)y;
-      }
+      if (n >= 3 * d) p.out2[(long)b * d + (n - 3 * d)] = y;  // query-fold rows: A0
+      else store_qkv_cache(p, b, n, y, step);
       break;
     }
   }
@@ -613,14 +566,14 @@ __global__ __launch_bounds__(512) void decode_logits_kernel(DecGemmParams p) {
     const long ks = min(wave + 8 * c, KS - 1);
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) {
-      ah[c][cb] = *reinterpret_cast<const h16x8*>(p.a_hi + (ks * p.nbs + cb) * 512 + lane * 8);
-      al[c][cb] = *reinterpret_cast<const h16x8*>(p.a_lo + (ks * p.nbs + cb) * 512 + lane * 8);
+      ah[c][cb] = *reinterpret_cast<const h16x8*>(p.a_hi + layout::frag_tile_offset(ks, cb, p.nbs) + layout::frag_lane_offset(lane));
+      al[c][cb] = *reinterpret_cast<const h16x8*>(p.a_lo + layout::frag_tile_offset(ks, cb, p.nbs) + layout::frag_lane_offset(lane));
     }
   }
   auto loadw = [&](h16x8 (&w)[CH], int rb) {
 #pragma unroll
     for (int c = 0; c < CH; ++c)
-      w[c] = *reinterpret_cast<const h16x8*>(p.W + ((long)min(rb, n_rb - 1) * KS + min(wave + 8 * c, KS - 1)) * 512 + lane * 8);
+      w[c] = *reinterpret_cast<const h16x8*>(p.W + layout::wfrag_tile_offset(min(rb, n_rb - 1), min(wave + 8 * c, KS - 1), KS) + layout::frag_lane_offset(lane));
   };
   // three register sets: the blocks of the next TWO iterations are in flight while one is multiplied (with one block
   // ahead an iteration was one memory round trip: 25 us for 80 MB at 64 clips). loadw clamps the block index, so the
@@ -669,7 +622,7 @@ __global__ __launch_bounds__(512) void decode_logits_kernel(DecGemmParams p) {
         const int n = rb * 16 + nn, b = cb * 16 + bl;
         if (n < p.N && b < p.batch) {
           if (p.logits_dump) p.logits_dump[(long)b * p.logits_dump_stride + n] = y;
-          if (y > bv[u]) { bv[u] = y; bi[u] = n; }
+          argmax_take(bv[u], bi[u], y, n);
         }
       }
     }
@@ -689,16 +642,7 @@ __global__ __launch_bounds__(512) void decode_logits_kernel(DecGemmParams p) {
   // the 16 lanes that share a clip hold its candidates of different row lanes: lowest index wins ties
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
-    {  // DPP butterflies inside the 16-lane row (the __shfl_xor form: eight dependent ds_bpermute round trips at the launch's end)
-      auto take = [&](float ov, int oi) { if (ov > bv[u] || (ov == bv[u] && oi < bi[u])) { bv[u] = ov; bi[u] = oi; } };
-#define AXW_ROW_STEP(CTRL) { const float ov = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(bv[u]), CTRL, 0xf, 0xf, true)); \
-                             const int oi = __builtin_amdgcn_update_dpp(0, bi[u], CTRL, 0xf, 0xf, true); take(ov, oi); }
-      AXW_ROW_STEP(0xB1)   // quad_perm [1,0,3,2]
-      AXW_ROW_STEP(0x4E)   // quad_perm [2,3,0,1]
-      AXW_ROW_STEP(0x141)  // row_half_mirror
-      AXW_ROW_STEP(0x140)  // row_mirror
-#undef AXW_ROW_STEP
-    }
+    row16_argmax(bv[u], bi[u]);  // DPP butterflies (the __shfl_xor form: eight dependent ds_bpermute round trips at the launch's end)
     const int o = tid + 512 * u, b = o >> 4;
     if (o < NB * 256 && (o & 15) == 0 && b < p.batch) {
       p.amax_val[(long)b * p.amax_stride + blockIdx.x] = bv[u];

@@ -20,7 +20,7 @@
 namespace axw {
 inline namespace AXW_NS {
 
-constexpr int kPartStride = 66;  // m, l, o[64]
+using layout::kPartStride;
 
 template <int BT>
 __device__ __forceinline__ void prologue_layernorm(const GemvParams& p, float* act, float* red) {
@@ -76,14 +76,14 @@ __device__ __forceinline__ void prologue_attn_combine(const GemvParams& p, float
     const int b = i / K, c = i - b * K;
     float v = 0.f;
     if (b < p.batch) {
-      const float* pp = p.part + ((long)b * p.n_head + (c >> 6)) * p.n_split * kPartStride;
+      const float* pp = p.part + layout::part_offset(b, c >> 6, 0, p.n_head, p.n_split);
       float ms[MAXS], ls[MAXS], os[MAXS];
 #pragma unroll
       for (int s = 0; s < MAXS; ++s) {  // independent loads, one round trip
         const bool on = s < p.n_split;
-        ms[s] = on ? pp[s * kPartStride] : -INFINITY;
-        ls[s] = on ? pp[s * kPartStride + 1] : 0.f;
-        os[s] = on ? pp[s * kPartStride + 2 + (c & 63)] : 0.f;
+        ms[s] = on ? pp[s * kPartStride + layout::kPartM] : -INFINITY;
+        ls[s] = on ? pp[s * kPartStride + layout::kPartL] : 0.f;
+        os[s] = on ? pp[s * kPartStride + layout::kPartO + (c & 63)] : 0.f;
       }
       float m = ms[0];
 #pragma unroll
@@ -214,25 +214,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p, int rows_per_wg
           case GEPI_STORE: p.out[(long)b * p.N + n] = y; break;
           case GEPI_GELU: p.out[(long)b * p.N + n] = gelu_erf(y); break;
           case GEPI_RESID: p.out[(long)b * p.N + n] = (first ? resid0[b] : p.out[(long)b * p.N + n]) + y; break;
-          case GEPI_QKV_CACHE: {
-            const int d = p.d_model;
-            if (n < d) {
-              p.out[(long)b * d + n] = y;
-            } else {
-              const int c = (n < 2 * d) ? n - d : n - 2 * d;
-              const int head = c >> 6, dd = c & 63;
-              const long base = (long)b * p.kv_batch_stride + (long)head * p.n_ctx_pad * 64;
-              const int step = stepb[b];
-              if (n < 2 * d)  // blocked K: [blk][dd/8][key%64][8]
-                p.k_cache[base + (long)(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)y;
-              else            // row-major V: [key][64]
-                p.v_cache[base + (long)step * 64 + dd] = (h16)y;
-            }
-            break;
-          }
+          case GEPI_QKV_CACHE: store_qkv_cache(p, b, n, y, stepb[b]); break;
           case GEPI_LOGITS:
             if (p.logits_dump) p.logits_dump[(long)b * p.logits_dump_stride + n] = y;
-            if (y > best_v[b] || (y == best_v[b] && n < best_i[b])) { best_v[b] = y; best_i[b] = n; }
+            argmax_take(best_v[b], best_i[b], y, n);
             break;
         }
       }
@@ -248,7 +233,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p, int rows_per_wg
       for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(v, o, 64);
         const int oi = __shfl_xor(ix, o, 64);
-        if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+        argmax_take(v, ix, ov, oi);
       }
       if (lane == 0) { s_val[wave * BT + b] = v; s_idx[wave * BT + b] = ix; }
     }
@@ -256,11 +241,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p, int rows_per_wg
     if (tid < BT && tid < p.batch) {
       float v = s_val[tid];
       int ix = s_idx[tid];
-      for (int w = 1; w < 4; ++w) {
-        const float ov = s_val[w * BT + tid];
-        const int oi = s_idx[w * BT + tid];
-        if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
-      }
+      for (int w = 1; w < 4; ++w) argmax_take(v, ix, s_val[w * BT + tid], s_idx[w * BT + tid]);
       p.amax_val[(long)tid * p.amax_stride + blockIdx.x] = v;
       p.amax_idx[(long)tid * p.amax_stride + blockIdx.x] = ix;
     }
@@ -372,22 +353,10 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvParams p, int rows_per_w
         case GEPI_STORE: p.out[n] = y; break;
         case GEPI_GELU: p.out[n] = gelu_erf(y); break;
         case GEPI_RESID: p.out[n] = (first ? resid0 : p.out[n]) + y; break;
-        case GEPI_QKV_CACHE: {
-          const int d = p.d_model;
-          if (n < d) {
-            p.out[n] = y;
-          } else {
-            const int c = (n < 2 * d) ? n - d : n - 2 * d;
-            const int head = c >> 6, dd = c & 63;
-            const long base = (long)head * p.n_ctx_pad * 64;
-            if (n < 2 * d) p.k_cache[base + (long)(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)y;
-            else p.v_cache[base + (long)step * 64 + dd] = (h16)y;
-          }
-          break;
-        }
+        case GEPI_QKV_CACHE: store_qkv_cache(p, 0, n, y, step); break;
         case GEPI_LOGITS:
           if (p.logits_dump) p.logits_dump[n] = y;
-          if (y > best_v || (y == best_v && n < best_i)) { best_v = y; best_i = n; }
+          argmax_take(best_v, best_i, y, n);
           break;
       }
     }
@@ -397,13 +366,12 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvParams p, int rows_per_w
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(best_v, o, 64);
       const int oi = __shfl_xor(best_i, o, 64);
-      if (ov > best_v || (ov == best_v && oi < best_i)) { best_v = ov; best_i = oi; }
+      argmax_take(best_v, best_i, ov, oi);
     }
     if (lane == 0) { s_val[wave] = best_v; s_idx[wave] = best_i; }
     __syncthreads();
     if (tid == 0) {
-      for (int w = 1; w < 4; ++w)
-        if (s_val[w] > best_v || (s_val[w] == best_v && s_idx[w] < best_i)) { best_v = s_val[w]; best_i = s_idx[w]; }
+      for (int w = 1; w < 4; ++w) argmax_take(best_v, best_i, s_val[w], s_idx[w]);
       p.amax_val[blockIdx.x] = best_v;
       p.amax_idx[blockIdx.x] = best_i;
     }
@@ -539,9 +507,7 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
     int idx = 0x7fffffff;
 #pragma unroll 4
     for (int i = lane; i < p.n_part; i += 64) {
-      const float ov = p.amax_val[(long)b * p.amax_stride + i];
-      const int oi = p.amax_idx[(long)b * p.amax_stride + i];
-      if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+      argmax_take(v, idx, p.amax_val[(long)b * p.amax_stride + i], p.amax_idx[(long)b * p.amax_stride + i]);
     }
     wave_argmax(v, idx);
     // no logit compared greater than -inf (all NaN / -inf: non-finite audio): std::max_element returns index 0

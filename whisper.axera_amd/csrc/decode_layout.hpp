@@ -1,0 +1,73 @@
+// decode_layout.hpp — the decoder's device data layouts, each defined ONCE: the blocked K cache, the row-major V cache, the
+// transposed V of the persistent launches' LDS cache, the fragment-major (hi, lo) activation pairs and packed weights, and the
+// attention split record. Kernels, the engine and the host-side table printer (tests/cpp/decode_layout_tables.cpp) all index
+// through these functions; tests/decode_kernel_reference.py restates the maps independently and the CPU suite compares the two
+// element for element. Plain C++: no HIP include, `__host__ __device__` only where the compiler is hipcc.
+#pragma once
+
+#ifdef __HIPCC__
+#define AXW_LAYOUT_FN __host__ __device__ constexpr inline
+#else
+#define AXW_LAYOUT_FN constexpr inline
+#endif
+
+namespace axw {
+namespace layout {
+
+// ------------------------------------------------------------------ K / V of one (clip, head): 64 dims per key, 64-key blocks
+constexpr int kKvDim = 64;                          // head dimension (all Whisper sizes)
+constexpr int kKvBlockKeys = 64;                    // keys per block
+constexpr int kKvBlockElems = kKvBlockKeys * kKvDim;  // 4096 elements: one block of K or of V
+constexpr int kKvChunkElems = 8 * kKvBlockKeys;     // 512: one 8-dim chunk of a K block (8 keys of a transposed V block)
+
+// elements of one head's K or V with `keys_pad` allocated keys (a multiple of 64)
+AXW_LAYOUT_FN long kv_head_elems(int keys_pad) { return (long)keys_pad * kKvDim; }
+// The readers' view of a blocked tile: element offset of (block, 8-wide chunk, row), a 16-byte piece of 8 elements.
+//   blocked K      chunk = dim / 8,        row = key % 64   (lane = key: the q.k dot product is lane-local)
+//   transposed V   chunk = (key % 64) / 8, row = dim        (lane = dim: o[dim] accumulates over key pairs)
+// Row-major V read in this order is piece chunk * 64 + row of the block's 512 sixteen-byte pieces: a whole-block copy (the persistent
+// launches' LDS-DMA of cross K and V tiles) walks both layouts with it.
+AXW_LAYOUT_FN int kv_chunk_offset(int block, int chunk, int row) { return block * kKvBlockElems + chunk * kKvChunkElems + row * 8; }
+// blocked K [key / 64][dim / 8][key % 64][8]: the self cache, the cross cache and the persistent launches' LDS K
+AXW_LAYOUT_FN int k_index(int key, int dim) { return kv_chunk_offset(key >> 6, dim >> 3, key & 63) + (dim & 7); }
+// row-major V [key][64]: the self and cross caches in global memory
+AXW_LAYOUT_FN int v_row_offset(int key) { return key * kKvDim; }
+AXW_LAYOUT_FN int v_index(int key, int dim) { return v_row_offset(key) + dim; }
+// transposed V of the persistent launches' own self-attention cache: [key / 64][(key % 64) / 8][dim][8 keys]
+AXW_LAYOUT_FN int vt_index(int key, int dim) { return kv_chunk_offset(key >> 6, (key >> 3) & 7, dim) + (key & 7); }
+
+// ------------------------------------------------------------------ fragment-major MFMA operands (v_mfma_f32_16x16x32)
+// A tile is 16 rows x 32 k = 512 elements in the order the instruction consumes them, so an operand load of a wave is ONE
+// contiguous 1 KiB access (lane * 16 bytes): element (lane, j) of a tile = [row & 15 = lane & 15][k & 31 = (lane >> 4) * 8 + j].
+//   activations (hi and lo each)  tile (ks, cb) at (ks * nbs + cb): clip = cb * 16 + (lane & 15), nbs = allocated clip blocks
+//   packed weights                tile (rb, ks) at (rb * KS + ks):  row  = rb * 16 + (lane & 15), KS = K / 32
+constexpr int kFragTileElems = 512;
+constexpr int kClipBlockStride = kFragTileElems;    // elements between the clip blocks of one k-step
+AXW_LAYOUT_FN int frag_lane_offset(int lane) { return lane * 8; }
+AXW_LAYOUT_FN int frag_in_tile(int row, int k) { return frag_lane_offset(((k >> 3) & 3) * 16 + (row & 15)) + (k & 7); }
+AXW_LAYOUT_FN long frag_tile_offset(long ks, int cb, int nbs) { return (ks * nbs + cb) * kFragTileElems; }
+AXW_LAYOUT_FN long wfrag_tile_offset(long rb, int ks, int KS) { return (rb * KS + ks) * kFragTileElems; }
+AXW_LAYOUT_FN long frag_index(int clip, int k, int nbs) { return frag_tile_offset(k >> 5, clip >> 4, nbs) + frag_in_tile(clip, k); }
+AXW_LAYOUT_FN long wfrag_index(int row, int k, int KS) { return wfrag_tile_offset(row >> 4, k >> 5, KS) + frag_in_tile(row, k); }
+AXW_LAYOUT_FN long frag_kstep_stride(int nbs) { return (long)nbs * kFragTileElems; }   // elements between consecutive k-steps of a pair buffer
+AXW_LAYOUT_FN long pair_elems(int k_steps, int nbs) { return k_steps * frag_kstep_stride(nbs); }  // one buffer (hi or lo) of a pair
+AXW_LAYOUT_FN long clip_block_offset(int clip0) { return (long)(clip0 / 16) * kClipBlockStride; }  // clip0: a multiple of 16
+AXW_LAYOUT_FN long wfrag_elems(int N, int K) { return wfrag_tile_offset((N + 15) / 16, 0, K / 32); }   // rows padded to 16
+// the packing kernels' direction: which W[row][k] sits at element i of the packed array
+struct RowK { int row, k; };
+AXW_LAYOUT_FN RowK wfrag_source(long i, int KS) {
+  const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
+  const long tile = i / kFragTileElems;
+  return RowK{(int)(tile / KS) * 16 + (lane & 15), (int)(tile % KS) * 32 + (lane >> 4) * 8 + j};
+}
+
+// ------------------------------------------------------------------ attention split record: m, l, o[64]
+constexpr int kPartM = 0, kPartL = 1, kPartO = 2;
+constexpr int kPartStride = kPartO + kKvDim;        // 66 floats
+constexpr int kAttnSplitMax = 6;                    // most workgroups per (clip, head) whose records one launch folds itself
+// record of (clip, head, split) in a [clips][n_head][n_split] array, and the floats `clips` clips take
+AXW_LAYOUT_FN long part_offset(long clip, int head, int split, int n_head, int n_split) { return ((clip * n_head + head) * n_split + split) * kPartStride; }
+AXW_LAYOUT_FN long part_elems(long clips, int n_head, int n_split) { return part_offset(clips, 0, 0, n_head, n_split); }
+
+}  // namespace layout
+}  // namespace axw

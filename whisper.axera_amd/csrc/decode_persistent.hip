@@ -274,9 +274,9 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
               const int dd = 2 * (tid & 31) + e;
               const float val = __uint_as_float(v[e]);
               if (tid < 64)  // K row `step`, blocked [blk][d/8][key%64][8]
-                sK[(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)val;
+                sK[layout::k_index(step, dd)] = (h16)val;
               else           // V row `step`, TRANSPOSED per block: [blk][key%64 / 8][dim][8 keys]
-                sV[(step >> 6) * 4096 + ((step >> 3) & 7) * 512 + dd * 8 + (step & 7)] = (h16)val;
+                sV[layout::vt_index(step, dd)] = (h16)val;
             }
           }
           if (fail) ctl[0] = 1;
@@ -530,10 +530,10 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
       const int cu0 = ca_unit_of(0, NU, wg, NS);
       if (cu0 >= 0) {
         const int lane = ctid & 63, cw = __builtin_amdgcn_readfirstlane(ctid >> 6);
-        const long off = (long)(cu0 / kCrossSplit) * 24 * 4096 + (long)((cu0 % kCrossSplit) * NCW + cw) * 4096;
+        const long off = (cu0 / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset((cu0 % kCrossSplit) * NCW + cw, 0, 0);
         for (int i = 0; i < 8; ++i) {
-          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_k + off + i * 512 + lane * 8), (lds_ptr_t)(sK + cw * 4096 + i * 512), 16, 0, kKvAux);
-          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_v + off + i * 512 + lane * 8), (lds_ptr_t)(sV + cw * 4096 + i * 512), 16, 0, kKvAux);
+          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_k + off + layout::kv_chunk_offset(0, i, lane)), (lds_ptr_t)(sK + layout::kv_chunk_offset(cw, i, 0)), 16, 0, kKvAux);
+          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_v + off + layout::kv_chunk_offset(0, i, lane)), (lds_ptr_t)(sV + layout::kv_chunk_offset(cw, i, 0)), 16, 0, kKvAux);
         }
       }
     }
@@ -560,10 +560,10 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         auto kv_piece = [&](int i0, int i1) {
           if (cun < 0) return;
           const int kb = (cun % kCrossSplit) * NCW + cw;  // 64-key block of this wave (24 blocks = t_pad 1536)
-          const long off = (long)ln * p.cross_layer_stride + (long)(cun / kCrossSplit) * 24 * 4096 + (long)kb * 4096;
+          const long off = (long)ln * p.cross_layer_stride + (cun / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset(kb, 0, 0);
           for (int i = i0; i < i1; ++i) {
-            const h16* src = (i < 8 ? p.cross_k : p.cross_v) + off + (i & 7) * 512 + lane * 8;
-            h16* dst = (i < 8 ? sK : sV) + cw * 4096 + (i & 7) * 512;
+            const h16* src = (i < 8 ? p.cross_k : p.cross_v) + off + layout::kv_chunk_offset(0, i & 7, lane);
+            h16* dst = (i < 8 ? sK : sV) + layout::kv_chunk_offset(cw, i & 7, 0);
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)dst, 16, 0, kKvAux);
           }
         };
@@ -606,7 +606,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           AXW_BARRIER_CHECK(0x200 + l)
           const int nblk = (step >> 6) + 1;
           if (cw < nblk)
-            attn_block<true>(sK + cw * 4096, sV + cw * 4096, qs, cw * 64 + lane <= step, pscr + cw * 64, wpart + cw * kPS, lane);
+            attn_block<true>(sK + cw * layout::kKvBlockElems, sV + cw * layout::kKvBlockElems, qs, cw * 64 + lane <= step, pscr + cw * 64, wpart + cw * kPS, lane);
           // no second workgroup barrier: the compute wave that arrives last merges the block partials and publishes
           __builtin_amdgcn_wave_barrier();
           int old = 0;
@@ -837,12 +837,12 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         wg_barrier();  // B3 (all waves)
         if (ctid == 0) {
           for (int w2 = 1; w2 < NCW; ++w2)
-            if (am_v[8 + w2] > bv || (am_v[8 + w2] == bv && am_i[8 + w2] < bi)) { bv = am_v[8 + w2]; bi = am_i[8 + w2]; }
+            argmax_take(bv, bi, am_v[8 + w2], am_i[8 + w2]);
           if (nres > 0) {  // the poller waves' candidates over the resident rows
             for (int w2 = 0; w2 < NPW; ++w2) {
               const float pv = pscr[w2];
               const int pi = reinterpret_cast<const int*>(pscr)[NPW + w2];
-              if (pv > bv || (pv == bv && pi < bi)) { bv = pv; bi = pi; }
+              argmax_take(bv, bi, pv, pi);
             }
           }
           am_v[8] = bv; am_i[8] = bi;

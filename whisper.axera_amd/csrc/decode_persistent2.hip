@@ -174,9 +174,9 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
                 const int dd = 2 * (tid & 31) + e;
                 const float val = __uint_as_float(v[e]);
                 if (tid < 64)  // K row `step`, blocked [blk][d/8][key%64][8]
-                  sK[(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)val;
+                  sK[layout::k_index(step, dd)] = (h16)val;
                 else           // V row `step`, TRANSPOSED per block: [blk][key%64 / 8][dim][8 keys]
-                  sV[(step >> 6) * 4096 + ((step >> 3) & 7) * 512 + dd * 8 + (step & 7)] = (h16)val;
+                  sV[layout::vt_index(step, dd)] = (h16)val;
               }
             }
             if (fail) ctl[0] = 1;
@@ -196,21 +196,21 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
             u32x4 kr[8], vr[8];
             {
               const bool on = pw < nblk;  // a block without a single key of this clip yet: all zeros, every key masked
-              const h16* kc = p.self_k1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * 4096) + (on ? pw : 0) * 4096;
-              const h16* vc = p.self_v1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * 4096) + (on ? pw : 0) * 4096;
+              const h16* kc = p.self_k1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * layout::kKvBlockElems) + (on ? pw : 0) * layout::kKvBlockElems;
+              const h16* vc = p.self_v1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * layout::kKvBlockElems) + (on ? pw : 0) * layout::kKvBlockElems;
               const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)kc, 0, on ? 8192 : 0, 0x27000);  // (0 bytes: loads return 0, no traffic)
               const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vc, 0, on ? 8192 : 0, 0x27000);
 #pragma unroll
-              for (int i = 0; i < 8; ++i) kr[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, (i * 512 + lane * 8) * 2, 0, 1);  // sc0: past L1
+              for (int i = 0; i < 8; ++i) kr[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, layout::kv_chunk_offset(0, i, lane) * 2, 0, 1);  // sc0: past L1
 #pragma unroll
-              for (int i = 0; i < 8; ++i) vr[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, (i * 512 + lane * 8) * 2, 0, 1);
+              for (int i = 0; i < 8; ++i) vr[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, layout::kv_chunk_offset(0, i, lane) * 2, 0, 1);
             }
             unsigned v[2];
             const bool fail = gather2<1>(GR, tag, v, p.err, ctl, qkv_pair(c));
             if (tid < 32) stage_q(v, qsc[c]);
             else if (tid < 96) {
-              h16* kd = p.self_k1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * 4096);
-              h16* vd = p.self_v1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * 4096);
+              h16* kd = p.self_k1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * layout::kKvBlockElems);
+              h16* vd = p.self_v1 + (c - 1) * p.self_clip_stride + (long)sa_unit * (NCW * layout::kKvBlockElems);
 #pragma unroll
               for (int e = 0; e < 2; ++e) {
                 const int dd = 2 * (tid & 31) + e;
@@ -221,8 +221,8 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
                 // load issued behind these stores: the very next gather) the stores have been acknowledged by L2; the reading
                 // waves are on this CU, at least one workgroup barrier behind that point (a whole decoder step, in fact), and
                 // read with sc0 = past the L1 that may still hold the line from an earlier step
-                if (tid < 64) kd[(step >> 6) * 4096 + (dd >> 3) * 512 + (step & 63) * 8 + (dd & 7)] = (h16)val;
-                else vd[(step >> 6) * 4096 + ((step >> 3) & 7) * 512 + dd * 8 + (step & 7)] = (h16)val;
+                if (tid < 64) kd[layout::k_index(step, dd)] = (h16)val;
+                else vd[layout::vt_index(step, dd)] = (h16)val;
                 kvtc[c][(tid < 64 ? 0 : 64) + dd] = (h16)val;
               }
             }
@@ -485,9 +485,9 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
       if (cu0 >= 0) {  // its K tiles; the V tiles are layer 0's own pieces
         const int lane = ctid & 63, cw = __builtin_amdgcn_readfirstlane(ctid >> 6);
         const int u0 = cu0 % NU;
-        const long off = (long)(cu0 / NU) * p.cross_clip_stride + (long)(u0 / kCrossSplit) * 24 * 4096 + (long)((u0 % kCrossSplit) * NCW + cw) * 4096;
+        const long off = (long)(cu0 / NU) * p.cross_clip_stride + (u0 / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset((u0 % kCrossSplit) * NCW + cw, 0, 0);
         for (int i = 0; i < 8; ++i)
-          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_k + off + i * 512 + lane * 8), (lds_ptr_t)(sK + cw * 4096 + i * 512), 16, 0, kKvAux);
+          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_k + off + layout::kv_chunk_offset(0, i, lane)), (lds_ptr_t)(sK + layout::kv_chunk_offset(cw, i, 0)), 16, 0, kKvAux);
       }
     }
 
@@ -517,10 +517,10 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           if (un < 0) return;
           const int uu = un % NU;
           const int kb = (uu % kCrossSplit) * NCW + cw;  // 64-key block of this wave (24 blocks = t_pad 1536)
-          const long off = (long)(un / NU) * p.cross_clip_stride + (long)lay * p.cross_layer_stride + (long)(uu / kCrossSplit) * 24 * 4096 + (long)kb * 4096;
+          const long off = (long)(un / NU) * p.cross_clip_stride + (long)lay * p.cross_layer_stride + (uu / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset(kb, 0, 0);
           for (int i = i0; i < i1; ++i) {
-            const h16* src = (i < 8 ? p.cross_k : p.cross_v) + off + (i & 7) * 512 + lane * 8;
-            h16* dst = (i < 8 ? sK : sV) + cw * 4096 + (i & 7) * 512;
+            const h16* src = (i < 8 ? p.cross_k : p.cross_v) + off + layout::kv_chunk_offset(0, i & 7, lane);
+            h16* dst = (i < 8 ? sK : sV) + layout::kv_chunk_offset(cw, i & 7, 0);
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)dst, 16, 0, kKvAux);
           }
         };
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
              // wave that arrives last merges the block partials and publishes.
             AXW_BARRIER_CHECK(0x200 + l)
             const int nblk = (step >> 6) + 1;
-            if (cw < nblk) attn_block<true>(sK + cw * 4096, sV + cw * 4096, qs, cw * 64 + lane <= step, pscr + cw * 64, wpart + cw * kPS, lane);
+            if (cw < nblk) attn_block<true>(sK + cw * layout::kKvBlockElems, sV + cw * layout::kKvBlockElems, qs, cw * 64 + lane <= step, pscr + cw * 64, wpart + cw * kPS, lane);
             __builtin_amdgcn_wave_barrier();
             int old = 0;
             if (lane == 0) old = __hip_atomic_fetch_add(ctl + 3, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);

@@ -41,7 +41,8 @@ constexpr bool kVocabNT = AXW_VOCAB_NT != 0;
 constexpr int kKvAux = AXW_KV_NT_LDS ? 2 : 0;  // aux bits of global_load_lds: 2 = nt
 constexpr int kSpinFree = 1024;
 constexpr long long kSpinTicks = 5000000;
-constexpr int kPS = 66;            // attention partial record in LDS: m, l, o[64]
+constexpr int kPS = layout::kPartStride;  // attention partial record in LDS: m, l, o[64]
+constexpr int kCrossKeysPad = 24 * layout::kKvBlockKeys;  // allocated cross-attention keys per head: 1500 padded to 24 blocks
 constexpr int kRec = 80;           // cross-attention partial record as granules: o[64] (four full lines), m, l; 5-line stride
 constexpr int kCrossSplit = 3;     // cross-attention key ranges per head (8 blocks of 64 keys each = 8 compute waves)
 constexpr int kKvBytes = 2 * NCW * 8192;  // LDS K/V region: K [8 blk][8][64][8] h16 + V [512 keys][64] h16
@@ -336,7 +337,7 @@ __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, con
   float sc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 2
   for (int i = 0; i < 8; ++i) {
-    const u32x4 kq = *reinterpret_cast<const u32x4*>(kblk + i * 512 + lane * 8);
+    const u32x4 kq = *reinterpret_cast<const u32x4*>(kblk + layout::kv_chunk_offset(0, i, lane));
     const u32x4 qh = *reinterpret_cast<const u32x4*>(qp + i * 4), ql = *reinterpret_cast<const u32x4*>(qp + 32 + i * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -359,7 +360,7 @@ __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, con
     const unsigned* pwu = reinterpret_cast<const unsigned*>(pw);
 #pragma unroll 2
     for (int i = 0; i < 8; ++i) {  // keys 8i..8i+7 of dim `lane`
-      const u32x4 vv = *reinterpret_cast<const u32x4*>(vblk + i * 512 + lane * 8);
+      const u32x4 vv = *reinterpret_cast<const u32x4*>(vblk + layout::kv_chunk_offset(0, i, lane));
       const u32x4 h4 = *reinterpret_cast<const u32x4*>(pwu + i * 4), l4 = *reinterpret_cast<const u32x4*>(pwu + 32 + i * 4);
 #pragma unroll
       for (int e = 0; e < 4; e += 2) {
@@ -381,7 +382,7 @@ __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, con
     for (int e = 0; e < 8; ++e) o[e] = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {  // V row of key 8i + (lane>>3), dims (lane&7)*8 .. +8
-      const u32x4 vv = *reinterpret_cast<const u32x4*>(vblk + (8 * i + (lane >> 3)) * 64 + (lane & 7) * 8);
+      const u32x4 vv = *reinterpret_cast<const u32x4*>(vblk + layout::v_index(8 * i + (lane >> 3), (lane & 7) * 8));
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         o[2 * e] = fmaf(pr[i], h16lo(vv[e]), o[2 * e]);
@@ -515,7 +516,7 @@ __device__ __forceinline__ void cross_unit_block(const h16* sK, const h16* sV, c
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   asm volatile("" ::: "memory");
   const int key = (ca_split * NCW + cw) * 64 + lane;
-  attn_block<false>(sK + cw * 4096, sV + cw * 4096, qs, key < n_audio_ctx, pscr + cw * 64, wpart + cw * kPS, lane);
+  attn_block<false>(sK + cw * layout::kKvBlockElems, sV + cw * layout::kKvBlockElems, qs, key < n_audio_ctx, pscr + cw * 64, wpart + cw * kPS, lane);
   __builtin_amdgcn_wave_barrier();
   int old = 0;
   if (lane == 0) old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -634,7 +635,7 @@ __device__ __forceinline__ void qfold_publish(int lane, const float* pk, const f
 #define AXW_PERSIST_LDS(QS_GAP)                                                                                              \
   extern __shared__ __attribute__((aligned(16))) char smem[];                                                                \
   h16* sK = reinterpret_cast<h16*>(smem);                                                                                    \
-  h16* sV = sK + NCW * 4096;                                                                                                 \
+  h16* sV = sK + NCW * layout::kKvBlockElems;                                                                                                 \
   float* act = reinterpret_cast<float*>(smem + kKvBytes);                                                                    \
   float* wpart = act + F + D / 8;                                                                                            \
   float* red = wpart + NCW * kPS;                                                                                            \

@@ -153,8 +153,8 @@ __global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesParams p) {
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < 4; ++w) {
-      if (s_tv[w] > tv || (s_tv[w] == tv && s_ti[w] < ti)) { tv = s_tv[w]; ti = s_ti[w]; }
-      if (s_sv[w] > sv || (s_sv[w] == sv && s_si[w] < si)) { sv = s_sv[w]; si = s_si[w]; }
+      argmax_take(tv, ti, s_tv[w], s_ti[w]);
+      argmax_take(sv, si, s_sv[w], s_si[w]);
       lse_merge(m, s, s_m[w], s_s[w]);
     }
     const float lse = (m == -INFINITY || m == INFINITY) ? m : m + logf(s);
@@ -269,8 +269,8 @@ __global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesPara
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < 4; ++w) {
-      if (s_tv[w] > tv || (s_tv[w] == tv && s_ti[w] < ti)) { tv = s_tv[w]; ti = s_ti[w]; }
-      if (s_sv[w] > sv || (s_sv[w] == sv && s_si[w] < si)) { sv = s_sv[w]; si = s_si[w]; }
+      argmax_take(tv, ti, s_tv[w], s_ti[w]);
+      argmax_take(sv, si, s_sv[w], s_si[w]);
       lse_merge(m, s, s_m[w], s_s[w]);
       lse_merge(mt, st, s_mt[w], s_st[w]);
     }

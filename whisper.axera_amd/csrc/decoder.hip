@@ -29,8 +29,11 @@
 namespace axw {
 inline namespace AXW_NS {
 
-constexpr int kPartStride = 66;  // m, l, o[64]  (decode_gemv.hip merges these partials)
-constexpr int kAttnSplitMax = 6;  // workgroups per (clip, head) whose partials a launch folds itself (Engine::kCrossSplitMax)
+using layout::kPartStride;    // split record m, l, o[64] (decode_gemv.hip merges these partials)
+using layout::kAttnSplitMax;  // workgroups per (clip, head) whose partials a launch folds itself
+using layout::kPartM;
+using layout::kPartL;
+using layout::kPartO;
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 
@@ -105,8 +108,8 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(DecAttnParams p, 
   const int blk_begin = split * bps, blk_cap_end = min(cap_blocks, blk_begin + bps);
 
   const float* __restrict__ qp = p.q + (long)b * p.d_model + head * 64;  // wave-uniform: scalar loads
-  const h16* kb = p.k + (long)b * p.kv_batch_stride + (long)head * cap_blocks * 4096;
-  const h16* vb = p.v + (long)b * p.kv_batch_stride + (long)head * cap_blocks * 4096;
+  const h16* kb = p.k + (long)b * p.kv_batch_stride + head * layout::kv_head_elems(cap_blocks * layout::kKvBlockKeys);
+  const h16* vb = p.v + (long)b * p.kv_batch_stride + head * layout::kv_head_elems(cap_blocks * layout::kKvBlockKeys);
 
   // The first block's K/V loads go out before the step counter is even known: every block below
   // cap_blocks is allocated (and zero-initialised), keys beyond n_keys are masked afterwards.
@@ -120,13 +123,13 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(DecAttnParams p, 
   auto load_k = [&](int bk, int limit) {
     const int lk = max(0, min(lane, limit - 1 - bk * 64));
 #pragma unroll
-    for (int i = 0; i < 8; ++i) kn[i] = ld_kv(kb, (long)bk * 4096 + i * 512 + lk * 8);
+    for (int i = 0; i < 8; ++i) kn[i] = ld_kv(kb, layout::kv_chunk_offset(bk, i, lk));
   };
   auto load_v = [&](int bk, int limit) {
     const int last = max(bk * 64, limit - 1);
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      vn[i] = ld_kv(vb, (long)min(bk * 64 + 8 * i + (lane >> 3), last) * 64 + (lane & 7) * 8);
+      vn[i] = ld_kv(vb, layout::v_index(min(bk * 64 + 8 * i + (lane >> 3), last), (lane & 7) * 8));
   };
   // cross-attention knows its key count; self-attention does not yet (the step counter is a load): its first block is
   // fetched whole (every block below cap_blocks is allocated and zero-initialised)
@@ -320,21 +323,21 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(DecAttnParams p, 
       o[e] = __uint_as_float(a[0]) + __uint_as_float(a[1]);
     }
   }
-  if (lane == 0) { s_part[wave][0] = m_w; s_part[wave][1] = l_w; }
+  if (lane == 0) { s_part[wave][kPartM] = m_w; s_part[wave][kPartL] = l_w; }
   if (lane < 8) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s_part[wave][2 + lane * 8 + e] = o[e];
+    for (int e = 0; e < 8; ++e) s_part[wave][kPartO + lane * 8 + e] = o[e];
   }
   __syncthreads();
   if (tid < 64) {
-    float m = fmaxf(fmaxf(s_part[0][0], s_part[1][0]), fmaxf(s_part[2][0], s_part[3][0]));
+    float m = fmaxf(fmaxf(s_part[0][kPartM], s_part[1][kPartM]), fmaxf(s_part[2][kPartM], s_part[3][kPartM]));
     float l = 0.f, ov = 0.f;
     if (m > -INFINITY) {
 #pragma unroll
       for (int w = 0; w < 4; ++w) {
-        const float f = __expf(s_part[w][0] - m);
-        l += f * s_part[w][1];
-        ov += f * s_part[w][2 + tid];
+        const float f = __expf(s_part[w][kPartM] - m);
+        l += f * s_part[w][kPartL];
+        ov += f * s_part[w][kPartO + tid];
       }
     }
     stamp_at(5);
@@ -343,12 +346,12 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(DecAttnParams p, 
       // each streaming its 24 key blocks one after the other). Every split publishes (m, l, o[64]) with write-through
       // stores, drains them, and draws a ticket; whoever draws the last one folds all of them IN SPLIT ORDER (the
       // result does not depend on who arrives last) and writes the output.
-      float* base = p.mpart + ((long)b * p.n_head + head) * p.n_split * kPartStride;
+      float* base = p.mpart + layout::part_offset(b, head, 0, p.n_head, p.n_split);
       float* mine = base + split * kPartStride;
-      __hip_atomic_store(mine + 2 + tid, ov, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(mine + kPartO + tid, ov, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (tid == 0) {
-        __hip_atomic_store(mine, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 1, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + kPartM, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + kPartL, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       stamp_at(6);
@@ -375,9 +378,9 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(DecAttnParams p, 
         ms[s2] = m; ls[s2] = l; os[s2] = ov;
         if (s2 < p.n_split && s2 != split) {
           const float* other = base + s2 * kPartStride;
-          ms[s2] = __hip_atomic_load(other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ls[s2] = __hip_atomic_load(other + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          os[s2] = __hip_atomic_load(other + 2 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ms[s2] = __hip_atomic_load(other + kPartM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ls[s2] = __hip_atomic_load(other + kPartL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          os[s2] = __hip_atomic_load(other + kPartO + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
       float M = -INFINITY, Ls = 0.f, O = 0.f;
@@ -396,21 +399,19 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(DecAttnParams p, 
       if (tid == 0) __hip_atomic_store(p.mcnt + b * p.n_head + head, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
       const float y = O / Ls;
       const h16 yh = (h16)y;
-      const int k = head * 64 + tid;
-      const long i = ((((long)(k >> 5) * p.nbs + (b >> 4)) * 64) + ((k >> 3) & 3) * 16 + (b & 15)) * 8 + (k & 7);
+      const long i = layout::frag_index(b, head * 64 + tid, p.nbs);
       p.out_hi[i] = yh;
       p.out_lo[i] = (h16)(y - (float)yh);
     } else if (p.out_hi) {  // single split: this IS the attention output (batched decode path)
       const float y = ov / l;
       const h16 yh = (h16)y;
-      const int k = head * 64 + tid;  // fragment-major pair (layout: decode_gemm.hip)
-      const long i = ((((long)(k >> 5) * p.nbs + (b >> 4)) * 64) + ((k >> 3) & 3) * 16 + (b & 15)) * 8 + (k & 7);
+      const long i = layout::frag_index(b, head * 64 + tid, p.nbs);  // fragment-major pair
       p.out_hi[i] = yh;
       p.out_lo[i] = (h16)(y - (float)yh);
     } else {
-      float* out = p.part + (((long)b * p.n_head + head) * p.n_split + split) * kPartStride;
-      if (tid == 0) { out[0] = m; out[1] = l; }
-      out[2 + tid] = ov;
+      float* out = p.part + layout::part_offset(b, head, split, p.n_head, p.n_split);
+      if (tid == 0) { out[kPartM] = m; out[kPartL] = l; }
+      out[kPartO + tid] = ov;
     }
     stamp_end();  // thread 0 sits in the wave that writes the output: the last thing a workgroup does
   }

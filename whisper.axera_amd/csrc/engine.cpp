@@ -122,7 +122,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
         if (!(ev && ev[0] == '0')) vocab_resident_rows_ = decode_persistent_vocab_resident_rows(cfg_.n_text_state, cfg_.n_vocab, persist_grid_);
       }
       if (persist_max_clips_ >= 2) {
-        self1_bytes_ = (size_t)cfg_.n_text_layer * cfg_.n_text_head * 8 * 4096 * 2;  // one later clip's cache (K; V alike)
+        self1_bytes_ = (size_t)cfg_.n_text_layer * cfg_.n_text_head * 8 * layout::kKvBlockElems * 2;  // one later clip's cache (K; V alike)
         d_self_k1_ = (h16*)dalloc((persist_max_clips_ - 1) * self1_bytes_, true);
         d_self_v1_ = (h16*)dalloc((persist_max_clips_ - 1) * self1_bytes_, true);
         allocs_.push_back(d_self_k1_);
@@ -569,10 +569,10 @@ void Engine::ensure_capacity(int batch) {
   d_attn_ = (h16*)A((size_t)B * T * d * 2);
   d_ffn_ = (h16*)A((size_t)B * T * 4 * d * 2);
   d_enc_part_ = (float*)A((size_t)4 * kEncPartClips * T * d * 4);  // split-K partials of the encoder's residual GEMMs (few clips only)
-  d_cross_k_ = (h16*)A((size_t)L * B * H * t_pad_ * 64 * 2, true);
-  d_cross_v_ = (h16*)A((size_t)L * B * H * t_pad_ * 64 * 2, true);
-  d_self_k_ = (h16*)A((size_t)L * B * H * Tc * 64 * 2, true);
-  d_self_v_ = (h16*)A((size_t)L * B * H * Tc * 64 * 2, true);
+  d_cross_k_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(t_pad_) * 2, true);
+  d_cross_v_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(t_pad_) * 2, true);
+  d_self_k_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
+  d_self_v_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
   d_xdec_ = (float*)A((size_t)B * d * 4, true);
   d_a0_ = (float*)A((size_t)B * d * 4, true);
   d_statp_ = (float*)A((size_t)B * (d / 16 + 1) * 2 * 4, true);
@@ -580,15 +580,15 @@ void Engine::ensure_capacity(int batch) {
   d_hid_ = (float*)A((size_t)B * 4 * d * 4, true);
   nbs_ = (B + 15) / 16;
   for (int i = 0; i < 2; ++i) {  // fragment-major h16 (hi, lo) activation pairs of the batched (MFMA) decode path
-    d_act_[i] = (h16*)A((size_t)nbs_ * 16 * d * 2, true);
-    d_att_[i] = (h16*)A((size_t)nbs_ * 16 * d * 2, true);
-    d_hidp_[i] = (h16*)A((size_t)nbs_ * 16 * 4 * d * 2, true);
+    d_act_[i] = (h16*)A((size_t)layout::pair_elems(d / 32, nbs_) * 2, true);
+    d_att_[i] = (h16*)A((size_t)layout::pair_elems(d / 32, nbs_) * 2, true);
+    d_hidp_[i] = (h16*)A((size_t)layout::pair_elems(4 * d / 32, nbs_) * 2, true);
   }
   split_cross_ = B <= 2 ? 8 : 3;  // the VALU path serves <= 4 clips; larger batches use one split per (clip, head)
   split_self_ = 2;
   d_part_ = (float*)A((size_t)4 * B * d * 4, true);  // split-K partials of the batched residual GEMMs
-  d_part_self_ = (float*)A((size_t)B * H * split_self_ * 66 * 4, true);
-  d_part_cross_ = (float*)A((size_t)B * H * split_cross_ * 66 * 4, true);
+  d_part_self_ = (float*)A((size_t)layout::part_elems(B, H, split_self_) * 4, true);
+  d_part_cross_ = (float*)A((size_t)layout::part_elems(B, H, split_cross_) * 4, true);
   GemvParams lp{};
   lp.N = cfg_.n_vocab; lp.K = d;
   n_amax_part_ = std::max(gemv_grid(lp), decode_gemm_grid(cfg_.n_vocab, logits_rt()));
@@ -603,7 +603,7 @@ void Engine::ensure_capacity(int batch) {
   HIP_CHECK(hipHostMalloc((void**)&h_done_live_, (size_t)B * 4, hipHostMallocMapped));
   memset(h_done_live_, 0, (size_t)B * 4);
   HIP_CHECK(hipHostGetDevicePointer((void**)&d_done_live_, h_done_live_, 0));
-  d_attn_mpart_ = (float*)A((size_t)B * cfg_.n_text_head * kCrossSplitMax * 66 * 4, true);
+  d_attn_mpart_ = (float*)A((size_t)layout::part_elems(B, cfg_.n_text_head, layout::kAttnSplitMax) * 4, true);
   d_attn_mcnt_ = (unsigned*)A((size_t)B * cfg_.n_text_head * 4, true);  // zero: every launch leaves its tickets at zero
   d_nout_ = (int*)A((size_t)B * 4, true);
   d_max_new_clip_ = (int*)A((size_t)B * 4, true);
@@ -905,7 +905,7 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
   HIP_CHECK(hipSetDevice(device_));
   if (slot < 0 || slot >= cap_) throw std::runtime_error("slot out of range");
   const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, T = cfg_.n_audio_ctx;
-  const size_t per = (size_t)H * t_pad_ * 64;
+  const size_t head = (size_t)layout::kv_head_elems(t_pad_), per = H * head;
   std::vector<uint16_t> hk(per), hv(per);
   HIP_CHECK(hipStreamSynchronize(stream()));
   for (int l = 0; l < L; ++l) {
@@ -914,8 +914,8 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
     for (int h = 0; h < H; ++h)
       for (int t = 0; t < T; ++t)
         for (int c = 0; c < 64; ++c) {
-          const uint16_t kbits = hk[(size_t)h * t_pad_ * 64 + (size_t)(t >> 6) * 4096 + (c >> 3) * 512 + (t & 63) * 8 + (c & 7)];
-          const uint16_t vbits = hv[(size_t)h * t_pad_ * 64 + (size_t)t * 64 + c];
+          const uint16_t kbits = hk[h * head + layout::k_index(t, c)];
+          const uint16_t vbits = hv[h * head + layout::v_index(t, c)];
           const float kf = h16_bits_to_float(kbits), vf = h16_bits_to_float(vbits);
           k_out[((size_t)l * T + t) * d + h * 64 + c] = kf;
           v_out[((size_t)l * T + t) * d + h * 64 + c] = vf;

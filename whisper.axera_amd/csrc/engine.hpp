@@ -98,6 +98,8 @@ class Engine final : public IEngine {
   void enqueue_step_tail(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, int* d_argmax, int n_part,
                          hipStream_t s);
   void enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStream_t s, bool forced, bool one_branch);
+  // what every attention launch of a step has in common, for clips [b0, b0 + nb): n_keys < 0 self-attention, else cross-attention
+  DecAttnParams attn_params(const float* q, const h16* k, const h16* v, long stride, int n_keys, int cap_blocks, int b0, int nb, bool forced) const;
   int decode_branches(int batch) const;
   void ensure_branch_streams(int batch);
   // the captured step of spec.mode / spec.mask; a scored graph writes the engine's own score arrays (spec.score_out is not read)
@@ -191,7 +193,6 @@ class Engine final : public IEngine {
   h16 *d_mel_tm_ = nullptr, *d_h1_ = nullptr, *d_ln_ = nullptr, *d_q_ = nullptr, *d_k_ = nullptr, *d_vt_ = nullptr,
        *d_attn_ = nullptr, *d_ffn_ = nullptr;
   float* d_x_ = nullptr;
-  static constexpr int kCrossSplitMax = 6;  // workgroups per (clip, head) of the batched cross-attention launch at few clips
   static constexpr int kEncPartClips = 2;  // split-K of the encoder's residual GEMMs pays for at most this many clips
   float* d_enc_part_ = nullptr;
   bool enc_split_k_ = true;

@@ -48,15 +48,12 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
     }
   };
   auto attn = [&](const h16* kc, const h16* vc, long stride, int n_keys, int cap_blocks, float* part, int n_split) {
-    DecAttnParams a{};
-    a.q = d_qdec_; a.k = kc; a.v = vc; a.kv_batch_stride = stride; a.part = part; a.n_split = n_split;
-    a.batch = batch; a.n_head = H; a.d_model = d; a.n_keys = n_keys; a.cap_blocks = cap_blocks; a.state = d_state_;
-    a.off = d_off_;
-    a.done = d_forced ? d_done_none_ : d_done_;
+    DecAttnParams a = attn_params(d_qdec_, kc, vc, stride, n_keys, cap_blocks, 0, batch, d_forced != nullptr);
+    a.part = part; a.n_split = n_split;
     if (spec.mask & 2) launch_decode_attention(a, s);
   };
 
-  const long self_stride = (long)H * Tc * 64, cross_stride = (long)H * t_pad_ * 64;
+  const long self_stride = H * layout::kv_head_elems(Tc), cross_stride = H * layout::kv_head_elems(t_pad_);
   for (int l = 0; l < L; ++l) {
     const DecLayerW& w = dec_[l];
     h16* sk = d_self_k_ + (size_t)l * cap_ * self_stride;
@@ -76,7 +73,7 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
     p.W = w.w_o; p.bias = w.b_o; p.N = d; p.K = d;
     p.prologue = PRO_ATTN_COMBINE; p.part = d_part_self_; p.n_split = split_self_; p.n_head = H;
     p.epilogue = GEPI_RESID; p.out = d_xdec_; p.state = d_state_;
-    gemv(p, [&](GemvParams& q, int b0) { q.part += (long)b0 * H * split_self_ * 66; q.out += (long)b0 * d; });
+    gemv(p, [&](GemvParams& q, int b0) { q.part += layout::part_elems(b0, H, split_self_); q.out += (long)b0 * d; });
     // cross attention (export_onnx.py:221-230)
     p = GemvParams{};
     p.W = w.w_cq; p.bias = w.b_cq; p.N = d; p.K = d;
@@ -88,7 +85,7 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
     p.W = w.w_co; p.bias = w.b_co; p.N = d; p.K = d;
     p.prologue = PRO_ATTN_COMBINE; p.part = d_part_cross_; p.n_split = split_cross_; p.n_head = H;
     p.epilogue = GEPI_RESID; p.out = d_xdec_; p.state = d_state_;
-    gemv(p, [&](GemvParams& q, int b0) { q.part += (long)b0 * H * split_cross_ * 66; q.out += (long)b0 * d; });
+    gemv(p, [&](GemvParams& q, int b0) { q.part += layout::part_elems(b0, H, split_cross_); q.out += (long)b0 * d; });
     // mlp (export_onnx.py:298)
     p = GemvParams{};
     p.W = w.w_fc1; p.bias = w.b_fc1; p.N = 4 * d; p.K = d;
@@ -137,6 +134,16 @@ void Engine::enqueue_step_tail(const StepSpec& spec, int batch, int max_new, con
   if (spec.mask & 4) launch_advance(a, s);
 }
 
+DecAttnParams Engine::attn_params(const float* q, const h16* k, const h16* v, long stride, int n_keys, int cap_blocks, int b0, int nb,
+                                  bool forced) const {
+  DecAttnParams a{};
+  a.q = q; a.k = k; a.v = v; a.kv_batch_stride = stride; a.part = nullptr; a.n_split = 1;
+  a.batch = nb; a.n_head = cfg_.n_text_head; a.d_model = cfg_.n_text_state; a.n_keys = n_keys; a.cap_blocks = cap_blocks; a.state = d_state_;
+  a.off = d_off_ + b0;
+  a.done = (forced ? d_done_none_ : d_done_) + b0;  // (never null: the attention launches read the flag unconditionally)
+  return a;
+}
+
 // bench "attn_stamp" (StepSpec::mask bit 16): the next {min begin, max end} slot, with what the launch is
 unsigned long long* Engine::next_stamp(const StepSpec& spec, int layer, int cross, int b0, int nb) {
   if (!(spec.mask & 16) || !d_stamp_) return nullptr;
@@ -151,12 +158,11 @@ unsigned long long* Engine::next_stamp(const StepSpec& spec, int layer, int cros
 // partials). b0 is a multiple of 16: every per-clip buffer of the range starts at a whole clip block.
 void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStream_t s, bool forced, bool one_branch) {
   const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, Tc = cfg_.n_text_ctx;
-  const long self_stride = (long)H * Tc * 64, cross_stride = (long)H * t_pad_ * 64;
-  const long frag0 = (long)(b0 / 16) * 512;  // fragment-major pair layouts: clip blocks are 512 elements apart within a k-step
+  const long self_stride = H * layout::kv_head_elems(Tc), cross_stride = H * layout::kv_head_elems(t_pad_);
+  const long frag0 = layout::clip_block_offset(b0);  // fragment-major pair layouts: this range's first clip block within a k-step
   float* x = d_xdec_ + (long)b0 * d;
   float* qd = d_qdec_ + (long)b0 * d;
   h16 *att_hi = d_att_[0] + frag0, *att_lo = d_att_[1] + frag0, *hid_hi = d_hidp_[0] + frag0, *hid_lo = d_hidp_[1] + frag0;
-  const int* done = (forced ? d_done_none_ : d_done_) + b0;  // (never null: the attention launches read the flag unconditionally)
   auto cgemm = [&](const h16* W, const float* bias, int N, int K, int epi, int rt) {
     DecCGemmParams c{};
     c.W = W; c.bias = bias; c.N = N; c.K = K; c.batch = nb; c.nbs = nbs_; c.epilogue = epi; c.rt = rt;
@@ -176,8 +182,8 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
   {
     const int blocks = t_pad_ / 64;
     for (int c : {6, 4, 3, 2})
-      if (c <= kCrossSplitMax && blocks % c == 0 && nb * H * c <= std::max(n_cu_, 64)) { cross_split = c; break; }
-    if (cross_split_env_ > 0 && cross_split_env_ <= kCrossSplitMax && blocks % cross_split_env_ == 0) cross_split = cross_split_env_;
+      if (c <= layout::kAttnSplitMax && blocks % c == 0 && nb * H * c <= std::max(n_cu_, 64)) { cross_split = c; break; }
+    if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && blocks % cross_split_env_ == 0) cross_split = cross_split_env_;
   }
   // Folded query: a split repeats nothing but a 3 KB gather, so the grid is sized for whole waves of workgroups instead (three
   // 136-register workgroups per CU are resident): AX_WHISPER_CROSS_SPLIT_FOLD forces a count (sweeps)
@@ -185,7 +191,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
   {
     static const int env = [] { const char* e = getenv("AX_WHISPER_CROSS_SPLIT_FOLD"); return e ? atoi(e) : 0; }();
     const int blocks = t_pad_ / 64;
-    if (env > 0 && env <= kCrossSplitMax && blocks % env == 0) cross_split_fold = env;
+    if (env > 0 && env <= layout::kAttnSplitMax && blocks % env == 0) cross_split_fold = env;
   }
   static const int gemm_stamp_point = [] { const char* e = getenv("AX_WHISPER_GEMM_STAMP_POINT"); return e ? atoi(e) : 0; }();
   int cur_layer = 0;
@@ -195,11 +201,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
     if (spec.mask & 1) launch_decode_cgemm(c, s);
   };
   auto attn = [&](const h16* kc, const h16* vc, long stride, int n_keys, int cap_blocks) {
-    DecAttnParams a{};
-    a.q = qd; a.k = kc; a.v = vc; a.kv_batch_stride = stride; a.part = nullptr; a.n_split = 1;
-    a.batch = nb; a.n_head = H; a.d_model = d; a.n_keys = n_keys; a.cap_blocks = cap_blocks; a.state = d_state_;
-    a.off = d_off_ + b0;
-    a.done = done;
+    DecAttnParams a = attn_params(qd, kc, vc, stride, n_keys, cap_blocks, b0, nb, forced);
     a.done_late = one_branch ? 1 : 0;  // the step is ONE chain of dependent launches (decoder.hip); tail branches of a multi-branch step keep the early check
     a.out_hi = att_hi; a.out_lo = att_lo; a.nbs = nbs_;
     return a;
@@ -240,7 +242,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
       DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64);
       a.q = nullptr;
       a.n_split = cross_split_fold;
-      a.mpart = d_attn_mpart_ + (long)b0 * H * kCrossSplitMax * 66;
+      a.mpart = d_attn_mpart_ + layout::part_elems(b0, H, layout::kAttnSplitMax);
       a.mcnt = d_attn_mcnt_ + (long)b0 * H;
       a.tq = a0; a.stat_part = statp; a.fold_s = cfold_[l].s; a.fold_c = cfold_[l].c;
       a.stamp = next_stamp(spec, l, 1, b0, nb);
@@ -249,7 +251,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
       DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64);
       a.q = nullptr;
       a.n_split = cross_split;
-      a.mpart = d_attn_mpart_ + (long)b0 * H * kCrossSplitMax * 66;
+      a.mpart = d_attn_mpart_ + layout::part_elems(b0, H, layout::kAttnSplitMax);
       a.mcnt = d_attn_mcnt_ + (long)b0 * H;
       a.x = x; a.ln_w = w.cross_ln_w; a.ln_b = w.cross_ln_b; a.wq = w.w_cq; a.bq = w.b_cq;
       a.stamp = next_stamp(spec, l, 1, b0, nb);
@@ -305,14 +307,14 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
                                          long logits_stride, int* d_argmax) {
   const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, Tc = cfg_.n_text_ctx;
   hipStream_t s = stream();
-  const long self_stride = (long)H * Tc * 64, cross_stride = (long)H * t_pad_ * 64;
+  const long self_stride = H * layout::kv_head_elems(Tc), cross_stride = H * layout::kv_head_elems(t_pad_);
 
   auto gemm = [&](DecGemmParams p, auto&& offset) {
     for (int b0 = 0; b0 < batch; b0 += 64) {
       DecGemmParams q = p;
       q.batch = std::min(64, batch - b0);
-      q.a_hi += (long)(b0 / 16) * 512;  // fragment-major: clip blocks are 512 elements apart within a k-step
-      q.a_lo += (long)(b0 / 16) * 512;
+      q.a_hi += layout::clip_block_offset(b0);  // fragment-major: this launch's first clip block within a k-step
+      q.a_lo += layout::clip_block_offset(b0);
       q.nbs = nbs_;
       q.off = d_off_ + b0;
       offset(q, b0);
@@ -343,17 +345,13 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
   };
   int stamp_layer = 0;
   auto attn = [&](const h16* kc, const h16* vc, long stride, int n_keys, int cap_blocks) {
-    DecAttnParams a{};
-    a.q = d_qdec_; a.k = kc; a.v = vc; a.kv_batch_stride = stride; a.part = nullptr; a.n_split = 1;
-    a.batch = batch; a.n_head = H; a.d_model = d; a.n_keys = n_keys; a.cap_blocks = cap_blocks; a.state = d_state_;
-    a.off = d_off_;
-    a.done = d_forced ? d_done_none_ : d_done_;
+    DecAttnParams a = attn_params(d_qdec_, kc, vc, stride, n_keys, cap_blocks, 0, batch, d_forced != nullptr);
     a.out_hi = d_att_[0]; a.out_lo = d_att_[1]; a.nbs = nbs_;
     if (n_keys >= 0) {  // cross-attention: few (clip, head) pairs leave CUs with one workgroup beside CUs with two (turbo, 16 clips: 320)
       int c = 1;
       for (int k : {6, 4, 3, 2})
-        if (k <= kCrossSplitMax && cap_blocks % k == 0 && batch * H * k <= 640) { c = k; break; }
-      if (cross_split_env_ > 0 && cross_split_env_ <= kCrossSplitMax && cap_blocks % cross_split_env_ == 0) c = cross_split_env_;
+        if (k <= layout::kAttnSplitMax && cap_blocks % k == 0 && batch * H * k <= 640) { c = k; break; }
+      if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && cap_blocks % cross_split_env_ == 0) c = cross_split_env_;
       a.n_split = c;
       a.mpart = d_attn_mpart_;
       a.mcnt = d_attn_mcnt_;
@@ -415,7 +413,7 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     ln(w.mlp_ln_w, w.mlp_ln_b);
     p = base(wp.w_fc1, w.b_fc1, 4 * d, d, d_act_[0], d_act_[1], GEPI_GELU);
     p.out_hi = d_hidp_[0]; p.out_lo = d_hidp_[1];
-    gemm(p, [&](DecGemmParams& q, int b0) { q.out_hi += (long)(b0 / 16) * 512; q.out_lo += (long)(b0 / 16) * 512; });
+    gemm(p, [&](DecGemmParams& q, int b0) { q.out_hi += layout::clip_block_offset(b0); q.out_lo += layout::clip_block_offset(b0); });
     resid(wp.w_fc2, w.b_fc2, 4 * d, d_hidp_[0], d_hidp_[1]);
   }
   ln(dec_ln_w_, dec_ln_b_);
@@ -612,9 +610,9 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
   p.wl = dec_w_arena_; p.fl = dec_f_arena_;
   p.qf = d_qfold_;
   p.tok_emb = tok_emb_; p.pos = dec_pos_; p.ln_w = dec_ln_w_; p.ln_b = dec_ln_b_;
-  p.cross_k = d_cross_k_ + (size_t)slot * H * t_pad_ * 64;  // this clip's slot, layer 0
-  p.cross_v = d_cross_v_ + (size_t)slot * H * t_pad_ * 64;
-  p.cross_layer_stride = (long)cap_ * H * t_pad_ * 64;
+  p.cross_k = d_cross_k_ + (size_t)slot * H * layout::kv_head_elems(t_pad_);  // this clip's slot, layer 0
+  p.cross_v = d_cross_v_ + (size_t)slot * H * layout::kv_head_elems(t_pad_);
+  p.cross_layer_stride = (long)cap_ * H * layout::kv_head_elems(t_pad_);
   p.n_layer = cfg_.n_text_layer; p.n_vocab = cfg_.n_vocab; p.n_ctx = Tc; p.n_audio_ctx = cfg_.n_audio_ctx;
   p.eot = cfg_.eot; p.max_new = max_new;
   p.total_steps = d_forced || d_logits || d_argmax ? 4 + n_forced : std::min(Tc, 4 + std::max(max_new, std::max(max_new1, max_new2)));
@@ -622,7 +620,7 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
   if (max_new1 >= 0) {
     p.n_clip = max_new2 >= 0 ? 3 : 2;
     if (persist_max_clips_ < p.n_clip || d_forced || d_logits || d_argmax || slot + p.n_clip > cap_) throw std::runtime_error("run_persistent: that many clips are unsupported here");
-    p.cross_clip_stride = (long)H * t_pad_ * 64;
+    p.cross_clip_stride = H * layout::kv_head_elems(t_pad_);
     p.self_k1 = d_self_k1_; p.self_v1 = d_self_v1_;
     p.gran_clip_u64 = (long)(gran_bytes_ / 8);
     p.out_ids1 = d_out_ids_ + (size_t)(slot + 1) * Tc; p.n_out1 = d_nout_ + slot + 1; p.max_new1 = max_new1;

@@ -190,11 +190,11 @@ int Engine::scan_stored16(int batch, int n_max, char (*names)[32], long long* no
       {"enc.mel", d_mel_tm_, B * mel_rows_ * cfg_.n_mels}, {"enc.conv1", d_h1_, B * h1_rows_ * d}, {"enc.ln", d_ln_, B * T * d},
       {"enc.q", d_q_, B * T * d}, {"enc.k", d_k_, B * T * d}, {"enc.vt", d_vt_, B * d * t_pad_}, {"enc.attn", d_attn_, B * T * d},
       {"enc.ffn_hidden", d_ffn_, B * T * 4 * d},
-      {"cross_k", d_cross_k_, L * (size_t)cap_ * H * t_pad_ * 64}, {"cross_v", d_cross_v_, L * (size_t)cap_ * H * t_pad_ * 64},
-      {"self_k", d_self_k_, L * (size_t)cap_ * H * Tc * 64}, {"self_v", d_self_v_, L * (size_t)cap_ * H * Tc * 64},
-      {"dec.act_hi", d_act_[0], (size_t)nbs_ * 16 * d}, {"dec.act_lo", d_act_[1], (size_t)nbs_ * 16 * d},
-      {"dec.att_hi", d_att_[0], (size_t)nbs_ * 16 * d}, {"dec.att_lo", d_att_[1], (size_t)nbs_ * 16 * d},
-      {"dec.hid_hi", d_hidp_[0], (size_t)nbs_ * 16 * 4 * d}, {"dec.hid_lo", d_hidp_[1], (size_t)nbs_ * 16 * 4 * d},
+      {"cross_k", d_cross_k_, L * (size_t)cap_ * H * layout::kv_head_elems(t_pad_)}, {"cross_v", d_cross_v_, L * (size_t)cap_ * H * layout::kv_head_elems(t_pad_)},
+      {"self_k", d_self_k_, L * (size_t)cap_ * H * layout::kv_head_elems(Tc)}, {"self_v", d_self_v_, L * (size_t)cap_ * H * layout::kv_head_elems(Tc)},
+      {"dec.act_hi", d_act_[0], (size_t)layout::pair_elems(d / 32, nbs_)}, {"dec.act_lo", d_act_[1], (size_t)layout::pair_elems(d / 32, nbs_)},
+      {"dec.att_hi", d_att_[0], (size_t)layout::pair_elems(d / 32, nbs_)}, {"dec.att_lo", d_att_[1], (size_t)layout::pair_elems(d / 32, nbs_)},
+      {"dec.hid_hi", d_hidp_[0], (size_t)layout::pair_elems(4 * d / 32, nbs_)}, {"dec.hid_lo", d_hidp_[1], (size_t)layout::pair_elems(4 * d / 32, nbs_)},
   };
   if (d_self_k1_) {
     bufs.push_back({"persist.self_k1", d_self_k1_, self1_bytes_ / 2 * (size_t)std::max(persist_max_clips_ - 1, 1)});

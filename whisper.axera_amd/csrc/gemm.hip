@@ -115,7 +115,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmParams& p, const float* 
           const int nv = n8 - p.n_layer * d;
           const int l = nv / d, c = nv - l * d;
           const long slot = ((long)l * p.n_batch_total + (p.kv_slot_map ? p.kv_slot_map[bz] : bz)) * (d >> 6) + (c >> 6);
-          dst = reinterpret_cast<h16*>(p.C2) + (slot * p.t_pad + m) * 64 + (c & 63);
+          dst = reinterpret_cast<h16*>(p.C2) + slot * layout::kv_head_elems(p.t_pad) + layout::v_index(m, c & 63);
         } else {
           dst = reinterpret_cast<h16*>(p.C) + (long)bz * p.c_batch_stride + (long)m * p.ldc + n8;
         }
@@ -188,7 +188,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&accw
 #pragma unroll
           for (int e = 0; e < 4; ++e) pk[e] = (h16)(acc[i][j][4 * q + e] + (p.bias ? p.bias[n + e] : 0.f));
           const long slot = ((long)l * p.n_batch_total + (p.kv_slot_map ? p.kv_slot_map[bz] : bz)) * (d >> 6) + head;
-          h16* dst = reinterpret_cast<h16*>(p.C) + slot * p.t_pad * 64 + (long)(m >> 6) * 4096 + (dd >> 3) * 512 + (m & 63) * 8 + (dd & 7);
+          h16* dst = reinterpret_cast<h16*>(p.C) + slot * layout::kv_head_elems(p.t_pad) + layout::k_index(m, dd);
           *reinterpret_cast<h16x4*>(dst) = pk;
         }
       }
@@ -472,7 +472,7 @@ __device__ __forceinline__ void gemm_epilogue16(const GemmParams& p, f32x4 (&acc
 #pragma unroll
           for (int e = 0; e < 4; ++e) pk[e] = (h16)(acc[nj][it][jt][e] + (p.bias ? p.bias[n + e] : 0.f));
           const long slot = ((long)l * p.n_batch_total + (p.kv_slot_map ? p.kv_slot_map[bz] : bz)) * (d >> 6) + head;
-          h16* dst = reinterpret_cast<h16*>(p.C) + slot * p.t_pad * 64 + (long)(m >> 6) * 4096 + (dd >> 3) * 512 + (m & 63) * 8 + (dd & 7);
+          h16* dst = reinterpret_cast<h16*>(p.C) + slot * layout::kv_head_elems(p.t_pad) + layout::k_index(m, dd);
           *reinterpret_cast<h16x4*>(dst) = pk;
         }
     }
