@@ -1,6 +1,8 @@
-// Runs the batched decoder step's kernels that go into libax_whisper.so one launch at a time, for tests/test_gpu_decode_kernels.py.
+// Runs the decoder step's kernels that go into libax_whisper.so one launch at a time, for tests/test_gpu_decode_kernels.py (the
+// batched step) and tests/test_gpu_gemv_kernels.py (the GEMV family, advance, embed).
 // Host-only code, built twice (-DAXW_F16=0 / 1) and linked against the objects `make` produced (build/decode_gemm.{bf16,f16}.o,
-// build/decoder.{bf16,f16}.o): the library has hidden visibility, and a recompilation would not be the shipped code.
+// build/decoder.{bf16,f16}.o, build/decode_gemv.{bf16,f16}.o): the library has hidden visibility, and a recompilation would not be
+// the shipped code.
 //
 //   decode_kernels_driver <manifest>        one command per line, executed in order (the manifest language of
 //                                           encoder_kernels_driver.cpp):
@@ -15,6 +17,9 @@
 //     attn ID key=value ...       one launch_decode_attention (DecAttnParams)
 //     packw ID key=value ...      one launch_pack_weight_frag
 //     packw_split ID key=value .. one launch_pack_weight_frag_split
+//     gemv ID key=value ...       one launch_gemv (GemvParams; `state` is not read by the kernels and stays null)
+//     advance ID key=value ...    one launch_advance (AdvanceParams; done_host may be an ordinary device buffer)
+//     embed ID key=value ...      one launch_embed (tok_emb, pos, tok, off, x, batch, d; n_vocab and n_ctx size the tables)
 //   every launch prints "ran ID gx gy gz" with the grid it started.
 // Keys carry the names of the parameter structs' fields; a pointer field names a buffer. Every launch is checked against the sizes of
 // the buffers it names (and the clip offsets a kernel would index a cache with) before it runs, and synchronised and checked for
@@ -79,6 +84,130 @@ static void check_cache(const KV& kv, long batch, long d, long n_ctx_pad, long k
   for (long b = 0; b < batch; ++b) if (ho[b] < 0 || ho[b] >= n_ctx_pad) die("clip offset outside the cache");
 }
 
+// launch_gemv's choice of lanes per weight row (decode_gemv.hip pick_lpr), to know the instantiation a launch would ask for
+static int gemv_lpr(long K) {
+  if (K % 512 == 0 && K / 512 <= 10 && K >= 1024) return 64;
+  if (K % 256 == 0 && K / 256 <= 6) return 32;
+  if (K % 128 == 0 && K / 128 <= 10) return 16;
+  return 0;
+}
+
+static long run_gemv(const KV& kv) {
+  GemvParams p{};
+  p.N = (int)num(kv, "N"); p.K = (int)num(kv, "K"); p.batch = (int)num(kv, "batch"); p.prologue = (int)num(kv, "prologue"); p.epilogue = (int)num(kv, "epilogue");
+  p.n_split = (int)num(kv, "n_split"); p.n_head = (int)num(kv, "n_head"); p.d_model = (int)num(kv, "d_model"); p.n_ctx_pad = (int)num(kv, "n_ctx_pad");
+  p.kv_batch_stride = num(kv, "kv_batch_stride"); p.amax_stride = (int)num(kv, "amax_stride"); p.logits_dump_stride = num(kv, "logits_dump_stride");
+  p.skip_before_step = (int)num(kv, "skip_before_step");
+  const long N = p.N, K = p.K, B = p.batch, d = p.d_model;
+  if (N < 1 || K < 128 || B < 1) die("bad gemv shape");
+  if (B > 4) die("gemv: at most 4 clips per launch");
+  const int lpr = gemv_lpr(K);
+  const long ch = lpr ? K / (8 * lpr) : 0;
+  if (!lpr || !(ch == 1 || ch == 2 || ch == 3 || ch == 4 || ch == 5 || ch == 6 || ch == 8 || ch == 10)) die("gemv: no instantiation for this K");
+  const long grid = gemv_grid(p);
+  if (grid < 1) die("gemv: no grid");
+  p.W = (const h16*)need(kv, "W", 2, N * K);
+  p.bias = (const float*)ptr(kv, "bias", 4, N);
+  switch (p.prologue) {
+    case PRO_PLAIN: p.in = (const float*)need(kv, "in", 4, B * K); break;
+    case PRO_LAYERNORM:
+      if (B > 1 && K > 2048) die("LayerNorm prologue of gemv_kernel: K > 2048");
+      p.in = (const float*)need(kv, "in", 4, B * K);
+      p.ln_w = (const float*)need(kv, "ln_w", 4, K);
+      p.ln_b = (const float*)need(kv, "ln_b", 4, K);
+      break;
+    case PRO_ATTN_COMBINE:
+      if (p.n_head < 1 || K != (long)p.n_head * 64) die("attention combine: K is 64 n_head");
+      if (p.n_split < 1) die("attention combine: n_split < 1");
+      if (p.n_split > 8) die("attention combine: n_split > 8");
+      p.part = (const float*)need(kv, "part", 4, layout::part_elems(B, p.n_head, p.n_split));
+      break;
+    default: die("unknown gemv prologue");
+  }
+  switch (p.epilogue) {
+    case GEPI_STORE: case GEPI_GELU: case GEPI_RESID: p.out = (float*)need(kv, "out", 4, B * N); break;
+    case GEPI_QKV_CACHE:
+      if (N != 3 * d) die("QKV_CACHE: N is 3 d_model");
+      p.out = (float*)need(kv, "out", 4, B * d);
+      check_cache(kv, B, d, p.n_ctx_pad, p.kv_batch_stride, p.k_cache, p.v_cache, p.off);
+      break;
+    case GEPI_LOGITS:
+      if (p.amax_stride < grid) die("amax_stride below the grid");
+      p.off = (const int*)need(kv, "off", 4, B);
+      p.amax_val = (float*)need(kv, "amax_val", 4, (B - 1) * p.amax_stride + grid);
+      p.amax_idx = (int*)need(kv, "amax_idx", 4, (B - 1) * p.amax_stride + grid);
+      if (has(kv, "logits_dump")) {
+        if (p.logits_dump_stride < N) die("logits_dump_stride below N");
+        p.logits_dump = (float*)need(kv, "logits_dump", 4, (B - 1) * p.logits_dump_stride + N);
+      }
+      break;
+    default: die("unknown gemv epilogue");
+  }
+  launch_gemv(p, nullptr);
+  return grid;
+}
+
+static void ids_below(const KV& kv, const char* k, long count, long limit, const char* what) {
+  const int* h = host_ints(kv, k);
+  for (long i = 0; i < count; ++i) if (h[i] < 0 || h[i] >= limit) die(std::string(what) + " outside its table (" + k + ")");
+}
+
+static long run_advance(const KV& kv) {
+  AdvanceParams p{};
+  p.n_part = (int)num(kv, "n_part"); p.amax_stride = (int)num(kv, "amax_stride"); p.batch = (int)num(kv, "batch"); p.n_ctx = (int)num(kv, "n_ctx");
+  p.eot = (int)num(kv, "eot"); p.max_new = (int)num(kv, "max_new"); p.n_vocab = (int)num(kv, "n_vocab"); p.n_forced = (int)num(kv, "n_forced");
+  p.d_model = (int)num(kv, "d_model"); p.n_prefix = (int)num(kv, "n_prefix");
+  const long B = p.batch, d = p.d_model, V = p.n_vocab, T = p.n_ctx;
+  if (B < 1 || T < 1 || V < 1 || p.n_part < 0 || p.n_prefix < 0 || p.n_forced < 0) die("bad advance shape");
+  if (d < 4 || d > 2048 || d % 4) die("advance: d_model above 2048 or no multiple of 4");
+  if (p.n_part > p.amax_stride) die("advance: n_part above amax_stride");
+  const long n_pre = p.n_prefix > 0 ? p.n_prefix : 4;
+  p.amax_val = (const float*)need(kv, "amax_val", 4, (B - 1) * p.amax_stride + p.n_part);
+  p.amax_idx = (const int*)need(kv, "amax_idx", 4, (B - 1) * p.amax_stride + p.n_part);
+  p.state = (DecState*)need(kv, "state", sizeof(DecState), 1);
+  p.off = (int*)need(kv, "off", 4, B);
+  p.tok = (int*)need(kv, "tok", 4, B);
+  p.sot = (const int*)need(kv, "sot", 4, n_pre);
+  p.tok_emb = (const h16*)need(kv, "tok_emb", 2, V * d);
+  p.pos = (const float*)need(kv, "pos", 4, T * d);
+  p.x = (float*)need(kv, "x", 4, B * d);
+  ids_below(kv, "off", B, T, "clip offset");
+  ids_below(kv, "tok", B, V, "token");
+  ids_below(kv, "sot", n_pre, V, "prefix token");
+  if (has(kv, "forced")) {
+    if (p.n_forced < 1) die("advance: forced without n_forced");
+    p.forced = (const int*)need(kv, "forced", 4, B * p.n_forced);
+    ids_below(kv, "forced", B * p.n_forced, V, "forced token");
+    p.done = (int*)ptr(kv, "done", 4, B);
+    p.n_out = (int*)ptr(kv, "n_out", 4, B);
+    p.out_ids = (int*)ptr(kv, "out_ids", 4, B * T);
+  } else {
+    p.done = (int*)need(kv, "done", 4, B);
+    p.n_out = (int*)need(kv, "n_out", 4, B);
+    p.out_ids = (int*)need(kv, "out_ids", 4, B * T);
+    ids_below(kv, "n_out", B, T, "id count");
+  }
+  if (has(kv, "argmax_dump")) p.argmax_dump = (int*)need(kv, "argmax_dump", 4, B * (p.n_forced + 1));
+  p.max_new_clip = (const int*)ptr(kv, "max_new_clip", 4, B);
+  p.done_host = (int*)ptr(kv, "done_host", 4, B);
+  launch_advance(p, nullptr);
+  return (B + 15) / 16;
+}
+
+static long run_embed(const KV& kv) {
+  const long B = num(kv, "batch"), d = num(kv, "d"), V = num(kv, "n_vocab"), T = num(kv, "n_ctx");
+  if (B < 1 || d < 1 || V < 1 || T < 1) die("bad embed shape");
+  const h16* te = (const h16*)need(kv, "tok_emb", 2, V * d);
+  const float* pos = (const float*)need(kv, "pos", 4, T * d);
+  const int* tok = (const int*)need(kv, "tok", 4, B);
+  const int* off = (const int*)need(kv, "off", 4, B);
+  float* x = (float*)need(kv, "x", 4, B * d);
+  ids_below(kv, "tok", B, V, "token");
+  ids_below(kv, "off", B, T, "clip offset");
+  launch_embed(te, pos, tok, off, x, (int)B, (int)d, nullptr);
+  return B;
+}
+
 int main(int argc, char** argv) {
   if (argc != 2) die("usage: decode_kernels_driver <manifest>");
   std::ifstream mf(argv[1]);
@@ -127,7 +256,8 @@ int main(int argc, char** argv) {
     } else if (cmd == "free") {
       CK(hipFree(buf(a).dev));
       bufs.erase(a);
-    } else if (cmd == "cgemm" || cmd == "dgemm" || cmd == "actprep" || cmd == "attn" || cmd == "packw" || cmd == "packw_split") {
+    } else if (cmd == "cgemm" || cmd == "dgemm" || cmd == "actprep" || cmd == "attn" || cmd == "packw" || cmd == "packw_split" || cmd == "gemv" ||
+               cmd == "advance" || cmd == "embed") {
       KV kv;
       while (ls >> tok) {
         const size_t eq = tok.find('=');
@@ -135,7 +265,13 @@ int main(int argc, char** argv) {
         kv[tok.substr(0, eq)] = tok.substr(eq + 1);
       }
       long gx = 1, gy = 1, gz = 1;
-      if (cmd == "cgemm") {
+      if (cmd == "gemv") {
+        gx = run_gemv(kv);
+      } else if (cmd == "advance") {
+        gx = run_advance(kv);
+      } else if (cmd == "embed") {
+        gx = run_embed(kv);
+      } else if (cmd == "cgemm") {
         DecCGemmParams p{};
         p.N = (int)num(kv, "N"); p.K = (int)num(kv, "K"); p.batch = (int)num(kv, "batch"); p.nbs = (int)num(kv, "nbs");
         p.epilogue = (int)num(kv, "epilogue"); p.rt = (int)num(kv, "rt", 1); p.d_model = (int)num(kv, "d_model");

@@ -19,52 +19,26 @@ still to be filled in here and in DESIGN.md. What is known without a GPU: the dr
 whole file passes when the driver process is replaced by the float32 emulations of tests/test_decode_kernel_reference.py (138
 tests; the modelgen-like residual family gives |g . x0| <= 257, a headroom of 255 x to half's 65504).
 """
-import os
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
 import decode_kernel_reference as R
+import kernel_driver
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "whisper.axera_amd")
-BUILD = os.path.join(PKG, "build")
-HIPCC = "/opt/rocm/bin/hipcc"
-DTYPES = ("bf16", "f16")
+DTYPES = kernel_driver.DTYPES
 
-_state = {"dead": None, "t0": time.time()}
-_ran = {dt: set() for dt in DTYPES}
-_worst = {}
+_session = kernel_driver.Session()
+_ran, _worst, _state = _session.ran, _session.worst, _session.state
 _facts = {}
-
-
-def _driver_exe(dt):
-    """build/decode_kernels_driver.<dt>, relinked whenever it is older than its source or the objects it links."""
-    exe = os.path.join(BUILD, "decode_kernels_driver." + dt)
-    src = os.path.join(ROOT, "tests", "cpp", "decode_kernels_driver.cpp")
-    objs = [os.path.join(BUILD, f"{k}.{dt}.o") for k in ("decode_gemm", "decoder")]
-    srcs = [src] + [os.path.join(PKG, "csrc", f) for f in ("decode_gemm.hip", "decoder.hip", "common.hpp", "decode_layout.hpp")]
-    newest = max(os.path.getmtime(f) for f in srcs + [o for o in objs if os.path.exists(o)])
-    if os.path.exists(exe) and os.path.getmtime(exe) >= newest:
-        return exe
-    r = subprocess.run(["make", "-C", PKG, "-j16"] + [os.path.relpath(o, PKG) for o in objs], capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    obj = exe + ".o"
-    for cmd in ([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-DAXW_F16=" + ("1" if dt == "f16" else "0"),
-                 "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-c", src, "-o", obj],
-                [HIPCC, "--offload-arch=gfx950", obj] + objs + ["-o", exe]):
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-    return exe
 
 
 @pytest.fixture(scope="module", params=DTYPES)
 def driver(request):
-    return request.param, _driver_exe(request.param)
+    return request.param, kernel_driver.driver_exe(request.param)
 
 
 def form_of(cmd, p, qall=None):
@@ -99,60 +73,7 @@ def grid_of(cmd, p):
 
 
 def run_groups(driver, tmp_path, groups, timeout=120, qall=None, keep=None):
-    """One driver process for all groups; every launch checked against what its predecessors left. Returns the notes."""
-    dt, exe = driver
-    if _state["dead"]:
-        pytest.fail("not run: an earlier driver run failed (" + _state["dead"] + ")")
-    tmp = str(tmp_path)
-    lines, n = [], 0
-    for gi, (bufs, launches) in enumerate(groups):
-        for name, content in bufs.items():
-            n += 1
-            f = os.path.join(tmp, f"in{n}.bin")
-            np.ascontiguousarray(content).tofile(f)
-            lines.append(f"alloc {name} {np.ascontiguousarray(content).nbytes} {f}")
-        for li, (cmd, ident, p, outs) in enumerate(launches):
-            lines.append(f"{cmd} {ident} " + " ".join(f"{k}={v}" for k, v in p.items()))
-            lines += [f"dump {o} {os.path.join(tmp, f'g{gi}.l{li}.{o}')}" for o in outs]
-        lines += [f"free {name}" for name in bufs]
-    mf = os.path.join(tmp, "manifest.txt")
-    with open(mf, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    env = dict(os.environ)
-    env.pop("AX_WHISPER_ATTN_QALL", None)
-    if qall is not None:
-        env["AX_WHISPER_ATTN_QALL"] = qall
-    try:
-        r = subprocess.run([exe, mf], capture_output=True, text=True, timeout=timeout, env=env)
-    except subprocess.TimeoutExpired:
-        _state["dead"] = "timeout"
-        raise
-    if r.returncode != 0 or not r.stdout.rstrip().endswith("done"):
-        _state["dead"] = f"exit status {r.returncode}"
-        pytest.fail(f"driver exit status {r.returncode}\n{r.stdout[-1500:]}\n{r.stderr[-1500:]}")
-    grids = {ln.split()[1]: tuple(int(v) for v in ln.split()[2:5]) for ln in r.stdout.splitlines() if ln.startswith("ran ")}
-    notes = {}
-    for gi, (bufs, launches) in enumerate(groups):
-        state, prev = dict(bufs), None
-        for li, (cmd, ident, p, outs) in enumerate(launches):
-            assert grids[ident] == grid_of(cmd, p), (ident, grids[ident])
-            got = {}
-            for o in outs:
-                f = os.path.join(tmp, f"g{gi}.l{li}.{o}")
-                got[o] = np.fromfile(f, dtype=np.uint16)
-                os.remove(f)
-            for what, w in R.verify(cmd, ident, p, state, got, dt, prev).items():
-                notes[what] = max(notes.get(what, 0.0), w)
-                _worst[dt, what] = max(_worst.get((dt, what), 0.0), w)
-            _ran[dt].add(form_of(cmd, p, qall))
-            if keep is not None:
-                keep[ident] = got
-            prev = got
-            for o in outs:
-                state[o] = R.strip(ident, got[o])
-    for what, w in sorted(notes.items()):
-        print(f"{dt} {what}: worst error / bound {w:.3f}")
-    return notes
+    return kernel_driver.run_groups(_session, R.verify, form_of, grid_of, driver, tmp_path, groups, timeout=timeout, qall=qall, keep=keep)
 
 
 OFFS8 = (0, 7, 63, 64, 65, 127, 128, 447)

@@ -9,7 +9,7 @@
 //   1. every lane issues the 16-byte weight loads of its first row BEFORE the prologue, so the HBM round
 //      trip overlaps the activation work;
 //   2. prologue builds the activation rows in LDS with all 256 threads: LayerNorm of the residual stream
-//      (single read, shifted one-pass variance, one block reduction), or the merge of the attention split
+//      (single read, mean and centred squares from registers: two block reductions), or the merge of the attention split
 //      partials, or a plain copy;
 //   3. LPR lanes share a weight row (LPR*16 contiguous bytes per load instruction, full cache lines), each
 //      lane owns CH chunks; the next row's loads are issued before the current row is reduced;
@@ -28,42 +28,59 @@ __device__ __forceinline__ void prologue_layernorm(const GemvParams& p, float* a
   const int K = p.K;
   constexpr int MAXE = 8;  // K <= 2048
   float v[BT][MAXE], g[MAXE], be[MAXE];
-  float s1[BT], s2[BT], shift[BT];
+  float s1[BT], s2[BT], mean[BT];
   // every global load of the prologue is issued here, before the first reduction
-#pragma unroll
-  for (int b = 0; b < BT; ++b) shift[b] = b < p.batch ? p.in[(long)b * K] : 0.f;
 #pragma unroll
   for (int e = 0; e < MAXE; ++e) {
     const int c = tid + 256 * e;
     g[e] = c < K ? p.ln_w[c] : 0.f;
     be[e] = c < K ? p.ln_b[c] : 0.f;
 #pragma unroll
-    for (int b = 0; b < BT; ++b) v[b][e] = (c < K && b < p.batch) ? p.in[(long)b * K + c] : shift[b];
+    for (int b = 0; b < BT; ++b) v[b][e] = (c < K && b < p.batch) ? p.in[(long)b * K + c] : 0.f;
   }
+  // two passes over the registers: the mean, then the squares of the CENTRED values (no cancellation whatever channel holds
+  // what; a shifted one-pass variance is only as good as its shift, and x[b][0] may be the row's outlier channel)
 #pragma unroll
-  for (int b = 0; b < BT; ++b) {  // shifted one-pass variance: no cancellation for data near `shift`
-    s1[b] = 0.f; s2[b] = 0.f;
+  for (int b = 0; b < BT; ++b) {
+    s1[b] = 0.f;
 #pragma unroll
-    for (int e = 0; e < MAXE; ++e) { const float t = v[b][e] - shift[b]; s1[b] += t; s2[b] += t * t; }
-    s1[b] = wave_sum(s1[b]); s2[b] = wave_sum(s2[b]);
+    for (int e = 0; e < MAXE; ++e) s1[b] += v[b][e];
+    s1[b] = wave_sum(s1[b]);
   }
   if (lane == 0) {
 #pragma unroll
-    for (int b = 0; b < BT; ++b) { red[(wave * BT + b) * 2] = s1[b]; red[(wave * BT + b) * 2 + 1] = s2[b]; }
+    for (int b = 0; b < BT; ++b) red[(wave * BT + b) * 2] = s1[b];
   }
   __syncthreads();
 #pragma unroll
   for (int b = 0; b < BT; ++b) {
-    float t1 = 0.f, t2 = 0.f;
+    float t1 = 0.f;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) { t1 += red[(w * BT + b) * 2]; t2 += red[(w * BT + b) * 2 + 1]; }
-    const float dm = t1 / K;  // mean - shift
-    const float var = fmaxf(t2 / K - dm * dm, 0.f);
-    const float mean = shift[b] + dm, rstd = rsqrtf(var + 1e-5f);
+    for (int w = 0; w < 4; ++w) t1 += red[(w * BT + b) * 2];
+    mean[b] = t1 / K;
+    s2[b] = 0.f;
+#pragma unroll
+    for (int e = 0; e < MAXE; ++e) {
+      const float t = tid + 256 * e < K ? v[b][e] - mean[b] : 0.f;
+      s2[b] += t * t;
+    }
+    s2[b] = wave_sum(s2[b]);
+  }
+  if (lane == 0) {  // the odd slots: nobody reads them before the barrier below, nobody writes the even ones after the one above
+#pragma unroll
+    for (int b = 0; b < BT; ++b) red[(wave * BT + b) * 2 + 1] = s2[b];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < BT; ++b) {
+    float t2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) t2 += red[(w * BT + b) * 2 + 1];
+    const float rstd = rsqrtf(t2 / K + 1e-5f);
 #pragma unroll
     for (int e = 0; e < MAXE; ++e) {
       const int c = tid + 256 * e;
-      if (c < K) act[b * K + c] = b < p.batch ? (v[b][e] - mean) * rstd * g[e] + be[e] : 0.f;
+      if (c < K) act[b * K + c] = b < p.batch ? (v[b][e] - mean[b]) * rstd * g[e] + be[e] : 0.f;
     }
   }
 }
@@ -284,7 +301,6 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvParams p, int rows_per_w
   float a[CH][8];
   if constexpr (PRO == PRO_LAYERNORM) {
     float g[CH][8], be[CH][8];
-    const float shift = p.in[0];
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c8 = (j + LPR * i) * 8;
@@ -295,15 +311,23 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvParams p, int rows_per_w
       g[i][0] = g0.x; g[i][1] = g0.y; g[i][2] = g0.z; g[i][3] = g0.w; g[i][4] = g1.x; g[i][5] = g1.y; g[i][6] = g1.z; g[i][7] = g1.w;
       be[i][0] = b0.x; be[i][1] = b0.y; be[i][2] = b0.z; be[i][3] = b0.w; be[i][4] = b1.x; be[i][5] = b1.y; be[i][6] = b1.z; be[i][7] = b1.w;
     }
-    float s1 = 0.f, s2 = 0.f;  // shifted one-pass variance
+    // two passes over the registers (mean, then squares of the centred values): one more lane-group reduction on the chain,
+    // and no cancellation whichever channel holds the row's outlier
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < CH; ++i)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { const float t = a[i][e] - shift; s1 += t; s2 += t * t; }
+      for (int e = 0; e < 8; ++e) s1 += a[i][e];
 #pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
-    const float dm = s1 / K, var = fmaxf(s2 / K - dm * dm, 0.f);
-    const float mean = shift + dm, rstd = rsqrtf(var + 1e-5f);
+    for (int o = LPR / 2; o > 0; o >>= 1) s1 += __shfl_xor(s1, o, 64);
+    const float mean = s1 / K;
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float t = a[i][e] - mean; s2 += t * t; }
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
+    const float rstd = rsqrtf(s2 / K + 1e-5f);
 #pragma unroll
     for (int i = 0; i < CH; ++i)
 #pragma unroll
