@@ -67,7 +67,10 @@ AX_WHISPER_API int AX_WHISPER_VisibleDeviceCount(void);
 /** Engines (devices) behind the handle; -1 for a NULL handle. */
 AX_WHISPER_API int AX_WHISPER_GetDeviceCount(AX_WHISPER_HANDLE handle);
 /** Integer config value by the key names of {type}_config.json (n_mels, n_vocab, eot, ...),
- *  plus "sot_seq0".."sot_seq3". Returns INT32_MIN for an unknown key. */
+ *  plus "sot_seq0".."sot_seq3". Returns INT32_MIN for an unknown key.
+ *  Test hook: "live_hip_objects" = the device and pinned buffers, streams, events and graphs that the handles of this
+ *  process hold right now (all of them, not this handle's alone): closing a handle, or an Init that fails, leaves the
+ *  count where it was before that handle. */
 AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char* key);
 /** Last error text of this handle (or of the last failed Init when handle is NULL). */
 AX_WHISPER_API const char* AX_WHISPER_LastError(AX_WHISPER_HANDLE handle);

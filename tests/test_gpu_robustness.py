@@ -210,6 +210,83 @@ def test_failed_inits_do_not_leak_device_memory(built_lib, micro_case, tmp_path)
     assert free0 - free1 < 16 << 20, (free0, free1)
 
 
+def _touch_every_lazily_created_object(e, tmp_path, monkeypatch):
+    """Everything a handle creates on demand, once each (csrc/engine.hpp: the four owner groups)."""
+    import modelgen
+
+    clips = [modelgen.synth_clip(i, 40000 + 1000 * i) for i in range(24)]
+    e.run_tokens(clips[0], max_new=4)  # one clip: the persistent launch
+    e.run_timestamp_scores_batch(clips[:4], max_new=4)  # the timestamp logits and the score arrays
+    assert len(e.run_tokens_batch(clips, max_new=4)) == 24  # capacity growth, a two-branch step graph, branch and pad streams, the queue probe
+    assert e.get_config_int("decode_branches") >= 2
+    e.run_tokens(modelgen.synth_clip(30, 65 * 16000), max_new=4)  # beyond a 60 s staging row: the overflow tail buffer
+    e.stream_open(4)
+    e.stream_admit_batch([0, 1], clips[:2], [4, 4])
+    left = {0, 1}
+    for _ in range(64):
+        for sl in e.stream_step(4):
+            e.stream_collect(sl)
+            left.discard(sl)
+        if not left:
+            break
+    assert not left
+    e.stream_close()
+    e.stream_open(6)  # regrows the ring and the admit events
+    e.stream_close()
+    e.run_long(modelgen.synth_clip(31, 70 * 16000), max_new=4)  # the arena and the pinned window table
+    assert e.scan_stored16(1)
+    assert e.bench("decode_step_ts_scored", 4, 0, 2) > 0
+    stamps = tmp_path / "attn_stamps.csv"
+    monkeypatch.setenv("AX_WHISPER_ATTN_STAMP", str(stamps))
+    assert e.bench("attn_stamp", 4, 0, 1) > 0 and stamps.exists()
+    with pytest.raises(RuntimeError, match="unknown target"):
+        e.bench("no_such_target", 4, 0, 1)
+
+
+def test_every_lazily_created_object_is_released(built_lib, micro_case, tmp_path, monkeypatch):
+    """Exact, where the two memory-bound tests are thresholded: "live_hip_objects" counts every device and pinned buffer,
+    stream, event and graph the handles of this process own (csrc/owned.hpp). A second handle that has touched everything
+    created on demand leaves the count where it was, twice."""
+    import gc
+
+    gc.collect()  # (a handle an earlier test left to the collector would change the count under this test)
+    a = built_lib.Whisper("micro", micro_case.root, "zh", device=0)
+    try:
+        base = a.get_config_int("live_hip_objects")
+        assert base > 0
+        for _ in range(2):
+            b = built_lib.Whisper("micro", micro_case.root, "zh", device=0, max_batch=1)
+            try:
+                _touch_every_lazily_created_object(b, tmp_path, monkeypatch)
+                assert b.get_config_int("live_hip_objects") > 2 * base  # (it counts what b grew)
+            finally:
+                b.close()
+            assert a.get_config_int("live_hip_objects") == base
+    finally:
+        a.close()
+
+
+def test_failed_init_releases_every_object(built_lib, micro_case, tmp_path):
+    """The constructor that throws half way (test_failed_inits_do_not_leak_device_memory), counted exactly: streams, events,
+    the staging buffer and every weight uploaded before the bad tensor are given back."""
+    import gc
+    import modelgen
+
+    w = dict(micro_case.weights)
+    w["decoder.ln.bias"] = np.ones(64, dtype=np.float32)  # loaded last: everything before it is already on the device
+    modelgen.write_model_dir(str(tmp_path), "micro", micro_case.dims, weights=w)
+    L = built_lib.load_library()
+    gc.collect()
+    a = built_lib.Whisper("micro", micro_case.root, "zh", device=0)
+    try:
+        base = a.get_config_int("live_hip_objects")
+        for _ in range(3):
+            assert L.AX_WHISPER_Init(b"micro", str(tmp_path).encode(), b"zh") is None
+            assert a.get_config_int("live_hip_objects") == base
+    finally:
+        a.close()
+
+
 def test_multi_device_handle_shards_a_batch(built_lib, micro_case, monkeypatch):
     """AX_WHISPER_InitMulti: one engine per listed device behind one handle, RunPCMBatch* split into contiguous blocks
     (csrc/multi_device.hpp). A one-GPU box lists its device twice (test hook) so that two real engines, two worker

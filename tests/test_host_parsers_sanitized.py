@@ -147,3 +147,14 @@ def test_device_group_under_thread_sanitizer(tmp_path):
                        env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
     assert "multi_device ok" in r.stdout and "WARNING: ThreadSanitizer" not in r.stderr
+
+
+def test_owned_handle_under_address_sanitizer(tmp_path):
+    """csrc/owned.hpp (the one owner of every HIP object of the engine) with a counting release on int handles: each handle
+    is released exactly once on every path (scope end, move, reset, container erase, a throw half way), release() gives it up,
+    and live_owned ends where it began. AddressSanitizer + UBSan, plain g++: the header includes nothing from HIP."""
+    exe = str(tmp_path / "owned_asan")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "cpp", "owned_test.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "owned ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]

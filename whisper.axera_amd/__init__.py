@@ -238,6 +238,10 @@ class Whisper:
         self.no_speech = g("no_speech")
         self.n_devices = self.L.AX_WHISPER_GetDeviceCount(self.h)
 
+    def get_config_int(self, key: str) -> int:
+        """AX_WHISPER_GetConfigInt: a config file key, or one of the engine's own (include/ax_whisper_api.h)."""
+        return self.L.AX_WHISPER_GetConfigInt(self.h, key.encode())
+
     def close(self):
         if getattr(self, "h", None):
             self.L.AX_WHISPER_Uninit(self.h)

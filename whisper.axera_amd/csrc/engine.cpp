@@ -1,5 +1,6 @@
 // engine.cpp — host side of the MI355X Whisper engine (see engine.hpp for what it replaces): construction, weights, slot buffers,
-// front-end, encoder and the entry points. The decode paths: engine_decode.cpp; utterance slots and bench hooks: engine_stream.cpp.
+// front-end, encoder and the entry points. The decode paths: engine_decode.cpp; utterance slots and the queue-placement probe:
+// engine_stream.cpp; long-form: engine_long.cpp; the bench and scan hooks: engine_bench.cpp.
 #include "engine_impl.hpp"
 
 #include "host_io.hpp"
@@ -29,8 +30,8 @@ Engine::Engine(const std::string& model_type, const std::string& model_path, con
   try {
     construct(model_type, model_path, language, device, max_batch);
   } catch (...) {
-    // the destructor of a partially constructed object never runs: a failed Init (missing / corrupt weights, shape
-    // mismatch, out of memory) must give back the stream, the events, the pinned buffers and every weight already uploaded
+    // a failed Init (missing / corrupt weights, shape mismatch, out of memory): the owners would give everything back by
+    // themselves, destroy() does it in order and under the capture mutex
     destroy();
     throw;
   }
@@ -60,25 +61,22 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));  // allocations + synchronous copies (iengine.hpp)
   HIP_CHECK(hipSetDevice(device_));
   device_set_ = true;
-  HIP_CHECK(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking));
-  for (auto& e : ev_) HIP_CHECK(hipEventCreate(&e));
+  own_stream_ = make_stream();
+  for (auto& e : ev_) e = make_event();
   // (the second branch's stream; the third and fourth are created when a step graph first needs them: every stream takes a turn
   // on the runtime's four hardware queues, and up to 64 clips only four of the engine's streams ever work side by side)
-  HIP_CHECK(hipStreamCreateWithFlags(&branch_stream_[0], hipStreamNonBlocking));
-  HIP_CHECK(hipStreamCreateWithFlags(&admit_stream_, hipStreamNonBlocking));
-  HIP_CHECK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
+  branch_stream_[0] = make_stream();
+  admit_stream_ = make_stream();
+  copy_stream_ = make_stream();
   if (const char* e = getenv("AX_WHISPER_PAD_STREAMS")) {  // diagnostic (profiles/scripts/stream_mode_probe.py): shifts which hardware
-    for (int i = 0; i < atoi(e) && i < 8; ++i) {            // queue every LATER stream of the process lands on (graph-internal ones too)
-      hipStream_t pad = nullptr;
-      HIP_CHECK(hipStreamCreateWithFlags(&pad, hipStreamNonBlocking));
-      pad_streams_.push_back(pad);
-    }
+    for (int i = 0; i < atoi(e) && i < 8; ++i)              // queue every LATER stream of the process lands on (graph-internal ones too)
+      pad_streams_.push_back(make_stream());
   }
-  for (auto& e : ev_ring_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : ev_step_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIP_CHECK(hipEventCreateWithFlags(&ev_upload_, hipEventDisableTiming));
-  HIP_CHECK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-  for (auto& e : ev_join_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : ev_ring_) e = make_event(hipEventDisableTiming);
+  for (auto& e : ev_step_) e = make_event(hipEventDisableTiming);
+  ev_upload_ = make_event(hipEventDisableTiming);
+  ev_fork_ = make_event(hipEventDisableTiming);
+  for (auto& e : ev_join_) e = make_event(hipEventDisableTiming);
 
   load_weights(weights_file);
 
@@ -86,7 +84,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     const char* e = getenv("AX_WHISPER_MAX_BATCH");
     max_batch = e ? atoi(e) : 1;
   }
-  HIP_CHECK(hipHostMalloc((void**)&h_poll_, 64 * sizeof(int), hipHostMallocDefault));
+  h_poll_ = pinned_array<int>(64);
   {  // persistent batch-1 decode: one workgroup per CU for the whole utterance (decode_persistent.hip)
     hipDeviceProp_t prop;
     HIP_CHECK(hipGetDeviceProperties(&prop, device_));
@@ -97,8 +95,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     if (persistent_ok_) {
       persist_grid_ = decode_persistent_grid(cfg_.n_text_state, prop.multiProcessorCount);
       gran_bytes_ = decode_persistent_gran_bytes(cfg_.n_text_state, persist_grid_);
-      d_gran_ = (u64*)dalloc(3 * gran_bytes_, true);  // one area per clip of a multi-clip launch
-      allocs_.push_back(d_gran_);
+      d_gran_ = (u64*)pooled<char>(allocs_, 3 * gran_bytes_, true);  // one area per clip of a multi-clip launch
       // two or three clips per launch (decode_persistent2.hip): the later clips' self-attention caches live in global memory
       // "0" / "1": one launch per clip, as before round 4; "2": at most two clips per launch (A/B, tests); default: up to three
       const char* e2 = getenv("AX_WHISPER_PERSIST2");
@@ -109,8 +106,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
       {
         const char* eq = getenv("AX_WHISPER_QFOLD");
         if (cfg_.n_text_state <= 768 && !(eq && eq[0] == '0')) {
-          d_qfold_ = (float*)dalloc(qfold_floats(cfg_.n_text_state, cfg_.n_text_layer) * sizeof(float));
-          allocs_.push_back(d_qfold_);
+          d_qfold_ = pooled<float>(allocs_, qfold_floats(cfg_.n_text_state, cfg_.n_text_layer));
           launch_qfold_build(dec_w_arena_, dec_f_arena_, d_qfold_, cfg_.n_text_state, cfg_.n_text_layer, own_stream_);
           HIP_CHECK(hipStreamSynchronize(own_stream_));
         }
@@ -123,10 +119,8 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
       }
       if (persist_max_clips_ >= 2) {
         self1_bytes_ = (size_t)cfg_.n_text_layer * cfg_.n_text_head * 8 * layout::kKvBlockElems * 2;  // one later clip's cache (K; V alike)
-        d_self_k1_ = (h16*)dalloc((persist_max_clips_ - 1) * self1_bytes_, true);
-        d_self_v1_ = (h16*)dalloc((persist_max_clips_ - 1) * self1_bytes_, true);
-        allocs_.push_back(d_self_k1_);
-        allocs_.push_back(d_self_v1_);
+        d_self_k1_ = (h16*)pooled<char>(allocs_, (persist_max_clips_ - 1) * self1_bytes_, true);
+        d_self_v1_ = (h16*)pooled<char>(allocs_, (persist_max_clips_ - 1) * self1_bytes_, true);
       }
     }
   }
@@ -168,45 +162,11 @@ void Engine::destroy() {
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   (void)hipSetDevice(device_);
   (void)hipDeviceSynchronize();
-  free_slot_buffers();  // also destroys the captured step graphs
-  for (void* p : allocs_) (void)hipFree(p);
-  allocs_.clear();
-  if (load_stage_) { (void)hipFree(load_stage_); load_stage_ = nullptr; }
-  if (d_over_) { (void)hipFree(d_over_); d_over_ = nullptr; over_cap_ = 0; }
-  free_long_arena();
-  if (h_poll_) { (void)hipHostFree(h_poll_); h_poll_ = nullptr; }
-  for (auto& e : ev_) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  for (auto& e : ev_join_) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  if (ev_fork_) { (void)hipEventDestroy(ev_fork_); ev_fork_ = nullptr; }
-  for (auto& b : branch_stream_) if (b) { (void)hipStreamDestroy(b); b = nullptr; }
-  if (admit_stream_) { (void)hipStreamDestroy(admit_stream_); admit_stream_ = nullptr; }
-  if (copy_stream_) { (void)hipStreamDestroy(copy_stream_); copy_stream_ = nullptr; }
-  for (auto& ps : pad_streams_) (void)hipStreamDestroy(ps);
-  pad_streams_.clear();
-  for (auto& e : ev_ring_) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  for (auto& e : ev_step_) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  if (ev_upload_) { (void)hipEventDestroy(ev_upload_); ev_upload_ = nullptr; }
-  if (h_admit_ring_) { (void)hipHostFree(h_admit_ring_); h_admit_ring_ = nullptr; }
-  for (auto& e : ev_admit_) if (e) (void)hipEventDestroy(e);
-  ev_admit_.clear();
-  if (h_done_live_) { (void)hipHostFree(h_done_live_); h_done_live_ = nullptr; }
-  if (own_stream_) { (void)hipStreamDestroy(own_stream_); own_stream_ = nullptr; }
-}
-
-void* Engine::dalloc(size_t bytes, bool zero) {
-  void* p = nullptr;
-  HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-  if (zero) {
-    // the engine's streams are non-blocking (not ordered against the null stream): finish the fill before any
-    // kernel on them can touch the buffer
-    hipError_t e = hipMemset(p, 0, std::max<size_t>(bytes, 256));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e) + " zero-filling a device buffer");
-    }
-  }
-  return p;
+  // (the member destructors would run after this lock is gone, and streams first)
+  free_slot_buffers();  // the captured step graphs, then the slot buffers
+  static_cast<EngineMemory&>(*this) = EngineMemory{};
+  static_cast<EngineEvents&>(*this) = EngineEvents{};
+  static_cast<EngineStreams&>(*this) = EngineStreams{};
 }
 
 // Whisper.cpp:86-101,129-139,241-251: config keys, comma-joined language lists, SOT sequence.
@@ -325,7 +285,7 @@ void Engine::load_weights(const SafeTensors& st) {
   note("decoder.token_embedding.weight");
   note("encoder.conv2.weight");
   note("encoder.blocks.0.mlp.0.weight");
-  load_stage_ = dalloc(max_bytes);  // a member: freed by destroy() when a later tensor throws
+  load_stage_ = device_alloc(max_bytes);  // a member: released under destroy()'s lock when a later tensor throws
   void* const stage = load_stage_;
 
   auto check = [&](const std::string& n, std::vector<int64_t> shape) -> const TensorView& {
@@ -340,8 +300,7 @@ void Engine::load_weights(const SafeTensors& st) {
   };
   auto to_f32 = [&](const std::string& n, std::vector<int64_t> shape) {
     const TensorView& t = check(n, shape);
-    float* dst = (float*)dalloc((size_t)t.numel() * 4);
-    allocs_.push_back(dst);
+    float* dst = pooled<float>(allocs_, (size_t)t.numel());
     up(t);
     launch_convert_to_f32(stage, dtype_code(t.dtype), dst, t.numel(), s);
     return dst;
@@ -356,8 +315,8 @@ void Engine::load_weights(const SafeTensors& st) {
     up(t);
     launch_convert_to_f32(stage, dtype_code(t.dtype), dst, t.numel(), s);
   };
-  auto new_h16 = [&](size_t n) { h16* p = (h16*)dalloc(n * 2, true); allocs_.push_back(p); return p; };
-  auto new_f32 = [&](size_t n) { float* p = (float*)dalloc(n * 4, true); allocs_.push_back(p); return p; };
+  auto new_h16 = [&](size_t n) { return pooled<h16>(allocs_, n, true); };
+  auto new_f32 = [&](size_t n) { return pooled<float>(allocs_, n, true); };
 
   // conv stem: [Cout][Cin][3] -> GEMM weights with k-major taps (gemm.hip header)
   conv1_k_ = ((3 * nm + 63) / 64) * 64;
@@ -507,8 +466,7 @@ void Engine::load_weights(const SafeTensors& st) {
   }
   tok_emb_packed_ = pack(tok_emb_, cfg_.n_vocab, d);
   HIP_CHECK(hipStreamSynchronize(s));
-  HIP_CHECK(hipFree(stage));
-  load_stage_ = nullptr;
+  load_stage_.reset();
 
   // front-end constants: DFT twiddles (double -> f32), periodic Hann (librosa.h:81), mel basis
   std::vector<float> tw(2 * kNFFT), win(kNFFT);
@@ -525,21 +483,16 @@ void Engine::load_weights(const SafeTensors& st) {
   HIP_CHECK(hipMemcpy(twiddle_, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(window_, win.data(), win.size() * 4, hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(mel_basis_t_, mb.data(), mb.size() * 4, hipMemcpyHostToDevice));
-  d_sot_ = (int*)dalloc(16);
-  allocs_.push_back(d_sot_);
+  d_sot_ = pooled<int>(allocs_, 4);
   HIP_CHECK(hipMemcpy(d_sot_, sot_seq_, 16, hipMemcpyHostToDevice));
 }
 
 // ------------------------------------------------------------------------------ slot buffers
 void Engine::free_slot_buffers() {
-  for (auto& g : graphs_) (void)hipGraphExecDestroy(g.second);
-  graphs_.clear();
-  for (void* p : slot_allocs_) (void)hipFree(p);
+  static_cast<EngineGraphs&>(*this) = EngineGraphs{};  // the captured steps hold pointers into the buffers
   slot_allocs_.clear();
-  d_ts_logits_ = nullptr;  // (one of slot_allocs_)
-  d_tok_lp_ = nullptr; d_dec_id_ = nullptr; d_nospeech_ = nullptr;  // (likewise)
-  own_scores_ = TsScoreParams{};
-  if (h_pcm_) { (void)hipHostFree(h_pcm_); h_pcm_ = nullptr; }
+  static_cast<SlotViews&>(*this) = SlotViews{};
+  h_pcm_.reset();
   cap_ = 0;
 }
 
@@ -550,10 +503,10 @@ void Engine::ensure_capacity(int batch) {
   free_slot_buffers();
   const int B = batch, d = cfg_.n_text_state, nm = cfg_.n_mels, H = cfg_.n_text_head, L = cfg_.n_text_layer;
   const int T = cfg_.n_audio_ctx, Tc = cfg_.n_text_ctx;
-  auto A = [&](size_t bytes, bool zero = false) { void* p = dalloc(bytes, zero); slot_allocs_.push_back(p); return p; };
+  auto A = [&](size_t bytes, bool zero = false) { return (void*)pooled<char>(slot_allocs_, bytes, zero); };
   pcm_stride_ = 2 * 480000;  // staging row of a clip (60 s; the window itself is 30 s); longer clips put their tails into d_over_
   d_pcm_ = (float*)A((size_t)B * pcm_stride_ * 4, true);
-  HIP_CHECK(hipHostMalloc((void**)&h_pcm_, (size_t)B * pcm_stride_ * 4, hipHostMallocDefault));
+  h_pcm_ = pinned_array<float>((size_t)B * pcm_stride_);
   d_nsamp_ = (int*)A((size_t)B * 4);
   d_over_off_ = (long long*)A((size_t)B * 8, true);
   d_gmax_ = (unsigned*)A((size_t)B * 4);
@@ -599,8 +552,7 @@ void Engine::ensure_capacity(int batch) {
   d_done_none_ = (int*)A((size_t)B * 4, true);  // all zero, never written: the "nobody has finished" flags of teacher-forced decodes
   d_off_ = (int*)A((size_t)B * 4, true);
   d_slot_map_ = (int*)A((size_t)B * 4, true);
-  if (h_done_live_) { (void)hipHostFree(h_done_live_); h_done_live_ = nullptr; }
-  HIP_CHECK(hipHostMalloc((void**)&h_done_live_, (size_t)B * 4, hipHostMallocMapped));
+  h_done_live_ = pinned_array<int>(B, hipHostMallocMapped);
   memset(h_done_live_, 0, (size_t)B * 4);
   HIP_CHECK(hipHostGetDevicePointer((void**)&d_done_live_, h_done_live_, 0));
   d_attn_mpart_ = (float*)A((size_t)layout::part_elems(B, cfg_.n_text_head, layout::kAttnSplitMax) * 4, true);
@@ -635,8 +587,9 @@ void Engine::upload_pcm(const float* const* pcm, const int* n_samples, int batch
     HIP_CHECK(hipStreamSynchronize(stream()));  // an earlier pass on this stream may still read the tails
   }
   if (over_total > over_cap_) {
-    if (d_over_) { (void)hipFree(d_over_); d_over_ = nullptr; over_cap_ = 0; }
-    HIP_CHECK(hipMalloc((void**)&d_over_, over_total * 4));
+    d_over_.reset();  // (first: the old and the new tails need not fit side by side)
+    over_cap_ = 0;
+    d_over_ = device_array<float>(over_total);
     over_cap_ = over_total;
   }
   if (over_used_) HIP_CHECK(hipMemcpy(d_over_off_, off.data(), (size_t)batch * 8, hipMemcpyHostToDevice));
@@ -702,14 +655,11 @@ void Engine::build_cblock_fold() {
     const float* qf = d_qfold_ + (size_t)l * qfold_floats(d, 1);  // per-layer block: M [d][d], then d, s, c [d] each (decode_persistent_common.hpp)
     const float* vecs = qf + (size_t)d * d;  // d, s, c
     DecLayerWP& wp = dec_packed_[l];
-    wp.m_lo = (h16*)dalloc((size_t)d * d * 2, true);
-    allocs_.push_back(wp.m_lo);
+    wp.m_lo = pooled<h16>(allocs_, (size_t)d * d, true);
     launch_pack_weight_frag_split(qf, wp.m_hi, wp.m_lo, d, d, s);
     CblockFold& c = cfold_[l];
-    c.b_qkv4 = (float*)dalloc((size_t)4 * d * 4, true);  // [b_qkv; 0]: the A0 rows have no bias
-    c.b_o2 = (float*)dalloc((size_t)2 * d * 4, true);    // [b_o; d]
-    allocs_.push_back(c.b_qkv4);
-    allocs_.push_back(c.b_o2);
+    c.b_qkv4 = pooled<float>(allocs_, (size_t)4 * d, true);  // [b_qkv; 0]: the A0 rows have no bias
+    c.b_o2 = pooled<float>(allocs_, (size_t)2 * d, true);    // [b_o; d]
     HIP_CHECK(hipMemcpyAsync(c.b_qkv4, dec_[l].b_qkv, (size_t)3 * d * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(c.b_o2, dec_[l].b_o, (size_t)d * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(c.b_o2 + d, vecs, (size_t)d * 4, hipMemcpyDeviceToDevice, s));
@@ -941,21 +891,18 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
   if (scored) ensure_ts_scores();
   hipStream_t s = stream();
   const int nv = cfg_.n_vocab, rows = n_forced + 1;
-  DevBuf b_forced, b_arg, b_logits, b_lp, b_dec, b_nsp, b_l0;  // scratch of this call
-  HIP_CHECK(hipMalloc(&b_forced.p, std::max<size_t>((size_t)batch * n_forced * 4, 256)));
-  HIP_CHECK(hipMalloc(&b_arg.p, (size_t)batch * rows * 4));
-  if (logits) HIP_CHECK(hipMalloc(&b_logits.p, (size_t)batch * rows * nv * 4));
+  // scratch of this call
+  DeviceArray<int> d_forced = device_array<int>((size_t)batch * n_forced), d_arg = device_array<int>((size_t)batch * rows), b_dec;
+  DeviceArray<float> d_logits, b_lp, b_nsp, b_l0;
+  if (logits) d_logits = device_array<float>((size_t)batch * rows * nv);
   StepSpec spec{mode};
   if (scored) {  // this call's own score arrays ([batch][rows]: the rules kernel's index is the history length)
-    HIP_CHECK(hipMalloc(&b_lp.p, (size_t)batch * rows * 4));
-    HIP_CHECK(hipMalloc(&b_dec.p, (size_t)batch * rows * 4));
-    HIP_CHECK(hipMalloc(&b_nsp.p, (size_t)batch * 4));
-    if (out.logits0) HIP_CHECK(hipMalloc(&b_l0.p, (size_t)batch * nv * 4));
-    spec.score_out = TsScoreParams{(float*)b_lp.p, (int*)b_dec.p, (long)rows, (float*)b_nsp.p, own_scores_.no_speech_id};
+    b_lp = device_array<float>((size_t)batch * rows);
+    b_dec = device_array<int>((size_t)batch * rows);
+    b_nsp = device_array<float>(batch);
+    if (out.logits0) b_l0 = device_array<float>((size_t)batch * nv);
+    spec.score_out = TsScoreParams{b_lp, b_dec, (long)rows, b_nsp, own_scores_.no_speech_id};
   }
-  int* d_forced = (int*)b_forced.p;
-  int* d_arg = (int*)b_arg.p;
-  float* d_logits = (float*)b_logits.p;
   if (n_forced) HIP_CHECK(hipMemcpy(d_forced, forced, (size_t)batch * n_forced * 4, hipMemcpyHostToDevice));
   bool done = false;
   if (batch == 1 && !tsm && persistent_usable()) {
@@ -972,13 +919,13 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
     if (tsm && lrow) HIP_CHECK(hipMemcpy2DAsync(lrow, (size_t)rows * nv * 4, d_ts_logits_, (size_t)ts_stride_ * 4, (size_t)nv * 4, batch,
                                                 hipMemcpyDeviceToDevice, s));
     // scored: the row of decode offset 0, which the no-speech value was taken from
-    if (st == 0 && b_l0.p) HIP_CHECK(hipMemcpy2DAsync(b_l0.p, (size_t)nv * 4, d_ts_logits_, (size_t)ts_stride_ * 4, (size_t)nv * 4, batch,
+    if (st == 0 && b_l0) HIP_CHECK(hipMemcpy2DAsync(b_l0, (size_t)nv * 4, d_ts_logits_, (size_t)ts_stride_ * 4, (size_t)nv * 4, batch,
                                                       hipMemcpyDeviceToDevice, s));
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  if (out.logprob) HIP_CHECK(hipMemcpy(out.logprob, b_lp.p, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
-  if (out.no_speech_logprob) HIP_CHECK(hipMemcpy(out.no_speech_logprob, b_nsp.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
-  if (out.logits0) HIP_CHECK(hipMemcpy(out.logits0, b_l0.p, (size_t)batch * nv * 4, hipMemcpyDeviceToHost));
+  if (out.logprob) HIP_CHECK(hipMemcpy(out.logprob, b_lp, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
+  if (out.no_speech_logprob) HIP_CHECK(hipMemcpy(out.no_speech_logprob, b_nsp, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  if (out.logits0) HIP_CHECK(hipMemcpy(out.logits0, b_l0, (size_t)batch * nv * 4, hipMemcpyDeviceToHost));
   if (logits) HIP_CHECK(hipMemcpy(logits, d_logits, (size_t)batch * rows * nv * 4, hipMemcpyDeviceToHost));
   if (argmax_ids) HIP_CHECK(hipMemcpy(argmax_ids, d_arg, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
 }
@@ -1014,31 +961,27 @@ void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int
   const long stride = ((long)nv + 3) / 4 * 4;
   for (int b = 0; b < batch; ++b)
     if (n_hist[b] < 0 || n_hist[b] > Tc) throw std::runtime_error("apply_timestamp_rules: n_hist out of range");
-  DevBuf b_log, b_hist, b_n, b_val, b_idx, b_lp, b_dec;
+  DeviceArray<float> b_lp, b_log = device_array<float>((size_t)batch * stride), b_val = device_array<float>(batch);
+  DeviceArray<int> b_dec, b_hist = device_array<int>((size_t)batch * Tc), b_n = device_array<int>(batch), b_idx = device_array<int>(batch);
   if (logprob) {  // [batch][n_text_ctx + 1]: the kernel's index is the history length
-    HIP_CHECK(hipMalloc(&b_lp.p, (size_t)batch * (Tc + 1) * 4));
-    HIP_CHECK(hipMalloc(&b_dec.p, (size_t)batch * (Tc + 1) * 4));
+    b_lp = device_array<float>((size_t)batch * (Tc + 1));
+    b_dec = device_array<int>((size_t)batch * (Tc + 1));
   }
-  HIP_CHECK(hipMalloc(&b_log.p, (size_t)batch * stride * 4));
-  HIP_CHECK(hipMalloc(&b_hist.p, (size_t)batch * Tc * 4));
-  HIP_CHECK(hipMalloc(&b_n.p, (size_t)batch * 4));
-  HIP_CHECK(hipMalloc(&b_val.p, (size_t)batch * 4));
-  HIP_CHECK(hipMalloc(&b_idx.p, (size_t)batch * 4));
-  HIP_CHECK(hipMemcpy2DAsync(b_log.p, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(b_hist.p, hist, (size_t)batch * Tc * 4, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(b_n.p, n_hist, (size_t)batch * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpy2DAsync(b_log, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_hist, hist, (size_t)batch * Tc * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_n, n_hist, (size_t)batch * 4, hipMemcpyHostToDevice, s));
   TsRulesParams r{};
-  r.logits = (const float*)b_log.p; r.stride = stride; r.batch = batch;
+  r.logits = b_log; r.stride = stride; r.batch = batch;
   r.n_vocab = nv; r.eot = cfg_.eot; r.ts_begin = cfg_.no_timestamps + 1;
   r.off = nullptr; r.n_prefix = 3; r.done = nullptr;
-  r.out_ids = (const int*)b_hist.p; r.n_out = (const int*)b_n.p; r.n_ctx = Tc;
-  r.amax_val = (float*)b_val.p; r.amax_idx = (int*)b_idx.p; r.amax_stride = 1;
-  if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{(float*)b_lp.p, (int*)b_dec.p, (long)Tc + 1, nullptr, 0}, s);
+  r.out_ids = b_hist; r.n_out = b_n; r.n_ctx = Tc;
+  r.amax_val = b_val; r.amax_idx = b_idx; r.amax_stride = 1;
+  if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, s);
   else launch_timestamp_rules(r, s);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(chosen, b_idx.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(chosen, b_idx, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
   for (int b = 0; logprob && b < batch; ++b)
-    HIP_CHECK(hipMemcpyAsync(logprob + b, (const float*)b_lp.p + (size_t)b * (Tc + 1) + n_hist[b], 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(logprob + b, b_lp + (size_t)b * (Tc + 1) + n_hist[b], 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -1052,13 +995,11 @@ void Engine::no_speech_logprob(const float* logits, int batch, float* out) {
   hipStream_t s = stream();
   const int nv = cfg_.n_vocab;
   const long stride = ((long)nv + 3) / 4 * 4;
-  DevBuf b_log, b_out;
-  HIP_CHECK(hipMalloc(&b_log.p, (size_t)batch * stride * 4));
-  HIP_CHECK(hipMalloc(&b_out.p, (size_t)batch * 4));
-  HIP_CHECK(hipMemcpy2DAsync(b_log.p, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
-  launch_row_logprob((const float*)b_log.p, stride, nv, (int)cfg_.ints.at("no_speech"), batch, (float*)b_out.p, s);
+  DeviceArray<float> b_log = device_array<float>((size_t)batch * stride), b_out = device_array<float>(batch);
+  HIP_CHECK(hipMemcpy2DAsync(b_log, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
+  launch_row_logprob(b_log, stride, nv, (int)cfg_.ints.at("no_speech"), batch, b_out, s);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(out, b_out.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(out, b_out, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -21,7 +21,88 @@ namespace axw {
 class SafeTensors;  // host_io.hpp
 inline namespace AXW_NS {
 
-class Engine final : public IEngine {
+// Every HIP object of an engine has exactly one owner (engine_impl.hpp, through which this header is included), in one of the
+// four groups below. Engine::destroy() empties them under device_capture_mutex in the order graph execs, memory, events,
+// streams (Engine's base order is the reverse, so its destructor alone would keep that order): a member added to a group is
+// released with it, nothing is listed a second time.
+struct EngineStreams {
+  Stream own_stream_;
+  std::vector<Stream> pad_streams_;  // align_graph_queue() (engine_stream.cpp); AX_WHISPER_PAD_STREAMS (diagnostic)
+  static constexpr int kMaxBranches = 4;   // parallel branches of the batched step graph
+  Stream branch_stream_[kMaxBranches - 1];
+  Stream admit_stream_, copy_stream_;  // (copies: stream_collect's D2H, never behind the queued decoder steps)
+};
+
+struct EngineEvents {
+  Event ev_fork_, ev_join_[EngineStreams::kMaxBranches - 1];
+  std::vector<Event> ev_admit_;     // one per slot: its encoder has finished
+  Event ev_step_[3];  // the host stays two steps ahead of the device (stream_step)
+  // admission passes do not wait for one another's encoder: clip lengths and slot maps go through a pinned ring of
+  // kAdmitRing entries (an entry is reused once the pass that filled it has finished), the PCM staging rows are reused once
+  // the previous pass's uploads have landed
+  static constexpr int kAdmitRing = 4;
+  Event ev_ring_[kAdmitRing], ev_upload_, ev_[5];
+};
+
+// long-form (engine_long.cpp): the PCM and the log-mel rows of every file of one call in one arena, kept for the next call
+// when small (allocated and freed under device_capture_mutex)
+struct LongArena {
+  DeviceArray<char> base; size_t bytes = 0;
+  float *pcm = nullptr, *store = nullptr;
+  long long *pcm_off = nullptr, *frame_off = nullptr;
+  int *n_samples = nullptr, *n_frames = nullptr, *win_file = nullptr, *win_seek = nullptr;
+  unsigned* gmax = nullptr;
+  int n_files = 0, n_windows = 0;
+};
+
+struct EngineMemory {
+  std::vector<DeviceMem> slot_allocs_;  // capacity-dependent buffers
+  std::vector<DeviceMem> allocs_;       // weights + constants (freed at destruction)
+  DeviceMem load_stage_;  // staging buffer of load_weights
+  PinnedArray<float> h_pcm_;
+  // clips longer than a staging row (60 s): their tails, packed, so that the clamp floor comes from ALL frames of the
+  // input however long it is (Whisper.cpp:158-172); grown on demand, empty for ordinary requests
+  DeviceArray<float> d_over_; size_t over_cap_ = 0;
+  LongArena long_;
+  PinnedArray<int> h_long_win_; int h_long_win_cap_ = 0;  // pinned [2][windows per pass]: file and seek of every slot
+  PinnedArray<int> h_poll_;
+  PinnedArray<int> h_done_live_; int* d_done_live_ = nullptr;  // host-mapped [cap] (and its device alias): advance_kernel raises a clip's
+                                                               // flag the moment it finishes; the host reads it without any wait
+  PinnedArray<int> h_admit_ring_;          // pinned [kAdmitRing][2][cap]
+  DeviceArray<unsigned long long> d_stamp_;  // bench "attn_stamp"
+};
+
+struct EngineGraphs {
+  std::map<long, GraphExec> graphs_;  // key: Engine::graph_key
+};
+
+// Typed pointers into slot_allocs_ (they own nothing): Engine::free_slot_buffers() resets all of them with the pool.
+struct SlotViews {
+  float* d_ts_logits_ = nullptr;  // [cap][ts_stride_], allocated on first use under device_capture_mutex
+  // scored mode (DESIGN.md "Confidence"): per-clip log-probability and id of every decision [cap][n_text_ctx], log p(<|nospeech|>)
+  // [cap]; allocated like d_ts_logits_. own_scores_: these arrays as the scored rules kernel takes them (decode_forced hands it
+  // its own [batch][n_forced + 1] buffers instead)
+  float* d_tok_lp_ = nullptr; int* d_dec_id_ = nullptr; float* d_nospeech_ = nullptr;
+  TsScoreParams own_scores_{};
+  float *d_a0_ = nullptr, *d_statp_ = nullptr;  // [B][d] A0 -> T; [B][d/16][2] block statistics of the residual rows
+  float* d_pcm_ = nullptr; long long* d_over_off_ = nullptr;
+  int* d_nsamp_ = nullptr; unsigned* d_gmax_ = nullptr; float* d_logmel_ = nullptr; float* d_mel_ref_ = nullptr;
+  h16 *d_mel_tm_ = nullptr, *d_h1_ = nullptr, *d_ln_ = nullptr, *d_q_ = nullptr, *d_k_ = nullptr, *d_vt_ = nullptr,
+       *d_attn_ = nullptr, *d_ffn_ = nullptr;
+  float *d_x_ = nullptr, *d_enc_part_ = nullptr;
+  h16 *d_cross_k_ = nullptr, *d_cross_v_ = nullptr, *d_self_k_ = nullptr, *d_self_v_ = nullptr;
+  float *d_xdec_ = nullptr, *d_qdec_ = nullptr, *d_hid_ = nullptr, *d_part_self_ = nullptr, *d_part_cross_ = nullptr;
+  h16 *d_act_[2] = {nullptr, nullptr}, *d_att_[2] = {nullptr, nullptr}, *d_hidp_[2] = {nullptr, nullptr};
+  float* d_part_ = nullptr; float* d_amax_val_ = nullptr; int* d_amax_idx_ = nullptr;
+  float* d_attn_mpart_ = nullptr;     // batched cross-attention in splits: partials and tickets (DecAttnParams::mpart / mcnt)
+  unsigned* d_attn_mcnt_ = nullptr;
+  int *d_tok_ = nullptr, *d_done_ = nullptr, *d_done_none_ = nullptr, *d_nout_ = nullptr, *d_out_ids_ = nullptr, *d_max_new_clip_ = nullptr;
+  int* d_off_ = nullptr;   // per-slot offsets (common.hpp: DecState)
+  int* d_slot_map_ = nullptr;            // [cap]: clip index of an admission pass -> slot
+  DecState* d_state_ = nullptr;
+};
+
+class Engine final : public IEngine, private EngineStreams, private EngineEvents, private EngineMemory, private EngineGraphs, private SlotViews {
  public:
   Engine(const std::string& model_type, const std::string& model_path, const std::string& language, int device, int max_batch);
   ~Engine() override;
@@ -64,8 +145,11 @@ class Engine final : public IEngine {
 
   void construct(const std::string& model_type, const std::string& model_path, const std::string& language, int device, int max_batch);
   void destroy();  // idempotent: the destructor's work, also run when the constructor throws
-  hipStream_t stream() const { return user_stream_ ? user_stream_ : own_stream_; }
-  void* dalloc(size_t bytes, bool zero = false);
+  hipStream_t stream() const { return user_stream_ ? user_stream_ : own_stream_.get(); }
+  // a new buffer of `pool` (allocs_ / slot_allocs_), which owns it
+  template <class T> T* pooled(std::vector<DeviceMem>& pool, size_t n, bool zero = false) {
+    return static_cast<T*>(pool.emplace_back(device_alloc(n * sizeof(T), zero)).get());
+  }
   void load_config(const std::string& dir, const std::string& type, const std::string& language);
   void load_weights(const SafeTensors& st);
   void load_t2s(const std::string& model_path);
@@ -104,38 +188,22 @@ class Engine final : public IEngine {
   void ensure_branch_streams(int batch);
   // the captured step of spec.mode / spec.mask; a scored graph writes the engine's own score arrays (spec.score_out is not read)
   hipGraphExec_t step_graph(StepSpec spec, int batch, int max_new);
+  void drop_step_graph(const StepSpec& spec, int batch, int max_new) { graphs_.erase(graph_key(spec, batch, max_new)); }
   // (two bits for the mode: plain, timestamp and scored steps are three different graphs)
   static long graph_key(const StepSpec& spec, int batch, int max_new) { return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 2) | spec.mode; }
   void require_timestamp_vocab() const;
-  void ensure_ts_logits();  // d_ts_logits_ [cap][ts_stride_], allocated on first use under device_capture_mutex
+  void ensure_ts_logits();  // d_ts_logits_ (SlotViews)
   void enqueue_timestamp_rules(const StepSpec& spec, int batch, const int* d_forced, int n_forced, hipStream_t s);
-  float* d_ts_logits_ = nullptr;
   long ts_stride_ = 0;
-  // scored mode (DESIGN.md "Confidence"): per-clip log-probability and id of every decision [cap][n_text_ctx], log p(<|nospeech|>)
-  // [cap]; allocated like d_ts_logits_. own_scores_: these arrays as the scored rules kernel takes them (decode_forced hands it
-  // its own [batch][n_forced + 1] buffers instead)
-  float* d_tok_lp_ = nullptr; int* d_dec_id_ = nullptr; float* d_nospeech_ = nullptr;
-  TsScoreParams own_scores_{};
   void require_scored_vocab() const;  // require_timestamp_vocab + a usable no_speech id
   void ensure_ts_scores();
   // scores of the last scored greedy loop over `batch` slots (n_ids: what fetch_ids returned)
   void fetch_scores(int batch, const int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
   void recover_streams();
-  // long-form (engine_long.cpp): the PCM and the log-mel rows of every file of one call in one arena, kept for the next call
-  // when small (allocated and freed under device_capture_mutex)
-  struct LongArena {
-    char* base = nullptr; size_t bytes = 0;
-    float *pcm = nullptr, *store = nullptr;
-    long long *pcm_off = nullptr, *frame_off = nullptr;
-    int *n_samples = nullptr, *n_frames = nullptr, *win_file = nullptr, *win_seek = nullptr;
-    unsigned* gmax = nullptr;
-    int n_files = 0, n_windows = 0;
-  } long_;
-  int* h_long_win_ = nullptr; int h_long_win_cap_ = 0;  // pinned [2][windows per pass]: file and seek of every slot
+  // long-form (engine_long.cpp)
   void long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows);  // upload + whole-file front-end
   void long_windows_to_slots(const int* files, const int* seeks, int count, bool want_ref_layout);
   void long_release();
-  void free_long_arena();
   int greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip = nullptr);
   // batch 1: the whole loop as one persistent launch (decode_persistent.hip); returns steps run, -1 if it gave up
   int run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot = 0, int max_new1 = -1, int max_new2 = -1);
@@ -149,15 +217,9 @@ class Engine final : public IEngine {
   bool feature_openai_ = false;  // feature_mode "openai" (engine.cpp load_config)
   int device_ = 0;
   bool device_set_ = false;
-  void* load_stage_ = nullptr;  // staging buffer of load_weights
-  hipStream_t own_stream_ = nullptr, user_stream_ = nullptr;
-  std::vector<hipStream_t> pad_streams_;  // align_graph_queue() (engine_stream.cpp); AX_WHISPER_PAD_STREAMS (diagnostic)
+  hipStream_t user_stream_ = nullptr;  // the caller's (AX_WHISPER_SetStream): not owned
   bool graph_branch_shares_queue(hipGraphExec_t exec, hipStream_t other);
-  static constexpr int kMaxBranches = 4;   // parallel branches of the batched step graph
-  hipStream_t branch_stream_[kMaxBranches - 1] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_fork_ = nullptr, ev_join_[kMaxBranches - 1] = {nullptr, nullptr, nullptr};
-  std::vector<void*> allocs_;       // weights + constants (freed at destruction)
-  std::vector<void*> slot_allocs_;  // capacity-dependent buffers
+  int queue_probe_mask();  // bench "queue_probe" (engine_stream.cpp: beside the probe kernels, which step_graph needs)
 
   // weights
   h16 *conv1_w_ = nullptr, *conv2_w_ = nullptr, *w_cross_kv_ = nullptr, *tok_emb_ = nullptr;
@@ -173,7 +235,6 @@ class Engine final : public IEngine {
   struct CblockFold { float *b_qkv4, *b_o2; const float *s, *c; };  // per layer: [b_qkv; 0], [b_o; d], s = W_cq g, c = W_cq beta + b_cq
   std::vector<CblockFold> cfold_;      // empty: the clip-block step keeps the fused query projection
   bool cfold_all_ = false;             // AX_WHISPER_CBLOCK_QFOLD=2: also in multi-branch steps (A/B, tests)
-  float *d_a0_ = nullptr, *d_statp_ = nullptr;  // [B][d] A0 -> T; [B][d/16][2] block statistics of the residual rows
   void build_cblock_fold();
   std::vector<DecLayerWP> dec_packed_;  // fragment-major copies for the batched decode path
   const h16* tok_emb_packed_ = nullptr;
@@ -185,29 +246,14 @@ class Engine final : public IEngine {
   // capacity-dependent
   int cap_ = 0;
   int t_pad_ = 1536, mel_rows_ = 3004, h1_rows_ = 3002;
-  float* d_pcm_ = nullptr; long pcm_stride_ = 0; float* h_pcm_ = nullptr;
-  // clips longer than a staging row (60 s): their tails, packed, so that the clamp floor comes from ALL frames of the
-  // input however long it is (Whisper.cpp:158-172); grown on demand, empty for ordinary requests
-  float* d_over_ = nullptr; size_t over_cap_ = 0; long long* d_over_off_ = nullptr; bool over_used_ = false;
-  int* d_nsamp_ = nullptr; unsigned* d_gmax_ = nullptr; float* d_logmel_ = nullptr; float* d_mel_ref_ = nullptr;
-  h16 *d_mel_tm_ = nullptr, *d_h1_ = nullptr, *d_ln_ = nullptr, *d_q_ = nullptr, *d_k_ = nullptr, *d_vt_ = nullptr,
-       *d_attn_ = nullptr, *d_ffn_ = nullptr;
-  float* d_x_ = nullptr;
+  long pcm_stride_ = 0;
+  bool over_used_ = false;  // this call put clip tails into d_over_
   static constexpr int kEncPartClips = 2;  // split-K of the encoder's residual GEMMs pays for at most this many clips
-  float* d_enc_part_ = nullptr;
   bool enc_split_k_ = true;
   float enc_rescale_thr_ = 8.f;  // launch_encoder_attention
   int gemv_max_ = 2;             // clips per call up to which the decoder step uses the GEMV family (AX_WHISPER_GEMV_MAX, <= 4)
   int cross_split_env_ = 0;      // AX_WHISPER_CROSS_SPLIT: workgroups per (clip, head) of the batched cross-attention, 0 = by clip count
-  h16 *d_cross_k_ = nullptr, *d_cross_v_ = nullptr, *d_self_k_ = nullptr, *d_self_v_ = nullptr;
-  float *d_xdec_ = nullptr, *d_qdec_ = nullptr, *d_hid_ = nullptr, *d_part_self_ = nullptr, *d_part_cross_ = nullptr;
-  h16 *d_act_[2] = {nullptr, nullptr}, *d_att_[2] = {nullptr, nullptr}, *d_hidp_[2] = {nullptr, nullptr};
-  float* d_part_ = nullptr;
-  float* d_amax_val_ = nullptr; int* d_amax_idx_ = nullptr; int n_amax_part_ = 0;
-  float* d_attn_mpart_ = nullptr;     // batched cross-attention in splits: partials and tickets (DecAttnParams::mpart / mcnt)
-  unsigned* d_attn_mcnt_ = nullptr;
-  int *d_tok_ = nullptr, *d_done_ = nullptr, *d_done_none_ = nullptr, *d_nout_ = nullptr, *d_out_ids_ = nullptr, *d_max_new_clip_ = nullptr;
-  int* d_off_ = nullptr;   // per-slot offsets (common.hpp: DecState)
+  int n_amax_part_ = 0;
   int n_cu_ = 0;            // compute units of the device
   // slot refill (stream_*): a slot is idle -> encoding (admitted, encoder in flight on admit_stream_) -> active (decoding)
   // -> finished (done flag seen) -> idle again after stream_collect
@@ -215,30 +261,13 @@ class Engine final : public IEngine {
   int stream_slots_ = 0;                 // > 0: a stream is open (slots of the step graph: at least 3)
   int stream_user_slots_ = 0;            // the n_slots the caller asked for: the slot indices it may use
   std::vector<int> slot_state_, slot_max_new_;
-  std::vector<hipEvent_t> ev_admit_;     // one per slot: its encoder has finished
-  hipStream_t admit_stream_ = nullptr;
-  int* h_done_live_ = nullptr; int* d_done_live_ = nullptr;  // host-mapped [cap] (and its device alias): advance_kernel raises a clip's
-                                                             // flag the moment it finishes; the host reads it without any wait
-  hipEvent_t ev_step_[3] = {nullptr, nullptr, nullptr};  // the host stays two steps ahead of the device (stream_step)
-  long step_seq_ = 0;
-  hipStream_t copy_stream_ = nullptr;    // stream_collect's D2H copies: never behind the queued decoder steps
-  int* d_slot_map_ = nullptr;            // [cap]: clip index of an admission pass -> slot
-  // admission passes do not wait for one another's encoder: clip lengths and slot maps go through a pinned ring of
-  // kAdmitRing entries (an entry is reused once the pass that filled it has finished), the PCM staging rows are reused once
-  // the previous pass's uploads have landed
-  static constexpr int kAdmitRing = 4;
-  int* h_admit_ring_ = nullptr;          // pinned [kAdmitRing][2][cap]
-  hipEvent_t ev_ring_[kAdmitRing] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_upload_ = nullptr;
-  long admit_seq_ = 0;
+  long step_seq_ = 0;   // decoder steps enqueued on the open stream (ev_step_)
+  long admit_seq_ = 0;  // admission passes of the open stream (h_admit_ring_, ev_ring_)
   void require_no_stream(const char* what) const;
-  DecState* d_state_ = nullptr;
-  int* h_poll_ = nullptr;  // pinned
   int split_self_ = 2, split_cross_ = 6;
   // bench "attn_stamp": every decode_attention launch of a captured step gets a {min begin, max end} slot (DecAttnParams::stamp)
   struct StampMeta { int layer, cross, b0, nb; };
   static constexpr size_t kStampWgs = 4096, kStampLaunches = 256;
-  unsigned long long* d_stamp_ = nullptr;
   std::vector<StampMeta> stamp_meta_;
   unsigned long long* next_stamp(const StepSpec& spec, int layer, int cross, int b0, int nb);
   // persistent batch-1 decode
@@ -254,8 +283,12 @@ class Engine final : public IEngine {
   int vocab_resident_rows_ = 0;        // one-clip launch: vocabulary rows per workgroup held in the poller waves (0: AX_WHISPER_VOCAB_RESIDENT=0 or unsupported width)
   u64* d_gran_ = nullptr; size_t gran_bytes_ = 0;
   float* d_qfold_ = nullptr;  // query-fold arena of the one-clip launch (d_model <= 768), nullptr = unfolded
-  std::map<long, hipGraphExec_t> graphs_;  // key: graph_key
-  hipEvent_t ev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // bench hooks (engine_bench.cpp): one private function per target, each returns what bench() returns
+  float bench_decode_step(const std::string& what, int batch, int arg, int iters);
+  float bench_attn_stamp(int batch, int arg, int iters);
+  float bench_encoder(int batch, int iters);
+  float bench_frontend(int batch, int iters);
+  float bench_frontend_long(int batch, int arg, int iters);
 };
 
 }  // inline namespace AXW_NS

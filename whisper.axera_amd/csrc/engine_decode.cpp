@@ -458,14 +458,13 @@ void Engine::persistent_succeeded() {
 // during capture" on everything enqueued afterwards): they are replaced.
 void Engine::recover_streams() {
   (void)hipGetLastError();
-  auto renew = [](hipStream_t& st) {
+  auto renew = [](Stream& st) {
     if (!st) return;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool bad = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
     if (!bad) return;
-    (void)hipStreamDestroy(st);
-    st = nullptr;
-    (void)hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    st.reset();
+    try { st = make_stream(); } catch (const std::exception&) {}  // (the caller reports the failed capture)
   };
   renew(own_stream_);
   for (auto& b : branch_stream_) renew(b);
@@ -477,7 +476,7 @@ void Engine::ensure_branch_streams(int batch) {
   if (batch <= gemv_max_ || !batched_ln_) return;
   const int nbr = decode_branches(batch);
   for (int i = 1; i < nbr - 1 && i < kMaxBranches - 1; ++i)
-    if (!branch_stream_[i]) HIP_CHECK(hipStreamCreateWithFlags(&branch_stream_[i], hipStreamNonBlocking));
+    if (!branch_stream_[i]) branch_stream_[i] = make_stream();
 }
 
 hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
@@ -485,7 +484,6 @@ hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
   auto it = graphs_.find(key);
   if (it != graphs_.end()) return it->second;
   hipStream_t s = stream();
-  hipGraph_t graph = nullptr;
   // nobody on this device allocates, copies synchronously or captures while this capture is open (iengine.hpp)
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   ensure_branch_streams(batch);  // before the capture opens
@@ -493,28 +491,28 @@ hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
   if (spec.mode == kDecodeScored) { ensure_ts_scores(); spec.score_out = own_scores_; }
   HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   hipError_t cap_err = hipSuccess;
+  hipGraph_t captured = nullptr;
   try {
     enqueue_decode_step(spec, batch, max_new, nullptr, 0, nullptr, 0, nullptr);
-    cap_err = hipStreamEndCapture(s, &graph);
+    cap_err = hipStreamEndCapture(s, &captured);
   } catch (...) {
-    (void)hipStreamEndCapture(s, &graph);
+    (void)hipStreamEndCapture(s, &captured);
+    Graph(captured).reset();  // a capture that fails leaves nothing behind
     recover_streams();
     throw;
   }
+  const Graph graph(captured);  // released on every path out of here, like the exec until graphs_ has it (the probe may throw)
   if (cap_err != hipSuccess || !graph) {  // an invalidated capture must not leave the engine's streams unusable for good
     recover_streams();
     throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(cap_err) + " capturing the decoder step");
   }
-  // graph and exec are released on every path out of here (the probe below may throw)
-  struct Holder {
-    hipGraph_t g;
+  GraphExec exec;
+  auto instantiate = [&] {
     hipGraphExec_t e = nullptr;
-    ~Holder() {
-      if (e) (void)hipGraphExecDestroy(e);
-      if (g) (void)hipGraphDestroy(g);
-    }
-  } hold{graph};
-  HIP_CHECK(hipGraphInstantiate(&hold.e, graph, nullptr, nullptr, 0));
+    HIP_CHECK(hipGraphInstantiate(&e, graph, nullptr, nullptr, 0));
+    exec.reset(e);
+  };
+  instantiate();
   {  // which hardware queue the graph's second branch runs on decides the slot stream's rate (engine_stream.cpp:
      // graph_branch_shares_queue); AX_WHISPER_ALIGN_QUEUES=0: as it falls.
      // ORDER: the probe REPLAYS the step, i.e. runs real decoder steps on whatever state the buffers hold. Every caller
@@ -523,25 +521,19 @@ hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
     if (align && !user_stream_ && batch > gemv_max_ && batched_ln_ && decode_branches(batch) >= 2 && spec.mask == 15) {
       constexpr size_t kMaxPadStreams = 8;  // per engine, whatever the number of distinct (batch, max_new) graphs a server sees
       int tries = 0;
-      bool aligned = graph_branch_shares_queue(hold.e, branch_stream_[0]);
+      bool aligned = graph_branch_shares_queue(exec, branch_stream_[0]);
       while (!aligned && tries < 4 && pad_streams_.size() < kMaxPadStreams) {
-        HIP_CHECK(hipGraphExecDestroy(hold.e));
-        hold.e = nullptr;
-        hipStream_t pad = nullptr;
-        HIP_CHECK(hipStreamCreateWithFlags(&pad, hipStreamNonBlocking));
-        pad_streams_.push_back(pad);
-        HIP_CHECK(hipGraphInstantiate(&hold.e, graph, nullptr, nullptr, 0));
+        exec.reset();  // (before the pad stream is made, as the order of these two decides the queues)
+        pad_streams_.push_back(make_stream());
+        instantiate();
         ++tries;
-        aligned = graph_branch_shares_queue(hold.e, branch_stream_[0]);  // the exec that is kept is the one that was probed
+        aligned = graph_branch_shares_queue(exec, branch_stream_[0]);  // the exec that is kept is the one that was probed
       }
       cfg_.ints["graph_queue_tries"] = tries;
       cfg_.ints["graph_queue_aligned"] = aligned ? 1 : 0;
     }
   }
-  hipGraphExec_t exec = hold.e;
-  hold.e = nullptr;  // kept: owned by graphs_ from here on
-  graphs_[key] = exec;
-  return exec;
+  return graphs_[key] = std::move(exec);
 }
 
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.
@@ -632,11 +624,10 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
   p.gran_bytes = (int)gran_bytes_;
   p.err = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d_gran_) + gran_bytes_ - 8);
   p.out_ids = d_out_ids_ + (size_t)slot * Tc; p.n_out = d_nout_ + slot; p.state = d_state_;
-  long long* d_prof = nullptr;
+  DeviceArray<long long> d_prof;
   const char* prof_path = getenv("AX_WHISPER_PERSIST_PROF");  // debugging aid: per-workgroup, per-phase time of the launch
   if (prof_path) {
-    HIP_CHECK(hipMalloc((void**)&d_prof, (size_t)persist_grid_ * 64 * 8));
-    HIP_CHECK(hipMemset(d_prof, 0, (size_t)persist_grid_ * 64 * 8));
+    d_prof = device_array<long long>((size_t)persist_grid_ * 64, true);
   }
   p.prof = d_prof;
   { const char* pc = getenv("AX_WHISPER_PERSIST_PROF_CLIP"); p.prof_clip = pc && pc[0] == '1'; }
@@ -656,7 +647,6 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
   if (d_prof) {
     std::vector<long long> hp((size_t)persist_grid_ * 64);
     HIP_CHECK(hipMemcpy(hp.data(), d_prof, hp.size() * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(d_prof);
     if (FILE* f = fopen(prof_path, "w")) {
       fprintf(f, "# steps %d grid %d; rows = workgroups, columns 0-31 = phase tick sums, 32-63 = absolute ticks of one layer (100 MHz)\n", h_poll_[9], persist_grid_);
       for (int g = 0; g < persist_grid_; ++g) {
@@ -685,8 +675,7 @@ void Engine::ensure_ts_logits() {
   if (d_ts_logits_) return;
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   ts_stride_ = ((long)cfg_.n_vocab + 3) / 4 * 4;  // 16-byte rows for the rules kernel's loads
-  d_ts_logits_ = (float*)dalloc((size_t)cap_ * ts_stride_ * 4, true);
-  slot_allocs_.push_back(d_ts_logits_);  // freed (and re-made at the new capacity) with the other slot buffers
+  d_ts_logits_ = pooled<float>(slot_allocs_, (size_t)cap_ * ts_stride_, true);  // freed (and re-made at the new capacity) with the other slot buffers
 }
 
 // Between the logits launch and advance_kernel: one argmax partial per sampling clip, chosen under the timestamp rules
@@ -713,10 +702,9 @@ void Engine::ensure_ts_scores() {
   if (d_tok_lp_) return;
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   const size_t n = (size_t)cap_ * cfg_.n_text_ctx;
-  d_tok_lp_ = (float*)dalloc(n * 4, true);
-  d_dec_id_ = (int*)dalloc(n * 4, true);
-  d_nospeech_ = (float*)dalloc((size_t)cap_ * 4, true);
-  for (void* p : {(void*)d_tok_lp_, (void*)d_dec_id_, (void*)d_nospeech_}) slot_allocs_.push_back(p);  // freed (and re-made) with the slot buffers
+  d_tok_lp_ = pooled<float>(slot_allocs_, n, true);  // (freed and re-made with the slot buffers)
+  d_dec_id_ = pooled<int>(slot_allocs_, n, true);
+  d_nospeech_ = pooled<float>(slot_allocs_, cap_, true);
   own_scores_ = TsScoreParams{d_tok_lp_, d_dec_id_, (long)cfg_.n_text_ctx, d_nospeech_, (int)cfg_.ints.at("no_speech")};
 }
 

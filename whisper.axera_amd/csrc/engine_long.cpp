@@ -14,17 +14,11 @@ static size_t long_max_bytes() {
 }
 static constexpr size_t kLongKeepBytes = (size_t)256 << 20;  // an arena up to this size stays allocated for the next call
 
-void Engine::free_long_arena() {
-  if (long_.base) (void)hipFree(long_.base);
-  long_ = LongArena{};
-  if (h_long_win_) { (void)hipHostFree(h_long_win_); h_long_win_ = nullptr; h_long_win_cap_ = 0; }
-}
-
 void Engine::long_release() {
   if (long_.bytes <= kLongKeepBytes) return;
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipStreamSynchronize(stream()));
-  free_long_arena();
+  long_ = LongArena{};
 }
 
 // pcm == nullptr: n_files files of silence (bench)
@@ -71,13 +65,13 @@ void Engine::long_prepare(const float* const* pcm, const int* n_samples, int n_f
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipStreamSynchronize(stream()));  // an earlier call on this stream may still read the arena
   if (o > long_.bytes) {
-    free_long_arena();
-    HIP_CHECK(hipMalloc((void**)&long_.base, o));
+    long_ = LongArena{};  // (first: the old and the new arena need not fit side by side)
+    long_.base = device_array<char>(o);
     long_.bytes = o;
   }
   if (n_windows > h_long_win_cap_) {
-    if (h_long_win_) { (void)hipHostFree(h_long_win_); h_long_win_ = nullptr; h_long_win_cap_ = 0; }
-    HIP_CHECK(hipHostMalloc((void**)&h_long_win_, (size_t)2 * n_windows * 4, hipHostMallocDefault));
+    h_long_win_cap_ = 0;
+    h_long_win_ = pinned_array<int>((size_t)2 * n_windows);
     h_long_win_cap_ = n_windows;
   }
   char* a = long_.base;
