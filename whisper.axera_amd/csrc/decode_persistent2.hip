@@ -201,9 +201,9 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
               const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)kc, 0, on ? 8192 : 0, 0x27000);  // (0 bytes: loads return 0, no traffic)
               const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vc, 0, on ? 8192 : 0, 0x27000);
 #pragma unroll
-              for (int i = 0; i < 8; ++i) kr[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, layout::kv_chunk_offset(0, i, lane) * 2, 0, 1);  // sc0: past L1
+              for (int i = 0; i < 8; ++i) kr[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, attn_regs_piece(i, lane) * 2, 0, 1);  // sc0: past L1
 #pragma unroll
-              for (int i = 0; i < 8; ++i) vr[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, layout::kv_chunk_offset(0, i, lane) * 2, 0, 1);
+              for (int i = 0; i < 8; ++i) vr[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, attn_regs_piece(i, lane) * 2, 0, 1);
             }
             unsigned v[2];
             const bool fail = gather2<1>(GR, tag, v, p.err, ctl, qkv_pair(c));
@@ -228,7 +228,27 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
             }
             if (fail) ctl[0] = 1;
             AXW_BARRIER_CHECK(0x200 + l)
-            {
+            if constexpr (kAttnMfma) {
+              // piece 2 b + ks holds, of K, dims 8 (4 ks + lane / 16) .. + 7 of key 16 b + lane % 16, and of the transposed V, keys
+              // 8 (4 ks + lane / 16) .. + 7 of dim 16 b + lane % 16
+              const bool mine = pw == (step >> 6);
+              const int g = lane >> 4, col = lane & 15, w_s = (step & 7) >> 1;
+              const bool vlane = mine && g == ((step >> 3) & 3);
+#pragma unroll
+              for (int i = 0; i < 8; ++i) {
+                const int b = i >> 1, ks = i & 1;
+                const u32x4 kn = *reinterpret_cast<const u32x4*>(kvtc[c] + (4 * ks + g) * 8);
+                const unsigned nv = reinterpret_cast<const unsigned short*>(kvtc[c])[64 + 16 * b + col];
+                const bool klane = mine && 16 * b + col == (step & 63);
+                const bool vpiece = vlane && ks == ((step >> 5) & 1);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  kr[i][e] = klane ? kn[e] : kr[i][e];
+                  const unsigned pv = (step & 1) ? ((vr[i][e] & 0xffffu) | (nv << 16)) : ((vr[i][e] & 0xffff0000u) | nv);
+                  vr[i][e] = (vpiece && e == w_s) ? pv : vr[i][e];
+                }
+              }
+            } else {
               const bool mine = pw == (step >> 6);  // this step's key is in this wave's block: key step % 64
               const int i_s = (step >> 3) & 7, w_s = (step & 7) >> 1;
               const unsigned nv = reinterpret_cast<const unsigned short*>(kvtc[c])[64 + lane];

@@ -37,7 +37,13 @@ constexpr int CT = NCW * 64;       // compute threads
 #ifndef AXW_KV_NT_LDS
 #define AXW_KV_NT_LDS 1
 #endif
+// The 64-key attention block's two products on the matrix pipe (1, attn_block below) or as v_dot2c / FMA dot products on the
+// vector pipe (0, the form of rounds 5-7, kept for the A/B: profiles/attn_matrix_pipe_ab.txt)
+#ifndef AXW_ATTN_MFMA
+#define AXW_ATTN_MFMA 1
+#endif
 constexpr bool kVocabNT = AXW_VOCAB_NT != 0;
+constexpr bool kAttnMfma = AXW_ATTN_MFMA != 0;
 constexpr int kKvAux = AXW_KV_NT_LDS ? 2 : 0;  // aux bits of global_load_lds: 2 = nt
 constexpr int kSpinFree = 1024;
 constexpr long long kSpinTicks = 5000000;
@@ -314,16 +320,141 @@ __device__ __forceinline__ u32x4 kv_global16(const h16* base, int off) {
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 8192, 0x27000);  // one 64-key block
   return __builtin_amdgcn_raw_buffer_load_b128(rs, off * 2, 0, 1);  // aux 1 = sc0
 }
-// One wave, one block of 64 keys in LDS: kblk = [8 (d/8)][64 keys][8] h16 (lane = key for the scores). Writes the
-// softmax partial (m, l, o[64]) to part[0..66). qp: the query as packed h16 pairs, [32] hi then [32] lo (q = hi + lo).
-// pw: 64 dwords of wave-private LDS scratch.
-// The block is VALU-bound (two compute waves share a SIMD; skipping its arithmetic altogether shortens the decode of
-// one clip by 12.6 %), so it is written for instruction count: the scores are v_dot2c dot products of the packed K
-// dwords with the packed query (2 instructions per 2 dims instead of 4), and for the self-attention cache, whose LDS
-// layout is this kernel's own, V is kept TRANSPOSED (VT: vblk = [8 (key/8)][64 dims][8 keys]) so that lane = dim
-// accumulates o[dim] with dot2 over key pairs against the packed probabilities — no unpacking, no cross-lane sums.
-// Cross-attention V tiles arrive by LDS-DMA in the HBM layout [64 keys][64 dims] and keep the lane = (key row, dim
-// chunk) form.
+// One wave, one block of 64 keys in LDS: kblk = [8 (d/8)][64 keys][8] h16. Writes the softmax partial (m, l, o[64]) to
+// part[0..66). qp: the query as packed h16 pairs, [32] hi then [32] lo (q = hi + lo). pw: 64 dwords of wave-private LDS
+// scratch. lane = key for the scores and the mask, lane = dim for the output.
+// Two compute waves share a SIMD and the block was VALU-bound as dot products (skipping its arithmetic altogether shortened
+// the decode of one clip by 12.6 %), so both products run on the matrix pipe, which nothing else in this launch uses:
+// v_mfma_f32_16x16x32 with the one-row operand (the query over dims, then the probabilities over keys) as A and the LDS tiles
+// as they are as B.
+//   A: lane l holds row l & 15, k = 8 (l >> 4) + j. Even rows carry the hi half of the (hi, lo) pair and odd rows the lo half
+//      (attn_a_frag: one ds_read_b128 from the packed pairs, eight distinct addresses per wave), so lane group g = l >> 4 finds
+//      hi . B in result register 0 and lo . B in register 1 (and the same again in 2 and 3: the rows of a product are
+//      independent, a spare row costs nothing and needs neither a zero piece nor a mask).
+//   B of the scores, key block kb, k-step ks (32 dims): the piece kv_chunk_offset(blk, 4 ks + l / 16, 16 kb + l % 16) of the
+//      blocked K. Four accumulators, one per 16-key block; lane group g takes acc[g][0] + acc[g][1], the score of key l.
+//      A masked key's K row may hold anything: it reaches its own column only, and that column is set to -inf.
+//   B of the output, dim block nb, k-step ks (32 keys): from the TRANSPOSED self-attention cache (VT: vblk = [8 (key/8)][64
+//      dims][8 keys], this kernel's own layout) the piece kv_chunk_offset(blk, 4 ks + l / 16, 16 nb + l % 16); from a row-major
+//      cross tile [64 keys][64 dims] (LDS-DMA in the HBM layout) two ds_read_b64_tr_b16 of keys 32 ks + 8 (l / 16) + {0..3},
+//      {4..7}, dims 16 nb .. + 15. Lane group g takes oc[g][0] + oc[g][1] = o[l].
+// The transposed reads and the MFMAs need EXEC all ones: every call site is wave-uniform (cw < nblk, a unit's waves).
+// LDS banks of the transposed reads on 128-byte V rows ((a / 4) % 64 per 32-lane half): rows q and q + 2 of a 4-row block and
+// the two blocks of a half (8 rows = 1 KiB apart) fall on the same eight banks, so a read is 4-way: 8 LDS cycles instead of
+// 2, 16 reads per block (HISTORY.md, round-8 notes: what a source-side swizzle of the tile's DMA would do about it).
+__device__ __forceinline__ h16x8 attn_a_frag(const unsigned* xp, int ks, int lane) {
+  return __builtin_bit_cast(h16x8, *reinterpret_cast<const u32x4*>(xp + 32 * (lane & 1) + 16 * ks + 4 * (lane >> 4)));
+}
+// lane group g = lane / 16 takes (hi + lo) of accumulator g
+__device__ __forceinline__ float attn_pick(const f32x4 (&acc)[4], int lane) {
+  const float s0 = acc[0][0] + acc[0][1], s1 = acc[1][0] + acc[1][1], s2 = acc[2][0] + acc[2][1], s3 = acc[3][0] + acc[3][1];
+  const int g = lane >> 4;
+  return g == 0 ? s0 : g == 1 ? s1 : g == 2 ? s2 : s3;
+}
+// this lane's h16 offset of B piece (blk kb or nb, k-step ks) in a blocked K or transposed V block
+__device__ __forceinline__ int attn_b_offset(int nb, int ks, int lane) { return layout::kv_chunk_offset(0, 4 * ks + (lane >> 4), 16 * nb + (lane & 15)); }
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
+// B piece (nb, ks) of a row-major V tile: two transposed reads (every lane of the wave active)
+__device__ __forceinline__ h16x8 attn_b_rowmajor(const h16* vblk, int nb, int ks, int lane) {
+  const int g = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;
+  const h16* a = vblk + layout::v_index(32 * ks + 8 * g + q, 16 * nb + 4 * pc);
+  struct { s16x4 lo, hi; } r;
+  r.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)a);
+  r.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(a + layout::v_index(4, 0)));
+  return __builtin_bit_cast(h16x8, r);
+}
+// scale, mask and softmax partial of the block (lane = key): returns the probability, m and l in every lane
+__device__ __forceinline__ float attn_softmax(float s, bool valid, float* m_out, float* l_out) {
+  s *= 0.125f;  // (64^-0.25)^2, export_onnx.py:116,124-126
+  if (!valid) s = -INFINITY;
+  const float m = wmax(s);  // -inf only for a block without a single valid key
+  const float pk = m > -INFINITY ? __expf(s - m) : 0.f;
+  *m_out = m;
+  *l_out = wsum(pk);
+  return pk;
+}
+// probabilities as packed (hi, lo) h16 in wave-private LDS: key k -> half-word k of ph (dwords 0..31) / pl (32..63)
+__device__ __forceinline__ void attn_put_p(float pk, float* pw, int lane) {
+  const h16 ph = (h16)pk, pl = (h16)(pk - (float)ph);
+  reinterpret_cast<h16*>(pw)[lane] = ph;
+  reinterpret_cast<h16*>(pw + 32)[lane] = pl;
+  __builtin_amdgcn_wave_barrier();
+}
+#if AXW_ATTN_MFMA
+template <bool VT>
+__device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, const unsigned* qp, bool valid, float* pw, float* part, int lane) {
+#ifdef AXW_ATTN_SKIP  // timing-only build (wrong results): bounds what any speed-up of this block's arithmetic can buy
+  if (lane == 0) { part[0] = 0.f; part[1] = 1.f; }
+  part[2 + lane] = 0.f;
+  return;
+#endif
+  f32x4 acc[4];
+  {
+    const h16x8 a0 = attn_a_frag(qp, 0, lane), a1 = attn_a_frag(qp, 1, lane);
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      const h16x8 b0 = *reinterpret_cast<const h16x8*>(kblk + attn_b_offset(kb, 0, lane)), b1 = *reinterpret_cast<const h16x8*>(kblk + attn_b_offset(kb, 1, lane));
+      acc[kb] = AXW_MFMA_16x16x32(a0, b0, (f32x4{0.f, 0.f, 0.f, 0.f}));
+      acc[kb] = AXW_MFMA_16x16x32(a1, b1, acc[kb]);
+      if (kb == 1) __builtin_amdgcn_sched_barrier(0);  // two 16-key blocks' operands in flight at a time: the row producers hold weight rows here
+    }
+  }
+  float m, lsum;
+  const float pk = attn_softmax(attn_pick(acc, lane), valid, &m, &lsum);
+  attn_put_p(pk, pw, lane);
+  const unsigned* pwu = reinterpret_cast<const unsigned*>(pw);
+  const h16x8 a0 = attn_a_frag(pwu, 0, lane), a1 = attn_a_frag(pwu, 1, lane);
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+    h16x8 b0, b1;
+    if constexpr (VT) {
+      b0 = *reinterpret_cast<const h16x8*>(vblk + attn_b_offset(nb, 0, lane));
+      b1 = *reinterpret_cast<const h16x8*>(vblk + attn_b_offset(nb, 1, lane));
+    } else {
+      b0 = attn_b_rowmajor(vblk, nb, 0, lane);
+      b1 = attn_b_rowmajor(vblk, nb, 1, lane);
+    }
+    acc[nb] = AXW_MFMA_16x16x32(a0, b0, (f32x4{0.f, 0.f, 0.f, 0.f}));
+    acc[nb] = AXW_MFMA_16x16x32(a1, b1, acc[nb]);
+    if (nb == 1) __builtin_amdgcn_sched_barrier(0);
+  }
+  if (lane == 0) { part[0] = m; part[1] = lsum; }
+  part[2 + lane] = attn_pick(acc, lane);
+}
+
+// attn_block<true> on a block whose 16 pieces are already in registers, in the order the products consume them (kr[2 kb + ks],
+// vr[2 nb + ks]: the pieces attn_b_offset(kb or nb, ks, lane) of the blocked K / the transposed V): the same operations in the
+// same order, so a block gives the same bits from either home.
+__device__ __forceinline__ int attn_regs_piece(int i, int lane) { return attn_b_offset(i >> 1, i & 1, lane); }
+__device__ __forceinline__ void attn_block_regs(const u32x4 (&kr)[8], const u32x4 (&vr)[8], const unsigned* qp, bool valid, float* pw, float* part, int lane) {
+  f32x4 acc[4];
+  {
+    const h16x8 a0 = attn_a_frag(qp, 0, lane), a1 = attn_a_frag(qp, 1, lane);
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      acc[kb] = AXW_MFMA_16x16x32(a0, __builtin_bit_cast(h16x8, kr[2 * kb]), (f32x4{0.f, 0.f, 0.f, 0.f}));
+      acc[kb] = AXW_MFMA_16x16x32(a1, __builtin_bit_cast(h16x8, kr[2 * kb + 1]), acc[kb]);
+    }
+  }
+  float m, lsum;
+  const float pk = attn_softmax(attn_pick(acc, lane), valid, &m, &lsum);
+  attn_put_p(pk, pw, lane);
+  const unsigned* pwu = reinterpret_cast<const unsigned*>(pw);
+  const h16x8 a0 = attn_a_frag(pwu, 0, lane), a1 = attn_a_frag(pwu, 1, lane);
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+    acc[nb] = AXW_MFMA_16x16x32(a0, __builtin_bit_cast(h16x8, vr[2 * nb]), (f32x4{0.f, 0.f, 0.f, 0.f}));
+    acc[nb] = AXW_MFMA_16x16x32(a1, __builtin_bit_cast(h16x8, vr[2 * nb + 1]), acc[nb]);
+  }
+  if (lane == 0) { part[0] = m; part[1] = lsum; }
+  part[2 + lane] = attn_pick(acc, lane);
+}
+#else  // AXW_ATTN_MFMA == 0: the vector-pipe form
+// The block as dot products on the vector pipe, written for instruction count: the scores are v_dot2c dot products of the
+// packed K dwords with the packed query (2 instructions per 2 dims instead of 4); with the transposed V, lane = dim accumulates
+// o[dim] with dot2 over key pairs against the packed probabilities; a row-major cross tile keeps the lane = (key row, dim chunk)
+// form and sums over lane bits 3-5.
 template <bool VT>
 __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, const unsigned* qp, bool valid, float* pw, float* part, int lane) {
 #ifdef AXW_ATTN_SKIP  // timing-only build (wrong results): bounds what any speed-up of this block's arithmetic can buy
@@ -401,6 +532,7 @@ __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, con
 
 // attn_block<true> on a block whose 16 pieces are already in registers (kr[i]: dims 8i..8i+7 of key `lane`; vr[i]: keys
 // 8i..8i+7 of dim `lane`): the same operations in the same order, so a block gives the same bits from either home.
+__device__ __forceinline__ int attn_regs_piece(int i, int lane) { return layout::kv_chunk_offset(0, i, lane); }
 __device__ __forceinline__ void attn_block_regs(const u32x4 (&kr)[8], const u32x4 (&vr)[8], const unsigned* qp, bool valid, float* pw, float* part, int lane) {
   float sc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -439,6 +571,7 @@ __device__ __forceinline__ void attn_block_regs(const u32x4 (&kr)[8], const u32x
   if (lane == 0) { part[0] = m; part[1] = lsum; }
   part[2 + lane] = o0 + o1;
 }
+#endif  // AXW_ATTN_MFMA
 
 // merge nb (<= NCW) wave partials (m, l, o[64]) in LDS: returns (l, o[c]) rescaled to the common maximum *m_out.
 // Unrolled over all NCW records with blocks >= nb masked: every LDS read goes out at once and the exponentials are
