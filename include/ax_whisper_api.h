@@ -269,6 +269,63 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongOpts(AX_WHISPER_HANDLE handle, float* pc
 AX_WHISPER_API int AX_WHISPER_RunFileLongOpts(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
                                               float logprob_threshold, char** result);
 
+/* ---- temperature fallback: seeded sampling in the rules kernel, long-form retry (DESIGN.md "Temperature fallback")
+ * Sampled decode mode is scored mode with a temperature t[b] and a random stream id per clip, and one seed per call. At a sampled
+ * step of a clip with t > 0 the decision is drawn from softmax(x[A] / t) over the final allowed set A of rules 1-5 (openai-whisper's
+ * Categorical(logits / temperature)), by Gumbel-max: c = argmax over A of x[i] / t - log(-log(u_i)), lowest id on ties, NaN logits
+ * masked. u_i = ((w >> 9) + 0.5) * 2^-23 where w is word i & 3 of Philox4x32-10 with key (seed low, seed high) and counter
+ * (i >> 2, n, stream low, stream high), n = the clip's history length: equal (seed, stream, n) give equal noise at any batch position,
+ * in any batch, on any device. The rules themselves are decided on the untempered logits, and the recorded log-probability stays
+ * the untempered x[c] - logsumexp(x[A]). A clip with t = 0 decides as scored mode does. Temperatures must be 0, or finite and >= 1e-6 (below that x / t
+ * overflows float32 for ordinary logits; at any t a quotient that does overflow has key +-inf, and equal keys go to the lowest id). */
+/** ScoreTimestampRules with temperature [batch], stream [batch] and seed: the sampled rules kernel alone on host data. Unlike
+ *  ScoreTimestampRules, a batch above the handle's current capacity grows it: the slots' cross K/V of earlier calls is then lost. */
+AX_WHISPER_API int AX_WHISPER_SampleTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                                   int batch, const float* temperature, const uint64_t* stream, uint64_t seed,
+                                                   int32_t* chosen, float* logprob);
+/** DecodeForcedTimestampScores in sampled mode: chosen [batch][n_forced+1] are the ids drawn at each step. */
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampSampled(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
+                                                           const float* temperature, const uint64_t* stream, uint64_t seed,
+                                                           float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob,
+                                                           float* logits0);
+/** RunPCMBatchTimestampScores in sampled mode. Sharded over the handle's devices; the stream ids are the caller's, so the
+ *  results do not depend on the sharding. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampSampled(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                          int batch, int max_new, const int* max_new_clip, const float* temperature,
+                                                          const uint64_t* stream, uint64_t seed, int32_t* ids, int* n_ids,
+                                                          float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
+/** Host only (no handle, no GPU): *ratio = n / (bytes of zlib's compress() at its default level), openai-whisper's
+ *  compression_ratio; n = 0 gives 0 / 8 = 0. zlib's runtime library (libz.so.1) is loaded at first use; -1 (AX_WHISPER_LastError(NULL))
+ *  when it is missing. */
+AX_WHISPER_API int AX_WHISPER_CompressionRatio(const unsigned char* bytes, int n, float* ratio);
+/** Host only: openai-whisper's fallback rule, in float32. 1 iff compression_ratio > compression_ratio_threshold or avg_logprob <
+ *  logprob_threshold — but 0 when exp(no_speech_logprob) > no_speech_threshold and avg_logprob < logprob_threshold (a silent window
+ *  is left to the silent-window rule). A NaN threshold switches its part off. openai-whisper's values are 2.4, -1.0 and 0.6. */
+AX_WHISPER_API int AX_WHISPER_WindowNeedsFallback(float compression_ratio, float avg_logprob, float no_speech_logprob,
+                                                  float compression_ratio_threshold, float logprob_threshold, float no_speech_threshold);
+/** RunPCMLongWindowsScored with temperature fallback. Attempt a of a window is decoded at temperatures[a] (1 .. 16 values, the first
+ *  usually 0; openai-whisper: 0, 0.2, .. 1.0), one sample each. The window's text is the raw bytes of its ids below eot with ASCII
+ *  whitespace stripped at both ends; a window whose text and scores need fallback (WindowNeedsFallback) and that has attempts left
+ *  does not advance: it is encoded and decoded again in the next pass. The last attempt is kept whatever it gives; the silent-window
+ *  rule and the window rule then apply to the kept attempt. Every attempt is a log entry: win_score[k*7 .. k*7+6] = no_speech_logprob,
+ *  avg_logprob, skipped, attempt, temperature, compression_ratio, kept (0 / 1); an attempt that is not kept has advance 0. The random
+ *  stream of a window is (seek, file id * 16 + attempt). file_ids [n_files] (each 0 .. 2^27 - 1) are the caller's names for its files;
+ *  NULL: a file's id is its index in this call. Equal (seed, file id) give a file the same windows beside any other files, at any
+ *  position in the call and on any number of devices; with NULL that holds for a file at the same index only (a file moved to
+ *  another index draws other noise). RunPCMLongFallback / RunFileLongFallback use file id 0. Not covered: best_of > 1, beam search, prompt reset, the Stream* calls. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsFallback(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                        int n_files, int max_new, int max_passes, float no_speech_threshold,
+                                                        float logprob_threshold, float compression_ratio_threshold,
+                                                        const float* temperatures, int n_temperatures, uint64_t seed, const int* file_ids,
+                                                        int win_cap, int* win_info, int32_t* ids, float* win_score, int* n_windows);
+/** RunPCMLongOpts / RunFileLongOpts with temperature fallback: the text of the kept attempts. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongFallback(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                                 float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                 int n_temperatures, uint64_t seed, char** result);
+AX_WHISPER_API int AX_WHISPER_RunFileLongFallback(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
+                                                  float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                  int n_temperatures, uint64_t seed, char** result);
+
 /** Host only (no handle, no GPU): the decode path Init picks for a decoder shape on a device with n_cu compute units, and the
  *  persistent launch's cross-attention role assignment, from the engine's own functions. plan4[0] = workgroups of the
  *  persistent launch, [1] = 1 iff the shape gets it (GetConfigInt "persistent_decode"), [2] = clips per launch
@@ -284,7 +341,8 @@ AX_WHISPER_API int AX_WHISPER_PersistentDecodePlan(int d_model, int n_head, int 
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
 /** Time `iters` launches of one named piece on the handle's stream with hipEvents; returns
  *  total ms in *ms_total. what: "decode_step" (one captured step graph at decode offset
- *  `arg`), "decode_step_ts" (the same step in timestamp mode), "decode_step_ts_scored" (in scored mode), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
+ *  `arg`), "decode_step_ts" (the same step in timestamp mode), "decode_step_ts_scored" (in scored mode), "decode_step_ts_sampled" (in sampled mode, every clip at temperature
+ *  $AX_WHISPER_BENCH_TEMPERATURE, default 1), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
  *  files of `arg` seconds + one window kernel), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);

@@ -82,6 +82,14 @@ SYMBOLS = {
     "AX_WHISPER_RunPCMLongWindowsScored": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_RunPCMLongOpts": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_RunFileLongOpts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_SampleTimestampRules": (C.c_int, [C.c_void_p, fp, ip, C.POINTER(C.c_int), C.c_int, fp, C.POINTER(C.c_uint64), C.c_uint64, ip, fp]),
+    "AX_WHISPER_DecodeForcedTimestampSampled": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, fp, C.POINTER(C.c_uint64), C.c_uint64, fp, ip, fp, fp, fp]),
+    "AX_WHISPER_RunPCMBatchTimestampSampled": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), fp, C.POINTER(C.c_uint64), C.c_uint64, ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_CompressionRatio": (C.c_int, [C.c_char_p, C.c_int, fp]),
+    "AX_WHISPER_WindowNeedsFallback": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "AX_WHISPER_RunPCMLongWindowsFallback": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongFallback": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunFileLongFallback": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_PersistentDecodePlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
@@ -182,6 +190,28 @@ def long_window_is_silent(no_speech_logprob: float, avg_logprob: float, no_speec
     no_speech_threshold and not avg_logprob > logprob_threshold, in float32."""
     L = load_library()
     return bool(L.AX_WHISPER_LongWindowIsSilent(float(no_speech_logprob), float(avg_logprob), float(no_speech_threshold), float(logprob_threshold)))
+
+
+DEFAULT_TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)  # openai-whisper's
+
+
+def compression_ratio(data) -> float:
+    """len(bytes) / len(zlib.compress(bytes)) (AX_WHISPER_CompressionRatio, host only); str is taken as UTF-8."""
+    L = load_library()
+    b = data.encode("utf-8") if isinstance(data, str) else bytes(data)
+    out = C.c_float()
+    if L.AX_WHISPER_CompressionRatio(b, len(b), C.byref(out)) != 0:
+        raise RuntimeError("AX_WHISPER_CompressionRatio failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return out.value
+
+
+def window_needs_fallback(compression_ratio: float, avg_logprob: float, no_speech_logprob: float, compression_ratio_threshold=None,
+                          logprob_threshold=None, no_speech_threshold=None) -> bool:
+    """openai-whisper's fallback rule (AX_WHISPER_WindowNeedsFallback, host only); None switches a threshold's part off."""
+    L = load_library()
+    nan = lambda v: float("nan") if v is None else float(v)
+    return bool(L.AX_WHISPER_WindowNeedsFallback(float(compression_ratio), float(avg_logprob), float(no_speech_logprob),
+                                                 nan(compression_ratio_threshold), nan(logprob_threshold), nan(no_speech_threshold)))
 
 
 def persistent_decode_plan(d_model: int, n_head: int, n_layer: int, n_cu: int, n_clips: int = 0, t0: int = 0, n_slots: int = 0):
@@ -358,6 +388,69 @@ class Whisper:
         self._check(self.L.AX_WHISPER_NoSpeechLogProb(self.h, lg.ctypes.data_as(fp), lg.shape[0], out.ctypes.data_as(fp)), "NoSpeechLogProb")
         return out
 
+    # ---- temperature fallback: seeded sampling in the rules kernel (DESIGN.md "Temperature fallback")
+    @staticmethod
+    def _sample_args(B, temperature, stream):
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=np.float32), (B,)))
+        st = np.ascontiguousarray(np.broadcast_to(np.asarray(stream, dtype=np.uint64), (B,)))
+        return t, st
+
+    def sample_timestamp_rules(self, logits, histories, temperature, stream, seed: int = 0):
+        """The sampled rules kernel alone: score_timestamp_rules with a temperature and a stream id per clip (scalars are
+        broadcast) and one seed -> (drawn ids, their untempered log-probabilities)."""
+        lg = _f32(logits).reshape(-1, self.n_vocab)
+        B = lg.shape[0]
+        hist = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        nh = (C.c_int * B)()
+        for b, h in enumerate(histories):
+            hist[b, : len(h)] = h
+            nh[b] = len(h)
+        t, st = self._sample_args(B, temperature, stream)
+        out = np.zeros(B, dtype=np.int32)
+        lp = np.zeros(B, dtype=np.float32)
+        self._check(self.L.AX_WHISPER_SampleTimestampRules(self.h, lg.ctypes.data_as(fp), hist.ctypes.data_as(ip), nh, B, t.ctypes.data_as(fp),
+                                                            st.ctypes.data_as(C.POINTER(C.c_uint64)), int(seed), out.ctypes.data_as(ip),
+                                                            lp.ctypes.data_as(fp)), "SampleTimestampRules")
+        return out.tolist(), lp
+
+    def decode_forced_timestamp_sampled(self, batch: int, forced, temperature, stream, seed: int = 0, want_logits: bool = True,
+                                        want_logits0: bool = False):
+        """decode_forced_timestamp_scores in sampled mode -> (logits, chosen, logprob, no_speech_logprob, logits0)."""
+        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
+        n = f.shape[1]
+        t, st = self._sample_args(batch, temperature, stream)
+        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
+        l0 = np.empty((batch, self.n_vocab), dtype=np.float32) if want_logits0 else None
+        ch = np.empty((batch, n + 1), dtype=np.int32)
+        lp = np.empty((batch, n + 1), dtype=np.float32)
+        nsp = np.empty(batch, dtype=np.float32)
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampSampled(self.h, batch, f.ctypes.data_as(ip), n, t.ctypes.data_as(fp),
+                                                                   st.ctypes.data_as(C.POINTER(C.c_uint64)), int(seed),
+                                                                   logits.ctypes.data_as(fp) if want_logits else None, ch.ctypes.data_as(ip),
+                                                                   lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
+                                                                   l0.ctypes.data_as(fp) if want_logits0 else None), "DecodeForcedTimestampSampled")
+        return logits, ch, lp, nsp, l0
+
+    def run_timestamp_sampled_batch(self, clips, temperature, stream, seed: int = 0, max_new: int = 0, max_new_clip=None):
+        """run_timestamp_scores_batch in sampled mode (AX_WHISPER_RunPCMBatchTimestampSampled): the same dict per clip."""
+        clips = [_f32(c) for c in clips]
+        B = len(clips)
+        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
+        lens = (C.c_int * B)(*[len(c) for c in clips])
+        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        t, st = self._sample_args(B, temperature, stream)
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        n = (C.c_int * B)()
+        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
+        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+        eot = (C.c_int * B)()
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampSampled(self.h, ptrs, lens, B, max_new, mc, t.ctypes.data_as(fp),
+                                                                  st.ctypes.data_as(C.POINTER(C.c_uint64)), int(seed), ids.ctypes.data_as(ip), n,
+                                                                  lp.ctypes.data_as(fp), avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), eot),
+                    "RunPCMBatchTimestampSampled")
+        return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
+                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+
     def segments(self, ids, num_samples: int):
         """[(start_s, end_s, text)] of one clip's timestamp-mode ids."""
         clip_s = min(num_samples / 16000.0, 30.0)
@@ -376,14 +469,25 @@ class Whisper:
         self._check(self.L.AX_WHISPER_ComputeMelWindow(self.h, a.ctypes.data_as(fp), len(a), int(seek), out.ctypes.data_as(fp)), "ComputeMelWindow")
         return out
 
-    def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0, no_speech_threshold=None, logprob_threshold=None, scores: bool = False):
+    def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0, no_speech_threshold=None, logprob_threshold=None, scores: bool = False,
+                         compression_ratio_threshold=None, temperatures=None, seed: int = 0, file_ids=None):
         """The seek loop over `files` (PCM arrays), one window of every unfinished file per pass. Per file, the list of its
         decoded windows (seek, window_frames, advance, ids, pass, slot) in order. max_new: id budget per window;
         max_passes > 0 stops after that many passes (the slots then hold the last pass's cross K/V).
         With a threshold (the silent-window rule: a skipped window advances by its window_frames) or scores=True the call is the
-        scored one and every tuple gains (no_speech_logprob, avg_logprob, skipped)."""
-        scored = scores or no_speech_threshold is not None or logprob_threshold is not None
+        scored one and every tuple gains (no_speech_logprob, avg_logprob, skipped).
+        With compression_ratio_threshold or temperatures the call is the fallback one (AX_WHISPER_RunPCMLongWindowsFallback;
+        temperatures default to 0, 0.2, .. 1.0): every attempt is a tuple, which gains (attempt, temperature, compression_ratio,
+        kept) after those three; there a missing logprob_threshold switches its part of the fallback rule off. file_ids: one id per
+        file naming its random streams (default: its index in `files`); equal (seed, id) give a file the same windows in any call."""
+        fallback = compression_ratio_threshold is not None or temperatures is not None
+        scored = fallback or scores or no_speech_threshold is not None or logprob_threshold is not None
         nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
+        if fallback:
+            lpt = float("nan") if logprob_threshold is None else float(logprob_threshold)
+            crt = float("nan") if compression_ratio_threshold is None else float(compression_ratio_threshold)
+            temps = _f32(DEFAULT_TEMPERATURES if temperatures is None else temperatures)
+        sw = 7 if fallback else 3
         files = [_f32(f) for f in files]
         n = len(files)
         ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
@@ -393,9 +497,15 @@ class Whisper:
         while True:
             info = np.zeros((cap, 7), dtype=np.int32)
             ids = np.zeros((cap, self.n_text_ctx), dtype=np.int32)
-            sc = np.zeros((cap, 3), dtype=np.float32)
+            sc = np.zeros((cap, sw), dtype=np.float32)
             nw = C.c_int()
-            if scored:
+            if fallback:
+                rc = self.L.AX_WHISPER_RunPCMLongWindowsFallback(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
+                                                                 temps.ctypes.data_as(fp), len(temps), int(seed),
+                                                                 (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None, cap,
+                                                                 info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
+                                                                 sc.ctypes.data_as(fp), C.byref(nw))
+            elif scored:
                 rc = self.L.AX_WHISPER_RunPCMLongWindowsScored(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, cap,
                                                                info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
                                                                sc.ctypes.data_as(fp), C.byref(nw))
@@ -414,16 +524,23 @@ class Whisper:
         for k in range(nw.value):
             f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
             w = (seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot)
-            out[f].append(w + (float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2])) if scored else w)
+            if scored:
+                w = w + (float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2]))
+            if fallback:
+                w = w + (int(sc[k, 3]), float(sc[k, 4]), float(sc[k, 5]), bool(sc[k, 6]))
+            out[f].append(w)
         return out
 
-    def run_long_scored(self, audio, max_new: int = 0, no_speech_threshold=None, logprob_threshold=None):
+    def run_long_scored(self, audio, max_new: int = 0, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None,
+                        temperatures=None, seed: int = 0):
         """run_long with confidence -> [(start_s, end_s, text, avg_logprob, no_speech_prob)]: every segment carries its window's two
-        numbers (as openai-whisper reports them); windows the silent-window rule skips yield nothing."""
+        numbers (as openai-whisper reports them); windows the silent-window rule skips yield nothing. With
+        compression_ratio_threshold or temperatures: under temperature fallback, the kept attempts only."""
         out = []
-        for seek, wf, _adv, ids, _p, _s, nsp, avg, skipped in self.run_long_windows([audio], max_new, no_speech_threshold=no_speech_threshold,
-                                                                                     logprob_threshold=logprob_threshold, scores=True)[0]:
-            if skipped:
+        for w in self.run_long_windows([audio], max_new, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, scores=True,
+                                       compression_ratio_threshold=compression_ratio_threshold, temperatures=temperatures, seed=seed)[0]:
+            seek, wf, _adv, ids, _p, _s, nsp, avg, skipped = w[:9]
+            if skipped or (len(w) > 9 and not w[12]):
                 continue
             for s, e, tb, te in split_window(ids, self.timestamp_begin, self.eot, wf)[0]:
                 out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te]), avg, float(np.exp(np.float32(nsp)))))
@@ -437,10 +554,23 @@ class Whisper:
                 out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te])))
         return out
 
-    def run_long_text(self, audio, no_speech_threshold=None, logprob_threshold=None) -> str:
+    def run_long_text(self, audio, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None, temperatures=None,
+                      seed: int = 0) -> str:
         """PCM or a wav path of any length -> the whole text (AX_WHISPER_RunPCMLong / RunFileLong; with a threshold: the *Opts
-        forms, the text without the windows the silent-window rule skips)."""
+        forms, the text without the windows the silent-window rule skips; with compression_ratio_threshold or temperatures: the
+        *Fallback forms)."""
         out = C.c_void_p()
+        if compression_ratio_threshold is not None or temperatures is not None:
+            nan = lambda v: float("nan") if v is None else float(v)
+            temps = _f32(DEFAULT_TEMPERATURES if temperatures is None else temperatures)
+            tail = (nan(no_speech_threshold), nan(logprob_threshold), nan(compression_ratio_threshold), temps.ctypes.data_as(fp), len(temps),
+                    int(seed), C.byref(out))
+            if isinstance(audio, (str, os.PathLike)):
+                self._check(self.L.AX_WHISPER_RunFileLongFallback(self.h, os.fspath(audio).encode(), *tail), "RunFileLongFallback")
+            else:
+                a = _f32(audio)
+                self._check(self.L.AX_WHISPER_RunPCMLongFallback(self.h, a.ctypes.data_as(fp), len(a), *tail), "RunPCMLongFallback")
+            return self._take(out.value)
         if no_speech_threshold is not None or logprob_threshold is not None:
             nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
             if isinstance(audio, (str, os.PathLike)):

@@ -550,6 +550,7 @@ AX_WHISPER_API int AX_WHISPER_ComputeMelWindow(AX_WHISPER_HANDLE handle, const f
 static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* const* pcm, const int* num_samples, int n_files, int max_new,
                         int max_passes, const axw::LongScoreOptions* opts, int win_cap, int* win_info, int32_t* ids, float* win_score,
                         int* n_windows) {
+  const bool fallback = opts && !opts->temperatures.empty();  // win_score rows then have 7 entries
   if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids || (opts && !win_score))))
     return -1;
   for (int b = 0; b < n_files; ++b)
@@ -567,7 +568,9 @@ static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* 
       const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
       memcpy(win_info + k * 7, row, sizeof row);
       memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
-      if (opts) { win_score[k * 3] = w.no_speech_logprob; win_score[k * 3 + 1] = w.avg_logprob; win_score[k * 3 + 2] = w.skipped ? 1.f : 0.f; }
+      float* sc = opts ? win_score + k * (fallback ? 7 : 3) : nullptr;
+      if (opts) { sc[0] = w.no_speech_logprob; sc[1] = w.avg_logprob; sc[2] = w.skipped ? 1.f : 0.f; }
+      if (fallback) { sc[3] = (float)w.attempt; sc[4] = w.temperature; sc[5] = w.compression_ratio; sc[6] = w.kept ? 1.f : 0.f; }
     }
     *n_windows = (int)log.size();
   });
@@ -592,7 +595,7 @@ static int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples,
     std::string text;
     std::vector<axw::WindowSegment> segs;
     for (const axw::LongWindow& w : log) {
-      if (w.skipped) continue;
+      if (w.skipped || !w.kept) continue;
       axw::split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
       for (const axw::WindowSegment& sg : segs) text += e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);  // host only
     }
@@ -631,6 +634,103 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsScored(AX_WHISPER_HANDLE handle, 
   const axw::LongScoreOptions opts{no_speech_threshold, logprob_threshold};
   return long_windows(handle, "RunPCMLongWindowsScored", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids, win_score,
                       n_windows);
+}
+
+// ---- temperature fallback (DESIGN.md "Temperature fallback")
+AX_WHISPER_API int AX_WHISPER_SampleTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                                   int batch, const float* temperature, const uint64_t* stream, uint64_t seed,
+                                                   int32_t* chosen, float* logprob) {
+  if (!handle || !logits || !hist || !n_hist || !temperature || !stream || !chosen || !logprob || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) {
+    const Engine::SampleSpec sample{temperature, stream, seed};
+    e.timestamp_rules(logits, hist, n_hist, batch, chosen, logprob, &sample);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampSampled(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
+                                                           const float* temperature, const uint64_t* stream, uint64_t seed,
+                                                           float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob,
+                                                           float* logits0) {
+  if (!handle || (n_forced > 0 && !forced) || !temperature || !stream || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) {
+    const Engine::ForcedScores scores{logprob, no_speech_logprob, logits0};
+    const Engine::SampleSpec sample{temperature, stream, seed};
+    e.decode_forced(Engine::kDecodeSampled, batch, forced, n_forced, logits, chosen, &scores, &sample);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampSampled(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                          int batch, int max_new, const int* max_new_clip, const float* temperature,
+                                                          const uint64_t* stream, uint64_t seed, int32_t* ids, int* n_ids,
+                                                          float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
+  if (!handle || !pcm || !num_samples || !temperature || !stream || !ids || !n_ids || !token_logprob || !avg_logprob || !no_speech_logprob ||
+      !ended_eot || batch < 1)
+    return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
+    const Engine::SampleSpec sample{temperature, stream, seed};
+    g.run_tokens(Engine::kDecodeSampled, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids, &scores,
+                 &sample);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_CompressionRatio(const unsigned char* bytes, int n, float* ratio) {
+  if ((n > 0 && !bytes) || n < 0 || !ratio) return -1;
+  return guarded_host([&] {
+    *ratio = axw::compression_ratio(bytes, (size_t)n);
+    return 0;
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_WindowNeedsFallback(float compression_ratio, float avg_logprob, float no_speech_logprob,
+                                                  float compression_ratio_threshold, float logprob_threshold, float no_speech_threshold) {
+  return axw::window_needs_fallback(compression_ratio, avg_logprob, no_speech_logprob, compression_ratio_threshold, logprob_threshold,
+                                    no_speech_threshold) ? 1 : 0;
+}
+
+// the options of the three fallback calls; false: a bad temperature list
+static bool fallback_options(float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                             int n_temperatures, uint64_t seed, axw::LongScoreOptions& opts) {
+  if (!temperatures || n_temperatures < 1 || n_temperatures > 16) return false;
+  opts.no_speech_threshold = no_speech_threshold; opts.logprob_threshold = logprob_threshold;
+  opts.compression_ratio_threshold = compression_ratio_threshold;
+  opts.temperatures.assign(temperatures, temperatures + n_temperatures);
+  opts.seed = seed;
+  return true;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsFallback(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                        int n_files, int max_new, int max_passes, float no_speech_threshold,
+                                                        float logprob_threshold, float compression_ratio_threshold,
+                                                        const float* temperatures, int n_temperatures, uint64_t seed, const int* file_ids,
+                                                        int win_cap, int* win_info, int32_t* ids, float* win_score, int* n_windows) {
+  axw::LongScoreOptions opts{};
+  if (!fallback_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, opts)) return -1;
+  for (int f = 0; file_ids && f < n_files; ++f) {
+    if (file_ids[f] < 0 || file_ids[f] >= (1 << 27)) return -1;  // (id * 16 + attempt is the stream's high word)
+    opts.file_ids.push_back(file_ids[f]);
+  }
+  return long_windows(handle, "RunPCMLongWindowsFallback", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids,
+                      win_score, n_windows);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongFallback(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                                 float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                 int n_temperatures, uint64_t seed, char** result) {
+  axw::LongScoreOptions opts{};
+  if (!fallback_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, opts)) return -1;
+  return long_text(handle, pcm_data, num_samples, &opts, result);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileLongFallback(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
+                                                  float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                  int n_temperatures, uint64_t seed, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return AX_WHISPER_RunPCMLongFallback(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
+                                       compression_ratio_threshold, temperatures, n_temperatures, seed, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {

@@ -482,6 +482,17 @@ struct TsScoreParams {
   float* no_speech; int no_speech_id;           // out: [batch], or nullptr
 };
 void launch_timestamp_rules_scored(const TsRulesParams& p, const TsScoreParams& q, hipStream_t s);
+// Sampled form (DESIGN.md "Temperature fallback"): the scored kernel whose decision, for a clip with temperature[b] > 0, is drawn
+// from softmax(x[A] / t) over the final allowed set by Gumbel-max: argmax over A of x[i] / t - log(-log(u_i)) (lowest id on ties),
+// u_i = ((w >> 9) + 0.5) * 2^-23 with w = word i & 3 of Philox4x32-10(counter (i >> 2, n, stream[b] low, stream[b] high), key
+// seed low, seed high), n = the clip's history length. The recorded log-probability stays the untempered x[c] - logsumexp(x[A]).
+// temperature[b] <= 0: the scored kernel's decision. All three are device memory, so one captured step serves every call.
+struct TsSampleParams {
+  const float* temperature;          // [batch]
+  const unsigned long long* stream;  // [batch]
+  const unsigned long long* seed;    // [1]
+};
+void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams& q, const TsSampleParams& r, hipStream_t s);
 // out[b] = logits[b][id] - logsumexp(logits[b][0 .. n_vocab)), NaN entries left out; rows [batch][stride], stride a multiple of 4
 void launch_row_logprob(const float* logits, long stride, int n_vocab, int id, int batch, float* out, hipStream_t s);
 

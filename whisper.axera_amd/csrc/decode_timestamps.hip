@@ -12,6 +12,10 @@
 // thread 0 knows logsumexp of the final allowed set A and writes log p(chosen) = x[chosen] - logsumexp(x[A]) and the decision id
 // at the clip's history length. At decode offset 0 (the step that fed sot) the scored launch takes the whole-row branch instead:
 // log p(<|nospeech|>) over the unfiltered row. The unscored kernel is untouched by all of this.
+//
+// Sampled form (DESIGN.md "Temperature fallback"): the scored form whose decision, for a clip at temperature t > 0, is drawn from
+// softmax(x[A] / t) by Gumbel-max with Philox4x32-10 noise: two more (key, id) pairs per thread (text and eot / timestamps, since
+// rule 5 is only known after the reduction), reduced like the argmax pairs. The other kernels are untouched by it.
 #include "common.hpp"
 
 namespace axw {
@@ -74,6 +78,8 @@ __device__ __forceinline__ void row_logprob(const float* row, int nv, int id, fl
   if (tid == 0) *out = logprob_of(row[id], m, s);
 }
 
+// (The rules prologue and the reductions below exist three times in this file — this kernel, the scored and the sampled form: a change
+// to a rule is made in all three.)
 __global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
@@ -175,6 +181,7 @@ __global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesParams p) {
 // The scored form: timestamp_rules_kernel line for line, plus the text-range (max, sum), the no-speech branch and the score stores.
 // A kernel of its own and not a template parameter of the one above: routed through a shared body, the unscored kernel came out
 // of hipcc with another register allocation, and timestamp mode without scores is to keep the instructions it had.
+// (One of three copies of the prologue and reductions: see the note above timestamp_rules_kernel.)
 __global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesParams p, TsScoreParams q) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
@@ -295,6 +302,191 @@ __global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesPara
   }
 }
 
+// ---- sampled form (DESIGN.md "Temperature fallback")
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"): counter c, key k -> four words; no state in memory
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// Gumbel-max key of one logit: x / t + g, g = -log(-log(u)), u = ((word >> 9) + 0.5) * 2^-23, never 0 or 1 (the accurate logf)
+__device__ __forceinline__ float gumbel_key(float x, float t, unsigned word) {
+  const float u = ((float)(word >> 9) + 0.5f) * 0x1p-23f;  // exact: 24 bits
+  return x / t - logf(-logf(u));
+}
+
+// The sampled form: timestamp_rules_scored_kernel line for line, plus two Gumbel (key, id) pairs per thread for clips whose temperature
+// is above 0: the decision is drawn from softmax(x[A] / t) over the final allowed set A, as argmax of x / t + Gumbel noise, the noise
+// of id i at history length n being word i & 3 of Philox(counter (i >> 2, n, stream), key seed). Rules 1 to 5 are decided on the
+// untempered logits and the recorded log-probability is the untempered one. A clip with t <= 0 takes the scored kernel's decision
+// and computes no random number. A kernel of its own for the reason given above the scored one.
+// (A change to a rule is made here, in timestamp_rules_kernel and in timestamp_rules_scored_kernel alike.)
+__global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesParams p, TsScoreParams q, TsSampleParams r) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
+  const int T = p.ts_begin, E = p.eot, nv = p.n_vocab;
+  // only clips that sample at this step: past the prefix and not finished
+  if (p.off && p.off[b] < p.n_prefix - 1) {
+    // the step that fed sot: the no-speech value of this clip
+    if (q.no_speech && p.off[b] == 0) row_logprob(p.logits + (long)b * p.stride, p.n_vocab, q.no_speech_id, q.no_speech + b);
+    return;
+  }
+  if (p.done && p.done[b]) return;
+
+  // ---- the clip's history: ids sampled so far (prefix excluded)
+  const int* seq;
+  int n;
+  if (p.forced) {
+    seq = p.forced + (long)b * p.n_forced;
+    n = min(max(p.off[b] - (p.n_prefix - 1), 0), p.n_forced);
+  } else {
+    seq = p.out_ids + (long)b * p.n_ctx;
+    n = min(max(p.n_out[b], 0), p.n_ctx);
+  }
+  __shared__ int s_last[4];
+  __shared__ float s_tv[4], s_sv[4], s_m[4], s_s[4];
+  __shared__ int s_ti[4], s_si[4];
+  int last = -1;  // index of the clip's last timestamp
+  for (int i = tid; i < n; i += 256)
+    if (seq[i] >= T) last = i;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+  if (lane == 0) s_last[wave] = last;
+  __syncthreads();
+  last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
+  const bool last_ts = n >= 1 && seq[n - 1] >= T;
+  const bool penult_ts = n < 2 || seq[n - 2] >= T;
+  const bool pair_open = last_ts && !penult_ts;  // one timestamp after text: the closing half of a pair may follow
+  // ---- the allowed sets: [0, E) iff text_on, E iff eot_on, [E + 1, T) never, [ts_lo, ts_hi)
+  const bool text_on = n > 0 && !pair_open;  // rules 2 (mask [0, E)) and 4
+  const bool eot_on = n > 0;                 // rule 4
+  int ts_lo = T, ts_hi = nv;
+  if (last >= 0) ts_lo = min(max(seq[last], T) + (pair_open ? 0 : 1), nv);  // rule 3
+  if (last_ts && penult_ts) ts_hi = T;                                       // rule 2: a pair just closed
+  if (n == 0) ts_hi = min(ts_hi, T + 51);                                    // rule 4: <= 1.0 s
+  ts_lo = min(ts_lo, ts_hi);
+
+  // ---- the clip's temperature and random stream (uniform over the workgroup)
+  const float temp = r.temperature[b];
+  const bool draw = temp > 0.f;
+  const unsigned long long sid = r.stream[b], seed = r.seed[0];
+  const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), c2 = (unsigned)sid, c3 = (unsigned)(sid >> 32);
+
+  const float* row = p.logits + (long)b * p.stride;
+  float tv = -INFINITY, sv = -INFINITY, m = -INFINITY, s = 0.f;
+  float mt = -INFINITY, st = 0.f;  // online logsumexp over the unmasked text ids and eot
+  float gt = -INFINITY, gs = -INFINITY;  // best Gumbel key over the unmasked text ids and eot / over the unmasked timestamps
+  int ti = 0x7fffffff, si = 0x7fffffff, gti = 0x7fffffff, gsi = 0x7fffffff;
+  // text ids [0, E]: chunks of four floats; NaN never compares greater (it counts as masked)
+  const int text_end = text_on ? E + 1 : (eot_on ? E + 1 : 0);
+  const int text_begin = text_on ? 0 : (eot_on ? E : 0);
+  for (int c = (text_begin >> 2) + tid; 4 * c < text_end; c += 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
+    float x[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = 4 * c + e;
+      const bool on = i < E ? text_on : (i == E && eot_on);
+      if (on && v[e] > tv) { tv = v[e]; ti = i; }
+      x[e] = (on && v[e] == v[e]) ? v[e] : -INFINITY;
+    }
+    lse_add4(mt, st, x[0], x[1], x[2], x[3]);
+    if (draw) {
+      unsigned w[4];
+      philox4x32_10((unsigned)c, (unsigned)n, c2, c3, k0, k1, w);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float key = gumbel_key(x[e], temp, w[e]);  // (a masked id: -inf)
+        if (key > gt) { gt = key; gti = 4 * c + e; }
+      }
+    }
+  }
+  for (int c = (ts_lo >> 2) + tid; 4 * c < ts_hi; c += 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
+    unsigned w[4];
+    if (draw) philox4x32_10((unsigned)c, (unsigned)n, c2, c3, k0, k1, w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = 4 * c + e;
+      if (i >= ts_lo && i < ts_hi && v[e] == v[e]) {
+        if (v[e] > sv) { sv = v[e]; si = i; }
+        lse_merge(m, s, v[e], 1.f);
+        if (draw) {
+          const float key = gumbel_key(v[e], temp, w[e]);
+          if (key > gs) { gs = key; gsi = i; }
+        }
+      }
+    }
+  }
+  // ---- reductions: first maximum wins (lower index on ties), logsumexp pairs merged in a fixed order
+  wave_argmax(tv, ti);
+  wave_argmax(sv, si);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    lse_merge(m, s, m2, s2);
+  }
+  __shared__ float s_mt[4], s_st[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(mt, o, 64), s2 = __shfl_xor(st, o, 64);
+    lse_merge(mt, st, m2, s2);
+  }
+  __shared__ float s_gt[4], s_gs[4];
+  __shared__ int s_gti[4], s_gsi[4];
+  if (draw) {
+    wave_argmax(gt, gti);
+    wave_argmax(gs, gsi);
+    if (lane == 0) { s_gt[wave] = gt; s_gti[wave] = gti; s_gs[wave] = gs; s_gsi[wave] = gsi; }
+  }
+  if (lane == 0) { s_mt[wave] = mt; s_st[wave] = st; }
+  if (lane == 0) { s_tv[wave] = tv; s_ti[wave] = ti; s_sv[wave] = sv; s_si[wave] = si; s_m[wave] = m; s_s[wave] = s; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) {
+      argmax_take(tv, ti, s_tv[w], s_ti[w]);
+      argmax_take(sv, si, s_sv[w], s_si[w]);
+      lse_merge(m, s, s_m[w], s_s[w]);
+      lse_merge(mt, st, s_mt[w], s_st[w]);
+    }
+    const float lse = (m == -INFINITY || m == INFINITY) ? m : m + logf(s);
+    float bv = -INFINITY;
+    int bi = E;  // nothing finite left: eot, the clip ends
+    if (draw) {
+      for (int w = 1; w < 4; ++w) {
+        argmax_take(gt, gti, s_gt[w], s_gti[w]);
+        argmax_take(gs, gsi, s_gs[w], s_gsi[w]);
+      }
+      // rule 5 fired: the timestamps' winner; else the larger key of the two winners (text ids are the lower ones: text on ties)
+      int gi = -1;
+      if (lse > tv) { if (gs > -INFINITY) gi = gsi; }
+      else if (gt > -INFINITY && gt >= gs) gi = gti;
+      else if (gs > -INFINITY) gi = gsi;
+      if (gi >= 0) { bi = gi; bv = row[gi]; }
+    } else if (lse > tv) {  // rule 5: the timestamps' probability mass beats every single text id
+      bv = sv; bi = si;
+    } else if (tv > -INFINITY && tv >= sv) {
+      bv = tv; bi = ti;
+    } else if (sv > -INFINITY) {
+      bv = sv; bi = si;
+    }
+    p.amax_val[(long)b * p.amax_stride] = bv;
+    p.amax_idx[(long)b * p.amax_stride] = bi;
+    // A = the timestamps alone when rule 5 fired, else text, eot and timestamps (timestamp pair first: a fixed order)
+    if (!(lse > tv)) lse_merge(m, s, mt, st);
+    if (n < q.stride) {
+      q.logprob[(long)b * q.stride + n] = logprob_of(bv, m, s);
+      q.decision[(long)b * q.stride + n] = bi;
+    }
+  }
+}
+
 // log p(row[id]) over the whole row, one workgroup per row (the no-speech value on rows of the caller's)
 __global__ __launch_bounds__(256) void row_logprob_kernel(const float* logits, long stride, int n_vocab, int id, float* out) {
   row_logprob(logits + (long)blockIdx.x * stride, n_vocab, id, out + blockIdx.x);
@@ -320,6 +512,16 @@ void launch_timestamp_rules_scored(const TsRulesParams& p, const TsScoreParams& 
     abort();
   }
   hipLaunchKernelGGL(timestamp_rules_scored_kernel, dim3(p.batch), dim3(256), 0, s, p, q);
+}
+
+void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams& q, const TsSampleParams& r, hipStream_t s) {
+  check_rules_params(p);
+  if (!q.logprob || !q.decision || q.stride < 1 || (q.no_speech && (q.no_speech_id < 0 || q.no_speech_id >= p.n_vocab)) || !r.temperature ||
+      !r.stream || !r.seed) {
+    fprintf(stderr, "[ax_whisper] launch_timestamp_rules_sampled: bad score or sample arrays / no-speech id %d\n", q.no_speech_id);
+    abort();
+  }
+  hipLaunchKernelGGL(timestamp_rules_sampled_kernel, dim3(p.batch), dim3(256), 0, s, p, q, r);
 }
 
 void launch_row_logprob(const float* logits, long stride, int n_vocab, int id, int batch, float* out, hipStream_t s) {

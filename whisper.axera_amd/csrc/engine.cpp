@@ -763,16 +763,18 @@ void Engine::run_encoder(int batch, const int* d_slot_map) {
 
 // ------------------------------------------------------------------------------ public entry points
 void Engine::run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
-                        int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores) {
+                        int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample) {
   if (batch < 1) throw std::runtime_error("batch must be >= 1");
   require_no_stream("run_tokens");
-  if (mode < kDecodePlain || mode > kDecodeScored) throw std::runtime_error("run_tokens: unknown decode mode");
-  if (scores && mode != kDecodeScored) throw std::runtime_error("run_tokens: scores need the scored decode mode");
+  if (mode < kDecodePlain || mode > kDecodeSampled) throw std::runtime_error("run_tokens: unknown decode mode");
+  if (scores && mode < kDecodeScored) throw std::runtime_error("run_tokens: scores need the scored or the sampled decode mode");
+  if ((mode == kDecodeSampled) != (sample != nullptr)) throw std::runtime_error("run_tokens: the sampled decode mode, and it alone, takes sample parameters");
   if (mode == kDecodeTimestamps) require_timestamp_vocab();
-  if (mode == kDecodeScored) require_scored_vocab();
+  if (mode >= kDecodeScored) require_scored_vocab();
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   ensure_capacity(batch);
+  if (sample) upload_sample(*sample, batch);
   hipStream_t s = stream();
   HIP_CHECK(hipEventRecord(ev_[0], s));
   if (pcm) {
@@ -874,15 +876,16 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
 }
 
 void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids,
-                           const ForcedScores* scores) {
-  if (mode < kDecodePlain || mode > kDecodeScored) throw std::runtime_error("decode_forced: unknown decode mode");
-  if (scores && mode != kDecodeScored) throw std::runtime_error("decode_forced: scores need the scored decode mode");
+                           const ForcedScores* scores, const SampleSpec* sample) {
+  if (mode < kDecodePlain || mode > kDecodeSampled) throw std::runtime_error("decode_forced: unknown decode mode");
+  if (scores && mode < kDecodeScored) throw std::runtime_error("decode_forced: scores need the scored or the sampled decode mode");
+  if ((mode == kDecodeSampled) != (sample != nullptr)) throw std::runtime_error("decode_forced: the sampled decode mode, and it alone, takes sample parameters");
   const ForcedScores out = scores ? *scores : ForcedScores{};
   require_no_stream("decode_forced");
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_forced: batch exceeds the encoded slots");
-  const bool tsm = mode != kDecodePlain, scored = mode == kDecodeScored;
+  const bool tsm = mode != kDecodePlain, scored = mode >= kDecodeScored;
   const int n_prefix = tsm ? 3 : 4;
   if (n_forced < 0 || n_forced + n_prefix > cfg_.n_text_ctx) throw std::runtime_error("decode_forced: n_forced out of range");
   if (tsm) require_timestamp_vocab();
@@ -903,6 +906,7 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
     if (out.logits0) b_l0 = device_array<float>((size_t)batch * nv);
     spec.score_out = TsScoreParams{b_lp, b_dec, (long)rows, b_nsp, own_scores_.no_speech_id};
   }
+  if (sample) { upload_sample(*sample, batch); spec.sample = own_sample_; }
   if (n_forced) HIP_CHECK(hipMemcpy(d_forced, forced, (size_t)batch * n_forced * 4, hipMemcpyHostToDevice));
   bool done = false;
   if (batch == 1 && !tsm && persistent_usable()) {
@@ -950,10 +954,12 @@ void Engine::decode_greedy(DecodeMode mode, int batch, int max_new, const int* m
 
 // The rules kernel alone, on host rows and histories (tests; callers with logits of their own)
 // logprob != nullptr: the scored kernel (each clip's entry at index 0 of a one-entry score row)
-void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) {
+void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
+                             const SampleSpec* sample) {
   require_no_stream("apply_timestamp_rules");
   require_timestamp_vocab();
-  if (batch < 1 || !logits || !hist || !n_hist || !chosen) throw std::runtime_error("apply_timestamp_rules: bad arguments");
+  if (batch < 1 || !logits || !hist || !n_hist || !chosen || (sample && !logprob)) throw std::runtime_error("apply_timestamp_rules: bad arguments");
+  if (sample) require_scored_vocab();
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   hipStream_t s = stream();
@@ -961,6 +967,10 @@ void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int
   const long stride = ((long)nv + 3) / 4 * 4;
   for (int b = 0; b < batch; ++b)
     if (n_hist[b] < 0 || n_hist[b] > Tc) throw std::runtime_error("apply_timestamp_rules: n_hist out of range");
+  if (sample) {
+    ensure_capacity(batch);  // (the sample arrays are per-slot buffers)
+    upload_sample(*sample, batch);
+  }
   DeviceArray<float> b_lp, b_log = device_array<float>((size_t)batch * stride), b_val = device_array<float>(batch);
   DeviceArray<int> b_dec, b_hist = device_array<int>((size_t)batch * Tc), b_n = device_array<int>(batch), b_idx = device_array<int>(batch);
   if (logprob) {  // [batch][n_text_ctx + 1]: the kernel's index is the history length
@@ -976,7 +986,8 @@ void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int
   r.off = nullptr; r.n_prefix = 3; r.done = nullptr;
   r.out_ids = b_hist; r.n_out = b_n; r.n_ctx = Tc;
   r.amax_val = b_val; r.amax_idx = b_idx; r.amax_stride = 1;
-  if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, s);
+  if (sample) launch_timestamp_rules_sampled(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, own_sample_, s);
+  else if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, s);
   else launch_timestamp_rules(r, s);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(chosen, b_idx, (size_t)batch * 4, hipMemcpyDeviceToHost, s));

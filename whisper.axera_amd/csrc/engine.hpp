@@ -84,6 +84,10 @@ struct SlotViews {
   // its own [batch][n_forced + 1] buffers instead)
   float* d_tok_lp_ = nullptr; int* d_dec_id_ = nullptr; float* d_nospeech_ = nullptr;
   TsScoreParams own_scores_{};
+  // sampled mode (DESIGN.md "Temperature fallback"): per-clip temperature and random stream [cap], the call's seed [1]; allocated
+  // with the score arrays. own_sample_: these arrays as the sampled rules kernel takes them
+  float* d_temp_ = nullptr; unsigned long long *d_rng_stream_ = nullptr, *d_rng_seed_ = nullptr;
+  TsSampleParams own_sample_{};
   float *d_a0_ = nullptr, *d_statp_ = nullptr;  // [B][d] A0 -> T; [B][d/16][2] block statistics of the residual rows
   float* d_pcm_ = nullptr; long long* d_over_off_ = nullptr;
   int* d_nsamp_ = nullptr; unsigned* d_gmax_ = nullptr; float* d_logmel_ = nullptr; float* d_mel_ref_ = nullptr;
@@ -109,7 +113,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   Engine(const Engine&) = delete;
 
   void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
-                  const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores) override;
+                  const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample = nullptr) override;
   std::string detokenize(const int32_t* ids, int n) const override;
   std::string transcript(const int32_t* ids, int n) const override;
   bool has_t2s() const { return (bool)t2s_; }
@@ -117,9 +121,10 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void encode_mel(const float* mel, int batch) override;
   void get_cross_kv(int slot, float* k_out, float* v_out) override;
   void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
-                     const ForcedScores* scores) override;
+                     const ForcedScores* scores, const SampleSpec* sample = nullptr) override;
   void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
-  void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) override;
+  void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
+                       const SampleSpec* sample = nullptr) override;
   void no_speech_logprob(const float* logits, int batch, float* out) override;
   void stream_open(int n_slots) override;
   void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) override;
@@ -168,7 +173,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     // launches of the step (all: 15): 1 GEMV/GEMM launches, 2 attention launches, 4 advance, 8 act_prep, 16 attention launches stamp
     // themselves (bench only)
     int mask = 15;
-    TsScoreParams score_out{};  // kDecodeScored: where the scored rules kernel writes
+    TsScoreParams score_out{};  // kDecodeScored, kDecodeSampled: where the scored / sampled rules kernel writes
+    TsSampleParams sample{};    // kDecodeSampled: what the sampled rules kernel draws with (the engine's own arrays)
   };
   // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
   // the rules kernel; first_step: the first decode step whose row is computed
@@ -189,7 +195,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // the captured step of spec.mode / spec.mask; a scored graph writes the engine's own score arrays (spec.score_out is not read)
   hipGraphExec_t step_graph(StepSpec spec, int batch, int max_new);
   void drop_step_graph(const StepSpec& spec, int batch, int max_new) { graphs_.erase(graph_key(spec, batch, max_new)); }
-  // (two bits for the mode: plain, timestamp and scored steps are three different graphs)
+  // (two bits for the mode: plain, timestamp, scored and sampled steps are four different graphs)
   static long graph_key(const StepSpec& spec, int batch, int max_new) { return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 2) | spec.mode; }
   void require_timestamp_vocab() const;
   void ensure_ts_logits();  // d_ts_logits_ (SlotViews)
@@ -197,6 +203,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   long ts_stride_ = 0;
   void require_scored_vocab() const;  // require_timestamp_vocab + a usable no_speech id
   void ensure_ts_scores();
+  // checks a SampleSpec of `batch` clips and puts it into the engine's own arrays (on the stream, before the steps that read them)
+  void upload_sample(const SampleSpec& sample, int batch);
   // scores of the last scored greedy loop over `batch` slots (n_ids: what fetch_ids returned)
   void fetch_scores(int batch, const int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
   void recover_streams();

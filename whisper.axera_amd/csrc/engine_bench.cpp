@@ -63,7 +63,8 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "queue_probe") return (float)queue_probe_mask();
   HIP_CHECK(hipSetDevice(device_));
   ensure_capacity(batch);
-  if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn" || what == "decode_step_ts" || what == "decode_step_ts_scored")
+  if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn" || what == "decode_step_ts" || what == "decode_step_ts_scored" ||
+      what == "decode_step_ts_sampled")
     return bench_decode_step(what, batch, arg, iters);
   if (what == "attn_stamp") return bench_attn_stamp(batch, arg, iters);
   if (what == "encoder") return bench_encoder(batch, iters);
@@ -86,12 +87,21 @@ static float timed_ms(hipStream_t s, Fn&& run) {
 }
 
 // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;
-// decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel); decode_step_ts_scored: with the scored rules kernel
+// decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel); decode_step_ts_scored: with the scored rules kernel;
+// decode_step_ts_sampled: with the sampled rules kernel, every clip at temperature AX_WHISPER_BENCH_TEMPERATURE (default 1)
 float Engine::bench_decode_step(const std::string& what, int batch, int arg, int iters) {
-  const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored";
+  const bool sampled = what == "decode_step_ts_sampled";
+  const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored" || sampled;
   if (what == "decode_step_ts") require_timestamp_vocab();
-  if (what == "decode_step_ts_scored") require_scored_vocab();
-  StepSpec spec{what == "decode_step_ts" ? kDecodeTimestamps : what == "decode_step_ts_scored" ? kDecodeScored : kDecodePlain};
+  if (what == "decode_step_ts_scored" || sampled) require_scored_vocab();
+  StepSpec spec{what == "decode_step_ts" ? kDecodeTimestamps : what == "decode_step_ts_scored" ? kDecodeScored : sampled ? kDecodeSampled : kDecodePlain};
+  if (sampled) {
+    const char* e = getenv("AX_WHISPER_BENCH_TEMPERATURE");
+    const std::vector<float> temps(batch, e ? (float)atof(e) : 1.f);
+    std::vector<uint64_t> streams(batch);
+    for (int b = 0; b < batch; ++b) streams[b] = (uint64_t)b;
+    upload_sample(SampleSpec{temps.data(), streams.data(), 1}, batch);
+  }
   spec.mask = whole ? 15 : (what == "decode_gemv" ? 1 : 2);
   hipStream_t s = stream();
   const int Tc = cfg_.n_text_ctx;

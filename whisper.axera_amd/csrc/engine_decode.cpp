@@ -116,7 +116,7 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
 // (scored mode: from offset 0 on — the row of the step that fed sot is the no-speech row; the row of offset 1 is computed and ignored)
 Engine::LogitsDump Engine::logits_dump(const StepSpec& spec, float* d_logits, long logits_stride) const {
   if (spec.mode == kDecodePlain) return {d_logits, logits_stride, 3};
-  return {d_ts_logits_, ts_stride_, spec.mode == kDecodeScored ? 0 : 2};
+  return {d_ts_logits_, ts_stride_, spec.mode >= kDecodeScored ? 0 : 2};
 }
 
 void Engine::enqueue_step_tail(const StepSpec& spec, int batch, int max_new, const int* d_forced, int n_forced, int* d_argmax, int n_part,
@@ -488,7 +488,7 @@ hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   ensure_branch_streams(batch);  // before the capture opens
   if (spec.mode != kDecodePlain) ensure_ts_logits();
-  if (spec.mode == kDecodeScored) { ensure_ts_scores(); spec.score_out = own_scores_; }
+  if (spec.mode >= kDecodeScored) { ensure_ts_scores(); spec.score_out = own_scores_; spec.sample = own_sample_; }
   HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   hipError_t cap_err = hipSuccess;
   hipGraph_t captured = nullptr;
@@ -687,7 +687,8 @@ void Engine::enqueue_timestamp_rules(const StepSpec& spec, int batch, const int*
   r.out_ids = d_out_ids_; r.n_out = d_nout_; r.n_ctx = cfg_.n_text_ctx;
   r.forced = d_forced; r.n_forced = n_forced;
   r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
-  if (spec.mode == kDecodeScored) launch_timestamp_rules_scored(r, spec.score_out, s);  // + the decision's log-probability, the no-speech value at offset 0
+  if (spec.mode == kDecodeSampled) launch_timestamp_rules_sampled(r, spec.score_out, spec.sample, s);  // + a draw at the clip's temperature
+  else if (spec.mode == kDecodeScored) launch_timestamp_rules_scored(r, spec.score_out, s);  // + the decision's log-probability, the no-speech value at offset 0
   else launch_timestamp_rules(r, s);
 }
 
@@ -706,6 +707,27 @@ void Engine::ensure_ts_scores() {
   d_dec_id_ = pooled<int>(slot_allocs_, n, true);
   d_nospeech_ = pooled<float>(slot_allocs_, cap_, true);
   own_scores_ = TsScoreParams{d_tok_lp_, d_dec_id_, (long)cfg_.n_text_ctx, d_nospeech_, (int)cfg_.ints.at("no_speech")};
+  d_temp_ = pooled<float>(slot_allocs_, cap_, true);  // (temperature 0: a sampled step decides as a scored one until a call says otherwise)
+  d_rng_stream_ = pooled<unsigned long long>(slot_allocs_, cap_, true);
+  d_rng_seed_ = pooled<unsigned long long>(slot_allocs_, 1, true);
+  own_sample_ = TsSampleParams{d_temp_, d_rng_stream_, d_rng_seed_};
+}
+
+void Engine::upload_sample(const SampleSpec& sample, int batch) {
+  if (!sample.temperature || !sample.stream) throw std::runtime_error("sampled decode needs a temperature and a stream id per clip");
+  for (int b = 0; b < batch; ++b)
+    // (below 1e-6 the quotient x / t leaves float32's range for ordinary logits and the draw would be decided by the tie rule)
+    if (!(sample.temperature[b] >= 0.f) || std::isinf(sample.temperature[b]) || (sample.temperature[b] > 0.f && sample.temperature[b] < 1e-6f))
+      throw std::runtime_error("sampled decode: temperature " + std::to_string(sample.temperature[b]) + " of clip " + std::to_string(b) +
+                               " (need 0, or a finite value >= 1e-6)");
+  ensure_ts_scores();
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "uint64_t");
+  hipStream_t s = stream();
+  const unsigned long long seed = sample.seed;
+  HIP_CHECK(hipMemcpyAsync(d_temp_, sample.temperature, (size_t)batch * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_rng_stream_, sample.stream, (size_t)batch * 8, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_rng_seed_, &seed, 8, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));  // (pageable sources, one of them on this stack)
 }
 
 // After fetch_ids of a scored greedy loop. Decision i of clip b sits at index i: i < n_ids are the kept ids, i == n_ids the decision

@@ -132,13 +132,24 @@ void Engine::compute_mel_window(const float* pcm, int n_samples, int seek, float
 
 // opts != nullptr: the windows are decoded in scored mode, every log entry carries its two numbers, and a window the silent-window
 // rule drops emits nothing and advances by its whole length (DESIGN.md "Confidence")
+// opts->temperatures non-empty: temperature fallback (DESIGN.md "Temperature fallback"). Sampled mode throughout; a pass entry is
+// (file, seek, attempt); a window that needs fallback and has attempts left does not advance, it is encoded and decoded again in
+// the next pass at the next temperature (one more log entry, kept = false on the one that failed).
 void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                               const LongScoreOptions* opts, std::vector<LongWindow>& log) {
   if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
   require_no_stream("run_long_windows");
   require_timestamp_vocab();
   if (opts) require_scored_vocab();
-  const StepSpec spec{opts ? kDecodeScored : kDecodeTimestamps};
+  const bool fallback = opts && !opts->temperatures.empty();
+  const int n_attempts = fallback ? (int)opts->temperatures.size() : 1;
+  if (n_attempts > 16) throw std::runtime_error("long-form: at most 16 temperatures");
+  if (fallback && !opts->file_ids.empty() && (long)opts->file_ids.size() < (long)opts->file_base + n_files)
+    throw std::runtime_error("long-form: fewer file ids than files");
+  for (int a = 0; a < n_attempts && fallback; ++a)
+    if (!(opts->temperatures[a] >= 0.f) || std::isinf(opts->temperatures[a]) || (opts->temperatures[a] > 0.f && opts->temperatures[a] < 1e-6f))
+      throw std::runtime_error("long-form: temperatures must be 0, or finite and >= 1e-6");
+  const StepSpec spec{fallback ? kDecodeSampled : opts ? kDecodeScored : kDecodeTimestamps};
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   // windows per pass: the engine's capacity (AX_WHISPER_MAX_BATCH / max_batch of Init, or what earlier calls grew it to);
@@ -150,7 +161,9 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   long_prepare(pcm, n_samples, n_files, S);
   HIP_CHECK(hipEventRecord(ev_[1], s));
   const int T = cfg_.no_timestamps + 1, E = cfg_.eot, Tc = cfg_.n_text_ctx;
-  std::vector<int> seek(n_files, 0), active, files(S), seeks(S), n_ids(S);
+  std::vector<int> seek(n_files, 0), attempt(n_files, 0), active, files(S), seeks(S), n_ids(S);
+  std::vector<float> temps(S);
+  std::vector<uint64_t> streams(S);
   std::vector<int32_t> ids((size_t)S * Tc);
   std::vector<float> avg(S), nsp(S);
   std::vector<WindowSegment> segs;
@@ -168,6 +181,14 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
     const int A = (int)active.size();
     if (A == 0) break;
     for (int i = 0; i < A; ++i) { files[i] = active[i]; seeks[i] = seek[active[i]]; }
+    if (fallback) {  // the clip's stream is (seek, file id * 16 + attempt): a file's draws do not depend on its neighbours
+      for (int i = 0; i < A; ++i) {
+        temps[i] = opts->temperatures[attempt[files[i]]];
+        streams[i] = (uint64_t)(uint32_t)seeks[i] | (uint64_t)(uint32_t)(opts->file_id(files[i]) * 16 + attempt[files[i]]) << 32;
+      }
+      // (waits for the stream, which the last pass's fetch left idle)
+      upload_sample(SampleSpec{temps.data(), streams.data(), opts->seed}, A);
+    }
     long_windows_to_slots(files.data(), seeks.data(), A, false);
     run_encoder(A);
     steps += greedy_loop(spec, A, max_new, nullptr);
@@ -180,8 +201,29 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
       w.window_frames = std::min(kFramesOut, n_samples[f] / kHop - seeks[i]);
       const int n = std::max(0, std::min(n_ids[i], Tc));
       w.ids.assign(ids.begin() + (size_t)i * Tc, ids.begin() + (size_t)i * Tc + n);
+      if (opts) { w.no_speech_logprob = nsp[i]; w.avg_logprob = avg[i]; }
+      if (fallback) {
+        // the window's text: the raw bytes of its ids below eot, before the zh post-pass
+        std::vector<int32_t> text_ids;
+        for (int32_t id : w.ids)
+          if (id < E) text_ids.push_back(id);
+        const std::string text = strip_ascii_space(detokenize(text_ids.data(), (int)text_ids.size()));
+        w.attempt = attempt[f]; w.temperature = temps[i];
+        w.compression_ratio = compression_ratio(reinterpret_cast<const unsigned char*>(text.data()), text.size());
+        const bool need = window_needs_fallback(w.compression_ratio, avg[i], nsp[i], opts->compression_ratio_threshold, opts->logprob_threshold,
+                                                opts->no_speech_threshold);
+        if (getenv("AX_WHISPER_LONG_LOG"))
+          fprintf(stderr, "[ax_whisper] long: file %d seek %d attempt %d (t %.2f): compression_ratio %.3f avg_logprob %.4f%s\n", f, seeks[i],
+                  w.attempt, w.temperature, w.compression_ratio, avg[i], need ? " (needs fallback)" : "");
+        if (need && attempt[f] + 1 < n_attempts) {  // decoded again in the next pass; the file stays where it is
+          w.kept = false; w.advance = 0;
+          ++attempt[f];
+          log.push_back(std::move(w));
+          continue;
+        }
+        attempt[f] = 0;  // kept (the last attempt even if it fails too)
+      }
       if (opts) {
-        w.no_speech_logprob = nsp[i]; w.avg_logprob = avg[i];
         w.skipped = long_window_is_silent(nsp[i], avg[i], opts->no_speech_threshold, opts->logprob_threshold);
         if (getenv("AX_WHISPER_LONG_LOG"))
           fprintf(stderr, "[ax_whisper] long: file %d seek %d: no_speech_logprob %.4f avg_logprob %.4f%s\n", f, seeks[i], nsp[i], avg[i],

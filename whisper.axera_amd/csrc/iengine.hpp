@@ -32,7 +32,12 @@ class IEngine {
   // "Segment timestamps"); ids then include timestamp tokens
   // kDecodeScored = kDecodeTimestamps that also keeps, per clip, the log-probability of every decision and log p(<|nospeech|>) at
   // the step that fed sot (DESIGN.md "Confidence"); the ids are those of kDecodeTimestamps
-  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1, kDecodeScored = 2 };
+  // kDecodeSampled = kDecodeScored whose decisions are drawn at a per-clip temperature from a per-clip random stream (DESIGN.md
+  // "Temperature fallback"); a clip at temperature 0 decides as kDecodeScored does. Needs a SampleSpec.
+  enum DecodeMode : int { kDecodePlain = 0, kDecodeTimestamps = 1, kDecodeScored = 2, kDecodeSampled = 3 };
+  // what kDecodeSampled draws with: host temperature [batch] (>= 0, not NaN), stream [batch] (the clip's random stream: equal
+  // (seed, stream, history length) give equal noise wherever the clip sits), one seed per call
+  struct SampleSpec { const float* temperature; const uint64_t* stream; uint64_t seed; };
   // what kDecodeScored keeps (DESIGN.md "Confidence"); every array may be null.
   // greedy: token_logprob [batch][n_text_ctx]: entries 0 .. n_ids[b] (one per kept id + the decision that ended the clip), the
   // rest 0; avg_logprob, no_speech_logprob, ended_eot [batch]
@@ -41,9 +46,11 @@ class IEngine {
   // of decode offset 0
   struct ForcedScores { float *logprob, *no_speech_logprob, *logits0; };
   // full path, host PCM or device PCM; ids [batch][n_text_ctx], n_ids [batch]
-  // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new; scores: kDecodeScored only
+  // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new; scores: kDecodeScored and
+  // kDecodeSampled only; sample: kDecodeSampled only (and required there)
   virtual void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
-                          int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores) = 0;
+                          int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores,
+                          const SampleSpec* sample = nullptr) = 0;
   virtual std::string detokenize(const int32_t* ids, int n) const = 0;
   // detokenize + the reference's zh post-pass (Traditional -> Simplified, Whisper.cpp:231-236) when its OpenCC data files were found
   virtual std::string transcript(const int32_t* ids, int n) const = 0;
@@ -51,14 +58,18 @@ class IEngine {
   virtual void compute_mel(const float* pcm, int n_samples, float* mel_out) = 0;
   virtual void encode_mel(const float* mel, int batch) = 0;
   virtual void get_cross_kv(int slot, float* k_out, float* v_out) = 0;
-  // timestamp and scored mode: logits are the raw logits (before the rules), chosen the ids the rules choose; scores: kDecodeScored only
+  // timestamp, scored and sampled mode: logits are the raw logits (before the rules), chosen the ids the rules choose; scores:
+  // kDecodeScored and kDecodeSampled only; sample: kDecodeSampled only (and required there)
   virtual void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
-                             const ForcedScores* scores) = 0;
+                             const ForcedScores* scores, const SampleSpec* sample = nullptr) = 0;
   // plain or timestamp mode; max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new
   virtual void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
   // the rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] (n_hist[b] ids each) -> chosen [batch];
   // logprob [batch] (null: the unscored kernel): the scored kernel, + the log-probability of every chosen id
-  virtual void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob) = 0;
+  // sample != nullptr (logprob required): the sampled kernel. The sample arrays are per-slot buffers: unlike the other two forms, a
+  // call with batch above the engine's current capacity grows it, which re-makes the slot buffers (the cross K/V of earlier calls is lost)
+  virtual void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
+                               const SampleSpec* sample = nullptr) = 0;
   // the no-speech kernel alone: logits [batch][n_vocab] -> out [batch] = log p(<|nospeech|>) over the whole row
   virtual void no_speech_logprob(const float* logits, int batch, float* out) = 0;
   // utterance slots refilled while the others decode (include/ax_whisper_api.h: AX_WHISPER_Stream*)

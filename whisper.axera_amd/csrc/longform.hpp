@@ -8,7 +8,11 @@
 
 #include <cmath>
 #include <cstdint>
+#include <stdexcept>
+#include <string>
 #include <vector>
+
+#include <dlfcn.h>
 
 namespace axw {
 
@@ -65,9 +69,64 @@ inline bool long_window_is_silent(float no_speech_logprob, float avg_logprob, fl
   return std::exp(no_speech_logprob) > no_speech_threshold && !(avg_logprob > logprob_threshold);
 }
 
+// Temperature fallback (DESIGN.md "Temperature fallback"; openai-whisper transcribe(): decode_with_fallback). A decoded window is
+// decoded again at the next temperature iff its text compresses too well (a repetition loop) or its average log-probability is too
+// low — unless it looks silent, which the silent-window rule then handles. A NaN threshold switches its part off. All in float32.
+inline bool window_needs_fallback(float compression_ratio, float avg_logprob, float no_speech_logprob, float compression_ratio_threshold,
+                                  float logprob_threshold, float no_speech_threshold) {
+  bool need = false;
+  if (compression_ratio > compression_ratio_threshold) need = true;
+  if (avg_logprob < logprob_threshold) need = true;
+  if (std::exp(no_speech_logprob) > no_speech_threshold && avg_logprob < logprob_threshold) need = false;  // silence
+  return need;
+}
+
+// The text the compression ratio is taken of: the window's bytes without ASCII whitespace at both ends
+inline std::string strip_ascii_space(const std::string& s) {
+  auto sp = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; };
+  size_t lo = 0, hi = s.size();
+  while (lo < hi && sp(s[lo])) ++lo;
+  while (hi > lo && sp(s[hi - 1])) --hi;
+  return s.substr(lo, hi - lo);
+}
+
+// n / len(zlib.compress(bytes)) at zlib's default level, as openai-whisper's compression_ratio (n = 0: 0 / 8 = 0). zlib's runtime
+// library is loaded at first use (libz.so.1: present wherever Python runs; its development symlink need not be); throws without it.
+inline float compression_ratio(const unsigned char* bytes, size_t n) {
+  typedef unsigned long (*bound_fn)(unsigned long);
+  typedef int (*compress_fn)(unsigned char*, unsigned long*, const unsigned char*, unsigned long);
+  struct Z { bound_fn bound = nullptr; compress_fn compress = nullptr; };
+  static const Z z = [] {
+    Z r;
+    if (void* h = dlopen("libz.so.1", RTLD_NOW | RTLD_LOCAL)) {
+      r.bound = reinterpret_cast<bound_fn>(dlsym(h, "compressBound"));
+      r.compress = reinterpret_cast<compress_fn>(dlsym(h, "compress"));
+    }
+    return r;
+  }();
+  if (!z.bound || !z.compress) throw std::runtime_error("compression ratio: libz.so.1 (zlib's runtime library) could not be loaded");
+  static const unsigned char none = 0;
+  unsigned long len = z.bound((unsigned long)n);
+  std::vector<unsigned char> out(len);
+  if (z.compress(out.data(), &len, n ? bytes : &none, (unsigned long)n) != 0 || len == 0) throw std::runtime_error("compression ratio: zlib compress failed");
+  return (float)((double)n / (double)len);
+}
+
 // scored long-form: thresholds of the silent-window rule (NaN no_speech_threshold: the rule is off, scores are still fetched)
+// With `temperatures` non-empty the call is the fallback loop: sampled decode mode throughout, attempt a of a window at
+// temperatures[a] (at most 16 attempts), a window that needs fallback is decoded again in the next pass. (openai-whisper's list
+// 0, 0.2, .. 1.0 is the default of the CLI and of the Python mirror: an empty list here keeps every existing call what it was.)
 struct LongScoreOptions {
   float no_speech_threshold, logprob_threshold;
+  float compression_ratio_threshold = NAN;
+  std::vector<float> temperatures;
+  uint64_t seed = 0;
+  int file_base = 0;  // index of this engine's first file in the whole call (set per engine when the files are sharded)
+  // The random stream of a window is (seek, file id * 16 + attempt). file_ids (empty, or one id >= 0 per file of the WHOLE call): the
+  // caller's names for its files, so that a file draws the same noise whatever its position in the call; empty: the file's index
+  // in the whole call.
+  std::vector<int> file_ids;
+  int file_id(int local_file) const { return file_ids.empty() ? file_base + local_file : file_ids[(size_t)(file_base + local_file)]; }
 };
 
 // one decoded window of AX_WHISPER_RunPCMLongWindows, in execution order
@@ -77,6 +136,10 @@ struct LongWindow {
   // scored calls only: the window's two numbers and whether the silent-window rule dropped it (then advance == window_frames)
   float no_speech_logprob = 0.f, avg_logprob = 0.f;
   bool skipped = false;
+  // fallback calls only: every attempt is an entry. kept: this attempt's result stands (the others advance by 0 and emit nothing)
+  int attempt = 0;
+  float temperature = 0.f, compression_ratio = 0.f;
+  bool kept = true;
 };
 
 }  // namespace axw

@@ -18,6 +18,8 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace axw {
@@ -64,6 +66,9 @@ void run_sharded(int n, int world, Fn&& fn) {
     if (failed[w]) throw std::runtime_error("device worker " + std::to_string(w) + ": " + errors[w]);
 }
 
+template <typename O, typename = void> struct has_file_base : std::false_type {};
+template <typename O> struct has_file_base<O, decltype((void)std::declval<O&>().file_base)> : std::true_type {};
+
 // G engines, one per device. E needs: std::mutex& mutex(); an enum DecodeMode; a struct ClipScores {float *token_logprob,
 // *avg_logprob, *no_speech_logprob; int* ended_eot;}; run_tokens and run_long_windows as they are called below.
 template <typename E>
@@ -78,8 +83,11 @@ class DeviceGroup {
   // Host PCM of `batch` clips -> ids [batch][n_ctx], n_ids [batch] (E::run_tokens: a decode mode, optional per-clip budgets
   // max_new_clip [batch], optional per-clip scores, token_logprob [batch][n_ctx]). With one engine (or one clip) this is the
   // engine's own call; otherwise workers = min(G, batch) engines each take one contiguous block of every per-clip array.
+  // sample (sampled decode mode; S = E::SampleSpec {temperature [batch], stream [batch], seed}): every shard gets its block of the two
+  // arrays; the stream ids are the caller's, so a clip's draws do not depend on the device it lands on.
+  template <typename S = std::nullptr_t>
   void run_tokens(typename E::DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                  int n_ctx, int32_t* ids, int* n_ids, const typename E::ClipScores* scores = nullptr) {
+                  int n_ctx, int32_t* ids, int* n_ids, const typename E::ClipScores* scores = nullptr, const S* sample = nullptr) {
     if (batch < 1) throw std::runtime_error("batch must be >= 1");
     auto from = [](auto* p, size_t k) { return p ? p + k : p; };
     for_each_shard(batch, [&](E& e, int, int lo, int hi) {
@@ -87,21 +95,35 @@ class DeviceGroup {
       if (scores)
         sc = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
               from(scores->ended_eot, lo)};
-      e.run_tokens(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), ids + (size_t)lo * n_ctx, n_ids + lo,
-                   scores ? &sc : nullptr);
+      if constexpr (std::is_same<S, std::nullptr_t>::value) {
+        e.run_tokens(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), ids + (size_t)lo * n_ctx, n_ids + lo,
+                     scores ? &sc : nullptr);
+      } else {
+        S sm{};
+        if (sample) sm = S{from(sample->temperature, lo), from(sample->stream, lo), sample->seed};
+        e.run_tokens(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), ids + (size_t)lo * n_ctx, n_ids + lo,
+                     scores ? &sc : nullptr, sample ? &sm : nullptr);
+      }
     });
   }
 
   // Long-form (E::run_long_windows; opts: the thresholds of the silent-window rule, or null): the FILES are split into contiguous
   // blocks, one per engine; every engine runs its own seek loop. The log holds worker 0's windows first, then worker 1's, ...; file
-  // indices count over the whole call, pass and slot are the engine's own. W needs an int member `file`.
+  // indices count over the whole call, pass and slot are the engine's own. W needs an int member `file`. Options with a member
+  // `file_base` (temperature fallback numbers its random streams by file) are handed to every engine with the index of its first file.
   template <typename W, typename O>
   void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const O* opts,
                         std::vector<W>& log) {
     if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
     std::vector<std::vector<W>> logs(size());
     for_each_shard(n_files, [&](E& e, int w, int lo, int hi) {
-      e.run_long_windows(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, opts, logs[w]);
+      if constexpr (has_file_base<O>::value) {
+        O mine{};
+        if (opts) { mine = *opts; mine.file_base = opts->file_base + lo; }
+        e.run_long_windows(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, opts ? &mine : nullptr, logs[w]);
+      } else {
+        e.run_long_windows(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, opts, logs[w]);
+      }
       for (W& x : logs[w]) x.file += lo;
     });
     for (auto& l : logs)

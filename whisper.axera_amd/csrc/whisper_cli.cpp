@@ -32,6 +32,10 @@ static void usage(const char* prog) {
           "                      unless its average token log-probability is above Y (without X nothing is skipped, without Y the\n"
           "                      no-speech probability alone decides; openai-whisper uses 0.6 and -1.0). Each segment line then ends\n"
           "                      in (avg_logprob ..., no_speech ...)\n"
+          "      --compression_ratio_threshold Z   (with --long) temperature fallback: a window whose text compresses by more than Z\n"
+          "                      (a repetition loop), or whose average log-probability is below Y, is decoded again with sampling\n"
+          "                      at temperatures 0.2, 0.4, .. 1.0 until one attempt passes (openai-whisper uses 2.4)\n"
+          "      --temperature_increment D, --seed N   the step between those temperatures [=0.2], the seed of the draws [=0]\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -121,28 +125,39 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav) {
 // --long: the seek loop over the whole file (AX_WHISPER_RunPCMLongWindows), its text, then one line per segment.
 // scored: under the silent-window rule (AX_WHISPER_RunPCMLongWindowsScored); skipped windows print nothing, the other lines end
 // in their window's two numbers
-static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_speech_threshold, float logprob_threshold, std::string& text,
+// temps non-empty: with temperature fallback (AX_WHISPER_RunPCMLongWindowsFallback): only kept attempts print
+static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_speech_threshold, float logprob_threshold,
+                    float compression_ratio_threshold, const std::vector<float>& temps, unsigned long long seed, std::string& text,
                     std::string& lines) {
+  const bool fallback = !temps.empty();
+  const size_t sw = fallback ? 7 : 3;  // floats per window score row
   float* pcm = nullptr;
   int n = 0;
   if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
   const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
   const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
-  int cap = n / 160 + 1;  // every window advances by at least one frame
+  int cap = (n / 160 + 1) * (fallback ? (int)temps.size() : 1);  // every window advances by at least one frame (after at most temps.size() attempts)
   std::vector<int> info((size_t)cap * 7);
   std::vector<int32_t> ids((size_t)cap * n_ctx);
-  std::vector<float> score(scored ? (size_t)cap * 3 : 0);
+  std::vector<float> score(scored ? (size_t)cap * sw : 0);
   int n_win = 0;
   const float* files[1] = {pcm};
-  const int rc = scored ? AX_WHISPER_RunPCMLongWindowsScored(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold, cap, info.data(),
+  const int rc = fallback ? AX_WHISPER_RunPCMLongWindowsFallback(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
+                                                                 compression_ratio_threshold, temps.data(), (int)temps.size(), seed, nullptr, cap,
+                                                                 info.data(), ids.data(), score.data(), &n_win)
+                 : scored ? AX_WHISPER_RunPCMLongWindowsScored(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold, cap, info.data(),
                                                              ids.data(), score.data(), &n_win)
                         : AX_WHISPER_RunPCMLongWindows(h, files, &n, 1, 0, 0, cap, info.data(), ids.data(), &n_win);
   free(pcm);
   if (rc != 0) return -1;
   for (int k = 0; k < n_win; ++k) {
-    if (scored && score[(size_t)k * 3 + 2] != 0.f) continue;  // a silent window
-    char tail[96] = "";
-    if (scored) snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g)", score[(size_t)k * 3 + 1], std::exp(score[(size_t)k * 3]));
+    if (scored && score[(size_t)k * sw + 2] != 0.f) continue;  // a silent window
+    if (fallback && score[(size_t)k * sw + 6] == 0.f) continue;  // an attempt that was decoded again
+    char tail[160] = "";
+    if (scored) snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g)", score[(size_t)k * sw + 1], std::exp(score[(size_t)k * sw]));
+    if (fallback)
+      snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g, temperature %.1f, compression_ratio %.3f)", score[(size_t)k * sw + 1],
+               std::exp(score[(size_t)k * sw]), score[(size_t)k * sw + 4], score[(size_t)k * sw + 5]);
     const int* w = &info[(size_t)k * 7];
     const int32_t* wi = &ids[(size_t)k * n_ctx];
     const int n_max = w[4] / 2 + 1;
@@ -165,7 +180,7 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
   bool timestamps = false, longform = false;
-  std::string nst_arg, lpt_arg;
+  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -179,7 +194,8 @@ int main(int argc, char** argv) {
       return false;
     };
     if (val("wav", "-w", wav) || val("model_type", "-t", model_type) || val("model_path", "-p", model_path) ||
-        val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg))
+        val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg) ||
+        val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -189,7 +205,11 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (wav.empty()) { fprintf(stderr, "need option: --wav\n"); usage(argv[0]); return 1; }
-  const bool scored = !nst_arg.empty() || !lpt_arg.empty();
+  // --compression_ratio_threshold turns temperature fallback on: attempts at 0, inc, 2 inc, .. 1.0 (inc 0.2 unless given)
+  const bool fallback = !crt_arg.empty();
+  if ((!tinc_arg.empty() || !seed_arg.empty()) && !fallback) { fprintf(stderr, "--temperature_increment / --seed need --compression_ratio_threshold\n"); usage(argv[0]); return 1; }
+  if (fallback && !longform) { fprintf(stderr, "--compression_ratio_threshold needs --long\n"); usage(argv[0]); return 1; }
+  const bool scored = fallback || !nst_arg.empty() || !lpt_arg.empty();
   if (scored && !longform) { fprintf(stderr, "--no_speech_threshold / --logprob_threshold need --long\n"); usage(argv[0]); return 1; }
   // one flag alone: no threshold on the average = no-speech alone decides (+inf); no threshold on no-speech = nothing is skipped
   // (NaN; as in openai-whisper, where the average only ever overrides a no-speech verdict) and the lines just carry their numbers
@@ -198,6 +218,20 @@ int main(int argc, char** argv) {
     char* end = nullptr;
     if (!nst_arg.empty()) { no_speech_threshold = strtof(nst_arg.c_str(), &end); if (*end) { fprintf(stderr, "bad value: --no_speech_threshold %s\n", nst_arg.c_str()); return 1; } }
     if (!lpt_arg.empty()) { logprob_threshold = strtof(lpt_arg.c_str(), &end); if (*end) { fprintf(stderr, "bad value: --logprob_threshold %s\n", lpt_arg.c_str()); return 1; } }
+  }
+  float compression_ratio_threshold = NAN;
+  std::vector<float> temps;
+  unsigned long long seed = 0;
+  if (fallback) {
+    char* end = nullptr;
+    compression_ratio_threshold = strtof(crt_arg.c_str(), &end);
+    if (*end) { fprintf(stderr, "bad value: --compression_ratio_threshold %s\n", crt_arg.c_str()); return 1; }
+    float inc = 0.2f;
+    if (!tinc_arg.empty()) { inc = strtof(tinc_arg.c_str(), &end); if (*end || !(inc > 0.f) || inc > 1.f) { fprintf(stderr, "bad value: --temperature_increment %s\n", tinc_arg.c_str()); return 1; } }
+    if (inc < 1.f / 15.f) { fprintf(stderr, "bad value: --temperature_increment %s (at most 16 attempts)\n", tinc_arg.c_str()); return 1; }
+    for (int k = 0; (float)k * inc <= 1.f + 1e-6f; ++k) temps.push_back((float)k * inc);
+    if (!seed_arg.empty()) { seed = strtoull(seed_arg.c_str(), &end, 0); if (*end) { fprintf(stderr, "bad value: --seed %s\n", seed_arg.c_str()); return 1; } }
+    if (lpt_arg.empty()) logprob_threshold = NAN;  // (no threshold on the average: that part of the fallback rule is off)
   }
 
   printf("wav_file: %s\n", wav.c_str());
@@ -218,7 +252,7 @@ int main(int argc, char** argv) {
   if (longform) {
     t0 = std::chrono::steady_clock::now();
     std::string text, lines;
-    if (run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, text, lines) != 0) {
+    if (run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, text, lines) != 0) {
       printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
       AX_WHISPER_Uninit(handle);
       return -1;
