@@ -312,7 +312,7 @@ AX_WHISPER_API int AX_WHISPER_WindowNeedsFallback(float compression_ratio, float
  *  stream of a window is (seek, file id * 16 + attempt). file_ids [n_files] (each 0 .. 2^27 - 1) are the caller's names for its files;
  *  NULL: a file's id is its index in this call. Equal (seed, file id) give a file the same windows beside any other files, at any
  *  position in the call and on any number of devices; with NULL that holds for a file at the same index only (a file moved to
- *  another index draws other noise). RunPCMLongFallback / RunFileLongFallback use file id 0. Not covered: best_of > 1, beam search, prompt reset, the Stream* calls. */
+ *  another index draws other noise). RunPCMLongFallback / RunFileLongFallback use file id 0. Not covered: best_of > 1, beam search inside this loop (RunPCMBatchBeam decodes single windows), prompt reset, the Stream* calls. */
 AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsFallback(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
                                                         int n_files, int max_new, int max_passes, float no_speech_threshold,
                                                         float logprob_threshold, float compression_ratio_threshold,
@@ -325,6 +325,64 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongFallback(AX_WHISPER_HANDLE handle, float
 AX_WHISPER_API int AX_WHISPER_RunFileLongFallback(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
                                                   float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
                                                   int n_temperatures, uint64_t seed, char** result);
+
+/** ---- Beam search (DESIGN.md "Beam search"): openai-whisper's BeamSearchDecoder over this project's timestamp rules.
+ *  K = beam_size (1 .. 8) hypotheses ("ranks") per clip, each in a decoder slot of its own: clip c owns slots [c*K, c*K+K), so
+ *  batch * K must not exceed the handle's max_batch (per device). Per step every live rank proposes the K+1 best ids of scored
+ *  mode's final allowed set with x[c] - logsumexp(x[A]); the clip's candidates are ordered by float32 sum_logprob + logprob
+ *  (descending; then parent rank, then position) and walked: the first K that are not eot become the new ranks, eot candidates met
+ *  before the K-th become finished records (the parent's ids, the score) while the clip's pool holds fewer than K. A clip whose pool
+ *  is full, or that has no live rank left, is complete; the loop ends when every clip is, or after max_new ids (one budget per call;
+ *  0 or above n_text_ctx - 3: n_text_ctx - 3). Then live ranks fill a pool that is not full, in rank order, and the winner is the
+ *  first record with the largest score / max(len, 1). K = 1 gives scored greedy mode's ids.
+ *  Per clip: ids [batch][n_text_ctx] / n_ids (the winner's, no eot), sum_logprob, avg_logprob = sum_logprob / (n_ids + 1),
+ *  no_speech_logprob (scored mode's, from the clip's first slot), ended_eot (1: the winner finished with eot, 0: it was cut at the
+ *  budget). A clip without any record: n_ids 0, -inf. Sharded over the handle's devices like RunPCMBatchTokens.
+ *  Not covered: best_of > 1, patience, a length penalty, per-clip budgets, the long-form loop, the Stream* calls. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchBeam(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                              int beam_size, int max_new, int32_t* ids, int* n_ids, float* sum_logprob,
+                                              float* avg_logprob, float* no_speech_logprob, int* ended_eot);
+/** Stage level (after EncodeMel of `batch` clips): the same decode over the encoded slots. Also every record of every clip, in
+ *  pool order then fill order (each may be NULL): rec_ids [batch][K][n_text_ctx], rec_len / rec_score / rec_pool [batch][K]
+ *  (rec_pool 1: from the pool), n_rec [batch], winner [batch] (index among the clip's records, -1: none).
+ *  Trace (trace_cap > 0; every array may be NULL), for sampled step n < trace_cap over S = batch * K slots: tr_rows
+ *  [trace_cap][S][n_vocab] the raw rows, tr_cand_id / tr_cand_logprob [trace_cap][S][K+1] and tr_n_cand [trace_cap][S] the
+ *  candidates by slot, and after the step's selection tr_S / tr_slot [trace_cap][S] by rank (sum_logprob, -inf: dead; the rank's
+ *  slot), tr_src [trace_cap][S] by slot (the slot its history and cache were taken from), tr_tok [trace_cap][S] by slot (the id
+ *  appended to its history), tr_pool_n [trace_cap][batch]. *n_steps (may be NULL): sampled steps the loop ran (the completion
+ *  counter is polled every 8 steps, so up to 16 steps run past the last completion; complete clips no longer change).
+ *  With beam_size > 1 the call OVERWRITES the encoded slots: clip c's cross K/V is copied into slots c*K .. c*K+K-1, so slots
+ *  1 .. batch*K-1 no longer hold what EncodeMel put there. Unlike the other stage-level Decode* calls it cannot be followed by
+ *  another Decode* (DecodeBeam included) on the same encoder output: call EncodeMel again first. */
+AX_WHISPER_API int AX_WHISPER_DecodeBeam(AX_WHISPER_HANDLE handle, int batch, int beam_size, int max_new, int32_t* ids, int* n_ids,
+                                         float* sum_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot,
+                                         int32_t* rec_ids, int* rec_len, float* rec_score, int* rec_pool, int* n_rec, int* winner,
+                                         int trace_cap, float* tr_rows, int32_t* tr_cand_id, float* tr_cand_logprob, int* tr_n_cand,
+                                         float* tr_S, int* tr_slot, int* tr_src, int32_t* tr_tok, int* tr_pool_n, int* n_steps);
+/** The candidates kernel alone: logits [rows][n_vocab], hist [rows][n_text_ctx] with n_hist[b] ids each -> the n_cand_max (1 .. 9)
+ *  best ids of each row's final allowed set, value descending, lower id first on equal values: cand_id / cand_logprob
+ *  [rows][n_cand_max] (entries from n_cand[b] on: eot, -inf), n_cand [rows]. */
+AX_WHISPER_API int AX_WHISPER_BeamCandidates(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                             int rows, int n_cand_max, int32_t* cand_id, float* cand_logprob, int* n_cand);
+/** The selection kernel alone, on the caller's beam state (the handle gives the device only). n: history length before the step;
+ *  stride: row stride of hist and pool_ids (n < stride). In: cand_id / cand_logprob [clips*K][K+1] and n_cand [clips*K] by slot, hist
+ *  [clips*K][stride] by slot. In / out: S and slot [clips*K] by rank (slot: the ranks of clip c hold each of c*K .. c*K+K-1 once),
+ *  pool_n [clips], pool_ids [clips*K][stride], pool_len / pool_score [clips*K], complete [clips]. Out: tok, src, slot_score
+ *  [clips*K] by slot (the id for the history's index n; the reorder's source; S of the rank in the slot), *n_completed: clips that
+ *  completed in this step. A surviving parent's best child stays in the parent's slot; the other children, then the dead ranks,
+ *  take the clip's remaining slots in ascending order: no slot is both a source and a destination. */
+AX_WHISPER_API int AX_WHISPER_BeamSelect(AX_WHISPER_HANDLE handle, int clips, int beam_size, int eot, int n, int stride,
+                                         const int32_t* cand_id, const float* cand_logprob, const int* n_cand, const int32_t* hist,
+                                         float* S, int* slot, int* pool_n, int32_t* pool_ids, int* pool_len, float* pool_score,
+                                         int* complete, int32_t* tok, int* src, float* slot_score, int* n_completed);
+/** Host only (no handle, no GPU): the fill and the ranking. In: the state after the loop (n: the histories' length; arrays as in
+ *  BeamSelect). Out (each may be NULL): the records rec_ids [clips*K][stride], rec_len / rec_score / rec_pool [clips*K], n_rec
+ *  [clips], winner [clips], and the winner's ids [clips][stride], n_ids, sum_logprob, avg_logprob, ended_eot [clips]. */
+AX_WHISPER_API int AX_WHISPER_BeamFinalize(int clips, int beam_size, int n, int stride, const int32_t* hist, const float* S,
+                                           const int* slot, const int* pool_n, const int32_t* pool_ids, const int* pool_len,
+                                           const float* pool_score, int32_t* rec_ids, int* rec_len, float* rec_score, int* rec_pool,
+                                           int* n_rec, int* winner, int32_t* ids, int* n_ids, float* sum_logprob, float* avg_logprob,
+                                           int* ended_eot);
 
 /** Host only (no handle, no GPU): the decode path Init picks for a decoder shape on a device with n_cu compute units, and the
  *  persistent launch's cross-attention role assignment, from the engine's own functions. plan4[0] = workgroups of the
@@ -342,7 +400,10 @@ AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
 /** Time `iters` launches of one named piece on the handle's stream with hipEvents; returns
  *  total ms in *ms_total. what: "decode_step" (one captured step graph at decode offset
  *  `arg`), "decode_step_ts" (the same step in timestamp mode), "decode_step_ts_scored" (in scored mode), "decode_step_ts_sampled" (in sampled mode, every clip at temperature
- *  $AX_WHISPER_BENCH_TEMPERATURE, default 1), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
+ *  $AX_WHISPER_BENCH_TEMPERATURE, default 1), "decode_step_beam" (the beam-search step of `batch` slots in groups of beam size `arg`,
+ *  from decode offset 224 on, one offset further per iteration; afterwards GetConfigInt "beam_bench_moved_slots" / "beam_bench_iters" /
+ *  "beam_bench_complete_clips" say how many slots the reorder launches copied in all, over how many iterations, and how many clips
+ *  had completed), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
  *  files of `arg` seconds + one window kernel), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);

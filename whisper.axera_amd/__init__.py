@@ -90,6 +90,15 @@ SYMBOLS = {
     "AX_WHISPER_RunPCMLongWindowsFallback": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_RunPCMLongFallback": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_RunFileLongFallback": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunPCMBatchBeam": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_DecodeBeam": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int),
+                                        ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.c_int, fp, ip, fp, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_BeamCandidates": (C.c_int, [C.c_void_p, fp, ip, C.POINTER(C.c_int), C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_BeamSelect": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int), ip,
+                                        fp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_BeamFinalize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp,
+                                          ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_PersistentDecodePlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
@@ -242,6 +251,46 @@ def _thresholds(no_speech_threshold, logprob_threshold):
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+_cip = C.POINTER(C.c_int)
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def beam_finalize(hist, S, slot, pool_n, pool_ids, pool_len, pool_score, n: int):
+    """Host only (AX_WHISPER_BeamFinalize): the fill and the ranking of beam search on the state after the loop. hist / pool_ids
+    [clips*K][stride], S / slot / pool_len / pool_score [clips*K] (S, slot by rank), pool_n [clips]; n: the histories' length.
+    Returns per clip a dict: ids, sum_logprob, avg_logprob, ended_eot, winner, records [(ids, score, from_pool)]."""
+    L = load_library()
+    hist, pool_ids = _i32(hist), _i32(pool_ids)
+    S, pool_score = _f32(S).reshape(-1), _f32(pool_score).reshape(-1)
+    slot, pool_n, pool_len = _i32(slot).reshape(-1), _i32(pool_n).reshape(-1), _i32(pool_len).reshape(-1)
+    clips, slots = len(pool_n), len(S)
+    K, stride = slots // max(clips, 1), hist.shape[-1]
+    hist, pool_ids = hist.reshape(slots, stride), pool_ids.reshape(slots, stride)
+    rec_ids = np.zeros((slots, stride), dtype=np.int32)
+    rec_len, rec_pool = np.zeros(slots, dtype=np.int32), np.zeros(slots, dtype=np.int32)
+    rec_score = np.zeros(slots, dtype=np.float32)
+    n_rec, winner, n_ids, eot = (np.zeros(clips, dtype=np.int32) for _ in range(4))
+    ids = np.zeros((clips, stride), dtype=np.int32)
+    sum_lp, avg_lp = np.zeros(clips, dtype=np.float32), np.zeros(clips, dtype=np.float32)
+    rc = L.AX_WHISPER_BeamFinalize(clips, K, int(n), stride, hist.ctypes.data_as(ip), S.ctypes.data_as(fp), slot.ctypes.data_as(_cip),
+                                   pool_n.ctypes.data_as(_cip), pool_ids.ctypes.data_as(ip), pool_len.ctypes.data_as(_cip), pool_score.ctypes.data_as(fp),
+                                   rec_ids.ctypes.data_as(ip), rec_len.ctypes.data_as(_cip), rec_score.ctypes.data_as(fp), rec_pool.ctypes.data_as(_cip),
+                                   n_rec.ctypes.data_as(_cip), winner.ctypes.data_as(_cip), ids.ctypes.data_as(ip), n_ids.ctypes.data_as(_cip),
+                                   sum_lp.ctypes.data_as(fp), avg_lp.ctypes.data_as(fp), eot.ctypes.data_as(_cip))
+    if rc != 0:
+        raise RuntimeError("AX_WHISPER_BeamFinalize failed: bad arguments")
+    return [_beam_clip(c, K, ids, n_ids, sum_lp, avg_lp, eot, winner, rec_ids, rec_len, rec_score, rec_pool, n_rec) for c in range(clips)]
+
+
+def _beam_clip(c, K, ids, n_ids, sum_lp, avg_lp, eot, winner, rec_ids, rec_len, rec_score, rec_pool, n_rec):
+    recs = [(rec_ids[c * K + i, : rec_len[c * K + i]].tolist(), np.float32(rec_score[c * K + i]), bool(rec_pool[c * K + i])) for i in range(n_rec[c])]
+    return dict(ids=ids[c, : n_ids[c]].tolist(), sum_logprob=np.float32(sum_lp[c]), avg_logprob=np.float32(avg_lp[c]), ended_eot=bool(eot[c]),
+                winner=int(winner[c]), records=recs)
 
 
 class Whisper:
@@ -451,14 +500,122 @@ class Whisper:
         return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
                      no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
 
+    # ---- beam search (DESIGN.md "Beam search")
+    def run_beam_batch(self, clips, beam_size: int = 5, max_new: int = 0):
+        """Per clip a dict: ids (the winner's, timestamp tokens included, no eot), sum_logprob, avg_logprob, no_speech_logprob,
+        ended_eot (AX_WHISPER_RunPCMBatchBeam). len(clips) * beam_size decoder slots must fit max_batch."""
+        clips = [_f32(c) for c in clips]
+        B = len(clips)
+        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
+        lens = (C.c_int * B)(*[len(c) for c in clips])
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        n = (C.c_int * B)()
+        sm, avg, nsp = (np.zeros(B, dtype=np.float32) for _ in range(3))
+        eot = (C.c_int * B)()
+        self._check(self.L.AX_WHISPER_RunPCMBatchBeam(self.h, ptrs, lens, B, int(beam_size), int(max_new), ids.ctypes.data_as(ip), n,
+                                                      sm.ctypes.data_as(fp), avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), eot), "RunPCMBatchBeam")
+        return [dict(ids=ids[b, : n[b]].tolist(), sum_logprob=np.float32(sm[b]), avg_logprob=np.float32(avg[b]),
+                     no_speech_logprob=np.float32(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+
+    def decode_beam(self, batch: int, beam_size: int, max_new: int = 0, trace: bool = False):
+        """Stage level, after encode_mel of `batch` clips (AX_WHISPER_DecodeBeam). Returns (results, trace): results as
+        run_beam_batch's plus winner and records [(ids, score, from_pool)]; trace is None, or a dict of arrays over the n_steps sampled
+        steps and S = batch * beam_size slots: rows [n][S][n_vocab], cand_id / cand_logprob [n][S][K+1], n_cand [n][S], and after each
+        step's selection S / slot [n][S] by rank, src / tok [n][S] by slot, pool_n [n][batch].
+        With beam_size > 1 the call overwrites the encoded slots (clip c's cross K/V is copied into slots c*K .. c*K+K-1): call
+        encode_mel again before any further decode_* call, decode_beam included. A trace holds max_new rows of S * n_vocab floats:
+        give a budget with it."""
+        K, B, Tc = int(beam_size), int(batch), self.n_text_ctx
+        S = B * K
+        budget = Tc - 3 if max_new <= 0 or max_new > Tc - 3 else int(max_new)
+        ids = np.zeros((B, Tc), dtype=np.int32)
+        n_ids, eot, n_rec, winner = (np.zeros(B, dtype=np.int32) for _ in range(4))
+        sm, avg, nsp = (np.zeros(B, dtype=np.float32) for _ in range(3))
+        rec_ids = np.zeros((max(S, 1), Tc), dtype=np.int32)
+        rec_len, rec_pool = np.zeros(max(S, 1), dtype=np.int32), np.zeros(max(S, 1), dtype=np.int32)
+        rec_score = np.zeros(max(S, 1), dtype=np.float32)
+        n_steps = C.c_int()
+        t = None
+        if trace and S > 0 and 1 <= K <= 8:
+            t = dict(rows=np.zeros((budget, S, self.n_vocab), dtype=np.float32), cand_id=np.zeros((budget, S, K + 1), dtype=np.int32),
+                     cand_logprob=np.zeros((budget, S, K + 1), dtype=np.float32), n_cand=np.zeros((budget, S), dtype=np.int32),
+                     S=np.zeros((budget, S), dtype=np.float32), slot=np.zeros((budget, S), dtype=np.int32), src=np.zeros((budget, S), dtype=np.int32),
+                     tok=np.zeros((budget, S), dtype=np.int32), pool_n=np.zeros((budget, B), dtype=np.int32))
+        pf = lambda k: t[k].ctypes.data_as(fp) if t else None
+        pi = lambda k: t[k].ctypes.data_as(ip) if t else None
+        self._check(self.L.AX_WHISPER_DecodeBeam(self.h, B, K, int(max_new), ids.ctypes.data_as(ip), n_ids.ctypes.data_as(_cip), sm.ctypes.data_as(fp),
+                                                 avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), eot.ctypes.data_as(_cip), rec_ids.ctypes.data_as(ip),
+                                                 rec_len.ctypes.data_as(_cip), rec_score.ctypes.data_as(fp), rec_pool.ctypes.data_as(_cip),
+                                                 n_rec.ctypes.data_as(_cip), winner.ctypes.data_as(_cip), budget if t else 0, pf("rows"), pi("cand_id"),
+                                                 pf("cand_logprob"), pi("n_cand"), pf("S"), pi("slot"), pi("src"), pi("tok"), pi("pool_n"),
+                                                 C.byref(n_steps)), "DecodeBeam")
+        out = []
+        for c in range(B):
+            r = _beam_clip(c, K, ids, n_ids, sm, avg, eot, winner, rec_ids, rec_len, rec_score, rec_pool, n_rec)
+            r["no_speech_logprob"] = np.float32(nsp[c])
+            out.append(r)
+        if t:
+            t = {k: v[: n_steps.value] for k, v in t.items()}
+            t["n_steps"] = n_steps.value
+        return out, t
+
+    def beam_candidates(self, logits, histories, n_cand_max: int):
+        """The candidates kernel alone: logits [rows][n_vocab], one id history per row -> (cand_id [rows][M], cand_logprob [rows][M],
+        n_cand [rows]); entries from n_cand on are eot / -inf (AX_WHISPER_BeamCandidates)."""
+        lg = _f32(logits).reshape(-1, self.n_vocab)
+        B, M = lg.shape[0], int(n_cand_max)
+        hist = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        nh = (C.c_int * B)()
+        for b, h in enumerate(histories):
+            hist[b, : len(h)] = h
+            nh[b] = len(h)
+        cid = np.zeros((B, max(M, 1)), dtype=np.int32)
+        clp = np.zeros((B, max(M, 1)), dtype=np.float32)
+        nc = np.zeros(B, dtype=np.int32)
+        self._check(self.L.AX_WHISPER_BeamCandidates(self.h, lg.ctypes.data_as(fp), hist.ctypes.data_as(ip), nh, B, M, cid.ctypes.data_as(ip),
+                                                     clp.ctypes.data_as(fp), nc.ctypes.data_as(_cip)), "BeamCandidates")
+        return cid, clp, nc
+
+    def beam_select(self, state: dict, cand_id, cand_logprob, n_cand, eot: int = None):
+        """The selection kernel alone (AX_WHISPER_BeamSelect). state: dict(K, n, hist [S][stride], S, slot [S] by rank, pool_n [clips],
+        pool_ids [S][stride], pool_len, pool_score [S], complete [clips]). Returns the new state (same keys, n + 1, hist with the
+        chosen ids at index n — the reorder's copies are NOT applied) plus tok, src, slot_score [S] by slot and n_completed."""
+        K, n = int(state["K"]), int(state["n"])
+        hist, pool_ids = _i32(state["hist"]).copy(), _i32(state["pool_ids"]).copy()
+        stride = hist.shape[-1]
+        S, pool_score = _f32(state["S"]).reshape(-1).copy(), _f32(state["pool_score"]).reshape(-1).copy()
+        slot, pool_n = _i32(state["slot"]).reshape(-1).copy(), _i32(state["pool_n"]).reshape(-1).copy()
+        pool_len, complete = _i32(state["pool_len"]).reshape(-1).copy(), _i32(state["complete"]).reshape(-1).copy()
+        clips, slots = len(pool_n), len(S)
+        cid, clp, nc = _i32(cand_id).reshape(slots, -1), _f32(cand_logprob).reshape(slots, -1), _i32(n_cand).reshape(-1)
+        tok, src = np.zeros(slots, dtype=np.int32), np.zeros(slots, dtype=np.int32)
+        ss = np.zeros(slots, dtype=np.float32)
+        done = C.c_int()
+        self._check(self.L.AX_WHISPER_BeamSelect(self.h, clips, K, self.eot if eot is None else int(eot), n, stride, cid.ctypes.data_as(ip),
+                                                 clp.ctypes.data_as(fp), nc.ctypes.data_as(_cip), hist.ctypes.data_as(ip), S.ctypes.data_as(fp),
+                                                 slot.ctypes.data_as(_cip), pool_n.ctypes.data_as(_cip), pool_ids.ctypes.data_as(ip),
+                                                 pool_len.ctypes.data_as(_cip), pool_score.ctypes.data_as(fp), complete.ctypes.data_as(_cip),
+                                                 tok.ctypes.data_as(ip), src.ctypes.data_as(_cip), ss.ctypes.data_as(fp), C.byref(done)), "BeamSelect")
+        hist = hist.reshape(slots, stride)
+        complete_before = _i32(state["complete"]).reshape(-1)
+        for s_ in range(slots):
+            if not complete_before[s_ // K]:
+                hist[s_, n] = tok[s_]
+        return dict(K=K, n=n + 1, hist=hist, S=S, slot=slot, pool_n=pool_n, pool_ids=pool_ids.reshape(slots, stride), pool_len=pool_len,
+                    pool_score=pool_score, complete=complete, tok=tok, src=src, slot_score=ss, n_completed=done.value)
+
+    beam_finalize = staticmethod(beam_finalize)
+
     def segments(self, ids, num_samples: int):
         """[(start_s, end_s, text)] of one clip's timestamp-mode ids."""
         clip_s = min(num_samples / 16000.0, 30.0)
         return [(s, e, self.transcript(ids[tb:te])) for s, e, tb, te in split_segments(ids, self.timestamp_begin, self.eot, clip_s)]
 
-    def run_timestamps(self, audio, max_new: int = 0):
-        """PCM (16 kHz mono f32) -> [(start_s, end_s, text)], one entry per segment."""
+    def run_timestamps(self, audio, max_new: int = 0, beam_size: int = 1):
+        """PCM (16 kHz mono f32) -> [(start_s, end_s, text)], one entry per segment. beam_size > 1: of the beam search's winner."""
         a = _f32(audio)
+        if beam_size > 1:
+            return self.segments(self.run_beam_batch([a], beam_size, max_new)[0]["ids"], len(a))
         return self.segments(self.run_timestamp_tokens_batch([a], max_new)[0], len(a))
 
     # ---- long-form: audio longer than 30 s, seek over 30 s windows on the segment timestamps

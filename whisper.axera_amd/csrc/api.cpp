@@ -478,6 +478,72 @@ AX_WHISPER_API int AX_WHISPER_NoSpeechLogProb(AX_WHISPER_HANDLE handle, const fl
   return guarded(handle, [&](Engine& e) { e.no_speech_logprob(logits, batch, out); });
 }
 
+// ---- beam search (DESIGN.md "Beam search")
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchBeam(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                              int beam_size, int max_new, int32_t* ids, int* n_ids, float* sum_logprob,
+                                              float* avg_logprob, float* no_speech_logprob, int* ended_eot) {
+  if (!handle || !pcm || !num_samples || !ids || !n_ids || !sum_logprob || !avg_logprob || !no_speech_logprob || !ended_eot || batch < 1) return -1;
+  for (int b = 0; b < batch; ++b)
+    if (!pcm[b] || num_samples[b] < 1) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    const axw::BeamResult out{ids, n_ids, sum_logprob, avg_logprob, ended_eot, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    g.run_beam(pcm, num_samples, batch, beam_size, max_new, g.primary().config().n_text_ctx, out, no_speech_logprob);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_DecodeBeam(AX_WHISPER_HANDLE handle, int batch, int beam_size, int max_new, int32_t* ids, int* n_ids,
+                                         float* sum_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot,
+                                         int32_t* rec_ids, int* rec_len, float* rec_score, int* rec_pool, int* n_rec, int* winner,
+                                         int trace_cap, float* tr_rows, int32_t* tr_cand_id, float* tr_cand_logprob, int* tr_n_cand,
+                                         float* tr_S, int* tr_slot, int* tr_src, int32_t* tr_tok, int* tr_pool_n, int* n_steps) {
+  if (!handle || !ids || !n_ids || batch < 1 || trace_cap < 0) return -1;
+  return guarded(handle, [&](Engine& e) {
+    const axw::BeamResult out{ids, n_ids, sum_logprob, avg_logprob, ended_eot, rec_ids, rec_len, rec_score, rec_pool, n_rec, winner};
+    Engine::BeamTrace tr{trace_cap, tr_rows, tr_cand_id, tr_cand_logprob, tr_n_cand, tr_S, tr_slot, tr_src, tr_tok, tr_pool_n, 0};
+    e.decode_beam(batch, beam_size, max_new, out, no_speech_logprob, &tr);
+    if (n_steps) *n_steps = tr.n_steps;
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_BeamCandidates(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
+                                             int rows, int n_cand_max, int32_t* cand_id, float* cand_logprob, int* n_cand) {
+  if (!handle || !logits || !hist || !n_hist || !cand_id || !cand_logprob || !n_cand || rows < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.beam_candidates(logits, hist, n_hist, rows, n_cand_max, cand_id, cand_logprob, n_cand); });
+}
+
+AX_WHISPER_API int AX_WHISPER_BeamSelect(AX_WHISPER_HANDLE handle, int clips, int beam_size, int eot, int n, int stride,
+                                         const int32_t* cand_id, const float* cand_logprob, const int* n_cand, const int32_t* hist,
+                                         float* S, int* slot, int* pool_n, int32_t* pool_ids, int* pool_len, float* pool_score,
+                                         int* complete, int32_t* tok, int* src, float* slot_score, int* n_completed) {
+  if (!handle || !cand_id || !cand_logprob || !n_cand || !hist || !S || !slot || !pool_n || !pool_ids || !pool_len || !pool_score || !complete ||
+      !tok || !src || !slot_score || !n_completed || clips < 1)
+    return -1;
+  return guarded(handle, [&](Engine& e) {
+    const Engine::BeamSelectIO io{clips, beam_size, eot, n, stride, cand_id, cand_logprob, n_cand, hist, S, slot, pool_n, pool_ids, pool_len,
+                                  pool_score, complete, tok, src, slot_score};
+    *n_completed = e.beam_select(io);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_BeamFinalize(int clips, int beam_size, int n, int stride, const int32_t* hist, const float* S,
+                                           const int* slot, const int* pool_n, const int32_t* pool_ids, const int* pool_len,
+                                           const float* pool_score, int32_t* rec_ids, int* rec_len, float* rec_score, int* rec_pool,
+                                           int* n_rec, int* winner, int32_t* ids, int* n_ids, float* sum_logprob, float* avg_logprob,
+                                           int* ended_eot) {
+  if (!hist || !S || !slot || !pool_n || !pool_ids || !pool_len || !pool_score || clips < 1 || beam_size < 1 || beam_size > axw::kBeamSizeMax ||
+      n < 0 || n > stride)
+    return -1;
+  for (int c = 0; c < clips; ++c)
+    if (pool_n[c] < 0 || pool_n[c] > beam_size) return -1;
+  for (int i = 0; i < clips * beam_size; ++i)
+    if (slot[i] < 0 || slot[i] >= clips * beam_size || pool_len[i] < 0 || pool_len[i] > stride) return -1;
+  return guarded_host([&] {
+    const axw::BeamState st{clips, beam_size, n, stride, hist, S, slot, pool_n, pool_ids, pool_len, pool_score};
+    axw::beam_finalize(st, axw::BeamResult{ids, n_ids, sum_logprob, avg_logprob, ended_eot, rec_ids, rec_len, rec_score, rec_pool, n_rec, winner});
+    return 0;
+  });
+}
+
 // Host only: one clip's ids (eot excluded) -> segments (DESIGN.md "Segment timestamps": openai-whisper's single-window split,
 // plus the tail rule). Any ids are accepted; the result never exceeds n_max entries.
 AX_WHISPER_API int AX_WHISPER_SplitSegments(const int32_t* ids, int n, int timestamp_begin, int eot, float clip_seconds, int n_max,

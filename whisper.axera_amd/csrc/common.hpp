@@ -496,6 +496,53 @@ void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams&
 // out[b] = logits[b][id] - logsumexp(logits[b][0 .. n_vocab)), NaN entries left out; rows [batch][stride], stride a multiple of 4
 void launch_row_logprob(const float* logits, long stride, int n_vocab, int id, int batch, float* out, hipStream_t s);
 
+// ---- beam search (decode_beam.hip; DESIGN.md "Beam search"): a clip owns K = beam slots [clip * K, clip * K + K); a hypothesis
+// ("rank") of the clip lives in one of them. Three launches per step on one stream, in this order.
+constexpr int kBeamMax = 8;                  // K
+constexpr int kBeamMaxCand = kBeamMax + 1;   // M = K + 1 candidates per hypothesis
+// One workgroup per slot: the M best ids of the final allowed set A (scored mode's: rules 1-5, NaN and -inf out) of the slot's
+// row under its history, value descending, lower id first on equal values, each with x[c] - logsumexp(x[A]).
+struct BeamCandParams {
+  const float* logits; long stride;  // fp32 rows [n_slots][stride], stride a multiple of 4
+  int n_slots, n_vocab, eot, ts_begin;
+  const int* hist; int hist_stride;  // histories [n_slots][hist_stride] (prefix excluded)
+  const int* n_hist; int n;          // history lengths: device [n_slots], or nullptr: n for every slot
+  const float* slot_score;           // device [n_slots] or nullptr: a slot whose value is -inf is dead and proposes nothing
+  const int* complete; int beam;     // device [n_slots / beam] or nullptr: the slots of a complete clip propose nothing
+  int n_cand_max;                    // M <= kBeamMaxCand
+  int* cand_id; float* cand_logprob; // out [n_slots][M]; entries from n_cand on: eot, -inf
+  int* n_cand;                       // out [n_slots]: min(M, |A|)
+};
+void launch_beam_candidates(const BeamCandParams& p, hipStream_t s);
+// One wave per clip: score = S[parent] + logprob in float32; order by score descending, parent rank, position; walk as
+// openai-whisper's BeamSearchDecoder.update. All state is read first and then overwritten in place.
+struct BeamSelectParams {
+  int n_clips, beam, eot, n;               // n: history length before this step (the chosen ids go to hist[.][n])
+  const int* cand_id; const float* cand_logprob; const int* n_cand;  // by slot, M = beam + 1 per slot
+  float* S; int* slot;                     // in/out [n_clips * beam] by rank: sum_logprob (-inf: dead), the rank's slot
+  float* slot_score;                       // out [n_clips * beam] by slot: S of the rank that lives there
+  int* hist; int hist_stride;              // in [.][0, n) / out [.][n], by slot
+  int* src;                                // out [n_clips * beam] by slot: the slot its history and cache come from (itself: stays)
+  int* pool_n;                             // in/out [n_clips]
+  int* pool_ids; int* pool_len; float* pool_score;  // in/out [n_clips * beam][hist_stride] / [n_clips * beam]: records in the order they finished
+  int* complete;                           // in/out [n_clips]
+  int* n_complete;                         // device counter, bumped once per clip that completes
+};
+void launch_beam_select(const BeamSelectParams& p, hipStream_t s);
+// For every slot with src[slot] != slot: hist[0, n) and, for every (layer, head), the 64-key blocks covering keys [0, off] of K and V
+struct BeamReorderParams {
+  const int* src; int n_slots;
+  int* hist; int hist_stride; int n;
+  h16* k; h16* v;                          // self-attention caches, layer 0, slot 0
+  long kv_batch_stride; int cap;           // elements of one slot of one layer; allocated slots (layer stride = cap * kv_batch_stride)
+  int n_layer, n_head, n_ctx_pad, off;
+};
+void launch_beam_reorder(const BeamReorderParams& p, hipStream_t s);
+// cross K/V of slot src -> slots dst0 .. dst0 + n_dst - 1 in every layer (src itself is skipped); slot_elems a multiple of 8.
+// Spreading clips 0 .. C-1 to groups of K: launch for the clips in DESCENDING order (clip i's destinations start at i * K >= i,
+// so sources not yet spread are never overwritten).
+void launch_beam_spread_cross(h16* k, h16* v, long layer_stride, long slot_elems, int n_layer, int src, int dst0, int n_dst, hipStream_t s);
+
 // ---- persistent decode (decode_persistent.hip, decode_persistent2.hip): the whole greedy loop of one to three clips in ONE launch
 typedef unsigned long long u64;
 struct PersistParams {

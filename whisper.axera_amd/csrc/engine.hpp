@@ -103,6 +103,13 @@ struct SlotViews {
   int *d_tok_ = nullptr, *d_done_ = nullptr, *d_done_none_ = nullptr, *d_nout_ = nullptr, *d_out_ids_ = nullptr, *d_max_new_clip_ = nullptr;
   int* d_off_ = nullptr;   // per-slot offsets (common.hpp: DecState)
   int* d_slot_map_ = nullptr;            // [cap]: clip index of an admission pass -> slot
+  // beam search (engine_beam.cpp; common.hpp: BeamCandParams / BeamSelectParams): per-slot and per-clip state [cap], histories and
+  // pool ids [cap][n_text_ctx], candidates [cap][kBeamMaxCand]; allocated on first use under device_capture_mutex
+  struct BeamViews {
+    int *hist = nullptr, *cand_id = nullptr, *n_cand = nullptr, *slot = nullptr, *src = nullptr, *pool_n = nullptr, *pool_ids = nullptr,
+        *pool_len = nullptr, *complete = nullptr, *n_complete = nullptr;
+    float *cand_lp = nullptr, *S = nullptr, *slot_score = nullptr, *pool_score = nullptr;
+  } beam_;
   DecState* d_state_ = nullptr;
 };
 
@@ -126,6 +133,12 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
                        const SampleSpec* sample = nullptr) override;
   void no_speech_logprob(const float* logits, int batch, float* out) override;
+  void run_beam(const float* const* pcm, const int* n_samples, int clips, int beam_size, int max_new, const BeamResult& out,
+                float* no_speech_logprob) override;
+  void decode_beam(int clips, int beam_size, int max_new, const BeamResult& out, float* no_speech_logprob, BeamTrace* trace) override;
+  void beam_candidates(const float* logits, const int32_t* hist, const int* n_hist, int rows, int n_cand_max, int32_t* cand_id,
+                       float* cand_logprob, int* n_cand) override;
+  int beam_select(const BeamSelectIO& io) override;
   void stream_open(int n_slots) override;
   void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) override;
   int stream_step(int n_steps, int* finished_slots) override;
@@ -216,6 +229,12 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // batch 1: the whole loop as one persistent launch (decode_persistent.hip); returns steps run, -1 if it gave up
   int run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot = 0, int max_new1 = -1, int max_new2 = -1);
   void fetch_ids(int batch, int32_t* ids, int* n_ids);
+  // beam search (engine_beam.cpp)
+  void ensure_beam_buffers();
+  void beam_begin(int clips, int K);  // the start state of `clips` groups of K slots, on the stream
+  void enqueue_beam_tail(int clips, int K, int off, int max_new, hipStream_t s);  // candidates, selection, reorder (off >= 2), advance
+  void beam_spread_cross(int clips, int K);
+  int beam_loop(int clips, int K, int max_new, const BeamResult& out, float* no_speech_logprob, BeamTrace* trace);
 
   ModelConfig cfg_;
   int sot_seq_[4] = {0, 0, 0, 0};
@@ -293,6 +312,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   float* d_qfold_ = nullptr;  // query-fold arena of the one-clip launch (d_model <= 768), nullptr = unfolded
   // bench hooks (engine_bench.cpp): one private function per target, each returns what bench() returns
   float bench_decode_step(const std::string& what, int batch, int arg, int iters);
+  float bench_decode_step_beam(int slots, int beam_size, int iters);
   float bench_attn_stamp(int batch, int arg, int iters);
   float bench_encoder(int batch, int iters);
   float bench_frontend(int batch, int iters);

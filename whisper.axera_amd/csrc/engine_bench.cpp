@@ -66,6 +66,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn" || what == "decode_step_ts" || what == "decode_step_ts_scored" ||
       what == "decode_step_ts_sampled")
     return bench_decode_step(what, batch, arg, iters);
+  if (what == "decode_step_beam") return bench_decode_step_beam(batch, arg, iters);
   if (what == "attn_stamp") return bench_attn_stamp(batch, arg, iters);
   if (what == "encoder") return bench_encoder(batch, iters);
   if (what == "frontend") return bench_frontend(batch, iters);
@@ -118,6 +119,70 @@ float Engine::bench_decode_step(const std::string& what, int batch, int arg, int
   HIP_CHECK(hipMemcpy(d_state_, &st, sizeof(st), hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(d_off_, offs.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
   return timed_ms(s, [&] { for (int i = 0; i < iters; ++i) HIP_CHECK(hipGraphLaunch(g, s)); });
+}
+
+// bench "decode_step_beam": the beam step (graph up to the logits dump + the four launches behind it) of `slots` slots in groups of
+// beam_size, from decode offset 224 (or what the context allows) on, one offset further per iteration. The pass runs twice from the
+// same state (zeroed self-attention caches, the start state of a decode placed at that offset): once timed, once more with the
+// reorder's source map read back after every iteration, so that the figure has a known meaning — GetConfigInt
+// "beam_bench_moved_slots": slots the reorder launch copied, summed over the iterations; "beam_bench_iters": iterations run;
+// "beam_bench_complete_clips": clips complete at the end (their kernels return at once).
+float Engine::bench_decode_step_beam(int slots, int beam_size, int iters) {
+  if (beam_size < 1 || beam_size > kBeamMax) throw std::runtime_error("bench decode_step_beam: arg is the beam size, 1 .. " + std::to_string(kBeamMax));
+  require_scored_vocab();
+  if (slots < beam_size || slots % beam_size != 0) throw std::runtime_error("bench decode_step_beam: batch must be a multiple of the beam size");
+  const int clips = slots / beam_size, Tc = cfg_.n_text_ctx;
+  hipStream_t s = stream();
+  hipGraphExec_t g = step_graph(StepSpec{kDecodeScored, 11}, slots, Tc - 3);
+  ensure_beam_buffers();
+  const int off0 = std::max(2, std::min(224, Tc - 2 - iters));
+  DecState st{off0, 0, 0, 0};
+  std::vector<int> offs(slots, off0), src(slots);
+  const size_t self_bytes = (size_t)cfg_.n_text_layer * cap_ * cfg_.n_text_head * layout::kv_head_elems(Tc) * sizeof(h16);
+  auto place = [&] {
+    HIP_CHECK(hipMemcpyAsync(d_state_, &st, sizeof(st), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_off_, offs.data(), (size_t)slots * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  };
+  long moved = 0;
+  int ran = 0;
+  auto pass = [&](bool count) {
+    HIP_CHECK(hipMemsetAsync(d_self_k_, 0, self_bytes, s));
+    HIP_CHECK(hipMemsetAsync(d_self_v_, 0, self_bytes, s));
+    reset_decode_state(slots);
+    beam_begin(clips, beam_size);
+    place();
+    HIP_CHECK(hipGraphLaunch(g, s));  // warm
+    enqueue_beam_tail(clips, beam_size, off0, Tc - 3, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    place();
+    const Event a = make_event(), b = make_event();
+    HIP_CHECK(hipEventRecord(a, s));
+    for (int i = 0; i < iters && off0 + i < Tc - 1; ++i) {
+      HIP_CHECK(hipGraphLaunch(g, s));
+      enqueue_beam_tail(clips, beam_size, off0 + i, Tc - 3, s);
+      if (count) {
+        HIP_CHECK(hipMemcpyAsync(src.data(), beam_.src, (size_t)slots * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        for (int k = 0; k < slots; ++k) moved += src[k] != k;
+        ++ran;
+      }
+    }
+    HIP_CHECK(hipEventRecord(b, s));
+    HIP_CHECK(hipEventSynchronize(b));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    return ms;
+  };
+  const float ms = pass(false);
+  (void)pass(true);
+  int n_complete = 0;
+  HIP_CHECK(hipMemcpyAsync(&n_complete, beam_.n_complete, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  cfg_.ints["beam_bench_moved_slots"] = moved;
+  cfg_.ints["beam_bench_iters"] = ran;
+  cfg_.ints["beam_bench_complete_clips"] = n_complete;
+  return ms;
 }
 
 // One replay of the production step graph (all launches, every branch) at decode offset `arg` whose decode_attention

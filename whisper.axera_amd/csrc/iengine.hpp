@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "beam.hpp"
 #include "longform.hpp"
 
 namespace axw {
@@ -72,6 +73,35 @@ class IEngine {
                                const SampleSpec* sample = nullptr) = 0;
   // the no-speech kernel alone: logits [batch][n_vocab] -> out [batch] = log p(<|nospeech|>) over the whole row
   virtual void no_speech_logprob(const float* logits, int batch, float* out) = 0;
+  // beam search (DESIGN.md "Beam search"; beam.hpp): K = beam_size hypotheses per clip, each in a slot of its own, so clips * K
+  // slots must fit the engine's capacity. out: the winner and every record of every clip (BeamResult's arrays, stride n_text_ctx).
+  // trace (decode_beam only; null: none): per sampled step n < cap, over S = clips * K slots: the dumped rows [cap][S][n_vocab], the
+  // candidates [cap][S][K + 1] and their counts [cap][S], and after the selection sum_logprob by rank [cap][S], rank -> slot
+  // [cap][S], the reorder's source by slot [cap][S], the id written at the history's index n by slot [cap][S], pool sizes [cap][clips].
+  // Every array may be null. n_steps: sampled steps the loop ran.
+  // decode_beam with beam_size > 1 spreads clip c's cross K/V over slots [c K, c K + K): the encoded slots are overwritten, and a
+  // further stage-level decode needs a new encode_mel.
+  struct BeamTrace {
+    int cap; float* rows; int32_t* cand_id; float* cand_logprob; int* n_cand; float* S; int* slot; int* src; int32_t* tok; int* pool_n;
+    int n_steps;
+  };
+  virtual void run_beam(const float* const* pcm, const int* n_samples, int clips, int beam_size, int max_new, const BeamResult& out,
+                        float* no_speech_logprob) = 0;
+  virtual void decode_beam(int clips, int beam_size, int max_new, const BeamResult& out, float* no_speech_logprob, BeamTrace* trace) = 0;
+  // the candidates kernel alone on host data: logits [rows][n_vocab], hist [rows][n_text_ctx] (n_hist[b] ids each) ->
+  // cand_id, cand_logprob [rows][n_cand_max], n_cand [rows]
+  virtual void beam_candidates(const float* logits, const int32_t* hist, const int* n_hist, int rows, int n_cand_max, int32_t* cand_id,
+                               float* cand_logprob, int* n_cand) = 0;
+  // the selection kernel alone on host data (common.hpp: BeamSelectParams; every pointer is host memory here, M = beam + 1):
+  // S, slot, pool_*, complete are updated in place; tok, src by slot and slot_score are written; returns the clips that completed
+  struct BeamSelectIO {
+    int clips, beam, eot, n, stride;
+    const int32_t* cand_id; const float* cand_logprob; const int* n_cand;
+    const int32_t* hist;
+    float* S; int* slot; int* pool_n; int32_t* pool_ids; int* pool_len; float* pool_score; int* complete;
+    int32_t* tok; int* src; float* slot_score;
+  };
+  virtual int beam_select(const BeamSelectIO& io) = 0;
   // utterance slots refilled while the others decode (include/ax_whisper_api.h: AX_WHISPER_Stream*)
   virtual void stream_open(int n_slots) = 0;
   virtual void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) = 0;

@@ -107,6 +107,24 @@ class DeviceGroup {
     });
   }
 
+  // Beam search (E::run_beam; R: the result arrays of beam.hpp, all per-clip with row stride n_ctx where they are rows): the clips
+  // are split like run_tokens' — every hypothesis of a clip lives on the clip's device.
+  template <typename R>
+  void run_beam(const float* const* pcm, const int* n_samples, int batch, int beam_size, int max_new, int n_ctx, const R& out,
+                float* no_speech_logprob) {
+    if (batch < 1) throw std::runtime_error("batch must be >= 1");
+    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
+    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
+      R o = out;
+      o.ids = from(out.ids, (size_t)lo * n_ctx); o.n_ids = from(out.n_ids, lo);
+      o.sum_logprob = from(out.sum_logprob, lo); o.avg_logprob = from(out.avg_logprob, lo); o.ended_eot = from(out.ended_eot, lo);
+      o.rec_ids = from(out.rec_ids, (size_t)lo * beam_size * n_ctx); o.rec_len = from(out.rec_len, (size_t)lo * beam_size);
+      o.rec_score = from(out.rec_score, (size_t)lo * beam_size); o.rec_pool = from(out.rec_pool, (size_t)lo * beam_size);
+      o.n_rec = from(out.n_rec, lo); o.winner = from(out.winner, lo);
+      e.run_beam(pcm + lo, n_samples + lo, hi - lo, beam_size, max_new, o, from(no_speech_logprob, lo));
+    });
+  }
+
   // Long-form (E::run_long_windows; opts: the thresholds of the silent-window rule, or null): the FILES are split into contiguous
   // blocks, one per engine; every engine runs its own seek loop. The log holds worker 0's windows first, then worker 1's, ...; file
   // indices count over the whole call, pass and slot are the engine's own. W needs an int member `file`. Options with a member

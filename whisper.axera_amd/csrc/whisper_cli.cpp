@@ -24,6 +24,8 @@ static void usage(const char* prog) {
           "  -p, --model_path    model path which contains tiny/ base/ small/ turbo/ (string [=../models-mi355x])\n"
           "      --language      en, zh (string [=zh])\n"
           "      --timestamps    after Result:, one line per segment: [mm:ss.mmm --> mm:ss.mmm] text\n"
+          "      --beam_size N   (with --timestamps, not with --long) the segment lines are those of beam search's winner over N\n"
+          "                      hypotheses (1 .. 8; openai-whisper's CLI uses 5) instead of the greedy decode's\n"
           "      --long          transcribe the whole file, not only its first 30 s: Result: is the whole text, followed by\n"
           "                      one [mm:ss.mmm --> mm:ss.mmm] line per segment with times from the file's start (hours\n"
           "                      roll into the minutes: 75:03.120). RTF: is wall time over the file's duration; without\n"
@@ -93,8 +95,9 @@ static std::string mmss_ms(long ms) {
 }
 static std::string mmss(float t) { return mmss_ms((long)(t * 1000.f + 0.5f)); }
 
-// --timestamps: the clip decoded again in timestamp mode, split into segments (AX_WHISPER_SplitSegments), one line each
-static int print_segments(AX_WHISPER_HANDLE h, const char* wav) {
+// --timestamps: the clip decoded again in timestamp mode (beam_size > 1: by beam search, AX_WHISPER_RunPCMBatchBeam), split into
+// segments (AX_WHISPER_SplitSegments), one line each
+static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size) {
   float* pcm = nullptr;
   int n = 0;
   if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
@@ -102,7 +105,10 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav) {
   std::vector<int32_t> ids(n_ctx > 0 ? n_ctx : 448);
   int n_ids = 0;
   const float* clips[1] = {pcm};
-  const int rc = AX_WHISPER_RunPCMBatchTimestampTokens(h, clips, &n, 1, 0, nullptr, ids.data(), &n_ids);
+  float sum_lp = 0.f, avg_lp = 0.f, nsp = 0.f;
+  int ended = 0;
+  const int rc = beam_size > 1 ? AX_WHISPER_RunPCMBatchBeam(h, clips, &n, 1, beam_size, 0, ids.data(), &n_ids, &sum_lp, &avg_lp, &nsp, &ended)
+                               : AX_WHISPER_RunPCMBatchTimestampTokens(h, clips, &n, 1, 0, nullptr, ids.data(), &n_ids);
   free(pcm);
   if (rc != 0) return -1;
   const float clip_s = n / 16000.f < 30.f ? n / 16000.f : 30.f;
@@ -180,7 +186,7 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
   bool timestamps = false, longform = false;
-  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg;
+  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -195,7 +201,8 @@ int main(int argc, char** argv) {
     };
     if (val("wav", "-w", wav) || val("model_type", "-t", model_type) || val("model_path", "-p", model_path) ||
         val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg) ||
-        val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg))
+        val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg) ||
+        val("beam_size", nullptr, beam_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -205,6 +212,14 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (wav.empty()) { fprintf(stderr, "need option: --wav\n"); usage(argv[0]); return 1; }
+  int beam_size = 1;
+  if (!beam_arg.empty()) {
+    char* end = nullptr;
+    const long v = strtol(beam_arg.c_str(), &end, 10);
+    if (*end || v < 1 || v > 8) { fprintf(stderr, "bad value: --beam_size %s (1 .. 8)\n", beam_arg.c_str()); return 1; }
+    beam_size = (int)v;
+    if (!timestamps || longform) { fprintf(stderr, "--beam_size needs --timestamps and does not go with --long\n"); usage(argv[0]); return 1; }
+  }
   // --compression_ratio_threshold turns temperature fallback on: attempts at 0, inc, 2 inc, .. 1.0 (inc 0.2 unless given)
   const bool fallback = !crt_arg.empty();
   if ((!tinc_arg.empty() || !seed_arg.empty()) && !fallback) { fprintf(stderr, "--temperature_increment / --seed need --compression_ratio_threshold\n"); usage(argv[0]); return 1; }
@@ -244,7 +259,9 @@ int main(int argc, char** argv) {
   const float duration = frames * 1.f / 16000;
 
   auto t0 = std::chrono::steady_clock::now();
-  AX_WHISPER_HANDLE handle = AX_WHISPER_Init(model_type.c_str(), model_path.c_str(), language.c_str());
+  // (beam search: one decoder slot per hypothesis)
+  AX_WHISPER_HANDLE handle = beam_size > 1 ? AX_WHISPER_InitEx(model_type.c_str(), model_path.c_str(), language.c_str(), -1, beam_size)
+                                           : AX_WHISPER_Init(model_type.c_str(), model_path.c_str(), language.c_str());
   auto t1 = std::chrono::steady_clock::now();
   if (!handle) { printf("AX_WHISPER_Init failed!\n"); return -1; }
   printf("Init whisper success, take %.4fseconds\n", std::chrono::duration<double>(t1 - t0).count());
@@ -274,7 +291,7 @@ int main(int argc, char** argv) {
   t1 = std::chrono::steady_clock::now();
   printf("Result: %s\n", result);
   const double rtf = std::chrono::duration<double>(t1 - t0).count() / duration;  // of AX_WHISPER_RunFile alone
-  if (timestamps && print_segments(handle, wav.c_str()) != 0) {
+  if (timestamps && print_segments(handle, wav.c_str(), beam_size) != 0) {
     printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
     free(result);
     AX_WHISPER_Uninit(handle);
