@@ -312,7 +312,7 @@ AX_WHISPER_API int AX_WHISPER_WindowNeedsFallback(float compression_ratio, float
  *  stream of a window is (seek, file id * 16 + attempt). file_ids [n_files] (each 0 .. 2^27 - 1) are the caller's names for its files;
  *  NULL: a file's id is its index in this call. Equal (seed, file id) give a file the same windows beside any other files, at any
  *  position in the call and on any number of devices; with NULL that holds for a file at the same index only (a file moved to
- *  another index draws other noise). RunPCMLongFallback / RunFileLongFallback use file id 0. Not covered: best_of > 1, beam search inside this loop (RunPCMBatchBeam decodes single windows), prompt reset, the Stream* calls. */
+ *  another index draws other noise). RunPCMLongFallback / RunFileLongFallback use file id 0. Not covered: best_of > 1, beam search inside this loop (RunPCMBatchBeam decodes single windows), the Stream* calls. Prompt conditioning and the prompt reset: RunPCMLongWindowsPrompted. */
 AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsFallback(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
                                                         int n_files, int max_new, int max_passes, float no_speech_threshold,
                                                         float logprob_threshold, float compression_ratio_threshold,
@@ -325,6 +325,71 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongFallback(AX_WHISPER_HANDLE handle, float
 AX_WHISPER_API int AX_WHISPER_RunFileLongFallback(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
                                                   float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
                                                   int n_temperatures, uint64_t seed, char** result);
+
+/* ---- prompt conditioning: prompt ids, a prefill pass, previous-text carry (DESIGN.md "Prompt conditioning")
+ * A prompt is a list of ids (there is no text encoder here): text ids below eot and timestamp ids; any other id is an error. Of a
+ * longer prompt the last n_text_ctx / 2 - 1 = 223 ids are used (openai-whisper's rule). A clip with P > 0 prompt ids decodes from the
+ * context [sot_prev, p_1 .. p_P, sot, language, transcribe] instead of [sot, language, transcribe]; P = 0 means no prompt at all (no
+ * sot_prev either): that clip decodes exactly as the unprompted calls decode it. Timestamp modes only. The context in front of
+ * `transcribe` is computed in one prefill pass (AX_WHISPER_PREFILL=step: fed one position per decoder step instead, as is
+ * every decoder shape the prefill kernels do not take; GetConfigInt "prefill" = the route the handle's prompted calls take, 0 the
+ * pass, 1 step-fed; a value other than prefill / step makes the first prompted call fail); the decisions come from the same steps as without a prompt. A prompted clip ends at eot, at its budget, or
+ * at the context end: at most n_text_ctx - 4 - P ids. Its no_speech_logprob is taken at the sot position of its context.
+ * Not covered: prompts under beam search, in the Stream* calls and whisper_srv, best_of > 1, encoding prompt TEXT to ids. */
+/** RunPCMBatchTimestampScores with prompt_ids [batch][prompt_stride] and n_prompt [batch] (0 .. prompt_stride). Sharded over the
+ *  handle's devices; the prompts travel with their clips. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampPrompted(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                           int batch, int max_new, const int* max_new_clip, const int32_t* prompt_ids,
+                                                           int prompt_stride, const int* n_prompt, int32_t* ids, int* n_ids,
+                                                           float* token_logprob, float* avg_logprob, float* no_speech_logprob,
+                                                           int* ended_eot);
+/** Stage level (after EncodeMel of `batch` clips): the decode state of slots 0 .. batch-1 as the prompted loop finds it before its
+ *  first step: reset, then every prompted slot's context cached and `transcribe` about to be fed. no_speech_logprob (may be NULL):
+ *  [batch], 0 for slots without a prompt; sot_logits (may be NULL): [batch][n_vocab], the raw logits row of the sot position that
+ *  value was taken from (zeros for slots without a prompt). */
+AX_WHISPER_API int AX_WHISPER_PrefillPrompts(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids, int prompt_stride,
+                                             const int* n_prompt, float* no_speech_logprob, float* sot_logits);
+/** Rows 0 .. n_rows-1 of the slot's self-attention cache, de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][n_text_state]. */
+AX_WHISPER_API int AX_WHISPER_GetSelfKV(AX_WHISPER_HANDLE handle, int slot, int n_rows, float* k_out, float* v_out);
+/** DecodeForcedTimestampScores under prompts (every clip needs one): forced [batch][n_forced] follow each clip's own context, row i
+ *  of logits / chosen / logprob [batch][n_forced+1] is the step that decides id i. There is no row of decode offset 0. */
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampPrompted(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids,
+                                                            int prompt_stride, const int* n_prompt, const int32_t* forced, int n_forced,
+                                                            float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob);
+/** Host only (no handle, no GPU): one step of the previous-text carry, after a kept window. State: all_ids [n_all] (starts as the
+ *  initial prompt ids) and reset_since. Unless `skipped`, the ids of the window's emitted segments are appended, timestamps
+ *  included, from each segment's opening timestamp to its closing one (the ranges SplitWindow cuts; ids after the last closed pair
+ *  and segments without text add nothing). Then, if condition_on_previous_text is 0 or temperature > 0.5, reset_since becomes the
+ *  new length. all_out (cap >= n_all + n_window ids) takes the new list, *n_all_out its length; *n_prompt_next =
+ *  min(*n_all_out - *reset_since_out, keep): the ids the next window is prompted with are the last that many (keep: 223). */
+AX_WHISPER_API int AX_WHISPER_CarryPrompt(const int32_t* all_ids, int n_all, int reset_since, const int32_t* window_ids, int n_window,
+                                          int timestamp_begin, int eot, int window_frames, int skipped, int condition_on_previous_text,
+                                          float temperature, int keep, int cap, int32_t* all_out, int* n_all_out, int* reset_since_out,
+                                          int* n_prompt_next);
+/** RunPCMLongWindowsFallback under prompt conditioning, per file: all_ids starts as the file's initial prompt
+ *  (initial_prompt_ids [n_files][prompt_stride], n_initial [n_files]; both may be NULL), a window's prompt is all_ids[reset_since:]
+ *  (its last 223 ids; every fallback attempt of a window gets the same one), and CarryPrompt runs after every kept window with the
+ *  kept attempt's temperature — the prompt reset of openai-whisper's loop. n_temperatures = 0 (temperatures may be NULL): no fallback,
+ *  the scored loop, win_score rows have 3 entries; else 7 as in RunPCMLongWindowsFallback. win_prompt (may be NULL): [win_cap], the
+ *  prompt length of every log entry. With no initial prompt and condition_on_previous_text = 0 the log is that of the unprompted call.
+ *  "Emitted segment" differs from openai-whisper's list in one place: a segment is dropped here when it has no text id, there when
+ *  its decoded text is blank or its start equals its end. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsPrompted(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                        int n_files, int max_new, int max_passes, float no_speech_threshold,
+                                                        float logprob_threshold, float compression_ratio_threshold,
+                                                        const float* temperatures, int n_temperatures, uint64_t seed, const int* file_ids,
+                                                        const int32_t* initial_prompt_ids, int prompt_stride, const int* n_initial,
+                                                        int condition_on_previous_text, int win_cap, int* win_info, int32_t* ids,
+                                                        float* win_score, int* win_prompt, int* n_windows);
+/** RunPCMLongFallback / RunFileLongFallback under prompt conditioning (initial_prompt_ids [n_initial], may be NULL / 0). */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongPrompted(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                                 float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                 int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
+                                                 int condition_on_previous_text, char** result);
+AX_WHISPER_API int AX_WHISPER_RunFileLongPrompted(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
+                                                  float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                  int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
+                                                  int condition_on_previous_text, char** result);
 
 /** ---- Beam search (DESIGN.md "Beam search"): openai-whisper's BeamSearchDecoder over this project's timestamp rules.
  *  K = beam_size (1 .. 8) hypotheses ("ranks") per clip, each in a decoder slot of its own: clip c owns slots [c*K, c*K+K), so
@@ -404,7 +469,8 @@ AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
  *  from decode offset 224 on, one offset further per iteration; afterwards GetConfigInt "beam_bench_moved_slots" / "beam_bench_iters" /
  *  "beam_bench_complete_clips" say how many slots the reorder launches copied in all, over how many iterations, and how many clips
  *  had completed), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
- *  files of `arg` seconds + one window kernel), or a kernel name listed in DESIGN.md. */
+ *  files of `arg` seconds + one window kernel), "prefill" (reset + PrefillPrompts of `batch` slots with prompts of arg - 3 ids each,
+ *  i.e. context length L = arg, by the handle's route), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);
 

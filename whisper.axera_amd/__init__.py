@@ -99,6 +99,16 @@ SYMBOLS = {
                                         fp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_BeamFinalize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp,
                                           ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMBatchTimestampPrompted": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.c_int, C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_PrefillPrompts": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), fp, fp]),
+    "AX_WHISPER_GetSelfKV": (C.c_int, [C.c_void_p, C.c_int, C.c_int, fp, fp]),
+    "AX_WHISPER_DecodeForcedTimestampPrompted": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), ip, C.c_int, fp, ip, fp, fp]),
+    "AX_WHISPER_CarryPrompt": (C.c_int, [ip, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, ip,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongWindowsPrompted": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_int),
+                                                       ip, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongPrompted": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunFileLongPrompted": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_PersistentDecodePlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
@@ -221,6 +231,22 @@ def window_needs_fallback(compression_ratio: float, avg_logprob: float, no_speec
     nan = lambda v: float("nan") if v is None else float(v)
     return bool(L.AX_WHISPER_WindowNeedsFallback(float(compression_ratio), float(avg_logprob), float(no_speech_logprob),
                                                  nan(compression_ratio_threshold), nan(logprob_threshold), nan(no_speech_threshold)))
+
+
+def carry_prompt(all_ids, reset_since: int, window_ids, timestamp_begin: int, eot: int, window_frames: int, skipped: bool = False,
+                 condition_on_previous_text: bool = True, temperature: float = 0.0, keep: int = 223):
+    """One step of the previous-text carry after a kept window (AX_WHISPER_CarryPrompt, host only) ->
+    (all_ids, reset_since, n_prompt_next): the next window's prompt is all_ids[reset_since:][-keep:]."""
+    L = load_library()
+    a, w = _i32(all_ids), _i32(window_ids)
+    cap = len(a) + len(w)
+    out = np.zeros(max(cap, 1), dtype=np.int32)
+    n, rs, npn = C.c_int(), C.c_int(), C.c_int()
+    if L.AX_WHISPER_CarryPrompt(a.ctypes.data_as(ip), len(a), int(reset_since), w.ctypes.data_as(ip), len(w), int(timestamp_begin), int(eot),
+                                int(window_frames), int(bool(skipped)), int(bool(condition_on_previous_text)), float(temperature), int(keep), cap,
+                                out.ctypes.data_as(ip), C.byref(n), C.byref(rs), C.byref(npn)) != 0:
+        raise RuntimeError("AX_WHISPER_CarryPrompt failed")
+    return out[: n.value].tolist(), rs.value, npn.value
 
 
 def persistent_decode_plan(d_model: int, n_head: int, n_layer: int, n_cu: int, n_clips: int = 0, t0: int = 0, n_slots: int = 0):
@@ -399,6 +425,73 @@ class Whisper:
                                                                  avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), eot), "RunPCMBatchTimestampScores")
         return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
                      no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+
+    # ---- prompt conditioning (DESIGN.md "Prompt conditioning"): prompts are id lists, an empty one means no prompt
+    @staticmethod
+    def _prompt_args(prompts):
+        B = len(prompts)
+        stride = max(1, max(len(p) for p in prompts))
+        ids = np.zeros((B, stride), dtype=np.int32)
+        for b, p in enumerate(prompts):
+            ids[b, : len(p)] = np.asarray(p, dtype=np.int32)
+        return ids, stride, (C.c_int * B)(*[len(p) for p in prompts])
+
+    def run_timestamp_prompted_batch(self, clips, prompts, max_new: int = 0, max_new_clip=None):
+        """run_timestamp_scores_batch with every clip conditioned on its prompt ids (AX_WHISPER_RunPCMBatchTimestampPrompted): the
+        same dict per clip."""
+        clips = [_f32(c) for c in clips]
+        B = len(clips)
+        if len(prompts) != B:
+            raise ValueError("one prompt (possibly empty) per clip")
+        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
+        lens = (C.c_int * B)(*[len(c) for c in clips])
+        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        pid, stride, npr = self._prompt_args(prompts)
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        n = (C.c_int * B)()
+        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
+        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+        eot = (C.c_int * B)()
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampPrompted(self.h, ptrs, lens, B, max_new, mc, pid.ctypes.data_as(ip), stride, npr,
+                                                                   ids.ctypes.data_as(ip), n, lp.ctypes.data_as(fp), avg.ctypes.data_as(fp),
+                                                                   nsp.ctypes.data_as(fp), eot), "RunPCMBatchTimestampPrompted")
+        return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
+                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+
+    def prefill_prompts(self, prompts, want_no_speech: bool = True, want_sot_logits: bool = False):
+        """Stage level, after encode_mel of len(prompts) clips: reset + the prompted slots' context cached, `transcribe` about to be
+        fed (AX_WHISPER_PrefillPrompts). Returns no_speech_logprob [batch] (0 for slots without a prompt) or None; with
+        want_sot_logits (no_speech_logprob, sot_logits [batch][n_vocab]: the raw row the value was taken from)."""
+        B = len(prompts)
+        pid, stride, npr = self._prompt_args(prompts)
+        nsp = np.zeros(B, dtype=np.float32) if want_no_speech or want_sot_logits else None
+        rows = np.zeros((B, self.n_vocab), dtype=np.float32) if want_sot_logits else None
+        self._check(self.L.AX_WHISPER_PrefillPrompts(self.h, B, pid.ctypes.data_as(ip), stride, npr, nsp.ctypes.data_as(fp) if nsp is not None else None,
+                                                     rows.ctypes.data_as(fp) if want_sot_logits else None), "PrefillPrompts")
+        return (nsp, rows) if want_sot_logits else nsp
+
+    def get_self_kv(self, slot: int, n_rows: int):
+        """Rows [0, n_rows) of the slot's self-attention cache -> (k, v), each fp32 [n_text_layer][n_rows][d]."""
+        k = np.empty((self.n_text_layer, n_rows, self.n_text_state), dtype=np.float32)
+        v = np.empty_like(k)
+        self._check(self.L.AX_WHISPER_GetSelfKV(self.h, slot, n_rows, k.ctypes.data_as(fp), v.ctypes.data_as(fp)), "GetSelfKV")
+        return k, v
+
+    def decode_forced_timestamp_prompted(self, prompts, forced, want_logits: bool = True):
+        """decode_forced_timestamp_scores under prompts (one non-empty prompt per clip): (logits [batch][n+1][n_vocab] or None, chosen,
+        logprob [batch][n+1], no_speech_logprob [batch]); row i is the step that decides id i."""
+        batch = len(prompts)
+        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
+        n = f.shape[1]
+        pid, stride, npr = self._prompt_args(prompts)
+        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
+        ch = np.empty((batch, n + 1), dtype=np.int32)
+        lp = np.empty((batch, n + 1), dtype=np.float32)
+        nsp = np.empty(batch, dtype=np.float32)
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampPrompted(self.h, batch, pid.ctypes.data_as(ip), stride, npr, f.ctypes.data_as(ip), n,
+                                                                    logits.ctypes.data_as(fp) if want_logits else None, ch.ctypes.data_as(ip),
+                                                                    lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp)), "DecodeForcedTimestampPrompted")
+        return logits, ch, lp, nsp
 
     def decode_forced_timestamp_scores(self, batch: int, forced, want_logits: bool = True, want_logits0: bool = True):
         """decode_forced_timestamps + (logprob [batch][n+1] of each step's chosen id, no_speech_logprob [batch], logits0
@@ -627,7 +720,8 @@ class Whisper:
         return out
 
     def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0, no_speech_threshold=None, logprob_threshold=None, scores: bool = False,
-                         compression_ratio_threshold=None, temperatures=None, seed: int = 0, file_ids=None):
+                         compression_ratio_threshold=None, temperatures=None, seed: int = 0, file_ids=None, initial_prompt_ids=None,
+                         condition_on_previous_text: bool = False):
         """The seek loop over `files` (PCM arrays), one window of every unfinished file per pass. Per file, the list of its
         decoded windows (seek, window_frames, advance, ids, pass, slot) in order. max_new: id budget per window;
         max_passes > 0 stops after that many passes (the slots then hold the last pass's cross K/V).
@@ -636,10 +730,15 @@ class Whisper:
         With compression_ratio_threshold or temperatures the call is the fallback one (AX_WHISPER_RunPCMLongWindowsFallback;
         temperatures default to 0, 0.2, .. 1.0): every attempt is a tuple, which gains (attempt, temperature, compression_ratio,
         kept) after those three; there a missing logprob_threshold switches its part of the fallback rule off. file_ids: one id per
-        file naming its random streams (default: its index in `files`); equal (seed, id) give a file the same windows in any call."""
+        file naming its random streams (default: its index in `files`); equal (seed, id) give a file the same windows in any call.
+        With initial_prompt_ids (one id list per file, or None) or condition_on_previous_text the call is the prompted one
+        (AX_WHISPER_RunPCMLongWindowsPrompted; scored, with fallback only if asked for as above): every tuple ends with the length of
+        the prompt its window was conditioned on."""
         fallback = compression_ratio_threshold is not None or temperatures is not None
-        scored = fallback or scores or no_speech_threshold is not None or logprob_threshold is not None
+        prompted = bool(condition_on_previous_text) or initial_prompt_ids is not None
+        scored = prompted or fallback or scores or no_speech_threshold is not None or logprob_threshold is not None
         nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
+        crt, temps = float("nan"), _f32([])
         if fallback:
             lpt = float("nan") if logprob_threshold is None else float(logprob_threshold)
             crt = float("nan") if compression_ratio_threshold is None else float(compression_ratio_threshold)
@@ -656,7 +755,19 @@ class Whisper:
             ids = np.zeros((cap, self.n_text_ctx), dtype=np.int32)
             sc = np.zeros((cap, sw), dtype=np.float32)
             nw = C.c_int()
-            if fallback:
+            wp = np.zeros(cap, dtype=np.int32)
+            if prompted:
+                init = [[] if q is None else list(q) for q in (initial_prompt_ids if initial_prompt_ids is not None else [None] * n)]
+                if len(init) != n:
+                    raise ValueError("one initial prompt (or None) per file")
+                pid, stride, npr = self._prompt_args(init)
+                rc = self.L.AX_WHISPER_RunPCMLongWindowsPrompted(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
+                                                                 temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed),
+                                                                 (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None,
+                                                                 pid.ctypes.data_as(ip), stride, npr, int(bool(condition_on_previous_text)), cap,
+                                                                 info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
+                                                                 sc.ctypes.data_as(fp), wp.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nw))
+            elif fallback:
                 rc = self.L.AX_WHISPER_RunPCMLongWindowsFallback(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
                                                                  temps.ctypes.data_as(fp), len(temps), int(seed),
                                                                  (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None, cap,
@@ -685,19 +796,23 @@ class Whisper:
                 w = w + (float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2]))
             if fallback:
                 w = w + (int(sc[k, 3]), float(sc[k, 4]), float(sc[k, 5]), bool(sc[k, 6]))
+            if prompted:
+                w = w + (int(wp[k]),)
             out[f].append(w)
         return out
 
     def run_long_scored(self, audio, max_new: int = 0, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None,
-                        temperatures=None, seed: int = 0):
+                        temperatures=None, seed: int = 0, initial_prompt_ids=None, condition_on_previous_text: bool = False):
         """run_long with confidence -> [(start_s, end_s, text, avg_logprob, no_speech_prob)]: every segment carries its window's two
         numbers (as openai-whisper reports them); windows the silent-window rule skips yield nothing. With
         compression_ratio_threshold or temperatures: under temperature fallback, the kept attempts only."""
         out = []
         for w in self.run_long_windows([audio], max_new, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, scores=True,
-                                       compression_ratio_threshold=compression_ratio_threshold, temperatures=temperatures, seed=seed)[0]:
+                                       compression_ratio_threshold=compression_ratio_threshold, temperatures=temperatures, seed=seed,
+                                       initial_prompt_ids=None if initial_prompt_ids is None else [initial_prompt_ids],
+                                       condition_on_previous_text=condition_on_previous_text)[0]:
             seek, wf, _adv, ids, _p, _s, nsp, avg, skipped = w[:9]
-            if skipped or (len(w) > 9 and not w[12]):
+            if skipped or (len(w) > 12 and not w[12]):
                 continue
             for s, e, tb, te in split_window(ids, self.timestamp_begin, self.eot, wf)[0]:
                 out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te]), avg, float(np.exp(np.float32(nsp)))))
@@ -712,11 +827,24 @@ class Whisper:
         return out
 
     def run_long_text(self, audio, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None, temperatures=None,
-                      seed: int = 0) -> str:
+                      seed: int = 0, initial_prompt_ids=None, condition_on_previous_text: bool = False) -> str:
         """PCM or a wav path of any length -> the whole text (AX_WHISPER_RunPCMLong / RunFileLong; with a threshold: the *Opts
         forms, the text without the windows the silent-window rule skips; with compression_ratio_threshold or temperatures: the
         *Fallback forms)."""
         out = C.c_void_p()
+        if condition_on_previous_text or (initial_prompt_ids is not None and len(initial_prompt_ids)):  # the *Prompted forms
+            nan = lambda v: float("nan") if v is None else float(v)
+            fallback = compression_ratio_threshold is not None or temperatures is not None
+            temps = _f32((DEFAULT_TEMPERATURES if temperatures is None else temperatures) if fallback else [])
+            init = _i32([] if initial_prompt_ids is None else initial_prompt_ids)
+            tail = (nan(no_speech_threshold), nan(logprob_threshold), nan(compression_ratio_threshold), temps.ctypes.data_as(fp) if fallback else None,
+                    len(temps), int(seed), init.ctypes.data_as(ip), len(init), int(bool(condition_on_previous_text)), C.byref(out))
+            if isinstance(audio, (str, os.PathLike)):
+                self._check(self.L.AX_WHISPER_RunFileLongPrompted(self.h, os.fspath(audio).encode(), *tail), "RunFileLongPrompted")
+            else:
+                a = _f32(audio)
+                self._check(self.L.AX_WHISPER_RunPCMLongPrompted(self.h, a.ctypes.data_as(fp), len(a), *tail), "RunPCMLongPrompted")
+            return self._take(out.value)
         if compression_ratio_threshold is not None or temperatures is not None:
             nan = lambda v: float("nan") if v is None else float(v)
             temps = _f32(DEFAULT_TEMPERATURES if temperatures is None else temperatures)

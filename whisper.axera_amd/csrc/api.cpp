@@ -615,7 +615,7 @@ AX_WHISPER_API int AX_WHISPER_ComputeMelWindow(AX_WHISPER_HANDLE handle, const f
 // the seek loop of RunPCMLongWindows[Scored] (`who`) and its log written out; opts / win_score: the scored call's, or nullptr
 static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* const* pcm, const int* num_samples, int n_files, int max_new,
                         int max_passes, const axw::LongScoreOptions* opts, int win_cap, int* win_info, int32_t* ids, float* win_score,
-                        int* n_windows) {
+                        int* n_windows, int* win_prompt = nullptr) {
   const bool fallback = opts && !opts->temperatures.empty();  // win_score rows then have 7 entries
   if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids || (opts && !win_score))))
     return -1;
@@ -636,6 +636,7 @@ static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* 
       memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
       float* sc = opts ? win_score + k * (fallback ? 7 : 3) : nullptr;
       if (opts) { sc[0] = w.no_speech_logprob; sc[1] = w.avg_logprob; sc[2] = w.skipped ? 1.f : 0.f; }
+      if (win_prompt) win_prompt[k] = w.n_prompt;
       if (fallback) { sc[3] = (float)w.attempt; sc[4] = w.temperature; sc[5] = w.compression_ratio; sc[6] = w.kept ? 1.f : 0.f; }
     }
     *n_windows = (int)log.size();
@@ -797,6 +798,129 @@ AX_WHISPER_API int AX_WHISPER_RunFileLongFallback(AX_WHISPER_HANDLE handle, cons
   if (!load_wav_for_run(handle, wav_file, wav)) return -1;
   return AX_WHISPER_RunPCMLongFallback(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
                                        compression_ratio_threshold, temperatures, n_temperatures, seed, result);
+}
+
+// ---- prompt conditioning (DESIGN.md "Prompt conditioning")
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampPrompted(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                           int batch, int max_new, const int* max_new_clip, const int32_t* prompt_ids,
+                                                           int prompt_stride, const int* n_prompt, int32_t* ids, int* n_ids,
+                                                           float* token_logprob, float* avg_logprob, float* no_speech_logprob,
+                                                           int* ended_eot) {
+  if (!handle || !pcm || !num_samples || !n_prompt || prompt_stride < 0 || (prompt_stride > 0 && !prompt_ids) || !ids || !n_ids || !token_logprob ||
+      !avg_logprob || !no_speech_logprob || !ended_eot || batch < 1)
+    return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
+    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
+    g.run_tokens_prompted(Engine::kDecodeScored, pcm, num_samples, batch, max_new, max_new_clip, prompts, g.primary().config().n_text_ctx, ids,
+                          n_ids, &scores);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_PrefillPrompts(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids, int prompt_stride,
+                                             const int* n_prompt, float* no_speech_logprob, float* sot_logits) {
+  if (!handle || !n_prompt || prompt_stride < 0 || (prompt_stride > 0 && !prompt_ids) || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.prefill_stage(batch, Engine::PromptSpec{prompt_ids, prompt_stride, n_prompt}, no_speech_logprob, sot_logits); });
+}
+
+AX_WHISPER_API int AX_WHISPER_GetSelfKV(AX_WHISPER_HANDLE handle, int slot, int n_rows, float* k_out, float* v_out) {
+  if (!handle || !k_out || !v_out) return -1;
+  return guarded(handle, [&](Engine& e) { e.get_self_kv(slot, n_rows, k_out, v_out); });
+}
+
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampPrompted(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids,
+                                                            int prompt_stride, const int* n_prompt, const int32_t* forced, int n_forced,
+                                                            float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob) {
+  if (!handle || !n_prompt || prompt_stride < 1 || !prompt_ids || (n_forced > 0 && !forced) || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) {
+    const Engine::ForcedScores scores{logprob, no_speech_logprob, nullptr};
+    e.decode_forced_prompted(Engine::kDecodeScored, batch, Engine::PromptSpec{prompt_ids, prompt_stride, n_prompt}, forced, n_forced, logits,
+                             chosen, &scores);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_CarryPrompt(const int32_t* all_ids, int n_all, int reset_since, const int32_t* window_ids, int n_window,
+                                          int timestamp_begin, int eot, int window_frames, int skipped, int condition_on_previous_text,
+                                          float temperature, int keep, int cap, int32_t* all_out, int* n_all_out, int* reset_since_out,
+                                          int* n_prompt_next) {
+  if (n_all < 0 || (n_all > 0 && !all_ids) || n_window < 0 || (n_window > 0 && !window_ids) || reset_since < 0 || reset_since > n_all ||
+      window_frames < 0 || keep < 0 || !all_out || !n_all_out || !reset_since_out || !n_prompt_next || cap < n_all + n_window)
+    return -1;
+  return guarded_host([&] {
+    axw::PromptCarry st;
+    st.all_ids.assign(all_ids, all_ids + n_all);
+    st.reset_since = reset_since;
+    axw::carry_prompt(st, window_ids, n_window, timestamp_begin, eot, window_frames, skipped != 0, condition_on_previous_text != 0, temperature);
+    std::copy(st.all_ids.begin(), st.all_ids.end(), all_out);
+    *n_all_out = (int)st.all_ids.size();
+    *reset_since_out = st.reset_since;
+    *n_prompt_next = std::min((int)st.all_ids.size() - st.reset_since, keep);
+    return 0;
+  });
+}
+
+// the options of the three prompted long-form calls; false: bad arguments
+static bool prompted_options(float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                             int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int prompt_stride, const int* n_initial,
+                             int n_files, int condition_on_previous_text, axw::LongScoreOptions& opts) {
+  if (n_temperatures < 0 || n_temperatures > 16 || (n_temperatures > 0 && !temperatures) || n_files < 1) return false;
+  opts.no_speech_threshold = no_speech_threshold; opts.logprob_threshold = logprob_threshold;
+  opts.compression_ratio_threshold = compression_ratio_threshold;
+  if (n_temperatures > 0) opts.temperatures.assign(temperatures, temperatures + n_temperatures);
+  opts.seed = seed;
+  opts.condition_on_previous_text = condition_on_previous_text != 0;
+  if (n_initial) {
+    if (prompt_stride < 0) return false;
+    opts.initial_prompt_ids.resize(n_files);
+    for (int f = 0; f < n_files; ++f) {
+      if (n_initial[f] < 0 || n_initial[f] > prompt_stride || (n_initial[f] > 0 && !initial_prompt_ids)) return false;
+      if (n_initial[f] > 0) opts.initial_prompt_ids[f].assign(initial_prompt_ids + (size_t)f * prompt_stride, initial_prompt_ids + (size_t)f * prompt_stride + n_initial[f]);
+    }
+  }
+  return true;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsPrompted(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
+                                                        int n_files, int max_new, int max_passes, float no_speech_threshold,
+                                                        float logprob_threshold, float compression_ratio_threshold,
+                                                        const float* temperatures, int n_temperatures, uint64_t seed, const int* file_ids,
+                                                        const int32_t* initial_prompt_ids, int prompt_stride, const int* n_initial,
+                                                        int condition_on_previous_text, int win_cap, int* win_info, int32_t* ids,
+                                                        float* win_score, int* win_prompt, int* n_windows) {
+  axw::LongScoreOptions opts{};
+  if (!prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids,
+                        prompt_stride, n_initial, n_files, condition_on_previous_text, opts))
+    return -1;
+  for (int f = 0; file_ids && f < n_files; ++f) {
+    if (file_ids[f] < 0 || file_ids[f] >= (1 << 27)) return -1;
+    opts.file_ids.push_back(file_ids[f]);
+  }
+  return long_windows(handle, "RunPCMLongWindowsPrompted", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids,
+                      win_score, n_windows, win_prompt);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongPrompted(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                                 float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                 int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
+                                                 int condition_on_previous_text, char** result) {
+  axw::LongScoreOptions opts{};
+  if (n_initial < 0 || !prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed,
+                                         initial_prompt_ids, n_initial, &n_initial, 1, condition_on_previous_text, opts))
+    return -1;
+  return long_text(handle, pcm_data, num_samples, &opts, result);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileLongPrompted(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
+                                                  float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                                  int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
+                                                  int condition_on_previous_text, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return AX_WHISPER_RunPCMLongPrompted(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
+                                       compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids, n_initial,
+                                       condition_on_previous_text, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {

@@ -458,6 +458,7 @@ struct AdvanceParams {
   int* argmax_dump;           // optional [B][n_forced+1]
   const h16* tok_emb; const float* pos; float* x; int d_model;  // fused embedding of the next step
   int n_prefix;               // prefix tokens fed before the first sampled step (sot[0 .. n_prefix)); 0 means 4
+  const int* base;            // optional device [B], forced mode: positions in front of the prefix (a prompted clip's L - 2); nullptr: none
 };
 void launch_advance(const AdvanceParams& p, hipStream_t s);
 
@@ -470,7 +471,8 @@ struct TsRulesParams {
   int n_prefix;
   const int* done;                   // device [batch] or nullptr: finished clips are skipped
   const int* out_ids; const int* n_out; int n_ctx;   // greedy history: [batch][n_ctx] ids, [batch] counts
-  const int* forced; int n_forced;   // teacher-forced history [batch][n_forced] (n = off - n_prefix + 1), or nullptr
+  const int* forced; int n_forced;   // teacher-forced history [batch][n_forced] (n = off - n_prefix + 1 - base), or nullptr
+  const int* base;                   // optional device [batch], forced mode: a prompted clip's L - 2; nullptr: none
   float* amax_val; int* amax_idx; int amax_stride;   // out: partial 0 of clip b at b * amax_stride
 };
 void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s);
@@ -542,6 +544,42 @@ void launch_beam_reorder(const BeamReorderParams& p, hipStream_t s);
 // Spreading clips 0 .. C-1 to groups of K: launch for the clips in DESCENDING order (clip i's destinations start at i * K >= i,
 // so sources not yet spread are never overwritten).
 void launch_beam_spread_cross(h16* k, h16* v, long layer_stride, long slot_elems, int n_layer, int src, int dst0, int n_dst, hipStream_t s);
+
+// ---- prompt prefill (decode_prefill.hip; DESIGN.md "Prompt conditioning"): the context rows [sot_prev, prompt, sot, language] of
+// every prompted clip in one pass. Rows of a clip are contiguous; per-row and per-clip tables live in device memory.
+// x[row] = tok_emb[ctx[row]] + pos[row_pos[row]], fp32 [rows][d]
+void launch_prefill_embed(const h16* tok_emb, const float* pos, const int* ctx, const int* row_pos, float* x, int rows, int d,
+                          hipStream_t s);
+// K and V columns of qkv (h16 [rows][3 d_model], the QKV GEMM's output) -> cache row row_pos[row] of slot row_slot[row]
+struct PrefillStoreParams {
+  const h16* qkv; int rows;
+  const int* row_pos; const int* row_slot;   // device [rows]
+  h16* k_cache; h16* v_cache;                // this layer, slot 0
+  long kv_slot_stride; int d_model; int n_ctx_pad;
+};
+void launch_prefill_cache_store(const PrefillStoreParams& p, hipStream_t s);
+// out[row0[c] + i] = softmax(q[row0[c] + i] . K^T / 8) V for i < len[c], per head, over the caches of slot[c]:
+// n_keys < 0: causal over the self cache (query i sees keys 0 .. i); else keys 0 .. n_keys - 1 of the cross cache
+struct PrefillAttnParams {
+  const h16* q; int ldq;                     // h16 rows, head h at columns [64 h, 64 h + 64)
+  const h16* k; const h16* v;                // this layer, slot 0: blocked K, row-major V
+  long kv_slot_stride; int keys_pad;         // elements per slot; allocated keys per head (a multiple of 64)
+  h16* out; int ldo;
+  const int* row0; const int* len; const int* slot;  // device [n_clips]
+  int n_clips, max_len, n_head, n_keys;
+};
+void launch_prefill_attention(const PrefillAttnParams& p, hipStream_t s);
+// out[c] = x[rows[c]], fp32 rows of d
+void launch_prefill_gather_rows(const float* x, const int* rows, float* out, int n, int d, hipStream_t s);
+// per prompted clip c, slot b = slot[c]: off[b] = len[c], tok[b] = transcribe, n_out[b] = 0, x[b] = tok_emb[transcribe] + pos[len[c]],
+// no_speech[b] = no_speech_clip[c] (both or neither null)
+struct PrefillHandoverParams {
+  const int* slot; const int* len; int n_clips;
+  int* off; int* tok; int* n_out; int transcribe;
+  const h16* tok_emb; const float* pos; float* x; int d_model;
+  float* no_speech; const float* no_speech_clip;
+};
+void launch_prefill_handover(const PrefillHandoverParams& p, hipStream_t s);
 
 // ---- persistent decode (decode_persistent.hip, decode_persistent2.hip): the whole greedy loop of one to three clips in ONE launch
 typedef unsigned long long u64;

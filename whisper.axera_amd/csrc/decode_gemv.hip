@@ -537,7 +537,7 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
     // no logit compared greater than -inf (all NaN / -inf: non-finite audio): std::max_element returns index 0
     // (Whisper.cpp:42-45); never let the "no candidate" index reach the embedding lookup below
     if ((unsigned)idx >= (unsigned)p.n_vocab) idx = 0;
-    const int gi = s - (n_pre - 1);
+    const int gi = s - (n_pre - 1) - (p.base ? p.base[b] : 0);  // teacher forcing under a prompt: the history starts behind the clip's context
     if (p.forced) {
       if (gi < p.n_forced) tok = p.forced[(long)b * p.n_forced + gi];
     } else {

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesParams p) {
   int n;
   if (p.forced) {
     seq = p.forced + (long)b * p.n_forced;
-    n = min(max(p.off[b] - (p.n_prefix - 1), 0), p.n_forced);
+    n = min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced);
   } else {
     seq = p.out_ids + (long)b * p.n_ctx;
     n = min(max(p.n_out[b], 0), p.n_ctx);
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesPara
   int n;
   if (p.forced) {
     seq = p.forced + (long)b * p.n_forced;
-    n = min(max(p.off[b] - (p.n_prefix - 1), 0), p.n_forced);
+    n = min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced);
   } else {
     seq = p.out_ids + (long)b * p.n_ctx;
     n = min(max(p.n_out[b], 0), p.n_ctx);
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesPar
   int n;
   if (p.forced) {
     seq = p.forced + (long)b * p.n_forced;
-    n = min(max(p.off[b] - (p.n_prefix - 1), 0), p.n_forced);
+    n = min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced);
   } else {
     seq = p.out_ids + (long)b * p.n_ctx;
     n = min(max(p.n_out[b], 0), p.n_ctx);

@@ -10,20 +10,6 @@ inline namespace AXW_NS {
 
 static int dtype_code(const std::string& d) { return d == "F32" ? 0 : d == "BF16" ? 1 : 2; }
 
-// host: the bits of one stored h16 value -> float (bfloat16: the upper half of the fp32 pattern; half: IEEE binary16)
-static float h16_bits_to_float(uint16_t bits) {
-#if AXW_F16
-  _Float16 h;
-  memcpy(&h, &bits, 2);
-  return (float)h;
-#else
-  const uint32_t u = (uint32_t)bits << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-#endif
-}
-
 // ------------------------------------------------------------------------------ construction
 Engine::Engine(const std::string& model_type, const std::string& model_path, const std::string& language, int device,
                int max_batch) {
@@ -131,6 +117,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
   cfg_.ints["persistent_qfold"] = d_qfold_ ? 1 : 0;
   cfg_.ints["vocab_resident_rows"] = vocab_resident_rows_;
   cfg_.ints["persistent_giveups"] = 0;
+  try { (void)prefill_route(); } catch (const std::exception&) {}  // "prefill": the route prompted calls take (a bad AX_WHISPER_PREFILL is reported by the first prompted call)
   {  // batched decode as clip-block GEMMs with LayerNorm prologue / residual epilogue (enqueue_decode_step_batched)
     const char* e = getenv("AX_WHISPER_BATCHED_LN");
     const int d = cfg_.n_text_state;
@@ -909,13 +896,28 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
   if (sample) { upload_sample(*sample, batch); spec.sample = own_sample_; }
   if (n_forced) HIP_CHECK(hipMemcpy(d_forced, forced, (size_t)batch * n_forced * 4, hipMemcpyHostToDevice));
   bool done = false;
+  if (prompt_ && !tsm) throw std::runtime_error("decode_forced_prompted: prompted decode exists in the timestamp modes only");
   if (batch == 1 && !tsm && persistent_usable()) {
     if (run_persistent(cfg_.n_text_ctx, d_forced, n_forced, d_logits, d_arg) >= 0) { done = true; persistent_succeeded(); }
     else persistent_gave_up();
   }
   if (!done) reset_decode_state(batch);
+  DeviceArray<int> d_base;
+  if (prompt_) {  // every clip's context is cached and `transcribe` about to be fed: the loop below starts at that step
+    std::vector<int> base(batch);
+    const int keep = cfg_.n_text_ctx / 2 - 1;
+    for (int b = 0; b < batch; ++b) {
+      if (prompt_->n_prompt[b] < 1) throw std::runtime_error("decode_forced_prompted: every clip needs a prompt");
+      base[b] = std::min(prompt_->n_prompt[b], keep) + 1;  // L - 2
+      if (base[b] + 3 + n_forced > cfg_.n_text_ctx) throw std::runtime_error("decode_forced_prompted: n_forced out of range");
+    }
+    prefill_prompts(batch, *prompt_, scored);
+    d_base = device_array<int>(batch);
+    HIP_CHECK(hipMemcpy(d_base, base.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
+    spec.base = d_base;
+  }
   if (!done) ensure_branch_streams(batch);
-  for (int st = 0; !done && st < n_prefix + n_forced; ++st) {
+  for (int st = prompt_ ? n_prefix - 1 : 0; !done && st < n_prefix + n_forced; ++st) {
     const int gi = st - (n_prefix - 1);
     float* lrow = (d_logits && gi >= 0) ? d_logits + (size_t)gi * nv : nullptr;
     enqueue_decode_step(spec, batch, cfg_.n_text_ctx, d_forced, n_forced, lrow, (long)rows * nv, d_arg);
@@ -928,7 +930,8 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
   }
   HIP_CHECK(hipStreamSynchronize(s));
   if (out.logprob) HIP_CHECK(hipMemcpy(out.logprob, b_lp, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
-  if (out.no_speech_logprob) HIP_CHECK(hipMemcpy(out.no_speech_logprob, b_nsp, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  // (under a prompt no step visits decode offset 0: the value is the hand-over's, in the engine's own array)
+  if (out.no_speech_logprob) HIP_CHECK(hipMemcpy(out.no_speech_logprob, prompt_ ? d_nospeech_ : b_nsp.get(), (size_t)batch * 4, hipMemcpyDeviceToHost));
   if (out.logits0) HIP_CHECK(hipMemcpy(out.logits0, b_l0, (size_t)batch * nv * 4, hipMemcpyDeviceToHost));
   if (logits) HIP_CHECK(hipMemcpy(logits, d_logits, (size_t)batch * rows * nv * 4, hipMemcpyDeviceToHost));
   if (argmax_ids) HIP_CHECK(hipMemcpy(argmax_ids, d_arg, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));

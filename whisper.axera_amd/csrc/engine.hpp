@@ -70,6 +70,14 @@ struct EngineMemory {
                                                                // flag the moment it finishes; the host reads it without any wait
   PinnedArray<int> h_admit_ring_;          // pinned [kAdmitRing][2][cap]
   DeviceArray<unsigned long long> d_stamp_;  // bench "attn_stamp"
+  // prompt prefill (engine_prefill.cpp): the pass's rows (residual stream fp32, activations h16, per-row tables) and per-clip
+  // arrays (gathered sot rows, no-speech values, tables), grown on first use under device_capture_mutex
+  struct PrefillScratch {
+    DeviceArray<float> x, xg, nsp, sot_logits;  // sot_logits [clips][ts_stride_]: the rows the no-speech values were taken from
+    DeviceArray<h16> ln, qkv, att, hid;
+    DeviceArray<int> row_tab, clip_tab;
+    int rows_cap = 0, clips_cap = 0;
+  } prefill_;
 };
 
 struct EngineGraphs {
@@ -121,6 +129,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
 
   void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
                   const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample = nullptr) override;
+  void run_tokens_prompted(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
+                           const PromptSpec& prompts, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample = nullptr) override;
   std::string detokenize(const int32_t* ids, int n) const override;
   std::string transcript(const int32_t* ids, int n) const override;
   bool has_t2s() const { return (bool)t2s_; }
@@ -129,6 +139,10 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void get_cross_kv(int slot, float* k_out, float* v_out) override;
   void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
                      const ForcedScores* scores, const SampleSpec* sample = nullptr) override;
+  void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) override;
+  void prefill_stage(int batch, const PromptSpec& prompts, float* no_speech_logprob, float* sot_logits) override;
+  void decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec& prompts, const int32_t* forced, int n_forced, float* logits,
+                              int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample = nullptr) override;
   void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
   void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
                        const SampleSpec* sample = nullptr) override;
@@ -188,6 +202,10 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     int mask = 15;
     TsScoreParams score_out{};  // kDecodeScored, kDecodeSampled: where the scored / sampled rules kernel writes
     TsSampleParams sample{};    // kDecodeSampled: what the sampled rules kernel draws with (the engine's own arrays)
+    // step-fed prompt route (engine_prefill.cpp; never captured): advance feeds forced[0 ..] from position 0 (a one-id prefix) and
+    // the logits launch is skipped (1) or dumps every row into d_ts_logits_ (2)
+    int feed = 0;
+    const int* base = nullptr;  // teacher-forced prompted decode: device [batch], the clips' L - 2 (AdvanceParams::base)
   };
   // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
   // the rules kernel; first_step: the first decode step whose row is computed
@@ -226,6 +244,20 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void long_windows_to_slots(const int* files, const int* seeks, int count, bool want_ref_layout);
   void long_release();
   int greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip = nullptr);
+  // prompt conditioning (engine_prefill.cpp). prompt_: the prompts of the call in progress (run_tokens_prompted,
+  // decode_forced_prompted), which greedy_loop / decode_forced hand to prefill_prompts after reset_decode_state
+  const PromptSpec* prompt_ = nullptr;
+  // no_speech_out / sot_logits_out (stage level; host [batch] / [batch][n_vocab], or null): the prompted slots' no-speech value and
+  // the raw logits row it was taken from; entries of unprompted slots are 0
+  void prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_speech, float* no_speech_out = nullptr, float* sot_logits_out = nullptr);
+  void prefill_pass(int rows, int n_clips, int max_len, bool want_no_speech);
+  void prefill_step_fed(int batch, const std::vector<int>& slot, const std::vector<int>& len, const std::vector<int>& ctx,
+                        const std::vector<int>& row0, bool want_no_speech);
+  void ensure_prefill_scratch(int rows, int clips);
+  int prefill_env_ = -1;           // the handle's route (AX_WHISPER_PREFILL; the step-fed route where the prefill kernels refuse the shape)
+  int prefill_force_ = -1;         // bench "prefill_pass" / "prefill_step": that route for the call in progress
+  int prefill_route();             // 0 the prefill pass, 1 the step-fed route (AX_WHISPER_PREFILL=step)
+  bool prefill_supported() const;  // the prefill kernels take this decoder shape
   // batch 1: the whole loop as one persistent launch (decode_persistent.hip); returns steps run, -1 if it gave up
   int run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot = 0, int max_new1 = -1, int max_new2 = -1);
   void fetch_ids(int batch, int32_t* ids, int* n_ids);
@@ -317,6 +349,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   float bench_encoder(int batch, int iters);
   float bench_frontend(int batch, int iters);
   float bench_frontend_long(int batch, int arg, int iters);
+  float bench_prefill(const std::string& what, int batch, int arg, int iters);
 };
 
 }  // inline namespace AXW_NS

@@ -71,6 +71,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "encoder") return bench_encoder(batch, iters);
   if (what == "frontend") return bench_frontend(batch, iters);
   if (what == "frontend_long") return bench_frontend_long(batch, arg, iters);
+  if (what == "prefill" || what == "prefill_pass" || what == "prefill_step") return bench_prefill(what, batch, arg, iters);
   throw std::runtime_error("bench: unknown target '" + what + "'");
 }
 
@@ -85,6 +86,29 @@ static float timed_ms(hipStream_t s, Fn&& run) {
   float ms = 0.f;
   HIP_CHECK(hipEventElapsedTime(&ms, a, b));
   return ms;
+}
+
+// prefill: reset + prefill_prompts (tables, route, no-speech row, hand-over) of `batch` slots, every one with a context of L = arg
+// positions, by the handle's route; prefill_pass / prefill_step: by that route whatever the handle's is (A/B on one handle).
+// The slots' cross K/V is whatever the last encoder pass left (zeros on a fresh handle): the work does not depend on it.
+float Engine::bench_prefill(const std::string& what, int batch, int arg, int iters) {
+  require_scored_vocab();
+  const int keep = cfg_.n_text_ctx / 2 - 1, P = std::max(1, std::min(arg - 3, keep));
+  std::vector<int32_t> ids((size_t)batch * P);
+  unsigned x = 12345u;
+  for (auto& v : ids) { x = x * 1664525u + 1013904223u; v = (int32_t)((x >> 8) % (unsigned)cfg_.eot); }
+  const std::vector<int> n_prompt(batch, P);
+  const PromptSpec ps{ids.data(), P, n_prompt.data()};
+  const ScopedSet<int> scope(prefill_force_, what == "prefill_pass" ? 0 : what == "prefill_step" ? 1 : -1);
+  hipStream_t s = stream();
+  reset_decode_state(batch);
+  prefill_prompts(batch, ps, true);  // warm: scratch, score arrays
+  return timed_ms(s, [&] {
+    for (int i = 0; i < iters; ++i) {
+      reset_decode_state(batch);
+      prefill_prompts(batch, ps, true);
+    }
+  });
 }
 
 // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;

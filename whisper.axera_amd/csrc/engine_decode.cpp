@@ -2,6 +2,8 @@
 // launches) — Whisper::run_decoder + the host loop of the reference (Whisper.cpp:207-222,290-346).
 #include "engine_impl.hpp"
 
+#include <climits>
+
 namespace axw {
 inline namespace AXW_NS {
 
@@ -115,6 +117,7 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
 // timestamp mode: the logits launch also runs at the step that fed `transcribe` and dumps every row for the rules kernel
 // (scored mode: from offset 0 on — the row of the step that fed sot is the no-speech row; the row of offset 1 is computed and ignored)
 Engine::LogitsDump Engine::logits_dump(const StepSpec& spec, float* d_logits, long logits_stride) const {
+  if (spec.feed) return {spec.feed == 2 ? d_ts_logits_ : nullptr, ts_stride_, spec.feed == 2 ? 0 : INT_MAX};
   if (spec.mode == kDecodePlain) return {d_logits, logits_stride, 3};
   return {d_ts_logits_, ts_stride_, spec.mode >= kDecodeScored ? 0 : 2};
 }
@@ -125,7 +128,8 @@ void Engine::enqueue_step_tail(const StepSpec& spec, int batch, int max_new, con
   if (rules && (spec.mask & 4)) enqueue_timestamp_rules(spec, batch, d_forced, n_forced, s);
   AdvanceParams a{};
   a.amax_val = d_amax_val_; a.amax_idx = d_amax_idx_; a.n_part = rules ? 1 : n_part; a.amax_stride = n_amax_part_;
-  a.n_prefix = rules ? 3 : 0;
+  a.n_prefix = spec.feed ? 1 : rules ? 3 : 0;
+  a.base = spec.base;
   a.state = d_state_; a.off = d_off_; a.tok = d_tok_; a.done = d_done_; a.n_out = d_nout_; a.out_ids = d_out_ids_; a.batch = batch;
   a.n_ctx = cfg_.n_text_ctx; a.eot = cfg_.eot; a.max_new = max_new; a.n_vocab = cfg_.n_vocab; a.max_new_clip = d_max_new_clip_; a.sot = d_sot_;
   a.forced = d_forced; a.n_forced = n_forced; a.argmax_dump = d_argmax;
@@ -568,6 +572,7 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
   }
   hipGraphExec_t g = step_graph(spec, batch, max_new);  // (a fresh multi-branch graph is probed with replays: before the state is set)
   reset_decode_state(batch, max_new_clip);
+  if (prompt_) prefill_prompts(batch, *prompt_, spec.mode >= kDecodeScored);  // prompted slots: context cached, `transcribe` next
   hipStream_t s = stream();
   const int total = std::min(Tc, 4 + max_new);
   const int kPoll = 8;  // steps between done-counter polls; at most 2*kPoll steps run past the last eot
@@ -685,7 +690,7 @@ void Engine::enqueue_timestamp_rules(const StepSpec& spec, int batch, const int*
   r.n_vocab = cfg_.n_vocab; r.eot = cfg_.eot; r.ts_begin = cfg_.no_timestamps + 1;
   r.off = d_off_; r.n_prefix = 3; r.done = d_forced ? nullptr : d_done_;
   r.out_ids = d_out_ids_; r.n_out = d_nout_; r.n_ctx = cfg_.n_text_ctx;
-  r.forced = d_forced; r.n_forced = n_forced;
+  r.forced = d_forced; r.n_forced = n_forced; r.base = spec.base;
   r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
   if (spec.mode == kDecodeSampled) launch_timestamp_rules_sampled(r, spec.score_out, spec.sample, s);  // + a draw at the clip's temperature
   else if (spec.mode == kDecodeScored) launch_timestamp_rules_scored(r, spec.score_out, s);  // + the decision's log-probability, the no-speech value at offset 0

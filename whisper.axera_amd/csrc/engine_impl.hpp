@@ -76,6 +76,31 @@ inline Event make_event(unsigned flags = hipEventDefault) {
   return Event(e);
 }
 
+// host: the bits of one stored h16 value -> float (bfloat16: the upper half of the fp32 pattern; half: IEEE binary16)
+inline float h16_bits_to_float(uint16_t bits) {
+#if AXW_F16
+  _Float16 h;
+  memcpy(&h, &bits, 2);
+  return (float)h;
+#else
+  const uint32_t u = (uint32_t)bits << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+#endif
+}
+
+// `slot` holds `value` until the guard leaves scope, then what it held before (a call's ambient argument: Engine::prompt_)
+template <class T> class ScopedSet {
+ public:
+  ScopedSet(T& slot, T value) : slot_(slot), old_(slot) { slot = value; }
+  ~ScopedSet() { slot_ = old_; }
+  ScopedSet(const ScopedSet&) = delete;
+ private:
+  T& slot_;
+  T old_;
+};
+
 // Launch-per-row-block form of the batched vocabulary projection (used where the register-resident form does not fit:
 // d_model 1280 beyond 48 clips): weight-row tiles of 16 rows per workgroup, two per wave (1 / 2 / 4 measured alike).
 static int logits_rt() { return 2; }

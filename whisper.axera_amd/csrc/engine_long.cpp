@@ -135,6 +135,8 @@ void Engine::compute_mel_window(const float* pcm, int n_samples, int seek, float
 // opts->temperatures non-empty: temperature fallback (DESIGN.md "Temperature fallback"). Sampled mode throughout; a pass entry is
 // (file, seek, attempt); a window that needs fallback and has attempts left does not advance, it is encoded and decoded again in
 // the next pass at the next temperature (one more log entry, kept = false on the one that failed).
+// opts->prompted(): prompt conditioning (DESIGN.md "Prompt conditioning"). Every file carries (all_ids, reset_since); a window's
+// prompt, the same for each of its attempts, goes to greedy_loop through prompt_, and carry_prompt runs after every kept window.
 void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                               const LongScoreOptions* opts, std::vector<LongWindow>& log) {
   if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
@@ -142,6 +144,9 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   require_timestamp_vocab();
   if (opts) require_scored_vocab();
   const bool fallback = opts && !opts->temperatures.empty();
+  const bool prompted = opts && opts->prompted();
+  if (prompted && !opts->initial_prompt_ids.empty() && (long)opts->initial_prompt_ids.size() < (long)opts->file_base + n_files)
+    throw std::runtime_error("long-form: fewer initial prompts than files");
   const int n_attempts = fallback ? (int)opts->temperatures.size() : 1;
   if (n_attempts > 16) throw std::runtime_error("long-form: at most 16 temperatures");
   if (fallback && !opts->file_ids.empty() && (long)opts->file_ids.size() < (long)opts->file_base + n_files)
@@ -167,6 +172,12 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   std::vector<int32_t> ids((size_t)S * Tc);
   std::vector<float> avg(S), nsp(S);
   std::vector<WindowSegment> segs;
+  // prompt conditioning: the carried text of every file; a window's prompt is the same for all of its attempts
+  const int keep = Tc / 2 - 1;
+  std::vector<PromptCarry> carry(prompted ? n_files : 0);
+  for (int f = 0; prompted && f < n_files && !opts->initial_prompt_ids.empty(); ++f) carry[f].all_ids = opts->initial_prompt_ids[(size_t)(opts->file_base + f)];
+  std::vector<int32_t> prompt_ids(prompted ? (size_t)S * keep : 0);
+  std::vector<int> n_prompt(prompted ? S : 0);
   int next_file = 0, steps = 0;
   for (int pass = 0; max_passes <= 0 || pass < max_passes; ++pass) {
     // finished files leave, the others move up, waiting files take the free places
@@ -191,7 +202,19 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
     }
     long_windows_to_slots(files.data(), seeks.data(), A, false);
     run_encoder(A);
-    steps += greedy_loop(spec, A, max_new, nullptr);
+    if (prompted) {
+      for (int i = 0; i < A; ++i) {
+        const PromptCarry& c = carry[files[i]];
+        const int n = std::min((int)c.all_ids.size() - c.reset_since, keep);
+        n_prompt[i] = n;
+        std::copy(c.all_ids.end() - n, c.all_ids.end(), prompt_ids.begin() + (size_t)i * keep);
+      }
+      const PromptSpec ps{prompt_ids.data(), keep, n_prompt.data()};
+      const ScopedSet<const PromptSpec*> scope(prompt_, &ps);
+      steps += greedy_loop(spec, A, max_new, nullptr);
+    } else {
+      steps += greedy_loop(spec, A, max_new, nullptr);
+    }
     fetch_ids(A, ids.data(), n_ids.data());
     if (opts) fetch_scores(A, n_ids.data(), nullptr, avg.data(), nsp.data(), nullptr);
     for (int i = 0; i < A; ++i) {
@@ -201,6 +224,7 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
       w.window_frames = std::min(kFramesOut, n_samples[f] / kHop - seeks[i]);
       const int n = std::max(0, std::min(n_ids[i], Tc));
       w.ids.assign(ids.begin() + (size_t)i * Tc, ids.begin() + (size_t)i * Tc + n);
+      if (prompted) w.n_prompt = n_prompt[i];
       if (opts) { w.no_speech_logprob = nsp[i]; w.avg_logprob = avg[i]; }
       if (fallback) {
         // the window's text: the raw bytes of its ids below eot, before the zh post-pass
@@ -231,6 +255,7 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
       }
       w.advance = w.skipped ? w.window_frames : split_window(w.ids.data(), n, T, E, w.window_frames, segs);
       seek[f] += w.advance;
+      if (prompted) carry_prompt(carry[f], w.ids.data(), n, T, E, w.window_frames, w.skipped, opts->condition_on_previous_text, fallback ? temps[i] : 0.f);
       log.push_back(std::move(w));
     }
   }

@@ -46,12 +46,19 @@ class IEngine {
   // forced: logprob [batch][n_forced+1] of each step's chosen id, no_speech_logprob [batch], logits0 [batch][n_vocab]: the raw row
   // of decode offset 0
   struct ForcedScores { float *logprob, *no_speech_logprob, *logits0; };
+  // prompt conditioning (DESIGN.md "Prompt conditioning"): n_prompt[b] ids of clip b at ids + b * stride (text ids below eot and
+  // timestamp ids; the last n_text_ctx / 2 - 1 are used), n_prompt[b] == 0: no prompt, the clip decodes as it does without this
+  struct PromptSpec { const int32_t* ids; int stride; const int* n_prompt; };
   // full path, host PCM or device PCM; ids [batch][n_text_ctx], n_ids [batch]
   // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new; scores: kDecodeScored and
   // kDecodeSampled only; sample: kDecodeSampled only (and required there)
   virtual void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
                           int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores,
                           const SampleSpec* sample = nullptr) = 0;
+  // run_tokens on host PCM in a timestamp mode, every clip conditioned on its prompt
+  virtual void run_tokens_prompted(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new,
+                                   const int* max_new_clip, const PromptSpec& prompts, int32_t* ids, int* n_ids, const ClipScores* scores,
+                                   const SampleSpec* sample = nullptr) = 0;
   virtual std::string detokenize(const int32_t* ids, int n) const = 0;
   // detokenize + the reference's zh post-pass (Traditional -> Simplified, Whisper.cpp:231-236) when its OpenCC data files were found
   virtual std::string transcript(const int32_t* ids, int n) const = 0;
@@ -59,6 +66,15 @@ class IEngine {
   virtual void compute_mel(const float* pcm, int n_samples, float* mel_out) = 0;
   virtual void encode_mel(const float* mel, int batch) = 0;
   virtual void get_cross_kv(int slot, float* k_out, float* v_out) = 0;
+  // the slot's self-attention cache rows [0, n_rows), de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][d]
+  virtual void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) = 0;
+  // after encode_mel: the decode state of slots [0, batch) as a prompted greedy loop finds it before its first step (reset, then the
+  // prompts' context cached and `transcribe` about to be fed); no_speech_logprob (or null): [batch], 0 for unprompted slots
+  // sot_logits (or null): [batch][n_vocab], the raw row the no-speech value of a prompted slot was taken from
+  virtual void prefill_stage(int batch, const PromptSpec& prompts, float* no_speech_logprob, float* sot_logits) = 0;
+  // decode_forced in a timestamp mode under prompts: the forced ids follow each clip's own context
+  virtual void decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec& prompts, const int32_t* forced, int n_forced, float* logits,
+                                      int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample = nullptr) = 0;
   // timestamp, scored and sampled mode: logits are the raw logits (before the rules), chosen the ids the rules choose; scores:
   // kDecodeScored and kDecodeSampled only; sample: kDecodeSampled only (and required there)
   virtual void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,

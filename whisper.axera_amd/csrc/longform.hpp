@@ -1,7 +1,7 @@
 // longform.hpp — long-form transcription, host side (no HIP types): the window rule and the log entry of one decoded window.
 //
-// Whisper's answer to audio longer than its 30 s window is a loop (openai-whisper transcribe(), here without its temperature /
-// no-speech / prompt parts): decode the window at `seek` in timestamp mode, cut it at the last complete segment, move the
+// Whisper's answer to audio longer than its 30 s window is a loop (openai-whisper transcribe(); its temperature, no-speech and
+// prompt parts are the options further down): decode the window at `seek` in timestamp mode, cut it at the last complete segment, move the
 // window's start there. split_window is the cut: one window's ids -> segments + the frames to advance by (DESIGN.md
 // "Long-form"). The single-clip split (AX_WHISPER_SplitSegments) keeps a trailing piece and is a different contract.
 #pragma once
@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -27,15 +28,22 @@ struct WindowSegment {
 //   at the last closed pair (that audio is decoded again), unless the ids end in a single timestamp (then the window is used up);
 //   without cuts: one segment over the whole window.
 //   Progress guard (not in openai-whisper, where a pair closing at 0.00 s loops for ever): advance <= 0 becomes window_frames.
-inline int split_window(const int32_t* ids, int n, int T, int E, int window_frames, std::vector<WindowSegment>& segs) {
+// ranges (optional): for every emitted segment the ids it spans, [lo, hi) from its opening timestamp to its closing one — what the
+// previous-text carry appends (carry_prompt below).
+inline int split_window(const int32_t* ids, int n, int T, int E, int window_frames, std::vector<WindowSegment>& segs,
+                        std::vector<std::pair<int, int>>* ranges = nullptr) {
   segs.clear();
+  if (ranges) ranges->clear();
   auto ts = [&](int i) { return ids[i] >= T; };
   auto time = [&](int i) { return (float)((double)(ids[i] - T) * 0.02); };  // the double product, rounded once
   auto emit = [&](int lo, int hi, float t0, float t1) {
     int tb = -1, te = -1;
     for (int i = lo; i < hi; ++i)
       if (ids[i] < E) { if (tb < 0) tb = i; te = i + 1; }
-    if (tb >= 0) segs.push_back({t0, t1, tb, te});  // a segment without text is not emitted
+    if (tb >= 0) {  // a segment without text is not emitted
+      segs.push_back({t0, t1, tb, te});
+      if (ranges) ranges->push_back({lo, hi});
+    }
   };
   std::vector<int> bounds;
   for (int i = 1; i < n; ++i)
@@ -112,6 +120,27 @@ inline float compression_ratio(const unsigned char* bytes, size_t n) {
   return (float)((double)n / (double)len);
 }
 
+// Prompt conditioning across windows (DESIGN.md "Prompt conditioning"; openai-whisper transcribe(): all_tokens / prompt_reset_since),
+// per file. A window's prompt is all_ids[reset_since:], of which the decoder takes the last n_text_ctx / 2 - 1.
+struct PromptCarry {
+  std::vector<int32_t> all_ids;  // starts as the file's initial prompt ids
+  int reset_since = 0;
+};
+// One step of the carry rule, after a KEPT window (ids: all of them, eot excluded): unless the window was skipped as silent, append
+// the ids of its emitted segments, timestamps included (ids after the last closed pair are dropped as split_window drops them;
+// segments without text add nothing); then, if conditioning is off or the kept attempt's temperature is above 0.5, the next prompt
+// starts behind everything so far.
+inline void carry_prompt(PromptCarry& st, const int32_t* ids, int n, int T, int E, int window_frames, bool skipped, bool condition_on_previous_text,
+                         float temperature) {
+  if (!skipped) {
+    std::vector<WindowSegment> segs;
+    std::vector<std::pair<int, int>> ranges;
+    split_window(ids, n, T, E, window_frames, segs, &ranges);
+    for (const auto& r : ranges) st.all_ids.insert(st.all_ids.end(), ids + r.first, ids + r.second);
+  }
+  if (!condition_on_previous_text || temperature > 0.5f) st.reset_since = (int)st.all_ids.size();
+}
+
 // scored long-form: thresholds of the silent-window rule (NaN no_speech_threshold: the rule is off, scores are still fetched)
 // With `temperatures` non-empty the call is the fallback loop: sampled decode mode throughout, attempt a of a window at
 // temperatures[a] (at most 16 attempts), a window that needs fallback is decoded again in the next pass. (openai-whisper's list
@@ -127,6 +156,16 @@ struct LongScoreOptions {
   // in the whole call.
   std::vector<int> file_ids;
   int file_id(int local_file) const { return file_ids.empty() ? file_base + local_file : file_ids[(size_t)(file_base + local_file)]; }
+  // Prompt conditioning (DESIGN.md "Prompt conditioning"): initial_prompt_ids (empty, or one list per file of the WHOLE call) start each
+  // file's carried text; condition_on_previous_text: every window is prompted with the text kept before it. Both off: the loop as it was.
+  std::vector<std::vector<int32_t>> initial_prompt_ids;
+  bool condition_on_previous_text = false;
+  bool prompted() const {
+    if (condition_on_previous_text) return true;
+    for (const auto& p : initial_prompt_ids)
+      if (!p.empty()) return true;
+    return false;
+  }
 };
 
 // one decoded window of AX_WHISPER_RunPCMLongWindows, in execution order
@@ -140,6 +179,7 @@ struct LongWindow {
   int attempt = 0;
   float temperature = 0.f, compression_ratio = 0.f;
   bool kept = true;
+  int n_prompt = 0;  // prompted calls only: ids the window was conditioned on (after the truncation to n_text_ctx / 2 - 1)
 };
 
 }  // namespace axw

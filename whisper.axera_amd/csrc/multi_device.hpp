@@ -107,6 +107,32 @@ class DeviceGroup {
     });
   }
 
+  // run_tokens under prompts (E::run_tokens_prompted; P = E::PromptSpec {ids [batch][stride], stride, n_prompt [batch]}): the prompts
+  // travel with their clips.
+  template <typename P, typename S = std::nullptr_t>
+  void run_tokens_prompted(typename E::DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new,
+                           const int* max_new_clip, const P& prompts, int n_ctx, int32_t* ids, int* n_ids, const typename E::ClipScores* scores,
+                           const S* sample = nullptr) {
+    if (batch < 1) throw std::runtime_error("batch must be >= 1");
+    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
+    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
+      typename E::ClipScores sc{};
+      if (scores)
+        sc = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
+              from(scores->ended_eot, lo)};
+      const P pr{from(prompts.ids, (size_t)lo * prompts.stride), prompts.stride, from(prompts.n_prompt, lo)};
+      if constexpr (std::is_same<S, std::nullptr_t>::value) {
+        e.run_tokens_prompted(mode, pcm + lo, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), pr, ids + (size_t)lo * n_ctx, n_ids + lo,
+                              scores ? &sc : nullptr);
+      } else {
+        S sm{};
+        if (sample) sm = S{from(sample->temperature, lo), from(sample->stream, lo), sample->seed};
+        e.run_tokens_prompted(mode, pcm + lo, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), pr, ids + (size_t)lo * n_ctx, n_ids + lo,
+                              scores ? &sc : nullptr, sample ? &sm : nullptr);
+      }
+    });
+  }
+
   // Beam search (E::run_beam; R: the result arrays of beam.hpp, all per-clip with row stride n_ctx where they are rows): the clips
   // are split like run_tokens' — every hypothesis of a clip lives on the clip's device.
   template <typename R>

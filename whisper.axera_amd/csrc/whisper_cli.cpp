@@ -38,6 +38,9 @@ static void usage(const char* prog) {
           "                      (a repetition loop), or whose average log-probability is below Y, is decoded again with sampling\n"
           "                      at temperatures 0.2, 0.4, .. 1.0 until one attempt passes (openai-whisper uses 2.4)\n"
           "      --temperature_increment D, --seed N   the step between those temperatures [=0.2], the seed of the draws [=0]\n"
+          "      --condition_on_previous_text   (with --long) every window is prompted with the text kept before it (openai-whisper's\n"
+          "                      default); a window kept at a temperature above 0.5 starts the prompt afresh\n"
+          "      --prompt_ids 1,2,3   (with --long) the file's initial prompt, as token ids (there is no text encoder here)\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -132,9 +135,10 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size) {
 // scored: under the silent-window rule (AX_WHISPER_RunPCMLongWindowsScored); skipped windows print nothing, the other lines end
 // in their window's two numbers
 // temps non-empty: with temperature fallback (AX_WHISPER_RunPCMLongWindowsFallback): only kept attempts print
+// prompted: under prompt conditioning (AX_WHISPER_RunPCMLongWindowsPrompted; always scored)
 static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_speech_threshold, float logprob_threshold,
-                    float compression_ratio_threshold, const std::vector<float>& temps, unsigned long long seed, std::string& text,
-                    std::string& lines) {
+                    float compression_ratio_threshold, const std::vector<float>& temps, unsigned long long seed, bool prompted,
+                    const std::vector<int32_t>& prompt_ids, bool condition, std::string& text, std::string& lines) {
   const bool fallback = !temps.empty();
   const size_t sw = fallback ? 7 : 3;  // floats per window score row
   float* pcm = nullptr;
@@ -148,7 +152,12 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
   std::vector<float> score(scored ? (size_t)cap * sw : 0);
   int n_win = 0;
   const float* files[1] = {pcm};
-  const int rc = fallback ? AX_WHISPER_RunPCMLongWindowsFallback(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
+  const int n_initial = (int)prompt_ids.size();
+  const int rc = prompted ? AX_WHISPER_RunPCMLongWindowsPrompted(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
+                                                                 compression_ratio_threshold, fallback ? temps.data() : nullptr, (int)temps.size(),
+                                                                 seed, nullptr, prompt_ids.data(), n_initial, &n_initial, condition ? 1 : 0, cap,
+                                                                 info.data(), ids.data(), score.data(), nullptr, &n_win)
+                 : fallback ? AX_WHISPER_RunPCMLongWindowsFallback(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
                                                                  compression_ratio_threshold, temps.data(), (int)temps.size(), seed, nullptr, cap,
                                                                  info.data(), ids.data(), score.data(), &n_win)
                  : scored ? AX_WHISPER_RunPCMLongWindowsScored(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold, cap, info.data(),
@@ -186,7 +195,8 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
   bool timestamps = false, longform = false;
-  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg;
+  bool condition = false;
+  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -202,11 +212,12 @@ int main(int argc, char** argv) {
     if (val("wav", "-w", wav) || val("model_type", "-t", model_type) || val("model_path", "-p", model_path) ||
         val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg) ||
         val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg) ||
-        val("beam_size", nullptr, beam_arg))
+        val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
     if (a == "--long") { longform = true; continue; }
+    if (a == "--condition_on_previous_text") { condition = true; continue; }
     fprintf(stderr, "undefined option: %s\n", a.c_str());
     usage(argv[0]);
     return 1;
@@ -224,7 +235,17 @@ int main(int argc, char** argv) {
   const bool fallback = !crt_arg.empty();
   if ((!tinc_arg.empty() || !seed_arg.empty()) && !fallback) { fprintf(stderr, "--temperature_increment / --seed need --compression_ratio_threshold\n"); usage(argv[0]); return 1; }
   if (fallback && !longform) { fprintf(stderr, "--compression_ratio_threshold needs --long\n"); usage(argv[0]); return 1; }
-  const bool scored = fallback || !nst_arg.empty() || !lpt_arg.empty();
+  std::vector<int32_t> prompt_ids;
+  for (size_t p = 0; p < prompt_arg.size();) {
+    char* end = nullptr;
+    const long v = strtol(prompt_arg.c_str() + p, &end, 10);
+    if (end == prompt_arg.c_str() + p || v < 0 || (*end && *end != ',')) { fprintf(stderr, "bad value: --prompt_ids %s\n", prompt_arg.c_str()); return 1; }
+    prompt_ids.push_back((int32_t)v);
+    p = (size_t)(end - prompt_arg.c_str()) + (*end ? 1 : 0);
+  }
+  const bool prompted = condition || !prompt_ids.empty();
+  if (prompted && !longform) { fprintf(stderr, "--condition_on_previous_text / --prompt_ids need --long\n"); usage(argv[0]); return 1; }
+  const bool scored = prompted || fallback || !nst_arg.empty() || !lpt_arg.empty();
   if (scored && !longform) { fprintf(stderr, "--no_speech_threshold / --logprob_threshold need --long\n"); usage(argv[0]); return 1; }
   // one flag alone: no threshold on the average = no-speech alone decides (+inf); no threshold on no-speech = nothing is skipped
   // (NaN; as in openai-whisper, where the average only ever overrides a no-speech verdict) and the lines just carry their numbers
@@ -269,7 +290,8 @@ int main(int argc, char** argv) {
   if (longform) {
     t0 = std::chrono::steady_clock::now();
     std::string text, lines;
-    if (run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, text, lines) != 0) {
+    if (run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompted, prompt_ids, condition,
+                 text, lines) != 0) {
       printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
       AX_WHISPER_Uninit(handle);
       return -1;
