@@ -33,6 +33,8 @@ if __name__ == "__main__":
 
 # (query fold, round 5: "P cq gathered" = a cross-attention unit has its query (T + statistics gathered), "C cq published" = a row
 # producer has published y1 / T / statistics; "P cq ln done" and "C cq rows start" do not exist there)
+# (merge inside the gather, round 9: the compute waves gather and merge the cross-attention records in one step, so the pollers stamp
+# "P co gathered" and "P co merged" at the same moment, behind the stage's one barrier; `P co.gather` holds the whole wait, `P co.merge` ~ 0)
 TL = ["P qkv gathered", "P qkv ln done", "P o gathered", "P cq gathered", "P cq ln done", "P co gathered", "P co merged",
       "P fc1 gathered", "P fc1 ln done", "P fc2 gathered",
       "C qkv published", "C sa published", "C o published", "C cq published", "C ca published", "C co published",

@@ -36,6 +36,29 @@ AXW_LAYOUT_FN int v_index(int key, int dim) { return v_row_offset(key) + dim; }
 // transposed V of the persistent launches' own self-attention cache: [key / 64][(key % 64) / 8][dim][8 keys]
 AXW_LAYOUT_FN int vt_index(int key, int dim) { return kv_chunk_offset(key >> 6, (key >> 3) & 7, dim) + (key & 7); }
 
+// ------------------------------------------------------------------ the persistent launches' LDS image of a cross V block
+// A row-major [64 keys][64 dims] block whose eight 16-byte chunks are permuted inside every 128-byte row: LDS slot (row R, chunk c)
+// holds the block's chunk c ^ x(R), x(R) = 2 (2 (R / 8 % 2) + R / 2 % 2). The matrix-pipe block reads the tile with transposed
+// 8-byte reads (ds_read_b64_tr_b16: per 32-lane half, rows q, q + 1, q + 2, q + 3 of two 4-row blocks eight rows apart, four
+// 8-byte columns each); on plain 128-byte rows, rows R and R + 2 and the two blocks share eight of the 64 banks, a 4-way conflict.
+// x moves rows R + 2 by two chunks (16 banks) and rows R + 8 by four (32 banks): every read of the block is conflict-free
+// (tests/test_cross_v_swizzle_layout.py counts it). A permutation inside a row: no LDS, no HBM byte and no memory line more.
+AXW_LAYOUT_FN int cross_v_swizzle(int row) { return 2 * (2 * ((row >> 3) & 1) + ((row >> 1) & 1)); }
+// element of (key, dim) in the swizzled block (swz) or the plain row-major one
+AXW_LAYOUT_FN int cross_v_index(int key, int dim, bool swz) {
+  return swz ? v_row_offset(key) + (((dim >> 3) ^ cross_v_swizzle(key)) << 3) + (dim & 7) : v_index(key, dim);
+}
+// staging: which of the block's 512 sixteen-byte pieces (row-major order, piece = 8 row + chunk) LDS piece `slot` receives
+AXW_LAYOUT_FN int cross_v_source_piece(int slot, bool swz) { return swz ? slot ^ cross_v_swizzle(slot >> 3) : slot; }
+// The address (element offset in the block) lane `lane` supplies to transposed read `half` (keys + 0..3 / + 4..7) of B piece (dim
+// block nb, k-step ks) of the output product: key 32 ks + 8 (lane / 16) + lane / 4 % 4 + 4 half, dims 16 nb + 4 (lane % 4) .. + 3.
+// x does not depend on ks, half or nb, so a lane keeps ONE base and a piece is base ^ 16 nb (+ 16 nb in the plain image) plus a
+// constant row offset.
+AXW_LAYOUT_FN int cross_v_read_base(int lane, bool swz) { return cross_v_index(8 * (lane >> 4) + ((lane >> 2) & 3), 4 * (lane & 3), swz); }
+AXW_LAYOUT_FN int cross_v_read_offset(int base, int nb, int ks, int half, bool swz) {
+  return (swz ? base ^ (16 * nb) : base + 16 * nb) + v_row_offset(32 * ks + 4 * half);
+}
+
 // ------------------------------------------------------------------ fragment-major MFMA operands (v_mfma_f32_16x16x32)
 // A tile is 16 rows x 32 k = 512 elements in the order the instruction consumes them, so an operand load of a wave is ONE
 // contiguous 1 KiB access (lane * 16 bytes): element (lane, j) of a tile = [row & 15 = lane & 15][k & 31 = (lane >> 4) * 8 + j].

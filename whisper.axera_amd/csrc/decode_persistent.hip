@@ -332,29 +332,46 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         }
         // ---- cross-attention output projection: merge the partials of every head
         if (in_o) {
-          // the pollers collect the first NP1 granules of the partial records, the (idle) compute waves the rest
-          unsigned y[2 * GP1];  // pair pi of the records: record pi / 33, granules 2 * (pi % 33), +1
-          const bool fail = gather2<GP1>(GR, tag, y, p.err, ctl, [&](int j) { const int pi = tid + j * PL; return pi < NPP1 ? O_PART + (pi / (kPS / 2)) * kRec + 2 * (pi % (kPS / 2)) : -1; });
-          float* pbuf = act + D;  // [H][kCrossSplit][66]
+          if constexpr (kCoMergeInGather && QF) {
+            // Merge inside the gather (co_gather_merge): the compute waves poll the records, merge in registers and write
+            // act[0..D) BEFORE the stage's one barrier; the pollers only meet them there. That write is safe with the query fold:
+            // a cross-attention unit needs the statistics line of EVERY row producer for its query, and a producer publishes that
+            // line through its compute wave that arrives LAST, behind all its waves' reads of act[0..D) (W_o's rows and the rows
+            // of M) — so every read of act by this workgroup lies causally behind any record a lane can have gathered. Not so
+            // without the fold: a head's query rows come from four producers only, so the unfolded launch keeps the LDS form,
+            // whose writes in front of the barrier go to pbuf. A lane that gives up sets ctl[0] before the check barrier: a
+            // merge of unfinished data is discarded there. Stamps 9 / 10 and timeline points 5 / 6 behind the barrier: for the
+            // pollers the records are gathered and merged at the same moment.
+            AXW_BARRIER_CHECK(0x600 + l)
+            AXW_STAMP(9)
+            AXW_TL(5)
+            AXW_STAMP(10)
+            AXW_TL(6)
+          } else {
+            // the pollers collect the first NP1 granules of the partial records, the (idle) compute waves the rest
+            unsigned y[2 * GP1];  // pair pi of the records: record pi / 33, granules 2 * (pi % 33), +1
+            const bool fail = gather2<GP1>(GR, tag, y, p.err, ctl, [&](int j) { const int pi = tid + j * PL; return pi < NPP1 ? O_PART + (pi / (kPS / 2)) * kRec + 2 * (pi % (kPS / 2)) : -1; });
+            float* pbuf = act + D;  // [H][kCrossSplit][66]
 #pragma unroll
-          for (int j = 0; j < GP1; ++j) {
-            const int pi = tid + j * PL;
-            if (pi < NPP1) { pbuf[2 * pi] = __uint_as_float(y[2 * j]); pbuf[2 * pi + 1] = __uint_as_float(y[2 * j + 1]); }
-          }
-          if (fail) ctl[0] = 1;
-          AXW_STAMP(9)
-          AXW_TL(5)
-          AXW_BARRIER_CHECK(0x600 + l)
-#pragma unroll
-          for (int k = 0; k < GD; ++k) {
-            const int i = tid + k * PL;
-            if (i < D) {
-              act[i] = merge_cross_records(pbuf, i);
+            for (int j = 0; j < GP1; ++j) {
+              const int pi = tid + j * PL;
+              if (pi < NPP1) { pbuf[2 * pi] = __uint_as_float(y[2 * j]); pbuf[2 * pi + 1] = __uint_as_float(y[2 * j + 1]); }
             }
+            if (fail) ctl[0] = 1;
+            AXW_STAMP(9)
+            AXW_TL(5)
+            AXW_BARRIER_CHECK(0x600 + l)
+#pragma unroll
+            for (int k = 0; k < GD; ++k) {
+              const int i = tid + k * PL;
+              if (i < D) {
+                act[i] = merge_cross_records(pbuf, i);
+              }
+            }
+            wg_barrier();
+            AXW_STAMP(10)
+            AXW_TL(6)
           }
-          wg_barrier();
-          AXW_STAMP(10)
-          AXW_TL(6)
         }
         // ---- mlp.0
         if constexpr (QF) {  // x += y1, then += y2: the unfolded launch's order of additions
@@ -531,10 +548,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
       if (cu0 >= 0) {
         const int lane = ctid & 63, cw = __builtin_amdgcn_readfirstlane(ctid >> 6);
         const long off = (cu0 / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset((cu0 % kCrossSplit) * NCW + cw, 0, 0);
-        for (int i = 0; i < 8; ++i) {
-          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_k + off + layout::kv_chunk_offset(0, i, lane)), (lds_ptr_t)(sK + layout::kv_chunk_offset(cw, i, 0)), 16, 0, kKvAux);
-          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_v + off + layout::kv_chunk_offset(0, i, lane)), (lds_ptr_t)(sV + layout::kv_chunk_offset(cw, i, 0)), 16, 0, kKvAux);
-        }
+        stage_cross_kv(p.cross_k + off, p.cross_v + off, sK + layout::kv_chunk_offset(cw, 0, 0), sV + layout::kv_chunk_offset(cw, 0, 0), 0, 16, lane);
       }
     }
 
@@ -561,11 +575,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           if (cun < 0) return;
           const int kb = (cun % kCrossSplit) * NCW + cw;  // 64-key block of this wave (24 blocks = t_pad 1536)
           const long off = (long)ln * p.cross_layer_stride + (cun / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset(kb, 0, 0);
-          for (int i = i0; i < i1; ++i) {
-            const h16* src = (i < 8 ? p.cross_k : p.cross_v) + off + layout::kv_chunk_offset(0, i & 7, lane);
-            h16* dst = (i < 8 ? sK : sV) + layout::kv_chunk_offset(cw, i & 7, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)dst, 16, 0, kKvAux);
-          }
+          stage_cross_kv(p.cross_k + off, p.cross_v + off, sK + layout::kv_chunk_offset(cw, 0, 0), sV + layout::kv_chunk_offset(cw, 0, 0), i0, i1, lane);
         };
         // ---- QKV rows (export_onnx.py:245-247)
         AXW_BARRIER_CHECK(0x100 + l)
@@ -683,19 +693,25 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         }
         // ---- cross-attention output projection
         if (in_o) {
-          {
-            unsigned y[2 * GP2];
-            const bool fail = gather2<GP2>(GR, tag, y, p.err, ctl, [&](int j) { const int pi = NPP1 + ctid + j * CT; return pi < NPP ? O_PART + (pi / (kPS / 2)) * kRec + 2 * (pi % (kPS / 2)) : -1; });
-            float* pbuf = act + D;
-#pragma unroll
-            for (int j = 0; j < GP2; ++j) {
-              const int pi = NPP1 + ctid + j * CT;
-              if (pi < NPP) { pbuf[2 * pi] = __uint_as_float(y[2 * j]); pbuf[2 * pi + 1] = __uint_as_float(y[2 * j + 1]); }
-            }
+          if constexpr (kCoMergeInGather && QF) {  // the merge tasks (see the pollers), one barrier
+            const bool fail = co_gather_merge<D>(GR, tag, O_PART, ctid, act, p.err, ctl);
             if (fail) ctl[0] = 1;
+            AXW_BARRIER_CHECK(0x600 + l)
+          } else {
+            {
+              unsigned y[2 * GP2];
+              const bool fail = gather2<GP2>(GR, tag, y, p.err, ctl, [&](int j) { const int pi = NPP1 + ctid + j * CT; return pi < NPP ? O_PART + (pi / (kPS / 2)) * kRec + 2 * (pi % (kPS / 2)) : -1; });
+              float* pbuf = act + D;
+#pragma unroll
+              for (int j = 0; j < GP2; ++j) {
+                const int pi = NPP1 + ctid + j * CT;
+                if (pi < NPP) { pbuf[2 * pi] = __uint_as_float(y[2 * j]); pbuf[2 * pi + 1] = __uint_as_float(y[2 * j + 1]); }
+              }
+              if (fail) ctl[0] = 1;
+            }
+            AXW_BARRIER_CHECK(0x600 + l)
+            wg_barrier();
           }
-          AXW_BARRIER_CHECK(0x600 + l)
-          wg_barrier();
           AXW_STAMP(24)
           AXW_TL(21)
           rb.run(w_co, b_co, D, act, ctid, res);

@@ -506,8 +506,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         const int lane = ctid & 63, cw = __builtin_amdgcn_readfirstlane(ctid >> 6);
         const int u0 = cu0 % NU;
         const long off = (long)(cu0 / NU) * p.cross_clip_stride + (u0 / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset((u0 % kCrossSplit) * NCW + cw, 0, 0);
-        for (int i = 0; i < 8; ++i)
-          __builtin_amdgcn_global_load_lds((gptr_t)(p.cross_k + off + layout::kv_chunk_offset(0, i, lane)), (lds_ptr_t)(sK + layout::kv_chunk_offset(cw, i, 0)), 16, 0, kKvAux);
+        stage_cross_kv(p.cross_k + off, p.cross_v + off, sK + layout::kv_chunk_offset(cw, 0, 0), sV + layout::kv_chunk_offset(cw, 0, 0), 0, 8, lane);
       }
     }
 
@@ -538,11 +537,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           const int uu = un % NU;
           const int kb = (uu % kCrossSplit) * NCW + cw;  // 64-key block of this wave (24 blocks = t_pad 1536)
           const long off = (long)(un / NU) * p.cross_clip_stride + (long)lay * p.cross_layer_stride + (uu / kCrossSplit) * layout::kv_head_elems(kCrossKeysPad) + layout::kv_chunk_offset(kb, 0, 0);
-          for (int i = i0; i < i1; ++i) {
-            const h16* src = (i < 8 ? p.cross_k : p.cross_v) + off + layout::kv_chunk_offset(0, i & 7, lane);
-            h16* dst = (i < 8 ? sK : sV) + layout::kv_chunk_offset(cw, i & 7, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)dst, 16, 0, kKvAux);
-          }
+          stage_cross_kv(p.cross_k + off, p.cross_v + off, sK + layout::kv_chunk_offset(cw, 0, 0), sV + layout::kv_chunk_offset(cw, 0, 0), i0, i1, lane);
         };
         // ---- QKV rows (export_onnx.py:245-247)
         float res[2];

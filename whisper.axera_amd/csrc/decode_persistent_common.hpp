@@ -42,8 +42,22 @@ constexpr int CT = NCW * 64;       // compute threads
 #ifndef AXW_ATTN_MFMA
 #define AXW_ATTN_MFMA 1
 #endif
+// The cross V tile in LDS with the 16-byte chunks of its rows permuted (1, layout::cross_v_swizzle: the transposed reads of the
+// matrix-pipe block are then free of bank conflicts) or plain row-major as in HBM (0, the form of round 8, kept for the A/B:
+// profiles/cross_segment_ab.txt)
+#ifndef AXW_CROSS_V_SWIZZLE
+#define AXW_CROSS_V_SWIZZLE 1
+#endif
+// The one-clip launch's merge of the cross-attention records: in registers by the lanes that gathered them, one workgroup barrier
+// (1; only with the query fold, see decode_persistent.hip), or through LDS behind a barrier of its own (0, the form of rounds 5-8,
+// which the multi-clip launch and the unfolded one-clip launch keep)
+#ifndef AXW_CO_MERGE_IN_GATHER
+#define AXW_CO_MERGE_IN_GATHER 1
+#endif
 constexpr bool kVocabNT = AXW_VOCAB_NT != 0;
 constexpr bool kAttnMfma = AXW_ATTN_MFMA != 0;
+constexpr bool kCrossVSwizzle = AXW_CROSS_V_SWIZZLE != 0;
+constexpr bool kCoMergeInGather = AXW_CO_MERGE_IN_GATHER != 0;
 constexpr int kKvAux = AXW_KV_NT_LDS ? 2 : 0;  // aux bits of global_load_lds: 2 = nt
 constexpr int kSpinFree = 1024;
 constexpr long long kSpinTicks = 5000000;
@@ -339,9 +353,11 @@ __device__ __forceinline__ u32x4 kv_global16(const h16* base, int off) {
 //      cross tile [64 keys][64 dims] (LDS-DMA in the HBM layout) two ds_read_b64_tr_b16 of keys 32 ks + 8 (l / 16) + {0..3},
 //      {4..7}, dims 16 nb .. + 15. Lane group g takes oc[g][0] + oc[g][1] = o[l].
 // The transposed reads and the MFMAs need EXEC all ones: every call site is wave-uniform (cw < nblk, a unit's waves).
-// LDS banks of the transposed reads on 128-byte V rows ((a / 4) % 64 per 32-lane half): rows q and q + 2 of a 4-row block and
-// the two blocks of a half (8 rows = 1 KiB apart) fall on the same eight banks, so a read is 4-way: 8 LDS cycles instead of
-// 2, 16 reads per block (HISTORY.md, round-8 notes: what a source-side swizzle of the tile's DMA would do about it).
+// LDS banks of the transposed reads on 128-byte V rows ((a / 4) % 64 per 32-lane half): in the plain row-major image rows q and
+// q + 2 of a 4-row block and the two blocks of a half (8 rows = 1 KiB apart) fall on the same eight banks, so a read is 4-way: 8
+// LDS cycles instead of 2, 16 reads per block. The cross tiles therefore live in LDS with the chunks of every row permuted
+// (attn_block<false, true>, layout::cross_v_swizzle; stage_cross_kv applies the map on the SOURCE side of the tile's DMA): every
+// read is conflict-free, 32 LDS cycles per block instead of 128. The plain image stays for the A/B and the block's own tests.
 __device__ __forceinline__ h16x8 attn_a_frag(const unsigned* xp, int ks, int lane) {
   return __builtin_bit_cast(h16x8, *reinterpret_cast<const u32x4*>(xp + 32 * (lane & 1) + 16 * ks + 4 * (lane >> 4)));
 }
@@ -355,13 +371,13 @@ __device__ __forceinline__ float attn_pick(const f32x4 (&acc)[4], int lane) {
 __device__ __forceinline__ int attn_b_offset(int nb, int ks, int lane) { return layout::kv_chunk_offset(0, 4 * ks + (lane >> 4), 16 * nb + (lane & 15)); }
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-// B piece (nb, ks) of a row-major V tile: two transposed reads (every lane of the wave active)
-__device__ __forceinline__ h16x8 attn_b_rowmajor(const h16* vblk, int nb, int ks, int lane) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;
-  const h16* a = vblk + layout::v_index(32 * ks + 8 * g + q, 16 * nb + 4 * pc);
+// B piece (nb, ks) of a row-major V tile, plain or swizzled: two transposed reads (every lane of the wave active). base: the lane's
+// layout::cross_v_read_base of the same image.
+template <bool SWZ>
+__device__ __forceinline__ h16x8 attn_b_rowmajor(const h16* vblk, int base, int nb, int ks) {
   struct { s16x4 lo, hi; } r;
-  r.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)a);
-  r.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(a + layout::v_index(4, 0)));
+  r.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(vblk + layout::cross_v_read_offset(base, nb, ks, 0, SWZ)));
+  r.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(vblk + layout::cross_v_read_offset(base, nb, ks, 1, SWZ)));
   return __builtin_bit_cast(h16x8, r);
 }
 // scale, mask and softmax partial of the block (lane = key): returns the probability, m and l in every lane
@@ -381,8 +397,9 @@ __device__ __forceinline__ void attn_put_p(float pk, float* pw, int lane) {
   reinterpret_cast<h16*>(pw + 32)[lane] = pl;
   __builtin_amdgcn_wave_barrier();
 }
+// VT: the transposed V (true) or a row-major tile (false), which is plain unless SWZ
 #if AXW_ATTN_MFMA
-template <bool VT>
+template <bool VT, bool SWZ = false>
 __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, const unsigned* qp, bool valid, float* pw, float* part, int lane) {
 #ifdef AXW_ATTN_SKIP  // timing-only build (wrong results): bounds what any speed-up of this block's arithmetic can buy
   if (lane == 0) { part[0] = 0.f; part[1] = 1.f; }
@@ -405,6 +422,7 @@ __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, con
   attn_put_p(pk, pw, lane);
   const unsigned* pwu = reinterpret_cast<const unsigned*>(pw);
   const h16x8 a0 = attn_a_frag(pwu, 0, lane), a1 = attn_a_frag(pwu, 1, lane);
+  const int vbase = VT ? 0 : layout::cross_v_read_base(lane, SWZ);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
     h16x8 b0, b1;
@@ -412,8 +430,8 @@ __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, con
       b0 = *reinterpret_cast<const h16x8*>(vblk + attn_b_offset(nb, 0, lane));
       b1 = *reinterpret_cast<const h16x8*>(vblk + attn_b_offset(nb, 1, lane));
     } else {
-      b0 = attn_b_rowmajor(vblk, nb, 0, lane);
-      b1 = attn_b_rowmajor(vblk, nb, 1, lane);
+      b0 = attn_b_rowmajor<SWZ>(vblk, vbase, nb, 0);
+      b1 = attn_b_rowmajor<SWZ>(vblk, vbase, nb, 1);
     }
     acc[nb] = AXW_MFMA_16x16x32(a0, b0, (f32x4{0.f, 0.f, 0.f, 0.f}));
     acc[nb] = AXW_MFMA_16x16x32(a1, b1, acc[nb]);
@@ -455,7 +473,7 @@ __device__ __forceinline__ void attn_block_regs(const u32x4 (&kr)[8], const u32x
 // packed K dwords with the packed query (2 instructions per 2 dims instead of 4); with the transposed V, lane = dim accumulates
 // o[dim] with dot2 over key pairs against the packed probabilities; a row-major cross tile keeps the lane = (key row, dim chunk)
 // form and sums over lane bits 3-5.
-template <bool VT>
+template <bool VT, bool SWZ = false>
 __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, const unsigned* qp, bool valid, float* pw, float* part, int lane) {
 #ifdef AXW_ATTN_SKIP  // timing-only build (wrong results): bounds what any speed-up of this block's arithmetic can buy
   if (lane == 0) { part[0] = 0.f; part[1] = 1.f; }
@@ -513,7 +531,7 @@ __device__ __forceinline__ void attn_block(const h16* kblk, const h16* vblk, con
     for (int e = 0; e < 8; ++e) o[e] = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {  // V row of key 8i + (lane>>3), dims (lane&7)*8 .. +8
-      const u32x4 vv = *reinterpret_cast<const u32x4*>(vblk + layout::v_index(8 * i + (lane >> 3), (lane & 7) * 8));
+      const u32x4 vv = *reinterpret_cast<const u32x4*>(vblk + layout::cross_v_index(8 * i + (lane >> 3), (lane & 7) * 8, SWZ));
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         o[2 * e] = fmaf(pr[i], h16lo(vv[e]), o[2 * e]);
@@ -638,6 +656,22 @@ struct RowSetF32 {
 __host__ __device__ constexpr long qfold_stride(int d) { return (long)d * d + 17L * d; }
 constexpr int QF_SQKV = 3, QF_CQKV = 6, QF_SFC1 = 9, QF_CFC1 = 13;  // vector offsets behind M, in units of D
 
+// LDS-DMA of pieces i0..i1 of one wave's 64-key cross block (16 pieces of 1 KiB: 0-7 the K block, 8-15 the V block; 16 bytes per
+// lane, the LDS destination of a piece is its base + lane * 16). gk, gv: the block in the cross caches (blocked K, row-major V);
+// sKw, sVw: the wave's blocks in LDS. K lands as it is. A V piece is eight rows of the tile: lane = 8 (row % 8) + chunk, and with
+// kCrossVSwizzle the lane fetches the chunk that layout::cross_v_source_piece gives its slot — the permutation is applied on the
+// SOURCE address, inside the same eight 128-byte lines.
+__device__ __forceinline__ void stage_cross_kv(const h16* gk, const h16* gv, h16* sKw, h16* sVw, int i0, int i1, int lane) {
+  for (int i = i0; i < i1; ++i) {
+    if (i < 8) {
+      __builtin_amdgcn_global_load_lds((gptr_t)(gk + layout::kv_chunk_offset(0, i, lane)), (lds_ptr_t)(sKw + layout::kv_chunk_offset(0, i, 0)), 16, 0, kKvAux);
+    } else {
+      const int src = layout::cross_v_source_piece(64 * (i - 8) + lane, kCrossVSwizzle);
+      __builtin_amdgcn_global_load_lds((gptr_t)(gv + 8 * src), (lds_ptr_t)(sVw + layout::kv_chunk_offset(0, i - 8, 0)), 16, 0, kKvAux);
+    }
+  }
+}
+
 // One cross-attention unit (a clip's head, one third of the 1536 padded keys) on the eight compute waves, behind the barrier that
 // handed over the query: every wave runs its 64-key block from the LDS tiles (export_onnx.py:221-230: fp32 softmax, no mask but
 // the padding), the wave that arrives last merges the eight partials and publishes the record — o[64] as four full lines, then
@@ -649,7 +683,7 @@ __device__ __forceinline__ void cross_unit_block(const h16* sK, const h16* sV, c
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   asm volatile("" ::: "memory");
   const int key = (ca_split * NCW + cw) * 64 + lane;
-  attn_block<false>(sK + cw * layout::kKvBlockElems, sV + cw * layout::kKvBlockElems, qs, key < n_audio_ctx, pscr + cw * 64, wpart + cw * kPS, lane);
+  attn_block<false, kCrossVSwizzle>(sK + cw * layout::kKvBlockElems, sV + cw * layout::kKvBlockElems, qs, key < n_audio_ctx, pscr + cw * 64, wpart + cw * kPS, lane);
   __builtin_amdgcn_wave_barrier();
   int old = 0;
   if (lane == 0) old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -662,22 +696,76 @@ __device__ __forceinline__ void cross_unit_block(const h16* sK, const h16* sV, c
   }
 }
 
-// The row producers' merge of a head's kCrossSplit partial records (pbuf: [H][kCrossSplit][kPS] = o[64], m, l each) into the
-// attention vector element i of this lane (softmax over the whole key range: rescale to the common maximum, then normalise).
-__device__ __forceinline__ float merge_cross_records(const float* pbuf, int i) {
-  const float* pp = pbuf + (i >> 6) * kCrossSplit * kPS;
-  float m = pp[64];
+// The row producers' merge of a head's kCrossSplit partial records into one element of the attention vector (softmax over the
+// whole key range: rescale to the common maximum, then normalise), on values: ms, ls the records' m and l, os their o of the
+// element. The one arithmetic of both forms below, so either gives the same bits.
+__device__ __forceinline__ float merge_cross_values(const float (&ms)[kCrossSplit], const float (&ls)[kCrossSplit], const float (&os)[kCrossSplit]) {
+  float m = ms[0];
 #pragma unroll
-  for (int sp = 1; sp < kCrossSplit; ++sp) m = fmaxf(m, pp[sp * kPS + 64]);
+  for (int sp = 1; sp < kCrossSplit; ++sp) m = fmaxf(m, ms[sp]);
   float lt = 0.f, ov = 0.f;
 #pragma unroll
   for (int sp = 0; sp < kCrossSplit; ++sp) {
-    const float ms = pp[sp * kPS + 64];
-    const float f = ms > -INFINITY ? __expf(ms - m) : 0.f;
-    lt += f * pp[sp * kPS + 65];
-    ov += f * pp[sp * kPS + (i & 63)];
+    const float f = ms[sp] > -INFINITY ? __expf(ms[sp] - m) : 0.f;
+    lt = fmaf(f, ls[sp], lt);  // explicit fmaf: both call sites compile to the same operations
+    ov = fmaf(f, os[sp], ov);
   }
   return ov / lt;
+}
+// The LDS form (the multi-clip launch; the one-clip launch with AXW_CO_MERGE_IN_GATHER=0): the records gathered into pbuf
+// ([H][kCrossSplit][kPS] = o[64], m, l each) behind a workgroup barrier, element i of this lane.
+__device__ __forceinline__ float merge_cross_records(const float* pbuf, int i) {
+  const float* pp = pbuf + (i >> 6) * kCrossSplit * kPS;
+  float ms[kCrossSplit], ls[kCrossSplit], os[kCrossSplit];
+#pragma unroll
+  for (int sp = 0; sp < kCrossSplit; ++sp) { ms[sp] = pp[sp * kPS + 64]; ls[sp] = pp[sp * kPS + 65]; os[sp] = pp[sp * kPS + (i & 63)]; }
+  return merge_cross_values(ms, ls, os);
+}
+// The merge inside the gather (the one-clip launch with the query fold): lane task t < D / 2 = (head t / 32, dims 2 (t % 32), + 1)
+// polls six pairs in one round trip — the dim pair of each of the head's kCrossSplit records (granules of the records at o_part,
+// kRec apart), then each record's (m, l) pair — merges in registers and writes act[2 t], act[2 t + 1]. The tasks go to the compute
+// waves, which idle here with little in their registers (the pollers hold the resident vocabulary rows: with half of the tasks they
+// spill): ctid = thread index among the compute waves takes task ctid, the lanes beyond D / 2 none (they still take part in the
+// give-up logic). Returns true on give-up; what it wrote then is discarded behind the caller's check barrier.
+template <int D>
+__device__ __forceinline__ bool co_gather_merge(__amdgpu_buffer_rsrc_t rs, unsigned tag, int o_part, int ctid, float* act, const unsigned* err, const int* ctl) {
+  static_assert(D / 2 <= CT, "one merge task per compute lane");
+  const int t = ctid < D / 2 ? ctid : -1;
+  // All six pairs are reloaded until every tag matches: no per-pair state (gather2 keeps a flag, an index and two values per
+  // pair, 24 registers more than the row producers have at this point), and two addresses with constant offsets.
+  const int b_o = (o_part + (t >> 5) * kCrossSplit * kRec + 2 * (t & 31)) * 8, b_ml = (o_part + (t >> 5) * kCrossSplit * kRec + 64) * 8;
+  u32x4 xo[kCrossSplit], xm[kCrossSplit];
+  bool fail = false;
+  long long t_start = 0;
+  for (int spins = 0;; ++spins) {
+    bool all = true;
+    if (t >= 0) {
+#pragma unroll
+      for (int sp = 0; sp < kCrossSplit; ++sp) xo[sp] = __builtin_amdgcn_raw_buffer_load_b128(rs, b_o + sp * kRec * 8, 0, 16);  // aux 16 = sc1
+#pragma unroll
+      for (int sp = 0; sp < kCrossSplit; ++sp) xm[sp] = __builtin_amdgcn_raw_buffer_load_b128(rs, b_ml + sp * kRec * 8, 0, 16);
+#pragma unroll
+      for (int sp = 0; sp < kCrossSplit; ++sp) all &= xo[sp][1] == tag && xo[sp][3] == tag && xm[sp][1] == tag && xm[sp][3] == tag;
+    }
+    if (all) break;
+    if ((spins & 63) == 63 && *(volatile const int*)ctl) { fail = true; break; }  // a wave of this workgroup gave up
+    if ((spins & 255) == 255 && spins >= kSpinFree) {
+      if (eget(err)) { fail = true; break; }                                      // another workgroup gave up: leave as well
+      const long long now = wall_clock64();
+      if (t_start == 0) t_start = now;
+      else if (now - t_start > kSpinTicks) { fail = true; break; }
+    }
+  }
+  if (t >= 0) {
+    float ms[kCrossSplit], ls[kCrossSplit], o0[kCrossSplit], o1[kCrossSplit];
+#pragma unroll
+    for (int sp = 0; sp < kCrossSplit; ++sp) {
+      o0[sp] = __uint_as_float(xo[sp][0]); o1[sp] = __uint_as_float(xo[sp][2]);
+      ms[sp] = __uint_as_float(xm[sp][0]); ls[sp] = __uint_as_float(xm[sp][2]);
+    }
+    *reinterpret_cast<float2*>(act + 2 * t) = float2{merge_cross_values(ms, ls, o0), merge_cross_values(ms, ls, o1)};
+  }
+  return fail;
 }
 
 // A cross-attention unit's side of the query fold: wave 0 gathers the head's 64 T values (lanes 0-31, pairs at granule base_cq)
