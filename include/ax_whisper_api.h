@@ -391,6 +391,80 @@ AX_WHISPER_API int AX_WHISPER_RunFileLongPrompted(AX_WHISPER_HANDLE handle, cons
                                                   int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
                                                   int condition_on_previous_text, char** result);
 
+/* ---- language and task per clip: detection on the GPU, a language and a task per clip (DESIGN.md "Language and task per clip")
+ * Languages are numbered by the config's all_language_codes, in file order: index j (0 .. n_lang-1, GetConfigInt "n_lang"; the
+ * handle's own: GetConfigInt "lang_index"). A request is lang [batch]: >= 0 an index, -1 the handle's language, -2 detect it from the
+ * clip; and task [batch]: 0 transcribe, 1 translate (refused when the config has no translate id). A NULL array means all -1 / all 0.
+ * Detection is openai-whisper's detect_language: the logits of the position that fed sot (context [sot] alone, no prompt in front),
+ * restricted to the language ids; lang_logprob [n_lang] = the language logits minus their logsumexp (float32, natural log; NaN
+ * entries are left out and get -inf), the detected index is the first maximum in file order; when nothing is finite the handle's
+ * language is detected and every value is -inf. A clip that detects, asks for another language than the handle's, for translate, or
+ * has a prompt decodes behind the context ([sot_prev, prompt] +) [sot, language] with its task id fed next, through the prefill
+ * hand-over of the prompted calls (AX_WHISPER_PREFILL=step: the step-fed route, detection included); any other clip decodes exactly
+ * as the calls without a language decode it. Timestamp modes only.
+ * Not covered: a language per request in whisper_srv and the Stream* calls (refused while a stream is open), under beam search and
+ * in plain mode; detection from more than the first 30 s.
+ * Text: the *Lang calls that return text run the zh Traditional-to-Simplified pass iff the CLIP's (file's) language is zh, whatever
+ * the handle's language is (a handle of another language looks for t2s.json when its first zh text arrives). */
+/** Host only. The index of a language code ("en", "zh", ...), -1 if the config does not list it. */
+AX_WHISPER_API int AX_WHISPER_LanguageIndex(AX_WHISPER_HANDLE handle, const char* code);
+/** Host only. The code of language `index` (valid until Uninit), NULL outside 0 .. n_lang-1. */
+AX_WHISPER_API const char* AX_WHISPER_LanguageCode(AX_WHISPER_HANDLE handle, int index);
+/** Front-end, encoder and detection of `batch` clips, nothing is decoded: lang_out [batch], lang_logprob (may be NULL)
+ *  [batch][n_lang]. Sharded over the handle's devices. */
+AX_WHISPER_API int AX_WHISPER_DetectLanguage(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                             int* lang_out, float* lang_logprob);
+/** RunPCMBatchTimestampPrompted with lang / task [batch] (either may be NULL); n_prompt may be NULL (no clip is prompted). lang_out
+ *  (may be NULL) [batch]: the index every clip was decoded under; lang_logprob (may be NULL) [batch][n_lang]: detecting clips, zeros
+ *  for the others. Sharded over the handle's devices. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampLang(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                                       int max_new, const int* max_new_clip, const int32_t* prompt_ids, int prompt_stride,
+                                                       const int* n_prompt, const int* lang, const int* task, int32_t* ids, int* n_ids,
+                                                       float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot,
+                                                       int* lang_out, float* lang_logprob);
+/** Stage level (after EncodeMel of `batch` clips): detection of slots 0 .. batch-1; lang_logprob and lang_logit (the raw language
+ *  logits) [batch][n_lang] may be NULL. The decode state is left reset. */
+AX_WHISPER_API int AX_WHISPER_DetectLanguageStage(AX_WHISPER_HANDLE handle, int batch, int* lang_out, float* lang_logprob, float* lang_logit);
+/** The detection kernel alone on host rows [n][n_text_state] of the decoder's final residual stream (before the final LayerNorm):
+ *  lang_logprob [n][n_lang], lang_index [n], lang_logit (may be NULL) [n][n_lang]. */
+AX_WHISPER_API int AX_WHISPER_LanguageLogProbRows(AX_WHISPER_HANDLE handle, const float* rows, int n, float* lang_logprob, int* lang_index,
+                                                  float* lang_logit);
+/** PrefillPrompts with lang / task [batch] (n_prompt, lang, task may be NULL): every clip that needs a context has it cached and its
+ *  task id about to be fed at offset L (2 without a prompt, P + 3 with one); check with GetSelfKV. lang_out, lang_logprob as above. */
+AX_WHISPER_API int AX_WHISPER_PrefillContexts(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids, int prompt_stride, const int* n_prompt,
+                                              const int* lang, const int* task, float* no_speech_logprob, float* sot_logits, int* lang_out,
+                                              float* lang_logprob);
+/** DecodeForcedTimestampPrompted with lang / task [batch]; here EVERY clip is handed over behind its context (prompted or not), so
+ *  row i of logits / chosen / logprob [batch][n_forced+1] is the step that decides id i for all of them. */
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampLang(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids, int prompt_stride,
+                                                        const int* n_prompt, const int* lang, const int* task, const int32_t* forced, int n_forced,
+                                                        float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob, int* lang_out);
+/** Long-form under a language and task per FILE. RunPCMLongWindowsPrompted (always scored; fallback and prompts only if asked for:
+ *  n_temperatures 0, n_initial NULL, NaN thresholds switch each part off) with lang / task [n_files] (either may be NULL) and
+ *  lang_out (may be NULL) [n_files]: the index every file was decoded under. -2 detects on the file's window at seek 0 (as
+ *  openai-whisper: once, on the first 30 s, also when that window is then skipped as silent); every later window of the file, and
+ *  every further attempt of the first, uses the result. The window log is that of RunPCMLongWindowsPrompted (win_prompt may be
+ *  NULL). A file without a window reports the index it asked for (the handle's where it asked for detection). */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsLang(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                    int max_new, int max_passes, float no_speech_threshold, float logprob_threshold,
+                                                    float compression_ratio_threshold, const float* temperatures, int n_temperatures,
+                                                    uint64_t seed, const int* file_ids, const int32_t* initial_prompt_ids, int prompt_stride,
+                                                    const int* n_initial, int condition_on_previous_text, const int* lang, const int* task,
+                                                    int win_cap, int* win_info, int32_t* ids, float* win_score, int* win_prompt,
+                                                    int* n_windows, int* lang_out);
+/** RunPCMLongPrompted / RunFileLongPrompted of one file under `lang` (>= 0, -1, -2) and `task` (0, 1); lang_out (may be NULL): the
+ *  file's language index. The text follows that language (zh pass). */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongLang(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                             float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                             int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
+                                             int condition_on_previous_text, int lang, int task, int* lang_out, char** result);
+AX_WHISPER_API int AX_WHISPER_RunFileLongLang(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold, float logprob_threshold,
+                                              float compression_ratio_threshold, const float* temperatures, int n_temperatures, uint64_t seed,
+                                              const int32_t* initial_prompt_ids, int n_initial, int condition_on_previous_text, int lang,
+                                              int task, int* lang_out, char** result);
+/** Host only. The text of ids decoded under language `lang_index`: AX_WHISPER_Transcript whose zh pass follows that language. */
+AX_WHISPER_API int AX_WHISPER_TranscriptLang(AX_WHISPER_HANDLE handle, const int32_t* ids, int n, int lang_index, char** result);
+
 /** ---- Beam search (DESIGN.md "Beam search"): openai-whisper's BeamSearchDecoder over this project's timestamp rules.
  *  K = beam_size (1 .. 8) hypotheses ("ranks") per clip, each in a decoder slot of its own: clip c owns slots [c*K, c*K+K), so
  *  batch * K must not exceed the handle's max_batch (per device). Per step every live rank proposes the K+1 best ids of scored

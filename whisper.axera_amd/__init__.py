@@ -109,6 +109,24 @@ SYMBOLS = {
                                                        ip, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "AX_WHISPER_RunPCMLongPrompted": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_RunFileLongPrompted": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_LanguageIndex": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "AX_WHISPER_LanguageCode": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "AX_WHISPER_DetectLanguage": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), fp]),
+    "AX_WHISPER_RunPCMBatchTimestampLang": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.c_int, C.POINTER(C.c_int),
+                                                      C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
+    "AX_WHISPER_DetectLanguageStage": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), fp, fp]),
+    "AX_WHISPER_LanguageLogProbRows": (C.c_int, [C.c_void_p, fp, C.c_int, fp, C.POINTER(C.c_int), fp]),
+    "AX_WHISPER_PrefillContexts": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), fp, fp, C.POINTER(C.c_int), fp]),
+    "AX_WHISPER_DecodeForcedTimestampLang": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.c_int, fp, ip, fp, fp,
+                                                       C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongWindowsLang": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, C.POINTER(C.c_int),
+                                                   ip, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongLang": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunFileLongLang": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_float, fp, C.c_int, C.c_uint64, ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_TranscriptLang": (C.c_int, [C.c_void_p, ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_PersistentDecodePlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
@@ -493,6 +511,140 @@ class Whisper:
                                                                     lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp)), "DecodeForcedTimestampPrompted")
         return logits, ch, lp, nsp
 
+    # ---- language and task per clip (DESIGN.md "Language and task per clip"): a language is a code of the config's list, None (the
+    # handle's language) or "auto" (detect it from the clip); a task is "transcribe" or "translate"
+    @property
+    def n_lang(self) -> int:
+        return self.get_config_int("n_lang")
+
+    def language_index(self, code: str) -> int:
+        """AX_WHISPER_LanguageIndex: the index of a language code, -1 if the config does not list it."""
+        return self.L.AX_WHISPER_LanguageIndex(self.h, code.encode())
+
+    def language_code(self, index: int):
+        """AX_WHISPER_LanguageCode: the code of language `index`, None outside the list."""
+        c = self.L.AX_WHISPER_LanguageCode(self.h, int(index))
+        return c.decode() if c is not None else None
+
+    def _lang_args(self, B, languages, tasks):
+        lang = task = None
+        if languages is not None:
+            if len(languages) != B:
+                raise ValueError("one language (a code, None or \"auto\") per clip")
+            v = []
+            for x in languages:
+                if isinstance(x, (int, np.integer)):  # an index as the C ABI takes it (-1 the handle's language, -2 detect)
+                    v.append(int(x))
+                    continue
+                j = -1 if x is None else -2 if x == "auto" else self.language_index(x)
+                if x is not None and x != "auto" and j < 0:
+                    raise ValueError(f"unknown language {x!r}")
+                v.append(j)
+            lang = (C.c_int * B)(*v)
+        if tasks is not None:
+            if len(tasks) != B:
+                raise ValueError("one task per clip")
+            for t in tasks:
+                if not isinstance(t, (int, np.integer)) and t not in (None, "transcribe", "translate"):
+                    raise ValueError(f"unknown task {t!r}")
+            # (an integer goes to the C ABI as it is: 0 transcribe, 1 translate)
+            task = (C.c_int * B)(*[int(t) if isinstance(t, (int, np.integer)) else 1 if t == "translate" else 0 for t in tasks])
+        return lang, task
+
+    def detect_language(self, clips):
+        """Front-end, encoder and detection only (AX_WHISPER_DetectLanguage): per clip (code, lang_logprob [n_lang])."""
+        clips = [_f32(c) for c in clips]
+        B = len(clips)
+        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
+        lens = (C.c_int * B)(*[len(c) for c in clips])
+        idx = (C.c_int * B)()
+        lp = np.zeros((B, self.n_lang), dtype=np.float32)
+        self._check(self.L.AX_WHISPER_DetectLanguage(self.h, ptrs, lens, B, idx, lp.ctypes.data_as(fp)), "DetectLanguage")
+        return [(self.language_code(idx[b]), lp[b].copy()) for b in range(B)]
+
+    def detect_language_stage(self, batch: int):
+        """Stage level, after encode_mel: (index [batch], lang_logprob [batch][n_lang], lang_logit [batch][n_lang])."""
+        idx = (C.c_int * batch)()
+        lp = np.zeros((batch, self.n_lang), dtype=np.float32)
+        lg = np.zeros((batch, self.n_lang), dtype=np.float32)
+        self._check(self.L.AX_WHISPER_DetectLanguageStage(self.h, batch, idx, lp.ctypes.data_as(fp), lg.ctypes.data_as(fp)), "DetectLanguageStage")
+        return np.array(idx[:], dtype=np.int32), lp, lg
+
+    def language_logprob_rows(self, rows):
+        """The detection kernel alone on residual rows [n][n_text_state]: (lang_logprob [n][n_lang], index [n], lang_logit [n][n_lang])."""
+        x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.n_text_state)
+        n = x.shape[0]
+        lp = np.zeros((n, self.n_lang), dtype=np.float32)
+        lg = np.zeros((n, self.n_lang), dtype=np.float32)
+        idx = (C.c_int * n)()
+        self._check(self.L.AX_WHISPER_LanguageLogProbRows(self.h, x.ctypes.data_as(fp), n, lp.ctypes.data_as(fp), idx, lg.ctypes.data_as(fp)),
+                    "LanguageLogProbRows")
+        return lp, np.array(idx[:], dtype=np.int32), lg
+
+    def run_timestamp_lang_batch(self, clips, languages=None, tasks=None, prompts=None, max_new: int = 0, max_new_clip=None):
+        """run_timestamp_prompted_batch under a language and task per clip (AX_WHISPER_RunPCMBatchTimestampLang): the same dict per
+        clip plus language (the code the clip was decoded under) and, for detecting clips, lang_logprob [n_lang]."""
+        clips = [_f32(c) for c in clips]
+        B = len(clips)
+        if prompts is not None and len(prompts) != B:
+            raise ValueError("one prompt (possibly empty) per clip")
+        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
+        lens = (C.c_int * B)(*[len(c) for c in clips])
+        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        pid, stride, npr = self._prompt_args(prompts) if prompts is not None else (None, 0, None)
+        lang, task = self._lang_args(B, languages, tasks)
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        n = (C.c_int * B)()
+        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
+        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+        eot = (C.c_int * B)()
+        lout = (C.c_int * B)()
+        llp = np.zeros((B, self.n_lang), dtype=np.float32)
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampLang(self.h, ptrs, lens, B, max_new, mc, pid.ctypes.data_as(ip) if pid is not None else None, stride, npr,
+                                                               lang, task, ids.ctypes.data_as(ip), n, lp.ctypes.data_as(fp), avg.ctypes.data_as(fp),
+                                                               nsp.ctypes.data_as(fp), eot, lout, llp.ctypes.data_as(fp)), "RunPCMBatchTimestampLang")
+        out = []
+        for b in range(B):
+            o = dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
+                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b]), language=self.language_code(lout[b]))
+            if languages is not None and (languages[b] == "auto" or languages[b] == -2):
+                o["lang_logprob"] = llp[b].copy()
+            out.append(o)
+        return out
+
+    def prefill_contexts(self, batch: int, languages=None, tasks=None, prompts=None, want_no_speech: bool = True):
+        """Stage level, after encode_mel of `batch` clips (AX_WHISPER_PrefillContexts): prefill_prompts under a language and task per
+        clip. Returns (no_speech_logprob [batch] or None, language index [batch], lang_logprob [batch][n_lang])."""
+        pid, stride, npr = self._prompt_args(prompts) if prompts is not None else (None, 0, None)
+        lang, task = self._lang_args(batch, languages, tasks)
+        nsp = np.zeros(batch, dtype=np.float32) if want_no_speech else None
+        lout = (C.c_int * batch)()
+        llp = np.zeros((batch, self.n_lang), dtype=np.float32)
+        self._check(self.L.AX_WHISPER_PrefillContexts(self.h, batch, pid.ctypes.data_as(ip) if pid is not None else None, stride, npr, lang, task,
+                                                      nsp.ctypes.data_as(fp) if nsp is not None else None, None, lout, llp.ctypes.data_as(fp)),
+                    "PrefillContexts")
+        return nsp, np.array(lout[:], dtype=np.int32), llp
+
+    def decode_forced_timestamp_lang(self, forced, languages=None, tasks=None, prompts=None, want_logits: bool = True):
+        """decode_forced_timestamp_prompted under a language and task per clip, every clip behind its own context: (logits
+        [batch][n+1][n_vocab] or None, chosen, logprob [batch][n+1], no_speech_logprob [batch], language index [batch])."""
+        f = np.ascontiguousarray(forced, dtype=np.int32)
+        batch = f.shape[0]
+        f = f.reshape(batch, -1)
+        n = f.shape[1]
+        pid, stride, npr = self._prompt_args(prompts) if prompts is not None else (None, 0, None)
+        lang, task = self._lang_args(batch, languages, tasks)
+        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
+        ch = np.empty((batch, n + 1), dtype=np.int32)
+        lp = np.empty((batch, n + 1), dtype=np.float32)
+        nsp = np.empty(batch, dtype=np.float32)
+        lout = (C.c_int * batch)()
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampLang(self.h, batch, pid.ctypes.data_as(ip) if pid is not None else None, stride, npr, lang, task,
+                                                                f.ctypes.data_as(ip), n, logits.ctypes.data_as(fp) if want_logits else None,
+                                                                ch.ctypes.data_as(ip), lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp), lout),
+                    "DecodeForcedTimestampLang")
+        return logits, ch, lp, nsp, np.array(lout[:], dtype=np.int32)
+
     def decode_forced_timestamp_scores(self, batch: int, forced, want_logits: bool = True, want_logits0: bool = True):
         """decode_forced_timestamps + (logprob [batch][n+1] of each step's chosen id, no_speech_logprob [batch], logits0
         [batch][n_vocab] or None: the raw row of decode offset 0). Returns (logits, chosen, logprob, no_speech_logprob, logits0)."""
@@ -721,7 +873,7 @@ class Whisper:
 
     def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0, no_speech_threshold=None, logprob_threshold=None, scores: bool = False,
                          compression_ratio_threshold=None, temperatures=None, seed: int = 0, file_ids=None, initial_prompt_ids=None,
-                         condition_on_previous_text: bool = False):
+                         condition_on_previous_text: bool = False, languages=None, tasks=None):
         """The seek loop over `files` (PCM arrays), one window of every unfinished file per pass. Per file, the list of its
         decoded windows (seek, window_frames, advance, ids, pass, slot) in order. max_new: id budget per window;
         max_passes > 0 stops after that many passes (the slots then hold the last pass's cross K/V).
@@ -733,9 +885,13 @@ class Whisper:
         file naming its random streams (default: its index in `files`); equal (seed, id) give a file the same windows in any call.
         With initial_prompt_ids (one id list per file, or None) or condition_on_previous_text the call is the prompted one
         (AX_WHISPER_RunPCMLongWindowsPrompted; scored, with fallback only if asked for as above): every tuple ends with the length of
-        the prompt its window was conditioned on."""
+        the prompt its window was conditioned on.
+        With languages (per file a code, None or "auto") or tasks ("transcribe" / "translate") the call is
+        AX_WHISPER_RunPCMLongWindowsLang, and the result is the pair (that list, the language code of every file); the tuples are
+        those of the prompted call."""
         fallback = compression_ratio_threshold is not None or temperatures is not None
-        prompted = bool(condition_on_previous_text) or initial_prompt_ids is not None
+        per_lang = languages is not None or tasks is not None
+        prompted = bool(condition_on_previous_text) or initial_prompt_ids is not None or per_lang
         scored = prompted or fallback or scores or no_speech_threshold is not None or logprob_threshold is not None
         nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
         crt, temps = float("nan"), _f32([])
@@ -761,6 +917,16 @@ class Whisper:
                 if len(init) != n:
                     raise ValueError("one initial prompt (or None) per file")
                 pid, stride, npr = self._prompt_args(init)
+            if per_lang:
+                lang, task = self._lang_args(n, languages, tasks)
+                lout = (C.c_int * n)()
+                rc = self.L.AX_WHISPER_RunPCMLongWindowsLang(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
+                                                             temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed),
+                                                             (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None,
+                                                             pid.ctypes.data_as(ip), stride, npr, int(bool(condition_on_previous_text)), lang, task, cap,
+                                                             info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
+                                                             sc.ctypes.data_as(fp), wp.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nw), lout)
+            elif prompted:
                 rc = self.L.AX_WHISPER_RunPCMLongWindowsPrompted(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
                                                                  temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed),
                                                                  (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None,
@@ -799,24 +965,40 @@ class Whisper:
             if prompted:
                 w = w + (int(wp[k]),)
             out[f].append(w)
+        if per_lang:
+            return out, [self.language_code(lout[f]) for f in range(n)]
         return out
 
+    def transcript_lang(self, ids, language) -> str:
+        """AX_WHISPER_TranscriptLang: the text of ids decoded under `language` (a code); the zh pass follows it, not the handle's."""
+        a = _i32(ids)
+        out = C.c_void_p()
+        self._check(self.L.AX_WHISPER_TranscriptLang(self.h, a.ctypes.data_as(ip), len(a), self.language_index(language), C.byref(out)), "TranscriptLang")
+        return self._take(out.value)
+
     def run_long_scored(self, audio, max_new: int = 0, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None,
-                        temperatures=None, seed: int = 0, initial_prompt_ids=None, condition_on_previous_text: bool = False):
+                        temperatures=None, seed: int = 0, initial_prompt_ids=None, condition_on_previous_text: bool = False, languages=None,
+                        tasks=None):
         """run_long with confidence -> [(start_s, end_s, text, avg_logprob, no_speech_prob)]: every segment carries its window's two
         numbers (as openai-whisper reports them); windows the silent-window rule skips yield nothing. With
-        compression_ratio_threshold or temperatures: under temperature fallback, the kept attempts only."""
+        compression_ratio_threshold or temperatures: under temperature fallback, the kept attempts only.
+        With languages / tasks (a one-entry list each, or None): under that language and task; the result is then the pair (that list,
+        the file's language code), and the text follows that language."""
         out = []
-        for w in self.run_long_windows([audio], max_new, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, scores=True,
-                                       compression_ratio_threshold=compression_ratio_threshold, temperatures=temperatures, seed=seed,
-                                       initial_prompt_ids=None if initial_prompt_ids is None else [initial_prompt_ids],
-                                       condition_on_previous_text=condition_on_previous_text)[0]:
+        wins = self.run_long_windows([audio], max_new, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, scores=True,
+                                     compression_ratio_threshold=compression_ratio_threshold, temperatures=temperatures, seed=seed,
+                                     initial_prompt_ids=None if initial_prompt_ids is None else [initial_prompt_ids],
+                                     condition_on_previous_text=condition_on_previous_text, languages=languages, tasks=tasks)
+        per_lang = languages is not None or tasks is not None
+        code = wins[1][0] if per_lang else None
+        for w in (wins[0] if per_lang else wins)[0]:
             seek, wf, _adv, ids, _p, _s, nsp, avg, skipped = w[:9]
             if skipped or (len(w) > 12 and not w[12]):
                 continue
             for s, e, tb, te in split_window(ids, self.timestamp_begin, self.eot, wf)[0]:
-                out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te]), avg, float(np.exp(np.float32(nsp)))))
-        return out
+                text = self.transcript_lang(ids[tb:te], code) if per_lang else self.transcript(ids[tb:te])
+                out.append((seek * 0.01 + s, seek * 0.01 + e, text, avg, float(np.exp(np.float32(nsp)))))
+        return (out, code) if per_lang else out
 
     def run_long(self, audio, max_new: int = 0):
         """PCM (16 kHz mono f32) of any length -> [(start_s, end_s, text)] with absolute times, one entry per segment."""
@@ -827,11 +1009,27 @@ class Whisper:
         return out
 
     def run_long_text(self, audio, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None, temperatures=None,
-                      seed: int = 0, initial_prompt_ids=None, condition_on_previous_text: bool = False) -> str:
+                      seed: int = 0, initial_prompt_ids=None, condition_on_previous_text: bool = False, languages=None, tasks=None) -> str:
         """PCM or a wav path of any length -> the whole text (AX_WHISPER_RunPCMLong / RunFileLong; with a threshold: the *Opts
         forms, the text without the windows the silent-window rule skips; with compression_ratio_threshold or temperatures: the
-        *Fallback forms)."""
+        *Fallback forms). With languages / tasks (a one-entry list each, or None): the *Lang forms, the text under that language and
+        task (its zh pass follows the file's language)."""
         out = C.c_void_p()
+        if languages is not None or tasks is not None:
+            nan = lambda v: float("nan") if v is None else float(v)
+            fallback = compression_ratio_threshold is not None or temperatures is not None
+            temps = _f32((DEFAULT_TEMPERATURES if temperatures is None else temperatures) if fallback else [])
+            init = _i32([] if initial_prompt_ids is None else initial_prompt_ids)
+            lang, task = self._lang_args(1, languages, tasks)
+            tail = (nan(no_speech_threshold), nan(logprob_threshold), nan(compression_ratio_threshold), temps.ctypes.data_as(fp) if fallback else None,
+                    len(temps), int(seed), init.ctypes.data_as(ip), len(init), int(bool(condition_on_previous_text)),
+                    lang[0] if lang is not None else -1, task[0] if task is not None else 0, None, C.byref(out))
+            if isinstance(audio, (str, os.PathLike)):
+                self._check(self.L.AX_WHISPER_RunFileLongLang(self.h, os.fspath(audio).encode(), *tail), "RunFileLongLang")
+            else:
+                a = _f32(audio)
+                self._check(self.L.AX_WHISPER_RunPCMLongLang(self.h, a.ctypes.data_as(fp), len(a), *tail), "RunPCMLongLang")
+            return self._take(out.value)
         if condition_on_previous_text or (initial_prompt_ids is not None and len(initial_prompt_ids)):  # the *Prompted forms
             nan = lambda v: float("nan") if v is None else float(v)
             fallback = compression_ratio_threshold is not None or temperatures is not None

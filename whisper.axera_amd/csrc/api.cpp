@@ -313,6 +313,12 @@ AX_WHISPER_API int AX_WHISPER_Transcript(AX_WHISPER_HANDLE handle, const int32_t
   return guarded(handle, [&](Engine& e) { *result = strdup(e.transcript(ids, n).c_str()); });
 }
 
+AX_WHISPER_API int AX_WHISPER_TranscriptLang(AX_WHISPER_HANDLE handle, const int32_t* ids, int n, int lang_index, char** result) {
+  if (!handle || (!ids && n > 0) || !result) return -1;
+  *result = nullptr;
+  return guarded(handle, [&](Engine& e) { *result = strdup(e.transcript_lang(ids, n, lang_index).c_str()); });
+}
+
 AX_WHISPER_API int AX_WHISPER_ConvertT2S(const char* config_path, const char* text, char** result) {
   if (!config_path || !text || !result) return -1;
   *result = nullptr;
@@ -650,7 +656,9 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const 
 }
 
 // text of one file's windows; opts: the silent-window rule's thresholds, or nullptr (the unscored loop)
-static int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const axw::LongScoreOptions* opts, char** result) {
+// file_lang (the *Lang forms): where opts->file_lang_out puts the file's language; the text pass then follows it
+static int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const axw::LongScoreOptions* opts, char** result,
+                     const int* file_lang = nullptr) {
   if (!handle || !pcm_data || !result || num_samples < 1) return -1;
   *result = nullptr;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
@@ -664,7 +672,9 @@ static int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples,
     for (const axw::LongWindow& w : log) {
       if (w.skipped || !w.kept) continue;
       axw::split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
-      for (const axw::WindowSegment& sg : segs) text += e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);  // host only
+      for (const axw::WindowSegment& sg : segs)  // host only
+        text += file_lang ? e.transcript_lang(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin, *file_lang)
+                          : e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);
     }
     *result = strdup(text.c_str());
   });
@@ -839,6 +849,81 @@ AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampPrompted(AX_WHISPER_HANDLE ha
   });
 }
 
+// ---- language and task per clip (DESIGN.md "Language and task per clip")
+AX_WHISPER_API int AX_WHISPER_LanguageIndex(AX_WHISPER_HANDLE handle, const char* code) {
+  Handle* h = H(handle);
+  if (!h || !code || h->group.size() == 0) return -1;
+  const auto& codes = h->group.primary().config().lang_codes;  // (fixed at Init)
+  const auto it = std::find(codes.begin(), codes.end(), std::string(code));
+  return it == codes.end() ? -1 : (int)(it - codes.begin());
+}
+
+AX_WHISPER_API const char* AX_WHISPER_LanguageCode(AX_WHISPER_HANDLE handle, int index) {
+  Handle* h = H(handle);
+  if (!h || h->group.size() == 0) return nullptr;
+  const auto& codes = h->group.primary().config().lang_codes;
+  return index < 0 || index >= (int)codes.size() ? nullptr : codes[(size_t)index].c_str();
+}
+
+AX_WHISPER_API int AX_WHISPER_DetectLanguage(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                             int* lang_out, float* lang_logprob) {
+  if (!handle || !pcm || !num_samples || !lang_out || batch < 1) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    g.detect_language(pcm, num_samples, batch, (int)g.primary().config().lang_tokens.size(), Engine::LangResult{lang_out, lang_logprob, nullptr});
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampLang(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                                       int max_new, const int* max_new_clip, const int32_t* prompt_ids, int prompt_stride,
+                                                       const int* n_prompt, const int* lang, const int* task, int32_t* ids, int* n_ids,
+                                                       float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot,
+                                                       int* lang_out, float* lang_logprob) {
+  if (!handle || !pcm || !num_samples || prompt_stride < 0 || (n_prompt && prompt_stride > 0 && !prompt_ids) || !ids || !n_ids || !token_logprob ||
+      !avg_logprob || !no_speech_logprob || !ended_eot || batch < 1)
+    return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
+    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
+    const auto& cfg = g.primary().config();
+    g.run_tokens_lang(Engine::kDecodeScored, pcm, num_samples, batch, max_new, max_new_clip, n_prompt ? &prompts : nullptr, Engine::LangSpec{lang, task},
+                      cfg.n_text_ctx, (int)cfg.lang_tokens.size(), ids, n_ids, &scores, Engine::LangResult{lang_out, lang_logprob, nullptr});
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_DetectLanguageStage(AX_WHISPER_HANDLE handle, int batch, int* lang_out, float* lang_logprob, float* lang_logit) {
+  if (!handle || !lang_out || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.detect_language_stage(batch, Engine::LangResult{lang_out, lang_logprob, lang_logit}); });
+}
+
+AX_WHISPER_API int AX_WHISPER_LanguageLogProbRows(AX_WHISPER_HANDLE handle, const float* rows, int n, float* lang_logprob, int* lang_index,
+                                                  float* lang_logit) {
+  if (!handle || !rows || !lang_logprob || !lang_index || n < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.language_logprob_rows(rows, n, lang_logprob, lang_index, lang_logit); });
+}
+
+AX_WHISPER_API int AX_WHISPER_PrefillContexts(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids, int prompt_stride, const int* n_prompt,
+                                              const int* lang, const int* task, float* no_speech_logprob, float* sot_logits, int* lang_out,
+                                              float* lang_logprob) {
+  if (!handle || prompt_stride < 0 || (n_prompt && prompt_stride > 0 && !prompt_ids) || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) {
+    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
+    e.prefill_contexts_stage(batch, n_prompt ? &prompts : nullptr, Engine::LangSpec{lang, task}, no_speech_logprob, sot_logits,
+                             Engine::LangResult{lang_out, lang_logprob, nullptr});
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampLang(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids, int prompt_stride,
+                                                        const int* n_prompt, const int* lang, const int* task, const int32_t* forced, int n_forced,
+                                                        float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob, int* lang_out) {
+  if (!handle || prompt_stride < 0 || (n_prompt && prompt_stride > 0 && !prompt_ids) || (n_forced > 0 && !forced) || batch < 1) return -1;
+  return guarded(handle, [&](Engine& e) {
+    const Engine::ForcedScores scores{logprob, no_speech_logprob, nullptr};
+    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
+    e.decode_forced_lang(Engine::kDecodeScored, batch, n_prompt ? &prompts : nullptr, Engine::LangSpec{lang, task}, forced, n_forced, logits, chosen,
+                         &scores, Engine::LangResult{lang_out, nullptr, nullptr});
+  });
+}
+
 AX_WHISPER_API int AX_WHISPER_CarryPrompt(const int32_t* all_ids, int n_all, int reset_since, const int32_t* window_ids, int n_window,
                                           int timestamp_begin, int eot, int window_frames, int skipped, int condition_on_previous_text,
                                           float temperature, int keep, int cap, int32_t* all_out, int* n_all_out, int* reset_since_out,
@@ -921,6 +1006,60 @@ AX_WHISPER_API int AX_WHISPER_RunFileLongPrompted(AX_WHISPER_HANDLE handle, cons
   return AX_WHISPER_RunPCMLongPrompted(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
                                        compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids, n_initial,
                                        condition_on_previous_text, result);
+}
+
+// ---- long-form under a language and task per file (DESIGN.md "Language and task per clip")
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsLang(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                    int max_new, int max_passes, float no_speech_threshold, float logprob_threshold,
+                                                    float compression_ratio_threshold, const float* temperatures, int n_temperatures,
+                                                    uint64_t seed, const int* file_ids, const int32_t* initial_prompt_ids, int prompt_stride,
+                                                    const int* n_initial, int condition_on_previous_text, const int* lang, const int* task,
+                                                    int win_cap, int* win_info, int32_t* ids, float* win_score, int* win_prompt,
+                                                    int* n_windows, int* lang_out) {
+  axw::LongScoreOptions opts{};
+  if (!prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids,
+                        prompt_stride, n_initial, n_files, condition_on_previous_text, opts))
+    return -1;
+  for (int f = 0; file_ids && f < n_files; ++f) {
+    if (file_ids[f] < 0 || file_ids[f] >= (1 << 27)) return -1;
+    opts.file_ids.push_back(file_ids[f]);
+  }
+  if (lang) opts.file_lang.assign(lang, lang + n_files);
+  if (task) opts.file_task.assign(task, task + n_files);
+  std::vector<int> got((size_t)n_files, -1);
+  opts.file_lang_out = lang_out ? lang_out : got.data();
+  return long_windows(handle, "RunPCMLongWindowsLang", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids, win_score,
+                      n_windows, win_prompt);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongLang(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
+                                             float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
+                                             int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
+                                             int condition_on_previous_text, int lang, int task, int* lang_out, char** result) {
+  axw::LongScoreOptions opts{};
+  if (n_initial < 0 || !prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed,
+                                         initial_prompt_ids, n_initial, &n_initial, 1, condition_on_previous_text, opts))
+    return -1;
+  opts.file_lang.assign(1, lang);
+  opts.file_task.assign(1, task);
+  int got = -1;
+  opts.file_lang_out = &got;
+  const int rc = long_text(handle, pcm_data, num_samples, &opts, result, &got);
+  if (rc == 0 && lang_out) *lang_out = got;
+  return rc;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileLongLang(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold, float logprob_threshold,
+                                              float compression_ratio_threshold, const float* temperatures, int n_temperatures, uint64_t seed,
+                                              const int32_t* initial_prompt_ids, int n_initial, int condition_on_previous_text, int lang,
+                                              int task, int* lang_out, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return AX_WHISPER_RunPCMLongLang(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
+                                   compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids, n_initial,
+                                   condition_on_previous_text, lang, task, lang_out, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {

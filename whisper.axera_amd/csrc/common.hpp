@@ -578,8 +578,26 @@ struct PrefillHandoverParams {
   int* off; int* tok; int* n_out; int transcribe;
   const h16* tok_emb; const float* pos; float* x; int d_model;
   float* no_speech; const float* no_speech_clip;
+  const int* task_tok;  // optional device [n_clips]: the id fed at len[c] instead of `transcribe` (a clip's task); nullptr: transcribe
 };
 void launch_prefill_handover(const PrefillHandoverParams& p, hipStream_t s);
+
+// ---- language detection (decode_language.hip; DESIGN.md "Language and task per clip"): per clip c, the final LayerNorm of the
+// fp32 residual row x[x_row ? x_row[c] : c] and its dot products with the n_lang language rows of the tied embedding ->
+// lang_logit (optional), lang_logprob = lang_logit - logsumexp (NaN entries left out, -inf), lang_index = the first maximum in
+// list order (nothing finite: fallback_index, every lang_logprob -inf); with ctx: ctx[lang_row[c]] = lang_tokens[lang_index[c]]
+constexpr int kLangMax = 128;     // languages
+constexpr int kLangMaxD = 2048;   // d_model
+struct LangDetectParams {
+  const float* x; const int* x_row;          // fp32 rows of d_model; device [n_clips] row numbers or nullptr
+  const float* ln_w; const float* ln_b; const h16* tok_emb;
+  const int* lang_tokens; int n_lang;        // device [n_lang], ids inside the vocabulary
+  int d_model, n_clips, fallback_index;
+  float* lang_logit; float* lang_logprob;    // out [n_clips][n_lang]
+  int* lang_index;                           // out [n_clips]
+  int* ctx; const int* lang_row;             // optional: the prefill pass's context table and, per clip, the entry to patch
+};
+void launch_language_detect(const LangDetectParams& p, hipStream_t s);
 
 // ---- persistent decode (decode_persistent.hip, decode_persistent2.hip): the whole greedy loop of one to three clips in ONE launch
 typedef unsigned long long u64;

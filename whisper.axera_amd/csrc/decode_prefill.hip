@@ -9,8 +9,8 @@
 //   prefill_attention_kernel     block attention of many queries over the decode layouts: causal over the slot's self cache, or over
 //                                the n_audio_ctx keys of its cross cache                                   h16 [rows][d]
 //   prefill_gather_rows_kernel   the final residual row of every clip's sot position (the no-speech row)   fp32 [clips][d]
-//   prefill_handover_kernel      the decode state the next step starts from: off = len, tok = transcribe, n_out = 0,
-//                                x_dec = tok_emb[transcribe] + pos[len], the no-speech value
+//   prefill_handover_kernel      the decode state the next step starts from: off = len, tok = transcribe (or the clip's
+//                                task id), n_out = 0, x_dec = tok_emb[tok] + pos[len], the no-speech value
 // Out of scope here as in the engine: beam search, the Stream* slots and the persistent launches take no prompt.
 //
 // prefill_attention_kernel: workgroup = 4 waves = 64 queries of one (clip, head), 16 query rows per wave; keys in the 64-key blocks of
@@ -203,14 +203,15 @@ void launch_prefill_gather_rows(const float* x, const int* rows, float* out, int
 __global__ __launch_bounds__(256) void prefill_handover_kernel(PrefillHandoverParams p) {
   const int c = blockIdx.x;
   const int b = p.slot[c], L = p.len[c];
+  const int tok = p.task_tok ? p.task_tok[c] : p.transcribe;  // (a clip's own task: DESIGN.md "Language and task per clip")
   if (threadIdx.x == 0) {
     p.off[b] = L;
-    p.tok[b] = p.transcribe;
+    p.tok[b] = tok;
     p.n_out[b] = 0;
     if (p.no_speech && p.no_speech_clip) p.no_speech[b] = p.no_speech_clip[c];
   }
   const int d = p.d_model;
-  for (int i = threadIdx.x; i < d; i += 256) p.x[(long)b * d + i] = (float)p.tok_emb[(long)p.transcribe * d + i] + p.pos[(long)L * d + i];
+  for (int i = threadIdx.x; i < d; i += 256) p.x[(long)b * d + i] = (float)p.tok_emb[(long)tok * d + i] + p.pos[(long)L * d + i];
 }
 
 void launch_prefill_handover(const PrefillHandoverParams& p, hipStream_t s) {

@@ -200,6 +200,9 @@ void Engine::load_config(const std::string& dir, const std::string& type, const 
   if (it == cfg_.lang_codes.end()) it = std::find(cfg_.lang_codes.begin(), cfg_.lang_codes.end(), std::string("zh"));
   if (it == cfg_.lang_codes.end()) it = cfg_.lang_codes.begin();
   effective_lang_ = *it;  // Whisper.cpp:244-248: an unknown language silently becomes DEFAULT_LANG
+  handle_lang_ = (int)(it - cfg_.lang_codes.begin());
+  cfg_.ints["n_lang"] = (long)cfg_.lang_codes.size();
+  cfg_.ints["lang_index"] = handle_lang_;  // the handle's language, as AX_WHISPER_LanguageIndex numbers them
   sot_seq_[0] = cfg_.sot;
   sot_seq_[1] = cfg_.lang_tokens[it - cfg_.lang_codes.begin()];
   sot_seq_[2] = cfg_.transcribe;
@@ -790,7 +793,12 @@ void Engine::run_tokens(DecodeMode mode, const float* const* pcm, const float* d
 // .ocd2 dictionaries it names) relative to the working directory; here: $AX_WHISPER_OPENCC_DIR, the working directory,
 // then the model directory. Missing files are not an error (the text then stays as decoded), a broken file is.
 void Engine::load_t2s(const std::string& model_path) {
-  if (effective_lang_ != "zh") return;
+  model_path_ = model_path;
+  if (effective_lang_ == "zh") t2s_ = find_t2s();
+}
+
+std::unique_ptr<T2SConverter> Engine::find_t2s() const {
+  const std::string& model_path = model_path_;
   std::vector<std::string> dirs;
   if (const char* e = getenv("AX_WHISPER_OPENCC_DIR")) dirs.push_back(std::string(e) + "/");
   dirs.push_back("");
@@ -798,14 +806,24 @@ void Engine::load_t2s(const std::string& model_path) {
   for (const std::string& d : dirs) {
     std::ifstream f(d + "t2s.json");
     if (!f.is_open()) continue;
-    t2s_.reset(new T2SConverter(d + "t2s.json"));
-    return;
+    return std::unique_ptr<T2SConverter>(new T2SConverter(d + "t2s.json"));
   }
+  return nullptr;
 }
 
 std::string Engine::transcript(const int32_t* ids, int n) const {
   std::string s = detokenize(ids, n);
   return t2s_ ? t2s_->convert(s) : s;
+}
+
+// The text of a clip decoded under language `lang` (an index of the config's list): the zh pass follows the CLIP's language, not the
+// handle's. A handle of another language looks for the dictionaries when its first zh clip arrives (same places, same rules).
+std::string Engine::transcript_lang(const int32_t* ids, int n, int lang) const {
+  std::string s = detokenize(ids, n);
+  if (lang < 0 || lang >= (int)cfg_.lang_codes.size() || cfg_.lang_codes[(size_t)lang] != "zh") return s;
+  if (t2s_) return t2s_->convert(s);
+  std::call_once(t2s_late_once_, [&] { t2s_late_ = find_t2s(); });
+  return t2s_late_ ? t2s_late_->convert(s) : s;
 }
 
 // Whisper.cpp:224-229 with bounds checks: bytes are concatenated, ids beyond the table skipped.
@@ -907,9 +925,11 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
     std::vector<int> base(batch);
     const int keep = cfg_.n_text_ctx / 2 - 1;
     for (int b = 0; b < batch; ++b) {
-      if (prompt_->n_prompt[b] < 1) throw std::runtime_error("decode_forced_prompted: every clip needs a prompt");
-      base[b] = std::min(prompt_->n_prompt[b], keep) + 1;  // L - 2
-      if (base[b] + 3 + n_forced > cfg_.n_text_ctx) throw std::runtime_error("decode_forced_prompted: n_forced out of range");
+      // (decode_forced_lang hands EVERY clip over behind a context: [sot, language] alone is L = 2)
+      if (prompt_->n_prompt[b] < 1 && !lang_) throw std::runtime_error("decode_forced_prompted: every clip needs a prompt");
+      const char* who = lang_ ? "decode_forced_lang" : "decode_forced_prompted";
+      base[b] = prompt_->n_prompt[b] < 1 ? 0 : std::min(prompt_->n_prompt[b], keep) + 1;  // L - 2
+      if (base[b] + 3 + n_forced > cfg_.n_text_ctx) throw std::runtime_error(std::string(who) + ": n_forced out of range");
     }
     prefill_prompts(batch, *prompt_, scored);
     d_base = device_array<int>(batch);

@@ -77,6 +77,10 @@ struct EngineMemory {
     DeviceArray<h16> ln, qkv, att, hid;
     DeviceArray<int> row_tab, clip_tab;
     int rows_cap = 0, clips_cap = 0;
+    // language and task per clip: the detecting slots and the context entries to patch [2][clips], the clips' task ids, and the detection kernel's
+    // language id list [n_lang] and outputs (index [clips], logprob and logit [clips][n_lang])
+    DeviceArray<int> det_tab, task_tok, lang_tok, lang_idx;
+    DeviceArray<float> lang_lp, lang_logit;
   } prefill_;
 };
 
@@ -133,6 +137,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
                            const PromptSpec& prompts, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample = nullptr) override;
   std::string detokenize(const int32_t* ids, int n) const override;
   std::string transcript(const int32_t* ids, int n) const override;
+  std::string transcript_lang(const int32_t* ids, int n, int lang) const override;
   bool has_t2s() const { return (bool)t2s_; }
   void compute_mel(const float* pcm, int n_samples, float* mel_out) override;
   void encode_mel(const float* mel, int batch) override;
@@ -143,6 +148,16 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void prefill_stage(int batch, const PromptSpec& prompts, float* no_speech_logprob, float* sot_logits) override;
   void decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec& prompts, const int32_t* forced, int n_forced, float* logits,
                               int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample = nullptr) override;
+  void run_tokens_lang(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
+                       const PromptSpec* prompts, const LangSpec& lang, int32_t* ids, int* n_ids, const ClipScores* scores,
+                       const LangResult& out) override;
+  void detect_language(const float* const* pcm, const int* n_samples, int batch, const LangResult& out) override;
+  void detect_language_stage(int batch, const LangResult& out) override;
+  void language_logprob_rows(const float* rows, int n, float* lang_logprob, int* lang_index, float* lang_logit) override;
+  void prefill_contexts_stage(int batch, const PromptSpec* prompts, const LangSpec& lang, float* no_speech_logprob, float* sot_logits,
+                              const LangResult& out) override;
+  void decode_forced_lang(DecodeMode mode, int batch, const PromptSpec* prompts, const LangSpec& lang, const int32_t* forced, int n_forced,
+                          float* logits, int32_t* chosen, const ForcedScores* scores, const LangResult& out) override;
   void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
   void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
                        const SampleSpec* sample = nullptr) override;
@@ -185,6 +200,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void load_config(const std::string& dir, const std::string& type, const std::string& language);
   void load_weights(const SafeTensors& st);
   void load_t2s(const std::string& model_path);
+  std::unique_ptr<T2SConverter> find_t2s() const;  // the converter of the first t2s.json found, or null
   void ensure_capacity(int batch);
   void free_slot_buffers();
   void upload_pcm(const float* const* pcm, const int* n_samples, int batch);
@@ -251,6 +267,23 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // the raw logits row it was taken from; entries of unprompted slots are 0
   void prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_speech, float* no_speech_out = nullptr, float* sot_logits_out = nullptr);
   void prefill_pass(int rows, int n_clips, int max_len, bool want_no_speech);
+  // language and task per clip (DESIGN.md "Language and task per clip"). lang_: the request of the call in progress and where its
+  // results go, beside prompt_ (a call that sets lang_ also sets prompt_, to an empty PromptSpec where no clip is prompted);
+  // prefill_prompts plans the contexts over both. force_context: every clip gets a context (decode_forced_lang).
+  struct LangCall { LangSpec spec; LangResult out; bool force_context; };
+  const LangCall* lang_ = nullptr;
+  int handle_lang_ = 0;  // index of the handle's language in the config's list
+  void require_lang_call(DecodeMode mode, const char* what) const;  // timestamp modes, no open stream
+  void check_lang_request(const LangSpec& lang, int batch) const;   // throws what the context plan would throw, before any GPU work
+  void ensure_lang_buffers();  // prefill_.lang_tok (+ the per-clip arrays, with ensure_prefill_scratch)
+  LangDetectParams detect_params(const float* x, int n_clips, bool want_logit) const;
+  // prefill route: the layers of one decoder step at offset 0 (no vocabulary projection, no advance) and the detection kernel on
+  // the detecting slots' final residual rows, all on the stream; d_ctx (or null) is patched at lang_row. Results stay on the device
+  // until fetch_detected.
+  void enqueue_detect_prefill(int batch, const std::vector<int>& slot, int* d_ctx, const std::vector<int>& lang_row, bool want_logit);
+  void fetch_detected(int n, int* idx, float* lp, float* logit);
+  // step-fed route: one decoder step at offset 0 with the logits dump, the pick on the host; leaves the decode state reset
+  void detect_step_fed(int batch, const std::vector<int>& slot, int* idx, float* lp, float* logit);
   void prefill_step_fed(int batch, const std::vector<int>& slot, const std::vector<int>& len, const std::vector<int>& ctx,
                         const std::vector<int>& row0, bool want_no_speech);
   void ensure_prefill_scratch(int rows, int clips);
@@ -272,6 +305,10 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   int sot_seq_[4] = {0, 0, 0, 0};
   std::vector<std::string> tokens_;
   std::unique_ptr<T2SConverter> t2s_;  // zh only
+  // a handle of another language: the converter for clips decoded under zh (transcript_lang), looked for at first use
+  std::string model_path_;
+  mutable std::once_flag t2s_late_once_;
+  mutable std::unique_ptr<T2SConverter> t2s_late_;
   std::string effective_lang_;
   bool feature_openai_ = false;  // feature_mode "openai" (engine.cpp load_config)
   int device_ = 0;
@@ -350,6 +387,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   float bench_frontend(int batch, int iters);
   float bench_frontend_long(int batch, int arg, int iters);
   float bench_prefill(const std::string& what, int batch, int arg, int iters);
+  float bench_detect_language(int batch, int arg, int iters);
 };
 
 }  // inline namespace AXW_NS

@@ -72,6 +72,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "frontend") return bench_frontend(batch, iters);
   if (what == "frontend_long") return bench_frontend_long(batch, arg, iters);
   if (what == "prefill" || what == "prefill_pass" || what == "prefill_step") return bench_prefill(what, batch, arg, iters);
+  if (what == "detect_language") return bench_detect_language(batch, arg, iters);
   throw std::runtime_error("bench: unknown target '" + what + "'");
 }
 
@@ -108,6 +109,20 @@ float Engine::bench_prefill(const std::string& what, int batch, int arg, int ite
       reset_decode_state(batch);
       prefill_prompts(batch, ps, true);
     }
+  });
+}
+
+// detect_language: detection of `batch` slots as AX_WHISPER_DetectLanguageStage runs it (reset, the [sot] position, the pick, the
+// results on the host); arg 0: the prefill route (one step's layers + the detection kernel), 1: the step-fed route (one decoder step with
+// the logits dump, the pick on the host), anything else: the handle's route. Cross K/V as bench "prefill" finds it.
+float Engine::bench_detect_language(int batch, int arg, int iters) {
+  require_timestamp_vocab();
+  const ScopedSet<int> scope(prefill_force_, arg == 0 ? 0 : arg == 1 ? 1 : -1);
+  std::vector<int> idx(batch);
+  const LangResult out{idx.data(), nullptr, nullptr};
+  detect_language_stage(batch, out);  // warm: scratch, the language id list
+  return timed_ms(stream(), [&] {
+    for (int i = 0; i < iters; ++i) detect_language_stage(batch, out);
   });
 }
 

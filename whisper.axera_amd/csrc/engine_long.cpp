@@ -137,6 +137,9 @@ void Engine::compute_mel_window(const float* pcm, int n_samples, int seek, float
 // the next pass at the next temperature (one more log entry, kept = false on the one that failed).
 // opts->prompted(): prompt conditioning (DESIGN.md "Prompt conditioning"). Every file carries (all_ids, reset_since); a window's
 // prompt, the same for each of its attempts, goes to greedy_loop through prompt_, and carry_prompt runs after every kept window.
+// opts->per_file_language(): a language and task per file (DESIGN.md "Language and task per clip"). Every window of a pass carries
+// its file's language and task to greedy_loop through lang_; a detecting file asks for -2 on its first window (seek 0, attempt 0)
+// and for the index that came back on every window after it.
 void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                               const LongScoreOptions* opts, std::vector<LongWindow>& log) {
   if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
@@ -145,6 +148,7 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   if (opts) require_scored_vocab();
   const bool fallback = opts && !opts->temperatures.empty();
   const bool prompted = opts && opts->prompted();
+  const bool per_lang = opts && opts->per_file_language();
   if (prompted && !opts->initial_prompt_ids.empty() && (long)opts->initial_prompt_ids.size() < (long)opts->file_base + n_files)
     throw std::runtime_error("long-form: fewer initial prompts than files");
   const int n_attempts = fallback ? (int)opts->temperatures.size() : 1;
@@ -155,6 +159,23 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
     if (!(opts->temperatures[a] >= 0.f) || std::isinf(opts->temperatures[a]) || (opts->temperatures[a] > 0.f && opts->temperatures[a] < 1e-6f))
       throw std::runtime_error("long-form: temperatures must be 0, or finite and >= 1e-6");
   const StepSpec spec{fallback ? kDecodeSampled : opts ? kDecodeScored : kDecodeTimestamps};
+  // the language every file decodes under (-2: still to be detected) and its task
+  std::vector<int> file_lang(per_lang ? n_files : 0, -1), file_task(per_lang ? n_files : 0, 0);
+  if (per_lang) {
+    require_lang_call(spec.mode, "run_long_windows");
+    for (const std::vector<int>* v : {&opts->file_lang, &opts->file_task})
+      if (!v->empty() && (long)v->size() < (long)opts->file_base + n_files) throw std::runtime_error("long-form: fewer languages or tasks than files");
+    for (int f = 0; f < n_files; ++f) {
+      if (!opts->file_lang.empty()) file_lang[f] = opts->file_lang[(size_t)(opts->file_base + f)];
+      if (!opts->file_task.empty()) file_task[f] = opts->file_task[(size_t)(opts->file_base + f)];
+    }
+    check_lang_request(LangSpec{file_lang.data(), file_task.data()}, n_files);  // a bad request fails before any GPU work
+    for (int f = 0; f < n_files; ++f) {
+      if (file_lang[f] == -1) file_lang[f] = handle_lang_;
+      // (a file without a window keeps this: the index it asked for, the handle's where it asked for detection)
+      if (opts->file_lang_out) opts->file_lang_out[opts->file_base + f] = file_lang[f] == -2 ? handle_lang_ : file_lang[f];
+    }
+  }
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   // windows per pass: the engine's capacity (AX_WHISPER_MAX_BATCH / max_batch of Init, or what earlier calls grew it to);
@@ -177,7 +198,8 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   std::vector<PromptCarry> carry(prompted ? n_files : 0);
   for (int f = 0; prompted && f < n_files && !opts->initial_prompt_ids.empty(); ++f) carry[f].all_ids = opts->initial_prompt_ids[(size_t)(opts->file_base + f)];
   std::vector<int32_t> prompt_ids(prompted ? (size_t)S * keep : 0);
-  std::vector<int> n_prompt(prompted ? S : 0);
+  std::vector<int> n_prompt(prompted || per_lang ? S : 0, 0);  // (a call under lang_ names its prompts too: none)
+  std::vector<int> win_lang(per_lang ? S : 0), win_task(per_lang ? S : 0), win_lang_got(per_lang ? S : 0);
   int next_file = 0, steps = 0;
   for (int pass = 0; max_passes <= 0 || pass < max_passes; ++pass) {
     // finished files leave, the others move up, waiting files take the free places
@@ -209,6 +231,21 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
         n_prompt[i] = n;
         std::copy(c.all_ids.end() - n, c.all_ids.end(), prompt_ids.begin() + (size_t)i * keep);
       }
+    }
+    if (per_lang) {
+      for (int i = 0; i < A; ++i) { win_lang[i] = file_lang[files[i]]; win_task[i] = file_task[files[i]]; }
+      const PromptSpec ps{prompt_ids.data(), keep, n_prompt.data()};
+      const LangCall call{LangSpec{win_lang.data(), win_task.data()}, LangResult{win_lang_got.data(), nullptr, nullptr}, false};
+      const ScopedSet<const PromptSpec*> scope(prompt_, &ps);
+      const ScopedSet<const LangCall*> lscope(lang_, &call);
+      steps += greedy_loop(spec, A, max_new, nullptr);
+      for (int i = 0; i < A; ++i) {
+        const int f = files[i];
+        if (file_lang[f] != -2) continue;
+        file_lang[f] = win_lang_got[i];  // detected once, on the window at seek 0; every later window of the file uses it
+        if (opts->file_lang_out) opts->file_lang_out[opts->file_base + f] = file_lang[f];
+      }
+    } else if (prompted) {
       const PromptSpec ps{prompt_ids.data(), keep, n_prompt.data()};
       const ScopedSet<const PromptSpec*> scope(prompt_, &ps);
       steps += greedy_loop(spec, A, max_new, nullptr);

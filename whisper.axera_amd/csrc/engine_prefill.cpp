@@ -4,7 +4,9 @@
 // steps (logits, rules, advance) run unchanged. Slots without a prompt are not touched.
 // Two routes lead to that state: the prefill pass (decode_prefill.hip + the encoder's GEMM / LayerNorm, all rows at once) and the
 // step-fed route (AX_WHISPER_PREFILL=step: one existing decoder step per position; the yardstick for error and time).
-// Out of scope: prompts under beam search, in the Stream* slots and in the persistent launches; best_of above 1.
+// A language and task per clip (DESIGN.md "Language and task per clip") is the same mechanism: the context [sot, language] is the
+// prompted case with an empty prompt and no sot_prev, the task id is what the hand-over feeds; language detection runs in front.
+// Out of scope: prompts and per-clip languages under beam search, in the Stream* slots and in the persistent launches; best_of above 1.
 #include "engine_impl.hpp"
 
 #include <climits>
@@ -13,37 +15,66 @@ namespace axw {
 inline namespace AXW_NS {
 
 namespace {
-// the prompted clips of one call, as the kernels' tables want them
+// the clips of one call that get a context, as the kernels' tables want them
 struct PromptPlan {
   std::vector<int> ctx, row_pos, row_slot;             // per row
-  std::vector<int> row0, len, slot, sot_row, n_kept;   // per prompted clip
+  std::vector<int> row0, len, slot, sot_row, n_kept;   // per context clip
+  std::vector<int> task_tok, lang_row;                 // per context clip: the id fed at the hand-over; the row that holds its language id
+  std::vector<int> detect;                             // the context clips that detect their language (indices into the arrays above)
+  std::vector<int> lang_index;                         // per clip of the batch: its language index; -2: to be detected
   int rows = 0, max_len = 0;
   int clips() const { return (int)slot.size(); }
 };
 }  // namespace
 
-// prompts.n_prompt[b] ids of clip b at prompts.ids + b * prompts.stride; truncated to their last n_text_ctx / 2 - 1 (openai-whisper)
-static PromptPlan plan_prompts(const ModelConfig& cfg, const int* sot_seq, int batch, const IEngine::PromptSpec& pr) {
+// The context plan of a call. prompts.n_prompt[b] ids of clip b at prompts.ids + b * prompts.stride, truncated to their last
+// n_text_ctx / 2 - 1 (openai-whisper); lang (or null): the language and task of every clip. A clip gets a context
+// ([sot_prev, prompt] if prompted) + [sot, language] when it is prompted, detects, asks for another language than the handle's or
+// another task than transcribe (or when force says so); without `lang` this is exactly the prompted clips of the call.
+static PromptPlan plan_contexts(const ModelConfig& cfg, const int* sot_seq, int handle_lang, int batch, const IEngine::PromptSpec& pr,
+                                const IEngine::LangSpec* lang, bool force) {
   if (!pr.n_prompt) throw std::runtime_error("prefill_prompts: no prompt lengths");
-  const auto it = cfg.ints.find("sot_prev");
-  if (it == cfg.ints.end() || it->second < 0 || it->second >= cfg.n_vocab) throw std::runtime_error("prompted decode needs a sot_prev id inside the vocabulary");
-  const int sot_prev = (int)it->second, keep = cfg.n_text_ctx / 2 - 1, ts_begin = cfg.no_timestamps + 1;
+  const int keep = cfg.n_text_ctx / 2 - 1, ts_begin = cfg.no_timestamps + 1, n_lang = (int)cfg.lang_tokens.size();
+  int sot_prev = -1, translate = -1;
+  {
+    const auto it = cfg.ints.find("sot_prev");
+    if (it != cfg.ints.end() && it->second >= 0 && it->second < cfg.n_vocab) sot_prev = (int)it->second;
+    const auto tr = cfg.ints.find("translate");
+    if (tr != cfg.ints.end() && tr->second >= 0 && tr->second < cfg.n_vocab) translate = (int)tr->second;
+  }
+  if (!lang && sot_prev < 0) throw std::runtime_error("prompted decode needs a sot_prev id inside the vocabulary");
   PromptPlan pl;
+  pl.lang_index.assign(batch, handle_lang);
   for (int b = 0; b < batch; ++b) {
     const int n = pr.n_prompt[b];
     if (n < 0 || n > pr.stride) throw std::runtime_error("prefill_prompts: prompt length " + std::to_string(n) + " of clip " + std::to_string(b) + " out of range");
-    if (n == 0) continue;
-    if (!pr.ids) throw std::runtime_error("prefill_prompts: no prompt ids");
-    const int P = std::min(n, keep);
-    const int32_t* src = pr.ids + (size_t)b * pr.stride + (n - P);
-    for (int i = 0; i < P; ++i)
-      if (src[i] < 0 || src[i] >= cfg.n_vocab || (src[i] >= cfg.eot && src[i] < ts_begin))
-        throw std::runtime_error("prefill_prompts: id " + std::to_string(src[i]) + " of clip " + std::to_string(b) + " is neither text nor a timestamp");
-    const int L = P + 3;
+    const int lg = lang && lang->lang ? lang->lang[b] : -1, task = lang && lang->task ? lang->task[b] : 0;
+    if (lg < -2 || lg >= n_lang) throw std::runtime_error("language index " + std::to_string(lg) + " of clip " + std::to_string(b) + " is outside [-2, " + std::to_string(n_lang) + ")");
+    if (task != 0 && task != 1) throw std::runtime_error("task " + std::to_string(task) + " of clip " + std::to_string(b) + " is neither 0 (transcribe) nor 1 (translate)");
+    if (task == 1 && translate < 0) throw std::runtime_error("translate: the config has no translate id inside the vocabulary");
+    if (lg == -2 && n_lang < 2) throw std::runtime_error("language detection needs a config with more than one language");
+    pl.lang_index[b] = lg == -1 ? handle_lang : lg;
+    if (n == 0 && !force && lg != -2 && pl.lang_index[b] == handle_lang && task == 0) continue;  // no context: the clip is not touched
+    int P = 0;
+    const int32_t* src = nullptr;
+    if (n > 0) {
+      if (!pr.ids) throw std::runtime_error("prefill_prompts: no prompt ids");
+      if (sot_prev < 0) throw std::runtime_error("prompted decode needs a sot_prev id inside the vocabulary");
+      P = std::min(n, keep);
+      src = pr.ids + (size_t)b * pr.stride + (n - P);
+      for (int i = 0; i < P; ++i)
+        if (src[i] < 0 || src[i] >= cfg.n_vocab || (src[i] >= cfg.eot && src[i] < ts_begin))
+          throw std::runtime_error("prefill_prompts: id " + std::to_string(src[i]) + " of clip " + std::to_string(b) + " is neither text nor a timestamp");
+    }
+    const int L = P ? P + 3 : 2, lead = L - 2;  // rows in front of sot
     if (L + 1 > cfg.n_text_ctx) throw std::runtime_error("prefill_prompts: the prompt leaves no room in the context");
-    pl.row0.push_back(pl.rows); pl.len.push_back(L); pl.slot.push_back(b); pl.sot_row.push_back(pl.rows + P + 1); pl.n_kept.push_back(P);
+    if (lg == -2) pl.detect.push_back(pl.clips());
+    pl.row0.push_back(pl.rows); pl.len.push_back(L); pl.slot.push_back(b); pl.sot_row.push_back(pl.rows + lead); pl.n_kept.push_back(P);
+    pl.task_tok.push_back(task == 1 ? translate : sot_seq[2]);
+    pl.lang_row.push_back(pl.rows + lead + 1);
     for (int i = 0; i < L; ++i) {
-      pl.ctx.push_back(i == 0 ? sot_prev : i <= P ? (int)src[i - 1] : sot_seq[i - P - 1]);
+      // (a detecting clip's language entry is the handle's until the detection kernel patches it)
+      pl.ctx.push_back(i < lead ? (i == 0 ? sot_prev : (int)src[i - 1]) : i == lead ? sot_seq[0] : lg >= 0 ? cfg.lang_tokens[lg] : sot_seq[1]);
       pl.row_pos.push_back(i);
       pl.row_slot.push_back(b);
     }
@@ -97,6 +128,11 @@ void Engine::ensure_prefill_scratch(int rows, int clips) {
     p.nsp = device_array<float>(clips);
     p.clip_tab = device_array<int>((size_t)clips * 4);
     p.sot_logits.reset();
+    p.det_tab = device_array<int>((size_t)clips * 2);
+    p.task_tok = device_array<int>(clips);
+    p.lang_idx = device_array<int>(clips);
+    p.lang_lp = device_array<float>((size_t)clips * kLangMax);
+    p.lang_logit = device_array<float>((size_t)clips * kLangMax);
     p.clips_cap = clips;
   }
   if (d_ts_logits_ && !p.sot_logits) {  // (freed with the engine; re-made when the capacity grows)
@@ -107,16 +143,23 @@ void Engine::ensure_prefill_scratch(int rows, int clips) {
 
 void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_speech, float* no_speech_out, float* sot_logits_out) {
   if (batch < 1 || batch > cap_) throw std::runtime_error("prefill_prompts: batch exceeds the slots");
-  const PromptPlan pl = plan_prompts(cfg_, sot_seq_, batch, prompts);
+  const LangCall* lc = lang_;
+  PromptPlan pl = plan_contexts(cfg_, sot_seq_, handle_lang_, batch, prompts, lc ? &lc->spec : nullptr, lc && lc->force_context);
+  const int n_lang = (int)cfg_.lang_tokens.size();
+  const LangResult lout = lc ? lc->out : LangResult{};
   for (int b = 0; no_speech_out && b < batch; ++b) no_speech_out[b] = 0.f;
   if (sot_logits_out) std::fill(sot_logits_out, sot_logits_out + (size_t)batch * cfg_.n_vocab, 0.f);
-  const int n = pl.clips();
+  if (lout.lang_logprob) std::fill(lout.lang_logprob, lout.lang_logprob + (size_t)batch * n_lang, 0.f);
+  if (lout.lang_logit) std::fill(lout.lang_logit, lout.lang_logit + (size_t)batch * n_lang, 0.f);
+  for (int b = 0; lout.detected && b < batch; ++b) lout.detected[b] = pl.lang_index[b];
+  const int n = pl.clips(), nd = (int)pl.detect.size();
   if (n == 0) return;
   const int route = prefill_route();
   if (want_no_speech) { require_scored_vocab(); ensure_ts_logits(); ensure_ts_scores(); }
   const int d = cfg_.n_text_state;
   hipStream_t s = stream();
   ensure_prefill_scratch(pl.rows, cap_);
+  if (lc) ensure_lang_buffers();
   PrefillScratch& pf = prefill_;
   int *d_ctx = pf.row_tab, *d_row_pos = d_ctx + pl.rows, *d_row_slot = d_row_pos + pl.rows;
   int *d_row0 = pf.clip_tab, *d_len = d_row0 + n, *d_slot = d_len + n, *d_sot_row = d_slot + n;
@@ -127,7 +170,19 @@ void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_
   HIP_CHECK(hipMemcpyAsync(d_len, pl.len.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_slot, pl.slot.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_sot_row, pl.sot_row.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  if (lc) HIP_CHECK(hipMemcpyAsync(pf.task_tok, pl.task_tok.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipStreamSynchronize(s));  // (pageable sources)
+
+  // detection first: the language entry of a detecting clip's context is written before the contexts are fed
+  std::vector<int> det_slot(nd), det_row(nd), det_idx(nd);
+  std::vector<float> det_lp((size_t)nd * n_lang), det_logit(lout.lang_logit ? (size_t)nd * n_lang : 0);
+  for (int i = 0; i < nd; ++i) { det_slot[i] = pl.slot[pl.detect[i]]; det_row[i] = pl.lang_row[pl.detect[i]]; }
+  if (nd > 0 && route == 0) {
+    enqueue_detect_prefill(batch, det_slot, d_ctx, det_row, lout.lang_logit != nullptr);  // (no host round trip: the kernel patches d_ctx)
+  } else if (nd > 0) {
+    detect_step_fed(batch, det_slot, det_idx.data(), det_lp.data(), lout.lang_logit ? det_logit.data() : nullptr);
+    for (int i = 0; i < nd; ++i) pl.ctx[det_row[i]] = cfg_.lang_tokens[det_idx[i]];
+  }
 
   if (route == 0) prefill_pass(pl.rows, n, pl.max_len, want_no_speech);
   else prefill_step_fed(batch, pl.slot, pl.len, pl.ctx, pl.row0, want_no_speech);
@@ -137,8 +192,18 @@ void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_
   h.off = d_off_; h.tok = d_tok_; h.n_out = d_nout_; h.transcribe = sot_seq_[2];
   h.tok_emb = tok_emb_; h.pos = dec_pos_; h.x = d_xdec_; h.d_model = d;
   if (want_no_speech) { h.no_speech = d_nospeech_; h.no_speech_clip = pf.nsp; }
+  if (lc) h.task_tok = pf.task_tok;
   launch_prefill_handover(h, s);
   HIP_CHECK(hipGetLastError());
+  if (nd > 0) {
+    if (route == 0) fetch_detected(nd, det_idx.data(), det_lp.data(), lout.lang_logit ? det_logit.data() : nullptr);
+    for (int i = 0; i < nd; ++i) {
+      const int b = det_slot[i];
+      if (lout.detected) lout.detected[b] = det_idx[i];
+      if (lout.lang_logprob) std::copy(det_lp.begin() + (size_t)i * n_lang, det_lp.begin() + (size_t)(i + 1) * n_lang, lout.lang_logprob + (size_t)b * n_lang);
+      if (lout.lang_logit) std::copy(det_logit.begin() + (size_t)i * n_lang, det_logit.begin() + (size_t)(i + 1) * n_lang, lout.lang_logit + (size_t)b * n_lang);
+    }
+  }
   if (want_no_speech && no_speech_out) {
     std::vector<float> v(n);
     HIP_CHECK(hipMemcpyAsync(v.data(), pf.nsp, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -150,6 +215,140 @@ void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_
       HIP_CHECK(hipMemcpyAsync(sot_logits_out + (size_t)pl.slot[c] * cfg_.n_vocab, pf.sot_logits + (size_t)c * ts_stride_, (size_t)cfg_.n_vocab * 4,
                                hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// ------------------------------------------------------------------------------ language detection
+namespace {
+// a PromptSpec for calls whose caller gave none: no clip is prompted
+struct NoPrompts {
+  std::vector<int> n;
+  IEngine::PromptSpec spec;
+  NoPrompts(int batch) : n((size_t)std::max(batch, 1), 0), spec{nullptr, 0, n.data()} {}
+};
+}  // namespace
+
+void Engine::require_lang_call(DecodeMode mode, const char* what) const {
+  if (mode < kDecodeTimestamps) throw std::runtime_error(std::string(what) + ": a language or task per clip exists in the timestamp modes only");
+  require_no_stream(what);
+  require_timestamp_vocab();
+}
+
+void Engine::check_lang_request(const LangSpec& lang, int batch) const {
+  const NoPrompts none(batch);
+  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, none.spec, &lang, false);
+}
+
+void Engine::ensure_lang_buffers() {
+  if (prefill_.lang_tok) return;
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  const int n_lang = (int)cfg_.lang_tokens.size();
+  if (n_lang > kLangMax) throw std::runtime_error("language list longer than " + std::to_string(kLangMax));
+  for (int t : cfg_.lang_tokens)
+    if (t < 0 || t >= cfg_.n_vocab) throw std::runtime_error("config: a language id lies outside the vocabulary");
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  DeviceArray<int> tok = device_array<int>(n_lang);
+  HIP_CHECK(hipMemcpy(tok, cfg_.lang_tokens.data(), (size_t)n_lang * 4, hipMemcpyHostToDevice));
+  prefill_.lang_tok = std::move(tok);
+}
+
+LangDetectParams Engine::detect_params(const float* x, int n_clips, bool want_logit) const {
+  LangDetectParams q{};
+  q.x = x; q.ln_w = dec_ln_w_; q.ln_b = dec_ln_b_; q.tok_emb = tok_emb_;
+  q.lang_tokens = prefill_.lang_tok; q.n_lang = (int)cfg_.lang_tokens.size();
+  q.d_model = cfg_.n_text_state; q.n_clips = n_clips; q.fallback_index = handle_lang_;
+  q.lang_logit = want_logit ? prefill_.lang_logit.get() : nullptr; q.lang_logprob = prefill_.lang_lp; q.lang_index = prefill_.lang_idx;
+  return q;
+}
+
+// Detection on the prefill route. The [sot] position of every slot of the batch goes through the layers of ONE existing decoder step
+// (offset 0, token sot, as reset_decode_state left them; openai-whisper's detect_language context, no prompt in front even for a
+// prompted clip) WITHOUT its vocabulary projection and WITHOUT advance_kernel, so the slots' final residual rows stand in d_xdec_;
+// the detection kernel reads the detecting slots' rows there and patches d_ctx, and the embedding launch puts x back to what the
+// reset left. Offsets, tokens and counters were never moved. The host is waited for once, for the upload of the slot table; nothing
+// waits between the detection and the context prefill that reads what it patched.
+// (Not the one-row prefill pass: that pass keeps attention and LayerNorm outputs in the 16-bit type, which measured 0.76 (bf16) and
+// 0.25 (half) of error in language logits whose smallest kept margin is 0.5 and 0.72, and it cost 2.1 ms against the 0.5 ms of a step.)
+void Engine::enqueue_detect_prefill(int batch, const std::vector<int>& slot, int* d_ctx, const std::vector<int>& lang_row, bool want_logit) {
+  const int nd = (int)slot.size();
+  hipStream_t s = stream();
+  PrefillScratch& pf = prefill_;
+  std::vector<int> tab((size_t)nd * 2);  // [slot | the context entry to patch]
+  for (int i = 0; i < nd; ++i) { tab[i] = slot[i]; tab[nd + i] = d_ctx ? lang_row[i] : 0; }
+  HIP_CHECK(hipMemcpyAsync(pf.det_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));  // (pageable source)
+  ensure_branch_streams(batch);
+  StepSpec spec{kDecodePlain};
+  spec.mask = 15 & ~4;  // no advance: offsets and tokens stay, x keeps the final residual
+  spec.feed = 1;        // no vocabulary projection
+  enqueue_decode_step(spec, batch, cfg_.n_text_ctx, nullptr, 0, nullptr, 0, nullptr);
+  LangDetectParams q = detect_params(d_xdec_, nd, want_logit);
+  q.x_row = pf.det_tab;
+  if (d_ctx) { q.ctx = d_ctx; q.lang_row = pf.det_tab + nd; }
+  launch_language_detect(q, s);
+  launch_embed(tok_emb_, dec_pos_, d_tok_, d_off_, d_xdec_, batch, cfg_.n_text_state, s);
+  HIP_CHECK(hipGetLastError());
+}
+
+void Engine::fetch_detected(int n, int* idx, float* lp, float* logit) {
+  const size_t nl = cfg_.lang_tokens.size();
+  hipStream_t s = stream();
+  HIP_CHECK(hipMemcpyAsync(idx, prefill_.lang_idx, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(lp, prefill_.lang_lp, n * nl * 4, hipMemcpyDeviceToHost, s));
+  if (logit) HIP_CHECK(hipMemcpyAsync(logit, prefill_.lang_logit, n * nl * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// The step-fed route's detection, the yardstick: one EXISTING decoder step at offset 0 (every slot of the batch feeds sot) with the
+// logits dump, the language entries of the dumped rows picked on the host by the definition (first maximum in list order, NaN
+// never wins; logsumexp over the entries that are not NaN; nothing finite: the handle's language, every value -inf).
+void Engine::detect_step_fed(int batch, const std::vector<int>& slot, int* idx, float* lp, float* logit) {
+  const int nd = (int)slot.size(), nl = (int)cfg_.lang_tokens.size(), nv = cfg_.n_vocab;
+  hipStream_t s = stream();
+  ensure_ts_logits();
+  std::vector<int> forced(batch, sot_seq_[0]);
+  DeviceArray<int> d_forced = device_array<int>(batch);
+  HIP_CHECK(hipMemcpyAsync(d_forced, forced.data(), (size_t)batch * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));  // (pageable source)
+  ensure_branch_streams(batch);
+  StepSpec spec{kDecodePlain};
+  spec.feed = 2;
+  enqueue_decode_step(spec, batch, cfg_.n_text_ctx, d_forced, 1, nullptr, 0, nullptr);
+  std::vector<float> row(nv);
+  for (int i = 0; i < nd; ++i) {
+    HIP_CHECK(hipMemcpyAsync(row.data(), d_ts_logits_ + (size_t)slot[i] * ts_stride_, (size_t)nv * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    float m = -INFINITY;
+    int best = -1;
+    bool any_finite = false;
+    for (int j = 0; j < nl; ++j) {
+      const float x = row[cfg_.lang_tokens[j]];
+      if (logit) logit[(size_t)i * nl + j] = x;
+      if (x > m) { m = x; best = j; }
+      any_finite = any_finite || std::isfinite(x);
+    }
+    float* out = lp + (size_t)i * nl;
+    if (best < 0 || !any_finite) {
+      idx[i] = handle_lang_;
+      std::fill(out, out + nl, -INFINITY);
+      continue;
+    }
+    idx[i] = best;
+    double sum = 0.0;
+    for (int j = 0; j < nl; ++j) {
+      const float x = row[cfg_.lang_tokens[j]];
+      if (x == x && m != INFINITY) sum += std::exp((double)x - (double)m);
+    }
+    for (int j = 0; j < nl; ++j) {
+      const float x = row[cfg_.lang_tokens[j]];
+      out[j] = x != x ? -INFINITY : m == INFINITY ? (x == INFINITY ? 0.f : -INFINITY) : (float)((double)x - ((double)m + std::log(sum)));
+    }
+  }
+  // back to what reset_decode_state left (prefill_step_fed, or the caller, starts from offset 0)
+  HIP_CHECK(hipMemsetAsync(d_off_, 0, (size_t)batch * 4, s));
+  HIP_CHECK(hipMemcpyAsync(d_tok_, forced.data(), (size_t)batch * 4, hipMemcpyHostToDevice, s));
+  launch_embed(tok_emb_, dec_pos_, d_tok_, d_off_, d_xdec_, batch, cfg_.n_text_state, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));  // (d_forced and forced leave scope)
 }
 
 // All context rows of the prompted clips through the decoder layers in one pass: the residual stream fp32 [rows][d], activations
@@ -310,9 +509,115 @@ void Engine::decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec
 void Engine::run_tokens_prompted(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
                                  const PromptSpec& prompts, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample) {
   if (mode < kDecodeTimestamps) throw std::runtime_error("prompted decode exists in the timestamp modes only");
-  (void)plan_prompts(cfg_, sot_seq_, std::max(batch, 0), prompts);  // a bad prompt fails before any GPU work
+  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, std::max(batch, 0), prompts, nullptr, false);  // a bad prompt fails before any GPU work
   const ScopedSet<const PromptSpec*> scope(prompt_, &prompts);
   run_tokens(mode, pcm, nullptr, 0, n_samples, batch, max_new, max_new_clip, ids, n_ids, scores, sample);
+}
+
+// ------------------------------------------------------------------------------ language and task per clip: entry points
+void Engine::run_tokens_lang(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
+                             const PromptSpec* prompts, const LangSpec& lang, int32_t* ids, int* n_ids, const ClipScores* scores,
+                             const LangResult& out) {
+  if (batch < 1) throw std::runtime_error("batch must be >= 1");
+  require_lang_call(mode, "run_tokens_lang");
+  if (mode == kDecodeSampled) throw std::runtime_error("run_tokens_lang: the sampled decode mode takes no language per clip");
+  const NoPrompts none(batch);
+  const PromptSpec& pr = prompts ? *prompts : none.spec;
+  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, pr, &lang, false);  // a bad request fails before any GPU work
+  const LangCall call{lang, out, false};
+  const ScopedSet<const PromptSpec*> scope(prompt_, &pr);
+  const ScopedSet<const LangCall*> lscope(lang_, &call);
+  run_tokens(mode, pcm, nullptr, 0, n_samples, batch, max_new, max_new_clip, ids, n_ids, scores, nullptr);
+}
+
+void Engine::detect_language_stage(int batch, const LangResult& out) {
+  require_lang_call(kDecodeTimestamps, "detect_language");
+  if (!out.detected) throw std::runtime_error("detect_language: no output array");
+  if (cfg_.lang_tokens.size() < 2) throw std::runtime_error("language detection needs a config with more than one language");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  if (batch < 1 || batch > cap_) throw std::runtime_error("detect_language: batch exceeds the encoded slots");
+  const int nl = (int)cfg_.lang_tokens.size();
+  reset_decode_state(batch);
+  std::vector<int> slot(batch), idx(batch);
+  for (int b = 0; b < batch; ++b) slot[b] = b;
+  std::vector<float> lp((size_t)batch * nl), logit(out.lang_logit ? (size_t)batch * nl : 0);
+  if (prefill_route() == 0) {
+    ensure_prefill_scratch(batch, cap_);
+    ensure_lang_buffers();
+    enqueue_detect_prefill(batch, slot, nullptr, slot, out.lang_logit != nullptr);
+    fetch_detected(batch, idx.data(), lp.data(), out.lang_logit ? logit.data() : nullptr);
+  } else {
+    detect_step_fed(batch, slot, idx.data(), lp.data(), out.lang_logit ? logit.data() : nullptr);
+  }
+  std::copy(idx.begin(), idx.end(), out.detected);
+  if (out.lang_logprob) std::copy(lp.begin(), lp.end(), out.lang_logprob);
+  if (out.lang_logit) std::copy(logit.begin(), logit.end(), out.lang_logit);
+}
+
+// front-end, encoder, detection: nothing is decoded
+void Engine::detect_language(const float* const* pcm, const int* n_samples, int batch, const LangResult& out) {
+  if (batch < 1) throw std::runtime_error("batch must be >= 1");
+  require_lang_call(kDecodeTimestamps, "detect_language");
+  if (!out.detected) throw std::runtime_error("detect_language: no output array");
+  if (cfg_.lang_tokens.size() < 2) throw std::runtime_error("language detection needs a config with more than one language");
+  HIP_CHECK(hipSetDevice(device_));
+  ensure_capacity(batch);
+  upload_pcm(pcm, n_samples, batch);
+  run_frontend(d_pcm_, (int)pcm_stride_, n_samples, batch, false, true);
+  run_encoder(batch);
+  detect_language_stage(batch, out);
+}
+
+void Engine::language_logprob_rows(const float* rows, int n, float* lang_logprob, int* lang_index, float* lang_logit) {
+  require_no_stream("language_logprob_rows");
+  if (!rows || n < 1 || !lang_logprob || !lang_index) throw std::runtime_error("language_logprob_rows: bad arguments");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  ensure_lang_buffers();
+  const size_t d = (size_t)cfg_.n_text_state, nl = cfg_.lang_tokens.size();
+  hipStream_t s = stream();
+  HIP_CHECK(hipStreamSynchronize(s));
+  DeviceArray<float> x = device_array<float>(n * d), lp = device_array<float>(n * nl), lg = device_array<float>(n * nl);
+  DeviceArray<int> ix = device_array<int>(n);
+  HIP_CHECK(hipMemcpy(x, rows, n * d * 4, hipMemcpyHostToDevice));
+  LangDetectParams q = detect_params(x, n, true);
+  q.lang_logit = lg; q.lang_logprob = lp; q.lang_index = ix;
+  launch_language_detect(q, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipMemcpy(lang_logprob, lp, n * nl * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(lang_index, ix, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (lang_logit) HIP_CHECK(hipMemcpy(lang_logit, lg, n * nl * 4, hipMemcpyDeviceToHost));
+}
+
+void Engine::prefill_contexts_stage(int batch, const PromptSpec* prompts, const LangSpec& lang, float* no_speech_logprob, float* sot_logits,
+                                    const LangResult& out) {
+  require_lang_call(kDecodeTimestamps, "prefill_contexts");
+  HIP_CHECK(hipSetDevice(device_));
+  if (batch < 1 || batch > cap_) throw std::runtime_error("prefill_contexts: batch exceeds the encoded slots");
+  const NoPrompts none(batch);
+  const PromptSpec& pr = prompts ? *prompts : none.spec;
+  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, pr, &lang, false);
+  const LangCall call{lang, out, false};
+  const ScopedSet<const LangCall*> lscope(lang_, &call);
+  reset_decode_state(batch);
+  prefill_prompts(batch, pr, no_speech_logprob != nullptr || sot_logits != nullptr, no_speech_logprob, sot_logits);
+}
+
+void Engine::decode_forced_lang(DecodeMode mode, int batch, const PromptSpec* prompts, const LangSpec& lang, const int32_t* forced, int n_forced,
+                                float* logits, int32_t* chosen, const ForcedScores* scores, const LangResult& out) {
+  require_lang_call(mode, "decode_forced_lang");
+  if (mode == kDecodeSampled) throw std::runtime_error("decode_forced_lang: not in the sampled decode mode");
+  if (scores && scores->logits0) throw std::runtime_error("decode_forced_lang: a clip behind a context has no row of decode offset 0");
+  if (batch < 1 || batch > cap_) throw std::runtime_error("decode_forced_lang: batch exceeds the encoded slots");
+  const NoPrompts none(batch);
+  const PromptSpec& pr = prompts ? *prompts : none.spec;
+  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, pr, &lang, true);
+  const LangCall call{lang, out, true};
+  const ScopedSet<const PromptSpec*> scope(prompt_, &pr);
+  const ScopedSet<const LangCall*> lscope(lang_, &call);
+  decode_forced(mode, batch, forced, n_forced, logits, chosen, scores, nullptr);
 }
 
 }  // inline namespace AXW_NS

@@ -49,6 +49,12 @@ class IEngine {
   // prompt conditioning (DESIGN.md "Prompt conditioning"): n_prompt[b] ids of clip b at ids + b * stride (text ids below eot and
   // timestamp ids; the last n_text_ctx / 2 - 1 are used), n_prompt[b] == 0: no prompt, the clip decodes as it does without this
   struct PromptSpec { const int32_t* ids; int stride; const int* n_prompt; };
+  // language and task per clip (DESIGN.md "Language and task per clip"): lang[b] >= 0 an index into the config's language list,
+  // -1 the handle's language, -2 detect it from the clip; task[b] 0 transcribe, 1 translate. A null array: all -1 / all 0.
+  struct LangSpec { const int* lang; const int* task; };
+  // what comes back per clip; every array may be null. detected [batch]: the language index the clip was decoded under (for explicit
+  // and default clips the index they were given); lang_logprob, lang_logit [batch][n_lang]: detecting clips only, the others' rows are 0
+  struct LangResult { int* detected; float* lang_logprob; float* lang_logit; };
   // full path, host PCM or device PCM; ids [batch][n_text_ctx], n_ids [batch]
   // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new; scores: kDecodeScored and
   // kDecodeSampled only; sample: kDecodeSampled only (and required there)
@@ -62,6 +68,8 @@ class IEngine {
   virtual std::string detokenize(const int32_t* ids, int n) const = 0;
   // detokenize + the reference's zh post-pass (Traditional -> Simplified, Whisper.cpp:231-236) when its OpenCC data files were found
   virtual std::string transcript(const int32_t* ids, int n) const = 0;
+  // the text of ids decoded under language `lang` (an index of the config's list): the zh pass follows that language, not the handle's
+  virtual std::string transcript_lang(const int32_t* ids, int n, int lang) const = 0;
   // stage-level
   virtual void compute_mel(const float* pcm, int n_samples, float* mel_out) = 0;
   virtual void encode_mel(const float* mel, int batch) = 0;
@@ -75,6 +83,23 @@ class IEngine {
   // decode_forced in a timestamp mode under prompts: the forced ids follow each clip's own context
   virtual void decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec& prompts, const int32_t* forced, int n_forced, float* logits,
                                       int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample = nullptr) = 0;
+  // ---- language and task per clip (engine_prefill.cpp). All of these exist in the timestamp modes only and refuse an open Stream*.
+  // run_tokens on host PCM under a language and task per clip; prompts may be null (no clip is prompted)
+  virtual void run_tokens_lang(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
+                               const PromptSpec* prompts, const LangSpec& lang, int32_t* ids, int* n_ids, const ClipScores* scores,
+                               const LangResult& out) = 0;
+  // front-end, encoder and detection only: out.detected [batch] (required), out.lang_logprob optional
+  virtual void detect_language(const float* const* pcm, const int* n_samples, int batch, const LangResult& out) = 0;
+  // after encode_mel: detection of slots [0, batch) (the decode state is reset and left reset)
+  virtual void detect_language_stage(int batch, const LangResult& out) = 0;
+  // the detection kernel alone on host residual rows [n][d]: lang_logprob [n][n_lang], lang_index [n], lang_logit [n][n_lang] or null
+  virtual void language_logprob_rows(const float* rows, int n, float* lang_logprob, int* lang_index, float* lang_logit) = 0;
+  // prefill_stage with a language and task per clip; prompts may be null
+  virtual void prefill_contexts_stage(int batch, const PromptSpec* prompts, const LangSpec& lang, float* no_speech_logprob, float* sot_logits,
+                                      const LangResult& out) = 0;
+  // decode_forced in a timestamp mode, EVERY clip handed over behind its own context [.., sot, language] with its task id
+  virtual void decode_forced_lang(DecodeMode mode, int batch, const PromptSpec* prompts, const LangSpec& lang, const int32_t* forced, int n_forced,
+                                  float* logits, int32_t* chosen, const ForcedScores* scores, const LangResult& out) = 0;
   // timestamp, scored and sampled mode: logits are the raw logits (before the rules), chosen the ids the rules choose; scores:
   // kDecodeScored and kDecodeSampled only; sample: kDecodeSampled only (and required there)
   virtual void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,

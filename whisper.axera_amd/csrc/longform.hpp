@@ -166,6 +166,14 @@ struct LongScoreOptions {
       if (!p.empty()) return true;
     return false;
   }
+  // Language and task per file (DESIGN.md "Language and task per clip"): file_lang / file_task (empty, or one entry per file of the
+  // WHOLE call): >= 0 a language index, -1 the handle's language, -2 detect it on the file's window at seek 0 (openai-whisper detects
+  // once on the first 30 s, also when that window is then skipped as silent; every later window uses the result); task 0
+  // transcribe, 1 translate. file_lang_out (or null): [files of the WHOLE call], the index every file was decoded under. All empty /
+  // null: the loop as it was.
+  std::vector<int> file_lang, file_task;
+  int* file_lang_out = nullptr;
+  bool per_file_language() const { return !file_lang.empty() || !file_task.empty() || file_lang_out; }
 };
 
 // one decoded window of AX_WHISPER_RunPCMLongWindows, in execution order

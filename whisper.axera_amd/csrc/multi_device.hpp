@@ -133,6 +133,39 @@ class DeviceGroup {
     });
   }
 
+  // run_tokens under a language and task per clip (E::run_tokens_lang; prompts may be null; L = E::LangSpec {lang [batch], task [batch]},
+  // R = E::LangResult {detected [batch], lang_logprob [batch][n_lang], lang_logit [batch][n_lang]}): requests and results travel with
+  // their clips.
+  template <typename P, typename L, typename R>
+  void run_tokens_lang(typename E::DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
+                       const P* prompts, const L& lang, int n_ctx, int n_lang, int32_t* ids, int* n_ids, const typename E::ClipScores* scores,
+                       const R& out) {
+    if (batch < 1) throw std::runtime_error("batch must be >= 1");
+    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
+    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
+      typename E::ClipScores sc{};
+      if (scores)
+        sc = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
+              from(scores->ended_eot, lo)};
+      P pr{};
+      if (prompts) pr = P{from(prompts->ids, (size_t)lo * prompts->stride), prompts->stride, from(prompts->n_prompt, lo)};
+      const L lg{from(lang.lang, lo), from(lang.task, lo)};
+      const R o{from(out.detected, lo), from(out.lang_logprob, (size_t)lo * n_lang), from(out.lang_logit, (size_t)lo * n_lang)};
+      e.run_tokens_lang(mode, pcm + lo, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), prompts ? &pr : nullptr, lg, ids + (size_t)lo * n_ctx,
+                        n_ids + lo, scores ? &sc : nullptr, o);
+    });
+  }
+
+  // Language detection alone (E::detect_language): front-end, encoder and detection of every clip on its shard's device.
+  template <typename R>
+  void detect_language(const float* const* pcm, const int* n_samples, int batch, int n_lang, const R& out) {
+    if (batch < 1) throw std::runtime_error("batch must be >= 1");
+    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
+    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
+      e.detect_language(pcm + lo, n_samples + lo, hi - lo, R{from(out.detected, lo), from(out.lang_logprob, (size_t)lo * n_lang), from(out.lang_logit, (size_t)lo * n_lang)});
+    });
+  }
+
   // Beam search (E::run_beam; R: the result arrays of beam.hpp, all per-clip with row stride n_ctx where they are rows): the clips
   // are split like run_tokens' — every hypothesis of a clip lives on the clip's device.
   template <typename R>

@@ -41,6 +41,10 @@ static void usage(const char* prog) {
           "      --condition_on_previous_text   (with --long) every window is prompted with the text kept before it (openai-whisper's\n"
           "                      default); a window kept at a temperature above 0.5 starts the prompt afresh\n"
           "      --prompt_ids 1,2,3   (with --long) the file's initial prompt, as token ids (there is no text encoder here)\n"
+          "      --detect_language   (with --timestamps or --long, not with --beam_size) detect the language from the first 30 s and\n"
+          "                      decode under it; prints Detected language: <code> (p = ...) before Result:. (--language keeps its\n"
+          "                      meaning: the handle's language, where an unknown code silently becomes zh; it has no \"auto\")\n"
+          "      --task T        transcribe or translate (with --timestamps or --long, not with --beam_size) [=transcribe]\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -98,9 +102,24 @@ static std::string mmss_ms(long ms) {
 }
 static std::string mmss(float t) { return mmss_ms((long)(t * 1000.f + 0.5f)); }
 
-// --timestamps: the clip decoded again in timestamp mode (beam_size > 1: by beam search, AX_WHISPER_RunPCMBatchBeam), split into
-// segments (AX_WHISPER_SplitSegments), one line each
-static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size) {
+// the language of the first 30 s (AX_WHISPER_DetectLanguage) and its "Detected language:" line; -1 on failure
+static int detect_and_print(AX_WHISPER_HANDLE h, const float* pcm, int n) {
+  const int n_lang = AX_WHISPER_GetConfigInt(h, "n_lang");
+  if (n_lang < 1) return -1;
+  std::vector<float> lp((size_t)n_lang);
+  const float* clips[1] = {pcm};
+  const int n30 = n < 480000 ? n : 480000;
+  int idx = -1;
+  if (AX_WHISPER_DetectLanguage(h, clips, &n30, 1, &idx, lp.data()) != 0 || idx < 0 || idx >= n_lang) return -1;
+  const char* code = AX_WHISPER_LanguageCode(h, idx);
+  printf("Detected language: %s (p = %.4f)\n", code ? code : "?", std::exp(lp[(size_t)idx]));
+  return idx;
+}
+
+// detect / task >= 0 (--detect_language, --task): the clip is decoded under the detected (else the handle's) language and that task
+// (AX_WHISPER_RunPCMBatchTimestampLang); then Result: is printed here too, from the same ids, and the text follows that language
+static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size, bool detect = false, int task = -1) {
+  const bool per_lang = detect || task >= 0;
   float* pcm = nullptr;
   int n = 0;
   if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
@@ -109,9 +128,29 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size) {
   int n_ids = 0;
   const float* clips[1] = {pcm};
   float sum_lp = 0.f, avg_lp = 0.f, nsp = 0.f;
-  int ended = 0;
-  const int rc = beam_size > 1 ? AX_WHISPER_RunPCMBatchBeam(h, clips, &n, 1, beam_size, 0, ids.data(), &n_ids, &sum_lp, &avg_lp, &nsp, &ended)
-                               : AX_WHISPER_RunPCMBatchTimestampTokens(h, clips, &n, 1, 0, nullptr, ids.data(), &n_ids);
+  int ended = 0, lang = -1;
+  int rc;
+  if (per_lang) {
+    if (detect && (lang = detect_and_print(h, pcm, n)) < 0) { free(pcm); return -1; }
+    const int tk = task > 0 ? 1 : 0;
+    std::vector<float> tok_lp(ids.size());
+    const int want = lang;
+    rc = AX_WHISPER_RunPCMBatchTimestampLang(h, clips, &n, 1, 0, nullptr, nullptr, 0, nullptr, &want, &tk, ids.data(), &n_ids, tok_lp.data(), &avg_lp,
+                                             &nsp, &ended, &lang, nullptr);
+    if (rc == 0) {
+      std::vector<int32_t> text_ids;
+      const int E = AX_WHISPER_GetConfigInt(h, "eot");
+      for (int i = 0; i < n_ids; ++i)
+        if (ids[i] < E) text_ids.push_back(ids[i]);
+      char* text = nullptr;
+      if (AX_WHISPER_TranscriptLang(h, text_ids.data(), (int)text_ids.size(), lang, &text) != 0) { free(pcm); return -1; }
+      printf("Result: %s\n", text ? text : "");
+      free(text);
+    }
+  } else {
+    rc = beam_size > 1 ? AX_WHISPER_RunPCMBatchBeam(h, clips, &n, 1, beam_size, 0, ids.data(), &n_ids, &sum_lp, &avg_lp, &nsp, &ended)
+                       : AX_WHISPER_RunPCMBatchTimestampTokens(h, clips, &n, 1, 0, nullptr, ids.data(), &n_ids);
+  }
   free(pcm);
   if (rc != 0) return -1;
   const float clip_s = n / 16000.f < 30.f ? n / 16000.f : 30.f;
@@ -124,7 +163,9 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size) {
     return -1;
   for (int k = 0; k < n_seg; ++k) {
     char* text = nullptr;
-    if (AX_WHISPER_Transcript(h, ids.data() + tb[k], te[k] - tb[k], &text) != 0) return -1;
+    if ((per_lang ? AX_WHISPER_TranscriptLang(h, ids.data() + tb[k], te[k] - tb[k], lang, &text)
+                  : AX_WHISPER_Transcript(h, ids.data() + tb[k], te[k] - tb[k], &text)) != 0)
+      return -1;
     printf("[%s --> %s] %s\n", mmss(st[k]).c_str(), mmss(en[k]).c_str(), text ? text : "");
     free(text);
   }
@@ -136,9 +177,13 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size) {
 // in their window's two numbers
 // temps non-empty: with temperature fallback (AX_WHISPER_RunPCMLongWindowsFallback): only kept attempts print
 // prompted: under prompt conditioning (AX_WHISPER_RunPCMLongWindowsPrompted; always scored)
+// detect / task >= 0: under a detected language (its line is printed here) or a task (AX_WHISPER_RunPCMLongWindowsLang; always
+// scored, prompts and fallback as asked for); the text then follows the file's language
 static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_speech_threshold, float logprob_threshold,
                     float compression_ratio_threshold, const std::vector<float>& temps, unsigned long long seed, bool prompted,
-                    const std::vector<int32_t>& prompt_ids, bool condition, std::string& text, std::string& lines) {
+                    const std::vector<int32_t>& prompt_ids, bool condition, std::string& text, std::string& lines, bool detect = false,
+                    int task = -1) {
+  const bool per_lang = detect || task >= 0;
   const bool fallback = !temps.empty();
   const size_t sw = fallback ? 7 : 3;  // floats per window score row
   float* pcm = nullptr;
@@ -153,7 +198,16 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
   int n_win = 0;
   const float* files[1] = {pcm};
   const int n_initial = (int)prompt_ids.size();
-  const int rc = prompted ? AX_WHISPER_RunPCMLongWindowsPrompted(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
+  int lang = -1;
+  const int tk = task > 0 ? 1 : 0;
+  if (detect && (lang = detect_and_print(h, pcm, n)) < 0) { free(pcm); return -1; }
+  const int want = lang;
+  const int rc = per_lang ? AX_WHISPER_RunPCMLongWindowsLang(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
+                                                             compression_ratio_threshold, fallback ? temps.data() : nullptr, (int)temps.size(),
+                                                             seed, nullptr, prompt_ids.data(), n_initial, &n_initial, condition ? 1 : 0,
+                                                             &want, &tk, cap, info.data(), ids.data(), score.data(), nullptr,
+                                                             &n_win, &lang)
+                 : prompted ? AX_WHISPER_RunPCMLongWindowsPrompted(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
                                                                  compression_ratio_threshold, fallback ? temps.data() : nullptr, (int)temps.size(),
                                                                  seed, nullptr, prompt_ids.data(), n_initial, &n_initial, condition ? 1 : 0, cap,
                                                                  info.data(), ids.data(), score.data(), nullptr, &n_win)
@@ -182,7 +236,8 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
     if (AX_WHISPER_SplitWindow(wi, w[4], T, E, w[2], n_max, st.data(), en.data(), tb.data(), te.data(), &n_seg, &adv) != 0) return -1;
     for (int s = 0; s < n_seg; ++s) {
       char* t = nullptr;
-      if (AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t) != 0) return -1;
+      if ((per_lang ? AX_WHISPER_TranscriptLang(h, wi + tb[s], te[s] - tb[s], lang, &t) : AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t)) != 0)
+        return -1;
       text += t ? t : "";
       // (absolute times in integer milliseconds: a float second loses the millisecond after a few hours)
       lines += "[" + mmss_ms(w[1] * 10L + (long)(st[s] * 1000.f + 0.5f)) + " --> " + mmss_ms(w[1] * 10L + (long)(en[s] * 1000.f + 0.5f)) + "] " + (t ? t : "") + tail + "\n";
@@ -195,7 +250,8 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
   bool timestamps = false, longform = false;
-  bool condition = false;
+  bool condition = false, detect = false;
+  std::string task_arg;
   std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -212,12 +268,13 @@ int main(int argc, char** argv) {
     if (val("wav", "-w", wav) || val("model_type", "-t", model_type) || val("model_path", "-p", model_path) ||
         val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg) ||
         val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg) ||
-        val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg))
+        val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg) || val("task", nullptr, task_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
     if (a == "--long") { longform = true; continue; }
     if (a == "--condition_on_previous_text") { condition = true; continue; }
+    if (a == "--detect_language") { detect = true; continue; }
     fprintf(stderr, "undefined option: %s\n", a.c_str());
     usage(argv[0]);
     return 1;
@@ -230,6 +287,17 @@ int main(int argc, char** argv) {
     if (*end || v < 1 || v > 8) { fprintf(stderr, "bad value: --beam_size %s (1 .. 8)\n", beam_arg.c_str()); return 1; }
     beam_size = (int)v;
     if (!timestamps || longform) { fprintf(stderr, "--beam_size needs --timestamps and does not go with --long\n"); usage(argv[0]); return 1; }
+  }
+  int task = -1;  // not given
+  if (!task_arg.empty()) {
+    if (task_arg != "transcribe" && task_arg != "translate") { fprintf(stderr, "bad value: --task %s (transcribe or translate)\n", task_arg.c_str()); return 1; }
+    task = task_arg == "translate" ? 1 : 0;
+  }
+  const bool per_lang = detect || task >= 0;
+  if (per_lang && ((!timestamps && !longform) || beam_size > 1)) {
+    fprintf(stderr, "--detect_language / --task need --timestamps or --long and do not go with --beam_size\n");
+    usage(argv[0]);
+    return 1;
   }
   // --compression_ratio_threshold turns temperature fallback on: attempts at 0, inc, 2 inc, .. 1.0 (inc 0.2 unless given)
   const bool fallback = !crt_arg.empty();
@@ -245,7 +313,7 @@ int main(int argc, char** argv) {
   }
   const bool prompted = condition || !prompt_ids.empty();
   if (prompted && !longform) { fprintf(stderr, "--condition_on_previous_text / --prompt_ids need --long\n"); usage(argv[0]); return 1; }
-  const bool scored = prompted || fallback || !nst_arg.empty() || !lpt_arg.empty();
+  const bool scored = prompted || fallback || !nst_arg.empty() || !lpt_arg.empty() || (per_lang && longform);
   if (scored && !longform) { fprintf(stderr, "--no_speech_threshold / --logprob_threshold need --long\n"); usage(argv[0]); return 1; }
   // one flag alone: no threshold on the average = no-speech alone decides (+inf); no threshold on no-speech = nothing is skipped
   // (NaN; as in openai-whisper, where the average only ever overrides a no-speech verdict) and the lines just carry their numbers
@@ -291,13 +359,26 @@ int main(int argc, char** argv) {
     t0 = std::chrono::steady_clock::now();
     std::string text, lines;
     if (run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompted, prompt_ids, condition,
-                 text, lines) != 0) {
+                 text, lines, detect, task) != 0) {
       printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
       AX_WHISPER_Uninit(handle);
       return -1;
     }
     t1 = std::chrono::steady_clock::now();
     printf("Result: %s\n%s", text.c_str(), lines.c_str());
+    printf("RTF: %.4f\n", std::chrono::duration<double>(t1 - t0).count() / duration);
+    AX_WHISPER_Uninit(handle);
+    return 0;
+  }
+
+  if (per_lang) {  // --timestamps under a language or task: one decode gives Result: and the segment lines
+    t0 = std::chrono::steady_clock::now();
+    if (print_segments(handle, wav.c_str(), 1, detect, task) != 0) {
+      printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
+      AX_WHISPER_Uninit(handle);
+      return -1;
+    }
+    t1 = std::chrono::steady_clock::now();
     printf("RTF: %.4f\n", std::chrono::duration<double>(t1 - t0).count() / duration);
     AX_WHISPER_Uninit(handle);
     return 0;
