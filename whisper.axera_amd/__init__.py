@@ -398,11 +398,46 @@ class Whisper:
         return self._take(out.value)
 
     # ---- additions ------------------------------------------------------------------------
-    def run_tokens_batch(self, clips, max_new: int = 0):
+    # what the clip-batch calls share: clips, lengths and budgets as the C ABI takes them; ids and scores as it fills them; the
+    # dict per clip they come back as; the arrays of a teacher-forced decode
+    @staticmethod
+    def _clip_args(clips, max_new_clip=None):
+        """-> (the clips as float32 arrays, which the pointers point into; B; pointers; lengths; per-clip budgets or None)"""
         clips = [_f32(c) for c in clips]
         B = len(clips)
         ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
         lens = (C.c_int * B)(*[len(c) for c in clips])
+        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        return clips, B, ptrs, lens, mc
+
+    def _score_buffers(self, B):
+        """-> ((ids, n_ids, token_logprob, avg_logprob, no_speech_logprob, ended_eot), the same six as C arguments, in that order)"""
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
+        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+        bufs = (ids, (C.c_int * B)(), lp, avg, nsp, (C.c_int * B)())
+        return bufs, (ids.ctypes.data_as(ip), bufs[1], lp.ctypes.data_as(fp), avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), bufs[5])
+
+    @staticmethod
+    def _clip_dicts(bufs):
+        ids, n, lp, avg, nsp, eot = bufs
+        return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
+                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(len(avg))]
+
+    def _forced_buffers(self, batch, forced, want_logits):
+        """-> ((logits [batch][n+1][n_vocab] or None, chosen, logprob [batch][n+1], no_speech_logprob [batch]), the forced ids and their
+        count n as C arguments, those four as C arguments)"""
+        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
+        n = f.shape[1]
+        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
+        ch = np.empty((batch, n + 1), dtype=np.int32)
+        lp = np.empty((batch, n + 1), dtype=np.float32)
+        nsp = np.empty(batch, dtype=np.float32)
+        return ((logits, ch, lp, nsp), (f.ctypes.data_as(ip), n),
+                (logits.ctypes.data_as(fp) if want_logits else None, ch.ctypes.data_as(ip), lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp)))
+
+    def run_tokens_batch(self, clips, max_new: int = 0):
+        clips, B, ptrs, lens, _ = self._clip_args(clips)
         ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
         n = (C.c_int * B)()
         self._check(self.L.AX_WHISPER_RunPCMBatchTokens(self.h, ptrs, lens, B, max_new, ids.ctypes.data_as(ip), n), "RunPCMBatchTokens")
@@ -414,11 +449,7 @@ class Whisper:
     # ---- segment timestamps (timestamp mode: prefix [sot, lang, transcribe], Whisper's timestamp rules on the GPU)
     def run_timestamp_tokens_batch(self, clips, max_new: int = 0, max_new_clip=None):
         """ids per clip, timestamp tokens included (AX_WHISPER_RunPCMBatchTimestampTokens)."""
-        clips = [_f32(c) for c in clips]
-        B = len(clips)
-        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
-        lens = (C.c_int * B)(*[len(c) for c in clips])
-        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        clips, B, ptrs, lens, mc = self._clip_args(clips, max_new_clip)
         ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
         n = (C.c_int * B)()
         self._check(self.L.AX_WHISPER_RunPCMBatchTimestampTokens(self.h, ptrs, lens, B, max_new, mc, ids.ctypes.data_as(ip), n),
@@ -429,52 +460,34 @@ class Whisper:
     def run_timestamp_scores_batch(self, clips, max_new: int = 0, max_new_clip=None):
         """Per clip a dict: ids (those of run_timestamp_tokens_batch), token_logprob (len(ids) + 1 values: one per id, then the
         decision that ended the clip), avg_logprob, no_speech_logprob, ended_eot (AX_WHISPER_RunPCMBatchTimestampScores)."""
-        clips = [_f32(c) for c in clips]
-        B = len(clips)
-        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
-        lens = (C.c_int * B)(*[len(c) for c in clips])
-        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
-        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
-        n = (C.c_int * B)()
-        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
-        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
-        eot = (C.c_int * B)()
-        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampScores(self.h, ptrs, lens, B, max_new, mc, ids.ctypes.data_as(ip), n, lp.ctypes.data_as(fp),
-                                                                 avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), eot), "RunPCMBatchTimestampScores")
-        return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
-                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+        clips, B, ptrs, lens, mc = self._clip_args(clips, max_new_clip)
+        bufs, out = self._score_buffers(B)
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampScores(self.h, ptrs, lens, B, max_new, mc, *out), "RunPCMBatchTimestampScores")
+        return self._clip_dicts(bufs)
 
     # ---- prompt conditioning (DESIGN.md "Prompt conditioning"): prompts are id lists, an empty one means no prompt
     @staticmethod
     def _prompt_args(prompts):
+        """-> (ids [batch][stride] as a C pointer, which keeps the array; stride; lengths); None: (None, 0, None), no prompts"""
+        if prompts is None:
+            return None, 0, None
         B = len(prompts)
         stride = max(1, max(len(p) for p in prompts))
         ids = np.zeros((B, stride), dtype=np.int32)
         for b, p in enumerate(prompts):
             ids[b, : len(p)] = np.asarray(p, dtype=np.int32)
-        return ids, stride, (C.c_int * B)(*[len(p) for p in prompts])
+        return ids.ctypes.data_as(ip), stride, (C.c_int * B)(*[len(p) for p in prompts])
 
     def run_timestamp_prompted_batch(self, clips, prompts, max_new: int = 0, max_new_clip=None):
         """run_timestamp_scores_batch with every clip conditioned on its prompt ids (AX_WHISPER_RunPCMBatchTimestampPrompted): the
         same dict per clip."""
-        clips = [_f32(c) for c in clips]
-        B = len(clips)
+        clips, B, ptrs, lens, mc = self._clip_args(clips, max_new_clip)
         if len(prompts) != B:
             raise ValueError("one prompt (possibly empty) per clip")
-        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
-        lens = (C.c_int * B)(*[len(c) for c in clips])
-        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
-        pid, stride, npr = self._prompt_args(prompts)
-        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
-        n = (C.c_int * B)()
-        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
-        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
-        eot = (C.c_int * B)()
-        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampPrompted(self.h, ptrs, lens, B, max_new, mc, pid.ctypes.data_as(ip), stride, npr,
-                                                                   ids.ctypes.data_as(ip), n, lp.ctypes.data_as(fp), avg.ctypes.data_as(fp),
-                                                                   nsp.ctypes.data_as(fp), eot), "RunPCMBatchTimestampPrompted")
-        return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
-                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+        bufs, out = self._score_buffers(B)
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampPrompted(self.h, ptrs, lens, B, max_new, mc, *self._prompt_args(prompts), *out),
+                    "RunPCMBatchTimestampPrompted")
+        return self._clip_dicts(bufs)
 
     def prefill_prompts(self, prompts, want_no_speech: bool = True, want_sot_logits: bool = False):
         """Stage level, after encode_mel of len(prompts) clips: reset + the prompted slots' context cached, `transcribe` about to be
@@ -484,7 +497,7 @@ class Whisper:
         pid, stride, npr = self._prompt_args(prompts)
         nsp = np.zeros(B, dtype=np.float32) if want_no_speech or want_sot_logits else None
         rows = np.zeros((B, self.n_vocab), dtype=np.float32) if want_sot_logits else None
-        self._check(self.L.AX_WHISPER_PrefillPrompts(self.h, B, pid.ctypes.data_as(ip), stride, npr, nsp.ctypes.data_as(fp) if nsp is not None else None,
+        self._check(self.L.AX_WHISPER_PrefillPrompts(self.h, B, pid, stride, npr, nsp.ctypes.data_as(fp) if nsp is not None else None,
                                                      rows.ctypes.data_as(fp) if want_sot_logits else None), "PrefillPrompts")
         return (nsp, rows) if want_sot_logits else nsp
 
@@ -499,17 +512,9 @@ class Whisper:
         """decode_forced_timestamp_scores under prompts (one non-empty prompt per clip): (logits [batch][n+1][n_vocab] or None, chosen,
         logprob [batch][n+1], no_speech_logprob [batch]); row i is the step that decides id i."""
         batch = len(prompts)
-        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
-        n = f.shape[1]
-        pid, stride, npr = self._prompt_args(prompts)
-        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
-        ch = np.empty((batch, n + 1), dtype=np.int32)
-        lp = np.empty((batch, n + 1), dtype=np.float32)
-        nsp = np.empty(batch, dtype=np.float32)
-        self._check(self.L.AX_WHISPER_DecodeForcedTimestampPrompted(self.h, batch, pid.ctypes.data_as(ip), stride, npr, f.ctypes.data_as(ip), n,
-                                                                    logits.ctypes.data_as(fp) if want_logits else None, ch.ctypes.data_as(ip),
-                                                                    lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp)), "DecodeForcedTimestampPrompted")
-        return logits, ch, lp, nsp
+        bufs, fin, out = self._forced_buffers(batch, forced, want_logits)
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampPrompted(self.h, batch, *self._prompt_args(prompts), *fin, *out), "DecodeForcedTimestampPrompted")
+        return bufs
 
     # ---- language and task per clip (DESIGN.md "Language and task per clip"): a language is a code of the config's list, None (the
     # handle's language) or "auto" (detect it from the clip); a task is "transcribe" or "translate"
@@ -553,10 +558,7 @@ class Whisper:
 
     def detect_language(self, clips):
         """Front-end, encoder and detection only (AX_WHISPER_DetectLanguage): per clip (code, lang_logprob [n_lang])."""
-        clips = [_f32(c) for c in clips]
-        B = len(clips)
-        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
-        lens = (C.c_int * B)(*[len(c) for c in clips])
+        clips, B, ptrs, lens, _ = self._clip_args(clips)
         idx = (C.c_int * B)()
         lp = np.zeros((B, self.n_lang), dtype=np.float32)
         self._check(self.L.AX_WHISPER_DetectLanguage(self.h, ptrs, lens, B, idx, lp.ctypes.data_as(fp)), "DetectLanguage")
@@ -584,43 +586,29 @@ class Whisper:
     def run_timestamp_lang_batch(self, clips, languages=None, tasks=None, prompts=None, max_new: int = 0, max_new_clip=None):
         """run_timestamp_prompted_batch under a language and task per clip (AX_WHISPER_RunPCMBatchTimestampLang): the same dict per
         clip plus language (the code the clip was decoded under) and, for detecting clips, lang_logprob [n_lang]."""
-        clips = [_f32(c) for c in clips]
-        B = len(clips)
+        clips, B, ptrs, lens, mc = self._clip_args(clips, max_new_clip)
         if prompts is not None and len(prompts) != B:
             raise ValueError("one prompt (possibly empty) per clip")
-        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
-        lens = (C.c_int * B)(*[len(c) for c in clips])
-        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
-        pid, stride, npr = self._prompt_args(prompts) if prompts is not None else (None, 0, None)
-        lang, task = self._lang_args(B, languages, tasks)
-        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
-        n = (C.c_int * B)()
-        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
-        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
-        eot = (C.c_int * B)()
+        bufs, out = self._score_buffers(B)
         lout = (C.c_int * B)()
         llp = np.zeros((B, self.n_lang), dtype=np.float32)
-        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampLang(self.h, ptrs, lens, B, max_new, mc, pid.ctypes.data_as(ip) if pid is not None else None, stride, npr,
-                                                               lang, task, ids.ctypes.data_as(ip), n, lp.ctypes.data_as(fp), avg.ctypes.data_as(fp),
-                                                               nsp.ctypes.data_as(fp), eot, lout, llp.ctypes.data_as(fp)), "RunPCMBatchTimestampLang")
-        out = []
-        for b in range(B):
-            o = dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
-                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b]), language=self.language_code(lout[b]))
+        self._check(self.L.AX_WHISPER_RunPCMBatchTimestampLang(self.h, ptrs, lens, B, max_new, mc, *self._prompt_args(prompts),
+                                                               *self._lang_args(B, languages, tasks), *out, lout, llp.ctypes.data_as(fp)),
+                    "RunPCMBatchTimestampLang")
+        res = self._clip_dicts(bufs)
+        for b, o in enumerate(res):
+            o["language"] = self.language_code(lout[b])
             if languages is not None and (languages[b] == "auto" or languages[b] == -2):
                 o["lang_logprob"] = llp[b].copy()
-            out.append(o)
-        return out
+        return res
 
     def prefill_contexts(self, batch: int, languages=None, tasks=None, prompts=None, want_no_speech: bool = True):
         """Stage level, after encode_mel of `batch` clips (AX_WHISPER_PrefillContexts): prefill_prompts under a language and task per
         clip. Returns (no_speech_logprob [batch] or None, language index [batch], lang_logprob [batch][n_lang])."""
-        pid, stride, npr = self._prompt_args(prompts) if prompts is not None else (None, 0, None)
-        lang, task = self._lang_args(batch, languages, tasks)
         nsp = np.zeros(batch, dtype=np.float32) if want_no_speech else None
         lout = (C.c_int * batch)()
         llp = np.zeros((batch, self.n_lang), dtype=np.float32)
-        self._check(self.L.AX_WHISPER_PrefillContexts(self.h, batch, pid.ctypes.data_as(ip) if pid is not None else None, stride, npr, lang, task,
+        self._check(self.L.AX_WHISPER_PrefillContexts(self.h, batch, *self._prompt_args(prompts), *self._lang_args(batch, languages, tasks),
                                                       nsp.ctypes.data_as(fp) if nsp is not None else None, None, lout, llp.ctypes.data_as(fp)),
                     "PrefillContexts")
         return nsp, np.array(lout[:], dtype=np.int32), llp
@@ -628,37 +616,21 @@ class Whisper:
     def decode_forced_timestamp_lang(self, forced, languages=None, tasks=None, prompts=None, want_logits: bool = True):
         """decode_forced_timestamp_prompted under a language and task per clip, every clip behind its own context: (logits
         [batch][n+1][n_vocab] or None, chosen, logprob [batch][n+1], no_speech_logprob [batch], language index [batch])."""
-        f = np.ascontiguousarray(forced, dtype=np.int32)
-        batch = f.shape[0]
-        f = f.reshape(batch, -1)
-        n = f.shape[1]
-        pid, stride, npr = self._prompt_args(prompts) if prompts is not None else (None, 0, None)
-        lang, task = self._lang_args(batch, languages, tasks)
-        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
-        ch = np.empty((batch, n + 1), dtype=np.int32)
-        lp = np.empty((batch, n + 1), dtype=np.float32)
-        nsp = np.empty(batch, dtype=np.float32)
+        batch = np.shape(forced)[0]
+        bufs, fin, out = self._forced_buffers(batch, forced, want_logits)
         lout = (C.c_int * batch)()
-        self._check(self.L.AX_WHISPER_DecodeForcedTimestampLang(self.h, batch, pid.ctypes.data_as(ip) if pid is not None else None, stride, npr, lang, task,
-                                                                f.ctypes.data_as(ip), n, logits.ctypes.data_as(fp) if want_logits else None,
-                                                                ch.ctypes.data_as(ip), lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp), lout),
-                    "DecodeForcedTimestampLang")
-        return logits, ch, lp, nsp, np.array(lout[:], dtype=np.int32)
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampLang(self.h, batch, *self._prompt_args(prompts), *self._lang_args(batch, languages, tasks),
+                                                                *fin, *out, lout), "DecodeForcedTimestampLang")
+        return (*bufs, np.array(lout[:], dtype=np.int32))
 
     def decode_forced_timestamp_scores(self, batch: int, forced, want_logits: bool = True, want_logits0: bool = True):
         """decode_forced_timestamps + (logprob [batch][n+1] of each step's chosen id, no_speech_logprob [batch], logits0
         [batch][n_vocab] or None: the raw row of decode offset 0). Returns (logits, chosen, logprob, no_speech_logprob, logits0)."""
-        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
-        n = f.shape[1]
-        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
+        bufs, fin, out = self._forced_buffers(batch, forced, want_logits)
         l0 = np.empty((batch, self.n_vocab), dtype=np.float32) if want_logits0 else None
-        ch = np.empty((batch, n + 1), dtype=np.int32)
-        lp = np.empty((batch, n + 1), dtype=np.float32)
-        nsp = np.empty(batch, dtype=np.float32)
-        self._check(self.L.AX_WHISPER_DecodeForcedTimestampScores(self.h, batch, f.ctypes.data_as(ip), n, logits.ctypes.data_as(fp) if want_logits else None,
-                                                                  ch.ctypes.data_as(ip), lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
-                                                                  l0.ctypes.data_as(fp) if want_logits0 else None), "DecodeForcedTimestampScores")
-        return logits, ch, lp, nsp, l0
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampScores(self.h, batch, *fin, *out, l0.ctypes.data_as(fp) if want_logits0 else None),
+                    "DecodeForcedTimestampScores")
+        return (*bufs, l0)
 
     def score_timestamp_rules(self, logits, histories):
         """The scored rules kernel alone: logits [batch][n_vocab], one id history per clip -> (chosen ids, their log-probabilities)."""
@@ -710,40 +682,22 @@ class Whisper:
     def decode_forced_timestamp_sampled(self, batch: int, forced, temperature, stream, seed: int = 0, want_logits: bool = True,
                                         want_logits0: bool = False):
         """decode_forced_timestamp_scores in sampled mode -> (logits, chosen, logprob, no_speech_logprob, logits0)."""
-        f = np.ascontiguousarray(forced, dtype=np.int32).reshape(batch, -1)
-        n = f.shape[1]
+        bufs, fin, out = self._forced_buffers(batch, forced, want_logits)
         t, st = self._sample_args(batch, temperature, stream)
-        logits = np.empty((batch, n + 1, self.n_vocab), dtype=np.float32) if want_logits else None
         l0 = np.empty((batch, self.n_vocab), dtype=np.float32) if want_logits0 else None
-        ch = np.empty((batch, n + 1), dtype=np.int32)
-        lp = np.empty((batch, n + 1), dtype=np.float32)
-        nsp = np.empty(batch, dtype=np.float32)
-        self._check(self.L.AX_WHISPER_DecodeForcedTimestampSampled(self.h, batch, f.ctypes.data_as(ip), n, t.ctypes.data_as(fp),
-                                                                   st.ctypes.data_as(C.POINTER(C.c_uint64)), int(seed),
-                                                                   logits.ctypes.data_as(fp) if want_logits else None, ch.ctypes.data_as(ip),
-                                                                   lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
-                                                                   l0.ctypes.data_as(fp) if want_logits0 else None), "DecodeForcedTimestampSampled")
-        return logits, ch, lp, nsp, l0
+        self._check(self.L.AX_WHISPER_DecodeForcedTimestampSampled(self.h, batch, *fin, t.ctypes.data_as(fp), st.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                                   int(seed), *out, l0.ctypes.data_as(fp) if want_logits0 else None),
+                    "DecodeForcedTimestampSampled")
+        return (*bufs, l0)
 
     def run_timestamp_sampled_batch(self, clips, temperature, stream, seed: int = 0, max_new: int = 0, max_new_clip=None):
         """run_timestamp_scores_batch in sampled mode (AX_WHISPER_RunPCMBatchTimestampSampled): the same dict per clip."""
-        clips = [_f32(c) for c in clips]
-        B = len(clips)
-        ptrs = (fp * B)(*[c.ctypes.data_as(fp) for c in clips])
-        lens = (C.c_int * B)(*[len(c) for c in clips])
-        mc = (C.c_int * B)(*[int(x) for x in max_new_clip]) if max_new_clip is not None else None
+        clips, B, ptrs, lens, mc = self._clip_args(clips, max_new_clip)
         t, st = self._sample_args(B, temperature, stream)
-        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
-        n = (C.c_int * B)()
-        lp = np.zeros((B, self.n_text_ctx), dtype=np.float32)
-        avg, nsp = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
-        eot = (C.c_int * B)()
+        bufs, out = self._score_buffers(B)
         self._check(self.L.AX_WHISPER_RunPCMBatchTimestampSampled(self.h, ptrs, lens, B, max_new, mc, t.ctypes.data_as(fp),
-                                                                  st.ctypes.data_as(C.POINTER(C.c_uint64)), int(seed), ids.ctypes.data_as(ip), n,
-                                                                  lp.ctypes.data_as(fp), avg.ctypes.data_as(fp), nsp.ctypes.data_as(fp), eot),
-                    "RunPCMBatchTimestampSampled")
-        return [dict(ids=ids[b, : n[b]].tolist(), token_logprob=lp[b, : n[b] + 1].copy(), avg_logprob=float(avg[b]),
-                     no_speech_logprob=float(nsp[b]), ended_eot=bool(eot[b])) for b in range(B)]
+                                                                  st.ctypes.data_as(C.POINTER(C.c_uint64)), int(seed), *out), "RunPCMBatchTimestampSampled")
+        return self._clip_dicts(bufs)
 
     # ---- beam search (DESIGN.md "Beam search")
     def run_beam_batch(self, clips, beam_size: int = 5, max_new: int = 0):
@@ -923,14 +877,14 @@ class Whisper:
                 rc = self.L.AX_WHISPER_RunPCMLongWindowsLang(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
                                                              temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed),
                                                              (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None,
-                                                             pid.ctypes.data_as(ip), stride, npr, int(bool(condition_on_previous_text)), lang, task, cap,
+                                                             pid, stride, npr, int(bool(condition_on_previous_text)), lang, task, cap,
                                                              info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
                                                              sc.ctypes.data_as(fp), wp.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nw), lout)
             elif prompted:
                 rc = self.L.AX_WHISPER_RunPCMLongWindowsPrompted(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
                                                                  temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed),
                                                                  (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None,
-                                                                 pid.ctypes.data_as(ip), stride, npr, int(bool(condition_on_previous_text)), cap,
+                                                                 pid, stride, npr, int(bool(condition_on_previous_text)), cap,
                                                                  info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
                                                                  sc.ctypes.data_as(fp), wp.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nw))
             elif fallback:

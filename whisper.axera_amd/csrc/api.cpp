@@ -256,11 +256,36 @@ AX_WHISPER_API int AX_WHISPER_RunFile(AX_WHISPER_HANDLE handle, const char* wav_
   return AX_WHISPER_RunPCM(handle, wav.mono.data(), (int)wav.mono.size(), result);
 }
 
+// What every clip-batch and stage-level function below does: fill a request (iengine.hpp) and make the one call that takes it.
+static Engine::DecodeRequest timestamp_request(Engine::DecodeMode mode, int max_new, const int* max_new_clip, const Engine::ClipScores* scores) {
+  Engine::DecodeRequest rq;
+  rq.mode = mode; rq.max_new = max_new; rq.max_new_clip = max_new_clip;
+  if (scores) rq.scores = *scores;
+  return rq;
+}
+
+// prompts: present when the caller gave prompt lengths
+static Engine::ClipContexts clip_contexts(const int32_t* prompt_ids, int prompt_stride, const int* n_prompt,
+                                          std::optional<Engine::LangSpec> lang = std::nullopt, Engine::LangResult lang_out = {}) {
+  Engine::ClipContexts c;
+  if (n_prompt) c.prompts = Engine::PromptSpec{prompt_ids, prompt_stride, n_prompt};
+  c.lang = lang; c.lang_out = lang_out;
+  return c;
+}
+
+static void run_request(axw::DeviceGroup<Engine>& g, const Engine::DecodeRequest& rq, const float* const* pcm, const int* num_samples, int batch,
+                        int32_t* ids, int* n_ids) {
+  const auto& cfg = g.primary().config();
+  g.run_tokens(rq, pcm, num_samples, batch, cfg.n_text_ctx, (int)cfg.lang_tokens.size(), ids, n_ids);
+}
+
 AX_WHISPER_API int AX_WHISPER_RunPCMBatchTokens(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
                                                 int batch, int max_new, int32_t* ids, int* n_ids) {
   if (!handle || !pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    g.run_tokens(Engine::kDecodePlain, pcm, num_samples, batch, max_new, nullptr, g.primary().config().n_text_ctx, ids, n_ids);
+    Engine::DecodeRequest rq;
+    rq.max_new = max_new;
+    run_request(g, rq, pcm, num_samples, batch, ids, n_ids);
   });
 }
 
@@ -268,7 +293,7 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampTokens(AX_WHISPER_HANDLE handl
                                                          int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) {
   if (!handle || !pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    g.run_tokens(Engine::kDecodeTimestamps, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids);
+    run_request(g, timestamp_request(Engine::kDecodeTimestamps, max_new, max_new_clip, nullptr), pcm, num_samples, batch, ids, n_ids);
   });
 }
 
@@ -283,7 +308,9 @@ AX_WHISPER_API int AX_WHISPER_RunDeviceBatchTokensRagged(AX_WHISPER_HANDLE handl
                                                          const int* max_new_clip, int32_t* ids, int* n_ids) {
   if (!handle || !d_pcm || !num_samples || !ids || !n_ids || batch < 1) return -1;
   return guarded(handle, [&](Engine& e) {
-    e.run_tokens(Engine::kDecodePlain, nullptr, d_pcm, stride, num_samples, batch, max_new, max_new_clip, ids, n_ids, nullptr);
+    Engine::DecodeRequest rq;
+    rq.max_new = max_new; rq.max_new_clip = max_new_clip;
+    e.run_tokens(rq, nullptr, d_pcm, stride, num_samples, batch, ids, n_ids);
   });
 }
 
@@ -296,7 +323,7 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatch(AX_WHISPER_HANDLE handle, const float*
     const int Tc = e.config().n_text_ctx;
     std::vector<int32_t> ids((size_t)batch * Tc);
     std::vector<int> n(batch);
-    g.run_tokens(Engine::kDecodePlain, pcm, num_samples, batch, 0, nullptr, Tc, ids.data(), n.data());
+    run_request(g, Engine::DecodeRequest{}, pcm, num_samples, batch, ids.data(), n.data());
     for (int b = 0; b < batch; ++b) results[b] = strdup(e.transcript(ids.data() + (size_t)b * Tc, n[b]).c_str());  // host only
   });
 }
@@ -437,13 +464,13 @@ AX_WHISPER_API int AX_WHISPER_ScanStored16(AX_WHISPER_HANDLE handle, int batch, 
 AX_WHISPER_API int AX_WHISPER_DecodeForced(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
                                            float* logits, int32_t* argmax_ids) {
   if (!handle || (n_forced > 0 && !forced)) return -1;
-  return guarded(handle, [&](Engine& e) { e.decode_forced(Engine::kDecodePlain, batch, forced, n_forced, logits, argmax_ids, nullptr); });
+  return guarded(handle, [&](Engine& e) { e.decode_forced(Engine::kDecodePlain, {}, batch, forced, n_forced, logits, argmax_ids, nullptr, nullptr); });
 }
 
 AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestamps(AX_WHISPER_HANDLE handle, int batch, const int32_t* forced, int n_forced,
                                                      float* logits, int32_t* chosen) {
   if (!handle || (n_forced > 0 && !forced)) return -1;
-  return guarded(handle, [&](Engine& e) { e.decode_forced(Engine::kDecodeTimestamps, batch, forced, n_forced, logits, chosen, nullptr); });
+  return guarded(handle, [&](Engine& e) { e.decode_forced(Engine::kDecodeTimestamps, {}, batch, forced, n_forced, logits, chosen, nullptr, nullptr); });
 }
 
 AX_WHISPER_API int AX_WHISPER_ApplyTimestampRules(AX_WHISPER_HANDLE handle, const float* logits, const int32_t* hist, const int* n_hist,
@@ -459,7 +486,7 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampScores(AX_WHISPER_HANDLE handl
   if (!handle || !pcm || !num_samples || !ids || !n_ids || !token_logprob || !avg_logprob || !no_speech_logprob || !ended_eot || batch < 1) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
-    g.run_tokens(Engine::kDecodeScored, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids, &scores);
+    run_request(g, timestamp_request(Engine::kDecodeScored, max_new, max_new_clip, &scores), pcm, num_samples, batch, ids, n_ids);
   });
 }
 
@@ -469,7 +496,7 @@ AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampScores(AX_WHISPER_HANDLE hand
   if (!handle || (n_forced > 0 && !forced)) return -1;
   return guarded(handle, [&](Engine& e) {
     const Engine::ForcedScores scores{logprob, no_speech_logprob, logits0};
-    e.decode_forced(Engine::kDecodeScored, batch, forced, n_forced, logits, chosen, &scores);
+    e.decode_forced(Engine::kDecodeScored, {}, batch, forced, n_forced, logits, chosen, &scores, nullptr);
   });
 }
 
@@ -732,7 +759,7 @@ AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampSampled(AX_WHISPER_HANDLE han
   return guarded(handle, [&](Engine& e) {
     const Engine::ForcedScores scores{logprob, no_speech_logprob, logits0};
     const Engine::SampleSpec sample{temperature, stream, seed};
-    e.decode_forced(Engine::kDecodeSampled, batch, forced, n_forced, logits, chosen, &scores, &sample);
+    e.decode_forced(Engine::kDecodeSampled, {}, batch, forced, n_forced, logits, chosen, &scores, &sample);
   });
 }
 
@@ -745,9 +772,9 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampSampled(AX_WHISPER_HANDLE hand
     return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
-    const Engine::SampleSpec sample{temperature, stream, seed};
-    g.run_tokens(Engine::kDecodeSampled, pcm, num_samples, batch, max_new, max_new_clip, g.primary().config().n_text_ctx, ids, n_ids, &scores,
-                 &sample);
+    Engine::DecodeRequest rq = timestamp_request(Engine::kDecodeSampled, max_new, max_new_clip, &scores);
+    rq.sample = Engine::SampleSpec{temperature, stream, seed};
+    run_request(g, rq, pcm, num_samples, batch, ids, n_ids);
   });
 }
 
@@ -821,16 +848,16 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampPrompted(AX_WHISPER_HANDLE han
     return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
-    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
-    g.run_tokens_prompted(Engine::kDecodeScored, pcm, num_samples, batch, max_new, max_new_clip, prompts, g.primary().config().n_text_ctx, ids,
-                          n_ids, &scores);
+    Engine::DecodeRequest rq = timestamp_request(Engine::kDecodeScored, max_new, max_new_clip, &scores);
+    rq.ctx = clip_contexts(prompt_ids, prompt_stride, n_prompt);
+    run_request(g, rq, pcm, num_samples, batch, ids, n_ids);
   });
 }
 
 AX_WHISPER_API int AX_WHISPER_PrefillPrompts(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids, int prompt_stride,
                                              const int* n_prompt, float* no_speech_logprob, float* sot_logits) {
   if (!handle || !n_prompt || prompt_stride < 0 || (prompt_stride > 0 && !prompt_ids) || batch < 1) return -1;
-  return guarded(handle, [&](Engine& e) { e.prefill_stage(batch, Engine::PromptSpec{prompt_ids, prompt_stride, n_prompt}, no_speech_logprob, sot_logits); });
+  return guarded(handle, [&](Engine& e) { e.prefill_stage(batch, clip_contexts(prompt_ids, prompt_stride, n_prompt), no_speech_logprob, sot_logits); });
 }
 
 AX_WHISPER_API int AX_WHISPER_GetSelfKV(AX_WHISPER_HANDLE handle, int slot, int n_rows, float* k_out, float* v_out) {
@@ -844,8 +871,8 @@ AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampPrompted(AX_WHISPER_HANDLE ha
   if (!handle || !n_prompt || prompt_stride < 1 || !prompt_ids || (n_forced > 0 && !forced) || batch < 1) return -1;
   return guarded(handle, [&](Engine& e) {
     const Engine::ForcedScores scores{logprob, no_speech_logprob, nullptr};
-    e.decode_forced_prompted(Engine::kDecodeScored, batch, Engine::PromptSpec{prompt_ids, prompt_stride, n_prompt}, forced, n_forced, logits,
-                             chosen, &scores);
+    e.decode_forced(Engine::kDecodeScored, clip_contexts(prompt_ids, prompt_stride, n_prompt), batch, forced, n_forced, logits, chosen, &scores,
+                    nullptr);
   });
 }
 
@@ -869,7 +896,9 @@ AX_WHISPER_API int AX_WHISPER_DetectLanguage(AX_WHISPER_HANDLE handle, const flo
                                              int* lang_out, float* lang_logprob) {
   if (!handle || !pcm || !num_samples || !lang_out || batch < 1) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    g.detect_language(pcm, num_samples, batch, (int)g.primary().config().lang_tokens.size(), Engine::LangResult{lang_out, lang_logprob, nullptr});
+    Engine::ClipContexts out;
+    out.lang_out = {lang_out, lang_logprob, nullptr};
+    g.detect_language(pcm, num_samples, batch, (int)g.primary().config().lang_tokens.size(), out);
   });
 }
 
@@ -883,10 +912,9 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchTimestampLang(AX_WHISPER_HANDLE handle,
     return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     const Engine::ClipScores scores{token_logprob, avg_logprob, no_speech_logprob, ended_eot};
-    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
-    const auto& cfg = g.primary().config();
-    g.run_tokens_lang(Engine::kDecodeScored, pcm, num_samples, batch, max_new, max_new_clip, n_prompt ? &prompts : nullptr, Engine::LangSpec{lang, task},
-                      cfg.n_text_ctx, (int)cfg.lang_tokens.size(), ids, n_ids, &scores, Engine::LangResult{lang_out, lang_logprob, nullptr});
+    Engine::DecodeRequest rq = timestamp_request(Engine::kDecodeScored, max_new, max_new_clip, &scores);
+    rq.ctx = clip_contexts(prompt_ids, prompt_stride, n_prompt, Engine::LangSpec{lang, task}, {lang_out, lang_logprob, nullptr});
+    run_request(g, rq, pcm, num_samples, batch, ids, n_ids);
   });
 }
 
@@ -906,9 +934,8 @@ AX_WHISPER_API int AX_WHISPER_PrefillContexts(AX_WHISPER_HANDLE handle, int batc
                                               float* lang_logprob) {
   if (!handle || prompt_stride < 0 || (n_prompt && prompt_stride > 0 && !prompt_ids) || batch < 1) return -1;
   return guarded(handle, [&](Engine& e) {
-    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
-    e.prefill_contexts_stage(batch, n_prompt ? &prompts : nullptr, Engine::LangSpec{lang, task}, no_speech_logprob, sot_logits,
-                             Engine::LangResult{lang_out, lang_logprob, nullptr});
+    e.prefill_stage(batch, clip_contexts(prompt_ids, prompt_stride, n_prompt, Engine::LangSpec{lang, task}, {lang_out, lang_logprob, nullptr}),
+                    no_speech_logprob, sot_logits);
   });
 }
 
@@ -918,9 +945,8 @@ AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampLang(AX_WHISPER_HANDLE handle
   if (!handle || prompt_stride < 0 || (n_prompt && prompt_stride > 0 && !prompt_ids) || (n_forced > 0 && !forced) || batch < 1) return -1;
   return guarded(handle, [&](Engine& e) {
     const Engine::ForcedScores scores{logprob, no_speech_logprob, nullptr};
-    const Engine::PromptSpec prompts{prompt_ids, prompt_stride, n_prompt};
-    e.decode_forced_lang(Engine::kDecodeScored, batch, n_prompt ? &prompts : nullptr, Engine::LangSpec{lang, task}, forced, n_forced, logits, chosen,
-                         &scores, Engine::LangResult{lang_out, nullptr, nullptr});
+    e.decode_forced(Engine::kDecodeScored, clip_contexts(prompt_ids, prompt_stride, n_prompt, Engine::LangSpec{lang, task}, {lang_out, nullptr, nullptr}),
+                    batch, forced, n_forced, logits, chosen, &scores, nullptr);
   });
 }
 

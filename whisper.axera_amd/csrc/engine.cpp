@@ -752,19 +752,22 @@ void Engine::run_encoder(int batch, const int* d_slot_map) {
 }
 
 // ------------------------------------------------------------------------------ public entry points
-void Engine::run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
-                        int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample) {
+void Engine::run_tokens(const DecodeRequest& rq, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
+                        int32_t* ids, int* n_ids) {
+  const DecodeMode mode = rq.mode;
   if (batch < 1) throw std::runtime_error("batch must be >= 1");
   require_no_stream("run_tokens");
   if (mode < kDecodePlain || mode > kDecodeSampled) throw std::runtime_error("run_tokens: unknown decode mode");
-  if (scores && mode < kDecodeScored) throw std::runtime_error("run_tokens: scores need the scored or the sampled decode mode");
-  if ((mode == kDecodeSampled) != (sample != nullptr)) throw std::runtime_error("run_tokens: the sampled decode mode, and it alone, takes sample parameters");
+  if (rq.scores && mode < kDecodeScored) throw std::runtime_error("run_tokens: scores need the scored or the sampled decode mode");
+  if ((mode == kDecodeSampled) != rq.sample.has_value()) throw std::runtime_error("run_tokens: the sampled decode mode, and it alone, takes sample parameters");
+  if (rq.ctx.lang && mode == kDecodeSampled) throw std::runtime_error("run_tokens: the sampled decode mode takes no language per clip");
+  check_contexts(mode, rq.ctx, batch, false, "run_tokens");  // a bad request fails before any GPU work
   if (mode == kDecodeTimestamps) require_timestamp_vocab();
   if (mode >= kDecodeScored) require_scored_vocab();
   HIP_CHECK(hipSetDevice(device_));
   auto t0 = std::chrono::steady_clock::now();
   ensure_capacity(batch);
-  if (sample) upload_sample(*sample, batch);
+  if (rq.sample) upload_sample(*rq.sample, batch);
   hipStream_t s = stream();
   HIP_CHECK(hipEventRecord(ev_[0], s));
   if (pcm) {
@@ -776,7 +779,7 @@ void Engine::run_tokens(DecodeMode mode, const float* const* pcm, const float* d
   HIP_CHECK(hipEventRecord(ev_[1], s));
   run_encoder(batch);
   HIP_CHECK(hipEventRecord(ev_[2], s));
-  const int steps = greedy_loop(StepSpec{mode}, batch, max_new, max_new_clip);
+  const int steps = greedy_loop(StepSpec{mode}, batch, rq.max_new, rq.max_new_clip, rq.ctx);
   fetch_ids(batch, ids, n_ids);
   // stage timings (events 3/4 are reused by the poll; bracket decode with a fresh record)
   HIP_CHECK(hipEventRecord(ev_[3], s));
@@ -786,7 +789,7 @@ void Engine::run_tokens(DecodeMode mode, const float* const* pcm, const float* d
   (void)hipEventElapsedTime(&timings[2], ev_[2], ev_[3]);
   timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   timings[4] = (float)steps;
-  if (scores) fetch_scores(batch, n_ids, scores->token_logprob, scores->avg_logprob, scores->no_speech_logprob, scores->ended_eot);
+  if (rq.scores) fetch_scores(batch, n_ids, rq.scores->token_logprob, rq.scores->avg_logprob, rq.scores->no_speech_logprob, rq.scores->ended_eot);
 }
 
 // Whisper.cpp:231-236: zh transcripts pass through OpenCC's t2s.json. The reference resolves "t2s.json" (and the two
@@ -880,13 +883,19 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
   }
 }
 
-void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* argmax_ids,
-                           const ForcedScores* scores, const SampleSpec* sample) {
+void Engine::decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, const int32_t* forced, int n_forced, float* logits,
+                           int32_t* argmax_ids, const ForcedScores* scores, const SampleSpec* sample) {
   if (mode < kDecodePlain || mode > kDecodeSampled) throw std::runtime_error("decode_forced: unknown decode mode");
   if (scores && mode < kDecodeScored) throw std::runtime_error("decode_forced: scores need the scored or the sampled decode mode");
   if ((mode == kDecodeSampled) != (sample != nullptr)) throw std::runtime_error("decode_forced: the sampled decode mode, and it alone, takes sample parameters");
   const ForcedScores out = scores ? *scores : ForcedScores{};
   require_no_stream("decode_forced");
+  // behind a context: under a language spec EVERY clip is handed over behind one ([sot, language] alone is L = 2)
+  const bool behind = ctx.any(), force_context = ctx.lang.has_value();
+  if (ctx.lang && mode == kDecodeSampled) throw std::runtime_error("decode_forced: the sampled decode mode takes no language per clip");
+  if (behind && out.logits0) throw std::runtime_error("decode_forced: a clip behind a context has no row of decode offset 0");
+  if (behind && (batch < 1 || batch > cap_)) throw std::runtime_error("decode_forced: batch exceeds the encoded slots");
+  check_contexts(mode, ctx, batch, force_context, "decode_forced");
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_forced: batch exceeds the encoded slots");
@@ -914,30 +923,28 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
   if (sample) { upload_sample(*sample, batch); spec.sample = own_sample_; }
   if (n_forced) HIP_CHECK(hipMemcpy(d_forced, forced, (size_t)batch * n_forced * 4, hipMemcpyHostToDevice));
   bool done = false;
-  if (prompt_ && !tsm) throw std::runtime_error("decode_forced_prompted: prompted decode exists in the timestamp modes only");
   if (batch == 1 && !tsm && persistent_usable()) {
     if (run_persistent(cfg_.n_text_ctx, d_forced, n_forced, d_logits, d_arg) >= 0) { done = true; persistent_succeeded(); }
     else persistent_gave_up();
   }
   if (!done) reset_decode_state(batch);
   DeviceArray<int> d_base;
-  if (prompt_) {  // every clip's context is cached and `transcribe` about to be fed: the loop below starts at that step
+  if (behind) {  // every clip's context is cached and its task id about to be fed: the loop below starts at that step
     std::vector<int> base(batch);
     const int keep = cfg_.n_text_ctx / 2 - 1;
     for (int b = 0; b < batch; ++b) {
-      // (decode_forced_lang hands EVERY clip over behind a context: [sot, language] alone is L = 2)
-      if (prompt_->n_prompt[b] < 1 && !lang_) throw std::runtime_error("decode_forced_prompted: every clip needs a prompt");
-      const char* who = lang_ ? "decode_forced_lang" : "decode_forced_prompted";
-      base[b] = prompt_->n_prompt[b] < 1 ? 0 : std::min(prompt_->n_prompt[b], keep) + 1;  // L - 2
-      if (base[b] + 3 + n_forced > cfg_.n_text_ctx) throw std::runtime_error(std::string(who) + ": n_forced out of range");
+      const int n = ctx.prompts ? ctx.prompts->n_prompt[b] : 0;
+      if (n < 1 && !force_context) throw std::runtime_error("decode_forced: under prompts every clip needs a prompt");
+      base[b] = n < 1 ? 0 : std::min(n, keep) + 1;  // L - 2
+      if (base[b] + 3 + n_forced > cfg_.n_text_ctx) throw std::runtime_error("decode_forced: n_forced out of range behind the context of clip " + std::to_string(b));
     }
-    prefill_prompts(batch, *prompt_, scored);
+    prefill_prompts(batch, ctx, force_context, scored);
     d_base = device_array<int>(batch);
     HIP_CHECK(hipMemcpy(d_base, base.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
     spec.base = d_base;
   }
   if (!done) ensure_branch_streams(batch);
-  for (int st = prompt_ ? n_prefix - 1 : 0; !done && st < n_prefix + n_forced; ++st) {
+  for (int st = behind ? n_prefix - 1 : 0; !done && st < n_prefix + n_forced; ++st) {
     const int gi = st - (n_prefix - 1);
     float* lrow = (d_logits && gi >= 0) ? d_logits + (size_t)gi * nv : nullptr;
     enqueue_decode_step(spec, batch, cfg_.n_text_ctx, d_forced, n_forced, lrow, (long)rows * nv, d_arg);
@@ -951,7 +958,7 @@ void Engine::decode_forced(DecodeMode mode, int batch, const int32_t* forced, in
   HIP_CHECK(hipStreamSynchronize(s));
   if (out.logprob) HIP_CHECK(hipMemcpy(out.logprob, b_lp, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
   // (under a prompt no step visits decode offset 0: the value is the hand-over's, in the engine's own array)
-  if (out.no_speech_logprob) HIP_CHECK(hipMemcpy(out.no_speech_logprob, prompt_ ? d_nospeech_ : b_nsp.get(), (size_t)batch * 4, hipMemcpyDeviceToHost));
+  if (out.no_speech_logprob) HIP_CHECK(hipMemcpy(out.no_speech_logprob, behind ? d_nospeech_ : b_nsp.get(), (size_t)batch * 4, hipMemcpyDeviceToHost));
   if (out.logits0) HIP_CHECK(hipMemcpy(out.logits0, b_l0, (size_t)batch * nv * 4, hipMemcpyDeviceToHost));
   if (logits) HIP_CHECK(hipMemcpy(logits, d_logits, (size_t)batch * rows * nv * 4, hipMemcpyDeviceToHost));
   if (argmax_ids) HIP_CHECK(hipMemcpy(argmax_ids, d_arg, (size_t)batch * rows * 4, hipMemcpyDeviceToHost));
@@ -965,7 +972,7 @@ void Engine::decode_greedy(DecodeMode mode, int batch, int max_new, const int* m
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_greedy: batch exceeds the encoded slots");
   hipStream_t s = stream();
   HIP_CHECK(hipEventRecord(ev_[2], s));
-  const int steps = greedy_loop(StepSpec{mode}, batch, max_new, max_new_clip);
+  const int steps = greedy_loop(StepSpec{mode}, batch, max_new, max_new_clip, ClipContexts{});
   fetch_ids(batch, ids, n_ids);
   HIP_CHECK(hipEventRecord(ev_[3], s));
   HIP_CHECK(hipEventSynchronize(ev_[3]));

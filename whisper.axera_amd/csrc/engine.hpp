@@ -131,10 +131,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   ~Engine() override;
   Engine(const Engine&) = delete;
 
-  void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int max_new,
-                  const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample = nullptr) override;
-  void run_tokens_prompted(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                           const PromptSpec& prompts, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample = nullptr) override;
+  void run_tokens(const DecodeRequest& rq, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int32_t* ids,
+                  int* n_ids) override;
   std::string detokenize(const int32_t* ids, int n) const override;
   std::string transcript(const int32_t* ids, int n) const override;
   std::string transcript_lang(const int32_t* ids, int n, int lang) const override;
@@ -142,22 +140,13 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void compute_mel(const float* pcm, int n_samples, float* mel_out) override;
   void encode_mel(const float* mel, int batch) override;
   void get_cross_kv(int slot, float* k_out, float* v_out) override;
-  void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
-                     const ForcedScores* scores, const SampleSpec* sample = nullptr) override;
+  void decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
+                     const ForcedScores* scores, const SampleSpec* sample) override;
   void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) override;
-  void prefill_stage(int batch, const PromptSpec& prompts, float* no_speech_logprob, float* sot_logits) override;
-  void decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec& prompts, const int32_t* forced, int n_forced, float* logits,
-                              int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample = nullptr) override;
-  void run_tokens_lang(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                       const PromptSpec* prompts, const LangSpec& lang, int32_t* ids, int* n_ids, const ClipScores* scores,
-                       const LangResult& out) override;
+  void prefill_stage(int batch, const ClipContexts& ctx, float* no_speech_logprob, float* sot_logits) override;
   void detect_language(const float* const* pcm, const int* n_samples, int batch, const LangResult& out) override;
   void detect_language_stage(int batch, const LangResult& out) override;
   void language_logprob_rows(const float* rows, int n, float* lang_logprob, int* lang_index, float* lang_logit) override;
-  void prefill_contexts_stage(int batch, const PromptSpec* prompts, const LangSpec& lang, float* no_speech_logprob, float* sot_logits,
-                              const LangResult& out) override;
-  void decode_forced_lang(DecodeMode mode, int batch, const PromptSpec* prompts, const LangSpec& lang, const int32_t* forced, int n_forced,
-                          float* logits, int32_t* chosen, const ForcedScores* scores, const LangResult& out) override;
   void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) override;
   void timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
                        const SampleSpec* sample = nullptr) override;
@@ -259,22 +248,22 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows);  // upload + whole-file front-end
   void long_windows_to_slots(const int* files, const int* seeks, int count, bool want_ref_layout);
   void long_release();
-  int greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip = nullptr);
-  // prompt conditioning (engine_prefill.cpp). prompt_: the prompts of the call in progress (run_tokens_prompted,
-  // decode_forced_prompted), which greedy_loop / decode_forced hand to prefill_prompts after reset_decode_state
-  const PromptSpec* prompt_ = nullptr;
-  // no_speech_out / sot_logits_out (stage level; host [batch] / [batch][n_vocab], or null): the prompted slots' no-speech value and
-  // the raw logits row it was taken from; entries of unprompted slots are 0
-  void prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_speech, float* no_speech_out = nullptr, float* sot_logits_out = nullptr);
+  // ctx: what the clips decode behind (prefill_prompts after reset_decode_state); an empty one: nothing in front of the start sequence
+  int greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip, const ClipContexts& ctx);
+  // prompt conditioning and a language and task per clip (engine_prefill.cpp; DESIGN.md "Prompt conditioning", "Language and task per
+  // clip"). A call's contexts travel as an argument from its entry point to prefill_prompts, which plans them and brings every clip
+  // that gets one to "context cached, task id about to be fed". force_context: every clip gets a context (decode_forced under a
+  // language spec).
+  // no_speech_out / sot_logits_out (stage level; host [batch] / [batch][n_vocab], or null): the no-speech value of the slots behind a
+  // context and the raw logits row it was taken from; entries of the other slots are 0
+  void prefill_prompts(int batch, const ClipContexts& ctx, bool force_context, bool want_no_speech, float* no_speech_out = nullptr,
+                       float* sot_logits_out = nullptr);
   void prefill_pass(int rows, int n_clips, int max_len, bool want_no_speech);
-  // language and task per clip (DESIGN.md "Language and task per clip"). lang_: the request of the call in progress and where its
-  // results go, beside prompt_ (a call that sets lang_ also sets prompt_, to an empty PromptSpec where no clip is prompted);
-  // prefill_prompts plans the contexts over both. force_context: every clip gets a context (decode_forced_lang).
-  struct LangCall { LangSpec spec; LangResult out; bool force_context; };
-  const LangCall* lang_ = nullptr;
   int handle_lang_ = 0;  // index of the handle's language in the config's list
+  // what an entry point asks before any GPU work: the mode rules of ctx (timestamp modes; under a language spec no open stream) and
+  // the context plan of `batch` clips, which throws on a bad prompt, language or task
+  void check_contexts(DecodeMode mode, const ClipContexts& ctx, int batch, bool force_context, const char* what) const;
   void require_lang_call(DecodeMode mode, const char* what) const;  // timestamp modes, no open stream
-  void check_lang_request(const LangSpec& lang, int batch) const;   // throws what the context plan would throw, before any GPU work
   void ensure_lang_buffers();  // prefill_.lang_tok (+ the per-clip arrays, with ensure_prefill_scratch)
   LangDetectParams detect_params(const float* x, int n_clips, bool want_logit) const;
   // prefill route: the layers of one decoder step at offset 0 (no vocabulary projection, no advance) and the detection kernel on

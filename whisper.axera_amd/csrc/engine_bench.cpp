@@ -99,15 +99,15 @@ float Engine::bench_prefill(const std::string& what, int batch, int arg, int ite
   unsigned x = 12345u;
   for (auto& v : ids) { x = x * 1664525u + 1013904223u; v = (int32_t)((x >> 8) % (unsigned)cfg_.eot); }
   const std::vector<int> n_prompt(batch, P);
-  const PromptSpec ps{ids.data(), P, n_prompt.data()};
+  const ClipContexts ctx{PromptSpec{ids.data(), P, n_prompt.data()}};
   const ScopedSet<int> scope(prefill_force_, what == "prefill_pass" ? 0 : what == "prefill_step" ? 1 : -1);
   hipStream_t s = stream();
   reset_decode_state(batch);
-  prefill_prompts(batch, ps, true);  // warm: scratch, score arrays
+  prefill_prompts(batch, ctx, false, true);  // warm: scratch, score arrays
   return timed_ms(s, [&] {
     for (int i = 0; i < iters; ++i) {
       reset_decode_state(batch);
-      prefill_prompts(batch, ps, true);
+      prefill_prompts(batch, ctx, false, true);
     }
   });
 }

@@ -541,7 +541,7 @@ hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
 }
 
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.
-int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip) {
+int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int* max_new_clip, const ClipContexts& ctx) {
   const int Tc = cfg_.n_text_ctx;
   const int n_prefix = spec.mode != kDecodePlain ? 3 : 4;  // timestamp mode: no <|notimestamps|>, one more id fits the context
   if (max_new <= 0 || max_new > Tc - n_prefix) max_new = Tc - n_prefix;
@@ -572,7 +572,7 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
   }
   hipGraphExec_t g = step_graph(spec, batch, max_new);  // (a fresh multi-branch graph is probed with replays: before the state is set)
   reset_decode_state(batch, max_new_clip);
-  if (prompt_) prefill_prompts(batch, *prompt_, spec.mode >= kDecodeScored);  // prompted slots: context cached, `transcribe` next
+  if (ctx.any()) prefill_prompts(batch, ctx, false, spec.mode >= kDecodeScored);  // slots behind a context: it is cached, the task id next
   hipStream_t s = stream();
   const int total = std::min(Tc, 4 + max_new);
   const int kPoll = 8;  // steps between done-counter polls; at most 2*kPoll steps run past the last eot

@@ -90,7 +90,7 @@ inline float h16_bits_to_float(uint16_t bits) {
 #endif
 }
 
-// `slot` holds `value` until the guard leaves scope, then what it held before (a call's ambient argument: Engine::prompt_)
+// `slot` holds `value` until the guard leaves scope, then what it held before (a bench hook's route for its call: Engine::prefill_force_)
 template <class T> class ScopedSet {
  public:
   ScopedSet(T& slot, T value) : slot_(slot), old_(slot) { slot = value; }

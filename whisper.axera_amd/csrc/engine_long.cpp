@@ -136,10 +136,10 @@ void Engine::compute_mel_window(const float* pcm, int n_samples, int seek, float
 // (file, seek, attempt); a window that needs fallback and has attempts left does not advance, it is encoded and decoded again in
 // the next pass at the next temperature (one more log entry, kept = false on the one that failed).
 // opts->prompted(): prompt conditioning (DESIGN.md "Prompt conditioning"). Every file carries (all_ids, reset_since); a window's
-// prompt, the same for each of its attempts, goes to greedy_loop through prompt_, and carry_prompt runs after every kept window.
+// prompt, the same for each of its attempts, goes to greedy_loop in the pass's contexts, and carry_prompt runs after every kept window.
 // opts->per_file_language(): a language and task per file (DESIGN.md "Language and task per clip"). Every window of a pass carries
-// its file's language and task to greedy_loop through lang_; a detecting file asks for -2 on its first window (seek 0, attempt 0)
-// and for the index that came back on every window after it.
+// its file's language and task to greedy_loop in the same contexts; a detecting file asks for -2 on its first window (seek 0,
+// attempt 0) and for the index that came back on every window after it.
 void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                               const LongScoreOptions* opts, std::vector<LongWindow>& log) {
   if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
@@ -162,14 +162,14 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   // the language every file decodes under (-2: still to be detected) and its task
   std::vector<int> file_lang(per_lang ? n_files : 0, -1), file_task(per_lang ? n_files : 0, 0);
   if (per_lang) {
-    require_lang_call(spec.mode, "run_long_windows");
     for (const std::vector<int>* v : {&opts->file_lang, &opts->file_task})
       if (!v->empty() && (long)v->size() < (long)opts->file_base + n_files) throw std::runtime_error("long-form: fewer languages or tasks than files");
     for (int f = 0; f < n_files; ++f) {
       if (!opts->file_lang.empty()) file_lang[f] = opts->file_lang[(size_t)(opts->file_base + f)];
       if (!opts->file_task.empty()) file_task[f] = opts->file_task[(size_t)(opts->file_base + f)];
     }
-    check_lang_request(LangSpec{file_lang.data(), file_task.data()}, n_files);  // a bad request fails before any GPU work
+    // a bad request fails before any GPU work
+    check_contexts(spec.mode, ClipContexts{std::nullopt, LangSpec{file_lang.data(), file_task.data()}}, n_files, false, "run_long_windows");
     for (int f = 0; f < n_files; ++f) {
       if (file_lang[f] == -1) file_lang[f] = handle_lang_;
       // (a file without a window keeps this: the index it asked for, the handle's where it asked for detection)
@@ -198,8 +198,12 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   std::vector<PromptCarry> carry(prompted ? n_files : 0);
   for (int f = 0; prompted && f < n_files && !opts->initial_prompt_ids.empty(); ++f) carry[f].all_ids = opts->initial_prompt_ids[(size_t)(opts->file_base + f)];
   std::vector<int32_t> prompt_ids(prompted ? (size_t)S * keep : 0);
-  std::vector<int> n_prompt(prompted || per_lang ? S : 0, 0);  // (a call under lang_ names its prompts too: none)
+  std::vector<int> n_prompt(prompted ? S : 0, 0);
   std::vector<int> win_lang(per_lang ? S : 0), win_task(per_lang ? S : 0), win_lang_got(per_lang ? S : 0);
+  // what every pass decodes behind: the arrays above, filled per pass
+  ClipContexts ctx;
+  if (prompted) ctx.prompts = PromptSpec{prompt_ids.data(), keep, n_prompt.data()};
+  if (per_lang) { ctx.lang = LangSpec{win_lang.data(), win_task.data()}; ctx.lang_out.detected = win_lang_got.data(); }
   int next_file = 0, steps = 0;
   for (int pass = 0; max_passes <= 0 || pass < max_passes; ++pass) {
     // finished files leave, the others move up, waiting files take the free places
@@ -232,25 +236,13 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
         std::copy(c.all_ids.end() - n, c.all_ids.end(), prompt_ids.begin() + (size_t)i * keep);
       }
     }
-    if (per_lang) {
-      for (int i = 0; i < A; ++i) { win_lang[i] = file_lang[files[i]]; win_task[i] = file_task[files[i]]; }
-      const PromptSpec ps{prompt_ids.data(), keep, n_prompt.data()};
-      const LangCall call{LangSpec{win_lang.data(), win_task.data()}, LangResult{win_lang_got.data(), nullptr, nullptr}, false};
-      const ScopedSet<const PromptSpec*> scope(prompt_, &ps);
-      const ScopedSet<const LangCall*> lscope(lang_, &call);
-      steps += greedy_loop(spec, A, max_new, nullptr);
-      for (int i = 0; i < A; ++i) {
-        const int f = files[i];
-        if (file_lang[f] != -2) continue;
-        file_lang[f] = win_lang_got[i];  // detected once, on the window at seek 0; every later window of the file uses it
-        if (opts->file_lang_out) opts->file_lang_out[opts->file_base + f] = file_lang[f];
-      }
-    } else if (prompted) {
-      const PromptSpec ps{prompt_ids.data(), keep, n_prompt.data()};
-      const ScopedSet<const PromptSpec*> scope(prompt_, &ps);
-      steps += greedy_loop(spec, A, max_new, nullptr);
-    } else {
-      steps += greedy_loop(spec, A, max_new, nullptr);
+    for (int i = 0; per_lang && i < A; ++i) { win_lang[i] = file_lang[files[i]]; win_task[i] = file_task[files[i]]; }
+    steps += greedy_loop(spec, A, max_new, nullptr, ctx);
+    for (int i = 0; per_lang && i < A; ++i) {
+      const int f = files[i];
+      if (file_lang[f] != -2) continue;
+      file_lang[f] = win_lang_got[i];  // detected once, on the window at seek 0; every later window of the file uses it
+      if (opts->file_lang_out) opts->file_lang_out[opts->file_base + f] = file_lang[f];
     }
     fetch_ids(A, ids.data(), n_ids.data());
     if (opts) fetch_scores(A, n_ids.data(), nullptr, avg.data(), nsp.data(), nullptr);

@@ -1,7 +1,9 @@
 // engine_prefill.cpp — axw::Engine: prompt conditioning (DESIGN.md "Prompt conditioning"). prefill_prompts() is the ONE place a
 // prompt enters the engine: between reset_decode_state and the first decoder step it brings every prompted slot to the state
 // "context [sot_prev, prompt, sot, language] cached, `transcribe` about to be fed at offset L = P + 3", after which the existing
-// steps (logits, rules, advance) run unchanged. Slots without a prompt are not touched.
+// steps (logits, rules, advance) run unchanged. Slots without a prompt are not touched. What it works on is its argument: the
+// ClipContexts of the call (iengine.hpp), handed down from the entry point (run_tokens, decode_forced, prefill_stage, the long-form
+// loop) through greedy_loop; the engine keeps no state of a call in progress.
 // Two routes lead to that state: the prefill pass (decode_prefill.hip + the encoder's GEMM / LayerNorm, all rows at once) and the
 // step-fed route (AX_WHISPER_PREFILL=step: one existing decoder step per position; the yardstick for error and time).
 // A language and task per clip (DESIGN.md "Language and task per clip") is the same mechanism: the context [sot, language] is the
@@ -27,13 +29,13 @@ struct PromptPlan {
 };
 }  // namespace
 
-// The context plan of a call. prompts.n_prompt[b] ids of clip b at prompts.ids + b * prompts.stride, truncated to their last
-// n_text_ctx / 2 - 1 (openai-whisper); lang (or null): the language and task of every clip. A clip gets a context
+// The context plan of a call. pr (or null: no clip is prompted): pr->n_prompt[b] ids of clip b at pr->ids + b * pr->stride, truncated
+// to their last n_text_ctx / 2 - 1 (openai-whisper); lang (or null): the language and task of every clip. A clip gets a context
 // ([sot_prev, prompt] if prompted) + [sot, language] when it is prompted, detects, asks for another language than the handle's or
 // another task than transcribe (or when force says so); without `lang` this is exactly the prompted clips of the call.
-static PromptPlan plan_contexts(const ModelConfig& cfg, const int* sot_seq, int handle_lang, int batch, const IEngine::PromptSpec& pr,
+static PromptPlan plan_contexts(const ModelConfig& cfg, const int* sot_seq, int handle_lang, int batch, const IEngine::PromptSpec* pr,
                                 const IEngine::LangSpec* lang, bool force) {
-  if (!pr.n_prompt) throw std::runtime_error("prefill_prompts: no prompt lengths");
+  if (pr && !pr->n_prompt) throw std::runtime_error("prefill_prompts: no prompt lengths");
   const int keep = cfg.n_text_ctx / 2 - 1, ts_begin = cfg.no_timestamps + 1, n_lang = (int)cfg.lang_tokens.size();
   int sot_prev = -1, translate = -1;
   {
@@ -42,12 +44,12 @@ static PromptPlan plan_contexts(const ModelConfig& cfg, const int* sot_seq, int 
     const auto tr = cfg.ints.find("translate");
     if (tr != cfg.ints.end() && tr->second >= 0 && tr->second < cfg.n_vocab) translate = (int)tr->second;
   }
-  if (!lang && sot_prev < 0) throw std::runtime_error("prompted decode needs a sot_prev id inside the vocabulary");
+  if (pr && !lang && sot_prev < 0) throw std::runtime_error("prompted decode needs a sot_prev id inside the vocabulary");
   PromptPlan pl;
   pl.lang_index.assign(batch, handle_lang);
   for (int b = 0; b < batch; ++b) {
-    const int n = pr.n_prompt[b];
-    if (n < 0 || n > pr.stride) throw std::runtime_error("prefill_prompts: prompt length " + std::to_string(n) + " of clip " + std::to_string(b) + " out of range");
+    const int n = pr ? pr->n_prompt[b] : 0;
+    if (pr && (n < 0 || n > pr->stride)) throw std::runtime_error("prefill_prompts: prompt length " + std::to_string(n) + " of clip " + std::to_string(b) + " out of range");
     const int lg = lang && lang->lang ? lang->lang[b] : -1, task = lang && lang->task ? lang->task[b] : 0;
     if (lg < -2 || lg >= n_lang) throw std::runtime_error("language index " + std::to_string(lg) + " of clip " + std::to_string(b) + " is outside [-2, " + std::to_string(n_lang) + ")");
     if (task != 0 && task != 1) throw std::runtime_error("task " + std::to_string(task) + " of clip " + std::to_string(b) + " is neither 0 (transcribe) nor 1 (translate)");
@@ -58,10 +60,10 @@ static PromptPlan plan_contexts(const ModelConfig& cfg, const int* sot_seq, int 
     int P = 0;
     const int32_t* src = nullptr;
     if (n > 0) {
-      if (!pr.ids) throw std::runtime_error("prefill_prompts: no prompt ids");
+      if (!pr->ids) throw std::runtime_error("prefill_prompts: no prompt ids");
       if (sot_prev < 0) throw std::runtime_error("prompted decode needs a sot_prev id inside the vocabulary");
       P = std::min(n, keep);
-      src = pr.ids + (size_t)b * pr.stride + (n - P);
+      src = pr->ids + (size_t)b * pr->stride + (n - P);
       for (int i = 0; i < P; ++i)
         if (src[i] < 0 || src[i] >= cfg.n_vocab || (src[i] >= cfg.eot && src[i] < ts_begin))
           throw std::runtime_error("prefill_prompts: id " + std::to_string(src[i]) + " of clip " + std::to_string(b) + " is neither text nor a timestamp");
@@ -141,12 +143,16 @@ void Engine::ensure_prefill_scratch(int rows, int clips) {
   }
 }
 
-void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_speech, float* no_speech_out, float* sot_logits_out) {
+static const IEngine::PromptSpec* or_null(const std::optional<IEngine::PromptSpec>& o) { return o ? &*o : nullptr; }
+static const IEngine::LangSpec* or_null(const std::optional<IEngine::LangSpec>& o) { return o ? &*o : nullptr; }
+
+void Engine::prefill_prompts(int batch, const ClipContexts& ctx, bool force_context, bool want_no_speech, float* no_speech_out,
+                             float* sot_logits_out) {
   if (batch < 1 || batch > cap_) throw std::runtime_error("prefill_prompts: batch exceeds the slots");
-  const LangCall* lc = lang_;
-  PromptPlan pl = plan_contexts(cfg_, sot_seq_, handle_lang_, batch, prompts, lc ? &lc->spec : nullptr, lc && lc->force_context);
+  const bool per_lang = ctx.lang.has_value();
+  PromptPlan pl = plan_contexts(cfg_, sot_seq_, handle_lang_, batch, or_null(ctx.prompts), or_null(ctx.lang), force_context);
   const int n_lang = (int)cfg_.lang_tokens.size();
-  const LangResult lout = lc ? lc->out : LangResult{};
+  const LangResult lout = per_lang ? ctx.lang_out : LangResult{};
   for (int b = 0; no_speech_out && b < batch; ++b) no_speech_out[b] = 0.f;
   if (sot_logits_out) std::fill(sot_logits_out, sot_logits_out + (size_t)batch * cfg_.n_vocab, 0.f);
   if (lout.lang_logprob) std::fill(lout.lang_logprob, lout.lang_logprob + (size_t)batch * n_lang, 0.f);
@@ -159,7 +165,7 @@ void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_
   const int d = cfg_.n_text_state;
   hipStream_t s = stream();
   ensure_prefill_scratch(pl.rows, cap_);
-  if (lc) ensure_lang_buffers();
+  if (per_lang) ensure_lang_buffers();
   PrefillScratch& pf = prefill_;
   int *d_ctx = pf.row_tab, *d_row_pos = d_ctx + pl.rows, *d_row_slot = d_row_pos + pl.rows;
   int *d_row0 = pf.clip_tab, *d_len = d_row0 + n, *d_slot = d_len + n, *d_sot_row = d_slot + n;
@@ -170,7 +176,7 @@ void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_
   HIP_CHECK(hipMemcpyAsync(d_len, pl.len.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_slot, pl.slot.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_sot_row, pl.sot_row.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-  if (lc) HIP_CHECK(hipMemcpyAsync(pf.task_tok, pl.task_tok.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  if (per_lang) HIP_CHECK(hipMemcpyAsync(pf.task_tok, pl.task_tok.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipStreamSynchronize(s));  // (pageable sources)
 
   // detection first: the language entry of a detecting clip's context is written before the contexts are fed
@@ -192,7 +198,7 @@ void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_
   h.off = d_off_; h.tok = d_tok_; h.n_out = d_nout_; h.transcribe = sot_seq_[2];
   h.tok_emb = tok_emb_; h.pos = dec_pos_; h.x = d_xdec_; h.d_model = d;
   if (want_no_speech) { h.no_speech = d_nospeech_; h.no_speech_clip = pf.nsp; }
-  if (lc) h.task_tok = pf.task_tok;
+  if (per_lang) h.task_tok = pf.task_tok;
   launch_prefill_handover(h, s);
   HIP_CHECK(hipGetLastError());
   if (nd > 0) {
@@ -218,24 +224,17 @@ void Engine::prefill_prompts(int batch, const PromptSpec& prompts, bool want_no_
 }
 
 // ------------------------------------------------------------------------------ language detection
-namespace {
-// a PromptSpec for calls whose caller gave none: no clip is prompted
-struct NoPrompts {
-  std::vector<int> n;
-  IEngine::PromptSpec spec;
-  NoPrompts(int batch) : n((size_t)std::max(batch, 1), 0), spec{nullptr, 0, n.data()} {}
-};
-}  // namespace
-
 void Engine::require_lang_call(DecodeMode mode, const char* what) const {
   if (mode < kDecodeTimestamps) throw std::runtime_error(std::string(what) + ": a language or task per clip exists in the timestamp modes only");
   require_no_stream(what);
   require_timestamp_vocab();
 }
 
-void Engine::check_lang_request(const LangSpec& lang, int batch) const {
-  const NoPrompts none(batch);
-  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, none.spec, &lang, false);
+void Engine::check_contexts(DecodeMode mode, const ClipContexts& ctx, int batch, bool force_context, const char* what) const {
+  if (!ctx.any()) return;
+  if (ctx.lang) require_lang_call(mode, what);
+  else if (mode < kDecodeTimestamps) throw std::runtime_error(std::string(what) + ": prompted decode exists in the timestamp modes only");
+  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, std::max(batch, 0), or_null(ctx.prompts), or_null(ctx.lang), force_context);
 }
 
 void Engine::ensure_lang_buffers() {
@@ -488,48 +487,18 @@ void Engine::get_self_kv(int slot, int n_rows, float* k_out, float* v_out) {
   }
 }
 
-// stage level: after encode_mel, the decode state of slots [0, batch) as a prompted greedy loop finds it before its first step
-void Engine::prefill_stage(int batch, const PromptSpec& prompts, float* no_speech_logprob, float* sot_logits) {
+// stage level: after encode_mel, the decode state of slots [0, batch) as a greedy loop under ctx finds it before its first step
+void Engine::prefill_stage(int batch, const ClipContexts& ctx, float* no_speech_logprob, float* sot_logits) {
   require_no_stream("prefill_prompts");
   require_timestamp_vocab();
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("prefill_prompts: batch exceeds the encoded slots");
+  check_contexts(kDecodeTimestamps, ctx, batch, false, "prefill_prompts");
   reset_decode_state(batch);
-  prefill_prompts(batch, prompts, no_speech_logprob != nullptr || sot_logits != nullptr, no_speech_logprob, sot_logits);
+  prefill_prompts(batch, ctx, false, no_speech_logprob != nullptr || sot_logits != nullptr, no_speech_logprob, sot_logits);
 }
 
-void Engine::decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec& prompts, const int32_t* forced, int n_forced, float* logits,
-                                    int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample) {
-  if (mode < kDecodeTimestamps) throw std::runtime_error("prompted decode exists in the timestamp modes only");
-  if (scores && scores->logits0) throw std::runtime_error("decode_forced_prompted: a prompted clip has no row of decode offset 0");
-  const ScopedSet<const PromptSpec*> scope(prompt_, &prompts);
-  decode_forced(mode, batch, forced, n_forced, logits, chosen, scores, sample);
-}
-
-void Engine::run_tokens_prompted(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                                 const PromptSpec& prompts, int32_t* ids, int* n_ids, const ClipScores* scores, const SampleSpec* sample) {
-  if (mode < kDecodeTimestamps) throw std::runtime_error("prompted decode exists in the timestamp modes only");
-  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, std::max(batch, 0), prompts, nullptr, false);  // a bad prompt fails before any GPU work
-  const ScopedSet<const PromptSpec*> scope(prompt_, &prompts);
-  run_tokens(mode, pcm, nullptr, 0, n_samples, batch, max_new, max_new_clip, ids, n_ids, scores, sample);
-}
-
-// ------------------------------------------------------------------------------ language and task per clip: entry points
-void Engine::run_tokens_lang(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                             const PromptSpec* prompts, const LangSpec& lang, int32_t* ids, int* n_ids, const ClipScores* scores,
-                             const LangResult& out) {
-  if (batch < 1) throw std::runtime_error("batch must be >= 1");
-  require_lang_call(mode, "run_tokens_lang");
-  if (mode == kDecodeSampled) throw std::runtime_error("run_tokens_lang: the sampled decode mode takes no language per clip");
-  const NoPrompts none(batch);
-  const PromptSpec& pr = prompts ? *prompts : none.spec;
-  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, pr, &lang, false);  // a bad request fails before any GPU work
-  const LangCall call{lang, out, false};
-  const ScopedSet<const PromptSpec*> scope(prompt_, &pr);
-  const ScopedSet<const LangCall*> lscope(lang_, &call);
-  run_tokens(mode, pcm, nullptr, 0, n_samples, batch, max_new, max_new_clip, ids, n_ids, scores, nullptr);
-}
-
+// ------------------------------------------------------------------------------ language detection: entry points
 void Engine::detect_language_stage(int batch, const LangResult& out) {
   require_lang_call(kDecodeTimestamps, "detect_language");
   if (!out.detected) throw std::runtime_error("detect_language: no output array");
@@ -589,35 +558,6 @@ void Engine::language_logprob_rows(const float* rows, int n, float* lang_logprob
   HIP_CHECK(hipMemcpy(lang_logprob, lp, n * nl * 4, hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(lang_index, ix, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (lang_logit) HIP_CHECK(hipMemcpy(lang_logit, lg, n * nl * 4, hipMemcpyDeviceToHost));
-}
-
-void Engine::prefill_contexts_stage(int batch, const PromptSpec* prompts, const LangSpec& lang, float* no_speech_logprob, float* sot_logits,
-                                    const LangResult& out) {
-  require_lang_call(kDecodeTimestamps, "prefill_contexts");
-  HIP_CHECK(hipSetDevice(device_));
-  if (batch < 1 || batch > cap_) throw std::runtime_error("prefill_contexts: batch exceeds the encoded slots");
-  const NoPrompts none(batch);
-  const PromptSpec& pr = prompts ? *prompts : none.spec;
-  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, pr, &lang, false);
-  const LangCall call{lang, out, false};
-  const ScopedSet<const LangCall*> lscope(lang_, &call);
-  reset_decode_state(batch);
-  prefill_prompts(batch, pr, no_speech_logprob != nullptr || sot_logits != nullptr, no_speech_logprob, sot_logits);
-}
-
-void Engine::decode_forced_lang(DecodeMode mode, int batch, const PromptSpec* prompts, const LangSpec& lang, const int32_t* forced, int n_forced,
-                                float* logits, int32_t* chosen, const ForcedScores* scores, const LangResult& out) {
-  require_lang_call(mode, "decode_forced_lang");
-  if (mode == kDecodeSampled) throw std::runtime_error("decode_forced_lang: not in the sampled decode mode");
-  if (scores && scores->logits0) throw std::runtime_error("decode_forced_lang: a clip behind a context has no row of decode offset 0");
-  if (batch < 1 || batch > cap_) throw std::runtime_error("decode_forced_lang: batch exceeds the encoded slots");
-  const NoPrompts none(batch);
-  const PromptSpec& pr = prompts ? *prompts : none.spec;
-  (void)plan_contexts(cfg_, sot_seq_, handle_lang_, batch, pr, &lang, true);
-  const LangCall call{lang, out, true};
-  const ScopedSet<const PromptSpec*> scope(prompt_, &pr);
-  const ScopedSet<const LangCall*> lscope(lang_, &call);
-  decode_forced(mode, batch, forced, n_forced, logits, chosen, scores, nullptr);
 }
 
 }  // inline namespace AXW_NS

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -55,16 +56,34 @@ class IEngine {
   // what comes back per clip; every array may be null. detected [batch]: the language index the clip was decoded under (for explicit
   // and default clips the index they were given); lang_logprob, lang_logit [batch][n_lang]: detecting clips only, the others' rows are 0
   struct LangResult { int* detected; float* lang_logprob; float* lang_logit; };
-  // full path, host PCM or device PCM; ids [batch][n_text_ctx], n_ids [batch]
-  // max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new; scores: kDecodeScored and
-  // kDecodeSampled only; sample: kDecodeSampled only (and required there)
-  virtual void run_tokens(DecodeMode mode, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
-                          int max_new, const int* max_new_clip, int32_t* ids, int* n_ids, const ClipScores* scores,
-                          const SampleSpec* sample = nullptr) = 0;
-  // run_tokens on host PCM in a timestamp mode, every clip conditioned on its prompt
-  virtual void run_tokens_prompted(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new,
-                                   const int* max_new_clip, const PromptSpec& prompts, int32_t* ids, int* n_ids, const ClipScores* scores,
-                                   const SampleSpec* sample = nullptr) = 0;
+  // What stands in front of `transcribe` for the clips of one call (engine_prefill.cpp): their prompts and their language and task. Both
+  // exist in the timestamp modes only; a language spec also refuses an open Stream*. lang_out is written when `lang` is present
+  // (detected[b] for every clip), and only then.
+  struct ClipContexts {
+    std::optional<PromptSpec> prompts;
+    std::optional<LangSpec> lang;
+    LangResult lang_out{};
+    bool any() const { return prompts || lang; }
+    ClipContexts block(int lo, int n_lang) const;
+  };
+  // The optional parts of one decode over a batch of clips. max_new_clip: host [batch] per-clip id budgets (<= 0: none), each capped by
+  // max_new; sample: kDecodeSampled, and it alone (required there); scores: kDecodeScored and kDecodeSampled only.
+  struct DecodeRequest {
+    DecodeMode mode = kDecodePlain;
+    int max_new = 0;
+    const int* max_new_clip = nullptr;
+    std::optional<SampleSpec> sample;
+    ClipContexts ctx;
+    std::optional<ClipScores> scores;
+    // THE block rule of a batch split over devices (multi_device.hpp): the same request for the clips from `lo` on. Every per-clip
+    // array that is not null moves to its entry of clip lo: token_logprob by rows of n_ctx, the prompt ids by rows of their stride,
+    // lang_logprob and lang_logit by rows of n_lang, every other array by one entry per clip.
+    DecodeRequest block(int lo, int n_ctx, int n_lang) const;
+  };
+  // full path, host PCM or device PCM; ids [batch][n_text_ctx], n_ids [batch]. A request with contexts fails on a bad prompt, language
+  // or task before any GPU work; a language spec is not taken in kDecodeSampled.
+  virtual void run_tokens(const DecodeRequest& rq, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
+                          int32_t* ids, int* n_ids) = 0;
   virtual std::string detokenize(const int32_t* ids, int n) const = 0;
   // detokenize + the reference's zh post-pass (Traditional -> Simplified, Whisper.cpp:231-236) when its OpenCC data files were found
   virtual std::string transcript(const int32_t* ids, int n) const = 0;
@@ -76,34 +95,24 @@ class IEngine {
   virtual void get_cross_kv(int slot, float* k_out, float* v_out) = 0;
   // the slot's self-attention cache rows [0, n_rows), de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][d]
   virtual void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) = 0;
-  // after encode_mel: the decode state of slots [0, batch) as a prompted greedy loop finds it before its first step (reset, then the
-  // prompts' context cached and `transcribe` about to be fed); no_speech_logprob (or null): [batch], 0 for unprompted slots
-  // sot_logits (or null): [batch][n_vocab], the raw row the no-speech value of a prompted slot was taken from
-  virtual void prefill_stage(int batch, const PromptSpec& prompts, float* no_speech_logprob, float* sot_logits) = 0;
-  // decode_forced in a timestamp mode under prompts: the forced ids follow each clip's own context
-  virtual void decode_forced_prompted(DecodeMode mode, int batch, const PromptSpec& prompts, const int32_t* forced, int n_forced, float* logits,
-                                      int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample = nullptr) = 0;
-  // ---- language and task per clip (engine_prefill.cpp). All of these exist in the timestamp modes only and refuse an open Stream*.
-  // run_tokens on host PCM under a language and task per clip; prompts may be null (no clip is prompted)
-  virtual void run_tokens_lang(DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                               const PromptSpec* prompts, const LangSpec& lang, int32_t* ids, int* n_ids, const ClipScores* scores,
-                               const LangResult& out) = 0;
+  // after encode_mel: the decode state of slots [0, batch) as a greedy loop under `ctx` finds it before its first step (reset, then the
+  // clips' contexts cached and their task id about to be fed); no_speech_logprob (or null): [batch], 0 for slots without a context
+  // sot_logits (or null): [batch][n_vocab], the raw row the no-speech value of a slot behind a context was taken from
+  virtual void prefill_stage(int batch, const ClipContexts& ctx, float* no_speech_logprob, float* sot_logits) = 0;
+  // ---- language detection (engine_prefill.cpp); refuses an open Stream*
   // front-end, encoder and detection only: out.detected [batch] (required), out.lang_logprob optional
   virtual void detect_language(const float* const* pcm, const int* n_samples, int batch, const LangResult& out) = 0;
   // after encode_mel: detection of slots [0, batch) (the decode state is reset and left reset)
   virtual void detect_language_stage(int batch, const LangResult& out) = 0;
   // the detection kernel alone on host residual rows [n][d]: lang_logprob [n][n_lang], lang_index [n], lang_logit [n][n_lang] or null
   virtual void language_logprob_rows(const float* rows, int n, float* lang_logprob, int* lang_index, float* lang_logit) = 0;
-  // prefill_stage with a language and task per clip; prompts may be null
-  virtual void prefill_contexts_stage(int batch, const PromptSpec* prompts, const LangSpec& lang, float* no_speech_logprob, float* sot_logits,
-                                      const LangResult& out) = 0;
-  // decode_forced in a timestamp mode, EVERY clip handed over behind its own context [.., sot, language] with its task id
-  virtual void decode_forced_lang(DecodeMode mode, int batch, const PromptSpec* prompts, const LangSpec& lang, const int32_t* forced, int n_forced,
-                                  float* logits, int32_t* chosen, const ForcedScores* scores, const LangResult& out) = 0;
   // timestamp, scored and sampled mode: logits are the raw logits (before the rules), chosen the ids the rules choose; scores:
-  // kDecodeScored and kDecodeSampled only; sample: kDecodeSampled only (and required there)
-  virtual void decode_forced(DecodeMode mode, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
-                             const ForcedScores* scores, const SampleSpec* sample = nullptr) = 0;
+  // kDecodeScored and kDecodeSampled only; sample (or null): kDecodeSampled only (and required there)
+  // ctx (timestamp modes): the forced ids follow each clip's own context. Under prompts alone every clip needs one; under a language
+  // spec (not in kDecodeSampled) EVERY clip is handed over behind its context [.., sot, language] with its task id. Behind a context
+  // no step visits decode offset 0: scores->logits0 is refused and the no-speech value is the hand-over's.
+  virtual void decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, const int32_t* forced, int n_forced, float* logits,
+                             int32_t* chosen, const ForcedScores* scores, const SampleSpec* sample) = 0;
   // plain or timestamp mode; max_new_clip: optional host [batch] per-clip id budgets (<= 0: none), each capped by max_new
   virtual void decode_greedy(DecodeMode mode, int batch, int max_new, const int* max_new_clip, int32_t* ids, int* n_ids) = 0;
   // the rules kernel alone on host data: logits [batch][n_vocab], hist [batch][n_text_ctx] (n_hist[b] ids each) -> chosen [batch];
@@ -171,6 +180,27 @@ class IEngine {
  protected:
   std::mutex mu_;
 };
+
+inline IEngine::ClipContexts IEngine::ClipContexts::block(int lo, int n_lang) const {
+  auto from = [](auto* p, size_t k) { return p ? p + k : p; };
+  ClipContexts c = *this;
+  if (c.prompts) *c.prompts = {from(prompts->ids, (size_t)lo * prompts->stride), prompts->stride, from(prompts->n_prompt, lo)};
+  if (c.lang) *c.lang = {from(lang->lang, lo), from(lang->task, lo)};
+  c.lang_out = {from(lang_out.detected, lo), from(lang_out.lang_logprob, (size_t)lo * n_lang), from(lang_out.lang_logit, (size_t)lo * n_lang)};
+  return c;
+}
+
+inline IEngine::DecodeRequest IEngine::DecodeRequest::block(int lo, int n_ctx, int n_lang) const {
+  auto from = [](auto* p, size_t k) { return p ? p + k : p; };
+  DecodeRequest r = *this;
+  r.max_new_clip = from(max_new_clip, lo);
+  if (r.sample) *r.sample = {from(sample->temperature, lo), from(sample->stream, lo), sample->seed};
+  r.ctx = ctx.block(lo, n_lang);
+  if (r.scores)
+    *r.scores = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
+                 from(scores->ended_eot, lo)};
+  return r;
+}
 
 // One persistent decode launch at a time per GPU, whichever build (bfloat16 / half) the launching handle belongs to:
 // the launch needs every CU, and two of them co-resident would each hold part of the chip until both give up. Defined

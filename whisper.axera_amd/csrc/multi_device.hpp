@@ -69,8 +69,10 @@ void run_sharded(int n, int world, Fn&& fn) {
 template <typename O, typename = void> struct has_file_base : std::false_type {};
 template <typename O> struct has_file_base<O, decltype((void)std::declval<O&>().file_base)> : std::true_type {};
 
-// G engines, one per device. E needs: std::mutex& mutex(); an enum DecodeMode; a struct ClipScores {float *token_logprob,
-// *avg_logprob, *no_speech_logprob; int* ended_eot;}; run_tokens and run_long_windows as they are called below.
+// G engines, one per device. E needs: std::mutex& mutex(); a copyable struct DecodeRequest with DecodeRequest block(int lo, int n_ctx,
+// int n_lang) const, the request of the clips from `lo` on (iengine.hpp states the rule once, for every per-clip array a request
+// can carry); run_tokens, run_beam and run_long_windows as they are called below; for detect_language a struct ClipContexts with a
+// member lang_out and ClipContexts block(int lo, int n_lang) const.
 template <typename E>
 class DeviceGroup {
  public:
@@ -80,90 +82,23 @@ class DeviceGroup {
   E& at(int i) { return *engines_.at(i); }
   E& primary() { return *engines_.at(0); }
 
-  // Host PCM of `batch` clips -> ids [batch][n_ctx], n_ids [batch] (E::run_tokens: a decode mode, optional per-clip budgets
-  // max_new_clip [batch], optional per-clip scores, token_logprob [batch][n_ctx]). With one engine (or one clip) this is the
-  // engine's own call; otherwise workers = min(G, batch) engines each take one contiguous block of every per-clip array.
-  // sample (sampled decode mode; S = E::SampleSpec {temperature [batch], stream [batch], seed}): every shard gets its block of the two
-  // arrays; the stream ids are the caller's, so a clip's draws do not depend on the device it lands on.
-  template <typename S = std::nullptr_t>
-  void run_tokens(typename E::DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                  int n_ctx, int32_t* ids, int* n_ids, const typename E::ClipScores* scores = nullptr, const S* sample = nullptr) {
+  // Host PCM of `batch` clips -> ids [batch][n_ctx], n_ids [batch] (E::run_tokens). With one engine (or one clip) this is the
+  // engine's own call; otherwise workers = min(G, batch) engines each take one contiguous block of the clips, and with it
+  // rq.block(first clip, n_ctx, n_lang): budgets, prompts, languages, sample arrays, scores and language results travel with their
+  // clips (the random stream ids are the caller's, so a clip's draws do not depend on the device it lands on).
+  void run_tokens(const typename E::DecodeRequest& rq, const float* const* pcm, const int* n_samples, int batch, int n_ctx, int n_lang,
+                  int32_t* ids, int* n_ids) {
     if (batch < 1) throw std::runtime_error("batch must be >= 1");
-    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
     for_each_shard(batch, [&](E& e, int, int lo, int hi) {
-      typename E::ClipScores sc{};
-      if (scores)
-        sc = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
-              from(scores->ended_eot, lo)};
-      if constexpr (std::is_same<S, std::nullptr_t>::value) {
-        e.run_tokens(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), ids + (size_t)lo * n_ctx, n_ids + lo,
-                     scores ? &sc : nullptr);
-      } else {
-        S sm{};
-        if (sample) sm = S{from(sample->temperature, lo), from(sample->stream, lo), sample->seed};
-        e.run_tokens(mode, pcm + lo, nullptr, 0, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), ids + (size_t)lo * n_ctx, n_ids + lo,
-                     scores ? &sc : nullptr, sample ? &sm : nullptr);
-      }
+      e.run_tokens(rq.block(lo, n_ctx, n_lang), pcm + lo, nullptr, 0, n_samples + lo, hi - lo, ids + (size_t)lo * n_ctx, n_ids + lo);
     });
   }
 
-  // run_tokens under prompts (E::run_tokens_prompted; P = E::PromptSpec {ids [batch][stride], stride, n_prompt [batch]}): the prompts
-  // travel with their clips.
-  template <typename P, typename S = std::nullptr_t>
-  void run_tokens_prompted(typename E::DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new,
-                           const int* max_new_clip, const P& prompts, int n_ctx, int32_t* ids, int* n_ids, const typename E::ClipScores* scores,
-                           const S* sample = nullptr) {
+  // Language detection alone (E::detect_language): front-end, encoder and detection of every clip on its shard's device; the results
+  // go to out.lang_out.
+  void detect_language(const float* const* pcm, const int* n_samples, int batch, int n_lang, const typename E::ClipContexts& out) {
     if (batch < 1) throw std::runtime_error("batch must be >= 1");
-    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
-    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
-      typename E::ClipScores sc{};
-      if (scores)
-        sc = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
-              from(scores->ended_eot, lo)};
-      const P pr{from(prompts.ids, (size_t)lo * prompts.stride), prompts.stride, from(prompts.n_prompt, lo)};
-      if constexpr (std::is_same<S, std::nullptr_t>::value) {
-        e.run_tokens_prompted(mode, pcm + lo, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), pr, ids + (size_t)lo * n_ctx, n_ids + lo,
-                              scores ? &sc : nullptr);
-      } else {
-        S sm{};
-        if (sample) sm = S{from(sample->temperature, lo), from(sample->stream, lo), sample->seed};
-        e.run_tokens_prompted(mode, pcm + lo, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), pr, ids + (size_t)lo * n_ctx, n_ids + lo,
-                              scores ? &sc : nullptr, sample ? &sm : nullptr);
-      }
-    });
-  }
-
-  // run_tokens under a language and task per clip (E::run_tokens_lang; prompts may be null; L = E::LangSpec {lang [batch], task [batch]},
-  // R = E::LangResult {detected [batch], lang_logprob [batch][n_lang], lang_logit [batch][n_lang]}): requests and results travel with
-  // their clips.
-  template <typename P, typename L, typename R>
-  void run_tokens_lang(typename E::DecodeMode mode, const float* const* pcm, const int* n_samples, int batch, int max_new, const int* max_new_clip,
-                       const P* prompts, const L& lang, int n_ctx, int n_lang, int32_t* ids, int* n_ids, const typename E::ClipScores* scores,
-                       const R& out) {
-    if (batch < 1) throw std::runtime_error("batch must be >= 1");
-    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
-    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
-      typename E::ClipScores sc{};
-      if (scores)
-        sc = {from(scores->token_logprob, (size_t)lo * n_ctx), from(scores->avg_logprob, lo), from(scores->no_speech_logprob, lo),
-              from(scores->ended_eot, lo)};
-      P pr{};
-      if (prompts) pr = P{from(prompts->ids, (size_t)lo * prompts->stride), prompts->stride, from(prompts->n_prompt, lo)};
-      const L lg{from(lang.lang, lo), from(lang.task, lo)};
-      const R o{from(out.detected, lo), from(out.lang_logprob, (size_t)lo * n_lang), from(out.lang_logit, (size_t)lo * n_lang)};
-      e.run_tokens_lang(mode, pcm + lo, n_samples + lo, hi - lo, max_new, from(max_new_clip, lo), prompts ? &pr : nullptr, lg, ids + (size_t)lo * n_ctx,
-                        n_ids + lo, scores ? &sc : nullptr, o);
-    });
-  }
-
-  // Language detection alone (E::detect_language): front-end, encoder and detection of every clip on its shard's device.
-  template <typename R>
-  void detect_language(const float* const* pcm, const int* n_samples, int batch, int n_lang, const R& out) {
-    if (batch < 1) throw std::runtime_error("batch must be >= 1");
-    auto from = [](auto* p, size_t k) { return p ? p + k : p; };
-    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
-      e.detect_language(pcm + lo, n_samples + lo, hi - lo, R{from(out.detected, lo), from(out.lang_logprob, (size_t)lo * n_lang), from(out.lang_logit, (size_t)lo * n_lang)});
-    });
+    for_each_shard(batch, [&](E& e, int, int lo, int hi) { e.detect_language(pcm + lo, n_samples + lo, hi - lo, out.block(lo, n_lang).lang_out); });
   }
 
   // Beam search (E::run_beam; R: the result arrays of beam.hpp, all per-clip with row stride n_ctx where they are rows): the clips
