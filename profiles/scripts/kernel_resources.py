@@ -7,7 +7,8 @@ static LDS bytes. tests/test_kernel_resources.py asserts the scratch / VGPR-spil
     python profiles/scripts/kernel_resources.py --parent DIR > profiles/NAME_kernel_resources.txt
 compares this tree with another checkout's csrc directory (DIR = its whisper.axera_amd/csrc), both builds, the Makefile's flags:
 one line per kernel with the six columns of either tree, marked `<< waves` where the waves-per-SIMD bucket changes (512 unified
-VGPRs per SIMD, allocated in granules of 8, at most 8 waves) and `*` where any column differs."""
+VGPRs per SIMD, allocated in granules of 8, at most 8 waves) and `*` where any column differs.
+`--files decode_timestamps,decode_beam` keeps either form to those kernel files."""
 import os
 import re
 import subprocess
@@ -17,7 +18,9 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.path.join(ROOT, "whisper.axera_amd", "csrc")
-FILES = ["frontend", "gemm", "encoder_attn", "decoder", "decode_gemv", "decode_gemm", "decode_persistent", "decode_persistent2", "decode_timestamps"]
+FILES = ["frontend", "gemm", "encoder_attn", "decoder", "decode_gemv", "decode_gemm", "decode_persistent", "decode_persistent2", "decode_timestamps", "decode_beam"]
+if "--files" in sys.argv:
+    FILES = sys.argv[sys.argv.index("--files") + 1].split(",")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]  # whisper.axera_amd/Makefile HIPFLAGS
 KEYS = ["vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"]
 

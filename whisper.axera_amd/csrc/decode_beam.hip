@@ -8,41 +8,14 @@
 //   beam_reorder_kernel     copies history and self-attention cache of every slot whose hypothesis came from another slot
 //   beam_spread_cross_kernel  before the loop: the cross K/V of a clip into the K slots of its group
 //
-// The three step kernels run one after the other on one stream and never communicate inside a launch. Kernels of their own, by this
-// file family's custom (see the note above timestamp_rules_scored_kernel): the rules prologue exists here a fourth time, and a change
-// to a rule is made here too.
-#include "common.hpp"
+// The three step kernels run one after the other on one stream and never communicate inside a launch. The rules themselves are
+// decode_rules.hpp's; the candidates kernel's loops over the row are its own (they feed sorted lists).
+#include "decode_rules.hpp"
 
 namespace axw {
 inline namespace AXW_NS {
 
 namespace {
-
-// (m, s): logsumexp = m + log(s). m == -inf: empty; m == +inf: +inf (s is kept at 1)    [as in decode_timestamps.hip]
-__device__ __forceinline__ void beam_lse_merge(float& m, float& s, float m2, float s2) {
-  if (m2 > m) {
-    const float tm = m, ts = s;
-    m = m2; s = s2; m2 = tm; s2 = ts;
-  }
-  if (m2 == -INFINITY) return;
-  if (m == INFINITY) { s = 1.f; return; }
-  s += s2 * expf(m2 - m);
-}
-
-__device__ __forceinline__ void beam_lse_add4(float& m, float& s, float x0, float x1, float x2, float x3) {
-  const float cm = fmaxf(fmaxf(x0, x1), fmaxf(x2, x3));
-  if (cm == -INFINITY) return;
-  if (cm > m) { s = m == -INFINITY ? 0.f : s * expf(m - cm); m = cm; }
-  if (m == INFINITY) { s = 1.f; return; }
-  s += (expf(x0 - m) + expf(x1 - m)) + (expf(x2 - m) + expf(x3 - m));
-}
-
-// x - lse with the edge cases of the contract: nothing finite in the set: -inf; x = +inf: 0
-__device__ __forceinline__ float beam_logprob_of(float x, float m, float s) {
-  if (m == -INFINITY || x == -INFINITY) return -INFINITY;
-  if (x == INFINITY) return 0.f;
-  return x - (m == INFINITY ? m : m + logf(s));
-}
 
 constexpr int kM = kBeamMaxCand;  // list length: every M <= 9 is served by the same fully unrolled lists
 constexpr int kNoId = 0x7fffffff;
@@ -92,35 +65,15 @@ __device__ __forceinline__ void wave_top(TopList& l, int M, float* out_v, int* o
 __global__ __launch_bounds__(256) void beam_candidates_kernel(BeamCandParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
-  const int T = p.ts_begin, E = p.eot, nv = p.n_vocab, M = p.n_cand_max;
+  const int E = p.eot, M = p.n_cand_max;
   // dead hypotheses and frozen clips propose nothing
   if ((p.slot_score && p.slot_score[b] == -INFINITY) || (p.complete && p.complete[b / p.beam])) {
     if (tid == 0) p.n_cand[b] = 0;
     return;
   }
   // ---- the slot's history: ids sampled so far (prefix excluded)
-  const int* seq = p.hist + (long)b * p.hist_stride;
   const int n = min(max(p.n_hist ? p.n_hist[b] : p.n, 0), p.hist_stride);
-  __shared__ int s_last[4];
-  int last = -1;  // index of the history's last timestamp
-  for (int i = tid; i < n; i += 256)
-    if (seq[i] >= T) last = i;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
-  if (lane == 0) s_last[wave] = last;
-  __syncthreads();
-  last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
-  const bool last_ts = n >= 1 && seq[n - 1] >= T;
-  const bool penult_ts = n < 2 || seq[n - 2] >= T;
-  const bool pair_open = last_ts && !penult_ts;  // one timestamp after text: the closing half of a pair may follow
-  // ---- the allowed sets: [0, E) iff text_on, E iff eot_on, [E + 1, T) never, [ts_lo, ts_hi)
-  const bool text_on = n > 0 && !pair_open;  // rules 2 (mask [0, E)) and 4
-  const bool eot_on = n > 0;                 // rule 4
-  int ts_lo = T, ts_hi = nv;
-  if (last >= 0) ts_lo = min(max(seq[last], T) + (pair_open ? 0 : 1), nv);  // rule 3
-  if (last_ts && penult_ts) ts_hi = T;                                       // rule 2: a pair just closed
-  if (n == 0) ts_hi = min(ts_hi, T + 51);                                    // rule 4: <= 1.0 s
-  ts_lo = min(ts_lo, ts_hi);
+  const AllowedSets a = allowed_sets(p.hist + (long)b * p.hist_stride, n, p.ts_begin, E, p.n_vocab);
 
   const float* row = p.logits + (long)b * p.stride;
   float tv = -INFINITY;                    // best unmasked id below T (rule 5's right-hand side)
@@ -129,61 +82,52 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(BeamCandParams p) 
   TopList lt, ls;                          // text + eot / timestamps: rule 5 is only known after the reduction
   lt.clear();
   ls.clear();
-  const int text_end = text_on ? E + 1 : (eot_on ? E + 1 : 0);
-  const int text_begin = text_on ? 0 : (eot_on ? E : 0);
-  for (int c = (text_begin >> 2) + tid; 4 * c < text_end; c += 256) {
+  for (int c = (a.text_begin >> 2) + tid; 4 * c < a.text_end; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
     float x[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * c + e;
-      const bool on = i < E ? text_on : (i == E && eot_on);
-      x[e] = (on && v[e] == v[e]) ? v[e] : -INFINITY;
+      x[e] = (text_id_on(a, i, E) && v[e] == v[e]) ? v[e] : -INFINITY;
       tv = fmaxf(tv, x[e]);
       lt.push(x[e], i);
     }
-    beam_lse_add4(mt, st, x[0], x[1], x[2], x[3]);
+    lse_add4(mt, st, x[0], x[1], x[2], x[3]);
   }
-  for (int c = (ts_lo >> 2) + tid; 4 * c < ts_hi; c += 256) {
+  for (int c = (a.ts_lo >> 2) + tid; 4 * c < a.ts_hi; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
     float x[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * c + e;
-      x[e] = (i >= ts_lo && i < ts_hi && v[e] == v[e]) ? v[e] : -INFINITY;
+      x[e] = (timestamp_on(a, i) && v[e] == v[e]) ? v[e] : -INFINITY;
       ls.push(x[e], i);
     }
-    beam_lse_add4(m, s, x[0], x[1], x[2], x[3]);
+    lse_add4(m, s, x[0], x[1], x[2], x[3]);
   }
   // ---- reductions: value pairs merged in a fixed order (lanes by xor butterfly, then waves 0..3)
   tv = wave_max(tv);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    beam_lse_merge(m, s, m2, s2);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(mt, o, 64), s2 = __shfl_xor(st, o, 64);
-    beam_lse_merge(mt, st, m2, s2);
-  }
+  lse_wave_reduce(m, s);
+  lse_wave_reduce(mt, st);
   // lists 0..3: the waves' text lists, 4..7: their timestamp lists
   __shared__ float s_tv[4], s_m[4], s_s[4], s_mt[4], s_st[4];
   __shared__ float s_lv[8][kM];
   __shared__ int s_li[8][kM];
+  // (the waves' values go to LDS before the list rounds and thread 0 reads its own back: nothing but the lists is live across the
+  // rounds, where the register count of this kernel peaks)
+  if (lane == 0) { s_tv[wave] = tv; s_m[wave] = m; s_s[wave] = s; s_mt[wave] = mt; s_st[wave] = st; }
   wave_top(lt, M, s_lv[wave], s_li[wave], lane);
   wave_top(ls, M, s_lv[4 + wave], s_li[4 + wave], lane);
-  if (lane == 0) { s_tv[wave] = tv; s_m[wave] = m; s_s[wave] = s; s_mt[wave] = mt; s_st[wave] = st; }
   __syncthreads();
   if (tid == 0) {
+    tv = s_tv[0]; m = s_m[0]; s = s_s[0]; mt = s_mt[0]; st = s_st[0];
     for (int w = 1; w < 4; ++w) {
       tv = fmaxf(tv, s_tv[w]);
-      beam_lse_merge(m, s, s_m[w], s_s[w]);
-      beam_lse_merge(mt, st, s_mt[w], s_st[w]);
+      lse_merge(m, s, s_m[w], s_s[w]);
+      lse_merge(mt, st, s_mt[w], s_st[w]);
     }
-    const float lse = (m == -INFINITY || m == INFINITY) ? m : m + logf(s);
-    const bool rule5 = lse > tv;  // the timestamps' probability mass beats every single text id: A = the timestamps alone
-    if (!rule5) beam_lse_merge(m, s, mt, st);  // (timestamp pair first: the scored kernel's order)
+    const bool rule5 = rule5_fires(m, s, tv);  // A = the timestamps alone
+    final_set_merge(rule5, m, s, mt, st);
     // merge of the lists that feed the result, heads compared in the fixed order 0..7 (lowest id on equal values)
     int hp[8];
 #pragma unroll
@@ -205,7 +149,7 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(BeamCandParams p) 
       for (int w = 0; w < 8; ++w)
         if (w == bw) ++hp[w];
       p.cand_id[(long)b * M + r] = bi;
-      p.cand_logprob[(long)b * M + r] = beam_logprob_of(bv, m, s);
+      p.cand_logprob[(long)b * M + r] = logprob_of(bv, m, s);
       ++count;
     }
     for (int r = count; r < M; ++r) { p.cand_id[(long)b * M + r] = E; p.cand_logprob[(long)b * M + r] = -INFINITY; }

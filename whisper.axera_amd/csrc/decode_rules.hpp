@@ -1,0 +1,116 @@
+// decode_rules.hpp — Whisper's timestamp rules as device functions: the one statement of what decode_timestamps.hip (the plain,
+// scored and sampled rules kernels) and decode_beam.hip (beam_candidates_kernel) decide alike. Shared: the logsumexp helpers, the
+// way from a history to the allowed sets (rules 2, 3 and 4), the history selection of TsRulesParams, and rule 5 with the final-set
+// merge and the pick of the winner. A change to a rule is made here and reaches all four kernels. Not shared: the loops over the
+// row. The rules kernels keep one winner per range and add the timestamps to their (max, sum) pair one by one; the beam kernel
+// feeds sorted lists and adds the timestamps in chunks of four, which rounds differently, and each form keeps its bits.
+// Every function that holds a barrier is called by all 256 threads of the workgroup (four waves) or by none.
+#pragma once
+#include "common.hpp"
+
+namespace axw {
+inline namespace AXW_NS {
+
+// ---- logsumexp as an online (m, s) pair: value = m + log(s). m == -inf: empty; m == +inf: +inf (s is kept at 1)
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+  if (m2 > m) {
+    const float tm = m, ts = s;
+    m = m2; s = s2; m2 = tm; s2 = ts;
+  }
+  if (m2 == -INFINITY) return;
+  if (m == INFINITY) { s = 1.f; return; }
+  s += s2 * expf(m2 - m);
+}
+
+// four logits at once (masked ones as -inf): the running maximum moves at most once per chunk
+__device__ __forceinline__ void lse_add4(float& m, float& s, float x0, float x1, float x2, float x3) {
+  const float cm = fmaxf(fmaxf(x0, x1), fmaxf(x2, x3));
+  if (cm == -INFINITY) return;
+  if (cm > m) { s = m == -INFINITY ? 0.f : s * expf(m - cm); m = cm; }
+  if (m == INFINITY) { s = 1.f; return; }
+  s += (expf(x0 - m) + expf(x1 - m)) + (expf(x2 - m) + expf(x3 - m));
+}
+
+// the pairs of a wave's lanes -> every lane (fixed order: xor butterfly)
+__device__ __forceinline__ void lse_wave_reduce(float& m, float& s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    lse_merge(m, s, m2, s2);
+  }
+}
+
+__device__ __forceinline__ float lse_value(float m, float s) { return (m == -INFINITY || m == INFINITY) ? m : m + logf(s); }
+
+// x - lse with the edge cases of the contract: nothing finite in the set: -inf; x = +inf: 0
+__device__ __forceinline__ float logprob_of(float x, float m, float s) {
+  if (m == -INFINITY || x == -INFINITY) return -INFINITY;
+  if (x == INFINITY) return 0.f;
+  return x - (m == INFINITY ? m : m + logf(s));
+}
+
+// ---- the history of clip b under TsRulesParams: the ids sampled so far (prefix excluded), teacher-forced or greedy
+struct RulesHistory {
+  const int* seq;
+  int n;
+};
+__device__ __forceinline__ RulesHistory rules_history(const TsRulesParams& p, int b) {
+  if (p.forced) return {p.forced + (long)b * p.n_forced, min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced)};
+  return {p.out_ids + (long)b * p.n_ctx, min(max(p.n_out[b], 0), p.n_ctx)};
+}
+
+// ---- the allowed sets after a history: [0, E) iff text_on, E iff eot_on, [E + 1, T) never, [ts_lo, ts_hi)
+struct AllowedSets {
+  bool text_on, eot_on;
+  int ts_lo, ts_hi;
+  int text_begin, text_end;  // the part of [0, E] that a row loop has to visit (empty: 0, 0)
+};
+// T: id of 0.00 s, E: eot, nv: the vocabulary. One barrier.
+__device__ __forceinline__ AllowedSets allowed_sets(const int* seq, int n, int T, int E, int nv) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int s_last[4];
+  int last = -1;  // index of the history's last timestamp
+  for (int i = tid; i < n; i += 256)
+    if (seq[i] >= T) last = i;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+  if (lane == 0) s_last[wave] = last;
+  __syncthreads();
+  last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
+  const bool last_ts = n >= 1 && seq[n - 1] >= T;
+  const bool penult_ts = n < 2 || seq[n - 2] >= T;
+  const bool pair_open = last_ts && !penult_ts;  // one timestamp after text: the closing half of a pair may follow
+  AllowedSets a;
+  a.text_on = n > 0 && !pair_open;  // rules 2 (mask [0, E)) and 4
+  a.eot_on = n > 0;                 // rule 4
+  a.ts_lo = T;
+  a.ts_hi = nv;
+  if (last >= 0) a.ts_lo = min(max(seq[last], T) + (pair_open ? 0 : 1), nv);  // rule 3
+  if (last_ts && penult_ts) a.ts_hi = T;                                       // rule 2: a pair just closed
+  if (n == 0) a.ts_hi = min(a.ts_hi, T + 51);                                  // rule 4: <= 1.0 s
+  a.ts_lo = min(a.ts_lo, a.ts_hi);
+  a.text_end = a.text_on ? E + 1 : (a.eot_on ? E + 1 : 0);
+  a.text_begin = a.text_on ? 0 : (a.eot_on ? E : 0);
+  return a;
+}
+__device__ __forceinline__ bool text_id_on(const AllowedSets& a, int i, int E) { return i < E ? a.text_on : (i == E && a.eot_on); }
+__device__ __forceinline__ bool timestamp_on(const AllowedSets& a, int i) { return i >= a.ts_lo && i < a.ts_hi; }
+
+// ---- rule 5 and the final allowed set A. (m, s): the pair of the unmasked timestamps; tv: the best unmasked id of [0, E]
+// rule 5: the timestamps' probability mass beats every single text id
+__device__ __forceinline__ bool rule5_fires(float m, float s, float tv) { return lse_value(m, s) > tv; }
+// (m, s) -> the pair of A: the timestamps alone when rule 5 fired, else timestamps, text and eot (timestamp pair first: a fixed
+// order); (mt, st): the pair of the unmasked ids of [0, E]
+__device__ __forceinline__ void final_set_merge(bool rule5, float& m, float& s, float mt, float st) {
+  if (!rule5) lse_merge(m, s, mt, st);
+}
+// The winner of A from the winners (value or key, id) of [0, E] and of the timestamps: the timestamps' when rule 5 fired, else
+// the larger one (text ids are the lower ones: text on ties). Nothing above -inf: eot with -inf, the clip ends.
+enum class Pick { kEot, kText, kTimestamp };
+__device__ __forceinline__ Pick final_pick(bool rule5, float tv, float sv) {
+  if (!rule5 && tv > -INFINITY && tv >= sv) return Pick::kText;
+  return sv > -INFINITY ? Pick::kTimestamp : Pick::kEot;
+}
+
+}  // inline namespace AXW_NS
+}  // namespace axw

@@ -11,55 +11,27 @@
 // Scored form (DESIGN.md "Confidence"): the same pass also keeps an online (max, sum) over the unmasked text ids and eot, so that
 // thread 0 knows logsumexp of the final allowed set A and writes log p(chosen) = x[chosen] - logsumexp(x[A]) and the decision id
 // at the clip's history length. At decode offset 0 (the step that fed sot) the scored launch takes the whole-row branch instead:
-// log p(<|nospeech|>) over the unfiltered row. The unscored kernel is untouched by all of this.
+// log p(<|nospeech|>) over the unfiltered row.
 //
 // Sampled form (DESIGN.md "Temperature fallback"): the scored form whose decision, for a clip at temperature t > 0, is drawn from
 // softmax(x[A] / t) by Gumbel-max with Philox4x32-10 noise: two more (key, id) pairs per thread (text and eot / timestamps, since
-// rule 5 is only known after the reduction), reduced like the argmax pairs. The other kernels are untouched by it.
-#include "common.hpp"
+// rule 5 is only known after the reduction), reduced like the argmax pairs.
+//
+// The three kernels are instantiations of one body, rules_body<MODE>: a lower form compiles none of what a higher one adds. The rules
+// themselves, the logsumexp helpers and the decision are decode_rules.hpp's, shared with decode_beam.hip.
+#include "decode_rules.hpp"
 
 namespace axw {
 inline namespace AXW_NS {
 
-// (m, s): logsumexp = m + log(s). m == -inf: empty; m == +inf: +inf (s is kept at 1)
-__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
-  if (m2 > m) {
-    const float tm = m, ts = s;
-    m = m2; s = s2; m2 = tm; s2 = ts;
-  }
-  if (m2 == -INFINITY) return;
-  if (m == INFINITY) { s = 1.f; return; }
-  s += s2 * expf(m2 - m);
-}
-
-// four logits at once (masked ones as -inf): the running maximum moves at most once per chunk
-__device__ __forceinline__ void lse_add4(float& m, float& s, float x0, float x1, float x2, float x3) {
-  const float cm = fmaxf(fmaxf(x0, x1), fmaxf(x2, x3));
-  if (cm == -INFINITY) return;
-  if (cm > m) { s = m == -INFINITY ? 0.f : s * expf(m - cm); m = cm; }
-  if (m == INFINITY) { s = 1.f; return; }
-  s += (expf(x0 - m) + expf(x1 - m)) + (expf(x2 - m) + expf(x3 - m));
-}
-
 // (m, s) of the whole workgroup -> thread 0 (fixed order: lanes by xor butterfly, then waves 0..3)
 __device__ __forceinline__ void lse_block_reduce(float& m, float& s, float* sh_m, float* sh_s) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    lse_merge(m, s, m2, s2);
-  }
+  lse_wave_reduce(m, s);
   if (lane == 0) { sh_m[wave] = m; sh_s[wave] = s; }
   __syncthreads();
   if (tid == 0)
     for (int w = 1; w < 4; ++w) lse_merge(m, s, sh_m[w], sh_s[w]);
-}
-
-// x - lse with the edge cases of the contract: nothing finite in the set: -inf; x = +inf: 0
-__device__ __forceinline__ float logprob_of(float x, float m, float s) {
-  if (m == -INFINITY || x == -INFINITY) return -INFINITY;
-  if (x == INFINITY) return 0.f;
-  return x - (m == INFINITY ? m : m + logf(s));
 }
 
 // log p(row[id]) over the WHOLE row (NaN entries left out), by one workgroup; thread 0 writes *out
@@ -78,231 +50,7 @@ __device__ __forceinline__ void row_logprob(const float* row, int nv, int id, fl
   if (tid == 0) *out = logprob_of(row[id], m, s);
 }
 
-// (The rules prologue and the reductions below exist three times in this file — this kernel, the scored and the sampled form: a change
-// to a rule is made in all three.)
-__global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesParams p) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x;
-  const int T = p.ts_begin, E = p.eot, nv = p.n_vocab;
-  // only clips that sample at this step: past the prefix and not finished
-  if (p.off && p.off[b] < p.n_prefix - 1) return;
-  if (p.done && p.done[b]) return;
-
-  // ---- the clip's history: ids sampled so far (prefix excluded)
-  const int* seq;
-  int n;
-  if (p.forced) {
-    seq = p.forced + (long)b * p.n_forced;
-    n = min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced);
-  } else {
-    seq = p.out_ids + (long)b * p.n_ctx;
-    n = min(max(p.n_out[b], 0), p.n_ctx);
-  }
-  __shared__ int s_last[4];
-  __shared__ float s_tv[4], s_sv[4], s_m[4], s_s[4];
-  __shared__ int s_ti[4], s_si[4];
-  int last = -1;  // index of the clip's last timestamp
-  for (int i = tid; i < n; i += 256)
-    if (seq[i] >= T) last = i;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
-  if (lane == 0) s_last[wave] = last;
-  __syncthreads();
-  last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
-  const bool last_ts = n >= 1 && seq[n - 1] >= T;
-  const bool penult_ts = n < 2 || seq[n - 2] >= T;
-  const bool pair_open = last_ts && !penult_ts;  // one timestamp after text: the closing half of a pair may follow
-  // ---- the allowed sets: [0, E) iff text_on, E iff eot_on, [E + 1, T) never, [ts_lo, ts_hi)
-  const bool text_on = n > 0 && !pair_open;  // rules 2 (mask [0, E)) and 4
-  const bool eot_on = n > 0;                 // rule 4
-  int ts_lo = T, ts_hi = nv;
-  if (last >= 0) ts_lo = min(max(seq[last], T) + (pair_open ? 0 : 1), nv);  // rule 3
-  if (last_ts && penult_ts) ts_hi = T;                                       // rule 2: a pair just closed
-  if (n == 0) ts_hi = min(ts_hi, T + 51);                                    // rule 4: <= 1.0 s
-  ts_lo = min(ts_lo, ts_hi);
-
-  const float* row = p.logits + (long)b * p.stride;
-  float tv = -INFINITY, sv = -INFINITY, m = -INFINITY, s = 0.f;
-  int ti = 0x7fffffff, si = 0x7fffffff;
-  // text ids [0, E]: chunks of four floats; NaN never compares greater (it counts as masked)
-  const int text_end = text_on ? E + 1 : (eot_on ? E + 1 : 0);
-  const int text_begin = text_on ? 0 : (eot_on ? E : 0);
-  for (int c = (text_begin >> 2) + tid; 4 * c < text_end; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = 4 * c + e;
-      const bool on = i < E ? text_on : (i == E && eot_on);
-      if (on && v[e] > tv) { tv = v[e]; ti = i; }
-    }
-  }
-  for (int c = (ts_lo >> 2) + tid; 4 * c < ts_hi; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = 4 * c + e;
-      if (i >= ts_lo && i < ts_hi && v[e] == v[e]) {
-        if (v[e] > sv) { sv = v[e]; si = i; }
-        lse_merge(m, s, v[e], 1.f);
-      }
-    }
-  }
-  // ---- reductions: first maximum wins (lower index on ties), logsumexp pairs merged in a fixed order
-  wave_argmax(tv, ti);
-  wave_argmax(sv, si);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    lse_merge(m, s, m2, s2);
-  }
-  if (lane == 0) { s_tv[wave] = tv; s_ti[wave] = ti; s_sv[wave] = sv; s_si[wave] = si; s_m[wave] = m; s_s[wave] = s; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w) {
-      argmax_take(tv, ti, s_tv[w], s_ti[w]);
-      argmax_take(sv, si, s_sv[w], s_si[w]);
-      lse_merge(m, s, s_m[w], s_s[w]);
-    }
-    const float lse = (m == -INFINITY || m == INFINITY) ? m : m + logf(s);
-    float bv = -INFINITY;
-    int bi = E;  // nothing finite left: eot, the clip ends
-    if (lse > tv) {  // rule 5: the timestamps' probability mass beats every single text id
-      bv = sv; bi = si;
-    } else if (tv > -INFINITY && tv >= sv) {
-      bv = tv; bi = ti;
-    } else if (sv > -INFINITY) {
-      bv = sv; bi = si;
-    }
-    p.amax_val[(long)b * p.amax_stride] = bv;
-    p.amax_idx[(long)b * p.amax_stride] = bi;
-  }
-}
-
-// The scored form: timestamp_rules_kernel line for line, plus the text-range (max, sum), the no-speech branch and the score stores.
-// A kernel of its own and not a template parameter of the one above: routed through a shared body, the unscored kernel came out
-// of hipcc with another register allocation, and timestamp mode without scores is to keep the instructions it had.
-// (One of three copies of the prologue and reductions: see the note above timestamp_rules_kernel.)
-__global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesParams p, TsScoreParams q) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x;
-  const int T = p.ts_begin, E = p.eot, nv = p.n_vocab;
-  // only clips that sample at this step: past the prefix and not finished
-  if (p.off && p.off[b] < p.n_prefix - 1) {
-    // the step that fed sot: the no-speech value of this clip
-    if (q.no_speech && p.off[b] == 0) row_logprob(p.logits + (long)b * p.stride, p.n_vocab, q.no_speech_id, q.no_speech + b);
-    return;
-  }
-  if (p.done && p.done[b]) return;
-
-  // ---- the clip's history: ids sampled so far (prefix excluded)
-  const int* seq;
-  int n;
-  if (p.forced) {
-    seq = p.forced + (long)b * p.n_forced;
-    n = min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced);
-  } else {
-    seq = p.out_ids + (long)b * p.n_ctx;
-    n = min(max(p.n_out[b], 0), p.n_ctx);
-  }
-  __shared__ int s_last[4];
-  __shared__ float s_tv[4], s_sv[4], s_m[4], s_s[4];
-  __shared__ int s_ti[4], s_si[4];
-  int last = -1;  // index of the clip's last timestamp
-  for (int i = tid; i < n; i += 256)
-    if (seq[i] >= T) last = i;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
-  if (lane == 0) s_last[wave] = last;
-  __syncthreads();
-  last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
-  const bool last_ts = n >= 1 && seq[n - 1] >= T;
-  const bool penult_ts = n < 2 || seq[n - 2] >= T;
-  const bool pair_open = last_ts && !penult_ts;  // one timestamp after text: the closing half of a pair may follow
-  // ---- the allowed sets: [0, E) iff text_on, E iff eot_on, [E + 1, T) never, [ts_lo, ts_hi)
-  const bool text_on = n > 0 && !pair_open;  // rules 2 (mask [0, E)) and 4
-  const bool eot_on = n > 0;                 // rule 4
-  int ts_lo = T, ts_hi = nv;
-  if (last >= 0) ts_lo = min(max(seq[last], T) + (pair_open ? 0 : 1), nv);  // rule 3
-  if (last_ts && penult_ts) ts_hi = T;                                       // rule 2: a pair just closed
-  if (n == 0) ts_hi = min(ts_hi, T + 51);                                    // rule 4: <= 1.0 s
-  ts_lo = min(ts_lo, ts_hi);
-
-  const float* row = p.logits + (long)b * p.stride;
-  float tv = -INFINITY, sv = -INFINITY, m = -INFINITY, s = 0.f;
-  float mt = -INFINITY, st = 0.f;  // online logsumexp over the unmasked text ids and eot
-  int ti = 0x7fffffff, si = 0x7fffffff;
-  // text ids [0, E]: chunks of four floats; NaN never compares greater (it counts as masked)
-  const int text_end = text_on ? E + 1 : (eot_on ? E + 1 : 0);
-  const int text_begin = text_on ? 0 : (eot_on ? E : 0);
-  for (int c = (text_begin >> 2) + tid; 4 * c < text_end; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
-    float x[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = 4 * c + e;
-      const bool on = i < E ? text_on : (i == E && eot_on);
-      if (on && v[e] > tv) { tv = v[e]; ti = i; }
-      x[e] = (on && v[e] == v[e]) ? v[e] : -INFINITY;
-    }
-    lse_add4(mt, st, x[0], x[1], x[2], x[3]);
-  }
-  for (int c = (ts_lo >> 2) + tid; 4 * c < ts_hi; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = 4 * c + e;
-      if (i >= ts_lo && i < ts_hi && v[e] == v[e]) {
-        if (v[e] > sv) { sv = v[e]; si = i; }
-        lse_merge(m, s, v[e], 1.f);
-      }
-    }
-  }
-  // ---- reductions: first maximum wins (lower index on ties), logsumexp pairs merged in a fixed order
-  wave_argmax(tv, ti);
-  wave_argmax(sv, si);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    lse_merge(m, s, m2, s2);
-  }
-  __shared__ float s_mt[4], s_st[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(mt, o, 64), s2 = __shfl_xor(st, o, 64);
-    lse_merge(mt, st, m2, s2);
-  }
-  if (lane == 0) { s_mt[wave] = mt; s_st[wave] = st; }
-  if (lane == 0) { s_tv[wave] = tv; s_ti[wave] = ti; s_sv[wave] = sv; s_si[wave] = si; s_m[wave] = m; s_s[wave] = s; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w) {
-      argmax_take(tv, ti, s_tv[w], s_ti[w]);
-      argmax_take(sv, si, s_sv[w], s_si[w]);
-      lse_merge(m, s, s_m[w], s_s[w]);
-      lse_merge(mt, st, s_mt[w], s_st[w]);
-    }
-    const float lse = (m == -INFINITY || m == INFINITY) ? m : m + logf(s);
-    float bv = -INFINITY;
-    int bi = E;  // nothing finite left: eot, the clip ends
-    if (lse > tv) {  // rule 5: the timestamps' probability mass beats every single text id
-      bv = sv; bi = si;
-    } else if (tv > -INFINITY && tv >= sv) {
-      bv = tv; bi = ti;
-    } else if (sv > -INFINITY) {
-      bv = sv; bi = si;
-    }
-    p.amax_val[(long)b * p.amax_stride] = bv;
-    p.amax_idx[(long)b * p.amax_stride] = bi;
-    // A = the timestamps alone when rule 5 fired, else text, eot and timestamps (timestamp pair first: a fixed order)
-    if (!(lse > tv)) lse_merge(m, s, mt, st);
-    if (n < q.stride) {
-      q.logprob[(long)b * q.stride + n] = logprob_of(bv, m, s);
-      q.decision[(long)b * q.stride + n] = bi;
-    }
-  }
-}
-
-// ---- sampled form (DESIGN.md "Temperature fallback")
+// ---- sampled form's noise (DESIGN.md "Temperature fallback")
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"): counter c, key k -> four words; no state in memory
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
 #pragma unroll
@@ -321,82 +69,63 @@ __device__ __forceinline__ float gumbel_key(float x, float t, unsigned word) {
   return x / t - logf(-logf(u));
 }
 
-// The sampled form: timestamp_rules_scored_kernel line for line, plus two Gumbel (key, id) pairs per thread for clips whose temperature
-// is above 0: the decision is drawn from softmax(x[A] / t) over the final allowed set A, as argmax of x / t + Gumbel noise, the noise
-// of id i at history length n being word i & 3 of Philox(counter (i >> 2, n, stream), key seed). Rules 1 to 5 are decided on the
-// untempered logits and the recorded log-probability is the untempered one. A clip with t <= 0 takes the scored kernel's decision
-// and computes no random number. A kernel of its own for the reason given above the scored one.
-// (A change to a rule is made here, in timestamp_rules_kernel and in timestamp_rules_scored_kernel alike.)
-__global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesParams p, TsScoreParams q, TsSampleParams r) {
+// ---- the rules kernels: one body in three forms, each of which has everything the one before it has
+enum RulesMode { kRulesPlain, kRulesScored, kRulesSampled };
+
+// kRulesPlain: the argmax partial alone (q and r are not read). kRulesScored: plus the (max, sum) pair of the unmasked ids of
+// [0, E], the no-speech branch and the score stores of q. kRulesSampled: plus, for a clip whose temperature is above 0, two Gumbel
+// (key, id) pairs per thread: the decision is drawn from softmax(x[A] / t) over the final allowed set A, as argmax of x / t + Gumbel
+// noise, the noise of id i at history length n being word i & 3 of Philox(counter (i >> 2, n, stream), key seed). Rules 1 to 5 are
+// decided on the untempered logits and the recorded log-probability is the untempered one; a clip with t <= 0 takes the scored
+// form's decision and computes no random number.
+template <RulesMode MODE>
+__device__ __forceinline__ void rules_body(const TsRulesParams& p, const TsScoreParams& q, const TsSampleParams& r) {
+  constexpr bool kScore = MODE >= kRulesScored, kSample = MODE == kRulesSampled;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
-  const int T = p.ts_begin, E = p.eot, nv = p.n_vocab;
+  const int T = p.ts_begin, E = p.eot;
   // only clips that sample at this step: past the prefix and not finished
   if (p.off && p.off[b] < p.n_prefix - 1) {
     // the step that fed sot: the no-speech value of this clip
-    if (q.no_speech && p.off[b] == 0) row_logprob(p.logits + (long)b * p.stride, p.n_vocab, q.no_speech_id, q.no_speech + b);
+    if constexpr (kScore)
+      if (q.no_speech && p.off[b] == 0) row_logprob(p.logits + (long)b * p.stride, p.n_vocab, q.no_speech_id, q.no_speech + b);
     return;
   }
   if (p.done && p.done[b]) return;
-
-  // ---- the clip's history: ids sampled so far (prefix excluded)
-  const int* seq;
-  int n;
-  if (p.forced) {
-    seq = p.forced + (long)b * p.n_forced;
-    n = min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced);
-  } else {
-    seq = p.out_ids + (long)b * p.n_ctx;
-    n = min(max(p.n_out[b], 0), p.n_ctx);
-  }
-  __shared__ int s_last[4];
-  __shared__ float s_tv[4], s_sv[4], s_m[4], s_s[4];
-  __shared__ int s_ti[4], s_si[4];
-  int last = -1;  // index of the clip's last timestamp
-  for (int i = tid; i < n; i += 256)
-    if (seq[i] >= T) last = i;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
-  if (lane == 0) s_last[wave] = last;
-  __syncthreads();
-  last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
-  const bool last_ts = n >= 1 && seq[n - 1] >= T;
-  const bool penult_ts = n < 2 || seq[n - 2] >= T;
-  const bool pair_open = last_ts && !penult_ts;  // one timestamp after text: the closing half of a pair may follow
-  // ---- the allowed sets: [0, E) iff text_on, E iff eot_on, [E + 1, T) never, [ts_lo, ts_hi)
-  const bool text_on = n > 0 && !pair_open;  // rules 2 (mask [0, E)) and 4
-  const bool eot_on = n > 0;                 // rule 4
-  int ts_lo = T, ts_hi = nv;
-  if (last >= 0) ts_lo = min(max(seq[last], T) + (pair_open ? 0 : 1), nv);  // rule 3
-  if (last_ts && penult_ts) ts_hi = T;                                       // rule 2: a pair just closed
-  if (n == 0) ts_hi = min(ts_hi, T + 51);                                    // rule 4: <= 1.0 s
-  ts_lo = min(ts_lo, ts_hi);
+  const RulesHistory h = rules_history(p, b);
+  const int n = h.n;
+  const AllowedSets a = allowed_sets(h.seq, n, T, E, p.n_vocab);
 
   // ---- the clip's temperature and random stream (uniform over the workgroup)
-  const float temp = r.temperature[b];
-  const bool draw = temp > 0.f;
-  const unsigned long long sid = r.stream[b], seed = r.seed[0];
-  const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), c2 = (unsigned)sid, c3 = (unsigned)(sid >> 32);
+  float temp = 0.f;
+  unsigned k0 = 0, k1 = 0, c2 = 0, c3 = 0;
+  if constexpr (kSample) {
+    temp = r.temperature[b];
+    const unsigned long long sid = r.stream[b], seed = r.seed[0];
+    k0 = (unsigned)seed; k1 = (unsigned)(seed >> 32); c2 = (unsigned)sid; c3 = (unsigned)(sid >> 32);
+  }
+  const bool draw = kSample && temp > 0.f;
 
+  // ---- one pass over the row
   const float* row = p.logits + (long)b * p.stride;
-  float tv = -INFINITY, sv = -INFINITY, m = -INFINITY, s = 0.f;
-  float mt = -INFINITY, st = 0.f;  // online logsumexp over the unmasked text ids and eot
-  float gt = -INFINITY, gs = -INFINITY;  // best Gumbel key over the unmasked text ids and eot / over the unmasked timestamps
-  int ti = 0x7fffffff, si = 0x7fffffff, gti = 0x7fffffff, gsi = 0x7fffffff;
+  float tv = -INFINITY, sv = -INFINITY;  // the first best unmasked id of [0, E] / unmasked timestamp
+  int ti = 0x7fffffff, si = 0x7fffffff;
+  float m = -INFINITY, s = 0.f;          // online logsumexp over the unmasked timestamps
+  float mt = -INFINITY, st = 0.f;        // scored: online logsumexp over the unmasked text ids and eot
+  float gt = -INFINITY, gs = -INFINITY;  // a clip that draws: best Gumbel key over the unmasked text ids and eot / timestamps
+  int gti = 0x7fffffff, gsi = 0x7fffffff;
   // text ids [0, E]: chunks of four floats; NaN never compares greater (it counts as masked)
-  const int text_end = text_on ? E + 1 : (eot_on ? E + 1 : 0);
-  const int text_begin = text_on ? 0 : (eot_on ? E : 0);
-  for (int c = (text_begin >> 2) + tid; 4 * c < text_end; c += 256) {
+  for (int c = (a.text_begin >> 2) + tid; 4 * c < a.text_end; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
-    float x[4];
+    [[maybe_unused]] float x[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * c + e;
-      const bool on = i < E ? text_on : (i == E && eot_on);
+      const bool on = text_id_on(a, i, E);
       if (on && v[e] > tv) { tv = v[e]; ti = i; }
       x[e] = (on && v[e] == v[e]) ? v[e] : -INFINITY;
     }
-    lse_add4(mt, st, x[0], x[1], x[2], x[3]);
+    if constexpr (kScore) lse_add4(mt, st, x[0], x[1], x[2], x[3]);
     if (draw) {
       unsigned w[4];
       philox4x32_10((unsigned)c, (unsigned)n, c2, c3, k0, k1, w);
@@ -407,14 +136,14 @@ __global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesPar
       }
     }
   }
-  for (int c = (ts_lo >> 2) + tid; 4 * c < ts_hi; c += 256) {
+  for (int c = (a.ts_lo >> 2) + tid; 4 * c < a.ts_hi; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
     unsigned w[4];
     if (draw) philox4x32_10((unsigned)c, (unsigned)n, c2, c3, k0, k1, w);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * c + e;
-      if (i >= ts_lo && i < ts_hi && v[e] == v[e]) {
+      if (timestamp_on(a, i) && v[e] == v[e]) {
         if (v[e] > sv) { sv = v[e]; si = i; }
         lse_merge(m, s, v[e], 1.f);
         if (draw) {
@@ -424,67 +153,60 @@ __global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesPar
       }
     }
   }
-  // ---- reductions: first maximum wins (lower index on ties), logsumexp pairs merged in a fixed order
+  // ---- reductions: first maximum wins (lower index on ties), logsumexp pairs merged in a fixed order (lanes by xor butterfly,
+  // then waves 0..3); thread 0 ends with the workgroup's values
+  __shared__ float s_tv[4], s_sv[4], s_m[4], s_s[4], s_mt[4], s_st[4], s_gt[4], s_gs[4];
+  __shared__ int s_ti[4], s_si[4], s_gti[4], s_gsi[4];
   wave_argmax(tv, ti);
   wave_argmax(sv, si);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    lse_merge(m, s, m2, s2);
-  }
-  __shared__ float s_mt[4], s_st[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(mt, o, 64), s2 = __shfl_xor(st, o, 64);
-    lse_merge(mt, st, m2, s2);
-  }
-  __shared__ float s_gt[4], s_gs[4];
-  __shared__ int s_gti[4], s_gsi[4];
+  lse_wave_reduce(m, s);
+  if constexpr (kScore) lse_wave_reduce(mt, st);
   if (draw) {
     wave_argmax(gt, gti);
     wave_argmax(gs, gsi);
     if (lane == 0) { s_gt[wave] = gt; s_gti[wave] = gti; s_gs[wave] = gs; s_gsi[wave] = gsi; }
   }
-  if (lane == 0) { s_mt[wave] = mt; s_st[wave] = st; }
+  if constexpr (kScore)
+    if (lane == 0) { s_mt[wave] = mt; s_st[wave] = st; }
   if (lane == 0) { s_tv[wave] = tv; s_ti[wave] = ti; s_sv[wave] = sv; s_si[wave] = si; s_m[wave] = m; s_s[wave] = s; }
   __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w) {
-      argmax_take(tv, ti, s_tv[w], s_ti[w]);
-      argmax_take(sv, si, s_sv[w], s_si[w]);
-      lse_merge(m, s, s_m[w], s_s[w]);
-      lse_merge(mt, st, s_mt[w], s_st[w]);
-    }
-    const float lse = (m == -INFINITY || m == INFINITY) ? m : m + logf(s);
-    float bv = -INFINITY;
-    int bi = E;  // nothing finite left: eot, the clip ends
+  if (tid != 0) return;
+  for (int w = 1; w < 4; ++w) {
+    argmax_take(tv, ti, s_tv[w], s_ti[w]);
+    argmax_take(sv, si, s_sv[w], s_si[w]);
+    lse_merge(m, s, s_m[w], s_s[w]);
+    if constexpr (kScore) lse_merge(mt, st, s_mt[w], s_st[w]);
     if (draw) {
-      for (int w = 1; w < 4; ++w) {
-        argmax_take(gt, gti, s_gt[w], s_gti[w]);
-        argmax_take(gs, gsi, s_gs[w], s_gsi[w]);
-      }
-      // rule 5 fired: the timestamps' winner; else the larger key of the two winners (text ids are the lower ones: text on ties)
-      int gi = -1;
-      if (lse > tv) { if (gs > -INFINITY) gi = gsi; }
-      else if (gt > -INFINITY && gt >= gs) gi = gti;
-      else if (gs > -INFINITY) gi = gsi;
-      if (gi >= 0) { bi = gi; bv = row[gi]; }
-    } else if (lse > tv) {  // rule 5: the timestamps' probability mass beats every single text id
-      bv = sv; bi = si;
-    } else if (tv > -INFINITY && tv >= sv) {
-      bv = tv; bi = ti;
-    } else if (sv > -INFINITY) {
-      bv = sv; bi = si;
+      argmax_take(gt, gti, s_gt[w], s_gti[w]);
+      argmax_take(gs, gsi, s_gs[w], s_gsi[w]);
     }
-    p.amax_val[(long)b * p.amax_stride] = bv;
-    p.amax_idx[(long)b * p.amax_stride] = bi;
-    // A = the timestamps alone when rule 5 fired, else text, eot and timestamps (timestamp pair first: a fixed order)
-    if (!(lse > tv)) lse_merge(m, s, mt, st);
+  }
+  // ---- the decision: the winner of the final allowed set by logit, or by key for a clip that draws
+  const bool rule5 = rule5_fires(m, s, tv);
+  float bv = -INFINITY;
+  int bi = E;
+  const Pick pick = final_pick(rule5, draw ? gt : tv, draw ? gs : sv);
+  if (pick == Pick::kText) { bi = draw ? gti : ti; bv = draw ? row[bi] : tv; }
+  if (pick == Pick::kTimestamp) { bi = draw ? gsi : si; bv = draw ? row[bi] : sv; }
+  p.amax_val[(long)b * p.amax_stride] = bv;
+  p.amax_idx[(long)b * p.amax_stride] = bi;
+  if constexpr (kScore) {
+    final_set_merge(rule5, m, s, mt, st);
     if (n < q.stride) {
       q.logprob[(long)b * q.stride + n] = logprob_of(bv, m, s);
       q.decision[(long)b * q.stride + n] = bi;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesParams p) { rules_body<kRulesPlain>(p, TsScoreParams{}, TsSampleParams{}); }
+
+__global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesParams p, TsScoreParams q) {
+  rules_body<kRulesScored>(p, q, TsSampleParams{});
+}
+
+__global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesParams p, TsScoreParams q, TsSampleParams r) {
+  rules_body<kRulesSampled>(p, q, r);
 }
 
 // log p(row[id]) over the whole row, one workgroup per row (the no-speech value on rows of the caller's)
@@ -505,9 +227,13 @@ void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s) {
   hipLaunchKernelGGL(timestamp_rules_kernel, dim3(p.batch), dim3(256), 0, s, p);
 }
 
+static bool score_params_ok(const TsRulesParams& p, const TsScoreParams& q) {
+  return q.logprob && q.decision && q.stride >= 1 && (!q.no_speech || (q.no_speech_id >= 0 && q.no_speech_id < p.n_vocab));
+}
+
 void launch_timestamp_rules_scored(const TsRulesParams& p, const TsScoreParams& q, hipStream_t s) {
   check_rules_params(p);
-  if (!q.logprob || !q.decision || q.stride < 1 || (q.no_speech && (q.no_speech_id < 0 || q.no_speech_id >= p.n_vocab))) {
+  if (!score_params_ok(p, q)) {
     fprintf(stderr, "[ax_whisper] launch_timestamp_rules_scored: bad score arrays / no-speech id %d\n", q.no_speech_id);
     abort();
   }
@@ -516,8 +242,7 @@ void launch_timestamp_rules_scored(const TsRulesParams& p, const TsScoreParams& 
 
 void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams& q, const TsSampleParams& r, hipStream_t s) {
   check_rules_params(p);
-  if (!q.logprob || !q.decision || q.stride < 1 || (q.no_speech && (q.no_speech_id < 0 || q.no_speech_id >= p.n_vocab)) || !r.temperature ||
-      !r.stream || !r.seed) {
+  if (!score_params_ok(p, q) || !r.temperature || !r.stream || !r.seed) {
     fprintf(stderr, "[ax_whisper] launch_timestamp_rules_sampled: bad score or sample arrays / no-speech id %d\n", q.no_speech_id);
     abort();
   }

@@ -982,6 +982,22 @@ void Engine::decode_greedy(DecodeMode mode, int batch, int max_new, const int* m
   timings[4] = (float)steps;
 }
 
+Engine::StagedRows Engine::stage_rows(const char* what, const float* logits, const int32_t* hist, const int* n_hist, int rows, hipStream_t s) {
+  const int nv = cfg_.n_vocab, Tc = cfg_.n_text_ctx;
+  for (int b = 0; hist && b < rows; ++b)
+    if (n_hist[b] < 0 || n_hist[b] > Tc) throw std::runtime_error(std::string(what) + ": n_hist out of range");
+  StagedRows r;
+  r.stride = ((long)nv + 3) / 4 * 4;
+  r.logits = device_array<float>((size_t)rows * r.stride);
+  HIP_CHECK(hipMemcpy2DAsync(r.logits, (size_t)r.stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, rows, hipMemcpyHostToDevice, s));
+  if (!hist) return r;
+  r.hist = device_array<int>((size_t)rows * Tc);
+  r.n_hist = device_array<int>(rows);
+  HIP_CHECK(hipMemcpyAsync(r.hist, hist, (size_t)rows * Tc * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(r.n_hist, n_hist, (size_t)rows * 4, hipMemcpyHostToDevice, s));
+  return r;
+}
+
 // The rules kernel alone, on host rows and histories (tests; callers with logits of their own)
 // logprob != nullptr: the scored kernel (each clip's entry at index 0 of a one-entry score row)
 void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int* n_hist, int batch, int32_t* chosen, float* logprob,
@@ -994,27 +1010,22 @@ void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int
   HIP_CHECK(hipSetDevice(device_));
   hipStream_t s = stream();
   const int nv = cfg_.n_vocab, Tc = cfg_.n_text_ctx;
-  const long stride = ((long)nv + 3) / 4 * 4;
-  for (int b = 0; b < batch; ++b)
-    if (n_hist[b] < 0 || n_hist[b] > Tc) throw std::runtime_error("apply_timestamp_rules: n_hist out of range");
+  const StagedRows in = stage_rows("apply_timestamp_rules", logits, hist, n_hist, batch, s);
   if (sample) {
     ensure_capacity(batch);  // (the sample arrays are per-slot buffers)
     upload_sample(*sample, batch);
   }
-  DeviceArray<float> b_lp, b_log = device_array<float>((size_t)batch * stride), b_val = device_array<float>(batch);
-  DeviceArray<int> b_dec, b_hist = device_array<int>((size_t)batch * Tc), b_n = device_array<int>(batch), b_idx = device_array<int>(batch);
+  DeviceArray<float> b_lp, b_val = device_array<float>(batch);
+  DeviceArray<int> b_dec, b_idx = device_array<int>(batch);
   if (logprob) {  // [batch][n_text_ctx + 1]: the kernel's index is the history length
     b_lp = device_array<float>((size_t)batch * (Tc + 1));
     b_dec = device_array<int>((size_t)batch * (Tc + 1));
   }
-  HIP_CHECK(hipMemcpy2DAsync(b_log, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(b_hist, hist, (size_t)batch * Tc * 4, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(b_n, n_hist, (size_t)batch * 4, hipMemcpyHostToDevice, s));
   TsRulesParams r{};
-  r.logits = b_log; r.stride = stride; r.batch = batch;
+  r.logits = in.logits; r.stride = in.stride; r.batch = batch;
   r.n_vocab = nv; r.eot = cfg_.eot; r.ts_begin = cfg_.no_timestamps + 1;
   r.off = nullptr; r.n_prefix = 3; r.done = nullptr;
-  r.out_ids = b_hist; r.n_out = b_n; r.n_ctx = Tc;
+  r.out_ids = in.hist; r.n_out = in.n_hist; r.n_ctx = Tc;
   r.amax_val = b_val; r.amax_idx = b_idx; r.amax_stride = 1;
   if (sample) launch_timestamp_rules_sampled(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, own_sample_, s);
   else if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, s);
@@ -1034,11 +1045,9 @@ void Engine::no_speech_logprob(const float* logits, int batch, float* out) {
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   hipStream_t s = stream();
-  const int nv = cfg_.n_vocab;
-  const long stride = ((long)nv + 3) / 4 * 4;
-  DeviceArray<float> b_log = device_array<float>((size_t)batch * stride), b_out = device_array<float>(batch);
-  HIP_CHECK(hipMemcpy2DAsync(b_log, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, batch, hipMemcpyHostToDevice, s));
-  launch_row_logprob(b_log, stride, nv, (int)cfg_.ints.at("no_speech"), batch, b_out, s);
+  const StagedRows in = stage_rows("no_speech_logprob", logits, nullptr, nullptr, batch, s);
+  DeviceArray<float> b_out = device_array<float>(batch);
+  launch_row_logprob(in.logits, in.stride, cfg_.n_vocab, (int)cfg_.ints.at("no_speech"), batch, b_out, s);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(out, b_out, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));

@@ -238,6 +238,11 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void enqueue_timestamp_rules(const StepSpec& spec, int batch, const int* d_forced, int n_forced, hipStream_t s);
   long ts_stride_ = 0;
   void require_scored_vocab() const;  // require_timestamp_vocab + a usable no_speech id
+  // What the kernels-alone entry points hand their kernel: host rows [rows][n_vocab] on the device at a stride of whole 16-byte
+  // chunks, with their histories [rows][n_text_ctx] and lengths (hist == nullptr: the rows alone), copied on the stream.
+  // Throws "<what>: n_hist out of range" before it allocates or copies anything.
+  struct StagedRows { DeviceArray<float> logits; DeviceArray<int> hist, n_hist; long stride = 0; };
+  StagedRows stage_rows(const char* what, const float* logits, const int32_t* hist, const int* n_hist, int rows, hipStream_t s);
   void ensure_ts_scores();
   // checks a SampleSpec of `batch` clips and puts it into the engine's own arrays (on the stream, before the steps that read them)
   void upload_sample(const SampleSpec& sample, int batch);

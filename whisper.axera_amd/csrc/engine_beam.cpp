@@ -235,22 +235,16 @@ void Engine::beam_candidates(const float* logits, const int32_t* hist, const int
   require_timestamp_vocab();
   if (rows < 1 || !logits || !hist || !n_hist || !cand_id || !cand_logprob || !n_cand || n_cand_max < 1 || n_cand_max > kBeamMaxCand)
     throw std::runtime_error("beam_candidates: bad arguments (1 .. " + std::to_string(kBeamMaxCand) + " candidates per row)");
-  const int nv = cfg_.n_vocab, Tc = cfg_.n_text_ctx, M = n_cand_max;
-  for (int b = 0; b < rows; ++b)
-    if (n_hist[b] < 0 || n_hist[b] > Tc) throw std::runtime_error("beam_candidates: n_hist out of range");
+  const int M = n_cand_max;
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   hipStream_t s = stream();
-  const long stride = ((long)nv + 3) / 4 * 4;
-  DeviceArray<float> b_log = device_array<float>((size_t)rows * stride), b_lp = device_array<float>((size_t)rows * M);
-  DeviceArray<int> b_hist = device_array<int>((size_t)rows * Tc), b_n = device_array<int>(rows), b_id = device_array<int>((size_t)rows * M),
-                   b_nc = device_array<int>(rows);
-  HIP_CHECK(hipMemcpy2DAsync(b_log, (size_t)stride * 4, logits, (size_t)nv * 4, (size_t)nv * 4, rows, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(b_hist, hist, (size_t)rows * Tc * 4, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(b_n, n_hist, (size_t)rows * 4, hipMemcpyHostToDevice, s));
+  const StagedRows in = stage_rows("beam_candidates", logits, hist, n_hist, rows, s);
+  DeviceArray<float> b_lp = device_array<float>((size_t)rows * M);
+  DeviceArray<int> b_id = device_array<int>((size_t)rows * M), b_nc = device_array<int>(rows);
   BeamCandParams c{};
-  c.logits = b_log; c.stride = stride; c.n_slots = rows; c.n_vocab = nv; c.eot = cfg_.eot; c.ts_begin = cfg_.no_timestamps + 1;
-  c.hist = b_hist; c.hist_stride = Tc; c.n_hist = b_n; c.beam = 1; c.n_cand_max = M;
+  c.logits = in.logits; c.stride = in.stride; c.n_slots = rows; c.n_vocab = cfg_.n_vocab; c.eot = cfg_.eot; c.ts_begin = cfg_.no_timestamps + 1;
+  c.hist = in.hist; c.hist_stride = cfg_.n_text_ctx; c.n_hist = in.n_hist; c.beam = 1; c.n_cand_max = M;
   c.cand_id = b_id; c.cand_logprob = b_lp; c.n_cand = b_nc;
   launch_beam_candidates(c, s);
   HIP_CHECK(hipGetLastError());
