@@ -1,5 +1,6 @@
-"""The process side of the stand-alone decode kernel tests (tests/test_gpu_decode_kernels.py, tests/test_gpu_gemv_kernels.py):
-building tests/cpp/decode_kernels_driver.cpp against the shipped objects, and running one driver process over a list of groups."""
+"""The process side of the stand-alone kernel tests (tests/test_gpu_decode_kernels.py, tests/test_gpu_gemv_kernels.py,
+tests/test_gpu_frontend_kernels.py): building a driver of tests/cpp/ against the shipped objects, and running one driver process over a
+list of groups."""
 import os
 import subprocess
 import time
@@ -24,12 +25,13 @@ class Session:
         self.worst = {}
 
 
-def driver_exe(dt):
-    """build/decode_kernels_driver.<dt>, relinked whenever it is older than its source or the objects it links."""
-    exe = os.path.join(BUILD, "decode_kernels_driver." + dt)
-    src = os.path.join(ROOT, "tests", "cpp", "decode_kernels_driver.cpp")
-    objs = [os.path.join(BUILD, f"{k}.{dt}.o") for k in LINKED]
-    srcs = [src] + [os.path.join(PKG, "csrc", f) for f in [k + ".hip" for k in LINKED] + ["common.hpp", "decode_layout.hpp"]]
+def driver_exe(dt, source="decode_kernels_driver.cpp", linked=LINKED, also=("common.hpp", "decode_layout.hpp")):
+    """build/<source's name>.<dt> from tests/cpp/<source>, relinked whenever it is older than its source or the objects it links
+    (build/<k>.<dt>.o for k in linked; `also`: further files of csrc/ the kernels are made of)."""
+    exe = os.path.join(BUILD, os.path.splitext(source)[0] + "." + dt)
+    src = os.path.join(ROOT, "tests", "cpp", source)
+    objs = [os.path.join(BUILD, f"{k}.{dt}.o") for k in linked]
+    srcs = [src] + [os.path.join(PKG, "csrc", f) for f in [k + ".hip" for k in linked] + list(also)]
     newest = max(os.path.getmtime(f) for f in srcs + [o for o in objs if os.path.exists(o)])
     if os.path.exists(exe) and os.path.getmtime(exe) >= newest:
         return exe

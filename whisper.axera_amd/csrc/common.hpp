@@ -262,8 +262,8 @@ struct FrontendParams {
   const float* twiddle;    // device [400][2] cos,sin
   const float* window;     // device [400]
   const float* mel_basis;  // device [n_mels][201]
-  float* power;            // device scratch [batch][n_frames_max][208]
-  float* logmel;           // device scratch [batch][n_mels][3008]
+  float* power;            // unused: read by no kernel, set by no caller (the power spectrum stays in LDS)
+  float* logmel;           // device scratch [batch][3000][n_mels]: log10 of the mel sums, before clamp and scale
   unsigned* gmax;          // device [batch] (float bits, ordered-int encoded)
   float* mel_ref;          // device [batch][n_mels][3000] f32 (reference layout) or nullptr
   h16* mel_tm;            // device [batch][mel_rows][n_mels] h16 time-major, row 0 = left pad, or nullptr
