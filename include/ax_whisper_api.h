@@ -533,6 +533,69 @@ AX_WHISPER_API int AX_WHISPER_BeamFinalize(int clips, int beam_size, int n, int 
 AX_WHISPER_API int AX_WHISPER_PersistentDecodePlan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots,
                                                    int* plan4, int* units);
 
+/* ---- Word-level timestamps (DESIGN.md "Word-level timestamps"): openai-whisper's word_timestamps=True for one window. The cross-attention
+ *  weights of a teacher-forced pass over [sot, language, task, notimestamps, text ids, eot] are normalised, median-filtered and averaged
+ *  over the alignment heads; dynamic time warping on the result gives the frame (20 ms) at which every text token begins. */
+/** Clips in, words out. ids [batch][n_text_ctx], n_ids [batch]: the greedy timestamp decode (AX_WHISPER_RunPCMBatchTimestampTokens'
+ *  ids; under lang / task, either may be NULL, AX_WHISPER_RunPCMBatchTimestampLang's, lang_out [batch] or NULL the language index each
+ *  clip was decoded under). Per clip b, with row stride n_max: n_segments[b] segments (AX_WHISPER_SplitSegments' of the ids), seg_start / seg_end [batch][n_max] in
+ *  seconds AFTER the word rule has moved them; n_words[b] words: word_segment (index among those segments), word_start, word_end
+ *  (seconds, rounded to 0.01), word_prob, and word_text_end: word w's bytes are text[b][word_text_end[w-1] .. word_text_end[w]) (0 for
+ *  w = 0); text[b] is malloc'ed, the caller frees every non-NULL entry, also after a failure. jump [batch][n_text_ctx] and
+ *  token_logprob [batch][n_text_ctx] (either may be NULL): what the words were made from, as AX_WHISPER_AlignTokens returns them for
+ *  the clip's text ids (the ids below eot of its segments, in order). -1 when a clip has more than n_max words or segments. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchWordTimestamps(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                                        int max_new, const int* lang, const int* task, int32_t* ids, int* n_ids, int* lang_out,
+                                                        int n_max, int* n_segments, double* seg_start, double* seg_end, int* n_words,
+                                                        int* word_segment, int* word_text_end, double* word_start, double* word_end,
+                                                        float* word_prob, char** text, int* jump, float* token_logprob);
+/** Stage level, after AX_WHISPER_EncodeMel: the alignment of slots [0, batch). Clip b: n_ids[b] text ids (below eot) at ids + b * stride,
+ *  num_frames[b] mel frames of its own (min(samples / 160, 3000): it aligns against num_frames[b] / 2 encoder frames), lang[b] (an index
+ *  of the language list, -1 or a NULL array: the handle's), task[b] (0 transcribe, 1 translate; NULL: 0). Out: jump [batch][stride + 1]
+ *  (n_ids[b] + 1 entries: the frame at which each text token, and the closing eot, begins), token_logprob [batch][stride] (log-softmax
+ *  over the ids below eot), matrix (or NULL) [batch][m_rows][m_ld]: rows [0, n_ids[b] + 5) x frames [0, num_frames[b] / 2), the rest is
+ *  not touched. A clip with n_ids[b] == 0 gets nothing; n_ids[b] + 5 > n_text_ctx is an error. The slots' self-attention caches are
+ *  overwritten, nothing else a later decode reads. AX_WHISPER_WORD_ALIGN=host: normalisation, median and path on the host (the
+ *  yardstick); GetConfigInt "word_align" = 0 the kernels, 1 the host. */
+AX_WHISPER_API int AX_WHISPER_AlignTokens(AX_WHISPER_HANDLE handle, int batch, const int32_t* ids, int stride, const int* n_ids,
+                                          const int* num_frames, const int* lang, const int* task, int* jump, float* token_logprob,
+                                          float* matrix, int m_rows, int m_ld);
+/** The alignment heads of a handle: n (layer, head) pairs; n == 0 restores what the handle was constructed with. That is the optional
+ *  key "alignment_heads": [[layer, head], ...] of {type}_config.json (tools/convert_weights.py --hf copies it from the checkpoint's
+ *  generation_config.json), else every head of the upper half of the layers. GetConfigInt "n_alignment_heads" counts the list in use. */
+AX_WHISPER_API int AX_WHISPER_SetAlignmentHeads(AX_WHISPER_HANDLE handle, const int* pairs, int n);
+/** Host only: the list a handle constructed from this config file starts with, as n (layer, head) pairs (at most n_max); -1 on a
+ *  list that names a head the decoder does not have, names one twice or is not a list of pairs. */
+AX_WHISPER_API int AX_WHISPER_ConfigAlignmentHeads(const char* config_path, int n_max, int* pairs, int* n);
+/** One alignment kernel alone on host data (the handle gives the device and the 16-bit type). Clip c has len[c] rows and n_keys[c] frames.
+ *  QKSoftmax: q fp32 [rows][64 n_head] (clip c's rows from row0[c]), k fp32 [n_slots][n_head][keys_pad][64] (clip c reads slot[c]), both
+ *  narrowed to the 16-bit type; heads [n_align]; P [n_clips][n_align][rows_pad][f_pad] in and out (f_pad a multiple of 64): row i < len[c],
+ *  frames up to the end of the last 64-frame block are written, the rest keeps what it held.
+ *  Normalize: matrix [n_clips][m_rows][m_ld] += inv_heads * (normalised, median-filtered P) summed over the n_align heads.
+ *  DTW: jump [n_clips][jump_ld], len[c] - 4 entries per clip: the path over -matrix[c][3 .. len[c] - 2]. */
+AX_WHISPER_API int AX_WHISPER_AlignQKSoftmax(AX_WHISPER_HANDLE handle, int n_clips, const int* len, const int* n_keys, const float* q, int rows,
+                                             int n_head, const int* row0, const float* k, int n_slots, int keys_pad, const int* slot,
+                                             const int* heads, int n_align, float* P, int rows_pad, int f_pad);
+AX_WHISPER_API int AX_WHISPER_AlignNormalize(AX_WHISPER_HANDLE handle, int n_clips, const int* len, const int* n_keys, const float* P, int n_align,
+                                             int rows_pad, int f_pad, float inv_heads, float* matrix, int m_rows, int m_ld);
+AX_WHISPER_API int AX_WHISPER_AlignDTW(AX_WHISPER_HANDLE handle, int n_clips, const int* len, const int* n_keys, const float* matrix, int m_rows,
+                                       int m_ld, int* jump, int jump_ld);
+/** Host only: matrix [n_rows][n_frames] (row stride ld floats) -> jump [n_rows], the frame of the first path point of every row:
+ *  dynamic time warping on -matrix with fp32 accumulation (one add per cell; ties go left), openai-whisper's dtw + backtrace. */
+AX_WHISPER_API int AX_WHISPER_AlignPath(const float* matrix, int n_rows, int n_frames, int ld, int* jump);
+/** Host only: openai-whisper's split_to_word_tokens over a tokens file. ids + language code -> word_tokens [n_words] (ids per word) and
+ *  the words' bytes (text malloc'ed, word w ends at byte word_text_end[w]). An id at or above eot has no text and starts a word. */
+AX_WHISPER_API int AX_WHISPER_SplitWords(const char* tokens_path, const int32_t* ids, int n, int eot, const char* language, int n_max,
+                                         int* word_tokens, int* word_text_end, int* n_words, char** text, int* n_bytes);
+/** Host only: the words of one window from its alignment: word split, word times from jump [n + 1], probabilities from token_logprob [n],
+ *  merge_punctuations and the heuristics of openai-whisper's add_word_timestamps. ids: the n text ids of the window's n_seg segments
+ *  in order, seg_tokens[s] of them in segment s; seg_start / seg_end are updated in place. Outputs as AX_WHISPER_RunPCMBatchWordTimestamps'. */
+AX_WHISPER_API int AX_WHISPER_WordsFromAlignment(const char* tokens_path, const int32_t* ids, int n, int eot, const char* language,
+                                                 const int* seg_tokens, double* seg_start, double* seg_end, int n_seg, const int* jump,
+                                                 const float* token_logprob, double last_speech_timestamp, int n_max, int* word_segment,
+                                                 int* word_text_end, double* word_start, double* word_end, float* word_prob, int* n_words,
+                                                 char** text, int* n_bytes);
+
 /** Stage timings of the last Run* / DecodeGreedy* call, ms (hipEvent): [0] front-end, [1] encoder,
  *  [2] decode loop, [3] whole call (wall), [4] decode steps executed. */
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
@@ -544,7 +607,8 @@ AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
  *  "beam_bench_complete_clips" say how many slots the reorder launches copied in all, over how many iterations, and how many clips
  *  had completed), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
  *  files of `arg` seconds + one window kernel), "prefill" (reset + PrefillPrompts of `batch` slots with prompts of arg - 3 ids each,
- *  i.e. context length L = arg, by the handle's route), or a kernel name listed in DESIGN.md. */
+ *  i.e. context length L = arg, by the handle's route), "word_align" / "word_align_host" (AlignTokens of `batch` slots with `arg` text ids
+ *  each against all frames, by the kernels / by the host route; host wall time), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);
 

@@ -1,0 +1,34 @@
+"""CPU: the word-alignment kernels (csrc/decode_align.hip) compile for gfx950, in both builds, without scratch memory or register
+spills (tests/test_kernel_resources.py says why that is a test), and each stays within the registers and the LDS of its build
+(DESIGN.md "Word-level timestamps": 72 / 90 / 25 registers (vector and accumulator), 50 / 40 / 30 SGPRs, 0 / 1536 / 6144 bytes of LDS)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "whisper.axera_amd", "csrc")
+
+#                       VGPRs, SGPRs, LDS bytes: ceilings a little above what the build takes (VGPRs and SGPRs in steps of 8)
+CEILINGS = {"align_qk_softmax": (80, 56, 0), "align_normalize": (96, 48, 1536), "align_dtw": (32, 32, 6144), "row_id_logprob": (24, 32, 32)}
+
+
+@pytest.mark.parametrize("f16", [0, 1], ids=["bf16", "fp16"])
+def test_no_scratch_no_spills_and_ceilings(f16, tmp_path):
+    out = tmp_path / "decode_align.s"
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                        f"-DAXW_F16={f16}", "--cuda-device-only", "-S", "-o", str(out), os.path.join(CSRC, "decode_align.hip")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    text = out.read_text()
+    field = lambda k: [int(x) for x in re.findall(r"^\s+\." + k + r":\s+(\d+)", text, re.M)]
+    names = re.findall(r"^\s+\.name:\s+(\S+)", text, re.M)
+    short = [next(k for k in CEILINGS if k + "_kernel" in n) for n in names]
+    assert sorted(short) == sorted(CEILINGS)
+    assert field("private_segment_fixed_size") == [0] * 4 and field("vgpr_spill_count") == [0] * 4 and field("sgpr_spill_count") == [0] * 4
+    for i, k in enumerate(short):
+        vg, sg, lds = CEILINGS[k]
+        got = (field("vgpr_count")[i], field("sgpr_count")[i], field("group_segment_fixed_size")[i])
+        assert got[0] <= vg and got[1] <= sg and got[2] == lds, (k, got)
+    assert "v_mfma_f32_16x16x32" in text

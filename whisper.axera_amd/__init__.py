@@ -26,6 +26,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ax_whisper_api.h"
 
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int32)
+_dblp = C.POINTER(C.c_double)
 _lib = None
 
 # name -> (restype, argtypes): every symbol include/ax_whisper_api.h declares
@@ -128,6 +129,24 @@ SYMBOLS = {
                                              C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "AX_WHISPER_TranscriptLang": (C.c_int, [C.c_void_p, ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_PersistentDecodePlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMBatchWordTimestamps": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), ip,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), _dblp, _dblp, C.POINTER(C.c_int),
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_int), _dblp, _dblp, fp, C.POINTER(C.c_void_p), C.POINTER(C.c_int), fp]),
+    "AX_WHISPER_AlignTokens": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), fp, fp, C.c_int, C.c_int]),
+    "AX_WHISPER_SetAlignmentHeads": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "AX_WHISPER_ConfigAlignmentHeads": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_AlignQKSoftmax": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.POINTER(C.c_int), fp, C.c_int,
+                                            C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, fp, C.c_int, C.c_int]),
+    "AX_WHISPER_AlignNormalize": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.c_int, C.c_float, fp, C.c_int,
+                                            C.c_int]),
+    "AX_WHISPER_AlignDTW": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "AX_WHISPER_AlignPath": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "AX_WHISPER_SplitWords": (C.c_int, [C.c_char_p, ip, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "AX_WHISPER_WordsFromAlignment": (C.c_int, [C.c_char_p, ip, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), _dblp, _dblp, C.c_int, C.POINTER(C.c_int), fp,
+                                                C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dblp, _dblp, fp, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
 }
 
 
@@ -302,6 +321,83 @@ _cip = C.POINTER(C.c_int)
 
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _ci(a):
+    """int32 array -> the `int*` of the C ABI"""
+    return a.ctypes.data_as(_cip)
+
+
+def _word_texts(L, out, n_bytes, text_end, n):
+    """the malloc'ed bytes of n words, word w ending at byte text_end[w] -> [bytes]; frees the buffer"""
+    b = C.string_at(out.value, n_bytes) if out.value else b""
+    if out.value:
+        L._free(out.value)
+    ends = [0] + [int(e) for e in text_end[:n]]
+    return [b[ends[w]: ends[w + 1]] for w in range(n)]
+
+
+def config_alignment_heads(config_path: str):
+    """Host only (AX_WHISPER_ConfigAlignmentHeads): the [(layer, head)] a handle constructed from this {type}_config.json starts
+    with: its "alignment_heads" key, else every head of the upper half of the decoder layers."""
+    L = load_library()
+    n_max = 4096
+    pairs, n = np.zeros(2 * n_max, dtype=np.int32), C.c_int()
+    if L.AX_WHISPER_ConfigAlignmentHeads(os.fspath(config_path).encode(), n_max, _ci(pairs), C.byref(n)) != 0:
+        raise RuntimeError("AX_WHISPER_ConfigAlignmentHeads failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return [(int(pairs[2 * i]), int(pairs[2 * i + 1])) for i in range(n.value)]
+
+
+def align_path(matrix) -> np.ndarray:
+    """Host only (AX_WHISPER_AlignPath): matrix [rows][frames] -> jump [rows], the frame of the first point of every row on the
+    DTW path over -matrix (fp32 accumulation, ties go left)."""
+    L = load_library()
+    m = _f32(matrix)
+    if m.ndim != 2:
+        raise ValueError("a [rows][frames] matrix")
+    jump = np.zeros(m.shape[0], dtype=np.int32)
+    if L.AX_WHISPER_AlignPath(m.ctypes.data_as(fp), m.shape[0], m.shape[1], m.shape[1], _ci(jump)) != 0:
+        raise RuntimeError("AX_WHISPER_AlignPath failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return jump
+
+
+def split_words(tokens_path: str, ids, eot: int, language: str):
+    """Host only (AX_WHISPER_SplitWords): openai-whisper's split_to_word_tokens -> [(word bytes, [ids])]."""
+    L = load_library()
+    a = _i32(ids).reshape(-1)
+    n_max = max(len(a), 1)
+    wt, te = np.zeros(n_max, dtype=np.int32), np.zeros(n_max, dtype=np.int32)
+    n, nb, out = C.c_int(), C.c_int(), C.c_void_p()
+    if L.AX_WHISPER_SplitWords(os.fspath(tokens_path).encode(), a.ctypes.data_as(ip), len(a), int(eot), language.encode(), n_max, _ci(wt), _ci(te),
+                               C.byref(n), C.byref(out), C.byref(nb)) != 0:
+        raise RuntimeError("AX_WHISPER_SplitWords failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    texts = _word_texts(L, out, nb.value, te, n.value)
+    ends = np.concatenate([[0], np.cumsum(wt[: n.value])])
+    return [(texts[w], a[ends[w]: ends[w + 1]].tolist()) for w in range(n.value)]
+
+
+def words_from_alignment(tokens_path: str, ids, eot: int, language: str, seg_tokens, seg_start, seg_end, jump, token_logprob,
+                         last_speech_timestamp: float = 0.0):
+    """Host only (AX_WHISPER_WordsFromAlignment): the words of one window -> ([(segment, word bytes, start, end, probability)],
+    seg_start, seg_end after the rule)."""
+    L = load_library()
+    a, st_n = _i32(ids).reshape(-1), _i32(seg_tokens).reshape(-1)
+    ss, se = np.array(seg_start, dtype=np.float64).reshape(-1), np.array(seg_end, dtype=np.float64).reshape(-1)
+    j, lp = _i32(jump).reshape(-1), _f32(token_logprob).reshape(-1)
+    if len(j) < len(a) + 1 or len(lp) < len(a) or len(ss) != len(st_n) or len(se) != len(st_n):
+        raise ValueError("jump needs len(ids) + 1 entries, token_logprob len(ids), the segment arrays one entry per segment")
+    n_max = len(a) + 1
+    wseg, te = np.zeros(n_max, dtype=np.int32), np.zeros(n_max, dtype=np.int32)
+    ws, we, wp = np.zeros(n_max, dtype=np.float64), np.zeros(n_max, dtype=np.float64), np.zeros(n_max, dtype=np.float32)
+    n, nb, out = C.c_int(), C.c_int(), C.c_void_p()
+    rc = L.AX_WHISPER_WordsFromAlignment(os.fspath(tokens_path).encode(), a.ctypes.data_as(ip), len(a), int(eot), language.encode(), _ci(st_n),
+                                         ss.ctypes.data_as(_dblp), se.ctypes.data_as(_dblp), len(st_n), _ci(j), lp.ctypes.data_as(fp),
+                                         float(last_speech_timestamp), n_max, _ci(wseg), _ci(te), ws.ctypes.data_as(_dblp), we.ctypes.data_as(_dblp),
+                                         wp.ctypes.data_as(fp), C.byref(n), C.byref(out), C.byref(nb))
+    if rc != 0:
+        raise RuntimeError("AX_WHISPER_WordsFromAlignment failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    texts = _word_texts(L, out, nb.value, te, n.value)
+    return [(int(wseg[w]), texts[w], float(ws[w]), float(we[w]), np.float32(wp[w])) for w in range(n.value)], ss, se
 
 
 def beam_finalize(hist, S, slot, pool_n, pool_ids, pool_len, pool_score, n: int):
@@ -804,6 +900,116 @@ class Whisper:
                     pool_score=pool_score, complete=complete, tok=tok, src=src, slot_score=ss, n_completed=done.value)
 
     beam_finalize = staticmethod(beam_finalize)
+
+    # ---- word-level timestamps (DESIGN.md "Word-level timestamps")
+    def set_alignment_heads(self, pairs=None):
+        """AX_WHISPER_SetAlignmentHeads: [(layer, head)]; None or empty restores what the handle was constructed with (the config file's
+        "alignment_heads", else every head of the upper half of the layers)."""
+        p = _i32(pairs if pairs else []).reshape(-1)
+        self._check(self.L.AX_WHISPER_SetAlignmentHeads(self.h, _ci(p) if len(p) else None, len(p) // 2), "SetAlignmentHeads")
+
+    def align_tokens(self, ids, num_frames, languages=None, tasks=None, want_matrix: bool = False):
+        """Stage level, after encode_mel of len(ids) clips (AX_WHISPER_AlignTokens): per clip its text ids and its own mel frame count ->
+        [dict(jump [n + 1], token_logprob [n], matrix [n + 5][frames // 2] if asked for)]. A clip without ids: empty arrays."""
+        B = len(ids)
+        stride = max(max((len(x) for x in ids), default=1), 1)
+        a = np.zeros((B, stride), dtype=np.int32)
+        for b, x in enumerate(ids):
+            a[b, : len(x)] = x
+        n = _i32([len(x) for x in ids])
+        fr = _i32(num_frames).reshape(-1)
+        if len(fr) != B:
+            raise ValueError("one frame count per clip")
+        lang, task = self._lang_args(B, languages, tasks)
+        jump = np.zeros((B, stride + 1), dtype=np.int32)
+        lp = np.zeros((B, stride), dtype=np.float32)
+        m_rows, m_ld = stride + 5, max(int(fr.max()) // 2, 1)
+        matrix = np.full((B, m_rows, m_ld), np.nan, dtype=np.float32) if want_matrix else None
+        self._check(self.L.AX_WHISPER_AlignTokens(self.h, B, a.ctypes.data_as(ip), stride, _ci(n), _ci(fr), lang, task, _ci(jump), lp.ctypes.data_as(fp),
+                                                  matrix.ctypes.data_as(fp) if want_matrix else None, m_rows, m_ld), "AlignTokens")
+        out = []
+        for b in range(B):
+            k = int(n[b])
+            o = dict(jump=jump[b, : k + 1].copy() if k else jump[b, :0].copy(), token_logprob=lp[b, :k].copy())
+            if want_matrix:
+                o["matrix"] = matrix[b, : k + 5, : int(fr[b]) // 2].copy() if k else matrix[b, :0, :0].copy()
+            out.append(o)
+        return out
+
+    def align_qk_softmax(self, q, k, row0, length, n_keys, slot, heads, rows_pad: int, f_pad: int, fill: float = np.nan):
+        """align_qk_softmax_kernel alone (AX_WHISPER_AlignQKSoftmax): q [rows][64 n_head], k [n_slots][n_head][keys_pad][64] ->
+        P [n_clips][len(heads)][rows_pad][f_pad], prefilled with `fill`."""
+        q, k = _f32(q), _f32(k)
+        n = len(length)
+        P = np.full((n, len(heads), rows_pad, f_pad), fill, dtype=np.float32)
+        ln, nk, r0, sl, hd = _i32(length), _i32(n_keys), _i32(row0), _i32(slot), _i32(heads)
+        self._check(self.L.AX_WHISPER_AlignQKSoftmax(self.h, n, _ci(ln), _ci(nk), q.ctypes.data_as(fp), q.shape[0], k.shape[1], _ci(r0), k.ctypes.data_as(fp),
+                                                     k.shape[0], k.shape[2], _ci(sl), _ci(hd), len(hd), P.ctypes.data_as(fp), rows_pad, f_pad),
+                    "AlignQKSoftmax")
+        return P
+
+    def align_normalize(self, P, length, n_keys, matrix, inv_heads: float):
+        """align_normalize_kernel alone (AX_WHISPER_AlignNormalize): P [n_clips][n_align][rows_pad][f_pad], matrix [n_clips][m_rows][m_ld]
+        -> the matrix with the layer's contribution added."""
+        P, m = _f32(P), _f32(matrix).copy()
+        ln, nk = _i32(length), _i32(n_keys)
+        self._check(self.L.AX_WHISPER_AlignNormalize(self.h, P.shape[0], _ci(ln), _ci(nk), P.ctypes.data_as(fp), P.shape[1], P.shape[2], P.shape[3],
+                                                     float(inv_heads), m.ctypes.data_as(fp), m.shape[1], m.shape[2]), "AlignNormalize")
+        return m
+
+    def align_dtw(self, matrix, length, n_keys, fill: int = -1):
+        """align_dtw_kernel alone (AX_WHISPER_AlignDTW): matrix [n_clips][m_rows][m_ld] -> jump [n_clips][m_rows] (length[c] - 4 entries
+        per clip, the rest keeps `fill`)."""
+        m = _f32(matrix)
+        ln, nk = _i32(length), _i32(n_keys)
+        jump = np.full((m.shape[0], m.shape[1]), fill, dtype=np.int32)
+        self._check(self.L.AX_WHISPER_AlignDTW(self.h, m.shape[0], _ci(ln), _ci(nk), m.ctypes.data_as(fp), m.shape[1], m.shape[2], _ci(jump), jump.shape[1]),
+                    "AlignDTW")
+        return jump
+
+    def run_word_timestamps_batch(self, clips, languages=None, tasks=None, max_new: int = 0):
+        """AX_WHISPER_RunPCMBatchWordTimestamps: per clip dict(ids, text_ids (the aligned ids), language, segments [(start, end, text,
+        [(word, start, end, probability)])], jump, token_logprob). Words are text decoded with errors="replace"; `words_bytes` holds them as bytes
+        with their segment index."""
+        clips, B, ptrs, lens, _ = self._clip_args(clips)
+        lang, task = self._lang_args(B, languages, tasks)
+        Tc = self.n_text_ctx
+        ids = np.zeros((B, Tc), dtype=np.int32)
+        n, lout, nseg, nw = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+        ss, se = np.zeros((B, Tc), dtype=np.float64), np.zeros((B, Tc), dtype=np.float64)
+        wseg, wte = np.zeros((B, Tc), dtype=np.int32), np.zeros((B, Tc), dtype=np.int32)
+        ws, we, wp = np.zeros((B, Tc), dtype=np.float64), np.zeros((B, Tc), dtype=np.float64), np.zeros((B, Tc), dtype=np.float32)
+        text = (C.c_void_p * B)()
+        jump, lp = np.zeros((B, Tc), dtype=np.int32), np.zeros((B, Tc), dtype=np.float32)
+        rc = self.L.AX_WHISPER_RunPCMBatchWordTimestamps(self.h, ptrs, lens, B, max_new, lang, task, ids.ctypes.data_as(ip), n, lout, Tc, nseg,
+                                                         ss.ctypes.data_as(_dblp), se.ctypes.data_as(_dblp), nw, _ci(wseg), _ci(wte), ws.ctypes.data_as(_dblp),
+                                                         we.ctypes.data_as(_dblp), wp.ctypes.data_as(fp), text, _ci(jump), lp.ctypes.data_as(fp))
+        texts = []
+        for b in range(B):  # (non-NULL entries are the caller's to free, also after a failure)
+            out = C.c_void_p(text[b])
+            texts.append(_word_texts(self.L, out, int(wte[b, nw[b] - 1]) if rc == 0 and nw[b] > 0 else 0, wte[b], nw[b] if rc == 0 else 0))
+        self._check(rc, "RunPCMBatchWordTimestamps")
+        res = []
+        for b in range(B):
+            row = ids[b, : n[b]]
+            spans = split_segments(row.tolist(), self.timestamp_begin, self.eot, min(len(clips[b]) / 16000.0, 30.0))
+            text_ids = [int(t) for (_, _, tb, te) in spans for t in row[tb:te] if t < self.eot][: Tc - 5]
+            n_text = len(text_ids)
+            wb = [(int(wseg[b, w]), texts[b][w], float(ws[b, w]), float(we[b, w]), np.float32(wp[b, w])) for w in range(nw[b])]
+            segs = []
+            for k in range(nseg[b]):
+                words = [(t.decode("utf-8", errors="replace"), s, e, float(p)) for (sg, t, s, e, p) in wb if sg == k]
+                segs.append((float(ss[b, k]), float(se[b, k]), "".join(w[0] for w in words), words))
+            res.append(dict(ids=row.tolist(), text_ids=text_ids, language=self.language_code(lout[b]), segments=segs, words_bytes=wb,
+                            jump=jump[b, : n_text + 1].copy(), token_logprob=lp[b, :n_text].copy()))
+        return res
+
+    def run_word_timestamps(self, audio, language=None):
+        """One clip (PCM or a wav path) -> [(start, end, text, [(word, start, end, probability)])], openai-whisper's word_timestamps=True
+        for one window; language: a code, None (the handle's) or "auto"."""
+        if isinstance(audio, (str, os.PathLike)):
+            audio, _, _ = load_audio_file(audio)
+        return self.run_word_timestamps_batch([audio], None if language is None else [language])[0]["segments"]
 
     def segments(self, ids, num_samples: int):
         """[(start_s, end_s, text)] of one clip's timestamp-mode ids."""

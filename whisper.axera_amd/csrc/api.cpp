@@ -26,6 +26,7 @@
 #include "host_io.hpp"
 #include "t2s.hpp"
 #include "multi_device.hpp"
+#include "words.hpp"
 
 using Engine = axw::IEngine;
 
@@ -1130,6 +1131,234 @@ AX_WHISPER_API int AX_WHISPER_StreamCollect(AX_WHISPER_HANDLE handle, int slot, 
 }
 AX_WHISPER_API int AX_WHISPER_StreamClose(AX_WHISPER_HANDLE handle) {
   return guarded(handle, [&](Engine& e) { e.stream_close(); });
+}
+
+// ---- word-level timestamps (DESIGN.md "Word-level timestamps")
+// Host only: matrix [n_rows][n_frames] (row stride ld floats) -> jump [n_rows] (words.hpp: align_path)
+AX_WHISPER_API int AX_WHISPER_AlignPath(const float* matrix, int n_rows, int n_frames, int ld, int* jump) {
+  if (!matrix || !jump || n_rows < 1 || n_frames < 1 || ld < n_frames) return -1;
+  return guarded_host([&] {
+    axw::align_path(matrix, n_rows, n_frames, ld, jump);
+    return 0;
+  });
+}
+
+// words -> the caller's arrays: the texts concatenated into one malloc'ed buffer, word w ending at byte text_end[w]
+static int emit_word_text(const std::vector<const std::string*>& words, int* text_end, char** text, int* n_bytes) {
+  std::string all;
+  for (size_t w = 0; w < words.size(); ++w) {
+    all += *words[w];
+    text_end[w] = (int)all.size();
+  }
+  *text = static_cast<char*>(malloc(all.size() + 1));
+  if (!*text) return -1;
+  memcpy(*text, all.data(), all.size());
+  (*text)[all.size()] = 0;
+  *n_bytes = (int)all.size();
+  return 0;
+}
+
+AX_WHISPER_API int AX_WHISPER_SplitWords(const char* tokens_path, const int32_t* ids, int n, int eot, const char* language, int n_max,
+                                         int* word_tokens, int* word_text_end, int* n_words, char** text, int* n_bytes) {
+  if (!tokens_path || (n > 0 && !ids) || n < 0 || !language || n_max < 0 || (n_max > 0 && (!word_tokens || !word_text_end)) || !n_words || !text || !n_bytes)
+    return -1;
+  *text = nullptr;
+  *n_words = *n_bytes = 0;
+  return guarded_host([&] {
+    const std::vector<std::string> table = axw::load_token_table(tokens_path);
+    const std::vector<axw::WordTokens> words = axw::split_words(table, ids, n, eot, language);
+    if ((int)words.size() > n_max) throw std::runtime_error("split_words: more words than n_max");
+    for (size_t w = 0; w < words.size(); ++w) word_tokens[w] = (int)words[w].tokens.size();
+    *n_words = (int)words.size();
+    std::vector<const std::string*> texts;
+    for (const axw::WordTokens& w : words) texts.push_back(&w.text);
+    return emit_word_text(texts, word_text_end, text, n_bytes);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_WordsFromAlignment(const char* tokens_path, const int32_t* ids, int n, int eot, const char* language,
+                                                 const int* seg_tokens, double* seg_start, double* seg_end, int n_seg, const int* jump,
+                                                 const float* token_logprob, double last_speech_timestamp, int n_max, int* word_segment,
+                                                 int* word_text_end, double* word_start, double* word_end, float* word_prob, int* n_words,
+                                                 char** text, int* n_bytes) {
+  if (!tokens_path || (n > 0 && (!ids || !token_logprob)) || n < 0 || !language || n_seg < 0 || (n_seg > 0 && (!seg_tokens || !seg_start || !seg_end)) ||
+      !jump || n_max < 0 || (n_max > 0 && (!word_segment || !word_text_end || !word_start || !word_end || !word_prob)) || !n_words || !text || !n_bytes)
+    return -1;
+  *text = nullptr;
+  *n_words = *n_bytes = 0;
+  return guarded_host([&] {
+    const std::vector<std::string> table = axw::load_token_table(tokens_path);
+    const std::vector<axw::WordOut> words =
+        axw::words_from_alignment(table, ids, n, eot, language, seg_tokens, seg_start, seg_end, n_seg, jump, token_logprob, last_speech_timestamp);
+    if ((int)words.size() > n_max) throw std::runtime_error("words_from_alignment: more words than n_max");
+    for (size_t w = 0; w < words.size(); ++w) {
+      word_segment[w] = words[w].segment; word_start[w] = words[w].start; word_end[w] = words[w].end; word_prob[w] = (float)words[w].probability;
+    }
+    *n_words = (int)words.size();
+    std::vector<const std::string*> texts;
+    for (const axw::WordOut& w : words) texts.push_back(&w.text);
+    return emit_word_text(texts, word_text_end, text, n_bytes);
+  });
+}
+
+// Host only: the alignment heads a handle constructed from this config file starts with
+AX_WHISPER_API int AX_WHISPER_ConfigAlignmentHeads(const char* config_path, int n_max, int* pairs, int* n) {
+  if (!config_path || !n || n_max < 0 || (n_max > 0 && !pairs)) return -1;
+  *n = 0;
+  return guarded_host([&] {
+    const axw::JsonValue j = axw::JsonParser(axw::read_text_file(config_path)).parse();
+    const int n_layer = (int)j.at("n_text_layer").as_int();
+    const int n_head = j.has("n_text_head") ? (int)j.at("n_text_head").as_int() : (int)j.at("n_text_state").as_int() / 64;
+    std::vector<std::pair<int, int>> v = axw::config_alignment_heads(j, n_layer, n_head);
+    if (v.empty()) v = axw::default_alignment_heads(n_layer, n_head);
+    if ((int)v.size() > n_max) throw std::runtime_error("config_alignment_heads: more heads than n_max");
+    for (size_t i = 0; i < v.size(); ++i) { pairs[2 * i] = v[i].first; pairs[2 * i + 1] = v[i].second; }
+    *n = (int)v.size();
+    return 0;
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_SetAlignmentHeads(AX_WHISPER_HANDLE handle, const int* pairs, int n) {
+  if (!handle || n < 0 || (n > 0 && !pairs)) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    for (int i = 0; i < g.size(); ++i) {
+      Engine& e = g.at(i);
+      std::lock_guard<std::mutex> lock(e.mutex());
+      e.set_alignment_heads(pairs, n);
+    }
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_AlignTokens(AX_WHISPER_HANDLE handle, int batch, const int32_t* ids, int stride, const int* n_ids,
+                                          const int* num_frames, const int* lang, const int* task, int* jump, float* token_logprob,
+                                          float* matrix, int m_rows, int m_ld) {
+  if (!handle || !ids || !n_ids || !num_frames || !jump || !token_logprob || batch < 1 || stride < 1) return -1;
+  return guarded(handle, [&](Engine& e) {
+    e.align_tokens(Engine::AlignRequest{batch, ids, stride, n_ids, num_frames, lang, task, jump, token_logprob, matrix, m_rows, m_ld});
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_AlignQKSoftmax(AX_WHISPER_HANDLE handle, int n_clips, const int* len, const int* n_keys, const float* q, int rows,
+                                             int n_head, const int* row0, const float* k, int n_slots, int keys_pad, const int* slot,
+                                             const int* heads, int n_align, float* P, int rows_pad, int f_pad) {
+  if (!handle || !len || !n_keys || !q || !row0 || !k || !slot || !heads || !P) return -1;
+  return guarded(handle, [&](Engine& e) {
+    Engine::AlignKernelIO io{};
+    io.n_clips = n_clips; io.len = len; io.n_keys = n_keys; io.q = q; io.rows = rows; io.n_head = n_head; io.row0 = row0;
+    io.k = k; io.n_slots = n_slots; io.keys_pad = keys_pad; io.slot = slot; io.heads = heads; io.n_align = n_align;
+    io.P = P; io.rows_pad = rows_pad; io.f_pad = f_pad;
+    e.align_kernel(0, io);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_AlignNormalize(AX_WHISPER_HANDLE handle, int n_clips, const int* len, const int* n_keys, const float* P, int n_align,
+                                             int rows_pad, int f_pad, float inv_heads, float* matrix, int m_rows, int m_ld) {
+  if (!handle || !len || !n_keys || !P || !matrix) return -1;
+  return guarded(handle, [&](Engine& e) {
+    Engine::AlignKernelIO io{};
+    io.n_clips = n_clips; io.len = len; io.n_keys = n_keys; io.n_align = n_align;
+    io.P = const_cast<float*>(P); io.rows_pad = rows_pad; io.f_pad = f_pad; io.matrix = matrix; io.m_rows = m_rows; io.m_ld = m_ld; io.inv_heads = inv_heads;
+    e.align_kernel(1, io);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_AlignDTW(AX_WHISPER_HANDLE handle, int n_clips, const int* len, const int* n_keys, const float* matrix, int m_rows,
+                                       int m_ld, int* jump, int jump_ld) {
+  if (!handle || !len || !n_keys || !matrix || !jump) return -1;
+  return guarded(handle, [&](Engine& e) {
+    Engine::AlignKernelIO io{};
+    io.n_clips = n_clips; io.len = len; io.n_keys = n_keys;
+    io.matrix = const_cast<float*>(matrix); io.m_rows = m_rows; io.m_ld = m_ld; io.jump = jump; io.jump_ld = jump_ld;
+    e.align_kernel(2, io);
+  });
+}
+
+// Clips in: the greedy timestamp decode of every clip (under its own language and task when given), the alignment of its text ids on
+// the engine that decoded it, and the host rule (words.hpp) on the result.
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchWordTimestamps(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int batch,
+                                                        int max_new, const int* lang, const int* task, int32_t* ids, int* n_ids, int* lang_out,
+                                                        int n_max, int* n_segments, double* seg_start, double* seg_end, int* n_words,
+                                                        int* word_segment, int* word_text_end, double* word_start, double* word_end,
+                                                        float* word_prob, char** text, int* jump, float* token_logprob) {
+  if (!handle || !pcm || !num_samples || !ids || !n_ids || batch < 1 || n_max < 1 || !n_segments || !seg_start || !seg_end || !n_words ||
+      !word_segment || !word_text_end || !word_start || !word_end || !word_prob || !text)
+    return -1;
+  for (int b = 0; b < batch; ++b) {
+    if (!pcm[b] || num_samples[b] < 1) return -1;
+    text[b] = nullptr;
+  }
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    const auto& cfg = g.primary().config();
+    const int Tc = cfg.n_text_ctx, T = cfg.no_timestamps + 1, eot = cfg.eot;
+    const bool per_lang = lang || task;
+    std::vector<int> detected(batch, -1);
+    Engine::DecodeRequest rq = timestamp_request(Engine::kDecodeTimestamps, max_new, nullptr, nullptr);
+    if (per_lang) rq.ctx = clip_contexts(nullptr, 0, nullptr, Engine::LangSpec{lang, task}, {detected.data(), nullptr, nullptr});
+    struct ClipText { std::vector<int32_t> text; std::vector<int> seg_tokens; std::vector<double> st, en; std::vector<int> jump; std::vector<float> lp; };
+    std::vector<ClipText> clip(batch);
+    g.run_tokens_then(rq, pcm, num_samples, batch, Tc, (int)cfg.lang_tokens.size(), ids, n_ids, [&](Engine& e, int lo, int hi) {
+      const int nb = hi - lo;
+      std::vector<int32_t> tids((size_t)nb * Tc, 0);
+      std::vector<int> tn(nb, 0), frames(nb), jmp((size_t)nb * (Tc + 1), 0);
+      std::vector<float> lp((size_t)nb * Tc, 0.f);
+      for (int b = lo; b < hi; ++b) {
+        ClipText& c = clip[b];
+        const int n = n_ids[b], cap = n / 2 + 1;
+        const int32_t* row = ids + (size_t)b * Tc;
+        std::vector<float> st(cap), en(cap);
+        std::vector<int> tb(cap), te(cap);
+        int n_seg = 0;
+        const float clip_s = num_samples[b] / 16000.f < 30.f ? num_samples[b] / 16000.f : 30.f;
+        if (AX_WHISPER_SplitSegments(row, n, T, eot, clip_s, cap, st.data(), en.data(), tb.data(), te.data(), &n_seg) != 0)
+          throw std::runtime_error("word timestamps: the segment split failed");
+        for (int k = 0; k < n_seg; ++k) {
+          int count = 0;
+          for (int i = tb[k]; i < te[k]; ++i)
+            if (row[i] < eot) { c.text.push_back(row[i]); ++count; }
+          c.seg_tokens.push_back(count); c.st.push_back(st[k]); c.en.push_back(en[k]);
+        }
+        if ((int)c.text.size() + 5 > Tc) c.text.resize(Tc - 5);  // (a decode never keeps that many ids; the alignment's bound)
+        tn[b - lo] = (int)c.text.size();
+        std::copy(c.text.begin(), c.text.end(), tids.begin() + (size_t)(b - lo) * Tc);
+        frames[b - lo] = std::min(num_samples[b] / 160, 3000);
+      }
+      std::vector<int> lg(nb, -1);
+      for (int b = lo; per_lang && b < hi; ++b) lg[b - lo] = detected[b];
+      e.align_tokens(Engine::AlignRequest{nb, tids.data(), Tc, tn.data(), frames.data(), lg.data(), task ? task + lo : nullptr, jmp.data(), lp.data(),
+                                          nullptr, 0, 0});
+      for (int b = lo; b < hi; ++b) {
+        clip[b].jump.assign(jmp.begin() + (size_t)(b - lo) * (Tc + 1), jmp.begin() + (size_t)(b - lo) * (Tc + 1) + tn[b - lo] + 1);
+        clip[b].lp.assign(lp.begin() + (size_t)(b - lo) * Tc, lp.begin() + (size_t)(b - lo) * Tc + tn[b - lo]);
+      }
+    });
+    const std::vector<std::string>& table = g.primary().token_table();
+    for (int b = 0; b < batch; ++b) {
+      ClipText& c = clip[b];
+      const int li = per_lang ? detected[b] : (int)cfg.ints.at("lang_index");
+      const std::string code = li >= 0 && li < (int)cfg.lang_codes.size() ? cfg.lang_codes[(size_t)li] : std::string();
+      const int n = (int)c.text.size(), n_seg = (int)c.seg_tokens.size();
+      int total = 0;
+      for (int& t : c.seg_tokens) { t = std::min(t, n - total); total += t; }
+      const std::vector<axw::WordOut> words = axw::words_from_alignment(table, c.text.data(), n, eot, code, c.seg_tokens.data(), c.st.data(), c.en.data(),
+                                                                        n_seg, c.jump.data(), c.lp.data(), 0.0);
+      if ((int)words.size() > n_max || n_seg > n_max) throw std::runtime_error("word timestamps: more words or segments than n_max");
+      n_segments[b] = n_seg;
+      for (int k = 0; k < n_seg; ++k) { seg_start[(size_t)b * n_max + k] = c.st[k]; seg_end[(size_t)b * n_max + k] = c.en[k]; }
+      const size_t o = (size_t)b * n_max;
+      for (size_t w = 0; w < words.size(); ++w) {
+        word_segment[o + w] = words[w].segment; word_start[o + w] = words[w].start; word_end[o + w] = words[w].end; word_prob[o + w] = (float)words[w].probability;
+      }
+      n_words[b] = (int)words.size();
+      int n_bytes = 0;
+      std::vector<const std::string*> texts;
+      for (const axw::WordOut& w : words) texts.push_back(&w.text);
+      if (emit_word_text(texts, word_text_end + o, text + b, &n_bytes) != 0)
+        throw std::runtime_error("word timestamps: out of memory");
+      if (lang_out) lang_out[b] = li;
+      if (jump) std::copy(c.jump.begin(), c.jump.end(), jump + (size_t)b * Tc);
+      if (token_logprob) std::copy(c.lp.begin(), c.lp.end(), token_logprob + (size_t)b * Tc);
+    }
+  });
 }
 
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5) {

@@ -599,6 +599,43 @@ struct LangDetectParams {
 };
 void launch_language_detect(const LangDetectParams& p, hipStream_t s);
 
+// ---- word-level timestamps (decode_align.hip; DESIGN.md "Word-level timestamps"). The rows of a clip are contiguous in q (clip c at
+// row0[c], len[c] rows); clip c attends to its own n_keys[c] frames. All per-clip tables are device memory.
+// P[c][a][i][f] = softmax over f < n_keys[c] of q[row0[c] + i][head a] . K[slot[c]][head a][f] / 8 for i < len[c], fp32; columns
+// [n_keys[c], the end of the last 64-key block) are written as zeros, nothing else is touched
+struct AlignQKParams {
+  const h16* q; int ldq;                     // h16 rows, head h at columns [64 h, 64 h + 64)
+  const h16* k; long kv_slot_stride; int keys_pad;  // this layer's blocked cross K, slot 0; allocated keys per head (a multiple of 64)
+  const int* row0; const int* len; const int* slot; const int* n_keys;  // device [n_clips]
+  const int* heads; int n_align;             // device [n_align]: the layer's alignment heads
+  float* P; int rows_pad, f_pad;             // out [n_clips][n_align][rows_pad][f_pad], f_pad a multiple of 64
+  int n_clips, max_len;
+};
+void launch_align_qk_softmax(const AlignQKParams& p, hipStream_t s);
+// matrix[c][i][f] += inv_heads * median7 over f (reflect padding; skipped at n_keys[c] <= 3) of (P[c][a][i][f] - mean_i) / std_i, summed
+// over the layer's heads a, for i < len[c], f < n_keys[c]; mean and population std over the clip's len[c] rows
+struct AlignNormParams {
+  const float* P; int rows_pad, f_pad, n_align;
+  const int* len; const int* n_keys;         // device [n_clips]
+  float* matrix; int m_rows, m_ld;           // [n_clips][m_rows][m_ld]
+  float inv_heads;
+  int n_clips, max_keys;
+};
+void launch_align_normalize(const AlignNormParams& p, hipStream_t s);
+// jump[c][i] = the frame of the first point in row i of the DTW path over -matrix[c][3 + i][f], i < N = len[c] - 4, f < n_keys[c]
+// (align_path.hpp); a clip with N < 1 or no frame is skipped
+constexpr int kAlignDtwThreads = 512;        // a thread per row of the cost table: N + 1 <= 512
+struct AlignDtwParams {
+  const float* matrix; int m_rows, m_ld;     // m_ld a multiple of 4
+  const int* len; const int* n_keys;         // device [n_clips]
+  uint8_t* trace; long trace_clip_stride;    // scratch [n_clips][>= (N + 1) (F + 1)]
+  int* jump; int jump_ld;                    // out [n_clips][jump_ld]
+  int n_clips, max_len;
+};
+void launch_align_dtw(const AlignDtwParams& p, hipStream_t s);
+// out[r] = logits[r][id[r]] - logsumexp(logits[r][0 .. n_ids)); rows [rows][stride]; an id outside [0, n_ids): -inf
+void launch_row_id_logprob(const float* logits, long stride, int n_ids, const int* id, int rows, float* out, hipStream_t s);
+
 // ---- persistent decode (decode_persistent.hip, decode_persistent2.hip): the whole greedy loop of one to three clips in ONE launch
 typedef unsigned long long u64;
 struct PersistParams {

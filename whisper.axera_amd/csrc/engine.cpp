@@ -4,6 +4,7 @@
 #include "engine_impl.hpp"
 
 #include "host_io.hpp"
+#include "words.hpp"
 
 namespace axw {
 inline namespace AXW_NS {
@@ -137,6 +138,10 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     if (const char* t = getenv("AX_WHISPER_ENC_RESCALE_THR")) enc_rescale_thr_ = std::max(0.f, std::min(AXW_F16 ? 15.f : 16.f, (float)atof(t)));
   }
   cfg_.ints["t2s"] = t2s_ ? 1 : 0;
+  {  // "word_align": visible through AX_WHISPER_GetConfigInt from the start; the variable is checked at the first alignment call
+    const char* e = getenv("AX_WHISPER_WORD_ALIGN");
+    cfg_.ints["word_align"] = e && !strcmp(e, "host") ? 1 : 0;
+  }
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half
   ensure_capacity(std::max(1, max_batch));
   HIP_CHECK(hipStreamSynchronize(own_stream_));
@@ -210,6 +215,9 @@ void Engine::load_config(const std::string& dir, const std::string& type, const 
   for (int i = 0; i < 4; ++i) cfg_.ints["sot_seq" + std::to_string(i)] = sot_seq_[i];
   cfg_.ints["timestamp_begin"] = cfg_.no_timestamps + 1;  // id of the 0.00 s timestamp (timestamp mode)
   if (!cfg_.ints.count("no_speech")) cfg_.ints["no_speech"] = cfg_.no_timestamps - 1;  // <|nospeech|> (scored mode), where the file omits it
+  // word-level timestamps: the checkpoint's alignment heads, where the file names them (words.hpp)
+  config_heads_ = align_heads_ = config_alignment_heads(j, cfg_.n_text_layer, cfg_.n_text_head);
+  cfg_.ints["n_alignment_heads"] = (long)alignment_heads().size();
 }
 
 // Slaney mel filterbank, arithmetic as librosa.h:102-144 (fp32), stored transposed [201][n_mels].

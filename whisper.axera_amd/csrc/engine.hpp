@@ -8,6 +8,7 @@
 // a time; this engine runs B utterance slots through every stage as one batch.
 #pragma once
 
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -134,6 +135,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void run_tokens(const DecodeRequest& rq, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch, int32_t* ids,
                   int* n_ids) override;
   std::string detokenize(const int32_t* ids, int n) const override;
+  const std::vector<std::string>& token_table() const override { return tokens_; }
   std::string transcript(const int32_t* ids, int n) const override;
   std::string transcript_lang(const int32_t* ids, int n, int lang) const override;
   bool has_t2s() const { return (bool)t2s_; }
@@ -157,6 +159,9 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void beam_candidates(const float* logits, const int32_t* hist, const int* n_hist, int rows, int n_cand_max, int32_t* cand_id,
                        float* cand_logprob, int* n_cand) override;
   int beam_select(const BeamSelectIO& io) override;
+  void align_tokens(const AlignRequest& rq) override;
+  void set_alignment_heads(const int* pairs, int n) override;
+  void align_kernel(int which, const AlignKernelIO& io) override;
   void stream_open(int n_slots) override;
   void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) override;
   int stream_step(int n_steps, int* finished_slots) override;
@@ -263,7 +268,18 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // context and the raw logits row it was taken from; entries of the other slots are 0
   void prefill_prompts(int batch, const ClipContexts& ctx, bool force_context, bool want_no_speech, float* no_speech_out = nullptr,
                        float* sot_logits_out = nullptr);
-  void prefill_pass(int rows, int n_clips, int max_len, bool want_no_speech);
+  // after_cq (null for every caller but the alignment): called for layer l once its cross-attention queries stand in prefill_.qkv
+  // (h16 [rows][d], behind the w_cq GEMM), before anything overwrites them
+  using LayerHook = std::function<void(int layer)>;
+  void prefill_pass(int rows, int n_clips, int max_len, bool want_no_speech, const LayerHook* after_cq = nullptr);
+  // word-level timestamps (engine_align.cpp; DESIGN.md "Word-level timestamps")
+  std::vector<std::pair<int, int>> align_heads_;  // (layer, head), sorted; empty: the default list
+  std::vector<std::pair<int, int>> config_heads_; // the config file's "alignment_heads" (empty: none): what n == 0 restores
+  std::vector<std::pair<int, int>> alignment_heads() const;
+  int align_env_ = -1;   // AX_WHISPER_WORD_ALIGN, read at first use: 0 the GPU route, 1 the host route
+  int align_force_ = -1; // bench "word_align" / "word_align_host": that route for the call in progress
+  int align_route();
+  float bench_word_align(const std::string& what, int batch, int arg, int iters);
   int handle_lang_ = 0;  // index of the handle's language in the config's list
   // what an entry point asks before any GPU work: the mode rules of ctx (timestamp modes; under a language spec no open stream) and
   // the context plan of `batch` clips, which throws on a bad prompt, language or task

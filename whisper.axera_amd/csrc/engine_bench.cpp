@@ -73,6 +73,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "frontend_long") return bench_frontend_long(batch, arg, iters);
   if (what == "prefill" || what == "prefill_pass" || what == "prefill_step") return bench_prefill(what, batch, arg, iters);
   if (what == "detect_language") return bench_detect_language(batch, arg, iters);
+  if (what == "word_align" || what == "word_align_host") return bench_word_align(what, batch, arg, iters);
   throw std::runtime_error("bench: unknown target '" + what + "'");
 }
 
@@ -124,6 +125,26 @@ float Engine::bench_detect_language(int batch, int arg, int iters) {
   return timed_ms(stream(), [&] {
     for (int i = 0; i < iters; ++i) detect_language_stage(batch, out);
   });
+}
+
+// word_align / word_align_host: align_tokens of `batch` slots, every one with arg text ids against all n_audio_ctx frames, by the
+// kernels / by the host route whatever the handle's is (A/B on one handle). Host time included: both routes end on the host.
+// Cross K/V as bench "prefill" finds it.
+float Engine::bench_word_align(const std::string& what, int batch, int arg, int iters) {
+  require_timestamp_vocab();
+  const int n = std::max(1, std::min(arg, cfg_.n_text_ctx - 5));
+  std::vector<int32_t> ids((size_t)batch * n);
+  unsigned x = 12345u;
+  for (auto& v : ids) { x = x * 1664525u + 1013904223u; v = (int32_t)((x >> 8) % (unsigned)cfg_.eot); }
+  const std::vector<int> n_ids(batch, n), frames(batch, 2 * cfg_.n_audio_ctx);
+  std::vector<int> jump((size_t)batch * (n + 1));
+  std::vector<float> lp((size_t)batch * n);
+  const AlignRequest rq{batch, ids.data(), n, n_ids.data(), frames.data(), nullptr, nullptr, jump.data(), lp.data(), nullptr, 0, 0};
+  const ScopedSet<int> scope(align_force_, what == "word_align" ? 0 : 1);
+  align_tokens(rq);  // warm: the prefill scratch
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < iters; ++i) align_tokens(rq);
+  return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;

@@ -352,7 +352,7 @@ void Engine::detect_step_fed(int batch, const std::vector<int>& slot, int* idx, 
 
 // All context rows of the prompted clips through the decoder layers in one pass: the residual stream fp32 [rows][d], activations
 // h16 (the encoder's arithmetic: LayerNorm -> h16, MFMA GEMMs with fp32 accumulation), K and V into the slots' self caches.
-void Engine::prefill_pass(int rows, int n_clips, int max_len, bool want_no_speech) {
+void Engine::prefill_pass(int rows, int n_clips, int max_len, bool want_no_speech, const LayerHook* after_cq) {
   const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, Tc = cfg_.n_text_ctx;
   hipStream_t s = stream();
   PrefillScratch& pf = prefill_;
@@ -391,6 +391,7 @@ void Engine::prefill_pass(int rows, int n_clips, int max_len, bool want_no_speec
     linear(pf.att, d, w.w_o, w.b_o, pf.x, d, EPI_RESID_F32);
     launch_layernorm_bf16(pf.x, w.cross_ln_w, w.cross_ln_b, pf.ln, rows, d, s);
     linear(pf.ln, d, w.w_cq, w.b_cq, pf.qkv, d, EPI_BIAS_BF16);
+    if (after_cq) (*after_cq)(l);
     attention(pf.qkv, d, ck, cv, cross_stride, t_pad_, cfg_.n_audio_ctx);
     linear(pf.att, d, w.w_co, w.b_co, pf.x, d, EPI_RESID_F32);
     launch_layernorm_bf16(pf.x, w.mlp_ln_w, w.mlp_ln_b, pf.ln, rows, d, s);

@@ -85,6 +85,7 @@ class IEngine {
   virtual void run_tokens(const DecodeRequest& rq, const float* const* pcm, const float* d_pcm, int d_stride, const int* n_samples, int batch,
                           int32_t* ids, int* n_ids) = 0;
   virtual std::string detokenize(const int32_t* ids, int n) const = 0;
+  virtual const std::vector<std::string>& token_table() const = 0;  // the bytes of every id of the tokens file
   // detokenize + the reference's zh post-pass (Traditional -> Simplified, Whisper.cpp:231-236) when its OpenCC data files were found
   virtual std::string transcript(const int32_t* ids, int n) const = 0;
   // the text of ids decoded under language `lang` (an index of the config's list): the zh pass follows that language, not the handle's
@@ -152,6 +153,34 @@ class IEngine {
     int32_t* tok; int* src; float* slot_score;
   };
   virtual int beam_select(const BeamSelectIO& io) = 0;
+  // ---- word-level timestamps (engine_align.cpp; DESIGN.md "Word-level timestamps"); refuses an open Stream*
+  // After encode_mel: the alignment of slots [0, batch). Clip b: n_ids[b] text ids (< eot) at ids + b * stride, num_frames[b] mel
+  // frames of its own (it aligns against num_frames[b] / 2 encoder frames), language index lang[b] (-1 or a null array: the handle's),
+  // task[b] (0 transcribe, 1 translate; null: 0). Out: jump [batch][stride + 1] (n_ids[b] + 1 entries: the frame at which each text
+  // token and the closing eot begin), token_logprob [batch][stride] (over the ids below eot), and optionally matrix
+  // [batch][m_rows][m_ld]: rows [0, n_ids[b] + 5) x frames [0, num_frames[b] / 2) of the head-averaged matrix, the rest untouched.
+  // A clip without ids gets nothing. The slots' self-attention caches and nothing else of the decode state are overwritten.
+  struct AlignRequest {
+    int batch; const int32_t* ids; int stride; const int* n_ids; const int* num_frames; const int* lang; const int* task;
+    int* jump; float* token_logprob; float* matrix; int m_rows, m_ld;
+  };
+  virtual void align_tokens(const AlignRequest& rq) = 0;
+  // the list of (layer, head) pairs the alignment averages over; n == 0: the default, every head of the upper half of the layers
+  virtual void set_alignment_heads(const int* pairs, int n) = 0;
+  // One kernel of decode_align.hip alone on host data (tests). Clip c has len[c] rows and n_keys[c] frames.
+  // qk_softmax: q fp32 [rows][64 n_head] (clip c at row0[c]), k fp32 [n_slots][n_head][keys_pad][64] (clip c reads slot[c]), both
+  // narrowed to the 16-bit type; P [n_clips][n_align][rows_pad][f_pad] is updated in place (the kernel writes what it writes).
+  // normalize: P as above, matrix [n_clips][m_rows][m_ld] updated in place. dtw: matrix -> jump [n_clips][jump_ld].
+  struct AlignKernelIO {
+    int n_clips; const int* len; const int* n_keys;
+    const float* q; int rows, n_head; const int* row0;
+    const float* k; int n_slots, keys_pad; const int* slot;
+    const int* heads; int n_align;
+    float* P; int rows_pad, f_pad;
+    float* matrix; int m_rows, m_ld; float inv_heads;
+    int* jump; int jump_ld;
+  };
+  virtual void align_kernel(int which, const AlignKernelIO& io) = 0;  // 0 qk_softmax, 1 normalize, 2 dtw
   // utterance slots refilled while the others decode (include/ax_whisper_api.h: AX_WHISPER_Stream*)
   virtual void stream_open(int n_slots) = 0;
   virtual void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) = 0;

@@ -94,6 +94,18 @@ class DeviceGroup {
     });
   }
 
+  // run_tokens, then after(engine, lo, hi) on the same engine while its slots still hold the block's encoder output (word-level
+  // timestamps: the alignment of the block's clips)
+  template <typename Fn>
+  void run_tokens_then(const typename E::DecodeRequest& rq, const float* const* pcm, const int* n_samples, int batch, int n_ctx, int n_lang,
+                       int32_t* ids, int* n_ids, Fn&& after) {
+    if (batch < 1) throw std::runtime_error("batch must be >= 1");
+    for_each_shard(batch, [&](E& e, int, int lo, int hi) {
+      e.run_tokens(rq.block(lo, n_ctx, n_lang), pcm + lo, nullptr, 0, n_samples + lo, hi - lo, ids + (size_t)lo * n_ctx, n_ids + lo);
+      after(e, lo, hi);
+    });
+  }
+
   // Language detection alone (E::detect_language): front-end, encoder and detection of every clip on its shard's device; the results
   // go to out.lang_out.
   void detect_language(const float* const* pcm, const int* n_samples, int batch, int n_lang, const typename E::ClipContexts& out) {

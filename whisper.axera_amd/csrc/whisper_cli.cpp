@@ -24,6 +24,8 @@ static void usage(const char* prog) {
           "  -p, --model_path    model path which contains tiny/ base/ small/ turbo/ (string [=../models-mi355x])\n"
           "      --language      en, zh (string [=zh])\n"
           "      --timestamps    after Result:, one line per segment: [mm:ss.mmm --> mm:ss.mmm] text\n"
+          "      --word_timestamps   (with --timestamps alone) under every segment line one indented line per word:\n"
+          "                      [mm:ss.mmm --> mm:ss.mmm] word (probability); the segment times are those the word rule leaves\n"
           "      --beam_size N   (with --timestamps, not with --long) the segment lines are those of beam search's winner over N\n"
           "                      hypotheses (1 .. 8; openai-whisper's CLI uses 5) instead of the greedy decode's\n"
           "      --long          transcribe the whole file, not only its first 30 s: Result: is the whole text, followed by\n"
@@ -172,6 +174,48 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size, b
   return 0;
 }
 
+// --timestamps --word_timestamps: the segment lines of the greedy timestamp decode with the times the word rule leaves them, and under
+// each one indented line per word (AX_WHISPER_RunPCMBatchWordTimestamps)
+static int print_words(AX_WHISPER_HANDLE h, const char* wav) {
+  float* pcm = nullptr;
+  int n = 0;
+  if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
+  const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
+  std::vector<int32_t> ids(n_ctx);
+  std::vector<int> wseg(n_ctx), wte(n_ctx);
+  std::vector<double> ss(n_ctx), se(n_ctx), ws(n_ctx), we(n_ctx);
+  std::vector<float> wp(n_ctx);
+  int n_ids = 0, n_seg = 0, n_words = 0;
+  char* text = nullptr;
+  const float* clips[1] = {pcm};
+  const int rc = AX_WHISPER_RunPCMBatchWordTimestamps(h, clips, &n, 1, 0, nullptr, nullptr, ids.data(), &n_ids, nullptr, n_ctx, &n_seg, ss.data(), se.data(),
+                                                      &n_words, wseg.data(), wte.data(), ws.data(), we.data(), wp.data(), &text, nullptr, nullptr);
+  free(pcm);
+  if (rc != 0) { free(text); return -1; }
+  const float clip_s = n / 16000.f < 30.f ? n / 16000.f : 30.f;
+  const int n_max = n_ids / 2 + 1;
+  std::vector<float> st(n_max), en(n_max);
+  std::vector<int> tb(n_max), te(n_max);
+  int n_split = 0;
+  if (AX_WHISPER_SplitSegments(ids.data(), n_ids, AX_WHISPER_GetConfigInt(h, "timestamp_begin"), AX_WHISPER_GetConfigInt(h, "eot"), clip_s, n_max,
+                               st.data(), en.data(), tb.data(), te.data(), &n_split) != 0 || n_split != n_seg) {
+    free(text);
+    return -1;
+  }
+  for (int k = 0, w = 0; k < n_seg; ++k) {
+    char* seg_text = nullptr;
+    if (AX_WHISPER_Transcript(h, ids.data() + tb[k], te[k] - tb[k], &seg_text) != 0) { free(text); return -1; }
+    printf("[%s --> %s] %s\n", mmss((float)ss[k]).c_str(), mmss((float)se[k]).c_str(), seg_text ? seg_text : "");
+    free(seg_text);
+    for (; w < n_words && wseg[w] == k; ++w) {
+      const int b = w ? wte[w - 1] : 0;
+      printf("  [%s --> %s] %.*s (%.3f)\n", mmss((float)ws[w]).c_str(), mmss((float)we[w]).c_str(), wte[w] - b, text + b, wp[w]);
+    }
+  }
+  free(text);
+  return 0;
+}
+
 // --long: the seek loop over the whole file (AX_WHISPER_RunPCMLongWindows), its text, then one line per segment.
 // scored: under the silent-window rule (AX_WHISPER_RunPCMLongWindowsScored); skipped windows print nothing, the other lines end
 // in their window's two numbers
@@ -249,7 +293,7 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
 
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
-  bool timestamps = false, longform = false;
+  bool timestamps = false, longform = false, word_timestamps = false;
   bool condition = false, detect = false;
   std::string task_arg;
   std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg;
@@ -272,6 +316,7 @@ int main(int argc, char** argv) {
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
+    if (a == "--word_timestamps") { word_timestamps = true; continue; }
     if (a == "--long") { longform = true; continue; }
     if (a == "--condition_on_previous_text") { condition = true; continue; }
     if (a == "--detect_language") { detect = true; continue; }
@@ -296,6 +341,11 @@ int main(int argc, char** argv) {
   const bool per_lang = detect || task >= 0;
   if (per_lang && ((!timestamps && !longform) || beam_size > 1)) {
     fprintf(stderr, "--detect_language / --task need --timestamps or --long and do not go with --beam_size\n");
+    usage(argv[0]);
+    return 1;
+  }
+  if (word_timestamps && (!timestamps || longform || beam_size > 1 || per_lang)) {
+    fprintf(stderr, "--word_timestamps needs --timestamps and does not go with --long, --beam_size, --detect_language or --task\n");
     usage(argv[0]);
     return 1;
   }
@@ -394,7 +444,7 @@ int main(int argc, char** argv) {
   t1 = std::chrono::steady_clock::now();
   printf("Result: %s\n", result);
   const double rtf = std::chrono::duration<double>(t1 - t0).count() / duration;  // of AX_WHISPER_RunFile alone
-  if (timestamps && print_segments(handle, wav.c_str(), beam_size) != 0) {
+  if (timestamps && (word_timestamps ? print_words(handle, wav.c_str()) : print_segments(handle, wav.c_str(), beam_size)) != 0) {
     printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
     free(result);
     AX_WHISPER_Uninit(handle);

@@ -87,7 +87,25 @@ def read_hf_checkpoint(path: str) -> dict:
     raise FileNotFoundError(f"{path}: neither model.safetensors nor model.safetensors.index.json")
 
 
-def write_model(weights: dict, model_type: str, model_path: str, dtype: str = "BF16", tiktoken_path: str | None = None) -> str:
+def hf_alignment_heads(path: str):
+    """The alignment heads a transformers checkpoint names: "alignment_heads": [[layer, head], ...] of the generation_config.json
+    beside its weights; None where there is no such file or key."""
+    import json
+
+    d = os.path.dirname(path) if path.endswith(".safetensors") else path
+    f = os.path.join(d, "generation_config.json")
+    if not os.path.exists(f):
+        return None
+    heads = json.load(open(f)).get("alignment_heads")
+    if heads is None:
+        return None
+    if not all(isinstance(p, (list, tuple)) and len(p) == 2 and all(isinstance(x, int) for x in p) for p in heads):
+        raise ValueError(f"{f}: alignment_heads is not a list of [layer, head] pairs")
+    return [[int(p[0]), int(p[1])] for p in heads]
+
+
+def write_model(weights: dict, model_type: str, model_path: str, dtype: str = "BF16", tiktoken_path: str | None = None,
+                alignment_heads=None) -> str:
     """tiktoken_path is REQUIRED for a real checkpoint: {type}-tokens.txt must carry the vocabulary the model was
     trained with (the reference's exporter writes it from the tokenizer, export_onnx.py:391-417)."""
     if not tiktoken_path:
@@ -103,7 +121,7 @@ def write_model(weights: dict, model_type: str, model_path: str, dtype: str = "B
         if n in weights:
             assert tuple(weights[n].shape) == tuple(s), (n, weights[n].shape, s)
     return modelgen.write_model_dir(model_path, model_type, dims, weights={k: v for k, v in weights.items() if k in expect},
-                                    dtype=dtype, tiktoken_path=tiktoken_path)
+                                    dtype=dtype, tiktoken_path=tiktoken_path, alignment_heads=alignment_heads)
 
 
 def main():
@@ -122,9 +140,11 @@ def main():
         ck = torch.load(a.openai, map_location="cpu")
         sd = ck.get("model_state_dict", ck)
         w = {k: v.float().numpy() for k, v in sd.items()}
+        heads = None  # (an openai checkpoint keeps its heads in the package, not in the file)
     else:
         w = hf_to_openai_names(read_hf_checkpoint(a.hf))
-    print(write_model(w, a.model_type, a.model_path, a.dtype, a.tiktoken))
+        heads = hf_alignment_heads(a.hf)  # word-level timestamps: the checkpoint's own heads go into the config
+    print(write_model(w, a.model_type, a.model_path, a.dtype, a.tiktoken, alignment_heads=heads))
 
 
 if __name__ == "__main__":

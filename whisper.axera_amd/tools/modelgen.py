@@ -397,13 +397,17 @@ def write_tokens(path: str, tiktoken_path: str | None) -> None:
 
 def write_model_dir(root: str, model_type: str, dims: dict | None = None, seed: int = 0,
                     tiktoken_path: str | None = None, dtype: str = "BF16",
-                    weights: Dict[str, np.ndarray] | None = None) -> str:
-    """Create ``{root}/{model_type}/`` with config, tokens and weights; returns the directory."""
+                    weights: Dict[str, np.ndarray] | None = None, alignment_heads=None) -> str:
+    """Create ``{root}/{model_type}/`` with config, tokens and weights; returns the directory. alignment_heads: the checkpoint's
+    [[layer, head], ...] for word-level timestamps (the config's optional key of that name); None: the key is left out."""
     dims = dims or DIMS[model_type]
     d = os.path.join(root, model_type)
     os.makedirs(d, exist_ok=True)
+    cfg = make_config(model_type, dims)
+    if alignment_heads is not None:
+        cfg["alignment_heads"] = [[int(l), int(h)] for l, h in alignment_heads]
     with open(os.path.join(d, f"{model_type}_config.json"), "w") as f:
-        json.dump(make_config(model_type, dims), f, indent=4)
+        json.dump(cfg, f, indent=4)
     write_tokens(os.path.join(d, f"{model_type}-tokens.txt"), tiktoken_path)
     if weights is None:
         weights = synth_weights(dims, seed, bf16=(dtype == "BF16"))
