@@ -608,9 +608,42 @@ AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
  *  had completed), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
  *  files of `arg` seconds + one window kernel), "prefill" (reset + PrefillPrompts of `batch` slots with prompts of arg - 3 ids each,
  *  i.e. context length L = arg, by the handle's route), "word_align" / "word_align_host" (AlignTokens of `batch` slots with `arg` text ids
- *  each against all frames, by the kernels / by the host route; host wall time), or a kernel name listed in DESIGN.md. */
+ *  each against all frames, by the kernels / by the host route; host wall time), "resample" (the resample kernel over `batch` clips
+ *  of 30 s at `arg` Hz into the staging rows), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);
+
+/* ---- additions: audio at any sample rate (DESIGN.md "Sample rates") ------------------- */
+/* Every entry point above takes 16 kHz mono PCM. The calls below take clips at their own rate and convert them to 16 kHz on the GPU
+ * with a polyphase Kaiser-windowed sinc (csrc/resample.hpp: the definition; csrc/resample.hip: the kernel). Accepted: 1000 <= rate <=
+ * 384000 Hz whose filter table has at most 2^22 entries (8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 88200, 96000 all do;
+ * 44101 does not), clips of at most 2^29 samples before and after. Everything else is refused with -1 and an error text
+ * (AX_WHISPER_LastError) before any GPU work. A clip at 16000 Hz takes the path it always took. */
+
+/** Host only: the length at 16 kHz of a clip of n samples at `rate`, ceil(n * 16000 / rate); -1 when the rate or the length is refused. */
+AX_WHISPER_API long long AX_WHISPER_ResampledLength(long long n, int rate);
+/** Host only: the filter of `rate` as the kernel uses it. *L phases, decimation *M, *K (2 K taps per phase); table (may be NULL: the
+ *  sizes alone) receives the L * 2 K float32 coefficients [L][2 K] when cap >= L * 2 K. 0 ok, -1 refused rate or a table beyond cap. */
+AX_WHISPER_API int AX_WHISPER_ResampleFilter(int rate, int* L, int* M, int* K, float* table, int cap);
+/** The resample kernel alone on host data: out[b] (capacity out_cap[b] samples) receives the n_out[b] samples of clip b at 16 kHz.
+ *  A clip at 16000 Hz is copied bit for bit. Batch-of-one calls serve long files. Refuses an open Stream*. */
+AX_WHISPER_API int AX_WHISPER_ResampleBatch(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, const int* rates,
+                                            int batch, float* const* out, const int* out_cap, int* n_out);
+/** AX_WHISPER_ComputeMel of a clip at `rate`: upload, resample kernel into the staging row, front-end (the fused path of the calls below). */
+AX_WHISPER_API int AX_WHISPER_ComputeMelRate(AX_WHISPER_HANDLE handle, const float* pcm, int num_samples, int rate, float* mel_out);
+/** AX_WHISPER_RunPCMBatchTokens (mode 0) / AX_WHISPER_RunPCMBatchTimestampTokens (mode 1) with a sample rate per clip; sharded over
+ *  the handle's devices like them, the rates travelling with their clips. */
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchRate(AX_WHISPER_HANDLE handle, int mode, const float* const* pcm, const int* num_samples,
+                                              const int* rates, int batch, int max_new, int32_t* ids, int* n_ids);
+/** AX_WHISPER_StreamAdmitBatch with a sample rate per clip (rates NULL: 16000 Hz). */
+AX_WHISPER_API int AX_WHISPER_StreamAdmitBatchRate(AX_WHISPER_HANDLE handle, const int* slots, const float* const* pcm,
+                                                   const int* num_samples, const int* rates, const int* max_new, int count);
+/** AX_WHISPER_RunFile that resamples by the file's own rate (and prints no warning); a 16 kHz file gives what RunFile gives. */
+AX_WHISPER_API int AX_WHISPER_RunFileResampled(AX_WHISPER_HANDLE handle, const char* wav_file, char** result);
+/** File decode (AX_WHISPER_LoadAudioFile) + GPU resampling: *samples is a malloc'd 16 kHz mono buffer that every PCM entry point
+ *  takes (long-form, fallback, prompted, language, beam, words); info (may be NULL): [0] the file's sample rate, [1] channels,
+ *  [2] samples per channel in the file. */
+AX_WHISPER_API int AX_WHISPER_LoadAudioFile16k(AX_WHISPER_HANDLE handle, const char* path, float** samples, int* n_samples, int* info);
 
 #ifdef __cplusplus
 }

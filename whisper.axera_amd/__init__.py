@@ -147,6 +147,15 @@ SYMBOLS = {
     "AX_WHISPER_WordsFromAlignment": (C.c_int, [C.c_char_p, ip, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), _dblp, _dblp, C.c_int, C.POINTER(C.c_int), fp,
                                                 C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dblp, _dblp, fp, C.POINTER(C.c_int),
                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "AX_WHISPER_ResampledLength": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "AX_WHISPER_ResampleFilter": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int]),
+    "AX_WHISPER_ResampleBatch": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(fp), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int)]),
+    "AX_WHISPER_ComputeMelRate": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_int, fp]),
+    "AX_WHISPER_RunPCMBatchRate": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, ip, C.POINTER(C.c_int)]),
+    "AX_WHISPER_StreamAdmitBatchRate": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "AX_WHISPER_RunFileResampled": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_LoadAudioFile16k": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 
@@ -194,6 +203,27 @@ def load_audio_file(path: str):
     a = np.ctypeslib.as_array(C.cast(out, fp), shape=(max(n.value, 1),))[: n.value].copy()
     L._free(out.value)
     return a, info[0], info[1]
+
+
+def resampled_length(n: int, rate: int) -> int:
+    """The length at 16 kHz of a clip of n samples at `rate` Hz, ceil(n * 16000 / rate) (host only); raises on a refused rate or length."""
+    L = load_library()
+    r = L.AX_WHISPER_ResampledLength(int(n), int(rate))
+    if r < 0:
+        raise ValueError("AX_WHISPER_ResampledLength: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return int(r)
+
+
+def resample_filter(rate: int):
+    """The polyphase filter of `rate` as the resample kernel uses it (host only) -> (L, M, K, table float32 [L][2 K])."""
+    L = load_library()
+    l, m, k = C.c_int(), C.c_int(), C.c_int()
+    if L.AX_WHISPER_ResampleFilter(int(rate), C.byref(l), C.byref(m), C.byref(k), None, 0) != 0:
+        raise ValueError("AX_WHISPER_ResampleFilter: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    table = np.empty((l.value, 2 * k.value), dtype=np.float32)
+    if L.AX_WHISPER_ResampleFilter(int(rate), C.byref(l), C.byref(m), C.byref(k), table.ctypes.data_as(fp), table.size) != 0:
+        raise ValueError("AX_WHISPER_ResampleFilter: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return l.value, m.value, k.value, table
 
 
 def detokenize_with_table(tokens_path: str, ids) -> bytes:
@@ -483,10 +513,13 @@ class Whisper:
         return s
 
     # ---- legacy entry points ------------------------------------------------------------
-    def run(self, audio) -> str:
-        """PCM (16 kHz mono f32) or a wav path -> text (python/whisper.py:213-271)."""
+    def run(self, audio, resample: bool = False) -> str:
+        """PCM (16 kHz mono f32) or a wav path -> text (python/whisper.py:213-271). resample: a file is converted to 16 kHz by its own
+        rate on the GPU first (AX_WHISPER_RunFileResampled); without it a file at another rate is fed as it is, with a warning."""
         out = C.c_void_p()
-        if isinstance(audio, (str, os.PathLike)):
+        if isinstance(audio, (str, os.PathLike)) and resample:
+            self._check(self.L.AX_WHISPER_RunFileResampled(self.h, os.fspath(audio).encode(), C.byref(out)), "AX_WHISPER_RunFileResampled")
+        elif isinstance(audio, (str, os.PathLike)):
             self._check(self.L.AX_WHISPER_RunFile(self.h, os.fspath(audio).encode(), C.byref(out)), "AX_WHISPER_RunFile")
         else:
             a = _f32(audio)
@@ -541,6 +574,39 @@ class Whisper:
 
     def run_tokens(self, pcm, max_new: int = 0):
         return self.run_tokens_batch([pcm], max_new)[0]
+
+    # ---- audio at any sample rate (DESIGN.md "Sample rates")
+    def resample_batch(self, clips, rates):
+        """The resample kernel alone: clips at rates[b] Hz -> their samples at 16 kHz (a clip at 16000 Hz comes back bit for bit)."""
+        clips, B, ptrs, lens, _ = self._clip_args(clips)
+        rt = (C.c_int * B)(*[int(r) for r in rates])
+        outs = [np.empty(max(resampled_length(len(c), r), 1), dtype=np.float32) for c, r in zip(clips, rt)]
+        optrs = (fp * B)(*[o.ctypes.data_as(fp) for o in outs])
+        caps = (C.c_int * B)(*[len(o) for o in outs])
+        n = (C.c_int * B)()
+        self._check(self.L.AX_WHISPER_ResampleBatch(self.h, ptrs, lens, rt, B, optrs, caps, n), "ResampleBatch")
+        return [o[: n[b]] for b, o in enumerate(outs)]
+
+    def resample(self, audio, rate: int) -> np.ndarray:
+        return self.resample_batch([audio], [rate])[0]
+
+    def run_tokens_batch_rate(self, clips, rates, max_new: int = 0, timestamps: bool = False):
+        """run_tokens_batch (timestamps: run_timestamp_tokens_batch) over clips at rates[b] Hz, resampled on the GPU behind their upload."""
+        clips, B, ptrs, lens, _ = self._clip_args(clips)
+        rt = (C.c_int * B)(*[int(r) for r in rates])
+        ids = np.zeros((B, self.n_text_ctx), dtype=np.int32)
+        n = (C.c_int * B)()
+        self._check(self.L.AX_WHISPER_RunPCMBatchRate(self.h, 1 if timestamps else 0, ptrs, lens, rt, B, max_new, ids.ctypes.data_as(ip), n),
+                    "RunPCMBatchRate")
+        return [ids[b, : n[b]].tolist() for b in range(B)]
+
+    def load_audio_file_16k(self, path):
+        """File decode + GPU resampling -> (mono f32 samples at 16 kHz, the file's sample rate, channels, samples per channel in the file)."""
+        out, n, info = C.c_void_p(), C.c_int(), (C.c_int * 3)()
+        self._check(self.L.AX_WHISPER_LoadAudioFile16k(self.h, os.fspath(path).encode(), C.byref(out), C.byref(n), info), "LoadAudioFile16k")
+        a = np.ctypeslib.as_array(C.cast(out, fp), shape=(max(n.value, 1),))[: n.value].copy()
+        self.L._free(out.value)
+        return a, info[0], info[1], info[2]
 
     # ---- segment timestamps (timestamp mode: prefix [sot, lang, transcribe], Whisper's timestamp rules on the GPU)
     def run_timestamp_tokens_batch(self, clips, max_new: int = 0, max_new_clip=None):
@@ -1295,10 +1361,13 @@ class Whisper:
     def set_stream(self, stream_ptr: int):
         self._check(self.L.AX_WHISPER_SetStream(self.h, C.c_void_p(stream_ptr)), "SetStream")
 
-    def compute_mel(self, pcm) -> np.ndarray:
+    def compute_mel(self, pcm, rate: int = 16000) -> np.ndarray:
         a = _f32(pcm)
         out = np.empty((self.n_mels, 3000), dtype=np.float32)
-        self._check(self.L.AX_WHISPER_ComputeMel(self.h, a.ctypes.data_as(fp), len(a), out.ctypes.data_as(fp)), "ComputeMel")
+        if rate == 16000:
+            self._check(self.L.AX_WHISPER_ComputeMel(self.h, a.ctypes.data_as(fp), len(a), out.ctypes.data_as(fp)), "ComputeMel")
+        else:
+            self._check(self.L.AX_WHISPER_ComputeMelRate(self.h, a.ctypes.data_as(fp), len(a), int(rate), out.ctypes.data_as(fp)), "ComputeMelRate")
         return out
 
     def encode_mel(self, mel):
@@ -1352,14 +1421,18 @@ class Whisper:
         a = _f32(pcm)
         self._check(self.L.AX_WHISPER_StreamAdmit(self.h, slot, a.ctypes.data_as(fp), len(a), max_new), "StreamAdmit")
 
-    def stream_admit_batch(self, slots, clips, max_new=None):
+    def stream_admit_batch(self, slots, clips, max_new=None, rates=None):
         clips = [_f32(c) for c in clips]
         n = len(clips)
         sl = (C.c_int * n)(*[int(x) for x in slots])
         ptrs = (fp * n)(*[c.ctypes.data_as(fp) for c in clips])
         lens = (C.c_int * n)(*[len(c) for c in clips])
         mn = (C.c_int * n)(*[int(x) for x in max_new]) if max_new is not None else None
-        self._check(self.L.AX_WHISPER_StreamAdmitBatch(self.h, sl, ptrs, lens, mn, n), "StreamAdmitBatch")
+        if rates is None:
+            self._check(self.L.AX_WHISPER_StreamAdmitBatch(self.h, sl, ptrs, lens, mn, n), "StreamAdmitBatch")
+        else:
+            rt = (C.c_int * n)(*[int(r) for r in rates])
+            self._check(self.L.AX_WHISPER_StreamAdmitBatchRate(self.h, sl, ptrs, lens, rt, mn, n), "StreamAdmitBatchRate")
 
     def stream_step(self, n_steps: int = 8):
         fin = (C.c_int * max(self._n_slots, 3))()

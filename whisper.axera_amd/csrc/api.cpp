@@ -26,6 +26,7 @@
 #include "host_io.hpp"
 #include "t2s.hpp"
 #include "multi_device.hpp"
+#include "resample.hpp"
 #include "words.hpp"
 
 using Engine = axw::IEngine;
@@ -1359,6 +1360,107 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchWordTimestamps(AX_WHISPER_HANDLE handle
       if (token_logprob) std::copy(c.lp.begin(), c.lp.end(), token_logprob + (size_t)b * Tc);
     }
   });
+}
+
+// ---- audio at any sample rate (DESIGN.md "Sample rates")
+AX_WHISPER_API long long AX_WHISPER_ResampledLength(long long n, int rate) {
+  std::string err;
+  const long long r = axw::resample::resampled_length(n, rate, err);
+  if (r < 0) g_init_error = err;
+  return r;
+}
+
+AX_WHISPER_API int AX_WHISPER_ResampleFilter(int rate, int* L, int* M, int* K, float* table, int cap) {
+  if (!L || !M || !K) return -1;
+  return guarded_host([&] {
+    axw::resample::Filter f;
+    std::string err;
+    if (!axw::resample::plan(rate, f, err)) { g_init_error = err; return -1; }
+    *L = f.L; *M = f.M; *K = f.K;
+    if (!table) return 0;
+    if ((long long)cap < f.entries()) { g_init_error = "ResampleFilter: the table has " + std::to_string(f.entries()) + " entries"; return -1; }
+    axw::resample::build_table(f, table);
+    return 0;
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_ResampleBatch(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, const int* rates,
+                                            int batch, float* const* out, const int* out_cap, int* n_out) {
+  if (!handle || !pcm || !num_samples || !rates || !out || !out_cap || !n_out || batch < 1) return -1;
+  for (int b = 0; b < batch; ++b) if (!pcm[b] || !out[b]) return -1;
+  return guarded(handle, [&](Engine& e) { e.resample(pcm, num_samples, rates, batch, out, out_cap, n_out); });
+}
+
+AX_WHISPER_API int AX_WHISPER_ComputeMelRate(AX_WHISPER_HANDLE handle, const float* pcm, int num_samples, int rate, float* mel_out) {
+  if (!handle || !pcm || !mel_out || num_samples < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.compute_mel(pcm, num_samples, mel_out, rate); });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMBatchRate(AX_WHISPER_HANDLE handle, int mode, const float* const* pcm, const int* num_samples,
+                                              const int* rates, int batch, int max_new, int32_t* ids, int* n_ids) {
+  if (!handle || !pcm || !num_samples || !rates || !ids || !n_ids || batch < 1 || (mode != 0 && mode != 1)) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    // refused rates and lengths fail here for the whole batch, before any device starts on its block
+    for (int b = 0; b < batch; ++b) {
+      std::string err;
+      if (axw::resample::resampled_length(num_samples[b], rates[b], err) < 0) throw std::runtime_error("clip " + std::to_string(b) + ": " + err);
+    }
+    Engine::DecodeRequest rq;
+    rq.mode = mode ? Engine::kDecodeTimestamps : Engine::kDecodePlain;
+    rq.max_new = max_new; rq.sample_rate = rates;
+    run_request(g, rq, pcm, num_samples, batch, ids, n_ids);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_StreamAdmitBatchRate(AX_WHISPER_HANDLE handle, const int* slots, const float* const* pcm,
+                                                   const int* num_samples, const int* rates, const int* max_new, int count) {
+  if (!handle || !slots || !pcm || !num_samples || count < 1) return -1;
+  for (int i = 0; i < count; ++i) if (!pcm[i] || num_samples[i] < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.stream_admit(slots, pcm, num_samples, max_new, count, rates); });
+}
+
+// file decode + the stage-level resample call on the primary engine: the file's samples at 16 kHz (its own at 16000 Hz)
+static int load_file_16k(AX_WHISPER_HANDLE handle, const char* path, std::vector<float>& pcm16, axw::WavData& wav) {
+  std::string err;
+  if (!axw::load_audio_file(path, wav, err)) {
+    H(handle)->set_error("load wav failed: " + err);
+    fprintf(stderr, "[ax_whisper] load wav failed: %s\n", err.c_str());
+    return -1;
+  }
+  if (wav.mono.empty()) { H(handle)->set_error("wav file holds no samples"); return -1; }
+  if (wav.sample_rate == axw::resample::kTargetRate) { pcm16 = wav.mono; return 0; }
+  const long long n16 = AX_WHISPER_ResampledLength((long long)wav.mono.size(), wav.sample_rate);
+  if (n16 < 0) { H(handle)->set_error(std::string(path) + ": " + g_init_error); return -1; }
+  pcm16.resize((size_t)n16);
+  const float* in = wav.mono.data();
+  float* out = pcm16.data();
+  const int n = (int)wav.mono.size(), cap = (int)n16;
+  int n_out = 0;
+  return AX_WHISPER_ResampleBatch(handle, &in, &n, &wav.sample_rate, 1, &out, &cap, &n_out);
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileResampled(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  std::vector<float> pcm16;
+  axw::WavData wav;
+  if (load_file_16k(handle, wav_file, pcm16, wav) != 0) return -1;
+  return AX_WHISPER_RunPCM(handle, pcm16.data(), (int)pcm16.size(), result);
+}
+
+AX_WHISPER_API int AX_WHISPER_LoadAudioFile16k(AX_WHISPER_HANDLE handle, const char* path, float** samples, int* n_samples, int* info) {
+  if (!handle || !path || !samples || !n_samples) return -1;
+  *samples = nullptr;
+  *n_samples = 0;
+  std::vector<float> pcm16;
+  axw::WavData wav;
+  if (load_file_16k(handle, path, pcm16, wav) != 0) return -1;
+  *samples = static_cast<float*>(malloc(std::max<size_t>(pcm16.size(), 1) * sizeof(float)));
+  if (!*samples) return -1;
+  memcpy(*samples, pcm16.data(), pcm16.size() * sizeof(float));
+  *n_samples = (int)pcm16.size();
+  if (info) { info[0] = wav.sample_rate; info[1] = wav.channels; info[2] = (int)wav.mono.size(); }
+  return 0;
 }
 
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5) {

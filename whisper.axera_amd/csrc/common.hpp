@@ -300,6 +300,41 @@ struct MelWindowParams {
 };
 void launch_mel_window(const MelWindowParams& p, hipStream_t s);
 
+// ------------------------------------------------------------------ sample-rate conversion (resample.hip; DESIGN.md "Sample rates")
+// One launch over a ragged batch of clips, each at its own rate: y_j = sum over i < 2 K of x[i0 + i - K + 1] H[r][i] with
+// i0 = floor(j M / L), r = (j M) mod L, x zero outside the clip (resample.hpp: the definition and the table H [L][2 K]).
+constexpr int kResampleTile = 256;        // consecutive outputs of one clip per workgroup, one per thread
+// LDS floats for a tile's input span [i0(first) - K + 1, i0(last) + K]: at most ceil(255 M / L) + 2 K, and M / L <= 24 (384 kHz),
+// K <= ceil(64 * 24 / ROLLOFF) = 1621 for every accepted rate, so 6120 + 3242 = 9362 is the widest: one staging pass always fits
+constexpr int kResampleSpan = 9472;
+constexpr int kResampleLdsTable = 2048;   // tables of up to this many entries (8, 12, 24 kHz) are read from LDS, larger ones through L2
+// A table on the device is H [L][2 K] as resample.hpp defines it, except a table with more than one phase that does not fit
+// kResampleLdsTable: that one is stored tap-major, [2 K][L] (lanes of a wave then read neighbouring entries; resample.hip)
+inline bool resample_table_tap_major(int L, int K) { return L > 1 && (long)L * 2 * K > kResampleLdsTable; }
+struct ResampleClip {       // device, one per clip of the launch
+  long long in_off;         // the clip's samples are in[in_off ... in_off + n_in)
+  long long out_off;        // packed placement: output j goes to out[out_off + j]
+  long long tab_off;        // the clip's table is tables[tab_off ... tab_off + L * 2 K), in the layout resample_table_tap_major says
+  int n_in, n_out;          // 1 <= n_in, n_out = ceil(n_in L / M)
+  int L, M, K;
+  int row;                  // row placement: the clip's staging row
+};
+struct ResampleParams {
+  const float* in; const float* tables;
+  const ResampleClip* clips;  // device [batch]
+  int batch;
+  float* out;
+  // stride > 0, row placement (the engine's staging rows, FrontendParams::overflow / over_off): output j of a clip goes to
+  // out[row * stride + j] for j < stride, else to overflow[over_off[row] + j - stride]; stride == 0: packed placement
+  int stride;
+  float* overflow; const long long* over_off;
+  int max_out;                // the largest n_out of the launch (grid.x = its tiles)
+};
+inline bool resample_shape_ok(int L, int M, int K) {  // what the kernel takes: the widest span of a tile fits its LDS
+  return L >= 1 && M >= 1 && K >= 1 && ((long)(kResampleTile - 1) * M + L - 1) / L + 2L * K <= kResampleSpan;
+}
+void launch_resample(const ResampleParams& p, hipStream_t s);
+
 // ------------------------------------------------------------------ decoder
 struct DecState {          // device-resident loop state, one per engine
   int step;                // decoder steps run since the last reset (bookkeeping; no kernel derives a position from it)

@@ -4,6 +4,7 @@
 #include "engine_impl.hpp"
 
 #include "host_io.hpp"
+#include "resample.hpp"
 #include "words.hpp"
 
 namespace axw {
@@ -564,17 +565,94 @@ void Engine::ensure_capacity(int batch) {
 }
 
 // ------------------------------------------------------------------------------ front-end
-void Engine::upload_pcm(const float* const* pcm, const int* n_samples, int batch) {
+// The filter of `rate` and its table in d_rs_tables_ (resample.hpp), built in float64 and uploaded the first time the handle meets
+// the rate. Throws on a rate resample.hpp refuses, before anything is allocated.
+const Engine::RateTable& Engine::rate_table(int rate) {
+  auto it = rate_tables_.find(rate);
+  if (it != rate_tables_.end()) return it->second;
+  resample::Filter f;
+  std::string err;
+  if (!resample::plan(rate, f, err)) throw std::runtime_error(err);
+  if (!resample_shape_ok(f.L, f.M, f.K)) throw std::runtime_error("sample rate " + std::to_string(rate) + " Hz: a tile's input span exceeds the kernel's LDS");
+  std::vector<float> H = resample::build_table(f);  // host work, outside the mutex
+  if (resample_table_tap_major(f.L, f.K)) {  // the device layout of a large table (common.hpp)
+    const int T = f.taps();
+    std::vector<float> Ht(H.size());
+    for (int r = 0; r < f.L; ++r)
+      for (int i = 0; i < T; ++i) Ht[(size_t)i * f.L + r] = H[(size_t)r * T + i];
+    H.swap(Ht);
+  }
+  // allocation and synchronous copies, which must not run beside another handle's stream capture (iengine.hpp)
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipStreamSynchronize(stream()));  // an earlier pass on this stream may still read the arena
+  const size_t need = rs_tables_used_ + H.size();
+  if (need > rs_tables_cap_) {
+    const size_t cap = std::max(need, 2 * rs_tables_cap_);
+    DeviceArray<float> grown = device_array<float>(cap);
+    if (rs_tables_used_) HIP_CHECK(hipMemcpy(grown, d_rs_tables_, rs_tables_used_ * 4, hipMemcpyDeviceToDevice));
+    d_rs_tables_ = std::move(grown);
+    rs_tables_cap_ = cap;
+  }
+  HIP_CHECK(hipMemcpy(d_rs_tables_ + rs_tables_used_, H.data(), H.size() * 4, hipMemcpyHostToDevice));
+  const RateTable t{f.L, f.M, f.K, (long long)rs_tables_used_};
+  rs_tables_used_ = need;
+  return rate_tables_.emplace(rate, t).first->second;
+}
+
+void Engine::ensure_resample_staging(size_t raw_samples, int clips) {
+  if (raw_samples <= raw_cap_ && clips <= rs_clips_cap_) return;
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipStreamSynchronize(stream()));  // an earlier pass on this stream may still read the staging
+  if (raw_samples > raw_cap_) {
+    d_raw_.reset(); h_raw_.reset();  // (first: the old and the new need not fit side by side)
+    raw_cap_ = 0;
+    d_raw_ = device_array<float>(raw_samples);
+    h_raw_ = pinned_array<float>(raw_samples);
+    raw_cap_ = raw_samples;
+  }
+  if (clips > rs_clips_cap_) {
+    d_rs_clips_.reset(); h_rs_clips_.reset();
+    rs_clips_cap_ = 0;
+    d_rs_clips_ = device_array<ResampleClip>((size_t)clips);
+    h_rs_clips_ = pinned_array<ResampleClip>((size_t)clips);
+    rs_clips_cap_ = clips;
+  }
+}
+
+void Engine::upload_pcm(const float* const* pcm, const int* n_samples, int batch, const int* rates, int* n_16k) {
   // Clips longer than a staging row: the reference computes the log-mel of the WHOLE input and takes the maximum over
   // all of its frames before it keeps 3000 of them (Whisper.cpp:158-172), so every sample counts for the clamp floor.
   // The first pcm_stride_ samples go through the pinned staging rows as always; the tails are packed into d_over_.
+  // A clip at another rate than 16 kHz (DESIGN.md "Sample rates"): its samples go to the raw staging as they are, and the resample
+  // kernel writes the clip's staging row and its tail in d_over_, where the front-end reads them. Everything below counts a
+  // clip's length at 16 kHz.
+  if (rates && !n_16k) throw std::runtime_error("upload_pcm: sample rates without a place for the resampled lengths");
+  std::vector<int> n16(n_samples, n_samples + batch);
+  std::vector<const RateTable*> rt(batch, nullptr);
+  size_t raw_total = 0;
+  int n_rs = 0;
+  for (int b = 0; b < batch && rates; ++b) {  // a refused rate or length fails here, before any GPU work
+    if (rates[b] == resample::kTargetRate) continue;
+    if (n_samples[b] < 1) throw std::runtime_error("empty audio clip");
+    std::string err;
+    const long long len = resample::resampled_length(n_samples[b], rates[b], err);
+    if (len < 0) throw std::runtime_error("clip " + std::to_string(b) + ": " + err);
+    n16[b] = (int)len;
+    raw_total += (size_t)n_samples[b];
+    ++n_rs;
+  }
+  if (n_rs) {
+    for (int b = 0; b < batch; ++b)
+      if (rates[b] != resample::kTargetRate) rt[b] = &rate_table(rates[b]);
+    ensure_resample_staging(raw_total, n_rs);
+  }
   std::vector<long long> off(batch, 0);
   size_t over_total = 0;
   for (int b = 0; b < batch; ++b) {
     // (the reflect-pad index of the STFT is 2n - 2 - j in 32-bit arithmetic: 2^29 samples = 9.3 hours is the cap)
-    if (n_samples[b] > (1 << 29)) throw std::runtime_error("clip " + std::to_string(b) + ": more than 2^29 samples");
+    if (n16[b] > (1 << 29)) throw std::runtime_error("clip " + std::to_string(b) + ": more than 2^29 samples");
     off[b] = (long long)over_total;
-    if (n_samples[b] > pcm_stride_) over_total += (size_t)n_samples[b] - (size_t)pcm_stride_;
+    if (n16[b] > pcm_stride_) over_total += (size_t)n16[b] - (size_t)pcm_stride_;
   }
   over_used_ = over_total > 0;
   // rare path (clips beyond a 60 s staging row): allocation and synchronous copies, which must not run beside another
@@ -591,7 +669,24 @@ void Engine::upload_pcm(const float* const* pcm, const int* n_samples, int batch
     over_cap_ = over_total;
   }
   if (over_used_) HIP_CHECK(hipMemcpy(d_over_off_, off.data(), (size_t)batch * 8, hipMemcpyHostToDevice));
+  size_t raw_off = 0;
+  int k = 0, max_out = 0;
   for (int b = 0; b < batch; ++b) {
+    if (rt[b]) {
+      // the finite-sample check runs on the raw samples, as below
+      float* dst = h_raw_ + raw_off;
+      const size_t n = (size_t)n_samples[b];
+      memcpy(dst, pcm[b], n * 4);
+      unsigned bad = 0;
+      for (size_t i = 0; i < n; ++i) bad |= !std::isfinite(dst[i]);
+      if (bad) throw std::runtime_error("clip " + std::to_string(b) + ": non-finite PCM sample (NaN or Inf)");
+      HIP_CHECK(hipMemcpyAsync(d_raw_ + raw_off, dst, n * 4, hipMemcpyHostToDevice, stream()));
+      ResampleClip& c = h_rs_clips_[k++];
+      c = ResampleClip{(long long)raw_off, 0, rt[b]->tab_off, n_samples[b], n16[b], rt[b]->L, rt[b]->M, rt[b]->K, b};
+      max_out = std::max(max_out, n16[b]);
+      raw_off += n;
+      continue;
+    }
     const int n = (int)std::min<long>(n_samples[b], pcm_stride_);
     // pcm_data is copied, not retained (api.cpp:151-152). The ABI asks for samples in [-1, 1] (ax_whisper_api.h:89 of the
     // reference); NaN / Inf samples turn every mel value, hence every logit, into NaN: refuse them here (-1 at the ABI)
@@ -607,6 +702,73 @@ void Engine::upload_pcm(const float* const* pcm, const int* n_samples, int batch
     HIP_CHECK(hipMemcpyAsync(d_pcm_ + (size_t)b * pcm_stride_, h_pcm_ + (size_t)b * pcm_stride_, (size_t)n * 4,
                              hipMemcpyHostToDevice, stream()));
     if (n_tail) HIP_CHECK(hipMemcpy(d_over_ + off[b], tail, n_tail * 4, hipMemcpyHostToDevice));  // rare path: pageable, synchronous
+  }
+  if (n_rs) {
+    HIP_CHECK(hipMemcpyAsync(d_rs_clips_, h_rs_clips_, (size_t)n_rs * sizeof(ResampleClip), hipMemcpyHostToDevice, stream()));
+    ResampleParams p{};
+    p.in = d_raw_; p.tables = d_rs_tables_; p.clips = d_rs_clips_; p.batch = n_rs;
+    p.out = d_pcm_; p.stride = (int)pcm_stride_; p.max_out = max_out;
+    if (over_used_) { p.overflow = d_over_; p.over_off = d_over_off_; }
+    launch_resample(p, stream());
+  }
+  if (n_16k) memcpy(n_16k, n16.data(), (size_t)batch * 4);
+}
+
+// Stage level: the resample kernel alone on host clips, packed placement; device buffers of this call's size.
+void Engine::resample(const float* const* pcm, const int* n_samples, const int* rates, int batch, float* const* out, const int* out_cap,
+                      int* n_out) {
+  require_no_stream("resample");
+  if (batch < 1) throw std::runtime_error("batch must be >= 1");
+  std::vector<long long> len(batch);
+  size_t in_total = 0, out_total = 0;
+  int n_rs = 0, max_out = 0;
+  for (int b = 0; b < batch; ++b) {  // every refusal before any GPU work
+    if (n_samples[b] < 1) throw std::runtime_error("empty audio clip");
+    std::string err;
+    len[b] = resample::resampled_length(n_samples[b], rates[b], err);
+    if (len[b] < 0) throw std::runtime_error("clip " + std::to_string(b) + ": " + err);
+    if (len[b] > out_cap[b]) throw std::runtime_error("clip " + std::to_string(b) + ": " + std::to_string(len[b]) + " samples at 16000 Hz do not fit out_cap");
+    unsigned bad = 0;
+    for (int i = 0; i < n_samples[b]; ++i) bad |= !std::isfinite(pcm[b][i]);
+    if (bad) throw std::runtime_error("clip " + std::to_string(b) + ": non-finite PCM sample (NaN or Inf)");
+    if (rates[b] == resample::kTargetRate) continue;
+    in_total += (size_t)n_samples[b]; out_total += (size_t)len[b];
+    max_out = std::max(max_out, (int)len[b]);
+    ++n_rs;
+  }
+  HIP_CHECK(hipSetDevice(device_));
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));  // allocations + synchronous copies (iengine.hpp)
+  if (n_rs) {
+    std::vector<ResampleClip> clips;
+    for (int b = 0; b < batch; ++b)
+      if (rates[b] != resample::kTargetRate) {
+        const RateTable& t = rate_table(rates[b]);
+        clips.push_back(ResampleClip{0, 0, t.tab_off, n_samples[b], (int)len[b], t.L, t.M, t.K, 0});
+      }
+    DeviceArray<float> d_in = device_array<float>(in_total), d_out = device_array<float>(out_total);
+    DeviceArray<ResampleClip> d_clips = device_array<ResampleClip>(clips.size());
+    size_t io = 0, oo = 0, k = 0;
+    for (int b = 0; b < batch; ++b) {
+      if (rates[b] == resample::kTargetRate) continue;
+      HIP_CHECK(hipMemcpy(d_in + io, pcm[b], (size_t)n_samples[b] * 4, hipMemcpyHostToDevice));
+      clips[k].in_off = (long long)io; clips[k].out_off = (long long)oo;
+      io += (size_t)n_samples[b]; oo += (size_t)len[b]; ++k;
+    }
+    HIP_CHECK(hipMemcpy(d_clips, clips.data(), clips.size() * sizeof(ResampleClip), hipMemcpyHostToDevice));
+    ResampleParams p{};
+    p.in = d_in; p.tables = d_rs_tables_; p.clips = d_clips; p.batch = n_rs; p.out = d_out; p.stride = 0; p.max_out = max_out;
+    launch_resample(p, stream());
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    k = 0;
+    for (int b = 0; b < batch; ++b) {
+      if (rates[b] == resample::kTargetRate) continue;
+      HIP_CHECK(hipMemcpy(out[b], d_out + clips[k].out_off, (size_t)len[b] * 4, hipMemcpyDeviceToHost));
+      ++k;
+    }
+  }
+  for (int b = 0; b < batch; ++b) {
+    if (rates[b] == resample::kTargetRate) memcpy(out[b], pcm[b], (size_t)n_samples[b] * 4);  // the identity, bit for bit
+    n_out[b] = (int)len[b];
   }
 }
 
@@ -779,9 +941,11 @@ void Engine::run_tokens(const DecodeRequest& rq, const float* const* pcm, const 
   hipStream_t s = stream();
   HIP_CHECK(hipEventRecord(ev_[0], s));
   if (pcm) {
-    upload_pcm(pcm, n_samples, batch);
-    run_frontend(d_pcm_, (int)pcm_stride_, n_samples, batch, false, true);
+    std::vector<int> n16(batch);  // the clips' lengths at 16 kHz: their own without rates
+    upload_pcm(pcm, n_samples, batch, rq.sample_rate, n16.data());
+    run_frontend(d_pcm_, (int)pcm_stride_, n16.data(), batch, false, true);
   } else {
+    if (rq.sample_rate) throw std::runtime_error("run_tokens: device PCM is taken at 16000 Hz (no sample rates)");
     run_frontend(d_pcm, d_stride, n_samples, batch, false);
   }
   HIP_CHECK(hipEventRecord(ev_[1], s));
@@ -845,14 +1009,15 @@ std::string Engine::detokenize(const int32_t* ids, int n) const {
   return out;
 }
 
-void Engine::compute_mel(const float* pcm, int n_samples, float* mel_out) {
+void Engine::compute_mel(const float* pcm, int n_samples, float* mel_out, int rate) {
   // an open stream's admission pass may still be reading the staging rows and front-end buffers this call overwrites
   require_no_stream("compute_mel");
   HIP_CHECK(hipSetDevice(device_));
   ensure_capacity(1);
   const float* arr[1] = {pcm};
-  upload_pcm(arr, &n_samples, 1);
-  run_frontend(d_pcm_, (int)pcm_stride_, &n_samples, 1, true, true);
+  int n16 = n_samples;
+  upload_pcm(arr, &n_samples, 1, &rate, &n16);
+  run_frontend(d_pcm_, (int)pcm_stride_, &n16, 1, true, true);
   HIP_CHECK(hipMemcpyAsync(mel_out, d_mel_ref_, (size_t)cfg_.n_mels * kFramesOut * 4, hipMemcpyDeviceToHost, stream()));
   HIP_CHECK(hipStreamSynchronize(stream()));
 }

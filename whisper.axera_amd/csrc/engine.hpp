@@ -64,6 +64,12 @@ struct EngineMemory {
   // clips longer than a staging row (60 s): their tails, packed, so that the clamp floor comes from ALL frames of the
   // input however long it is (Whisper.cpp:158-172); grown on demand, empty for ordinary requests
   DeviceArray<float> d_over_; size_t over_cap_ = 0;
+  // sample rates (DESIGN.md "Sample rates"): the filter tables of every rate the handle has met, packed in one arena (built on
+  // first use under device_capture_mutex, kept for the handle's life), and the raw staging of clips that are not at 16 kHz: their
+  // samples as uploaded (pinned host + device, grown on demand under the mutex, kept) and the launch's clip descriptors
+  DeviceArray<float> d_rs_tables_; size_t rs_tables_cap_ = 0, rs_tables_used_ = 0;
+  DeviceArray<float> d_raw_; PinnedArray<float> h_raw_; size_t raw_cap_ = 0;
+  DeviceArray<ResampleClip> d_rs_clips_; PinnedArray<ResampleClip> h_rs_clips_; int rs_clips_cap_ = 0;
   LongArena long_;
   PinnedArray<int> h_long_win_; int h_long_win_cap_ = 0;  // pinned [2][windows per pass]: file and seek of every slot
   PinnedArray<int> h_poll_;
@@ -139,7 +145,9 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   std::string transcript(const int32_t* ids, int n) const override;
   std::string transcript_lang(const int32_t* ids, int n, int lang) const override;
   bool has_t2s() const { return (bool)t2s_; }
-  void compute_mel(const float* pcm, int n_samples, float* mel_out) override;
+  void compute_mel(const float* pcm, int n_samples, float* mel_out, int rate = 16000) override;
+  void resample(const float* const* pcm, const int* n_samples, const int* rates, int batch, float* const* out, const int* out_cap,
+                int* n_out) override;
   void encode_mel(const float* mel, int batch) override;
   void get_cross_kv(int slot, float* k_out, float* v_out) override;
   void decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
@@ -163,7 +171,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void set_alignment_heads(const int* pairs, int n) override;
   void align_kernel(int which, const AlignKernelIO& io) override;
   void stream_open(int n_slots) override;
-  void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) override;
+  void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count,
+                    const int* rates = nullptr) override;
   int stream_step(int n_steps, int* finished_slots) override;
   void stream_collect(int slot, int32_t* ids, int* n_ids) override;
   void stream_close() override;
@@ -197,7 +206,15 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   std::unique_ptr<T2SConverter> find_t2s() const;  // the converter of the first t2s.json found, or null
   void ensure_capacity(int batch);
   void free_slot_buffers();
-  void upload_pcm(const float* const* pcm, const int* n_samples, int batch);
+  // rates (or null: every clip at 16000 Hz): a clip at another rate goes to the raw staging and the resample kernel writes its
+  // staging row (and overflow tail); n_16k (required with rates): the clips' lengths at 16 kHz, which run_frontend then takes
+  void upload_pcm(const float* const* pcm, const int* n_samples, int batch, const int* rates = nullptr, int* n_16k = nullptr);
+  // sample rates (engine.cpp): a rate's filter and where its table sits in d_rs_tables_ (built and uploaded on first use)
+  struct RateTable { int L, M, K; long long tab_off; };
+  std::map<int, RateTable> rate_tables_;
+  const RateTable& rate_table(int rate);
+  void ensure_resample_staging(size_t raw_samples, int clips);  // d_raw_ / h_raw_, d_rs_clips_ / h_rs_clips_
+  float bench_resample(int batch, int rate, int iters);
   // pinned_ns: optional pinned host [batch] the clip lengths are staged through (then nothing here waits for the stream)
   void run_frontend(const float* d_pcm, int stride, const int* n_samples, int batch, bool want_ref_layout, bool staged = false,
                     int* pinned_ns = nullptr);

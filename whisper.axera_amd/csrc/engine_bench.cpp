@@ -2,6 +2,8 @@
 // isolation (one private function per target), AX_WHISPER_ScanStored16 looks for non-finite values in what the engine stores.
 #include "engine_impl.hpp"
 
+#include "resample.hpp"
+
 namespace axw {
 inline namespace AXW_NS {
 
@@ -70,6 +72,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "attn_stamp") return bench_attn_stamp(batch, arg, iters);
   if (what == "encoder") return bench_encoder(batch, iters);
   if (what == "frontend") return bench_frontend(batch, iters);
+  if (what == "resample") return bench_resample(batch, arg, iters);
   if (what == "frontend_long") return bench_frontend_long(batch, arg, iters);
   if (what == "prefill" || what == "prefill_pass" || what == "prefill_step") return bench_prefill(what, batch, arg, iters);
   if (what == "detect_language") return bench_detect_language(batch, arg, iters);
@@ -339,6 +342,25 @@ float Engine::bench_frontend(int batch, int iters) {
   std::vector<int> ns(batch, 480000);
   run_frontend(d_pcm_, (int)pcm_stride_, ns.data(), batch, false);
   return timed_ms(stream(), [&] { for (int i = 0; i < iters; ++i) run_frontend(d_pcm_, (int)pcm_stride_, ns.data(), batch, false); });
+}
+
+// the resample kernel over `batch` clips of 30 s (silence) at `rate` Hz into the staging rows, as upload_pcm launches it
+float Engine::bench_resample(int batch, int rate, int iters) {
+  if (rate == resample::kTargetRate) throw std::runtime_error("bench resample: arg = the clips' sample rate, other than 16000");
+  const RateTable& t = rate_table(rate);
+  const int n = 30 * rate;
+  std::string err;
+  const int n_out = (int)resample::resampled_length(n, rate, err);
+  ensure_resample_staging((size_t)batch * n, batch);
+  for (int b = 0; b < batch; ++b) h_rs_clips_[b] = ResampleClip{(long long)b * n, 0, t.tab_off, n, n_out, t.L, t.M, t.K, b};
+  hipStream_t s = stream();
+  HIP_CHECK(hipMemsetAsync(d_raw_, 0, (size_t)batch * n * 4, s));
+  HIP_CHECK(hipMemcpyAsync(d_rs_clips_, h_rs_clips_, (size_t)batch * sizeof(ResampleClip), hipMemcpyHostToDevice, s));
+  ResampleParams p{};
+  p.in = d_raw_; p.tables = d_rs_tables_; p.clips = d_rs_clips_; p.batch = batch;
+  p.out = d_pcm_; p.stride = (int)pcm_stride_; p.max_out = n_out;
+  launch_resample(p, s);
+  return timed_ms(s, [&] { for (int i = 0; i < iters; ++i) launch_resample(p, s); });
 }
 
 // whole-file front-end of `batch` files of `arg` seconds (silence) + one window kernel over all of them

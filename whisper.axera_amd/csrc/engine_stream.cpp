@@ -57,7 +57,7 @@ void Engine::stream_close() {
   cfg_.ints["stream_slots"] = 0;
 }
 
-void Engine::stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) {
+void Engine::stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count, const int* rates) {
   HIP_CHECK(hipSetDevice(device_));
   if (stream_slots_ == 0) throw std::runtime_error("stream_admit: no stream open");
   if (count < 1 || count > stream_user_slots_) throw std::runtime_error("stream_admit: count out of range");
@@ -78,7 +78,8 @@ void Engine::stream_admit(const int* slots, const float* const* pcm, const int* 
     ~StreamSwap() { u = keep; }
   } swap(user_stream_, admit_stream_);
   // Nothing below waits for an earlier pass's ENCODER: the ring entry of this pass was last used kAdmitRing passes ago, the
-  // PCM staging rows by the pass before (its uploads are the first thing it enqueued)
+  // PCM staging rows by the pass before (its uploads are the first thing it enqueued). With sample rates the pass's resample kernel
+  // reads the raw staging behind those uploads, so ev_upload_ is recorded behind that kernel: one wait covers both stagings
   const int ring = (int)(admit_seq_ % kAdmitRing);
   if (admit_seq_ >= kAdmitRing) HIP_CHECK(hipEventSynchronize(ev_ring_[ring]));
   if (admit_seq_ > 0) HIP_CHECK(hipEventSynchronize(ev_upload_));
@@ -86,9 +87,10 @@ void Engine::stream_admit(const int* slots, const float* const* pcm, const int* 
   int* h_map = h_ns + cap_;
   memcpy(h_map, slots, (size_t)count * 4);
   HIP_CHECK(hipMemcpyAsync(d_slot_map_, h_map, (size_t)count * 4, hipMemcpyHostToDevice, admit_stream_));
-  upload_pcm(pcm, n_samples, count);
+  std::vector<int> n16(count);  // the clips' lengths at 16 kHz: their own without rates
+  upload_pcm(pcm, n_samples, count, rates, n16.data());  // (with rates: uploads, then the resample kernel)
   HIP_CHECK(hipEventRecord(ev_upload_, admit_stream_));
-  run_frontend(d_pcm_, (int)pcm_stride_, n_samples, count, false, true, h_ns);
+  run_frontend(d_pcm_, (int)pcm_stride_, n16.data(), count, false, true, h_ns);
   run_encoder(count, d_slot_map_);
   HIP_CHECK(hipEventRecord(ev_ring_[ring], admit_stream_));
   ++admit_seq_;

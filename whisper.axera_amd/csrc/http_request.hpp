@@ -18,6 +18,8 @@ struct HttpHead {
   size_t content_length = 0;    // 0 if absent or malformed
   bool length_ok = true;        // false: a Content-Length header is present but is not a plain decimal number
   bool expect_continue = false;
+  int sample_rate = 16000;      // value of X-Sample-Rate in Hz (16000 if absent)
+  bool rate_ok = true;          // false: an X-Sample-Rate header is present but is not a plain positive decimal number
   size_t header_end = std::string::npos;  // offset of the blank line's "\r\n\r\n" in the buffer
 };
 
@@ -62,6 +64,13 @@ inline bool parse_http_head(const std::string& buf, HttpHead& h) {
     h.length_ok = !cl.empty() && cl.size() <= 15 && std::all_of(cl.begin(), cl.end(), [](char c) { return c >= '0' && c <= '9'; });
     if (h.length_ok) h.content_length = (size_t)strtoull(cl.c_str(), nullptr, 10);
   }
+  bool has_rate = false;
+  const std::string sr = http_header_value(lhead, "x-sample-rate:", &has_rate);
+  if (has_rate) {
+    // a plain decimal number of at most 7 digits, not zero; which rates the engine takes is its own decision (a refused one is a 400 too)
+    h.rate_ok = !sr.empty() && sr.size() <= 7 && std::all_of(sr.begin(), sr.end(), [](char c) { return c >= '0' && c <= '9'; }) && atoi(sr.c_str()) > 0;
+    if (h.rate_ok) h.sample_rate = atoi(sr.c_str());
+  }
   h.content_type = http_header_value(lhead, "content-type:");
   h.expect_continue = http_header_value(lhead, "expect:").find("100-continue") != std::string::npos;
   return true;
@@ -81,6 +90,7 @@ inline const char* asr_request_error(const HttpHead& h, size_t body_bytes) {
     return R"({"error": "Content-Type must be application/octet-stream"})";
   if (body_bytes == 0) return R"({"error": "Request body is empty"})";                     // hpp:58-62
   if (body_bytes % sizeof(float) != 0) return R"({"error": "Data size must be multiple of 4 bytes"})";  // hpp:65-71
+  if (!h.rate_ok) return R"({"error": "X-Sample-Rate must be a positive integer in Hz"})";
   return nullptr;
 }
 

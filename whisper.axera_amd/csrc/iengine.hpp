@@ -72,11 +72,14 @@ class IEngine {
     DecodeMode mode = kDecodePlain;
     int max_new = 0;
     const int* max_new_clip = nullptr;
+    // host [batch] sample rates of the clips in Hz (DESIGN.md "Sample rates"), null: every clip is 16000 Hz. A clip at another rate is
+    // resampled on the GPU between its upload and the front-end; a rate resample.hpp refuses fails the call before any GPU work
+    const int* sample_rate = nullptr;
     std::optional<SampleSpec> sample;
     ClipContexts ctx;
     std::optional<ClipScores> scores;
     // THE block rule of a batch split over devices (multi_device.hpp): the same request for the clips from `lo` on. Every per-clip
-    // array that is not null moves to its entry of clip lo: token_logprob by rows of n_ctx, the prompt ids by rows of their stride,
+    // array that is not null (the sample rates among them) moves to its entry of clip lo: token_logprob by rows of n_ctx, the prompt ids by rows of their stride,
     // lang_logprob and lang_logit by rows of n_lang, every other array by one entry per clip.
     DecodeRequest block(int lo, int n_ctx, int n_lang) const;
   };
@@ -91,7 +94,12 @@ class IEngine {
   // the text of ids decoded under language `lang` (an index of the config's list): the zh pass follows that language, not the handle's
   virtual std::string transcript_lang(const int32_t* ids, int n, int lang) const = 0;
   // stage-level
-  virtual void compute_mel(const float* pcm, int n_samples, float* mel_out) = 0;
+  // rate: the clip's sample rate; other than 16000 Hz the clip is resampled on the GPU first (the fused upload path)
+  virtual void compute_mel(const float* pcm, int n_samples, float* mel_out, int rate = 16000) = 0;
+  // the resample kernel alone on host clips (DESIGN.md "Sample rates"): out[b] (capacity out_cap[b] samples) receives the n_out[b]
+  // samples of clip b at 16000 Hz; a clip at 16000 Hz is copied bit for bit. Device buffers are sized by the call.
+  virtual void resample(const float* const* pcm, const int* n_samples, const int* rates, int batch, float* const* out, const int* out_cap,
+                        int* n_out) = 0;
   virtual void encode_mel(const float* mel, int batch) = 0;
   virtual void get_cross_kv(int slot, float* k_out, float* v_out) = 0;
   // the slot's self-attention cache rows [0, n_rows), de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][d]
@@ -183,7 +191,9 @@ class IEngine {
   virtual void align_kernel(int which, const AlignKernelIO& io) = 0;  // 0 qk_softmax, 1 normalize, 2 dtw
   // utterance slots refilled while the others decode (include/ax_whisper_api.h: AX_WHISPER_Stream*)
   virtual void stream_open(int n_slots) = 0;
-  virtual void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count) = 0;
+  // rates (or null: 16000 Hz): host [count], as DecodeRequest::sample_rate
+  virtual void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count,
+                            const int* rates = nullptr) = 0;
   virtual int stream_step(int n_steps, int* finished_slots) = 0;  // returns the number of finished slots written
   virtual void stream_collect(int slot, int32_t* ids, int* n_ids) = 0;
   virtual void stream_close() = 0;
@@ -223,6 +233,7 @@ inline IEngine::DecodeRequest IEngine::DecodeRequest::block(int lo, int n_ctx, i
   auto from = [](auto* p, size_t k) { return p ? p + k : p; };
   DecodeRequest r = *this;
   r.max_new_clip = from(max_new_clip, lo);
+  r.sample_rate = from(sample_rate, lo);
   if (r.sample) *r.sample = {from(sample->temperature, lo), from(sample->stream, lo), sample->seed};
   r.ctx = ctx.block(lo, n_lang);
   if (r.scores)

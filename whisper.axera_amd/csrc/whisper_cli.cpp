@@ -46,6 +46,10 @@ static void usage(const char* prog) {
           "      --detect_language   (with --timestamps or --long, not with --beam_size) detect the language from the first 30 s and\n"
           "                      decode under it; prints Detected language: <code> (p = ...) before Result:. (--language keeps its\n"
           "                      meaning: the handle's language, where an unknown code silently becomes zh; it has no \"auto\")\n"
+          "      --resample      a file whose sample rate is not 16000 Hz is converted to 16 kHz on the GPU first, by the file's own\n"
+          "                      rate (1000 .. 384000 Hz; AX_WHISPER_LoadAudioFile16k); every mode above then works on it, and the\n"
+          "                      duration behind RTF: is the file's real one. Without the flag nothing changes: such a file is fed\n"
+          "                      as it is, with a warning, and its duration is counted at 16000 Hz\n"
           "      --task T        transcribe or translate (with --timestamps or --long, not with --beam_size) [=transcribe]\n"
           "  -?, --help          print this message\n",
           prog);
@@ -97,6 +101,14 @@ static bool wav_frames(const char* path, long* frames) {
   }
 }
 
+// --resample: the file's samples at 16 kHz (AX_WHISPER_LoadAudioFile16k: file decode + GPU resampling); else the file's samples as
+// they are. info3 (or null): the file's sample rate, channels, samples per channel.
+static bool g_resample = false;
+static int load_pcm(AX_WHISPER_HANDLE h, const char* wav, float** pcm, int* n, int* info3 = nullptr) {
+  if (g_resample) return AX_WHISPER_LoadAudioFile16k(h, wav, pcm, n, info3);
+  return AX_WHISPER_LoadAudioFile(wav, pcm, n, nullptr);
+}
+
 static std::string mmss_ms(long ms) {
   char b[32];
   snprintf(b, sizeof b, "%02ld:%02ld.%03ld", ms / 60000, (ms / 1000) % 60, ms % 1000);
@@ -124,7 +136,7 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size, b
   const bool per_lang = detect || task >= 0;
   float* pcm = nullptr;
   int n = 0;
-  if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
+  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
   const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx");
   std::vector<int32_t> ids(n_ctx > 0 ? n_ctx : 448);
   int n_ids = 0;
@@ -179,7 +191,7 @@ static int print_segments(AX_WHISPER_HANDLE h, const char* wav, int beam_size, b
 static int print_words(AX_WHISPER_HANDLE h, const char* wav) {
   float* pcm = nullptr;
   int n = 0;
-  if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
+  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
   const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
   std::vector<int32_t> ids(n_ctx);
   std::vector<int> wseg(n_ctx), wte(n_ctx);
@@ -232,7 +244,7 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
   const size_t sw = fallback ? 7 : 3;  // floats per window score row
   float* pcm = nullptr;
   int n = 0;
-  if (AX_WHISPER_LoadAudioFile(wav, &pcm, &n, nullptr) != 0 || n < 1) { free(pcm); return -1; }
+  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
   const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
   const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
   int cap = (n / 160 + 1) * (fallback ? (int)temps.size() : 1);  // every window advances by at least one frame (after at most temps.size() attempts)
@@ -318,6 +330,7 @@ int main(int argc, char** argv) {
     if (a == "--timestamps") { timestamps = true; continue; }
     if (a == "--word_timestamps") { word_timestamps = true; continue; }
     if (a == "--long") { longform = true; continue; }
+    if (a == "--resample") { g_resample = true; continue; }
     if (a == "--condition_on_previous_text") { condition = true; continue; }
     if (a == "--detect_language") { detect = true; continue; }
     fprintf(stderr, "undefined option: %s\n", a.c_str());
@@ -395,7 +408,7 @@ int main(int argc, char** argv) {
 
   long frames = 0;
   if (!wav_frames(wav.c_str(), &frames) || frames <= 0) { printf("load wav failed!\n"); return -1; }
-  const float duration = frames * 1.f / 16000;
+  float duration = frames * 1.f / 16000;
 
   auto t0 = std::chrono::steady_clock::now();
   // (beam search: one decoder slot per hypothesis)
@@ -404,6 +417,18 @@ int main(int argc, char** argv) {
   auto t1 = std::chrono::steady_clock::now();
   if (!handle) { printf("AX_WHISPER_Init failed!\n"); return -1; }
   printf("Init whisper success, take %.4fseconds\n", std::chrono::duration<double>(t1 - t0).count());
+  if (g_resample) {  // the file's real duration: its frames at its own rate
+    float* pcm = nullptr;
+    int n = 0, info[3] = {0, 0, 0};
+    if (load_pcm(handle, wav.c_str(), &pcm, &n, info) != 0 || info[0] < 1) {
+      printf("load wav failed! %s\n", AX_WHISPER_LastError(handle));
+      free(pcm);
+      AX_WHISPER_Uninit(handle);
+      return -1;
+    }
+    free(pcm);
+    duration = info[2] * 1.f / info[0];
+  }
 
   if (longform) {
     t0 = std::chrono::steady_clock::now();
@@ -436,7 +461,7 @@ int main(int argc, char** argv) {
 
   t0 = std::chrono::steady_clock::now();
   char* result = nullptr;
-  if (0 != AX_WHISPER_RunFile(handle, wav.c_str(), &result)) {
+  if (0 != (g_resample ? AX_WHISPER_RunFileResampled(handle, wav.c_str(), &result) : AX_WHISPER_RunFile(handle, wav.c_str(), &result))) {
     printf("AX_WHISPER_Run failed!\n");
     AX_WHISPER_Uninit(handle);
     return -1;

@@ -5,6 +5,9 @@
 // with Content-Type application/octet-stream and a body of raw little-endian f32 PCM (16 kHz mono);
 // replies {"success": true, "text": ...}; 400 with the reference's error strings for a wrong
 // content type / empty body / size % 4 != 0 / failed run. Adds GET /health.
+// An optional request header X-Sample-Rate: <Hz> says that the body is at another rate than 16 kHz: the clip is then admitted
+// through the ...Rate calls (resampled on the GPU behind its upload, DESIGN.md "Sample rates"), in the slot-refill path and the batch
+// path alike; absent or 16000: the path it always took. A rate the engine refuses is a 400 with its error text.
 //
 // What is new: the reference calls one non-re-entrant handle from cpp-httplib's thread pool with
 // no lock. Here connection threads only parse requests and enqueue them; one
@@ -48,6 +51,7 @@
 
 struct Job {
   std::vector<float> pcm;
+  int rate = 16000;  // X-Sample-Rate
   std::promise<std::pair<bool, std::string>> done;
   std::chrono::steady_clock::time_point arrived = std::chrono::steady_clock::now();
 };
@@ -79,6 +83,28 @@ static std::string json_escape(const std::string& s) {
   return o;
 }
 
+// AX_WHISPER_RunPCMBatch over jobs whose clips may be at other rates than 16 kHz: with none of them, that call itself; otherwise
+// AX_WHISPER_RunPCMBatchRate and the transcript of every clip's ids
+static int run_batch_texts(AX_WHISPER_HANDLE model, Job* const* jobs, int n, char** texts) {
+  std::vector<const float*> ptrs(n);
+  std::vector<int> lens(n), rates(n);
+  bool all16 = true;
+  for (int i = 0; i < n; ++i) {
+    ptrs[i] = jobs[i]->pcm.data(); lens[i] = (int)jobs[i]->pcm.size(); rates[i] = jobs[i]->rate;
+    all16 = all16 && rates[i] == 16000;
+  }
+  if (all16) return AX_WHISPER_RunPCMBatch(model, ptrs.data(), lens.data(), n, texts);
+  const int Tc = std::max(1, AX_WHISPER_GetConfigInt(model, "n_text_ctx"));
+  std::vector<int32_t> ids((size_t)n * Tc);
+  std::vector<int> n_ids(n);
+  for (int i = 0; i < n; ++i) texts[i] = nullptr;
+  if (AX_WHISPER_RunPCMBatchRate(model, 0, ptrs.data(), lens.data(), rates.data(), n, 0, ids.data(), n_ids.data()) != 0) return -1;
+  int rc = 0;
+  for (int i = 0; i < n; ++i)
+    if (AX_WHISPER_Transcript(model, ids.data() + (size_t)i * Tc, n_ids[i], &texts[i]) != 0) rc = -1;
+  return rc;
+}
+
 static void batcher(AX_WHISPER_HANDLE model, int max_batch, int wait_ms) {
   while (!g_stop) {
     std::vector<Job*> jobs;
@@ -92,18 +118,15 @@ static void batcher(AX_WHISPER_HANDLE model, int max_batch, int wait_ms) {
     }
     const int n = (int)jobs.size();
     if (n == 0) continue;  // another device's batcher took the requests while this one waited for stragglers
-    std::vector<const float*> ptrs(n);
-    std::vector<int> lens(n);
     std::vector<char*> texts(n, nullptr);
-    for (int i = 0; i < n; ++i) { ptrs[i] = jobs[i]->pcm.data(); lens[i] = (int)jobs[i]->pcm.size(); }
-    int rc = AX_WHISPER_RunPCMBatch(model, ptrs.data(), lens.data(), n, texts.data());
+    int rc = run_batch_texts(model, jobs.data(), n, texts.data());
     std::vector<int> ok(n, rc == 0);
     if (rc != 0 && n > 1) {
       // one bad request (e.g. non-finite samples) must not fail the strangers batched with it: run them one by one
       for (int i = 0; i < n; ++i) {
         free(texts[i]);
         texts[i] = nullptr;
-        ok[i] = AX_WHISPER_RunPCMBatch(model, &ptrs[i], &lens[i], 1, &texts[i]) == 0;
+        ok[i] = run_batch_texts(model, &jobs[i], 1, &texts[i]) == 0;
       }
     }
     for (int i = 0; i < n; ++i) {
@@ -133,10 +156,8 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
   auto report = [&] { g_busy_slots += busy - reported; reported = busy; };  // /health sums the devices
   auto fail = [](Job* j) { j->done.set_value({false, std::string()}); };
   auto run_alone = [&](Job* j) {
-    const float* ptr = j->pcm.data();
-    int len = (int)j->pcm.size();
     char* text = nullptr;
-    const bool ok = AX_WHISPER_RunPCMBatch(model, &ptr, &len, 1, &text) == 0 && text;
+    const bool ok = run_batch_texts(model, &j, 1, &text) == 0 && text;
     j->done.set_value({ok, text ? std::string(text) : std::string()});
     free(text);
     ++g_served;
@@ -167,11 +188,8 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
       // clips of 444 ids against ~240 ms for two live slots of the step sequence); a refused group (one bad request) is served one by one
       if (open) { AX_WHISPER_StreamClose(model); open = false; }
       const int n = (int)take.size();
-      const float* ptrs[3];
-      int lens[3];
       char* texts[3] = {nullptr, nullptr, nullptr};
-      for (int i = 0; i < n; ++i) { ptrs[i] = take[i]->pcm.data(); lens[i] = (int)take[i]->pcm.size(); }
-      bool ok = AX_WHISPER_RunPCMBatch(model, ptrs, lens, n, texts) == 0;
+      bool ok = run_batch_texts(model, take.data(), n, texts) == 0;
       for (int i = 0; i < n; ++i) ok = ok && texts[i];
       if (ok) {
         for (int i = 0; i < n; ++i) { take[i]->done.set_value({true, std::string(texts[i])}); ++g_served; }
@@ -190,19 +208,24 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
       // refused (one bad request: e.g. non-finite samples) the requests are admitted one by one so that only that one fails
       std::vector<int> sl;
       std::vector<const float*> ptrs;
-      std::vector<int> lens;
+      std::vector<int> lens, rates;
       for (int i = 0, s2 = 0; i < (int)take.size(); ++i) {
         while (owner[s2]) ++s2;
         sl.push_back(s2++);
         ptrs.push_back(take[i]->pcm.data());
         lens.push_back((int)take[i]->pcm.size());
+        rates.push_back(take[i]->rate);
       }
-      if (AX_WHISPER_StreamAdmitBatch(model, sl.data(), ptrs.data(), lens.data(), nullptr, (int)take.size()) == 0) {
+      // (a pass without a clip at another rate is the call it always was)
+      const bool all16 = std::all_of(rates.begin(), rates.end(), [](int r) { return r == 16000; });
+      if ((all16 ? AX_WHISPER_StreamAdmitBatch(model, sl.data(), ptrs.data(), lens.data(), nullptr, (int)take.size())
+                 : AX_WHISPER_StreamAdmitBatchRate(model, sl.data(), ptrs.data(), lens.data(), rates.data(), nullptr, (int)take.size())) == 0) {
         for (size_t i = 0; i < take.size(); ++i) owner[sl[i]] = take[i];
         busy += (int)take.size();
       } else {
         for (size_t i = 0; i < take.size(); ++i) {
-          if (AX_WHISPER_StreamAdmit(model, sl[i], ptrs[i], lens[i], 0) != 0) { fail(take[i]); continue; }
+          if ((rates[i] == 16000 ? AX_WHISPER_StreamAdmit(model, sl[i], ptrs[i], lens[i], 0)
+                                 : AX_WHISPER_StreamAdmitBatchRate(model, &sl[i], &ptrs[i], &lens[i], &rates[i], nullptr, 1)) != 0) { fail(take[i]); continue; }
           owner[sl[i]] = take[i];
           ++busy;
         }
@@ -290,7 +313,9 @@ static void serve(int fd) {
     const char* c = "HTTP/1.1 100 Continue\r\n\r\n";
     (void)!send(fd, c, strlen(c), MSG_NOSIGNAL);
   }
-  if (clen > g_max_body) {  // 30 s of audio is 1.92 MB; nothing longer than the cap is read at all
+  // (the cap counts seconds of audio: it scales with X-Sample-Rate, so that 30 s at 48 kHz, 5.76 MB, fit as 30 s at 16 kHz do)
+  const size_t max_body = hh.rate_ok && hh.sample_rate > 16000 ? (size_t)((double)g_max_body * hh.sample_rate / 16000.0) : g_max_body;
+  if (clen > max_body) {  // 30 s of audio is 1.92 MB; nothing longer than the cap is read at all
     send_response(fd, 413, R"({"error": "Request body too large"})");
     shutdown(fd, SHUT_RDWR);
     close(fd);
@@ -324,9 +349,13 @@ static void serve(int fd) {
     send_response(fd, 404, R"({"error": "Not found"})");
   } else if (const char* bad = axw::asr_request_error(hh, body.size())) {
     send_response(fd, 400, bad);
+  } else if (hh.sample_rate != 16000 && AX_WHISPER_ResampledLength((long long)(body.size() / sizeof(float)), hh.sample_rate) < 0) {
+    // a rate or a length the resampler refuses: its error text, before the clip is queued
+    send_response(fd, 400, "{\"error\": \"" + json_escape(AX_WHISPER_LastError(nullptr)) + "\"}");
   } else {
     {
       Job job;
+      job.rate = hh.sample_rate;
       job.pcm.resize(body.size() / sizeof(float));
       memcpy(job.pcm.data(), body.data(), body.size());                                      // hpp:103-113
       auto fut = job.done.get_future();
