@@ -351,6 +351,12 @@ AX_WHISPER_API int AX_WHISPER_PrefillPrompts(AX_WHISPER_HANDLE handle, int batch
                                              const int* n_prompt, float* no_speech_logprob, float* sot_logits);
 /** Rows 0 .. n_rows-1 of the slot's self-attention cache, de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][n_text_state]. */
 AX_WHISPER_API int AX_WHISPER_GetSelfKV(AX_WHISPER_HANDLE handle, int slot, int n_rows, float* k_out, float* v_out);
+/** The self-attention cache of a later clip of the last two- or three-clip persistent launch (DecodeGreedy of 2 or 3 clips; clip 0's
+ *  cache never leaves the chip). clip: 1 or 2, the clip's position in that launch. k_out, v_out: fp32
+ *  [n_text_layer][512][n_text_state], all 8 blocks x 64 keys of every (layer, head) de-blocked, the 16-bit values widened exactly;
+ *  rows no step of the launch wrote are zero. -1 with an error text when the handle holds no such cache
+ *  (GetConfigInt "persistent_max_clips" <= clip). */
+AX_WHISPER_API int AX_WHISPER_GetPersistentSelfKV(AX_WHISPER_HANDLE handle, int clip, float* k_out, float* v_out);
 /** DecodeForcedTimestampScores under prompts (every clip needs one): forced [batch][n_forced] follow each clip's own context, row i
  *  of logits / chosen / logprob [batch][n_forced+1] is the step that decides id i. There is no row of decode offset 0. */
 AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampPrompted(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids,

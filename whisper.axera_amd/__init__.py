@@ -103,6 +103,7 @@ SYMBOLS = {
     "AX_WHISPER_RunPCMBatchTimestampPrompted": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.c_int, C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_PrefillPrompts": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), fp, fp]),
     "AX_WHISPER_GetSelfKV": (C.c_int, [C.c_void_p, C.c_int, C.c_int, fp, fp]),
+    "AX_WHISPER_GetPersistentSelfKV": (C.c_int, [C.c_void_p, C.c_int, fp, fp]),
     "AX_WHISPER_DecodeForcedTimestampPrompted": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), ip, C.c_int, fp, ip, fp, fp]),
     "AX_WHISPER_CarryPrompt": (C.c_int, [ip, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, ip,
                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -668,6 +669,14 @@ class Whisper:
         k = np.empty((self.n_text_layer, n_rows, self.n_text_state), dtype=np.float32)
         v = np.empty_like(k)
         self._check(self.L.AX_WHISPER_GetSelfKV(self.h, slot, n_rows, k.ctypes.data_as(fp), v.ctypes.data_as(fp)), "GetSelfKV")
+        return k, v
+
+    def get_persistent_self_kv(self, clip: int):
+        """The self-attention cache of clip `clip` (1 or 2: its position in the last two- or three-clip persistent launch) ->
+        (k, v), each fp32 [n_text_layer][512][d]: every block of every (layer, head), rows no step wrote included (zeros)."""
+        k = np.empty((self.n_text_layer, 512, self.n_text_state), dtype=np.float32)
+        v = np.empty_like(k)
+        self._check(self.L.AX_WHISPER_GetPersistentSelfKV(self.h, clip, k.ctypes.data_as(fp), v.ctypes.data_as(fp)), "GetPersistentSelfKV")
         return k, v
 
     def decode_forced_timestamp_prompted(self, prompts, forced, want_logits: bool = True):

@@ -867,6 +867,11 @@ AX_WHISPER_API int AX_WHISPER_GetSelfKV(AX_WHISPER_HANDLE handle, int slot, int 
   return guarded(handle, [&](Engine& e) { e.get_self_kv(slot, n_rows, k_out, v_out); });
 }
 
+AX_WHISPER_API int AX_WHISPER_GetPersistentSelfKV(AX_WHISPER_HANDLE handle, int clip, float* k_out, float* v_out) {
+  if (!handle || !k_out || !v_out) return -1;
+  return guarded(handle, [&](Engine& e) { e.get_persistent_self_kv(clip, k_out, v_out); });
+}
+
 AX_WHISPER_API int AX_WHISPER_DecodeForcedTimestampPrompted(AX_WHISPER_HANDLE handle, int batch, const int32_t* prompt_ids,
                                                             int prompt_stride, const int* n_prompt, const int32_t* forced, int n_forced,
                                                             float* logits, int32_t* chosen, float* logprob, float* no_speech_logprob) {

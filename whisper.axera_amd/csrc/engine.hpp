@@ -153,6 +153,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
                      const ForcedScores* scores, const SampleSpec* sample) override;
   void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) override;
+  void get_persistent_self_kv(int clip, float* k_out, float* v_out) override;
   void prefill_stage(int batch, const ClipContexts& ctx, float* no_speech_logprob, float* sot_logits) override;
   void detect_language(const float* const* pcm, const int* n_samples, int batch, const LangResult& out) override;
   void detect_language_stage(int batch, const LangResult& out) override;

@@ -59,6 +59,36 @@ int Engine::scan_stored16(int batch, int n_max, char (*names)[32], long long* no
   return n;
 }
 
+// ------------------------------------------------------------------------------ the later clips' caches of a multi-clip launch
+// back to [n_text_layer][512][d] fp32 from the blocked K / transposed V of clip `clip` (1, 2) of the last two- or three-clip
+// persistent launch (decode_persistent2.hip: [layer * n_head + head][8 blocks][4096] per clip); GetSelfKV's twin. Every block is
+// returned, so a test sees the rows no step wrote, too.
+void Engine::get_persistent_self_kv(int clip, float* k_out, float* v_out) {
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  if (clip < 1 || clip > 2) throw std::runtime_error("get_persistent_self_kv: clip is 1 or 2 (clip 0's cache is on-chip)");
+  if (persist_max_clips_ <= clip || !d_self_k1_ || !d_self_v1_)
+    throw std::runtime_error("get_persistent_self_kv: this handle runs " + std::to_string(persist_max_clips_) + " clip(s) per persistent launch, there is no cache of clip " +
+                             std::to_string(clip));
+  const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer;
+  constexpr int kBlocks = 8, kRows = kBlocks * layout::kKvBlockKeys;
+  const size_t unit = (size_t)kBlocks * layout::kKvBlockElems, per = (size_t)L * H * unit;
+  if (per * 2 != self1_bytes_) throw std::runtime_error("get_persistent_self_kv: cache size mismatch");
+  std::vector<uint16_t> hk(per), hv(per);
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  HIP_CHECK(hipMemcpy(hk.data(), d_self_k1_ + (size_t)(clip - 1) * per, per * 2, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(hv.data(), d_self_v1_ + (size_t)(clip - 1) * per, per * 2, hipMemcpyDeviceToHost));
+  for (int l = 0; l < L; ++l)
+    for (int h = 0; h < H; ++h) {
+      const size_t u = ((size_t)l * H + h) * unit;
+      for (int t = 0; t < kRows; ++t)
+        for (int c = 0; c < layout::kKvDim; ++c) {
+          k_out[((size_t)l * kRows + t) * d + h * 64 + c] = h16_bits_to_float(hk[u + layout::k_index(t, c)]);
+          v_out[((size_t)l * kRows + t) * d + h * 64 + c] = h16_bits_to_float(hv[u + layout::vt_index(t, c)]);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ bench
 float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   require_no_stream("bench");

@@ -104,6 +104,9 @@ class IEngine {
   virtual void get_cross_kv(int slot, float* k_out, float* v_out) = 0;
   // the slot's self-attention cache rows [0, n_rows), de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][d]
   virtual void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) = 0;
+  // the self-attention cache of clip `clip` (1 or 2: its position in the last multi-clip persistent launch), all 8 blocks x 64 keys
+  // of every (layer, head), de-blocked: k_out, v_out fp32 [n_text_layer][512][d]. Throws where the handle holds no such cache.
+  virtual void get_persistent_self_kv(int clip, float* k_out, float* v_out) = 0;
   // after encode_mel: the decode state of slots [0, batch) as a greedy loop under `ctx` finds it before its first step (reset, then the
   // clips' contexts cached and their task id about to be fed); no_speech_logprob (or null): [batch], 0 for slots without a context
   // sot_logits (or null): [batch][n_vocab], the raw row the no-speech value of a slot behind a context was taken from
