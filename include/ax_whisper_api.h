@@ -566,6 +566,19 @@ AX_WHISPER_API int AX_WHISPER_RunPCMBatchWordTimestamps(AX_WHISPER_HANDLE handle
 AX_WHISPER_API int AX_WHISPER_AlignTokens(AX_WHISPER_HANDLE handle, int batch, const int32_t* ids, int stride, const int* n_ids,
                                           const int* num_frames, const int* lang, const int* task, int* jump, float* token_logprob,
                                           float* matrix, int m_rows, int m_ld);
+/** The token probabilities alone on host data (csrc/vocab_logprob.hip; DESIGN.md "Fused vocabulary log-probabilities"). x fp32
+ *  [n_rows][n_text_state]: rows of the decoder's final residual stream (before the final LayerNorm); ids [n_rows], each in [0, eot).
+ *  out[r] = logit[r][ids[r]] - logsumexp over columns [0, eot) of logit[r][.], logit = LayerNorm(x) . tied embedding^T.
+ *  route 0 ("rows"): the logits launch four rows at a time, 64 logits rows written and one number read out of each, what AlignTokens
+ *  and every one-window call use. route 1 ("fused"): LayerNorm into the 16-bit type, one MFMA launch over row tiles x vocabulary splits
+ *  that keeps an online (max, sum) per row and never writes a logit, one merge launch; bit-identical from run to run; what the
+ *  long-form word calls use. AX_WHISPER_WORD_LOGPROB=rows|fused overrides the route of every alignment (not of this call; a mistyped
+ *  value fails the first alignment call); GetConfigInt "word_logprob" = 0 no override, 1 rows, 2 fused. */
+AX_WHISPER_API int AX_WHISPER_VocabLogProbRows(AX_WHISPER_HANDLE handle, const float* x, int n_rows, const int32_t* ids, float* out, int route);
+/** Host only: the fused route's tiling of n_rows rows of d_model over eot columns: plan3[0] rows per row tile, [1] vocabulary splits,
+ *  [2] columns per split (split s covers columns [s * plan3[2], min((s + 1) * plan3[2], eot))). -1: a shape the kernel does not take
+ *  (d_model a multiple of 128 up to 2048). */
+AX_WHISPER_API int AX_WHISPER_VocabLogProbPlan(int d_model, int n_rows, int eot, int* plan3);
 /** The alignment heads of a handle: n (layer, head) pairs; n == 0 restores what the handle was constructed with. That is the optional
  *  key "alignment_heads": [[layer, head], ...] of {type}_config.json (tools/convert_weights.py --hf copies it from the checkpoint's
  *  generation_config.json), else every head of the upper half of the layers. GetConfigInt "n_alignment_heads" counts the list in use. */
@@ -602,6 +615,81 @@ AX_WHISPER_API int AX_WHISPER_WordsFromAlignment(const char* tokens_path, const 
                                                  int* word_text_end, double* word_start, double* word_end, float* word_prob, int* n_words,
                                                  char** text, int* n_bytes);
 
+/** Host only: AX_WHISPER_WordsFromAlignment for a window that starts time_offset seconds into its file (long-form: seek / 100).
+ *  Word times are round2(time_offset + jump / 50); seg_start / seg_end, last_speech_timestamp and the rule's max(0, .) clamps are all
+ *  in FILE time, as openai-whisper's add_word_timestamps sees them inside transcribe(). time_offset 0: AX_WHISPER_WordsFromAlignment. */
+AX_WHISPER_API int AX_WHISPER_WordsFromAlignmentAt(const char* tokens_path, const int32_t* ids, int n, int eot, const char* language,
+                                                   const int* seg_tokens, double* seg_start, double* seg_end, int n_seg, const int* jump,
+                                                   const float* token_logprob, double last_speech_timestamp, double time_offset, int n_max,
+                                                   int* word_segment, int* word_text_end, double* word_start, double* word_end,
+                                                   float* word_prob, int* n_words, char** text, int* n_bytes);
+
+/* ---- Word timestamps in long-form (DESIGN.md "Word-level timestamps", "Words in the seek loop"): openai-whisper's
+ *  transcribe(word_timestamps=True). After the decisions of a pass (fallback kept / not kept, silent skip, AX_WHISPER_SplitWindow)
+ *  every kept, non-skipped window is aligned, one AlignTokens call per pass over the pass's slots, under the file's language and
+ *  task, with the fused token probabilities (AX_WHISPER_VocabLogProbRows, route 1; AX_WHISPER_WORD_LOGPROB overrides). The word rule
+ *  runs in file time with the file's last_speech_timestamp (0.0 at first, then the end of the last word of the last window that had
+ *  one), and the seek moves by AX_WHISPER_LongWordAdvance. The prompt carry is unchanged: it takes ids, not times.
+ *  Known limit: the alignment's GEMMs may add in another order when a pass holds more rows. Where a window's alignment matrix has
+ *  near-ties, its word times can differ by a few frames between a file decoded alone and the same file beside others, and since the
+ *  last word's end moves the seek, the file's later windows can then differ too ("Known limit").
+ *  Not covered: hallucination_silence_threshold; words under beam search, in the Stream* calls and whisper_srv; the one-window calls
+ *  (RunPCMBatchWordTimestamps, AlignTokens) keep the rows route of the token probabilities. */
+/** Host only: the seek rule. ids [n]: one window's ids (eot excluded); seek, window_frames: the window's start and length in frames
+ *  of 10 ms; split_advance: AX_WHISPER_SplitWindow's advance; has_word / last_word_end: whether the window yielded a word and the
+ *  end of its last one in FILE time. Unless the ids end in a single timestamp (last id >= timestamp_begin, the one before below):
+ *  if last_word_end > seek / 100, the new seek is round(last_word_end * 100) (nearest frame, ties to even). An advance <= 0 or
+ *  > window_frames keeps split_advance (progress guard). *advance: the frames to move by; *by_word_end: 1 iff the word end was taken. */
+AX_WHISPER_API int AX_WHISPER_LongWordAdvance(const int32_t* ids, int n, int timestamp_begin, int seek, int window_frames, int split_advance,
+                                              int has_word, double last_word_end, int* advance, int* by_word_end);
+/** The options of the long-form calls below: those of AX_WHISPER_RunPCMLongWindowsLang, under the same names and with the same
+ *  meaning (NaN thresholds, n_temperatures 0, NULL arrays switch each part off; arrays hold one entry per file), plus word_timestamps
+ *  (0: the loop as RunPCMLongWindowsLang runs it). */
+typedef struct AX_WHISPER_LONG_OPTIONS {
+  float no_speech_threshold, logprob_threshold, compression_ratio_threshold;
+  const float* temperatures; int n_temperatures; uint64_t seed; const int* file_ids;
+  const int32_t* initial_prompt_ids; int prompt_stride; const int* n_initial; int condition_on_previous_text;
+  const int* lang; const int* task;
+  int word_timestamps;
+} AX_WHISPER_LONG_OPTIONS;
+/** The word part of the window log, row k = window k of win_info. win_words [win_cap][4]: text ids aligned, segments, words, 1 iff
+ *  the advance is the word-end seek. text_ids / token_logprob [win_cap][n_text_ctx] and jump [win_cap][n_text_ctx + 1]: the aligned
+ *  ids (those below eot of SplitWindow's segments), the alignment's raw log-probabilities and jumps (ids + 1 entries). Packed in
+ *  window order: seg_tokens / seg_start / seg_end [seg_cap] (ids of the segment among text_ids; the times the word rule left, FILE
+ *  time), word_segment (index among the window's segments) / word_text_end / word_start / word_end / word_prob [word_cap]; word w's
+ *  bytes are text[word_text_end[w-1] .. word_text_end[w]) (0 for the first word of the call). text is malloc'ed (the caller frees
+ *  it, also after a failure). Windows that were skipped, not kept, or decoded with word_timestamps 0 have a zero row. */
+typedef struct AX_WHISPER_LONG_WORD_LOG {
+  int seg_cap, word_cap;
+  int* win_words; int32_t* text_ids; int* jump; float* token_logprob;
+  int* seg_tokens; double* seg_start; double* seg_end;
+  int* word_segment; int* word_text_end; double* word_start; double* word_end; float* word_prob;
+  char* text;
+} AX_WHISPER_LONG_WORD_LOG;
+/** RunPCMLongWindowsLang under `opts` with the full log: win_info, ids, win_score, win_prompt (may be NULL), n_windows, lang_out (may be
+ *  NULL) as there; words (may be NULL when opts->word_timestamps is 0): the word log. -1 with "N windows were decoded" / "N segments" /
+ *  "N words" in LastError when a capacity is too small; nothing but text is then written. Sharded over the handle's devices. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsWords(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                     int max_new, int max_passes, const AX_WHISPER_LONG_OPTIONS* opts, int win_cap, int* win_info,
+                                                     int32_t* ids, float* win_score, int* win_prompt, int* n_windows, int* lang_out,
+                                                     AX_WHISPER_LONG_WORD_LOG* words);
+/** One file's segments and words. Every array is malloc'ed by the call and released by AX_WHISPER_FreeLongWords. Segment k: seg_start /
+ *  seg_end (seconds in the file, after the word rule), its text (the transcript of its ids, under the file's language) the bytes
+ *  seg_text[seg_text_end[k-1] .. seg_text_end[k]); word w: word_segment (index among the file's segments), word_start, word_end,
+ *  word_prob, its bytes in word_text likewise. */
+typedef struct AX_WHISPER_LONG_WORDS {
+  int n_segments, n_words;
+  double* seg_start; double* seg_end; int* seg_text_end; char* seg_text;
+  int* word_segment; double* word_start; double* word_end; float* word_prob; int* word_text_end; char* word_text;
+} AX_WHISPER_LONG_WORDS;
+/** Long-form transcription of one file (16 kHz mono PCM, or a wav file) with word timestamps, under `opts` (its arrays hold one entry;
+ *  word_timestamps is taken as 1); lang_out (may be NULL): the file's language index. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWords(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const AX_WHISPER_LONG_OPTIONS* opts,
+                                              int* lang_out, AX_WHISPER_LONG_WORDS* out);
+AX_WHISPER_API int AX_WHISPER_RunFileLongWords(AX_WHISPER_HANDLE handle, const char* wav_file, const AX_WHISPER_LONG_OPTIONS* opts, int* lang_out,
+                                               AX_WHISPER_LONG_WORDS* out);
+AX_WHISPER_API void AX_WHISPER_FreeLongWords(AX_WHISPER_LONG_WORDS* out);
+
 /** Stage timings of the last Run* / DecodeGreedy* call, ms (hipEvent): [0] front-end, [1] encoder,
  *  [2] decode loop, [3] whole call (wall), [4] decode steps executed. */
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
@@ -614,7 +702,8 @@ AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
  *  had completed), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
  *  files of `arg` seconds + one window kernel), "prefill" (reset + PrefillPrompts of `batch` slots with prompts of arg - 3 ids each,
  *  i.e. context length L = arg, by the handle's route), "word_align" / "word_align_host" (AlignTokens of `batch` slots with `arg` text ids
- *  each against all frames, by the kernels / by the host route; host wall time), "resample" (the resample kernel over `batch` clips
+ *  each against all frames, by the kernels / by the host route; host wall time), "word_logprob" / "word_logprob_rows" (the token
+ *  probabilities of batch * arg residual rows alone, by the fused kernel / four rows per logits launch; host wall time), "resample" (the resample kernel over `batch` clips
  *  of 30 s at `arg` Hz into the staging rows), or a kernel name listed in DESIGN.md. */
 AX_WHISPER_API int AX_WHISPER_Bench(AX_WHISPER_HANDLE handle, const char* what, int batch, int arg,
                                     int iters, float* ms_total);

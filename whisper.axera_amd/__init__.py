@@ -29,6 +29,29 @@ ip = C.POINTER(C.c_int32)
 _dblp = C.POINTER(C.c_double)
 _lib = None
 
+class LongOptions(C.Structure):
+    """AX_WHISPER_LONG_OPTIONS"""
+    _fields_ = [("no_speech_threshold", C.c_float), ("logprob_threshold", C.c_float), ("compression_ratio_threshold", C.c_float),
+                ("temperatures", fp), ("n_temperatures", C.c_int), ("seed", C.c_uint64), ("file_ids", C.POINTER(C.c_int)),
+                ("initial_prompt_ids", ip), ("prompt_stride", C.c_int), ("n_initial", C.POINTER(C.c_int)), ("condition_on_previous_text", C.c_int),
+                ("lang", C.POINTER(C.c_int)), ("task", C.POINTER(C.c_int)), ("word_timestamps", C.c_int)]
+
+
+class LongWordLog(C.Structure):
+    """AX_WHISPER_LONG_WORD_LOG"""
+    _fields_ = [("seg_cap", C.c_int), ("word_cap", C.c_int), ("win_words", C.POINTER(C.c_int)), ("text_ids", ip), ("jump", C.POINTER(C.c_int)),
+                ("token_logprob", fp), ("seg_tokens", C.POINTER(C.c_int)), ("seg_start", _dblp), ("seg_end", _dblp),
+                ("word_segment", C.POINTER(C.c_int)), ("word_text_end", C.POINTER(C.c_int)), ("word_start", _dblp), ("word_end", _dblp),
+                ("word_prob", fp), ("text", C.c_void_p)]
+
+
+class LongWords(C.Structure):
+    """AX_WHISPER_LONG_WORDS"""
+    _fields_ = [("n_segments", C.c_int), ("n_words", C.c_int), ("seg_start", _dblp), ("seg_end", _dblp), ("seg_text_end", C.POINTER(C.c_int)),
+                ("seg_text", C.c_void_p), ("word_segment", C.POINTER(C.c_int)), ("word_start", _dblp), ("word_end", _dblp), ("word_prob", fp),
+                ("word_text_end", C.POINTER(C.c_int)), ("word_text", C.c_void_p)]
+
+
 # name -> (restype, argtypes): every symbol include/ax_whisper_api.h declares
 SYMBOLS = {
     "AX_WHISPER_Init": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p]),
@@ -135,6 +158,8 @@ SYMBOLS = {
                                                        C.POINTER(C.c_int), C.POINTER(C.c_int), _dblp, _dblp, fp, C.POINTER(C.c_void_p), C.POINTER(C.c_int), fp]),
     "AX_WHISPER_AlignTokens": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int), fp, fp, C.c_int, C.c_int]),
+    "AX_WHISPER_VocabLogProbRows": (C.c_int, [C.c_void_p, fp, C.c_int, ip, fp, C.c_int]),
+    "AX_WHISPER_VocabLogProbPlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "AX_WHISPER_SetAlignmentHeads": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "AX_WHISPER_ConfigAlignmentHeads": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "AX_WHISPER_AlignQKSoftmax": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.POINTER(C.c_int), fp, C.c_int,
@@ -148,6 +173,16 @@ SYMBOLS = {
     "AX_WHISPER_WordsFromAlignment": (C.c_int, [C.c_char_p, ip, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), _dblp, _dblp, C.c_int, C.POINTER(C.c_int), fp,
                                                 C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dblp, _dblp, fp, C.POINTER(C.c_int),
                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "AX_WHISPER_WordsFromAlignmentAt": (C.c_int, [C.c_char_p, ip, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), _dblp, _dblp, C.c_int, C.POINTER(C.c_int), fp,
+                                                  C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dblp, _dblp, fp, C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "AX_WHISPER_LongWordAdvance": (C.c_int, [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongWindowsWords": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(LongOptions), C.c_int,
+                                                    C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                    C.POINTER(LongWordLog)]),
+    "AX_WHISPER_RunPCMLongWords": (C.c_int, [C.c_void_p, fp, C.c_int, C.POINTER(LongOptions), C.POINTER(C.c_int), C.POINTER(LongWords)]),
+    "AX_WHISPER_RunFileLongWords": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(LongOptions), C.POINTER(C.c_int), C.POINTER(LongWords)]),
+    "AX_WHISPER_FreeLongWords": (None, [C.POINTER(LongWords)]),
     "AX_WHISPER_ResampledLength": (C.c_longlong, [C.c_longlong, C.c_int]),
     "AX_WHISPER_ResampleFilter": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int]),
     "AX_WHISPER_ResampleBatch": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(fp), C.POINTER(C.c_int),
@@ -379,6 +414,16 @@ def config_alignment_heads(config_path: str):
     return [(int(pairs[2 * i]), int(pairs[2 * i + 1])) for i in range(n.value)]
 
 
+def vocab_logprob_plan(d_model: int, n_rows: int, eot: int):
+    """Host only (AX_WHISPER_VocabLogProbPlan): the fused log-prob kernel's tiling -> (rows per row tile, vocabulary splits,
+    columns per split)."""
+    L = load_library()
+    plan = (C.c_int * 3)()
+    if L.AX_WHISPER_VocabLogProbPlan(int(d_model), int(n_rows), int(eot), plan) != 0:
+        raise ValueError("AX_WHISPER_VocabLogProbPlan: a shape the kernel does not take")
+    return plan[0], plan[1], plan[2]
+
+
 def align_path(matrix) -> np.ndarray:
     """Host only (AX_WHISPER_AlignPath): matrix [rows][frames] -> jump [rows], the frame of the first point of every row on the
     DTW path over -matrix (fp32 accumulation, ties go left)."""
@@ -407,10 +452,25 @@ def split_words(tokens_path: str, ids, eot: int, language: str):
     return [(texts[w], a[ends[w]: ends[w + 1]].tolist()) for w in range(n.value)]
 
 
+def long_word_advance(ids, timestamp_begin: int, seek: int, window_frames: int, split_advance: int, last_word_end=None):
+    """Host only (AX_WHISPER_LongWordAdvance): the seek rule of long-form under word timestamps. ids: one window's ids (eot excluded),
+    last_word_end: the end of the window's last word in file time, None without a word -> (advance in frames, whether the word end
+    was taken)."""
+    L = load_library()
+    a = _i32(ids).reshape(-1)
+    adv, by = C.c_int(), C.c_int()
+    if L.AX_WHISPER_LongWordAdvance(a.ctypes.data_as(ip), len(a), int(timestamp_begin), int(seek), int(window_frames), int(split_advance),
+                                    0 if last_word_end is None else 1, 0.0 if last_word_end is None else float(last_word_end),
+                                    C.byref(adv), C.byref(by)) != 0:
+        raise RuntimeError("AX_WHISPER_LongWordAdvance failed")
+    return adv.value, bool(by.value)
+
+
 def words_from_alignment(tokens_path: str, ids, eot: int, language: str, seg_tokens, seg_start, seg_end, jump, token_logprob,
-                         last_speech_timestamp: float = 0.0):
+                         last_speech_timestamp: float = 0.0, time_offset=None):
     """Host only (AX_WHISPER_WordsFromAlignment): the words of one window -> ([(segment, word bytes, start, end, probability)],
-    seg_start, seg_end after the rule)."""
+    seg_start, seg_end after the rule). time_offset (seconds; None: the call as it was): AX_WHISPER_WordsFromAlignmentAt, the window
+    starts there in its file, and segment times, last_speech_timestamp and the words are in file time."""
     L = load_library()
     a, st_n = _i32(ids).reshape(-1), _i32(seg_tokens).reshape(-1)
     ss, se = np.array(seg_start, dtype=np.float64).reshape(-1), np.array(seg_end, dtype=np.float64).reshape(-1)
@@ -421,10 +481,10 @@ def words_from_alignment(tokens_path: str, ids, eot: int, language: str, seg_tok
     wseg, te = np.zeros(n_max, dtype=np.int32), np.zeros(n_max, dtype=np.int32)
     ws, we, wp = np.zeros(n_max, dtype=np.float64), np.zeros(n_max, dtype=np.float64), np.zeros(n_max, dtype=np.float32)
     n, nb, out = C.c_int(), C.c_int(), C.c_void_p()
-    rc = L.AX_WHISPER_WordsFromAlignment(os.fspath(tokens_path).encode(), a.ctypes.data_as(ip), len(a), int(eot), language.encode(), _ci(st_n),
-                                         ss.ctypes.data_as(_dblp), se.ctypes.data_as(_dblp), len(st_n), _ci(j), lp.ctypes.data_as(fp),
-                                         float(last_speech_timestamp), n_max, _ci(wseg), _ci(te), ws.ctypes.data_as(_dblp), we.ctypes.data_as(_dblp),
-                                         wp.ctypes.data_as(fp), C.byref(n), C.byref(out), C.byref(nb))
+    head = (os.fspath(tokens_path).encode(), a.ctypes.data_as(ip), len(a), int(eot), language.encode(), _ci(st_n), ss.ctypes.data_as(_dblp),
+            se.ctypes.data_as(_dblp), len(st_n), _ci(j), lp.ctypes.data_as(fp), float(last_speech_timestamp))
+    tail = (n_max, _ci(wseg), _ci(te), ws.ctypes.data_as(_dblp), we.ctypes.data_as(_dblp), wp.ctypes.data_as(fp), C.byref(n), C.byref(out), C.byref(nb))
+    rc = L.AX_WHISPER_WordsFromAlignment(*head, *tail) if time_offset is None else L.AX_WHISPER_WordsFromAlignmentAt(*head, float(time_offset), *tail)
     if rc != 0:
         raise RuntimeError("AX_WHISPER_WordsFromAlignment failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
     texts = _word_texts(L, out, nb.value, te, n.value)
@@ -1011,6 +1071,21 @@ class Whisper:
             out.append(o)
         return out
 
+    def vocab_logprob_rows(self, x, ids, route: str = "fused") -> np.ndarray:
+        """The token probabilities alone (AX_WHISPER_VocabLogProbRows): x [rows][n_text_state] final residual rows, one id below eot per
+        row -> float32 [rows], log p(id) over the ids below eot. route "fused": csrc/vocab_logprob.hip; "rows": the logits launch
+        four rows at a time."""
+        if route not in ("rows", "fused"):
+            raise ValueError("route is rows or fused")
+        x = _f32(x).reshape(-1, self.n_text_state)
+        a = _i32(ids).reshape(-1)
+        if len(a) != x.shape[0]:
+            raise ValueError("one id per row")
+        out = np.zeros(len(a), dtype=np.float32)
+        self._check(self.L.AX_WHISPER_VocabLogProbRows(self.h, x.ctypes.data_as(fp), len(a), a.ctypes.data_as(ip), out.ctypes.data_as(fp),
+                                                       1 if route == "fused" else 0), "VocabLogProbRows")
+        return out
+
     def align_qk_softmax(self, q, k, row0, length, n_keys, slot, heads, rows_pad: int, f_pad: int, fill: float = np.nan):
         """align_qk_softmax_kernel alone (AX_WHISPER_AlignQKSoftmax): q [rows][64 n_head], k [n_slots][n_head][keys_pad][64] ->
         P [n_clips][len(heads)][rows_pad][f_pad], prefilled with `fill`."""
@@ -1108,7 +1183,7 @@ class Whisper:
 
     def run_long_windows(self, files, max_new: int = 0, max_passes: int = 0, no_speech_threshold=None, logprob_threshold=None, scores: bool = False,
                          compression_ratio_threshold=None, temperatures=None, seed: int = 0, file_ids=None, initial_prompt_ids=None,
-                         condition_on_previous_text: bool = False, languages=None, tasks=None):
+                         condition_on_previous_text: bool = False, languages=None, tasks=None, word_timestamps=None):
         """The seek loop over `files` (PCM arrays), one window of every unfinished file per pass. Per file, the list of its
         decoded windows (seek, window_frames, advance, ids, pass, slot) in order. max_new: id budget per window;
         max_passes > 0 stops after that many passes (the slots then hold the last pass's cross K/V).
@@ -1123,7 +1198,13 @@ class Whisper:
         the prompt its window was conditioned on.
         With languages (per file a code, None or "auto") or tasks ("transcribe" / "translate") the call is
         AX_WHISPER_RunPCMLongWindowsLang, and the result is the pair (that list, the language code of every file); the tuples are
-        those of the prompted call."""
+        those of the prompted call.
+        word_timestamps (None: the calls above as they were; True / False): AX_WHISPER_RunPCMLongWindowsWords, see
+        _run_long_windows_words, whose result with False is the languages / tasks call's."""
+        if word_timestamps is not None:
+            return self._run_long_windows_words(files, max_new, max_passes, no_speech_threshold, logprob_threshold, compression_ratio_threshold,
+                                                temperatures, seed, file_ids, initial_prompt_ids, condition_on_previous_text, languages, tasks,
+                                                bool(word_timestamps))
         fallback = compression_ratio_threshold is not None or temperatures is not None
         per_lang = languages is not None or tasks is not None
         prompted = bool(condition_on_previous_text) or initial_prompt_ids is not None or per_lang
@@ -1203,6 +1284,115 @@ class Whisper:
         if per_lang:
             return out, [self.language_code(lout[f]) for f in range(n)]
         return out
+
+    def _long_options(self, n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed, file_ids, initial_prompt_ids,
+                      condition_on_previous_text, languages, tasks, word_timestamps):
+        """-> (AX_WHISPER_LONG_OPTIONS, what its pointers point into, whether the call has fallback): the arguments of run_long_windows as
+        its languages / tasks form hands them to the C ABI"""
+        fallback = compression_ratio_threshold is not None or temperatures is not None
+        nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
+        crt, temps = float("nan"), _f32([])
+        if fallback:
+            lpt = float("nan") if logprob_threshold is None else float(logprob_threshold)
+            crt = float("nan") if compression_ratio_threshold is None else float(compression_ratio_threshold)
+            temps = _f32(DEFAULT_TEMPERATURES if temperatures is None else temperatures)
+        init = [[] if q is None else list(q) for q in (initial_prompt_ids if initial_prompt_ids is not None else [None] * n)]
+        if len(init) != n:
+            raise ValueError("one initial prompt (or None) per file")
+        pid, stride, npr = self._prompt_args(init)
+        lang, task = self._lang_args(n, languages, tasks)
+        fid = (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None
+        o = LongOptions(nst, lpt, crt, temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed), fid, pid, stride, npr,
+                        int(bool(condition_on_previous_text)), lang, task, int(bool(word_timestamps)))
+        return o, (temps, pid, npr, lang, task, fid), fallback
+
+    def _run_long_windows_words(self, files, max_new, max_passes, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures,
+                                seed, file_ids, initial_prompt_ids, condition_on_previous_text, languages, tasks, word_timestamps):
+        """AX_WHISPER_RunPCMLongWindowsWords -> (per file its windows, the language code of every file). A window is the tuple of the
+        languages / tasks call of run_long_windows, and with word_timestamps one more entry, a dict: text_ids, seg_tokens, jump,
+        token_logprob (what was aligned and what the alignment gave), seg_start, seg_end (file time, after the word rule), words
+        [(segment, word bytes, start, end, probability)] in file time, by_word_end (the advance is the word-end seek)."""
+        files = [_f32(f) for f in files]
+        n = len(files)
+        o, keep, fallback = self._long_options(n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed, file_ids,
+                                               initial_prompt_ids, condition_on_previous_text, languages, tasks, word_timestamps)
+        sw = 7 if fallback else 3
+        ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
+        lens = (C.c_int * n)(*[len(f) for f in files])
+        Tc = self.n_text_ctx
+        cap = sum(len(f) // 160 // 3000 + 2 for f in files) * 2
+        pi = C.POINTER(C.c_int)
+        while True:
+            info, ids, sc = np.zeros((cap, 7), dtype=np.int32), np.zeros((cap, Tc), dtype=np.int32), np.zeros((cap, sw), dtype=np.float32)
+            wp, nw, lout = np.zeros(cap, dtype=np.int32), C.c_int(), (C.c_int * n)()
+            m = cap * Tc  # (a window has fewer segments and words than ids)
+            ww, tid, jmp = np.zeros((cap, 4), dtype=np.int32), np.zeros((cap, Tc), dtype=np.int32), np.zeros((cap, Tc + 1), dtype=np.int32)
+            tlp = np.zeros((cap, Tc), dtype=np.float32)
+            sgt, wsg, wte = (np.zeros(m, dtype=np.int32) for _ in range(3))
+            sgs, sge, wst, wen = (np.zeros(m, dtype=np.float64) for _ in range(4))
+            wpr = np.zeros(m, dtype=np.float32)
+            log = LongWordLog(m, m, ww.ctypes.data_as(pi), tid.ctypes.data_as(ip), jmp.ctypes.data_as(pi), tlp.ctypes.data_as(fp), sgt.ctypes.data_as(pi),
+                              sgs.ctypes.data_as(_dblp), sge.ctypes.data_as(_dblp), wsg.ctypes.data_as(pi), wte.ctypes.data_as(pi),
+                              wst.ctypes.data_as(_dblp), wen.ctypes.data_as(_dblp), wpr.ctypes.data_as(fp), None)
+            rc = self.L.AX_WHISPER_RunPCMLongWindowsWords(self.h, ptrs, lens, n, int(max_new), int(max_passes), C.byref(o), cap, info.ctypes.data_as(pi),
+                                                          ids.ctypes.data_as(ip), sc.ctypes.data_as(fp), wp.ctypes.data_as(pi), C.byref(nw), lout,
+                                                          C.byref(log))
+            text = C.string_at(log.text, int(wte[max(int(ww[: nw.value, 2].sum()) - 1, 0)])) if log.text and rc == 0 else b""
+            if log.text:
+                self.L._free(log.text)
+            if rc != 0:
+                msg = (self.L.AX_WHISPER_LastError(self.h) or b"").decode()
+                need = re.search(r"(\d+) windows were decoded, win_cap is", msg)
+                if need:
+                    cap = int(need.group(1))
+                    continue
+                raise RuntimeError("RunPCMLongWindowsWords failed: " + msg)
+            break
+        out = [[] for _ in range(n)]
+        sg = wd = 0
+        for k in range(nw.value):
+            f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
+            w = (seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot, float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2]))
+            if fallback:
+                w = w + (int(sc[k, 3]), float(sc[k, 4]), float(sc[k, 5]), bool(sc[k, 6]))
+            w = w + (int(wp[k]),)
+            if word_timestamps:
+                nt, ns, nwd, by = (int(x) for x in ww[k])
+                words = []
+                for j in range(wd, wd + nwd):
+                    words.append((int(wsg[j]), text[int(wte[j - 1]) if j else 0: int(wte[j])], float(wst[j]), float(wen[j]), np.float32(wpr[j])))
+                w = w + (dict(text_ids=tid[k, :nt].tolist(), seg_tokens=sgt[sg: sg + ns].tolist(), jump=jmp[k, : nt + 1].copy() if nt else jmp[k, :0].copy(),
+                              token_logprob=tlp[k, :nt].copy(), seg_start=sgs[sg: sg + ns].tolist(), seg_end=sge[sg: sg + ns].tolist(), words=words,
+                              by_word_end=bool(by)),)
+                sg, wd = sg + ns, wd + nwd
+            out[f].append(w)
+        return out, [self.language_code(lout[f]) for f in range(n)]
+
+    def run_long_words(self, audio, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None, temperatures=None, seed: int = 0,
+                       initial_prompt_ids=None, condition_on_previous_text: bool = False, language=None, task=None):
+        """PCM (16 kHz mono f32) or a wav path of any length -> [(start_s, end_s, text, [(word, start_s, end_s, probability)])], one entry
+        per segment, times in the file (AX_WHISPER_RunPCMLongWords / RunFileLongWords): long-form transcription with word timestamps,
+        under the thresholds, the temperature fallback, the prompt conditioning and the language / task of run_long_windows."""
+        o, keep, _ = self._long_options(1, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed, None,
+                                        None if initial_prompt_ids is None else [initial_prompt_ids], condition_on_previous_text,
+                                        None if language is None else [language], None if task is None else [task], True)
+        r = LongWords()
+        if isinstance(audio, (str, os.PathLike)):
+            self._check(self.L.AX_WHISPER_RunFileLongWords(self.h, os.fspath(audio).encode(), C.byref(o), None, C.byref(r)), "RunFileLongWords")
+        else:
+            a = _f32(audio)
+            self._check(self.L.AX_WHISPER_RunPCMLongWords(self.h, a.ctypes.data_as(fp), len(a), C.byref(o), None, C.byref(r)), "RunPCMLongWords")
+        try:
+            st = C.string_at(r.seg_text, r.seg_text_end[r.n_segments - 1]) if r.n_segments else b""
+            wt = C.string_at(r.word_text, r.word_text_end[r.n_words - 1]) if r.n_words else b""
+            out = [[r.seg_start[k], r.seg_end[k], st[(r.seg_text_end[k - 1] if k else 0): r.seg_text_end[k]].decode("utf-8", errors="replace"), []]
+                   for k in range(r.n_segments)]
+            for w in range(r.n_words):
+                word = wt[(r.word_text_end[w - 1] if w else 0): r.word_text_end[w]].decode("utf-8", errors="replace")
+                out[r.word_segment[w]][3].append((word, r.word_start[w], r.word_end[w], float(r.word_prob[w])))
+            return [tuple(s) for s in out]
+        finally:
+            self.L.AX_WHISPER_FreeLongWords(C.byref(r))
 
     def transcript_lang(self, ids, language) -> str:
         """AX_WHISPER_TranscriptLang: the text of ids decoded under `language` (a code); the zh pass follows it, not the handle's."""

@@ -28,6 +28,7 @@
 #include "multi_device.hpp"
 #include "resample.hpp"
 #include "words.hpp"
+#include "vocab_logprob_plan.hpp"
 
 using Engine = axw::IEngine;
 
@@ -650,7 +651,7 @@ AX_WHISPER_API int AX_WHISPER_ComputeMelWindow(AX_WHISPER_HANDLE handle, const f
 // the seek loop of RunPCMLongWindows[Scored] (`who`) and its log written out; opts / win_score: the scored call's, or nullptr
 static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* const* pcm, const int* num_samples, int n_files, int max_new,
                         int max_passes, const axw::LongScoreOptions* opts, int win_cap, int* win_info, int32_t* ids, float* win_score,
-                        int* n_windows, int* win_prompt = nullptr) {
+                        int* n_windows, int* win_prompt = nullptr, AX_WHISPER_LONG_WORD_LOG* words = nullptr) {
   const bool fallback = opts && !opts->temperatures.empty();  // win_score rows then have 7 entries
   if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids || (opts && !win_score))))
     return -1;
@@ -664,6 +665,35 @@ static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* 
     if ((long)log.size() > win_cap)
       throw std::runtime_error(std::string(who) + ": " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
     const int Tc = g.primary().config().n_text_ctx;
+    if (words) {  // the word log (word-timestamp calls), under the same rule
+      size_t n_seg = 0, n_word = 0;
+      for (const axw::LongWindow& w : log) { n_seg += w.seg_tokens.size(); n_word += w.words.size(); }
+      if (n_seg > (size_t)words->seg_cap) throw std::runtime_error(std::string(who) + ": " + std::to_string(n_seg) + " segments, seg_cap is " + std::to_string(words->seg_cap));
+      if (n_word > (size_t)words->word_cap) throw std::runtime_error(std::string(who) + ": " + std::to_string(n_word) + " words, word_cap is " + std::to_string(words->word_cap));
+      std::string all;
+      size_t sg = 0, wd = 0;
+      for (size_t k = 0; k < log.size(); ++k) {
+        const axw::LongWindow& w = log[k];
+        const int row[4] = {(int)w.text_ids.size(), (int)w.seg_tokens.size(), (int)w.words.size(), w.by_word_end ? 1 : 0};
+        memcpy(words->win_words + k * 4, row, sizeof row);
+        std::copy(w.text_ids.begin(), w.text_ids.end(), words->text_ids + k * (size_t)Tc);
+        std::copy(w.word_logprob.begin(), w.word_logprob.end(), words->token_logprob + k * (size_t)Tc);
+        std::copy(w.jump.begin(), w.jump.end(), words->jump + k * (size_t)(Tc + 1));
+        for (size_t s = 0; s < w.seg_tokens.size(); ++s, ++sg) {
+          words->seg_tokens[sg] = w.seg_tokens[s]; words->seg_start[sg] = w.seg_start[s]; words->seg_end[sg] = w.seg_end[s];
+        }
+        for (const axw::LongWord& x : w.words) {
+          all += x.text;
+          words->word_segment[wd] = x.segment; words->word_text_end[wd] = (int)all.size(); words->word_start[wd] = x.start; words->word_end[wd] = x.end;
+          words->word_prob[wd] = x.probability;
+          ++wd;
+        }
+      }
+      words->text = static_cast<char*>(malloc(all.size() + 1));
+      if (!words->text) throw std::runtime_error(std::string(who) + ": out of memory");
+      memcpy(words->text, all.data(), all.size());
+      words->text[all.size()] = 0;
+    }
     for (size_t k = 0; k < log.size(); ++k) {
       const axw::LongWindow& w = log[k];
       const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
@@ -1207,6 +1237,152 @@ AX_WHISPER_API int AX_WHISPER_WordsFromAlignment(const char* tokens_path, const 
   });
 }
 
+AX_WHISPER_API int AX_WHISPER_WordsFromAlignmentAt(const char* tokens_path, const int32_t* ids, int n, int eot, const char* language,
+                                                   const int* seg_tokens, double* seg_start, double* seg_end, int n_seg, const int* jump,
+                                                   const float* token_logprob, double last_speech_timestamp, double time_offset, int n_max,
+                                                   int* word_segment, int* word_text_end, double* word_start, double* word_end,
+                                                   float* word_prob, int* n_words, char** text, int* n_bytes) {
+  if (!tokens_path || (n > 0 && (!ids || !token_logprob)) || n < 0 || !language || n_seg < 0 || (n_seg > 0 && (!seg_tokens || !seg_start || !seg_end)) ||
+      !jump || n_max < 0 || (n_max > 0 && (!word_segment || !word_text_end || !word_start || !word_end || !word_prob)) || !n_words || !text || !n_bytes)
+    return -1;
+  *text = nullptr;
+  *n_words = *n_bytes = 0;
+  return guarded_host([&] {
+    const std::vector<std::string> table = axw::load_token_table(tokens_path);
+    const std::vector<axw::WordOut> words = axw::words_from_alignment(table, ids, n, eot, language, seg_tokens, seg_start, seg_end, n_seg, jump,
+                                                                      token_logprob, last_speech_timestamp, time_offset);
+    if ((int)words.size() > n_max) throw std::runtime_error("words_from_alignment: more words than n_max");
+    for (size_t w = 0; w < words.size(); ++w) {
+      word_segment[w] = words[w].segment; word_start[w] = words[w].start; word_end[w] = words[w].end; word_prob[w] = (float)words[w].probability;
+    }
+    *n_words = (int)words.size();
+    std::vector<const std::string*> texts;
+    for (const axw::WordOut& w : words) texts.push_back(&w.text);
+    return emit_word_text(texts, word_text_end, text, n_bytes);
+  });
+}
+
+// ---- word timestamps in long-form (DESIGN.md "Word-level timestamps": words in the seek loop)
+AX_WHISPER_API int AX_WHISPER_LongWordAdvance(const int32_t* ids, int n, int timestamp_begin, int seek, int window_frames, int split_advance,
+                                              int has_word, double last_word_end, int* advance, int* by_word_end) {
+  if (n < 0 || (n > 0 && !ids) || seek < 0 || window_frames < 0 || !advance) return -1;
+  bool by = false;
+  *advance = axw::long_word_advance(ids, n, timestamp_begin, seek, window_frames, split_advance, has_word != 0, last_word_end, &by);
+  if (by_word_end) *by_word_end = by ? 1 : 0;
+  return 0;
+}
+
+// AX_WHISPER_LONG_OPTIONS -> LongScoreOptions (as RunPCMLongWindowsLang reads its arguments); got: where file_lang_out points when
+// the caller passes no lang_out
+static bool long_options(const AX_WHISPER_LONG_OPTIONS* o, int n_files, int* lang_out, std::vector<int>& got, axw::LongScoreOptions& opts) {
+  if (!o || n_files < 1) return false;
+  if (!prompted_options(o->no_speech_threshold, o->logprob_threshold, o->compression_ratio_threshold, o->temperatures, o->n_temperatures, o->seed,
+                        o->initial_prompt_ids, o->prompt_stride, o->n_initial, n_files, o->condition_on_previous_text, opts))
+    return false;
+  for (int f = 0; o->file_ids && f < n_files; ++f) {
+    if (o->file_ids[f] < 0 || o->file_ids[f] >= (1 << 27)) return false;
+    opts.file_ids.push_back(o->file_ids[f]);
+  }
+  if (o->lang) opts.file_lang.assign(o->lang, o->lang + n_files);
+  if (o->task) opts.file_task.assign(o->task, o->task + n_files);
+  got.assign((size_t)n_files, -1);
+  opts.file_lang_out = lang_out ? lang_out : got.data();
+  opts.word_timestamps = o->word_timestamps != 0;
+  return true;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsWords(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                     int max_new, int max_passes, const AX_WHISPER_LONG_OPTIONS* o, int win_cap, int* win_info,
+                                                     int32_t* ids, float* win_score, int* win_prompt, int* n_windows, int* lang_out,
+                                                     AX_WHISPER_LONG_WORD_LOG* words) {
+  axw::LongScoreOptions opts{};
+  std::vector<int> got;
+  if (!long_options(o, n_files, lang_out, got, opts)) return -1;
+  if (words) words->text = nullptr;
+  if (opts.word_timestamps && (!words || words->seg_cap < 0 || words->word_cap < 0 || (win_cap > 0 && (!words->win_words || !words->text_ids || !words->jump ||
+      !words->token_logprob)) || (words->seg_cap > 0 && (!words->seg_tokens || !words->seg_start || !words->seg_end)) ||
+      (words->word_cap > 0 && (!words->word_segment || !words->word_text_end || !words->word_start || !words->word_end || !words->word_prob))))
+    return -1;
+  return long_windows(handle, "RunPCMLongWindowsWords", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids, win_score,
+                      n_windows, win_prompt, opts.word_timestamps ? words : nullptr);
+}
+
+// one file's log -> its segments and words; the arrays are malloc'ed into out
+static void long_words_result(Engine& e, const std::vector<axw::LongWindow>& log, int lang_index, AX_WHISPER_LONG_WORDS* out) {
+  const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
+  std::vector<double> ss, se, ws, we;
+  std::vector<int> s_end, w_seg, w_end;
+  std::vector<float> wp;
+  std::string s_text, w_text;
+  std::vector<axw::WindowSegment> segs;
+  for (const axw::LongWindow& w : log) {
+    if (w.skipped || !w.kept) continue;
+    axw::split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
+    const int base = (int)ss.size();
+    for (size_t k = 0; k < segs.size(); ++k) {
+      ss.push_back(k < w.seg_start.size() ? w.seg_start[k] : (double)w.seek / 100.0 + segs[k].start);
+      se.push_back(k < w.seg_end.size() ? w.seg_end[k] : (double)w.seek / 100.0 + segs[k].end);
+      s_text += e.transcript_lang(w.ids.data() + segs[k].tok_begin, segs[k].tok_end - segs[k].tok_begin, lang_index);
+      s_end.push_back((int)s_text.size());
+    }
+    for (const axw::LongWord& x : w.words) {
+      w_seg.push_back(base + x.segment); ws.push_back(x.start); we.push_back(x.end); wp.push_back(x.probability);
+      w_text += x.text;
+      w_end.push_back((int)w_text.size());
+    }
+  }
+  auto dup = [](const auto& v) {
+    using V = typename std::decay<decltype(v[0])>::type;
+    V* p = static_cast<V*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(V)));
+    if (!p) throw std::runtime_error("long words: out of memory");
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(V));
+    return p;
+  };
+  out->n_segments = (int)ss.size(); out->n_words = (int)ws.size();
+  out->seg_start = dup(ss); out->seg_end = dup(se); out->seg_text_end = dup(s_end); out->seg_text = strdup(s_text.c_str());
+  out->word_segment = dup(w_seg); out->word_start = dup(ws); out->word_end = dup(we); out->word_prob = dup(wp); out->word_text_end = dup(w_end);
+  out->word_text = static_cast<char*>(malloc(w_text.size() + 1));
+  if (!out->seg_text || !out->word_text) throw std::runtime_error("long words: out of memory");
+  memcpy(out->word_text, w_text.data(), w_text.size());
+  out->word_text[w_text.size()] = 0;
+}
+
+AX_WHISPER_API void AX_WHISPER_FreeLongWords(AX_WHISPER_LONG_WORDS* out) {
+  if (!out) return;
+  free(out->seg_start); free(out->seg_end); free(out->seg_text_end); free(out->seg_text);
+  free(out->word_segment); free(out->word_start); free(out->word_end); free(out->word_prob); free(out->word_text_end); free(out->word_text);
+  *out = AX_WHISPER_LONG_WORDS{};
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongWords(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const AX_WHISPER_LONG_OPTIONS* o,
+                                              int* lang_out, AX_WHISPER_LONG_WORDS* out) {
+  if (!handle || !pcm_data || num_samples < 1 || !out) return -1;
+  *out = AX_WHISPER_LONG_WORDS{};
+  axw::LongScoreOptions opts{};
+  std::vector<int> got;
+  int file_lang = -1;
+  if (!long_options(o, 1, &file_lang, got, opts)) return -1;
+  opts.word_timestamps = true;
+  const int rc = guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    std::vector<axw::LongWindow> log;
+    const float* files[1] = {pcm_data};
+    g.run_long_windows(files, &num_samples, 1, 0, 0, &opts, log);
+    long_words_result(g.primary(), log, file_lang, out);
+  });
+  if (rc != 0) AX_WHISPER_FreeLongWords(out);
+  if (rc == 0 && lang_out) *lang_out = file_lang;
+  return rc;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileLongWords(AX_WHISPER_HANDLE handle, const char* wav_file, const AX_WHISPER_LONG_OPTIONS* o, int* lang_out,
+                                               AX_WHISPER_LONG_WORDS* out) {
+  if (!handle || !wav_file || !out) return -1;
+  *out = AX_WHISPER_LONG_WORDS{};
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return AX_WHISPER_RunPCMLongWords(handle, wav.mono.data(), (int)wav.mono.size(), o, lang_out, out);
+}
+
 // Host only: the alignment heads a handle constructed from this config file starts with
 AX_WHISPER_API int AX_WHISPER_ConfigAlignmentHeads(const char* config_path, int n_max, int* pairs, int* n) {
   if (!config_path || !n || n_max < 0 || (n_max > 0 && !pairs)) return -1;
@@ -1242,6 +1418,16 @@ AX_WHISPER_API int AX_WHISPER_AlignTokens(AX_WHISPER_HANDLE handle, int batch, c
   return guarded(handle, [&](Engine& e) {
     e.align_tokens(Engine::AlignRequest{batch, ids, stride, n_ids, num_frames, lang, task, jump, token_logprob, matrix, m_rows, m_ld});
   });
+}
+
+AX_WHISPER_API int AX_WHISPER_VocabLogProbRows(AX_WHISPER_HANDLE handle, const float* x, int n_rows, const int32_t* ids, float* out, int route) {
+  if (!handle || !x || !ids || !out || n_rows < 1 || (route != 0 && route != 1)) return -1;
+  return guarded(handle, [&](Engine& e) { e.vocab_logprob_rows(x, n_rows, ids, out, route); });
+}
+
+AX_WHISPER_API int AX_WHISPER_VocabLogProbPlan(int d_model, int n_rows, int eot, int* plan3) {
+  if (!plan3) return -1;
+  return axw::vocab_logprob_plan(d_model, n_rows, eot, plan3, plan3 + 1, plan3 + 2) ? 0 : -1;
 }
 
 AX_WHISPER_API int AX_WHISPER_AlignQKSoftmax(AX_WHISPER_HANDLE handle, int n_clips, const int* len, const int* n_keys, const float* q, int rows,

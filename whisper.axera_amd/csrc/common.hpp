@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "decode_layout.hpp"
+#include "vocab_logprob_plan.hpp"
 
 // ------------------------------------------------------------------ the 16-bit storage / MFMA operand type
 // Every kernel file and the engine are compiled TWICE (Makefile): -DAXW_F16=0 -> bfloat16 (the default; what
@@ -670,6 +671,21 @@ struct AlignDtwParams {
 void launch_align_dtw(const AlignDtwParams& p, hipStream_t s);
 // out[r] = logits[r][id[r]] - logsumexp(logits[r][0 .. n_ids)); rows [rows][stride]; an id outside [0, n_ids): -inf
 void launch_row_id_logprob(const float* logits, long stride, int n_ids, const int* id, int rows, float* out, hipStream_t s);
+
+// ---- fused vocabulary log-probabilities (vocab_logprob.hip): out[r] = logit[r][id[r]] - logsumexp(logit[r][0 .. eot)) with
+// logit = a . W^T, a the LayerNorm'ed rows in the 16-bit type; the logits are never written. An id outside [0, eot): -inf.
+constexpr size_t kVocabLogProbMaxLds = 66560;  // the row tile in LDS: 64 rows of 512 + 8, 32 of 1024 + 8, 16 of 2048 + 8 elements
+struct VocabLogProbParams {
+  const h16* a;                  // [rows rounded up to row_tile][d]: the rows beyond `rows` are zeros
+  const h16* W; int n_vocab;     // the tied embedding [n_vocab][d]
+  const int* id;                 // device [rows]
+  int rows, d, eot;
+  int row_tile, n_splits, split_cols;  // vocab_logprob_plan's
+  float* part_m; float* part_s;  // scratch [n_splits][rows]
+  float* target;                 // scratch [rows]
+  float* out;                    // [rows]
+};
+void launch_vocab_logprob(const VocabLogProbParams& p, hipStream_t s);  // the main and the merge launch
 
 // ---- persistent decode (decode_persistent.hip, decode_persistent2.hip): the whole greedy loop of one to three clips in ONE launch
 typedef unsigned long long u64;

@@ -143,6 +143,10 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     const char* e = getenv("AX_WHISPER_WORD_ALIGN");
     cfg_.ints["word_align"] = e && !strcmp(e, "host") ? 1 : 0;
   }
+  {  // "word_logprob": the override of the token-probability route, 0 none, 1 rows, 2 fused; checked at the first alignment call too
+    const char* e = getenv("AX_WHISPER_WORD_LOGPROB");
+    cfg_.ints["word_logprob"] = e && !strcmp(e, "rows") ? 1 : e && !strcmp(e, "fused") ? 2 : 0;
+  }
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half
   ensure_capacity(std::max(1, max_batch));
   HIP_CHECK(hipStreamSynchronize(own_stream_));

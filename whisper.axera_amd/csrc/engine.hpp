@@ -171,6 +171,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void align_tokens(const AlignRequest& rq) override;
   void set_alignment_heads(const int* pairs, int n) override;
   void align_kernel(int which, const AlignKernelIO& io) override;
+  void vocab_logprob_rows(const float* x, int n_rows, const int32_t* ids, float* out, int route) override;
   void stream_open(int n_slots) override;
   void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count,
                     const int* rates = nullptr) override;
@@ -297,6 +298,14 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   int align_env_ = -1;   // AX_WHISPER_WORD_ALIGN, read at first use: 0 the GPU route, 1 the host route
   int align_force_ = -1; // bench "word_align" / "word_align_host": that route for the call in progress
   int align_route();
+  // token probabilities (kAlignLogProbRows / kAlignLogProbFused): AX_WHISPER_WORD_LOGPROB, read at first use (-1 unread, 0 none,
+  // 1 rows, 2 fused), overrides what a request asks for
+  int logprob_env_ = -1;
+  int logprob_route(int requested);
+  // lp[i] = log p(id[i]) over the ids below eot from the final residual row x[row[i]] (row == nullptr: x[i]); all device memory
+  void token_logprob_rows(const float* x, const int* row, const int* id, int n, float* lp, hipStream_t s);   // four rows per logits launch
+  void token_logprob_fused(const float* x, const int* row, const int* id, int n, float* lp, hipStream_t s);  // vocab_logprob.hip
+  float bench_word_logprob(const std::string& what, int batch, int arg, int iters);
   float bench_word_align(const std::string& what, int batch, int arg, int iters);
   int handle_lang_ = 0;  // index of the handle's language in the config's list
   // what an entry point asks before any GPU work: the mode rules of ctx (timestamp modes; under a language spec no open stream) and

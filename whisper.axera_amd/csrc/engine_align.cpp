@@ -9,7 +9,11 @@
 // AX_WHISPER_WORD_ALIGN=host is the yardstick route: the P scratch of every aligned layer goes to the host, where words.hpp's
 // align_normalize_host and align_path do what the two kernels do. AX_WHISPER_GetConfigInt(h, "word_align") = the route of this
 // handle: 0 the kernels, 1 the host.
-// Out of scope: decoder shapes the prefill kernels refuse (an error), words in the long-form loop, under beam search and in Stream*.
+// The token probabilities have two routes (AlignRequest::logprob_route): rows, the logits launch four rows at a time, and fused,
+// vocab_logprob.hip (no logits row is written). AX_WHISPER_WORD_LOGPROB=rows|fused overrides the request;
+// AX_WHISPER_GetConfigInt(h, "word_logprob") = 0 no override, 1 rows, 2 fused.
+// Out of scope: decoder shapes the prefill kernels refuse (an error), words under beam search and in Stream* (the long-form loop
+// calls align_tokens once per pass: engine_long.cpp).
 #include "engine_impl.hpp"
 #include "words.hpp"
 
@@ -61,6 +65,91 @@ int Engine::align_route() {
   return align_force_ >= 0 ? align_force_ : align_env_;
 }
 
+// AX_WHISPER_WORD_LOGPROB, like AX_WHISPER_WORD_ALIGN: read (and a mistyped value refused) at the first alignment call
+int Engine::logprob_route(int requested) {
+  if (logprob_env_ < 0) {
+    const char* e = getenv("AX_WHISPER_WORD_LOGPROB");
+    if (!e || !e[0]) logprob_env_ = 0;
+    else if (!strcmp(e, "rows")) logprob_env_ = 1;
+    else if (!strcmp(e, "fused")) logprob_env_ = 2;
+    else throw std::runtime_error("AX_WHISPER_WORD_LOGPROB must be rows or fused");
+    cfg_.ints["word_logprob"] = logprob_env_;
+  }
+  if (requested != kAlignLogProbRows && requested != kAlignLogProbFused) throw std::runtime_error("align_tokens: unknown log-prob route " + std::to_string(requested));
+  return logprob_env_ == 1 ? kAlignLogProbRows : logprob_env_ == 2 ? kAlignLogProbFused : requested;
+}
+
+// The rows route: the rows through the logits launch, four at a time, 64 dumped logits rows per round, one value out of each.
+// The round's buffers are the call's own (the slots' argmax partials and offsets are not touched).
+void Engine::token_logprob_rows(const float* x, const int* row, const int* id, int n, float* lp, hipStream_t s) {
+  const int d = cfg_.n_text_state;
+  const long vstride = ((long)cfg_.n_vocab + 3) / 4 * 4;
+  DeviceArray<float> xg = device_array<float>((size_t)kAlignLogitRows * d), logits = device_array<float>((size_t)kAlignLogitRows * vstride),
+                     amax_val = device_array<float>((size_t)4 * n_amax_part_);
+  DeviceArray<int> amax_idx = device_array<int>((size_t)4 * n_amax_part_), off4 = device_array<int>(4, true);
+  GemvParams g{};
+  g.W = tok_emb_; g.bias = nullptr; g.N = cfg_.n_vocab; g.K = d;
+  g.prologue = PRO_LAYERNORM; g.in = xg; g.ln_w = dec_ln_w_; g.ln_b = dec_ln_b_;
+  g.epilogue = GEPI_LOGITS; g.state = d_state_; g.off = off4; g.amax_val = amax_val; g.amax_idx = amax_idx; g.amax_stride = n_amax_part_;
+  g.skip_before_step = 0; g.logits_dump = logits; g.logits_dump_stride = vstride;
+  for (int r0 = 0; r0 < n; r0 += kAlignLogitRows) {
+    const int cnt = std::min(kAlignLogitRows, n - r0);
+    if (row) launch_prefill_gather_rows(x, row + r0, xg, cnt, d, s);
+    else g.in = x + (size_t)r0 * d;
+    for (int q0 = 0; q0 < cnt; q0 += 4) {
+      GemvParams q = g;
+      q.batch = std::min(4, cnt - q0);
+      q.in += (long)q0 * d;
+      q.logits_dump += (long)q0 * vstride;
+      launch_gemv(q, s);
+    }
+    launch_row_id_logprob(logits, vstride, cfg_.eot, id + r0, cnt, lp + r0, s);
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));  // (the buffers leave scope)
+}
+
+// The fused route (vocab_logprob.hip): gather, LayerNorm into the 16-bit operand, main launch, merge. The rows that pad the last
+// row tile are zeros.
+void Engine::token_logprob_fused(const float* x, const int* row, const int* id, int n, float* lp, hipStream_t s) {
+  const int d = cfg_.n_text_state;
+  VocabLogProbParams p{};
+  if (!vocab_logprob_plan(d, n, cfg_.eot, &p.row_tile, &p.n_splits, &p.split_cols))
+    throw std::runtime_error("the fused token probabilities do not take " + std::to_string(n) + " rows of " + std::to_string(d));
+  const size_t rows_pad = ((size_t)n + p.row_tile - 1) / p.row_tile * p.row_tile;
+  DeviceArray<float> xg = device_array<float>(row ? (size_t)n * d : 1), part = device_array<float>((size_t)2 * p.n_splits * n), target = device_array<float>(n);
+  DeviceArray<h16> a = device_array<h16>(rows_pad * d);
+  if (rows_pad > (size_t)n) HIP_CHECK(hipMemsetAsync(a + (size_t)n * d, 0, (rows_pad - n) * d * sizeof(h16), s));
+  if (row) launch_prefill_gather_rows(x, row, xg, n, d, s);
+  launch_layernorm_bf16(const_cast<float*>(row ? (const float*)xg : x), dec_ln_w_, dec_ln_b_, a, n, d, s);  // (no partials: x is read only)
+  p.a = a; p.W = tok_emb_; p.n_vocab = cfg_.n_vocab; p.id = id; p.rows = n; p.d = d; p.eot = cfg_.eot;
+  p.part_m = part; p.part_s = part + (size_t)p.n_splits * n; p.target = target; p.out = lp;
+  launch_vocab_logprob(p, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));  // (the buffers leave scope)
+}
+
+void Engine::vocab_logprob_rows(const float* x, int n_rows, const int32_t* ids, float* out, int route) {
+  require_no_stream("vocab_logprob_rows");
+  if (!x || !ids || !out || n_rows < 1 || (route != kAlignLogProbRows && route != kAlignLogProbFused)) throw std::runtime_error("vocab_logprob_rows: bad arguments");
+  if (cfg_.eot < 1 || cfg_.eot > cfg_.n_vocab) throw std::runtime_error("vocab_logprob_rows: the config's eot lies outside the vocabulary");
+  for (int r = 0; r < n_rows; ++r)
+    if (ids[r] < 0 || ids[r] >= cfg_.eot) throw std::runtime_error("vocab_logprob_rows: id " + std::to_string(ids[r]) + " of row " + std::to_string(r) + " is not below eot");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  hipStream_t s = stream();
+  const size_t d = (size_t)cfg_.n_text_state;
+  DeviceArray<float> dx = device_array<float>(n_rows * d), lp = device_array<float>(n_rows);
+  DeviceArray<int> did = device_array<int>(n_rows);
+  HIP_CHECK(hipMemcpyAsync(dx, x, n_rows * d * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(did, ids, (size_t)n_rows * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));  // (pageable sources)
+  if (route == kAlignLogProbFused) token_logprob_fused(dx, nullptr, did, n_rows, lp, s);
+  else token_logprob_rows(dx, nullptr, did, n_rows, lp, s);
+  HIP_CHECK(hipMemcpyAsync(out, lp, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
 void Engine::align_tokens(const AlignRequest& rq) {
   require_no_stream("align_tokens");
   require_timestamp_vocab();
@@ -69,7 +158,7 @@ void Engine::align_tokens(const AlignRequest& rq) {
   if (!rq.ids || rq.stride < 1 || !rq.n_ids || !rq.num_frames || !rq.jump || !rq.token_logprob)
     throw std::runtime_error("align_tokens: bad arguments");
   if (!prefill_supported()) throw std::runtime_error("align_tokens: the prefill kernels do not take this decoder shape");
-  const int route = align_route();
+  const int route = align_route(), lp_route = logprob_route(rq.logprob_route);
   if (route == 0 && Tc - 4 >= kAlignDtwThreads) throw std::runtime_error("align_tokens: the DTW kernel takes at most " + std::to_string(kAlignDtwThreads + 3) + " context rows");
   int translate = -1;
   {
@@ -110,12 +199,7 @@ void Engine::align_tokens(const AlignRequest& rq) {
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   hipStream_t s = stream();
-  const long vstride = ((long)cfg_.n_vocab + 3) / 4 * 4;
   const long cross_stride = (long)cfg_.n_text_head * layout::kv_head_elems(t_pad_);
-  // the logits rounds' own buffers (the slots' argmax partials and offsets are not touched)
-  DeviceArray<float> xg = device_array<float>((size_t)kAlignLogitRows * d), logits = device_array<float>((size_t)kAlignLogitRows * vstride),
-                     amax_val = device_array<float>((size_t)4 * n_amax_part_);
-  DeviceArray<int> amax_idx = device_array<int>((size_t)4 * n_amax_part_), off4 = device_array<int>(4, true);
 
   // chunks of consecutive clips whose P scratch fits the budget
   for (size_t c0 = 0; c0 < clips.size();) {
@@ -214,24 +298,9 @@ void Engine::align_tokens(const AlignRequest& rq) {
         align_path(h_matrix.data() + ((size_t)c * rows_pad + 3) * f_pad, len[c] - 4, n_keys[c], f_pad, h_jump.data() + (size_t)c * Tc);
     }
 
-    // token probabilities: the final residual rows of positions 3 .. n + 2 through the logits launch, four rows at a time
-    GemvParams g{};
-    g.W = tok_emb_; g.bias = nullptr; g.N = cfg_.n_vocab; g.K = d;
-    g.prologue = PRO_LAYERNORM; g.in = xg; g.ln_w = dec_ln_w_; g.ln_b = dec_ln_b_;
-    g.epilogue = GEPI_LOGITS; g.state = d_state_; g.off = off4; g.amax_val = amax_val; g.amax_idx = amax_idx; g.amax_stride = n_amax_part_;
-    g.skip_before_step = 0; g.logits_dump = logits; g.logits_dump_stride = vstride;
-    for (int r0 = 0; r0 < n_lp; r0 += kAlignLogitRows) {
-      const int cnt = std::min(kAlignLogitRows, n_lp - r0);
-      launch_prefill_gather_rows(pf.x, d_lp_row + r0, xg, cnt, d, s);
-      for (int q0 = 0; q0 < cnt; q0 += 4) {
-        GemvParams q = g;
-        q.batch = std::min(4, cnt - q0);
-        q.in += (long)q0 * d;
-        q.logits_dump += (long)q0 * vstride;
-        launch_gemv(q, s);
-      }
-      launch_row_id_logprob(logits, vstride, cfg_.eot, d_lp_id + r0, cnt, d_lp + r0, s);
-    }
+    // token probabilities: the final residual rows of positions 3 .. n + 2
+    if (lp_route == kAlignLogProbFused) token_logprob_fused(pf.x, d_lp_row, d_lp_id, n_lp, d_lp, s);
+    else token_logprob_rows(pf.x, d_lp_row, d_lp_id, n_lp, d_lp, s);
     HIP_CHECK(hipGetLastError());
     std::vector<float> h_lp(n_lp);
     HIP_CHECK(hipMemcpyAsync(h_lp.data(), d_lp, (size_t)n_lp * 4, hipMemcpyDeviceToHost, s));

@@ -107,6 +107,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "prefill" || what == "prefill_pass" || what == "prefill_step") return bench_prefill(what, batch, arg, iters);
   if (what == "detect_language") return bench_detect_language(batch, arg, iters);
   if (what == "word_align" || what == "word_align_host") return bench_word_align(what, batch, arg, iters);
+  if (what == "word_logprob" || what == "word_logprob_rows") return bench_word_logprob(what, batch, arg, iters);
   throw std::runtime_error("bench: unknown target '" + what + "'");
 }
 
@@ -177,6 +178,30 @@ float Engine::bench_word_align(const std::string& what, int batch, int arg, int 
   align_tokens(rq);  // warm: the prefill scratch
   const auto t0 = std::chrono::steady_clock::now();
   for (int i = 0; i < iters; ++i) align_tokens(rq);
+  return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// word_logprob / word_logprob_rows: the token probabilities of `batch` clips x arg ids alone (batch * arg final residual rows, seeded,
+// already on the device), by the fused kernel / by the logits launch four rows at a time (A/B on one handle). Scratch allocation and
+// the closing synchronisation are inside, as align_tokens pays them.
+float Engine::bench_word_logprob(const std::string& what, int batch, int arg, int iters) {
+  require_timestamp_vocab();
+  const int n = batch * std::max(1, std::min(arg, cfg_.n_text_ctx - 5)), d = cfg_.n_text_state;
+  std::vector<float> hx((size_t)n * d);
+  std::vector<int> hid(n);
+  unsigned x = 12345u;
+  for (auto& v : hx) { x = x * 1664525u + 1013904223u; v = (float)(int)((x >> 8) & 0xffff) / 16384.f - 2.f; }
+  for (auto& v : hid) { x = x * 1664525u + 1013904223u; v = (int)((x >> 8) % (unsigned)cfg_.eot); }
+  hipStream_t s = stream();
+  DeviceArray<float> dx = device_array<float>(hx.size()), lp = device_array<float>(n);
+  DeviceArray<int> did = device_array<int>(n);
+  HIP_CHECK(hipMemcpy(dx, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(did, hid.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  const bool fused = what == "word_logprob";
+  auto run = [&] { fused ? token_logprob_fused(dx, nullptr, did, n, lp, s) : token_logprob_rows(dx, nullptr, did, n, lp, s); };
+  run();  // warm
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < iters; ++i) run();
   return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 

@@ -1,6 +1,7 @@
 // engine_long.cpp — long-form transcription (DESIGN.md "Long-form"): the log-mel of whole files kept in HBM, and the seek loop
 // that decodes one 30 s window of every unfinished file per pass through the batched encoder and the timestamp-mode step graph.
 #include "engine_impl.hpp"
+#include "words.hpp"
 
 namespace axw {
 inline namespace AXW_NS {
@@ -204,6 +205,13 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   ClipContexts ctx;
   if (prompted) ctx.prompts = PromptSpec{prompt_ids.data(), keep, n_prompt.data()};
   if (per_lang) { ctx.lang = LangSpec{win_lang.data(), win_task.data()}; ctx.lang_out.detected = win_lang_got.data(); }
+  // word timestamps: the tables of the pass's one alignment call, the log entry a slot's window went to, every file's last word end
+  const bool words = opts && opts->word_timestamps;
+  std::vector<int32_t> al_ids(words ? (size_t)S * Tc : 0);
+  std::vector<int> al_n(words ? S : 0), al_frames(words ? S : 0), al_lang(words ? S : 0), al_task(words ? S : 0), al_jump(words ? (size_t)S * (Tc + 1) : 0);
+  std::vector<float> al_lp(words ? (size_t)S * Tc : 0);
+  std::vector<long> win_log(words ? S : 0, -1);
+  std::vector<double> last_speech(words ? n_files : 0, 0.0);
   int next_file = 0, steps = 0;
   for (int pass = 0; max_passes <= 0 || pass < max_passes; ++pass) {
     // finished files leave, the others move up, waiting files take the free places
@@ -285,7 +293,62 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
       w.advance = w.skipped ? w.window_frames : split_window(w.ids.data(), n, T, E, w.window_frames, segs);
       seek[f] += w.advance;
       if (prompted) carry_prompt(carry[f], w.ids.data(), n, T, E, w.window_frames, w.skipped, opts->condition_on_previous_text, fallback ? temps[i] : 0.f);
+      if (words && !w.skipped) win_log[i] = (long)log.size();
       log.push_back(std::move(w));
+    }
+    if (!words) continue;
+    // Word timestamps: the decisions of the pass stand; its kept, non-skipped windows are aligned in ONE call over the pass's slots
+    // (their cross K/V is still there; the alignment overwrites self-attention caches, which the next pass rewrites), then the word
+    // rule runs per window in file time and long_word_advance may move the file's seek to the last word's end.
+    bool any = false;
+    for (int i = 0; i < A; ++i) {
+      al_n[i] = 0; al_frames[i] = 2; al_lang[i] = -1; al_task[i] = 0;
+      if (win_log[i] < 0) continue;
+      LongWindow& w = log[(size_t)win_log[i]];
+      split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
+      const double time_offset = (double)w.seek / 100.0;
+      for (const WindowSegment& sg : segs) {
+        int count = 0;
+        for (int k = sg.tok_begin; k < sg.tok_end; ++k)
+          if (w.ids[k] < E && (int)w.text_ids.size() + 5 < Tc) { w.text_ids.push_back(w.ids[k]); ++count; }  // (the alignment's bound)
+        w.seg_tokens.push_back(count);
+        w.seg_start.push_back(time_offset + (double)sg.start);
+        w.seg_end.push_back(time_offset + (double)sg.end);
+      }
+      if (w.window_frames < 2 || w.text_ids.empty()) continue;  // (no encoder frame to align against, or no text: no words)
+      al_n[i] = (int)w.text_ids.size();
+      std::copy(w.text_ids.begin(), w.text_ids.end(), al_ids.begin() + (size_t)i * Tc);
+      al_frames[i] = w.window_frames;
+      if (per_lang) { al_lang[i] = file_lang[files[i]]; al_task[i] = file_task[files[i]]; }
+      any = true;
+    }
+    if (any)
+      align_tokens(AlignRequest{A, al_ids.data(), Tc, al_n.data(), al_frames.data(), al_lang.data(), al_task.data(), al_jump.data(), al_lp.data(), nullptr,
+                                0, 0, opts->word_logprob_route});
+    for (int i = 0; i < A; ++i) {
+      if (win_log[i] < 0) continue;
+      LongWindow& w = log[(size_t)win_log[i]];
+      win_log[i] = -1;
+      const int f = files[i], nt = al_n[i], li = per_lang ? file_lang[f] : handle_lang_;
+      if (nt > 0) {
+        w.jump.assign(al_jump.begin() + (size_t)i * (Tc + 1), al_jump.begin() + (size_t)i * (Tc + 1) + nt + 1);
+        w.word_logprob.assign(al_lp.begin() + (size_t)i * Tc, al_lp.begin() + (size_t)i * Tc + nt);
+        const std::string code = li >= 0 && li < (int)cfg_.lang_codes.size() ? cfg_.lang_codes[(size_t)li] : std::string();
+        for (const WordOut& o : words_from_alignment(token_table(), w.text_ids.data(), nt, E, code, w.seg_tokens.data(), w.seg_start.data(), w.seg_end.data(),
+                                                     (int)w.seg_tokens.size(), w.jump.data(), w.word_logprob.data(), last_speech[f], (double)w.seek / 100.0))
+          w.words.push_back(LongWord{o.segment, o.text, o.start, o.end, (float)o.probability});
+      } else {
+        w.text_ids.clear();  // (nothing was aligned)
+        for (int& t : w.seg_tokens) t = 0;
+      }
+      const bool has_word = !w.words.empty();
+      const double last_word_end = has_word ? w.words.back().end : 0.0;
+      bool by_word_end = false;
+      const int adv = long_word_advance(w.ids.data(), (int)w.ids.size(), T, w.seek, w.window_frames, w.advance, has_word, last_word_end, &by_word_end);
+      seek[f] += adv - w.advance;
+      w.advance = adv;
+      w.by_word_end = by_word_end;
+      if (has_word) last_speech[f] = last_word_end;
     }
   }
   HIP_CHECK(hipEventRecord(ev_[3], s));

@@ -174,8 +174,16 @@ class IEngine {
   struct AlignRequest {
     int batch; const int32_t* ids; int stride; const int* n_ids; const int* num_frames; const int* lang; const int* task;
     int* jump; float* token_logprob; float* matrix; int m_rows, m_ld;
+    // how token_logprob is computed: kAlignLogProbRows, the logits launch four rows at a time and one value read out of every row,
+    // or kAlignLogProbFused, vocab_logprob.hip (the LayerNorm'ed row is narrowed to the 16-bit type; no logits row is written).
+    // AX_WHISPER_WORD_LOGPROB=rows|fused overrides it.
+    int logprob_route = 0;
   };
+  enum : int { kAlignLogProbRows = 0, kAlignLogProbFused = 1 };
   virtual void align_tokens(const AlignRequest& rq) = 0;
+  // the token probabilities alone on host data (tests, A/B): x fp32 [n_rows][n_text_state] final residual rows, one id in [0, eot)
+  // per row -> out [n_rows] = log p(id) over the ids below eot, by `route` itself (the environment does not override it here)
+  virtual void vocab_logprob_rows(const float* x, int n_rows, const int32_t* ids, float* out, int route) = 0;
   // the list of (layer, head) pairs the alignment averages over; n == 0: the default, every head of the upper half of the layers
   virtual void set_alignment_heads(const int* pairs, int n) = 0;
   // One kernel of decode_align.hip alone on host data (tests). Clip c has len[c] rows and n_keys[c] frames.

@@ -69,6 +69,25 @@ inline int split_window(const int32_t* ids, int n, int T, int E, int window_fram
   return (int)advance;
 }
 
+// The seek rule under word timestamps (DESIGN.md "Word-level timestamps", long-form; openai-whisper transcribe() with
+// word_timestamps=True). ids: the window's ids (eot excluded), seek: its start in frames of 10 ms, split_advance: what split_window
+// gave; has_word / last_word_end: whether the window yielded a word and the end of its last one, seconds in FILE time.
+// Unless the ids end in a single timestamp (last id >= T, the one before it < T): if the last word ends behind the window's start
+// (last_word_end > seek / 100), the next window starts there, at round(last_word_end * 100) (to the nearest frame, ties to even, as
+// Python's round). Progress guard, in the spirit of split_window's: an advance <= 0 or > window_frames keeps split_window's.
+// Returns the advance; *by_word_end (optional): whether the word-end seek was taken.
+inline int long_word_advance(const int32_t* ids, int n, int T, int seek, int window_frames, int split_advance, bool has_word, double last_word_end,
+                             bool* by_word_end = nullptr) {
+  if (by_word_end) *by_word_end = false;
+  const bool single_end = n >= 2 && ids[n - 1] >= T && ids[n - 2] < T;
+  if (single_end || !has_word || !(last_word_end > (double)seek / 100.0)) return split_advance;
+  const double target = std::nearbyint(last_word_end * 100.0);
+  const double advance = target - (double)seek;
+  if (!(advance > 0) || advance > (double)window_frames) return split_advance;
+  if (by_word_end) *by_word_end = true;
+  return (int)advance;
+}
+
 // The silent-window rule of the seek loop (DESIGN.md "Confidence"; openai-whisper transcribe(): should_skip). no_speech_logprob:
 // log p(<|nospeech|>) at the step that fed sot; avg_logprob: the window's average token log-probability. A window is skipped iff
 // the no-speech PROBABILITY exceeds its threshold and the average log-probability does not exceed its own: logprob_threshold
@@ -174,6 +193,19 @@ struct LongScoreOptions {
   std::vector<int> file_lang, file_task;
   int* file_lang_out = nullptr;
   bool per_file_language() const { return !file_lang.empty() || !file_task.empty() || file_lang_out; }
+  // Word timestamps (DESIGN.md "Word-level timestamps", long-form): after the decisions of a pass every kept, non-skipped window is
+  // aligned (one align_tokens call per pass), the word rule runs in file time with the file's last_speech_timestamp, and
+  // long_word_advance may move the seek to the last word's end. word_logprob_route: the route of the token probabilities
+  // (0 rows, 1 fused). Off: the loop as it was.
+  bool word_timestamps = false;
+  int word_logprob_route = 1;
+};
+
+struct LongWord {
+  int segment;          // index among the window's segments
+  std::string text;     // the word's bytes
+  double start, end;    // seconds in file time
+  float probability;
 };
 
 // one decoded window of AX_WHISPER_RunPCMLongWindows, in execution order
@@ -188,6 +220,15 @@ struct LongWindow {
   float temperature = 0.f, compression_ratio = 0.f;
   bool kept = true;
   int n_prompt = 0;  // prompted calls only: ids the window was conditioned on (after the truncation to n_text_ctx / 2 - 1)
+  // word-timestamp calls only, on kept windows that were not skipped (else empty): the text ids that were aligned (those below eot
+  // of split_window's segments, seg_tokens[s] of them in segment s), the alignment's raw jump [n + 1] and token_logprob [n], the
+  // segment starts and ends the word rule left and the words, both in file time, and which advance was taken
+  std::vector<int32_t> text_ids;
+  std::vector<int> seg_tokens, jump;
+  std::vector<float> word_logprob;
+  std::vector<double> seg_start, seg_end;
+  std::vector<LongWord> words;
+  bool by_word_end = false;  // advance is long_word_advance's word-end seek, not split_window's
 };
 
 }  // namespace axw

@@ -24,8 +24,9 @@ static void usage(const char* prog) {
           "  -p, --model_path    model path which contains tiny/ base/ small/ turbo/ (string [=../models-mi355x])\n"
           "      --language      en, zh (string [=zh])\n"
           "      --timestamps    after Result:, one line per segment: [mm:ss.mmm --> mm:ss.mmm] text\n"
-          "      --word_timestamps   (with --timestamps alone) under every segment line one indented line per word:\n"
-          "                      [mm:ss.mmm --> mm:ss.mmm] word (probability); the segment times are those the word rule leaves\n"
+          "      --word_timestamps   (with --timestamps alone, or with --long) under every segment line one indented line per word:\n"
+          "                      [mm:ss.mmm --> mm:ss.mmm] word (probability); the segment times are those the word rule leaves.\n"
+          "                      With --long the seek follows the last word's end, as openai-whisper's transcribe(word_timestamps=True)\n"
           "      --beam_size N   (with --timestamps, not with --long) the segment lines are those of beam search's winner over N\n"
           "                      hypotheses (1 .. 8; openai-whisper's CLI uses 5) instead of the greedy decode's\n"
           "      --long          transcribe the whole file, not only its first 30 s: Result: is the whole text, followed by\n"
@@ -303,6 +304,43 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
   return 0;
 }
 
+// --long --word_timestamps: the seek loop with words (AX_WHISPER_RunPCMLongWords) under the same thresholds, fallback, prompts, language
+// and task as run_long: the whole text, then one line per segment (the times the word rule left) and under it one indented line per word
+static int run_long_words(AX_WHISPER_HANDLE h, const char* wav, float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold,
+                          const std::vector<float>& temps, unsigned long long seed, const std::vector<int32_t>& prompt_ids, bool condition,
+                          std::string& text, std::string& lines, bool detect, int task) {
+  float* pcm = nullptr;
+  int n = 0;
+  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
+  int lang = -1;
+  if (detect && (lang = detect_and_print(h, pcm, n)) < 0) { free(pcm); return -1; }
+  const int want = lang, tk = task > 0 ? 1 : 0, n_initial = (int)prompt_ids.size();
+  AX_WHISPER_LONG_OPTIONS o{};
+  o.no_speech_threshold = no_speech_threshold; o.logprob_threshold = logprob_threshold; o.compression_ratio_threshold = compression_ratio_threshold;
+  o.temperatures = temps.empty() ? nullptr : temps.data(); o.n_temperatures = (int)temps.size(); o.seed = seed;
+  o.initial_prompt_ids = prompt_ids.data(); o.prompt_stride = n_initial; o.n_initial = &n_initial; o.condition_on_previous_text = condition ? 1 : 0;
+  o.lang = &want; o.task = &tk; o.word_timestamps = 1;
+  AX_WHISPER_LONG_WORDS r{};
+  const int rc = AX_WHISPER_RunPCMLongWords(h, pcm, n, &o, nullptr, &r);
+  free(pcm);
+  if (rc != 0) return -1;
+  for (int k = 0, w = 0; k < r.n_segments; ++k) {
+    const int sb = k ? r.seg_text_end[k - 1] : 0;
+    const std::string seg(r.seg_text + sb, r.seg_text + r.seg_text_end[k]);
+    text += seg;
+    lines += "[" + mmss_ms((long)(r.seg_start[k] * 1000.0 + 0.5)) + " --> " + mmss_ms((long)(r.seg_end[k] * 1000.0 + 0.5)) + "] " + seg + "\n";
+    for (; w < r.n_words && r.word_segment[w] == k; ++w) {
+      const int b = w ? r.word_text_end[w - 1] : 0;
+      char p[32];
+      snprintf(p, sizeof p, " (%.3f)", r.word_prob[w]);
+      lines += "  [" + mmss_ms((long)(r.word_start[w] * 1000.0 + 0.5)) + " --> " + mmss_ms((long)(r.word_end[w] * 1000.0 + 0.5)) + "] " +
+               std::string(r.word_text + b, r.word_text + r.word_text_end[w]) + p + "\n";
+    }
+  }
+  AX_WHISPER_FreeLongWords(&r);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
   bool timestamps = false, longform = false, word_timestamps = false;
@@ -357,8 +395,8 @@ int main(int argc, char** argv) {
     usage(argv[0]);
     return 1;
   }
-  if (word_timestamps && (!timestamps || longform || beam_size > 1 || per_lang)) {
-    fprintf(stderr, "--word_timestamps needs --timestamps and does not go with --long, --beam_size, --detect_language or --task\n");
+  if (word_timestamps && !longform && (!timestamps || beam_size > 1 || per_lang)) {
+    fprintf(stderr, "--word_timestamps needs --timestamps or --long; with --timestamps it does not go with --beam_size, --detect_language or --task\n");
     usage(argv[0]);
     return 1;
   }
@@ -433,8 +471,10 @@ int main(int argc, char** argv) {
   if (longform) {
     t0 = std::chrono::steady_clock::now();
     std::string text, lines;
-    if (run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompted, prompt_ids, condition,
-                 text, lines, detect, task) != 0) {
+    if ((word_timestamps ? run_long_words(handle, wav.c_str(), no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompt_ids,
+                                          condition, text, lines, detect, task)
+                         : run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompted,
+                                    prompt_ids, condition, text, lines, detect, task)) != 0) {
       printf("AX_WHISPER_Run failed! %s\n", AX_WHISPER_LastError(handle));
       AX_WHISPER_Uninit(handle);
       return -1;

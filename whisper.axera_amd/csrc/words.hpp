@@ -277,9 +277,12 @@ struct WordOut {
 
 // find_alignment's words from the path + add_word_timestamps of one window. ids: the n text ids (< eot) of the window's segments
 // in order, seg_tokens[s] of them in segment s; jump [n + 1] frames of 20 ms, logprob [n]; seg_start / seg_end are updated in place.
+// time_offset: the window's start in the file, seconds (long-form: seek / 100). Word times are round2(time_offset + jump / 50);
+// seg_start / seg_end, last_speech_timestamp and the max(0, .) clamps are then all in file time, as openai-whisper's
+// add_word_timestamps sees them inside transcribe(). The word durations (median, sentence-end cut) are taken before the offset.
 inline std::vector<WordOut> words_from_alignment(const std::vector<std::string>& table, const int32_t* ids, int n, int eot, const std::string& lang,
                                                  const int* seg_tokens, double* seg_start, double* seg_end, int n_seg, const int* jump,
-                                                 const float* logprob, double last_speech_timestamp) {
+                                                 const float* logprob, double last_speech_timestamp, double time_offset = 0.0) {
   std::vector<WordOut> out;
   if (n_seg == 0) return out;
   long total = 0;
@@ -339,7 +342,7 @@ inline std::vector<WordOut> words_from_alignment(const std::vector<std::string>&
     const size_t first = out.size();
     while (wi < al.size() && saved < seg_tokens[s]) {
       const WordTiming& t = al[wi];
-      if (!t.text.empty()) out.push_back(WordOut{s, t.text, round2(t.start), round2(t.end), t.probability});
+      if (!t.text.empty()) out.push_back(WordOut{s, t.text, round2(time_offset + t.start), round2(time_offset + t.end), t.probability});
       saved += (int)t.tokens.size();
       ++wi;
     }
