@@ -700,7 +700,8 @@ AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5);
  *  from decode offset 224 on, one offset further per iteration; afterwards GetConfigInt "beam_bench_moved_slots" / "beam_bench_iters" /
  *  "beam_bench_complete_clips" say how many slots the reorder launches copied in all, over how many iterations, and how many clips
  *  had completed), "encoder", "frontend", "frontend_long" (whole-file front-end of `batch`
- *  files of `arg` seconds + one window kernel), "prefill" (reset + PrefillPrompts of `batch` slots with prompts of arg - 3 ids each,
+ *  files of `arg` seconds + one window kernel), "long_cut_plan" (chunked long-form: levels kernel + plan kernels over `batch` resident
+ *  files of `arg` seconds, default parameters), "prefill" (reset + PrefillPrompts of `batch` slots with prompts of arg - 3 ids each,
  *  i.e. context length L = arg, by the handle's route), "word_align" / "word_align_host" (AlignTokens of `batch` slots with `arg` text ids
  *  each against all frames, by the kernels / by the host route; host wall time), "word_logprob" / "word_logprob_rows" (the token
  *  probabilities of batch * arg residual rows alone, by the fused kernel / four rows per logits launch; host wall time), "resample" (the resample kernel over `batch` clips
@@ -739,6 +740,68 @@ AX_WHISPER_API int AX_WHISPER_RunFileResampled(AX_WHISPER_HANDLE handle, const c
  *  takes (long-form, fallback, prompted, language, beam, words); info (may be NULL): [0] the file's sample rate, [1] channels,
  *  [2] samples per channel in the file. */
 AX_WHISPER_API int AX_WHISPER_LoadAudioFile16k(AX_WHISPER_HANDLE handle, const char* path, float** samples, int* n_samples, int* info);
+
+/* ---- additions: chunked long-form (DESIGN.md "Chunked long-form"; csrc/long_cuts.hpp: the definitions) ------------------- */
+/* The seek loop above decodes a file's windows one after the other, so one file fills one decoder slot. The calls below choose
+ * every window of a file BEFORE decoding and decode them side by side, min(slots, remaining) per pass. A cut goes to the quietest
+ * frame of a search range, chosen on the GPU from the file's own log-mel store (no voice-activity model):
+ *   level of frame f        e[f] = mean over the mels of what the encoder will see, (max(S[f][m], G - 8) + 4) / 4
+ *   smoothed level          s[f] = mean of e over [f - R, f + R], the index clamped to the file's 1 + num_samples / 160 frames
+ *   cut rule                seek = 0; while content - seek > max_frames: among the even f in [seek + min_frames, seek + max_frames] the
+ *                           smallest s[f] (fp32, exact; a tie goes to the largest f) ends the window (seek, f - seek), seek = f;
+ *                           the last window is (seek, content - seek). content = num_samples / 160.
+ * min_frames and max_frames are even, 2 <= min_frames <= max_frames <= 3000; smooth_frames R is 0 .. 64. A window's features are its
+ * frames, zero from frame len on. The trade-off is that of every batched Whisper pipeline: windows are decoded independently (no
+ * text of an earlier window, no seek feedback), and where a search range holds no quiet frame a word may straddle a cut. The seek
+ * loop stays the default. Not covered, refused with a text in AX_WHISPER_LastError: language detection (lang -2), temperatures and
+ * fallback, prompts and condition_on_previous_text, word timestamps, beam search, AX_WHISPER_FEATURE_MODE=openai. */
+typedef struct AX_WHISPER_CHUNK_OPTIONS {
+  int max_frames;     /* W_max, default 3000 */
+  int min_frames;     /* W_min, default 2000 */
+  int smooth_frames;  /* R, default 25 */
+  int beam_size;      /* 1 (anything else is refused) */
+} AX_WHISPER_CHUNK_OPTIONS;
+/** Host only (no handle, no GPU): the cut rule on a caller's levels s [content] (finite). seek / len [win_cap] receive the windows,
+ *  *n_windows their number (at most ceil(content / min_frames) + 1; content 0: none). -1 on bad parameters, non-finite levels or a
+ *  win_cap too small (nothing written; the text in AX_WHISPER_LastError(NULL)). */
+AX_WHISPER_API int AX_WHISPER_LongCutPlanHost(const float* s, int content, int min_frames, int max_frames, int win_cap, int* seek, int* len,
+                                              int* n_windows);
+/** Host only: one window's ids (eot excluded) -> its segments in FILE time. The split is AX_WHISPER_SplitSegments' with clip_seconds =
+ *  len / 100 (the trailing piece is kept: no later window decodes that audio again); every time t becomes seek / 100 + min(t, len / 100). */
+AX_WHISPER_API int AX_WHISPER_ChunkedSegments(const int32_t* ids, int n, int timestamp_begin, int eot, int seek, int len, int n_max, double* start,
+                                              double* end, int* tok_begin, int* tok_end, int* n_seg);
+/** Stage level: whole-file front-end + levels kernel over n_files files in one launch. e[b] / s[b] (either array, or an entry, may be
+ *  NULL): host [1 + num_samples[b] / 160]. */
+AX_WHISPER_API int AX_WHISPER_LongFrameLevels(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                              int smooth_frames, float* const* e, float* const* s);
+/** Stage level: the plan kernel alone on a caller's levels, as AX_WHISPER_LongCutPlanHost (content >= 1). */
+AX_WHISPER_API int AX_WHISPER_LongCutPlanFromLevels(AX_WHISPER_HANDLE handle, const float* s, int content, int min_frames, int max_frames,
+                                                    int win_cap, int* seek, int* len, int* n_windows);
+/** Stage level: front-end + levels + plan of n_files files in one call (chunk NULL: the defaults). n_windows [n_files]: windows per
+ *  file; win_file / win_seek / win_len [win_cap]: all of them in the order file-then-seek; s (may be NULL, as may its entries): the
+ *  levels the plan was made from, as in LongFrameLevels. -1 with "N windows were planned" in LastError when win_cap is too small. */
+AX_WHISPER_API int AX_WHISPER_LongCutPlan(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                          const AX_WHISPER_CHUNK_OPTIONS* chunk, int win_cap, int* n_windows, int* win_file, int* win_seek,
+                                          int* win_len, float* const* s);
+/** Stage level: AX_WHISPER_ComputeMelWindow for a window of `len` frames (0 .. 3000): bit-equal to it on frames below len, zero from
+ *  there on. */
+AX_WHISPER_API int AX_WHISPER_ComputeMelWindowCut(AX_WHISPER_HANDLE handle, const float* pcm, int num_samples, int seek, int len, float* mel_out);
+/** The chunked call over n_files files; the log is RunPCMLongWindows': window k: win_info[k*7 .. k*7+6] = file index, seek, window_frames,
+ *  advance (both the window's length), n_ids, pass, encoder slot; ids[k*n_text_ctx ..]. Windows come in the order file-then-seek; pass p
+ *  holds windows p * slots .. of that order in slots 0 .. A-1. chunk (NULL: the defaults); opts (NULL: none): no_speech_threshold /
+ *  logprob_threshold (either not NaN, or win_score not NULL: the scored decode mode; win_score [win_cap][3] = no_speech_logprob,
+ *  avg_logprob, 1 iff AX_WHISPER_LongWindowIsSilent drops the window's segments), lang (>= 0 or -1) and task per file; every other
+ *  member must be off (see above). max_new, max_passes, win_cap and the sharding over several devices as in RunPCMLongWindows. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongChunkedWindows(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                       int max_new, int max_passes, const AX_WHISPER_CHUNK_OPTIONS* chunk,
+                                                       const AX_WHISPER_LONG_OPTIONS* opts, int win_cap, int* win_info, int32_t* ids,
+                                                       float* win_score, int* n_windows);
+/** Text of a whole file by the chunked call: the transcripts of AX_WHISPER_ChunkedSegments' segments of every window that was not
+ *  dropped as silent, concatenated (under opts->lang[0] when given). *result malloc'd. */
+AX_WHISPER_API int AX_WHISPER_RunPCMLongChunked(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const AX_WHISPER_CHUNK_OPTIONS* chunk,
+                                                const AX_WHISPER_LONG_OPTIONS* opts, char** result);
+AX_WHISPER_API int AX_WHISPER_RunFileLongChunked(AX_WHISPER_HANDLE handle, const char* wav_file, const AX_WHISPER_CHUNK_OPTIONS* chunk,
+                                                 const AX_WHISPER_LONG_OPTIONS* opts, char** result);
 
 #ifdef __cplusplus
 }

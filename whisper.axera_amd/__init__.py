@@ -37,6 +37,11 @@ class LongOptions(C.Structure):
                 ("lang", C.POINTER(C.c_int)), ("task", C.POINTER(C.c_int)), ("word_timestamps", C.c_int)]
 
 
+class ChunkOptions(C.Structure):
+    """AX_WHISPER_CHUNK_OPTIONS"""
+    _fields_ = [("max_frames", C.c_int), ("min_frames", C.c_int), ("smooth_frames", C.c_int), ("beam_size", C.c_int)]
+
+
 class LongWordLog(C.Structure):
     """AX_WHISPER_LONG_WORD_LOG"""
     _fields_ = [("seg_cap", C.c_int), ("word_cap", C.c_int), ("win_words", C.POINTER(C.c_int)), ("text_ids", ip), ("jump", C.POINTER(C.c_int)),
@@ -192,6 +197,18 @@ SYMBOLS = {
     "AX_WHISPER_StreamAdmitBatchRate": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "AX_WHISPER_RunFileResampled": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "AX_WHISPER_LoadAudioFile16k": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_LongCutPlanHost": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_ChunkedSegments": (C.c_int, [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dblp, _dblp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int)]),
+    "AX_WHISPER_LongFrameLevels": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(fp), C.POINTER(fp)]),
+    "AX_WHISPER_LongCutPlanFromLevels": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_LongCutPlan": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.POINTER(ChunkOptions), C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(fp)]),
+    "AX_WHISPER_ComputeMelWindowCut": (C.c_int, [C.c_void_p, fp, C.c_int, C.c_int, C.c_int, fp]),
+    "AX_WHISPER_RunPCMLongChunkedWindows": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(ChunkOptions),
+                                                      C.POINTER(LongOptions), C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_RunPCMLongChunked": (C.c_int, [C.c_void_p, fp, C.c_int, C.POINTER(ChunkOptions), C.POINTER(LongOptions), C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_RunFileLongChunked": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(ChunkOptions), C.POINTER(LongOptions), C.POINTER(C.c_void_p)]),
 }
 
 
@@ -305,6 +322,37 @@ def split_window(ids, timestamp_begin: int, eot: int, window_frames: int):
                                 C.byref(n), C.byref(adv)) != 0:
         raise RuntimeError("AX_WHISPER_SplitWindow failed")
     return [(float(st[k]), float(en[k]), int(tb[k]), int(te[k])) for k in range(n.value)], adv.value
+
+
+def long_cut_plan_host(s, min_frames: int = 2000, max_frames: int = 3000, content=None):
+    """The cut rule of chunked long-form on levels s (AX_WHISPER_LongCutPlanHost, host only) -> [(seek, len)]. content: frames of
+    audio (default: len(s)). Raises ValueError on refused parameters or non-finite levels."""
+    L = load_library()
+    a = _f32(s)
+    content = len(a) if content is None else int(content)
+    if content > len(a):
+        raise ValueError("content beyond the levels")
+    cap = content // max(int(min_frames), 1) + 2
+    seek, ln, n = (C.c_int * cap)(), (C.c_int * cap)(), C.c_int()
+    if L.AX_WHISPER_LongCutPlanHost(a.ctypes.data_as(fp), content, int(min_frames), int(max_frames), cap, seek, ln, C.byref(n)) != 0:
+        raise ValueError("AX_WHISPER_LongCutPlanHost: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return [(seek[k], ln[k]) for k in range(n.value)]
+
+
+def chunked_segments(ids, timestamp_begin: int, eot: int, seek: int, length: int):
+    """One window's ids (eot excluded) of chunked long-form -> [(start_s, end_s, tok_begin, tok_end)] in FILE time
+    (AX_WHISPER_ChunkedSegments, host only)."""
+    L = load_library()
+    a = np.ascontiguousarray(ids, dtype=np.int32)
+    n_max = len(a) // 2 + 1
+    st, en = np.zeros(n_max, dtype=np.float64), np.zeros(n_max, dtype=np.float64)
+    tb, te = np.zeros(n_max, dtype=np.int32), np.zeros(n_max, dtype=np.int32)
+    n = C.c_int()
+    pi = C.POINTER(C.c_int)
+    if L.AX_WHISPER_ChunkedSegments(a.ctypes.data_as(ip), len(a), int(timestamp_begin), int(eot), int(seek), int(length), n_max,
+                                    st.ctypes.data_as(_dblp), en.ctypes.data_as(_dblp), tb.ctypes.data_as(pi), te.ctypes.data_as(pi), C.byref(n)) != 0:
+        raise RuntimeError("AX_WHISPER_ChunkedSegments failed")
+    return [(float(st[k]), float(en[k]), int(tb[k]), int(te[k])) for k in range(n.value)]
 
 
 def long_window_is_silent(no_speech_logprob: float, avg_logprob: float, no_speech_threshold: float, logprob_threshold: float) -> bool:
@@ -1431,6 +1479,115 @@ class Whisper:
         for seek, wf, _adv, ids, _p, _s in self.run_long_windows([audio], max_new)[0]:
             for s, e, tb, te in split_window(ids, self.timestamp_begin, self.eot, wf)[0]:
                 out.append((seek * 0.01 + s, seek * 0.01 + e, self.transcript(ids[tb:te])))
+        return out
+
+    # ---- chunked long-form: the windows are chosen before decoding (cuts at quiet frames, on the GPU) and decoded side by side
+    def long_frame_levels(self, files, smooth_frames: int = 25):
+        """Whole-file front-end + levels kernel over `files` in one launch -> per file (e, s), float32 [1 + len // 160] each
+        (AX_WHISPER_LongFrameLevels)."""
+        files = [_f32(f) for f in files]
+        n = len(files)
+        ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
+        lens = (C.c_int * n)(*[len(f) for f in files])
+        e = [np.empty(1 + len(f) // 160, dtype=np.float32) for f in files]
+        s = [np.empty(1 + len(f) // 160, dtype=np.float32) for f in files]
+        self._check(self.L.AX_WHISPER_LongFrameLevels(self.h, ptrs, lens, n, int(smooth_frames), (fp * n)(*[x.ctypes.data_as(fp) for x in e]),
+                                                      (fp * n)(*[x.ctypes.data_as(fp) for x in s])), "LongFrameLevels")
+        return list(zip(e, s))
+
+    def long_cut_plan_from_levels(self, s, min_frames: int = 2000, max_frames: int = 3000):
+        """The plan kernel alone on levels s [content] -> [(seek, len)] (AX_WHISPER_LongCutPlanFromLevels)."""
+        a = _f32(s)
+        cap = len(a) // max(int(min_frames), 1) + 2
+        seek, ln, n = (C.c_int * cap)(), (C.c_int * cap)(), C.c_int()
+        self._check(self.L.AX_WHISPER_LongCutPlanFromLevels(self.h, a.ctypes.data_as(fp), len(a), int(min_frames), int(max_frames), cap, seek, ln,
+                                                            C.byref(n)), "LongCutPlanFromLevels")
+        return [(seek[k], ln[k]) for k in range(n.value)]
+
+    def long_cut_plan(self, files, min_frames: int = 2000, max_frames: int = 3000, smooth_frames: int = 25, levels: bool = False):
+        """Front-end + levels + plan of `files` in one call -> per file [(seek, len)]; levels=True: the pair (that, per file the
+        smoothed levels s the plan was made from) (AX_WHISPER_LongCutPlan)."""
+        files = [_f32(f) for f in files]
+        n = len(files)
+        ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
+        lens = (C.c_int * n)(*[len(f) for f in files])
+        cap = sum(len(f) // 160 // max(int(min_frames), 1) + 2 for f in files)
+        chunk = ChunkOptions(int(max_frames), int(min_frames), int(smooth_frames), 1)
+        nw, wf, ws, wl = (C.c_int * n)(), (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
+        s = [np.empty(1 + len(f) // 160, dtype=np.float32) for f in files]
+        self._check(self.L.AX_WHISPER_LongCutPlan(self.h, ptrs, lens, n, C.byref(chunk), cap, nw, wf, ws, wl,
+                                                  (fp * n)(*[x.ctypes.data_as(fp) for x in s]) if levels else None), "LongCutPlan")
+        out, k = [[] for _ in range(n)], 0
+        for f in range(n):
+            for _ in range(nw[f]):
+                assert wf[k] == f
+                out[f].append((ws[k], wl[k]))
+                k += 1
+        return (out, s) if levels else out
+
+    def compute_mel_window_cut(self, pcm, seek: int, length: int) -> np.ndarray:
+        """compute_mel_window for a window of `length` frames: zero from there on (AX_WHISPER_ComputeMelWindowCut)."""
+        a = _f32(pcm)
+        out = np.empty((self.n_mels, 3000), dtype=np.float32)
+        self._check(self.L.AX_WHISPER_ComputeMelWindowCut(self.h, a.ctypes.data_as(fp), len(a), int(seek), int(length), out.ctypes.data_as(fp)),
+                    "ComputeMelWindowCut")
+        return out
+
+    def run_long_chunked_windows(self, files, max_new: int = 0, max_passes: int = 0, min_frames: int = 2000, max_frames: int = 3000,
+                                 smooth_frames: int = 25, no_speech_threshold=None, logprob_threshold=None, scores: bool = False, languages=None,
+                                 tasks=None, beam_size: int = 1, **refused):
+        """Chunked long-form over `files` (AX_WHISPER_RunPCMLongChunkedWindows): per file the list of its windows (seek, window_frames,
+        advance, ids, pass, slot) in order, window_frames = advance = the window's length. With a threshold or scores=True the call is
+        the scored one and every tuple gains (no_speech_logprob, avg_logprob, skipped). languages / tasks: per file, as in
+        run_long_windows ("auto" is refused). refused: the options of run_long_windows this mode does not cover (temperatures,
+        compression_ratio_threshold, initial_prompt_ids, condition_on_previous_text, word_timestamps); the library refuses them."""
+        files = [_f32(f) for f in files]
+        n = len(files)
+        scored = scores or no_speech_threshold is not None or logprob_threshold is not None
+        o, keep, _ = self._long_options(n, no_speech_threshold, logprob_threshold, refused.pop("compression_ratio_threshold", None),
+                                        refused.pop("temperatures", None), 0, None, refused.pop("initial_prompt_ids", None),
+                                        refused.pop("condition_on_previous_text", False), languages, tasks, refused.pop("word_timestamps", False))
+        if refused:
+            raise TypeError("unknown options: " + ", ".join(sorted(refused)))
+        if no_speech_threshold is None and logprob_threshold is None:
+            o.no_speech_threshold = o.logprob_threshold = float("nan")
+        chunk = ChunkOptions(int(max_frames), int(min_frames), int(smooth_frames), int(beam_size))
+        ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
+        lens = (C.c_int * n)(*[len(f) for f in files])
+        cap = sum(len(f) // 160 // max(int(min_frames), 1) + 2 for f in files)
+        info = np.zeros((cap, 7), dtype=np.int32)
+        ids = np.zeros((cap, self.n_text_ctx), dtype=np.int32)
+        sc = np.zeros((cap, 3), dtype=np.float32)
+        nw = C.c_int()
+        self._check(self.L.AX_WHISPER_RunPCMLongChunkedWindows(self.h, ptrs, lens, n, int(max_new), int(max_passes), C.byref(chunk), C.byref(o), cap,
+                                                               info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
+                                                               sc.ctypes.data_as(fp) if scored else None, C.byref(nw)), "RunPCMLongChunkedWindows")
+        out = [[] for _ in range(n)]
+        for k in range(nw.value):
+            f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
+            w = (seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot)
+            if scored:
+                w = w + (float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2]))
+            out[f].append(w)
+        return out
+
+    def run_long_chunked(self, audio, max_new: int = 0, min_frames: int = 2000, max_frames: int = 3000, smooth_frames: int = 25,
+                         no_speech_threshold=None, logprob_threshold=None, language=None, task=None, **refused):
+        """PCM (16 kHz mono f32) or an audio file of any length -> [(start_s, end_s, text)] in file time by chunked long-form: one
+        entry per segment of every window (chunked_segments), without the windows the silent-window rule drops."""
+        if isinstance(audio, (str, os.PathLike)):
+            audio, _, _ = load_audio_file(audio)
+        per_lang = language is not None or task is not None
+        wins = self.run_long_chunked_windows([audio], max_new, 0, min_frames, max_frames, smooth_frames, no_speech_threshold, logprob_threshold,
+                                             languages=[language] if per_lang else None, tasks=[task] if per_lang else None, **refused)[0]
+        out = []
+        for w in wins:
+            seek, wf, _adv, ids = w[:4]
+            if len(w) > 8 and w[8]:
+                continue
+            for s, e, tb, te in chunked_segments(ids, self.timestamp_begin, self.eot, seek, wf):
+                text = self.transcript_lang(ids[tb:te], language) if language not in (None, -1) else self.transcript(ids[tb:te])
+                out.append((s, e, text))
         return out
 
     def run_long_text(self, audio, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None, temperatures=None,

@@ -1654,6 +1654,165 @@ AX_WHISPER_API int AX_WHISPER_LoadAudioFile16k(AX_WHISPER_HANDLE handle, const c
   return 0;
 }
 
+// ---- chunked long-form (DESIGN.md "Chunked long-form"; long_cuts.hpp)
+AX_WHISPER_API int AX_WHISPER_LongCutPlanHost(const float* s, int content, int min_frames, int max_frames, int win_cap, int* seek, int* len,
+                                              int* n_windows) {
+  if (!n_windows || content < 0 || (content > 0 && !s) || win_cap < 0 || (win_cap > 0 && (!seek || !len))) return -1;
+  *n_windows = 0;
+  return guarded_host([&] {
+    const std::vector<axw::CutWindow> plan = axw::cut_plan(s, content, min_frames, max_frames);
+    if ((long)plan.size() > win_cap) throw std::runtime_error(std::to_string(plan.size()) + " windows were planned, win_cap is " + std::to_string(win_cap));
+    for (size_t k = 0; k < plan.size(); ++k) { seek[k] = plan[k].seek; len[k] = plan[k].len; }
+    *n_windows = (int)plan.size();
+    return 0;
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_ChunkedSegments(const int32_t* ids, int n, int timestamp_begin, int eot, int seek, int len, int n_max, double* start,
+                                              double* end, int* tok_begin, int* tok_end, int* n_seg) {
+  if ((n > 0 && !ids) || n < 0 || !n_seg || seek < 0 || len < 0 || len > axw::kCutMaxFrames || n_max < 0 ||
+      (n_max > 0 && (!start || !end || !tok_begin || !tok_end)))
+    return -1;
+  *n_seg = 0;
+  return guarded_host([&] {
+    const std::vector<axw::ChunkSegment> segs = axw::chunked_segments(ids, n, timestamp_begin, eot, seek, len);
+    const int count = (int)std::min<size_t>(segs.size(), (size_t)n_max);
+    for (int k = 0; k < count; ++k) { start[k] = segs[k].start; end[k] = segs[k].end; tok_begin[k] = segs[k].tok_begin; tok_end[k] = segs[k].tok_end; }
+    *n_seg = count;
+    return 0;
+  });
+}
+
+static bool files_ok(const float* const* pcm, const int* num_samples, int n_files) {
+  if (!pcm || !num_samples || n_files < 1) return false;
+  for (int b = 0; b < n_files; ++b)
+    if (!pcm[b] || num_samples[b] < 1) return false;
+  return true;
+}
+
+AX_WHISPER_API int AX_WHISPER_LongFrameLevels(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                              int smooth_frames, float* const* e, float* const* s) {
+  if (!handle || !files_ok(pcm, num_samples, n_files)) return -1;
+  return guarded(handle, [&](Engine& en) { en.long_frame_levels(pcm, num_samples, n_files, smooth_frames, e, s); });
+}
+
+AX_WHISPER_API int AX_WHISPER_LongCutPlanFromLevels(AX_WHISPER_HANDLE handle, const float* s, int content, int min_frames, int max_frames,
+                                                    int win_cap, int* seek, int* len, int* n_windows) {
+  if (!handle || !s || content < 1 || !n_windows || win_cap < 0 || (win_cap > 0 && (!seek || !len))) return -1;
+  *n_windows = 0;
+  return guarded(handle, [&](Engine& e) {
+    std::vector<axw::CutWindow> plan;
+    e.long_cut_plan_from_levels(s, content, min_frames, max_frames, plan);
+    if ((long)plan.size() > win_cap) throw std::runtime_error(std::to_string(plan.size()) + " windows were planned, win_cap is " + std::to_string(win_cap));
+    for (size_t k = 0; k < plan.size(); ++k) { seek[k] = plan[k].seek; len[k] = plan[k].len; }
+    *n_windows = (int)plan.size();
+  });
+}
+
+static axw::CutParams cut_params(const AX_WHISPER_CHUNK_OPTIONS* c) {
+  axw::CutParams p;
+  if (c) { p.w_max = c->max_frames; p.w_min = c->min_frames; p.smooth = c->smooth_frames; }
+  return p;
+}
+
+AX_WHISPER_API int AX_WHISPER_LongCutPlan(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                          const AX_WHISPER_CHUNK_OPTIONS* chunk, int win_cap, int* n_windows, int* win_file, int* win_seek,
+                                          int* win_len, float* const* s) {
+  if (!handle || !files_ok(pcm, num_samples, n_files) || !n_windows || win_cap < 0 || (win_cap > 0 && (!win_file || !win_seek || !win_len))) return -1;
+  return guarded(handle, [&](Engine& e) {
+    std::vector<int> n, wf, ws, wl;
+    e.long_cut_plan(pcm, num_samples, n_files, cut_params(chunk), n, wf, ws, wl, s);
+    if ((long)wf.size() > win_cap) throw std::runtime_error(std::to_string(wf.size()) + " windows were planned, win_cap is " + std::to_string(win_cap));
+    std::copy(n.begin(), n.end(), n_windows);
+    std::copy(wf.begin(), wf.end(), win_file);
+    std::copy(ws.begin(), ws.end(), win_seek);
+    std::copy(wl.begin(), wl.end(), win_len);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_ComputeMelWindowCut(AX_WHISPER_HANDLE handle, const float* pcm, int num_samples, int seek, int len, float* mel_out) {
+  if (!handle || !pcm || !mel_out || num_samples < 1 || seek < 0) return -1;
+  return guarded(handle, [&](Engine& e) { e.compute_mel_window_cut(pcm, num_samples, seek, len, mel_out); });
+}
+
+// AX_WHISPER_CHUNK_OPTIONS + AX_WHISPER_LONG_OPTIONS -> ChunkedOptions; what the mode does not cover travels along and is refused by the
+// engine with its text (longform.hpp: chunked_options_error)
+static axw::ChunkedOptions chunked_options(const AX_WHISPER_CHUNK_OPTIONS* chunk, const AX_WHISPER_LONG_OPTIONS* o, int n_files, bool want_scores) {
+  axw::ChunkedOptions c;
+  c.cut = cut_params(chunk);
+  c.beam_size = chunk ? chunk->beam_size : 1;
+  c.scored = want_scores;
+  if (!o) return c;
+  c.no_speech_threshold = o->no_speech_threshold; c.logprob_threshold = o->logprob_threshold;
+  if (!std::isnan(o->no_speech_threshold) || !std::isnan(o->logprob_threshold)) c.scored = true;
+  if (o->lang) c.file_lang.assign(o->lang, o->lang + n_files);
+  if (o->task) c.file_task.assign(o->task, o->task + n_files);
+  c.n_temperatures = o->temperatures ? std::max(o->n_temperatures, 0) : 0;
+  c.compression_ratio_threshold = !std::isnan(o->compression_ratio_threshold);
+  for (int f = 0; o->initial_prompt_ids && o->n_initial && f < n_files; ++f)
+    if (o->n_initial[f] > 0) c.initial_prompt = true;
+  c.condition_on_previous_text = o->condition_on_previous_text != 0;
+  c.word_timestamps = o->word_timestamps != 0;
+  return c;
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongChunkedWindows(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
+                                                       int max_new, int max_passes, const AX_WHISPER_CHUNK_OPTIONS* chunk,
+                                                       const AX_WHISPER_LONG_OPTIONS* o, int win_cap, int* win_info, int32_t* ids,
+                                                       float* win_score, int* n_windows) {
+  if (!handle || !files_ok(pcm, num_samples, n_files) || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids))) return -1;
+  *n_windows = 0;
+  const axw::ChunkedOptions opts = chunked_options(chunk, o, n_files, win_score != nullptr);
+  if (opts.scored && win_cap > 0 && !win_score) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    std::vector<axw::LongWindow> log;
+    g.run_long_chunked(pcm, num_samples, n_files, max_new, max_passes, opts, log);
+    if ((long)log.size() > win_cap)  // nothing is written unless everything fits
+      throw std::runtime_error("RunPCMLongChunkedWindows: " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
+    const int Tc = g.primary().config().n_text_ctx;
+    for (size_t k = 0; k < log.size(); ++k) {
+      const axw::LongWindow& w = log[k];
+      const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
+      memcpy(win_info + k * 7, row, sizeof row);
+      memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
+      if (opts.scored) { win_score[k * 3] = w.no_speech_logprob; win_score[k * 3 + 1] = w.avg_logprob; win_score[k * 3 + 2] = w.skipped ? 1.f : 0.f; }
+    }
+    *n_windows = (int)log.size();
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunPCMLongChunked(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const AX_WHISPER_CHUNK_OPTIONS* chunk,
+                                                const AX_WHISPER_LONG_OPTIONS* o, char** result) {
+  if (!handle || !pcm_data || !result || num_samples < 1) return -1;
+  *result = nullptr;
+  const axw::ChunkedOptions opts = chunked_options(chunk, o, 1, false);
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    Engine& e = g.primary();
+    std::vector<axw::LongWindow> log;
+    const float* files[1] = {pcm_data};
+    g.run_long_chunked(files, &num_samples, 1, 0, 0, opts, log);
+    const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
+    const bool lang = !opts.file_lang.empty() && opts.file_lang[0] >= 0;
+    std::string text;
+    for (const axw::LongWindow& w : log) {
+      if (w.skipped) continue;
+      for (const axw::ChunkSegment& sg : axw::chunked_segments(w.ids.data(), (int)w.ids.size(), T, E, w.seek, w.window_frames))  // host only
+        text += lang ? e.transcript_lang(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin, opts.file_lang[0])
+                     : e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);
+    }
+    *result = strdup(text.c_str());
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_RunFileLongChunked(AX_WHISPER_HANDLE handle, const char* wav_file, const AX_WHISPER_CHUNK_OPTIONS* chunk,
+                                                 const AX_WHISPER_LONG_OPTIONS* o, char** result) {
+  if (!handle || !wav_file || !result) return -1;
+  *result = nullptr;
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return AX_WHISPER_RunPCMLongChunked(handle, wav.mono.data(), (int)wav.mono.size(), chunk, o, result);
+}
+
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5) {
   if (!handle || !out5) return -1;
   return guarded(handle, [&](Engine& e) { memcpy(out5, e.timings, sizeof(float) * 5); });

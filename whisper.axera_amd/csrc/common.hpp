@@ -301,6 +301,38 @@ struct MelWindowParams {
 };
 void launch_mel_window(const MelWindowParams& p, hipStream_t s);
 
+// ------------------------------------------------------------------ chunked long-form (long_cuts.hip; long_cuts.hpp: the definitions)
+constexpr int kLevelTile = 256;  // frames of one file per workgroup of the levels kernel; its LDS holds the tile + 64 frames each side
+// One launch over a ragged batch of files: e[f] = mean over the mels of what the encoder will see of store row f, s[f] = the mean of
+// e over [f - R, f + R] with the index clamped to the file. Both are written at frame_off[file] + f, as the store's rows are.
+struct LongLevelsParams {
+  const float* store;
+  const long long* frame_off;  // device [n_files]
+  const int* n_frames;         // device [n_files]
+  const unsigned* gmax;        // device [n_files] (ordered-int encoded)
+  float* s;                    // device [sum of n_frames]
+  float* e;                    // device [sum of n_frames] or nullptr
+  int n_mels, n_files, smooth; // smooth = R, 0 .. 64; n_mels a multiple of 8
+  int max_frames;              // frames of the longest file (grid.x = its tiles)
+};
+void launch_long_levels(const LongLevelsParams& p, hipStream_t s);
+// The cut rule on the device, one workgroup per file, then the compaction into the flat order file-then-seek. File b's windows are
+// first written to seg_seek / seg_len [seg_off[b] ...) (room for cut_plan_capacity of them), its count to n_windows[b]; the second
+// kernel moves them to win_file / win_seek / win_len [sum of the counts], which mel_window_cut_kernel reads.
+struct LongCutPlanParams {
+  const float* s;              // device: the smoothed levels, file b's at frame_off[b] ...
+  const long long* frame_off;  // device [n_files]
+  const int* n_samples;        // device [n_files]: content = n_samples / 160
+  const int* seg_off;          // device [n_files + 1]: file b's room is seg_off[b + 1] - seg_off[b] windows
+  int *seg_seek, *seg_len;     // device [seg_off[n_files]]
+  int* n_windows;              // device [n_files]
+  int *win_file, *win_seek, *win_len;  // device [seg_off[n_files]]
+  int n_files, w_min, w_max;
+};
+void launch_long_cut_plan(const LongCutPlanParams& p, hipStream_t s);
+// launch_mel_window for windows that end at a cut: window a holds win_len[a] frames, zero from there on
+void launch_mel_window_cut(const MelWindowParams& p, const int* win_len, hipStream_t s);
+
 // ------------------------------------------------------------------ sample-rate conversion (resample.hip; DESIGN.md "Sample rates")
 // One launch over a ragged batch of clips, each at its own rate: y_j = sum over i < 2 K of x[i0 + i - K + 1] H[r][i] with
 // i0 = floor(j M / L), r = (j M) mod L, x zero outside the clip (resample.hpp: the definition and the table H [L][2 K]).

@@ -54,6 +54,16 @@ struct LongArena {
   int *n_samples = nullptr, *n_frames = nullptr, *win_file = nullptr, *win_seek = nullptr;
   unsigned* gmax = nullptr;
   int n_files = 0, n_windows = 0;
+  // chunked calls only (long_prepare with cut parameters; else null): the smoothed and the frame levels [frames of all files], every
+  // file's room in the per-file window lists, those lists, and the plan block the host fetches in one copy:
+  // [n_windows per file | win_file | win_seek | win_len], the last three [plan_cap] in the flat order file-then-seek
+  float *levels = nullptr, *levels_e = nullptr;
+  int *seg_off = nullptr, *seg_seek = nullptr, *seg_len = nullptr, *plan = nullptr;
+  int plan_cap = 0, max_frames = 0;
+  int* plan_n() const { return plan; }
+  int* plan_file() const { return plan + n_files; }
+  int* plan_seek() const { return plan + n_files + plan_cap; }
+  int* plan_len() const { return plan + n_files + 2 * (size_t)plan_cap; }
 };
 
 struct EngineMemory {
@@ -181,6 +191,13 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) override;
   void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                         const LongScoreOptions* opts, std::vector<LongWindow>& log) override;
+  void run_long_chunked(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const ChunkedOptions& opts,
+                        std::vector<LongWindow>& log) override;
+  void long_frame_levels(const float* const* pcm, const int* n_samples, int n_files, int smooth, float* const* e, float* const* s) override;
+  void long_cut_plan(const float* const* pcm, const int* n_samples, int n_files, const CutParams& cut, std::vector<int>& n_windows,
+                     std::vector<int>& win_file, std::vector<int>& win_seek, std::vector<int>& win_len, float* const* s_out) override;
+  void long_cut_plan_from_levels(const float* s, int content, int w_min, int w_max, std::vector<CutWindow>& plan) override;
+  void compute_mel_window_cut(const float* pcm, int n_samples, int seek, int len, float* mel_out) override;
   int scan_stored16(int batch, int n_max, char (*names)[32], long long* nonfinite, float* maxabs) override;
   float bench(const std::string& what, int batch, int arg, int iters) override;
   void set_stream(void* s) override { user_stream_ = static_cast<hipStream_t>(s); }
@@ -274,7 +291,12 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void fetch_scores(int batch, const int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
   void recover_streams();
   // long-form (engine_long.cpp)
-  void long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows);  // upload + whole-file front-end
+  // upload + whole-file front-end; cut (chunked calls): also room for the levels (want_e: both of them) and the cut plan
+  void long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows, const CutParams* cut = nullptr, bool want_e = false);
+  void long_plan(const CutParams& cut);  // levels kernel + plan kernels over the prepared files
+  // the plan block in one copy -> windows per file and the flat lists; returns the number of windows
+  int long_fetch_plan(std::vector<int>& n_windows, std::vector<int>& win_file, std::vector<int>& win_seek, std::vector<int>& win_len);
+  void long_cut_windows_to_slots(int first, int count, bool want_ref_layout);  // windows [first, first + count) of the plan -> slots 0 ..
   void long_windows_to_slots(const int* files, const int* seeks, int count, bool want_ref_layout);
   void long_release();
   // ctx: what the clips decode behind (prefill_prompts after reset_decode_state); an empty one: nothing in front of the start sequence
@@ -423,6 +445,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   float bench_encoder(int batch, int iters);
   float bench_frontend(int batch, int iters);
   float bench_frontend_long(int batch, int arg, int iters);
+  float bench_long_cut_plan(int batch, int arg, int iters);
   float bench_prefill(const std::string& what, int batch, int arg, int iters);
   float bench_detect_language(int batch, int arg, int iters);
 };

@@ -104,6 +104,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "frontend") return bench_frontend(batch, iters);
   if (what == "resample") return bench_resample(batch, arg, iters);
   if (what == "frontend_long") return bench_frontend_long(batch, arg, iters);
+  if (what == "long_cut_plan") return bench_long_cut_plan(batch, arg, iters);
   if (what == "prefill" || what == "prefill_pass" || what == "prefill_step") return bench_prefill(what, batch, arg, iters);
   if (what == "detect_language") return bench_detect_language(batch, arg, iters);
   if (what == "word_align" || what == "word_align_host") return bench_word_align(what, batch, arg, iters);
@@ -436,6 +437,22 @@ float Engine::bench_frontend_long(int batch, int arg, int iters) {
       long_windows_to_slots(files.data(), seeks.data(), batch, false);
     }
   });
+  long_release();
+  return ms;
+}
+
+// chunked long-form: levels kernel + plan kernels over `batch` resident files of `arg` seconds, default parameters. The files are a
+// ramp (silence would make every level equal), so the scans meet distinct values; what is timed does not depend on them.
+float Engine::bench_long_cut_plan(int batch, int arg, int iters) {
+  if (arg < 1 || arg > 33554) throw std::runtime_error("bench long_cut_plan: arg = seconds of audio per file, 1 .. 33554");
+  std::vector<int> ns(batch, arg * 16000);
+  std::vector<float> ramp((size_t)arg * 16000);
+  for (size_t i = 0; i < ramp.size(); ++i) ramp[i] = 0.5f * std::sin(0.05f * (float)(i % 40000)) * (float)(1 + i % 7919) / 7919.f;
+  std::vector<const float*> files(batch, ramp.data());
+  const CutParams cut;
+  long_prepare(files.data(), ns.data(), batch, 1, &cut, false);
+  long_plan(cut);  // warm
+  const float ms = timed_ms(stream(), [&] { for (int i = 0; i < iters; ++i) long_plan(cut); });
   long_release();
   return ms;
 }

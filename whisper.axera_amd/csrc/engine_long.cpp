@@ -23,7 +23,7 @@ void Engine::long_release() {
 }
 
 // pcm == nullptr: n_files files of silence (bench)
-void Engine::long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows) {
+void Engine::long_prepare(const float* const* pcm, const int* n_samples, int n_files, int n_windows, const CutParams* cut, bool want_e) {
   if (feature_openai_)
     throw std::runtime_error("long-form needs the default front-end: AX_WHISPER_FEATURE_MODE=openai trims the input to 30 s before the STFT");
   if (cfg_.n_mels % 8 != 0) throw std::runtime_error("long-form needs n_mels to be a multiple of 8");
@@ -47,7 +47,16 @@ void Engine::long_prepare(const float* const* pcm, const int* n_samples, int n_f
     frames += (size_t)nf[b];
     max_frames = std::max(max_frames, nf[b]);
   }
-  // arena: [pcm | store | pcm_off | frame_off | n_samples | n_frames | gmax | win_file | win_seek], pieces 256-byte aligned
+  // chunked calls: every file's room in the window lists (long_cuts.hpp: at most ceil(content / W_min) + 1 windows)
+  std::vector<int> seg_off(cut ? n_files + 1 : 0, 0);
+  for (int b = 0; cut && b < n_files; ++b) {
+    const long room = (long)seg_off[b] + std::max(1, cut_plan_capacity(n_samples[b] / kHop, cut->w_min));  // (at least one: the stage-level window call)
+    if (room > (1L << 28)) throw std::runtime_error("chunked long-form: more than 2^28 windows");
+    seg_off[b + 1] = (int)room;
+  }
+  const size_t plan_cap = cut ? (size_t)seg_off[n_files] : 0;
+  // arena: [pcm | store | pcm_off | frame_off | n_samples | n_frames | gmax | win_file | win_seek], pieces 256-byte aligned;
+  // chunked calls add [levels | frame levels | seg_off | seg_seek | seg_len | plan block]
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t o = 0;
   const size_t o_pcm = o; o += up(samples * 4);
@@ -59,6 +68,12 @@ void Engine::long_prepare(const float* const* pcm, const int* n_samples, int n_f
   const size_t o_gmax = o; o += up((size_t)n_files * 4);
   const size_t o_wf = o; o += up((size_t)n_windows * 4);
   const size_t o_ws = o; o += up((size_t)n_windows * 4);
+  const size_t o_lev = o; o += cut ? up(frames * 4) : 0;
+  const size_t o_leve = o; o += cut && want_e ? up(frames * 4) : 0;
+  const size_t o_so = o; o += cut ? up((size_t)(n_files + 1) * 4) : 0;
+  const size_t o_ss = o; o += up(plan_cap * 4);
+  const size_t o_sl = o; o += up(plan_cap * 4);
+  const size_t o_plan = o; o += cut ? up(((size_t)n_files + 3 * plan_cap) * 4) : 0;
   if (o > long_max_bytes())
     throw std::runtime_error("long-form: the PCM and log-mel stores of this call need " + std::to_string(o) + " bytes, the cap is " +
                              std::to_string(long_max_bytes()) + " (AX_WHISPER_LONG_MAX_BYTES)");
@@ -81,6 +96,10 @@ void Engine::long_prepare(const float* const* pcm, const int* n_samples, int n_f
   long_.n_samples = (int*)(a + o_ns); long_.n_frames = (int*)(a + o_nf); long_.gmax = (unsigned*)(a + o_gmax);
   long_.win_file = (int*)(a + o_wf); long_.win_seek = (int*)(a + o_ws);
   long_.n_files = n_files; long_.n_windows = n_windows;
+  long_.levels = cut ? (float*)(a + o_lev) : nullptr; long_.levels_e = cut && want_e ? (float*)(a + o_leve) : nullptr;
+  long_.seg_off = cut ? (int*)(a + o_so) : nullptr; long_.seg_seek = cut ? (int*)(a + o_ss) : nullptr; long_.seg_len = cut ? (int*)(a + o_sl) : nullptr;
+  long_.plan = cut ? (int*)(a + o_plan) : nullptr; long_.plan_cap = (int)plan_cap; long_.max_frames = max_frames;
+  if (cut) HIP_CHECK(hipMemcpy(long_.seg_off, seg_off.data(), (size_t)(n_files + 1) * 4, hipMemcpyHostToDevice));
   for (int b = 0; b < n_files; ++b) {
     if (pcm) HIP_CHECK(hipMemcpy(long_.pcm + pcm_off[b], pcm[b], (size_t)n_samples[b] * 4, hipMemcpyHostToDevice));
     else HIP_CHECK(hipMemset(long_.pcm + pcm_off[b], 0, (size_t)n_samples[b] * 4));
@@ -355,6 +374,245 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   HIP_CHECK(hipEventSynchronize(ev_[3]));
   (void)hipEventElapsedTime(&timings[0], ev_[0], ev_[1]);  // upload + whole-file front-end
   timings[1] = 0.f;                                        // (encoder and decode loop alternate: both are in [2])
+  (void)hipEventElapsedTime(&timings[2], ev_[1], ev_[3]);
+  timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  timings[4] = (float)steps;
+  long_release();
+}
+
+// ------------------------------------------------------------------------------ chunked long-form (DESIGN.md "Chunked long-form")
+// levels kernel + plan kernels over the files long_prepare left in the arena (prepared with cut parameters)
+void Engine::long_plan(const CutParams& cut) {
+  LongLevelsParams lv{};
+  lv.store = long_.store; lv.frame_off = long_.frame_off; lv.n_frames = long_.n_frames; lv.gmax = long_.gmax;
+  lv.s = long_.levels; lv.e = long_.levels_e;
+  lv.n_mels = cfg_.n_mels; lv.n_files = long_.n_files; lv.smooth = cut.smooth; lv.max_frames = long_.max_frames;
+  launch_long_levels(lv, stream());
+  LongCutPlanParams pl{};
+  pl.s = long_.levels; pl.frame_off = long_.frame_off; pl.n_samples = long_.n_samples; pl.seg_off = long_.seg_off;
+  pl.seg_seek = long_.seg_seek; pl.seg_len = long_.seg_len;
+  pl.n_windows = long_.plan_n(); pl.win_file = long_.plan_file(); pl.win_seek = long_.plan_seek(); pl.win_len = long_.plan_len();
+  pl.n_files = long_.n_files; pl.w_min = cut.w_min; pl.w_max = cut.w_max;
+  launch_long_cut_plan(pl, stream());
+}
+
+int Engine::long_fetch_plan(std::vector<int>& n_windows, std::vector<int>& win_file, std::vector<int>& win_seek, std::vector<int>& win_len) {
+  const size_t nf = (size_t)long_.n_files, cap = (size_t)long_.plan_cap;
+  std::vector<int> block(nf + 3 * cap);
+  HIP_CHECK(hipMemcpyAsync(block.data(), long_.plan, block.size() * 4, hipMemcpyDeviceToHost, stream()));
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  n_windows.assign(block.begin(), block.begin() + nf);
+  long total = 0;
+  for (int n : n_windows) {
+    if (n < 0) throw std::runtime_error("chunked long-form: bad plan");
+    total += n;
+  }
+  if (total > (long)cap) throw std::runtime_error("chunked long-form: bad plan");
+  win_file.assign(block.begin() + nf, block.begin() + nf + total);
+  win_seek.assign(block.begin() + nf + cap, block.begin() + nf + cap + total);
+  win_len.assign(block.begin() + nf + 2 * cap, block.begin() + nf + 2 * cap + total);
+  return (int)total;
+}
+
+// windows [first, first + count) of the plan -> encoder slots 0 .. count - 1: the kernel reads the plan's own lists
+void Engine::long_cut_windows_to_slots(int first, int count, bool want_ref_layout) {
+  if (count < 1 || count > cap_ || first < 0 || first + count > long_.plan_cap) throw std::runtime_error("chunked long-form: bad window range");
+  MelWindowParams w{};
+  w.store = long_.store; w.frame_off = long_.frame_off; w.n_frames = long_.n_frames; w.gmax = long_.gmax;
+  w.win_file = long_.plan_file() + first; w.win_seek = long_.plan_seek() + first;
+  w.mel_tm = d_mel_tm_; w.mel_ref = want_ref_layout ? d_mel_ref_ : nullptr;
+  w.mel_rows = mel_rows_; w.n_mels = cfg_.n_mels; w.n_windows = count;
+  launch_mel_window_cut(w, long_.plan_len() + first, stream());
+}
+
+static void check_cut(const CutParams& cut) {
+  const std::string bad = cut_params_error(cut.w_min, cut.w_max, cut.smooth);
+  if (!bad.empty()) throw std::runtime_error(bad);
+}
+
+void Engine::long_frame_levels(const float* const* pcm, const int* n_samples, int n_files, int smooth, float* const* e, float* const* s) {
+  require_no_stream("long_frame_levels");
+  if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
+  CutParams cut;
+  cut.smooth = smooth;
+  check_cut(cut);
+  HIP_CHECK(hipSetDevice(device_));
+  long_prepare(pcm, n_samples, n_files, 1, &cut, true);
+  long_plan(cut);
+  size_t off = 0;
+  for (int b = 0; b < n_files; ++b) {
+    const size_t nf = 1 + (size_t)n_samples[b] / kHop;
+    if (e && e[b]) HIP_CHECK(hipMemcpyAsync(e[b], long_.levels_e + off, nf * 4, hipMemcpyDeviceToHost, stream()));
+    if (s && s[b]) HIP_CHECK(hipMemcpyAsync(s[b], long_.levels + off, nf * 4, hipMemcpyDeviceToHost, stream()));
+    off += nf;
+  }
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  long_release();
+}
+
+void Engine::long_cut_plan(const float* const* pcm, const int* n_samples, int n_files, const CutParams& cut, std::vector<int>& n_windows,
+                           std::vector<int>& win_file, std::vector<int>& win_seek, std::vector<int>& win_len, float* const* s_out) {
+  require_no_stream("long_cut_plan");
+  if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
+  check_cut(cut);
+  HIP_CHECK(hipSetDevice(device_));
+  long_prepare(pcm, n_samples, n_files, 1, &cut, false);
+  long_plan(cut);
+  size_t off = 0;
+  for (int b = 0; b < n_files; ++b) {
+    const size_t nf = 1 + (size_t)n_samples[b] / kHop;
+    if (s_out && s_out[b]) HIP_CHECK(hipMemcpyAsync(s_out[b], long_.levels + off, nf * 4, hipMemcpyDeviceToHost, stream()));
+    off += nf;
+  }
+  long_fetch_plan(n_windows, win_file, win_seek, win_len);
+  long_release();
+}
+
+// the plan kernels alone: the caller's levels take the place of a one-file arena
+void Engine::long_cut_plan_from_levels(const float* s, int content, int w_min, int w_max, std::vector<CutWindow>& plan) {
+  require_no_stream("long_cut_plan_from_levels");
+  CutParams cut;
+  cut.w_min = w_min; cut.w_max = w_max; cut.smooth = 0;
+  check_cut(cut);
+  if (content < 1 || content > (1 << 29) / kHop) throw std::runtime_error("long_cut_plan_from_levels: content must be 1 .. 2^29 / 160 frames");
+  for (int f = 0; f < content; ++f)
+    if (!std::isfinite(s[f])) throw std::runtime_error("chunked long-form: level " + std::to_string(f) + " is not finite");
+  HIP_CHECK(hipSetDevice(device_));
+  const int cap = cut_plan_capacity(content, w_min);
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // [levels | frame_off (8) | n_samples | seg_off (2) | seg_seek | seg_len | plan block (1 + 3 cap)]
+  size_t o = 0;
+  const size_t o_lev = o; o += up((size_t)content * 4);
+  const size_t o_foff = o; o += up(8);
+  const size_t o_ns = o; o += up(4);
+  const size_t o_so = o; o += up(8);
+  const size_t o_ss = o; o += up((size_t)cap * 4);
+  const size_t o_sl = o; o += up((size_t)cap * 4);
+  const size_t o_plan = o; o += up(((size_t)1 + 3 * (size_t)cap) * 4);
+  std::vector<int> block((size_t)1 + 3 * (size_t)cap);
+  {
+    std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    DeviceArray<char> mem = device_array<char>(o);
+    char* a = mem;
+    const long long zero = 0;
+    const int ns = content * kHop, so[2] = {0, cap};
+    HIP_CHECK(hipMemcpy(a + o_lev, s, (size_t)content * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(a + o_foff, &zero, 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(a + o_ns, &ns, 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(a + o_so, so, 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipDeviceSynchronize());  // (the engine's streams are not ordered against the null stream)
+    LongCutPlanParams pl{};
+    pl.s = (const float*)(a + o_lev); pl.frame_off = (const long long*)(a + o_foff); pl.n_samples = (const int*)(a + o_ns);
+    pl.seg_off = (const int*)(a + o_so); pl.seg_seek = (int*)(a + o_ss); pl.seg_len = (int*)(a + o_sl);
+    int* plan_dev = (int*)(a + o_plan);
+    pl.n_windows = plan_dev; pl.win_file = plan_dev + 1; pl.win_seek = plan_dev + 1 + cap; pl.win_len = plan_dev + 1 + 2 * (size_t)cap;
+    pl.n_files = 1; pl.w_min = w_min; pl.w_max = w_max;
+    launch_long_cut_plan(pl, stream());
+    HIP_CHECK(hipMemcpyAsync(block.data(), plan_dev, block.size() * 4, hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+  }
+  const int n = block[0];
+  if (n < 0 || n > cap) throw std::runtime_error("chunked long-form: bad plan");
+  plan.clear();
+  for (int k = 0; k < n; ++k) plan.push_back({block[(size_t)1 + cap + k], block[(size_t)1 + 2 * (size_t)cap + k]});
+}
+
+void Engine::compute_mel_window_cut(const float* pcm, int n_samples, int seek, int len, float* mel_out) {
+  require_no_stream("compute_mel_window_cut");
+  if (seek < 0) throw std::runtime_error("compute_mel_window_cut: negative seek");
+  if (len < 0 || len > kFramesOut) throw std::runtime_error("compute_mel_window_cut: len must be 0 .. 3000");
+  HIP_CHECK(hipSetDevice(device_));
+  ensure_capacity(1);
+  const float* arr[1] = {pcm};
+  // a one-window plan written by the host where the plan kernels would write it: the arena of a chunked call with the fewest
+  // windows of room a file can have (W_min = W_max = 3000; long_prepare gives every file at least one)
+  CutParams cut;
+  cut.w_min = cut.w_max = kCutMaxFrames;
+  long_prepare(arr, &n_samples, 1, 1, &cut, false);
+  if (long_.plan_cap < 1) throw std::runtime_error("compute_mel_window_cut: the file holds no frame of audio");
+  const int file = 0;
+  hipStream_t s = stream();
+  HIP_CHECK(hipMemcpyAsync(long_.plan_file(), &file, 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(long_.plan_seek(), &seek, 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(long_.plan_len(), &len, 4, hipMemcpyHostToDevice, s));
+  long_cut_windows_to_slots(0, 1, true);
+  HIP_CHECK(hipMemcpyAsync(mel_out, d_mel_ref_, (size_t)cfg_.n_mels * kFramesOut * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  long_release();
+}
+
+// The passes: windows [base, base + A) of the flat plan -> slots 0 .. A - 1 -> encoder -> timestamp-mode decode -> ids to the host.
+// No window waits for another one's result, so a pass is full whenever enough windows are left, whichever files they belong to.
+void Engine::run_long_chunked(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const ChunkedOptions& opts,
+                              std::vector<LongWindow>& log) {
+  if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
+  require_no_stream("run_long_chunked");
+  if (feature_openai_)
+    throw std::runtime_error("chunked long-form needs the default front-end: AX_WHISPER_FEATURE_MODE=openai trims the input to 30 s before the STFT");
+  {
+    const std::string bad = chunked_options_error(opts, opts.file_base + n_files);
+    if (!bad.empty()) throw std::runtime_error(bad);
+  }
+  require_timestamp_vocab();
+  if (opts.scored) require_scored_vocab();
+  const bool per_lang = !opts.file_lang.empty() || !opts.file_task.empty();
+  const StepSpec spec{opts.scored ? kDecodeScored : kDecodeTimestamps};
+  std::vector<int> file_lang(per_lang ? n_files : 0, -1), file_task(per_lang ? n_files : 0, 0);
+  if (per_lang) {
+    for (int f = 0; f < n_files; ++f) {
+      if (!opts.file_lang.empty()) file_lang[f] = opts.file_lang[(size_t)(opts.file_base + f)];
+      if (!opts.file_task.empty()) file_task[f] = opts.file_task[(size_t)(opts.file_base + f)];
+    }
+    check_contexts(spec.mode, ClipContexts{std::nullopt, LangSpec{file_lang.data(), file_task.data()}}, n_files, false, "run_long_chunked");
+    for (int f = 0; f < n_files; ++f)
+      if (file_lang[f] == -1) file_lang[f] = handle_lang_;
+  }
+  HIP_CHECK(hipSetDevice(device_));
+  auto t0 = std::chrono::steady_clock::now();
+  hipStream_t s = stream();
+  HIP_CHECK(hipEventRecord(ev_[0], s));
+  long_prepare(pcm, n_samples, n_files, 1, &opts.cut, false);
+  long_plan(opts.cut);
+  std::vector<int> n_windows, win_file, win_seek, win_len;
+  const int total = long_fetch_plan(n_windows, win_file, win_seek, win_len);  // the one copy of the plan: counts and times
+  HIP_CHECK(hipEventRecord(ev_[1], s));
+  // windows per pass: the engine's capacity, as in the seek loop
+  const int S = std::max(1, std::min(total, std::max(cap_, 1)));
+  ensure_capacity(S);
+  const int Tc = cfg_.n_text_ctx;
+  std::vector<int> n_ids(S), win_lang(per_lang ? S : 0), win_task(per_lang ? S : 0);
+  std::vector<int32_t> ids((size_t)S * Tc);
+  std::vector<float> avg(S), nsp(S);
+  ClipContexts ctx;
+  if (per_lang) ctx.lang = LangSpec{win_lang.data(), win_task.data()};
+  int steps = 0, pass = 0;
+  for (int base = 0; base < total && (max_passes <= 0 || pass < max_passes); ++pass) {
+    const int A = std::min(S, total - base);
+    long_cut_windows_to_slots(base, A, false);
+    run_encoder(A);
+    for (int i = 0; per_lang && i < A; ++i) { win_lang[i] = file_lang[win_file[base + i]]; win_task[i] = file_task[win_file[base + i]]; }
+    steps += greedy_loop(spec, A, max_new, nullptr, ctx);
+    fetch_ids(A, ids.data(), n_ids.data());
+    if (opts.scored) fetch_scores(A, n_ids.data(), nullptr, avg.data(), nsp.data(), nullptr);
+    for (int i = 0; i < A; ++i) {
+      LongWindow w;
+      w.file = win_file[base + i]; w.seek = win_seek[base + i]; w.window_frames = w.advance = win_len[base + i];
+      w.pass = pass; w.slot = i;
+      const int n = std::max(0, std::min(n_ids[i], Tc));
+      w.ids.assign(ids.begin() + (size_t)i * Tc, ids.begin() + (size_t)i * Tc + n);
+      if (opts.scored) {
+        w.no_speech_logprob = nsp[i]; w.avg_logprob = avg[i];
+        w.skipped = long_window_is_silent(nsp[i], avg[i], opts.no_speech_threshold, opts.logprob_threshold);
+      }
+      log.push_back(std::move(w));
+    }
+    base += A;
+  }
+  HIP_CHECK(hipEventRecord(ev_[3], s));
+  HIP_CHECK(hipEventSynchronize(ev_[3]));
+  (void)hipEventElapsedTime(&timings[0], ev_[0], ev_[1]);  // upload + whole-file front-end + levels + plan
+  timings[1] = 0.f;
   (void)hipEventElapsedTime(&timings[2], ev_[1], ev_[3]);
   timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   timings[4] = (float)steps;

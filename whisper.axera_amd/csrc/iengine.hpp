@@ -219,6 +219,20 @@ class IEngine {
   // opts (null: the unscored loop): the scores of every window in the log; the silent-window rule under opts' thresholds
   virtual void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
                                 const LongScoreOptions* opts, std::vector<LongWindow>& log) = 0;
+  // chunked long-form (DESIGN.md "Chunked long-form"; long_cuts.hpp): the cut points are chosen before decoding (levels kernel + plan
+  // kernel on the files' log-mel store), then the windows are decoded min(slots, remaining) at a time in the flat order
+  // file-then-seek. One log entry per window: window_frames = advance = the window's length.
+  virtual void run_long_chunked(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const ChunkedOptions& opts,
+                                std::vector<LongWindow>& log) = 0;
+  // stage level: e and s of every file, host [n_files][1 + n_samples / 160] (either may be null)
+  virtual void long_frame_levels(const float* const* pcm, const int* n_samples, int n_files, int smooth, float* const* e, float* const* s) = 0;
+  // stage level: front-end + levels + plan; the flat lists and, when s_out is not null, the levels the plan was made from
+  virtual void long_cut_plan(const float* const* pcm, const int* n_samples, int n_files, const CutParams& cut, std::vector<int>& n_windows,
+                             std::vector<int>& win_file, std::vector<int>& win_seek, std::vector<int>& win_len, float* const* s_out) = 0;
+  // stage level: the plan kernel alone on a caller's levels s [content]
+  virtual void long_cut_plan_from_levels(const float* s, int content, int w_min, int w_max, std::vector<CutWindow>& plan) = 0;
+  // stage level: compute_mel_window for a window of `len` frames
+  virtual void compute_mel_window_cut(const float* pcm, int n_samples, int seek, int len, float* mel_out) = 0;
   virtual float bench(const std::string& what, int batch, int arg, int iters) = 0;
   virtual void set_stream(void* hip_stream) = 0;
   virtual const ModelConfig& config() const = 0;

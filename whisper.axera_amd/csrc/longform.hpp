@@ -15,7 +15,42 @@
 
 #include <dlfcn.h>
 
+#include "long_cuts.hpp"
+
 namespace axw {
+
+// Chunked long-form (DESIGN.md "Chunked long-form"; long_cuts.hpp: the definitions): the options of one call. Windows are decoded
+// independently, so everything that feeds one window's result into the next one has no meaning here and is refused, as is what the
+// mode does not cover yet; the members below the line only carry what was asked for to the one place that refuses it.
+struct ChunkedOptions {
+  CutParams cut;
+  // the scored decode mode: every window carries its two numbers, long_window_is_silent under the thresholds drops a window's segments
+  bool scored = false;
+  float no_speech_threshold = NAN, logprob_threshold = NAN;
+  // a language (>= 0, or -1: the handle's) and a task per file of the WHOLE call (empty: the handle's, transcribe)
+  std::vector<int> file_lang, file_task;
+  int file_base = 0;  // index of this engine's first file in the whole call
+  // ---- refused
+  int n_temperatures = 0;
+  bool compression_ratio_threshold = false, initial_prompt = false, condition_on_previous_text = false, word_timestamps = false;
+  int beam_size = 1;
+};
+// empty: the call can run; else the text of the refusal (n_files: files of the WHOLE call)
+inline std::string chunked_options_error(const ChunkedOptions& o, int n_files) {
+  const std::string bad = cut_params_error(o.cut.w_min, o.cut.w_max, o.cut.smooth);
+  if (!bad.empty()) return bad;
+  for (const std::vector<int>* v : {&o.file_lang, &o.file_task})
+    if (!v->empty() && (long)v->size() < (long)n_files) return "chunked long-form: fewer languages or tasks than files";
+  for (int l : o.file_lang)
+    if (l == -2) return "chunked long-form: language detection (-2) is not covered: detect the language first (AX_WHISPER_DetectLanguage)";
+  if (o.n_temperatures > 0 || o.compression_ratio_threshold)
+    return "chunked long-form: temperatures and temperature fallback are not covered (windows are decoded once, greedily)";
+  if (o.initial_prompt || o.condition_on_previous_text)
+    return "chunked long-form: prompts and condition_on_previous_text are not covered (windows are decoded independently)";
+  if (o.word_timestamps) return "chunked long-form: word timestamps are not covered";
+  if (o.beam_size != 1) return "chunked long-form: beam search is not covered (beam_size must be 1)";
+  return std::string();
+}
 
 struct WindowSegment {
   float start, end;        // seconds, relative to the window

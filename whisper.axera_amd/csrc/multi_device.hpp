@@ -154,6 +154,22 @@ class DeviceGroup {
       for (W& x : l) log.push_back(std::move(x));
   }
 
+  // Chunked long-form (E::run_long_chunked): the files are split like run_long_windows', every engine plans and decodes its own
+  // block, the log is joined the same way. O needs an int member file_base.
+  template <typename W, typename O>
+  void run_long_chunked(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes, const O& opts, std::vector<W>& log) {
+    if (n_files < 1) throw std::runtime_error("n_files must be >= 1");
+    std::vector<std::vector<W>> logs(size());
+    for_each_shard(n_files, [&](E& e, int w, int lo, int hi) {
+      O mine = opts;
+      mine.file_base = opts.file_base + lo;
+      e.run_long_chunked(pcm + lo, n_samples + lo, hi - lo, max_new, max_passes, mine, logs[w]);
+      for (W& x : logs[w]) x.file += lo;
+    });
+    for (auto& l : logs)
+      for (W& x : l) log.push_back(std::move(x));
+  }
+
  private:
   // fn(engine, worker, lo, hi) for every non-empty block of n items (run_sharded over min(G, n) workers). An engine is serialised
   // by its own mutex (a handle may be shared between threads), engines of different devices run concurrently.

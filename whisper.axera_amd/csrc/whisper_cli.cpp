@@ -29,6 +29,11 @@ static void usage(const char* prog) {
           "                      With --long the seek follows the last word's end, as openai-whisper's transcribe(word_timestamps=True)\n"
           "      --beam_size N   (with --timestamps, not with --long) the segment lines are those of beam search's winner over N\n"
           "                      hypotheses (1 .. 8; openai-whisper's CLI uses 5) instead of the greedy decode's\n"
+          "      --chunked       (with --long) choose every window before decoding, cut at the quietest frame of a search range, and decode\n"
+          "                      the windows side by side: faster on one long file; windows are decoded independently (no fallback, prompts,\n"
+          "                      language detection or word timestamps)\n"
+          "      --chunk_max_s S, --chunk_min_s S, --chunk_smooth_ms MS   (with --chunked) the longest and shortest window [=30, 20] and\n"
+          "                      the width of the level's smoothing box [=510]\n"
           "      --long          transcribe the whole file, not only its first 30 s: Result: is the whole text, followed by\n"
           "                      one [mm:ss.mmm --> mm:ss.mmm] line per segment with times from the file's start (hours\n"
           "                      roll into the minutes: 75:03.120). RTF: is wall time over the file's duration; without\n"
@@ -304,6 +309,57 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
   return 0;
 }
 
+// --long --chunked: the windows are chosen before decoding (cuts at quiet frames) and decoded side by side
+// (AX_WHISPER_RunPCMLongChunkedWindows); the text, then one line per segment of AX_WHISPER_ChunkedSegments in file time. What the
+// mode does not cover (fallback, prompts, detection, words) is handed on and refused by the library with its text.
+static int run_long_chunked(AX_WHISPER_HANDLE h, const char* wav, const AX_WHISPER_CHUNK_OPTIONS& chunk, bool scored, float no_speech_threshold,
+                            float logprob_threshold, float compression_ratio_threshold, const std::vector<float>& temps, const std::vector<int32_t>& prompt_ids,
+                            bool condition, bool detect, int task, bool word_timestamps, std::string& text, std::string& lines) {
+  float* pcm = nullptr;
+  int n = 0;
+  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
+  const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
+  const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
+  const int cap = n / 160 / (chunk.min_frames > 0 ? chunk.min_frames : 1) + 2;
+  std::vector<int> info((size_t)cap * 7);
+  std::vector<int32_t> ids((size_t)cap * n_ctx);
+  std::vector<float> score(scored ? (size_t)cap * 3 : 0);
+  int n_win = 0;
+  const float* files[1] = {pcm};
+  const int n_initial = (int)prompt_ids.size(), lang = detect ? -2 : -1, tk = task > 0 ? 1 : 0;
+  AX_WHISPER_LONG_OPTIONS o{};
+  o.no_speech_threshold = scored ? no_speech_threshold : NAN; o.logprob_threshold = scored ? logprob_threshold : NAN;
+  o.compression_ratio_threshold = compression_ratio_threshold;
+  o.temperatures = temps.empty() ? nullptr : temps.data(); o.n_temperatures = (int)temps.size();
+  o.initial_prompt_ids = prompt_ids.empty() ? nullptr : prompt_ids.data(); o.prompt_stride = n_initial; o.n_initial = prompt_ids.empty() ? nullptr : &n_initial;
+  o.condition_on_previous_text = condition ? 1 : 0;
+  if (detect || task >= 0) { o.lang = &lang; o.task = &tk; }
+  o.word_timestamps = word_timestamps ? 1 : 0;
+  const int rc = AX_WHISPER_RunPCMLongChunkedWindows(h, files, &n, 1, 0, 0, &chunk, &o, cap, info.data(), ids.data(), scored ? score.data() : nullptr, &n_win);
+  free(pcm);
+  if (rc != 0) return -1;
+  for (int k = 0; k < n_win; ++k) {
+    if (scored && score[(size_t)k * 3 + 2] != 0.f) continue;  // a silent window
+    char tail[160] = "";
+    if (scored) snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g)", score[(size_t)k * 3 + 1], std::exp(score[(size_t)k * 3]));
+    const int* w = &info[(size_t)k * 7];
+    const int32_t* wi = &ids[(size_t)k * n_ctx];
+    const int n_max = w[4] / 2 + 1;
+    std::vector<double> st(n_max), en(n_max);
+    std::vector<int> tb(n_max), te(n_max);
+    int n_seg = 0;
+    if (AX_WHISPER_ChunkedSegments(wi, w[4], T, E, w[1], w[2], n_max, st.data(), en.data(), tb.data(), te.data(), &n_seg) != 0) return -1;
+    for (int s = 0; s < n_seg; ++s) {
+      char* t = nullptr;
+      if (AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t) != 0) return -1;
+      text += t ? t : "";
+      lines += "[" + mmss_ms((long)(st[s] * 1000.0 + 0.5)) + " --> " + mmss_ms((long)(en[s] * 1000.0 + 0.5)) + "] " + (t ? t : "") + tail + "\n";
+      free(t);
+    }
+  }
+  return 0;
+}
+
 // --long --word_timestamps: the seek loop with words (AX_WHISPER_RunPCMLongWords) under the same thresholds, fallback, prompts, language
 // and task as run_long: the whole text, then one line per segment (the times the word rule left) and under it one indented line per word
 static int run_long_words(AX_WHISPER_HANDLE h, const char* wav, float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold,
@@ -344,8 +400,8 @@ static int run_long_words(AX_WHISPER_HANDLE h, const char* wav, float no_speech_
 int main(int argc, char** argv) {
   std::string wav, model_type = "turbo", model_path = "../models-mi355x", language = "zh";
   bool timestamps = false, longform = false, word_timestamps = false;
-  bool condition = false, detect = false;
-  std::string task_arg;
+  bool condition = false, detect = false, chunked = false;
+  std::string task_arg, cmax_arg, cmin_arg, csmooth_arg;
   std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -362,12 +418,14 @@ int main(int argc, char** argv) {
     if (val("wav", "-w", wav) || val("model_type", "-t", model_type) || val("model_path", "-p", model_path) ||
         val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg) ||
         val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg) ||
-        val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg) || val("task", nullptr, task_arg))
+        val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg) || val("task", nullptr, task_arg) ||
+        val("chunk_max_s", nullptr, cmax_arg) || val("chunk_min_s", nullptr, cmin_arg) || val("chunk_smooth_ms", nullptr, csmooth_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
     if (a == "--word_timestamps") { word_timestamps = true; continue; }
     if (a == "--long") { longform = true; continue; }
+    if (a == "--chunked") { chunked = true; continue; }
     if (a == "--resample") { g_resample = true; continue; }
     if (a == "--condition_on_previous_text") { condition = true; continue; }
     if (a == "--detect_language") { detect = true; continue; }
@@ -383,6 +441,19 @@ int main(int argc, char** argv) {
     if (*end || v < 1 || v > 8) { fprintf(stderr, "bad value: --beam_size %s (1 .. 8)\n", beam_arg.c_str()); return 1; }
     beam_size = (int)v;
     if (!timestamps || longform) { fprintf(stderr, "--beam_size needs --timestamps and does not go with --long\n"); usage(argv[0]); return 1; }
+  }
+  if ((chunked || !cmax_arg.empty() || !cmin_arg.empty() || !csmooth_arg.empty()) && (!longform || !chunked)) {
+    fprintf(stderr, "--chunked needs --long; --chunk_max_s / --chunk_min_s / --chunk_smooth_ms need --long --chunked\n");
+    usage(argv[0]);
+    return 1;
+  }
+  AX_WHISPER_CHUNK_OPTIONS chunk = {3000, 2000, 25, 1};
+  {
+    // seconds -> frames of 10 ms, milliseconds of box width -> R (the box is 2 R + 1 frames); the library checks the ranges
+    char* end = nullptr;
+    if (!cmax_arg.empty()) { chunk.max_frames = (int)std::lround(strtod(cmax_arg.c_str(), &end) * 100.0); if (*end) { fprintf(stderr, "bad value: --chunk_max_s %s\n", cmax_arg.c_str()); return 1; } }
+    if (!cmin_arg.empty()) { chunk.min_frames = (int)std::lround(strtod(cmin_arg.c_str(), &end) * 100.0); if (*end) { fprintf(stderr, "bad value: --chunk_min_s %s\n", cmin_arg.c_str()); return 1; } }
+    if (!csmooth_arg.empty()) { chunk.smooth_frames = (int)std::lround((strtod(csmooth_arg.c_str(), &end) / 10.0 - 1.0) / 2.0); if (*end) { fprintf(stderr, "bad value: --chunk_smooth_ms %s\n", csmooth_arg.c_str()); return 1; } }
   }
   int task = -1;  // not given
   if (!task_arg.empty()) {
@@ -450,7 +521,9 @@ int main(int argc, char** argv) {
 
   auto t0 = std::chrono::steady_clock::now();
   // (beam search: one decoder slot per hypothesis)
+  // (chunked long-form: 16 windows side by side unless AX_WHISPER_MAX_BATCH says otherwise)
   AX_WHISPER_HANDLE handle = beam_size > 1 ? AX_WHISPER_InitEx(model_type.c_str(), model_path.c_str(), language.c_str(), -1, beam_size)
+                             : chunked && !getenv("AX_WHISPER_MAX_BATCH") ? AX_WHISPER_InitEx(model_type.c_str(), model_path.c_str(), language.c_str(), -1, 16)
                                            : AX_WHISPER_Init(model_type.c_str(), model_path.c_str(), language.c_str());
   auto t1 = std::chrono::steady_clock::now();
   if (!handle) { printf("AX_WHISPER_Init failed!\n"); return -1; }
@@ -471,7 +544,9 @@ int main(int argc, char** argv) {
   if (longform) {
     t0 = std::chrono::steady_clock::now();
     std::string text, lines;
-    if ((word_timestamps ? run_long_words(handle, wav.c_str(), no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompt_ids,
+    if ((chunked ? run_long_chunked(handle, wav.c_str(), chunk, !nst_arg.empty() || !lpt_arg.empty(), no_speech_threshold, logprob_threshold,
+                                    compression_ratio_threshold, temps, prompt_ids, condition, detect, task, word_timestamps, text, lines)
+         : word_timestamps ? run_long_words(handle, wav.c_str(), no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompt_ids,
                                           condition, text, lines, detect, task)
                          : run_long(handle, wav.c_str(), scored, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompted,
                                     prompt_ids, condition, text, lines, detect, task)) != 0) {
