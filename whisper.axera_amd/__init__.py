@@ -426,6 +426,28 @@ def _thresholds(no_speech_threshold, logprob_threshold):
             float("inf") if logprob_threshold is None else float(logprob_threshold))
 
 
+def _long_fallback_args(o):
+    return (o.no_speech_threshold, o.logprob_threshold, o.compression_ratio_threshold, o.temperatures, o.n_temperatures, o.seed)
+
+
+def _long_prompted_args(o):
+    return _long_fallback_args(o) + (o.file_ids, o.initial_prompt_ids, o.prompt_stride, o.n_initial, o.condition_on_previous_text)
+
+
+def _long_text_prompted_args(o):
+    return _long_fallback_args(o) + (o.initial_prompt_ids, o.n_initial[0], o.condition_on_previous_text)
+
+
+# The legacy argument lists of the long-form exports, each a part of a LongOptions `o`: the form (what follows RunPCMLongWindows in the
+# export's name) -> the arguments between the files and the outputs. The one-file text forms (RunPCMLong<form> / RunFileLong<form>)
+# take one prompt, one language and one task by value and no file ids; their last None is lang_out.
+_LONG_FORMS = {"": lambda o: (), "Scored": lambda o: (o.no_speech_threshold, o.logprob_threshold),
+               "Fallback": lambda o: _long_fallback_args(o) + (o.file_ids,), "Prompted": _long_prompted_args,
+               "Lang": lambda o: _long_prompted_args(o) + (o.lang, o.task), "Words": lambda o: (C.byref(o),)}
+_LONG_TEXT_FORMS = {"": lambda o: (), "Opts": _LONG_FORMS["Scored"], "Fallback": _long_fallback_args, "Prompted": _long_text_prompted_args,
+                    "Lang": lambda o: _long_text_prompted_args(o) + (o.lang[0] if o.lang else -1, o.task[0] if o.task else 0, None)}
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -1247,78 +1269,89 @@ class Whisper:
         With languages (per file a code, None or "auto") or tasks ("transcribe" / "translate") the call is
         AX_WHISPER_RunPCMLongWindowsLang, and the result is the pair (that list, the language code of every file); the tuples are
         those of the prompted call.
-        word_timestamps (None: the calls above as they were; True / False): AX_WHISPER_RunPCMLongWindowsWords, see
-        _run_long_windows_words, whose result with False is the languages / tasks call's."""
-        if word_timestamps is not None:
-            return self._run_long_windows_words(files, max_new, max_passes, no_speech_threshold, logprob_threshold, compression_ratio_threshold,
-                                                temperatures, seed, file_ids, initial_prompt_ids, condition_on_previous_text, languages, tasks,
-                                                bool(word_timestamps))
-        fallback = compression_ratio_threshold is not None or temperatures is not None
-        per_lang = languages is not None or tasks is not None
-        prompted = bool(condition_on_previous_text) or initial_prompt_ids is not None or per_lang
-        scored = prompted or fallback or scores or no_speech_threshold is not None or logprob_threshold is not None
-        nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
-        crt, temps = float("nan"), _f32([])
-        if fallback:
-            lpt = float("nan") if logprob_threshold is None else float(logprob_threshold)
-            crt = float("nan") if compression_ratio_threshold is None else float(compression_ratio_threshold)
-            temps = _f32(DEFAULT_TEMPERATURES if temperatures is None else temperatures)
-        sw = 7 if fallback else 3
+        word_timestamps (None: the calls above as they were; True / False): AX_WHISPER_RunPCMLongWindowsWords, whose result with
+        False is the languages / tasks call's, and with True one more entry per window, a dict: text_ids, seg_tokens, jump,
+        token_logprob (what was aligned and what the alignment gave), seg_start, seg_end (file time, after the word rule), words
+        [(segment, word bytes, start, end, probability)] in file time, by_word_end (the advance is the word-end seek)."""
         files = [_f32(f) for f in files]
-        n = len(files)
+        o, keep, fallback = self._long_options(len(files), no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed,
+                                               file_ids, initial_prompt_ids, condition_on_previous_text, languages, tasks, word_timestamps)
+        per_lang = languages is not None or tasks is not None
+        prompted = bool(condition_on_previous_text) or initial_prompt_ids is not None
+        scored = scores or no_speech_threshold is not None or logprob_threshold is not None
+        form = ("Words" if word_timestamps is not None else "Lang" if per_lang else "Prompted" if prompted else "Fallback" if fallback else
+                "Scored" if scored else "")
+        out, codes = self._long_windows(form, files, max_new, max_passes, o, fallback)
+        return out if codes is None else (out, codes)
+
+    def _long_options(self, n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed, file_ids, initial_prompt_ids,
+                      condition_on_previous_text, languages, tasks, word_timestamps, logprob_nan: bool = False):
+        """-> (AX_WHISPER_LONG_OPTIONS, what its pointers point into, whether the call has fallback): the option arguments of the
+        long-form methods as the C ABI takes them; every legacy argument list is a part of this struct (_LONG_FORMS). None
+        thresholds become the values that switch their comparison off (_thresholds); with fallback a missing logprob_threshold is
+        NaN, which switches its part of the fallback rule off (logprob_nan: also without fallback, as the one-file Prompted and Lang
+        text forms have always passed it)."""
+        fallback = compression_ratio_threshold is not None or temperatures is not None
+        nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
+        if logprob_threshold is None and (fallback or logprob_nan):
+            lpt = float("nan")
+        crt = float("nan") if compression_ratio_threshold is None else float(compression_ratio_threshold)
+        temps = _f32((DEFAULT_TEMPERATURES if temperatures is None else temperatures) if fallback else [])
+        init = [[] if q is None else list(q) for q in (initial_prompt_ids if initial_prompt_ids is not None else [None] * n)]
+        if len(init) != n:
+            raise ValueError("one initial prompt (or None) per file")
+        pid, stride, npr = self._prompt_args(init)
+        lang, task = self._lang_args(n, languages, tasks)
+        fid = (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None
+        o = LongOptions(nst, lpt, crt, temps.ctypes.data_as(fp) if fallback else None, len(temps), int(seed), fid, pid, stride, npr,
+                        int(bool(condition_on_previous_text)), lang, task, int(bool(word_timestamps)))
+        return o, (temps, pid, npr, lang, task, fid), fallback
+
+    def _long_windows(self, form, files, max_new, max_passes, o, fallback, chunk=None):
+        """One window-log call, AX_WHISPER_RunPCMLongWindows<form> (with chunk, a ChunkOptions: AX_WHISPER_RunPCMLongChunkedWindows,
+        form "" or "Scored") over `files` (float32 arrays) under the LongOptions `o` -> (per file the list of its windows, the
+        language code of every file or None). The buffers hold `cap` windows; a call that decodes more says how many and is repeated.
+        A window is (seek, window_frames, advance, ids, pass, slot), then what its form adds (run_long_windows)."""
+        n, Tc, pi = len(files), self.n_text_ctx, C.POINTER(C.c_int)
         ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
         lens = (C.c_int * n)(*[len(f) for f in files])
-        # room for every window advancing fully, twice over; a call that decodes more says how many, and is repeated
-        cap = sum(len(f) // 160 // 3000 + 2 for f in files) * 2
+        name = "RunPCMLongChunkedWindows" if chunk is not None else "RunPCMLongWindowsWords" if form == "Words" else "RunPCMLongWindows"
+        fn = getattr(self.L, "AX_WHISPER_" + (name if chunk is not None else "RunPCMLongWindows" + form))
+        scored, prompted, per_lang, words = form != "", form in ("Prompted", "Lang", "Words"), form in ("Lang", "Words"), form == "Words" and bool(o.word_timestamps)
+        # room for every window advancing fully, twice over (chunked: every window of the plan at its shortest)
+        cap = sum(len(f) // 160 // 3000 + 2 for f in files) * 2 if chunk is None else sum(len(f) // 160 // max(chunk.min_frames, 1) + 2 for f in files)
         while True:
-            info = np.zeros((cap, 7), dtype=np.int32)
-            ids = np.zeros((cap, self.n_text_ctx), dtype=np.int32)
-            sc = np.zeros((cap, sw), dtype=np.float32)
-            nw = C.c_int()
-            wp = np.zeros(cap, dtype=np.int32)
-            if prompted:
-                init = [[] if q is None else list(q) for q in (initial_prompt_ids if initial_prompt_ids is not None else [None] * n)]
-                if len(init) != n:
-                    raise ValueError("one initial prompt (or None) per file")
-                pid, stride, npr = self._prompt_args(init)
-            if per_lang:
-                lang, task = self._lang_args(n, languages, tasks)
-                lout = (C.c_int * n)()
-                rc = self.L.AX_WHISPER_RunPCMLongWindowsLang(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
-                                                             temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed),
-                                                             (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None,
-                                                             pid, stride, npr, int(bool(condition_on_previous_text)), lang, task, cap,
-                                                             info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
-                                                             sc.ctypes.data_as(fp), wp.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nw), lout)
-            elif prompted:
-                rc = self.L.AX_WHISPER_RunPCMLongWindowsPrompted(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
-                                                                 temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed),
-                                                                 (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None,
-                                                                 pid, stride, npr, int(bool(condition_on_previous_text)), cap,
-                                                                 info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
-                                                                 sc.ctypes.data_as(fp), wp.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nw))
-            elif fallback:
-                rc = self.L.AX_WHISPER_RunPCMLongWindowsFallback(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, crt,
-                                                                 temps.ctypes.data_as(fp), len(temps), int(seed),
-                                                                 (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None, cap,
-                                                                 info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
-                                                                 sc.ctypes.data_as(fp), C.byref(nw))
-            elif scored:
-                rc = self.L.AX_WHISPER_RunPCMLongWindowsScored(self.h, ptrs, lens, n, int(max_new), int(max_passes), nst, lpt, cap,
-                                                               info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
-                                                               sc.ctypes.data_as(fp), C.byref(nw))
-            else:
-                rc = self.L.AX_WHISPER_RunPCMLongWindows(self.h, ptrs, lens, n, int(max_new), int(max_passes), cap,
-                                                         info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip), C.byref(nw))
-            if rc != 0:
-                msg = (self.L.AX_WHISPER_LastError(self.h) or b"").decode()
-                need = re.search(r"(\d+) windows were decoded, win_cap is", msg)
-                if need:
-                    cap = int(need.group(1))
-                    continue
-                raise RuntimeError("RunPCMLongWindows failed: " + msg)
-            break
+            info, ids, wp = np.zeros((cap, 7), dtype=np.int32), np.zeros((cap, Tc), dtype=np.int32), np.zeros(cap, dtype=np.int32)
+            sc = np.zeros((cap, 7 if fallback else 3), dtype=np.float32)
+            nw, lout = C.c_int(), (C.c_int * n)()
+            outs = (cap, info.ctypes.data_as(pi), ids.ctypes.data_as(ip)) + ((sc.ctypes.data_as(fp),) if scored else (None,) if chunk is not None else ())
+            outs += ((wp.ctypes.data_as(pi),) if prompted else ()) + (C.byref(nw),) + ((lout,) if per_lang else ())
+            if form == "Words":
+                m = cap * Tc  # (a window has fewer segments and words than ids)
+                ww, tid, jmp = np.zeros((cap, 4), dtype=np.int32), np.zeros((cap, Tc), dtype=np.int32), np.zeros((cap, Tc + 1), dtype=np.int32)
+                tlp = np.zeros((cap, Tc), dtype=np.float32)
+                sgt, wsg, wte = (np.zeros(m, dtype=np.int32) for _ in range(3))
+                sgs, sge, wst, wen = (np.zeros(m, dtype=np.float64) for _ in range(4))
+                wpr = np.zeros(m, dtype=np.float32)
+                log = LongWordLog(m, m, ww.ctypes.data_as(pi), tid.ctypes.data_as(ip), jmp.ctypes.data_as(pi), tlp.ctypes.data_as(fp), sgt.ctypes.data_as(pi),
+                                  sgs.ctypes.data_as(_dblp), sge.ctypes.data_as(_dblp), wsg.ctypes.data_as(pi), wte.ctypes.data_as(pi),
+                                  wst.ctypes.data_as(_dblp), wen.ctypes.data_as(_dblp), wpr.ctypes.data_as(fp), None)
+                outs += (C.byref(log),)
+            args = (C.byref(chunk), C.byref(o)) if chunk is not None else _LONG_FORMS[form](o)
+            rc = fn(self.h, ptrs, lens, n, int(max_new), int(max_passes), *args, *outs)
+            if form == "Words":
+                text = C.string_at(log.text, int(wte[max(int(ww[: nw.value, 2].sum()) - 1, 0)])) if log.text and rc == 0 else b""
+                if log.text:
+                    self.L._free(log.text)
+            if rc == 0:
+                break
+            msg = (self.L.AX_WHISPER_LastError(self.h) or b"").decode()
+            need = re.search(r"(\d+) windows were decoded, win_cap is", msg)
+            if not need:
+                raise RuntimeError(name + " failed: " + msg)
+            cap = int(need.group(1))
         out = [[] for _ in range(n)]
+        sg = wd = 0
         for k in range(nw.value):
             f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
             w = (seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot)
@@ -1328,93 +1361,16 @@ class Whisper:
                 w = w + (int(sc[k, 3]), float(sc[k, 4]), float(sc[k, 5]), bool(sc[k, 6]))
             if prompted:
                 w = w + (int(wp[k]),)
-            out[f].append(w)
-        if per_lang:
-            return out, [self.language_code(lout[f]) for f in range(n)]
-        return out
-
-    def _long_options(self, n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed, file_ids, initial_prompt_ids,
-                      condition_on_previous_text, languages, tasks, word_timestamps):
-        """-> (AX_WHISPER_LONG_OPTIONS, what its pointers point into, whether the call has fallback): the arguments of run_long_windows as
-        its languages / tasks form hands them to the C ABI"""
-        fallback = compression_ratio_threshold is not None or temperatures is not None
-        nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
-        crt, temps = float("nan"), _f32([])
-        if fallback:
-            lpt = float("nan") if logprob_threshold is None else float(logprob_threshold)
-            crt = float("nan") if compression_ratio_threshold is None else float(compression_ratio_threshold)
-            temps = _f32(DEFAULT_TEMPERATURES if temperatures is None else temperatures)
-        init = [[] if q is None else list(q) for q in (initial_prompt_ids if initial_prompt_ids is not None else [None] * n)]
-        if len(init) != n:
-            raise ValueError("one initial prompt (or None) per file")
-        pid, stride, npr = self._prompt_args(init)
-        lang, task = self._lang_args(n, languages, tasks)
-        fid = (C.c_int * n)(*[int(x) for x in file_ids]) if file_ids is not None else None
-        o = LongOptions(nst, lpt, crt, temps.ctypes.data_as(fp) if fallback else None, len(temps) if fallback else 0, int(seed), fid, pid, stride, npr,
-                        int(bool(condition_on_previous_text)), lang, task, int(bool(word_timestamps)))
-        return o, (temps, pid, npr, lang, task, fid), fallback
-
-    def _run_long_windows_words(self, files, max_new, max_passes, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures,
-                                seed, file_ids, initial_prompt_ids, condition_on_previous_text, languages, tasks, word_timestamps):
-        """AX_WHISPER_RunPCMLongWindowsWords -> (per file its windows, the language code of every file). A window is the tuple of the
-        languages / tasks call of run_long_windows, and with word_timestamps one more entry, a dict: text_ids, seg_tokens, jump,
-        token_logprob (what was aligned and what the alignment gave), seg_start, seg_end (file time, after the word rule), words
-        [(segment, word bytes, start, end, probability)] in file time, by_word_end (the advance is the word-end seek)."""
-        files = [_f32(f) for f in files]
-        n = len(files)
-        o, keep, fallback = self._long_options(n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed, file_ids,
-                                               initial_prompt_ids, condition_on_previous_text, languages, tasks, word_timestamps)
-        sw = 7 if fallback else 3
-        ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
-        lens = (C.c_int * n)(*[len(f) for f in files])
-        Tc = self.n_text_ctx
-        cap = sum(len(f) // 160 // 3000 + 2 for f in files) * 2
-        pi = C.POINTER(C.c_int)
-        while True:
-            info, ids, sc = np.zeros((cap, 7), dtype=np.int32), np.zeros((cap, Tc), dtype=np.int32), np.zeros((cap, sw), dtype=np.float32)
-            wp, nw, lout = np.zeros(cap, dtype=np.int32), C.c_int(), (C.c_int * n)()
-            m = cap * Tc  # (a window has fewer segments and words than ids)
-            ww, tid, jmp = np.zeros((cap, 4), dtype=np.int32), np.zeros((cap, Tc), dtype=np.int32), np.zeros((cap, Tc + 1), dtype=np.int32)
-            tlp = np.zeros((cap, Tc), dtype=np.float32)
-            sgt, wsg, wte = (np.zeros(m, dtype=np.int32) for _ in range(3))
-            sgs, sge, wst, wen = (np.zeros(m, dtype=np.float64) for _ in range(4))
-            wpr = np.zeros(m, dtype=np.float32)
-            log = LongWordLog(m, m, ww.ctypes.data_as(pi), tid.ctypes.data_as(ip), jmp.ctypes.data_as(pi), tlp.ctypes.data_as(fp), sgt.ctypes.data_as(pi),
-                              sgs.ctypes.data_as(_dblp), sge.ctypes.data_as(_dblp), wsg.ctypes.data_as(pi), wte.ctypes.data_as(pi),
-                              wst.ctypes.data_as(_dblp), wen.ctypes.data_as(_dblp), wpr.ctypes.data_as(fp), None)
-            rc = self.L.AX_WHISPER_RunPCMLongWindowsWords(self.h, ptrs, lens, n, int(max_new), int(max_passes), C.byref(o), cap, info.ctypes.data_as(pi),
-                                                          ids.ctypes.data_as(ip), sc.ctypes.data_as(fp), wp.ctypes.data_as(pi), C.byref(nw), lout,
-                                                          C.byref(log))
-            text = C.string_at(log.text, int(wte[max(int(ww[: nw.value, 2].sum()) - 1, 0)])) if log.text and rc == 0 else b""
-            if log.text:
-                self.L._free(log.text)
-            if rc != 0:
-                msg = (self.L.AX_WHISPER_LastError(self.h) or b"").decode()
-                need = re.search(r"(\d+) windows were decoded, win_cap is", msg)
-                if need:
-                    cap = int(need.group(1))
-                    continue
-                raise RuntimeError("RunPCMLongWindowsWords failed: " + msg)
-            break
-        out = [[] for _ in range(n)]
-        sg = wd = 0
-        for k in range(nw.value):
-            f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
-            w = (seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot, float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2]))
-            if fallback:
-                w = w + (int(sc[k, 3]), float(sc[k, 4]), float(sc[k, 5]), bool(sc[k, 6]))
-            w = w + (int(wp[k]),)
-            if word_timestamps:
+            if words:
                 nt, ns, nwd, by = (int(x) for x in ww[k])
-                words = []
-                for j in range(wd, wd + nwd):
-                    words.append((int(wsg[j]), text[int(wte[j - 1]) if j else 0: int(wte[j])], float(wst[j]), float(wen[j]), np.float32(wpr[j])))
+                wl = [(int(wsg[j]), text[int(wte[j - 1]) if j else 0: int(wte[j])], float(wst[j]), float(wen[j]), np.float32(wpr[j])) for j in range(wd, wd + nwd)]
                 w = w + (dict(text_ids=tid[k, :nt].tolist(), seg_tokens=sgt[sg: sg + ns].tolist(), jump=jmp[k, : nt + 1].copy() if nt else jmp[k, :0].copy(),
-                              token_logprob=tlp[k, :nt].copy(), seg_start=sgs[sg: sg + ns].tolist(), seg_end=sge[sg: sg + ns].tolist(), words=words,
+                              token_logprob=tlp[k, :nt].copy(), seg_start=sgs[sg: sg + ns].tolist(), seg_end=sge[sg: sg + ns].tolist(), words=wl,
                               by_word_end=bool(by)),)
                 sg, wd = sg + ns, wd + nwd
             out[f].append(w)
-        return out, [self.language_code(lout[f]) for f in range(n)]
+        return out, [self.language_code(lout[f]) for f in range(n)] if per_lang else None
+
 
     def run_long_words(self, audio, no_speech_threshold=None, logprob_threshold=None, compression_ratio_threshold=None, temperatures=None, seed: int = 0,
                        initial_prompt_ids=None, condition_on_previous_text: bool = False, language=None, task=None):
@@ -1542,9 +1498,8 @@ class Whisper:
         run_long_windows ("auto" is refused). refused: the options of run_long_windows this mode does not cover (temperatures,
         compression_ratio_threshold, initial_prompt_ids, condition_on_previous_text, word_timestamps); the library refuses them."""
         files = [_f32(f) for f in files]
-        n = len(files)
         scored = scores or no_speech_threshold is not None or logprob_threshold is not None
-        o, keep, _ = self._long_options(n, no_speech_threshold, logprob_threshold, refused.pop("compression_ratio_threshold", None),
+        o, keep, _ = self._long_options(len(files), no_speech_threshold, logprob_threshold, refused.pop("compression_ratio_threshold", None),
                                         refused.pop("temperatures", None), 0, None, refused.pop("initial_prompt_ids", None),
                                         refused.pop("condition_on_previous_text", False), languages, tasks, refused.pop("word_timestamps", False))
         if refused:
@@ -1552,24 +1507,8 @@ class Whisper:
         if no_speech_threshold is None and logprob_threshold is None:
             o.no_speech_threshold = o.logprob_threshold = float("nan")
         chunk = ChunkOptions(int(max_frames), int(min_frames), int(smooth_frames), int(beam_size))
-        ptrs = (fp * n)(*[f.ctypes.data_as(fp) for f in files])
-        lens = (C.c_int * n)(*[len(f) for f in files])
-        cap = sum(len(f) // 160 // max(int(min_frames), 1) + 2 for f in files)
-        info = np.zeros((cap, 7), dtype=np.int32)
-        ids = np.zeros((cap, self.n_text_ctx), dtype=np.int32)
-        sc = np.zeros((cap, 3), dtype=np.float32)
-        nw = C.c_int()
-        self._check(self.L.AX_WHISPER_RunPCMLongChunkedWindows(self.h, ptrs, lens, n, int(max_new), int(max_passes), C.byref(chunk), C.byref(o), cap,
-                                                               info.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(ip),
-                                                               sc.ctypes.data_as(fp) if scored else None, C.byref(nw)), "RunPCMLongChunkedWindows")
-        out = [[] for _ in range(n)]
-        for k in range(nw.value):
-            f, seek, wf, adv, n_ids, pas, slot = (int(x) for x in info[k])
-            w = (seek, wf, adv, ids[k, :n_ids].tolist(), pas, slot)
-            if scored:
-                w = w + (float(sc[k, 0]), float(sc[k, 1]), bool(sc[k, 2]))
-            out[f].append(w)
-        return out
+        return self._long_windows("Scored" if scored else "", files, max_new, max_passes, o, False, chunk)[0]
+
 
     def run_long_chunked(self, audio, max_new: int = 0, min_frames: int = 2000, max_frames: int = 3000, smooth_frames: int = 25,
                          no_speech_threshold=None, logprob_threshold=None, language=None, task=None, **refused):
@@ -1594,62 +1533,25 @@ class Whisper:
                       seed: int = 0, initial_prompt_ids=None, condition_on_previous_text: bool = False, languages=None, tasks=None) -> str:
         """PCM or a wav path of any length -> the whole text (AX_WHISPER_RunPCMLong / RunFileLong; with a threshold: the *Opts
         forms, the text without the windows the silent-window rule skips; with compression_ratio_threshold or temperatures: the
-        *Fallback forms). With languages / tasks (a one-entry list each, or None): the *Lang forms, the text under that language and
-        task (its zh pass follows the file's language)."""
+        *Fallback forms; with condition_on_previous_text or a non-empty initial_prompt_ids: the *Prompted forms). With languages /
+        tasks (a one-entry list each, or None): the *Lang forms, the text under that language and task (its zh pass follows the
+        file's language)."""
+        form = ("Lang" if languages is not None or tasks is not None else
+                "Prompted" if condition_on_previous_text or (initial_prompt_ids is not None and len(initial_prompt_ids)) else
+                "Fallback" if compression_ratio_threshold is not None or temperatures is not None else
+                "Opts" if no_speech_threshold is not None or logprob_threshold is not None else "")
+        o, keep, _ = self._long_options(1, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, seed, None,
+                                        None if initial_prompt_ids is None else [initial_prompt_ids], condition_on_previous_text, languages, tasks,
+                                        False, logprob_nan=form in ("Prompted", "Lang"))
         out = C.c_void_p()
-        if languages is not None or tasks is not None:
-            nan = lambda v: float("nan") if v is None else float(v)
-            fallback = compression_ratio_threshold is not None or temperatures is not None
-            temps = _f32((DEFAULT_TEMPERATURES if temperatures is None else temperatures) if fallback else [])
-            init = _i32([] if initial_prompt_ids is None else initial_prompt_ids)
-            lang, task = self._lang_args(1, languages, tasks)
-            tail = (nan(no_speech_threshold), nan(logprob_threshold), nan(compression_ratio_threshold), temps.ctypes.data_as(fp) if fallback else None,
-                    len(temps), int(seed), init.ctypes.data_as(ip), len(init), int(bool(condition_on_previous_text)),
-                    lang[0] if lang is not None else -1, task[0] if task is not None else 0, None, C.byref(out))
-            if isinstance(audio, (str, os.PathLike)):
-                self._check(self.L.AX_WHISPER_RunFileLongLang(self.h, os.fspath(audio).encode(), *tail), "RunFileLongLang")
-            else:
-                a = _f32(audio)
-                self._check(self.L.AX_WHISPER_RunPCMLongLang(self.h, a.ctypes.data_as(fp), len(a), *tail), "RunPCMLongLang")
-            return self._take(out.value)
-        if condition_on_previous_text or (initial_prompt_ids is not None and len(initial_prompt_ids)):  # the *Prompted forms
-            nan = lambda v: float("nan") if v is None else float(v)
-            fallback = compression_ratio_threshold is not None or temperatures is not None
-            temps = _f32((DEFAULT_TEMPERATURES if temperatures is None else temperatures) if fallback else [])
-            init = _i32([] if initial_prompt_ids is None else initial_prompt_ids)
-            tail = (nan(no_speech_threshold), nan(logprob_threshold), nan(compression_ratio_threshold), temps.ctypes.data_as(fp) if fallback else None,
-                    len(temps), int(seed), init.ctypes.data_as(ip), len(init), int(bool(condition_on_previous_text)), C.byref(out))
-            if isinstance(audio, (str, os.PathLike)):
-                self._check(self.L.AX_WHISPER_RunFileLongPrompted(self.h, os.fspath(audio).encode(), *tail), "RunFileLongPrompted")
-            else:
-                a = _f32(audio)
-                self._check(self.L.AX_WHISPER_RunPCMLongPrompted(self.h, a.ctypes.data_as(fp), len(a), *tail), "RunPCMLongPrompted")
-            return self._take(out.value)
-        if compression_ratio_threshold is not None or temperatures is not None:
-            nan = lambda v: float("nan") if v is None else float(v)
-            temps = _f32(DEFAULT_TEMPERATURES if temperatures is None else temperatures)
-            tail = (nan(no_speech_threshold), nan(logprob_threshold), nan(compression_ratio_threshold), temps.ctypes.data_as(fp), len(temps),
-                    int(seed), C.byref(out))
-            if isinstance(audio, (str, os.PathLike)):
-                self._check(self.L.AX_WHISPER_RunFileLongFallback(self.h, os.fspath(audio).encode(), *tail), "RunFileLongFallback")
-            else:
-                a = _f32(audio)
-                self._check(self.L.AX_WHISPER_RunPCMLongFallback(self.h, a.ctypes.data_as(fp), len(a), *tail), "RunPCMLongFallback")
-            return self._take(out.value)
-        if no_speech_threshold is not None or logprob_threshold is not None:
-            nst, lpt = _thresholds(no_speech_threshold, logprob_threshold)
-            if isinstance(audio, (str, os.PathLike)):
-                self._check(self.L.AX_WHISPER_RunFileLongOpts(self.h, os.fspath(audio).encode(), nst, lpt, C.byref(out)), "RunFileLongOpts")
-            else:
-                a = _f32(audio)
-                self._check(self.L.AX_WHISPER_RunPCMLongOpts(self.h, a.ctypes.data_as(fp), len(a), nst, lpt, C.byref(out)), "RunPCMLongOpts")
-            return self._take(out.value)
         if isinstance(audio, (str, os.PathLike)):
-            self._check(self.L.AX_WHISPER_RunFileLong(self.h, os.fspath(audio).encode(), C.byref(out)), "RunFileLong")
+            name, head = "RunFileLong" + form, (os.fspath(audio).encode(),)
         else:
             a = _f32(audio)
-            self._check(self.L.AX_WHISPER_RunPCMLong(self.h, a.ctypes.data_as(fp), len(a), C.byref(out)), "RunPCMLong")
+            name, head = "RunPCMLong" + form, (a.ctypes.data_as(fp), len(a))
+        self._check(getattr(self.L, "AX_WHISPER_" + name)(self.h, *head, *_LONG_TEXT_FORMS[form](o), C.byref(out)), name)
         return self._take(out.value)
+
 
     def decode_forced_timestamps(self, batch: int, forced, want_logits: bool = True):
         """Teacher-forced timestamp-mode decode of the EncodeMel slots -> (raw logits [batch][n+1][n_vocab] or None,

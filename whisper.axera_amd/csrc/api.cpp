@@ -29,6 +29,7 @@
 #include "resample.hpp"
 #include "words.hpp"
 #include "vocab_logprob_plan.hpp"
+#include "long_call.hpp"
 
 using Engine = axw::IEngine;
 
@@ -162,6 +163,146 @@ AX_WHISPER_HANDLE init_guarded(F&& f) {
   }
 }
 
+// the file decode of RunFile / RunFileLong: false (and the handle's error text set) when the file cannot be used
+bool load_wav_for_run(AX_WHISPER_HANDLE handle, const char* wav_file, axw::WavData& wav) {
+  std::string err;
+  if (!axw::load_audio_file(wav_file, wav, err)) {
+    H(handle)->set_error("load wav failed: " + err);
+    fprintf(stderr, "[ax_whisper] load wav failed: %s\n", err.c_str());
+    return false;
+  }
+  if (wav.mono.empty()) {
+    H(handle)->set_error("wav file holds no samples");
+    return false;
+  }
+  if (wav.sample_rate != 16000)  // the reference silently mis-transcribes (no resampler anywhere in its C++)
+    fprintf(stderr, "[ax_whisper] warning: %s is %d Hz, expected 16000 Hz (see cpp/resample_wav.sh of the reference)\n",
+            wav_file, wav.sample_rate);
+  return true;
+}
+
+// every Run*File* form: load the file, then pcm_form(samples, n), the PCM form of the same call; *out is cleared first
+template <typename T, typename F>
+int run_wav(AX_WHISPER_HANDLE handle, const char* wav_file, T* out, F&& pcm_form) {
+  if (!handle || !wav_file || !out) return -1;
+  *out = T{};
+  axw::WavData wav;
+  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
+  return pcm_form(wav.mono.data(), (int)wav.mono.size());
+}
+
+// ---- long-form: the three bodies behind the Run*Long* exports (long_call.hpp: what an export asks for; DESIGN.md "Long-form entry
+// points"). An export fills a LongCall and names its outputs; the chunked exports share the row writer and the text join.
+using axw::WindowLogOut;
+
+// Nothing of a log is written unless everything fits: the refusal names the count, and the caller comes again with that capacity.
+void require_win_cap(const char* who, size_t n_windows, int win_cap) {
+  if ((long)n_windows > win_cap)
+    throw std::runtime_error(std::string(who) + ": " + std::to_string(n_windows) + " windows were decoded, win_cap is " + std::to_string(win_cap));
+}
+
+// the rows of a log that fits; score_width: floats per win_score row (0 unscored, 3 scored, 7 with fallback)
+void write_window_rows(const std::vector<axw::LongWindow>& log, int Tc, int score_width, const WindowLogOut& out) {
+  for (size_t k = 0; k < log.size(); ++k) {
+    const axw::LongWindow& w = log[k];
+    const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
+    memcpy(out.win_info + k * 7, row, sizeof row);
+    memcpy(out.ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
+    float* sc = out.win_score + k * (size_t)score_width;
+    if (score_width >= 3) { sc[0] = w.no_speech_logprob; sc[1] = w.avg_logprob; sc[2] = w.skipped ? 1.f : 0.f; }
+    if (score_width == 7) { sc[3] = (float)w.attempt; sc[4] = w.temperature; sc[5] = w.compression_ratio; sc[6] = w.kept ? 1.f : 0.f; }
+    if (out.win_prompt) out.win_prompt[k] = w.n_prompt;
+  }
+  *out.n_windows = (int)log.size();
+}
+
+// the word part of a log (word-timestamp calls), under the same rule
+void write_word_log(const char* who, const std::vector<axw::LongWindow>& log, int Tc, AX_WHISPER_LONG_WORD_LOG* words) {
+  size_t n_seg = 0, n_word = 0;
+  for (const axw::LongWindow& w : log) { n_seg += w.seg_tokens.size(); n_word += w.words.size(); }
+  if (n_seg > (size_t)words->seg_cap) throw std::runtime_error(std::string(who) + ": " + std::to_string(n_seg) + " segments, seg_cap is " + std::to_string(words->seg_cap));
+  if (n_word > (size_t)words->word_cap) throw std::runtime_error(std::string(who) + ": " + std::to_string(n_word) + " words, word_cap is " + std::to_string(words->word_cap));
+  std::string all;
+  size_t sg = 0, wd = 0;
+  for (size_t k = 0; k < log.size(); ++k) {
+    const axw::LongWindow& w = log[k];
+    const int row[4] = {(int)w.text_ids.size(), (int)w.seg_tokens.size(), (int)w.words.size(), w.by_word_end ? 1 : 0};
+    memcpy(words->win_words + k * 4, row, sizeof row);
+    std::copy(w.text_ids.begin(), w.text_ids.end(), words->text_ids + k * (size_t)Tc);
+    std::copy(w.word_logprob.begin(), w.word_logprob.end(), words->token_logprob + k * (size_t)Tc);
+    std::copy(w.jump.begin(), w.jump.end(), words->jump + k * (size_t)(Tc + 1));
+    for (size_t s = 0; s < w.seg_tokens.size(); ++s, ++sg) {
+      words->seg_tokens[sg] = w.seg_tokens[s]; words->seg_start[sg] = w.seg_start[s]; words->seg_end[sg] = w.seg_end[s];
+    }
+    for (const axw::LongWord& x : w.words) {
+      all += x.text;
+      words->word_segment[wd] = x.segment; words->word_text_end[wd] = (int)all.size(); words->word_start[wd] = x.start; words->word_end[wd] = x.end;
+      words->word_prob[wd] = x.probability;
+      ++wd;
+    }
+  }
+  words->text = static_cast<char*>(malloc(all.size() + 1));
+  if (!words->text) throw std::runtime_error(std::string(who) + ": out of memory");
+  memcpy(words->text, all.data(), all.size());
+  words->text[all.size()] = 0;
+}
+
+// Window log: the seek loop over the files of export `who`, then its log written to `out`
+int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* const* pcm, const int* num_samples, int n_files, int max_new,
+                 int max_passes, const axw::LongCall& call, const WindowLogOut& out) {
+  axw::LongRun run;
+  if (!axw::long_run_options(call, n_files, out.lang_out, run)) return -1;
+  if (out.words) out.words->text = nullptr;
+  if (run.opts.word_timestamps && !axw::word_log_ok(out.words, out.win_cap)) return -1;
+  if (!handle || !axw::long_files_ok(pcm, num_samples, n_files) || !axw::window_log_ok(out, run.scored)) return -1;
+  *out.n_windows = 0;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    std::vector<axw::LongWindow> log;
+    g.run_long_windows(pcm, num_samples, n_files, max_new, max_passes, run.get(), log);
+    const int Tc = g.primary().config().n_text_ctx;
+    require_win_cap(who, log.size(), out.win_cap);
+    if (run.opts.word_timestamps) write_word_log(who, log, Tc, out.words);
+    write_window_rows(log, Tc, !run.scored ? 0 : run.opts.temperatures.empty() ? 3 : 7, out);
+  });
+}
+
+// the text of a log: the segments (segs(w): tok_begin / tok_end into w.ids) of every window that stands (kept, not skipped as silent),
+// joined; lang (or null: the handle's): the language index the text follows
+template <typename Segs>
+std::string join_segment_texts(Engine& e, const std::vector<axw::LongWindow>& log, const int* lang, Segs&& segs) {
+  std::string text;
+  for (const axw::LongWindow& w : log) {
+    if (w.skipped || !w.kept) continue;
+    for (const auto& sg : segs(w))  // host only
+      text += lang ? e.transcript_lang(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin, *lang)
+                   : e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);
+  }
+  return text;
+}
+
+// Text: the seek loop over one file, then the text of its windows. Calls that collect the language (the *Lang forms) answer it in
+// *lang_out (may be NULL), and the text follows it.
+int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const axw::LongCall& call, int* lang_out, char** result) {
+  axw::LongRun run;
+  if (!axw::long_run_options(call, 1, nullptr, run)) return -1;
+  if (!handle || !pcm_data || !result || num_samples < 1) return -1;
+  *result = nullptr;
+  const int rc = guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    Engine& e = g.primary();
+    std::vector<axw::LongWindow> log;
+    const float* files[1] = {pcm_data};
+    g.run_long_windows(files, &num_samples, 1, 0, 0, run.get(), log);
+    const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
+    std::vector<axw::WindowSegment> segs;
+    *result = strdup(join_segment_texts(e, log, run.lang.empty() ? nullptr : run.lang.data(), [&](const axw::LongWindow& w) -> const std::vector<axw::WindowSegment>& {
+      axw::split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
+      return segs;
+    }).c_str());
+  });
+  if (rc == 0 && lang_out && !run.lang.empty()) *lang_out = run.lang[0];
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -233,30 +374,8 @@ AX_WHISPER_API int AX_WHISPER_RunPCM(AX_WHISPER_HANDLE handle, float* pcm_data, 
   return AX_WHISPER_RunPCMBatch(handle, &pcm_data, &num_samples, 1, result);
 }
 
-// the file decode of RunFile / RunFileLong: false (and the handle's error text set) when the file cannot be used
-static bool load_wav_for_run(AX_WHISPER_HANDLE handle, const char* wav_file, axw::WavData& wav) {
-  std::string err;
-  if (!axw::load_audio_file(wav_file, wav, err)) {
-    H(handle)->set_error("load wav failed: " + err);
-    fprintf(stderr, "[ax_whisper] load wav failed: %s\n", err.c_str());
-    return false;
-  }
-  if (wav.mono.empty()) {
-    H(handle)->set_error("wav file holds no samples");
-    return false;
-  }
-  if (wav.sample_rate != 16000)  // the reference silently mis-transcribes (no resampler anywhere in its C++)
-    fprintf(stderr, "[ax_whisper] warning: %s is %d Hz, expected 16000 Hz (see cpp/resample_wav.sh of the reference)\n",
-            wav_file, wav.sample_rate);
-  return true;
-}
-
 AX_WHISPER_API int AX_WHISPER_RunFile(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCM(handle, wav.mono.data(), (int)wav.mono.size(), result);
+  return run_wav(handle, wav_file, result, [&](float* pcm, int n) { return AX_WHISPER_RunPCM(handle, pcm, n, result); });
 }
 
 // What every clip-batch and stage-level function below does: fill a request (iengine.hpp) and make the one call that takes it.
@@ -648,114 +767,26 @@ AX_WHISPER_API int AX_WHISPER_ComputeMelWindow(AX_WHISPER_HANDLE handle, const f
   return guarded(handle, [&](Engine& e) { e.compute_mel_window(pcm, num_samples, seek, mel_out); });
 }
 
-// the seek loop of RunPCMLongWindows[Scored] (`who`) and its log written out; opts / win_score: the scored call's, or nullptr
-static int long_windows(AX_WHISPER_HANDLE handle, const char* who, const float* const* pcm, const int* num_samples, int n_files, int max_new,
-                        int max_passes, const axw::LongScoreOptions* opts, int win_cap, int* win_info, int32_t* ids, float* win_score,
-                        int* n_windows, int* win_prompt = nullptr, AX_WHISPER_LONG_WORD_LOG* words = nullptr) {
-  const bool fallback = opts && !opts->temperatures.empty();  // win_score rows then have 7 entries
-  if (!handle || !pcm || !num_samples || n_files < 1 || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids || (opts && !win_score))))
-    return -1;
-  for (int b = 0; b < n_files; ++b)
-    if (!pcm[b] || num_samples[b] < 1) return -1;
-  *n_windows = 0;
-  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    std::vector<axw::LongWindow> log;
-    g.run_long_windows(pcm, num_samples, n_files, max_new, max_passes, opts, log);
-    // nothing is written unless everything fits
-    if ((long)log.size() > win_cap)
-      throw std::runtime_error(std::string(who) + ": " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
-    const int Tc = g.primary().config().n_text_ctx;
-    if (words) {  // the word log (word-timestamp calls), under the same rule
-      size_t n_seg = 0, n_word = 0;
-      for (const axw::LongWindow& w : log) { n_seg += w.seg_tokens.size(); n_word += w.words.size(); }
-      if (n_seg > (size_t)words->seg_cap) throw std::runtime_error(std::string(who) + ": " + std::to_string(n_seg) + " segments, seg_cap is " + std::to_string(words->seg_cap));
-      if (n_word > (size_t)words->word_cap) throw std::runtime_error(std::string(who) + ": " + std::to_string(n_word) + " words, word_cap is " + std::to_string(words->word_cap));
-      std::string all;
-      size_t sg = 0, wd = 0;
-      for (size_t k = 0; k < log.size(); ++k) {
-        const axw::LongWindow& w = log[k];
-        const int row[4] = {(int)w.text_ids.size(), (int)w.seg_tokens.size(), (int)w.words.size(), w.by_word_end ? 1 : 0};
-        memcpy(words->win_words + k * 4, row, sizeof row);
-        std::copy(w.text_ids.begin(), w.text_ids.end(), words->text_ids + k * (size_t)Tc);
-        std::copy(w.word_logprob.begin(), w.word_logprob.end(), words->token_logprob + k * (size_t)Tc);
-        std::copy(w.jump.begin(), w.jump.end(), words->jump + k * (size_t)(Tc + 1));
-        for (size_t s = 0; s < w.seg_tokens.size(); ++s, ++sg) {
-          words->seg_tokens[sg] = w.seg_tokens[s]; words->seg_start[sg] = w.seg_start[s]; words->seg_end[sg] = w.seg_end[s];
-        }
-        for (const axw::LongWord& x : w.words) {
-          all += x.text;
-          words->word_segment[wd] = x.segment; words->word_text_end[wd] = (int)all.size(); words->word_start[wd] = x.start; words->word_end[wd] = x.end;
-          words->word_prob[wd] = x.probability;
-          ++wd;
-        }
-      }
-      words->text = static_cast<char*>(malloc(all.size() + 1));
-      if (!words->text) throw std::runtime_error(std::string(who) + ": out of memory");
-      memcpy(words->text, all.data(), all.size());
-      words->text[all.size()] = 0;
-    }
-    for (size_t k = 0; k < log.size(); ++k) {
-      const axw::LongWindow& w = log[k];
-      const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
-      memcpy(win_info + k * 7, row, sizeof row);
-      memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
-      float* sc = opts ? win_score + k * (fallback ? 7 : 3) : nullptr;
-      if (opts) { sc[0] = w.no_speech_logprob; sc[1] = w.avg_logprob; sc[2] = w.skipped ? 1.f : 0.f; }
-      if (win_prompt) win_prompt[k] = w.n_prompt;
-      if (fallback) { sc[3] = (float)w.attempt; sc[4] = w.temperature; sc[5] = w.compression_ratio; sc[6] = w.kept ? 1.f : 0.f; }
-    }
-    *n_windows = (int)log.size();
-  });
-}
-
 AX_WHISPER_API int AX_WHISPER_RunPCMLongWindows(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
                                                 int max_new, int max_passes, int win_cap, int* win_info, int32_t* ids, int* n_windows) {
-  return long_windows(handle, "RunPCMLongWindows", pcm, num_samples, n_files, max_new, max_passes, nullptr, win_cap, win_info, ids, nullptr,
-                      n_windows);
-}
-
-// text of one file's windows; opts: the silent-window rule's thresholds, or nullptr (the unscored loop)
-// file_lang (the *Lang forms): where opts->file_lang_out puts the file's language; the text pass then follows it
-static int long_text(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, const axw::LongScoreOptions* opts, char** result,
-                     const int* file_lang = nullptr) {
-  if (!handle || !pcm_data || !result || num_samples < 1) return -1;
-  *result = nullptr;
-  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
-    Engine& e = g.primary();
-    std::vector<axw::LongWindow> log;
-    const float* files[1] = {pcm_data};
-    g.run_long_windows(files, &num_samples, 1, 0, 0, opts, log);
-    const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
-    std::string text;
-    std::vector<axw::WindowSegment> segs;
-    for (const axw::LongWindow& w : log) {
-      if (w.skipped || !w.kept) continue;
-      axw::split_window(w.ids.data(), (int)w.ids.size(), T, E, w.window_frames, segs);
-      for (const axw::WindowSegment& sg : segs)  // host only
-        text += file_lang ? e.transcript_lang(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin, *file_lang)
-                          : e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);
-    }
-    *result = strdup(text.c_str());
-  });
+  return long_windows(handle, "RunPCMLongWindows", pcm, num_samples, n_files, max_new, max_passes, axw::long_call_plain(),
+                      {win_cap, win_info, ids, nullptr, nullptr, n_windows, nullptr, nullptr});
 }
 
 AX_WHISPER_API int AX_WHISPER_RunPCMLong(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, char** result) {
-  return long_text(handle, pcm_data, num_samples, nullptr, result);
+  return long_text(handle, pcm_data, num_samples, axw::long_call_plain(), nullptr, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunPCMLongOpts(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
                                              float logprob_threshold, char** result) {
-  const axw::LongScoreOptions opts{no_speech_threshold, logprob_threshold};
-  return long_text(handle, pcm_data, num_samples, &opts, result);
+  return long_text(handle, pcm_data, num_samples, axw::long_call_scored(no_speech_threshold, logprob_threshold), nullptr, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLongOpts(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
                                               float logprob_threshold, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCMLongOpts(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold, result);
+  return run_wav(handle, wav_file, result, [&](float* pcm, int n) {
+    return AX_WHISPER_RunPCMLongOpts(handle, pcm, n, no_speech_threshold, logprob_threshold, result);
+  });
 }
 
 AX_WHISPER_API int AX_WHISPER_LongWindowIsSilent(float no_speech_logprob, float avg_logprob, float no_speech_threshold,
@@ -767,9 +798,9 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsScored(AX_WHISPER_HANDLE handle, 
                                                       int n_files, int max_new, int max_passes, float no_speech_threshold,
                                                       float logprob_threshold, int win_cap, int* win_info, int32_t* ids, float* win_score,
                                                       int* n_windows) {
-  const axw::LongScoreOptions opts{no_speech_threshold, logprob_threshold};
-  return long_windows(handle, "RunPCMLongWindowsScored", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids, win_score,
-                      n_windows);
+  return long_windows(handle, "RunPCMLongWindowsScored", pcm, num_samples, n_files, max_new, max_passes,
+                      axw::long_call_scored(no_speech_threshold, logprob_threshold),
+                      {win_cap, win_info, ids, win_score, nullptr, n_windows, nullptr, nullptr});
 }
 
 // ---- temperature fallback (DESIGN.md "Temperature fallback")
@@ -824,49 +855,31 @@ AX_WHISPER_API int AX_WHISPER_WindowNeedsFallback(float compression_ratio, float
                                     no_speech_threshold) ? 1 : 0;
 }
 
-// the options of the three fallback calls; false: a bad temperature list
-static bool fallback_options(float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
-                             int n_temperatures, uint64_t seed, axw::LongScoreOptions& opts) {
-  if (!temperatures || n_temperatures < 1 || n_temperatures > 16) return false;
-  opts.no_speech_threshold = no_speech_threshold; opts.logprob_threshold = logprob_threshold;
-  opts.compression_ratio_threshold = compression_ratio_threshold;
-  opts.temperatures.assign(temperatures, temperatures + n_temperatures);
-  opts.seed = seed;
-  return true;
-}
-
 AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsFallback(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
                                                         int n_files, int max_new, int max_passes, float no_speech_threshold,
                                                         float logprob_threshold, float compression_ratio_threshold,
                                                         const float* temperatures, int n_temperatures, uint64_t seed, const int* file_ids,
                                                         int win_cap, int* win_info, int32_t* ids, float* win_score, int* n_windows) {
-  axw::LongScoreOptions opts{};
-  if (!fallback_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, opts)) return -1;
-  for (int f = 0; file_ids && f < n_files; ++f) {
-    if (file_ids[f] < 0 || file_ids[f] >= (1 << 27)) return -1;  // (id * 16 + attempt is the stream's high word)
-    opts.file_ids.push_back(file_ids[f]);
-  }
-  return long_windows(handle, "RunPCMLongWindowsFallback", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids,
-                      win_score, n_windows);
+  return long_windows(handle, "RunPCMLongWindowsFallback", pcm, num_samples, n_files, max_new, max_passes,
+                      axw::long_call_fallback(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, file_ids),
+                      {win_cap, win_info, ids, win_score, nullptr, n_windows, nullptr, nullptr});
 }
 
 AX_WHISPER_API int AX_WHISPER_RunPCMLongFallback(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
                                                  float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
                                                  int n_temperatures, uint64_t seed, char** result) {
-  axw::LongScoreOptions opts{};
-  if (!fallback_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, opts)) return -1;
-  return long_text(handle, pcm_data, num_samples, &opts, result);
+  return long_text(handle, pcm_data, num_samples,
+                   axw::long_call_fallback(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, nullptr),
+                   nullptr, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLongFallback(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
                                                   float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
                                                   int n_temperatures, uint64_t seed, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCMLongFallback(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
-                                       compression_ratio_threshold, temperatures, n_temperatures, seed, result);
+  return run_wav(handle, wav_file, result, [&](float* pcm, int n) {
+    return AX_WHISPER_RunPCMLongFallback(handle, pcm, n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures,
+                                         n_temperatures, seed, result);
+  });
 }
 
 // ---- prompt conditioning (DESIGN.md "Prompt conditioning")
@@ -1007,27 +1020,6 @@ AX_WHISPER_API int AX_WHISPER_CarryPrompt(const int32_t* all_ids, int n_all, int
   });
 }
 
-// the options of the three prompted long-form calls; false: bad arguments
-static bool prompted_options(float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
-                             int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int prompt_stride, const int* n_initial,
-                             int n_files, int condition_on_previous_text, axw::LongScoreOptions& opts) {
-  if (n_temperatures < 0 || n_temperatures > 16 || (n_temperatures > 0 && !temperatures) || n_files < 1) return false;
-  opts.no_speech_threshold = no_speech_threshold; opts.logprob_threshold = logprob_threshold;
-  opts.compression_ratio_threshold = compression_ratio_threshold;
-  if (n_temperatures > 0) opts.temperatures.assign(temperatures, temperatures + n_temperatures);
-  opts.seed = seed;
-  opts.condition_on_previous_text = condition_on_previous_text != 0;
-  if (n_initial) {
-    if (prompt_stride < 0) return false;
-    opts.initial_prompt_ids.resize(n_files);
-    for (int f = 0; f < n_files; ++f) {
-      if (n_initial[f] < 0 || n_initial[f] > prompt_stride || (n_initial[f] > 0 && !initial_prompt_ids)) return false;
-      if (n_initial[f] > 0) opts.initial_prompt_ids[f].assign(initial_prompt_ids + (size_t)f * prompt_stride, initial_prompt_ids + (size_t)f * prompt_stride + n_initial[f]);
-    }
-  }
-  return true;
-}
-
 AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsPrompted(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples,
                                                         int n_files, int max_new, int max_passes, float no_speech_threshold,
                                                         float logprob_threshold, float compression_ratio_threshold,
@@ -1035,40 +1027,30 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsPrompted(AX_WHISPER_HANDLE handle
                                                         const int32_t* initial_prompt_ids, int prompt_stride, const int* n_initial,
                                                         int condition_on_previous_text, int win_cap, int* win_info, int32_t* ids,
                                                         float* win_score, int* win_prompt, int* n_windows) {
-  axw::LongScoreOptions opts{};
-  if (!prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids,
-                        prompt_stride, n_initial, n_files, condition_on_previous_text, opts))
-    return -1;
-  for (int f = 0; file_ids && f < n_files; ++f) {
-    if (file_ids[f] < 0 || file_ids[f] >= (1 << 27)) return -1;
-    opts.file_ids.push_back(file_ids[f]);
-  }
-  return long_windows(handle, "RunPCMLongWindowsPrompted", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids,
-                      win_score, n_windows, win_prompt);
+  return long_windows(handle, "RunPCMLongWindowsPrompted", pcm, num_samples, n_files, max_new, max_passes,
+                      axw::long_call_prompted(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed,
+                                              file_ids, initial_prompt_ids, prompt_stride, n_initial, condition_on_previous_text),
+                      {win_cap, win_info, ids, win_score, win_prompt, n_windows, nullptr, nullptr});
 }
 
 AX_WHISPER_API int AX_WHISPER_RunPCMLongPrompted(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
                                                  float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
                                                  int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
                                                  int condition_on_previous_text, char** result) {
-  axw::LongScoreOptions opts{};
-  if (n_initial < 0 || !prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed,
-                                         initial_prompt_ids, n_initial, &n_initial, 1, condition_on_previous_text, opts))
-    return -1;
-  return long_text(handle, pcm_data, num_samples, &opts, result);
+  return long_text(handle, pcm_data, num_samples,
+                   axw::long_call_prompted(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed,
+                                           nullptr, initial_prompt_ids, n_initial, &n_initial, condition_on_previous_text),
+                   nullptr, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLongPrompted(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold,
                                                   float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
                                                   int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
                                                   int condition_on_previous_text, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCMLongPrompted(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
-                                       compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids, n_initial,
-                                       condition_on_previous_text, result);
+  return run_wav(handle, wav_file, result, [&](float* pcm, int n) {
+    return AX_WHISPER_RunPCMLongPrompted(handle, pcm, n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures,
+                                         n_temperatures, seed, initial_prompt_ids, n_initial, condition_on_previous_text, result);
+  });
 }
 
 // ---- long-form under a language and task per file (DESIGN.md "Language and task per clip")
@@ -1079,58 +1061,38 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsLang(AX_WHISPER_HANDLE handle, co
                                                     const int* n_initial, int condition_on_previous_text, const int* lang, const int* task,
                                                     int win_cap, int* win_info, int32_t* ids, float* win_score, int* win_prompt,
                                                     int* n_windows, int* lang_out) {
-  axw::LongScoreOptions opts{};
-  if (!prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids,
-                        prompt_stride, n_initial, n_files, condition_on_previous_text, opts))
-    return -1;
-  for (int f = 0; file_ids && f < n_files; ++f) {
-    if (file_ids[f] < 0 || file_ids[f] >= (1 << 27)) return -1;
-    opts.file_ids.push_back(file_ids[f]);
-  }
-  if (lang) opts.file_lang.assign(lang, lang + n_files);
-  if (task) opts.file_task.assign(task, task + n_files);
-  std::vector<int> got((size_t)n_files, -1);
-  opts.file_lang_out = lang_out ? lang_out : got.data();
-  return long_windows(handle, "RunPCMLongWindowsLang", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids, win_score,
-                      n_windows, win_prompt);
+  return long_windows(handle, "RunPCMLongWindowsLang", pcm, num_samples, n_files, max_new, max_passes,
+                      axw::long_call_lang(axw::long_call_prompted(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures,
+                                                                  n_temperatures, seed, file_ids, initial_prompt_ids, prompt_stride, n_initial,
+                                                                  condition_on_previous_text),
+                                          lang, task),
+                      {win_cap, win_info, ids, win_score, win_prompt, n_windows, lang_out, nullptr});
 }
 
 AX_WHISPER_API int AX_WHISPER_RunPCMLongLang(AX_WHISPER_HANDLE handle, float* pcm_data, int num_samples, float no_speech_threshold,
                                              float logprob_threshold, float compression_ratio_threshold, const float* temperatures,
                                              int n_temperatures, uint64_t seed, const int32_t* initial_prompt_ids, int n_initial,
                                              int condition_on_previous_text, int lang, int task, int* lang_out, char** result) {
-  axw::LongScoreOptions opts{};
-  if (n_initial < 0 || !prompted_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures, seed,
-                                         initial_prompt_ids, n_initial, &n_initial, 1, condition_on_previous_text, opts))
-    return -1;
-  opts.file_lang.assign(1, lang);
-  opts.file_task.assign(1, task);
-  int got = -1;
-  opts.file_lang_out = &got;
-  const int rc = long_text(handle, pcm_data, num_samples, &opts, result, &got);
-  if (rc == 0 && lang_out) *lang_out = got;
-  return rc;
+  return long_text(handle, pcm_data, num_samples,
+                   axw::long_call_lang(axw::long_call_prompted(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures,
+                                                               n_temperatures, seed, nullptr, initial_prompt_ids, n_initial, &n_initial,
+                                                               condition_on_previous_text),
+                                       &lang, &task),
+                   lang_out, result);
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLongLang(AX_WHISPER_HANDLE handle, const char* wav_file, float no_speech_threshold, float logprob_threshold,
                                               float compression_ratio_threshold, const float* temperatures, int n_temperatures, uint64_t seed,
                                               const int32_t* initial_prompt_ids, int n_initial, int condition_on_previous_text, int lang,
                                               int task, int* lang_out, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCMLongLang(handle, wav.mono.data(), (int)wav.mono.size(), no_speech_threshold, logprob_threshold,
-                                   compression_ratio_threshold, temperatures, n_temperatures, seed, initial_prompt_ids, n_initial,
-                                   condition_on_previous_text, lang, task, lang_out, result);
+  return run_wav(handle, wav_file, result, [&](float* pcm, int n) {
+    return AX_WHISPER_RunPCMLongLang(handle, pcm, n, no_speech_threshold, logprob_threshold, compression_ratio_threshold, temperatures, n_temperatures,
+                                     seed, initial_prompt_ids, n_initial, condition_on_previous_text, lang, task, lang_out, result);
+  });
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLong(AX_WHISPER_HANDLE handle, const char* wav_file, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCMLong(handle, wav.mono.data(), (int)wav.mono.size(), result);
+  return run_wav(handle, wav_file, result, [&](float* pcm, int n) { return AX_WHISPER_RunPCMLong(handle, pcm, n, result); });
 }
 
 AX_WHISPER_API int AX_WHISPER_DecodeGreedy(AX_WHISPER_HANDLE handle, int batch, int max_new, int32_t* ids, int* n_ids) {
@@ -1272,39 +1234,12 @@ AX_WHISPER_API int AX_WHISPER_LongWordAdvance(const int32_t* ids, int n, int tim
   return 0;
 }
 
-// AX_WHISPER_LONG_OPTIONS -> LongScoreOptions (as RunPCMLongWindowsLang reads its arguments); got: where file_lang_out points when
-// the caller passes no lang_out
-static bool long_options(const AX_WHISPER_LONG_OPTIONS* o, int n_files, int* lang_out, std::vector<int>& got, axw::LongScoreOptions& opts) {
-  if (!o || n_files < 1) return false;
-  if (!prompted_options(o->no_speech_threshold, o->logprob_threshold, o->compression_ratio_threshold, o->temperatures, o->n_temperatures, o->seed,
-                        o->initial_prompt_ids, o->prompt_stride, o->n_initial, n_files, o->condition_on_previous_text, opts))
-    return false;
-  for (int f = 0; o->file_ids && f < n_files; ++f) {
-    if (o->file_ids[f] < 0 || o->file_ids[f] >= (1 << 27)) return false;
-    opts.file_ids.push_back(o->file_ids[f]);
-  }
-  if (o->lang) opts.file_lang.assign(o->lang, o->lang + n_files);
-  if (o->task) opts.file_task.assign(o->task, o->task + n_files);
-  got.assign((size_t)n_files, -1);
-  opts.file_lang_out = lang_out ? lang_out : got.data();
-  opts.word_timestamps = o->word_timestamps != 0;
-  return true;
-}
-
 AX_WHISPER_API int AX_WHISPER_RunPCMLongWindowsWords(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
                                                      int max_new, int max_passes, const AX_WHISPER_LONG_OPTIONS* o, int win_cap, int* win_info,
                                                      int32_t* ids, float* win_score, int* win_prompt, int* n_windows, int* lang_out,
                                                      AX_WHISPER_LONG_WORD_LOG* words) {
-  axw::LongScoreOptions opts{};
-  std::vector<int> got;
-  if (!long_options(o, n_files, lang_out, got, opts)) return -1;
-  if (words) words->text = nullptr;
-  if (opts.word_timestamps && (!words || words->seg_cap < 0 || words->word_cap < 0 || (win_cap > 0 && (!words->win_words || !words->text_ids || !words->jump ||
-      !words->token_logprob)) || (words->seg_cap > 0 && (!words->seg_tokens || !words->seg_start || !words->seg_end)) ||
-      (words->word_cap > 0 && (!words->word_segment || !words->word_text_end || !words->word_start || !words->word_end || !words->word_prob))))
-    return -1;
-  return long_windows(handle, "RunPCMLongWindowsWords", pcm, num_samples, n_files, max_new, max_passes, &opts, win_cap, win_info, ids, win_score,
-                      n_windows, win_prompt, opts.word_timestamps ? words : nullptr);
+  return long_windows(handle, "RunPCMLongWindowsWords", pcm, num_samples, n_files, max_new, max_passes, axw::long_call_options(o, false),
+                      {win_cap, win_info, ids, win_score, win_prompt, n_windows, lang_out, words});
 }
 
 // one file's log -> its segments and words; the arrays are malloc'ed into out
@@ -1358,29 +1293,22 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongWords(AX_WHISPER_HANDLE handle, float* p
                                               int* lang_out, AX_WHISPER_LONG_WORDS* out) {
   if (!handle || !pcm_data || num_samples < 1 || !out) return -1;
   *out = AX_WHISPER_LONG_WORDS{};
-  axw::LongScoreOptions opts{};
-  std::vector<int> got;
-  int file_lang = -1;
-  if (!long_options(o, 1, &file_lang, got, opts)) return -1;
-  opts.word_timestamps = true;
+  axw::LongRun run;
+  if (!axw::long_run_options(axw::long_call_options(o, true), 1, nullptr, run)) return -1;
   const int rc = guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     std::vector<axw::LongWindow> log;
     const float* files[1] = {pcm_data};
-    g.run_long_windows(files, &num_samples, 1, 0, 0, &opts, log);
-    long_words_result(g.primary(), log, file_lang, out);
+    g.run_long_windows(files, &num_samples, 1, 0, 0, run.get(), log);
+    long_words_result(g.primary(), log, run.lang[0], out);
   });
   if (rc != 0) AX_WHISPER_FreeLongWords(out);
-  if (rc == 0 && lang_out) *lang_out = file_lang;
+  if (rc == 0 && lang_out) *lang_out = run.lang[0];
   return rc;
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLongWords(AX_WHISPER_HANDLE handle, const char* wav_file, const AX_WHISPER_LONG_OPTIONS* o, int* lang_out,
                                                AX_WHISPER_LONG_WORDS* out) {
-  if (!handle || !wav_file || !out) return -1;
-  *out = AX_WHISPER_LONG_WORDS{};
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCMLongWords(handle, wav.mono.data(), (int)wav.mono.size(), o, lang_out, out);
+  return run_wav(handle, wav_file, out, [&](float* pcm, int n) { return AX_WHISPER_RunPCMLongWords(handle, pcm, n, o, lang_out, out); });
 }
 
 // Host only: the alignment heads a handle constructed from this config file starts with
@@ -1683,16 +1611,9 @@ AX_WHISPER_API int AX_WHISPER_ChunkedSegments(const int32_t* ids, int n, int tim
   });
 }
 
-static bool files_ok(const float* const* pcm, const int* num_samples, int n_files) {
-  if (!pcm || !num_samples || n_files < 1) return false;
-  for (int b = 0; b < n_files; ++b)
-    if (!pcm[b] || num_samples[b] < 1) return false;
-  return true;
-}
-
 AX_WHISPER_API int AX_WHISPER_LongFrameLevels(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
                                               int smooth_frames, float* const* e, float* const* s) {
-  if (!handle || !files_ok(pcm, num_samples, n_files)) return -1;
+  if (!handle || !axw::long_files_ok(pcm, num_samples, n_files)) return -1;
   return guarded(handle, [&](Engine& en) { en.long_frame_levels(pcm, num_samples, n_files, smooth_frames, e, s); });
 }
 
@@ -1718,7 +1639,7 @@ static axw::CutParams cut_params(const AX_WHISPER_CHUNK_OPTIONS* c) {
 AX_WHISPER_API int AX_WHISPER_LongCutPlan(AX_WHISPER_HANDLE handle, const float* const* pcm, const int* num_samples, int n_files,
                                           const AX_WHISPER_CHUNK_OPTIONS* chunk, int win_cap, int* n_windows, int* win_file, int* win_seek,
                                           int* win_len, float* const* s) {
-  if (!handle || !files_ok(pcm, num_samples, n_files) || !n_windows || win_cap < 0 || (win_cap > 0 && (!win_file || !win_seek || !win_len))) return -1;
+  if (!handle || !axw::long_files_ok(pcm, num_samples, n_files) || !n_windows || win_cap < 0 || (win_cap > 0 && (!win_file || !win_seek || !win_len))) return -1;
   return guarded(handle, [&](Engine& e) {
     std::vector<int> n, wf, ws, wl;
     e.long_cut_plan(pcm, num_samples, n_files, cut_params(chunk), n, wf, ws, wl, s);
@@ -1760,24 +1681,15 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongChunkedWindows(AX_WHISPER_HANDLE handle,
                                                        int max_new, int max_passes, const AX_WHISPER_CHUNK_OPTIONS* chunk,
                                                        const AX_WHISPER_LONG_OPTIONS* o, int win_cap, int* win_info, int32_t* ids,
                                                        float* win_score, int* n_windows) {
-  if (!handle || !files_ok(pcm, num_samples, n_files) || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids))) return -1;
+  if (!handle || !axw::long_files_ok(pcm, num_samples, n_files) || win_cap < 0 || !n_windows || (win_cap > 0 && (!win_info || !ids))) return -1;
   *n_windows = 0;
   const axw::ChunkedOptions opts = chunked_options(chunk, o, n_files, win_score != nullptr);
   if (opts.scored && win_cap > 0 && !win_score) return -1;
   return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
     std::vector<axw::LongWindow> log;
     g.run_long_chunked(pcm, num_samples, n_files, max_new, max_passes, opts, log);
-    if ((long)log.size() > win_cap)  // nothing is written unless everything fits
-      throw std::runtime_error("RunPCMLongChunkedWindows: " + std::to_string(log.size()) + " windows were decoded, win_cap is " + std::to_string(win_cap));
-    const int Tc = g.primary().config().n_text_ctx;
-    for (size_t k = 0; k < log.size(); ++k) {
-      const axw::LongWindow& w = log[k];
-      const int row[7] = {w.file, w.seek, w.window_frames, w.advance, (int)w.ids.size(), w.pass, w.slot};
-      memcpy(win_info + k * 7, row, sizeof row);
-      memcpy(ids + k * (size_t)Tc, w.ids.data(), w.ids.size() * sizeof(int32_t));
-      if (opts.scored) { win_score[k * 3] = w.no_speech_logprob; win_score[k * 3 + 1] = w.avg_logprob; win_score[k * 3 + 2] = w.skipped ? 1.f : 0.f; }
-    }
-    *n_windows = (int)log.size();
+    require_win_cap("RunPCMLongChunkedWindows", log.size(), win_cap);
+    write_window_rows(log, g.primary().config().n_text_ctx, opts.scored ? 3 : 0, {win_cap, win_info, ids, win_score, nullptr, n_windows, nullptr, nullptr});
   });
 }
 
@@ -1793,24 +1705,15 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongChunked(AX_WHISPER_HANDLE handle, float*
     g.run_long_chunked(files, &num_samples, 1, 0, 0, opts, log);
     const int T = (int)e.config().ints.at("timestamp_begin"), E = e.config().eot;
     const bool lang = !opts.file_lang.empty() && opts.file_lang[0] >= 0;
-    std::string text;
-    for (const axw::LongWindow& w : log) {
-      if (w.skipped) continue;
-      for (const axw::ChunkSegment& sg : axw::chunked_segments(w.ids.data(), (int)w.ids.size(), T, E, w.seek, w.window_frames))  // host only
-        text += lang ? e.transcript_lang(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin, opts.file_lang[0])
-                     : e.transcript(w.ids.data() + sg.tok_begin, sg.tok_end - sg.tok_begin);
-    }
-    *result = strdup(text.c_str());
+    *result = strdup(join_segment_texts(e, log, lang ? &opts.file_lang[0] : nullptr, [&](const axw::LongWindow& w) {
+      return axw::chunked_segments(w.ids.data(), (int)w.ids.size(), T, E, w.seek, w.window_frames);
+    }).c_str());
   });
 }
 
 AX_WHISPER_API int AX_WHISPER_RunFileLongChunked(AX_WHISPER_HANDLE handle, const char* wav_file, const AX_WHISPER_CHUNK_OPTIONS* chunk,
                                                  const AX_WHISPER_LONG_OPTIONS* o, char** result) {
-  if (!handle || !wav_file || !result) return -1;
-  *result = nullptr;
-  axw::WavData wav;
-  if (!load_wav_for_run(handle, wav_file, wav)) return -1;
-  return AX_WHISPER_RunPCMLongChunked(handle, wav.mono.data(), (int)wav.mono.size(), chunk, o, result);
+  return run_wav(handle, wav_file, result, [&](float* pcm, int n) { return AX_WHISPER_RunPCMLongChunked(handle, pcm, n, chunk, o, result); });
 }
 
 AX_WHISPER_API int AX_WHISPER_GetTimings(AX_WHISPER_HANDLE handle, float* out5) {

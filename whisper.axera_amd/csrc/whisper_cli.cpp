@@ -234,6 +234,64 @@ static int print_words(AX_WHISPER_HANDLE h, const char* wav) {
   return 0;
 }
 
+// ---- --long. Shared by its modes: the options as the library's struct, and one file's samples with the buffers of its window log.
+// n_initial / lang / task are the caller's own (the struct points at them); no temperatures: a NULL list.
+static AX_WHISPER_LONG_OPTIONS long_options(float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold,
+                                            const std::vector<float>& temps, unsigned long long seed, const std::vector<int32_t>& prompt_ids,
+                                            const int* n_initial, bool condition, const int* lang, const int* task, bool word_timestamps) {
+  AX_WHISPER_LONG_OPTIONS o{};
+  o.no_speech_threshold = no_speech_threshold; o.logprob_threshold = logprob_threshold; o.compression_ratio_threshold = compression_ratio_threshold;
+  o.temperatures = temps.empty() ? nullptr : temps.data(); o.n_temperatures = (int)temps.size(); o.seed = seed;
+  o.initial_prompt_ids = prompt_ids.data(); o.prompt_stride = *n_initial; o.n_initial = n_initial; o.condition_on_previous_text = condition ? 1 : 0;
+  o.lang = lang; o.task = task; o.word_timestamps = word_timestamps ? 1 : 0;
+  return o;
+}
+
+struct LongLog {
+  float* pcm = nullptr;
+  int n = 0, n_ctx = 448, n_win = 0;
+  size_t sw = 0;  // floats per score row: 0 (unscored), 3, or 7 with fallback
+  std::vector<int> info;
+  std::vector<int32_t> ids;
+  std::vector<float> score;
+  ~LongLog() { free(pcm); }
+  bool load(AX_WHISPER_HANDLE h, const char* wav) {
+    if (AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0) n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx");
+    return load_pcm(h, wav, &pcm, &n) == 0 && n >= 1;
+  }
+  void size(int cap, size_t score_width) { sw = score_width; info.resize((size_t)cap * 7); ids.resize((size_t)cap * n_ctx); score.resize((size_t)cap * sw); }
+  // Text and lines of the log: silent windows and attempts that were decoded again print nothing, the other lines end in their
+  // window's numbers. segs(info row, ids, n_max, start_ms, end_ms, tok_begin, tok_end) -> the window's segments in file time, or -1.
+  // (absolute times in integer milliseconds: a float second loses the millisecond after a few hours)
+  template <typename Segs>
+  int print(AX_WHISPER_HANDLE h, bool per_lang, int lang, Segs&& segs, std::string& text, std::string& lines) const {
+    for (int k = 0; k < n_win; ++k) {
+      const float* sc = sw ? &score[(size_t)k * sw] : nullptr;
+      if ((sw && sc[2] != 0.f) || (sw == 7 && sc[6] == 0.f)) continue;
+      char tail[160] = "";
+      if (sw) snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g)", sc[1], std::exp(sc[0]));
+      if (sw == 7)
+        snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g, temperature %.1f, compression_ratio %.3f)", sc[1], std::exp(sc[0]), sc[4], sc[5]);
+      const int* w = &info[(size_t)k * 7];
+      const int32_t* wi = &ids[(size_t)k * n_ctx];
+      const int n_max = w[4] / 2 + 1;
+      std::vector<long> st(n_max), en(n_max);
+      std::vector<int> tb(n_max), te(n_max);
+      const int n_seg = segs(w, wi, n_max, st.data(), en.data(), tb.data(), te.data());
+      if (n_seg < 0) return -1;
+      for (int s = 0; s < n_seg; ++s) {
+        char* t = nullptr;
+        if ((per_lang ? AX_WHISPER_TranscriptLang(h, wi + tb[s], te[s] - tb[s], lang, &t) : AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t)) != 0)
+          return -1;
+        text += t ? t : "";
+        lines += "[" + mmss_ms(st[s]) + " --> " + mmss_ms(en[s]) + "] " + (t ? t : "") + tail + "\n";
+        free(t);
+      }
+    }
+    return 0;
+  }
+};
+
 // --long: the seek loop over the whole file (AX_WHISPER_RunPCMLongWindows), its text, then one line per segment.
 // scored: under the silent-window rule (AX_WHISPER_RunPCMLongWindowsScored); skipped windows print nothing, the other lines end
 // in their window's two numbers
@@ -247,66 +305,43 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
                     int task = -1) {
   const bool per_lang = detect || task >= 0;
   const bool fallback = !temps.empty();
-  const size_t sw = fallback ? 7 : 3;  // floats per window score row
-  float* pcm = nullptr;
-  int n = 0;
-  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
-  const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
-  const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
-  int cap = (n / 160 + 1) * (fallback ? (int)temps.size() : 1);  // every window advances by at least one frame (after at most temps.size() attempts)
-  std::vector<int> info((size_t)cap * 7);
-  std::vector<int32_t> ids((size_t)cap * n_ctx);
-  std::vector<float> score(scored ? (size_t)cap * sw : 0);
-  int n_win = 0;
-  const float* files[1] = {pcm};
-  const int n_initial = (int)prompt_ids.size();
+  LongLog L;
+  if (!L.load(h, wav)) return -1;
+  const int cap = (L.n / 160 + 1) * (fallback ? (int)temps.size() : 1);  // every window advances by at least one frame (after at most temps.size() attempts)
+  L.size(cap, !scored ? 0 : fallback ? 7 : 3);
+  const float* files[1] = {L.pcm};
+  const int n_initial = (int)prompt_ids.size(), tk = task > 0 ? 1 : 0;
   int lang = -1;
-  const int tk = task > 0 ? 1 : 0;
-  if (detect && (lang = detect_and_print(h, pcm, n)) < 0) { free(pcm); return -1; }
+  if (detect && (lang = detect_and_print(h, L.pcm, L.n)) < 0) return -1;
   const int want = lang;
-  const int rc = per_lang ? AX_WHISPER_RunPCMLongWindowsLang(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
-                                                             compression_ratio_threshold, fallback ? temps.data() : nullptr, (int)temps.size(),
-                                                             seed, nullptr, prompt_ids.data(), n_initial, &n_initial, condition ? 1 : 0,
-                                                             &want, &tk, cap, info.data(), ids.data(), score.data(), nullptr,
-                                                             &n_win, &lang)
-                 : prompted ? AX_WHISPER_RunPCMLongWindowsPrompted(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
-                                                                 compression_ratio_threshold, fallback ? temps.data() : nullptr, (int)temps.size(),
-                                                                 seed, nullptr, prompt_ids.data(), n_initial, &n_initial, condition ? 1 : 0, cap,
-                                                                 info.data(), ids.data(), score.data(), nullptr, &n_win)
-                 : fallback ? AX_WHISPER_RunPCMLongWindowsFallback(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold,
-                                                                 compression_ratio_threshold, temps.data(), (int)temps.size(), seed, nullptr, cap,
-                                                                 info.data(), ids.data(), score.data(), &n_win)
-                 : scored ? AX_WHISPER_RunPCMLongWindowsScored(h, files, &n, 1, 0, 0, no_speech_threshold, logprob_threshold, cap, info.data(),
-                                                             ids.data(), score.data(), &n_win)
-                        : AX_WHISPER_RunPCMLongWindows(h, files, &n, 1, 0, 0, cap, info.data(), ids.data(), &n_win);
-  free(pcm);
+  const AX_WHISPER_LONG_OPTIONS o = long_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompt_ids, &n_initial,
+                                                 condition, &want, &tk, false);
+  int* const info = L.info.data();
+  int32_t* const ids = L.ids.data();
+  float* const score = L.score.data();
+  const int rc = per_lang ? AX_WHISPER_RunPCMLongWindowsLang(h, files, &L.n, 1, 0, 0, o.no_speech_threshold, o.logprob_threshold, o.compression_ratio_threshold,
+                                                             o.temperatures, o.n_temperatures, o.seed, nullptr, o.initial_prompt_ids, o.prompt_stride,
+                                                             o.n_initial, o.condition_on_previous_text, o.lang, o.task, cap, info, ids, score, nullptr,
+                                                             &L.n_win, &lang)
+                 : prompted ? AX_WHISPER_RunPCMLongWindowsPrompted(h, files, &L.n, 1, 0, 0, o.no_speech_threshold, o.logprob_threshold,
+                                                                 o.compression_ratio_threshold, o.temperatures, o.n_temperatures, o.seed, nullptr,
+                                                                 o.initial_prompt_ids, o.prompt_stride, o.n_initial, o.condition_on_previous_text, cap,
+                                                                 info, ids, score, nullptr, &L.n_win)
+                 : fallback ? AX_WHISPER_RunPCMLongWindowsFallback(h, files, &L.n, 1, 0, 0, o.no_speech_threshold, o.logprob_threshold,
+                                                                 o.compression_ratio_threshold, o.temperatures, o.n_temperatures, o.seed, nullptr, cap,
+                                                                 info, ids, score, &L.n_win)
+                 : scored ? AX_WHISPER_RunPCMLongWindowsScored(h, files, &L.n, 1, 0, 0, o.no_speech_threshold, o.logprob_threshold, cap, info, ids, score,
+                                                             &L.n_win)
+                        : AX_WHISPER_RunPCMLongWindows(h, files, &L.n, 1, 0, 0, cap, info, ids, &L.n_win);
   if (rc != 0) return -1;
-  for (int k = 0; k < n_win; ++k) {
-    if (scored && score[(size_t)k * sw + 2] != 0.f) continue;  // a silent window
-    if (fallback && score[(size_t)k * sw + 6] == 0.f) continue;  // an attempt that was decoded again
-    char tail[160] = "";
-    if (scored) snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g)", score[(size_t)k * sw + 1], std::exp(score[(size_t)k * sw]));
-    if (fallback)
-      snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g, temperature %.1f, compression_ratio %.3f)", score[(size_t)k * sw + 1],
-               std::exp(score[(size_t)k * sw]), score[(size_t)k * sw + 4], score[(size_t)k * sw + 5]);
-    const int* w = &info[(size_t)k * 7];
-    const int32_t* wi = &ids[(size_t)k * n_ctx];
-    const int n_max = w[4] / 2 + 1;
-    std::vector<float> st(n_max), en(n_max);
-    std::vector<int> tb(n_max), te(n_max);
+  const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
+  return L.print(h, per_lang, lang, [&](const int* w, const int32_t* wi, int n_max, long* st, long* en, int* tb, int* te) {
+    std::vector<float> s(n_max), e(n_max);
     int n_seg = 0, adv = 0;
-    if (AX_WHISPER_SplitWindow(wi, w[4], T, E, w[2], n_max, st.data(), en.data(), tb.data(), te.data(), &n_seg, &adv) != 0) return -1;
-    for (int s = 0; s < n_seg; ++s) {
-      char* t = nullptr;
-      if ((per_lang ? AX_WHISPER_TranscriptLang(h, wi + tb[s], te[s] - tb[s], lang, &t) : AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t)) != 0)
-        return -1;
-      text += t ? t : "";
-      // (absolute times in integer milliseconds: a float second loses the millisecond after a few hours)
-      lines += "[" + mmss_ms(w[1] * 10L + (long)(st[s] * 1000.f + 0.5f)) + " --> " + mmss_ms(w[1] * 10L + (long)(en[s] * 1000.f + 0.5f)) + "] " + (t ? t : "") + tail + "\n";
-      free(t);
-    }
-  }
-  return 0;
+    if (AX_WHISPER_SplitWindow(wi, w[4], T, E, w[2], n_max, s.data(), e.data(), tb, te, &n_seg, &adv) != 0) return -1;
+    for (int k = 0; k < n_seg; ++k) { st[k] = w[1] * 10L + (long)(s[k] * 1000.f + 0.5f); en[k] = w[1] * 10L + (long)(e[k] * 1000.f + 0.5f); }
+    return n_seg;
+  }, text, lines);
 }
 
 // --long --chunked: the windows are chosen before decoding (cuts at quiet frames) and decoded side by side
@@ -315,49 +350,27 @@ static int run_long(AX_WHISPER_HANDLE h, const char* wav, bool scored, float no_
 static int run_long_chunked(AX_WHISPER_HANDLE h, const char* wav, const AX_WHISPER_CHUNK_OPTIONS& chunk, bool scored, float no_speech_threshold,
                             float logprob_threshold, float compression_ratio_threshold, const std::vector<float>& temps, const std::vector<int32_t>& prompt_ids,
                             bool condition, bool detect, int task, bool word_timestamps, std::string& text, std::string& lines) {
-  float* pcm = nullptr;
-  int n = 0;
-  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
-  const int n_ctx = AX_WHISPER_GetConfigInt(h, "n_text_ctx") > 0 ? AX_WHISPER_GetConfigInt(h, "n_text_ctx") : 448;
-  const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
-  const int cap = n / 160 / (chunk.min_frames > 0 ? chunk.min_frames : 1) + 2;
-  std::vector<int> info((size_t)cap * 7);
-  std::vector<int32_t> ids((size_t)cap * n_ctx);
-  std::vector<float> score(scored ? (size_t)cap * 3 : 0);
-  int n_win = 0;
-  const float* files[1] = {pcm};
+  LongLog L;
+  if (!L.load(h, wav)) return -1;
+  const int cap = L.n / 160 / (chunk.min_frames > 0 ? chunk.min_frames : 1) + 2;
+  L.size(cap, scored ? 3 : 0);
+  const float* files[1] = {L.pcm};
   const int n_initial = (int)prompt_ids.size(), lang = detect ? -2 : -1, tk = task > 0 ? 1 : 0;
-  AX_WHISPER_LONG_OPTIONS o{};
-  o.no_speech_threshold = scored ? no_speech_threshold : NAN; o.logprob_threshold = scored ? logprob_threshold : NAN;
-  o.compression_ratio_threshold = compression_ratio_threshold;
-  o.temperatures = temps.empty() ? nullptr : temps.data(); o.n_temperatures = (int)temps.size();
-  o.initial_prompt_ids = prompt_ids.empty() ? nullptr : prompt_ids.data(); o.prompt_stride = n_initial; o.n_initial = prompt_ids.empty() ? nullptr : &n_initial;
-  o.condition_on_previous_text = condition ? 1 : 0;
-  if (detect || task >= 0) { o.lang = &lang; o.task = &tk; }
-  o.word_timestamps = word_timestamps ? 1 : 0;
-  const int rc = AX_WHISPER_RunPCMLongChunkedWindows(h, files, &n, 1, 0, 0, &chunk, &o, cap, info.data(), ids.data(), scored ? score.data() : nullptr, &n_win);
-  free(pcm);
-  if (rc != 0) return -1;
-  for (int k = 0; k < n_win; ++k) {
-    if (scored && score[(size_t)k * 3 + 2] != 0.f) continue;  // a silent window
-    char tail[160] = "";
-    if (scored) snprintf(tail, sizeof tail, " (avg_logprob %.4f, no_speech %.3g)", score[(size_t)k * 3 + 1], std::exp(score[(size_t)k * 3]));
-    const int* w = &info[(size_t)k * 7];
-    const int32_t* wi = &ids[(size_t)k * n_ctx];
-    const int n_max = w[4] / 2 + 1;
-    std::vector<double> st(n_max), en(n_max);
-    std::vector<int> tb(n_max), te(n_max);
+  const bool per_lang = detect || task >= 0;
+  AX_WHISPER_LONG_OPTIONS o = long_options(scored ? no_speech_threshold : NAN, scored ? logprob_threshold : NAN, compression_ratio_threshold, temps, 0,
+                                           prompt_ids, &n_initial, condition, per_lang ? &lang : nullptr, per_lang ? &tk : nullptr, word_timestamps);
+  if (prompt_ids.empty()) { o.initial_prompt_ids = nullptr; o.n_initial = nullptr; }
+  if (AX_WHISPER_RunPCMLongChunkedWindows(h, files, &L.n, 1, 0, 0, &chunk, &o, cap, L.info.data(), L.ids.data(), scored ? L.score.data() : nullptr,
+                                          &L.n_win) != 0)
+    return -1;
+  const int T = AX_WHISPER_GetConfigInt(h, "timestamp_begin"), E = AX_WHISPER_GetConfigInt(h, "eot");
+  return L.print(h, false, -1, [&](const int* w, const int32_t* wi, int n_max, long* st, long* en, int* tb, int* te) {
+    std::vector<double> s(n_max), e(n_max);
     int n_seg = 0;
-    if (AX_WHISPER_ChunkedSegments(wi, w[4], T, E, w[1], w[2], n_max, st.data(), en.data(), tb.data(), te.data(), &n_seg) != 0) return -1;
-    for (int s = 0; s < n_seg; ++s) {
-      char* t = nullptr;
-      if (AX_WHISPER_Transcript(h, wi + tb[s], te[s] - tb[s], &t) != 0) return -1;
-      text += t ? t : "";
-      lines += "[" + mmss_ms((long)(st[s] * 1000.0 + 0.5)) + " --> " + mmss_ms((long)(en[s] * 1000.0 + 0.5)) + "] " + (t ? t : "") + tail + "\n";
-      free(t);
-    }
-  }
-  return 0;
+    if (AX_WHISPER_ChunkedSegments(wi, w[4], T, E, w[1], w[2], n_max, s.data(), e.data(), tb, te, &n_seg) != 0) return -1;
+    for (int k = 0; k < n_seg; ++k) { st[k] = (long)(s[k] * 1000.0 + 0.5); en[k] = (long)(e[k] * 1000.0 + 0.5); }
+    return n_seg;
+  }, text, lines);
 }
 
 // --long --word_timestamps: the seek loop with words (AX_WHISPER_RunPCMLongWords) under the same thresholds, fallback, prompts, language
@@ -365,21 +378,15 @@ static int run_long_chunked(AX_WHISPER_HANDLE h, const char* wav, const AX_WHISP
 static int run_long_words(AX_WHISPER_HANDLE h, const char* wav, float no_speech_threshold, float logprob_threshold, float compression_ratio_threshold,
                           const std::vector<float>& temps, unsigned long long seed, const std::vector<int32_t>& prompt_ids, bool condition,
                           std::string& text, std::string& lines, bool detect, int task) {
-  float* pcm = nullptr;
-  int n = 0;
-  if (load_pcm(h, wav, &pcm, &n) != 0 || n < 1) { free(pcm); return -1; }
+  LongLog L;  // (the samples only)
+  if (!L.load(h, wav)) return -1;
   int lang = -1;
-  if (detect && (lang = detect_and_print(h, pcm, n)) < 0) { free(pcm); return -1; }
+  if (detect && (lang = detect_and_print(h, L.pcm, L.n)) < 0) return -1;
   const int want = lang, tk = task > 0 ? 1 : 0, n_initial = (int)prompt_ids.size();
-  AX_WHISPER_LONG_OPTIONS o{};
-  o.no_speech_threshold = no_speech_threshold; o.logprob_threshold = logprob_threshold; o.compression_ratio_threshold = compression_ratio_threshold;
-  o.temperatures = temps.empty() ? nullptr : temps.data(); o.n_temperatures = (int)temps.size(); o.seed = seed;
-  o.initial_prompt_ids = prompt_ids.data(); o.prompt_stride = n_initial; o.n_initial = &n_initial; o.condition_on_previous_text = condition ? 1 : 0;
-  o.lang = &want; o.task = &tk; o.word_timestamps = 1;
+  const AX_WHISPER_LONG_OPTIONS o = long_options(no_speech_threshold, logprob_threshold, compression_ratio_threshold, temps, seed, prompt_ids, &n_initial,
+                                                 condition, &want, &tk, true);
   AX_WHISPER_LONG_WORDS r{};
-  const int rc = AX_WHISPER_RunPCMLongWords(h, pcm, n, &o, nullptr, &r);
-  free(pcm);
-  if (rc != 0) return -1;
+  if (AX_WHISPER_RunPCMLongWords(h, L.pcm, L.n, &o, nullptr, &r) != 0) return -1;
   for (int k = 0, w = 0; k < r.n_segments; ++k) {
     const int sb = k ? r.seg_text_end[k - 1] : 0;
     const std::string seg(r.seg_text + sb, r.seg_text + r.seg_text_end[k]);
