@@ -803,6 +803,38 @@ AX_WHISPER_API int AX_WHISPER_RunPCMLongChunked(AX_WHISPER_HANDLE handle, float*
 AX_WHISPER_API int AX_WHISPER_RunFileLongChunked(AX_WHISPER_HANDLE handle, const char* wav_file, const AX_WHISPER_CHUNK_OPTIONS* chunk,
                                                  const AX_WHISPER_LONG_OPTIONS* opts, char** result);
 
+/* ---- additions: the slot stream in timestamp mode (DESIGN.md "Slot stream in timestamp mode") --------------------------------- */
+/* A stream opened in mode 1 decodes every slot in the scored timestamp mode: the prefix is the slot's own [sot, language, task]
+ * (no <|notimestamps|>: the id budget without max_new is n_text_ctx - 3), the ids carry their timestamp tokens, and every slot keeps
+ * the log-probability of each decision, log p(<|nospeech|>) and its language. A slot walks its own prefix step by step; with
+ * lang -2 the language is picked on the GPU from the logits row of the step that fed sot (openai-whisper's detect_language) and
+ * fed by the same step. One mode per open stream. Refused with a text in AX_WHISPER_LastError, the handle and an open stream staying
+ * usable: an unknown mode; lang / task arrays or StreamCollectScored on a mode-0 stream; a language index outside [-2, n_lang); a
+ * task other than 0 or 1; translate without a `translate` id in the config; detection on a config that lists one language.
+ * Not covered in slots: sampling and fallback, prompts, beam search, word timestamps. GetConfigInt "stream_mode": the open stream's. */
+/** AX_WHISPER_StreamOpen with a mode: 0 the plain greedy decode in the handle's language (exactly StreamOpen), 1 scored timestamps. */
+AX_WHISPER_API int AX_WHISPER_StreamOpenMode(AX_WHISPER_HANDLE handle, int n_slots, int mode);
+/** AX_WHISPER_StreamAdmitBatchRate with a language and task per clip (mode-1 stream): lang[i] >= 0 an index of the config's language
+ *  list, -1 the handle's language, -2 detect; task[i] 0 transcribe, 1 translate. rates, max_new, lang and task may each be NULL
+ *  (16000 Hz, no budget, all -1, all 0). None admitted when any clip is refused. */
+AX_WHISPER_API int AX_WHISPER_StreamAdmitBatchLang(AX_WHISPER_HANDLE handle, const int* slots, const float* const* pcm, const int* num_samples,
+                                                   const int* rates, const int* max_new, const int* lang, const int* task, int count);
+/** AX_WHISPER_StreamCollect of a mode-1 stream with the slot's scores: token_logprob host [n_text_ctx] (entries 0 .. *n_ids: one per
+ *  kept id and the decision that ended the clip; the rest 0), *avg_logprob, *no_speech_logprob, *ended_eot as
+ *  AX_WHISPER_RunPCMBatchTimestampScores defines them; *lang_out the language index the clip was decoded under; lang_logprob host
+ *  [n_lang]: a detecting clip's language log-probabilities, zeros otherwise. Everything but ids and n_ids may be NULL. */
+AX_WHISPER_API int AX_WHISPER_StreamCollectScored(AX_WHISPER_HANDLE handle, int slot, int32_t* ids, int* n_ids, float* token_logprob,
+                                                  float* avg_logprob, float* no_speech_logprob, int* ended_eot, int* lang_out,
+                                                  float* lang_logprob);
+/** Stage level: the stream's rules kernel alone on host data, n slots. rows [n][n_vocab]; off, done, detect [n]; hist [n][n_text_ctx]
+ *  with n_hist [n] ids each. In/out, written only where the kernel writes (a caller's sentinel stays elsewhere): slot_ctx [n][4],
+ *  chosen and logprob [n] (a slot at offset >= 2: AX_WHISPER_ScoreTimestampRules' decision), no_speech [n], lang_out [n],
+ *  lang_logprob [n][n_lang]. A slot with done set is not touched; offset 0 writes no_speech and, with detect, the language outputs and
+ *  slot_ctx[4 b + 1]; offset 1 writes nothing. Refuses an open Stream*. */
+AX_WHISPER_API int AX_WHISPER_StreamRulesStage(AX_WHISPER_HANDLE handle, int n, const float* rows, const int* off, const int* done,
+                                               const int* detect, const int32_t* hist, const int* n_hist, int* slot_ctx, int32_t* chosen,
+                                               float* logprob, float* no_speech, int* lang_out, float* lang_logprob);
+
 #ifdef __cplusplus
 }
 #endif

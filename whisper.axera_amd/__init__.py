@@ -209,6 +209,12 @@ SYMBOLS = {
                                                       C.POINTER(LongOptions), C.c_int, C.POINTER(C.c_int), ip, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_RunPCMLongChunked": (C.c_int, [C.c_void_p, fp, C.c_int, C.POINTER(ChunkOptions), C.POINTER(LongOptions), C.POINTER(C.c_void_p)]),
     "AX_WHISPER_RunFileLongChunked": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(ChunkOptions), C.POINTER(LongOptions), C.POINTER(C.c_void_p)]),
+    "AX_WHISPER_StreamOpenMode": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "AX_WHISPER_StreamAdmitBatchLang": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(fp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "AX_WHISPER_StreamCollectScored": (C.c_int, [C.c_void_p, C.c_int, ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
+    "AX_WHISPER_StreamRulesStage": (C.c_int, [C.c_void_p, C.c_int, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), ip, fp, fp, C.POINTER(C.c_int), fp]),
 }
 
 
@@ -1671,22 +1677,34 @@ class Whisper:
         return [ids[b, : n[b]].tolist() for b in range(batch)]
 
     # ---- utterance slots refilled while the others decode (AX_WHISPER_Stream*)
-    def stream_open(self, n_slots: int):
-        self._check(self.L.AX_WHISPER_StreamOpen(self.h, n_slots), "StreamOpen")
+    def stream_open(self, n_slots: int, timestamps: bool = False):
+        """timestamps: the scored timestamp mode (AX_WHISPER_StreamOpenMode, mode 1; an integer is passed on as the mode)."""
+        if timestamps is False:
+            self._check(self.L.AX_WHISPER_StreamOpen(self.h, n_slots), "StreamOpen")
+        else:
+            self._check(self.L.AX_WHISPER_StreamOpenMode(self.h, n_slots, 1 if timestamps is True else int(timestamps)), "StreamOpenMode")
         self._n_slots = n_slots
 
-    def stream_admit(self, slot: int, pcm, max_new: int = 0):
-        a = _f32(pcm)
-        self._check(self.L.AX_WHISPER_StreamAdmit(self.h, slot, a.ctypes.data_as(fp), len(a), max_new), "StreamAdmit")
+    def stream_admit(self, slot: int, pcm, max_new: int = 0, language=None, task=None):
+        """language (a code, None or "auto") and task ("transcribe" / "translate"): a stream opened with timestamps=True."""
+        if language is None and task is None:
+            a = _f32(pcm)
+            self._check(self.L.AX_WHISPER_StreamAdmit(self.h, slot, a.ctypes.data_as(fp), len(a), max_new), "StreamAdmit")
+        else:
+            self.stream_admit_batch([slot], [pcm], [max_new], languages=[language], tasks=None if task is None else [task])
 
-    def stream_admit_batch(self, slots, clips, max_new=None, rates=None):
+    def stream_admit_batch(self, slots, clips, max_new=None, rates=None, languages=None, tasks=None):
         clips = [_f32(c) for c in clips]
         n = len(clips)
         sl = (C.c_int * n)(*[int(x) for x in slots])
         ptrs = (fp * n)(*[c.ctypes.data_as(fp) for c in clips])
         lens = (C.c_int * n)(*[len(c) for c in clips])
         mn = (C.c_int * n)(*[int(x) for x in max_new]) if max_new is not None else None
-        if rates is None:
+        if languages is not None or tasks is not None:
+            lang, task = self._lang_args(n, languages, tasks)
+            rt = (C.c_int * n)(*[int(r) for r in rates]) if rates is not None else None
+            self._check(self.L.AX_WHISPER_StreamAdmitBatchLang(self.h, sl, ptrs, lens, rt, mn, lang, task, n), "StreamAdmitBatchLang")
+        elif rates is None:
             self._check(self.L.AX_WHISPER_StreamAdmitBatch(self.h, sl, ptrs, lens, mn, n), "StreamAdmitBatch")
         else:
             rt = (C.c_int * n)(*[int(r) for r in rates])
@@ -1704,8 +1722,89 @@ class Whisper:
         self._check(self.L.AX_WHISPER_StreamCollect(self.h, slot, ids.ctypes.data_as(ip), C.byref(n)), "StreamCollect")
         return ids[: n.value].tolist()
 
+    def stream_collect_scored(self, slot: int):
+        """A finished slot of a timestamp-mode stream: dict(ids, token_logprob [n_ids + 1], avg_logprob, no_speech_logprob, ended_eot,
+        language (the code the clip was decoded under), lang_index, lang_logprob [n_lang]: a detecting clip's, zeros otherwise)."""
+        ids = np.zeros(self.n_text_ctx, dtype=np.int32)
+        lp = np.zeros(self.n_text_ctx, dtype=np.float32)
+        llp = np.zeros(self.n_lang, dtype=np.float32)
+        n, eot, lang = C.c_int(), C.c_int(), C.c_int()
+        avg, nsp = C.c_float(), C.c_float()
+        self._check(self.L.AX_WHISPER_StreamCollectScored(self.h, slot, ids.ctypes.data_as(ip), C.byref(n), lp.ctypes.data_as(fp),
+                                                           C.cast(C.byref(avg), fp), C.cast(C.byref(nsp), fp), C.byref(eot), C.byref(lang),
+                                                           llp.ctypes.data_as(fp)), "StreamCollectScored")
+        return dict(ids=ids[: n.value].tolist(), token_logprob=lp[: min(n.value + 1, self.n_text_ctx)].copy(), avg_logprob=avg.value,
+                    no_speech_logprob=nsp.value, ended_eot=bool(eot.value), language=self.language_code(lang.value), lang_index=lang.value,
+                    lang_logprob=llp)
+
+    def stream_rules_stage(self, rows, off, done, detect, histories, slot_ctx, sentinel: float = -7.0, sentinel_int: int = -7):
+        """The stream's rules kernel alone (AX_WHISPER_StreamRulesStage) on rows [n][n_vocab], off / done / detect [n], one id history per
+        slot and slot_ctx [n][4]. Every output starts as a sentinel and is written only where the kernel writes: dict(chosen, logprob,
+        no_speech, slot_ctx, lang_out, lang_logprob [n][n_lang])."""
+        lg = _f32(rows).reshape(-1, self.n_vocab)
+        n = lg.shape[0]
+        hist = np.zeros((n, self.n_text_ctx), dtype=np.int32)
+        nh = (C.c_int * n)()
+        for b, h in enumerate(histories):
+            hist[b, : len(h)] = h
+            nh[b] = len(h)
+        ctx = np.ascontiguousarray(slot_ctx, dtype=np.int32).reshape(n, 4).copy()
+        chosen = np.full(n, sentinel_int, dtype=np.int32)
+        lang = np.full(n, sentinel_int, dtype=np.int32)
+        lp = np.full(n, sentinel, dtype=np.float32)
+        nsp = np.full(n, sentinel, dtype=np.float32)
+        llp = np.full((n, self.n_lang), sentinel, dtype=np.float32)
+        ci = lambda a: (C.c_int * n)(*[int(x) for x in a])
+        cp = C.POINTER(C.c_int)
+        self._check(self.L.AX_WHISPER_StreamRulesStage(self.h, n, lg.ctypes.data_as(fp), ci(off), ci(done), ci(detect), hist.ctypes.data_as(ip), nh,
+                                                        ctx.ctypes.data_as(cp), chosen.ctypes.data_as(ip), lp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
+                                                        lang.ctypes.data_as(cp), llp.ctypes.data_as(fp)), "StreamRulesStage")
+        return dict(chosen=chosen, logprob=lp, no_speech=nsp, slot_ctx=ctx, lang_out=lang, lang_logprob=llp)
+
     def stream_close(self):
         self._check(self.L.AX_WHISPER_StreamClose(self.h), "StreamClose")
+
+    def run_stream_timestamps(self, clips, n_slots: int, max_new=0, languages=None, tasks=None, steps_per_call: int = 8):
+        """`clips` through n_slots refillable slots in the scored timestamp mode, in arrival order; max_new: one budget or one per clip;
+        languages / tasks: one per clip, as run_timestamp_lang_batch takes them. Per clip (segments, ids, token_logprobs, avg_logprob,
+        no_speech_logprob, language, lang_logprob): segments [(start, end, text)] by split_segments with the text under the slot's
+        language (transcript_lang), lang_logprob for detecting clips and None otherwise."""
+        N = len(clips)
+        budgets = list(max_new) if hasattr(max_new, "__len__") else [max_new] * N
+        if languages is not None and len(languages) != N:
+            raise ValueError("one language (a code, None or \"auto\") per clip")
+        if tasks is not None and len(tasks) != N:
+            raise ValueError("one task per clip")
+        self.stream_open(n_slots, timestamps=True)
+        try:
+            out = [None] * N
+            owner = {}
+            free = list(range(n_slots))
+            nxt = 0
+            while nxt < N or owner:
+                k = min(len(free), N - nxt)
+                if k > 0:
+                    self.stream_admit_batch(free[:k], clips[nxt:nxt + k], budgets[nxt:nxt + k],
+                                            languages=None if languages is None else languages[nxt:nxt + k],
+                                            tasks=None if tasks is None else tasks[nxt:nxt + k])
+                for i in range(k):
+                    owner[free.pop(0)] = nxt
+                    nxt += 1
+                for sl in self.stream_step(steps_per_call):
+                    if sl not in owner:
+                        continue
+                    c = owner.pop(sl)
+                    r = self.stream_collect_scored(sl)
+                    free.append(sl)
+                    clip_s = min(len(clips[c]) / 16000.0, 30.0)
+                    segs = [(a, b, self.transcript_lang(r["ids"][t0:t1], r["language"]))
+                            for a, b, t0, t1 in split_segments(r["ids"], self.timestamp_begin, self.eot, clip_s)]
+                    detected = languages is not None and (languages[c] == "auto" or languages[c] == -2)
+                    out[c] = (segs, r["ids"], r["token_logprob"], r["avg_logprob"], r["no_speech_logprob"], r["language"],
+                              r["lang_logprob"] if detected else None)
+            return out
+        finally:
+            self.stream_close()
 
     def run_stream(self, clips, n_slots: int, max_new=0, steps_per_call: int = 8, min_admit: int = 1, stamps=None):
         """Feed `clips` through n_slots refillable slots in arrival order; max_new: one budget or one per clip.

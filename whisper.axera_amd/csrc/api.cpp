@@ -1131,6 +1131,35 @@ AX_WHISPER_API int AX_WHISPER_StreamClose(AX_WHISPER_HANDLE handle) {
   return guarded(handle, [&](Engine& e) { e.stream_close(); });
 }
 
+// ---- slot stream in timestamp mode (DESIGN.md "Slot stream in timestamp mode")
+AX_WHISPER_API int AX_WHISPER_StreamOpenMode(AX_WHISPER_HANDLE handle, int n_slots, int mode) {
+  return guarded(handle, [&](Engine& e) { e.stream_open(n_slots, mode); });
+}
+AX_WHISPER_API int AX_WHISPER_StreamAdmitBatchLang(AX_WHISPER_HANDLE handle, const int* slots, const float* const* pcm, const int* num_samples,
+                                                   const int* rates, const int* max_new, const int* lang, const int* task, int count) {
+  if (!handle || !slots || !pcm || !num_samples || count < 1) return -1;
+  for (int i = 0; i < count; ++i) if (!pcm[i] || num_samples[i] < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.stream_admit(slots, pcm, num_samples, max_new, count, rates, lang, task); });
+}
+AX_WHISPER_API int AX_WHISPER_StreamCollectScored(AX_WHISPER_HANDLE handle, int slot, int32_t* ids, int* n_ids, float* token_logprob,
+                                                  float* avg_logprob, float* no_speech_logprob, int* ended_eot, int* lang_out,
+                                                  float* lang_logprob) {
+  if (!handle || !ids || !n_ids) return -1;
+  return guarded(handle, [&](Engine& e) {
+    e.stream_collect_scored(slot, ids, n_ids, Engine::SlotScores{token_logprob, avg_logprob, no_speech_logprob, ended_eot, lang_out, lang_logprob});
+  });
+}
+AX_WHISPER_API int AX_WHISPER_StreamRulesStage(AX_WHISPER_HANDLE handle, int n, const float* rows, const int* off, const int* done,
+                                               const int* detect, const int32_t* hist, const int* n_hist, int* slot_ctx, int32_t* chosen,
+                                               float* logprob, float* no_speech, int* lang_out, float* lang_logprob) {
+  if (!handle || !rows || !off || !done || !detect || !hist || !n_hist || !slot_ctx || !chosen || !logprob || !no_speech || !lang_out ||
+      !lang_logprob || n < 1)
+    return -1;
+  return guarded(handle, [&](Engine& e) {
+    e.stream_rules_stage(Engine::StreamRulesIO{n, rows, off, done, detect, hist, n_hist, slot_ctx, chosen, logprob, no_speech, lang_out, lang_logprob});
+  });
+}
+
 // ---- word-level timestamps (DESIGN.md "Word-level timestamps")
 // Host only: matrix [n_rows][n_frames] (row stride ld floats) -> jump [n_rows] (words.hpp: align_path)
 AX_WHISPER_API int AX_WHISPER_AlignPath(const float* matrix, int n_rows, int n_frames, int ld, int* jump) {

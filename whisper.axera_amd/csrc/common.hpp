@@ -514,7 +514,7 @@ void launch_act_prep(float* x, const float* g, const float* be, h16* hi, h16* lo
 void launch_pack_weight_frag(const h16* w, h16* wp, int N, int K, hipStream_t s);
 void launch_pack_weight_frag_split(const float* w, h16* hi, h16* lo, int N, int K, hipStream_t s);  // fp32 -> (hi, lo) h16 pair
 
-struct AdvanceParams {
+struct AdvanceArgs {  // what advance_kernel itself takes
   const float* amax_val; const int* amax_idx; int n_part; int amax_stride;
   DecState* state; int* off; int* tok; int* done; int* n_out; int* out_ids; int batch;
   int* done_host;             // optional host-mapped [batch]: set (behind a system-scope fence) when a clip finishes, so that the
@@ -527,6 +527,12 @@ struct AdvanceParams {
   const h16* tok_emb; const float* pos; float* x; int d_model;  // fused embedding of the next step
   int n_prefix;               // prefix tokens fed before the first sampled step (sot[0 .. n_prefix)); 0 means 4
   const int* base;            // optional device [B], forced mode: positions in front of the prefix (a prompted clip's L - 2); nullptr: none
+};
+// What callers fill in. sot_clip stands behind AdvanceArgs, not inside it: advance_kernel's argument block, and with it the code of
+// every call that sets no sot_clip, stays what it was before the field existed.
+struct AdvanceParams : AdvanceArgs {
+  const int* sot_clip;        // optional device [B][4]: a prefix per clip (slot stream in timestamp mode); the token fed behind offset s
+                              // is sot_clip[4 b + s + 1] instead of sot[s + 1]. Set: the second instantiation of the kernel runs
 };
 void launch_advance(const AdvanceParams& p, hipStream_t s);
 
@@ -666,6 +672,20 @@ struct LangDetectParams {
   int* ctx; const int* lang_row;             // optional: the prefill pass's context table and, per clip, the entry to patch
 };
 void launch_language_detect(const LangDetectParams& p, hipStream_t s);
+
+// ---- slot stream in timestamp mode (decode_timestamps.hip: stream_rules_kernel; DESIGN.md "Slot stream in timestamp mode"): the
+// scored rules kernel for slots that are refilled. Slot b with done[b] set: nothing at all. Else at offset 0: no_speech[b], and with
+// detect[b] the language pick of the row that is already there (lang_logit[j] = row[lang_tokens[j]], the definition of
+// LangDetectParams) -> slot_ctx[4 b + 1] = lang_tokens[pick], lang_out[b], lang_logprob[b][0 .. n_lang). Offset 1: nothing. From
+// offset n_prefix - 1 on: the scored decision. TsRulesParams::off and ::done and TsScoreParams::no_speech are required.
+struct StreamRulesParams {
+  const int* detect;                         // device [batch]
+  int* slot_ctx;                             // device [batch][4]: [sot, language id, task id, unused], the table advance_kernel feeds from
+  const int* lang_tokens; int n_lang;        // device [n_lang] (n_lang <= kLangMax), ids inside the vocabulary
+  int fallback_index;                        // nothing finite: this index
+  int* lang_out; float* lang_logprob;        // out [batch], [batch][n_lang]
+};
+void launch_stream_rules(const TsRulesParams& p, const TsScoreParams& q, const StreamRulesParams& t, hipStream_t s);
 
 // ---- word-level timestamps (decode_align.hip; DESIGN.md "Word-level timestamps"). The rows of a clip are contiguous in q (clip c at
 // row0[c], len[c] rows); clip c attends to its own n_keys[c] frames. All per-clip tables are device memory.

@@ -488,7 +488,12 @@ void launch_gemv(const GemvParams& p, hipStream_t s) {
 // loop state and the next position's embedding beside the partials, the step ticket right behind the step counter, and
 // the embedding row in 8-byte pieces that are all in flight before the first store (as `for (c = lane; c < d; c += 64)`
 // the row was 12 load -> add -> store round trips, 12.7 us per step at turbo dims).
-__global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
+// Two instantiations. Params = AdvanceArgs: every call without a prefix per clip. Params = AdvanceParams (the slot stream in timestamp
+// mode): the prefix is the clip's own, sot_clip[4 b + ...], which the stream's reset kernel and rules kernel write on this stream in
+// front of this launch.
+template <class Params>
+__global__ __launch_bounds__(1024) void advance_kernel(Params p) {
+  constexpr bool CLIP_SOT = sizeof(Params) == sizeof(AdvanceParams);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x * 16 + wave;
   // the engine-wide step counter is bookkeeping only (steps run since the reset): whichever workgroup draws the last
@@ -522,7 +527,8 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
   if (done_b) {
     // nothing: the slot waits for Engine::stream_admit or the end of the batch
   } else if (s < n_pre - 1) {
-    tok = p.sot[s + 1];
+    if constexpr (CLIP_SOT) tok = p.sot_clip[4 * b + s + 1];
+    else tok = p.sot[s + 1];
     if (lane == 0) p.tok[b] = tok;
   } else {
     const int n_out = greedy ? p.n_out[b] : 0;
@@ -580,7 +586,8 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceParams p) {
 
 void launch_advance(const AdvanceParams& p, hipStream_t s) {
   if (p.d_model > 2048 || p.d_model % 4 != 0) { fprintf(stderr, "[ax_whisper] launch_advance: d_model %d unsupported\n", p.d_model); abort(); }
-  hipLaunchKernelGGL(advance_kernel, dim3((p.batch + 15) / 16), dim3(1024), 0, s, p);
+  if (p.sot_clip) hipLaunchKernelGGL(advance_kernel<AdvanceParams>, dim3((p.batch + 15) / 16), dim3(1024), 0, s, p);
+  else hipLaunchKernelGGL(advance_kernel<AdvanceArgs>, dim3((p.batch + 15) / 16), dim3(1024), 0, s, static_cast<const AdvanceArgs&>(p));
 }
 
 }  // inline namespace AXW_NS

@@ -17,6 +17,9 @@
 // softmax(x[A] / t) by Gumbel-max with Philox4x32-10 noise: two more (key, id) pairs per thread (text and eot / timestamps, since
 // rule 5 is only known after the reduction), reduced like the argmax pairs.
 //
+// Stream form (DESIGN.md "Slot stream in timestamp mode"): stream_rules_kernel, the scored form for slots that are refilled while the
+// others decode: a slot whose done flag is set is left alone, offset 0 also picks the clip's language from the row when asked to.
+//
 // The three kernels are instantiations of one body, rules_body<MODE>: a lower form compiles none of what a higher one adds. The rules
 // themselves, the logsumexp helpers and the decision are decode_rules.hpp's, shared with decode_beam.hip.
 #include "decode_rules.hpp"
@@ -209,6 +212,63 @@ __global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesPar
   rules_body<kRulesSampled>(p, q, r);
 }
 
+// ---- slot stream in timestamp mode (DESIGN.md "Slot stream in timestamp mode"): the scored form for slots that are refilled while
+// the others decode. One workgroup per slot; every branch below is uniform over the workgroup.
+//   done[b] set (idle, or finished and not yet refilled): NOTHING, checked before the offset — an idle slot rests at offset 0 with a
+//     stale row, and the scored kernel's order (offset first) would overwrite its no-speech value and detect a language nobody asked for;
+//   offset 0: no_speech[b] as the scored kernel writes it; with detect[b], openai-whisper's detect_language from the same row (the
+//     context is [sot] at position 0 over the clip's own cross K/V): thread j < n_lang gathers row[lang_tokens[j]] into LDS; wave 0
+//     then holds languages l and l + 64 in lane l and takes the first maximum in list order (NaN never wins; lanes by xor butterfly)
+//     and sum exp(x - max) over the entries that are not NaN (lanes by xor butterfly: decode_language.hip step 3, the same arithmetic);
+//     lang_logprob[j] = x[j] - (max + log sum), -inf for NaN; nothing finite: fallback_index, every value -inf. Lane 0 writes
+//     slot_ctx[4 b + 1], which this step's advance launch feeds next on the same stream: no extra pass, no host round trip;
+//   offset 1 (the language id was fed): nothing;
+//   offset >= n_prefix - 1: rules_body<kRulesScored>, whose own offset and done tests then pass.
+__global__ __launch_bounds__(256) void stream_rules_kernel(TsRulesParams p, TsScoreParams q, StreamRulesParams t) {
+  const int b = blockIdx.x;
+  if (p.done[b]) return;
+  const int off = p.off[b];
+  if (off >= p.n_prefix - 1) { rules_body<kRulesScored>(p, q, TsSampleParams{}); return; }
+  if (off != 0) return;
+  const float* row = p.logits + (long)b * p.stride;
+  row_logprob(row, p.n_vocab, q.no_speech_id, q.no_speech + b);
+  if (!t.detect[b]) return;
+  __shared__ float s_logit[kLangMax];
+  const int tid = threadIdx.x, lane = tid & 63, n_lang = t.n_lang;
+  if (tid < n_lang) s_logit[tid] = row[t.lang_tokens[tid]];
+  __syncthreads();
+  if (tid >= 64) return;
+  const int j0 = lane, j1 = lane + 64;
+  const float x0 = j0 < n_lang ? s_logit[j0] : NAN, x1 = j1 < n_lang ? s_logit[j1] : NAN;
+  float m = -INFINITY;
+  int idx = 0x7fffffff;
+  argmax_take(m, idx, x0, j0);  // (a NaN compares false: never taken)
+  argmax_take(m, idx, x1, j1);
+  wave_argmax(m, idx);
+  const float n_finite = wave_sum((fabsf(x0) < INFINITY ? 1.f : 0.f) + (fabsf(x1) < INFINITY ? 1.f : 0.f));
+  const bool none = !(n_finite > 0.f) || idx >= n_lang;
+  float lp0, lp1;
+  if (none) {
+    idx = t.fallback_index;
+    lp0 = lp1 = -INFINITY;
+  } else if (m == INFINITY) {  // the maxima share the whole mass
+    lp0 = x0 == INFINITY ? 0.f : -INFINITY;
+    lp1 = x1 == INFINITY ? 0.f : -INFINITY;
+  } else {
+    float s = (x0 == x0 ? expf(x0 - m) : 0.f) + (x1 == x1 ? expf(x1 - m) : 0.f);
+    s = wave_sum(s);
+    const float lse = m + logf(s);
+    lp0 = x0 == x0 ? x0 - lse : -INFINITY;
+    lp1 = x1 == x1 ? x1 - lse : -INFINITY;
+  }
+  if (j0 < n_lang) t.lang_logprob[(long)b * n_lang + j0] = lp0;
+  if (j1 < n_lang) t.lang_logprob[(long)b * n_lang + j1] = lp1;
+  if (lane == 0) {
+    t.lang_out[b] = idx;
+    t.slot_ctx[4 * b + 1] = t.lang_tokens[idx];
+  }
+}
+
 // log p(row[id]) over the whole row, one workgroup per row (the no-speech value on rows of the caller's)
 __global__ __launch_bounds__(256) void row_logprob_kernel(const float* logits, long stride, int n_vocab, int id, float* out) {
   row_logprob(logits + (long)blockIdx.x * stride, n_vocab, id, out + blockIdx.x);
@@ -247,6 +307,16 @@ void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams&
     abort();
   }
   hipLaunchKernelGGL(timestamp_rules_sampled_kernel, dim3(p.batch), dim3(256), 0, s, p, q, r);
+}
+
+void launch_stream_rules(const TsRulesParams& p, const TsScoreParams& q, const StreamRulesParams& t, hipStream_t s) {
+  check_rules_params(p);
+  if (!score_params_ok(p, q) || !q.no_speech || !p.off || !p.done || p.forced || !t.detect || !t.slot_ctx || !t.lang_tokens || !t.lang_out ||
+      !t.lang_logprob || t.n_lang < 1 || t.n_lang > kLangMax || t.fallback_index < 0 || t.fallback_index >= t.n_lang) {
+    fprintf(stderr, "[ax_whisper] launch_stream_rules: bad score or slot arrays / n_lang %d\n", t.n_lang);
+    abort();
+  }
+  hipLaunchKernelGGL(stream_rules_kernel, dim3(p.batch), dim3(256), 0, s, p, q, t);
 }
 
 void launch_row_logprob(const float* logits, long stride, int n_vocab, int id, int batch, float* out, hipStream_t s) {

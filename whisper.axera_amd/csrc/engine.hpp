@@ -132,6 +132,10 @@ struct SlotViews {
   int *d_tok_ = nullptr, *d_done_ = nullptr, *d_done_none_ = nullptr, *d_nout_ = nullptr, *d_out_ids_ = nullptr, *d_max_new_clip_ = nullptr;
   int* d_off_ = nullptr;   // per-slot offsets (common.hpp: DecState)
   int* d_slot_map_ = nullptr;            // [cap]: clip index of an admission pass -> slot
+  // slot stream in timestamp mode (DESIGN.md "Slot stream in timestamp mode"): every slot's prefix [cap][4] = [sot, language id, task
+  // id, unused], detect flag and language index [cap], lang_logprob [cap][n_lang]; allocated like d_ts_logits_
+  int *d_slot_ctx_ = nullptr, *d_slot_detect_ = nullptr, *d_slot_lang_ = nullptr;
+  float* d_slot_lang_lp_ = nullptr;
   // beam search (engine_beam.cpp; common.hpp: BeamCandParams / BeamSelectParams): per-slot and per-clip state [cap], histories and
   // pool ids [cap][n_text_ctx], candidates [cap][kBeamMaxCand]; allocated on first use under device_capture_mutex
   struct BeamViews {
@@ -182,11 +186,13 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void set_alignment_heads(const int* pairs, int n) override;
   void align_kernel(int which, const AlignKernelIO& io) override;
   void vocab_logprob_rows(const float* x, int n_rows, const int32_t* ids, float* out, int route) override;
-  void stream_open(int n_slots) override;
+  void stream_open(int n_slots, int mode = 0) override;
   void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count,
-                    const int* rates = nullptr) override;
+                    const int* rates = nullptr, const int* lang = nullptr, const int* task = nullptr) override;
   int stream_step(int n_steps, int* finished_slots) override;
   void stream_collect(int slot, int32_t* ids, int* n_ids) override;
+  void stream_collect_scored(int slot, int32_t* ids, int* n_ids, const SlotScores& out) override;
+  void stream_rules_stage(const StreamRulesIO& io) override;
   void stream_close() override;
   void compute_mel_window(const float* pcm, int n_samples, int seek, float* mel_out) override;
   void run_long_windows(const float* const* pcm, const int* n_samples, int n_files, int max_new, int max_passes,
@@ -252,6 +258,9 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     // the logits launch is skipped (1) or dumps every row into d_ts_logits_ (2)
     int feed = 0;
     const int* base = nullptr;  // teacher-forced prompted decode: device [batch], the clips' L - 2 (AdvanceParams::base)
+    // slot stream in timestamp mode (engine_stream.cpp; kDecodeScored only): the rules launch is stream_rules_kernel and the advance
+    // launch feeds every slot its own prefix from d_slot_ctx_
+    bool slots = false;
   };
   // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
   // the rules kernel; first_step: the first decode step whose row is computed
@@ -272,8 +281,10 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // the captured step of spec.mode / spec.mask; a scored graph writes the engine's own score arrays (spec.score_out is not read)
   hipGraphExec_t step_graph(StepSpec spec, int batch, int max_new);
   void drop_step_graph(const StepSpec& spec, int batch, int max_new) { graphs_.erase(graph_key(spec, batch, max_new)); }
-  // (two bits for the mode: plain, timestamp, scored and sampled steps are four different graphs)
-  static long graph_key(const StepSpec& spec, int batch, int max_new) { return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 2) | spec.mode; }
+  // (two bits for the mode: plain, timestamp, scored and sampled steps are four different graphs; one for the slot stream's scored step)
+  static long graph_key(const StepSpec& spec, int batch, int max_new) {
+    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 3) | (spec.slots ? 4 : 0) | spec.mode;
+  }
   void require_timestamp_vocab() const;
   void ensure_ts_logits();  // d_ts_logits_ (SlotViews)
   void enqueue_timestamp_rules(const StepSpec& spec, int batch, const int* d_forced, int n_forced, hipStream_t s);
@@ -289,6 +300,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void upload_sample(const SampleSpec& sample, int batch);
   // scores of the last scored greedy loop over `batch` slots (n_ids: what fetch_ids returned)
   void fetch_scores(int batch, const int* n_ids, float* token_logprob, float* avg_logprob, float* no_speech_logprob, int* ended_eot);
+  // one clip of it: lp / dec [n_text_ctx] as the scored rules kernel left them -> token_logprob [n_text_ctx], avg_logprob, ended_eot
+  void clip_score_summary(const float* lp, const int* dec, int n_ids, float* token_logprob, float* avg_logprob, int* ended_eot) const;
   void recover_streams();
   // long-form (engine_long.cpp)
   // upload + whole-file front-end; cut (chunked calls): also room for the levels (want_e: both of them) and the cut plan
@@ -416,6 +429,12 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   int stream_slots_ = 0;                 // > 0: a stream is open (slots of the step graph: at least 3)
   int stream_user_slots_ = 0;            // the n_slots the caller asked for: the slot indices it may use
   std::vector<int> slot_state_, slot_max_new_;
+  int stream_mode_ = 0;                  // of the open stream: 0 plain, 1 scored timestamp mode
+  std::vector<int> slot_lang_, slot_task_, slot_detect_;  // mode 1, per slot: language index, task id, detect flag of the admitted clip
+  StepSpec stream_spec() const { StepSpec sp{}; if (stream_mode_ == 1) { sp.mode = kDecodeScored; sp.slots = true; } return sp; }
+  int stream_n_prefix() const { return stream_mode_ == 1 ? 3 : 4; }
+  void ensure_stream_ts();  // d_slot_ctx_ ... (SlotViews), the language id list
+  StreamRulesParams stream_rules_params() const;
   long step_seq_ = 0;   // decoder steps enqueued on the open stream (ev_step_)
   long admit_seq_ = 0;  // admission passes of the open stream (h_admit_ring_, ev_ring_)
   void require_no_stream(const char* what) const;

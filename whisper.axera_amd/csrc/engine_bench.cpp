@@ -96,7 +96,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   HIP_CHECK(hipSetDevice(device_));
   ensure_capacity(batch);
   if (what == "decode_step" || what == "decode_gemv" || what == "decode_attn" || what == "decode_step_ts" || what == "decode_step_ts_scored" ||
-      what == "decode_step_ts_sampled")
+      what == "decode_step_ts_sampled" || what == "stream_step_ts")
     return bench_decode_step(what, batch, arg, iters);
   if (what == "decode_step_beam") return bench_decode_step_beam(batch, arg, iters);
   if (what == "attn_stamp") return bench_attn_stamp(batch, arg, iters);
@@ -208,13 +208,20 @@ float Engine::bench_word_logprob(const std::string& what, int batch, int arg, in
 
 // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;
 // decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel); decode_step_ts_scored: with the scored rules kernel;
-// decode_step_ts_sampled: with the sampled rules kernel, every clip at temperature AX_WHISPER_BENCH_TEMPERATURE (default 1)
+// decode_step_ts_sampled: with the sampled rules kernel, every clip at temperature AX_WHISPER_BENCH_TEMPERATURE (default 1);
+// stream_step_ts: the scored step of the slot stream in timestamp mode (stream_rules_kernel, a prefix per slot), the same placement
 float Engine::bench_decode_step(const std::string& what, int batch, int arg, int iters) {
   const bool sampled = what == "decode_step_ts_sampled";
-  const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored" || sampled;
+  const bool slots = what == "stream_step_ts";
+  const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored" || sampled || slots;
   if (what == "decode_step_ts") require_timestamp_vocab();
-  if (what == "decode_step_ts_scored" || sampled) require_scored_vocab();
-  StepSpec spec{what == "decode_step_ts" ? kDecodeTimestamps : what == "decode_step_ts_scored" ? kDecodeScored : sampled ? kDecodeSampled : kDecodePlain};
+  if (what == "decode_step_ts_scored" || sampled || slots) require_scored_vocab();
+  StepSpec spec{what == "decode_step_ts" ? kDecodeTimestamps : (what == "decode_step_ts_scored" || slots) ? kDecodeScored : sampled ? kDecodeSampled : kDecodePlain};
+  if (slots) {
+    if (cfg_.lang_tokens.empty()) throw std::runtime_error("bench stream_step_ts: the config lists no languages");
+    ensure_stream_ts();
+    spec.slots = true;
+  }
   if (sampled) {
     const char* e = getenv("AX_WHISPER_BENCH_TEMPERATURE");
     const std::vector<float> temps(batch, e ? (float)atof(e) : 1.f);

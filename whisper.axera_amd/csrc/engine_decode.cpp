@@ -135,6 +135,7 @@ void Engine::enqueue_step_tail(const StepSpec& spec, int batch, int max_new, con
   a.forced = d_forced; a.n_forced = n_forced; a.argmax_dump = d_argmax;
   a.tok_emb = tok_emb_; a.pos = dec_pos_; a.x = d_xdec_; a.d_model = cfg_.n_text_state;
   a.done_host = d_forced ? nullptr : d_done_live_;
+  if (spec.slots) a.sot_clip = d_slot_ctx_;  // a prefix per slot: the second instantiation of the kernel
   if (spec.mask & 4) launch_advance(a, s);
 }
 
@@ -692,7 +693,8 @@ void Engine::enqueue_timestamp_rules(const StepSpec& spec, int batch, const int*
   r.out_ids = d_out_ids_; r.n_out = d_nout_; r.n_ctx = cfg_.n_text_ctx;
   r.forced = d_forced; r.n_forced = n_forced; r.base = spec.base;
   r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
-  if (spec.mode == kDecodeSampled) launch_timestamp_rules_sampled(r, spec.score_out, spec.sample, s);  // + a draw at the clip's temperature
+  if (spec.slots) launch_stream_rules(r, spec.score_out, stream_rules_params(), s);  // idle slots, the no-speech value and detection at offset 0
+  else if (spec.mode == kDecodeSampled) launch_timestamp_rules_sampled(r, spec.score_out, spec.sample, s);  // + a draw at the clip's temperature
   else if (spec.mode == kDecodeScored) launch_timestamp_rules_scored(r, spec.score_out, s);  // + the decision's log-probability, the no-speech value at offset 0
   else launch_timestamp_rules(r, s);
 }
@@ -747,17 +749,22 @@ void Engine::fetch_scores(int batch, const int* n_ids, float* token_logprob, flo
   HIP_CHECK(hipMemcpyAsync(nsp.data(), d_nospeech_, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   for (int b = 0; b < batch; ++b) {
-    const int n = std::max(0, std::min(n_ids[b], Tc - 1));
-    const bool eot = dec[(size_t)b * Tc + n] == cfg_.eot;
-    double sum = eot ? (double)lp[(size_t)b * Tc + n] : 0.0;
-    for (int i = 0; i < n; ++i) sum += (double)lp[(size_t)b * Tc + i];
-    if (token_logprob) {
-      for (int i = 0; i < Tc; ++i) token_logprob[(size_t)b * Tc + i] = i <= n ? lp[(size_t)b * Tc + i] : 0.f;
-    }
-    if (avg_logprob) avg_logprob[b] = (float)(sum / (double)(n + 1));  // openai-whisper: sum_logprobs / (len(tokens) + 1)
+    clip_score_summary(&lp[(size_t)b * Tc], &dec[(size_t)b * Tc], n_ids[b], token_logprob ? token_logprob + (size_t)b * Tc : nullptr,
+                       avg_logprob ? avg_logprob + b : nullptr, ended_eot ? ended_eot + b : nullptr);
     if (no_speech_logprob) no_speech_logprob[b] = nsp[b];
-    if (ended_eot) ended_eot[b] = eot ? 1 : 0;
   }
+}
+
+void Engine::clip_score_summary(const float* lp, const int* dec, int n_ids, float* token_logprob, float* avg_logprob, int* ended_eot) const {
+  const int Tc = cfg_.n_text_ctx;
+  const int n = std::max(0, std::min(n_ids, Tc - 1));
+  const bool eot = dec[n] == cfg_.eot;
+  double sum = eot ? (double)lp[n] : 0.0;
+  for (int i = 0; i < n; ++i) sum += (double)lp[i];
+  if (token_logprob)
+    for (int i = 0; i < Tc; ++i) token_logprob[i] = i <= n ? lp[i] : 0.f;
+  if (avg_logprob) *avg_logprob = (float)(sum / (double)(n + 1));  // openai-whisper: sum_logprobs / (len(tokens) + 1)
+  if (ended_eot) *ended_eot = eot ? 1 : 0;
 }
 
 void Engine::fetch_ids(int batch, int32_t* ids, int* n_ids) {

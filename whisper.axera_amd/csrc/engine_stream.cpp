@@ -20,17 +20,57 @@ __global__ static void slot_reset_kernel(int slot, int max_new, const int* sot, 
   for (int c = threadIdx.x; c < d; c += blockDim.x) x[(long)slot * d + c] = (float)tok_emb[(long)t * d + c] + pos[c];  // position 0
 }
 
-void Engine::stream_open(int n_slots) {
+// The timestamp twin of slot_reset_kernel (stream mode 1): the slot's own prefix [sot, language id, task id, unused], its detect flag
+// and language index, and a zeroed lang_logprob row, so that nothing of the clip that sat here before is left: the language and
+// the detect flag are rewritten here, the no-speech value by the rules kernel at offset 0 (every clip passes it), the score entries
+// [0 .. n_ids] by the sampled steps.
+__global__ static void slot_reset_ts_kernel(int slot, int max_new, int sot, int lang_tok, int task_tok, int lang_index, int detect, int n_lang,
+                                            int* slot_ctx, int* slot_detect, int* slot_lang, float* slot_lang_lp, int* off, int* tok, int* done,
+                                            int* n_out, int* max_new_clip, const h16* tok_emb, const float* pos, float* x, int d) {
+  if (threadIdx.x == 0) {
+    off[slot] = 0; tok[slot] = sot; n_out[slot] = 0; max_new_clip[slot] = max_new; done[slot] = 0;
+    slot_ctx[4 * slot] = sot; slot_ctx[4 * slot + 1] = lang_tok; slot_ctx[4 * slot + 2] = task_tok; slot_ctx[4 * slot + 3] = 0;
+    slot_detect[slot] = detect; slot_lang[slot] = lang_index;
+  }
+  for (int j = threadIdx.x; j < n_lang; j += blockDim.x) slot_lang_lp[(long)slot * n_lang + j] = 0.f;
+  for (int c = threadIdx.x; c < d; c += blockDim.x) x[(long)slot * d + c] = (float)tok_emb[(long)sot * d + c] + pos[c];  // position 0
+}
+
+void Engine::ensure_stream_ts() {
+  ensure_lang_buffers();
+  if (d_slot_ctx_) return;
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  d_slot_ctx_ = pooled<int>(slot_allocs_, (size_t)cap_ * 4, true);  // (freed and re-made with the slot buffers)
+  d_slot_detect_ = pooled<int>(slot_allocs_, cap_, true);
+  d_slot_lang_ = pooled<int>(slot_allocs_, cap_, true);
+  d_slot_lang_lp_ = pooled<float>(slot_allocs_, (size_t)cap_ * cfg_.lang_tokens.size(), true);
+}
+
+StreamRulesParams Engine::stream_rules_params() const {
+  StreamRulesParams t{};
+  t.detect = d_slot_detect_; t.slot_ctx = d_slot_ctx_; t.lang_tokens = prefill_.lang_tok; t.n_lang = (int)cfg_.lang_tokens.size();
+  t.fallback_index = handle_lang_; t.lang_out = d_slot_lang_; t.lang_logprob = d_slot_lang_lp_;
+  return t;
+}
+
+void Engine::stream_open(int n_slots, int mode) {
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   if (n_slots < 1) throw std::runtime_error("stream_open: n_slots must be >= 1");
+  if (mode != 0 && mode != 1) throw std::runtime_error("stream_open: unknown mode " + std::to_string(mode) + " (0 plain, 1 scored timestamps)");
   if (user_stream_) throw std::runtime_error("stream_open: not with a caller-supplied stream (AX_WHISPER_SetStream)");
+  if (mode == 1) {
+    require_scored_vocab();
+    if (cfg_.lang_tokens.empty()) throw std::runtime_error("stream_open: the timestamp mode needs the config's language list");
+  }
   stream_close();
   ensure_capacity(std::max(n_slots, 3));
   const int n = std::max(n_slots, 3);  // the step sequence of 3+ slots handles any mix of idle and active slots
   hipStream_t s = stream();
-  // plain mode, every launch. Captured here, outside the serving loop (and probed with replays: before the state is set)
-  (void)step_graph(StepSpec{}, n, cfg_.n_text_ctx - 4);
+  stream_mode_ = mode;
+  if (mode == 1) ensure_stream_ts();
+  // every launch of the mode's step. Captured here, outside the serving loop (and probed with replays: before the state is set)
+  (void)step_graph(stream_spec(), n, cfg_.n_text_ctx - stream_n_prefix());
   reset_decode_state(n);
   std::vector<int> ones(n, 1);         // every slot idle: its attention launches return at once
   HIP_CHECK(hipMemcpy(d_done_, ones.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -40,11 +80,15 @@ void Engine::stream_open(int n_slots) {
   HIP_CHECK(hipStreamSynchronize(s));
   slot_state_.assign(n, kIdle);
   slot_max_new_.assign(n, 0);
+  slot_lang_.assign(n, handle_lang_);
+  slot_task_.assign(n, sot_seq_[2]);
+  slot_detect_.assign(n, 0);
   memset(h_done_live_, 0, (size_t)cap_ * 4);
   step_seq_ = 0;
   stream_slots_ = n;
   stream_user_slots_ = n_slots;
   cfg_.ints["stream_slots"] = n_slots;
+  cfg_.ints["stream_mode"] = mode;
 }
 
 void Engine::stream_close() {
@@ -53,14 +97,28 @@ void Engine::stream_close() {
   (void)hipStreamSynchronize(stream());
   stream_slots_ = 0;
   stream_user_slots_ = 0;
+  stream_mode_ = 0;
   slot_state_.clear();
   cfg_.ints["stream_slots"] = 0;
+  cfg_.ints["stream_mode"] = 0;
 }
 
-void Engine::stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count, const int* rates) {
+void Engine::stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count, const int* rates,
+                          const int* lang, const int* task) {
   HIP_CHECK(hipSetDevice(device_));
   if (stream_slots_ == 0) throw std::runtime_error("stream_admit: no stream open");
   if (count < 1 || count > stream_user_slots_) throw std::runtime_error("stream_admit: count out of range");
+  // a language or task per clip: refused before anything is enqueued, so the stream and its running slots are left as they were
+  if ((lang || task) && stream_mode_ != 1) throw std::runtime_error("stream_admit: a language or task per clip needs a stream opened in timestamp mode (AX_WHISPER_StreamOpenMode, mode 1)");
+  const int n_lang = (int)cfg_.lang_tokens.size();
+  int translate = -1;  // (as plan_contexts reads it: an id inside the vocabulary, or none)
+  if (const auto tr = cfg_.ints.find("translate"); tr != cfg_.ints.end() && tr->second >= 0 && tr->second < cfg_.n_vocab) translate = (int)tr->second;
+  for (int i = 0; i < count; ++i) {
+    if (lang && (lang[i] < -2 || lang[i] >= n_lang)) throw std::runtime_error("stream_admit: language index " + std::to_string(lang[i]) + " of clip " + std::to_string(i) + " outside [-2, " + std::to_string(n_lang) + ")");
+    if (lang && lang[i] == -2 && n_lang < 2) throw std::runtime_error("stream_admit: language detection needs a config that lists more than one language");
+    if (task && task[i] != 0 && task[i] != 1) throw std::runtime_error("stream_admit: task " + std::to_string(task[i]) + " of clip " + std::to_string(i) + " (0 transcribe, 1 translate)");
+    if (task && task[i] == 1 && translate < 0) throw std::runtime_error("stream_admit: translate: the config has no translate id inside the vocabulary");
+  }
   for (int i = 0; i < count; ++i) {
     // the slots the caller opened, not the 3 the step graph is rounded up to: finished_slots of StreamStep is [n_slots]
     if (slots[i] < 0 || slots[i] >= stream_user_slots_) throw std::runtime_error("stream_admit: slot out of range");
@@ -98,8 +156,12 @@ void Engine::stream_admit(const int* slots, const float* const* pcm, const int* 
     HIP_CHECK(hipEventRecord(ev_admit_[slots[i]], admit_stream_));
     h_done_live_[slots[i]] = 0;
     slot_state_[slots[i]] = kEncoding;
-    const int mn = max_new ? max_new[i] : 0;
-    slot_max_new_[slots[i]] = (mn > 0 && mn < Tc - 4) ? mn : Tc - 4;
+    const int mn = max_new ? max_new[i] : 0, room = Tc - stream_n_prefix();
+    slot_max_new_[slots[i]] = (mn > 0 && mn < room) ? mn : room;
+    const int lg = lang ? lang[i] : -1;
+    slot_lang_[slots[i]] = lg >= 0 ? lg : handle_lang_;
+    slot_detect_[slots[i]] = lg == -2 ? 1 : 0;
+    slot_task_[slots[i]] = (task && task[i] == 1) ? translate : sot_seq_[2];  // the task id itself
   }
 }
 
@@ -127,13 +189,19 @@ int Engine::stream_step(int n_steps, int* finished_slots) {
       if (q == hipErrorNotReady && active == 0) { HIP_CHECK(hipEventSynchronize(ev_admit_[i])); q = hipSuccess; }
       if (q == hipErrorNotReady) continue;
       HIP_CHECK(q);
-      hipLaunchKernelGGL(slot_reset_kernel, dim3(1), dim3(256), 0, s, i, slot_max_new_[i], d_sot_, d_off_, d_tok_, d_done_, d_nout_,
-                         d_max_new_clip_, tok_emb_, dec_pos_, d_xdec_, cfg_.n_text_state);
+      if (stream_mode_ == 1)
+        hipLaunchKernelGGL(slot_reset_ts_kernel, dim3(1), dim3(256), 0, s, i, slot_max_new_[i], sot_seq_[0], cfg_.lang_tokens[slot_lang_[i]],
+                           slot_task_[i], slot_lang_[i], slot_detect_[i], (int)cfg_.lang_tokens.size(),
+                           d_slot_ctx_, d_slot_detect_, d_slot_lang_, d_slot_lang_lp_, d_off_, d_tok_, d_done_, d_nout_, d_max_new_clip_, tok_emb_,
+                           dec_pos_, d_xdec_, cfg_.n_text_state);
+      else
+        hipLaunchKernelGGL(slot_reset_kernel, dim3(1), dim3(256), 0, s, i, slot_max_new_[i], d_sot_, d_off_, d_tok_, d_done_, d_nout_,
+                           d_max_new_clip_, tok_emb_, dec_pos_, d_xdec_, cfg_.n_text_state);
       slot_state_[i] = kActive;
       ++active;
     }
   };
-  hipGraphExec_t g = step_graph(StepSpec{}, n, cfg_.n_text_ctx - 4);  // the graph stream_open captured
+  hipGraphExec_t g = step_graph(stream_spec(), n, cfg_.n_text_ctx - stream_n_prefix());  // the graph stream_open captured
   // The host runs two steps ahead of the device (it waits for step k-2 before it enqueues step k): the queue never runs dry,
   // and what the host sees in the flags is at most two steps old, so a waiting clip takes a freed slot within two steps.
   for (int st = 0; st < std::max(1, n_steps); ++st) {
@@ -161,6 +229,86 @@ void Engine::stream_collect(int slot, int32_t* ids, int* n_ids) {
   HIP_CHECK(hipMemcpyAsync(n_ids, d_nout_ + slot, 4, hipMemcpyDeviceToHost, copy_stream_));
   HIP_CHECK(hipStreamSynchronize(copy_stream_));
   slot_state_[slot] = kIdle;
+}
+
+// Mode 1: the ids (timestamp tokens included) and the slot's scores and language, on copy_stream_ like the ids: the slot's score
+// entries, no-speech value and language were final before its done flag was raised (the rules launch of a step runs in front of its
+// advance launch), and a slot whose flag is set is written by nobody until it is refilled.
+void Engine::stream_collect_scored(int slot, int32_t* ids, int* n_ids, const SlotScores& out) {
+  HIP_CHECK(hipSetDevice(device_));
+  if (stream_slots_ == 0) throw std::runtime_error("stream_collect_scored: no stream open");
+  if (stream_mode_ != 1) throw std::runtime_error("stream_collect_scored: the stream was not opened in timestamp mode (AX_WHISPER_StreamOpenMode, mode 1)");
+  if (slot < 0 || slot >= stream_user_slots_ || slot_state_[slot] != kFinished) throw std::runtime_error("stream_collect_scored: slot has not finished");
+  const int Tc = cfg_.n_text_ctx, n_lang = (int)cfg_.lang_tokens.size();
+  std::vector<float> lp(Tc), llp(n_lang);
+  std::vector<int> dec(Tc);
+  float nsp = 0.f;
+  int lang = 0;
+  HIP_CHECK(hipMemcpyAsync(ids, d_out_ids_ + (size_t)slot * Tc, (size_t)Tc * 4, hipMemcpyDeviceToHost, copy_stream_));
+  HIP_CHECK(hipMemcpyAsync(n_ids, d_nout_ + slot, 4, hipMemcpyDeviceToHost, copy_stream_));
+  HIP_CHECK(hipMemcpyAsync(lp.data(), d_tok_lp_ + (size_t)slot * Tc, (size_t)Tc * 4, hipMemcpyDeviceToHost, copy_stream_));
+  HIP_CHECK(hipMemcpyAsync(dec.data(), d_dec_id_ + (size_t)slot * Tc, (size_t)Tc * 4, hipMemcpyDeviceToHost, copy_stream_));
+  HIP_CHECK(hipMemcpyAsync(&nsp, d_nospeech_ + slot, 4, hipMemcpyDeviceToHost, copy_stream_));
+  HIP_CHECK(hipMemcpyAsync(&lang, d_slot_lang_ + slot, 4, hipMemcpyDeviceToHost, copy_stream_));
+  HIP_CHECK(hipMemcpyAsync(llp.data(), d_slot_lang_lp_ + (size_t)slot * n_lang, (size_t)n_lang * 4, hipMemcpyDeviceToHost, copy_stream_));
+  HIP_CHECK(hipStreamSynchronize(copy_stream_));
+  clip_score_summary(lp.data(), dec.data(), *n_ids, out.token_logprob, out.avg_logprob, out.ended_eot);
+  if (out.no_speech_logprob) *out.no_speech_logprob = nsp;
+  if (out.lang) *out.lang = lang;
+  if (out.lang_logprob) std::copy(llp.begin(), llp.end(), out.lang_logprob);
+  slot_state_[slot] = kIdle;
+}
+
+// The stream's rules kernel alone on host data (tests). `chosen` / `logprob` come from a one-partial argmax row and a score row of
+// n_text_ctx + 1 entries per slot, as Engine::timestamp_rules has them; every output starts from the caller's values.
+void Engine::stream_rules_stage(const StreamRulesIO& io) {
+  require_no_stream("stream_rules_stage");
+  require_scored_vocab();
+  const int n = io.n, Tc = cfg_.n_text_ctx, n_lang = (int)cfg_.lang_tokens.size();
+  if (n < 1 || !io.rows || !io.off || !io.done || !io.detect || !io.hist || !io.n_hist || !io.slot_ctx || !io.chosen || !io.logprob ||
+      !io.no_speech || !io.lang_out || !io.lang_logprob)
+    throw std::runtime_error("stream_rules_stage: bad arguments");
+  if (n_lang < 1) throw std::runtime_error("stream_rules_stage: the config lists no languages");
+  for (int b = 0; b < n; ++b)
+    if (io.off[b] < 0 || io.off[b] >= Tc) throw std::runtime_error("stream_rules_stage: offset out of range");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  ensure_lang_buffers();
+  hipStream_t s = stream();
+  const StagedRows in = stage_rows("stream_rules_stage", io.rows, io.hist, io.n_hist, n, s);
+  DeviceArray<int> b_off = device_array<int>(n), b_done = device_array<int>(n), b_det = device_array<int>(n), b_ctx = device_array<int>((size_t)n * 4),
+                   b_idx = device_array<int>(n), b_dec = device_array<int>((size_t)n * (Tc + 1)), b_lang = device_array<int>(n);
+  DeviceArray<float> b_val = device_array<float>(n), b_lp = device_array<float>((size_t)n * (Tc + 1)), b_nsp = device_array<float>(n),
+                     b_llp = device_array<float>((size_t)n * n_lang);
+  HIP_CHECK(hipMemcpyAsync(b_off, io.off, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_done, io.done, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_det, io.detect, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_ctx, io.slot_ctx, (size_t)n * 16, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_idx, io.chosen, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_nsp, io.no_speech, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_lang, io.lang_out, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(b_llp, io.lang_logprob, (size_t)n * n_lang * 4, hipMemcpyHostToDevice, s));
+  for (int b = 0; b < n; ++b)  // the entry the kernel would write: the caller's sentinel
+    HIP_CHECK(hipMemcpyAsync(b_lp + (size_t)b * (Tc + 1) + io.n_hist[b], io.logprob + b, 4, hipMemcpyHostToDevice, s));
+  TsRulesParams r{};
+  r.logits = in.logits; r.stride = in.stride; r.batch = n;
+  r.n_vocab = cfg_.n_vocab; r.eot = cfg_.eot; r.ts_begin = cfg_.no_timestamps + 1;
+  r.off = b_off; r.n_prefix = 3; r.done = b_done;
+  r.out_ids = in.hist; r.n_out = in.n_hist; r.n_ctx = Tc;
+  r.amax_val = b_val; r.amax_idx = b_idx; r.amax_stride = 1;
+  StreamRulesParams t{};
+  t.detect = b_det; t.slot_ctx = b_ctx; t.lang_tokens = prefill_.lang_tok; t.n_lang = n_lang; t.fallback_index = handle_lang_;
+  t.lang_out = b_lang; t.lang_logprob = b_llp;
+  launch_stream_rules(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, b_nsp, (int)cfg_.ints.at("no_speech")}, t, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(io.chosen, b_idx, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(io.slot_ctx, b_ctx, (size_t)n * 16, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(io.no_speech, b_nsp, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(io.lang_out, b_lang, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(io.lang_logprob, b_llp, (size_t)n * n_lang * 4, hipMemcpyDeviceToHost, s));
+  for (int b = 0; b < n; ++b)
+    HIP_CHECK(hipMemcpyAsync(io.logprob + b, b_lp + (size_t)b * (Tc + 1) + io.n_hist[b], 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // ------------------------------------------------------------------------------ which of the engine's streams run side by side?

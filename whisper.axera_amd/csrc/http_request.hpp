@@ -20,6 +20,15 @@ struct HttpHead {
   bool expect_continue = false;
   int sample_rate = 16000;      // value of X-Sample-Rate in Hz (16000 if absent)
   bool rate_ok = true;          // false: an X-Sample-Rate header is present but is not a plain positive decimal number
+  // the request fields of a server started with --timestamps (DESIGN.md "Slot stream in timestamp mode"); each *_ok is false when
+  // the header is present but malformed
+  int timestamps = -1;          // X-Timestamps: 0 | 1 (-1: absent)
+  bool timestamps_ok = true;
+  std::string language;         // X-Language: a language code, lower-cased, or "auto" ("" if absent)
+  bool has_language = false, language_ok = true;  // (well-formed: 1 .. 12 characters of [a-z-]; whether the model lists it is the engine's answer)
+  int task = -1;                // X-Task: 0 transcribe | 1 translate (-1: absent)
+  bool task_ok = true;
+  bool has_slot_fields() const { return timestamps != -1 || !timestamps_ok || has_language || task != -1 || !task_ok; }
   size_t header_end = std::string::npos;  // offset of the blank line's "\r\n\r\n" in the buffer
 };
 
@@ -71,6 +80,22 @@ inline bool parse_http_head(const std::string& buf, HttpHead& h) {
     h.rate_ok = !sr.empty() && sr.size() <= 7 && std::all_of(sr.begin(), sr.end(), [](char c) { return c >= '0' && c <= '9'; }) && atoi(sr.c_str()) > 0;
     if (h.rate_ok) h.sample_rate = atoi(sr.c_str());
   }
+  bool has_ts = false, has_task = false;
+  const std::string ts = http_header_value(lhead, "x-timestamps:", &has_ts);
+  if (has_ts) {
+    h.timestamps_ok = ts == "0" || ts == "1";
+    if (h.timestamps_ok) h.timestamps = ts == "1" ? 1 : 0;
+  }
+  const std::string lg = http_header_value(lhead, "x-language:", &h.has_language);
+  if (h.has_language) {
+    h.language_ok = !lg.empty() && lg.size() <= 12 && std::all_of(lg.begin(), lg.end(), [](char c) { return (c >= 'a' && c <= 'z') || c == '-'; });
+    if (h.language_ok) h.language = lg;
+  }
+  const std::string tk = http_header_value(lhead, "x-task:", &has_task);
+  if (has_task) {
+    h.task_ok = tk == "transcribe" || tk == "translate";
+    if (h.task_ok) h.task = tk == "translate" ? 1 : 0;
+  }
   h.content_type = http_header_value(lhead, "content-type:");
   h.expect_continue = http_header_value(lhead, "expect:").find("100-continue") != std::string::npos;
   return true;
@@ -93,5 +118,17 @@ inline const char* asr_request_error(const HttpHead& h, size_t body_bytes) {
   if (!h.rate_ok) return R"({"error": "X-Sample-Rate must be a positive integer in Hz"})";
   return nullptr;
 }
+
+// The slot fields of a POST /asr (X-Timestamps, X-Language, X-Task): nullptr if they can be served, else the error body (status 400).
+// server_timestamps: the server runs its slots in timestamp mode (--timestamps); without it any of the three is refused.
+inline const char* asr_slot_fields_error(const HttpHead& h, bool server_timestamps) {
+  if (!h.timestamps_ok) return R"({"error": "X-Timestamps must be 0 or 1"})";
+  if (!h.language_ok) return R"({"error": "X-Language must be a language code or auto"})";
+  if (!h.task_ok) return R"({"error": "X-Task must be transcribe or translate"})";
+  if (!server_timestamps && h.has_slot_fields()) return R"({"error": "X-Timestamps, X-Language and X-Task need a server started with --timestamps"})";
+  return nullptr;
+}
+// (a well-formed X-Language the model does not list)
+inline const char* asr_unknown_language_error() { return R"({"error": "X-Language names a language the model does not list"})"; }
 
 }  // namespace axw

@@ -201,12 +201,27 @@ class IEngine {
   };
   virtual void align_kernel(int which, const AlignKernelIO& io) = 0;  // 0 qk_softmax, 1 normalize, 2 dtw
   // utterance slots refilled while the others decode (include/ax_whisper_api.h: AX_WHISPER_Stream*)
-  virtual void stream_open(int n_slots) = 0;
+  // mode 0: the plain greedy decode in the handle's language; mode 1: the scored timestamp mode (DESIGN.md "Slot stream in timestamp
+  // mode"): prefix [sot, language, task] per slot, ids with their timestamp tokens, scores and a language per slot. One mode per stream.
+  virtual void stream_open(int n_slots, int mode = 0) = 0;
   // rates (or null: 16000 Hz): host [count], as DecodeRequest::sample_rate
+  // lang, task (mode 1 only; either may be null: all -1 / all 0): host [count], as LangSpec
   virtual void stream_admit(const int* slots, const float* const* pcm, const int* n_samples, const int* max_new, int count,
-                            const int* rates = nullptr) = 0;
+                            const int* rates = nullptr, const int* lang = nullptr, const int* task = nullptr) = 0;
   virtual int stream_step(int n_steps, int* finished_slots) = 0;  // returns the number of finished slots written
   virtual void stream_collect(int slot, int32_t* ids, int* n_ids) = 0;
+  // mode 1: stream_collect plus the slot's scores (token_logprob [n_text_ctx]: entries 0 .. n_ids, the rest 0; the others one value)
+  // and its language (lang_logprob [n_lang]: a detecting clip's, else zeros). Every array but ids and n_ids may be null.
+  struct SlotScores { float *token_logprob, *avg_logprob, *no_speech_logprob; int* ended_eot; int* lang; float* lang_logprob; };
+  virtual void stream_collect_scored(int slot, int32_t* ids, int* n_ids, const SlotScores& out) = 0;
+  // the stream's rules kernel alone on host data (tests): rows [n][n_vocab], off / done / detect [n], hist [n][n_text_ctx] with
+  // n_hist [n], slot_ctx [n][4] (in/out), and sentinel-filled outputs that are written only where the kernel writes: chosen, logprob
+  // [n] (the decision and its log-probability of a slot that samples), no_speech [n], lang_out [n], lang_logprob [n][n_lang] (all in/out)
+  struct StreamRulesIO {
+    int n; const float* rows; const int* off; const int* done; const int* detect; const int32_t* hist; const int* n_hist;
+    int* slot_ctx; int32_t* chosen; float* logprob; float* no_speech; int* lang_out; float* lang_logprob;
+  };
+  virtual void stream_rules_stage(const StreamRulesIO& io) = 0;
   virtual void stream_close() = 0;
   // every 16-bit tensor the engine STORES between kernels (encoder activations of `batch` clips, cross / self K/V caches, the
   // decoder's activation pairs): non-finite count and max |x| per buffer; returns the number of buffers reported (<= n_max)

@@ -21,6 +21,11 @@
 //       serve more clips per second (Whisper-small, clips of 60-150 ids: 341 / 456 / 489 clips/s with 64 / 128 / 256).
 //   --scheduler batches: micro-batches (up to --max_batch clips, waiting at most --batch_wait_ms for
 //       stragglers) through AX_WHISPER_RunPCMBatch; a batch returns when its slowest clip has finished.
+//   --timestamps (slots scheduler only; refused with --scheduler batches): the slots run in the scored timestamp mode
+//       (AX_WHISPER_StreamOpenMode, mode 1; DESIGN.md "Slot stream in timestamp mode") and a request may carry X-Language: <code>|auto,
+//       X-Task: transcribe|translate and X-Timestamps: 0|1. The reply is the reference's plus "language"; with X-Timestamps: 1 also
+//       "segments" [{"start", "end", "text"}], "avg_logprob" and "no_speech_prob". Every request then goes through the slots (the
+//       one-clip and group short cuts decode in plain mode). Without the flag nothing changes, and any of the three headers is a 400.
 // Connections: at most --max_conns at a time (503 beyond), a body of at most --max_body_mb (413 beyond; 30 s of
 // audio is 1.92 MB), --recv_timeout_s per read, and a body that ends before its Content-Length is a 400, not a
 // transcription of half a clip.
@@ -35,6 +40,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cmath>
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +58,8 @@
 struct Job {
   std::vector<float> pcm;
   int rate = 16000;  // X-Sample-Rate
+  int lang = -1, task = 0;   // --timestamps: X-Language as the C ABI takes it (an index, -1 the handle's, -2 detect), X-Task
+  bool want_segments = false;  // X-Timestamps: 1
   std::promise<std::pair<bool, std::string>> done;
   std::chrono::steady_clock::time_point arrived = std::chrono::steady_clock::now();
 };
@@ -64,6 +72,7 @@ static std::atomic<int> g_conns{0}, g_busy_slots{0};
 static std::atomic<long> g_served{0};
 static std::vector<AX_WHISPER_HANDLE> g_models;  // for /health
 static int g_max_conns = 256, g_recv_timeout_s = 10;
+static bool g_timestamps = false;  // --timestamps: the slots run in timestamp mode and a job's result is its whole reply body
 static size_t g_max_body = (size_t)16 << 20;
 
 static std::string json_escape(const std::string& s) {
@@ -145,7 +154,38 @@ static void batcher(AX_WHISPER_HANDLE model, int max_batch, int wait_ms) {
 // per clip against 1.74 ms alone (bench.py stream64.encoder_pass_by_group_size). Default N = 1 (admit as they come): on
 // MI355X at 64 slots and 60-150 ids per clip that measures FASTER than N = 8 (366 against 354 clips/s, bench.py stream64),
 // because a slot that waits for company idles for whole decoder steps; the knob is for models whose encoder dominates.
-static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, int steps_per_call, int min_admit, int admit_wait_ms) {
+// --timestamps: the reply body of one collected slot (the caller sends it as it is)
+static std::string timestamp_reply(AX_WHISPER_HANDLE model, const Job& job, const int32_t* ids, int n, float avg_logprob, float no_speech_logprob,
+                                   int lang, bool& ok) {
+  const int tb = AX_WHISPER_GetConfigInt(model, "no_timestamps") + 1, eot = AX_WHISPER_GetConfigInt(model, "eot");
+  const float clip_s = std::min((float)job.pcm.size() / (float)job.rate, 30.0f);
+  const int n_max = n / 2 + 1;
+  std::vector<float> st(n_max), en(n_max);
+  std::vector<int> b(n_max), e(n_max);
+  int n_seg = 0;
+  ok = AX_WHISPER_SplitSegments(ids, n, tb, eot, clip_s, n_max, st.data(), en.data(), b.data(), e.data(), &n_seg) == 0;
+  std::string text, segs;
+  for (int k = 0; ok && k < n_seg; ++k) {
+    char* t = nullptr;
+    ok = AX_WHISPER_TranscriptLang(model, ids + b[k], e[k] - b[k], lang, &t) == 0 && t;
+    if (!ok) { free(t); break; }
+    text += t;
+    char head[96];
+    snprintf(head, sizeof head, "%s{\"start\": %.2f, \"end\": %.2f, \"text\": \"", k ? ", " : "", (double)st[k], (double)en[k]);
+    segs += head + json_escape(t) + "\"}";
+    free(t);
+  }
+  const char* code = AX_WHISPER_LanguageCode(model, lang);
+  std::string body = "{\n  \"success\": true,\n  \"text\": \"" + json_escape(text) + "\",\n  \"language\": \"" + json_escape(code ? code : "") + "\"";
+  if (job.want_segments) {
+    char num[96];
+    snprintf(num, sizeof num, ",\n  \"avg_logprob\": %.9g,\n  \"no_speech_prob\": %.9g", (double)avg_logprob, (double)std::exp((double)no_speech_logprob));
+    body += ",\n  \"segments\": [" + segs + "]" + num;
+  }
+  return body + "\n}";
+}
+
+static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, int steps_per_call, int min_admit, int admit_wait_ms, bool timestamps) {
   const int Tc = std::max(1, AX_WHISPER_GetConfigInt(model, "n_text_ctx"));
   std::vector<Job*> owner(n_slots, nullptr);
   std::vector<int> fin(std::max(n_slots, 3));
@@ -176,14 +216,14 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
                         std::chrono::steady_clock::now() - g_queue.front()->arrived < std::chrono::milliseconds(admit_wait_ms);
       while (!hold && !g_queue.empty() && busy + (int)take.size() < n_slots) { take.push_back(g_queue.front()); g_queue.pop_front(); }
     }
-    if (busy == 0 && take.size() == 1) {  // alone on an idle device
+    if (!timestamps && busy == 0 && take.size() == 1) {  // alone on an idle device
       if (open) { AX_WHISPER_StreamClose(model); open = false; }
       run_alone(take[0]);
       continue;
     }
     // (persistent_decode is 0 while the engine backs off after a give-up — CUs taken by another process: the group path would then
     // run the launch-per-phase sequence synchronously, ~316 ms per pair against ~240 ms through slots, with no admission meanwhile)
-    if (busy == 0 && take.size() >= 2 && (int)take.size() <= launch_clips && AX_WHISPER_GetConfigInt(model, "persistent_decode") == 1) {
+    if (!timestamps && busy == 0 && take.size() >= 2 && (int)take.size() <= launch_clips && AX_WHISPER_GetConfigInt(model, "persistent_decode") == 1) {
       // two or three requests on an idle device: their greedy loops in ONE persistent launch (134 ms for a pair of Whisper-small
       // clips of 444 ids against ~240 ms for two live slots of the step sequence); a refused group (one bad request) is served one by one
       if (open) { AX_WHISPER_StreamClose(model); open = false; }
@@ -200,7 +240,8 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
       continue;
     }
     if (!take.empty() && !open) {
-      if (AX_WHISPER_StreamOpen(model, n_slots) != 0) { for (Job* j : take) run_alone(j); continue; }
+      if (timestamps && AX_WHISPER_StreamOpenMode(model, n_slots, 1) != 0) { for (Job* j : take) fail(j); continue; }
+      if (!timestamps && AX_WHISPER_StreamOpen(model, n_slots) != 0) { for (Job* j : take) run_alone(j); continue; }
       open = true;
     }
     if (!take.empty()) {
@@ -208,7 +249,8 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
       // refused (one bad request: e.g. non-finite samples) the requests are admitted one by one so that only that one fails
       std::vector<int> sl;
       std::vector<const float*> ptrs;
-      std::vector<int> lens, rates;
+      std::vector<int> lens, rates, langs, tasks;
+      for (Job* j : take) { langs.push_back(j->lang); tasks.push_back(j->task); }
       for (int i = 0, s2 = 0; i < (int)take.size(); ++i) {
         while (owner[s2]) ++s2;
         sl.push_back(s2++);
@@ -218,14 +260,17 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
       }
       // (a pass without a clip at another rate is the call it always was)
       const bool all16 = std::all_of(rates.begin(), rates.end(), [](int r) { return r == 16000; });
-      if ((all16 ? AX_WHISPER_StreamAdmitBatch(model, sl.data(), ptrs.data(), lens.data(), nullptr, (int)take.size())
-                 : AX_WHISPER_StreamAdmitBatchRate(model, sl.data(), ptrs.data(), lens.data(), rates.data(), nullptr, (int)take.size())) == 0) {
+      if ((timestamps ? AX_WHISPER_StreamAdmitBatchLang(model, sl.data(), ptrs.data(), lens.data(), all16 ? nullptr : rates.data(), nullptr, langs.data(),
+                                                        tasks.data(), (int)take.size())
+           : all16   ? AX_WHISPER_StreamAdmitBatch(model, sl.data(), ptrs.data(), lens.data(), nullptr, (int)take.size())
+                     : AX_WHISPER_StreamAdmitBatchRate(model, sl.data(), ptrs.data(), lens.data(), rates.data(), nullptr, (int)take.size())) == 0) {
         for (size_t i = 0; i < take.size(); ++i) owner[sl[i]] = take[i];
         busy += (int)take.size();
       } else {
         for (size_t i = 0; i < take.size(); ++i) {
-          if ((rates[i] == 16000 ? AX_WHISPER_StreamAdmit(model, sl[i], ptrs[i], lens[i], 0)
-                                 : AX_WHISPER_StreamAdmitBatchRate(model, &sl[i], &ptrs[i], &lens[i], &rates[i], nullptr, 1)) != 0) { fail(take[i]); continue; }
+          if ((timestamps          ? AX_WHISPER_StreamAdmitBatchLang(model, &sl[i], &ptrs[i], &lens[i], &rates[i], nullptr, &langs[i], &tasks[i], 1)
+               : rates[i] == 16000 ? AX_WHISPER_StreamAdmit(model, sl[i], ptrs[i], lens[i], 0)
+                                   : AX_WHISPER_StreamAdmitBatchRate(model, &sl[i], &ptrs[i], &lens[i], &rates[i], nullptr, 1)) != 0) { fail(take[i]); continue; }
           owner[sl[i]] = take[i];
           ++busy;
         }
@@ -247,10 +292,19 @@ static void slot_scheduler(AX_WHISPER_HANDLE model, int n_slots, int wait_ms, in
       if (sl < 0 || sl >= n_slots || !owner[sl]) continue;
       int n = 0;
       char* text = nullptr;
-      if (AX_WHISPER_StreamCollect(model, sl, ids.data(), &n) != 0) { collect_failed = true; break; }
-      const bool ok = AX_WHISPER_Transcript(model, ids.data(), n, &text) == 0 && text;
-      owner[sl]->done.set_value({ok, text ? std::string(text) : std::string()});
-      free(text);
+      if (timestamps) {
+        float avg = 0.f, nsp = 0.f;
+        int lang = 0;
+        if (AX_WHISPER_StreamCollectScored(model, sl, ids.data(), &n, nullptr, &avg, &nsp, nullptr, &lang, nullptr) != 0) { collect_failed = true; break; }
+        bool ok = false;
+        std::string body = timestamp_reply(model, *owner[sl], ids.data(), n, avg, nsp, lang, ok);
+        owner[sl]->done.set_value({ok, ok ? body : std::string()});
+      } else {
+        if (AX_WHISPER_StreamCollect(model, sl, ids.data(), &n) != 0) { collect_failed = true; break; }
+        const bool ok = AX_WHISPER_Transcript(model, ids.data(), n, &text) == 0 && text;
+        owner[sl]->done.set_value({ok, text ? std::string(text) : std::string()});
+        free(text);
+      }
       owner[sl] = nullptr;
       --busy;
       ++g_served;
@@ -349,6 +403,10 @@ static void serve(int fd) {
     send_response(fd, 404, R"({"error": "Not found"})");
   } else if (const char* bad = axw::asr_request_error(hh, body.size())) {
     send_response(fd, 400, bad);
+  } else if (const char* bad = axw::asr_slot_fields_error(hh, g_timestamps)) {
+    send_response(fd, 400, bad);
+  } else if (hh.has_language && hh.language != "auto" && AX_WHISPER_LanguageIndex(g_models[0], hh.language.c_str()) < 0) {
+    send_response(fd, 400, axw::asr_unknown_language_error());
   } else if (hh.sample_rate != 16000 && AX_WHISPER_ResampledLength((long long)(body.size() / sizeof(float)), hh.sample_rate) < 0) {
     // a rate or a length the resampler refuses: its error text, before the clip is queued
     send_response(fd, 400, "{\"error\": \"" + json_escape(AX_WHISPER_LastError(nullptr)) + "\"}");
@@ -356,6 +414,9 @@ static void serve(int fd) {
     {
       Job job;
       job.rate = hh.sample_rate;
+      if (hh.has_language) job.lang = hh.language == "auto" ? -2 : AX_WHISPER_LanguageIndex(g_models[0], hh.language.c_str());
+      job.task = hh.task == 1 ? 1 : 0;
+      job.want_segments = hh.timestamps == 1;
       job.pcm.resize(body.size() / sizeof(float));
       memcpy(job.pcm.data(), body.data(), body.size());                                      // hpp:103-113
       auto fut = job.done.get_future();
@@ -363,6 +424,7 @@ static void serve(int fd) {
       g_cv.notify_all();
       auto res = fut.get();
       if (!res.first) send_response(fd, 400, R"({"error": "Run model failed!"})");           // hpp:79-83
+      else if (g_timestamps) send_response(fd, 200, res.second);
       else send_response(fd, 200, "{\n  \"success\": true,\n  \"text\": \"" + json_escape(res.second) + "\"\n}");  // hpp:86-90
     }
   }
@@ -373,6 +435,7 @@ static void serve(int fd) {
 int main(int argc, char** argv) {
   int port = 8080, max_batch = 64, wait_ms = 5, steps_per_call = 8, max_body_mb = 16, min_admit = 1, admit_wait_ms = 20;
   std::string model_type = "turbo", model_path = "../models-mi355x", language = "zh", devices, scheduler = "slots";
+  bool timestamps = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -387,6 +450,7 @@ int main(int argc, char** argv) {
     if (val("batch_wait_ms", nullptr, v)) { wait_ms = std::max(0, atoi(v.c_str())); continue; }
     if (val("model_type", "-t", model_type) || val("model_path", "-p", model_path) || val("language", "-l", language)) continue;
     if (val("devices", nullptr, devices) || val("scheduler", nullptr, scheduler)) continue;
+    if (a == "--timestamps") { timestamps = true; continue; }
     if (val("steps_per_call", nullptr, v)) { steps_per_call = std::max(1, atoi(v.c_str())); continue; }
     if (val("min_admit", nullptr, v)) { min_admit = std::max(1, atoi(v.c_str())); continue; }
     if (val("admit_wait_ms", nullptr, v)) { admit_wait_ms = std::max(0, atoi(v.c_str())); continue; }
@@ -394,13 +458,14 @@ int main(int argc, char** argv) {
     if (val("max_body_mb", nullptr, v)) { max_body_mb = std::max(1, atoi(v.c_str())); continue; }
     if (val("recv_timeout_s", nullptr, v)) { g_recv_timeout_s = std::max(1, atoi(v.c_str())); continue; }
     fprintf(stderr, "usage: %s [--port 8080] [-t model_type] [-p model_path] [-l language] [--max_batch 64] [--batch_wait_ms 5] [--devices all|0,1,..]\n"
-                    "          [--scheduler slots|batches] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
+                    "          [--scheduler slots|batches] [--timestamps] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
     return a == "--help" || a == "-?" ? 0 : 1;
   }
   printf("port: %d\n", port);
   printf("model_path: %s\n", model_path.c_str());
   printf("model_type: %s\n", model_type.c_str());
   printf("language: %s\n", language.c_str());
+  if (timestamps && scheduler == "batches") { printf("--timestamps needs --scheduler slots (micro-batches decode in plain mode)\n"); return 1; }
 
   // one handle (one engine, one batcher thread) per device
   std::vector<int> devs;
@@ -432,6 +497,8 @@ int main(int argc, char** argv) {
   printf("devices: %d\n", (int)models.size());
   if (scheduler != "slots" && scheduler != "batches") { printf("--scheduler must be slots or batches\n"); return 1; }
   printf("scheduler: %s\n", scheduler.c_str());
+  if (timestamps) printf("timestamps: on\n");
+  g_timestamps = timestamps;
   g_models = models;
   g_max_body = (size_t)max_body_mb << 20;
 
@@ -448,7 +515,7 @@ int main(int argc, char** argv) {
 
   std::vector<std::thread> bts;
   for (AX_WHISPER_HANDLE m : models) {
-    if (scheduler == "slots" && max_batch >= 2) bts.emplace_back(slot_scheduler, m, max_batch, wait_ms, steps_per_call, min_admit, admit_wait_ms);
+    if (scheduler == "slots" && (max_batch >= 2 || timestamps)) bts.emplace_back(slot_scheduler, m, max_batch, wait_ms, steps_per_call, min_admit, admit_wait_ms, timestamps);
     else bts.emplace_back(batcher, m, max_batch, wait_ms);
   }
   signal(SIGPIPE, SIG_IGN);
