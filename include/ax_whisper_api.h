@@ -586,6 +586,29 @@ AX_WHISPER_API int AX_WHISPER_SetAlignmentHeads(AX_WHISPER_HANDLE handle, const 
 /** Host only: the list a handle constructed from this config file starts with, as n (layer, head) pairs (at most n_max); -1 on a
  *  list that names a head the decoder does not have, names one twice or is not a list of pairs. */
 AX_WHISPER_API int AX_WHISPER_ConfigAlignmentHeads(const char* config_path, int n_max, int* pairs, int* n);
+/** Token suppression (DESIGN.md "Token suppression"): the handle's suppress set, n vocabulary ids (duplicates are fine). At every
+ *  sampled step of timestamp mode an id of the set counts exactly as if its logit were -inf, before rules 2 to 5 and before
+ *  anything is normalised: it is never rule 5's best text id, never part of the log-probabilities' normaliser, never drawn and never
+ *  a beam candidate. Every timestamp-mode entry point picks the set up from the handle: the batch, scored, sampled, prompted, language,
+ *  beam, long-form, chunked and word calls, a stream opened in mode 1, and the stage-level ApplyTimestampRules, ScoreTimestampRules,
+ *  SampleTimestampRules, BeamCandidates, StreamRulesStage and DecodeForced*. Not filtered: no_speech_logprob, language detection,
+ *  the word-timestamp token probabilities, plain mode. Ids of [0, eot) matter; ids of (eot, timestamp_begin) are accepted and have
+ *  no effect (rule 1 masks them); -1 with an error text for eot, a timestamp id, an id outside the vocabulary, more than n_vocab
+ *  entries, or while a stream is open (a stream opened afterwards uses the set). n == 0 restores what the handle was constructed
+ *  with: the optional key "suppress_tokens": [ids ...] of {type}_config.json, where an entry -1 stands for NonSpeechTokens of the
+ *  model's tokens file; absent or []: no set, and nothing this library computes or launches differs from a build without the
+ *  feature. GetConfigInt "n_suppress_tokens" counts the set in use. With several devices every engine gets the set. */
+AX_WHISPER_API int AX_WHISPER_SetSuppressTokens(AX_WHISPER_HANDLE handle, const int* ids, int n);
+/** The set in use, sorted, duplicates dropped (at most n_max ids; -1 if there are more). */
+AX_WHISPER_API int AX_WHISPER_GetSuppressTokens(AX_WHISPER_HANDLE handle, int n_max, int* ids, int* n);
+/** Host only: openai-whisper's non_speech_tokens (what its suppress_tokens = -1 stands for) from a {type}-tokens.txt, sorted: the
+ *  first id of " -" and " '", and for every symbol of its list the first id of the symbol and of " " + symbol where that is the
+ *  whole encoding or the symbol is one of the musical signs; 82 ids for the multilingual vocabulary. -1 with an error text
+ *  (AX_WHISPER_LastError(NULL)) where the file gives a needed byte no id. */
+AX_WHISPER_API int AX_WHISPER_NonSpeechTokens(const char* tokens_path, int n_max, int* ids, int* n);
+/** Host only: the set a handle constructed from this config file starts with (tokens_path is read only where the list holds -1 and
+ *  may be NULL otherwise); -1 on a key that is not a list of ids or names an id that SetSuppressTokens refuses. */
+AX_WHISPER_API int AX_WHISPER_ConfigSuppressTokens(const char* config_path, const char* tokens_path, int n_max, int* ids, int* n);
 /** One alignment kernel alone on host data (the handle gives the device and the 16-bit type). Clip c has len[c] rows and n_keys[c] frames.
  *  QKSoftmax: q fp32 [rows][64 n_head] (clip c's rows from row0[c]), k fp32 [n_slots][n_head][keys_pad][64] (clip c reads slot[c]), both
  *  narrowed to the 16-bit type; heads [n_align]; P [n_clips][n_align][rows_pad][f_pad] in and out (f_pad a multiple of 64): row i < len[c],

@@ -167,6 +167,10 @@ SYMBOLS = {
     "AX_WHISPER_VocabLogProbPlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "AX_WHISPER_SetAlignmentHeads": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "AX_WHISPER_ConfigAlignmentHeads": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_SetSuppressTokens": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "AX_WHISPER_GetSuppressTokens": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_NonSpeechTokens": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_ConfigSuppressTokens": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "AX_WHISPER_AlignQKSoftmax": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.POINTER(C.c_int), fp, C.c_int,
                                             C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, fp, C.c_int, C.c_int]),
     "AX_WHISPER_AlignNormalize": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.c_int, C.c_float, fp, C.c_int,
@@ -490,6 +494,29 @@ def config_alignment_heads(config_path: str):
     return [(int(pairs[2 * i]), int(pairs[2 * i + 1])) for i in range(n.value)]
 
 
+def non_speech_tokens(tokens_path: str):
+    """Host only (AX_WHISPER_NonSpeechTokens): the sorted ids that openai-whisper's suppress_tokens = -1 stands for, derived from a
+    {type}-tokens.txt (DESIGN.md "Token suppression")."""
+    L = load_library()
+    n_max = 4096
+    ids, n = np.zeros(n_max, dtype=np.int32), C.c_int()
+    if L.AX_WHISPER_NonSpeechTokens(os.fspath(tokens_path).encode(), n_max, _ci(ids), C.byref(n)) != 0:
+        raise RuntimeError("AX_WHISPER_NonSpeechTokens failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return [int(x) for x in ids[: n.value]]
+
+
+def config_suppress_tokens(config_path: str, tokens_path: str = None):
+    """Host only (AX_WHISPER_ConfigSuppressTokens): the sorted suppress set a handle constructed from this {type}_config.json starts
+    with: its "suppress_tokens" key, an entry -1 standing for non_speech_tokens(tokens_path); absent or []: none."""
+    L = load_library()
+    n_max = 1 << 17
+    ids, n = np.zeros(n_max, dtype=np.int32), C.c_int()
+    tp = os.fspath(tokens_path).encode() if tokens_path is not None else None
+    if L.AX_WHISPER_ConfigSuppressTokens(os.fspath(config_path).encode(), tp, n_max, _ci(ids), C.byref(n)) != 0:
+        raise RuntimeError("AX_WHISPER_ConfigSuppressTokens failed: " + (L.AX_WHISPER_LastError(None) or b"").decode())
+    return [int(x) for x in ids[: n.value]]
+
+
 def vocab_logprob_plan(d_model: int, n_rows: int, eot: int):
     """Host only (AX_WHISPER_VocabLogProbPlan): the fused log-prob kernel's tiling -> (rows per row tile, vocabulary splits,
     columns per split)."""
@@ -623,6 +650,7 @@ class Whisper:
         self.timestamp_begin = g("timestamp_begin")
         self.no_speech = g("no_speech")
         self.n_devices = self.L.AX_WHISPER_GetDeviceCount(self.h)
+        self._tokens_path = os.path.join(model_path, model_type, f"{model_type}-tokens.txt")
 
     def get_config_int(self, key: str) -> int:
         """AX_WHISPER_GetConfigInt: a config file key, or one of the engine's own (include/ax_whisper_api.h)."""
@@ -1111,6 +1139,25 @@ class Whisper:
                     pool_score=pool_score, complete=complete, tok=tok, src=src, slot_score=ss, n_completed=done.value)
 
     beam_finalize = staticmethod(beam_finalize)
+
+    # ---- token suppression (DESIGN.md "Token suppression")
+    def set_suppress_tokens(self, ids=None):
+        """AX_WHISPER_SetSuppressTokens: the ids that every timestamp-mode decode of this handle treats as -inf; "non_speech": the
+        list that openai-whisper's -1 stands for, from the model's tokens file; None or empty restores what the config file gave."""
+        if isinstance(ids, str):
+            if ids != "non_speech":
+                raise ValueError('set_suppress_tokens: ids is a list of ids, None or "non_speech"')
+            ids = non_speech_tokens(self._tokens_path)
+        a = _i32(list(ids) if ids is not None else []).reshape(-1)
+        self._check(self.L.AX_WHISPER_SetSuppressTokens(self.h, _ci(a) if len(a) else None, len(a)), "SetSuppressTokens")
+
+    @property
+    def suppress_tokens(self):
+        """AX_WHISPER_GetSuppressTokens: the set in use, sorted."""
+        n_max = max(self.get_config_int("n_suppress_tokens"), 1)
+        ids, n = np.zeros(n_max, dtype=np.int32), C.c_int()
+        self._check(self.L.AX_WHISPER_GetSuppressTokens(self.h, n_max, _ci(ids), C.byref(n)), "GetSuppressTokens")
+        return [int(x) for x in ids[: n.value]]
 
     # ---- word-level timestamps (DESIGN.md "Word-level timestamps")
     def set_alignment_heads(self, pairs=None):

@@ -28,6 +28,7 @@
 #include "multi_device.hpp"
 #include "resample.hpp"
 #include "words.hpp"
+#include "suppress.hpp"
 #include "vocab_logprob_plan.hpp"
 #include "long_call.hpp"
 
@@ -1365,6 +1366,59 @@ AX_WHISPER_API int AX_WHISPER_SetAlignmentHeads(AX_WHISPER_HANDLE handle, const 
       std::lock_guard<std::mutex> lock(e.mutex());
       e.set_alignment_heads(pairs, n);
     }
+  });
+}
+
+// ---- token suppression (DESIGN.md "Token suppression"; suppress.hpp)
+static int copy_ids_out(const std::vector<int>& v, int n_max, int* ids, int* n, const char* what) {
+  if ((int)v.size() > n_max) throw std::runtime_error(std::string(what) + ": more ids than n_max");
+  for (size_t i = 0; i < v.size(); ++i) ids[i] = v[i];
+  *n = (int)v.size();
+  return 0;
+}
+
+AX_WHISPER_API int AX_WHISPER_SetSuppressTokens(AX_WHISPER_HANDLE handle, const int* ids, int n) {
+  if (!handle || n < 0 || (n > 0 && !ids)) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    // every engine gets the set or none does: all of them held, the list checked once and every refusal asked for before the first install
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (int i = 0; i < g.size(); ++i) locks.emplace_back(g.at(i).mutex());
+    const axw::ModelConfig& c = g.primary().config();
+    if (n > 0) (void)axw::checked_suppress_tokens(ids, n, c.n_vocab, c.eot, c.no_timestamps + 1, "set_suppress_tokens");
+    for (int i = 0; i < g.size(); ++i) {
+      const auto it = g.at(i).config().ints.find("stream_slots");
+      if (it != g.at(i).config().ints.end() && it->second > 0)
+        throw std::runtime_error("set_suppress_tokens: not while a stream is open (engine " + std::to_string(i) + "); the stream's captured step has made its choice");
+    }
+    for (int i = 0; i < g.size(); ++i) g.at(i).set_suppress_tokens(ids, n);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_GetSuppressTokens(AX_WHISPER_HANDLE handle, int n_max, int* ids, int* n) {
+  if (!handle || !n || n_max < 0 || (n_max > 0 && !ids)) return -1;
+  *n = 0;
+  return guarded(handle, [&](Engine& e) { copy_ids_out(e.suppress_tokens(), n_max, ids, n, "get_suppress_tokens"); });
+}
+
+// Host only: the list that suppress_tokens = -1 stands for, derived from a tokens file
+AX_WHISPER_API int AX_WHISPER_NonSpeechTokens(const char* tokens_path, int n_max, int* ids, int* n) {
+  if (!tokens_path || !n || n_max < 0 || (n_max > 0 && !ids)) return -1;
+  *n = 0;
+  return guarded_host([&] { return copy_ids_out(axw::non_speech_tokens(axw::load_token_table(tokens_path)), n_max, ids, n, "non_speech_tokens"); });
+}
+
+// Host only: the suppress set a handle constructed from this config file starts with (tokens_path: read only for a -1 entry)
+AX_WHISPER_API int AX_WHISPER_ConfigSuppressTokens(const char* config_path, const char* tokens_path, int n_max, int* ids, int* n) {
+  if (!config_path || !n || n_max < 0 || (n_max > 0 && !ids)) return -1;
+  *n = 0;
+  return guarded_host([&] {
+    const axw::JsonValue j = axw::JsonParser(axw::read_text_file(config_path)).parse();
+    const int no_ts = (int)j.at("no_timestamps").as_int();
+    const std::vector<int> v = axw::config_suppress_tokens(j, (int)j.at("n_vocab").as_int(), (int)j.at("eot").as_int(), no_ts + 1, [&] {
+      if (!tokens_path) throw std::runtime_error("config_suppress_tokens: the list holds -1 and no tokens file was given");
+      return axw::load_token_table(tokens_path);
+    });
+    return copy_ids_out(v, n_max, ids, n, "config_suppress_tokens");
   });
 }
 

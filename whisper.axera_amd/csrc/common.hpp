@@ -538,7 +538,7 @@ void launch_advance(const AdvanceParams& p, hipStream_t s);
 
 // ---- timestamp rules (decode_timestamps.hip): one argmax partial per clip that samples at this step, chosen under
 // Whisper's timestamp rules from the clip's dumped logits row and its history
-struct TsRulesParams {
+struct TsRulesArgs {
   const float* logits; long stride;  // fp32 rows [batch][stride], stride a multiple of 4
   int batch, n_vocab, eot, ts_begin;  // ts_begin = no_timestamps + 1: id of 0.00 s
   const int* off;                    // device [batch] or nullptr (every clip samples); clips with off < n_prefix - 1 are skipped
@@ -548,6 +548,11 @@ struct TsRulesParams {
   const int* forced; int n_forced;   // teacher-forced history [batch][n_forced] (n = off - n_prefix + 1 - base), or nullptr
   const int* base;                   // optional device [batch], forced mode: a prompted clip's L - 2; nullptr: none
   float* amax_val; int* amax_idx; int amax_stride;   // out: partial 0 of clip b at b * amax_stride
+};
+// What callers fill in. suppress stands behind TsRulesArgs, not inside it: the argument block of the rules kernels, and with it the
+// code of every launch without a set, is what it was before there were sets; a launch with one runs the kernels' second instantiation.
+struct TsRulesParams : TsRulesArgs {
+  const unsigned* suppress;          // token suppression (suppress.hpp: the mask of the handle's set), or nullptr: no set
 };
 void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s);
 // Scored form (DESIGN.md "Confidence"): the rules kernel that also writes, for every clip that samples at this step, the
@@ -588,6 +593,7 @@ struct BeamCandParams {
   int n_cand_max;                    // M <= kBeamMaxCand
   int* cand_id; float* cand_logprob; // out [n_slots][M]; entries from n_cand on: eot, -inf
   int* n_cand;                       // out [n_slots]: min(M, |A|)
+  const unsigned* suppress;          // token suppression (suppress.hpp: the mask of the handle's set), or nullptr: no set
 };
 void launch_beam_candidates(const BeamCandParams& p, hipStream_t s);
 // One wave per clip: score = S[parent] + logprob in float32; order by score descending, parent rank, position; walk as

@@ -84,11 +84,12 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(BeamCandParams p) 
   ls.clear();
   for (int c = (a.text_begin >> 2) + tid; 4 * c < a.text_end; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
+    const unsigned sup = p.suppress ? suppress_bits4(p.suppress, c) : 0u;  // (measured: this loop loses nothing to the test inside it)
     float x[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * c + e;
-      x[e] = (text_id_on(a, i, E) && v[e] == v[e]) ? v[e] : -INFINITY;
+      x[e] = (text_id_on(a, i, E) && !suppressed(sup, e) && v[e] == v[e]) ? v[e] : -INFINITY;
       tv = fmaxf(tv, x[e]);
       lt.push(x[e], i);
     }

@@ -54,7 +54,7 @@ struct RulesHistory {
   const int* seq;
   int n;
 };
-__device__ __forceinline__ RulesHistory rules_history(const TsRulesParams& p, int b) {
+__device__ __forceinline__ RulesHistory rules_history(const TsRulesArgs& p, int b) {
   if (p.forced) return {p.forced + (long)b * p.n_forced, min(max(p.off[b] - (p.n_prefix - 1) - (p.base ? p.base[b] : 0), 0), p.n_forced)};
   return {p.out_ids + (long)b * p.n_ctx, min(max(p.n_out[b], 0), p.n_ctx)};
 }
@@ -95,6 +95,25 @@ __device__ __forceinline__ AllowedSets allowed_sets(const int* seq, int n, int T
 }
 __device__ __forceinline__ bool text_id_on(const AllowedSets& a, int i, int E) { return i < E ? a.text_on : (i == E && a.eot_on); }
 __device__ __forceinline__ bool timestamp_on(const AllowedSets& a, int i) { return i >= a.ts_lo && i < a.ts_hi; }
+
+// ---- token suppression (DESIGN.md "Token suppression"): a suppressed id counts as -inf before rules 2 to 5. mask: bit i & 31 of
+// word i >> 5 is set iff id i is suppressed, whole 16-byte groups of words over the vocabulary; the host leaves every bit from eot
+// up clear, so eot needs no case of its own and only the text loops look. nullptr: no set (uniform over the workgroup).
+// The four bits of the 16-byte chunk c of a row (ids 4 c .. 4 c + 3); mask: the words in global memory or an LDS image of them.
+__device__ __forceinline__ unsigned suppress_bits4(const unsigned* mask, int c) { return (mask[c >> 3] >> ((c & 7) * 4)) & 15u; }
+
+__device__ __forceinline__ bool suppressed(unsigned bits4, int e) { return (bits4 >> e) & 1u; }
+// The words of ids [0, E] -> an image in the launch's dynamic LDS (suppress_lds_bytes), which is returned. One barrier: called by
+// all 256 threads. Only the kernels' instantiation with a set holds a call.
+// Measured per step with the 82 non-speech ids (profiles/suppress_tokens_bench.txt): the rules kernels are faster with the image
+// (their loop waits for one dependent word per chunk otherwise), the beam kernel with the words read in its loop, so rules_body
+// stages and beam_candidates_kernel does not.
+__device__ __forceinline__ const unsigned* suppress_stage(const unsigned* mask, int E) {
+  extern __shared__ unsigned s_suppress[];
+  for (int i = threadIdx.x; i <= (E >> 5); i += 256) s_suppress[i] = mask[i];
+  __syncthreads();
+  return s_suppress;
+}
 
 // ---- rule 5 and the final allowed set A. (m, s): the pair of the unmasked timestamps; tv: the best unmasked id of [0, E]
 // rule 5: the timestamps' probability mass beats every single text id

@@ -78,11 +78,14 @@ enum RulesMode { kRulesPlain, kRulesScored, kRulesSampled };
 // kRulesPlain: the argmax partial alone (q and r are not read). kRulesScored: plus the (max, sum) pair of the unmasked ids of
 // [0, E], the no-speech branch and the score stores of q. kRulesSampled: plus, for a clip whose temperature is above 0, two Gumbel
 // (key, id) pairs per thread: the decision is drawn from softmax(x[A] / t) over the final allowed set A, as argmax of x / t + Gumbel
-// noise, the noise of id i at history length n being word i & 3 of Philox(counter (i >> 2, n, stream), key seed). Rules 1 to 5 are
+// noise, the noise of id i at history length n being word i & 3 of Philox(counter (i >> 2, n, stream), key seed), whatever the
+// suppress set (p.suppress; decode_rules.hpp) holds: a suppressed id is masked like one that a rule masks. Rules 1 to 5 are
 // decided on the untempered logits and the recorded log-probability is the untempered one; a clip with t <= 0 takes the scored
 // form's decision and computes no random number.
-template <RulesMode MODE>
-__device__ __forceinline__ void rules_body(const TsRulesParams& p, const TsScoreParams& q, const TsSampleParams& r) {
+// kSet: the instantiation of a launch with a suppress set, mask its words. Without one (kSet false, mask not read) the body compiles to
+// what it was before there were sets: the kernels below exist in both forms and the launch functions choose by TsRulesParams::suppress.
+template <RulesMode MODE, bool kSet>
+__device__ __forceinline__ void rules_body(const TsRulesArgs& p, const unsigned* mask, const TsScoreParams& q, const TsSampleParams& r) {
   constexpr bool kScore = MODE >= kRulesScored, kSample = MODE == kRulesSampled;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
@@ -111,6 +114,8 @@ __device__ __forceinline__ void rules_body(const TsRulesParams& p, const TsScore
 
   // ---- one pass over the row
   const float* row = p.logits + (long)b * p.stride;
+  [[maybe_unused]] const unsigned* suppress = nullptr;
+  if constexpr (kSet) suppress = suppress_stage(mask, E);
   float tv = -INFINITY, sv = -INFINITY;  // the first best unmasked id of [0, E] / unmasked timestamp
   int ti = 0x7fffffff, si = 0x7fffffff;
   float m = -INFINITY, s = 0.f;          // online logsumexp over the unmasked timestamps
@@ -120,11 +125,14 @@ __device__ __forceinline__ void rules_body(const TsRulesParams& p, const TsScore
   // text ids [0, E]: chunks of four floats; NaN never compares greater (it counts as masked)
   for (int c = (a.text_begin >> 2) + tid; 4 * c < a.text_end; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
+    [[maybe_unused]] unsigned sup = 0;
+    if constexpr (kSet) sup = suppress_bits4(suppress, c);
     [[maybe_unused]] float x[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * c + e;
-      const bool on = text_id_on(a, i, E);
+      bool on = text_id_on(a, i, E);
+      if constexpr (kSet) on = on && !suppressed(sup, e);
       if (on && v[e] > tv) { tv = v[e]; ti = i; }
       x[e] = (on && v[e] == v[e]) ? v[e] : -INFINITY;
     }
@@ -202,14 +210,27 @@ __device__ __forceinline__ void rules_body(const TsRulesParams& p, const TsScore
   }
 }
 
-__global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesParams p) { rules_body<kRulesPlain>(p, TsScoreParams{}, TsSampleParams{}); }
+__global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesArgs p) { rules_body<kRulesPlain, false>(p, nullptr, TsScoreParams{}, TsSampleParams{}); }
 
-__global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesParams p, TsScoreParams q) {
-  rules_body<kRulesScored>(p, q, TsSampleParams{});
+__global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesArgs p, TsScoreParams q) {
+  rules_body<kRulesScored, false>(p, nullptr, q, TsSampleParams{});
 }
 
-__global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesParams p, TsScoreParams q, TsSampleParams r) {
-  rules_body<kRulesSampled>(p, q, r);
+__global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesArgs p, TsScoreParams q, TsSampleParams r) {
+  rules_body<kRulesSampled, false>(p, nullptr, q, r);
+}
+
+// the same three under a suppress set (dynamic LDS: suppress_lds_bytes)
+__global__ __launch_bounds__(256) void timestamp_rules_suppress_kernel(TsRulesArgs p, const unsigned* mask) {
+  rules_body<kRulesPlain, true>(p, mask, TsScoreParams{}, TsSampleParams{});
+}
+
+__global__ __launch_bounds__(256) void timestamp_rules_scored_suppress_kernel(TsRulesArgs p, const unsigned* mask, TsScoreParams q) {
+  rules_body<kRulesScored, true>(p, mask, q, TsSampleParams{});
+}
+
+__global__ __launch_bounds__(256) void timestamp_rules_sampled_suppress_kernel(TsRulesArgs p, const unsigned* mask, TsScoreParams q, TsSampleParams r) {
+  rules_body<kRulesSampled, true>(p, mask, q, r);
 }
 
 // ---- slot stream in timestamp mode (DESIGN.md "Slot stream in timestamp mode"): the scored form for slots that are refilled while
@@ -224,55 +245,31 @@ __global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesPar
 //     slot_ctx[4 b + 1], which this step's advance launch feeds next on the same stream: no extra pass, no host round trip;
 //   offset 1 (the language id was fed): nothing;
 //   offset >= n_prefix - 1: rules_body<kRulesScored>, whose own offset and done tests then pass.
-__global__ __launch_bounds__(256) void stream_rules_kernel(TsRulesParams p, TsScoreParams q, StreamRulesParams t) {
-  const int b = blockIdx.x;
-  if (p.done[b]) return;
-  const int off = p.off[b];
-  if (off >= p.n_prefix - 1) { rules_body<kRulesScored>(p, q, TsSampleParams{}); return; }
-  if (off != 0) return;
-  const float* row = p.logits + (long)b * p.stride;
-  row_logprob(row, p.n_vocab, q.no_speech_id, q.no_speech + b);
-  if (!t.detect[b]) return;
-  __shared__ float s_logit[kLangMax];
-  const int tid = threadIdx.x, lane = tid & 63, n_lang = t.n_lang;
-  if (tid < n_lang) s_logit[tid] = row[t.lang_tokens[tid]];
-  __syncthreads();
-  if (tid >= 64) return;
-  const int j0 = lane, j1 = lane + 64;
-  const float x0 = j0 < n_lang ? s_logit[j0] : NAN, x1 = j1 < n_lang ? s_logit[j1] : NAN;
-  float m = -INFINITY;
-  int idx = 0x7fffffff;
-  argmax_take(m, idx, x0, j0);  // (a NaN compares false: never taken)
-  argmax_take(m, idx, x1, j1);
-  wave_argmax(m, idx);
-  const float n_finite = wave_sum((fabsf(x0) < INFINITY ? 1.f : 0.f) + (fabsf(x1) < INFINITY ? 1.f : 0.f));
-  const bool none = !(n_finite > 0.f) || idx >= n_lang;
-  float lp0, lp1;
-  if (none) {
-    idx = t.fallback_index;
-    lp0 = lp1 = -INFINITY;
-  } else if (m == INFINITY) {  // the maxima share the whole mass
-    lp0 = x0 == INFINITY ? 0.f : -INFINITY;
-    lp1 = x1 == INFINITY ? 0.f : -INFINITY;
-  } else {
-    float s = (x0 == x0 ? expf(x0 - m) : 0.f) + (x1 == x1 ? expf(x1 - m) : 0.f);
-    s = wave_sum(s);
-    const float lse = m + logf(s);
-    lp0 = x0 == x0 ? x0 - lse : -INFINITY;
-    lp1 = x1 == x1 ? x1 - lse : -INFINITY;
-  }
-  if (j0 < n_lang) t.lang_logprob[(long)b * n_lang + j0] = lp0;
-  if (j1 < n_lang) t.lang_logprob[(long)b * n_lang + j1] = lp1;
-  if (lane == 0) {
-    t.lang_out[b] = idx;
-    t.slot_ctx[4 * b + 1] = t.lang_tokens[idx];
-  }
+__global__ __launch_bounds__(256) void stream_rules_kernel(TsRulesArgs p, TsScoreParams q, StreamRulesParams t) {
+#define AXW_STREAM_SET false
+#define AXW_STREAM_MASK nullptr
+#include "stream_rules_body.inc"
+#undef AXW_STREAM_SET
+#undef AXW_STREAM_MASK
+}
+
+__global__ __launch_bounds__(256) void stream_rules_suppress_kernel(TsRulesArgs p, const unsigned* mask, TsScoreParams q, StreamRulesParams t) {
+#define AXW_STREAM_SET true
+#define AXW_STREAM_MASK mask
+#include "stream_rules_body.inc"
+#undef AXW_STREAM_SET
+#undef AXW_STREAM_MASK
 }
 
 // log p(row[id]) over the whole row, one workgroup per row (the no-speech value on rows of the caller's)
 __global__ __launch_bounds__(256) void row_logprob_kernel(const float* logits, long stride, int n_vocab, int id, float* out) {
   row_logprob(logits + (long)blockIdx.x * stride, n_vocab, id, out + blockIdx.x);
 }
+
+// dynamic LDS of a rules launch under a set: the image of the suppress mask's words of [0, eot] (decode_rules.hpp: suppress_stage)
+static size_t suppress_lds_bytes(const TsRulesParams& p) { return ((size_t)(p.eot >> 5) + 1) * sizeof(unsigned); }
+// (the kernels take the arguments without the set: a launch without one is the launch it was before there were sets)
+static const TsRulesArgs& args_of(const TsRulesParams& p) { return p; }
 
 static void check_rules_params(const TsRulesParams& p) {
   if (p.stride % 4 != 0 || p.stride < p.n_vocab || p.ts_begin <= p.eot || p.ts_begin > p.n_vocab) {
@@ -284,7 +281,8 @@ static void check_rules_params(const TsRulesParams& p) {
 
 void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s) {
   check_rules_params(p);
-  hipLaunchKernelGGL(timestamp_rules_kernel, dim3(p.batch), dim3(256), 0, s, p);
+  if (p.suppress) hipLaunchKernelGGL(timestamp_rules_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress);
+  else hipLaunchKernelGGL(timestamp_rules_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p));
 }
 
 static bool score_params_ok(const TsRulesParams& p, const TsScoreParams& q) {
@@ -297,7 +295,8 @@ void launch_timestamp_rules_scored(const TsRulesParams& p, const TsScoreParams& 
     fprintf(stderr, "[ax_whisper] launch_timestamp_rules_scored: bad score arrays / no-speech id %d\n", q.no_speech_id);
     abort();
   }
-  hipLaunchKernelGGL(timestamp_rules_scored_kernel, dim3(p.batch), dim3(256), 0, s, p, q);
+  if (p.suppress) hipLaunchKernelGGL(timestamp_rules_scored_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q);
+  else hipLaunchKernelGGL(timestamp_rules_scored_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p), q);
 }
 
 void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams& q, const TsSampleParams& r, hipStream_t s) {
@@ -306,7 +305,8 @@ void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams&
     fprintf(stderr, "[ax_whisper] launch_timestamp_rules_sampled: bad score or sample arrays / no-speech id %d\n", q.no_speech_id);
     abort();
   }
-  hipLaunchKernelGGL(timestamp_rules_sampled_kernel, dim3(p.batch), dim3(256), 0, s, p, q, r);
+  if (p.suppress) hipLaunchKernelGGL(timestamp_rules_sampled_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q, r);
+  else hipLaunchKernelGGL(timestamp_rules_sampled_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p), q, r);
 }
 
 void launch_stream_rules(const TsRulesParams& p, const TsScoreParams& q, const StreamRulesParams& t, hipStream_t s) {
@@ -316,7 +316,8 @@ void launch_stream_rules(const TsRulesParams& p, const TsScoreParams& q, const S
     fprintf(stderr, "[ax_whisper] launch_stream_rules: bad score or slot arrays / n_lang %d\n", t.n_lang);
     abort();
   }
-  hipLaunchKernelGGL(stream_rules_kernel, dim3(p.batch), dim3(256), 0, s, p, q, t);
+  if (p.suppress) hipLaunchKernelGGL(stream_rules_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q, t);
+  else hipLaunchKernelGGL(stream_rules_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p), q, t);
 }
 
 void launch_row_logprob(const float* logits, long stride, int n_vocab, int id, int batch, float* out, hipStream_t s) {

@@ -148,6 +148,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     cfg_.ints["word_logprob"] = e && !strcmp(e, "rows") ? 1 : e && !strcmp(e, "fused") ? 2 : 0;
   }
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half
+  install_suppress(config_suppress_);
   ensure_capacity(std::max(1, max_batch));
   HIP_CHECK(hipStreamSynchronize(own_stream_));
 }
@@ -223,6 +224,10 @@ void Engine::load_config(const std::string& dir, const std::string& type, const 
   // word-level timestamps: the checkpoint's alignment heads, where the file names them (words.hpp)
   config_heads_ = align_heads_ = config_alignment_heads(j, cfg_.n_text_layer, cfg_.n_text_head);
   cfg_.ints["n_alignment_heads"] = (long)alignment_heads().size();
+  // token suppression: the set the file names (suppress.hpp; -1: the non-speech list of the tokens file), installed by construct()
+  config_suppress_ = config_suppress_tokens(j, cfg_.n_vocab, cfg_.eot, cfg_.no_timestamps + 1,
+                                            [&] { return load_token_table(dir + "/" + type + "-tokens.txt"); });
+  cfg_.ints["n_suppress_tokens"] = 0;
 }
 
 // Slaney mel filterbank, arithmetic as librosa.h:102-144 (fp32), stored transposed [201][n_mels].
@@ -1204,6 +1209,7 @@ void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int
   r.off = nullptr; r.n_prefix = 3; r.done = nullptr;
   r.out_ids = in.hist; r.n_out = in.n_hist; r.n_ctx = Tc;
   r.amax_val = b_val; r.amax_idx = b_idx; r.amax_stride = 1;
+  r.suppress = suppress_mask();
   if (sample) launch_timestamp_rules_sampled(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, own_sample_, s);
   else if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, s);
   else launch_timestamp_rules(r, s);

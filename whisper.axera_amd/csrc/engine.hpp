@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "iengine.hpp"
+#include "suppress.hpp"
 #include "t2s.hpp"
 
 namespace axw {
@@ -184,6 +185,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   int beam_select(const BeamSelectIO& io) override;
   void align_tokens(const AlignRequest& rq) override;
   void set_alignment_heads(const int* pairs, int n) override;
+  void set_suppress_tokens(const int* ids, int n) override;
+  const std::vector<int>& suppress_tokens() const override { return suppress_ids_; }
   void align_kernel(int which, const AlignKernelIO& io) override;
   void vocab_logprob_rows(const float* x, int n_rows, const int32_t* ids, float* out, int route) override;
   void stream_open(int n_slots, int mode = 0) override;
@@ -281,11 +284,20 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // the captured step of spec.mode / spec.mask; a scored graph writes the engine's own score arrays (spec.score_out is not read)
   hipGraphExec_t step_graph(StepSpec spec, int batch, int max_new);
   void drop_step_graph(const StepSpec& spec, int batch, int max_new) { graphs_.erase(graph_key(spec, batch, max_new)); }
-  // (two bits for the mode: plain, timestamp, scored and sampled steps are four different graphs; one for the slot stream's scored step)
-  static long graph_key(const StepSpec& spec, int batch, int max_new) {
-    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 3) | (spec.slots ? 4 : 0) | spec.mode;
+  // (two bits for the mode: plain, timestamp, scored and sampled steps are four different graphs; one for the slot stream's scored
+  // step; one for "a suppress set is installed" where the graph holds a rules launch, which has the mask's pointer by value)
+  long graph_key(const StepSpec& spec, int batch, int max_new) const {
+    const bool suppress = spec.mode != kDecodePlain && (spec.mask & 4) && suppress_mask();
+    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 4) | (suppress ? 8 : 0) | (spec.slots ? 4 : 0) | spec.mode;
   }
   void require_timestamp_vocab() const;
+  // token suppression (DESIGN.md "Token suppression"; suppress.hpp): the handle's set as a sorted id list, what the config file
+  // gave (what n == 0 restores), and its mask on the device: allocated on first use under device_capture_mutex, at one address
+  // for the life of the handle, rewritten on the engine's stream
+  std::vector<int> suppress_ids_, config_suppress_;
+  unsigned* d_suppress_ = nullptr;  // (in allocs_)
+  const unsigned* suppress_mask() const { return suppress_ids_.empty() ? nullptr : d_suppress_; }  // what the parameter structs get
+  void install_suppress(const std::vector<int>& ids);
   void ensure_ts_logits();  // d_ts_logits_ (SlotViews)
   void enqueue_timestamp_rules(const StepSpec& spec, int batch, const int* d_forced, int n_forced, hipStream_t s);
   long ts_stride_ = 0;

@@ -64,6 +64,7 @@ void Engine::enqueue_beam_tail(int clips, int K, int off, int max_new, hipStream
     c.hist = beam_.hist; c.hist_stride = Tc; c.n_hist = nullptr; c.n = n;
     c.slot_score = beam_.slot_score; c.complete = beam_.complete; c.beam = K; c.n_cand_max = K + 1;
     c.cand_id = beam_.cand_id; c.cand_logprob = beam_.cand_lp; c.n_cand = beam_.n_cand;
+    c.suppress = suppress_mask();
     launch_beam_candidates(c, s);
     BeamSelectParams q{};
     q.n_clips = clips; q.beam = K; q.eot = cfg_.eot; q.n = n;
@@ -246,6 +247,7 @@ void Engine::beam_candidates(const float* logits, const int32_t* hist, const int
   c.logits = in.logits; c.stride = in.stride; c.n_slots = rows; c.n_vocab = cfg_.n_vocab; c.eot = cfg_.eot; c.ts_begin = cfg_.no_timestamps + 1;
   c.hist = in.hist; c.hist_stride = cfg_.n_text_ctx; c.n_hist = in.n_hist; c.beam = 1; c.n_cand_max = M;
   c.cand_id = b_id; c.cand_logprob = b_lp; c.n_cand = b_nc;
+  c.suppress = suppress_mask();
   launch_beam_candidates(c, s);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(cand_id, b_id, (size_t)rows * M * 4, hipMemcpyDeviceToHost, s));

@@ -693,10 +693,35 @@ void Engine::enqueue_timestamp_rules(const StepSpec& spec, int batch, const int*
   r.out_ids = d_out_ids_; r.n_out = d_nout_; r.n_ctx = cfg_.n_text_ctx;
   r.forced = d_forced; r.n_forced = n_forced; r.base = spec.base;
   r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
+  r.suppress = suppress_mask();
   if (spec.slots) launch_stream_rules(r, spec.score_out, stream_rules_params(), s);  // idle slots, the no-speech value and detection at offset 0
   else if (spec.mode == kDecodeSampled) launch_timestamp_rules_sampled(r, spec.score_out, spec.sample, s);  // + a draw at the clip's temperature
   else if (spec.mode == kDecodeScored) launch_timestamp_rules_scored(r, spec.score_out, s);  // + the decision's log-probability, the no-speech value at offset 0
   else launch_timestamp_rules(r, s);
+}
+
+// ------------------------------------------------------------------------------ token suppression
+// The set becomes `ids` (checked and sorted: suppress.hpp). The mask keeps its address, so nothing that was captured with the
+// pointer goes stale; a step captured without one is kept under the other key (graph_key).
+void Engine::install_suppress(const std::vector<int>& ids) {
+  if (!ids.empty()) {
+    std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+    HIP_CHECK(hipSetDevice(device_));
+    const std::vector<uint32_t> mask = axw::suppress_mask(ids, cfg_.n_vocab, cfg_.eot);
+    if (!d_suppress_) d_suppress_ = pooled<unsigned>(allocs_, mask.size(), true);
+    hipStream_t s = stream();
+    HIP_CHECK(hipMemcpyAsync(d_suppress_, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (a pageable source on this stack)
+  }
+  suppress_ids_ = ids;
+  cfg_.ints["n_suppress_tokens"] = (long)suppress_ids_.size();
+}
+
+void Engine::set_suppress_tokens(const int* ids, int n) {
+  require_no_stream("set_suppress_tokens");  // an open stream's captured step has made its choice
+  if (n < 0 || (n > 0 && !ids)) throw std::runtime_error("set_suppress_tokens: bad arguments");
+  install_suppress(n == 0 ? config_suppress_
+                          : checked_suppress_tokens(ids, n, cfg_.n_vocab, cfg_.eot, cfg_.no_timestamps + 1, "set_suppress_tokens"));
 }
 
 void Engine::require_scored_vocab() const {

@@ -296,6 +296,7 @@ void Engine::stream_rules_stage(const StreamRulesIO& io) {
   r.off = b_off; r.n_prefix = 3; r.done = b_done;
   r.out_ids = in.hist; r.n_out = in.n_hist; r.n_ctx = Tc;
   r.amax_val = b_val; r.amax_idx = b_idx; r.amax_stride = 1;
+  r.suppress = suppress_mask();
   StreamRulesParams t{};
   t.detect = b_det; t.slot_ctx = b_ctx; t.lang_tokens = prefill_.lang_tok; t.n_lang = n_lang; t.fallback_index = handle_lang_;
   t.lang_out = b_lang; t.lang_logprob = b_llp;

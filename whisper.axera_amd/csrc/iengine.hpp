@@ -186,6 +186,10 @@ class IEngine {
   virtual void vocab_logprob_rows(const float* x, int n_rows, const int32_t* ids, float* out, int route) = 0;
   // the list of (layer, head) pairs the alignment averages over; n == 0: the default, every head of the upper half of the layers
   virtual void set_alignment_heads(const int* pairs, int n) = 0;
+  // token suppression (DESIGN.md "Token suppression"): the handle's suppress set, which every timestamp-mode decode and rules entry
+  // point applies; n == 0: what the config file gave. Refuses an open Stream*.
+  virtual void set_suppress_tokens(const int* ids, int n) = 0;
+  virtual const std::vector<int>& suppress_tokens() const = 0;  // sorted
   // One kernel of decode_align.hip alone on host data (tests). Clip c has len[c] rows and n_keys[c] frames.
   // qk_softmax: q fp32 [rows][64 n_head] (clip c at row0[c]), k fp32 [n_slots][n_head][keys_pad][64] (clip c reads slot[c]), both
   // narrowed to the 16-bit type; P [n_clips][n_align][rows_pad][f_pad] is updated in place (the kernel writes what it writes).

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ax_whisper_api.h"
+#include "suppress_flag.hpp"
 
 static void usage(const char* prog) {
   fprintf(stderr,
@@ -57,6 +58,9 @@ static void usage(const char* prog) {
           "                      duration behind RTF: is the file's real one. Without the flag nothing changes: such a file is fed\n"
           "                      as it is, with a warning, and its duration is counted at 16000 Hz\n"
           "      --task T        transcribe or translate (with --timestamps or --long, not with --beam_size) [=transcribe]\n"
+          "      --suppress_tokens -1|1,2,3   (with --timestamps or --long) ids the decode never samples, as openai-whisper's\n"
+          "                      suppress_tokens: -1 the non-speech ids of the model's tokens file (brackets, quotes, musical signs),\n"
+          "                      or a list; replaces what the config file's \"suppress_tokens\" gave\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -409,7 +413,7 @@ int main(int argc, char** argv) {
   bool timestamps = false, longform = false, word_timestamps = false;
   bool condition = false, detect = false, chunked = false;
   std::string task_arg, cmax_arg, cmin_arg, csmooth_arg;
-  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg;
+  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg, suppress_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -426,7 +430,8 @@ int main(int argc, char** argv) {
         val("language", nullptr, language) || val("no_speech_threshold", nullptr, nst_arg) || val("logprob_threshold", nullptr, lpt_arg) ||
         val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg) ||
         val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg) || val("task", nullptr, task_arg) ||
-        val("chunk_max_s", nullptr, cmax_arg) || val("chunk_min_s", nullptr, cmin_arg) || val("chunk_smooth_ms", nullptr, csmooth_arg))
+        val("chunk_max_s", nullptr, cmax_arg) || val("chunk_min_s", nullptr, cmin_arg) || val("chunk_smooth_ms", nullptr, csmooth_arg) ||
+        val("suppress_tokens", nullptr, suppress_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -490,6 +495,13 @@ int main(int argc, char** argv) {
     prompt_ids.push_back((int32_t)v);
     p = (size_t)(end - prompt_arg.c_str()) + (*end ? 1 : 0);
   }
+  // --suppress_tokens -1 | 1,2,3 (suppress_flag.hpp)
+  std::vector<int> suppress_ids;
+  if (!suppress_arg.empty() && !timestamps && !longform) { fprintf(stderr, "--suppress_tokens needs --timestamps or --long (plain mode is not filtered)\n"); usage(argv[0]); return 1; }
+  if (!suppress_arg.empty()) {
+    std::string err;
+    if (!suppress_flag_ids(suppress_arg, model_path, model_type, suppress_ids, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+  }
   const bool prompted = condition || !prompt_ids.empty();
   if (prompted && !longform) { fprintf(stderr, "--condition_on_previous_text / --prompt_ids need --long\n"); usage(argv[0]); return 1; }
   const bool scored = prompted || fallback || !nst_arg.empty() || !lpt_arg.empty() || (per_lang && longform);
@@ -535,6 +547,14 @@ int main(int argc, char** argv) {
   auto t1 = std::chrono::steady_clock::now();
   if (!handle) { printf("AX_WHISPER_Init failed!\n"); return -1; }
   printf("Init whisper success, take %.4fseconds\n", std::chrono::duration<double>(t1 - t0).count());
+  if (!suppress_ids.empty()) {
+    if (AX_WHISPER_SetSuppressTokens(handle, suppress_ids.data(), (int)suppress_ids.size()) != 0) {
+      printf("--suppress_tokens failed! %s\n", AX_WHISPER_LastError(handle));
+      AX_WHISPER_Uninit(handle);
+      return -1;
+    }
+    printf("suppress_tokens: %d ids\n", (int)suppress_ids.size());
+  }
   if (g_resample) {  // the file's real duration: its frames at its own rate
     float* pcm = nullptr;
     int n = 0, info[3] = {0, 0, 0};

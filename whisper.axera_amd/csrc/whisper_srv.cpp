@@ -54,6 +54,7 @@
 
 #include "ax_whisper_api.h"
 #include "http_request.hpp"
+#include "suppress_flag.hpp"
 
 struct Job {
   std::vector<float> pcm;
@@ -434,7 +435,7 @@ static void serve(int fd) {
 
 int main(int argc, char** argv) {
   int port = 8080, max_batch = 64, wait_ms = 5, steps_per_call = 8, max_body_mb = 16, min_admit = 1, admit_wait_ms = 20;
-  std::string model_type = "turbo", model_path = "../models-mi355x", language = "zh", devices, scheduler = "slots";
+  std::string model_type = "turbo", model_path = "../models-mi355x", language = "zh", devices, scheduler = "slots", suppress_arg;
   bool timestamps = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -449,7 +450,7 @@ int main(int argc, char** argv) {
     if (val("max_batch", nullptr, v)) { max_batch = std::max(1, atoi(v.c_str())); continue; }
     if (val("batch_wait_ms", nullptr, v)) { wait_ms = std::max(0, atoi(v.c_str())); continue; }
     if (val("model_type", "-t", model_type) || val("model_path", "-p", model_path) || val("language", "-l", language)) continue;
-    if (val("devices", nullptr, devices) || val("scheduler", nullptr, scheduler)) continue;
+    if (val("devices", nullptr, devices) || val("scheduler", nullptr, scheduler) || val("suppress_tokens", nullptr, suppress_arg)) continue;
     if (a == "--timestamps") { timestamps = true; continue; }
     if (val("steps_per_call", nullptr, v)) { steps_per_call = std::max(1, atoi(v.c_str())); continue; }
     if (val("min_admit", nullptr, v)) { min_admit = std::max(1, atoi(v.c_str())); continue; }
@@ -458,7 +459,7 @@ int main(int argc, char** argv) {
     if (val("max_body_mb", nullptr, v)) { max_body_mb = std::max(1, atoi(v.c_str())); continue; }
     if (val("recv_timeout_s", nullptr, v)) { g_recv_timeout_s = std::max(1, atoi(v.c_str())); continue; }
     fprintf(stderr, "usage: %s [--port 8080] [-t model_type] [-p model_path] [-l language] [--max_batch 64] [--batch_wait_ms 5] [--devices all|0,1,..]\n"
-                    "          [--scheduler slots|batches] [--timestamps] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
+                    "          [--scheduler slots|batches] [--timestamps] [--suppress_tokens -1|1,2,3] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
     return a == "--help" || a == "-?" ? 0 : 1;
   }
   printf("port: %d\n", port);
@@ -466,6 +467,13 @@ int main(int argc, char** argv) {
   printf("model_type: %s\n", model_type.c_str());
   printf("language: %s\n", language.c_str());
   if (timestamps && scheduler == "batches") { printf("--timestamps needs --scheduler slots (micro-batches decode in plain mode)\n"); return 1; }
+  // --suppress_tokens -1 | 1,2,3 (with --timestamps: plain mode is not filtered; suppress_flag.hpp)
+  std::vector<int> suppress_ids;
+  if (!suppress_arg.empty()) {
+    if (!timestamps) { printf("--suppress_tokens needs --timestamps (plain mode is not filtered)\n"); return 1; }
+    std::string err;
+    if (!suppress_flag_ids(suppress_arg, model_path, model_type, suppress_ids, err)) { printf("%s\n", err.c_str()); return 1; }
+  }
 
   // one handle (one engine, one batcher thread) per device
   std::vector<int> devs;
@@ -492,12 +500,19 @@ int main(int argc, char** argv) {
       return -1;
     }
     models.push_back(m);
+    // (set here, before the scheduler opens the handle's stream: the stream's captured step takes the set it finds)
+    if (!suppress_ids.empty() && AX_WHISPER_SetSuppressTokens(m, suppress_ids.data(), (int)suppress_ids.size()) != 0) {
+      printf("--suppress_tokens failed! %s\n", AX_WHISPER_LastError(m));
+      for (AX_WHISPER_HANDLE o : models) AX_WHISPER_Uninit(o);
+      return -1;
+    }
   }
   if (models.empty()) { printf("init server failed!\n"); return -1; }
   printf("devices: %d\n", (int)models.size());
   if (scheduler != "slots" && scheduler != "batches") { printf("--scheduler must be slots or batches\n"); return 1; }
   printf("scheduler: %s\n", scheduler.c_str());
   if (timestamps) printf("timestamps: on\n");
+  if (!suppress_ids.empty()) printf("suppress_tokens: %d ids\n", (int)suppress_ids.size());
   g_timestamps = timestamps;
   g_models = models;
   g_max_body = (size_t)max_body_mb << 20;

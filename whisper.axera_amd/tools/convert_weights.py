@@ -104,8 +104,26 @@ def hf_alignment_heads(path: str):
     return [[int(p[0]), int(p[1])] for p in heads]
 
 
+def hf_suppress_tokens(path: str):
+    """The ids a transformers checkpoint never samples: "suppress_tokens": [ids ...] of the generation_config.json beside its weights
+    (the non-speech ids plus special ids between eot and the timestamps, which the engine accepts and rule 1 masks anyway); None
+    where there is no such file or key."""
+    import json
+
+    d = os.path.dirname(path) if path.endswith(".safetensors") else path
+    f = os.path.join(d, "generation_config.json")
+    if not os.path.exists(f):
+        return None
+    ids = json.load(open(f)).get("suppress_tokens")
+    if ids is None:
+        return None
+    if not isinstance(ids, list) or not all(isinstance(x, int) and not isinstance(x, bool) for x in ids):
+        raise ValueError(f"{f}: suppress_tokens is not a list of ids")
+    return [int(x) for x in ids]
+
+
 def write_model(weights: dict, model_type: str, model_path: str, dtype: str = "BF16", tiktoken_path: str | None = None,
-                alignment_heads=None) -> str:
+                alignment_heads=None, suppress_tokens=None) -> str:
     """tiktoken_path is REQUIRED for a real checkpoint: {type}-tokens.txt must carry the vocabulary the model was
     trained with (the reference's exporter writes it from the tokenizer, export_onnx.py:391-417)."""
     if not tiktoken_path:
@@ -121,7 +139,8 @@ def write_model(weights: dict, model_type: str, model_path: str, dtype: str = "B
         if n in weights:
             assert tuple(weights[n].shape) == tuple(s), (n, weights[n].shape, s)
     return modelgen.write_model_dir(model_path, model_type, dims, weights={k: v for k, v in weights.items() if k in expect},
-                                    dtype=dtype, tiktoken_path=tiktoken_path, alignment_heads=alignment_heads)
+                                    dtype=dtype, tiktoken_path=tiktoken_path, alignment_heads=alignment_heads,
+                                    suppress_tokens=suppress_tokens)
 
 
 def main():
@@ -133,6 +152,8 @@ def main():
     ap.add_argument("--model_path", "-p", required=True)
     ap.add_argument("--dtype", default="BF16", choices=["BF16", "F16", "F32"])
     ap.add_argument("--tiktoken", required=True, help="multilingual.tiktoken vocabulary for {type}-tokens.txt")
+    ap.add_argument("--suppress_tokens", default=None,
+                    help='"suppress_tokens" of the config: -1 (the non-speech ids) or ids 1,2,3; overrides what --hf would copy')
     a = ap.parse_args()
     if a.openai:
         import torch
@@ -141,10 +162,14 @@ def main():
         sd = ck.get("model_state_dict", ck)
         w = {k: v.float().numpy() for k, v in sd.items()}
         heads = None  # (an openai checkpoint keeps its heads in the package, not in the file)
+        suppress = None  # (and decodes with suppress_tokens = -1 unless told otherwise: --suppress_tokens -1)
     else:
         w = hf_to_openai_names(read_hf_checkpoint(a.hf))
         heads = hf_alignment_heads(a.hf)  # word-level timestamps: the checkpoint's own heads go into the config
-    print(write_model(w, a.model_type, a.model_path, a.dtype, a.tiktoken, alignment_heads=heads))
+        suppress = hf_suppress_tokens(a.hf)  # token suppression: the checkpoint's own list too
+    if a.suppress_tokens is not None:
+        suppress = modelgen.parse_suppress_tokens(a.suppress_tokens)
+    print(write_model(w, a.model_type, a.model_path, a.dtype, a.tiktoken, alignment_heads=heads, suppress_tokens=suppress))
 
 
 if __name__ == "__main__":

@@ -397,15 +397,19 @@ def write_tokens(path: str, tiktoken_path: str | None) -> None:
 
 def write_model_dir(root: str, model_type: str, dims: dict | None = None, seed: int = 0,
                     tiktoken_path: str | None = None, dtype: str = "BF16",
-                    weights: Dict[str, np.ndarray] | None = None, alignment_heads=None) -> str:
+                    weights: Dict[str, np.ndarray] | None = None, alignment_heads=None, suppress_tokens=None) -> str:
     """Create ``{root}/{model_type}/`` with config, tokens and weights; returns the directory. alignment_heads: the checkpoint's
-    [[layer, head], ...] for word-level timestamps (the config's optional key of that name); None: the key is left out."""
+    [[layer, head], ...] for word-level timestamps (the config's optional key of that name); None: the key is left out.
+    suppress_tokens: the ids timestamp mode never samples (the config's optional key of that name; -1: the non-speech list of the
+    tokens file, derived when the model is loaded); None: the key is left out."""
     dims = dims or DIMS[model_type]
     d = os.path.join(root, model_type)
     os.makedirs(d, exist_ok=True)
     cfg = make_config(model_type, dims)
     if alignment_heads is not None:
         cfg["alignment_heads"] = [[int(l), int(h)] for l, h in alignment_heads]
+    if suppress_tokens is not None:
+        cfg["suppress_tokens"] = [int(i) for i in suppress_tokens]
     with open(os.path.join(d, f"{model_type}_config.json"), "w") as f:
         json.dump(cfg, f, indent=4)
     write_tokens(os.path.join(d, f"{model_type}-tokens.txt"), tiktoken_path)
@@ -437,6 +441,13 @@ def synth_long_clip(seconds: int = 75, loud_at: int = 70) -> np.ndarray:
     return (x * g).astype(np.float32)
 
 
+def parse_suppress_tokens(text: str | None):
+    """``--suppress_tokens -1|1,2,3`` -> the list for the config's "suppress_tokens" key (None: no flag, no key)"""
+    if text is None:
+        return None
+    return [int(t) for t in text.split(",") if t.strip()]
+
+
 if __name__ == "__main__":
     import argparse
 
@@ -445,5 +456,7 @@ if __name__ == "__main__":
     ap.add_argument("--model_path", "-p", required=True)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tiktoken", default=None)
+    ap.add_argument("--suppress_tokens", default=None, help='"suppress_tokens" of the config: -1 (non-speech ids; needs --tiktoken) or ids 1,2,3')
     a = ap.parse_args()
-    print(write_model_dir(a.model_path, a.model_type, seed=a.seed, tiktoken_path=a.tiktoken))
+    print(write_model_dir(a.model_path, a.model_type, seed=a.seed, tiktoken_path=a.tiktoken,
+                          suppress_tokens=parse_suppress_tokens(a.suppress_tokens)))
