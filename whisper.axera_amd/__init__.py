@@ -656,6 +656,12 @@ class Whisper:
         """AX_WHISPER_GetConfigInt: a config file key, or one of the engine's own (include/ax_whisper_api.h)."""
         return self.L.AX_WHISPER_GetConfigInt(self.h, key.encode())
 
+    @property
+    def persistent_ts_launches(self) -> int:
+        """One-clip timestamp and scored decodes of this handle that ran as ONE persistent launch under the timestamp rules and
+        finished without a give-up (the route is on with AX_WHISPER_PERSIST_TS=1), summed over the handle's engines."""
+        return self.get_config_int("persistent_ts_launches")
+
     def close(self):
         if getattr(self, "h", None):
             self.L.AX_WHISPER_Uninit(self.h)

@@ -521,7 +521,7 @@ AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char*
   if (!h || !key || h->group.size() == 0) return INT_MIN;
   if (!strcmp(key, "n_devices")) return h->group.size();
   if (!strcmp(key, "live_hip_objects")) return (int)axw::live_owned.load();  // test hook: of every handle of the process
-  if (!strcmp(key, "persistent_giveups")) {  // a count: summed over the handle's engines
+  if (!strcmp(key, "persistent_giveups") || !strcmp(key, "persistent_ts_launches")) {  // counts: summed over the handle's engines
     long sum = 0;
     for (int i = 0; i < h->group.size(); ++i) {
       Engine& e = h->group.at(i);

@@ -777,6 +777,15 @@ struct PersistParams {
   // One-clip launch: the poller waves keep the tail of their workgroup's vocabulary rows in registers for the whole launch
   // (decode_persistent.hip "resident vocabulary rows"); 0 (AX_WHISPER_VOCAB_RESIDENT=0): every row is streamed every step
   int vocab_resident;
+  // One-clip launch under the timestamp rules (decode_persistent_rules.hpp; rules = 1: the kernel's rules instantiation). n_prefix: ids
+  // of the prefix (4 plain: [sot, language, transcribe, notimestamps]; 3 under the rules); ts_begin: id of 0.00 s; suppress: the
+  // suppress mask's words (decode_rules.hpp) or nullptr. Scored mode: ts_logprob / ts_decision ([ts_stride], index = history length)
+  // and no_speech (one value) as the scored rules kernel writes them, nullptr: timestamp mode. logits0_dump: teacher forcing, the row
+  // of the step that fed sot (scored mode only).
+  int rules, n_prefix, ts_begin;
+  const unsigned* suppress;
+  float* ts_logprob; int* ts_decision; long ts_stride; float* no_speech; int no_speech_id;
+  float* logits0_dump;
 };
 bool decode_persistent_supported(int d_model, int n_head, int n_layer, int n_cu);
 int decode_persistent_grid(int d_model, int n_cu);
@@ -785,6 +794,7 @@ size_t qfold_floats(int d_model, int n_layer);                // floats of the q
 void launch_qfold_build(const h16* wl, const float* fl, float* qf, int d_model, int n_layer, hipStream_t s);
 hipError_t launch_decode_persistent(const PersistParams& p, int d_model, int grid, hipStream_t s);  // n_clip 1, 2 or 3
 int decode_persistent_max_clips(int d_model, int n_head, int n_layer, int grid);  // clips per persistent launch: 1, 2 or 3
+bool decode_persistent_rules_supported(int n_vocab, int grid);  // the rules instantiation: every workgroup's rows fit its suppress image
 int decode_persistent_vocab_resident_rows(int d_model, int n_vocab, int grid);    // vocabulary rows a workgroup of the one-clip launch keeps on-chip
 // host only: the decisions above for a shape + the cross-attention role assignment of a launch (AX_WHISPER_PersistentDecodePlan)
 int decode_persistent_plan(int d_model, int n_head, int n_layer, int n_cu, int n_clips, int t0, int n_slots, int* plan4, int* units);

@@ -28,6 +28,7 @@
 // Every spin is bounded: a lane that waits too long raises a flag, its workgroup sets an error word and leaves; the
 // others see the word (or time out themselves) and leave too, so the grid always drains. The host then falls back.
 #include "decode_persistent_common.hpp"
+#include "decode_persistent_rules.hpp"
 
 namespace axw {
 inline namespace AXW_NS {
@@ -121,10 +122,18 @@ size_t qfold_floats(int d_model, int n_layer) { return (size_t)n_layer * (size_t
 // the timeline build, which has a few registers less to give, keeps five. Rows wider than 3 chunks keep none.
 template <int CD, bool PROF>
 constexpr int kVocabRes = CD > 3 ? 0 : PROF ? 5 : 6;
-template <int LD, int CD, int LF, int CF, bool PROF, bool QF>
+//
+// RULES = 1 (decode_persistent_rules.hpp): the launch of timestamp and scored mode. The prefix is [sot, language,
+// transcribe]; both row loops of the vocabulary phase keep a RulesRec per lane under the step's allowed sets instead of one
+// candidate; compute wave 0 folds the sixteen wave records and publishes the workgroup's eight words at O_REC with one store
+// instruction; the pollers gather the P records in the round trip that carried the argmax pairs, and every workgroup decides the
+// token with decode_rules.hpp's functions. The history's four values travel in registers. Scored mode (PersistParams::ts_logprob)
+// also runs the vocabulary phase at step 0 over the whole row: the no-speech value. RULES = 0 compiles none of it.
+template <int LD, int CD, int LF, int CF, bool PROF, bool QF, int RULES>
 __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) {
   AXW_PERSIST_SHAPES
-  constexpr int NRES = kVocabRes<CD, PROF>, VCAP = NRES * (PL / LD);  // resident passes, rows
+  // (the rules' row loop needs the registers of one resident pass: as many passes as the timeline build keeps)
+  constexpr int NRES = kVocabRes<CD, PROF || RULES != 0>, VCAP = NRES * (PL / LD);  // resident passes, rows
   constexpr int XG = D, X0R = 2 * D, A0S = 3 * D;  // QF: act[XG..) = g_cross . x0, act[X0R..) = x0 (written with the QKV LayerNorm, read by
                                                   // the row producers), act[A0S + slot] = A0 of the slot's row (free until the partial records)
   AXW_PERSIST_LDS(4)  // red[2*NPW]: the stage's mean (QF: the statistics' shift), red[2*NPW + 1]: the shift the sums are relative to
@@ -136,6 +145,45 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
   if (PROF && tl_on && (tid == 0 || tid == PL)) prof_acc[32 + (IDX)] = wall_clock64();
   int tok = AXW_COLD(sot)[0];
   int n_out = 0, n_done = 0, steps_run = 0;
+  // steps whose logits are dropped (the prefix but its last id), and whether a step runs the vocabulary phase (scored rules: step 0
+  // as well, the no-speech row). Macros: the plain instantiations keep their literals.
+#define AXW_NSKIP (RULES ? AXW_COLD(n_prefix) - 1 : 3)
+#define AXW_VOCAB_STEP(STEP) (RULES ? ((STEP) >= AXW_COLD(n_prefix) - 1 || ((STEP) == 0 && AXW_COLD(no_speech) != nullptr)) : (STEP) >= 3)
+#define AXW_SKIP_STEP(STEP) (RULES ? !AXW_VOCAB_STEP(STEP) : (STEP) < 3)
+  [[maybe_unused]] constexpr int O_REC = O_STAT + D;  // RULES: workgroup wg's record, granules O_REC + 8 wg ..+ 7
+  [[maybe_unused]] unsigned *rec_c = nullptr, *rec_p = nullptr, *rec_g = nullptr, *sup = nullptr;
+  [[maybe_unused]] RulesState hist{-1, false, false};
+  if constexpr (RULES) {
+    rec_c = reinterpret_cast<unsigned*>(prof_acc + 64) + 32;  // behind the plain carve-up (kRulesLdsBytes)
+    rec_p = rec_c + NCW * kRecWords;
+    rec_g = rec_p + NPW * kRecWords;
+    sup = rec_g + NPW * 4;
+    // the suppress mask's words over this workgroup's rows, once per launch (zeros without a set: one code path)
+    if (tid < kRulesSupWords) {
+      const unsigned N = (unsigned)AXW_COLD(n_vocab);
+      const int wi = (int)(((unsigned)rwg * N / (unsigned)P) >> 5) + tid;
+      const unsigned* mask = AXW_COLD(suppress);
+      sup[tid] = (mask && wi <= (int)((N - 1) >> 5)) ? mask[wi] : 0u;
+    }
+    __syncthreads();
+  }
+  // RULES: what the row loops of `step` need; v0: the workgroup's first row
+  [[maybe_unused]] auto rules_step = [&](int step, int v0) -> RulesStep {
+    RulesStep q;
+    const int T = AXW_COLD(ts_begin), skip = AXW_NSKIP;
+    q.E = AXW_COLD(eot);
+    q.no_speech_id = AXW_COLD(no_speech_id);
+    q.w0 = v0 >> 5;
+    q.whole = step < skip;
+    q.a = allowed_sets_from_state(step - skip, hist.last_ts, hist.last_is_ts, hist.penult_is_ts, T, q.E, AXW_COLD(n_vocab));
+    return q;
+  };
+  // RULES: where the step's row is dumped (teacher forcing), nullptr: nowhere
+  [[maybe_unused]] auto rules_dump = [&](int step) -> float* {
+    const int skip = AXW_NSKIP;
+    if (step < skip) return AXW_COLD(logits0_dump);
+    return AXW_COLD(logits_dump) ? AXW_COLD(logits_dump) + (long)(step - skip) * AXW_COLD(n_vocab) : nullptr;
+  };
 
   if (poller) {
     // ======================================================================================= pollers
@@ -418,7 +466,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
 
       steps_run = step + 1;
       asm volatile("" : "+v"(tid));
-      if (step < 3) {  // SOT steps: feed the next forced token, logits are discarded (Whisper.cpp:214-217)
+      if (AXW_SKIP_STEP(step)) {  // SOT steps: feed the next forced token, logits are discarded (Whisper.cpp:214-217)
         tok = AXW_COLD(sot)[step + 1];
         if constexpr (QF) wg_barrier();  // the next step's first stage writes act before its barrier: nobody may still be reading it
         continue;
@@ -432,9 +480,12 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
           int v0, vb, v1;
           vocab_tail(v0, vb, v1);
           if (vb < v1) {
-            float* dump = AXW_COLD(logits_dump) ? AXW_COLD(logits_dump) + (long)(step - 3) * AXW_COLD(n_vocab) : nullptr;
+            float* dump = RULES ? rules_dump(step) : AXW_COLD(logits_dump) ? AXW_COLD(logits_dump) + (long)(step - 3) * AXW_COLD(n_vocab) : nullptr;
             float bv = -INFINITY;
             int bi = 0x7fffffff;
+            [[maybe_unused]] RulesRec rec = rules_rec_empty();
+            [[maybe_unused]] RulesStep rq{};
+            if constexpr (RULES) rq = rules_step(step, v0);
 #pragma unroll
             for (int k = 0; k < NRES; ++k) {
               u32x4 w[CD];
@@ -450,37 +501,86 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
               const int row = vb + k * (PL / LD) + tid / LD;
               if (tid % LD == 0 && row < v1) {
                 if (dump) dump[row] = acc;
-                if (acc > bv) { bv = acc; bi = row; }
+                if constexpr (RULES) rules_rec_row(rec, rq, sup, acc, row);
+                else if (acc > bv) { bv = acc; bi = row; }
               }
             }
-            wave_argmax(bv, bi);
-            // one candidate per poller wave in pscr (free between the attention phases); am_v[0..8) is not: the pollers write
-            // the grid's merge there behind B3, while compute wave 0 may still be folding
-            if ((tid & 63) == 0) { pscr[tid >> 6] = bv; reinterpret_cast<int*>(pscr)[NPW + (tid >> 6)] = bi; }
+            if constexpr (RULES) {  // one record per poller wave
+              rules_rec_wave_reduce(rec);
+              if ((tid & 63) == 0) rules_rec_store(rec_p + (tid >> 6) * kRecWords, rec);
+            } else {
+              wave_argmax(bv, bi);
+              // one candidate per poller wave in pscr (free between the attention phases); am_v[0..8) is not: the pollers write
+              // the grid's merge there behind B3, while compute wave 0 may still be folding
+              if ((tid & 63) == 0) { pscr[tid >> 6] = bv; reinterpret_cast<int*>(pscr)[NPW + (tid >> 6)] = bi; }
+            }
           }
         }
         AXW_STAMP(14)
         wg_barrier();  // B3: the compute waves have their workgroup argmax
-        unsigned v[2];  // {value, row index} of workgroup tid: one pair
-        const bool fail2 = gather2<1>(GR, (unsigned)(step + 1), v, p.err, ctl, [&](int) { return tid < P ? O_AMAX + 2 * tid : -1; });
-        // first max wins (Whisper.cpp:42-45)
-        float cv = tid < P ? __uint_as_float(v[0]) : -INFINITY;
-        int ci = tid < P ? (int)v[1] : 0x7fffffff;
-        wave_argmax(cv, ci);  // DPP + row swaps: the __shfl_xor form is twelve dependent ds_bpermute round trips on the token's path
-        if ((tid & 63) == 0) { am_v[tid >> 6] = cv; am_i[tid >> 6] = ci; }
-        if (fail2) ctl[0] = 1;
-        AXW_STAMP(15)
-        AXW_BARRIER_CHECK(0xA00)  // B4
+        if constexpr (RULES) {
+          // lanes t < 256: (tv, ti), (sv, si) of workgroup t; lanes 256 + t: (mt, st), (m, s) of workgroup t — two pairs per lane, the
+          // round trip of the argmax pairs. Waves 0-3 reduce winners, waves 4-7 logsumexp pairs; wave results to rec_g.
+          unsigned v[4];
+          const int gw = tid & 255;
+          const bool fail2 = gather2<2>(GR, (unsigned)(step + 1), v, p.err, ctl, [&](int k) { return gw < P ? O_REC + kRecWords * gw + (tid >> 8) * 4 + 2 * k : -1; });
+          float r0 = __uint_as_float(v[0]), r2 = __uint_as_float(v[2]);
+          if (tid < 256) {
+            int i0 = (int)v[1], i1 = (int)v[3];
+            if (gw >= P) { r0 = -INFINITY; i0 = 0x7fffffff; r2 = -INFINITY; i1 = 0x7fffffff; }
+            wave_argmax(r0, i0);
+            wave_argmax(r2, i1);
+            if ((tid & 63) == 0) { unsigned* o = rec_g + 4 * (tid >> 6); o[0] = __float_as_uint(r0); o[1] = (unsigned)i0; o[2] = __float_as_uint(r2); o[3] = (unsigned)i1; }
+          } else {
+            float r1 = __uint_as_float(v[1]), r3 = __uint_as_float(v[3]);
+            if (gw >= P) { r0 = -INFINITY; r1 = 0.f; r2 = -INFINITY; r3 = 0.f; }
+            lse_wave_reduce_dpp(r0, r1);
+            lse_wave_reduce_dpp(r2, r3);
+            if ((tid & 63) == 0) { unsigned* o = rec_g + 4 * (tid >> 6); o[0] = __float_as_uint(r0); o[1] = __float_as_uint(r1); o[2] = __float_as_uint(r2); o[3] = __float_as_uint(r3); }
+          }
+          if (fail2) ctl[0] = 1;
+          AXW_STAMP(15)
+          AXW_BARRIER_CHECK(0xA00)  // B4
+        } else {
+          unsigned v[2];  // {value, row index} of workgroup tid: one pair
+          const bool fail2 = gather2<1>(GR, (unsigned)(step + 1), v, p.err, ctl, [&](int) { return tid < P ? O_AMAX + 2 * tid : -1; });
+          // first max wins (Whisper.cpp:42-45)
+          float cv = tid < P ? __uint_as_float(v[0]) : -INFINITY;
+          int ci = tid < P ? (int)v[1] : 0x7fffffff;
+          wave_argmax(cv, ci);  // DPP + row swaps: the __shfl_xor form is twelve dependent ds_bpermute round trips on the token's path
+          if ((tid & 63) == 0) { am_v[tid >> 6] = cv; am_i[tid >> 6] = ci; }
+          if (fail2) ctl[0] = 1;
+          AXW_STAMP(15)
+          AXW_BARRIER_CHECK(0xA00)  // B4
+        }
       }
-      float cv = am_v[0];
-      int best_idx = am_i[0];
-      for (int w2 = 1; w2 < NPW; ++w2)
-        if (am_v[w2] > cv || (am_v[w2] == cv && am_i[w2] < best_idx)) { cv = am_v[w2]; best_idx = am_i[w2]; }
-      // no logit compared greater than -inf (all NaN / -inf: non-finite audio): std::max_element returns index 0
-      // (Whisper.cpp:42-45); never let the "no candidate" index reach the embedding lookup
-      if ((unsigned)best_idx >= (unsigned)AXW_COLD(n_vocab)) best_idx = 0;
-      wg_barrier();  // B5: am_v/am_i are free again
-      const int gi = step - 3;
+      // (declared here, in front of both branches, as the plain launch always had them: the plain instantiations keep their code)
+      [[maybe_unused]] float cv = RULES ? 0.f : am_v[0];
+      int best_idx = RULES ? 0 : am_i[0];
+      if constexpr (RULES) {
+        const RulesRec g = rules_rec_grid(rec_g);
+        wg_barrier();  // B5: rec_g is free again
+        if (step < AXW_NSKIP) {  // the step that fed sot: the no-speech value, then on with the prefix
+          if (wg == 0 && tid == 0) AXW_COLD(no_speech)[0] = rules_no_speech_logprob(g);
+          tok = AXW_COLD(sot)[step + 1];
+          continue;
+        }
+        const RulesDecision dec = rules_decide(g, AXW_COLD(eot));
+        best_idx = dec.id;
+        const int nh = step - AXW_NSKIP;  // the history's length
+        if (wg == 0 && tid == 0 && AXW_COLD(ts_logprob) && nh < AXW_COLD(ts_stride)) {
+          AXW_COLD(ts_logprob)[nh] = dec.logprob;
+          AXW_COLD(ts_decision)[nh] = dec.id;
+        }
+      } else {
+        for (int w2 = 1; w2 < NPW; ++w2)
+          if (am_v[w2] > cv || (am_v[w2] == cv && am_i[w2] < best_idx)) { cv = am_v[w2]; best_idx = am_i[w2]; }
+        // no logit compared greater than -inf (all NaN / -inf: non-finite audio): std::max_element returns index 0
+        // (Whisper.cpp:42-45); never let the "no candidate" index reach the embedding lookup
+        if ((unsigned)best_idx >= (unsigned)AXW_COLD(n_vocab)) best_idx = 0;
+        wg_barrier();  // B5: am_v/am_i are free again
+      }
+      const int gi = RULES ? step - AXW_NSKIP : step - 3;
       if (AXW_COLD(forced)) {
         if (wg == 0 && tid == 0 && AXW_COLD(argmax_dump) && gi <= AXW_COLD(n_forced)) AXW_COLD(argmax_dump)[gi] = best_idx;
         if (gi < AXW_COLD(n_forced)) tok = AXW_COLD(forced)[gi];
@@ -490,6 +590,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         ++n_out;
         tok = best_idx;
       }
+      if constexpr (RULES) rules_state_push(hist, tok, AXW_COLD(ts_begin));
     }
 #undef AXW_LN_STAGE
 #undef AXW_LN_STAGE_X
@@ -771,7 +872,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         }
         // next consumer of the residual stream: the next layer's QKV rows, the vocabulary projection, or the next step
         if (l + 1 < L) qkv_prefetch(l + 1);
-        else if (step >= 3) ra.prefetch(AXW_COLD(tok_emb), nullptr, D, AXW_COLD(n_vocab), rwg, P, ctid);
+        else if (AXW_VOCAB_STEP(step)) ra.prefetch(AXW_COLD(tok_emb), nullptr, D, AXW_COLD(n_vocab), rwg, P, ctid);
         else qkv_prefetch(0);
         kv_piece(13, 16);
         AXW_STAMP(29)
@@ -780,7 +881,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
 
       steps_run = step + 1;
       asm volatile("" : "+v"(ctid));
-      if (step < 3) {
+      if (AXW_SKIP_STEP(step)) {
         tok = AXW_COLD(sot)[step + 1];
         if constexpr (QF) wg_barrier();
         continue;
@@ -806,17 +907,21 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         }
         float bv = -INFINITY;
         int bi = 0x7fffffff;
-        float* dump = AXW_COLD(logits_dump) ? AXW_COLD(logits_dump) + (long)(step - 3) * N : nullptr;
+        float* dump = RULES ? rules_dump(step) : AXW_COLD(logits_dump) ? AXW_COLD(logits_dump) + (long)(step - 3) * N : nullptr;
         // the pollers hold the last `nres` rows of the range (vocab_tail): stream the rest
         const int nres = NRES > 0 && AXW_COLD(vocab_resident) ? (ra.r1 - ra.r0 > VCAP ? VCAP : ra.r1 - ra.r0) : 0;
         const int r0 = ra.r0, r1 = ra.r1 - nres;
+        [[maybe_unused]] RulesRec rec = rules_rec_empty();
+        [[maybe_unused]] RulesStep rq{};
+        if constexpr (RULES) rq = rules_step(step, ra.r0);
         auto consume = [&](const u32x4 (&wr)[CD], int row) {
           float acc;
           if constexpr (kActInRegs) acc = rows_dot_reg<LD, CD>(wr, a);
           else acc = rows_dot<LD, CD>(wr, act, ctid);
           if (j == 0) {
             if (dump) dump[row] = acc;
-            if (acc > bv) { bv = acc; bi = row; }
+            if constexpr (RULES) rules_rec_row(rec, rq, sup, acc, row);
+            else if (acc > bv) { bv = acc; bi = row; }
           }
         };
         if constexpr (CD <= 3) {  // two passes ahead: ra.w holds pass 0, wn pass 1
@@ -845,37 +950,62 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         }
         // the next step's first rows: requested before the token is even known
         qkv_prefetch(0);
-        // workgroup argmax: lanes with j == 0 hold candidates; the lower index wins ties
-        if (j != 0) { bv = -INFINITY; bi = 0x7fffffff; }
-        wave_argmax(bv, bi);
-        if (lane == 0) { am_v[8 + cw] = bv; am_i[8 + cw] = bi; }
-        // compute waves only: named exchange through LDS, then wave 0 publishes. The pollers sit at B3 meanwhile.
-        wg_barrier();  // B3 (all waves)
-        if (ctid == 0) {
-          for (int w2 = 1; w2 < NCW; ++w2)
-            argmax_take(bv, bi, am_v[8 + w2], am_i[8 + w2]);
-          if (nres > 0) {  // the poller waves' candidates over the resident rows
-            for (int w2 = 0; w2 < NPW; ++w2) {
-              const float pv = pscr[w2];
-              const int pi = reinterpret_cast<const int*>(pscr)[NPW + w2];
-              argmax_take(bv, bi, pv, pi);
-            }
+        if constexpr (RULES) {
+          // one record per compute wave (lanes with j != 0 hold the empty one); behind B3 compute wave 0 folds them with the poller
+          // waves' and publishes the workgroup's eight words: lanes 0-7, one store instruction
+          rules_rec_wave_reduce(rec);
+          if (lane == 0) rules_rec_store(rec_c + cw * kRecWords, rec);
+          wg_barrier();  // B3 (all waves)
+          if (cw == 0) {
+            const RulesRec wr = rules_rec_fold(rec_c, rec_p, nres > 0, lane);
+            if (lane < kRecWords) gput_u(G + O_REC + kRecWords * wg + lane, (unsigned)(step + 1), rules_rec_word(wr, lane));
           }
-          am_v[8] = bv; am_i[8] = bi;
+          AXW_STAMP(30)
+          AXW_BARRIER_CHECK(0xA00)  // B4
+        } else {
+          // workgroup argmax: lanes with j == 0 hold candidates; the lower index wins ties
+          if (j != 0) { bv = -INFINITY; bi = 0x7fffffff; }
+          wave_argmax(bv, bi);
+          if (lane == 0) { am_v[8 + cw] = bv; am_i[8 + cw] = bi; }
+          // compute waves only: named exchange through LDS, then wave 0 publishes. The pollers sit at B3 meanwhile.
+          wg_barrier();  // B3 (all waves)
+          if (ctid == 0) {
+            for (int w2 = 1; w2 < NCW; ++w2)
+              argmax_take(bv, bi, am_v[8 + w2], am_i[8 + w2]);
+            if (nres > 0) {  // the poller waves' candidates over the resident rows
+              for (int w2 = 0; w2 < NPW; ++w2) {
+                const float pv = pscr[w2];
+                const int pi = reinterpret_cast<const int*>(pscr)[NPW + w2];
+                argmax_take(bv, bi, pv, pi);
+              }
+            }
+            am_v[8] = bv; am_i[8] = bi;
+          }
+          __builtin_amdgcn_wave_barrier();
+          if (ctid < 2)  // value and index of this workgroup's best row in ONE store instruction
+            gput_u(G + O_AMAX + 2 * wg + ctid, (unsigned)(step + 1), ctid == 0 ? __float_as_uint(am_v[8]) : (unsigned)am_i[8]);
+          AXW_STAMP(30)
+          AXW_BARRIER_CHECK(0xA00)  // B4
         }
-        __builtin_amdgcn_wave_barrier();
-        if (ctid < 2)  // value and index of this workgroup's best row in ONE store instruction
-          gput_u(G + O_AMAX + 2 * wg + ctid, (unsigned)(step + 1), ctid == 0 ? __float_as_uint(am_v[8]) : (unsigned)am_i[8]);
-        AXW_STAMP(30)
-        AXW_BARRIER_CHECK(0xA00)  // B4
       }
-      float cv = am_v[0];
-      int best_idx = am_i[0];
-      for (int w2 = 1; w2 < NPW; ++w2)
-        if (am_v[w2] > cv || (am_v[w2] == cv && am_i[w2] < best_idx)) { cv = am_v[w2]; best_idx = am_i[w2]; }
-      if ((unsigned)best_idx >= (unsigned)AXW_COLD(n_vocab)) best_idx = 0;  // as in the pollers' copy of this merge
-      wg_barrier();  // B5
-      const int gi = step - 3;
+      // (declared here, in front of both branches, as the plain launch always had them: the plain instantiations keep their code)
+      [[maybe_unused]] float cv = RULES ? 0.f : am_v[0];
+      int best_idx = RULES ? 0 : am_i[0];
+      if constexpr (RULES) {  // as in the pollers' copy of this decision
+        const RulesRec g = rules_rec_grid(rec_g);
+        wg_barrier();  // B5
+        if (step < AXW_NSKIP) {
+          tok = AXW_COLD(sot)[step + 1];
+          continue;
+        }
+        best_idx = rules_decide(g, AXW_COLD(eot)).id;
+      } else {
+        for (int w2 = 1; w2 < NPW; ++w2)
+          if (am_v[w2] > cv || (am_v[w2] == cv && am_i[w2] < best_idx)) { cv = am_v[w2]; best_idx = am_i[w2]; }
+        if ((unsigned)best_idx >= (unsigned)AXW_COLD(n_vocab)) best_idx = 0;  // as in the pollers' copy of this merge
+        wg_barrier();  // B5
+      }
+      const int gi = RULES ? step - AXW_NSKIP : step - 3;
       if (AXW_COLD(forced)) {
         if (gi < AXW_COLD(n_forced)) tok = AXW_COLD(forced)[gi];
       } else {
@@ -883,6 +1013,7 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
         ++n_out;
         tok = best_idx;
       }
+      if constexpr (RULES) rules_state_push(hist, tok, AXW_COLD(ts_begin));
     }
   }
 
@@ -893,6 +1024,9 @@ __global__ __launch_bounds__(PT) void decode_persistent_kernel(PersistParams p) 
     AXW_COLD(state)->n_done = n_done;
   }
 #undef AXW_TL
+#undef AXW_NSKIP
+#undef AXW_VOCAB_STEP
+#undef AXW_SKIP_STEP
 }
 
 // ---------------------------------------------------------------------------------------- host side (both launches)
@@ -930,18 +1064,30 @@ int decode_persistent_vocab_resident_rows(int d_model, int n_vocab, int grid) {
   return cap < rows ? cap : rows;
 }
 // 16 d-wide buffers, the argmax pairs at 16 d (up to 512 granules), the fold's statistics at 16 d + 512 (one 16-granule line
-// per row producer, at most d / 16 of them), the error word last
-size_t decode_persistent_gran_bytes(int d_model, int /*grid*/) { return ((size_t)16 * d_model + 512 + (size_t)d_model + 64) * 8; }
+// per row producer, at most d / 16 of them), the rules instantiation's records at 17 d + 512 (eight granules per workgroup, at most
+// 256 of them), the error word last
+size_t decode_persistent_gran_bytes(int d_model, int /*grid*/) { return ((size_t)16 * d_model + 512 + (size_t)d_model + 256 * kRecWords + 64) * 8; }
+// the rules instantiation keeps the suppress mask's words over a workgroup's rows in LDS (decode_persistent_rules.hpp)
+bool decode_persistent_rules_supported(int n_vocab, int grid) { return grid >= 1 && grid <= 256 && n_vocab / grid + 1 <= kRulesMaxRange; }
 
 // the profiling stamps are a separate instantiation: the production kernel carries none of their code
 template <int LD, int CD, int LF, int CF>
 static hipError_t launch_one(const PersistParams& p, int grid, hipStream_t s) {
   constexpr int D = 8 * LD * CD;
+  if (p.rules) {  // timestamp and scored mode: the rules instantiation (no timeline build of it)
+    if (p.prof || p.n_prefix < 2 || p.n_prefix > 4 || !decode_persistent_rules_supported(p.n_vocab, grid) || p.ts_begin <= p.eot || p.ts_begin > p.n_vocab ||
+        (p.ts_logprob && (!p.ts_decision || !p.no_speech || p.ts_stride < 1 || p.no_speech_id < 0 || p.no_speech_id >= p.n_vocab)))
+      return hipErrorInvalidValue;
+    if constexpr (D <= 768) {
+      if (p.qf) return launch_persistent(decode_persistent_kernel<LD, CD, LF, CF, false, true, 1>, D, 1, p, grid, s, kRulesLdsBytes);
+    }
+    return launch_persistent(decode_persistent_kernel<LD, CD, LF, CF, false, false, 1>, D, 1, p, grid, s, kRulesLdsBytes);
+  }
   if constexpr (D <= 768) {  // the query fold, when the engine built its arena (p.qf)
     if (p.qf)
-      return launch_persistent(p.prof ? decode_persistent_kernel<LD, CD, LF, CF, true, true> : decode_persistent_kernel<LD, CD, LF, CF, false, true>, D, 1, p, grid, s);
+      return launch_persistent(p.prof ? decode_persistent_kernel<LD, CD, LF, CF, true, true, 0> : decode_persistent_kernel<LD, CD, LF, CF, false, true, 0>, D, 1, p, grid, s);
   }
-  return launch_persistent(p.prof ? decode_persistent_kernel<LD, CD, LF, CF, true, false> : decode_persistent_kernel<LD, CD, LF, CF, false, false>, D, 1, p, grid, s);
+  return launch_persistent(p.prof ? decode_persistent_kernel<LD, CD, LF, CF, true, false, 0> : decode_persistent_kernel<LD, CD, LF, CF, false, false, 0>, D, 1, p, grid, s);
 }
 
 hipError_t launch_decode_persistent(const PersistParams& p, int d_model, int grid, hipStream_t s) {

@@ -1000,8 +1000,9 @@ hipError_t persist_dispatch(int d_model, Fn&& fn) {
 }
 
 // one persistent kernel instantiation on `grid` workgroups with the LDS of nc clips
-inline hipError_t launch_persistent(void (*kfn)(PersistParams), int d, int nc, const PersistParams& p, int grid, hipStream_t s) {
-  const size_t lds = persist_lds_bytes(d, nc);
+// (extra_lds: bytes behind the common carve-up, the rules instantiation's)
+inline hipError_t launch_persistent(void (*kfn)(PersistParams), int d, int nc, const PersistParams& p, int grid, hipStream_t s, size_t extra_lds = 0) {
+  const size_t lds = persist_lds_bytes(d, nc) + extra_lds;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(PT), lds, s, p);

@@ -93,6 +93,26 @@ __device__ __forceinline__ AllowedSets allowed_sets(const int* seq, int n, int T
   a.text_begin = a.text_on ? 0 : (a.eot_on ? E : 0);
   return a;
 }
+// The same sets for a loop that carries the history's four values instead of its ids (the persistent launch's rules instantiation,
+// decode_persistent_rules.hpp): n, the id of the last timestamp (any value below T: none), whether the last id is a timestamp and
+// whether the one before it is (neither is read where the history is too short). No barrier, no memory.
+__device__ __forceinline__ AllowedSets allowed_sets_from_state(int n, int last_ts_id, bool last_is_ts, bool penult_is_ts, int T, int E, int nv) {
+  const bool last_ts = n >= 1 && last_is_ts;
+  const bool penult_ts = n < 2 || penult_is_ts;
+  const bool pair_open = last_ts && !penult_ts;
+  AllowedSets a;
+  a.text_on = n > 0 && !pair_open;
+  a.eot_on = n > 0;
+  a.ts_lo = T;
+  a.ts_hi = nv;
+  if (n >= 1 && last_ts_id >= T) a.ts_lo = min(last_ts_id + (pair_open ? 0 : 1), nv);
+  if (last_ts && penult_ts) a.ts_hi = T;
+  if (n == 0) a.ts_hi = min(a.ts_hi, T + 51);
+  a.ts_lo = min(a.ts_lo, a.ts_hi);
+  a.text_end = a.text_on ? E + 1 : (a.eot_on ? E + 1 : 0);
+  a.text_begin = a.text_on ? 0 : (a.eot_on ? E : 0);
+  return a;
+}
 __device__ __forceinline__ bool text_id_on(const AllowedSets& a, int i, int E) { return i < E ? a.text_on : (i == E && a.eot_on); }
 __device__ __forceinline__ bool timestamp_on(const AllowedSets& a, int i) { return i >= a.ts_lo && i < a.ts_hi; }
 

@@ -105,6 +105,15 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
         const char* ev = getenv("AX_WHISPER_VOCAB_RESIDENT");
         if (!(ev && ev[0] == '0')) vocab_resident_rows_ = decode_persistent_vocab_resident_rows(cfg_.n_text_state, cfg_.n_vocab, persist_grid_);
       }
+      // one clip in timestamp or scored mode: the launch's rules instantiation (decode_persistent_rules.hpp), for a
+      // vocabulary with Whisper's timestamp ids whose ranges fit the launch's suppress image. Off unless AX_WHISPER_PERSIST_TS=1: the
+      // two routes round a row's last bits differently, and two existing tests compare scores of one-clip windows across entry
+      // points bit for bit
+      {
+        const char* et = getenv("AX_WHISPER_PERSIST_TS");
+        const int T = cfg_.no_timestamps + 1;
+        persistent_ts_ = et && et[0] == '1' && cfg_.n_vocab - T == 1501 && T > cfg_.eot && decode_persistent_rules_supported(cfg_.n_vocab, persist_grid_);
+      }
       if (persist_max_clips_ >= 2) {
         self1_bytes_ = (size_t)cfg_.n_text_layer * cfg_.n_text_head * 8 * layout::kKvBlockElems * 2;  // one later clip's cache (K; V alike)
         d_self_k1_ = (h16*)pooled<char>(allocs_, (persist_max_clips_ - 1) * self1_bytes_, true);
@@ -119,6 +128,8 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
   cfg_.ints["persistent_qfold"] = d_qfold_ ? 1 : 0;
   cfg_.ints["vocab_resident_rows"] = vocab_resident_rows_;
   cfg_.ints["persistent_giveups"] = 0;
+  cfg_.ints["persistent_ts"] = persistent_ts_ ? 1 : 0;  // one-clip timestamp and scored decodes take the persistent launch
+  cfg_.ints["persistent_ts_launches"] = 0;              // such launches that finished without a give-up
   try { (void)prefill_route(); } catch (const std::exception&) {}  // "prefill": the route prompted calls take (a bad AX_WHISPER_PREFILL is reported by the first prompted call)
   {  // batched decode as clip-block GEMMs with LayerNorm prologue / residual epilogue (enqueue_decode_step_batched)
     const char* e = getenv("AX_WHISPER_BATCHED_LN");
@@ -1108,6 +1119,13 @@ void Engine::decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, 
   if (batch == 1 && !tsm && persistent_usable()) {
     if (run_persistent(cfg_.n_text_ctx, d_forced, n_forced, d_logits, d_arg) >= 0) { done = true; persistent_succeeded(); }
     else persistent_gave_up();
+  } else if (persistent_ts_route(mode, batch, ctx)) {  // timestamp and scored mode: the launch's rules instantiation (rows as the launch computed them)
+    if (run_persistent(cfg_.n_text_ctx, d_forced, n_forced, d_logits, d_arg, 0, -1, -1, mode, scored ? &spec.score_out : nullptr, b_l0) >= 0) {
+      done = true;
+      persistent_succeeded();
+    } else {
+      persistent_gave_up();
+    }
   }
   if (!done) reset_decode_state(batch);
   DeviceArray<int> d_base;

@@ -376,7 +376,12 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   int prefill_route();             // 0 the prefill pass, 1 the step-fed route (AX_WHISPER_PREFILL=step)
   bool prefill_supported() const;  // the prefill kernels take this decoder shape
   // batch 1: the whole loop as one persistent launch (decode_persistent.hip); returns steps run, -1 if it gave up
-  int run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot = 0, int max_new1 = -1, int max_new2 = -1);
+  // mode kDecodeTimestamps / kDecodeScored (one clip, slot 0): the launch's rules instantiation; scores: where a scored launch writes
+  // (nullptr: the engine's own arrays), d_logits0: teacher forcing, the row of decode offset 0
+  int run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot = 0, int max_new1 = -1, int max_new2 = -1,
+                     DecodeMode mode = kDecodePlain, const TsScoreParams* scores = nullptr, float* d_logits0 = nullptr);
+  // timestamp / scored mode of ONE clip without a context through that launch (AX_WHISPER_PERSIST_TS=1 turns the route on); asks persistent_usable()
+  bool persistent_ts_route(DecodeMode mode, int batch, const ClipContexts& ctx);
   void fetch_ids(int batch, int32_t* ids, int* n_ids);
   // beam search (engine_beam.cpp)
   void ensure_beam_buffers();
@@ -466,6 +471,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void persistent_gave_up();
   void persistent_succeeded();
   int persist_grid_ = 0;
+  bool persistent_ts_ = false;         // the rules instantiation serves this handle's one-clip timestamp and scored decodes ("persistent_ts")
+  long persist_ts_launches_ = 0;       // such launches that finished without a give-up ("persistent_ts_launches")
   int vocab_resident_rows_ = 0;        // one-clip launch: vocabulary rows per workgroup held in the poller waves (0: AX_WHISPER_VOCAB_RESIDENT=0 or unsupported width)
   u64* d_gran_ = nullptr; size_t gran_bytes_ = 0;
   float* d_qfold_ = nullptr;  // query-fold arena of the one-clip launch (d_model <= 768), nullptr = unfolded

@@ -447,6 +447,12 @@ bool Engine::persistent_usable() {
   }
   return true;
 }
+// One clip in timestamp or scored mode, no context: the launch's rules instantiation. Everything else under the rules stays on the
+// launch-per-phase step: sampled mode, prompts, a language or task per clip, two or more clips (beam search and the slot stream never
+// come here). Asked once per request, last of all: persistent_usable() counts a back-off down.
+bool Engine::persistent_ts_route(DecodeMode mode, int batch, const ClipContexts& ctx) {
+  return (mode == kDecodeTimestamps || mode == kDecodeScored) && batch == 1 && !ctx.any() && persistent_ts_ && persistent_usable();
+}
 void Engine::persistent_gave_up() {
   persist_backoff_ = std::min(persist_backoff_ ? persist_backoff_ * 4 : 8, 4096);
   persist_skip_ = persist_backoff_;
@@ -551,9 +557,16 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
   // pair against 2 x 116 ms for one launch per clip (shapes without a multi-clip launch, AX_WHISPER_PERSIST2=0) and 316 ms through
   // the launch-per-phase path. Each clip stops at its own eot / budget.
   // (asked ONCE per request: persistent_usable() counts a back-off down)
-  // (timestamp mode: the launch-per-phase step only — the persistent launches carry no timestamp rules)
+  // (timestamp and scored mode: one clip through the one-clip launch's rules instantiation, DESIGN.md §11 — one clip, 440 ids,
+  // Whisper-small dims: profiles/persist_ts_bench.txt; everything else under the rules takes the launch-per-phase step)
   const bool usable = spec.mode == kDecodePlain && batch <= std::max(2, persist_max_clips_) && persistent_usable();
-  if (usable && batch >= 2 && batch <= persist_max_clips_) {
+  if (!spec.slots && !spec.feed && persistent_ts_route(spec.mode, batch, ctx)) {
+    int mn = max_new;
+    if (max_new_clip && max_new_clip[0] > 0) mn = std::min(mn, max_new_clip[0]);
+    const int st = run_persistent(mn, nullptr, 0, nullptr, nullptr, 0, -1, -1, spec.mode);
+    if (st >= 0) { persistent_succeeded(); return st; }
+    persistent_gave_up();
+  } else if (usable && batch >= 2 && batch <= persist_max_clips_) {
     int mn[3] = {max_new, -1, -1};
     for (int b = 0; b < batch; ++b) mn[b] = (max_new_clip && max_new_clip[b] > 0) ? std::min(max_new, max_new_clip[b]) : max_new;
     const int st = run_persistent(mn[0], nullptr, 0, nullptr, nullptr, 0, mn[1], mn[2]);
@@ -597,7 +610,15 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
 
 // max_new1 >= 0 (max_new2 >= 0): TWO (THREE) clips in this launch — slots `slot`, `slot + 1` (, `slot + 2`), budgets max_new / max_new1
 // (/ max_new2) (greedy decode only)
-int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot, int max_new1, int max_new2) {
+int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot, int max_new1, int max_new2,
+                           DecodeMode mode, const TsScoreParams* scores, float* d_logits0) {
+  const bool rules = mode != kDecodePlain, scored = mode == kDecodeScored;
+  if (rules) {  // the launch's rules instantiation: one clip, timestamp or scored mode
+    if (mode > kDecodeScored || max_new1 >= 0 || slot != 0 || !persistent_ts_) throw std::runtime_error("run_persistent: no rules launch for this request");
+    require_timestamp_vocab();
+    if (scored) { require_scored_vocab(); ensure_ts_scores(); }
+  }
+  const int n_prefix = rules ? 3 : 4;
   // The launch needs every workgroup resident at once (one per CU): two of them in flight on one GPU could each hold
   // part of the CUs and starve the other until both give up. Handles of one process on one device take turns.
   // (one mutex per device, shared by the bfloat16 and the half build of this file: iengine.hpp)
@@ -613,7 +634,18 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
   p.cross_layer_stride = (long)cap_ * H * layout::kv_head_elems(t_pad_);
   p.n_layer = cfg_.n_text_layer; p.n_vocab = cfg_.n_vocab; p.n_ctx = Tc; p.n_audio_ctx = cfg_.n_audio_ctx;
   p.eot = cfg_.eot; p.max_new = max_new;
-  p.total_steps = d_forced || d_logits || d_argmax ? 4 + n_forced : std::min(Tc, 4 + std::max(max_new, std::max(max_new1, max_new2)));
+  p.total_steps = d_forced || d_logits || d_argmax ? n_prefix + n_forced : std::min(Tc, n_prefix + std::max(max_new, std::max(max_new1, max_new2)));
+  p.n_prefix = n_prefix;
+  if (rules) {
+    p.rules = 1;
+    p.ts_begin = cfg_.no_timestamps + 1;
+    p.suppress = suppress_mask();
+    if (scored) {
+      const TsScoreParams& q = scores ? *scores : own_scores_;
+      p.ts_logprob = q.logprob; p.ts_decision = q.decision; p.ts_stride = q.stride; p.no_speech = q.no_speech; p.no_speech_id = q.no_speech_id;
+      p.logits0_dump = d_logits0;
+    }
+  }
   p.n_clip = 1;
   if (max_new1 >= 0) {
     p.n_clip = max_new2 >= 0 ? 3 : 2;
@@ -632,6 +664,7 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
   p.out_ids = d_out_ids_ + (size_t)slot * Tc; p.n_out = d_nout_ + slot; p.state = d_state_;
   DeviceArray<long long> d_prof;
   const char* prof_path = getenv("AX_WHISPER_PERSIST_PROF");  // debugging aid: per-workgroup, per-phase time of the launch
+  if (prof_path && rules) prof_path = nullptr;  // (the rules instantiation has no timeline build)
   if (prof_path) {
     d_prof = device_array<long long>((size_t)persist_grid_ * 64, true);
   }
@@ -666,6 +699,7 @@ int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float
     fprintf(stderr, "[ax_whisper] persistent decode gave up (code 0x%x); falling back to the launch-per-phase path\n", (unsigned)h_poll_[8]);
     return -1;
   }
+  if (rules) cfg_.ints["persistent_ts_launches"] = ++persist_ts_launches_;
   return h_poll_[9];
 }
 
