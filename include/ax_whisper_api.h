@@ -127,6 +127,16 @@ AX_WHISPER_API int AX_WHISPER_ComputeMel(AX_WHISPER_HANDLE handle, const float* 
 AX_WHISPER_API int AX_WHISPER_EncodeMel(AX_WHISPER_HANDLE handle, const float* mel, int batch);
 /** Copy slot's cross K/V back as fp32 [n_text_layer][1500][n_text_state] (reference layout). */
 AX_WHISPER_API int AX_WHISPER_GetCrossKV(AX_WHISPER_HANDLE handle, int slot, float* k_out, float* v_out);
+/** FP8 cross K/V (opt-in): a handle made while the environment variable AX_WHISPER_CROSS_KV is "fp8" also keeps the cross K/V as
+ *  OCP e4m3fn codes with one power-of-two scale per (layer, slot, head, K or V, head dimension), written by a quantise kernel at the
+ *  end of the encoder, and the cross-attention launches of decoder steps of more than two clips read the codes. Absent or "h16":
+ *  today's behaviour; any other value fails Init with an error text. AX_WHISPER_GetConfigInt: "cross_kv_fp8" (0 / 1),
+ *  "cross_kv_fp8_launches" (cross-attention launches that took the fp8 kernel).
+ *  GetCrossKVFp8: the slot's raw codes de-blocked to [n_text_layer][1500][n_text_state] bytes (value = code * scale) and its scales
+ *  [n_text_layer][n_text_head][2][64] (K's 64, then V's). CrossKVQuantize: the quantise kernel alone on every slot of the handle.
+ *  Both return -1 on a handle without the mode. */
+AX_WHISPER_API int AX_WHISPER_GetCrossKVFp8(AX_WHISPER_HANDLE handle, int slot, uint8_t* k_codes, uint8_t* v_codes, float* scales);
+AX_WHISPER_API int AX_WHISPER_CrossKVQuantize(AX_WHISPER_HANDLE handle);
 /** Parity aid: scan every 16-bit tensor the engine keeps between kernels (encoder activations of clips 0..batch-1, cross and
  *  self K/V caches, the decoder's activation pairs) after EncodeMel / Decode*: names [n_max][32] chars, nonfinite [n_max]
  *  (NaN or Inf elements), maxabs [n_max] (largest finite |x|), *n_out buffers reported. A trained model's outlier channels

@@ -17,6 +17,7 @@ import os
 import re
 import time
 import subprocess
+import threading
 
 import numpy as np
 
@@ -28,6 +29,7 @@ fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int32)
 _dblp = C.POINTER(C.c_double)
 _lib = None
+_cross_kv_env_lock = threading.Lock()  # Whisper(cross_kv=...): the variable is process-wide, one handle at a time is made under it
 
 class LongOptions(C.Structure):
     """AX_WHISPER_LONG_OPTIONS"""
@@ -82,6 +84,8 @@ SYMBOLS = {
     "AX_WHISPER_ComputeMel": (C.c_int, [C.c_void_p, fp, C.c_int, fp]),
     "AX_WHISPER_EncodeMel": (C.c_int, [C.c_void_p, fp, C.c_int]),
     "AX_WHISPER_GetCrossKV": (C.c_int, [C.c_void_p, C.c_int, fp, fp]),
+    "AX_WHISPER_GetCrossKVFp8": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), fp]),
+    "AX_WHISPER_CrossKVQuantize": (C.c_int, [C.c_void_p]),
     "AX_WHISPER_ScanStored16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64), fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_DecodeForced": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, fp, ip]),
     "AX_WHISPER_DecodeGreedy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, C.POINTER(C.c_int)]),
@@ -630,9 +634,38 @@ def _beam_clip(c, K, ids, n_ids, sum_lp, avg_lp, eot, winner, rec_ids, rec_len, 
 class Whisper:
     """Mirror of the reference's ``Whisper`` (python/whisper.py:54-99, cpp/src/Whisper.hpp:28-59)."""
 
-    def __init__(self, model_type: str, model_path: str, language: str = "zh", device: int = -1, max_batch: int = 0, devices=None):
-        """devices: a list of HIP ordinals (or "all") -> one engine per device behind this handle (AX_WHISPER_InitMulti)."""
+    def __init__(self, model_type: str, model_path: str, language: str = "zh", device: int = -1, max_batch: int = 0, devices=None,
+                 cross_kv: str | None = None):
+        """devices: a list of HIP ordinals (or "all") -> one engine per device behind this handle (AX_WHISPER_InitMulti).
+        cross_kv: "fp8" keeps the cross K/V as e4m3fn codes too and lets decoder steps of more than two clips read them (opt-in;
+        DESIGN.md "FP8 cross K/V"); "h16" or None: the h16 images alone. The library reads the mode from AX_WHISPER_CROSS_KV while
+        the handle is made: the variable is set for that call and put back afterwards, under a lock that every construction with a
+        cross_kv argument takes (a handle made at the same moment on another thread WITHOUT the argument, or by other code through
+        the C ABI, reads whatever the variable holds then)."""
         self.L = load_library()
+        if cross_kv is None:
+            self._init_handle(model_type, model_path, language, device, max_batch, devices)
+        else:
+            with _cross_kv_env_lock:
+                before = os.environ.get("AX_WHISPER_CROSS_KV")
+                os.environ["AX_WHISPER_CROSS_KV"] = str(cross_kv)
+                try:
+                    self._init_handle(model_type, model_path, language, device, max_batch, devices)
+                finally:
+                    if before is None:
+                        del os.environ["AX_WHISPER_CROSS_KV"]
+                    else:
+                        os.environ["AX_WHISPER_CROSS_KV"] = before
+        g = lambda k: self.L.AX_WHISPER_GetConfigInt(self.h, k.encode())
+        self.n_mels, self.n_vocab, self.n_text_ctx = g("n_mels"), g("n_vocab"), g("n_text_ctx")
+        self.n_text_layer, self.n_text_state, self.eot = g("n_text_layer"), g("n_text_state"), g("eot")
+        self.sot_seq = [g(f"sot_seq{i}") for i in range(4)]
+        self.timestamp_begin = g("timestamp_begin")
+        self.no_speech = g("no_speech")
+        self.n_devices = self.L.AX_WHISPER_GetDeviceCount(self.h)
+        self._tokens_path = os.path.join(model_path, model_type, f"{model_type}-tokens.txt")
+
+    def _init_handle(self, model_type, model_path, language, device, max_batch, devices):
         if devices is not None:
             if devices == "all":
                 self.h = self.L.AX_WHISPER_InitMulti(model_type.encode(), model_path.encode(), language.encode(), None, 0, max_batch)
@@ -643,14 +676,6 @@ class Whisper:
             self.h = self.L.AX_WHISPER_InitEx(model_type.encode(), model_path.encode(), language.encode(), device, max_batch)
         if not self.h:
             raise RuntimeError("AX_WHISPER_Init failed: " + (self.L.AX_WHISPER_LastError(None) or b"").decode())
-        g = lambda k: self.L.AX_WHISPER_GetConfigInt(self.h, k.encode())
-        self.n_mels, self.n_vocab, self.n_text_ctx = g("n_mels"), g("n_vocab"), g("n_text_ctx")
-        self.n_text_layer, self.n_text_state, self.eot = g("n_text_layer"), g("n_text_state"), g("eot")
-        self.sot_seq = [g(f"sot_seq{i}") for i in range(4)]
-        self.timestamp_begin = g("timestamp_begin")
-        self.no_speech = g("no_speech")
-        self.n_devices = self.L.AX_WHISPER_GetDeviceCount(self.h)
-        self._tokens_path = os.path.join(model_path, model_type, f"{model_type}-tokens.txt")
 
     def get_config_int(self, key: str) -> int:
         """AX_WHISPER_GetConfigInt: a config file key, or one of the engine's own (include/ax_whisper_api.h)."""
@@ -1699,6 +1724,20 @@ class Whisper:
         k, v = np.empty(shape, dtype=np.float32), np.empty(shape, dtype=np.float32)
         self._check(self.L.AX_WHISPER_GetCrossKV(self.h, slot, k.ctypes.data_as(fp), v.ctypes.data_as(fp)), "GetCrossKV")
         return k, v
+
+    def get_cross_kv_fp8(self, slot: int = 0):
+        """A cross_kv="fp8" handle's stored codes and scales of `slot`: (k_codes, v_codes) uint8 [n_text_layer][1500][n_text_state], raw
+        e4m3fn bytes, and scales float32 [n_text_layer][n_text_head][2][64] (K's 64, then V's); value = code * scale."""
+        shape = (self.n_text_layer, 1500, self.n_text_state)
+        k, v = np.empty(shape, dtype=np.uint8), np.empty(shape, dtype=np.uint8)
+        sc = np.empty((self.n_text_layer, self.n_text_state // 64, 2, 64), dtype=np.float32)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self.L.AX_WHISPER_GetCrossKVFp8(self.h, slot, k.ctypes.data_as(u8), v.ctypes.data_as(u8), sc.ctypes.data_as(fp)), "GetCrossKVFp8")
+        return k, v, sc
+
+    def cross_kv_quantize(self):
+        """The quantise kernel alone over every slot of a cross_kv="fp8" handle (the h16 images as they stand -> codes and scales)."""
+        self._check(self.L.AX_WHISPER_CrossKVQuantize(self.h), "CrossKVQuantize")
 
     def scan_stored16(self, batch: int = 1):
         """{buffer name: (non-finite elements, max finite |x|)} over every 16-bit tensor the engine stores between kernels."""

@@ -521,7 +521,7 @@ AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char*
   if (!h || !key || h->group.size() == 0) return INT_MIN;
   if (!strcmp(key, "n_devices")) return h->group.size();
   if (!strcmp(key, "live_hip_objects")) return (int)axw::live_owned.load();  // test hook: of every handle of the process
-  if (!strcmp(key, "persistent_giveups") || !strcmp(key, "persistent_ts_launches")) {  // counts: summed over the handle's engines
+  if (!strcmp(key, "persistent_giveups") || !strcmp(key, "persistent_ts_launches") || !strcmp(key, "cross_kv_fp8_launches")) {  // counts: summed over the handle's engines
     long sum = 0;
     for (int i = 0; i < h->group.size(); ++i) {
       Engine& e = h->group.at(i);
@@ -573,6 +573,16 @@ AX_WHISPER_API int AX_WHISPER_EncodeMel(AX_WHISPER_HANDLE handle, const float* m
 AX_WHISPER_API int AX_WHISPER_GetCrossKV(AX_WHISPER_HANDLE handle, int slot, float* k_out, float* v_out) {
   if (!handle || !k_out || !v_out) return -1;
   return guarded(handle, [&](Engine& e) { e.get_cross_kv(slot, k_out, v_out); });
+}
+
+AX_WHISPER_API int AX_WHISPER_GetCrossKVFp8(AX_WHISPER_HANDLE handle, int slot, uint8_t* k_codes, uint8_t* v_codes, float* scales) {
+  if (!handle || !k_codes || !v_codes || !scales) return -1;
+  return guarded(handle, [&](Engine& e) { e.get_cross_kv_fp8(slot, k_codes, v_codes, scales); });
+}
+
+AX_WHISPER_API int AX_WHISPER_CrossKVQuantize(AX_WHISPER_HANDLE handle) {
+  if (!handle) return -1;
+  return guarded(handle, [&](Engine& e) { e.cross_kv_quantize(); });
 }
 
 AX_WHISPER_API int AX_WHISPER_ScanStored16(AX_WHISPER_HANDLE handle, int batch, int n_max, char* names, int64_t* nonfinite,

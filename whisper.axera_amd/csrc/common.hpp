@@ -459,6 +459,36 @@ struct DecAttnParams {
 };
 void launch_decode_attention(const DecAttnParams& p, hipStream_t s);
 
+// ---- FP8 cross K/V (cross_kv_fp8.hip; decode_layout.hpp "FP8 cross K/V"): opt-in storage of the batched step's cross-attention
+// h16 cross K (blocked) and V (row-major) of `clips` clips -> e4m3fn code images and power-of-two scales, one workgroup per
+// (layer, clip, head, K or V). Clip b's images are those of slot slot_map[b] (device; nullptr: slot b), as EPI_CROSS_KV wrote them.
+struct CrossKvQuantParams {
+  const h16* k; const h16* v;              // [layer][n_slots][head] images of keys_pad keys
+  unsigned char* k8; unsigned char* v8;    // the code images, same order
+  float* scales;                           // [layer][n_slots][head][2][64]
+  const int* slot_map;
+  int n_layer, n_slots, n_head, clips;
+  int n_keys, keys_pad;                    // valid keys (<= keys_pad) and allocated keys (a multiple of 64) per (slot, head)
+};
+void launch_cross_kv_quantize(const CrossKvQuantParams& p, hipStream_t s);
+
+// single-query cross-attention over the code images: decode_attention_kernel's three query modes, split record, ticket hand-off and
+// fragment-major (hi, lo) output pair (the fields below mean what their namesakes in DecAttnParams mean)
+struct DecAttnFp8Params {
+  const float* q;
+  const unsigned char* k8; const unsigned char* v8; long kv_batch_bytes;  // this layer, the launch's first slot
+  const float* scales; long scale_batch_stride;                          // this layer, the launch's first slot: [head][2][64] per slot
+  int n_split;
+  int batch, n_head, d_model;
+  int n_keys, cap_blocks;
+  const int* done; int done_late;
+  h16* out_hi; h16* out_lo; int nbs;
+  float* mpart; unsigned* mcnt;
+  const float* x; const float* ln_w; const float* ln_b; const h16* wq; const float* bq;
+  const float* tq; const float* stat_part; const float* fold_s; const float* fold_c;
+};
+void launch_decode_cross_attention_fp8(const DecAttnFp8Params& p, hipStream_t s);
+
 // ---- batched decode (3..64 clips per launch): activations as h16 (hi, lo) pairs, MFMA GEMM (decode_gemm.hip)
 struct DecGemmParams {
   const h16* W;                           // fragment-major packed weights

@@ -36,6 +36,40 @@ AXW_LAYOUT_FN int v_index(int key, int dim) { return v_row_offset(key) + dim; }
 // transposed V of the persistent launches' own self-attention cache: [key / 64][(key % 64) / 8][dim][8 keys]
 AXW_LAYOUT_FN int vt_index(int key, int dim) { return kv_chunk_offset(key >> 6, (key >> 3) & 7, dim) + (key & 7); }
 
+// ------------------------------------------------------------------ FP8 cross K/V of one (clip, head) (cross_kv_fp8.hip; opt-in)
+// One byte per element, OCP e4m3fn (largest finite value 448, 0x7f / 0xff NaN; never the fnuz variant), with ONE power-of-two scale
+// per (layer, slot, head, K or V, head dimension): value = code * 2^e. e is the smallest integer with amax * 2^-e <= 448, amax
+// over the clip's valid keys of that dimension, taken from the exponent and mantissa fields of amax itself (448 = 1.75 * 2^8:
+// e = E - 8 where the mantissa is at most 1.75, else E - 7), kept in [kKv8ExpMin, kKv8ExpMax] so that 2^e and 2^-e are both
+// normal fp32 numbers; an all-zero channel has e = 0. x * 2^-e is exact in fp32, so a code is one round-to-nearest-even of an exact
+// value and the host reproduces it bit for bit (tests/cross_fp8_reference.py).
+//   K image  blocked [key / 64][dim / 16][key % 64][16] bytes  (lane = key: a wave's 16-byte loads of one chunk are a contiguous 1 KiB)
+//   V image  row-major [key][64] bytes
+//   scales   fp32 [layer][slot][head][K, V][64]
+// Bytes of keys at or beyond the clip's key count are code 0 in both images.
+constexpr int kKv8BlockBytes = kKvBlockKeys * kKvDim;   // 4096: one 64-key block of K or of V
+constexpr int kKv8ChunkBytes = 16 * kKvBlockKeys;       // 1024: one 16-dim chunk of a K block
+constexpr int kKv8ExpMin = -126, kKv8ExpMax = 120;
+AXW_LAYOUT_FN long kv8_head_bytes(int keys_pad) { return (long)keys_pad * kKvDim; }
+AXW_LAYOUT_FN int k8_chunk_offset(int block, int chunk, int row) { return block * kKv8BlockBytes + chunk * kKv8ChunkBytes + row * 16; }
+AXW_LAYOUT_FN int k8_index(int key, int dim) { return k8_chunk_offset(key >> 6, dim >> 4, key & 63) + (dim & 15); }
+AXW_LAYOUT_FN int v8_row_offset(int key) { return key * kKvDim; }
+AXW_LAYOUT_FN int v8_index(int key, int dim) { return v8_row_offset(key) + dim; }
+constexpr int kKv8ScaleK = 0, kKv8ScaleV = 1;
+constexpr int kKv8ScaleHead = 2 * kKvDim;               // floats of one (layer, slot, head): K's 64, then V's 64
+AXW_LAYOUT_FN long kv8_scale_index(long layer, long slot, int head, int kv, int dim, int n_slots, int n_head) {
+  return ((layer * n_slots + slot) * n_head + head) * kKv8ScaleHead + kv * kKvDim + dim;
+}
+AXW_LAYOUT_FN long kv8_scale_elems(int n_layer, int n_slots, int n_head) { return kv8_scale_index(n_layer, 0, 0, 0, 0, n_slots, n_head); }
+// the scale exponent e of a channel whose largest magnitude has the fp32 bit pattern amax_bits (sign bit clear)
+AXW_LAYOUT_FN int kv8_scale_exponent(unsigned amax_bits) {
+  if (amax_bits == 0u) return 0;
+  const int field = (int)(amax_bits >> 23), E = (field ? field : 1) - 127;
+  const int e = (amax_bits & 0x7fffffu) <= 0x600000u ? E - 8 : E - 7;
+  return e < kKv8ExpMin ? kKv8ExpMin : e > kKv8ExpMax ? kKv8ExpMax : e;
+}
+AXW_LAYOUT_FN unsigned kv8_pow2_bits(int e) { return (unsigned)(e + 127) << 23; }  // fp32 bit pattern of 2^e, e in [-126, 127]
+
 // ------------------------------------------------------------------ the persistent launches' LDS image of a cross V block
 // A row-major [64 keys][64 dims] block whose eight 16-byte chunks are permuted inside every 128-byte row: LDS slot (row R, chunk c)
 // holds the block's chunk c ^ x(R), x(R) = 2 (2 (R / 8 % 2) + R / 2 % 2). The matrix-pipe block reads the tile with transposed

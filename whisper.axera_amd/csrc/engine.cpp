@@ -158,6 +158,13 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     const char* e = getenv("AX_WHISPER_WORD_LOGPROB");
     cfg_.ints["word_logprob"] = e && !strcmp(e, "rows") ? 1 : e && !strcmp(e, "fused") ? 2 : 0;
   }
+  {  // FP8 cross K/V for the batched step (cross_kv_fp8.hip): opt-in, absent or "h16": the h16 images alone
+    const char* e = getenv("AX_WHISPER_CROSS_KV");
+    if (e && !strcmp(e, "fp8")) cross_fp8_ = true;
+    else if (e && e[0] && strcmp(e, "h16")) throw std::runtime_error(std::string("AX_WHISPER_CROSS_KV=") + e + ": expected h16 or fp8");
+    cfg_.ints["cross_kv_fp8"] = cross_fp8_ ? 1 : 0;
+    cfg_.ints["cross_kv_fp8_launches"] = 0;
+  }
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half
   install_suppress(config_suppress_);
   ensure_capacity(std::max(1, max_batch));
@@ -543,6 +550,11 @@ void Engine::ensure_capacity(int batch) {
   d_enc_part_ = (float*)A((size_t)4 * kEncPartClips * T * d * 4);  // split-K partials of the encoder's residual GEMMs (few clips only)
   d_cross_k_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(t_pad_) * 2, true);
   d_cross_v_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(t_pad_) * 2, true);
+  if (cross_fp8_) {  // half the h16 cross bytes again
+    d_cross_k8_ = (unsigned char*)A((size_t)L * B * H * layout::kv8_head_bytes(t_pad_), true);
+    d_cross_v8_ = (unsigned char*)A((size_t)L * B * H * layout::kv8_head_bytes(t_pad_), true);
+    d_cross_scales_ = (float*)A((size_t)layout::kv8_scale_elems(L, B, H) * 4, true);
+  }
   d_self_k_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
   d_self_v_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
   d_xdec_ = (float*)A((size_t)B * d * 4, true);
@@ -939,6 +951,25 @@ void Engine::run_encoder(int batch, const int* d_slot_map) {
   c.M = T; c.N = 2 * L * d; c.K = d; c.batch = batch; c.d_model = d; c.t_pad = t_pad_;
   c.n_batch_total = cap_; c.n_layer = L; c.epilogue = EPI_CROSS_KV;
   launch_gemm(c, s);
+  if (cross_fp8_) enqueue_cross_kv_quantize(batch, d_slot_map, s);
+}
+
+// FP8 cross K/V: codes and scales of `clips` clips' slots from the h16 images the epilogue above left (which stay)
+void Engine::enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s) {
+  CrossKvQuantParams q{};
+  q.k = d_cross_k_; q.v = d_cross_v_; q.k8 = d_cross_k8_; q.v8 = d_cross_v8_; q.scales = d_cross_scales_;
+  q.slot_map = d_slot_map;
+  q.n_layer = cfg_.n_text_layer; q.n_slots = cap_; q.n_head = cfg_.n_text_head; q.clips = clips;
+  q.n_keys = cfg_.n_audio_ctx; q.keys_pad = t_pad_;
+  launch_cross_kv_quantize(q, s);
+}
+
+void Engine::cross_kv_quantize() {
+  if (!cross_fp8_) throw std::runtime_error("cross_kv_quantize: the handle was not made under AX_WHISPER_CROSS_KV=fp8");
+  require_no_stream("cross_kv_quantize");
+  HIP_CHECK(hipSetDevice(device_));
+  enqueue_cross_kv_quantize(cap_, nullptr, stream());
+  HIP_CHECK(hipStreamSynchronize(stream()));
 }
 
 // ------------------------------------------------------------------------------ public entry points
@@ -971,7 +1002,7 @@ void Engine::run_tokens(const DecodeRequest& rq, const float* const* pcm, const 
   HIP_CHECK(hipEventRecord(ev_[1], s));
   run_encoder(batch);
   HIP_CHECK(hipEventRecord(ev_[2], s));
-  const int steps = greedy_loop(StepSpec{mode}, batch, rq.max_new, rq.max_new_clip, rq.ctx);
+  const int steps = greedy_loop(step_spec(mode), batch, rq.max_new, rq.max_new_clip, rq.ctx);
   fetch_ids(batch, ids, n_ids);
   // stage timings (events 3/4 are reused by the poll; bracket decode with a fresh record)
   HIP_CHECK(hipEventRecord(ev_[3], s));
@@ -1076,6 +1107,30 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
   }
 }
 
+// the slot's code images as they are stored, de-blocked to [n_text_layer][1500][d] bytes, and its scales [n_text_layer][H][2][64]
+void Engine::get_cross_kv_fp8(int slot, unsigned char* k_codes, unsigned char* v_codes, float* scales) {
+  if (!cross_fp8_) throw std::runtime_error("get_cross_kv_fp8: the handle was not made under AX_WHISPER_CROSS_KV=fp8");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  if (slot < 0 || slot >= cap_) throw std::runtime_error("slot out of range");
+  const int d = cfg_.n_text_state, H = cfg_.n_text_head, L = cfg_.n_text_layer, T = cfg_.n_audio_ctx;
+  const size_t head = (size_t)layout::kv8_head_bytes(t_pad_), per = H * head;
+  std::vector<unsigned char> hk(per), hv(per);
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  for (int l = 0; l < L; ++l) {
+    HIP_CHECK(hipMemcpy(hk.data(), d_cross_k8_ + ((size_t)l * cap_ + slot) * per, per, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(hv.data(), d_cross_v8_ + ((size_t)l * cap_ + slot) * per, per, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(scales + (size_t)l * H * layout::kKv8ScaleHead, d_cross_scales_ + layout::kv8_scale_index(l, slot, 0, 0, 0, cap_, H),
+                        (size_t)H * layout::kKv8ScaleHead * 4, hipMemcpyDeviceToHost));
+    for (int h = 0; h < H; ++h)
+      for (int t = 0; t < T; ++t)
+        for (int c = 0; c < 64; ++c) {
+          k_codes[((size_t)l * T + t) * d + h * 64 + c] = hk[h * head + layout::k8_index(t, c)];
+          v_codes[((size_t)l * T + t) * d + h * 64 + c] = hv[h * head + layout::v8_index(t, c)];
+        }
+  }
+}
+
 void Engine::decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, const int32_t* forced, int n_forced, float* logits,
                            int32_t* argmax_ids, const ForcedScores* scores, const SampleSpec* sample) {
   if (mode < kDecodePlain || mode > kDecodeSampled) throw std::runtime_error("decode_forced: unknown decode mode");
@@ -1105,7 +1160,7 @@ void Engine::decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, 
   DeviceArray<int> d_forced = device_array<int>((size_t)batch * n_forced), d_arg = device_array<int>((size_t)batch * rows), b_dec;
   DeviceArray<float> d_logits, b_lp, b_nsp, b_l0;
   if (logits) d_logits = device_array<float>((size_t)batch * rows * nv);
-  StepSpec spec{mode};
+  StepSpec spec = step_spec(mode);
   if (scored) {  // this call's own score arrays ([batch][rows]: the rules kernel's index is the history length)
     b_lp = device_array<float>((size_t)batch * rows);
     b_dec = device_array<int>((size_t)batch * rows);
@@ -1172,7 +1227,7 @@ void Engine::decode_greedy(DecodeMode mode, int batch, int max_new, const int* m
   if (batch < 1 || batch > cap_) throw std::runtime_error("decode_greedy: batch exceeds the encoded slots");
   hipStream_t s = stream();
   HIP_CHECK(hipEventRecord(ev_[2], s));
-  const int steps = greedy_loop(StepSpec{mode}, batch, max_new, max_new_clip, ClipContexts{});
+  const int steps = greedy_loop(step_spec(mode), batch, max_new, max_new_clip, ClipContexts{});
   fetch_ids(batch, ids, n_ids);
   HIP_CHECK(hipEventRecord(ev_[3], s));
   HIP_CHECK(hipEventSynchronize(ev_[3]));

@@ -103,7 +103,10 @@ struct EngineMemory {
 };
 
 struct EngineGraphs {
-  std::map<long, GraphExec> graphs_;  // key: Engine::graph_key
+  // key: Engine::graph_key; with every captured step, the fp8 cross-attention launches one replay of it runs
+  struct StepGraph { GraphExec exec; int fp8_launches = 0; };
+  struct StepGraphRef { hipGraphExec_t exec; int fp8_launches; operator hipGraphExec_t() const { return exec; } };  // what step_graph() hands out
+  std::map<long, StepGraph> graphs_;
 };
 
 // Typed pointers into slot_allocs_ (they own nothing): Engine::free_slot_buffers() resets all of them with the pool.
@@ -125,6 +128,10 @@ struct SlotViews {
        *d_attn_ = nullptr, *d_ffn_ = nullptr;
   float *d_x_ = nullptr, *d_enc_part_ = nullptr;
   h16 *d_cross_k_ = nullptr, *d_cross_v_ = nullptr, *d_self_k_ = nullptr, *d_self_v_ = nullptr;
+  // FP8 cross K/V (AX_WHISPER_CROSS_KV=fp8; decode_layout.hpp "FP8 cross K/V"): the code images [L][cap][H] and their scales, beside
+  // the h16 images; null on a default handle
+  unsigned char *d_cross_k8_ = nullptr, *d_cross_v8_ = nullptr;
+  float* d_cross_scales_ = nullptr;
   float *d_xdec_ = nullptr, *d_qdec_ = nullptr, *d_hid_ = nullptr, *d_part_self_ = nullptr, *d_part_cross_ = nullptr;
   h16 *d_act_[2] = {nullptr, nullptr}, *d_att_[2] = {nullptr, nullptr}, *d_hidp_[2] = {nullptr, nullptr};
   float* d_part_ = nullptr; float* d_amax_val_ = nullptr; int* d_amax_idx_ = nullptr;
@@ -165,6 +172,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
                 int* n_out) override;
   void encode_mel(const float* mel, int batch) override;
   void get_cross_kv(int slot, float* k_out, float* v_out) override;
+  void get_cross_kv_fp8(int slot, unsigned char* k_codes, unsigned char* v_codes, float* scales) override;
+  void cross_kv_quantize() override;
   void decode_forced(DecodeMode mode, const ClipContexts& ctx, int batch, const int32_t* forced, int n_forced, float* logits, int32_t* chosen,
                      const ForcedScores* scores, const SampleSpec* sample) override;
   void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) override;
@@ -264,7 +273,12 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     // slot stream in timestamp mode (engine_stream.cpp; kDecodeScored only): the rules launch is stream_rules_kernel and the advance
     // launch feeds every slot its own prefix from d_slot_ctx_
     bool slots = false;
+    // the cross-attention launches of a step of more than gemv_max_ clips read the FP8 code images (cross_kv_fp8.hip); set from the
+    // handle's mode by step_spec(), left clear by beam search (its spread kernel copies only the h16 images) and by the detection
+    // and step-fed context steps of engine_prefill.cpp
+    bool cross_fp8 = false;
   };
+  StepSpec step_spec(DecodeMode mode = kDecodePlain, int mask = 15) const { StepSpec sp{mode, mask}; sp.cross_fp8 = cross_fp8_; return sp; }
   // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
   // the rules kernel; first_step: the first decode step whose row is computed
   struct LogitsDump { float* rows; long stride; int first_step; };
@@ -282,13 +296,13 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   int decode_branches(int batch) const;
   void ensure_branch_streams(int batch);
   // the captured step of spec.mode / spec.mask; a scored graph writes the engine's own score arrays (spec.score_out is not read)
-  hipGraphExec_t step_graph(StepSpec spec, int batch, int max_new);
+  StepGraphRef step_graph(StepSpec spec, int batch, int max_new);
   void drop_step_graph(const StepSpec& spec, int batch, int max_new) { graphs_.erase(graph_key(spec, batch, max_new)); }
   // (two bits for the mode: plain, timestamp, scored and sampled steps are four different graphs; one for the slot stream's scored
   // step; one for "a suppress set is installed" where the graph holds a rules launch, which has the mask's pointer by value)
   long graph_key(const StepSpec& spec, int batch, int max_new) const {
     const bool suppress = spec.mode != kDecodePlain && (spec.mask & 4) && suppress_mask();
-    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 4) | (suppress ? 8 : 0) | (spec.slots ? 4 : 0) | spec.mode;
+    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 5) | (spec.cross_fp8 ? 16 : 0) | (suppress ? 8 : 0) | (spec.slots ? 4 : 0) | spec.mode;
   }
   void require_timestamp_vocab() const;
   // token suppression (DESIGN.md "Token suppression"; suppress.hpp): the handle's set as a sorted id list, what the config file
@@ -448,7 +462,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   std::vector<int> slot_state_, slot_max_new_;
   int stream_mode_ = 0;                  // of the open stream: 0 plain, 1 scored timestamp mode
   std::vector<int> slot_lang_, slot_task_, slot_detect_;  // mode 1, per slot: language index, task id, detect flag of the admitted clip
-  StepSpec stream_spec() const { StepSpec sp{}; if (stream_mode_ == 1) { sp.mode = kDecodeScored; sp.slots = true; } return sp; }
+  StepSpec stream_spec() const { StepSpec sp = step_spec(); if (stream_mode_ == 1) { sp.mode = kDecodeScored; sp.slots = true; } return sp; }
   int stream_n_prefix() const { return stream_mode_ == 1 ? 3 : 4; }
   void ensure_stream_ts();  // d_slot_ctx_ ... (SlotViews), the language id list
   StreamRulesParams stream_rules_params() const;
@@ -456,6 +470,20 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   long admit_seq_ = 0;  // admission passes of the open stream (h_admit_ring_, ev_ring_)
   void require_no_stream(const char* what) const;
   int split_self_ = 2, split_cross_ = 6;
+  // FP8 cross K/V: the handle's mode (read at construction) and the cross-attention launches that took the fp8 kernel
+  // ("cross_kv_fp8_launches"). The step sequences count what they enqueue in enq_fp8_launches_; a direct enqueue adds that to the
+  // counter when it returns (enqueue_decode_step), a capture keeps it with its graph, and every replay of the graph adds it
+  // (launch_step_graph, which all replays of a captured step go through).
+  bool cross_fp8_ = false;
+  long cross_fp8_launches_ = 0;
+  int enq_fp8_launches_ = 0;
+  bool in_step_capture_ = false;  // step_graph is capturing: what is enqueued runs at the replays
+  void note_fp8_launches(long n) { if (n) { cross_fp8_launches_ += n; cfg_.ints["cross_kv_fp8_launches"] = (int)cross_fp8_launches_; } }
+  void launch_step_graph(const StepGraphRef& g, hipStream_t s);  // hipGraphLaunch of a step_graph() exec
+  void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s);
+  // the fp8 cross-attention launch of layer l for clips [b0, b0 + nb) with a's query mode, splits and outputs
+  void launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s);
+  float bench_cross_kv_quant(int batch, int iters);
   // bench "attn_stamp": every decode_attention launch of a captured step gets a {min begin, max end} slot (DecAttnParams::stamp)
   struct StampMeta { int layer, cross, b0, nb; };
   static constexpr size_t kStampWgs = 4096, kStampLaunches = 256;

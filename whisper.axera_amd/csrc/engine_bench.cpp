@@ -101,6 +101,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
   if (what == "decode_step_beam") return bench_decode_step_beam(batch, arg, iters);
   if (what == "attn_stamp") return bench_attn_stamp(batch, arg, iters);
   if (what == "encoder") return bench_encoder(batch, iters);
+  if (what == "cross_kv_quant") return bench_cross_kv_quant(batch, iters);
   if (what == "frontend") return bench_frontend(batch, iters);
   if (what == "resample") return bench_resample(batch, arg, iters);
   if (what == "frontend_long") return bench_frontend_long(batch, arg, iters);
@@ -216,7 +217,7 @@ float Engine::bench_decode_step(const std::string& what, int batch, int arg, int
   const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored" || sampled || slots;
   if (what == "decode_step_ts") require_timestamp_vocab();
   if (what == "decode_step_ts_scored" || sampled || slots) require_scored_vocab();
-  StepSpec spec{what == "decode_step_ts" ? kDecodeTimestamps : (what == "decode_step_ts_scored" || slots) ? kDecodeScored : sampled ? kDecodeSampled : kDecodePlain};
+  StepSpec spec = step_spec(what == "decode_step_ts" ? kDecodeTimestamps : (what == "decode_step_ts_scored" || slots) ? kDecodeScored : sampled ? kDecodeSampled : kDecodePlain);
   if (slots) {
     if (cfg_.lang_tokens.empty()) throw std::runtime_error("bench stream_step_ts: the config lists no languages");
     ensure_stream_ts();
@@ -233,18 +234,18 @@ float Engine::bench_decode_step(const std::string& what, int batch, int arg, int
   hipStream_t s = stream();
   const int Tc = cfg_.n_text_ctx;
   reset_decode_state(batch);
-  hipGraphExec_t g = step_graph(spec, batch, Tc - 4);
+  const StepGraphRef g = step_graph(spec, batch, Tc - 4);
   arg = std::max(0, std::min(arg, Tc - 1 - iters));
   DecState st{arg, 0, 0, 0};
   std::vector<int> offs(batch, arg);  // every slot at position `arg`
   HIP_CHECK(hipMemcpy(d_state_, &st, sizeof(st), hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(d_off_, offs.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
-  HIP_CHECK(hipGraphLaunch(g, s));  // warm
+  launch_step_graph(g, s);  // warm
   st.step = arg;
   HIP_CHECK(hipStreamSynchronize(s));
   HIP_CHECK(hipMemcpy(d_state_, &st, sizeof(st), hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(d_off_, offs.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
-  return timed_ms(s, [&] { for (int i = 0; i < iters; ++i) HIP_CHECK(hipGraphLaunch(g, s)); });
+  return timed_ms(s, [&] { for (int i = 0; i < iters; ++i) launch_step_graph(g, s); });
 }
 
 // bench "decode_step_beam": the beam step (graph up to the logits dump + the four launches behind it) of `slots` slots in groups of
@@ -324,7 +325,7 @@ float Engine::bench_attn_stamp(int batch, int arg, int iters) {
     std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));  // an allocation (iengine.hpp)
     d_stamp_ = device_array<unsigned long long>(n_words, true);
   }
-  StepSpec spec{};
+  StepSpec spec = step_spec();
   spec.mask = 15 | 16;
   hipStream_t s = stream();
   const int Tc = cfg_.n_text_ctx;
@@ -399,6 +400,13 @@ float Engine::bench_attn_stamp(int batch, int arg, int iters) {
 float Engine::bench_encoder(int batch, int iters) {
   run_encoder(batch);
   return timed_ms(stream(), [&] { for (int i = 0; i < iters; ++i) run_encoder(batch); });
+}
+
+// the quantise kernel alone over `batch` slots' h16 cross K/V as it stands (an fp8 handle only)
+float Engine::bench_cross_kv_quant(int batch, int iters) {
+  if (!cross_fp8_) throw std::runtime_error("bench cross_kv_quant: the handle was not made under AX_WHISPER_CROSS_KV=fp8");
+  enqueue_cross_kv_quantize(batch, nullptr, stream());
+  return timed_ms(stream(), [&] { for (int i = 0; i < iters; ++i) enqueue_cross_kv_quantize(batch, nullptr, stream()); });
 }
 
 float Engine::bench_frontend(int batch, int iters) {

@@ -36,7 +36,9 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
   // 3+ clips: the clip-block sequence (a 4-clip step: 0.78 ms through the GEMV family, 0.59 through clip-block GEMMs);
   // one clip that cannot use the persistent launch and two clips that cannot either stay on the GEMV family
   if (batch > gemv_max_) {
+    const int fp8_before = enq_fp8_launches_;
     enqueue_decode_step_batched(spec, batch, max_new, d_forced, n_forced, d_logits, logits_stride, d_argmax);
+    if (!in_step_capture_) note_fp8_launches(enq_fp8_launches_ - fp8_before);  // enqueued directly: these launches run once
     return;
   }
 
@@ -149,6 +151,33 @@ DecAttnParams Engine::attn_params(const float* q, const h16* k, const h16* v, lo
   return a;
 }
 
+// The cross-attention launch `a` describes (its query mode, splits, done flags and outputs), over the FP8 code images of layer l,
+// clips [b0, b0 + nb) instead of the h16 ones
+void Engine::launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s) {
+  const int H = cfg_.n_text_head;
+  const long slot_bytes = H * layout::kv8_head_bytes(t_pad_);
+  DecAttnFp8Params f{};
+  f.q = a.q;
+  f.k8 = d_cross_k8_ + ((size_t)l * cap_ + b0) * slot_bytes;
+  f.v8 = d_cross_v8_ + ((size_t)l * cap_ + b0) * slot_bytes;
+  f.kv_batch_bytes = slot_bytes;
+  f.scales = d_cross_scales_ + layout::kv8_scale_index(l, b0, 0, 0, 0, cap_, H);
+  f.scale_batch_stride = (long)H * layout::kKv8ScaleHead;
+  f.n_split = a.n_split; f.batch = a.batch; f.n_head = a.n_head; f.d_model = a.d_model; f.n_keys = a.n_keys; f.cap_blocks = a.cap_blocks;
+  f.done = a.done; f.done_late = a.done_late;
+  f.out_hi = a.out_hi; f.out_lo = a.out_lo; f.nbs = a.nbs; f.mpart = a.mpart; f.mcnt = a.mcnt;
+  f.x = a.x; f.ln_w = a.ln_w; f.ln_b = a.ln_b; f.wq = a.wq; f.bq = a.bq;
+  f.tq = a.tq; f.stat_part = a.stat_part; f.fold_s = a.fold_s; f.fold_c = a.fold_c;
+  launch_decode_cross_attention_fp8(f, s);
+  ++enq_fp8_launches_;
+}
+
+// a step_graph() exec on the stream; its fp8 cross-attention launches are counted per replay
+void Engine::launch_step_graph(const StepGraphRef& g, hipStream_t s) {
+  HIP_CHECK(hipGraphLaunch(g.exec, s));
+  note_fp8_launches(g.fp8_launches);
+}
+
 // bench "attn_stamp" (StepSpec::mask bit 16): the next {min begin, max end} slot, with what the launch is
 unsigned long long* Engine::next_stamp(const StepSpec& spec, int layer, int cross, int b0, int nb) {
   if (!(spec.mask & 16) || !d_stamp_) return nullptr;
@@ -211,6 +240,12 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
     a.out_hi = att_hi; a.out_lo = att_lo; a.nbs = nbs_;
     return a;
   };
+  // a cross-attention launch: over the FP8 code images where the step asks for them (stamped measurement steps keep the h16 kernel,
+  // the only one that carries stamp code)
+  auto cross = [&](const DecAttnParams& a, int l) {
+    if (spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, b0, s);
+    else launch_decode_attention(a, s);
+  };
   const int n_blk = (nb + 15) / 16;
   // two row tiles per workgroup where one would make more workgroups than can be resident at once
   // (fewer, fatter workgroups at few clips — two row tiles from 100 or from 40 workgroups on — measured 2 % slower at 4 and 8 clips)
@@ -251,7 +286,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
       a.mcnt = d_attn_mcnt_ + (long)b0 * H;
       a.tq = a0; a.stat_part = statp; a.fold_s = cfold_[l].s; a.fold_c = cfold_[l].c;
       a.stamp = next_stamp(spec, l, 1, b0, nb);
-      if (spec.mask & 2) launch_decode_attention(a, s);
+      if (spec.mask & 2) cross(a, l);
     } else if (fuse_cq && d <= 1024) {  // the cross-attention workgroups project their own queries (decode_attention_kernel<1>)
       DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64);
       a.q = nullptr;
@@ -260,12 +295,12 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
       a.mcnt = d_attn_mcnt_ + (long)b0 * H;
       a.x = x; a.ln_w = w.cross_ln_w; a.ln_b = w.cross_ln_b; a.wq = w.w_cq; a.bq = w.b_cq;
       a.stamp = next_stamp(spec, l, 1, b0, nb);
-      if (spec.mask & 2) launch_decode_attention(a, s);
+      if (spec.mask & 2) cross(a, l);
     } else {
       c = cgemm(wq.w_cq, w.b_cq, d, d, GEPI_STORE, 1);
       c.x = x; c.ln_w = w.cross_ln_w; c.ln_b = w.cross_ln_b; c.out = qd;
       cgo(c, 7);
-      if (spec.mask & 2) { DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64); a.stamp = next_stamp(spec, l, 1, b0, nb); launch_decode_attention(a, s); }
+      if (spec.mask & 2) { DecAttnParams a = attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64); a.stamp = next_stamp(spec, l, 1, b0, nb); cross(a, l); }
     }
     c = cgemm(wq.w_co, w.b_co, d, d, GEPI_RESID, 1);
     c.a_hi = att_hi; c.a_lo = att_lo; c.out = x;
@@ -348,8 +383,7 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     pend_n = p.ksplit;
     pend_bias = bias;
   };
-  int stamp_layer = 0;
-  auto attn = [&](const h16* kc, const h16* vc, long stride, int n_keys, int cap_blocks) {
+  auto attn = [&](int l, const h16* kc, const h16* vc, long stride, int n_keys, int cap_blocks) {
     DecAttnParams a = attn_params(d_qdec_, kc, vc, stride, n_keys, cap_blocks, 0, batch, d_forced != nullptr);
     a.out_hi = d_att_[0]; a.out_lo = d_att_[1]; a.nbs = nbs_;
     if (n_keys >= 0) {  // cross-attention: few (clip, head) pairs leave CUs with one workgroup beside CUs with two (turbo, 16 clips: 320)
@@ -361,8 +395,10 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
       a.mpart = d_attn_mpart_;
       a.mcnt = d_attn_mcnt_;
     }
-    a.stamp = next_stamp(spec, stamp_layer, n_keys >= 0 ? 1 : 0, 0, batch);
-    if (spec.mask & 2) launch_decode_attention(a, s);
+    a.stamp = next_stamp(spec, l, n_keys >= 0 ? 1 : 0, 0, batch);
+    if (!(spec.mask & 2)) return;
+    if (n_keys >= 0 && spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, 0, s);
+    else launch_decode_attention(a, s);
   };
   auto base = [&](const h16* W, const float* bias, int N, int K, const h16* ahi, const h16* alo, int epi) {
     DecGemmParams p{};
@@ -396,7 +432,6 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     }
   }
   for (int l = 0; l < L && !batched_ln_; ++l) {
-    stamp_layer = l;
     const DecLayerW& w = dec_[l];
     h16* sk = d_self_k_ + (size_t)l * cap_ * self_stride;
     h16* sv = d_self_v_ + (size_t)l * cap_ * self_stride;
@@ -407,13 +442,13 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     DecGemmParams p = base(wp.w_qkv, w.b_qkv, 3 * d, d, d_act_[0], d_act_[1], GEPI_QKV_CACHE);
     p.out = d_qdec_; p.k_cache = sk; p.v_cache = sv; p.kv_batch_stride = self_stride;
     gemm(p, [&](DecGemmParams& q, int b0) { q.out += (long)b0 * d; q.k_cache += b0 * self_stride; q.v_cache += b0 * self_stride; });
-    attn(sk, sv, self_stride, -1, Tc / 64);
+    attn(l, sk, sv, self_stride, -1, Tc / 64);
     resid(wp.w_o, w.b_o, d, d_att_[0], d_att_[1]);
     ln(w.cross_ln_w, w.cross_ln_b);
     p = base(wp.w_cq, w.b_cq, d, d, d_act_[0], d_act_[1], GEPI_STORE);
     p.out = d_qdec_;
     gemm(p, [&](DecGemmParams& q, int b0) { q.out += (long)b0 * d; });
-    attn(ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64);
+    attn(l, ck, cv, cross_stride, cfg_.n_audio_ctx, t_pad_ / 64);
     resid(wp.w_co, w.b_co, d, d_att_[0], d_att_[1]);
     ln(w.mlp_ln_w, w.mlp_ln_b);
     p = base(wp.w_fc1, w.b_fc1, 4 * d, d, d_act_[0], d_act_[1], GEPI_GELU);
@@ -490,10 +525,10 @@ void Engine::ensure_branch_streams(int batch) {
     if (!branch_stream_[i]) branch_stream_[i] = make_stream();
 }
 
-hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
+Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
   const long key = graph_key(spec, batch, max_new);  // plain and timestamp-mode steps are different graphs
   auto it = graphs_.find(key);
-  if (it != graphs_.end()) return it->second;
+  if (it != graphs_.end()) return {it->second.exec, it->second.fp8_launches};
   hipStream_t s = stream();
   // nobody on this device allocates, copies synchronously or captures while this capture is open (iengine.hpp)
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
@@ -503,6 +538,8 @@ hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
   HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   hipError_t cap_err = hipSuccess;
   hipGraph_t captured = nullptr;
+  const ScopedSet<bool> capturing(in_step_capture_, true);  // what the capture enqueues has not run: it is counted per replay
+  enq_fp8_launches_ = 0;
   try {
     enqueue_decode_step(spec, batch, max_new, nullptr, 0, nullptr, 0, nullptr);
     cap_err = hipStreamEndCapture(s, &captured);
@@ -544,7 +581,8 @@ hipGraphExec_t Engine::step_graph(StepSpec spec, int batch, int max_new) {
       cfg_.ints["graph_queue_aligned"] = aligned ? 1 : 0;
     }
   }
-  return graphs_[key] = std::move(exec);
+  StepGraph& kept = graphs_[key] = StepGraph{std::move(exec), enq_fp8_launches_};
+  return {kept.exec, kept.fp8_launches};
 }
 
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.
@@ -584,7 +622,7 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
     if (b == batch) { persistent_succeeded(); return steps; }
     persistent_gave_up();  // these utterances (and the next few) take the launch-per-phase path
   }
-  hipGraphExec_t g = step_graph(spec, batch, max_new);  // (a fresh multi-branch graph is probed with replays: before the state is set)
+  const StepGraphRef g = step_graph(spec, batch, max_new);  // (a fresh multi-branch graph is probed with replays: before the state is set)
   reset_decode_state(batch, max_new_clip);
   if (ctx.any()) prefill_prompts(batch, ctx, false, spec.mode >= kDecodeScored);  // slots behind a context: it is cached, the task id next
   hipStream_t s = stream();
@@ -593,7 +631,7 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
   hipEvent_t pe[2] = {ev_[3], ev_[4]};
   int steps = 0, polls = 0;
   for (int st = 0; st < total; ++st) {
-    HIP_CHECK(hipGraphLaunch(g, s));
+    launch_step_graph(g, s);
     ++steps;
     if ((st + 1) % kPoll == 0 && st >= 4) {
       if (polls >= 1) {  // look at the poll issued kPoll steps ago (keeps the queue full)

@@ -178,7 +178,7 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
   for (int a = 0; a < n_attempts && fallback; ++a)
     if (!(opts->temperatures[a] >= 0.f) || std::isinf(opts->temperatures[a]) || (opts->temperatures[a] > 0.f && opts->temperatures[a] < 1e-6f))
       throw std::runtime_error("long-form: temperatures must be 0, or finite and >= 1e-6");
-  const StepSpec spec{fallback ? kDecodeSampled : opts ? kDecodeScored : kDecodeTimestamps};
+  const StepSpec spec = step_spec(fallback ? kDecodeSampled : opts ? kDecodeScored : kDecodeTimestamps);
   // the language every file decodes under (-2: still to be detected) and its task
   std::vector<int> file_lang(per_lang ? n_files : 0, -1), file_task(per_lang ? n_files : 0, 0);
   if (per_lang) {
@@ -557,7 +557,7 @@ void Engine::run_long_chunked(const float* const* pcm, const int* n_samples, int
   require_timestamp_vocab();
   if (opts.scored) require_scored_vocab();
   const bool per_lang = !opts.file_lang.empty() || !opts.file_task.empty();
-  const StepSpec spec{opts.scored ? kDecodeScored : kDecodeTimestamps};
+  const StepSpec spec = step_spec(opts.scored ? kDecodeScored : kDecodeTimestamps);
   std::vector<int> file_lang(per_lang ? n_files : 0, -1), file_task(per_lang ? n_files : 0, 0);
   if (per_lang) {
     for (int f = 0; f < n_files; ++f) {

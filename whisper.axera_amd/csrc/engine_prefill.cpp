@@ -276,7 +276,7 @@ void Engine::enqueue_detect_prefill(int batch, const std::vector<int>& slot, int
   HIP_CHECK(hipMemcpyAsync(pf.det_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipStreamSynchronize(s));  // (pageable source)
   ensure_branch_streams(batch);
-  StepSpec spec{kDecodePlain};
+  StepSpec spec{kDecodePlain};  // (cross_fp8 clear: detection and the step-fed contexts read the h16 cross K/V, as the prefill kernels do)
   spec.mask = 15 & ~4;  // no advance: offsets and tokens stay, x keeps the final residual
   spec.feed = 1;        // no vocabulary projection
   enqueue_decode_step(spec, batch, cfg_.n_text_ctx, nullptr, 0, nullptr, 0, nullptr);
@@ -309,7 +309,7 @@ void Engine::detect_step_fed(int batch, const std::vector<int>& slot, int* idx, 
   HIP_CHECK(hipMemcpyAsync(d_forced, forced.data(), (size_t)batch * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipStreamSynchronize(s));  // (pageable source)
   ensure_branch_streams(batch);
-  StepSpec spec{kDecodePlain};
+  StepSpec spec{kDecodePlain};  // (cross_fp8 clear: detection and the step-fed contexts read the h16 cross K/V, as the prefill kernels do)
   spec.feed = 2;
   enqueue_decode_step(spec, batch, cfg_.n_text_ctx, d_forced, 1, nullptr, 0, nullptr);
   std::vector<float> row(nv);
@@ -446,7 +446,7 @@ void Engine::prefill_step_fed(int batch, const std::vector<int>& slot, const std
   HIP_CHECK(hipStreamSynchronize(s));  // (pageable sources)
   ensure_branch_streams(batch);
   for (int st = 0; st < max_len; ++st) {
-    StepSpec spec{kDecodePlain};
+    StepSpec spec{kDecodePlain};  // (cross_fp8 clear: detection and the step-fed contexts read the h16 cross K/V, as the prefill kernels do)
     spec.feed = 1;
     for (int c = 0; want_no_speech && c < n; ++c)
       if (len[c] - 2 == st) spec.feed = 2;  // the position of sot: P + 1

@@ -201,7 +201,7 @@ int Engine::stream_step(int n_steps, int* finished_slots) {
       ++active;
     }
   };
-  hipGraphExec_t g = step_graph(stream_spec(), n, cfg_.n_text_ctx - stream_n_prefix());  // the graph stream_open captured
+  const StepGraphRef g = step_graph(stream_spec(), n, cfg_.n_text_ctx - stream_n_prefix());  // the graph stream_open captured
   // The host runs two steps ahead of the device (it waits for step k-2 before it enqueues step k): the queue never runs dry,
   // and what the host sees in the flags is at most two steps old, so a waiting clip takes a freed slot within two steps.
   for (int st = 0; st < std::max(1, n_steps); ++st) {
@@ -209,7 +209,7 @@ int Engine::stream_step(int n_steps, int* finished_slots) {
     harvest();
     activate_ready();
     if (n_in(kActive) == 0) break;  // nothing decodes and nothing is ready: a step would be the GEMM chain for nobody
-    HIP_CHECK(hipGraphLaunch(g, s));
+    launch_step_graph(g, s);
     HIP_CHECK(hipEventRecord(ev_step_[step_seq_ % 3], s));
     ++step_seq_;
   }

@@ -102,6 +102,10 @@ class IEngine {
                         int* n_out) = 0;
   virtual void encode_mel(const float* mel, int batch) = 0;
   virtual void get_cross_kv(int slot, float* k_out, float* v_out) = 0;
+  // FP8 cross K/V (a handle made under AX_WHISPER_CROSS_KV=fp8; throws on another): the slot's codes de-blocked to [L][n_audio_ctx][d]
+  // bytes and its scales [L][H][2][64]; the quantise kernel alone on every slot of the handle
+  virtual void get_cross_kv_fp8(int slot, unsigned char* k_codes, unsigned char* v_codes, float* scales) = 0;
+  virtual void cross_kv_quantize() = 0;
   // the slot's self-attention cache rows [0, n_rows), de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][d]
   virtual void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) = 0;
   // the self-attention cache of clip `clip` (1 or 2: its position in the last multi-clip persistent launch), all 8 blocks x 64 keys

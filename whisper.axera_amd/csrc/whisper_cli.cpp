@@ -58,6 +58,8 @@ static void usage(const char* prog) {
           "                      duration behind RTF: is the file's real one. Without the flag nothing changes: such a file is fed\n"
           "                      as it is, with a warning, and its duration is counted at 16000 Hz\n"
           "      --task T        transcribe or translate (with --timestamps or --long, not with --beam_size) [=transcribe]\n"
+          "      --cross_kv h16|fp8   fp8: keep the cross K/V as e4m3fn codes too; decoder steps of more than two clips read them\n"
+          "                      (opt-in, results differ from h16; not under --beam_size)\n"
           "      --suppress_tokens -1|1,2,3   (with --timestamps or --long) ids the decode never samples, as openai-whisper's\n"
           "                      suppress_tokens: -1 the non-speech ids of the model's tokens file (brackets, quotes, musical signs),\n"
           "                      or a list; replaces what the config file's \"suppress_tokens\" gave\n"
@@ -413,7 +415,7 @@ int main(int argc, char** argv) {
   bool timestamps = false, longform = false, word_timestamps = false;
   bool condition = false, detect = false, chunked = false;
   std::string task_arg, cmax_arg, cmin_arg, csmooth_arg;
-  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg, suppress_arg;
+  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg, suppress_arg, cross_kv_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -431,7 +433,7 @@ int main(int argc, char** argv) {
         val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg) ||
         val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg) || val("task", nullptr, task_arg) ||
         val("chunk_max_s", nullptr, cmax_arg) || val("chunk_min_s", nullptr, cmin_arg) || val("chunk_smooth_ms", nullptr, csmooth_arg) ||
-        val("suppress_tokens", nullptr, suppress_arg))
+        val("suppress_tokens", nullptr, suppress_arg) || val("cross_kv", nullptr, cross_kv_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -446,6 +448,8 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (wav.empty()) { fprintf(stderr, "need option: --wav\n"); usage(argv[0]); return 1; }
+  // --cross_kv h16 | fp8: the library reads the mode from AX_WHISPER_CROSS_KV when the handle is made (a bad value fails Init)
+  if (!cross_kv_arg.empty()) setenv("AX_WHISPER_CROSS_KV", cross_kv_arg.c_str(), 1);
   int beam_size = 1;
   if (!beam_arg.empty()) {
     char* end = nullptr;

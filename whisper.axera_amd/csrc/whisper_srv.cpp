@@ -435,7 +435,7 @@ static void serve(int fd) {
 
 int main(int argc, char** argv) {
   int port = 8080, max_batch = 64, wait_ms = 5, steps_per_call = 8, max_body_mb = 16, min_admit = 1, admit_wait_ms = 20;
-  std::string model_type = "turbo", model_path = "../models-mi355x", language = "zh", devices, scheduler = "slots", suppress_arg;
+  std::string model_type = "turbo", model_path = "../models-mi355x", language = "zh", devices, scheduler = "slots", suppress_arg, cross_kv_arg;
   bool timestamps = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -451,6 +451,7 @@ int main(int argc, char** argv) {
     if (val("batch_wait_ms", nullptr, v)) { wait_ms = std::max(0, atoi(v.c_str())); continue; }
     if (val("model_type", "-t", model_type) || val("model_path", "-p", model_path) || val("language", "-l", language)) continue;
     if (val("devices", nullptr, devices) || val("scheduler", nullptr, scheduler) || val("suppress_tokens", nullptr, suppress_arg)) continue;
+    if (val("cross_kv", nullptr, cross_kv_arg)) continue;
     if (a == "--timestamps") { timestamps = true; continue; }
     if (val("steps_per_call", nullptr, v)) { steps_per_call = std::max(1, atoi(v.c_str())); continue; }
     if (val("min_admit", nullptr, v)) { min_admit = std::max(1, atoi(v.c_str())); continue; }
@@ -459,13 +460,15 @@ int main(int argc, char** argv) {
     if (val("max_body_mb", nullptr, v)) { max_body_mb = std::max(1, atoi(v.c_str())); continue; }
     if (val("recv_timeout_s", nullptr, v)) { g_recv_timeout_s = std::max(1, atoi(v.c_str())); continue; }
     fprintf(stderr, "usage: %s [--port 8080] [-t model_type] [-p model_path] [-l language] [--max_batch 64] [--batch_wait_ms 5] [--devices all|0,1,..]\n"
-                    "          [--scheduler slots|batches] [--timestamps] [--suppress_tokens -1|1,2,3] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
+                    "          [--scheduler slots|batches] [--timestamps] [--cross_kv h16|fp8] [--suppress_tokens -1|1,2,3] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
     return a == "--help" || a == "-?" ? 0 : 1;
   }
   printf("port: %d\n", port);
   printf("model_path: %s\n", model_path.c_str());
   printf("model_type: %s\n", model_type.c_str());
   printf("language: %s\n", language.c_str());
+  // --cross_kv h16 | fp8: the library reads the mode from AX_WHISPER_CROSS_KV when a handle is made (a bad value fails Init)
+  if (!cross_kv_arg.empty()) { setenv("AX_WHISPER_CROSS_KV", cross_kv_arg.c_str(), 1); printf("cross_kv: %s\n", cross_kv_arg.c_str()); }
   if (timestamps && scheduler == "batches") { printf("--timestamps needs --scheduler slots (micro-batches decode in plain mode)\n"); return 1; }
   // --suppress_tokens -1 | 1,2,3 (with --timestamps: plain mode is not filtered; suppress_flag.hpp)
   std::vector<int> suppress_ids;
