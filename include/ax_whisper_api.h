@@ -137,6 +137,12 @@ AX_WHISPER_API int AX_WHISPER_GetCrossKV(AX_WHISPER_HANDLE handle, int slot, flo
  *  Both return -1 on a handle without the mode. */
 AX_WHISPER_API int AX_WHISPER_GetCrossKVFp8(AX_WHISPER_HANDLE handle, int slot, uint8_t* k_codes, uint8_t* v_codes, float* scales);
 AX_WHISPER_API int AX_WHISPER_CrossKVQuantize(AX_WHISPER_HANDLE handle);
+/* Shared cross K/V under beam search (opt-in; a mode of Init, read through AX_WHISPER_GetConfigInt): on a handle made while the environment variable AX_WHISPER_BEAM_CROSS is "shared", the
+ *  K hypotheses of a clip read ONE cross K/V copy, the clip's own, through a grouped cross-attention kernel, in beam calls of more
+ *  than two slots with K > 1 (an FP8 cross K/V handle keeps the copies). Absent or "copy": today's behaviour, a copy per hypothesis;
+ *  any other value fails Init with an error text. A beam's logits differ from the copy path's in their last bits (another summation
+ *  order). AX_WHISPER_GetConfigInt: "beam_cross_shared" (0 / 1), "beam_cross_shared_launches" (cross-attention launches that took
+ *  the grouped kernel). */
 /** Parity aid: scan every 16-bit tensor the engine keeps between kernels (encoder activations of clips 0..batch-1, cross and
  *  self K/V caches, the decoder's activation pairs) after EncodeMel / Decode*: names [n_max][32] chars, nonfinite [n_max]
  *  (NaN or Inf elements), maxabs [n_max] (largest finite |x|), *n_out buffers reported. A trained model's outlier channels

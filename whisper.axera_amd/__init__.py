@@ -635,27 +635,32 @@ class Whisper:
     """Mirror of the reference's ``Whisper`` (python/whisper.py:54-99, cpp/src/Whisper.hpp:28-59)."""
 
     def __init__(self, model_type: str, model_path: str, language: str = "zh", device: int = -1, max_batch: int = 0, devices=None,
-                 cross_kv: str | None = None):
+                 cross_kv: str | None = None, beam_cross: str | None = None):
         """devices: a list of HIP ordinals (or "all") -> one engine per device behind this handle (AX_WHISPER_InitMulti).
         cross_kv: "fp8" keeps the cross K/V as e4m3fn codes too and lets decoder steps of more than two clips read them (opt-in;
-        DESIGN.md "FP8 cross K/V"); "h16" or None: the h16 images alone. The library reads the mode from AX_WHISPER_CROSS_KV while
-        the handle is made: the variable is set for that call and put back afterwards, under a lock that every construction with a
-        cross_kv argument takes (a handle made at the same moment on another thread WITHOUT the argument, or by other code through
-        the C ABI, reads whatever the variable holds then)."""
+        DESIGN.md "FP8 cross K/V"); "h16" or None: the h16 images alone.
+        beam_cross: "shared" lets the K hypotheses of a clip under beam search read ONE cross K/V copy, the clip's own (opt-in;
+        DESIGN.md "Shared cross K/V"); "copy" or None: a copy per hypothesis.
+        The library reads both modes from AX_WHISPER_CROSS_KV / AX_WHISPER_BEAM_CROSS while the handle is made: the variables are
+        set for that call and put back afterwards, under a lock that every construction with such an argument takes (a handle made
+        at the same moment on another thread WITHOUT the arguments, or by other code through the C ABI, reads whatever the variables
+        hold then)."""
         self.L = load_library()
-        if cross_kv is None:
+        modes = {k: str(v) for k, v in (("AX_WHISPER_CROSS_KV", cross_kv), ("AX_WHISPER_BEAM_CROSS", beam_cross)) if v is not None}
+        if not modes:
             self._init_handle(model_type, model_path, language, device, max_batch, devices)
         else:
             with _cross_kv_env_lock:
-                before = os.environ.get("AX_WHISPER_CROSS_KV")
-                os.environ["AX_WHISPER_CROSS_KV"] = str(cross_kv)
+                before = {k: os.environ.get(k) for k in modes}
+                os.environ.update(modes)
                 try:
                     self._init_handle(model_type, model_path, language, device, max_batch, devices)
                 finally:
-                    if before is None:
-                        del os.environ["AX_WHISPER_CROSS_KV"]
-                    else:
-                        os.environ["AX_WHISPER_CROSS_KV"] = before
+                    for k, v in before.items():
+                        if v is None:
+                            del os.environ[k]
+                        else:
+                            os.environ[k] = v
         g = lambda k: self.L.AX_WHISPER_GetConfigInt(self.h, k.encode())
         self.n_mels, self.n_vocab, self.n_text_ctx = g("n_mels"), g("n_vocab"), g("n_text_ctx")
         self.n_text_layer, self.n_text_state, self.eot = g("n_text_layer"), g("n_text_state"), g("eot")

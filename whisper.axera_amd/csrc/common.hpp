@@ -489,6 +489,29 @@ struct DecAttnFp8Params {
 };
 void launch_decode_cross_attention_fp8(const DecAttnFp8Params& p, hipStream_t s);
 
+// ---- grouped cross-attention (decode_attention_group.hip; beam search with one cross K/V copy per clip): the slots
+// [c * group, c * group + group) are the hypotheses ("ranks") of clip c and all attend over the K/V of slot c, where the encoder put
+// it. One workgroup per (split, head, clip) serves the clip's ranks that lie inside the launch's slot range [slot0, slot0 + nslots):
+// it reads their queries and writes their outputs / split records, and nothing of a slot outside the range. The three query modes,
+// the split record, the ticket hand-off and the fragment-major (hi, lo) output pair are decode_attention_kernel's, per rank.
+struct DecAttnGroupParams {
+  const h16* k; const h16* v; long kv_slot_stride;  // this layer, slot 0 of the HANDLE (a clip's K/V may lie outside the slot range)
+  int group;                                        // ranks per clip, 1 .. 8
+  int slot0, nslots;                                // the launch's slots; slot0 is a multiple of 16
+  // everything below has the origin of slot0 (DecAttnParams: "same clip origin as q / out") and means what its namesake means there
+  const float* q;
+  int n_split, n_head, d_model;
+  int n_keys, cap_blocks;
+  const int* done; int done_late;
+  h16* out_hi; h16* out_lo; int nbs;
+  float* mpart; unsigned* mcnt;                     // the ticket of a group is the counter of its first rank inside the range
+  const float* x; const float* ln_w; const float* ln_b; const h16* wq; const float* bq;
+  const float* tq; const float* stat_part; const float* fold_s; const float* fold_c;
+};
+void launch_decode_cross_attention_group(const DecAttnGroupParams& p, hipStream_t s);
+// clips with at least one rank in [slot0, slot0 + nslots): the launch's grid.z
+inline int cross_group_clips(int slot0, int nslots, int group) { return (slot0 + nslots - 1) / group - slot0 / group + 1; }
+
 // ---- batched decode (3..64 clips per launch): activations as h16 (hi, lo) pairs, MFMA GEMM (decode_gemm.hip)
 struct DecGemmParams {
   const h16* W;                           // fragment-major packed weights

@@ -165,6 +165,13 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     cfg_.ints["cross_kv_fp8"] = cross_fp8_ ? 1 : 0;
     cfg_.ints["cross_kv_fp8_launches"] = 0;
   }
+  {  // beam search over one cross K/V copy per clip (decode_attention_group.hip): opt-in, absent or "copy": a copy per hypothesis
+    const char* e = getenv("AX_WHISPER_BEAM_CROSS");
+    if (e && !strcmp(e, "shared")) beam_cross_shared_ = true;
+    else if (e && e[0] && strcmp(e, "copy")) throw std::runtime_error(std::string("AX_WHISPER_BEAM_CROSS=") + e + ": expected copy or shared");
+    cfg_.ints["beam_cross_shared"] = beam_cross_shared_ ? 1 : 0;
+    cfg_.ints["beam_cross_shared_launches"] = 0;
+  }
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half
   install_suppress(config_suppress_);
   ensure_capacity(std::max(1, max_batch));

@@ -104,8 +104,9 @@ struct EngineMemory {
 
 struct EngineGraphs {
   // key: Engine::graph_key; with every captured step, the fp8 cross-attention launches one replay of it runs
-  struct StepGraph { GraphExec exec; int fp8_launches = 0; };
-  struct StepGraphRef { hipGraphExec_t exec; int fp8_launches; operator hipGraphExec_t() const { return exec; } };  // what step_graph() hands out
+  // and the grouped ones (beam search with a shared cross K/V)
+  struct StepGraph { GraphExec exec; int fp8_launches = 0; int group_launches = 0; };
+  struct StepGraphRef { hipGraphExec_t exec; int fp8_launches; int group_launches; operator hipGraphExec_t() const { return exec; } };  // what step_graph() hands out
   std::map<long, StepGraph> graphs_;
 };
 
@@ -277,6 +278,10 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     // handle's mode by step_spec(), left clear by beam search (its spread kernel copies only the h16 images) and by the detection
     // and step-fed context steps of engine_prefill.cpp
     bool cross_fp8 = false;
+    // beam search with ONE cross K/V copy per clip (decode_attention_group.hip): the slots [c K, c K + K) are the ranks of clip c and
+    // the cross-attention launches of a step of more than gemv_max_ slots read slot c's K/V for all of them; K here, 0: every slot its
+    // own. Set by beam_loop alone, on a handle made under AX_WHISPER_BEAM_CROSS=shared.
+    int cross_group = 0;
   };
   StepSpec step_spec(DecodeMode mode = kDecodePlain, int mask = 15) const { StepSpec sp{mode, mask}; sp.cross_fp8 = cross_fp8_; return sp; }
   // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
@@ -302,7 +307,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // step; one for "a suppress set is installed" where the graph holds a rules launch, which has the mask's pointer by value)
   long graph_key(const StepSpec& spec, int batch, int max_new) const {
     const bool suppress = spec.mode != kDecodePlain && (spec.mask & 4) && suppress_mask();
-    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 5) | (spec.cross_fp8 ? 16 : 0) | (suppress ? 8 : 0) | (spec.slots ? 4 : 0) | spec.mode;
+    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 9) | ((long)spec.cross_group << 5) | (spec.cross_fp8 ? 16 : 0) | (suppress ? 8 : 0) |
+           (spec.slots ? 4 : 0) | spec.mode;
   }
   void require_timestamp_vocab() const;
   // token suppression (DESIGN.md "Token suppression"; suppress.hpp): the handle's set as a sorted id list, what the config file
@@ -480,6 +486,16 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   bool in_step_capture_ = false;  // step_graph is capturing: what is enqueued runs at the replays
   void note_fp8_launches(long n) { if (n) { cross_fp8_launches_ += n; cfg_.ints["cross_kv_fp8_launches"] = (int)cross_fp8_launches_; } }
   void launch_step_graph(const StepGraphRef& g, hipStream_t s);  // hipGraphLaunch of a step_graph() exec
+  // Shared cross K/V under beam search: the handle's mode (AX_WHISPER_BEAM_CROSS, read at construction) and the cross-attention
+  // launches that took the grouped kernel ("beam_cross_shared_launches"), counted as the fp8 launches are
+  bool beam_cross_shared_ = false;
+  long cross_group_launches_ = 0;
+  int enq_group_launches_ = 0;
+  void note_group_launches(long n) { if (n) { cross_group_launches_ += n; cfg_.ints["beam_cross_shared_launches"] = (int)cross_group_launches_; } }
+  // the grouped cross-attention launch of layer l for slots [b0, b0 + nb) in groups of K, with a's query mode, splits and outputs
+  void launch_cross_attention_group(const DecAttnParams& a, int l, int b0, int K, hipStream_t s);
+  // the group size a beam call of clips x K hypotheses runs its step with (0: the copy path)
+  int beam_cross_group(int clips, int K) const { return beam_cross_shared_ && !cross_fp8_ && K > 1 && clips * K > gemv_max_ ? K : 0; }
   void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s);
   // the fp8 cross-attention launch of layer l for clips [b0, b0 + nb) with a's query mode, splits and outputs
   void launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s);

@@ -108,9 +108,13 @@ int Engine::beam_loop(int clips, int K, int max_new, const BeamResult& out, floa
   if (max_new <= 0 || max_new > Tc - 3) max_new = Tc - 3;
   hipStream_t s = stream();
   // layers + the logits dump from offset 0 on; asked for BEFORE the decode state is set up (step_graph)
-  hipGraphExec_t g = step_graph(StepSpec{kDecodeScored, 11}, slots, max_new);
+  // shared cross K/V (AX_WHISPER_BEAM_CROSS=shared): the step's cross-attention reads clip c's K/V where the encoder put it, slot c,
+  // for all K ranks, and nothing is spread; steps of the GEMV family, K = 1 and an FP8 handle keep a copy per slot
+  StepSpec spec{kDecodeScored, 11};
+  spec.cross_group = beam_cross_group(clips, K);
+  const StepGraphRef g = step_graph(spec, slots, max_new);
   ensure_beam_buffers();
-  beam_spread_cross(clips, K);
+  if (!spec.cross_group) beam_spread_cross(clips, K);
   reset_decode_state(slots);
   beam_begin(clips, K);
   const int total = 2 + max_new;
@@ -118,7 +122,7 @@ int Engine::beam_loop(int clips, int K, int max_new, const BeamResult& out, floa
   hipEvent_t pe[2] = {ev_[3], ev_[4]};
   int steps = 0, polls = 0;
   for (int st = 0; st < total; ++st) {
-    HIP_CHECK(hipGraphLaunch(g, s));
+    launch_step_graph(g, s);
     ++steps;
     if (st == 0) launch_row_logprob(d_ts_logits_, ts_stride_, nv, (int)cfg_.ints.at("no_speech"), slots, d_nospeech_, s);
     const int n = st - 2;

@@ -99,6 +99,7 @@ float Engine::bench(const std::string& what, int batch, int arg, int iters) {
       what == "decode_step_ts_sampled" || what == "stream_step_ts")
     return bench_decode_step(what, batch, arg, iters);
   if (what == "decode_step_beam") return bench_decode_step_beam(batch, arg, iters);
+  if (what == "decode_attn_beam") return bench_decode_step(what, batch, arg, iters);
   if (what == "attn_stamp") return bench_attn_stamp(batch, arg, iters);
   if (what == "encoder") return bench_encoder(batch, iters);
   if (what == "cross_kv_quant") return bench_cross_kv_quant(batch, iters);
@@ -210,8 +211,12 @@ float Engine::bench_word_logprob(const std::string& what, int batch, int arg, in
 // decode_gemv / decode_attn: the same captured step with only the GEMV / only the attention launches;
 // decode_step_ts: the whole step in timestamp mode (logits dump + rules kernel); decode_step_ts_scored: with the scored rules kernel;
 // decode_step_ts_sampled: with the sampled rules kernel, every clip at temperature AX_WHISPER_BENCH_TEMPERATURE (default 1);
-// stream_step_ts: the scored step of the slot stream in timestamp mode (stream_rules_kernel, a prefix per slot), the same placement
+// stream_step_ts: the scored step of the slot stream in timestamp mode (stream_rules_kernel, a prefix per slot), the same placement;
+// decode_attn_beam: decode_attn of the beam step of `batch` slots in groups of arg (the beam size) at offset 224: on a shared-cross
+// handle the cross-attention launches are the grouped ones
 float Engine::bench_decode_step(const std::string& what, int batch, int arg, int iters) {
+  const bool attn_beam = what == "decode_attn_beam";
+  if (attn_beam && (arg < 1 || arg > kBeamMax || batch % arg != 0)) throw std::runtime_error("bench decode_attn_beam: arg is the beam size, batch a multiple of it");
   const bool sampled = what == "decode_step_ts_sampled";
   const bool slots = what == "stream_step_ts";
   const bool whole = what == "decode_step" || what == "decode_step_ts" || what == "decode_step_ts_scored" || sampled || slots;
@@ -231,6 +236,7 @@ float Engine::bench_decode_step(const std::string& what, int batch, int arg, int
     upload_sample(SampleSpec{temps.data(), streams.data(), 1}, batch);
   }
   spec.mask = whole ? 15 : (what == "decode_gemv" ? 1 : 2);
+  if (attn_beam) { spec = StepSpec{kDecodeScored, 2}; spec.cross_group = beam_cross_group(batch / arg, arg); arg = 224; }
   hipStream_t s = stream();
   const int Tc = cfg_.n_text_ctx;
   reset_decode_state(batch);
@@ -260,7 +266,9 @@ float Engine::bench_decode_step_beam(int slots, int beam_size, int iters) {
   if (slots < beam_size || slots % beam_size != 0) throw std::runtime_error("bench decode_step_beam: batch must be a multiple of the beam size");
   const int clips = slots / beam_size, Tc = cfg_.n_text_ctx;
   hipStream_t s = stream();
-  hipGraphExec_t g = step_graph(StepSpec{kDecodeScored, 11}, slots, Tc - 3);
+  StepSpec spec{kDecodeScored, 11};
+  spec.cross_group = beam_cross_group(clips, beam_size);  // (a shared-cross handle measures the shared step, as beam_loop runs it)
+  const StepGraphRef g = step_graph(spec, slots, Tc - 3);
   ensure_beam_buffers();
   const int off0 = std::max(2, std::min(224, Tc - 2 - iters));
   DecState st{off0, 0, 0, 0};
@@ -279,14 +287,14 @@ float Engine::bench_decode_step_beam(int slots, int beam_size, int iters) {
     reset_decode_state(slots);
     beam_begin(clips, beam_size);
     place();
-    HIP_CHECK(hipGraphLaunch(g, s));  // warm
+    launch_step_graph(g, s);  // warm
     enqueue_beam_tail(clips, beam_size, off0, Tc - 3, s);
     HIP_CHECK(hipStreamSynchronize(s));
     place();
     const Event a = make_event(), b = make_event();
     HIP_CHECK(hipEventRecord(a, s));
     for (int i = 0; i < iters && off0 + i < Tc - 1; ++i) {
-      HIP_CHECK(hipGraphLaunch(g, s));
+      launch_step_graph(g, s);
       enqueue_beam_tail(clips, beam_size, off0 + i, Tc - 3, s);
       if (count) {
         HIP_CHECK(hipMemcpyAsync(src.data(), beam_.src, (size_t)slots * 4, hipMemcpyDeviceToHost, s));

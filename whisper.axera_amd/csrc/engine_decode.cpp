@@ -36,9 +36,12 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
   // 3+ clips: the clip-block sequence (a 4-clip step: 0.78 ms through the GEMV family, 0.59 through clip-block GEMMs);
   // one clip that cannot use the persistent launch and two clips that cannot either stay on the GEMV family
   if (batch > gemv_max_) {
-    const int fp8_before = enq_fp8_launches_;
+    const int fp8_before = enq_fp8_launches_, group_before = enq_group_launches_;
     enqueue_decode_step_batched(spec, batch, max_new, d_forced, n_forced, d_logits, logits_stride, d_argmax);
-    if (!in_step_capture_) note_fp8_launches(enq_fp8_launches_ - fp8_before);  // enqueued directly: these launches run once
+    if (!in_step_capture_) {  // enqueued directly: these launches run once
+      note_fp8_launches(enq_fp8_launches_ - fp8_before);
+      note_group_launches(enq_group_launches_ - group_before);
+    }
     return;
   }
 
@@ -172,10 +175,30 @@ void Engine::launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, h
   ++enq_fp8_launches_;
 }
 
-// a step_graph() exec on the stream; its fp8 cross-attention launches are counted per replay
+// The cross-attention launch `a` describes for slots [b0, b0 + nb) (its query mode, splits, done flags and outputs) as ONE workgroup
+// per (split, head, clip): the slots are the ranks of clips of K, which all read the K/V of the clip's own slot
+void Engine::launch_cross_attention_group(const DecAttnParams& a, int l, int b0, int K, hipStream_t s) {
+  const long slot_elems = cfg_.n_text_head * layout::kv_head_elems(t_pad_);
+  DecAttnGroupParams g{};
+  g.k = d_cross_k_ + (size_t)l * cap_ * slot_elems;
+  g.v = d_cross_v_ + (size_t)l * cap_ * slot_elems;
+  g.kv_slot_stride = slot_elems;
+  g.group = K; g.slot0 = b0; g.nslots = a.batch;
+  g.q = a.q;
+  g.n_split = a.n_split; g.n_head = a.n_head; g.d_model = a.d_model; g.n_keys = a.n_keys; g.cap_blocks = a.cap_blocks;
+  g.done = a.done; g.done_late = a.done_late;
+  g.out_hi = a.out_hi; g.out_lo = a.out_lo; g.nbs = a.nbs; g.mpart = a.mpart; g.mcnt = a.mcnt;
+  g.x = a.x; g.ln_w = a.ln_w; g.ln_b = a.ln_b; g.wq = a.wq; g.bq = a.bq;
+  g.tq = a.tq; g.stat_part = a.stat_part; g.fold_s = a.fold_s; g.fold_c = a.fold_c;
+  launch_decode_cross_attention_group(g, s);
+  ++enq_group_launches_;
+}
+
+// a step_graph() exec on the stream; its fp8 and grouped cross-attention launches are counted per replay
 void Engine::launch_step_graph(const StepGraphRef& g, hipStream_t s) {
   HIP_CHECK(hipGraphLaunch(g.exec, s));
   note_fp8_launches(g.fp8_launches);
+  note_group_launches(g.group_launches);
 }
 
 // bench "attn_stamp" (StepSpec::mask bit 16): the next {min begin, max end} slot, with what the launch is
@@ -212,11 +235,13 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
   // record to the fold, and a second workgroup on a CU shares its memory path — decode ms per call at Whisper-small dims by splits
   // (profiles/r05_cross_split_sweep.txt): 4 clips 6: 249, 4: 241, 3: 241, 2: 246 | 6 clips 4: 259, 3: 250, 2: 251 |
   // 8 clips 6: 289, 4: 263, 3: 262, 2: 261 | 10 clips 2: 264.5, 1: 267 | 12 clips 2: 283, 1: 272.
+  // (grouped cross-attention: a workgroup per clip with a rank in the range, not per slot)
+  const int cross_wg = spec.cross_group ? cross_group_clips(b0, nb, spec.cross_group) : nb;
   int cross_split = 1;
   {
     const int blocks = t_pad_ / 64;
     for (int c : {6, 4, 3, 2})
-      if (c <= layout::kAttnSplitMax && blocks % c == 0 && nb * H * c <= std::max(n_cu_, 64)) { cross_split = c; break; }
+      if (c <= layout::kAttnSplitMax && blocks % c == 0 && cross_wg * H * c <= std::max(n_cu_, 64)) { cross_split = c; break; }
     if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && blocks % cross_split_env_ == 0) cross_split = cross_split_env_;
   }
   // Folded query: a split repeats nothing but a 3 KB gather, so the grid is sized for whole waves of workgroups instead (three
@@ -243,7 +268,8 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
   // a cross-attention launch: over the FP8 code images where the step asks for them (stamped measurement steps keep the h16 kernel,
   // the only one that carries stamp code)
   auto cross = [&](const DecAttnParams& a, int l) {
-    if (spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, b0, s);
+    if (spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, b0, spec.cross_group, s);
+    else if (spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, b0, s);
     else launch_decode_attention(a, s);
   };
   const int n_blk = (nb + 15) / 16;
@@ -389,7 +415,7 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     if (n_keys >= 0) {  // cross-attention: few (clip, head) pairs leave CUs with one workgroup beside CUs with two (turbo, 16 clips: 320)
       int c = 1;
       for (int k : {6, 4, 3, 2})
-        if (k <= layout::kAttnSplitMax && cap_blocks % k == 0 && batch * H * k <= 640) { c = k; break; }
+        if (k <= layout::kAttnSplitMax && cap_blocks % k == 0 && (spec.cross_group ? cross_group_clips(0, batch, spec.cross_group) : batch) * H * k <= 640) { c = k; break; }
       if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && cap_blocks % cross_split_env_ == 0) c = cross_split_env_;
       a.n_split = c;
       a.mpart = d_attn_mpart_;
@@ -397,7 +423,8 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     }
     a.stamp = next_stamp(spec, l, n_keys >= 0 ? 1 : 0, 0, batch);
     if (!(spec.mask & 2)) return;
-    if (n_keys >= 0 && spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, 0, s);
+    if (n_keys >= 0 && spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, 0, spec.cross_group, s);
+    else if (n_keys >= 0 && spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, 0, s);
     else launch_decode_attention(a, s);
   };
   auto base = [&](const h16* W, const float* bias, int N, int K, const h16* ahi, const h16* alo, int epi) {
@@ -528,7 +555,7 @@ void Engine::ensure_branch_streams(int batch) {
 Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
   const long key = graph_key(spec, batch, max_new);  // plain and timestamp-mode steps are different graphs
   auto it = graphs_.find(key);
-  if (it != graphs_.end()) return {it->second.exec, it->second.fp8_launches};
+  if (it != graphs_.end()) return {it->second.exec, it->second.fp8_launches, it->second.group_launches};
   hipStream_t s = stream();
   // nobody on this device allocates, copies synchronously or captures while this capture is open (iengine.hpp)
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
@@ -540,6 +567,7 @@ Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
   hipGraph_t captured = nullptr;
   const ScopedSet<bool> capturing(in_step_capture_, true);  // what the capture enqueues has not run: it is counted per replay
   enq_fp8_launches_ = 0;
+  enq_group_launches_ = 0;
   try {
     enqueue_decode_step(spec, batch, max_new, nullptr, 0, nullptr, 0, nullptr);
     cap_err = hipStreamEndCapture(s, &captured);
@@ -581,8 +609,8 @@ Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
       cfg_.ints["graph_queue_aligned"] = aligned ? 1 : 0;
     }
   }
-  StepGraph& kept = graphs_[key] = StepGraph{std::move(exec), enq_fp8_launches_};
-  return {kept.exec, kept.fp8_launches};
+  StepGraph& kept = graphs_[key] = StepGraph{std::move(exec), enq_fp8_launches_, enq_group_launches_};
+  return {kept.exec, kept.fp8_launches, kept.group_launches};
 }
 
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.
