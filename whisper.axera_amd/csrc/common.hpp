@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #include "decode_layout.hpp"
 #include "vocab_logprob_plan.hpp"
@@ -431,32 +433,66 @@ int gemv_grid(const GemvParams& p);  // number of workgroups launch_gemv will us
 void launch_embed(const h16* tok_emb, const float* pos, const int* tok, const int* off, float* x, int batch, int d,
                   hipStream_t s);
 
-// single-query attention over blocked K / row-major V, writes split partials [B][H][n_split][66]
-struct DecAttnParams {
+// ---- what the single-query attention launches below have in common (the device side: decode_attention_common.hpp).
+// The h16 and the grouped launch's parameter structs derive from their own K/V addressing, then AttnQuerySource, then AttnResultSink
+// (the FP8 launch keeps a flat struct with the same field names, see there): every field keeps
+// its plain name (p.k, p.tq, p.n_split), the structs stay trivially copyable, and the shared parts are passed and assigned whole.
+// Where the head's 64 query values of clip b come from. tq != nullptr: folded; else wq != nullptr: fused; else read from q.
+struct AttnQuerySource {
   const float* q;             // [B][d]
+  // fused query projection (batched cross-attention): q = Wq[head rows] . LayerNorm(x[b]) + bq computed by the
+  // (clip, head) workgroup itself while its first K/V block is in flight
+  const float* x; const float* ln_w; const float* ln_b; const h16* wq; const float* bq;
+  // folded query (decode_gemm.hip "QUERY FOLD"): q[j] = rstd (tq[b][j] - mean fold_s[j]) + fold_c[j], mean / rstd of
+  // the clip's residual row from its stat_part[b][d_model / 16][2] block statistics
+  const float* tq; const float* stat_part; const float* fold_s; const float* fold_c;
+  int d_model;
+};
+// Who is skipped, how the key blocks are divided, and where the result goes.
+struct AttnResultSink {
+  int n_split, n_head;
+  const int* done;            // device [B], never null: clips whose flag is set are skipped (greedy loop past their eot); all zero where nobody stops
+  int done_late;              // few clips (a launch is one dependent chain): the flag is looked at BEHIND the first requests, not before them
+  h16* out_hi; h16* out_lo; int nbs; // normalised output as a fragment-major h16 pair; with n_split > 1
+                                     // the splits of a (clip, head) meet through mpart / mcnt and the last one to arrive writes it
+  float* mpart; unsigned* mcnt;      // [B][H][n_split][66] / [B][H] (zero between launches), same clip origin as q / out
+};
+// The checks every launcher makes of a query source and a sink (d_model per mode, the mode's pointers, done, the split count and,
+// where the launch folds its splits itself, mpart / mcnt): aborts with `what` in the message, else returns the query mode
+// (0 read, 1 fused, 2 folded) and, for the fused mode of the one-row kernels, the NCHL instantiation (0: the generic chunk loop).
+struct AttnQueryPlan { int mode, nchl; };
+inline AttnQueryPlan plan_attention_query(const AttnQuerySource& q, const AttnResultSink& k, const char* what) {
+  const int mode = q.tq ? 2 : q.wq ? 1 : 0;
+  const bool query_ok = mode == 2   ? q.d_model <= 1024 && q.d_model % 64 == 0 && q.stat_part && q.fold_s && q.fold_c
+                        : mode == 1 ? q.d_model <= 1024 && q.d_model % 32 == 0 && q.x && q.ln_w && q.ln_b && q.bq
+                                    : q.q != nullptr;
+  // splits that meet inside the launch need the records and the tickets; only a launch that reads its query may leave partials instead
+  const bool folds = k.out_hi && k.n_split != 1;
+  const bool sink_ok = k.done && k.n_split >= 1 && (!folds || (k.n_split <= layout::kAttnSplitMax && k.out_lo && k.mpart && k.mcnt)) &&
+                       (mode == 0 || k.n_split == 1 || k.out_hi);
+  if (!query_ok || !sink_ok) {
+    fprintf(stderr, "[ax_whisper] %s: query mode %d, d_model %d, n_split %d unsupported\n", what, mode, q.d_model, k.n_split);
+    abort();
+  }
+  const bool all_up_front = mode == 1 && (q.d_model == 384 || q.d_model == 512 || q.d_model == 768 || q.d_model == 1024);
+  return {mode, all_up_front ? q.d_model / 32 : 0};
+}
+
+// single-query attention over blocked K / row-major V; without out_hi it writes split partials [B][H][n_split][66] to `part`
+struct DecAttnKv {
   const h16* k; const h16* v; long kv_batch_stride;   // this layer, slot 0
-  float* part; int n_split;
-  int batch, n_head, d_model;
+  float* part;
+  int batch;
   int n_keys;                 // fixed key count (cross) or -1: off[b] + 1 (self)
   int cap_blocks;             // allocated 64-key blocks per (slot, head): 24 cross, 7 self
   const DecState* state;
   const int* off;             // per-clip offsets [B]
-  const int* done;            // device [B], never null: clips whose flag is set are skipped (greedy loop past their eot); all zero where nobody stops
-  int done_late;              // few clips (a launch is one dependent chain): the flag is looked at BEHIND the first requests, not before them
-  h16* out_hi; h16* out_lo; int nbs; // normalised output as a fragment-major h16 pair instead of partials; with n_split > 1
-                                     // the splits of a (clip, head) meet through mpart / mcnt and the last one to arrive writes it
-  float* mpart; unsigned* mcnt;      // [B][H][n_split][66] / [B][H] (zero between launches), same clip origin as q / out
-  // fused query projection (batched cross-attention): q = Wq[head rows] . LayerNorm(x[b]) + bq computed by the
-  // (clip, head) workgroup itself while its first K/V block is in flight; wq == nullptr: q is read from `q`
-  const float* x; const float* ln_w; const float* ln_b; const h16* wq; const float* bq;
-  // folded query (decode_gemm.hip "QUERY FOLD"; tq != nullptr): q[j] = rstd (tq[b][j] - mean fold_s[j]) + fold_c[j], mean / rstd of
-  // the clip's residual row from its stat_part[b][d_model / 16][2] block statistics
-  const float* tq; const float* stat_part; const float* fold_s; const float* fold_c;
   // measurement only (Engine::bench "attn_stamp"): [workgroups][2] = {begin, end} of every workgroup of this launch in
   // 100 MHz wall-clock ticks, written by the kernel itself (a separate template instantiation: the production kernel
   // carries no stamp code)
   unsigned long long* stamp;
 };
+struct DecAttnParams : DecAttnKv, AttnQuerySource, AttnResultSink {};
 void launch_decode_attention(const DecAttnParams& p, hipStream_t s);
 
 // ---- FP8 cross K/V (cross_kv_fp8.hip; decode_layout.hpp "FP8 cross K/V"): opt-in storage of the batched step's cross-attention
@@ -473,7 +509,9 @@ struct CrossKvQuantParams {
 void launch_cross_kv_quantize(const CrossKvQuantParams& p, hipStream_t s);
 
 // single-query cross-attention over the code images: decode_attention_kernel's three query modes, split record, ticket hand-off and
-// fragment-major (hi, lo) output pair (the fields below mean what their namesakes in DecAttnParams mean)
+// fragment-major (hi, lo) output pair (the fields below mean what their namesakes in AttnQuerySource / AttnResultSink mean).
+// This kernel keeps its own flat struct and its own copy of the shared pieces: it is register-tight, any change to its text moved
+// its instructions, and the shared form measured 0.3 - 1.3 % slower (profiles/cross_attention_refactor_bench.txt).
 struct DecAttnFp8Params {
   const float* q;
   const unsigned char* k8; const unsigned char* v8; long kv_batch_bytes;  // this layer, the launch's first slot
@@ -493,21 +531,16 @@ void launch_decode_cross_attention_fp8(const DecAttnFp8Params& p, hipStream_t s)
 // [c * group, c * group + group) are the hypotheses ("ranks") of clip c and all attend over the K/V of slot c, where the encoder put
 // it. One workgroup per (split, head, clip) serves the clip's ranks that lie inside the launch's slot range [slot0, slot0 + nslots):
 // it reads their queries and writes their outputs / split records, and nothing of a slot outside the range. The three query modes,
-// the split record, the ticket hand-off and the fragment-major (hi, lo) output pair are decode_attention_kernel's, per rank.
-struct DecAttnGroupParams {
+// the split record, the ticket hand-off and the fragment-major (hi, lo) output pair are those of decode_attention_common.hpp, per rank.
+struct DecAttnGroupKv {
   const h16* k; const h16* v; long kv_slot_stride;  // this layer, slot 0 of the HANDLE (a clip's K/V may lie outside the slot range)
   int group;                                        // ranks per clip, 1 .. 8
   int slot0, nslots;                                // the launch's slots; slot0 is a multiple of 16
-  // everything below has the origin of slot0 (DecAttnParams: "same clip origin as q / out") and means what its namesake means there
-  const float* q;
-  int n_split, n_head, d_model;
   int n_keys, cap_blocks;
-  const int* done; int done_late;
-  h16* out_hi; h16* out_lo; int nbs;
-  float* mpart; unsigned* mcnt;                     // the ticket of a group is the counter of its first rank inside the range
-  const float* x; const float* ln_w; const float* ln_b; const h16* wq; const float* bq;
-  const float* tq; const float* stat_part; const float* fold_s; const float* fold_c;
 };
+// the query source and the sink have the origin of slot0 ("same clip origin as q / out"); the ticket of a group is the counter of its
+// first rank inside the range
+struct DecAttnGroupParams : DecAttnGroupKv, AttnQuerySource, AttnResultSink {};
 void launch_decode_cross_attention_group(const DecAttnGroupParams& p, hipStream_t s);
 // clips with at least one rank in [slot0, slot0 + nslots): the launch's grid.z
 inline int cross_group_clips(int slot0, int nslots, int group) { return (slot0 + nslots - 1) / group - slot0 / group + 1; }

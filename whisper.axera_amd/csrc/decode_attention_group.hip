@@ -32,10 +32,11 @@
 // is loaded once and multiplied with all G LayerNormed rows (they sit in the LDS of the V tiles, which are not in use yet);
 // 2 the folded query r (T - mu s) + c.
 // Behind the key loop: per rank the split record (m, l, o[64]), the ticket hand-off (one ticket per workgroup: the group's splits
-// all serve the same ranks) and the last arriver's fold in split order, then the fragment-major (hi, lo) output pair — all as in
-// decode_attention_kernel. A rank whose done flag is set gets no record and no output; a group whose ranks are all done returns
+// all serve the same ranks) and the last arriver's fold in split order, then the fragment-major (hi, lo) output pair — the shared
+// pieces of decode_attention_common.hpp. A rank whose done flag is set gets no record and no output; a group whose ranks are all done returns
 // before any K/V request (done_late == 0) or right behind the first ones (done_late == 1).
 #include "common.hpp"
+#include "decode_attention_common.hpp"
 
 namespace axw {
 inline namespace AXW_NS {
@@ -201,15 +202,8 @@ __global__ __launch_bounds__(256) void decode_cross_attention_group_kernel(DecAt
     for (int g = wave; g < kGroupMax; g += 4) {  // one wave per rank: lane = dimension, and one block statistic each
       float qv = 0.f;
       if (g < G) {
-        const long b = rel0 + g;
-        const float tq = p.tq[b * d + head * 64 + lane], sj = p.fold_s[head * 64 + lane], cj = p.fold_c[head * 64 + lane];
-        f32x2_t sp = {0.f, 0.f};
-        if (lane < nst) sp = *reinterpret_cast<const f32x2_t*>(p.stat_part + (b * nst + lane) * 2);
-        // Chan et al. (decoder.hip): the row's mean from the block sums, its centred squares from the blocks' own + 16 (block mean - mean)^2
-        const float mean = wave_sum(sp[0]) / (float)d;
-        const float dm = sp[0] * (1.f / 16.f) - mean;
-        const float m2 = wave_sum(lane < nst ? sp[1] + 16.f * dm * dm : 0.f);
-        qv = rsqrtf(m2 / (float)d + 1e-5f) * (tq - mean * sj) + cj;
+        const auto fq = attn::folded_query_request(p.tq, p.stat_part, p.fold_s, p.fold_c, rel0 + g, head, lane, d, nst);
+        qv = attn::folded_query_value(fq, lane, d, nst);
       }
       put_pair(s_qa, g, lane, qv);
     }
@@ -291,103 +285,54 @@ __global__ __launch_bounds__(256) void decode_cross_attention_group_kernel(DecAt
   for (int j = 0; j < 2; ++j) {
     const int g = wave + 4 * j;
     m[j] = -INFINITY; l[j] = 0.f; ov[j] = 0.f;
-    if (g < G) {
-      const float* r = recs + g * kPartStride;
-      m[j] = fmaxf(fmaxf(r[kPartM], r[kWaveRec + kPartM]), fmaxf(r[2 * kWaveRec + kPartM], r[3 * kWaveRec + kPartM]));
-      if (m[j] > -INFINITY) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const float f = __expf(r[w * kWaveRec + kPartM] - m[j]);
-          l[j] += f * r[w * kWaveRec + kPartL];
-          ov[j] += f * r[w * kWaveRec + kPartO + lane];
-        }
-      }
-    }
+    if (g < G) attn::merge_wave_records(recs + g * kPartStride, kWaveRec, lane, m[j], l[j], ov[j]);
   }
-  auto write_out = [&](int g, float y) {
-    const h16 yh = (h16)y;
-    const long i = layout::frag_index(rel0 + g, head * 64 + lane, p.nbs);  // fragment-major pair
-    p.out_hi[i] = yh;
-    p.out_lo[i] = (h16)(y - (float)yh);
-  };
+  auto write_out = [&](int g, float y) { attn::store_out_pair(p.out_hi, p.out_lo, rel0 + g, head * 64 + lane, p.nbs, y); };
   if (p.n_split == 1) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) { const int g = wave + 4 * j; if (g < G && (live >> g & 1)) write_out(g, ov[j] / l[j]); }
     return;
   }
-  // Splits (decode_attention_kernel): every split publishes its ranks' records with write-through stores and drains them; behind a
-  // barrier ONE lane draws the workgroup's ticket; whoever draws the last one folds all splits' records IN SPLIT ORDER.
+  // Splits (decode_attention_common.hpp): every wave publishes its ranks' records and drains them; behind a barrier ONE lane draws
+  // the workgroup's ticket (the group's splits all serve the same ranks); whoever draws the last one folds every rank's records.
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int g = wave + 4 * j;
-    if (g < G && (live >> g & 1)) {
-      float* mine = p.mpart + layout::part_offset(rel0 + g, head, split, p.n_head, p.n_split);
-      __hip_atomic_store(mine + kPartO + lane, ov[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (lane == 0) {
-        __hip_atomic_store(mine + kPartM, m[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + kPartL, l[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    if (!(g < G && (live >> g & 1))) continue;
+    float* mine = p.mpart + layout::part_offset(rel0 + g, head, split, p.n_head, p.n_split);
+    attn::publish_split_record(mine, lane, m[j], l[j], ov[j]);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  attn::drain_split_stores();
   __syncthreads();
   unsigned* cnt = p.mcnt + (long)rel0 * p.n_head + head;
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-  if (tid == 0) s_ticket = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  const unsigned ticket = attn::draw_split_ticket(cnt, tid == 0);
+  if (tid == 0) s_ticket = ticket;
   __syncthreads();
   if (s_ticket != (unsigned)p.n_split - 1u) return;
-  if (tid == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
+  if (tid == 0) attn::reset_split_counter(cnt);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int g = wave + 4 * j;
     if (!(g < G && (live >> g & 1))) continue;
     const float* base = p.mpart + layout::part_offset(rel0 + g, head, 0, p.n_head, p.n_split);
-    float ms[kAttnSplitMax], ls[kAttnSplitMax], os[kAttnSplitMax];  // every record requested before the first one is used
-#pragma unroll
-    for (int s2 = 0; s2 < kAttnSplitMax; ++s2) {
-      ms[s2] = m[j]; ls[s2] = l[j]; os[s2] = ov[j];
-      if (s2 < p.n_split && s2 != split) {
-        const float* other = base + s2 * kPartStride;
-        ms[s2] = __hip_atomic_load(other + kPartM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ls[s2] = __hip_atomic_load(other + kPartL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        os[s2] = __hip_atomic_load(other + kPartO + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    float M = -INFINITY, Ls = 0.f, O = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < kAttnSplitMax; ++s2) {
-      if (s2 < p.n_split) {
-        const float mn = fmaxf(M, ms[s2]);
-        const float f1 = M > -INFINITY ? __expf(M - mn) : 0.f, f2 = ms[s2] > -INFINITY ? __expf(ms[s2] - mn) : 0.f;
-        Ls = f1 * Ls + f2 * ls[s2];
-        O = f1 * O + f2 * os[s2];
-        M = mn;
-      }
-    }
-    write_out(g, O / Ls);
+    write_out(g, attn::fold_split_records(base, split, p.n_split, lane, m[j], l[j], ov[j]));
   }
 }
 
 }  // namespace
 
 void launch_decode_cross_attention_group(const DecAttnGroupParams& p, hipStream_t s) {
-  const bool folded = p.tq != nullptr, fused = !folded && p.wq != nullptr;
-  const bool shape_ok = p.group >= 1 && p.group <= kGroupMax && p.nslots >= 1 && p.slot0 >= 0 && p.slot0 % 16 == 0 && p.n_head >= 1 &&
-                        p.d_model == p.n_head * layout::kKvDim && p.cap_blocks >= 1 &&
-                        p.n_keys >= 1 && p.n_keys <= p.cap_blocks * layout::kKvBlockKeys && p.n_split >= 1 && p.n_split <= kAttnSplitMax &&
-                        p.out_hi && p.out_lo && p.done && (p.n_split == 1 || (p.mpart && p.mcnt));
-  const bool query_ok = folded ? p.d_model <= 1024 && p.d_model % 64 == 0 && p.stat_part && p.fold_s && p.fold_c
-                        : fused ? p.d_model <= 1024 && p.d_model % 32 == 0 && p.x && p.ln_w && p.ln_b && p.bq
-                                : p.q != nullptr;
-  if (!shape_ok || !query_ok) {
-    fprintf(stderr, "[ax_whisper] grouped cross-attention: group %d, slots %d + %d, d_model %d, n_head %d, n_keys %d, n_split %d unsupported\n",
-            p.group, p.slot0, p.nslots, p.d_model, p.n_head, p.n_keys, p.n_split);
+  if (!(p.group >= 1 && p.group <= kGroupMax && p.nslots >= 1 && p.slot0 >= 0 && p.slot0 % 16 == 0 && p.n_head >= 1 &&
+        p.d_model == p.n_head * layout::kKvDim && p.cap_blocks >= 1 && p.n_keys >= 1 && p.n_keys <= p.cap_blocks * layout::kKvBlockKeys &&
+        p.out_hi && p.out_lo)) {
+    fprintf(stderr, "[ax_whisper] grouped cross-attention: group %d, slots %d + %d, d_model %d, n_head %d, n_keys %d unsupported\n",
+            p.group, p.slot0, p.nslots, p.d_model, p.n_head, p.n_keys);
     abort();
   }
+  const AttnQueryPlan plan = plan_attention_query(p, p, "grouped cross-attention");
   const dim3 grid(p.n_split, p.n_head, cross_group_clips(p.slot0, p.nslots, p.group));
-  if (folded) hipLaunchKernelGGL((decode_cross_attention_group_kernel<2>), grid, dim3(256), 0, s, p);
-  else if (fused) hipLaunchKernelGGL((decode_cross_attention_group_kernel<1>), grid, dim3(256), 0, s, p);
+  if (plan.mode == 2) hipLaunchKernelGGL((decode_cross_attention_group_kernel<2>), grid, dim3(256), 0, s, p);
+  else if (plan.mode == 1) hipLaunchKernelGGL((decode_cross_attention_group_kernel<1>), grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL((decode_cross_attention_group_kernel<0>), grid, dim3(256), 0, s, p);
 }
 

@@ -499,6 +499,13 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s);
   // the fp8 cross-attention launch of layer l for clips [b0, b0 + nb) with a's query mode, splits and outputs
   void launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s);
+  // The cross-attention launch `a` describes for layer l, slots [b0, b0 + a.batch): grouped where the step asks for it, else over the
+  // FP8 code images where it asks for those, else the h16 kernel — which a stamped (measurement) launch always keeps, being the only
+  // one that carries stamp code
+  void launch_cross_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s);
+  // Workgroups per (clip, head) of a cross-attention launch over `blocks` key blocks: the largest of 6, 4, 3, 2 that divides the
+  // blocks and keeps wg_per_split * it within wg_limit, else 1; AX_WHISPER_CROSS_SPLIT overrides
+  int cross_split_count(int wg_per_split, int blocks, int wg_limit) const;
   float bench_cross_kv_quant(int batch, int iters);
   // bench "attn_stamp": every decode_attention launch of a captured step gets a {min begin, max end} slot (DecAttnParams::stamp)
   struct StampMeta { int layer, cross, b0, nb; };

@@ -147,9 +147,11 @@ void Engine::enqueue_step_tail(const StepSpec& spec, int batch, int max_new, con
 DecAttnParams Engine::attn_params(const float* q, const h16* k, const h16* v, long stride, int n_keys, int cap_blocks, int b0, int nb,
                                   bool forced) const {
   DecAttnParams a{};
-  a.q = q; a.k = k; a.v = v; a.kv_batch_stride = stride; a.part = nullptr; a.n_split = 1;
-  a.batch = nb; a.n_head = cfg_.n_text_head; a.d_model = cfg_.n_text_state; a.n_keys = n_keys; a.cap_blocks = cap_blocks; a.state = d_state_;
+  a.q = q; a.d_model = cfg_.n_text_state;
+  a.k = k; a.v = v; a.kv_batch_stride = stride; a.part = nullptr;
+  a.batch = nb; a.n_keys = n_keys; a.cap_blocks = cap_blocks; a.state = d_state_;
   a.off = d_off_ + b0;
+  a.n_split = 1; a.n_head = cfg_.n_text_head;
   a.done = (forced ? d_done_none_ : d_done_) + b0;  // (never null: the attention launches read the flag unconditionally)
   return a;
 }
@@ -180,18 +182,27 @@ void Engine::launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, h
 void Engine::launch_cross_attention_group(const DecAttnParams& a, int l, int b0, int K, hipStream_t s) {
   const long slot_elems = cfg_.n_text_head * layout::kv_head_elems(t_pad_);
   DecAttnGroupParams g{};
+  static_cast<AttnQuerySource&>(g) = a; static_cast<AttnResultSink&>(g) = a;
   g.k = d_cross_k_ + (size_t)l * cap_ * slot_elems;
   g.v = d_cross_v_ + (size_t)l * cap_ * slot_elems;
   g.kv_slot_stride = slot_elems;
   g.group = K; g.slot0 = b0; g.nslots = a.batch;
-  g.q = a.q;
-  g.n_split = a.n_split; g.n_head = a.n_head; g.d_model = a.d_model; g.n_keys = a.n_keys; g.cap_blocks = a.cap_blocks;
-  g.done = a.done; g.done_late = a.done_late;
-  g.out_hi = a.out_hi; g.out_lo = a.out_lo; g.nbs = a.nbs; g.mpart = a.mpart; g.mcnt = a.mcnt;
-  g.x = a.x; g.ln_w = a.ln_w; g.ln_b = a.ln_b; g.wq = a.wq; g.bq = a.bq;
-  g.tq = a.tq; g.stat_part = a.stat_part; g.fold_s = a.fold_s; g.fold_c = a.fold_c;
+  g.n_keys = a.n_keys; g.cap_blocks = a.cap_blocks;
   launch_decode_cross_attention_group(g, s);
   ++enq_group_launches_;
+}
+
+void Engine::launch_cross_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s) {
+  if (spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, b0, spec.cross_group, s);
+  else if (spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, b0, s);
+  else launch_decode_attention(a, s);
+}
+
+int Engine::cross_split_count(int wg_per_split, int blocks, int wg_limit) const {
+  if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && blocks % cross_split_env_ == 0) return cross_split_env_;
+  for (int c : {6, 4, 3, 2})
+    if (c <= layout::kAttnSplitMax && blocks % c == 0 && wg_per_split * c <= wg_limit) return c;
+  return 1;
 }
 
 // a step_graph() exec on the stream; its fp8 and grouped cross-attention launches are counted per replay
@@ -237,13 +248,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
   // 8 clips 6: 289, 4: 263, 3: 262, 2: 261 | 10 clips 2: 264.5, 1: 267 | 12 clips 2: 283, 1: 272.
   // (grouped cross-attention: a workgroup per clip with a rank in the range, not per slot)
   const int cross_wg = spec.cross_group ? cross_group_clips(b0, nb, spec.cross_group) : nb;
-  int cross_split = 1;
-  {
-    const int blocks = t_pad_ / 64;
-    for (int c : {6, 4, 3, 2})
-      if (c <= layout::kAttnSplitMax && blocks % c == 0 && cross_wg * H * c <= std::max(n_cu_, 64)) { cross_split = c; break; }
-    if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && blocks % cross_split_env_ == 0) cross_split = cross_split_env_;
-  }
+  const int cross_split = cross_split_count(cross_wg * H, t_pad_ / 64, std::max(n_cu_, 64));
   // Folded query: a split repeats nothing but a 3 KB gather, so the grid is sized for whole waves of workgroups instead (three
   // 136-register workgroups per CU are resident): AX_WHISPER_CROSS_SPLIT_FOLD forces a count (sweeps)
   int cross_split_fold = cross_split;
@@ -265,13 +270,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
     a.out_hi = att_hi; a.out_lo = att_lo; a.nbs = nbs_;
     return a;
   };
-  // a cross-attention launch: over the FP8 code images where the step asks for them (stamped measurement steps keep the h16 kernel,
-  // the only one that carries stamp code)
-  auto cross = [&](const DecAttnParams& a, int l) {
-    if (spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, b0, spec.cross_group, s);
-    else if (spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, b0, s);
-    else launch_decode_attention(a, s);
-  };
+  auto cross = [&](const DecAttnParams& a, int l) { launch_cross_attention(spec, a, l, b0, s); };
   const int n_blk = (nb + 15) / 16;
   // two row tiles per workgroup where one would make more workgroups than can be resident at once
   // (fewer, fatter workgroups at few clips — two row tiles from 100 or from 40 workgroups on — measured 2 % slower at 4 and 8 clips)
@@ -413,18 +412,13 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     DecAttnParams a = attn_params(d_qdec_, kc, vc, stride, n_keys, cap_blocks, 0, batch, d_forced != nullptr);
     a.out_hi = d_att_[0]; a.out_lo = d_att_[1]; a.nbs = nbs_;
     if (n_keys >= 0) {  // cross-attention: few (clip, head) pairs leave CUs with one workgroup beside CUs with two (turbo, 16 clips: 320)
-      int c = 1;
-      for (int k : {6, 4, 3, 2})
-        if (k <= layout::kAttnSplitMax && cap_blocks % k == 0 && (spec.cross_group ? cross_group_clips(0, batch, spec.cross_group) : batch) * H * k <= 640) { c = k; break; }
-      if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && cap_blocks % cross_split_env_ == 0) c = cross_split_env_;
-      a.n_split = c;
+      a.n_split = cross_split_count((spec.cross_group ? cross_group_clips(0, batch, spec.cross_group) : batch) * H, cap_blocks, 640);
       a.mpart = d_attn_mpart_;
       a.mcnt = d_attn_mcnt_;
     }
     a.stamp = next_stamp(spec, l, n_keys >= 0 ? 1 : 0, 0, batch);
     if (!(spec.mask & 2)) return;
-    if (n_keys >= 0 && spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, 0, spec.cross_group, s);
-    else if (n_keys >= 0 && spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, 0, s);
+    if (n_keys >= 0) launch_cross_attention(spec, a, l, 0, s);
     else launch_decode_attention(a, s);
   };
   auto base = [&](const h16* W, const float* bias, int N, int K, const h16* ahi, const h16* alo, int epi) {
