@@ -545,6 +545,18 @@ void launch_decode_cross_attention_group(const DecAttnGroupParams& p, hipStream_
 // clips with at least one rank in [slot0, slot0 + nslots): the launch's grid.z
 inline int cross_group_clips(int slot0, int nslots, int group) { return (slot0 + nslots - 1) / group - slot0 / group + 1; }
 
+// ---- grouped cross-attention over the FP8 code images (decode_attention_group_fp8.hip; a handle with both opt-in modes): the grouped
+// launch above with clip c's K/V read as the e4m3fn codes and power-of-two scales of slot c (decode_layout.hpp "FP8 cross K/V").
+struct DecAttnGroupFp8Kv {
+  const unsigned char* k8; const unsigned char* v8; long kv_slot_bytes;  // this layer, slot 0 of the HANDLE
+  const float* scales; long scale_slot_stride;                           // this layer, slot 0 of the HANDLE: [head][2][64] per slot
+  int group;                                                             // ranks per clip, 1 .. 8
+  int slot0, nslots;                                                     // the launch's slots; slot0 is a multiple of 16
+  int n_keys, cap_blocks;
+};
+struct DecAttnGroupFp8Params : DecAttnGroupFp8Kv, AttnQuerySource, AttnResultSink {};
+void launch_decode_cross_attention_group_fp8(const DecAttnGroupFp8Params& p, hipStream_t s);
+
 // ---- batched decode (3..64 clips per launch): activations as h16 (hi, lo) pairs, MFMA GEMM (decode_gemm.hip)
 struct DecGemmParams {
   const h16* W;                           // fragment-major packed weights

@@ -275,12 +275,13 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     // launch feeds every slot its own prefix from d_slot_ctx_
     bool slots = false;
     // the cross-attention launches of a step of more than gemv_max_ clips read the FP8 code images (cross_kv_fp8.hip); set from the
-    // handle's mode by step_spec(), left clear by beam search (its spread kernel copies only the h16 images) and by the detection
-    // and step-fed context steps of engine_prefill.cpp
+    // handle's mode by step_spec(); beam search sets it only together with cross_group (its spread kernel copies only the h16 images),
+    // and the detection and step-fed context steps of engine_prefill.cpp leave it clear
     bool cross_fp8 = false;
     // beam search with ONE cross K/V copy per clip (decode_attention_group.hip): the slots [c K, c K + K) are the ranks of clip c and
     // the cross-attention launches of a step of more than gemv_max_ slots read slot c's K/V for all of them; K here, 0: every slot its
-    // own. Set by beam_loop alone, on a handle made under AX_WHISPER_BEAM_CROSS=shared.
+    // own. Set by beam_loop alone, on a handle made under AX_WHISPER_BEAM_CROSS=shared. With cross_fp8 set too (a handle with both
+    // modes), the launches read slot c's code images instead (decode_attention_group_fp8.hip).
     int cross_group = 0;
   };
   StepSpec step_spec(DecodeMode mode = kDecodePlain, int mask = 15) const { StepSpec sp{mode, mask}; sp.cross_fp8 = cross_fp8_; return sp; }
@@ -494,13 +495,23 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void note_group_launches(long n) { if (n) { cross_group_launches_ += n; cfg_.ints["beam_cross_shared_launches"] = (int)cross_group_launches_; } }
   // the grouped cross-attention launch of layer l for slots [b0, b0 + nb) in groups of K, with a's query mode, splits and outputs
   void launch_cross_attention_group(const DecAttnParams& a, int l, int b0, int K, hipStream_t s);
+  // the same launch over the FP8 code images and scales of the clips' own slots (counts in both launch counters)
+  void launch_cross_attention_group_fp8(const DecAttnParams& a, int l, int b0, int K, hipStream_t s);
   // the group size a beam call of clips x K hypotheses runs its step with (0: the copy path)
-  int beam_cross_group(int clips, int K) const { return beam_cross_shared_ && !cross_fp8_ && K > 1 && clips * K > gemv_max_ ? K : 0; }
+  int beam_cross_group(int clips, int K) const { return beam_cross_shared_ && K > 1 && clips * K > gemv_max_ ? K : 0; }
+  // the step a beam call of clips x K hypotheses runs: `mask` of the scored step; grouped on a shared-cross handle, and then over
+  // the code images where the handle keeps them (an FP8 handle without the shared mode keeps the h16 copies)
+  StepSpec beam_step_spec(int clips, int K, int mask) const {
+    StepSpec sp{kDecodeScored, mask};
+    sp.cross_group = beam_cross_group(clips, K);
+    sp.cross_fp8 = sp.cross_group && cross_fp8_;
+    return sp;
+  }
   void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s);
   // the fp8 cross-attention launch of layer l for clips [b0, b0 + nb) with a's query mode, splits and outputs
   void launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s);
-  // The cross-attention launch `a` describes for layer l, slots [b0, b0 + a.batch): grouped where the step asks for it, else over the
-  // FP8 code images where it asks for those, else the h16 kernel — which a stamped (measurement) launch always keeps, being the only
+  // The cross-attention launch `a` describes for layer l, slots [b0, b0 + a.batch): grouped where the step asks for it (over the FP8
+  // code images where it asks for those too), else over the FP8 code images where it asks for those, else the h16 kernel — which a stamped (measurement) launch always keeps, being the only
   // one that carries stamp code
   void launch_cross_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s);
   // Workgroups per (clip, head) of a cross-attention launch over `blocks` key blocks: the largest of 6, 4, 3, 2 that divides the

@@ -109,9 +109,9 @@ int Engine::beam_loop(int clips, int K, int max_new, const BeamResult& out, floa
   hipStream_t s = stream();
   // layers + the logits dump from offset 0 on; asked for BEFORE the decode state is set up (step_graph)
   // shared cross K/V (AX_WHISPER_BEAM_CROSS=shared): the step's cross-attention reads clip c's K/V where the encoder put it, slot c,
-  // for all K ranks, and nothing is spread; steps of the GEMV family, K = 1 and an FP8 handle keep a copy per slot
-  StepSpec spec{kDecodeScored, 11};
-  spec.cross_group = beam_cross_group(clips, K);
+  // for all K ranks, and nothing is spread (on an FP8 handle too: the step then reads slot c's codes, which the encoder pass left
+  // there with the slot map of its h16 images); steps of the GEMV family, K = 1 and an FP8 handle without that mode keep a copy per slot
+  const StepSpec spec = beam_step_spec(clips, K, 11);
   const StepGraphRef g = step_graph(spec, slots, max_new);
   ensure_beam_buffers();
   if (!spec.cross_group) beam_spread_cross(clips, K);

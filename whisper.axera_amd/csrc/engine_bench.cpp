@@ -236,7 +236,7 @@ float Engine::bench_decode_step(const std::string& what, int batch, int arg, int
     upload_sample(SampleSpec{temps.data(), streams.data(), 1}, batch);
   }
   spec.mask = whole ? 15 : (what == "decode_gemv" ? 1 : 2);
-  if (attn_beam) { spec = StepSpec{kDecodeScored, 2}; spec.cross_group = beam_cross_group(batch / arg, arg); arg = 224; }
+  if (attn_beam) { spec = beam_step_spec(batch / arg, arg, 2); arg = 224; }
   hipStream_t s = stream();
   const int Tc = cfg_.n_text_ctx;
   reset_decode_state(batch);
@@ -266,8 +266,7 @@ float Engine::bench_decode_step_beam(int slots, int beam_size, int iters) {
   if (slots < beam_size || slots % beam_size != 0) throw std::runtime_error("bench decode_step_beam: batch must be a multiple of the beam size");
   const int clips = slots / beam_size, Tc = cfg_.n_text_ctx;
   hipStream_t s = stream();
-  StepSpec spec{kDecodeScored, 11};
-  spec.cross_group = beam_cross_group(clips, beam_size);  // (a shared-cross handle measures the shared step, as beam_loop runs it)
+  const StepSpec spec = beam_step_spec(clips, beam_size, 11);  // (a shared-cross handle measures the shared step, as beam_loop runs it)
   const StepGraphRef g = step_graph(spec, slots, Tc - 3);
   ensure_beam_buffers();
   const int off0 = std::max(2, std::min(224, Tc - 2 - iters));

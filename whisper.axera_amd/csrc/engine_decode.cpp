@@ -192,8 +192,27 @@ void Engine::launch_cross_attention_group(const DecAttnParams& a, int l, int b0,
   ++enq_group_launches_;
 }
 
+// ... and over the FP8 code images and scales of the clips' own slots
+void Engine::launch_cross_attention_group_fp8(const DecAttnParams& a, int l, int b0, int K, hipStream_t s) {
+  const int H = cfg_.n_text_head;
+  const long slot_bytes = H * layout::kv8_head_bytes(t_pad_);
+  DecAttnGroupFp8Params g{};
+  static_cast<AttnQuerySource&>(g) = a; static_cast<AttnResultSink&>(g) = a;
+  g.k8 = d_cross_k8_ + (size_t)l * cap_ * slot_bytes;
+  g.v8 = d_cross_v8_ + (size_t)l * cap_ * slot_bytes;
+  g.kv_slot_bytes = slot_bytes;
+  g.scales = d_cross_scales_ + layout::kv8_scale_index(l, 0, 0, 0, 0, cap_, H);
+  g.scale_slot_stride = (long)H * layout::kKv8ScaleHead;
+  g.group = K; g.slot0 = b0; g.nslots = a.batch;
+  g.n_keys = a.n_keys; g.cap_blocks = a.cap_blocks;
+  launch_decode_cross_attention_group_fp8(g, s);
+  ++enq_group_launches_;
+  ++enq_fp8_launches_;
+}
+
 void Engine::launch_cross_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s) {
-  if (spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, b0, spec.cross_group, s);
+  if (spec.cross_group && spec.cross_fp8 && !a.stamp) launch_cross_attention_group_fp8(a, l, b0, spec.cross_group, s);
+  else if (spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, b0, spec.cross_group, s);
   else if (spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, b0, s);
   else launch_decode_attention(a, s);
 }

@@ -59,9 +59,10 @@ static void usage(const char* prog) {
           "                      as it is, with a warning, and its duration is counted at 16000 Hz\n"
           "      --task T        transcribe or translate (with --timestamps or --long, not with --beam_size) [=transcribe]\n"
           "      --cross_kv h16|fp8   fp8: keep the cross K/V as e4m3fn codes too; decoder steps of more than two clips read them\n"
-          "                      (opt-in, results differ from h16; not under --beam_size)\n"
+          "                      (opt-in, results differ from h16; under --beam_size only with --beam_cross shared)\n"
           "      --beam_cross copy|shared   shared: the hypotheses of a clip under --beam_size read one cross K/V copy, the clip's own\n"
-          "                      (opt-in; a beam's logits differ from the copy path in their last bits)\n"
+          "                      (opt-in; a beam's logits differ from the copy path in their last bits; with --cross_kv fp8 the copy is\n"
+          "                      read as its FP8 codes)\n"
           "      --suppress_tokens -1|1,2,3   (with --timestamps or --long) ids the decode never samples, as openai-whisper's\n"
           "                      suppress_tokens: -1 the non-speech ids of the model's tokens file (brackets, quotes, musical signs),\n"
           "                      or a list; replaces what the config file's \"suppress_tokens\" gave\n"
