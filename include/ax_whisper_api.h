@@ -143,6 +143,22 @@ AX_WHISPER_API int AX_WHISPER_CrossKVQuantize(AX_WHISPER_HANDLE handle);
  *  any other value fails Init with an error text. A beam's logits differ from the copy path's in their last bits (another summation
  *  order). AX_WHISPER_GetConfigInt: "beam_cross_shared" (0 / 1), "beam_cross_shared_launches" (cross-attention launches that took
  *  the grouped kernel). */
+/* Tree self-attention under beam search (opt-in; a mode of Init): on a handle made while the environment variable AX_WHISPER_BEAM_SELF
+ *  is "tree", the self-attention K/V cache never moves between the slots of a clip: a table says for every hypothesis and position
+ *  which slot holds the row, one workgroup per (head, clip) loads every referenced (slot, 64-key block) once for all K hypotheses, and
+ *  the reorder copies table rows instead of cache blocks; in beam calls of more than two slots with K > 1. Absent or "copy": today's
+ *  behaviour; any other value fails Init with an error text. A beam's logits differ from the copy path's in their last bits (another
+ *  summation order). Composes with AX_WHISPER_BEAM_CROSS and AX_WHISPER_CROSS_KV. AX_WHISPER_GetConfigInt: "beam_self_tree" (0 / 1),
+ *  "beam_self_tree_launches" (self-attention launches that took the tree kernel). */
+/** The tree self-attention kernel alone, on host data (the handle gives the device, n_head and d_model = 64 n_head). Slot s is rank
+ *  s % beam_size of clip s / beam_size. q [slots][d_model]; k, v [kv_slots][n_head][cap_keys][64] in logical order as raw 16-bit
+ *  patterns of the handle's storage type (kv_slots >= slots, cap_keys a multiple of 64 up to 512); origin [slots][cap_keys]: the local
+ *  slot (0 .. beam_size - 1) that holds position p < off[s] of slot s's hypothesis (position off[s] is the slot's own); off, done
+ *  [slots]. The kernel runs `launches` times over the slots [slot0, slot0 + nslots) (slot0 a multiple of 16) on the same buffers.
+ *  out [slots][d_model]: hi + lo of the output pair; NaN where no launch wrote (slots outside the range, done slots). */
+AX_WHISPER_API int AX_WHISPER_BeamTreeAttention(AX_WHISPER_HANDLE handle, int slots, int kv_slots, int beam_size, int cap_keys, int slot0,
+                                                int nslots, int launches, const float* q, const uint16_t* k, const uint16_t* v,
+                                                const uint8_t* origin, const int* off, const int* done, float* out);
 /** Parity aid: scan every 16-bit tensor the engine keeps between kernels (encoder activations of clips 0..batch-1, cross and
  *  self K/V caches, the decoder's activation pairs) after EncodeMel / Decode*: names [n_max][32] chars, nonfinite [n_max]
  *  (NaN or Inf elements), maxabs [n_max] (largest finite |x|), *n_out buffers reported. A trained model's outlier channels

@@ -130,6 +130,8 @@ SYMBOLS = {
     "AX_WHISPER_BeamCandidates": (C.c_int, [C.c_void_p, fp, ip, C.POINTER(C.c_int), C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_BeamSelect": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int), ip,
                                         fp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int)]),
+    "AX_WHISPER_BeamTreeAttention": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [fp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
     "AX_WHISPER_BeamFinalize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, ip, fp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp,
                                           ip, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_RunPCMBatchTimestampPrompted": (C.c_int, [C.c_void_p, C.POINTER(fp), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), ip, C.c_int, C.POINTER(C.c_int), ip, C.POINTER(C.c_int), fp, fp, fp, C.POINTER(C.c_int)]),
@@ -635,18 +637,20 @@ class Whisper:
     """Mirror of the reference's ``Whisper`` (python/whisper.py:54-99, cpp/src/Whisper.hpp:28-59)."""
 
     def __init__(self, model_type: str, model_path: str, language: str = "zh", device: int = -1, max_batch: int = 0, devices=None,
-                 cross_kv: str | None = None, beam_cross: str | None = None):
+                 cross_kv: str | None = None, beam_cross: str | None = None, beam_self: str | None = None):
         """devices: a list of HIP ordinals (or "all") -> one engine per device behind this handle (AX_WHISPER_InitMulti).
         cross_kv: "fp8" keeps the cross K/V as e4m3fn codes too and lets decoder steps of more than two clips read them (opt-in;
         DESIGN.md "FP8 cross K/V"); "h16" or None: the h16 images alone.
         beam_cross: "shared" lets the K hypotheses of a clip under beam search read ONE cross K/V copy, the clip's own (opt-in;
         DESIGN.md "Shared cross K/V"); "copy" or None: a copy per hypothesis.
-        The library reads both modes from AX_WHISPER_CROSS_KV / AX_WHISPER_BEAM_CROSS while the handle is made: the variables are
+        beam_self: "tree" keeps the self-attention cache of beam search in place and reads it through an ancestry table, every
+        referenced block once per clip (opt-in; DESIGN.md "Tree self-attention"); "copy" or None: cache blocks move with hypotheses.
+        The library reads the modes from AX_WHISPER_CROSS_KV / AX_WHISPER_BEAM_CROSS / AX_WHISPER_BEAM_SELF while the handle is made: the variables are
         set for that call and put back afterwards, under a lock that every construction with such an argument takes (a handle made
         at the same moment on another thread WITHOUT the arguments, or by other code through the C ABI, reads whatever the variables
         hold then)."""
         self.L = load_library()
-        modes = {k: str(v) for k, v in (("AX_WHISPER_CROSS_KV", cross_kv), ("AX_WHISPER_BEAM_CROSS", beam_cross)) if v is not None}
+        modes = {k: str(v) for k, v in (("AX_WHISPER_CROSS_KV", cross_kv), ("AX_WHISPER_BEAM_CROSS", beam_cross), ("AX_WHISPER_BEAM_SELF", beam_self)) if v is not None}
         if not modes:
             self._init_handle(model_type, model_path, language, device, max_batch, devices)
         else:
@@ -1173,6 +1177,23 @@ class Whisper:
                 hist[s_, n] = tok[s_]
         return dict(K=K, n=n + 1, hist=hist, S=S, slot=slot, pool_n=pool_n, pool_ids=pool_ids.reshape(slots, stride), pool_len=pool_len,
                     pool_score=pool_score, complete=complete, tok=tok, src=src, slot_score=ss, n_completed=done.value)
+
+    def beam_tree_attention(self, q, k, v, origin, off, done, K: int, slot0: int = 0, nslots: int = None, launches: int = 1):
+        """decode_self_attention_tree_kernel alone (AX_WHISPER_BeamTreeAttention). q [slots][d_model] fp32; k, v [kv_slots][n_head][keys][64]
+        uint16 bit patterns of the handle's 16-bit type, logical order; origin [slots][keys] uint8; off, done [slots]. Returns fp32
+        [slots][d_model], hi + lo of the output pair: NaN where the launches over [slot0, slot0 + nslots) wrote nothing."""
+        q, off, done = _f32(q), _i32(off).reshape(-1), _i32(done).reshape(-1)
+        k, v = np.ascontiguousarray(k, dtype=np.uint16), np.ascontiguousarray(v, dtype=np.uint16)
+        origin = np.ascontiguousarray(origin, dtype=np.uint8)
+        slots, keys = origin.shape
+        assert q.shape == (slots, self.n_text_state) and k.shape == v.shape and k.shape[2:] == (keys, 64) and len(off) == len(done) == slots
+        out = np.empty((slots, self.n_text_state), dtype=np.float32)
+        u16p, u8p = C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+        self._check(self.L.AX_WHISPER_BeamTreeAttention(self.h, slots, k.shape[0], int(K), keys, int(slot0), slots - slot0 if nslots is None else int(nslots),
+                                                        int(launches), q.ctypes.data_as(fp), k.ctypes.data_as(u16p), v.ctypes.data_as(u16p),
+                                                        origin.ctypes.data_as(u8p), off.ctypes.data_as(_cip), done.ctypes.data_as(_cip),
+                                                        out.ctypes.data_as(fp)), "BeamTreeAttention")
+        return out
 
     beam_finalize = staticmethod(beam_finalize)
 

@@ -522,7 +522,7 @@ AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char*
   if (!strcmp(key, "n_devices")) return h->group.size();
   if (!strcmp(key, "live_hip_objects")) return (int)axw::live_owned.load();  // test hook: of every handle of the process
   if (!strcmp(key, "persistent_giveups") || !strcmp(key, "persistent_ts_launches") || !strcmp(key, "cross_kv_fp8_launches") ||
-      !strcmp(key, "beam_cross_shared_launches")) {  // counts: summed over the handle's engines
+      !strcmp(key, "beam_cross_shared_launches") || !strcmp(key, "beam_self_tree_launches")) {  // counts: summed over the handle's engines
     long sum = 0;
     for (int i = 0; i < h->group.size(); ++i) {
       Engine& e = h->group.at(i);
@@ -689,6 +689,16 @@ AX_WHISPER_API int AX_WHISPER_BeamSelect(AX_WHISPER_HANDLE handle, int clips, in
     const Engine::BeamSelectIO io{clips, beam_size, eot, n, stride, cand_id, cand_logprob, n_cand, hist, S, slot, pool_n, pool_ids, pool_len,
                                   pool_score, complete, tok, src, slot_score};
     *n_completed = e.beam_select(io);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_BeamTreeAttention(AX_WHISPER_HANDLE handle, int slots, int kv_slots, int beam_size, int cap_keys, int slot0, int nslots,
+                                                int launches, const float* q, const uint16_t* k, const uint16_t* v, const uint8_t* origin,
+                                                const int* off, const int* done, float* out) {
+  if (!handle || !q || !k || !v || !origin || !off || !done || !out || slots < 1) return -1;
+  return guarded(handle, [&](Engine& e) {
+    const Engine::BeamTreeAttnIO io{slots, kv_slots, beam_size, cap_keys, slot0, nslots, launches, q, k, v, origin, off, done, out};
+    e.beam_tree_attention(io);
   });
 }
 

@@ -557,6 +557,26 @@ struct DecAttnGroupFp8Kv {
 struct DecAttnGroupFp8Params : DecAttnGroupFp8Kv, AttnQuerySource, AttnResultSink {};
 void launch_decode_cross_attention_group_fp8(const DecAttnGroupFp8Params& p, hipStream_t s);
 
+// ---- tree self-attention (decode_attention_tree.hip; beam search over an ancestry table, opt-in): the slots [c * group, c * group +
+// group) are the ranks of clip c, the self K/V never moves between them, and origin[slot][p] (uint8, a local slot 0 .. group - 1) says
+// which of the clip's slots holds the K/V row of position p < off[slot] of the hypothesis living in `slot`; position off[slot] is the
+// slot's own (the kernel takes it as such). One workgroup per (head, clip) serves the clip's ranks inside [slot0, slot0 + nslots): it
+// reads K/V of any slot of the clip, and queries, offsets, done flags and outputs of its own ranks only.
+constexpr int kTreeBlocksMax = 8;  // 64-key blocks per (slot, head) the kernel's LDS origin image holds
+struct DecAttnTreeParams {
+  const h16* k; const h16* v; long kv_slot_stride;      // this layer, slot 0 of the HANDLE
+  const unsigned char* origin; int origin_stride;       // slot 0 of the HANDLE; bytes per slot (>= cap_blocks * 64)
+  int group;                                            // ranks per clip, 1 .. 8
+  int slot0, nslots;                                    // the launch's slots; slot0 is a multiple of 16
+  // everything below has the origin of slot0
+  const float* q;                                       // [nslots][d_model]: what the QKV launch wrote
+  const int* off;                                       // [nslots]: the position this step wrote; keys [0, off] are attended over
+  const int* done;                                      // [nslots], never null: a rank whose flag is set gets no output
+  int n_head, d_model, cap_blocks;
+  h16* out_hi; h16* out_lo; int nbs;                    // fragment-major (hi, lo) pair
+};
+void launch_decode_self_attention_tree(const DecAttnTreeParams& p, hipStream_t s);
+
 // ---- batched decode (3..64 clips per launch): activations as h16 (hi, lo) pairs, MFMA GEMM (decode_gemm.hip)
 struct DecGemmParams {
   const h16* W;                           // fragment-major packed weights
@@ -718,6 +738,14 @@ struct BeamReorderParams {
   int n_layer, n_head, n_ctx_pad, off;
 };
 void launch_beam_reorder(const BeamReorderParams& p, hipStream_t s);
+// The reorder of a tree handle (decode_attention_tree.hip): for every slot with src[slot] != slot, hist[0, n) and the origin row
+// [0, n_origin) of slot src; no K/V
+struct BeamAncestryParams {
+  const int* src; int n_slots;
+  int* hist; int hist_stride; int n;
+  unsigned char* origin; int origin_stride; int n_origin;
+};
+void launch_beam_ancestry(const BeamAncestryParams& p, hipStream_t s);
 // cross K/V of slot src -> slots dst0 .. dst0 + n_dst - 1 in every layer (src itself is skipped); slot_elems a multiple of 8.
 // Spreading clips 0 .. C-1 to groups of K: launch for the clips in DESCENDING order (clip i's destinations start at i * K >= i,
 // so sources not yet spread are never overwritten).

@@ -172,6 +172,16 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     cfg_.ints["beam_cross_shared"] = beam_cross_shared_ ? 1 : 0;
     cfg_.ints["beam_cross_shared_launches"] = 0;
   }
+  {  // beam search over an ancestry table (decode_attention_tree.hip): opt-in, absent or "copy": the cache blocks move with the hypotheses
+    const char* e = getenv("AX_WHISPER_BEAM_SELF");
+    if (e && !strcmp(e, "tree")) beam_self_tree_ = true;
+    else if (e && e[0] && strcmp(e, "copy")) throw std::runtime_error(std::string("AX_WHISPER_BEAM_SELF=") + e + ": expected copy or tree");
+    if (beam_self_tree_ && (cfg_.n_text_ctx % layout::kKvBlockKeys != 0 || cfg_.n_text_ctx / layout::kKvBlockKeys > kTreeBlocksMax))
+      throw std::runtime_error("AX_WHISPER_BEAM_SELF=tree: n_text_ctx " + std::to_string(cfg_.n_text_ctx) + " (need a multiple of 64 up to " +
+                               std::to_string(kTreeBlocksMax * layout::kKvBlockKeys) + ")");
+    cfg_.ints["beam_self_tree"] = beam_self_tree_ ? 1 : 0;
+    cfg_.ints["beam_self_tree_launches"] = 0;
+  }
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half
   install_suppress(config_suppress_);
   ensure_capacity(std::max(1, max_batch));

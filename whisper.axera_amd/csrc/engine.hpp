@@ -104,9 +104,9 @@ struct EngineMemory {
 
 struct EngineGraphs {
   // key: Engine::graph_key; with every captured step, the fp8 cross-attention launches one replay of it runs
-  // and the grouped ones (beam search with a shared cross K/V)
-  struct StepGraph { GraphExec exec; int fp8_launches = 0; int group_launches = 0; };
-  struct StepGraphRef { hipGraphExec_t exec; int fp8_launches; int group_launches; operator hipGraphExec_t() const { return exec; } };  // what step_graph() hands out
+  // and the grouped ones (beam search with a shared cross K/V), and the tree self-attention launches (beam search over an ancestry table)
+  struct StepGraph { GraphExec exec; int fp8_launches = 0; int group_launches = 0; int tree_launches = 0; };
+  struct StepGraphRef { hipGraphExec_t exec; int fp8_launches; int group_launches; int tree_launches; operator hipGraphExec_t() const { return exec; } };  // what step_graph() hands out
   std::map<long, StepGraph> graphs_;
 };
 
@@ -151,6 +151,10 @@ struct SlotViews {
     int *hist = nullptr, *cand_id = nullptr, *n_cand = nullptr, *slot = nullptr, *src = nullptr, *pool_n = nullptr, *pool_ids = nullptr,
         *pool_len = nullptr, *complete = nullptr, *n_complete = nullptr;
     float *cand_lp = nullptr, *S = nullptr, *slot_score = nullptr, *pool_score = nullptr;
+    // a tree handle only (AX_WHISPER_BEAM_SELF=tree; common.hpp: DecAttnTreeParams): [cap][n_text_ctx], which local slot of its clip
+    // holds position p of the hypothesis in the slot. Entries at and beyond a slot's offset hold the slot itself (beam_begin writes the
+    // identity, and nothing writes beyond the offset), so a row copied up to the offset INCLUSIVE is the child's row.
+    unsigned char* origin = nullptr;
   } beam_;
   DecState* d_state_ = nullptr;
 };
@@ -193,6 +197,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void beam_candidates(const float* logits, const int32_t* hist, const int* n_hist, int rows, int n_cand_max, int32_t* cand_id,
                        float* cand_logprob, int* n_cand) override;
   int beam_select(const BeamSelectIO& io) override;
+  void beam_tree_attention(const BeamTreeAttnIO& io) override;
   void align_tokens(const AlignRequest& rq) override;
   void set_alignment_heads(const int* pairs, int n) override;
   void set_suppress_tokens(const int* ids, int n) override;
@@ -283,6 +288,10 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     // own. Set by beam_loop alone, on a handle made under AX_WHISPER_BEAM_CROSS=shared. With cross_fp8 set too (a handle with both
     // modes), the launches read slot c's code images instead (decode_attention_group_fp8.hip).
     int cross_group = 0;
+    // beam search over an ancestry table (decode_attention_tree.hip): the self-attention launches of a step of more than gemv_max_
+    // slots run one workgroup per (head, clip) over beam_.origin, and the self K/V never moves between slots; K here, 0: every slot
+    // streams its own cache. Set by beam_step_spec alone, on a handle made under AX_WHISPER_BEAM_SELF=tree.
+    int self_group = 0;
   };
   StepSpec step_spec(DecodeMode mode = kDecodePlain, int mask = 15) const { StepSpec sp{mode, mask}; sp.cross_fp8 = cross_fp8_; return sp; }
   // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
@@ -308,8 +317,9 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // step; one for "a suppress set is installed" where the graph holds a rules launch, which has the mask's pointer by value)
   long graph_key(const StepSpec& spec, int batch, int max_new) const {
     const bool suppress = spec.mode != kDecodePlain && (spec.mask & 4) && suppress_mask();
-    return ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 9) | ((long)spec.cross_group << 5) | (spec.cross_fp8 ? 16 : 0) | (suppress ? 8 : 0) |
-           (spec.slots ? 4 : 0) | spec.mode;
+    // (self_group sits above every other field: a key without it is the number it always was)
+    return ((long)spec.self_group << 56) | ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 9) | ((long)spec.cross_group << 5) |
+           (spec.cross_fp8 ? 16 : 0) | (suppress ? 8 : 0) | (spec.slots ? 4 : 0) | spec.mode;
   }
   void require_timestamp_vocab() const;
   // token suppression (DESIGN.md "Token suppression"; suppress.hpp): the handle's set as a sorted id list, what the config file
@@ -407,7 +417,11 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // beam search (engine_beam.cpp)
   void ensure_beam_buffers();
   void beam_begin(int clips, int K);  // the start state of `clips` groups of K slots, on the stream
-  void enqueue_beam_tail(int clips, int K, int off, int max_new, hipStream_t s);  // candidates, selection, reorder (off >= 2), advance
+  // candidates, selection, reorder (off >= 2; on a tree step the ancestry update instead), advance
+  void enqueue_beam_tail(int clips, int K, int off, int max_new, hipStream_t s);
+  // a tree handle: the origin rows of clips x K slots; position p < prefix of every slot on local slot 0 of its clip (`converged`) or on
+  // the slot itself, the slot itself from there on (beam_begin: prefix 0)
+  void beam_origin_begin(int clips, int K, int prefix, bool converged);
   void beam_spread_cross(int clips, int K);
   int beam_loop(int clips, int K, int max_new, const BeamResult& out, float* no_speech_logprob, BeamTrace* trace);
 
@@ -505,8 +519,20 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     StepSpec sp{kDecodeScored, mask};
     sp.cross_group = beam_cross_group(clips, K);
     sp.cross_fp8 = sp.cross_group && cross_fp8_;
+    sp.self_group = beam_self_group(clips, K);
     return sp;
   }
+  // Tree self-attention under beam search: the handle's mode (AX_WHISPER_BEAM_SELF, read at construction) and the self-attention
+  // launches that took the tree kernel ("beam_self_tree_launches"), counted as the fp8 and grouped launches are
+  bool beam_self_tree_ = false;
+  long self_tree_launches_ = 0;
+  int enq_tree_launches_ = 0;
+  void note_tree_launches(long n) { if (n) { self_tree_launches_ += n; cfg_.ints["beam_self_tree_launches"] = (int)self_tree_launches_; } }
+  // the group size a beam call of clips x K hypotheses runs its self-attention with (0: the copy path), under cross_group's rule
+  int beam_self_group(int clips, int K) const { return beam_self_tree_ && K > 1 && clips * K > gemv_max_ ? K : 0; }
+  // The self-attention launch `a` describes for layer l, slots [b0, b0 + a.batch): the tree kernel where the step asks for it, else
+  // decode_attention_kernel — which a stamped (measurement) launch always keeps
+  void launch_self_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s);
   void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s);
   // the fp8 cross-attention launch of layer l for clips [b0, b0 + nb) with a's query mode, splits and outputs
   void launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s);

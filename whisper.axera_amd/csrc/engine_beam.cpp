@@ -30,6 +30,16 @@ void Engine::ensure_beam_buffers() {
   beam_.pool_n = pooled<int>(slot_allocs_, B, true);
   beam_.complete = pooled<int>(slot_allocs_, B, true);
   beam_.n_complete = pooled<int>(slot_allocs_, 1, true);
+  if (beam_self_tree_) beam_.origin = pooled<unsigned char>(slot_allocs_, B * Tc, true);
+}
+
+void Engine::beam_origin_begin(int clips, int K, int prefix, bool converged) {
+  const int slots = clips * K, Tc = cfg_.n_text_ctx;
+  std::vector<unsigned char> org((size_t)slots * Tc);
+  for (int i = 0; i < slots; ++i)
+    for (int p = 0; p < Tc; ++p) org[(size_t)i * Tc + p] = (unsigned char)(p < prefix && converged ? 0 : i % K);
+  HIP_CHECK(hipMemcpyAsync(beam_.origin, org.data(), org.size(), hipMemcpyHostToDevice, stream()));
+  HIP_CHECK(hipStreamSynchronize(stream()));  // (stack vector)
 }
 
 // Start: rank j in slot c * K + j, S_0 = 0 and the other ranks dead, an empty pool; histories hold valid ids (eot) everywhere, since
@@ -51,6 +61,7 @@ void Engine::beam_begin(int clips, int K) {
   HIP_CHECK(hipMemsetAsync(beam_.complete, 0, (size_t)clips * 4, s));
   HIP_CHECK(hipMemsetAsync(beam_.n_complete, 0, 4, s));
   HIP_CHECK(hipStreamSynchronize(s));  // (stack vectors)
+  if (beam_.origin) beam_origin_begin(clips, K, 0, false);  // every slot starts on its own cache rows
 }
 
 // What follows the logits dump of the step at decode offset `off` (every slot is at the same offset: the loop is lock-step)
@@ -74,7 +85,12 @@ void Engine::enqueue_beam_tail(int clips, int K, int off, int max_new, hipStream
     q.pool_n = beam_.pool_n; q.pool_ids = beam_.pool_ids; q.pool_len = beam_.pool_len; q.pool_score = beam_.pool_score;
     q.complete = beam_.complete; q.n_complete = beam_.n_complete;
     launch_beam_select(q, s);
-    if (K > 1) {  // (one hypothesis per clip never moves)
+    if (beam_self_group(clips, K)) {  // a tree step: the history and the origin row move, positions [0, off] of it; the cache stays
+      BeamAncestryParams r{};
+      r.src = beam_.src; r.n_slots = slots; r.hist = beam_.hist; r.hist_stride = Tc; r.n = n;
+      r.origin = beam_.origin; r.origin_stride = Tc; r.n_origin = std::min(off + 1, Tc);
+      launch_beam_ancestry(r, s);
+    } else if (K > 1) {  // (one hypothesis per clip never moves)
       BeamReorderParams r{};
       r.src = beam_.src; r.n_slots = slots; r.hist = beam_.hist; r.hist_stride = Tc; r.n = n;
       r.k = d_self_k_; r.v = d_self_v_; r.kv_batch_stride = H * layout::kv_head_elems(Tc); r.cap = cap_;
@@ -112,6 +128,7 @@ int Engine::beam_loop(int clips, int K, int max_new, const BeamResult& out, floa
   // for all K ranks, and nothing is spread (on an FP8 handle too: the step then reads slot c's codes, which the encoder pass left
   // there with the slot map of its h16 images); steps of the GEMV family, K = 1 and an FP8 handle without that mode keep a copy per slot
   const StepSpec spec = beam_step_spec(clips, K, 11);
+  if (spec.self_group) ensure_beam_buffers();  // (a tree step's launches carry the ancestry table's address)
   const StepGraphRef g = step_graph(spec, slots, max_new);
   ensure_beam_buffers();
   if (!spec.cross_group) beam_spread_cross(clips, K);
@@ -308,6 +325,58 @@ int Engine::beam_select(const BeamSelectIO& io) {
   HIP_CHECK(hipMemcpy2DAsync(io.tok, 4, b_hist + io.n, (size_t)io.stride * 4, 4, slots, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   return n_complete;
+}
+
+// The tree self-attention kernel alone, on host data (tests). Needs the engine for its device, head count and width.
+void Engine::beam_tree_attention(const BeamTreeAttnIO& io) {
+  require_no_stream("beam_tree_attention");
+  check_beam_size(io.beam, "beam_tree_attention");
+  const int H = cfg_.n_text_head, d = cfg_.n_text_state, K = io.beam, S = io.slots, keys = io.cap_keys;
+  if (S < 1 || S % K != 0 || io.kv_slots < S || keys < 64 || keys % 64 != 0 || keys / 64 > kTreeBlocksMax || io.slot0 < 0 || io.slot0 % 16 != 0 ||
+      io.nslots < 1 || io.slot0 + io.nslots > S || io.launches < 1 || !io.q || !io.k || !io.v || !io.origin || !io.off || !io.done || !io.out)
+    throw std::runtime_error("beam_tree_attention: bad arguments (whole clips of beam_size slots, 64 .. " + std::to_string(kTreeBlocksMax * 64) +
+                             " keys in whole blocks, a slot range inside them that starts at a multiple of 16)");
+  for (int i = 0; i < S; ++i) {  // the kernel indexes with these
+    if (io.off[i] < 0 || io.off[i] >= keys) throw std::runtime_error("beam_tree_attention: offset out of range");
+    for (int p = 0; p < io.off[i]; ++p)
+      if (io.origin[(size_t)i * keys + p] >= K) throw std::runtime_error("beam_tree_attention: origin entry beyond the clip's slots");
+  }
+  // K into the blocked cache layout; V is row-major there as here
+  const size_t head = (size_t)layout::kv_head_elems(keys), per = H * head, nbs = (S + 15) / 16;
+  std::vector<uint16_t> kp((size_t)io.kv_slots * per);
+  for (size_t sh = 0; sh < (size_t)io.kv_slots * H; ++sh)
+    for (int t = 0; t < keys; ++t)
+      for (int c = 0; c < layout::kKvDim; ++c) kp[sh * head + layout::k_index(t, c)] = io.k[sh * head + (size_t)t * layout::kKvDim + c];
+  const size_t pair = (size_t)layout::pair_elems(d / 32, (int)nbs);
+  const std::vector<uint16_t> fill(pair, 0xffffu);  // NaN bits in both 16-bit formats
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  hipStream_t s = stream();
+  DeviceArray<h16> b_k = device_array<h16>(kp.size()), b_v = device_array<h16>(kp.size()), b_hi = device_array<h16>(pair), b_lo = device_array<h16>(pair);
+  DeviceArray<float> b_q = device_array<float>((size_t)S * d);
+  DeviceArray<unsigned char> b_org = device_array<unsigned char>((size_t)S * keys);
+  DeviceArray<int> b_off = device_array<int>(S), b_done = device_array<int>(S);
+  auto up = [&](void* dst, const void* src, size_t bytes) { HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s)); };
+  up(b_k, kp.data(), kp.size() * 2); up(b_v, io.v, kp.size() * 2); up(b_hi, fill.data(), pair * 2); up(b_lo, fill.data(), pair * 2);
+  up(b_q, io.q, (size_t)S * d * 4); up(b_org, io.origin, (size_t)S * keys); up(b_off, io.off, (size_t)S * 4); up(b_done, io.done, (size_t)S * 4);
+  DecAttnTreeParams t{};
+  t.k = b_k; t.v = b_v; t.kv_slot_stride = (long)per;
+  t.origin = b_org; t.origin_stride = keys;
+  t.group = K; t.slot0 = io.slot0; t.nslots = io.nslots;
+  t.q = b_q + (size_t)io.slot0 * d; t.off = b_off + io.slot0; t.done = b_done + io.slot0;
+  t.n_head = H; t.d_model = d; t.cap_blocks = keys / 64;
+  t.out_hi = b_hi + layout::clip_block_offset(io.slot0); t.out_lo = b_lo + layout::clip_block_offset(io.slot0); t.nbs = (int)nbs;
+  for (int i = 0; i < io.launches; ++i) launch_decode_self_attention_tree(t, s);
+  HIP_CHECK(hipGetLastError());
+  std::vector<uint16_t> hi(pair), lo(pair);
+  HIP_CHECK(hipMemcpyAsync(hi.data(), b_hi, pair * 2, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(lo.data(), b_lo, pair * 2, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  for (int i = 0; i < S; ++i)
+    for (int c = 0; c < d; ++c) {
+      const size_t at = (size_t)layout::frag_index(i, c, (int)nbs);
+      io.out[(size_t)i * d + c] = h16_bits_to_float(hi[at]) + h16_bits_to_float(lo[at]);
+    }
 }
 
 }  // inline namespace AXW_NS

@@ -214,6 +214,8 @@ float Engine::bench_word_logprob(const std::string& what, int batch, int arg, in
 // stream_step_ts: the scored step of the slot stream in timestamp mode (stream_rules_kernel, a prefix per slot), the same placement;
 // decode_attn_beam: decode_attn of the beam step of `batch` slots in groups of arg (the beam size) at offset 224: on a shared-cross
 // handle the cross-attention launches are the grouped ones
+static bool bench_tree_identity() { const char* e = getenv("AX_WHISPER_BENCH_TREE_PREFIX"); return e && !strcmp(e, "identity"); }
+
 float Engine::bench_decode_step(const std::string& what, int batch, int arg, int iters) {
   const bool attn_beam = what == "decode_attn_beam";
   if (attn_beam && (arg < 1 || arg > kBeamMax || batch % arg != 0)) throw std::runtime_error("bench decode_attn_beam: arg is the beam size, batch a multiple of it");
@@ -236,10 +238,15 @@ float Engine::bench_decode_step(const std::string& what, int batch, int arg, int
     upload_sample(SampleSpec{temps.data(), streams.data(), 1}, batch);
   }
   spec.mask = whole ? 15 : (what == "decode_gemv" ? 1 : 2);
+  const int beam_clips = attn_beam ? batch / arg : 0, beam_size = arg;
   if (attn_beam) { spec = beam_step_spec(batch / arg, arg, 2); arg = 224; }
   hipStream_t s = stream();
   const int Tc = cfg_.n_text_ctx;
   reset_decode_state(batch);
+  if (spec.self_group) {  // a tree step reads the ancestry table: the placement of bench_decode_step_beam
+    ensure_beam_buffers();
+    beam_origin_begin(beam_clips, beam_size, std::max(0, std::min(arg, Tc - 1 - iters)), !bench_tree_identity());
+  }
   const StepGraphRef g = step_graph(spec, batch, Tc - 4);
   arg = std::max(0, std::min(arg, Tc - 1 - iters));
   DecState st{arg, 0, 0, 0};
@@ -266,7 +273,8 @@ float Engine::bench_decode_step_beam(int slots, int beam_size, int iters) {
   if (slots < beam_size || slots % beam_size != 0) throw std::runtime_error("bench decode_step_beam: batch must be a multiple of the beam size");
   const int clips = slots / beam_size, Tc = cfg_.n_text_ctx;
   hipStream_t s = stream();
-  const StepSpec spec = beam_step_spec(clips, beam_size, 11);  // (a shared-cross handle measures the shared step, as beam_loop runs it)
+  const StepSpec spec = beam_step_spec(clips, beam_size, 11);  // (a shared-cross or tree handle measures its own step, as beam_loop runs it)
+  if (spec.self_group) ensure_beam_buffers();
   const StepGraphRef g = step_graph(spec, slots, Tc - 3);
   ensure_beam_buffers();
   const int off0 = std::max(2, std::min(224, Tc - 2 - iters));
@@ -285,6 +293,10 @@ float Engine::bench_decode_step_beam(int slots, int beam_size, int iters) {
     HIP_CHECK(hipMemsetAsync(d_self_v_, 0, self_bytes, s));
     reset_decode_state(slots);
     beam_begin(clips, beam_size);
+    // A tree handle: a decode that has reached off0 has long lost all but one ancestor of its early positions (the loop below moves
+    // 30 % of the slots per step), so positions [0, off0) start on ONE slot per clip; AX_WHISPER_BENCH_TREE_PREFIX=identity starts
+    // them on K different slots instead, the worst case, which no decode reaches. From off0 on the table is what the steps make it.
+    if (spec.self_group) beam_origin_begin(clips, beam_size, off0, !bench_tree_identity());
     place();
     launch_step_graph(g, s);  // warm
     enqueue_beam_tail(clips, beam_size, off0, Tc - 3, s);
@@ -314,6 +326,23 @@ float Engine::bench_decode_step_beam(int slots, int beam_size, int iters) {
   HIP_CHECK(hipMemcpyAsync(&n_complete, beam_.n_complete, 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   cfg_.ints["beam_bench_moved_slots"] = moved;
+  // a tree handle: the (slot, block) loads the counted pass's LAST step needed per layer and head against the copy path's K per block
+  long blocks_needed = 0, blocks_total = 0;
+  if (spec.self_group && ran > 0) {
+    const int off = off0 + ran - 1, K = beam_size;
+    std::vector<unsigned char> org((size_t)slots * Tc);
+    HIP_CHECK(hipMemcpy(org.data(), beam_.origin, org.size(), hipMemcpyDeviceToHost));
+    for (int c = 0; c < clips; ++c)
+      for (int b = 0; b <= off / 64; ++b) {
+        unsigned need = 0;
+        for (int r = 0; r < K; ++r)
+          for (int p = b * 64; p < std::min(b * 64 + 64, off + 1); ++p) need |= 1u << (p == off ? r : org[(size_t)(c * K + r) * Tc + p]);
+        blocks_needed += __builtin_popcount(need);
+        blocks_total += K;
+      }
+  }
+  cfg_.ints["beam_bench_self_blocks_needed"] = (int)blocks_needed;
+  cfg_.ints["beam_bench_self_blocks_total"] = (int)blocks_total;
   cfg_.ints["beam_bench_iters"] = ran;
   cfg_.ints["beam_bench_complete_clips"] = n_complete;
   return ms;

@@ -36,11 +36,12 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
   // 3+ clips: the clip-block sequence (a 4-clip step: 0.78 ms through the GEMV family, 0.59 through clip-block GEMMs);
   // one clip that cannot use the persistent launch and two clips that cannot either stay on the GEMV family
   if (batch > gemv_max_) {
-    const int fp8_before = enq_fp8_launches_, group_before = enq_group_launches_;
+    const int fp8_before = enq_fp8_launches_, group_before = enq_group_launches_, tree_before = enq_tree_launches_;
     enqueue_decode_step_batched(spec, batch, max_new, d_forced, n_forced, d_logits, logits_stride, d_argmax);
     if (!in_step_capture_) {  // enqueued directly: these launches run once
       note_fp8_launches(enq_fp8_launches_ - fp8_before);
       note_group_launches(enq_group_launches_ - group_before);
+      note_tree_launches(enq_tree_launches_ - tree_before);
     }
     return;
   }
@@ -217,6 +218,27 @@ void Engine::launch_cross_attention(const StepSpec& spec, const DecAttnParams& a
   else launch_decode_attention(a, s);
 }
 
+// The self-attention launch `a` describes for slots [b0, b0 + nb): on a tree step ONE workgroup per (head, clip) over the ancestry
+// table, reading the K/V of any slot of the clip (a branch's launch may read slots of the branch beside it: positions below the
+// step's offset, which nobody writes any more)
+void Engine::launch_self_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s) {
+  if (!spec.self_group || a.stamp) { launch_decode_attention(a, s); return; }
+  if (!beam_.origin) throw std::runtime_error("tree self-attention: the ancestry table is not allocated (ensure_beam_buffers comes first)");
+  const int Tc = cfg_.n_text_ctx;
+  const long slot_elems = cfg_.n_text_head * layout::kv_head_elems(Tc);
+  DecAttnTreeParams t{};
+  t.k = d_self_k_ + (size_t)l * cap_ * slot_elems;
+  t.v = d_self_v_ + (size_t)l * cap_ * slot_elems;
+  t.kv_slot_stride = slot_elems;
+  t.origin = beam_.origin; t.origin_stride = Tc;
+  t.group = spec.self_group; t.slot0 = b0; t.nslots = a.batch;
+  t.q = a.q; t.off = a.off; t.done = a.done;
+  t.n_head = a.n_head; t.d_model = a.d_model; t.cap_blocks = a.cap_blocks;
+  t.out_hi = a.out_hi; t.out_lo = a.out_lo; t.nbs = a.nbs;
+  launch_decode_self_attention_tree(t, s);
+  ++enq_tree_launches_;
+}
+
 int Engine::cross_split_count(int wg_per_split, int blocks, int wg_limit) const {
   if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && blocks % cross_split_env_ == 0) return cross_split_env_;
   for (int c : {6, 4, 3, 2})
@@ -229,6 +251,7 @@ void Engine::launch_step_graph(const StepGraphRef& g, hipStream_t s) {
   HIP_CHECK(hipGraphLaunch(g.exec, s));
   note_fp8_launches(g.fp8_launches);
   note_group_launches(g.group_launches);
+  note_tree_launches(g.tree_launches);
 }
 
 // bench "attn_stamp" (StepSpec::mask bit 16): the next {min begin, max end} slot, with what the launch is
@@ -317,7 +340,7 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
     c.out = qd; c.k_cache = sk; c.v_cache = sv; c.kv_batch_stride = self_stride;
     if (qfold) { c.fold_row0 = 3 * d; c.ln_w2 = w.cross_ln_w; c.out2 = a0; }
     cgo(c, 2);
-    if (spec.mask & 2) { DecAttnParams a = attn(sk, sv, self_stride, -1, Tc / 64); a.stamp = next_stamp(spec, l, 0, b0, nb); launch_decode_attention(a, s); }
+    if (spec.mask & 2) { DecAttnParams a = attn(sk, sv, self_stride, -1, Tc / 64); a.stamp = next_stamp(spec, l, 0, b0, nb); launch_self_attention(spec, a, l, b0, s); }
     c = qfold ? cgemm(wq.w_o, cfold_[l].b_o2, 2 * d, d, GEPI_RESID, 1) : cgemm(wq.w_o, w.b_o, d, d, GEPI_RESID, 1);
     c.a_hi = att_hi; c.a_lo = att_lo; c.out = x;
     if (qfold) { c.fold_row0 = d; c.W_lo = wq.m_lo; c.out2 = a0; c.stat_part = statp; }
@@ -438,7 +461,7 @@ void Engine::enqueue_decode_step_batched(const StepSpec& spec, int batch, int ma
     a.stamp = next_stamp(spec, l, n_keys >= 0 ? 1 : 0, 0, batch);
     if (!(spec.mask & 2)) return;
     if (n_keys >= 0) launch_cross_attention(spec, a, l, 0, s);
-    else launch_decode_attention(a, s);
+    else launch_self_attention(spec, a, l, 0, s);
   };
   auto base = [&](const h16* W, const float* bias, int N, int K, const h16* ahi, const h16* alo, int epi) {
     DecGemmParams p{};
@@ -568,7 +591,7 @@ void Engine::ensure_branch_streams(int batch) {
 Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
   const long key = graph_key(spec, batch, max_new);  // plain and timestamp-mode steps are different graphs
   auto it = graphs_.find(key);
-  if (it != graphs_.end()) return {it->second.exec, it->second.fp8_launches, it->second.group_launches};
+  if (it != graphs_.end()) return {it->second.exec, it->second.fp8_launches, it->second.group_launches, it->second.tree_launches};
   hipStream_t s = stream();
   // nobody on this device allocates, copies synchronously or captures while this capture is open (iengine.hpp)
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
@@ -581,6 +604,7 @@ Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
   const ScopedSet<bool> capturing(in_step_capture_, true);  // what the capture enqueues has not run: it is counted per replay
   enq_fp8_launches_ = 0;
   enq_group_launches_ = 0;
+  enq_tree_launches_ = 0;
   try {
     enqueue_decode_step(spec, batch, max_new, nullptr, 0, nullptr, 0, nullptr);
     cap_err = hipStreamEndCapture(s, &captured);
@@ -622,8 +646,8 @@ Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
       cfg_.ints["graph_queue_aligned"] = aligned ? 1 : 0;
     }
   }
-  StepGraph& kept = graphs_[key] = StepGraph{std::move(exec), enq_fp8_launches_, enq_group_launches_};
-  return {kept.exec, kept.fp8_launches, kept.group_launches};
+  StepGraph& kept = graphs_[key] = StepGraph{std::move(exec), enq_fp8_launches_, enq_group_launches_, enq_tree_launches_};
+  return {kept.exec, kept.fp8_launches, kept.group_launches, kept.tree_launches};
 }
 
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.

@@ -168,6 +168,17 @@ class IEngine {
     int32_t* tok; int* src; float* slot_score;
   };
   virtual int beam_select(const BeamSelectIO& io) = 0;
+  // decode_self_attention_tree_kernel alone on host data (common.hpp: DecAttnTreeParams; the model's head count and width): slot s is
+  // rank s % beam of clip s / beam. q [slots][d_model]; k, v [kv_slots][n_head][cap_keys][64] in logical order as raw 16-bit patterns
+  // (kv_slots >= slots; packed into the cache layouts of decode_layout.hpp in scratch memory); origin [slots][cap_keys]; off, done
+  // [slots]. The kernel is launched `launches` times over the slots [slot0, slot0 + nslots) on output pairs filled with NaN bits;
+  // out [slots][d_model]: hi + lo of the pair, NaN where no launch wrote.
+  struct BeamTreeAttnIO {
+    int slots, kv_slots, beam, cap_keys, slot0, nslots, launches;
+    const float* q; const uint16_t* k; const uint16_t* v; const uint8_t* origin; const int* off; const int* done;
+    float* out;
+  };
+  virtual void beam_tree_attention(const BeamTreeAttnIO& io) = 0;
   // ---- word-level timestamps (engine_align.cpp; DESIGN.md "Word-level timestamps"); refuses an open Stream*
   // After encode_mel: the alignment of slots [0, batch). Clip b: n_ids[b] text ids (< eot) at ids + b * stride, num_frames[b] mel
   // frames of its own (it aligns against num_frames[b] / 2 encoder frames), language index lang[b] (-1 or a null array: the handle's),

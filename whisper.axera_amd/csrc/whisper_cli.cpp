@@ -63,6 +63,8 @@ static void usage(const char* prog) {
           "      --beam_cross copy|shared   shared: the hypotheses of a clip under --beam_size read one cross K/V copy, the clip's own\n"
           "                      (opt-in; a beam's logits differ from the copy path in their last bits; with --cross_kv fp8 the copy is\n"
           "                      read as its FP8 codes)\n"
+          "      --beam_self copy|tree   tree: the self-attention cache under --beam_size stays in place and is read through an ancestry\n"
+          "                      table, every referenced block once per clip (opt-in; logits differ from the copy path in their last bits)\n"
           "      --suppress_tokens -1|1,2,3   (with --timestamps or --long) ids the decode never samples, as openai-whisper's\n"
           "                      suppress_tokens: -1 the non-speech ids of the model's tokens file (brackets, quotes, musical signs),\n"
           "                      or a list; replaces what the config file's \"suppress_tokens\" gave\n"
@@ -418,7 +420,7 @@ int main(int argc, char** argv) {
   bool timestamps = false, longform = false, word_timestamps = false;
   bool condition = false, detect = false, chunked = false;
   std::string task_arg, cmax_arg, cmin_arg, csmooth_arg;
-  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg, suppress_arg, cross_kv_arg, beam_cross_arg;
+  std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg, suppress_arg, cross_kv_arg, beam_cross_arg, beam_self_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -436,7 +438,8 @@ int main(int argc, char** argv) {
         val("compression_ratio_threshold", nullptr, crt_arg) || val("temperature_increment", nullptr, tinc_arg) || val("seed", nullptr, seed_arg) ||
         val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg) || val("task", nullptr, task_arg) ||
         val("chunk_max_s", nullptr, cmax_arg) || val("chunk_min_s", nullptr, cmin_arg) || val("chunk_smooth_ms", nullptr, csmooth_arg) ||
-        val("suppress_tokens", nullptr, suppress_arg) || val("cross_kv", nullptr, cross_kv_arg) || val("beam_cross", nullptr, beam_cross_arg))
+        val("suppress_tokens", nullptr, suppress_arg) || val("cross_kv", nullptr, cross_kv_arg) || val("beam_cross", nullptr, beam_cross_arg) ||
+        val("beam_self", nullptr, beam_self_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -455,6 +458,8 @@ int main(int argc, char** argv) {
   if (!cross_kv_arg.empty()) setenv("AX_WHISPER_CROSS_KV", cross_kv_arg.c_str(), 1);
   // --beam_cross copy | shared: likewise, from AX_WHISPER_BEAM_CROSS
   if (!beam_cross_arg.empty()) setenv("AX_WHISPER_BEAM_CROSS", beam_cross_arg.c_str(), 1);
+  // --beam_self copy | tree: from AX_WHISPER_BEAM_SELF
+  if (!beam_self_arg.empty()) setenv("AX_WHISPER_BEAM_SELF", beam_self_arg.c_str(), 1);
   int beam_size = 1;
   if (!beam_arg.empty()) {
     char* end = nullptr;
