@@ -633,6 +633,22 @@ AX_WHISPER_API int AX_WHISPER_ConfigAlignmentHeads(const char* config_path, int 
 AX_WHISPER_API int AX_WHISPER_SetSuppressTokens(AX_WHISPER_HANDLE handle, const int* ids, int n);
 /** The set in use, sorted, duplicates dropped (at most n_max ids; -1 if there are more). */
 AX_WHISPER_API int AX_WHISPER_GetSuppressTokens(AX_WHISPER_HANDLE handle, int n_max, int* ids, int* n);
+/** Repetition rules (DESIGN.md "Repetition rules"): CTranslate2's and transformers' repetition_penalty and no_repeat_ngram_size, applied
+ *  inside the rules kernels to the raw row of every sampled step of timestamp mode, before the suppress set and rules 2 to 5, from the
+ *  clip's own history (the ids sampled or teacher-forced so far, prefix and prompt excluded, timestamps counting as elements).
+ *  repetition_penalty p > 0 (1.0: off): every distinct text id c < eot of the history gets x[c] = x[c] < 0 ? x[c] * p : x[c] / p, once
+ *  however often it occurs; timestamps and eot are never scaled (a closed pair repeats a timestamp by rule: the one deviation from
+ *  transformers). no_repeat_ngram_size g (0: off, or 2 .. 16): the text id that would complete a g-gram already in the history counts
+ *  as -inf; a continuation that is a timestamp or eot is never banned. Log-probabilities and draws are taken from the edited row;
+ *  no_speech_logprob, language detection and the word-timestamp token probabilities are not edited, plain mode is not filtered. Every
+ *  entry point that picks up the suppress set picks these up, beam search with each hypothesis' own history. -1 with an error text
+ *  for p <= 0 or not finite, g of 1, below 0 or above 16, or while a stream is open. (1.0, 0): off, and nothing this library computes
+ *  or launches differs from a handle that never called this. The optional keys "repetition_penalty" and "no_repeat_ngram_size" of
+ *  {type}_config.json give a handle its starting values. GetConfigInt "repetition_rules": 0 or 1, "no_repeat_ngram_size": g. With
+ *  several devices every engine gets the values. */
+AX_WHISPER_API int AX_WHISPER_SetRepetitionRules(AX_WHISPER_HANDLE handle, float repetition_penalty, int no_repeat_ngram_size);
+/** The values in use. */
+AX_WHISPER_API int AX_WHISPER_GetRepetitionRules(AX_WHISPER_HANDLE handle, float* repetition_penalty, int* no_repeat_ngram_size);
 /** Host only: openai-whisper's non_speech_tokens (what its suppress_tokens = -1 stands for) from a {type}-tokens.txt, sorted: the
  *  first id of " -" and " '", and for every symbol of its list the first id of the symbol and of " " + symbol where that is the
  *  whole encoding or the symbol is one of the musical signs; 82 ids for the multilingual vocabulary. -1 with an error text

@@ -175,6 +175,8 @@ SYMBOLS = {
     "AX_WHISPER_ConfigAlignmentHeads": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "AX_WHISPER_SetSuppressTokens": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "AX_WHISPER_GetSuppressTokens": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "AX_WHISPER_SetRepetitionRules": (C.c_int, [C.c_void_p, C.c_float, C.c_int]),
+    "AX_WHISPER_GetRepetitionRules": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "AX_WHISPER_NonSpeechTokens": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "AX_WHISPER_ConfigSuppressTokens": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "AX_WHISPER_AlignQKSoftmax": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.POINTER(C.c_int), fp, C.c_int,
@@ -1215,6 +1217,19 @@ class Whisper:
         ids, n = np.zeros(n_max, dtype=np.int32), C.c_int()
         self._check(self.L.AX_WHISPER_GetSuppressTokens(self.h, n_max, _ci(ids), C.byref(n)), "GetSuppressTokens")
         return [int(x) for x in ids[: n.value]]
+
+    # ---- repetition rules (DESIGN.md "Repetition rules")
+    def set_repetition_rules(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
+        """AX_WHISPER_SetRepetitionRules: the penalty (> 0; 1.0 off) on the text ids of a clip's history and the size (0 off, 2 .. 16) of
+        the n-grams no timestamp-mode decode of this handle repeats; both edit the row before the suppress set and the timestamp rules."""
+        self._check(self.L.AX_WHISPER_SetRepetitionRules(self.h, float(repetition_penalty), int(no_repeat_ngram_size)), "SetRepetitionRules")
+
+    @property
+    def repetition_rules(self):
+        """AX_WHISPER_GetRepetitionRules: (repetition_penalty, no_repeat_ngram_size) in use."""
+        p, g = C.c_float(), C.c_int()
+        self._check(self.L.AX_WHISPER_GetRepetitionRules(self.h, C.byref(p), C.byref(g)), "GetRepetitionRules")
+        return float(p.value), int(g.value)
 
     # ---- word-level timestamps (DESIGN.md "Word-level timestamps")
     def set_alignment_heads(self, pairs=None):

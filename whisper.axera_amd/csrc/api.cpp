@@ -1421,6 +1421,28 @@ AX_WHISPER_API int AX_WHISPER_GetSuppressTokens(AX_WHISPER_HANDLE handle, int n_
   return guarded(handle, [&](Engine& e) { copy_ids_out(e.suppress_tokens(), n_max, ids, n, "get_suppress_tokens"); });
 }
 
+// ---- repetition rules (DESIGN.md "Repetition rules")
+AX_WHISPER_API int AX_WHISPER_SetRepetitionRules(AX_WHISPER_HANDLE handle, float repetition_penalty, int no_repeat_ngram_size) {
+  if (!handle) return -1;
+  return guarded_group(handle, [&](axw::DeviceGroup<Engine>& g) {
+    // every engine gets the values or none does: all of them held and every refusal asked for before the first install
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (int i = 0; i < g.size(); ++i) locks.emplace_back(g.at(i).mutex());
+    axw::check_repetition_rules(repetition_penalty, no_repeat_ngram_size, "set_repetition_rules");
+    for (int i = 0; i < g.size(); ++i) {
+      const auto it = g.at(i).config().ints.find("stream_slots");
+      if (it != g.at(i).config().ints.end() && it->second > 0)
+        throw std::runtime_error("set_repetition_rules: not while a stream is open (engine " + std::to_string(i) + "); the stream's captured step has made its choice");
+    }
+    for (int i = 0; i < g.size(); ++i) g.at(i).set_repetition_rules(repetition_penalty, no_repeat_ngram_size);
+  });
+}
+
+AX_WHISPER_API int AX_WHISPER_GetRepetitionRules(AX_WHISPER_HANDLE handle, float* repetition_penalty, int* no_repeat_ngram_size) {
+  if (!handle || !repetition_penalty || !no_repeat_ngram_size) return -1;
+  return guarded(handle, [&](Engine& e) { e.repetition_rules(repetition_penalty, no_repeat_ngram_size); });
+}
+
 // Host only: the list that suppress_tokens = -1 stands for, derived from a tokens file
 AX_WHISPER_API int AX_WHISPER_NonSpeechTokens(const char* tokens_path, int n_max, int* ids, int* n) {
   if (!tokens_path || !n || n_max < 0 || (n_max > 0 && !ids)) return -1;

@@ -669,8 +669,13 @@ struct TsRulesArgs {
 };
 // What callers fill in. suppress stands behind TsRulesArgs, not inside it: the argument block of the rules kernels, and with it the
 // code of every launch without a set, is what it was before there were sets; a launch with one runs the kernels' second instantiation.
+// Repetition rules (DESIGN.md "Repetition rules"): the handle's two values in device memory, read by the kernels' rules
+// instantiation, so that a captured step depends on "rules on or off" alone. penalty > 0 (1: none), ngram 0 (none) or 2 .. 16.
+constexpr int kNoRepeatNgramMax = 16;
+struct RepRules { float penalty; int ngram; };
 struct TsRulesParams : TsRulesArgs {
   const unsigned* suppress;          // token suppression (suppress.hpp: the mask of the handle's set), or nullptr: no set
+  const RepRules* rep;               // repetition rules (device), or nullptr: off; set: the kernels' third instantiation runs
 };
 void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s);
 // Scored form (DESIGN.md "Confidence"): the rules kernel that also writes, for every clip that samples at this step, the
@@ -714,6 +719,8 @@ struct BeamCandParams {
   const unsigned* suppress;          // token suppression (suppress.hpp: the mask of the handle's set), or nullptr: no set
 };
 void launch_beam_candidates(const BeamCandParams& p, hipStream_t s);
+// The same under the repetition rules (decode_beam_rep.hip): each slot's row is edited from its own history before the set and the rules
+void launch_beam_candidates_rep(const BeamCandParams& p, const RepRules* rules, hipStream_t s);
 // One wave per clip: score = S[parent] + logprob in float32; order by score descending, parent rank, position; walk as
 // openai-whisper's BeamSearchDecoder.update. All state is read first and then overwritten in place.
 struct BeamSelectParams {

@@ -9,153 +9,20 @@
 //   beam_spread_cross_kernel  before the loop: the cross K/V of a clip into the K slots of its group
 //
 // The three step kernels run one after the other on one stream and never communicate inside a launch. The rules themselves are
-// decode_rules.hpp's; the candidates kernel's loops over the row are its own (they feed sorted lists).
-#include "decode_rules.hpp"
+// decode_rules.hpp's; the candidates kernel's loops over the row are its own (they feed sorted lists): beam_candidates_body.inc,
+// whose second instantiation, under the repetition rules, is decode_beam_rep.hip's.
+#include "decode_beam_candidates.hpp"
 
 namespace axw {
 inline namespace AXW_NS {
 
-namespace {
-
-constexpr int kM = kBeamMaxCand;  // list length: every M <= 9 is served by the same fully unrolled lists
-constexpr int kNoId = 0x7fffffff;
-
-// A thread's sorted top-kM list: value descending, and among equal values the id that came first (a thread meets its ids in
-// ascending order, so that is the lower id). Static indices only: the arrays live in registers.
-struct TopList {
-  float v[kM];
-  int i[kM];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int j = 0; j < kM; ++j) { v[j] = -INFINITY; i[j] = kNoId; }
-  }
-  // NaN and -inf never enter (neither compares greater than the -inf the list starts with)
-  __device__ __forceinline__ void push(float x, int id) {
-    if (!(x > v[kM - 1])) return;
-    v[kM - 1] = x; i[kM - 1] = id;
-#pragma unroll
-    for (int j = kM - 1; j > 0; --j) {
-      const bool up = v[j] > v[j - 1];  // strict: never past an equal value that came earlier
-      const float tv = v[j - 1];
-      const int ti = i[j - 1];
-      v[j - 1] = up ? v[j] : tv; i[j - 1] = up ? i[j] : ti;
-      v[j] = up ? tv : v[j];     i[j] = up ? ti : i[j];
-    }
-  }
-  __device__ __forceinline__ void pop() {
-#pragma unroll
-    for (int j = 0; j < kM - 1; ++j) { v[j] = v[j + 1]; i[j] = i[j + 1]; }
-    v[kM - 1] = -INFINITY; i[kM - 1] = kNoId;
-  }
-};
-
-// the wave's M best (value descending, lowest id on ties) -> out_v / out_i [M] in LDS, by M rounds of wave_argmax over the heads
-__device__ __forceinline__ void wave_top(TopList& l, int M, float* out_v, int* out_i, int lane) {
-  for (int r = 0; r < M; ++r) {
-    float bv = l.v[0];
-    int bi = l.i[0];
-    wave_argmax(bv, bi);
-    if (bi != kNoId && bi == l.i[0]) l.pop();  // ids are unique over the wave: exactly one lane owns the winner
-    if (lane == 0) { out_v[r] = bv; out_i[r] = bi; }
-  }
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(256) void beam_candidates_kernel(BeamCandParams p) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x;
-  const int E = p.eot, M = p.n_cand_max;
-  // dead hypotheses and frozen clips propose nothing
-  if ((p.slot_score && p.slot_score[b] == -INFINITY) || (p.complete && p.complete[b / p.beam])) {
-    if (tid == 0) p.n_cand[b] = 0;
-    return;
-  }
-  // ---- the slot's history: ids sampled so far (prefix excluded)
-  const int n = min(max(p.n_hist ? p.n_hist[b] : p.n, 0), p.hist_stride);
-  const AllowedSets a = allowed_sets(p.hist + (long)b * p.hist_stride, n, p.ts_begin, E, p.n_vocab);
-
-  const float* row = p.logits + (long)b * p.stride;
-  float tv = -INFINITY;                    // best unmasked id below T (rule 5's right-hand side)
-  float m = -INFINITY, s = 0.f;            // online logsumexp over the unmasked timestamps
-  float mt = -INFINITY, st = 0.f;          // ... over the unmasked text ids and eot
-  TopList lt, ls;                          // text + eot / timestamps: rule 5 is only known after the reduction
-  lt.clear();
-  ls.clear();
-  for (int c = (a.text_begin >> 2) + tid; 4 * c < a.text_end; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
-    const unsigned sup = p.suppress ? suppress_bits4(p.suppress, c) : 0u;  // (measured: this loop loses nothing to the test inside it)
-    float x[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = 4 * c + e;
-      x[e] = (text_id_on(a, i, E) && !suppressed(sup, e) && v[e] == v[e]) ? v[e] : -INFINITY;
-      tv = fmaxf(tv, x[e]);
-      lt.push(x[e], i);
-    }
-    lse_add4(mt, st, x[0], x[1], x[2], x[3]);
-  }
-  for (int c = (a.ts_lo >> 2) + tid; 4 * c < a.ts_hi; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
-    float x[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = 4 * c + e;
-      x[e] = (timestamp_on(a, i) && v[e] == v[e]) ? v[e] : -INFINITY;
-      ls.push(x[e], i);
-    }
-    lse_add4(m, s, x[0], x[1], x[2], x[3]);
-  }
-  // ---- reductions: value pairs merged in a fixed order (lanes by xor butterfly, then waves 0..3)
-  tv = wave_max(tv);
-  lse_wave_reduce(m, s);
-  lse_wave_reduce(mt, st);
-  // lists 0..3: the waves' text lists, 4..7: their timestamp lists
-  __shared__ float s_tv[4], s_m[4], s_s[4], s_mt[4], s_st[4];
-  __shared__ float s_lv[8][kM];
-  __shared__ int s_li[8][kM];
-  // (the waves' values go to LDS before the list rounds and thread 0 reads its own back: nothing but the lists is live across the
-  // rounds, where the register count of this kernel peaks)
-  if (lane == 0) { s_tv[wave] = tv; s_m[wave] = m; s_s[wave] = s; s_mt[wave] = mt; s_st[wave] = st; }
-  wave_top(lt, M, s_lv[wave], s_li[wave], lane);
-  wave_top(ls, M, s_lv[4 + wave], s_li[4 + wave], lane);
-  __syncthreads();
-  if (tid == 0) {
-    tv = s_tv[0]; m = s_m[0]; s = s_s[0]; mt = s_mt[0]; st = s_st[0];
-    for (int w = 1; w < 4; ++w) {
-      tv = fmaxf(tv, s_tv[w]);
-      lse_merge(m, s, s_m[w], s_s[w]);
-      lse_merge(mt, st, s_mt[w], s_st[w]);
-    }
-    const bool rule5 = rule5_fires(m, s, tv);  // A = the timestamps alone
-    final_set_merge(rule5, m, s, mt, st);
-    // merge of the lists that feed the result, heads compared in the fixed order 0..7 (lowest id on equal values)
-    int hp[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) hp[w] = 0;
-    int count = 0;
-    for (int r = 0; r < M; ++r) {
-      float bv = -INFINITY;
-      int bi = kNoId, bw = -1;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        if (w < 4 && rule5) continue;
-        if (hp[w] >= M) continue;
-        const float v = s_lv[w][hp[w]];
-        const int i = s_li[w][hp[w]];
-        if (i != kNoId && (bw < 0 || v > bv || (v == bv && i < bi))) { bv = v; bi = i; bw = w; }
-      }
-      if (bw < 0) break;
-#pragma unroll
-      for (int w = 0; w < 8; ++w)
-        if (w == bw) ++hp[w];
-      p.cand_id[(long)b * M + r] = bi;
-      p.cand_logprob[(long)b * M + r] = logprob_of(bv, m, s);
-      ++count;
-    }
-    for (int r = count; r < M; ++r) { p.cand_id[(long)b * M + r] = E; p.cand_logprob[(long)b * M + r] = -INFINITY; }
-    p.n_cand[b] = count;
-  }
+  using namespace beam_cand;
+#define AXW_BEAM_REP false
+#define AXW_BEAM_RULES nullptr
+#include "beam_candidates_body.inc"
+#undef AXW_BEAM_REP
+#undef AXW_BEAM_RULES
 }
 
 // One wave per clip. e = rank * M + position numbers the clip's candidates in (parent rank, position) order, so "beats" is

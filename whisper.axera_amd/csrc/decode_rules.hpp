@@ -135,6 +135,70 @@ __device__ __forceinline__ const unsigned* suppress_stage(const unsigned* mask, 
   return s_suppress;
 }
 
+// ---- repetition rules (DESIGN.md "Repetition rules"): both edit the raw row before suppression and rules 2 to 5, from the
+// history seq[0, n). Built once per workgroup in the launch's dynamic LDS (repetition_lds_bytes), before the row loop:
+//   ban:  the image suppress_stage builds (zeros without a set) with one more bit per banned continuation: for every i in
+//         [0, n - g] whose g - 1 ids equal the history's last g - 1, the id seq[i + g - 1] if it is below E. The row loops test it
+//         with suppress_bits4, as they test a set;
+//   seen: one bit per distinct id below E of the history, which is what scales an id once however often it occurs.
+// Timestamps and eot get no bit in either image. An id outside [0, E) is never used as an index.
+struct RepImages {
+  const unsigned* ban;
+  const unsigned* seen;
+  float penalty;
+};
+// dynamic LDS of a launch under the rules (host): the ban image and the seen bitmap, the words of ids [0, eot] each
+inline size_t repetition_lds_bytes(int eot) { return 2 * ((size_t)(eot >> 5) + 1) * sizeof(unsigned); }
+// the sign-dependent scale of CTranslate2 and transformers (NaN stays NaN, +-inf and zero stay what they are)
+__device__ __forceinline__ float repetition_scale(float x, float penalty) { return x < 0.f ? x * penalty : x / penalty; }
+// four logits of chunk c under the seen image
+__device__ __forceinline__ f32x4 repetition_scale4(f32x4 v, const RepImages& r, int c) {
+  const unsigned seen = suppress_bits4(r.seen, c);
+  if (seen) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if ((seen >> e) & 1u) v[e] = repetition_scale(v[e], r.penalty);
+  }
+  return v;
+}
+__device__ __forceinline__ bool repetition_seen(const RepImages& r, int i) { return (r.seen[i >> 5] >> (i & 31)) & 1u; }
+// mask: the suppress words or nullptr. Two barriers: called by all 256 threads (uniform arguments).
+__device__ __forceinline__ RepImages repetition_stage(const unsigned* mask, const RepRules* rules, const int* seq, int n, int E) {
+  extern __shared__ unsigned s_suppress[];
+  const int tid = threadIdx.x, words = (E >> 5) + 1;
+  unsigned* ban = s_suppress;
+  unsigned* seen = s_suppress + words;
+  const float penalty = rules->penalty;
+  const int g = rules->ngram;
+  for (int i = tid; i < words; i += 256) {
+    ban[i] = mask ? mask[i] : 0u;
+    seen[i] = 0u;
+  }
+  __syncthreads();
+  if (penalty != 1.f)
+    for (int i = tid; i < n; i += 256) {
+      const int id = seq[i];
+      if (id >= 0 && id < E) atomicOr(&seen[id >> 5], 1u << (id & 31));
+    }
+  if (g >= 2 && g <= kNoRepeatNgramMax && n >= g) {
+    // the tail, last id first: uniform over the workgroup, so the compiler may keep it in scalar registers
+    int tail[kNoRepeatNgramMax - 1];
+#pragma unroll
+    for (int j = 0; j < kNoRepeatNgramMax - 1; ++j) tail[j] = j < g - 1 ? seq[n - 1 - j] : 0;
+    for (int i = tid; i <= n - g; i += 256) {
+      const int* last = seq + i + g - 2;  // the candidate's last id; its continuation is last[1] (i + g - 1 <= n - 1)
+      bool match = true;  // (from the last id backwards; after the first difference a lane loads nothing more)
+#pragma unroll
+      for (int j = 0; j < kNoRepeatNgramMax - 1; ++j)
+        if (j < g - 1 && match) match = last[-j] == tail[j];
+      const int id = last[1];
+      if (match && id >= 0 && id < E) atomicOr(&ban[id >> 5], 1u << (id & 31));
+    }
+  }
+  __syncthreads();
+  return {ban, seen, penalty};
+}
+
 // ---- rule 5 and the final allowed set A. (m, s): the pair of the unmasked timestamps; tv: the best unmasked id of [0, E]
 // rule 5: the timestamps' probability mass beats every single text id
 __device__ __forceinline__ bool rule5_fires(float m, float s, float tv) { return lse_value(m, s) > tv; }

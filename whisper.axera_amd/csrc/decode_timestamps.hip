@@ -82,10 +82,17 @@ enum RulesMode { kRulesPlain, kRulesScored, kRulesSampled };
 // suppress set (p.suppress; decode_rules.hpp) holds: a suppressed id is masked like one that a rule masks. Rules 1 to 5 are
 // decided on the untempered logits and the recorded log-probability is the untempered one; a clip with t <= 0 takes the scored
 // form's decision and computes no random number.
-// kSet: the instantiation of a launch with a suppress set, mask its words. Without one (kSet false, mask not read) the body compiles to
+// BITS: which image of bits the text loop tests. kBitsSet: the instantiation of a launch with a suppress set, mask its words. Without one (kBitsNone, mask not read) the body compiles to
 // what it was before there were sets: the kernels below exist in both forms and the launch functions choose by TsRulesParams::suppress.
-template <RulesMode MODE, bool kSet>
-__device__ __forceinline__ void rules_body(const TsRulesArgs& p, const unsigned* mask, const TsScoreParams& q, const TsSampleParams& r) {
+// kBitsRep: the instantiation of a launch under the repetition rules (DESIGN.md "Repetition rules"; rules: the handle's two values,
+// mask: the set's words or nullptr). The workgroup builds the ban and seen images of decode_rules.hpp from the clip's history; the
+// text loop scales the seen ids and tests the ban image, which holds the set's bits too. Everything that is recorded or drawn is
+// taken from the edited row. kBitsNone and kBitsSet (rules not read) compile to what they were before there were such rules.
+enum RulesBits { kBitsNone, kBitsSet, kBitsRep };
+template <RulesMode MODE, RulesBits BITS>
+__device__ __forceinline__ void rules_body(const TsRulesArgs& p, const unsigned* mask, const TsScoreParams& q, const TsSampleParams& r,
+                                           [[maybe_unused]] const RepRules* rules = nullptr) {
+  constexpr bool kSet = BITS == kBitsSet, kRep = BITS == kBitsRep, kBits = BITS != kBitsNone;
   constexpr bool kScore = MODE >= kRulesScored, kSample = MODE == kRulesSampled;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
@@ -116,6 +123,11 @@ __device__ __forceinline__ void rules_body(const TsRulesArgs& p, const unsigned*
   const float* row = p.logits + (long)b * p.stride;
   [[maybe_unused]] const unsigned* suppress = nullptr;
   if constexpr (kSet) suppress = suppress_stage(mask, E);
+  [[maybe_unused]] RepImages ri{};
+  if constexpr (kRep) {
+    ri = repetition_stage(mask, rules, h.seq, n, E);
+    suppress = ri.ban;
+  }
   float tv = -INFINITY, sv = -INFINITY;  // the first best unmasked id of [0, E] / unmasked timestamp
   int ti = 0x7fffffff, si = 0x7fffffff;
   float m = -INFINITY, s = 0.f;          // online logsumexp over the unmasked timestamps
@@ -124,15 +136,16 @@ __device__ __forceinline__ void rules_body(const TsRulesArgs& p, const unsigned*
   int gti = 0x7fffffff, gsi = 0x7fffffff;
   // text ids [0, E]: chunks of four floats; NaN never compares greater (it counts as masked)
   for (int c = (a.text_begin >> 2) + tid; 4 * c < a.text_end; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
+    f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * c);
+    if constexpr (kRep) v = repetition_scale4(v, ri, c);
     [[maybe_unused]] unsigned sup = 0;
-    if constexpr (kSet) sup = suppress_bits4(suppress, c);
+    if constexpr (kBits) sup = suppress_bits4(suppress, c);
     [[maybe_unused]] float x[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * c + e;
       bool on = text_id_on(a, i, E);
-      if constexpr (kSet) on = on && !suppressed(sup, e);
+      if constexpr (kBits) on = on && !suppressed(sup, e);
       if (on && v[e] > tv) { tv = v[e]; ti = i; }
       x[e] = (on && v[e] == v[e]) ? v[e] : -INFINITY;
     }
@@ -197,7 +210,12 @@ __device__ __forceinline__ void rules_body(const TsRulesArgs& p, const unsigned*
   float bv = -INFINITY;
   int bi = E;
   const Pick pick = final_pick(rule5, draw ? gt : tv, draw ? gs : sv);
-  if (pick == Pick::kText) { bi = draw ? gti : ti; bv = draw ? row[bi] : tv; }
+  if (pick == Pick::kText) {
+    bi = draw ? gti : ti;
+    bv = draw ? row[bi] : tv;
+    if constexpr (kRep)
+      if (draw && bi < E && repetition_seen(ri, bi)) bv = repetition_scale(bv, ri.penalty);  // (the drawn id's value in the edited row)
+  }
   if (pick == Pick::kTimestamp) { bi = draw ? gsi : si; bv = draw ? row[bi] : sv; }
   p.amax_val[(long)b * p.amax_stride] = bv;
   p.amax_idx[(long)b * p.amax_stride] = bi;
@@ -210,27 +228,41 @@ __device__ __forceinline__ void rules_body(const TsRulesArgs& p, const unsigned*
   }
 }
 
-__global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesArgs p) { rules_body<kRulesPlain, false>(p, nullptr, TsScoreParams{}, TsSampleParams{}); }
+__global__ __launch_bounds__(256) void timestamp_rules_kernel(TsRulesArgs p) { rules_body<kRulesPlain, kBitsNone>(p, nullptr, TsScoreParams{}, TsSampleParams{}); }
 
 __global__ __launch_bounds__(256) void timestamp_rules_scored_kernel(TsRulesArgs p, TsScoreParams q) {
-  rules_body<kRulesScored, false>(p, nullptr, q, TsSampleParams{});
+  rules_body<kRulesScored, kBitsNone>(p, nullptr, q, TsSampleParams{});
 }
 
 __global__ __launch_bounds__(256) void timestamp_rules_sampled_kernel(TsRulesArgs p, TsScoreParams q, TsSampleParams r) {
-  rules_body<kRulesSampled, false>(p, nullptr, q, r);
+  rules_body<kRulesSampled, kBitsNone>(p, nullptr, q, r);
 }
 
 // the same three under a suppress set (dynamic LDS: suppress_lds_bytes)
 __global__ __launch_bounds__(256) void timestamp_rules_suppress_kernel(TsRulesArgs p, const unsigned* mask) {
-  rules_body<kRulesPlain, true>(p, mask, TsScoreParams{}, TsSampleParams{});
+  rules_body<kRulesPlain, kBitsSet>(p, mask, TsScoreParams{}, TsSampleParams{});
 }
 
 __global__ __launch_bounds__(256) void timestamp_rules_scored_suppress_kernel(TsRulesArgs p, const unsigned* mask, TsScoreParams q) {
-  rules_body<kRulesScored, true>(p, mask, q, TsSampleParams{});
+  rules_body<kRulesScored, kBitsSet>(p, mask, q, TsSampleParams{});
 }
 
 __global__ __launch_bounds__(256) void timestamp_rules_sampled_suppress_kernel(TsRulesArgs p, const unsigned* mask, TsScoreParams q, TsSampleParams r) {
-  rules_body<kRulesSampled, true>(p, mask, q, r);
+  rules_body<kRulesSampled, kBitsSet>(p, mask, q, r);
+}
+
+// the same three under the repetition rules (dynamic LDS: repetition_lds_bytes; mask: the set's words or nullptr)
+__global__ __launch_bounds__(256) void timestamp_rules_rep_kernel(TsRulesArgs p, const unsigned* mask, const RepRules* rules) {
+  rules_body<kRulesPlain, kBitsRep>(p, mask, TsScoreParams{}, TsSampleParams{}, rules);
+}
+
+__global__ __launch_bounds__(256) void timestamp_rules_scored_rep_kernel(TsRulesArgs p, const unsigned* mask, const RepRules* rules, TsScoreParams q) {
+  rules_body<kRulesScored, kBitsRep>(p, mask, q, TsSampleParams{}, rules);
+}
+
+__global__ __launch_bounds__(256) void timestamp_rules_sampled_rep_kernel(TsRulesArgs p, const unsigned* mask, const RepRules* rules, TsScoreParams q,
+                                                                          TsSampleParams r) {
+  rules_body<kRulesSampled, kBitsRep>(p, mask, q, r, rules);
 }
 
 // ---- slot stream in timestamp mode (DESIGN.md "Slot stream in timestamp mode"): the scored form for slots that are refilled while
@@ -246,19 +278,34 @@ __global__ __launch_bounds__(256) void timestamp_rules_sampled_suppress_kernel(T
 //   offset 1 (the language id was fed): nothing;
 //   offset >= n_prefix - 1: rules_body<kRulesScored>, whose own offset and done tests then pass.
 __global__ __launch_bounds__(256) void stream_rules_kernel(TsRulesArgs p, TsScoreParams q, StreamRulesParams t) {
-#define AXW_STREAM_SET false
+#define AXW_STREAM_BITS kBitsNone
 #define AXW_STREAM_MASK nullptr
+#define AXW_STREAM_RULES nullptr
 #include "stream_rules_body.inc"
-#undef AXW_STREAM_SET
+#undef AXW_STREAM_BITS
 #undef AXW_STREAM_MASK
+#undef AXW_STREAM_RULES
 }
 
 __global__ __launch_bounds__(256) void stream_rules_suppress_kernel(TsRulesArgs p, const unsigned* mask, TsScoreParams q, StreamRulesParams t) {
-#define AXW_STREAM_SET true
+#define AXW_STREAM_BITS kBitsSet
 #define AXW_STREAM_MASK mask
+#define AXW_STREAM_RULES nullptr
 #include "stream_rules_body.inc"
-#undef AXW_STREAM_SET
+#undef AXW_STREAM_BITS
 #undef AXW_STREAM_MASK
+#undef AXW_STREAM_RULES
+}
+
+__global__ __launch_bounds__(256) void stream_rules_rep_kernel(TsRulesArgs p, const unsigned* mask, const RepRules* rules, TsScoreParams q,
+                                                               StreamRulesParams t) {
+#define AXW_STREAM_BITS kBitsRep
+#define AXW_STREAM_MASK mask
+#define AXW_STREAM_RULES rules
+#include "stream_rules_body.inc"
+#undef AXW_STREAM_BITS
+#undef AXW_STREAM_MASK
+#undef AXW_STREAM_RULES
 }
 
 // log p(row[id]) over the whole row, one workgroup per row (the no-speech value on rows of the caller's)
@@ -281,7 +328,8 @@ static void check_rules_params(const TsRulesParams& p) {
 
 void launch_timestamp_rules(const TsRulesParams& p, hipStream_t s) {
   check_rules_params(p);
-  if (p.suppress) hipLaunchKernelGGL(timestamp_rules_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress);
+  if (p.rep) hipLaunchKernelGGL(timestamp_rules_rep_kernel, dim3(p.batch), dim3(256), repetition_lds_bytes(p.eot), s, args_of(p), p.suppress, p.rep);
+  else if (p.suppress) hipLaunchKernelGGL(timestamp_rules_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress);
   else hipLaunchKernelGGL(timestamp_rules_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p));
 }
 
@@ -295,7 +343,8 @@ void launch_timestamp_rules_scored(const TsRulesParams& p, const TsScoreParams& 
     fprintf(stderr, "[ax_whisper] launch_timestamp_rules_scored: bad score arrays / no-speech id %d\n", q.no_speech_id);
     abort();
   }
-  if (p.suppress) hipLaunchKernelGGL(timestamp_rules_scored_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q);
+  if (p.rep) hipLaunchKernelGGL(timestamp_rules_scored_rep_kernel, dim3(p.batch), dim3(256), repetition_lds_bytes(p.eot), s, args_of(p), p.suppress, p.rep, q);
+  else if (p.suppress) hipLaunchKernelGGL(timestamp_rules_scored_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q);
   else hipLaunchKernelGGL(timestamp_rules_scored_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p), q);
 }
 
@@ -305,7 +354,8 @@ void launch_timestamp_rules_sampled(const TsRulesParams& p, const TsScoreParams&
     fprintf(stderr, "[ax_whisper] launch_timestamp_rules_sampled: bad score or sample arrays / no-speech id %d\n", q.no_speech_id);
     abort();
   }
-  if (p.suppress) hipLaunchKernelGGL(timestamp_rules_sampled_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q, r);
+  if (p.rep) hipLaunchKernelGGL(timestamp_rules_sampled_rep_kernel, dim3(p.batch), dim3(256), repetition_lds_bytes(p.eot), s, args_of(p), p.suppress, p.rep, q, r);
+  else if (p.suppress) hipLaunchKernelGGL(timestamp_rules_sampled_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q, r);
   else hipLaunchKernelGGL(timestamp_rules_sampled_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p), q, r);
 }
 
@@ -316,7 +366,8 @@ void launch_stream_rules(const TsRulesParams& p, const TsScoreParams& q, const S
     fprintf(stderr, "[ax_whisper] launch_stream_rules: bad score or slot arrays / n_lang %d\n", t.n_lang);
     abort();
   }
-  if (p.suppress) hipLaunchKernelGGL(stream_rules_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q, t);
+  if (p.rep) hipLaunchKernelGGL(stream_rules_rep_kernel, dim3(p.batch), dim3(256), repetition_lds_bytes(p.eot), s, args_of(p), p.suppress, p.rep, q, t);
+  else if (p.suppress) hipLaunchKernelGGL(stream_rules_suppress_kernel, dim3(p.batch), dim3(256), suppress_lds_bytes(p), s, args_of(p), p.suppress, q, t);
   else hipLaunchKernelGGL(stream_rules_kernel, dim3(p.batch), dim3(256), 0, s, args_of(p), q, t);
 }
 

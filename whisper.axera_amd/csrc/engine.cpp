@@ -184,6 +184,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
   }
   cfg_.ints["fp16"] = AXW_F16;  // 16-bit storage / MFMA operand type of this engine: 0 bfloat16, 1 IEEE half
   install_suppress(config_suppress_);
+  install_repetition_rules(config_rep_.penalty, config_rep_.ngram);
   ensure_capacity(std::max(1, max_batch));
   HIP_CHECK(hipStreamSynchronize(own_stream_));
 }
@@ -263,6 +264,10 @@ void Engine::load_config(const std::string& dir, const std::string& type, const 
   config_suppress_ = config_suppress_tokens(j, cfg_.n_vocab, cfg_.eot, cfg_.no_timestamps + 1,
                                             [&] { return load_token_table(dir + "/" + type + "-tokens.txt"); });
   cfg_.ints["n_suppress_tokens"] = 0;
+  // repetition rules: the optional keys "repetition_penalty" and "no_repeat_ngram_size" (absent: off), installed by construct()
+  config_repetition_rules(j, config_rep_.penalty, config_rep_.ngram);
+  cfg_.ints["repetition_rules"] = 0;
+  cfg_.ints["no_repeat_ngram_size"] = 0;
 }
 
 // Slaney mel filterbank, arithmetic as librosa.h:102-144 (fp32), stored transposed [201][n_mels].
@@ -1300,6 +1305,7 @@ void Engine::timestamp_rules(const float* logits, const int32_t* hist, const int
   r.out_ids = in.hist; r.n_out = in.n_hist; r.n_ctx = Tc;
   r.amax_val = b_val; r.amax_idx = b_idx; r.amax_stride = 1;
   r.suppress = suppress_mask();
+  r.rep = repetition_rules_dev();
   if (sample) launch_timestamp_rules_sampled(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, own_sample_, s);
   else if (logprob) launch_timestamp_rules_scored(r, TsScoreParams{b_lp, b_dec, (long)Tc + 1, nullptr, 0}, s);
   else launch_timestamp_rules(r, s);

@@ -202,6 +202,8 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void set_alignment_heads(const int* pairs, int n) override;
   void set_suppress_tokens(const int* ids, int n) override;
   const std::vector<int>& suppress_tokens() const override { return suppress_ids_; }
+  void set_repetition_rules(float penalty, int ngram) override;
+  void repetition_rules(float* penalty, int* ngram) const override { *penalty = rep_.penalty; *ngram = rep_.ngram; }
   void align_kernel(int which, const AlignKernelIO& io) override;
   void vocab_logprob_rows(const float* x, int n_rows, const int32_t* ids, float* out, int route) override;
   void stream_open(int n_slots, int mode = 0) override;
@@ -314,11 +316,13 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   StepGraphRef step_graph(StepSpec spec, int batch, int max_new);
   void drop_step_graph(const StepSpec& spec, int batch, int max_new) { graphs_.erase(graph_key(spec, batch, max_new)); }
   // (two bits for the mode: plain, timestamp, scored and sampled steps are four different graphs; one for the slot stream's scored
-  // step; one for "a suppress set is installed" where the graph holds a rules launch, which has the mask's pointer by value)
+  // step; one for "a suppress set is installed" where the graph holds a rules launch, which has the mask's pointer by value; one,
+  // in the same way, for "the repetition rules are on")
   long graph_key(const StepSpec& spec, int batch, int max_new) const {
     const bool suppress = spec.mode != kDecodePlain && (spec.mask & 4) && suppress_mask();
-    // (self_group sits above every other field: a key without it is the number it always was)
-    return ((long)spec.self_group << 56) | ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 9) | ((long)spec.cross_group << 5) |
+    const bool rep = spec.mode != kDecodePlain && (spec.mask & 4) && repetition_rules_dev();
+    // (self_group and the repetition bit sit above every other field: a key without them is the number it always was)
+    return ((long)spec.self_group << 56) | (rep ? 1L << 55 : 0) | ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 9) | ((long)spec.cross_group << 5) |
            (spec.cross_fp8 ? 16 : 0) | (suppress ? 8 : 0) | (spec.slots ? 4 : 0) | spec.mode;
   }
   void require_timestamp_vocab() const;
@@ -329,6 +333,12 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   unsigned* d_suppress_ = nullptr;  // (in allocs_)
   const unsigned* suppress_mask() const { return suppress_ids_.empty() ? nullptr : d_suppress_; }  // what the parameter structs get
   void install_suppress(const std::vector<int>& ids);
+  // repetition rules (DESIGN.md "Repetition rules"): the handle's values, what the config file gave, and their copy on the device:
+  // allocated on first use, at one address for the life of the handle, rewritten on the engine's stream
+  RepRules rep_{1.f, 0}, config_rep_{1.f, 0};
+  RepRules* d_rep_ = nullptr;  // (in allocs_)
+  const RepRules* repetition_rules_dev() const { return rep_.penalty != 1.f || rep_.ngram != 0 ? d_rep_ : nullptr; }  // what the parameter structs get
+  void install_repetition_rules(float penalty, int ngram);
   void ensure_ts_logits();  // d_ts_logits_ (SlotViews)
   void enqueue_timestamp_rules(const StepSpec& spec, int batch, const int* d_forced, int n_forced, hipStream_t s);
   long ts_stride_ = 0;

@@ -549,7 +549,10 @@ bool Engine::persistent_usable() {
 // launch-per-phase step: sampled mode, prompts, a language or task per clip, two or more clips (beam search and the slot stream never
 // come here). Asked once per request, last of all: persistent_usable() counts a back-off down.
 bool Engine::persistent_ts_route(DecodeMode mode, int batch, const ClipContexts& ctx) {
-  return (mode == kDecodeTimestamps || mode == kDecodeScored) && batch == 1 && !ctx.any() && persistent_ts_ && persistent_usable();
+  // (the launch's rules instantiation carries four values of the history, not its ids: a handle under the repetition rules, which
+  // scan the ids, takes the launch-per-phase step)
+  return (mode == kDecodeTimestamps || mode == kDecodeScored) && batch == 1 && !ctx.any() && persistent_ts_ && !repetition_rules_dev() &&
+         persistent_usable();
 }
 void Engine::persistent_gave_up() {
   persist_backoff_ = std::min(persist_backoff_ ? persist_backoff_ * 4 : 8, 4096);
@@ -831,6 +834,7 @@ void Engine::enqueue_timestamp_rules(const StepSpec& spec, int batch, const int*
   r.forced = d_forced; r.n_forced = n_forced; r.base = spec.base;
   r.amax_val = d_amax_val_; r.amax_idx = d_amax_idx_; r.amax_stride = n_amax_part_;
   r.suppress = suppress_mask();
+  r.rep = repetition_rules_dev();
   if (spec.slots) launch_stream_rules(r, spec.score_out, stream_rules_params(), s);  // idle slots, the no-speech value and detection at offset 0
   else if (spec.mode == kDecodeSampled) launch_timestamp_rules_sampled(r, spec.score_out, spec.sample, s);  // + a draw at the clip's temperature
   else if (spec.mode == kDecodeScored) launch_timestamp_rules_scored(r, spec.score_out, s);  // + the decision's log-probability, the no-speech value at offset 0
@@ -859,6 +863,30 @@ void Engine::set_suppress_tokens(const int* ids, int n) {
   if (n < 0 || (n > 0 && !ids)) throw std::runtime_error("set_suppress_tokens: bad arguments");
   install_suppress(n == 0 ? config_suppress_
                           : checked_suppress_tokens(ids, n, cfg_.n_vocab, cfg_.eot, cfg_.no_timestamps + 1, "set_suppress_tokens"));
+}
+
+// ------------------------------------------------------------------------------ repetition rules
+// The two values go to one small struct in device memory that the kernels' rules instantiation reads: it keeps its address, and a
+// captured step depends only on whether the rules are on (graph_key).
+void Engine::install_repetition_rules(float penalty, int ngram) {
+  check_repetition_rules(penalty, ngram, "set_repetition_rules");
+  if (penalty != 1.f || ngram != 0) {
+    std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+    HIP_CHECK(hipSetDevice(device_));
+    if (!d_rep_) d_rep_ = pooled<RepRules>(allocs_, 1, true);
+    const RepRules v{penalty, ngram};
+    hipStream_t s = stream();
+    HIP_CHECK(hipMemcpyAsync(d_rep_, &v, sizeof(v), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (a pageable source on this stack)
+  }
+  rep_ = RepRules{penalty, ngram};
+  cfg_.ints["repetition_rules"] = repetition_rules_dev() ? 1 : 0;
+  cfg_.ints["no_repeat_ngram_size"] = ngram;
+}
+
+void Engine::set_repetition_rules(float penalty, int ngram) {
+  require_no_stream("set_repetition_rules");  // an open stream's captured step has made its choice
+  install_repetition_rules(penalty, ngram);
 }
 
 void Engine::require_scored_vocab() const {

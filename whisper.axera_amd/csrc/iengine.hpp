@@ -205,6 +205,11 @@ class IEngine {
   // point applies; n == 0: what the config file gave. Refuses an open Stream*.
   virtual void set_suppress_tokens(const int* ids, int n) = 0;
   virtual const std::vector<int>& suppress_tokens() const = 0;  // sorted
+  // repetition rules (DESIGN.md "Repetition rules"): the penalty (> 0; 1: none) and the n-gram size (0: none, or 2 .. 16) that
+  // every timestamp-mode decode, rules entry and beam search of the handle applies to the row before the set and the rules; refused
+  // while a stream is open
+  virtual void set_repetition_rules(float penalty, int ngram) = 0;
+  virtual void repetition_rules(float* penalty, int* ngram) const = 0;
   // One kernel of decode_align.hip alone on host data (tests). Clip c has len[c] rows and n_keys[c] frames.
   // qk_softmax: q fp32 [rows][64 n_head] (clip c at row0[c]), k fp32 [n_slots][n_head][keys_pad][64] (clip c reads slot[c]), both
   // narrowed to the 16-bit type; P [n_clips][n_align][rows_pad][f_pad] is updated in place (the kernel writes what it writes).

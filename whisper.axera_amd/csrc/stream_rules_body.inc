@@ -1,10 +1,11 @@
 // stream_rules_body.inc — the body of stream_rules_kernel (decode_timestamps.hip), included once per instantiation: without a suppress
-// set (AXW_STREAM_SET false, AXW_STREAM_MASK nullptr), where it is the kernel it was before there were sets, and with one. The
-// branches of offset 0 and 1 do not look at the set. In scope: TsRulesArgs p, TsScoreParams q, StreamRulesParams t.
+// set (AXW_STREAM_BITS kBitsNone, AXW_STREAM_MASK nullptr), where it is the kernel it was before there were sets, with one (kBitsSet),
+// and under the repetition rules (kBitsRep, AXW_STREAM_RULES the handle's values). The branches of offset 0 and 1 look at neither.
+// In scope: TsRulesArgs p, TsScoreParams q, StreamRulesParams t.
   const int b = blockIdx.x;
   if (p.done[b]) return;
   const int off = p.off[b];
-  if (off >= p.n_prefix - 1) { rules_body<kRulesScored, AXW_STREAM_SET>(p, AXW_STREAM_MASK, q, TsSampleParams{}); return; }
+  if (off >= p.n_prefix - 1) { rules_body<kRulesScored, AXW_STREAM_BITS>(p, AXW_STREAM_MASK, q, TsSampleParams{}, AXW_STREAM_RULES); return; }
   if (off != 0) return;
   const float* row = p.logits + (long)b * p.stride;
   row_logprob(row, p.n_vocab, q.no_speech_id, q.no_speech + b);

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <stdexcept>
@@ -115,6 +116,32 @@ inline std::vector<int> config_suppress_tokens(const JsonValue& j, int n_vocab, 
   std::sort(flat.begin(), flat.end());
   flat.erase(std::unique(flat.begin(), flat.end()), flat.end());
   return checked_suppress_tokens(flat.data(), (int)flat.size(), n_vocab, eot, ts_begin, "config: suppress_tokens");
+}
+
+// ------------------------------------------------------------------------------ repetition rules (DESIGN.md "Repetition rules")
+// Which values the two rules take: a finite penalty above 0 (1: none) and an n-gram size of 0 (none) or 2 .. 16
+inline void check_repetition_rules(float penalty, int ngram, const char* what) {
+  if (!(penalty > 0.f) || !std::isfinite(penalty))
+    throw std::runtime_error(std::string(what) + ": repetition_penalty " + std::to_string(penalty) + " (need a finite value above 0; 1 is off)");
+  if (ngram != 0 && (ngram < 2 || ngram > 16))
+    throw std::runtime_error(std::string(what) + ": no_repeat_ngram_size " + std::to_string(ngram) + " (need 0 for off, or 2 .. 16)");
+}
+// The optional keys "repetition_penalty" and "no_repeat_ngram_size" of {type}_config.json (absent: 1.0 and 0)
+inline void config_repetition_rules(const JsonValue& j, float& penalty, int& ngram) {
+  penalty = 1.f;
+  ngram = 0;
+  if (j.has("repetition_penalty")) {
+    const JsonValue& v = j.at("repetition_penalty");
+    if (v.kind != JsonValue::Number) throw std::runtime_error("config: repetition_penalty must be a number");
+    penalty = (float)v.num;
+  }
+  if (j.has("no_repeat_ngram_size")) {
+    const JsonValue& v = j.at("no_repeat_ngram_size");
+    if (v.kind != JsonValue::Number || v.num != (double)(long)v.num || v.num < 0 || v.num > 1e6)
+      throw std::runtime_error("config: no_repeat_ngram_size must be a whole number");
+    ngram = (int)v.num;
+  }
+  check_repetition_rules(penalty, ngram, "config");
 }
 
 // ------------------------------------------------------------------------------ the device form

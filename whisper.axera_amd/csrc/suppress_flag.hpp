@@ -1,6 +1,7 @@
 // suppress_flag.hpp — the value of --suppress_tokens as whisper_cli and whisper_srv take it, through the C ABI alone:
 // "-1": the non-speech ids derived from the model's tokens file (AX_WHISPER_NonSpeechTokens, host only); "1,2,3": those ids.
 #pragma once
+#include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -31,5 +32,28 @@ inline bool suppress_flag_ids(const std::string& arg, const std::string& model_p
     p = (size_t)(end - arg.c_str()) + (*end ? 1 : 0);
   }
   if (ids.empty()) { err = "bad value: --suppress_tokens " + arg + " (no ids)"; return false; }
+  return true;
+}
+
+// --repetition_penalty P and --no_repeat_ngram_size N as both tools take them (DESIGN.md "Repetition rules"): a flag that is absent
+// keeps what the handle has (the config file's value). Returns false with `err` set where a value does not parse or the library
+// refuses it; with neither flag nothing is called.
+inline bool apply_repetition_flags(AX_WHISPER_HANDLE handle, const std::string& penalty_arg, const std::string& ngram_arg, std::string& err) {
+  if (penalty_arg.empty() && ngram_arg.empty()) return true;
+  float p = 1.f;
+  int g = 0;
+  if (AX_WHISPER_GetRepetitionRules(handle, &p, &g) != 0) { err = std::string("repetition rules failed! ") + AX_WHISPER_LastError(handle); return false; }
+  char* end = nullptr;
+  if (!penalty_arg.empty()) {
+    p = strtof(penalty_arg.c_str(), &end);
+    if (end == penalty_arg.c_str() || *end) { err = "bad value: --repetition_penalty " + penalty_arg; return false; }
+  }
+  if (!ngram_arg.empty()) {
+    const long v = strtol(ngram_arg.c_str(), &end, 10);
+    if (end == ngram_arg.c_str() || *end || v < 0 || v > 1000) { err = "bad value: --no_repeat_ngram_size " + ngram_arg; return false; }
+    g = (int)v;
+  }
+  if (AX_WHISPER_SetRepetitionRules(handle, p, g) != 0) { err = std::string("repetition rules failed! ") + AX_WHISPER_LastError(handle); return false; }
+  printf("repetition_penalty: %g, no_repeat_ngram_size: %d\n", p, g);
   return true;
 }

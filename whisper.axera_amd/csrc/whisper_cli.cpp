@@ -68,6 +68,9 @@ static void usage(const char* prog) {
           "      --suppress_tokens -1|1,2,3   (with --timestamps or --long) ids the decode never samples, as openai-whisper's\n"
           "                      suppress_tokens: -1 the non-speech ids of the model's tokens file (brackets, quotes, musical signs),\n"
           "                      or a list; replaces what the config file's \"suppress_tokens\" gave\n"
+          "      --repetition_penalty P   (with --timestamps or --long) CTranslate2's / transformers' penalty on the text ids a window\n"
+          "                      has decoded already (> 0; 1.0 off)\n"
+          "      --no_repeat_ngram_size N (with --timestamps or --long) no n-gram of N text ids is decoded twice in a window (0 off, 2 .. 16)\n"
           "  -?, --help          print this message\n",
           prog);
 }
@@ -421,6 +424,7 @@ int main(int argc, char** argv) {
   bool condition = false, detect = false, chunked = false;
   std::string task_arg, cmax_arg, cmin_arg, csmooth_arg;
   std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg, suppress_arg, cross_kv_arg, beam_cross_arg, beam_self_arg;
+  std::string rep_penalty_arg, rep_ngram_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -439,7 +443,8 @@ int main(int argc, char** argv) {
         val("beam_size", nullptr, beam_arg) || val("prompt_ids", nullptr, prompt_arg) || val("task", nullptr, task_arg) ||
         val("chunk_max_s", nullptr, cmax_arg) || val("chunk_min_s", nullptr, cmin_arg) || val("chunk_smooth_ms", nullptr, csmooth_arg) ||
         val("suppress_tokens", nullptr, suppress_arg) || val("cross_kv", nullptr, cross_kv_arg) || val("beam_cross", nullptr, beam_cross_arg) ||
-        val("beam_self", nullptr, beam_self_arg))
+        val("beam_self", nullptr, beam_self_arg) || val("repetition_penalty", nullptr, rep_penalty_arg) ||
+        val("no_repeat_ngram_size", nullptr, rep_ngram_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -516,6 +521,11 @@ int main(int argc, char** argv) {
     std::string err;
     if (!suppress_flag_ids(suppress_arg, model_path, model_type, suppress_ids, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
   }
+  if ((!rep_penalty_arg.empty() || !rep_ngram_arg.empty()) && !timestamps && !longform) {
+    fprintf(stderr, "--repetition_penalty / --no_repeat_ngram_size need --timestamps or --long (plain mode is not filtered)\n");
+    usage(argv[0]);
+    return 1;
+  }
   const bool prompted = condition || !prompt_ids.empty();
   if (prompted && !longform) { fprintf(stderr, "--condition_on_previous_text / --prompt_ids need --long\n"); usage(argv[0]); return 1; }
   const bool scored = prompted || fallback || !nst_arg.empty() || !lpt_arg.empty() || (per_lang && longform);
@@ -568,6 +578,14 @@ int main(int argc, char** argv) {
       return -1;
     }
     printf("suppress_tokens: %d ids\n", (int)suppress_ids.size());
+  }
+  {
+    std::string err;
+    if (!apply_repetition_flags(handle, rep_penalty_arg, rep_ngram_arg, err)) {
+      printf("%s\n", err.c_str());
+      AX_WHISPER_Uninit(handle);
+      return -1;
+    }
   }
   if (g_resample) {  // the file's real duration: its frames at its own rate
     float* pcm = nullptr;

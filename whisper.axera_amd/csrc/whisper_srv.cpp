@@ -435,7 +435,7 @@ static void serve(int fd) {
 
 int main(int argc, char** argv) {
   int port = 8080, max_batch = 64, wait_ms = 5, steps_per_call = 8, max_body_mb = 16, min_admit = 1, admit_wait_ms = 20;
-  std::string model_type = "turbo", model_path = "../models-mi355x", language = "zh", devices, scheduler = "slots", suppress_arg, cross_kv_arg;
+  std::string model_type = "turbo", model_path = "../models-mi355x", language = "zh", devices, scheduler = "slots", suppress_arg, cross_kv_arg, rep_penalty_arg, rep_ngram_arg;
   bool timestamps = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -452,6 +452,7 @@ int main(int argc, char** argv) {
     if (val("model_type", "-t", model_type) || val("model_path", "-p", model_path) || val("language", "-l", language)) continue;
     if (val("devices", nullptr, devices) || val("scheduler", nullptr, scheduler) || val("suppress_tokens", nullptr, suppress_arg)) continue;
     if (val("cross_kv", nullptr, cross_kv_arg)) continue;
+    if (val("repetition_penalty", nullptr, rep_penalty_arg) || val("no_repeat_ngram_size", nullptr, rep_ngram_arg)) continue;
     if (a == "--timestamps") { timestamps = true; continue; }
     if (val("steps_per_call", nullptr, v)) { steps_per_call = std::max(1, atoi(v.c_str())); continue; }
     if (val("min_admit", nullptr, v)) { min_admit = std::max(1, atoi(v.c_str())); continue; }
@@ -460,7 +461,7 @@ int main(int argc, char** argv) {
     if (val("max_body_mb", nullptr, v)) { max_body_mb = std::max(1, atoi(v.c_str())); continue; }
     if (val("recv_timeout_s", nullptr, v)) { g_recv_timeout_s = std::max(1, atoi(v.c_str())); continue; }
     fprintf(stderr, "usage: %s [--port 8080] [-t model_type] [-p model_path] [-l language] [--max_batch 64] [--batch_wait_ms 5] [--devices all|0,1,..]\n"
-                    "          [--scheduler slots|batches] [--timestamps] [--cross_kv h16|fp8] [--suppress_tokens -1|1,2,3] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
+                    "          [--scheduler slots|batches] [--timestamps] [--cross_kv h16|fp8] [--suppress_tokens -1|1,2,3] [--repetition_penalty 1.0] [--no_repeat_ngram_size 0] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
     return a == "--help" || a == "-?" ? 0 : 1;
   }
   printf("port: %d\n", port);
@@ -476,6 +477,11 @@ int main(int argc, char** argv) {
     if (!timestamps) { printf("--suppress_tokens needs --timestamps (plain mode is not filtered)\n"); return 1; }
     std::string err;
     if (!suppress_flag_ids(suppress_arg, model_path, model_type, suppress_ids, err)) { printf("%s\n", err.c_str()); return 1; }
+  }
+
+  if ((!rep_penalty_arg.empty() || !rep_ngram_arg.empty()) && !timestamps) {
+    printf("--repetition_penalty / --no_repeat_ngram_size need --timestamps (plain mode is not filtered)\n");
+    return 1;
   }
 
   // one handle (one engine, one batcher thread) per device
@@ -506,6 +512,12 @@ int main(int argc, char** argv) {
     // (set here, before the scheduler opens the handle's stream: the stream's captured step takes the set it finds)
     if (!suppress_ids.empty() && AX_WHISPER_SetSuppressTokens(m, suppress_ids.data(), (int)suppress_ids.size()) != 0) {
       printf("--suppress_tokens failed! %s\n", AX_WHISPER_LastError(m));
+      for (AX_WHISPER_HANDLE o : models) AX_WHISPER_Uninit(o);
+      return -1;
+    }
+    std::string rep_err;
+    if (!apply_repetition_flags(m, rep_penalty_arg, rep_ngram_arg, rep_err)) {  // (before the stream opens, as the set)
+      printf("%s\n", rep_err.c_str());
       for (AX_WHISPER_HANDLE o : models) AX_WHISPER_Uninit(o);
       return -1;
     }

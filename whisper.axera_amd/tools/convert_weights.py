@@ -122,8 +122,25 @@ def hf_suppress_tokens(path: str):
     return [int(x) for x in ids]
 
 
+def hf_repetition_rules(path: str):
+    """"repetition_penalty" and "no_repeat_ngram_size" of the generation_config.json beside a transformers checkpoint's weights, as a
+    dict of the keys that are there; None where there is no such file or neither key."""
+    import json
+
+    d = os.path.dirname(path) if path.endswith(".safetensors") else path
+    f = os.path.join(d, "generation_config.json")
+    if not os.path.exists(f):
+        return None
+    g = json.load(open(f))
+    out = {k: g[k] for k in ("repetition_penalty", "no_repeat_ngram_size") if g.get(k) is not None}
+    for k, v in out.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{f}: {k} is not a number")
+    return out or None
+
+
 def write_model(weights: dict, model_type: str, model_path: str, dtype: str = "BF16", tiktoken_path: str | None = None,
-                alignment_heads=None, suppress_tokens=None) -> str:
+                alignment_heads=None, suppress_tokens=None, repetition_rules=None) -> str:
     """tiktoken_path is REQUIRED for a real checkpoint: {type}-tokens.txt must carry the vocabulary the model was
     trained with (the reference's exporter writes it from the tokenizer, export_onnx.py:391-417)."""
     if not tiktoken_path:
@@ -140,7 +157,7 @@ def write_model(weights: dict, model_type: str, model_path: str, dtype: str = "B
             assert tuple(weights[n].shape) == tuple(s), (n, weights[n].shape, s)
     return modelgen.write_model_dir(model_path, model_type, dims, weights={k: v for k, v in weights.items() if k in expect},
                                     dtype=dtype, tiktoken_path=tiktoken_path, alignment_heads=alignment_heads,
-                                    suppress_tokens=suppress_tokens)
+                                    suppress_tokens=suppress_tokens, repetition_rules=repetition_rules)
 
 
 def main():
@@ -163,13 +180,15 @@ def main():
         w = {k: v.float().numpy() for k, v in sd.items()}
         heads = None  # (an openai checkpoint keeps its heads in the package, not in the file)
         suppress = None  # (and decodes with suppress_tokens = -1 unless told otherwise: --suppress_tokens -1)
+        rep = None
     else:
         w = hf_to_openai_names(read_hf_checkpoint(a.hf))
         heads = hf_alignment_heads(a.hf)  # word-level timestamps: the checkpoint's own heads go into the config
         suppress = hf_suppress_tokens(a.hf)  # token suppression: the checkpoint's own list too
+        rep = hf_repetition_rules(a.hf)  # repetition rules: the checkpoint's own values, where it has any
     if a.suppress_tokens is not None:
         suppress = modelgen.parse_suppress_tokens(a.suppress_tokens)
-    print(write_model(w, a.model_type, a.model_path, a.dtype, a.tiktoken, alignment_heads=heads, suppress_tokens=suppress))
+    print(write_model(w, a.model_type, a.model_path, a.dtype, a.tiktoken, alignment_heads=heads, suppress_tokens=suppress, repetition_rules=rep))
 
 
 if __name__ == "__main__":

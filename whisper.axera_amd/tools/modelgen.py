@@ -397,11 +397,13 @@ def write_tokens(path: str, tiktoken_path: str | None) -> None:
 
 def write_model_dir(root: str, model_type: str, dims: dict | None = None, seed: int = 0,
                     tiktoken_path: str | None = None, dtype: str = "BF16",
-                    weights: Dict[str, np.ndarray] | None = None, alignment_heads=None, suppress_tokens=None) -> str:
+                    weights: Dict[str, np.ndarray] | None = None, alignment_heads=None, suppress_tokens=None,
+                    repetition_rules=None) -> str:
     """Create ``{root}/{model_type}/`` with config, tokens and weights; returns the directory. alignment_heads: the checkpoint's
     [[layer, head], ...] for word-level timestamps (the config's optional key of that name); None: the key is left out.
     suppress_tokens: the ids timestamp mode never samples (the config's optional key of that name; -1: the non-speech list of the
-    tokens file, derived when the model is loaded); None: the key is left out."""
+    tokens file, derived when the model is loaded); None: the key is left out. repetition_rules: a dict with "repetition_penalty" and /
+    or "no_repeat_ngram_size" (the config's optional keys of those names); None: both are left out."""
     dims = dims or DIMS[model_type]
     d = os.path.join(root, model_type)
     os.makedirs(d, exist_ok=True)
@@ -410,6 +412,9 @@ def write_model_dir(root: str, model_type: str, dims: dict | None = None, seed: 
         cfg["alignment_heads"] = [[int(l), int(h)] for l, h in alignment_heads]
     if suppress_tokens is not None:
         cfg["suppress_tokens"] = [int(i) for i in suppress_tokens]
+    for key, kind in (("repetition_penalty", float), ("no_repeat_ngram_size", int)):
+        if repetition_rules and repetition_rules.get(key) is not None:
+            cfg[key] = kind(repetition_rules[key])
     with open(os.path.join(d, f"{model_type}_config.json"), "w") as f:
         json.dump(cfg, f, indent=4)
     write_tokens(os.path.join(d, f"{model_type}-tokens.txt"), tiktoken_path)
