@@ -137,6 +137,21 @@ AX_WHISPER_API int AX_WHISPER_GetCrossKV(AX_WHISPER_HANDLE handle, int slot, flo
  *  Both return -1 on a handle without the mode. */
 AX_WHISPER_API int AX_WHISPER_GetCrossKVFp8(AX_WHISPER_HANDLE handle, int slot, uint8_t* k_codes, uint8_t* v_codes, float* scales);
 AX_WHISPER_API int AX_WHISPER_CrossKVQuantize(AX_WHISPER_HANDLE handle);
+/* Cross-attention over each clip's own audio span (opt-in; a mode of Init, read through AX_WHISPER_GetConfigInt): on a handle made while
+ *  the environment variable AX_WHISPER_CROSS_SPAN is "audio", every slot has a span of min(1500, ceil(samples / 320) + margin) encoder
+ *  frames (samples: the clip's 16 kHz sample count, for long-form the window's; margin: AX_WHISPER_CROSS_SPAN_MARGIN frames, default
+ *  100 = 2 s), and the cross-attention launches of decoder steps of more than two slots read only those frames, through a work list
+ *  balanced by key blocks. A slot whose length the entry point does not know (EncodeMel, bench handles) has 1500. Composes with
+ *  AX_WHISPER_CROSS_KV=fp8. Not covered: calls of one or two clips, the persistent launches, the prefill, alignment and
+ *  language-detection reads, beam search, and the encoder, which still computes all 1500 frames. The effect on a trained model's
+ *  transcripts is unmeasured, so the mode is off by default. Absent or "full": today's behaviour; any other value fails Init with an
+ *  error text. AX_WHISPER_GetConfigInt: "cross_span" (0 / 1), "cross_span_margin", "cross_span_launches".
+ *  CrossSpanAttention: the plan kernel and the span kernel alone over the handle's current cross K/V of `layer` (the code images on an
+ *  FP8 handle), slots 0 .. n - 1 (n at most the handle's capacity), q / out fp32 [n][n_text_state], spans [n] in keys (clamped to 1 ..
+ *  1500). GetCrossSpans: the spans the decoder steps read, out [capacity] (AX_WHISPER_GetConfigInt "capacity": max_batch of Init, or what
+ *  a larger call grew the handle to). Both return -1 on a handle without the mode. */
+AX_WHISPER_API int AX_WHISPER_CrossSpanAttention(AX_WHISPER_HANDLE handle, int layer, int n, const float* q, const int* spans, float* out);
+AX_WHISPER_API int AX_WHISPER_GetCrossSpans(AX_WHISPER_HANDLE handle, int* out);
 /* Shared cross K/V under beam search (opt-in; a mode of Init, read through AX_WHISPER_GetConfigInt): on a handle made while the environment variable AX_WHISPER_BEAM_CROSS is "shared", the
  *  K hypotheses of a clip read ONE cross K/V copy, the clip's own, through a grouped cross-attention kernel, in beam calls of more
  *  than two slots with K > 1 (an FP8 cross K/V handle keeps the copies). Absent or "copy": today's behaviour, a copy per hypothesis;

@@ -86,6 +86,8 @@ SYMBOLS = {
     "AX_WHISPER_GetCrossKV": (C.c_int, [C.c_void_p, C.c_int, fp, fp]),
     "AX_WHISPER_GetCrossKVFp8": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), fp]),
     "AX_WHISPER_CrossKVQuantize": (C.c_int, [C.c_void_p]),
+    "AX_WHISPER_CrossSpanAttention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, fp, C.POINTER(C.c_int), fp]),
+    "AX_WHISPER_GetCrossSpans": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "AX_WHISPER_ScanStored16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64), fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_DecodeForced": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, fp, ip]),
     "AX_WHISPER_DecodeGreedy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, C.POINTER(C.c_int)]),
@@ -639,7 +641,7 @@ class Whisper:
     """Mirror of the reference's ``Whisper`` (python/whisper.py:54-99, cpp/src/Whisper.hpp:28-59)."""
 
     def __init__(self, model_type: str, model_path: str, language: str = "zh", device: int = -1, max_batch: int = 0, devices=None,
-                 cross_kv: str | None = None, beam_cross: str | None = None, beam_self: str | None = None):
+                 cross_kv: str | None = None, beam_cross: str | None = None, beam_self: str | None = None, cross_span: str | None = None):
         """devices: a list of HIP ordinals (or "all") -> one engine per device behind this handle (AX_WHISPER_InitMulti).
         cross_kv: "fp8" keeps the cross K/V as e4m3fn codes too and lets decoder steps of more than two clips read them (opt-in;
         DESIGN.md "FP8 cross K/V"); "h16" or None: the h16 images alone.
@@ -647,12 +649,16 @@ class Whisper:
         DESIGN.md "Shared cross K/V"); "copy" or None: a copy per hypothesis.
         beam_self: "tree" keeps the self-attention cache of beam search in place and reads it through an ancestry table, every
         referenced block once per clip (opt-in; DESIGN.md "Tree self-attention"); "copy" or None: cache blocks move with hypotheses.
-        The library reads the modes from AX_WHISPER_CROSS_KV / AX_WHISPER_BEAM_CROSS / AX_WHISPER_BEAM_SELF while the handle is made: the variables are
+        cross_span: "audio" lets the cross-attention of decoder steps of more than two slots read only each clip's own audio span,
+        min(1500, ceil(samples / 320) + margin) encoder frames (opt-in, effect on a trained model's transcripts unmeasured; DESIGN.md
+        "Cross-attention spans"; the margin is AX_WHISPER_CROSS_SPAN_MARGIN frames, default 100); "full" or None: all 1500 frames.
+        The library reads the modes from AX_WHISPER_CROSS_KV / AX_WHISPER_BEAM_CROSS / AX_WHISPER_BEAM_SELF / AX_WHISPER_CROSS_SPAN while the handle is made: the variables are
         set for that call and put back afterwards, under a lock that every construction with such an argument takes (a handle made
         at the same moment on another thread WITHOUT the arguments, or by other code through the C ABI, reads whatever the variables
         hold then)."""
         self.L = load_library()
-        modes = {k: str(v) for k, v in (("AX_WHISPER_CROSS_KV", cross_kv), ("AX_WHISPER_BEAM_CROSS", beam_cross), ("AX_WHISPER_BEAM_SELF", beam_self)) if v is not None}
+        modes = {k: str(v) for k, v in (("AX_WHISPER_CROSS_KV", cross_kv), ("AX_WHISPER_BEAM_CROSS", beam_cross), ("AX_WHISPER_BEAM_SELF", beam_self),
+                                              ("AX_WHISPER_CROSS_SPAN", cross_span)) if v is not None}
         if not modes:
             self._init_handle(model_type, model_path, language, device, max_batch, devices)
         else:
@@ -1779,6 +1785,24 @@ class Whisper:
     def cross_kv_quantize(self):
         """The quantise kernel alone over every slot of a cross_kv="fp8" handle (the h16 images as they stand -> codes and scales)."""
         self._check(self.L.AX_WHISPER_CrossKVQuantize(self.h), "CrossKVQuantize")
+
+    def cross_span_attention(self, layer: int, q, spans):
+        """The plan kernel and the span cross-attention kernel alone on a cross_span="audio" handle: slot b attends with query q[b]
+        (fp32 [n][n_text_state]) over the first spans[b] keys of its current cross K/V of `layer` (the FP8 codes on a cross_kv="fp8"
+        handle). Returns the attention output fp32 [n][n_text_state]."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        spans = np.ascontiguousarray(spans, dtype=np.int32)
+        assert q.ndim == 2 and q.shape == (len(spans), self.n_text_state)
+        out = np.empty_like(q)
+        self._check(self.L.AX_WHISPER_CrossSpanAttention(self.h, layer, len(spans), q.ctypes.data_as(fp), spans.ctypes.data_as(C.POINTER(C.c_int)),
+                                                         out.ctypes.data_as(fp)), "CrossSpanAttention")
+        return out
+
+    def cross_spans(self):
+        """The spans (in encoder frames) the decoder steps of a cross_span="audio" handle read, one per slot of its capacity."""
+        out = np.zeros(self.get_config_int("capacity"), dtype=np.int32)
+        self._check(self.L.AX_WHISPER_GetCrossSpans(self.h, out.ctypes.data_as(C.POINTER(C.c_int))), "GetCrossSpans")
+        return out
 
     def scan_stored16(self, batch: int = 1):
         """{buffer name: (non-finite elements, max finite |x|)} over every 16-bit tensor the engine stores between kernels."""

@@ -522,7 +522,7 @@ AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char*
   if (!strcmp(key, "n_devices")) return h->group.size();
   if (!strcmp(key, "live_hip_objects")) return (int)axw::live_owned.load();  // test hook: of every handle of the process
   if (!strcmp(key, "persistent_giveups") || !strcmp(key, "persistent_ts_launches") || !strcmp(key, "cross_kv_fp8_launches") ||
-      !strcmp(key, "beam_cross_shared_launches") || !strcmp(key, "beam_self_tree_launches")) {  // counts: summed over the handle's engines
+      !strcmp(key, "beam_cross_shared_launches") || !strcmp(key, "beam_self_tree_launches") || !strcmp(key, "cross_span_launches")) {  // counts: summed over the handle's engines
     long sum = 0;
     for (int i = 0; i < h->group.size(); ++i) {
       Engine& e = h->group.at(i);
@@ -584,6 +584,16 @@ AX_WHISPER_API int AX_WHISPER_GetCrossKVFp8(AX_WHISPER_HANDLE handle, int slot, 
 AX_WHISPER_API int AX_WHISPER_CrossKVQuantize(AX_WHISPER_HANDLE handle) {
   if (!handle) return -1;
   return guarded(handle, [&](Engine& e) { e.cross_kv_quantize(); });
+}
+
+AX_WHISPER_API int AX_WHISPER_CrossSpanAttention(AX_WHISPER_HANDLE handle, int layer, int n, const float* q, const int* spans, float* out) {
+  if (!handle || !q || !spans || !out || n < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.cross_span_attention(layer, n, q, spans, out); });
+}
+
+AX_WHISPER_API int AX_WHISPER_GetCrossSpans(AX_WHISPER_HANDLE handle, int* out) {
+  if (!handle || !out) return -1;
+  return guarded(handle, [&](Engine& e) { e.get_cross_spans(out); });
 }
 
 AX_WHISPER_API int AX_WHISPER_ScanStored16(AX_WHISPER_HANDLE handle, int batch, int n_max, char* names, int64_t* nonfinite,

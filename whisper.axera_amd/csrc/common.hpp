@@ -557,6 +557,41 @@ struct DecAttnGroupFp8Kv {
 struct DecAttnGroupFp8Params : DecAttnGroupFp8Kv, AttnQuerySource, AttnResultSink {};
 void launch_decode_cross_attention_group_fp8(const DecAttnGroupFp8Params& p, hipStream_t s);
 
+// ---- cross-attention over each slot's own audio span (decode_attention_span.hip; opt-in): a work list instead of a grid of
+// (split, head, clip). An encoder frame is 320 samples; a slot's span is the frames of its audio plus a margin of padding frames.
+AXW_LAYOUT_FN int cross_span_frames(int samples, int margin, int n_keys) {
+  const long f = ((long)(samples > 0 ? samples : 0) + 319) / 320 + (margin > 0 ? margin : 0);
+  return f < 1 ? 1 : f > n_keys ? n_keys : (int)f;
+}
+constexpr int kSpanMaxRanges = 4;  // slot ranges (branches of the step graph) one plan launch serves
+// one workgroup's work: blocks [first, first + count) of (slot, head), piece `piece` of `pieces`, over the slot's first n_keys keys
+struct CrossSpanItem { int slot_head /* slot | head << 16 */, blocks /* first | count << 16 */, piece /* piece | pieces << 16 */, n_keys; };
+struct CrossSpanPlanParams {
+  const int* spans;          // [slots] of the handle, slot 0
+  int n_keys, n_head;        // n_audio_ctx: spans are clamped to [1, n_keys]
+  CrossSpanItem* items;      // list of range r at items + b0[r] * n_head * kAttnSplitMax
+  int* counts;               // its length at counts[b0[r] / 16]
+  int n_ranges;
+  int b0[kSpanMaxRanges], nb[kSpanMaxRanges];  // b0: a multiple of 16; item slots are relative to it
+  int target[kSpanMaxRanges];                  // workgroups the range's blocks are divided among
+  int max_pieces, min_blocks;                  // pieces per (slot, head) at most (1 .. kAttnSplitMax); blocks per piece the division aims for at least
+};
+void launch_cross_span_plan(const CrossSpanPlanParams& p, hipStream_t s);
+// K/V (h16 images, or with k8 != nullptr the code images and scales), the list and the launch's slots; the query source (read or
+// fused; no folded mode) and the sink have the origin of the range's first slot, as the items' slot indices do. n_split is not read:
+// the records of a (slot, head) lie kAttnSplitMax apart.
+struct DecAttnSpanKv {
+  const h16* k; const h16* v; long kv_slot_stride;
+  const unsigned char* k8; const unsigned char* v8; long kv_slot_bytes;
+  const float* scales; long scale_slot_stride;
+  const CrossSpanItem* items; const int* count;
+  int batch, cap_blocks;
+  int grid;                  // workgroups: at least the list's length whatever the spans (Engine::span_grid)
+};
+struct DecAttnSpanParams : DecAttnSpanKv, AttnQuerySource, AttnResultSink {};
+void launch_decode_cross_attention_span(const DecAttnSpanParams& p, hipStream_t s);
+void launch_cross_span_set(const int* samples, const int* slot_map, int* spans, int count, int n_slots, int margin, int n_keys, hipStream_t s);
+
 // ---- tree self-attention (decode_attention_tree.hip; beam search over an ancestry table, opt-in): the slots [c * group, c * group +
 // group) are the ranks of clip c, the self K/V never moves between them, and origin[slot][p] (uint8, a local slot 0 .. group - 1) says
 // which of the clip's slots holds the K/V row of position p < off[slot] of the hypothesis living in `slot`; position off[slot] is the

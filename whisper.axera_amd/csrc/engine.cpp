@@ -165,6 +165,21 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
     cfg_.ints["cross_kv_fp8"] = cross_fp8_ ? 1 : 0;
     cfg_.ints["cross_kv_fp8_launches"] = 0;
   }
+  {  // cross-attention over each slot's own audio span (decode_attention_span.hip): opt-in, absent or "full": all n_audio_ctx frames
+    const char* e = getenv("AX_WHISPER_CROSS_SPAN");
+    if (e && !strcmp(e, "audio")) cross_span_ = true;
+    else if (e && e[0] && strcmp(e, "full")) throw std::runtime_error(std::string("AX_WHISPER_CROSS_SPAN=") + e + ": expected full or audio");
+    if (const char* m = getenv("AX_WHISPER_CROSS_SPAN_MARGIN")) {
+      char* end = nullptr;
+      const long v = strtol(m, &end, 10);
+      if (end == m || *end || v < 0 || v > 1000000) throw std::runtime_error(std::string("AX_WHISPER_CROSS_SPAN_MARGIN=") + m + ": expected a number of encoder frames");
+      cross_span_margin_ = (int)v;
+    }
+    if (const char* t = getenv("AX_WHISPER_CROSS_SPAN_PIECES")) cross_span_pieces_ = std::max(1, std::min(layout::kAttnSplitMax, atoi(t)));
+    cfg_.ints["cross_span"] = cross_span_ ? 1 : 0;
+    cfg_.ints["cross_span_margin"] = cross_span_margin_;
+    cfg_.ints["cross_span_launches"] = 0;
+  }
   {  // beam search over one cross K/V copy per clip (decode_attention_group.hip): opt-in, absent or "copy": a copy per hypothesis
     const char* e = getenv("AX_WHISPER_BEAM_CROSS");
     if (e && !strcmp(e, "shared")) beam_cross_shared_ = true;
@@ -577,6 +592,17 @@ void Engine::ensure_capacity(int batch) {
     d_cross_v8_ = (unsigned char*)A((size_t)L * B * H * layout::kv8_head_bytes(t_pad_), true);
     d_cross_scales_ = (float*)A((size_t)layout::kv8_scale_elems(L, B, H) * 4, true);
   }
+  if (cross_span_) {
+    d_cross_span_ = (int*)A((size_t)B * 4);
+    d_cross_span_next_ = (int*)A((size_t)B * 4);
+    d_span_samples_ = (int*)A((size_t)B * 4, true);
+    d_span_items_ = (CrossSpanItem*)A((size_t)B * H * layout::kAttnSplitMax * sizeof(CrossSpanItem), true);
+    d_span_count_ = (int*)A((size_t)((B + 15) / 16) * 4, true);  // zero: a launch before the first plan has no items
+    span_plan_batch_ = 0;
+    const std::vector<int> full(B, T);  // every slot's length is unknown
+    HIP_CHECK(hipMemcpy(d_cross_span_, full.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_cross_span_next_, full.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+  }
   d_self_k_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
   d_self_v_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
   d_xdec_ = (float*)A((size_t)B * d * 4, true);
@@ -615,6 +641,7 @@ void Engine::ensure_capacity(int batch) {
   d_out_ids_ = (int*)A((size_t)B * Tc * 4, true);
   d_state_ = (DecState*)A(sizeof(DecState), true);
   cap_ = B;
+  cfg_.ints["capacity"] = B;  // slots of the handle: max_batch of Init, or what a larger call grew it to
   cfg_.ints["decode_branches"] = (B > 4 && batched_ln_) ? decode_branches(B) : 1;  // at full capacity (bench.py reads it)
 }
 
@@ -886,7 +913,8 @@ void Engine::build_cblock_fold() {
 }
 
 // ------------------------------------------------------------------------------ encoder
-void Engine::run_encoder(int batch, const int* d_slot_map) {
+void Engine::run_encoder(int batch, const int* d_slot_map, const int* d_samples) {
+  enqueue_cross_spans(d_samples, batch, d_slot_map);
   const int d = cfg_.n_text_state, nm = cfg_.n_mels, T = cfg_.n_audio_ctx, H = cfg_.n_audio_head, L = cfg_.n_text_layer;
   hipStream_t s = stream();
   GemmParams g{};
@@ -986,6 +1014,74 @@ void Engine::enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStre
   launch_cross_kv_quantize(q, s);
 }
 
+// ------------------------------------------------------------------------------ cross-attention spans
+void Engine::enqueue_cross_spans(const int* d_samples, int count, const int* d_slot_map) {
+  if (!cross_span_) return;
+  // an open slot stream: the step graph may be reading the live spans and the work lists built from them; the admitted clips' spans
+  // wait in d_cross_span_next_ until slot_reset_kernel takes them over, in stream order with the steps
+  int* dst = stream_slots_ > 0 ? d_cross_span_next_ : d_cross_span_;
+  launch_cross_span_set(d_samples, d_slot_map, dst, count, cap_, cross_span_margin_, cfg_.n_audio_ctx, stream());
+  if (stream_slots_ == 0) span_plan_batch_ = 0;
+}
+
+void Engine::upload_cross_spans(const int* samples, int count) {
+  if (!cross_span_) return;
+  hipStream_t s = stream();
+  HIP_CHECK(hipMemcpyAsync(d_span_samples_, samples, (size_t)count * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));  // (the caller's vector)
+}
+
+void Engine::get_cross_spans(int* out) {
+  if (!cross_span_) throw std::runtime_error("get_cross_spans: the handle was not made under AX_WHISPER_CROSS_SPAN=audio");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  HIP_CHECK(hipMemcpy(out, d_cross_span_, (size_t)cap_ * 4, hipMemcpyDeviceToHost));
+}
+
+// The plan and the span kernel alone: q -> d_qdec_, the caller's spans in place of the slots' (restored afterwards), one launch over
+// slots [0, n) of `layer`, the fragment-major (hi, lo) output pair read back as hi + lo.
+void Engine::cross_span_attention(int layer, int n, const float* q, const int* spans, float* out) {
+  if (!cross_span_) throw std::runtime_error("cross_span_attention: the handle was not made under AX_WHISPER_CROSS_SPAN=audio");
+  require_no_stream("cross_span_attention");
+  const int d = cfg_.n_text_state, H = cfg_.n_text_head;
+  if (layer < 0 || layer >= cfg_.n_text_layer || n < 1 || n > cap_) throw std::runtime_error("cross_span_attention: layer or slot count out of range");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  hipStream_t s = stream();
+  std::vector<int> keep(cap_);
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipMemcpy(keep.data(), d_cross_span_, (size_t)cap_ * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(d_cross_span_, spans, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_qdec_, q, (size_t)n * d * 4, hipMemcpyHostToDevice));
+  CrossSpanPlanParams pl{};
+  pl.spans = d_cross_span_; pl.n_keys = cfg_.n_audio_ctx; pl.n_head = H; pl.items = d_span_items_; pl.counts = d_span_count_;
+  pl.n_ranges = 1; pl.b0[0] = 0; pl.nb[0] = n; pl.target[0] = span_target(n);
+  pl.max_pieces = cross_span_pieces_; pl.min_blocks = 2;
+  launch_cross_span_plan(pl, s);
+  span_plan_batch_ = 0;  // the lists on the device are this call's
+  const long cross_stride = H * layout::kv_head_elems(t_pad_);
+  DecAttnParams a = attn_params(d_qdec_, d_cross_k_ + (size_t)layer * cap_ * cross_stride, d_cross_v_ + (size_t)layer * cap_ * cross_stride,
+                                cross_stride, cfg_.n_audio_ctx, t_pad_ / 64, 0, n, true);
+  a.out_hi = d_att_[0]; a.out_lo = d_att_[1]; a.nbs = nbs_;
+  a.mpart = d_attn_mpart_; a.mcnt = d_attn_mcnt_;
+  launch_cross_attention_span(a, cross_fp8_, layer, 0, s);
+  note_span_launches(enq_span_launches_);
+  enq_span_launches_ = 0;
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));
+  const size_t pair = (size_t)layout::pair_elems(d / 32, nbs_);
+  std::vector<uint16_t> hi(pair), lo(pair);
+  HIP_CHECK(hipMemcpy(hi.data(), d_att_[0], pair * 2, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(lo.data(), d_att_[1], pair * 2, hipMemcpyDeviceToHost));
+  for (int b = 0; b < n; ++b)
+    for (int c = 0; c < d; ++c) {
+      const size_t i = (size_t)layout::frag_index(b, c, nbs_);
+      out[(size_t)b * d + c] = h16_bits_to_float(hi[i]) + h16_bits_to_float(lo[i]);
+    }
+  HIP_CHECK(hipMemcpy(d_cross_span_, keep.data(), (size_t)cap_ * 4, hipMemcpyHostToDevice));
+}
+
 void Engine::cross_kv_quantize() {
   if (!cross_fp8_) throw std::runtime_error("cross_kv_quantize: the handle was not made under AX_WHISPER_CROSS_KV=fp8");
   require_no_stream("cross_kv_quantize");
@@ -1022,7 +1118,7 @@ void Engine::run_tokens(const DecodeRequest& rq, const float* const* pcm, const 
     run_frontend(d_pcm, d_stride, n_samples, batch, false);
   }
   HIP_CHECK(hipEventRecord(ev_[1], s));
-  run_encoder(batch);
+  run_encoder(batch, nullptr, d_nsamp_);  // (the front-end left the clips' 16 kHz lengths there)
   HIP_CHECK(hipEventRecord(ev_[2], s));
   const int steps = greedy_loop(step_spec(mode), batch, rq.max_new, rq.max_new_clip, rq.ctx);
   fetch_ids(batch, ids, n_ids);

@@ -105,8 +105,10 @@ struct EngineMemory {
 struct EngineGraphs {
   // key: Engine::graph_key; with every captured step, the fp8 cross-attention launches one replay of it runs
   // and the grouped ones (beam search with a shared cross K/V), and the tree self-attention launches (beam search over an ancestry table)
-  struct StepGraph { GraphExec exec; int fp8_launches = 0; int group_launches = 0; int tree_launches = 0; };
-  struct StepGraphRef { hipGraphExec_t exec; int fp8_launches; int group_launches; int tree_launches; operator hipGraphExec_t() const { return exec; } };  // what step_graph() hands out
+  // span_launches / span_batch: the span cross-attention launches of one replay and the slots the step's work lists are planned for
+  // (0: none; Engine::launch_step_graph replans before a replay when spans have changed)
+  struct StepGraph { GraphExec exec; int fp8_launches = 0; int group_launches = 0; int tree_launches = 0; int span_launches = 0; int span_batch = 0; };
+  struct StepGraphRef { hipGraphExec_t exec; int fp8_launches; int group_launches; int tree_launches; int span_launches; int span_batch; operator hipGraphExec_t() const { return exec; } };  // what step_graph() hands out
   std::map<long, StepGraph> graphs_;
 };
 
@@ -133,6 +135,11 @@ struct SlotViews {
   // the h16 images; null on a default handle
   unsigned char *d_cross_k8_ = nullptr, *d_cross_v8_ = nullptr;
   float* d_cross_scales_ = nullptr;
+  // cross-attention over each slot's span (AX_WHISPER_CROSS_SPAN=audio; decode_attention_span.hip): the spans the step reads [cap], the
+  // spans of clips admitted to a slot stream but not yet decoding [cap] (slot_reset_kernel moves a slot's entry over), sample counts
+  // staged for the span kernel [cap], the work lists [cap][H][kAttnSplitMax] and their lengths [cap / 16]; null on a default handle
+  int *d_cross_span_ = nullptr, *d_cross_span_next_ = nullptr, *d_span_samples_ = nullptr, *d_span_count_ = nullptr;
+  CrossSpanItem* d_span_items_ = nullptr;
   float *d_xdec_ = nullptr, *d_qdec_ = nullptr, *d_hid_ = nullptr, *d_part_self_ = nullptr, *d_part_cross_ = nullptr;
   h16 *d_act_[2] = {nullptr, nullptr}, *d_att_[2] = {nullptr, nullptr}, *d_hidp_[2] = {nullptr, nullptr};
   float* d_part_ = nullptr; float* d_amax_val_ = nullptr; int* d_amax_idx_ = nullptr;
@@ -263,7 +270,9 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // pinned_ns: optional pinned host [batch] the clip lengths are staged through (then nothing here waits for the stream)
   void run_frontend(const float* d_pcm, int stride, const int* n_samples, int batch, bool want_ref_layout, bool staged = false,
                     int* pinned_ns = nullptr);
-  void run_encoder(int batch, const int* d_slot_map = nullptr);  // cross K/V of clip b goes to slot d_slot_map[b] (device), else b
+  // cross K/V of clip b goes to slot d_slot_map[b] (device), else b; d_samples (device, or null: unknown): the clips' sample counts
+  // at 16 kHz, from which a span handle takes the slots' spans
+  void run_encoder(int batch, const int* d_slot_map = nullptr, const int* d_samples = nullptr);
   void reset_decode_state(int batch, const int* max_new_clip = nullptr);
   // What one decoder step is built as: every step sequence, the graph it is captured into and the key that graph is cached
   // under are made from ONE of these, handed down as an argument.
@@ -294,8 +303,17 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     // slots run one workgroup per (head, clip) over beam_.origin, and the self K/V never moves between slots; K here, 0: every slot
     // streams its own cache. Set by beam_step_spec alone, on a handle made under AX_WHISPER_BEAM_SELF=tree.
     int self_group = 0;
+    // the cross-attention launches of a step of more than gemv_max_ slots run decode_cross_attention_span_kernel over the handle's
+    // work lists (over the code images with cross_fp8); set from the handle's mode by step_spec(). Beam search and the steps of
+    // engine_prefill.cpp leave it clear. Such a step keeps the fused query projection (no clip-block query fold).
+    bool cross_span = false;
   };
-  StepSpec step_spec(DecodeMode mode = kDecodePlain, int mask = 15) const { StepSpec sp{mode, mask}; sp.cross_fp8 = cross_fp8_; return sp; }
+  StepSpec step_spec(DecodeMode mode = kDecodePlain, int mask = 15) const {
+    StepSpec sp{mode, mask};
+    sp.cross_fp8 = cross_fp8_;
+    sp.cross_span = cross_span_;
+    return sp;
+  }
   // logits rows of one step that leave it: plain mode, the caller's; timestamp and scored mode, every row, into d_ts_logits_ for
   // the rules kernel; first_step: the first decode step whose row is computed
   struct LogitsDump { float* rows; long stride; int first_step; };
@@ -322,7 +340,7 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
     const bool suppress = spec.mode != kDecodePlain && (spec.mask & 4) && suppress_mask();
     const bool rep = spec.mode != kDecodePlain && (spec.mask & 4) && repetition_rules_dev();
     // (self_group and the repetition bit sit above every other field: a key without them is the number it always was)
-    return ((long)spec.self_group << 56) | (rep ? 1L << 55 : 0) | ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 9) | ((long)spec.cross_group << 5) |
+    return ((long)spec.self_group << 56) | (rep ? 1L << 55 : 0) | (spec.cross_span ? 1L << 54 : 0) | ((((long)batch * 1024 + max_new) * 32 + spec.mask) << 9) | ((long)spec.cross_group << 5) |
            (spec.cross_fp8 ? 16 : 0) | (suppress ? 8 : 0) | (spec.slots ? 4 : 0) | spec.mode;
   }
   void require_timestamp_vocab() const;
@@ -543,6 +561,29 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   // The self-attention launch `a` describes for layer l, slots [b0, b0 + a.batch): the tree kernel where the step asks for it, else
   // decode_attention_kernel — which a stamped (measurement) launch always keeps
   void launch_self_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s);
+  // Cross-attention over each slot's span (DESIGN.md "Cross-attention spans"): the handle's mode and margin (read at construction)
+  // and the launches that took the span kernel ("cross_span_launches"), counted as the fp8 launches are.
+  bool cross_span_ = false;
+  int cross_span_margin_ = 100;    // encoder frames of padding a slot keeps behind its audio
+  int cross_span_pieces_ = layout::kAttnSplitMax;  // AX_WHISPER_CROSS_SPAN_PIECES (A/B): pieces per (slot, head) at most
+  long cross_span_launches_ = 0;
+  int enq_span_launches_ = 0;
+  int span_plan_batch_ = 0;        // slots the work lists on the device are planned for (0: none, or the spans changed since)
+  void note_span_launches(long n) { if (n) { cross_span_launches_ += n; cfg_.ints["cross_span_launches"] = (int)cross_span_launches_; } }
+  // spans of `count` clips from their sample counts on the device (nullptr: length unknown, n_audio_ctx), clip i -> slot
+  // d_slot_map[i] (nullptr: i); on an open slot stream into d_cross_span_next_. Enqueued on stream(); no-op on a default handle.
+  void enqueue_cross_spans(const int* d_samples, int count, const int* d_slot_map);
+  // the same from host sample counts (long-form windows): staged through d_span_samples_, waits for the stream
+  void upload_cross_spans(const int* samples, int count);
+  // slot ranges of the cross-attention launches of a step of `batch` slots, as enqueue_decode_step_batched forms them
+  int span_ranges(int batch, int* b0, int* nb) const;
+  int span_target(int nb) const;   // workgroups a range's blocks are divided among
+  int span_grid(int nb) const;     // workgroups of its launches: a bound of the list's length whatever the spans
+  // the work lists of a step of `batch` slots, on the stream, if the ones on the device are not those
+  void ensure_span_plan(int batch, hipStream_t s);
+  void launch_cross_attention_span(const DecAttnParams& a, bool fp8, int l, int b0, hipStream_t s);
+  void cross_span_attention(int layer, int n, const float* q, const int* spans, float* out) override;
+  void get_cross_spans(int* out) override;
   void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s);
   // the fp8 cross-attention launch of layer l for clips [b0, b0 + nb) with a's query mode, splits and outputs
   void launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s);

@@ -243,6 +243,20 @@ float Engine::bench_decode_step(const std::string& what, int batch, int arg, int
   hipStream_t s = stream();
   const int Tc = cfg_.n_text_ctx;
   reset_decode_state(batch);
+  if (spec.cross_span) {
+    // AX_WHISPER_BENCH_CROSS_SPAN=<keys>: that span for every slot (absent: n_audio_ctx, a slot of unknown length); "mixed": spans
+    // uniform in 150 .. n_audio_ctx from a fixed sequence
+    const char* e = getenv("AX_WHISPER_BENCH_CROSS_SPAN");
+    std::vector<int> sp(batch, cfg_.n_audio_ctx);
+    unsigned long long x = 0x9E3779B97F4A7C15ull;
+    for (int b = 0; b < batch && e; ++b) {
+      x = x * 6364136223846793005ull + 1442695040888963407ull;
+      sp[b] = !strcmp(e, "mixed") ? 150 + (int)((x >> 33) % (unsigned long long)std::max(1, cfg_.n_audio_ctx - 149))
+                                  : std::max(1, std::min(cfg_.n_audio_ctx, atoi(e)));
+    }
+    HIP_CHECK(hipMemcpy(d_cross_span_, sp.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
+    span_plan_batch_ = 0;
+  }
   if (spec.self_group) {  // a tree step reads the ancestry table: the placement of bench_decode_step_beam
     ensure_beam_buffers();
     beam_origin_begin(beam_clips, beam_size, std::max(0, std::min(arg, Tc - 1 - iters)), !bench_tree_identity());

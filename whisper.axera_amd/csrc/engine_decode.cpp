@@ -36,9 +36,12 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
   // 3+ clips: the clip-block sequence (a 4-clip step: 0.78 ms through the GEMV family, 0.59 through clip-block GEMMs);
   // one clip that cannot use the persistent launch and two clips that cannot either stay on the GEMV family
   if (batch > gemv_max_) {
-    const int fp8_before = enq_fp8_launches_, group_before = enq_group_launches_, tree_before = enq_tree_launches_;
+    const int fp8_before = enq_fp8_launches_, group_before = enq_group_launches_, tree_before = enq_tree_launches_, span_before = enq_span_launches_;
+    // (a captured step is planned for at its replays: launch_step_graph)
+    if (spec.cross_span && !spec.cross_group && !in_step_capture_) ensure_span_plan(batch, stream());
     enqueue_decode_step_batched(spec, batch, max_new, d_forced, n_forced, d_logits, logits_stride, d_argmax);
     if (!in_step_capture_) {  // enqueued directly: these launches run once
+      note_span_launches(enq_span_launches_ - span_before);
       note_fp8_launches(enq_fp8_launches_ - fp8_before);
       note_group_launches(enq_group_launches_ - group_before);
       note_tree_launches(enq_tree_launches_ - tree_before);
@@ -214,6 +217,7 @@ void Engine::launch_cross_attention_group_fp8(const DecAttnParams& a, int l, int
 void Engine::launch_cross_attention(const StepSpec& spec, const DecAttnParams& a, int l, int b0, hipStream_t s) {
   if (spec.cross_group && spec.cross_fp8 && !a.stamp) launch_cross_attention_group_fp8(a, l, b0, spec.cross_group, s);
   else if (spec.cross_group && !a.stamp) launch_cross_attention_group(a, l, b0, spec.cross_group, s);
+  else if (spec.cross_span && !a.stamp) launch_cross_attention_span(a, spec.cross_fp8, l, b0, s);
   else if (spec.cross_fp8 && !a.stamp) launch_cross_attention_fp8(a, l, b0, s);
   else launch_decode_attention(a, s);
 }
@@ -239,6 +243,66 @@ void Engine::launch_self_attention(const StepSpec& spec, const DecAttnParams& a,
   ++enq_tree_launches_;
 }
 
+// ---- cross-attention spans (decode_attention_span.hip). The launch `a` describes for slots [b0, b0 + a.batch) of layer l as a work
+// list: its query (read or fused), done flags and outputs; the list of the range that starts at b0, which ensure_span_plan built
+void Engine::launch_cross_attention_span(const DecAttnParams& a, bool fp8, int l, int b0, hipStream_t s) {
+  const int H = cfg_.n_text_head;
+  if (b0 % 16 != 0) throw std::runtime_error("span cross-attention: a slot range starts inside a clip block");
+  DecAttnSpanParams p{};
+  static_cast<AttnQuerySource&>(p) = a; static_cast<AttnResultSink&>(p) = a;
+  if (fp8) {
+    const long slot_bytes = H * layout::kv8_head_bytes(t_pad_);
+    p.k8 = d_cross_k8_ + ((size_t)l * cap_ + b0) * slot_bytes;
+    p.v8 = d_cross_v8_ + ((size_t)l * cap_ + b0) * slot_bytes;
+    p.kv_slot_bytes = slot_bytes;
+    p.scales = d_cross_scales_ + layout::kv8_scale_index(l, b0, 0, 0, 0, cap_, H);
+    p.scale_slot_stride = (long)H * layout::kKv8ScaleHead;
+  } else {
+    p.k = a.k; p.v = a.v; p.kv_slot_stride = a.kv_batch_stride;
+  }
+  p.items = d_span_items_ + (size_t)b0 * H * layout::kAttnSplitMax;
+  p.count = d_span_count_ + b0 / 16;
+  p.batch = a.batch; p.cap_blocks = a.cap_blocks;
+  p.grid = span_grid(a.batch);
+  launch_decode_cross_attention_span(p, s);
+  ++enq_span_launches_;
+  if (fp8) ++enq_fp8_launches_;
+}
+
+int Engine::span_ranges(int batch, int* b0, int* nb) const {
+  const int nbr = batched_ln_ ? decode_branches(batch) : 1;
+  if (nbr == 1) { b0[0] = 0; nb[0] = batch; return 1; }
+  const int per = ((batch + nbr - 1) / nbr + 15) / 16 * 16;  // (enqueue_decode_step_batched)
+  int n = 0;
+  for (int i = 0; i < nbr && i * per < batch; ++i) { b0[n] = i * per; nb[n] = std::min(per, batch - i * per); ++n; }
+  return n;
+}
+
+// One workgroup per (slot, head) where those fill the chip; fewer slots are cut into pieces up to one workgroup per CU (the bound the
+// fixed splits keep: enqueue_layers_cblock)
+int Engine::span_target(int nb) const {
+  const int pairs = nb * cfg_.n_text_head;
+  return std::max(pairs, std::min(pairs * cross_span_pieces_, std::max(n_cu_, 64)));
+}
+// pieces of a slot <= blocks / per + 1 and sum(blocks) / per <= target: the list holds at most target + pairs items
+int Engine::span_grid(int nb) const {
+  const int pairs = nb * cfg_.n_text_head;
+  return std::min(pairs * cross_span_pieces_, span_target(nb) + pairs);
+}
+
+void Engine::ensure_span_plan(int batch, hipStream_t s) {
+  if (span_plan_batch_ == batch) return;
+  static_assert(kSpanMaxRanges >= kMaxBranches, "a range per branch");
+  CrossSpanPlanParams pl{};
+  pl.spans = d_cross_span_; pl.n_keys = cfg_.n_audio_ctx; pl.n_head = cfg_.n_text_head;
+  pl.items = d_span_items_; pl.counts = d_span_count_;
+  pl.n_ranges = span_ranges(batch, pl.b0, pl.nb);
+  for (int r = 0; r < pl.n_ranges; ++r) pl.target[r] = span_target(pl.nb[r]);
+  pl.max_pieces = cross_span_pieces_; pl.min_blocks = 2;
+  launch_cross_span_plan(pl, s);
+  span_plan_batch_ = batch;
+}
+
 int Engine::cross_split_count(int wg_per_split, int blocks, int wg_limit) const {
   if (cross_split_env_ > 0 && cross_split_env_ <= layout::kAttnSplitMax && blocks % cross_split_env_ == 0) return cross_split_env_;
   for (int c : {6, 4, 3, 2})
@@ -248,7 +312,9 @@ int Engine::cross_split_count(int wg_per_split, int blocks, int wg_limit) const 
 
 // a step_graph() exec on the stream; its fp8 and grouped cross-attention launches are counted per replay
 void Engine::launch_step_graph(const StepGraphRef& g, hipStream_t s) {
+  if (g.span_batch) ensure_span_plan(g.span_batch, s);  // a launch of its own in front of the graph, only when spans have changed
   HIP_CHECK(hipGraphLaunch(g.exec, s));
+  note_span_launches(g.span_launches);
   note_fp8_launches(g.fp8_launches);
   note_group_launches(g.group_launches);
   note_tree_launches(g.tree_launches);
@@ -331,7 +397,8 @@ void Engine::enqueue_layers_cblock(const StepSpec& spec, int b0, int nb, hipStre
     // Measured (profiles/r06_cblock_qfold_ab.txt, Whisper-small, step at t = 224): 4 clips 0.4915 -> 0.4784 ms, 8: 0.5317 -> 0.5119,
     // 16: 0.6244 -> 0.6115; 64 clips (two branches): 1.091 -> 1.135 — the attention launches gain 1 % there (the W_cq rows come from L2
     // beside 147 MB of K/V per launch) and the two fatter GEMM launches cost 7 % of the chain. So: one-branch steps only.
-    const bool qfold = !cfold_.empty() && fuse_cq && d <= 1024 && (one_branch || cfold_all_);
+    // (a span step keeps the fused projection: the span kernel has no folded query mode)
+    const bool qfold = !cfold_.empty() && fuse_cq && d <= 1024 && (one_branch || cfold_all_) && !spec.cross_span;
     float* a0 = d_a0_ + (long)b0 * d;
     float* statp = d_statp_ + (long)b0 * (d / 16) * 2;
     DecCGemmParams c = qfold ? cgemm(wq.w_qkv, cfold_[l].b_qkv4, 4 * d, d, GEPI_QKV_CACHE, rt_for(4 * d))
@@ -594,7 +661,7 @@ void Engine::ensure_branch_streams(int batch) {
 Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
   const long key = graph_key(spec, batch, max_new);  // plain and timestamp-mode steps are different graphs
   auto it = graphs_.find(key);
-  if (it != graphs_.end()) return {it->second.exec, it->second.fp8_launches, it->second.group_launches, it->second.tree_launches};
+  if (it != graphs_.end()) return {it->second.exec, it->second.fp8_launches, it->second.group_launches, it->second.tree_launches, it->second.span_launches, it->second.span_batch};
   hipStream_t s = stream();
   // nobody on this device allocates, copies synchronously or captures while this capture is open (iengine.hpp)
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
@@ -608,6 +675,7 @@ Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
   enq_fp8_launches_ = 0;
   enq_group_launches_ = 0;
   enq_tree_launches_ = 0;
+  enq_span_launches_ = 0;
   try {
     enqueue_decode_step(spec, batch, max_new, nullptr, 0, nullptr, 0, nullptr);
     cap_err = hipStreamEndCapture(s, &captured);
@@ -629,6 +697,7 @@ Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
     exec.reset(e);
   };
   instantiate();
+  if (enq_span_launches_) ensure_span_plan(batch, s);  // the probe's replays read the work lists: those of this batch, never an older plan's
   {  // which hardware queue the graph's second branch runs on decides the slot stream's rate (engine_stream.cpp:
      // graph_branch_shares_queue); AX_WHISPER_ALIGN_QUEUES=0: as it falls.
      // ORDER: the probe REPLAYS the step, i.e. runs real decoder steps on whatever state the buffers hold. Every caller
@@ -649,8 +718,9 @@ Engine::StepGraphRef Engine::step_graph(StepSpec spec, int batch, int max_new) {
       cfg_.ints["graph_queue_aligned"] = aligned ? 1 : 0;
     }
   }
-  StepGraph& kept = graphs_[key] = StepGraph{std::move(exec), enq_fp8_launches_, enq_group_launches_, enq_tree_launches_};
-  return {kept.exec, kept.fp8_launches, kept.group_launches, kept.tree_launches};
+  StepGraph& kept = graphs_[key] = StepGraph{std::move(exec), enq_fp8_launches_, enq_group_launches_, enq_tree_launches_, enq_span_launches_,
+                                             enq_span_launches_ ? batch : 0};
+  return {kept.exec, kept.fp8_launches, kept.group_launches, kept.tree_launches, kept.span_launches, kept.span_batch};
 }
 
 // Whisper.cpp:207-222. Returns the number of decoder steps executed.

@@ -254,7 +254,12 @@ void Engine::run_long_windows(const float* const* pcm, const int* n_samples, int
       upload_sample(SampleSpec{temps.data(), streams.data(), opts->seed}, A);
     }
     long_windows_to_slots(files.data(), seeks.data(), A, false);
-    run_encoder(A);
+    if (cross_span_) {  // a window's span follows the samples of the window, not of the file
+      std::vector<int> win_samples(A);
+      for (int i = 0; i < A; ++i) win_samples[i] = (int)std::min<long>((long)kFramesOut * kHop, (long)n_samples[files[i]] - (long)seeks[i] * kHop);
+      upload_cross_spans(win_samples.data(), A);
+    }
+    run_encoder(A, nullptr, d_span_samples_);
     if (prompted) {
       for (int i = 0; i < A; ++i) {
         const PromptCarry& c = carry[files[i]];
@@ -590,7 +595,12 @@ void Engine::run_long_chunked(const float* const* pcm, const int* n_samples, int
   for (int base = 0; base < total && (max_passes <= 0 || pass < max_passes); ++pass) {
     const int A = std::min(S, total - base);
     long_cut_windows_to_slots(base, A, false);
-    run_encoder(A);
+    if (cross_span_) {  // a window's span follows its own frames (win_len mel frames of kHop samples)
+      std::vector<int> win_samples(A);
+      for (int i = 0; i < A; ++i) win_samples[i] = std::min(kFramesOut, win_len[base + i]) * kHop;
+      upload_cross_spans(win_samples.data(), A);
+    }
+    run_encoder(A, nullptr, d_span_samples_);
     for (int i = 0; per_lang && i < A; ++i) { win_lang[i] = file_lang[win_file[base + i]]; win_task[i] = file_task[win_file[base + i]]; }
     steps += greedy_loop(spec, A, max_new, nullptr, ctx);
     fetch_ids(A, ids.data(), n_ids.data());

@@ -14,9 +14,11 @@ void Engine::require_no_stream(const char* what) const {
 }
 
 __global__ static void slot_reset_kernel(int slot, int max_new, const int* sot, int* off, int* tok, int* done, int* n_out, int* max_new_clip,
-                                         const h16* tok_emb, const float* pos, float* x, int d) {
+                                         const h16* tok_emb, const float* pos, float* x, int d, const int* span_next, int* span) {
   const int t = sot[0];
   if (threadIdx.x == 0) { off[slot] = 0; tok[slot] = t; n_out[slot] = 0; max_new_clip[slot] = max_new; done[slot] = 0; }
+  // a span handle (else both null): the span of the clip now in the slot, which its admission pass left beside the live one
+  if (threadIdx.x == 0 && span) span[slot] = span_next[slot];
   for (int c = threadIdx.x; c < d; c += blockDim.x) x[(long)slot * d + c] = (float)tok_emb[(long)t * d + c] + pos[c];  // position 0
 }
 
@@ -26,7 +28,9 @@ __global__ static void slot_reset_kernel(int slot, int max_new, const int* sot, 
 // [0 .. n_ids] by the sampled steps.
 __global__ static void slot_reset_ts_kernel(int slot, int max_new, int sot, int lang_tok, int task_tok, int lang_index, int detect, int n_lang,
                                             int* slot_ctx, int* slot_detect, int* slot_lang, float* slot_lang_lp, int* off, int* tok, int* done,
-                                            int* n_out, int* max_new_clip, const h16* tok_emb, const float* pos, float* x, int d) {
+                                            int* n_out, int* max_new_clip, const h16* tok_emb, const float* pos, float* x, int d,
+                                            const int* span_next, int* span) {
+  if (threadIdx.x == 0 && span) span[slot] = span_next[slot];  // (as slot_reset_kernel)
   if (threadIdx.x == 0) {
     off[slot] = 0; tok[slot] = sot; n_out[slot] = 0; max_new_clip[slot] = max_new; done[slot] = 0;
     slot_ctx[4 * slot] = sot; slot_ctx[4 * slot + 1] = lang_tok; slot_ctx[4 * slot + 2] = task_tok; slot_ctx[4 * slot + 3] = 0;
@@ -149,7 +153,7 @@ void Engine::stream_admit(const int* slots, const float* const* pcm, const int* 
   upload_pcm(pcm, n_samples, count, rates, n16.data());  // (with rates: uploads, then the resample kernel)
   HIP_CHECK(hipEventRecord(ev_upload_, admit_stream_));
   run_frontend(d_pcm_, (int)pcm_stride_, n16.data(), count, false, true, h_ns);
-  run_encoder(count, d_slot_map_);
+  run_encoder(count, d_slot_map_, d_nsamp_);
   HIP_CHECK(hipEventRecord(ev_ring_[ring], admit_stream_));
   ++admit_seq_;
   for (int i = 0; i < count; ++i) {
@@ -193,10 +197,11 @@ int Engine::stream_step(int n_steps, int* finished_slots) {
         hipLaunchKernelGGL(slot_reset_ts_kernel, dim3(1), dim3(256), 0, s, i, slot_max_new_[i], sot_seq_[0], cfg_.lang_tokens[slot_lang_[i]],
                            slot_task_[i], slot_lang_[i], slot_detect_[i], (int)cfg_.lang_tokens.size(),
                            d_slot_ctx_, d_slot_detect_, d_slot_lang_, d_slot_lang_lp_, d_off_, d_tok_, d_done_, d_nout_, d_max_new_clip_, tok_emb_,
-                           dec_pos_, d_xdec_, cfg_.n_text_state);
+                           dec_pos_, d_xdec_, cfg_.n_text_state, (const int*)d_cross_span_next_, d_cross_span_);
       else
         hipLaunchKernelGGL(slot_reset_kernel, dim3(1), dim3(256), 0, s, i, slot_max_new_[i], d_sot_, d_off_, d_tok_, d_done_, d_nout_,
-                           d_max_new_clip_, tok_emb_, dec_pos_, d_xdec_, cfg_.n_text_state);
+                           d_max_new_clip_, tok_emb_, dec_pos_, d_xdec_, cfg_.n_text_state, (const int*)d_cross_span_next_, d_cross_span_);
+      span_plan_batch_ = 0;  // a span handle plans again before the next step (launch_step_graph)
       slot_state_[i] = kActive;
       ++active;
     }

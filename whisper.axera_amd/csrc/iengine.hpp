@@ -106,6 +106,11 @@ class IEngine {
   // bytes and its scales [L][H][2][64]; the quantise kernel alone on every slot of the handle
   virtual void get_cross_kv_fp8(int slot, unsigned char* k_codes, unsigned char* v_codes, float* scales) = 0;
   virtual void cross_kv_quantize() = 0;
+  // Cross-attention spans (a handle made under AX_WHISPER_CROSS_SPAN=audio; throws on another). cross_span_attention: the plan and
+  // the span kernel alone over the handle's current cross K/V of `layer` (the code images on an FP8 handle), slots 0 .. n - 1, query
+  // from a buffer: q, out fp32 [n][d], spans [n] in keys. get_cross_spans: the spans the decoder steps read, out [capacity].
+  virtual void cross_span_attention(int layer, int n, const float* q, const int* spans, float* out) = 0;
+  virtual void get_cross_spans(int* out) = 0;
   // the slot's self-attention cache rows [0, n_rows), de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][d]
   virtual void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) = 0;
   // the self-attention cache of clip `clip` (1 or 2: its position in the last multi-clip persistent launch), all 8 blocks x 64 keys

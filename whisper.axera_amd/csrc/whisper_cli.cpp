@@ -60,6 +60,9 @@ static void usage(const char* prog) {
           "      --task T        transcribe or translate (with --timestamps or --long, not with --beam_size) [=transcribe]\n"
           "      --cross_kv h16|fp8   fp8: keep the cross K/V as e4m3fn codes too; decoder steps of more than two clips read them\n"
           "                      (opt-in, results differ from h16; under --beam_size only with --beam_cross shared)\n"
+          "      --cross_span full|audio   audio: decoder steps of more than two clips attend only over each clip's own audio span,\n"
+          "                      ceil(samples / 320) + AX_WHISPER_CROSS_SPAN_MARGIN (default 100) encoder frames (opt-in; the effect on a\n"
+          "                      trained model's transcripts is unmeasured; beam search reads all 1500 frames)\n"
           "      --beam_cross copy|shared   shared: the hypotheses of a clip under --beam_size read one cross K/V copy, the clip's own\n"
           "                      (opt-in; a beam's logits differ from the copy path in their last bits; with --cross_kv fp8 the copy is\n"
           "                      read as its FP8 codes)\n"
@@ -424,7 +427,7 @@ int main(int argc, char** argv) {
   bool condition = false, detect = false, chunked = false;
   std::string task_arg, cmax_arg, cmin_arg, csmooth_arg;
   std::string nst_arg, lpt_arg, crt_arg, tinc_arg, seed_arg, beam_arg, prompt_arg, suppress_arg, cross_kv_arg, beam_cross_arg, beam_self_arg;
-  std::string rep_penalty_arg, rep_ngram_arg;
+  std::string rep_penalty_arg, rep_ngram_arg, cross_span_arg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&](const char* lng, const char* sht, std::string& dst) -> bool {
@@ -444,7 +447,7 @@ int main(int argc, char** argv) {
         val("chunk_max_s", nullptr, cmax_arg) || val("chunk_min_s", nullptr, cmin_arg) || val("chunk_smooth_ms", nullptr, csmooth_arg) ||
         val("suppress_tokens", nullptr, suppress_arg) || val("cross_kv", nullptr, cross_kv_arg) || val("beam_cross", nullptr, beam_cross_arg) ||
         val("beam_self", nullptr, beam_self_arg) || val("repetition_penalty", nullptr, rep_penalty_arg) ||
-        val("no_repeat_ngram_size", nullptr, rep_ngram_arg))
+        val("no_repeat_ngram_size", nullptr, rep_ngram_arg) || val("cross_span", nullptr, cross_span_arg))
       continue;
     if (a == "--help" || a == "-?") { usage(argv[0]); return 0; }
     if (a == "--timestamps") { timestamps = true; continue; }
@@ -461,6 +464,8 @@ int main(int argc, char** argv) {
   if (wav.empty()) { fprintf(stderr, "need option: --wav\n"); usage(argv[0]); return 1; }
   // --cross_kv h16 | fp8: the library reads the mode from AX_WHISPER_CROSS_KV when the handle is made (a bad value fails Init)
   if (!cross_kv_arg.empty()) setenv("AX_WHISPER_CROSS_KV", cross_kv_arg.c_str(), 1);
+  // --cross_span full | audio: likewise, from AX_WHISPER_CROSS_SPAN
+  if (!cross_span_arg.empty()) setenv("AX_WHISPER_CROSS_SPAN", cross_span_arg.c_str(), 1);
   // --beam_cross copy | shared: likewise, from AX_WHISPER_BEAM_CROSS
   if (!beam_cross_arg.empty()) setenv("AX_WHISPER_BEAM_CROSS", beam_cross_arg.c_str(), 1);
   // --beam_self copy | tree: from AX_WHISPER_BEAM_SELF
