@@ -152,6 +152,21 @@ AX_WHISPER_API int AX_WHISPER_CrossKVQuantize(AX_WHISPER_HANDLE handle);
  *  a larger call grew the handle to). Both return -1 on a handle without the mode. */
 AX_WHISPER_API int AX_WHISPER_CrossSpanAttention(AX_WHISPER_HANDLE handle, int layer, int n, const float* q, const int* spans, float* out);
 AX_WHISPER_API int AX_WHISPER_GetCrossSpans(AX_WHISPER_HANDLE handle, int* out);
+/* Encoder over each clip's own audio span (opt-in; the third value of the option above): on a handle made while AX_WHISPER_CROSS_SPAN is
+ *  "encoder", everything "audio" does holds, and an encoder pass whose cross K/V only span kernels will read computes frames
+ *  [0, span) of a clip alone: their positional rows, self-attention among them, cross K/V (and FP8 codes) for them. Such a pass runs in
+ *  front of a decode of more than three slots without prompts, per-clip languages, detection, alignment or beam search (the batched
+ *  entry point, stream admission in plain mode); every other pass, long-form and chunked windows included, computes all 1500 frames. For one clip
+ *  this is whisper.cpp's audio_ctx = span: an approximation of the model, frames inside the span no longer attend to the padding
+ *  behind it. Its effect on a trained model's transcripts is unmeasured, so the mode is off by default. A reader that streams all 1500
+ *  frames (calls of one to three clips, prefill, alignment, detection, beam search, the stage-level decode calls) fails with an error
+ *  text on a slot whose last pass was truncated; GetCrossKV / GetCrossKVFp8 return such a slot's frames [0, encoded) and zeros behind.
+ *  AX_WHISPER_GetConfigInt: "cross_span" is 2, "encoder_span_passes" counts the truncated passes, "encoder_span_frames" is the row count
+ *  of the last one. EncoderSpanAttention: the ragged self-attention kernel alone, q / k / v / out fp32 [n][1500][64 n_audio_head], clip b
+ *  over its first spans[b] frames (clamped to 1 .. 1500); rows and columns at or beyond a span are not read as values, out rows at or
+ *  beyond it are zero. Returns -1 on a handle without the mode. AX_WHISPER_ENC_SPAN_ROWS=64|128 (read at Init of such a handle only) is a
+ *  test and A/B hook: it fixes the kernel's query-block height, which the engine otherwise chooses per pass. */
+AX_WHISPER_API int AX_WHISPER_EncoderSpanAttention(AX_WHISPER_HANDLE handle, int n, const float* q, const float* k, const float* v, const int* spans, float* out);
 /* Shared cross K/V under beam search (opt-in; a mode of Init, read through AX_WHISPER_GetConfigInt): on a handle made while the environment variable AX_WHISPER_BEAM_CROSS is "shared", the
  *  K hypotheses of a clip read ONE cross K/V copy, the clip's own, through a grouped cross-attention kernel, in beam calls of more
  *  than two slots with K > 1 (an FP8 cross K/V handle keeps the copies). Absent or "copy": today's behaviour, a copy per hypothesis;

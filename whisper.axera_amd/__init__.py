@@ -88,6 +88,7 @@ SYMBOLS = {
     "AX_WHISPER_CrossKVQuantize": (C.c_int, [C.c_void_p]),
     "AX_WHISPER_CrossSpanAttention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, fp, C.POINTER(C.c_int), fp]),
     "AX_WHISPER_GetCrossSpans": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "AX_WHISPER_EncoderSpanAttention": (C.c_int, [C.c_void_p, C.c_int, fp, fp, fp, C.POINTER(C.c_int), fp]),
     "AX_WHISPER_ScanStored16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int64), fp, C.POINTER(C.c_int)]),
     "AX_WHISPER_DecodeForced": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int, fp, ip]),
     "AX_WHISPER_DecodeGreedy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip, C.POINTER(C.c_int)]),
@@ -651,7 +652,9 @@ class Whisper:
         referenced block once per clip (opt-in; DESIGN.md "Tree self-attention"); "copy" or None: cache blocks move with hypotheses.
         cross_span: "audio" lets the cross-attention of decoder steps of more than two slots read only each clip's own audio span,
         min(1500, ceil(samples / 320) + margin) encoder frames (opt-in, effect on a trained model's transcripts unmeasured; DESIGN.md
-        "Cross-attention spans"; the margin is AX_WHISPER_CROSS_SPAN_MARGIN frames, default 100); "full" or None: all 1500 frames.
+        "Cross-attention spans"; the margin is AX_WHISPER_CROSS_SPAN_MARGIN frames, default 100); "encoder": the same, and an encoder
+        pass whose cross K/V only those launches will read computes the clip's span of frames alone (for one clip whisper.cpp's
+        audio_ctx; opt-in, effect on transcripts unmeasured; DESIGN.md "Encoder spans"); "full" or None: all 1500 frames.
         The library reads the modes from AX_WHISPER_CROSS_KV / AX_WHISPER_BEAM_CROSS / AX_WHISPER_BEAM_SELF / AX_WHISPER_CROSS_SPAN while the handle is made: the variables are
         set for that call and put back afterwards, under a lock that every construction with such an argument takes (a handle made
         at the same moment on another thread WITHOUT the arguments, or by other code through the C ABI, reads whatever the variables
@@ -1796,6 +1799,18 @@ class Whisper:
         out = np.empty_like(q)
         self._check(self.L.AX_WHISPER_CrossSpanAttention(self.h, layer, len(spans), q.ctypes.data_as(fp), spans.ctypes.data_as(C.POINTER(C.c_int)),
                                                          out.ctypes.data_as(fp)), "CrossSpanAttention")
+        return out
+
+    def encoder_span_attention(self, q, k, v, spans):
+        """The ragged encoder self-attention kernel alone on a cross_span="encoder" handle: q, k, v fp32 [n][n_audio_ctx][d]; clip b
+        attends among its first spans[b] frames. Rows at or beyond a span are never read as values (they may hold NaN). Returns fp32
+        [n][n_audio_ctx][d] with rows at or beyond a clip's span zero."""
+        q, k, v = (np.ascontiguousarray(a, dtype=np.float32) for a in (q, k, v))
+        spans = np.ascontiguousarray(spans, dtype=np.int32)
+        assert q.ndim == 3 and q.shape[0] == len(spans) and q.shape == k.shape == v.shape
+        out = np.empty_like(q)
+        self._check(self.L.AX_WHISPER_EncoderSpanAttention(self.h, len(spans), q.ctypes.data_as(fp), k.ctypes.data_as(fp), v.ctypes.data_as(fp),
+                                                           spans.ctypes.data_as(C.POINTER(C.c_int)), out.ctypes.data_as(fp)), "EncoderSpanAttention")
         return out
 
     def cross_spans(self):

@@ -522,7 +522,8 @@ AX_WHISPER_API int AX_WHISPER_GetConfigInt(AX_WHISPER_HANDLE handle, const char*
   if (!strcmp(key, "n_devices")) return h->group.size();
   if (!strcmp(key, "live_hip_objects")) return (int)axw::live_owned.load();  // test hook: of every handle of the process
   if (!strcmp(key, "persistent_giveups") || !strcmp(key, "persistent_ts_launches") || !strcmp(key, "cross_kv_fp8_launches") ||
-      !strcmp(key, "beam_cross_shared_launches") || !strcmp(key, "beam_self_tree_launches") || !strcmp(key, "cross_span_launches")) {  // counts: summed over the handle's engines
+      !strcmp(key, "beam_cross_shared_launches") || !strcmp(key, "beam_self_tree_launches") || !strcmp(key, "cross_span_launches") ||
+      !strcmp(key, "encoder_span_passes")) {  // counts: summed over the handle's engines
     long sum = 0;
     for (int i = 0; i < h->group.size(); ++i) {
       Engine& e = h->group.at(i);
@@ -594,6 +595,11 @@ AX_WHISPER_API int AX_WHISPER_CrossSpanAttention(AX_WHISPER_HANDLE handle, int l
 AX_WHISPER_API int AX_WHISPER_GetCrossSpans(AX_WHISPER_HANDLE handle, int* out) {
   if (!handle || !out) return -1;
   return guarded(handle, [&](Engine& e) { e.get_cross_spans(out); });
+}
+
+AX_WHISPER_API int AX_WHISPER_EncoderSpanAttention(AX_WHISPER_HANDLE handle, int n, const float* q, const float* k, const float* v, const int* spans, float* out) {
+  if (!handle || !q || !k || !v || !spans || !out || n < 1) return -1;
+  return guarded(handle, [&](Engine& e) { e.encoder_span_attention(n, q, k, v, spans, out); });
 }
 
 AX_WHISPER_API int AX_WHISPER_ScanStored16(AX_WHISPER_HANDLE handle, int batch, int n_max, char* names, int64_t* nonfinite,

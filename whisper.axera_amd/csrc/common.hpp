@@ -256,6 +256,23 @@ void launch_layernorm_bf16(float* x, const float* g, const float* b, h16* y, lon
 void launch_encoder_attention(const h16* q, const h16* k, const h16* vt, h16* o, int batch, int T, int t_pad,
                               int d_model, int n_head, hipStream_t s, float rescale_thr = 8.f);
 
+// ragged encoder self-attention (encoder_attn_span.hip; AX_WHISPER_CROSS_SPAN=encoder): clip b attends among its first spans[b]
+// frames. The buffers are the ones above, clips `rows` frames apart; rows and columns at or beyond a clip's span are never trusted
+// (they may hold NaN), output rows [span, rows_out) are written as zeros. One workgroup per item of a host-built list.
+struct EncSpanAttnParams {
+  const h16* q; const h16* k; const h16* vt; h16* o;
+  const int* spans;          // device [clips], clamped to 1 .. rows by the kernel
+  const int* chunk;          // device [9]: XCD x takes items [chunk[x], chunk[x + 1])
+  const int* items;          // device: clip << 12 | head << 6 | query block
+  int rows, rows_out;        // frames between clips (n_audio_ctx); output rows per clip the launch writes (>= every span, <= rows)
+  int t_pad, d_model, n_head;
+  float rescale_thr;
+};
+struct EncSpanList { int chunk[9]; std::vector<int> items; int grid; };
+// block_rows: 128 or 64 query rows per workgroup
+EncSpanList build_encoder_span_list(const int* spans, int n, int rows, int n_head, int block_rows);
+void launch_encoder_attention_span(const EncSpanAttnParams& p, int block_rows, int grid, hipStream_t s);
+
 // ------------------------------------------------------------------ front-end
 struct FrontendParams {
   const float* pcm;        // device [batch][stride]
@@ -505,6 +522,7 @@ struct CrossKvQuantParams {
   const int* slot_map;
   int n_layer, n_slots, n_head, clips;
   int n_keys, keys_pad;                    // valid keys (<= keys_pad) and allocated keys (a multiple of 64) per (slot, head)
+  const int* spans;                        // device [clips] or nullptr: clip b has min(spans[b], n_keys) valid keys, scales and codes from those alone
 };
 void launch_cross_kv_quantize(const CrossKvQuantParams& p, hipStream_t s);
 

@@ -37,7 +37,8 @@ __global__ __launch_bounds__(256) void cross_kv_quantize_kernel(CrossKvQuantPara
   const h16* src = (kv ? p.v : p.k) + hidx * layout::kv_head_elems(p.keys_pad);
   unsigned char* dst = (kv ? p.v8 : p.k8) + hidx * layout::kv8_head_bytes(p.keys_pad);
   const int c16 = kv ? tid & 3 : tid >> 6, row = kv ? tid >> 2 : tid & 63;  // K: lane = key; V: four threads per row
-  const int n_keys = min(p.n_keys, p.keys_pad), n_blk = p.keys_pad >> 6, n_blk_valid = (n_keys + 63) >> 6;
+  // spans (a truncated encoder pass; else null): clip b's images hold frames [0, spans[b]) of this pass, older rows behind them
+  const int n_keys = min(p.spans ? max(p.spans[b], 1) : p.n_keys, min(p.n_keys, p.keys_pad)), n_blk = p.keys_pad >> 6, n_blk_valid = (n_keys + 63) >> 6;
   auto load16 = [&](int key, float* x) {  // the 16 values of (key, dims 16 c16 ..)
     const u32x4 lo = *reinterpret_cast<const u32x4*>(src + (kv ? layout::v_index(key, c16 * 16) : layout::k_index(key, c16 * 16)));
     const u32x4 hi = *reinterpret_cast<const u32x4*>(src + (kv ? layout::v_index(key, c16 * 16 + 8) : layout::k_index(key, c16 * 16 + 8)));

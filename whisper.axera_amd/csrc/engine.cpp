@@ -168,7 +168,15 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
   {  // cross-attention over each slot's own audio span (decode_attention_span.hip): opt-in, absent or "full": all n_audio_ctx frames
     const char* e = getenv("AX_WHISPER_CROSS_SPAN");
     if (e && !strcmp(e, "audio")) cross_span_ = true;
-    else if (e && e[0] && strcmp(e, "full")) throw std::runtime_error(std::string("AX_WHISPER_CROSS_SPAN=") + e + ": expected full or audio");
+    else if (e && !strcmp(e, "encoder")) cross_span_ = enc_span_ = true;  // and the encoder over the spans (encoder_attn_span.hip)
+    else if (e && e[0] && strcmp(e, "full")) throw std::runtime_error(std::string("AX_WHISPER_CROSS_SPAN=") + e + ": expected full, audio or encoder");
+    if (enc_span_) {
+      // test and A/B hook: the query-block height of every truncated pass, 64 or 128, instead of Engine::span_block_rows' choice
+      if (const char* t = getenv("AX_WHISPER_ENC_SPAN_ROWS")) enc_span_rows_ = atoi(t) == 64 ? 64 : atoi(t) == 128 ? 128 : 0;
+      for (auto& ev : ev_enc_list_) ev = make_event(hipEventDisableTiming);
+      cfg_.ints["encoder_span_passes"] = 0;
+      cfg_.ints["encoder_span_frames"] = 0;
+    }
     if (const char* m = getenv("AX_WHISPER_CROSS_SPAN_MARGIN")) {
       char* end = nullptr;
       const long v = strtol(m, &end, 10);
@@ -176,7 +184,7 @@ void Engine::construct(const std::string& model_type, const std::string& model_p
       cross_span_margin_ = (int)v;
     }
     if (const char* t = getenv("AX_WHISPER_CROSS_SPAN_PIECES")) cross_span_pieces_ = std::max(1, std::min(layout::kAttnSplitMax, atoi(t)));
-    cfg_.ints["cross_span"] = cross_span_ ? 1 : 0;
+    cfg_.ints["cross_span"] = enc_span_ ? 2 : cross_span_ ? 1 : 0;
     cfg_.ints["cross_span_margin"] = cross_span_margin_;
     cfg_.ints["cross_span_launches"] = 0;
   }
@@ -603,6 +611,14 @@ void Engine::ensure_capacity(int batch) {
     HIP_CHECK(hipMemcpy(d_cross_span_, full.data(), (size_t)B * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(d_cross_span_next_, full.data(), (size_t)B * 4, hipMemcpyHostToDevice));
   }
+  enc_frames_.assign((size_t)B, T);
+  enc_short_ = 0;
+  if (enc_span_) {
+    enc_list_ints_ = (size_t)B + 16 + (size_t)B * cfg_.n_audio_head * ((T + 63) / 64);
+    d_enc_list_ = (int*)A(enc_list_ints_ * 4, true);
+    h_enc_list_ = pinned_array<int>(kAdmitRing * enc_list_ints_);
+    enc_list_seq_ = 0;
+  }
   d_self_k_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
   d_self_v_ = (h16*)A((size_t)L * B * H * layout::kv_head_elems(Tc) * 2, true);
   d_xdec_ = (float*)A((size_t)B * d * 4, true);
@@ -913,30 +929,45 @@ void Engine::build_cblock_fold() {
 }
 
 // ------------------------------------------------------------------------------ encoder
-void Engine::run_encoder(int batch, const int* d_slot_map, const int* d_samples) {
+void Engine::run_encoder(int batch, const int* d_slot_map, const int* d_samples, const int* h_span_samples, const int* h_slots) {
   enqueue_cross_spans(d_samples, batch, d_slot_map);
   const int d = cfg_.n_text_state, nm = cfg_.n_mels, T = cfg_.n_audio_ctx, H = cfg_.n_audio_head, L = cfg_.n_text_layer;
   hipStream_t s = stream();
+  // A truncated pass (DESIGN.md "Encoder spans"): S rows per clip at the buffers' strides, S = the longest span of the pass rounded up
+  // to a GEMM tile; rows [span, S) of a shorter clip are computed and never used. M below is T on every other pass.
+  std::vector<int> spans;
+  int M = T;
+  if (enc_span_ && h_span_samples) {
+    spans.resize((size_t)batch);
+    int longest = 1;
+    for (int b = 0; b < batch; ++b) longest = std::max(longest, spans[b] = cross_span_frames(h_span_samples[b], cross_span_margin_, T));
+    M = std::min(T, (longest + 127) / 128 * 128);
+    ++enc_span_passes_;
+    cfg_.ints["encoder_span_passes"] = (int)enc_span_passes_;
+    cfg_.ints["encoder_span_frames"] = M;
+  }
+  const bool truncated = !spans.empty();
+  note_encoded(batch, h_slots, truncated ? spans.data() : nullptr);
   GemmParams g{};
   // conv1 + GELU (export_onnx.py:158): A row t = mel frames t-1,t,t+1 (time-major, row 0 = zero pad)
   g.A = d_mel_tm_; g.lda = nm; g.a_batch_stride = (long)mel_rows_ * nm;
   g.W = conv1_w_; g.bias = conv1_b_;
   g.C = d_h1_ + d; g.ldc = d; g.c_batch_stride = (long)h1_rows_ * d;  // output row t -> h1 row t+1
-  g.M = kFramesOut; g.N = d; g.K = conv1_k_; g.batch = batch; g.d_model = d; g.epilogue = EPI_BIAS_GELU_BF16;
+  g.M = truncated ? 2 * M : kFramesOut; g.N = d; g.K = conv1_k_; g.batch = batch; g.d_model = d; g.epilogue = EPI_BIAS_GELU_BF16;
   launch_gemm(g, s);
   // conv2 (stride 2) + GELU + positional embedding (export_onnx.py:159-176): A row t = h1 rows 2t-1,2t,2t+1
   g = GemmParams{};
   g.A = d_h1_; g.lda = 2 * d; g.a_batch_stride = (long)h1_rows_ * d;
   g.W = conv2_w_; g.bias = conv2_b_; g.aux = enc_pos_;
   g.C = d_x_; g.ldc = d; g.c_batch_stride = (long)T * d;
-  g.M = T; g.N = d; g.K = 3 * d; g.batch = batch; g.d_model = d; g.epilogue = EPI_GELU_POS_F32;
+  g.M = M; g.N = d; g.K = 3 * d; g.batch = batch; g.d_model = d; g.epilogue = EPI_GELU_POS_F32;
   launch_gemm(g, s);
 
   auto linear = [&](const h16* A, int K, const h16* W, const float* bias, void* C, int N, int epi) {
     GemmParams q{};
     q.A = A; q.lda = K; q.a_batch_stride = (long)T * K;
     q.W = W; q.bias = bias; q.C = C; q.ldc = N; q.c_batch_stride = (long)T * N;
-    q.M = T; q.N = N; q.K = K; q.batch = batch; q.d_model = d; q.epilogue = epi;
+    q.M = M; q.N = N; q.K = K; q.batch = batch; q.d_model = d; q.epilogue = epi;
     launch_gemm(q, s);
   };
   // Residual GEMMs of a one-clip encoder pass have 72 tiles of 128x128 for 256 CUs: split K (2-4 slices along grid.y)
@@ -944,15 +975,16 @@ void Engine::run_encoder(int batch, const int* d_slot_map, const int* d_samples)
   int pend_n = 0;
   const float* pend_bias = nullptr;
   auto resid = [&](const h16* A, int K, const h16* W, const float* bias) {
-    const int tiles = (d / 128) * ((T + 127) / 128) * batch, nk = K / 64;
+    const int tiles = (d / 128) * ((M + 127) / 128) * batch, nk = K / 64;
     int split = 1;
-    if (enc_split_k_ && d % 128 == 0 && batch <= kEncPartClips && tiles * 2 <= 256)
+    // (the partial slabs hold clip b's rows at b * M, the LayerNorm that folds them reads row b * T + t: the same place for one clip or M = T)
+    if (enc_split_k_ && d % 128 == 0 && batch <= kEncPartClips && tiles * 2 <= 256 && (batch == 1 || M == T))
       for (int sp = 4; sp > 1; --sp)
         if (nk % sp == 0 && nk / sp >= 4 && tiles * sp <= 512) { split = sp; break; }
     if (split == 1) { linear(A, K, W, bias, d_x_, d, EPI_RESID_F32); return; }
     GemmParams q{};
     q.A = A; q.lda = K; q.a_batch_stride = (long)T * K;
-    q.W = W; q.M = T; q.N = d; q.K = K; q.batch = batch; q.d_model = d; q.epilogue = EPI_PARTIAL_F32;
+    q.W = W; q.M = M; q.N = d; q.K = K; q.batch = batch; q.d_model = d; q.epilogue = EPI_PARTIAL_F32;
     q.ksplit = split; q.part = d_enc_part_; q.part_stride = (long)kEncPartClips * T * d;
     launch_gemm(q, s);
     pend_n = split;
@@ -971,8 +1003,8 @@ void Engine::run_encoder(int batch, const int* d_slot_map, const int* d_samples)
     q.C = d_q_; q.c_batch_stride = (long)T * d;
     q.C2 = d_k_; q.c2_batch_stride = (long)T * d;
     q.C3 = d_vt_; q.c3_batch_stride = (long)d * t_pad_;
-    q.M = T; q.N = 3 * d; q.K = d; q.batch = batch; q.d_model = d; q.t_pad = t_pad_; q.epilogue = EPI_QKV;
-    if (enc_split_k_ && (3 * d / 128) * ((T + 127) / 128) * batch <= 256) {
+    q.M = M; q.N = 3 * d; q.K = d; q.batch = batch; q.d_model = d; q.t_pad = t_pad_; q.epilogue = EPI_QKV;
+    if (enc_split_k_ && (3 * d / 128) * ((M + 127) / 128) * batch <= 256) {
       // few tiles (one clip: 144 + 72): the Q,K launch and the V launch (swapped operands) run side by side
       HIP_CHECK(hipEventRecord(ev_fork_, s));
       HIP_CHECK(hipStreamWaitEvent(branch_stream_[0], ev_fork_, 0));
@@ -985,7 +1017,8 @@ void Engine::run_encoder(int batch, const int* d_slot_map, const int* d_samples)
     } else {
       launch_gemm(q, s);
     }
-    launch_encoder_attention(d_q_, d_k_, d_vt_, d_attn_, batch, T, t_pad_, d, H, s, enc_rescale_thr_);
+    if (truncated) enqueue_encoder_span_attention(batch, l == 0 ? spans.data() : nullptr, M, s);  // (the list of the pass: uploaded once)
+    else launch_encoder_attention(d_q_, d_k_, d_vt_, d_attn_, batch, T, t_pad_, d, H, s, enc_rescale_thr_);
     resid(d_attn_, d, e.w_o, e.b_o);
     layernorm(e.ln2_w, e.ln2_b);
     linear(d_ln_, d, e.w_fc1, e.b_fc1, d_ffn_, 4 * d, EPI_BIAS_GELU_BF16);
@@ -998,20 +1031,103 @@ void Engine::run_encoder(int batch, const int* d_slot_map, const int* d_samples)
   c.W = w_cross_kv_; c.bias = b_cross_kv_;
   c.C = d_cross_k_; c.C2 = d_cross_v_;
   c.kv_slot_map = d_slot_map;  // an admission pass (stream_admit) scatters its clips into whichever slots are idle
-  c.M = T; c.N = 2 * L * d; c.K = d; c.batch = batch; c.d_model = d; c.t_pad = t_pad_;
+  c.M = M; c.N = 2 * L * d; c.K = d; c.batch = batch; c.d_model = d; c.t_pad = t_pad_;
   c.n_batch_total = cap_; c.n_layer = L; c.epilogue = EPI_CROSS_KV;
   launch_gemm(c, s);
-  if (cross_fp8_) enqueue_cross_kv_quantize(batch, d_slot_map, s);
+  if (cross_fp8_) enqueue_cross_kv_quantize(batch, d_slot_map, s, truncated ? d_enc_list_ : nullptr);
 }
 
 // FP8 cross K/V: codes and scales of `clips` clips' slots from the h16 images the epilogue above left (which stay)
-void Engine::enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s) {
+void Engine::enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s, const int* d_spans) {
   CrossKvQuantParams q{};
+  q.spans = d_spans;
   q.k = d_cross_k_; q.v = d_cross_v_; q.k8 = d_cross_k8_; q.v8 = d_cross_v8_; q.scales = d_cross_scales_;
   q.slot_map = d_slot_map;
   q.n_layer = cfg_.n_text_layer; q.n_slots = cap_; q.n_head = cfg_.n_text_head; q.clips = clips;
   q.n_keys = cfg_.n_audio_ctx; q.keys_pad = t_pad_;
   launch_cross_kv_quantize(q, s);
+}
+
+// ------------------------------------------------------------------------------ encoder spans
+void Engine::note_encoded(int batch, const int* h_slots, const int* spans) {
+  const int T = cfg_.n_audio_ctx;
+  for (int b = 0; b < batch; ++b) {
+    const int slot = h_slots ? h_slots[b] : b;
+    if (slot < 0 || slot >= cap_) continue;
+    const int now = spans ? spans[b] : T;
+    enc_short_ += (now < T) - (enc_frames_[(size_t)slot] < T);
+    enc_frames_[(size_t)slot] = now;
+  }
+}
+
+void Engine::require_full_frames(int b0, int n, const char* who) const {
+  if (enc_short_ == 0) return;
+  for (int b = std::max(b0, 0); b < std::min(b0 + n, cap_); ++b)
+    if (enc_frames_[(size_t)b] < cfg_.n_audio_ctx)
+      throw std::runtime_error(std::string(who) + ": slot " + std::to_string(b) + " holds " + std::to_string(enc_frames_[(size_t)b]) + " of " +
+                               std::to_string(cfg_.n_audio_ctx) + " encoder frames (its last pass ran under AX_WHISPER_CROSS_SPAN=encoder) and this reader takes them all: encode the clip again through this call's own entry point");
+}
+
+// The ragged self-attention over d_q_ / d_k_ / d_vt_ -> d_attn_ for `batch` clips. spans (host) non-null: build the pass's work list
+// and copy it, with the spans, to d_enc_list_ through the pinned ring; null: the list the stream already carries (the next layer).
+// Selection of the block height: Engine::span_block_rows (64 rows while 128-row items would not fill two workgroups per CU).
+void Engine::enqueue_encoder_span_attention(int batch, const int* spans, int rows_out, hipStream_t s) {
+  const int T = cfg_.n_audio_ctx, H = cfg_.n_audio_head;
+  int& rows = enc_list_rows_;
+  int& grid = enc_list_grid_;
+  if (spans) {
+    long items128 = 0;
+    for (int b = 0; b < batch; ++b) items128 += (long)H * ((std::min(std::max(spans[b], 1), T) + 127) / 128);
+    rows = span_block_rows(items128);
+    const EncSpanList list = build_encoder_span_list(spans, batch, T, H, rows);
+    if ((size_t)cap_ + 9 + list.items.size() > enc_list_ints_) throw std::runtime_error("encoder span attention: work list larger than its buffer");
+    const int ring = (int)(enc_list_seq_ % kAdmitRing);
+    if (enc_list_seq_ >= kAdmitRing) HIP_CHECK(hipEventSynchronize(ev_enc_list_[ring]));  // the copy of kAdmitRing passes ago: long done
+    int* h = h_enc_list_ + (size_t)ring * enc_list_ints_;
+    memcpy(h, spans, (size_t)batch * 4);
+    memcpy(h + cap_, list.chunk, 9 * 4);
+    memcpy(h + cap_ + 9, list.items.data(), list.items.size() * 4);
+    HIP_CHECK(hipMemcpyAsync(d_enc_list_, h, ((size_t)cap_ + 9 + list.items.size()) * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipEventRecord(ev_enc_list_[ring], s));
+    ++enc_list_seq_;
+    grid = list.grid;
+  }
+  EncSpanAttnParams p{};
+  p.q = d_q_; p.k = d_k_; p.vt = d_vt_; p.o = d_attn_;
+  p.spans = d_enc_list_; p.chunk = d_enc_list_ + cap_; p.items = d_enc_list_ + cap_ + 9;
+  p.rows = T; p.rows_out = rows_out; p.t_pad = t_pad_; p.d_model = cfg_.n_text_state; p.n_head = H; p.rescale_thr = enc_rescale_thr_;
+  launch_encoder_attention_span(p, rows, grid, s);
+}
+
+// Stage level: the list and the kernel alone. q, k -> d_q_, d_k_ narrowed; v -> d_vt_ in the stored frame order (gemm.hip, EPI_QKV),
+// the 36 padding columns and whatever else the caller did not give filled with NaN patterns first.
+void Engine::encoder_span_attention(int n, const float* q, const float* k, const float* v, const int* spans, float* out) {
+  if (!enc_span_) throw std::runtime_error("encoder_span_attention: the handle was not made under AX_WHISPER_CROSS_SPAN=encoder");
+  require_no_stream("encoder_span_attention");
+  std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
+  HIP_CHECK(hipSetDevice(device_));
+  ensure_capacity(n);
+  const int T = cfg_.n_audio_ctx, d = cfg_.n_text_state;
+  hipStream_t s = stream();
+  HIP_CHECK(hipStreamSynchronize(s));
+  const size_t rows = (size_t)n * T;
+  std::vector<uint16_t> hq(rows * d), hk(rows * d), hv((size_t)n * d * t_pad_, (uint16_t)0xffff);
+  for (size_t i = 0; i < rows * d; ++i) { hq[i] = float_to_h16_bits(q[i]); hk[i] = float_to_h16_bits(k[i]); }
+  for (int b = 0; b < n; ++b)
+    for (int t = 0; t < T; ++t) {
+      const int pos = (t & ~15) | ((t & 4) << 1) | ((t & 8) >> 1) | (t & 3);  // frames of a 16-group: [0-3, 8-11, 4-7, 12-15]
+      for (int c = 0; c < d; ++c) hv[((size_t)b * d + c) * t_pad_ + pos] = float_to_h16_bits(v[((size_t)b * T + t) * d + c]);
+    }
+  HIP_CHECK(hipMemcpy(d_q_, hq.data(), hq.size() * 2, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_k_, hk.data(), hk.size() * 2, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_vt_, hv.data(), hv.size() * 2, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_attn_, 0xff, rows * d * 2));
+  enqueue_encoder_span_attention(n, spans, T, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipMemcpy(hq.data(), d_attn_, rows * d * 2, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < rows * d; ++i) out[i] = h16_bits_to_float(hq[i]);
+  HIP_CHECK(hipMemset(d_vt_, 0, hv.size() * 2));  // the padding columns as ensure_capacity left them: the full kernel multiplies them by p = 0
 }
 
 // ------------------------------------------------------------------------------ cross-attention spans
@@ -1085,6 +1201,7 @@ void Engine::cross_span_attention(int layer, int n, const float* q, const int* s
 void Engine::cross_kv_quantize() {
   if (!cross_fp8_) throw std::runtime_error("cross_kv_quantize: the handle was not made under AX_WHISPER_CROSS_KV=fp8");
   require_no_stream("cross_kv_quantize");
+  require_full_frames(0, cap_, "cross_kv_quantize");
   HIP_CHECK(hipSetDevice(device_));
   enqueue_cross_kv_quantize(cap_, nullptr, stream());
   HIP_CHECK(hipStreamSynchronize(stream()));
@@ -1109,8 +1226,8 @@ void Engine::run_tokens(const DecodeRequest& rq, const float* const* pcm, const 
   if (rq.sample) upload_sample(*rq.sample, batch);
   hipStream_t s = stream();
   HIP_CHECK(hipEventRecord(ev_[0], s));
+  std::vector<int> n16(n_samples, n_samples + batch);  // the clips' lengths at 16 kHz: their own without rates
   if (pcm) {
-    std::vector<int> n16(batch);  // the clips' lengths at 16 kHz: their own without rates
     upload_pcm(pcm, n_samples, batch, rq.sample_rate, n16.data());
     run_frontend(d_pcm_, (int)pcm_stride_, n16.data(), batch, false, true);
   } else {
@@ -1118,7 +1235,9 @@ void Engine::run_tokens(const DecodeRequest& rq, const float* const* pcm, const 
     run_frontend(d_pcm, d_stride, n_samples, batch, false);
   }
   HIP_CHECK(hipEventRecord(ev_[1], s));
-  run_encoder(batch, nullptr, d_nsamp_);  // (the front-end left the clips' 16 kHz lengths there)
+  // (the front-end left the clips' 16 kHz lengths in d_nsamp_; on the host too when the greedy loop below will read the cross K/V
+  // through span kernels alone: the pass then stops at the clips' spans)
+  run_encoder(batch, nullptr, d_nsamp_, encoder_span_ok(batch, rq.ctx.any()) ? n16.data() : nullptr);
   HIP_CHECK(hipEventRecord(ev_[2], s));
   const int steps = greedy_loop(step_spec(mode), batch, rq.max_new, rq.max_new_clip, rq.ctx);
   fetch_ids(batch, ids, n_ids);
@@ -1218,7 +1337,8 @@ void Engine::get_cross_kv(int slot, float* k_out, float* v_out) {
         for (int c = 0; c < 64; ++c) {
           const uint16_t kbits = hk[h * head + layout::k_index(t, c)];
           const uint16_t vbits = hv[h * head + layout::v_index(t, c)];
-          const float kf = h16_bits_to_float(kbits), vf = h16_bits_to_float(vbits);
+          const bool enc = t < enc_frames_[(size_t)slot];  // behind a truncated pass's frames: rows of an earlier clip, returned as zeros
+          const float kf = enc ? h16_bits_to_float(kbits) : 0.f, vf = enc ? h16_bits_to_float(vbits) : 0.f;
           k_out[((size_t)l * T + t) * d + h * 64 + c] = kf;
           v_out[((size_t)l * T + t) * d + h * 64 + c] = vf;
         }

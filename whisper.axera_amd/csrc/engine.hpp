@@ -272,7 +272,11 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
                     int* pinned_ns = nullptr);
   // cross K/V of clip b goes to slot d_slot_map[b] (device), else b; d_samples (device, or null: unknown): the clips' sample counts
   // at 16 kHz, from which a span handle takes the slots' spans
-  void run_encoder(int batch, const int* d_slot_map = nullptr, const int* d_samples = nullptr);
+  // h_span_samples (host [batch], or null): the same counts on the host, given only when encoder_span_ok() said that every reader of
+  // this pass's cross K/V is a span kernel: the pass is then truncated to the clips' spans (DESIGN.md "Encoder spans"); h_slots (host,
+  // or null: b): the slot map again, for the record of frames encoded per slot
+  void run_encoder(int batch, const int* d_slot_map = nullptr, const int* d_samples = nullptr, const int* h_span_samples = nullptr,
+                   const int* h_slots = nullptr);
   void reset_decode_state(int batch, const int* max_new_clip = nullptr);
   // What one decoder step is built as: every step sequence, the graph it is captured into and the key that graph is cached
   // under are made from ONE of these, handed down as an argument.
@@ -584,7 +588,33 @@ class Engine final : public IEngine, private EngineStreams, private EngineEvents
   void launch_cross_attention_span(const DecAttnParams& a, bool fp8, int l, int b0, hipStream_t s);
   void cross_span_attention(int layer, int n, const float* q, const int* spans, float* out) override;
   void get_cross_spans(int* out) override;
-  void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s);
+  // Encoder over each clip's own span (AX_WHISPER_CROSS_SPAN=encoder; encoder_attn_span.hip, DESIGN.md "Encoder spans"): a span handle
+  // whose encoder passes compute frames [0, span) of a clip when nothing but span kernels will read its cross K/V.
+  bool enc_span_ = false;
+  int enc_span_rows_ = 0;          // AX_WHISPER_ENC_SPAN_ROWS (A/B, tests): 64 or 128 query rows per workgroup; 0: span_block_rows()
+  long enc_span_passes_ = 0;
+  std::vector<int> enc_frames_;    // [cap]: frames the slot's cross K/V holds since its last encoder pass (n_audio_ctx: all)
+  int enc_short_ = 0;              // slots with fewer than n_audio_ctx
+  // the work list of a pass: device [cap spans | 9 chunk bounds | items], filled from a pinned ring in stream order (an entry is
+  // reused once the copy out of it has run: no pass waits for another's encoder)
+  int* d_enc_list_ = nullptr; PinnedArray<int> h_enc_list_; size_t enc_list_ints_ = 0; long enc_list_seq_ = 0;
+  Event ev_enc_list_[kAdmitRing];
+  int enc_list_rows_ = 128, enc_list_grid_ = 0;  // block height and grid of the list d_enc_list_ holds
+  // THE predicate: may the encoder pass in front of a decode of `slots` slots be truncated? Only if every cross K/V reader of the call
+  // is a span kernel: a batched step (more slots than the GEMV family and the persistent launches take) with no prefill, alignment,
+  // detection or beam search (`other_readers`).
+  bool encoder_span_ok(int slots, bool other_readers) const {
+    return enc_span_ && !other_readers && slots > std::max(gemv_max_, std::max(2, persist_max_clips_));
+  }
+  // 64-row blocks when 128-row blocks would leave workgroup slots of the machine empty (two workgroups per CU); a first guess
+  int span_block_rows(long items128) const { return enc_span_rows_ ? enc_span_rows_ : items128 < 2L * n_cu_ ? 64 : 128; }
+  // a reader that streams all n_audio_ctx frames of slots [b0, b0 + n): refuses a slot whose last pass was truncated
+  void require_full_frames(int b0, int n, const char* who) const;
+  void note_encoded(int batch, const int* h_slots, const int* spans);  // spans null: n_audio_ctx
+  // launch over the encoder's q/k/v^T/attn buffers, clips' spans from the host; returns nothing the host waits for
+  void enqueue_encoder_span_attention(int batch, const int* spans, int rows_out, hipStream_t s);
+  void encoder_span_attention(int n, const float* q, const float* k, const float* v, const int* spans, float* out) override;
+  void enqueue_cross_kv_quantize(int clips, const int* d_slot_map, hipStream_t s, const int* d_spans = nullptr);  // d_spans: a truncated pass's [clips]
   // the fp8 cross-attention launch of layer l for clips [b0, b0 + nb) with a's query mode, splits and outputs
   void launch_cross_attention_fp8(const DecAttnParams& a, int l, int b0, hipStream_t s);
   // The cross-attention launch `a` describes for layer l, slots [b0, b0 + a.batch): grouped where the step asks for it (over the FP8

@@ -24,21 +24,6 @@ namespace {
 constexpr size_t kAlignScratchBytes = (size_t)256 << 20;  // the P scratch of one chunk of clips stays under this
 constexpr int kAlignLogitRows = 64;                       // rows per round of the token-probability logits
 constexpr int kAlignChunkRows = 4096;                     // context rows of one chunk: bounds the prefill pass's scratch, which the engine keeps
-
-// narrowing on the host, round to nearest even, as the device's conversions
-uint16_t float_to_h16_bits(float f) {
-#if AXW_F16
-  const _Float16 h = (_Float16)f;
-  uint16_t b;
-  memcpy(&b, &h, 2);
-  return b;
-#else
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1)) >> 16);
-#endif
-}
 }  // namespace
 
 std::vector<std::pair<int, int>> Engine::alignment_heads() const {
@@ -155,6 +140,7 @@ void Engine::align_tokens(const AlignRequest& rq) {
   require_timestamp_vocab();
   const int batch = rq.batch, Tc = cfg_.n_text_ctx, d = cfg_.n_text_state, n_lang = (int)cfg_.lang_tokens.size();
   if (batch < 1 || batch > cap_) throw std::runtime_error("align_tokens: batch exceeds the encoded slots");
+  require_full_frames(0, batch, "align_tokens");
   if (!rq.ids || rq.stride < 1 || !rq.n_ids || !rq.num_frames || !rq.jump || !rq.token_logprob)
     throw std::runtime_error("align_tokens: bad arguments");
   if (!prefill_supported()) throw std::runtime_error("align_tokens: the prefill kernels do not take this decoder shape");

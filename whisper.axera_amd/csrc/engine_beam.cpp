@@ -117,6 +117,7 @@ void Engine::beam_spread_cross(int clips, int K) {
   const long slot_elems = cfg_.n_text_head * layout::kv_head_elems(t_pad_);
   for (int c = clips - 1; c >= 0; --c)
     launch_beam_spread_cross(d_cross_k_, d_cross_v_, (long)cap_ * slot_elems, slot_elems, cfg_.n_text_layer, c, c * K, K, stream());
+  note_encoded(clips * K, nullptr, nullptr);  // the destination slots hold copies of whole clips (beam_loop refused anything else)
 }
 
 // The loop over the encoded clips in slots 0 .. clips - 1. Returns the decoder steps run.
@@ -124,6 +125,8 @@ int Engine::beam_loop(int clips, int K, int max_new, const BeamResult& out, floa
   const int Tc = cfg_.n_text_ctx, nv = cfg_.n_vocab, slots = clips * K;
   if (max_new <= 0 || max_new > Tc - 3) max_new = Tc - 3;
   hipStream_t s = stream();
+  // every cross-attention form of beam search, and the spread below, reads all frames of the clips' slots
+  require_full_frames(0, clips, "beam search");
   // layers + the logits dump from offset 0 on; asked for BEFORE the decode state is set up (step_graph)
   // shared cross K/V (AX_WHISPER_BEAM_CROSS=shared): the step's cross-attention reads clip c's K/V where the encoder put it, slot c,
   // for all K ranks, and nothing is spread (on an FP8 handle too: the step then reads slot c's codes, which the encoder pass left

@@ -448,8 +448,23 @@ float Engine::bench_attn_stamp(int batch, int arg, int iters) {
 }
 
 float Engine::bench_encoder(int batch, int iters) {
-  run_encoder(batch);
-  return timed_ms(stream(), [&] { for (int i = 0; i < iters; ++i) run_encoder(batch); });
+  // an encoder-span handle under AX_WHISPER_BENCH_CROSS_SPAN=<frames> | mixed (as bench_decode_step reads it): truncated passes over
+  // clips of those spans (sample counts that give them: no span below the handle's margin); else the full pass
+  std::vector<int> ns;
+  if (const char* e = enc_span_ ? getenv("AX_WHISPER_BENCH_CROSS_SPAN") : nullptr) {
+    unsigned long long x = 0x9E3779B97F4A7C15ull;
+    for (int b = 0; b < batch; ++b) {
+      x = x * 6364136223846793005ull + 1442695040888963407ull;
+      const int span = !strcmp(e, "mixed") ? 150 + (int)((x >> 33) % (unsigned long long)std::max(1, cfg_.n_audio_ctx - 149))
+                                           : std::max(1, std::min(cfg_.n_audio_ctx, atoi(e)));
+      ns.push_back(std::max(0, span - cross_span_margin_) * 320);
+    }
+  }
+  const int* h = ns.empty() ? nullptr : ns.data();
+  if (h) upload_cross_spans(h, batch);  // the decoder's spans follow the same counts
+  const int* dn = h ? d_span_samples_ : nullptr;
+  run_encoder(batch, nullptr, dn, h);
+  return timed_ms(stream(), [&] { for (int i = 0; i < iters; ++i) run_encoder(batch, nullptr, dn, h); });
 }
 
 // the quantise kernel alone over `batch` slots' h16 cross K/V as it stands (an fp8 handle only)

@@ -49,6 +49,7 @@ void Engine::enqueue_decode_step(const StepSpec& spec, int batch, int max_new, c
     return;
   }
 
+  require_full_frames(0, batch, "a decoder step of one or two slots");
   // the VALU GEMV handles <= 4 clips per launch; tile the batch (gemv_max_ <= 4: one tile)
   auto gemv = [&](GemvParams p, auto&& offset) {
     for (int b0 = 0; b0 < batch; b0 += 4) {
@@ -735,6 +736,8 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
   // (asked ONCE per request: persistent_usable() counts a back-off down)
   // (timestamp and scored mode: one clip through the one-clip launch's rules instantiation, DESIGN.md §11 — one clip, 440 ids,
   // Whisper-small dims: profiles/persist_ts_bench.txt; everything else under the rules takes the launch-per-phase step)
+  // (an encoder-span handle: the pass in front was truncated only under this very condition, Engine::encoder_span_ok)
+  if (!(spec.cross_span && !spec.cross_group && encoder_span_ok(batch, ctx.any()))) require_full_frames(0, batch, "a decode with a reader of all encoder frames");
   const bool usable = spec.mode == kDecodePlain && batch <= std::max(2, persist_max_clips_) && persistent_usable();
   if (!spec.slots && !spec.feed && persistent_ts_route(spec.mode, batch, ctx)) {
     int mn = max_new;
@@ -789,6 +792,7 @@ int Engine::greedy_loop(const StepSpec& spec, int batch, int max_new, const int*
 int Engine::run_persistent(int max_new, const int* d_forced, int n_forced, float* d_logits, int* d_argmax, int slot, int max_new1, int max_new2,
                            DecodeMode mode, const TsScoreParams* scores, float* d_logits0) {
   const bool rules = mode != kDecodePlain, scored = mode == kDecodeScored;
+  require_full_frames(slot, 1 + (max_new1 >= 0) + (max_new2 >= 0), "the persistent decode");
   if (rules) {  // the launch's rules instantiation: one clip, timestamp or scored mode
     if (mode > kDecodeScored || max_new1 >= 0 || slot != 0 || !persistent_ts_) throw std::runtime_error("run_persistent: no rules launch for this request");
     require_timestamp_vocab();

@@ -90,6 +90,21 @@ inline float h16_bits_to_float(uint16_t bits) {
 #endif
 }
 
+// narrowing on the host, round to nearest even, as the device's conversions
+inline uint16_t float_to_h16_bits(float f) {
+#if AXW_F16
+  const _Float16 h = (_Float16)f;
+  uint16_t b;
+  memcpy(&b, &h, 2);
+  return b;
+#else
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1)) >> 16);
+#endif
+}
+
 // `slot` holds `value` until the guard leaves scope, then what it held before (a bench hook's route for its call: Engine::prefill_force_)
 template <class T> class ScopedSet {
  public:

@@ -160,6 +160,7 @@ void Engine::prefill_prompts(int batch, const ClipContexts& ctx, bool force_cont
   for (int b = 0; lout.detected && b < batch; ++b) lout.detected[b] = pl.lang_index[b];
   const int n = pl.clips(), nd = (int)pl.detect.size();
   if (n == 0) return;
+  for (int sl : pl.slot) require_full_frames(sl, 1, "prompt prefill");
   const int route = prefill_route();
   if (want_no_speech) { require_scored_vocab(); ensure_ts_logits(); ensure_ts_scores(); }
   const int d = cfg_.n_text_state;
@@ -507,6 +508,7 @@ void Engine::detect_language_stage(int batch, const LangResult& out) {
   std::lock_guard<std::recursive_mutex> capture_lock(device_capture_mutex(device_));
   HIP_CHECK(hipSetDevice(device_));
   if (batch < 1 || batch > cap_) throw std::runtime_error("detect_language: batch exceeds the encoded slots");
+  require_full_frames(0, batch, "detect_language");
   const int nl = (int)cfg_.lang_tokens.size();
   reset_decode_state(batch);
   std::vector<int> slot(batch), idx(batch);

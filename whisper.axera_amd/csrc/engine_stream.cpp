@@ -153,7 +153,9 @@ void Engine::stream_admit(const int* slots, const float* const* pcm, const int* 
   upload_pcm(pcm, n_samples, count, rates, n16.data());  // (with rates: uploads, then the resample kernel)
   HIP_CHECK(hipEventRecord(ev_upload_, admit_stream_));
   run_frontend(d_pcm_, (int)pcm_stride_, n16.data(), count, false, true, h_ns);
-  run_encoder(count, d_slot_map_, d_nsamp_);
+  // (a plain-mode stream reads cross K/V through the span kernels of its batched step alone; the timestamp mode's contexts and
+  // detection read every frame)
+  run_encoder(count, d_slot_map_, d_nsamp_, encoder_span_ok(stream_slots_, stream_mode_ != 0) ? n16.data() : nullptr, slots);
   HIP_CHECK(hipEventRecord(ev_ring_[ring], admit_stream_));
   ++admit_seq_;
   for (int i = 0; i < count; ++i) {

@@ -111,6 +111,9 @@ class IEngine {
   // from a buffer: q, out fp32 [n][d], spans [n] in keys. get_cross_spans: the spans the decoder steps read, out [capacity].
   virtual void cross_span_attention(int layer, int n, const float* q, const int* spans, float* out) = 0;
   virtual void get_cross_spans(int* out) = 0;
+  // the ragged encoder self-attention alone (a handle made under AX_WHISPER_CROSS_SPAN=encoder; throws on another): q, k, v, out fp32
+  // [n][n_audio_ctx][64 n_audio_head], clip b over its first spans[b] frames; out rows >= spans[b] are zero
+  virtual void encoder_span_attention(int n, const float* q, const float* k, const float* v, const int* spans, float* out) = 0;
   // the slot's self-attention cache rows [0, n_rows), de-blocked: k_out, v_out fp32 [n_text_layer][n_rows][d]
   virtual void get_self_kv(int slot, int n_rows, float* k_out, float* v_out) = 0;
   // the self-attention cache of clip `clip` (1 or 2: its position in the last multi-clip persistent launch), all 8 blocks x 64 keys

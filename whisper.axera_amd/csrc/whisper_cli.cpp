@@ -60,9 +60,11 @@ static void usage(const char* prog) {
           "      --task T        transcribe or translate (with --timestamps or --long, not with --beam_size) [=transcribe]\n"
           "      --cross_kv h16|fp8   fp8: keep the cross K/V as e4m3fn codes too; decoder steps of more than two clips read them\n"
           "                      (opt-in, results differ from h16; under --beam_size only with --beam_cross shared)\n"
-          "      --cross_span full|audio   audio: decoder steps of more than two clips attend only over each clip's own audio span,\n"
+          "      --cross_span full|audio|encoder   audio: decoder steps of more than two clips attend only over each clip's own audio span,\n"
           "                      ceil(samples / 320) + AX_WHISPER_CROSS_SPAN_MARGIN (default 100) encoder frames (opt-in; the effect on a\n"
           "                      trained model's transcripts is unmeasured; beam search reads all 1500 frames)\n"
+          "                      encoder: audio, and an encoder pass that only such steps will read computes each clip's span of\n"
+          "                      frames alone (opt-in; an approximation of the model, its effect on transcripts is unmeasured)\n"
           "      --beam_cross copy|shared   shared: the hypotheses of a clip under --beam_size read one cross K/V copy, the clip's own\n"
           "                      (opt-in; a beam's logits differ from the copy path in their last bits; with --cross_kv fp8 the copy is\n"
           "                      read as its FP8 codes)\n"
@@ -464,7 +466,7 @@ int main(int argc, char** argv) {
   if (wav.empty()) { fprintf(stderr, "need option: --wav\n"); usage(argv[0]); return 1; }
   // --cross_kv h16 | fp8: the library reads the mode from AX_WHISPER_CROSS_KV when the handle is made (a bad value fails Init)
   if (!cross_kv_arg.empty()) setenv("AX_WHISPER_CROSS_KV", cross_kv_arg.c_str(), 1);
-  // --cross_span full | audio: likewise, from AX_WHISPER_CROSS_SPAN
+  // --cross_span full | audio | encoder: likewise, from AX_WHISPER_CROSS_SPAN
   if (!cross_span_arg.empty()) setenv("AX_WHISPER_CROSS_SPAN", cross_span_arg.c_str(), 1);
   // --beam_cross copy | shared: likewise, from AX_WHISPER_BEAM_CROSS
   if (!beam_cross_arg.empty()) setenv("AX_WHISPER_BEAM_CROSS", beam_cross_arg.c_str(), 1);

@@ -461,7 +461,7 @@ int main(int argc, char** argv) {
     if (val("max_body_mb", nullptr, v)) { max_body_mb = std::max(1, atoi(v.c_str())); continue; }
     if (val("recv_timeout_s", nullptr, v)) { g_recv_timeout_s = std::max(1, atoi(v.c_str())); continue; }
     fprintf(stderr, "usage: %s [--port 8080] [-t model_type] [-p model_path] [-l language] [--max_batch 64] [--batch_wait_ms 5] [--devices all|0,1,..]\n"
-                    "          [--scheduler slots|batches] [--timestamps] [--cross_kv h16|fp8] [--cross_span full|audio] [--suppress_tokens -1|1,2,3] [--repetition_penalty 1.0] [--no_repeat_ngram_size 0] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
+                    "          [--scheduler slots|batches] [--timestamps] [--cross_kv h16|fp8] [--cross_span full|audio|encoder] [--suppress_tokens -1|1,2,3] [--repetition_penalty 1.0] [--no_repeat_ngram_size 0] [--steps_per_call 8] [--min_admit 1] [--admit_wait_ms 20] [--max_conns 256] [--max_body_mb 16] [--recv_timeout_s 10]\n", argv[0]);
     return a == "--help" || a == "-?" ? 0 : 1;
   }
   printf("port: %d\n", port);
@@ -470,7 +470,7 @@ int main(int argc, char** argv) {
   printf("language: %s\n", language.c_str());
   // --cross_kv h16 | fp8: the library reads the mode from AX_WHISPER_CROSS_KV when a handle is made (a bad value fails Init)
   if (!cross_kv_arg.empty()) { setenv("AX_WHISPER_CROSS_KV", cross_kv_arg.c_str(), 1); printf("cross_kv: %s\n", cross_kv_arg.c_str()); }
-  // --cross_span full | audio: likewise, from AX_WHISPER_CROSS_SPAN (opt-in: decoder steps read only each clip's own audio span)
+  // --cross_span full | audio | encoder: likewise, from AX_WHISPER_CROSS_SPAN (opt-in: decoder steps read only each clip's own audio span)
   if (!cross_span_arg.empty()) { setenv("AX_WHISPER_CROSS_SPAN", cross_span_arg.c_str(), 1); printf("cross_span: %s\n", cross_span_arg.c_str()); }
   if (timestamps && scheduler == "batches") { printf("--timestamps needs --scheduler slots (micro-batches decode in plain mode)\n"); return 1; }
   // --suppress_tokens -1 | 1,2,3 (with --timestamps: plain mode is not filtered; suppress_flag.hpp)
